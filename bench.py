@@ -3,7 +3,7 @@
 the 3-D SIMPLE Stokes system (BASELINE.json configs[3]: MAC grid n=136, ~1e7 DoF, fp64),
 plus the HBM roofline of its dominant kernel and the CPU oracle timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one BPCG iteration (reference loop body: solvers/bramblepasciak_new.py:200-249):
 3 CSR SpMVs (B^T, A, B), the block-Jacobi preconditioner apply, the lumped-mass apply, two
@@ -61,8 +61,9 @@ def parse_args():
     ap.add_argument("--cpu-iters", type=int, default=-1, help="oracle iterations to time (-1: auto, 0: skip)")
     ap.add_argument("--kernel-reps", type=int, default=30)
     ap.add_argument("--windows", type=int, default=5,
-                    help="consecutive timed windows of --steps iterations each; `value` is their median "
-                         "(a single ~0.1-s window cannot separate a 3 %% change from noise), all reported as window_values")
+                    help="the --steps timed iterations are split into this many consecutive windows of near-equal length; "
+                         "`value` is the median of their rates (one window cannot separate a 3 %% change from noise), "
+                         "all reported as window_values")
     ap.add_argument("--mypre-a", dest="mypre_a", type=int, default=1,
                     help="1: also run the reference's default preconditioner MypreA(GS=True) with the auxiliary-space term on "
                          "the headline system (`roofline_mypre_a_gs`); 0 skips it")
@@ -72,7 +73,39 @@ def parse_args():
     ap.add_argument("--hdg", type=int, default=36,
                     help="grid of the secondary HDG-like measurement (facet blocks of 12 dofs, ~84 non-zeros per "
                          "row: the reference's row regime, SURVEY.md A7); 0 skips it")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed loop computed in its last step -- the solution "
+                         "(velocity, pressure) and the error history a caller of BramblePasciakCG receives -- as "
+                         "DIR/<name>.npy in float64 (single GPU only)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def window_bounds(steps, windows):
+    """[begin, end) offsets of min(windows, steps) consecutive windows of near-equal length covering `steps` steps."""
+    n = max(1, min(windows, steps))
+    edges = [steps * w // n for w in range(n + 1)]
+    return list(zip(edges[:-1], edges[1:]))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """Write each array of `arrays` (name -> 1-D array) as <directory>/<name>.npy in float64, at most
+    DUMP_BUDGET_BYTES in all.  An array longer than its share of the budget is replaced by a fixed sample: the sorted
+    indices drawn by default_rng(seed) depend on the array's length only, so two runs with the same arguments write
+    the same entries."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    cap = (DUMP_BUDGET_BYTES // len(arrays) - 4096) // 8          # (4 KiB per file for the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def hdg_like_roofline(torch, eng, grid, reps=40):
@@ -460,6 +493,8 @@ def main():
             agree = torch.tensor([float(tier_level)], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
             dist.all_reduce(agree, op=dist.ReduceOp.MIN)
             tier_level = int(agree.item())
+    if partitioned and args.dump_outputs:
+        raise SystemExit("--dump-outputs: single GPU only")
     if args.gpus != world and rank == 0:
         print("note: --gpus %d but WORLD_SIZE %d; using WORLD_SIZE" % (args.gpus, world), file=sys.stderr)
 
@@ -472,8 +507,9 @@ def main():
     info = eng.device_info()
     quiet = contextlib.redirect_stdout(sys.stderr)      # stdout carries the ONE JSON line only
     K, W = args.steps, args.warmup
-    NWIN = max(1, args.windows)          # consecutive timed windows of exactly K steps each; value = their median
-    total_its = W + NWIN * K
+    bounds = window_bounds(K, args.windows)      # the K timed steps in consecutive windows; value = median of their rates
+    NWIN = len(bounds)
+    total_its = W + K
 
     t_asm = time.perf_counter()
     sysm = mac_stokes(args.dim, args.n, args.nu)
@@ -587,20 +623,20 @@ def main():
         run.start(tol=0.0, maxsteps=total_its + prof_its)
         run.iterate(0, W)
         windows = []
-        for w in range(NWIN):                               # each window: K steps, barrier + synchronize on both sides
+        for a, b in bounds:                                 # each window: barrier + synchronize on both sides
             torch.cuda.synchronize()
             dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            run.iterate(W + w * K, W + (w + 1) * K)
+            run.iterate(W + a, W + b)
             torch.cuda.synchronize()
             dist.barrier()
             torch.cuda.synchronize()
             windows.append(time.perf_counter() - t0)
         tt = torch.tensor(windows, dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)           # per window: the slowest rank
-        windows = [float(v) for v in tt.tolist()]
-        elapsed = float(np.median(windows))
+        rates = [(b - a) / float(v) for (a, b), v in zip(bounds, tt.tolist())]
+        elapsed = K / float(np.median(rates))               # K steps at the median window rate
         done, _, last = run.poll()
         hist = run.history(total_its - 1)
         ok = (not done) and last == total_its - 1 and bool(np.all(np.isfinite(hist)))
@@ -644,8 +680,9 @@ def main():
                 "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K,
                 "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
                 "data": "synthetic",
-                "timing": "median of %d consecutive windows of %d steps (max over ranks per window)" % (NWIN, K),
-                "window_values": [K / w for w in windows],
+                "timing": "median rate of %d consecutive windows over %d timed steps (max over ranks per window)"
+                          % (NWIN, K),
+                "window_values": rates,
                 "config": {"workload": "templates/NavierStokesSIMPLE_test_3D.py restated: 3-D MAC Stokes n=%d, "
                                        "%d DoF, BPCG v2, %s preA, row-partitioned over %d GPUs"
                                        % (args.n, sysm.ndof, args.pre, world),
@@ -690,16 +727,23 @@ def main():
 
     loop.enqueue(0, W)
     torch.cuda.synchronize()
-    windows = []
-    for w in range(NWIN):                                   # each window: exactly K steps between two synchronisations
-        t0 = time.perf_counter()
-        loop.enqueue(W + w * K, W + (w + 1) * K)
-        torch.cuda.synchronize()
-        windows.append(time.perf_counter() - t0)
-    elapsed = float(np.median(windows))
+    # the windows follow each other on the stream with no synchronisation between them: HIP events between windows
+    # time each one on the device, the host clock the whole stretch of K steps
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(NWIN + 1)]
+    t0 = time.perf_counter()
+    ev[0].record()
+    for w, (a, b) in enumerate(bounds):
+        loop.enqueue(W + a, W + b)
+        ev[w + 1].record()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    rates = [1e3 * (b - a) / ev[w].elapsed_time(ev[w + 1]) for w, (a, b) in enumerate(bounds)]
+    elapsed = K / float(np.median(rates))                  # K steps at the median window rate
     done, _, last = loop.poll()
     hist = loop.history(total_its - 1)
     valid = (not done) and last == total_its - 1 and bool(np.all(np.isfinite(hist)))
+    if args.dump_outputs:                                   # before the kernel timings below iterate further
+        dump_outputs(args.dump_outputs, {"velocity": sol[0].numpy(), "pressure": sol[1].numpy(), "history": hist})
 
     # ---- roofline of the dominant kernel: C23 = rows of A and rows of B in one launch -------------
     a_info, b_info = A.handle.info(), B.handle.info()
@@ -831,8 +875,9 @@ def main():
         "metric": "Krylov iters/sec, 3D SIMPLE Stokes solve (BPCG)", "value": K / elapsed, "unit": "iters/s",
         "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "timing": "median of %d consecutive windows of %d steps" % (NWIN, K),
-        "window_values": [K / w for w in windows],
+        "timing": "median rate of %d consecutive windows over %d timed steps (HIP events between the windows)"
+                  % (NWIN, K),
+        "window_values": rates, "wall_ms_per_step": 1e3 * wall / K,
         "config": {"workload": "templates/NavierStokesSIMPLE_test_3D.py restated: %d-D MAC Stokes n=%d, %d DoF, "
                                "BPCG v2 (solvers/bramblepasciak_new.py), %s preA, lumped-mass preM, Re=%g"
                                % (args.dim, args.n, sysm.ndof, args.pre, 1.0 / args.nu),

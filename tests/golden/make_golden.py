@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ (run in the BUILD CONTAINER only).
 
-How: the reference's *unmodified* solver files are loaded from /root/reference
+How: the reference's *unmodified* solver files are loaded from a checkout of it given on the command line
 (minres.py, bramble_pasciak_cg.py, solvers/bramblepasciak_new.py, orthonormalization.py) with
 ``ngsolve`` resolved to a test-only stand-in, TWICE:
 
@@ -22,7 +22,7 @@ numpy/scipy arithmetic; against real NGSolve output parity is unpinned.
 Nothing of the reference is written to the repo: only inputs (generator parameters, seed) and
 outputs (k, histories, iteration counts, norms, solution samples).
 
-    python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py <reference checkout>          # rewrites tests/golden/*.npz
 """
 
 import contextlib
@@ -38,7 +38,7 @@ import scipy.sparse as sp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+REF = None            # the reference checkout (command line)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "navier-stokes-solver_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -469,4 +469,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.isdir(sys.argv[1]):
+        raise SystemExit("usage: make_golden.py <checkout of matschiner/navier-stokes-solver>")
+    REF = os.path.abspath(sys.argv[1])
     main()
