@@ -168,6 +168,12 @@ NSS_API int nss_csr_operand_form(nss_csr_t a, int32_t* form);
  * bits: only the partition of the rows into workgroups changes. */
 NSS_API int nss_csr_plan_for_blocks(nss_csr_t a, nss_bjac_t j, int32_t* planned);
 NSS_API int nss_csr_plan_for_pairs(nss_csr_t a, int32_t* pair_staged);
+/* Launch-plan generation of `a`: 0 for the plan made at upload; every re-plan (the two calls above, and the joint
+ * cycle of nss_amg_create_auxiliary over the matrices of its hierarchies) takes a fresh, larger value from one
+ * process-wide counter.  A re-plan changes the row-block count, hence the dot partials every fused loop writes: each
+ * loop state records the largest generation among its matrices in `plan_gen` (with the capacities of its partials
+ * buffers in `cap_*`) when it sizes them with its nss_*_workspace, and refuses to launch once that has moved. */
+NSS_API int nss_csr_plan_generation(nss_csr_t a, int64_t* generation);
 /* the same question without re-planning */
 NSS_API int nss_csr_pair_staged(nss_csr_t a, int32_t* pair_staged);
 /* process-wide override (tests, measurements): 0 = kernels never take the pair-staged form (they gather through the
@@ -231,10 +237,12 @@ NSS_API int nss_bjac_info(nss_bjac_t j, int32_t* bs, int32_t* nblocks, int64_t* 
 NSS_API int nss_bjac_set_colors(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors, const int32_t* h_color_ptr,
                                 const int32_t* h_color_rowptr, const int32_t* h_rowdof, const int32_t* h_ridx);
 /* The same sweeps with the colour-major numbering used INSIDE the sweep as well: `a_perm` = P A P^T from
- * nss_csr_permute (rows AND columns in the colour-major block order; n_perm rows = the dofs of the blocks, n_perm + 1
- * columns, the last standing for the dofs outside every block; every row block of its launch plan holds whole
- * Gauss-Seidel blocks and at most 256 rows).  A sweep call gathers x and y into that numbering once, runs ONE launch
- * per colour (rows of the colour with the block solve in the epilogue: the residuals of a row block pass through LDS)
+ * nss_csr_permute (rows AND columns in the colour-major block order; n_perm rows = the dofs of the blocks; the dofs
+ * outside every block, ascending, are the trailing columns n_perm .. n_perm + n_uncovered - 1 -- n_perm + 1 columns,
+ * the last one without entries, when every dof is in a block; every row block of its launch plan holds whole
+ * Gauss-Seidel blocks and at most 256 rows).  A sweep call gathers x and y into that numbering once (y also at the
+ * uncovered dofs: the sweep reads A(block, uncovered) y and leaves those entries as they are), runs ONE launch per
+ * colour (rows of the colour with the block solve in the epilogue: the residuals of a row block pass through LDS)
  * and scatters y back once; the symmetric operator gathers / scatters once for both sweeps.  Same products in the
  * same order as the two-launch form: same bits. */
 NSS_API int nss_bjac_set_colors_permuted(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors, const int32_t* h_color_ptr,
@@ -279,7 +287,11 @@ NSS_API int nss_amg_create(int32_t nlevels, const nss_amg_level_t* h_levels, nss
  * (templates/NavierStokesSIMPLE_iterative.py:291,320-357,380,383).  T (rows: velocity dofs, columns: the
  * stacked per-component auxiliary spaces) and its explicit transpose TT; comps[c] = V-cycle handle of
  * component c's auxiliary operator (nss_amg_create), sizes adding up to the columns of T.  Accepted
- * wherever a V-cycle handle is (nss_amg_apply_f64, pre_amg of the fused loops). */
+ * wherever a V-cycle handle is (nss_amg_apply_f64, pre_amg of the fused loops).
+ * When components share a hierarchy (joint cycle, nss_amg_batch_components) this RE-PLANS that hierarchy's level
+ * matrices (A, P, R and the coarse inverse) in place: loop states that hold any of them must query their workspace
+ * again (nss_csr_plan_generation).  The handle itself remembers the generations it planned: a later re-plan of one
+ * of those matrices makes nss_amg_apply_f64 (and every loop with it as pre_amg) refuse. */
 NSS_API int nss_amg_create_auxiliary(nss_csr_t T, nss_csr_t TT, int32_t ncomp, const nss_amg_t* h_comps,
                                      nss_amg_t* out);
 /* Components that share ONE hierarchy handle (the same Laplacian and boundary conditions for every velocity component)
@@ -377,6 +389,11 @@ typedef struct nss_bpcg2_s {
    * the nranks values added in rank order) and the halo of t1 travels by a put kernel into the neighbours' landing
    * zones; no collective library on the critical path.  NULL: RCCL (nss_dist_t). */
   struct nss_p2p_s* p2p;
+  /* the launch plans the partials were sized for: plan_gen = the largest nss_csr_plan_generation of A, B, BT at the
+   * workspace query, cap_* = entries allocated for each partials buffer.  Every launching entry point refuses the
+   * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
+  int64_t plan_gen;
+  int64_t cap_a, cap_b, cap_c;
 } nss_bpcg2_t;
 
 enum {
@@ -564,6 +581,11 @@ typedef struct nss_cg_s {
   double* hist;
   double *partials_a, *partials_b;  /* A's row-block count / element-wise grid: nss_cg_workspace() */
   int32_t n;
+  /* the launch plans the partials were sized for: plan_gen = the largest nss_csr_plan_generation of A at the
+   * workspace query, cap_* = entries allocated for each partials buffer.  Every launching entry point refuses the
+   * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
+  int64_t plan_gen;
+  int64_t cap_a, cap_b;
 } nss_cg_t;
 NSS_API int nss_cg_workspace(const nss_cg_t* s, int64_t* partials_a, int64_t* partials_b);
 NSS_API int nss_cg_iterate(const nss_cg_t* s, int32_t it_begin, int32_t it_end, nss_stream_t stream);
@@ -596,6 +618,11 @@ typedef struct nss_lanczos_s {
   double* hist;                /* double[2 * maxsteps]                                                     */
   double *partials_a, *partials_b;  /* sizes: nss_lanczos_workspace()                                      */
   int32_t n;
+  /* the launch plans the partials were sized for: plan_gen = the largest nss_csr_plan_generation of A at the
+   * workspace query, cap_* = entries allocated for each partials buffer.  Every launching entry point refuses the
+   * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
+  int64_t plan_gen;
+  int64_t cap_a, cap_b;
 } nss_lanczos_t;
 NSS_API int nss_lanczos_workspace(const nss_lanczos_t* s, int64_t* partials_a, int64_t* partials_b);
 /* out[i] = the start vector's entry of global index offset + i (hipla/eigen.py::lanczos_start_values: a hash of the
@@ -651,6 +678,11 @@ typedef struct nss_minres_s {
    * iteration's set until the caller (or nss_minres_iterate_dist) all-reduces them out of place into
    * slots 0 (delta) / 2 (gamma_new^2). */
   int32_t local_sums;
+  /* the launch plans the partials were sized for: plan_gen = the largest nss_csr_plan_generation of A, B, BT at the
+   * workspace query, cap_* = entries allocated for each partials buffer.  Every launching entry point refuses the
+   * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
+  int64_t plan_gen;
+  int64_t cap_a, cap_b, cap_c;
 } nss_minres_t;
 
 NSS_API int nss_minres_workspace(const nss_minres_t* s, int64_t* partials_a, int64_t* partials_b,
@@ -706,6 +738,11 @@ typedef struct nss_bpcg1_s {
   double k;
   int32_t n_u, n_p;
   int32_t local_sums;
+  /* the launch plans the partials were sized for: plan_gen = the largest nss_csr_plan_generation of A, B, BT at the
+   * workspace query, cap_* = entries allocated for each partials buffer.  Every launching entry point refuses the
+   * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
+  int64_t plan_gen;
+  int64_t cap_a, cap_b, cap_c;
 } nss_bpcg1_t;
 
 NSS_API int nss_bpcg1_workspace(const nss_bpcg1_t* s, int64_t* partials_a, int64_t* partials_b,

@@ -44,7 +44,8 @@ struct nss_amg_s {
   // the rowblk -> rowptr chain
   struct MultiDesc {
     const nss_csr_s* mat;
-    const int32_t* rowblk;           // the launch plan the descriptors were made from (checked at every launch)
+    int64_t plan_gen;                // generation of the launch plan the descriptors were made from (checked at
+                                     // every launch: a freed and re-allocated rowblk can come back at the same address)
     int32_t* desc;
   };
   std::vector<MultiDesc> multi_desc;

@@ -241,7 +241,9 @@ __global__ __launch_bounds__(kBlock) void amg_diag_multi_kernel(int32_t n, doubl
 static const int32_t* multi_desc_of(const nss_amg_s& aux, const nss_csr_s& A) {
   for (const auto& e : aux.multi_desc)
     if (e.mat == &A) {
-      if (e.rowblk != A.rowblk) throw Error("amg: a level matrix of the joint cycle was re-planned after the handle was created");
+      if (e.plan_gen != A.plan_gen)
+        throw Error("amg: a level matrix of the joint cycle was re-planned after the handle was created (plan generation " +
+                    std::to_string(e.plan_gen) + " -> " + std::to_string(A.plan_gen) + ")");
       return e.desc;
     }
   throw Error("amg: a matrix of the joint cycle has no row-block descriptors");
@@ -383,7 +385,10 @@ int nss_amg_create_auxiliary(nss_csr_t T, nss_csr_t TT, int32_t ncomp, const nss
       for (int c = 1; c < ncomp; ++c) shared = shared && h_comps[c] == h_comps[0];
       if (shared && h_comps[0]->levels.size() >= 2) {
         // every level operator is read once for all components: row blocks of at most kMultiChunk products (the plan
-        // of the matrices changes -- set-up only; per-row sums of the single-vector kernels keep their bits)
+        // of the matrices changes -- set-up only; per-row sums of the single-vector kernels keep their bits).  This
+        // RE-PLANS the shared hierarchy in place: each matrix gets a new plan generation, so loop states holding one of
+        // them refuse until they re-size their partials, and the descriptors below record the generation they were
+        // made for (multi_desc_of)
         const nss_amg_s& h = *h_comps[0];
         for (const AmgLevel& lv : h.levels) {
           replan_row_blocks(*const_cast<nss_csr_s*>(lv.A), kMultiChunk);
@@ -395,7 +400,7 @@ int nss_amg_create_auxiliary(nss_csr_t T, nss_csr_t TT, int32_t ncomp, const nss
           if (!M || M->nblk == 0) return;
           int32_t* desc = nullptr;
           NSS_HIP(hipMalloc(&desc, sizeof(int32_t) * 4 * size_t(M->nblk)));
-          a->multi_desc.push_back({M, M->rowblk, desc});
+          a->multi_desc.push_back({M, M->plan_gen, desc});
           hipLaunchKernelGGL(multi_desc_kernel, dim3((M->nblk + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, M->nblk,
                              M->rowblk, M->rowptr, desc);
           NSS_CHECK_LAUNCH();

@@ -359,6 +359,9 @@ static void bpcg1_check(const nss_bpcg1_t* s) {
               "bpcg1: NULL work buffer");
   for (int c = 0; c < 2; ++c)
     NSS_REQUIRE(s->x[c] && s->r[c] && s->d[c] && s->a[c] && s->t1[c] && s->t2[c], "bpcg1: NULL vector");
+  const int64_t need[3] = {s->A->nblk, s->B->nblk, p_grid(*s)};     // = nss_bpcg1_workspace
+  const int64_t cap[3] = {s->cap_a, s->cap_b, s->cap_c};
+  check_plan("bpcg1", plan_stamp({s->A, s->B, s->BT}), s->plan_gen, need, cap, 3);
 }
 
 struct Bpcg1Dist {

@@ -723,6 +723,20 @@ static void launch_k4(const nss_bpcg2_t& s, int it, bool fold, hipStream_t st) {
   NSS_CHECK_LAUNCH();
 }
 
+// what nss_bpcg2_workspace reports for the current launch plans
+static void bpcg2_need(const nss_bpcg2_t& s, int64_t* need) {
+  need[0] = s.A->nblk;
+  need[1] = s.B->nblk;
+  need[2] = k4_partials(s);
+}
+
+static void bpcg2_check_plan(const nss_bpcg2_t& s) {
+  int64_t need[3];
+  bpcg2_need(s, need);
+  const int64_t cap[3] = {s.cap_a, s.cap_b, s.cap_c};
+  check_plan("bpcg2", plan_stamp({s.A, s.B, s.BT}), s.plan_gen, need, cap, 3);
+}
+
 void bpcg2_check_state(const nss_bpcg2_t* s) {
   NSS_REQUIRE(s != nullptr, "bpcg2: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "bpcg2: NULL matrix handle");
@@ -777,6 +791,7 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
   NSS_REQUIRE(s->u0 && s->u1 && s->d0 && s->d1 && s->w0 && s->w1 && s->s0 && s->s1 && s->z0 && s->q && s->t0 &&
                   s->t1 && s->t2 && s->t3 && s->t4,
               "bpcg2: NULL vector");
+  bpcg2_check_plan(*s);
 }
 
 // SpMV phases over the row blocks [b0, b1) of their matrix (b1 < 0: all).  The block-Jacobi
@@ -991,9 +1006,11 @@ extern "C" {
 int nss_bpcg2_workspace(const nss_bpcg2_t* s, int64_t* partials_a, int64_t* partials_b, int64_t* partials_c) {
   return guarded([&] {
     NSS_REQUIRE(s && s->A && s->B, "bpcg2_workspace: NULL state / matrices");
-    if (partials_a) *partials_a = s->A->nblk;
-    if (partials_b) *partials_b = s->B->nblk;
-    if (partials_c) *partials_c = k4_partials(*s);
+    int64_t need[3];
+    bpcg2_need(*s, need);
+    if (partials_a) *partials_a = need[0];
+    if (partials_b) *partials_b = need[1];
+    if (partials_c) *partials_c = need[2];
   });
 }
 
@@ -1074,6 +1091,8 @@ int nss_bpcg2_poll(const nss_bpcg2_t* s, int32_t* done, int32_t* it_final, int32
   return guarded([&] {
     NSS_REQUIRE(s && s->ctrl, "bpcg2_poll: NULL state");
     if (s->hist && s->partials_c && s->scal && s->A && s->B) {   // compact plan: the books of the last computed iteration
+      NSS_REQUIRE(s->BT, "bpcg2_poll: NULL matrix handle");
+      bpcg2_check_plan(*s);
       hipLaunchKernelGGL(bpcg2_close_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), close_args(*s, fold_sums(*s)));
       NSS_CHECK_LAUNCH();
     }

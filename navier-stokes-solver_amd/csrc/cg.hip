@@ -132,6 +132,9 @@ static void cg_check(const nss_cg_t* s) {
   NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels[0].n == s->n, "cg: AMG size mismatch");
   NSS_REQUIRE(s->x && s->r && s->z && s->p && s->q && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b,
               "cg: NULL buffer");
+  const int64_t need[2] = {s->A->nblk, std::max<int64_t>(cg_grid(*s), s->pre_bjac ? bjac_dot_grid(*s->pre_bjac) : 0)};
+  const int64_t cap[2] = {s->cap_a, s->cap_b};     // (need = nss_cg_workspace)
+  check_plan("cg", plan_stamp({s->A}), s->plan_gen, need, cap, 2);
 }
 
 static void cg_iteration(const nss_cg_t& s, int it, hipStream_t st) {

@@ -26,6 +26,9 @@
 
 #include "nss_common.h"
 
+#include <initializer_list>
+#include <string>
+
 namespace nss {
 
 // Non-temporal loads for the col/val streams: they are read exactly once, and keeping them
@@ -108,6 +111,10 @@ struct nss_csr_s {
   int32_t chunk = nss::kChunk;   // products the kernels' LDS buffer holds (the template parameter CH)
   int32_t blk_products = nss::kChunk;   // products per row block the launch plan aims at (<= chunk; nss_csr_plan_for_pairs)
   std::vector<int32_t> cuts;     // row positions no row block spans (kept for re-planning)
+  // Launch-plan generation: 0 for the plan made at upload; every re-plan (nss_csr_plan_for_pairs / _for_blocks, the
+  // joint AMG cycle of nss_amg_create_auxiliary) takes the next value of ONE process-wide counter, so the largest
+  // generation among the matrices of a loop state changes exactly when one of them was re-planned (plan_stamp).
+  int64_t plan_gen = 0;
   // Compressed column stream: when the columns of every row block fall into at most 16 aligned
   // windows of 4096 columns (grid operators: a row block touches its own grid plane and the two
   // neighbouring ones -- a few narrow clusters far apart) the kernel streams 2 bytes per entry,
@@ -790,5 +797,33 @@ struct EpiAxpby {
   }
   __device__ void finish(int, double*) const {}
 };
+
+}  // namespace nss
+
+namespace nss {
+
+// largest launch-plan generation among `ms` (NULL entries skipped): what a loop state records in `plan_gen` when it
+// sizes its dot partials (the host computes the same from nss_csr_plan_generation)
+inline int64_t plan_stamp(std::initializer_list<const nss_csr_s*> ms) {
+  int64_t g = 0;
+  for (const nss_csr_s* m : ms)
+    if (m && m->plan_gen > g) g = m->plan_gen;
+  return g;
+}
+
+// Refuse a loop state before any launch when a matrix of it was re-planned since its partials were sized (its kernels
+// and sum launches take the CURRENT row-block counts), or when a partials buffer holds fewer entries than the
+// workspace query asks for now.  need / cap: n counts.
+inline void check_plan(const char* who, int64_t stamp, int64_t recorded, const int64_t* need, const int64_t* cap, int n) {
+  if (stamp != recorded)
+    throw Error(std::string("invalid argument: ") + who + ": a matrix of this state was re-planned (plan generation " +
+                std::to_string(recorded) + " -> " + std::to_string(stamp) + ": nss_csr_plan_for_pairs, " +
+                "nss_csr_plan_for_blocks or nss_amg_create_auxiliary) after its dot partials were sized; query the " +
+                "workspace again, re-allocate and record plan_gen / cap_*");
+  for (int i = 0; i < n; ++i)
+    if (need[i] > cap[i])
+      throw Error(std::string("invalid argument: ") + who + ": partials buffer " + char('a' + i) + " holds " +
+                  std::to_string(cap[i]) + " entries, the launch plan needs " + std::to_string(need[i]));
+}
 
 }  // namespace nss

@@ -328,6 +328,8 @@ static bool lz_fused(const nss_lanczos_t& s) {
 }
 static bool lz_fold_a(const nss_lanczos_t& s) { return g_lanczos_fold_mode == 1 || s.A->nblk <= kLzFoldMax; }
 
+static int64_t lz_partials_b(const nss_lanczos_t& s);
+
 static void lz_check(const nss_lanczos_t* s) {
   NSS_REQUIRE(s != nullptr && s->A != nullptr, "lanczos: NULL state / matrix");
   NSS_REQUIRE(s->A->m == s->n && s->A->n == s->n, "lanczos: matrix does not match n");
@@ -338,6 +340,9 @@ static void lz_check(const nss_lanczos_t* s) {
   for (int i = 0; i < 3; ++i) NSS_REQUIRE(s->v[i] != nullptr, "lanczos: NULL vector");
   NSS_REQUIRE(s->z[0] && s->z[1] && s->p && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b,
               "lanczos: NULL buffer");
+  const int64_t need[2] = {s->A->nblk, 2 * lz_partials_b(*s)};      // = nss_lanczos_workspace
+  const int64_t cap[2] = {s->cap_a, s->cap_b};
+  check_plan("lanczos", plan_stamp({s->A}), s->plan_gen, need, cap, 2);
 }
 
 // z = pre_scale * pre x for everything that is not the fused point Jacobi; leaves the partials of <z, x> in

@@ -464,6 +464,17 @@ static bool m_merged_rows(const nss_minres_t& s) {
   return s.BT->m == s.A->m && fixed_width_copy(*s.BT);
 }
 
+// what nss_minres_workspace reports for the current launch plans
+static void minres_need(const nss_minres_t& s, int64_t* need) {
+  int64_t dotg = m_dot_grid(s);
+  if (s.pre_bjac) dotg = std::max<int64_t>(dotg, bjac_dot_grid(*s.pre_bjac));
+  need[0] = std::max<int64_t>(s.A->nblk, dotg);
+  need[1] = s.B->nblk;
+  // M3 in either form (block Jacobi fused: one lane per block; else two entries per lane)
+  const int64_t gu_fused = s.pre_bjac ? (s.pre_bjac->nblocks + kBlock - 1) / kBlock : 0;
+  need[2] = std::max<int64_t>(gu_fused, m_gu(s)) + m_gp(s);
+}
+
 static void minres_check(const nss_minres_t* s) {
   NSS_REQUIRE(s != nullptr, "minres: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "minres: NULL matrix handle");
@@ -483,6 +494,10 @@ static void minres_check(const nss_minres_t* s) {
     NSS_REQUIRE(s->u[c] && s->kz[c] && s->z[0][c] && s->z[1][c], "minres: NULL vector");
     for (int j = 0; j < 3; ++j) NSS_REQUIRE(s->v[j][c] && s->w[j][c], "minres: NULL ring vector");
   }
+  int64_t need[3];
+  minres_need(*s, need);
+  const int64_t cap[3] = {s->cap_a, s->cap_b, s->cap_c};
+  check_plan("minres", plan_stamp({s->A, s->B, s->BT}), s->plan_gen, need, cap, 3);
 }
 
 template <int BS>
@@ -615,13 +630,11 @@ extern "C" {
 int nss_minres_workspace(const nss_minres_t* s, int64_t* partials_a, int64_t* partials_b, int64_t* partials_c) {
   return guarded([&] {
     NSS_REQUIRE(s && s->A && s->B && s->BT, "minres_workspace: NULL state / matrices");
-    int64_t dotg = m_dot_grid(*s);
-    if (s->pre_bjac) dotg = std::max<int64_t>(dotg, bjac_dot_grid(*s->pre_bjac));
-    if (partials_a) *partials_a = std::max<int64_t>(s->A->nblk, dotg);
-    if (partials_b) *partials_b = s->B->nblk;
-    // M3 in either form (block Jacobi fused: one lane per block; else two entries per lane)
-    const int64_t gu_fused = s->pre_bjac ? (s->pre_bjac->nblocks + kBlock - 1) / kBlock : 0;
-    if (partials_c) *partials_c = std::max<int64_t>(gu_fused, m_gu(*s)) + m_gp(*s);
+    int64_t need[3];
+    minres_need(*s, need);
+    if (partials_a) *partials_a = need[0];
+    if (partials_b) *partials_b = need[1];
+    if (partials_c) *partials_c = need[2];
   });
 }
 

@@ -26,7 +26,9 @@ struct nss_bjac_s {
   int32_t* ridx = nullptr;                // device [bs][nblocks]: permuted row of a block entry, -1 = padding
   double* res = nullptr;                  // device: residual of the colour being swept (permuted rows)
   // Colour-major layout INSIDE the sweep (nss_bjac_set_colors_permuted): gs_mat is P A P^T -- rows and columns in the
-  // colour-major block order, dofs that belong to no block map to the extra column n_perm (always 0) -- the iterate
+  // colour-major block order; the dofs that belong to no block (`covered`, ascending) are the trailing columns
+  // n_perm .. n_perm + n_uncovered - 1, gathered from y on every entry and never updated or scattered (with every dof
+  // covered: one extra column n_perm without entries, 0) -- the iterate
   // and the right-hand side are gathered into that numbering once on entry (yt, xt) and the iterate is scattered back
   // once on exit; a colour is then ONE launch: the rows of the colour with the block solve in the epilogue (every
   // row block of gs_mat holds whole Gauss-Seidel blocks and at most kGsRows rows; the residuals of a row block pass
@@ -36,7 +38,7 @@ struct nss_bjac_s {
   uint8_t* gpos = nullptr;                // [n_perm] position of the row inside its block
   uint8_t* glen = nullptr;                // [n_perm] rows of its block
   double* ginv = nullptr;                 // [bs][n_perm]: ginv[k][r] = (A_bb^-1)(row r, k-th row of the block)
-  double *xt = nullptr, *yt = nullptr;    // [n_perm + 1]
+  double *xt = nullptr, *yt = nullptr;    // [n_perm + max(1, n_uncovered)]
 };
 
 namespace nss {

@@ -278,18 +278,21 @@ struct EpiGsFused {
   }
 };
 
-// entry: xt = x[rowdof], yt = y[rowdof] (or 0), the extra slot behind them 0
+// entry: xt = x[rowdof], yt = y[rowdof] (or 0); behind them the trailing columns of the dofs in no block: yt = y[unc]
+// (they couple to the blocks through A and are never updated; xt = 0 there), or -- every dof covered -- one slot, 0
 __global__ __launch_bounds__(kBlock) void gs_enter_kernel(int32_t n_perm, const int32_t* __restrict__ rowdof,
+                                                           int32_t n_unc, const int32_t* __restrict__ unc,
                                                            const double* __restrict__ x, const double* __restrict__ y,
                                                            double* __restrict__ xt, double* __restrict__ yt,
                                                            const int32_t* __restrict__ done) {
   if (done && done[0] != 0) return;
   const int stride = gridDim.x * kBlock;
-  for (int r = blockIdx.x * kBlock + threadIdx.x; r <= n_perm; r += stride) {
-    const bool live = r < n_perm;
-    const int d = live ? rowdof[r] : 0;
-    if (x) xt[r] = live ? x[d] : 0.0;                    // (x == NULL: the permuted copy of the previous call stays)
-    yt[r] = (live && y) ? y[d] : 0.0;
+  const int n_ext = n_perm + (n_unc > 0 ? n_unc : 1);
+  for (int r = blockIdx.x * kBlock + threadIdx.x; r < n_ext; r += stride) {
+    const bool row = r < n_perm, trail = !row && r - n_perm < n_unc;
+    const int d = row ? rowdof[r] : (trail ? unc[r - n_perm] : 0);
+    if (x) xt[r] = row ? x[d] : 0.0;                     // (x == NULL: the permuted copy of the previous call stays)
+    yt[r] = ((row || trail) && y) ? y[d] : 0.0;
   }
 }
 
@@ -359,8 +362,8 @@ static void gs_sweep_permuted(const nss_bjac_s& j, double xscale, bool backward,
 }
 
 static void gs_enter(const nss_bjac_s& j, const double* x, const double* y, const int32_t* done, hipStream_t st) {
-  hipLaunchKernelGGL(gs_enter_kernel, dim3(stream_grid(int64_t(j.n_perm) + 1, kBlock)), dim3(kBlock), 0, st, j.n_perm,
-                     j.rowdof, x, y, j.xt, j.yt, done);
+  hipLaunchKernelGGL(gs_enter_kernel, dim3(stream_grid(int64_t(j.n_perm) + std::max(1, j.n_uncovered), kBlock)),
+                     dim3(kBlock), 0, st, j.n_perm, j.rowdof, j.n_uncovered, j.covered, x, y, j.xt, j.yt, done);
   NSS_CHECK_LAUNCH();
 }
 
@@ -664,8 +667,10 @@ int nss_bjac_set_colors_permuted(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors
   return guarded([&] {
     NSS_REQUIRE(j && a_perm && h_color_ptr && h_color_rowptr && h_rowdof && h_ridx, "bjac_set_colors_permuted: NULL argument");
     const int32_t n_perm = a_perm->m;
-    NSS_REQUIRE(a_perm->n == n_perm + 1, "bjac_set_colors_permuted: the permuted matrix must have n_perm + 1 columns (the "
-                                         "last one stands for the dofs outside every block)");
+    const size_t n_ext = size_t(n_perm) + size_t(std::max(1, j->n_uncovered));
+    NSS_REQUIRE(int64_t(a_perm->n) == int64_t(n_ext),
+                "bjac_set_colors_permuted: the permuted matrix must have n_perm + n_uncovered columns (the dofs outside "
+                "every block last, ascending), n_perm + 1 when every dof is in a block");
     NSS_REQUIRE(int64_t(n_perm) + j->n_uncovered == j->n, "bjac_set_colors_permuted: the permuted rows must be exactly the dofs of the blocks");
     // the common part (offsets, rowdof, ridx, the residual buffer of the two-launch form)
     set_colors_common(j, a_perm, ncolors, h_color_ptr, h_color_rowptr, h_rowdof, h_ridx, true);
@@ -695,10 +700,10 @@ int nss_bjac_set_colors_permuted(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors
     NSS_HIP(hipMalloc(&j->gpos, std::max<size_t>(1, n_perm)));
     NSS_HIP(hipMalloc(&j->glen, std::max<size_t>(1, n_perm)));
     NSS_HIP(hipMalloc(&j->ginv, sizeof(double) * size_t(j->bs) * std::max<size_t>(1, n_perm)));
-    NSS_HIP(hipMalloc(&j->xt, sizeof(double) * (size_t(n_perm) + 1)));
-    NSS_HIP(hipMalloc(&j->yt, sizeof(double) * (size_t(n_perm) + 1)));
-    NSS_HIP(hipMemset(j->xt, 0, sizeof(double) * (size_t(n_perm) + 1)));
-    NSS_HIP(hipMemset(j->yt, 0, sizeof(double) * (size_t(n_perm) + 1)));
+    NSS_HIP(hipMalloc(&j->xt, sizeof(double) * n_ext));
+    NSS_HIP(hipMalloc(&j->yt, sizeof(double) * n_ext));
+    NSS_HIP(hipMemset(j->xt, 0, sizeof(double) * n_ext));
+    NSS_HIP(hipMemset(j->yt, 0, sizeof(double) * n_ext));
     hipLaunchKernelGGL(gs_pack_inverse_kernel, dim3((j->nblocks + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, j->bs,
                        j->nblocks, n_perm, j->ridx, j->inv, j->ginv, j->gpos, j->glen);
     NSS_CHECK_LAUNCH();

@@ -757,6 +757,9 @@ int nss_csr_destroy(nss_csr_t a) {
   });
 }
 
+// process-wide source of launch-plan generations (nss_csr_s::plan_gen); set-up is single-threaded per process
+static int64_t g_plan_generation = 0;
+
 // new launch plan with at most `products` products per row block; every derived column stream is rebuilt
 static void replan(nss_csr_s& A, int products, int max_rows = 0, const uint8_t* row_pos = nullptr,
                    std::vector<int32_t>* blk_out = nullptr) {
@@ -800,6 +803,7 @@ static void replan(nss_csr_s& A, int products, int max_rows = 0, const uint8_t* 
   A.rg = rg;                                             // (unchanged: the lanes-per-row rule does not see `products`)
   A.nblk = int32_t(blk.size()) - 1;
   A.blk_products = products;
+  A.plan_gen = ++g_plan_generation;                     // (loop states sized for the old plan now refuse)
   compress_columns(A, nullptr);
   if (blk_out) blk_out->swap(blk);
 }
@@ -863,6 +867,13 @@ int nss_csr_plan_for_pairs(nss_csr_t a, int32_t* pair_staged) {
       if (!a->pair_ok) replan(*a, before);               // wide operators: shorter blocks do not help; back to the full plan
     }
     if (pair_staged) *pair_staged = (a->blkseg && a->pair_ok) ? 1 : 0;
+  });
+}
+
+int nss_csr_plan_generation(nss_csr_t a, int64_t* generation) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr && generation != nullptr, "csr_plan_generation: NULL argument");
+    *generation = a->plan_gen;
   });
 }
 

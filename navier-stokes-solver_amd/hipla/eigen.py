@@ -44,7 +44,8 @@ class _LanczosState:
                 _fields_ = ([(n, C.c_void_p) for n in ("A", "pre_diag", "pre_bjac", "pre_amg")]
                             + [("pre_scale", C.c_double), ("v", C.c_void_p * 3), ("z", C.c_void_p * 2), ("p", C.c_void_p),
                                ("scal", C.c_void_p), ("ctrl", C.c_void_p), ("hist", C.c_void_p),
-                               ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("n", C.c_int32)])
+                               ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("n", C.c_int32),
+                               ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64)])
             cls._cls = LanczosState
         return cls._cls
 
@@ -90,10 +91,7 @@ def _native_lanczos(mat, pre, start, tol, maxsteps, check_every):
         st.v[i] = vecs[i].data_ptr()
     st.z[0], st.z[1], st.p = vecs[3].data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr()
     st.n = n
-    na, nb = C.c_int64(), C.c_int64()
-    eng._check(eng.lib.nss_lanczos_workspace(C.byref(st), C.byref(na), C.byref(nb)))
-    partials = [eng.zeros(max(1, na.value)), eng.zeros(max(1, nb.value))]
-    st.partials_a, st.partials_b = partials[0].data_ptr(), partials[1].data_ptr()
+    partials = fused.fit_partials(eng, st, eng.lib.nss_lanczos_workspace, ("A",))    # noqa: F841 (keeps them alive)
     scal = eng.zeros(8)
     ctrl = eng.torch.zeros(4, dtype=eng.torch.int32, device=eng.device)
     hist = eng.zeros(2 * maxsteps)

@@ -38,7 +38,8 @@ class Bpcg2State(C.Structure):
                    ("ghost_p_mode", C.c_int32), ("ghost_p_n", C.c_int32), ("ghost_b", C.c_void_p),
                    ("ghost_t3", C.c_void_p), ("ghost_w1", C.c_void_p), ("ghost_minv", C.c_void_p),
                    ("local_sums", C.c_int32), ("pre_dist_amg", C.c_void_p), ("dist_compact", C.c_int32),
-                   ("pre_dist_aux", C.c_void_p), ("p2p", C.c_void_p)])
+                   ("pre_dist_aux", C.c_void_p), ("p2p", C.c_void_p)]
+                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)])
 
 
 class HaloStruct(C.Structure):
@@ -148,6 +149,37 @@ def _extension_is_in_place_safe(H):
     return not np.intersect1d(rows_with_entries, np.unique(col), assume_unique=True).size
 
 
+def plan_stamp(eng, *mats):
+    """Largest launch-plan generation (nss_csr_plan_generation) among raw ``nss_csr_t`` pointers (None skipped): what a
+    loop state records in ``plan_gen`` when it sizes its dot partials.  A re-plan of a shared matrix
+    (nss_csr_plan_for_pairs / _for_blocks, nss_amg_create_auxiliary) moves it."""
+    out, gen = C.c_int64(), 0
+    for ptr in mats:
+        if ptr:
+            eng._check(eng.lib.nss_csr_plan_generation(ptr, C.byref(out)))
+            gen = max(gen, out.value)
+    return gen
+
+
+def fit_partials(eng, st, workspace, mats, partials=None):
+    """Size the dot partials of loop state `st` for the CURRENT launch plans of its matrices (field names `mats`):
+    query `workspace` (nss_*_workspace), allocate one buffer per count and record ``plan_gen`` / ``cap_*`` in the
+    state.  With the buffers of an earlier call in `partials` nothing happens unless a matrix was re-planned since
+    (the library refuses a stale state before any launch).  Returns the buffers (the caller keeps them alive)."""
+    stamp = plan_stamp(eng, *(getattr(st, m) for m in mats))
+    if partials is not None and stamp == st.plan_gen:
+        return partials
+    names = [n for n in ("a", "b", "c") if hasattr(type(st), "cap_" + n)]
+    counts = [C.c_int64() for _ in names]
+    eng._check(workspace(C.byref(st), *(C.byref(c) for c in counts)))
+    partials = [eng.zeros(max(1, c.value)) for c in counts]
+    for n, buf in zip(names, partials):
+        setattr(st, "partials_" + n, buf.data_ptr())
+        setattr(st, "cap_" + n, buf.numel())
+    st.plan_gen = stamp
+    return partials
+
+
 def _plain(v, n):
     return isinstance(v, Vector) and v.size == n
 
@@ -241,10 +273,7 @@ class Bpcg2Loop:
         st.pre_dist_amg = dist_amg
         st.pre_dist_aux = dist_aux
         self.keep.append(dist_amg)
-        na, nb, nc = C.c_int64(), C.c_int64(), C.c_int64()
-        eng._check(self.lib.nss_bpcg2_workspace(C.byref(st), C.byref(na), C.byref(nb), C.byref(nc)))
-        self.partials = [eng.zeros(max(1, v.value)) for v in (na, nb, nc)]
-        st.partials_a, st.partials_b, st.partials_c = (p.data_ptr() for p in self.partials)
+        self.partials = fit_partials(eng, st, self.lib.nss_bpcg2_workspace, ("A", "B", "BT"))
         self.scal = eng.zeros(16)
         self.ctrl = torch.zeros(8, dtype=torch.int32, device=eng.device)
         st.scal, st.ctrl = self.scal.data_ptr(), self.ctrl.data_ptr()
@@ -255,6 +284,8 @@ class Bpcg2Loop:
     def start(self, wdn, err0, tol, rel_err, maxsteps):
         """Upload the scalars of iteration 0 and clear the control words / history."""
         eng, st = self.eng, self.state
+        # a matrix this loop holds may have been re-planned by another consumer since (shared B, B^T, A)
+        self.partials = fit_partials(eng, st, self.lib.nss_bpcg2_workspace, ("A", "B", "BT"), self.partials)
         self.maxsteps = int(maxsteps)
         self.hist = eng.zeros(max(1, self.maxsteps))
         st.hist = self.hist.data_ptr()
@@ -342,7 +373,8 @@ class MinresState(C.Structure):
                    ("z", (C.c_void_p * 2) * 2), ("kz", C.c_void_p * 2),
                    ("scal", C.c_void_p), ("ctrl", C.c_void_p), ("hist", C.c_void_p),
                    ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("partials_c", C.c_void_p),
-                   ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)])
+                   ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)]
+                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)])
 
 
 (M_DELTA, M_GAMMA, M_G2, M_ETA_OLD, M_C_OLD, M_C, M_S_OLD, M_S, M_RES_OLD, M_ERR0, M_TOL) = range(11)
@@ -417,10 +449,7 @@ class MinresLoop:
             for j in range(2):
                 st.z[j][c] = z_ring[j][c].buf.data_ptr()
         st.n_u, st.n_p = A.height, B.height
-        na, nb, nc = C.c_int64(), C.c_int64(), C.c_int64()
-        eng._check(self.lib.nss_minres_workspace(C.byref(st), C.byref(na), C.byref(nb), C.byref(nc)))
-        self.partials = [eng.zeros(max(1, x.value)) for x in (na, nb, nc)]
-        st.partials_a, st.partials_b, st.partials_c = (p.data_ptr() for p in self.partials)
+        self.partials = fit_partials(eng, st, self.lib.nss_minres_workspace, ("A", "B", "BT"))
         self.scal = eng.zeros(64)           # two sets of 32 scalars, double-buffered by the parity of k
         self.ctrl = torch.zeros(4, dtype=torch.int32, device=eng.device)
         st.scal, st.ctrl = self.scal.data_ptr(), self.ctrl.data_ptr()
@@ -431,6 +460,7 @@ class MinresLoop:
         """Iterations k = 1.. as the reference's while loop.  Returns (errors, hit_relative_tol)."""
         eng, st = self.eng, self.state
         poll_every = poll_every or POLL_EVERY
+        self.partials = fit_partials(eng, st, self.lib.nss_minres_workspace, ("A", "B", "BT"), self.partials)
         self.hist = eng.zeros(maxsteps + 2)
         st.hist = self.hist.data_ptr()
         scal = np.zeros(64)                 # iteration k = 1 reads the first set
@@ -460,7 +490,8 @@ class Bpcg1State(C.Structure):
                 + [(n, C.c_void_p * 2) for n in ("x", "r", "d", "a", "t1", "t2")]
                 + [("scal", C.c_void_p), ("ctrl", C.c_void_p), ("hist", C.c_void_p),
                    ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("partials_c", C.c_void_p),
-                   ("k", C.c_double), ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)])
+                   ("k", C.c_double), ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)]
+                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)])
 
 
 class Bpcg1Loop:
@@ -519,10 +550,7 @@ class Bpcg1Loop:
             for c in range(2):
                 arr[c] = vecs[name][c].buf.data_ptr()
         st.n_u, st.n_p = A.height, B.height
-        na, nb, nc = C.c_int64(), C.c_int64(), C.c_int64()
-        eng._check(self.lib.nss_bpcg1_workspace(C.byref(st), C.byref(na), C.byref(nb), C.byref(nc)))
-        self.partials = [eng.zeros(max(1, x.value)) for x in (na, nb, nc)]
-        st.partials_a, st.partials_b, st.partials_c = (p.data_ptr() for p in self.partials)
+        self.partials = fit_partials(eng, st, self.lib.nss_bpcg1_workspace, ("A", "B", "BT"))
         self.scal = eng.zeros(16)
         self.ctrl = torch.zeros(4, dtype=torch.int32, device=eng.device)
         st.scal, st.ctrl = self.scal.data_ptr(), self.ctrl.data_ptr()
@@ -536,6 +564,7 @@ class Bpcg1Loop:
         """Returns (errors, converged): errors[i] = err_i/err_0 as appended at :118."""
         eng, st = self.eng, self.state
         poll_every = poll_every or POLL_EVERY
+        self.partials = fit_partials(eng, st, self.lib.nss_bpcg1_workspace, ("A", "B", "BT"), self.partials)
         self.hist = eng.zeros(max(1, max_steps))
         st.hist = self.hist.data_ptr()
         scal = np.zeros(16)
@@ -559,7 +588,7 @@ class CgState(C.Structure):
     """ctypes mirror of ``nss_cg_t`` (include/nss_krylov.h)."""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "pre_diag", "pre_bjac", "pre_amg", "x", "r", "z", "p", "q",
                                            "scal", "ctrl", "hist", "partials_a", "partials_b")]
-                + [("n", C.c_int32)])
+                + [("n", C.c_int32), ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64)])
 
 
 class CgLoop:
@@ -597,10 +626,7 @@ class CgLoop:
         st.pre_amg = kind[1].handle.ptr if kind[0] == "amg" else None
         for name, buf in self.work.items():
             setattr(st, name, buf.data_ptr())
-        na, nb = C.c_int64(), C.c_int64()
-        eng._check(self.lib.nss_cg_workspace(C.byref(st), C.byref(na), C.byref(nb)))
-        self.partials = [eng.zeros(max(1, v.value)) for v in (na, nb)]
-        st.partials_a, st.partials_b = (p.data_ptr() for p in self.partials)
+        self.partials = fit_partials(eng, st, self.lib.nss_cg_workspace, ("A",))
         self.scal = eng.zeros(8)
         self.ctrl = torch.zeros(4, dtype=torch.int32, device=eng.device)
         st.scal, st.ctrl = self.scal.data_ptr(), self.ctrl.data_ptr()
@@ -612,6 +638,7 @@ class CgLoop:
         from math import sqrt
         eng, st, w = self.eng, self.state, self.work
         poll_every = poll_every or POLL_EVERY
+        self.partials = fit_partials(eng, st, self.lib.nss_cg_workspace, ("A",), self.partials)
         eng.fill(x, 0.0)
         eng.copy(b, w["r"])
         kind, pre = self.kind

@@ -50,6 +50,7 @@ def _signatures():
         "nss_csr_operand_form": (C.c_int, [vp, c_i32_p]),
         "nss_csr_plan_for_pairs": (C.c_int, [vp, c_i32_p]),
         "nss_csr_pair_staged": (C.c_int, [vp, c_i32_p]),
+        "nss_csr_plan_generation": (C.c_int, [vp, c_i64_p]),
         "nss_csr_pair_mode": (C.c_int, [i32]),
         "nss_p2p_blob_bytes": (C.c_int, [i32, i32, c_i64_p]),
         "nss_p2p_create": (C.c_int, [i32, i32, i32, vp, vp, C.POINTER(vp), vp]),
@@ -200,6 +201,12 @@ class _CsrHandle:
         out = C.c_int32()
         self.engine._check(self.engine.lib.nss_csr_plan_for_blocks(self.ptr, bjac_handle.ptr, C.byref(out)))
         return bool(out.value)
+
+    def plan_generation(self):
+        """Launch-plan generation (nss_csr_plan_generation): 0 for the plan made at upload, moved by every re-plan."""
+        out = C.c_int64()
+        self.engine._check(self.engine.lib.nss_csr_plan_generation(self.ptr, C.byref(out)))
+        return out.value
 
     def plan_for_pairs(self, replan=True):
         """Re-plan (in place, set-up only) so that kernels whose operand is an expression of two vectors can take both

@@ -631,7 +631,8 @@ class BlockGaussSeidel(BaseMatrix):
         iterate, the right-hand side and the matrix (P A P^T) live in the colour-major block numbering: x and y are
         gathered once on entry and y scattered once on exit, every colour is one launch (block solve in the SpMV's
         epilogue) over contiguous data; "rows" -- round 1's form: rows of A permuted, columns and vectors in the
-        original numbering, two launches per colour.  Same bits for the same colours.
+        original numbering, two launches per colour.  Same bits for the same colours, also when some dofs belong to
+        no block: both layouts read y there (the coupling A(block, uncovered) y) and leave it unchanged.
         `coloring_method`: "greedy" (default; first fit in block order on the host: the parity colouring of grid-like
         block graphs, 2 - 4 balanced colours) or "luby" (maximal independent sets on the device: 5 - 6 colours with a
         tail of tiny ones).  NSS_GS_COLORING overrides.
@@ -683,13 +684,19 @@ class BlockGaussSeidel(BaseMatrix):
         block_row0 = np.concatenate([[0], np.cumsum(rows_per_block)])
         color_rowptr = block_row0[ptr]
         if layout == "colour-major":
-            # P A P^T: columns renamed too (dofs outside every block -> the extra column n_perm, which stays 0); row
-            # blocks of at most 256 rows that hold whole Gauss-Seidel blocks
+            # P A P^T: columns renamed too -- the dofs outside every block, ascending, become the trailing columns
+            # n_perm, n_perm + 1, ... (gathered from y on every sweep, never updated: the sweep keeps their coupling to
+            # the blocks); with every dof covered one extra column without entries; row blocks of at most 256 rows that
+            # hold whole Gauss-Seidel blocks
             n_perm = int(rowdof.size)
-            colmap = np.full(self.n, n_perm, dtype=np.int32)
+            uncovered = np.setdiff1d(np.arange(self.n, dtype=np.int64), rowdof)
+            self.n_uncovered = int(uncovered.size)
+            colmap = np.empty(self.n, dtype=np.int32)
             colmap[rowdof] = np.arange(n_perm, dtype=np.int32)
+            colmap[uncovered] = n_perm + np.arange(uncovered.size, dtype=np.int32)
             pos = (np.arange(n_perm, dtype=np.int64) - np.repeat(block_row0[:-1], rows_per_block)).astype(np.uint8)
-            self.perm_handle = self.engine.csr_permute(mat.handle, rowdof, colmap, n_perm + 1, cuts=color_rowptr,
+            self.perm_handle = self.engine.csr_permute(mat.handle, rowdof, colmap, n_perm + max(1, self.n_uncovered),
+                                                       cuts=color_rowptr,
                                                        max_rows=256, row_pos=pos)
             self.engine.bjac_set_colors_permuted(self.handle, self.perm_handle, ptr, color_rowptr, rowdof,
                                                  np.ascontiguousarray(ridx.T))

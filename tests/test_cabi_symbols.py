@@ -128,3 +128,46 @@ def test_host_routine_tridiagonal_extremes_against_lapack(lib):
             assert abs(lo2 - lo) <= 1e-13 * ref[-1] and abs(hi2 - hi) <= 1e-13 * ref[-1], j
         prev = (lo, hi)
     assert lib.nss_tridiag_extremes(None, None, 3, None, None) != 0 and b"tridiag_extremes" in lib.nss_last_error()
+
+
+def _struct_mirrors():
+    """C name -> ctypes mirror of every state struct the host fills in and passes by pointer."""
+    from hipla import eigen, fused
+    return {"nss_bpcg2_t": fused.Bpcg2State, "nss_minres_t": fused.MinresState, "nss_bpcg1_t": fused.Bpcg1State,
+            "nss_cg_t": fused.CgState, "nss_lanczos_t": eigen._LanczosState.get(), "nss_halo_t": fused.HaloStruct}
+
+
+def test_ctypes_state_mirrors_match_the_header(tmp_path):
+    """The library reads the loop states through the header's layout, the host writes them through the ctypes mirrors:
+    compile a C program against include/nss_krylov.h that prints sizeof / offsetof / field size of every field the
+    mirror names, and compare field by field.  A field missing from the header fails to compile; one missing from the
+    mirror, or of another width, moves an offset or the size."""
+    import shutil
+    import subprocess
+    cc = next((c for c in (os.environ.get("CC"), "cc", "gcc", "clang") if c and shutil.which(c)), None)
+    if cc is None:
+        pytest.skip("no C compiler")
+    mirrors = _struct_mirrors()
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "nss_krylov.h"', "int main(void) {"]
+    for cname, mirror in mirrors.items():
+        lines.append('  printf("%s - %%zu %%zu\\n", sizeof(%s), _Alignof(%s));' % (cname, cname, cname))
+        for fname, _ in mirror._fields_:
+            lines.append('  printf("%s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));'
+                         % (cname, fname, cname, fname, cname, fname))
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                   check=True, capture_output=True, text=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
+    got = {(c, f): (int(a), int(b)) for c, f, a, b in (line.split() for line in out if line)}
+    for cname, mirror in mirrors.items():
+        assert got[(cname, "-")] == (ctypes.sizeof(mirror), ctypes.alignment(mirror)), cname
+        for fname, ftype in mirror._fields_:
+            desc = getattr(mirror, fname)
+            assert got[(cname, fname)] == (desc.offset, desc.size), (cname, fname)
+            assert desc.size == ctypes.sizeof(ftype), (cname, fname)
+    # the state structs end with the plan generation and the capacities of the partials (plan-sharing guard)
+    for cname in ("nss_bpcg2_t", "nss_minres_t", "nss_bpcg1_t", "nss_cg_t", "nss_lanczos_t"):
+        names = [f for f, _ in mirrors[cname]._fields_]
+        assert "plan_gen" in names and "cap_a" in names and "cap_b" in names, cname

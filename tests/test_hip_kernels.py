@@ -505,3 +505,97 @@ def test_csr_transpose_native(hip_engine):
         assert np.max(np.abs(out.numpy() - ref)) <= RTOL * (np.abs(m.T) @ np.abs(y) + 1e-300).max()
         t_host = T.to_scipy()
         assert abs(t_host - m.T).max() == 0 if m.nnz else True
+
+
+def _blocks_leaving_dofs_uncovered(case):
+    """(system, blocks as lists of dofs, uncovered dofs): Gauss-Seidel blocks that leave some velocity dofs in no
+    block -- the situation of blocks built from free dofs only."""
+    if case == "line3_free_dofs":           # line blocks without the ones touching the west wall
+        s = mac_stokes(2, 24)
+        idx = s.line_blocks(3)
+        west = np.concatenate([g[..., 0].ravel() for g in s.component_ids])
+        idx = idx[:, ~np.isin(idx, west).any(axis=0)]
+        blocks = [list(b[b >= 0]) for b in idx.T]
+    elif case == "ragged_10pc_uncovered":   # random ragged blocks, about 10 % of the dofs in none
+        s = mac_stokes(2, 14)
+        rng = np.random.default_rng(7)
+        perm = rng.permutation(s.n_u)[s.n_u // 10:]
+        cuts = np.sort(rng.choice(np.arange(1, perm.size), size=perm.size // 3, replace=False))
+        blocks = [list(b) for b in np.split(perm, cuts) if len(b) <= 16]
+    else:                                   # 3-D facet blocks, a random fifth of them dropped
+        s = mac_stokes(3, 6)
+        idx = s.facet_blocks()
+        keep = np.random.default_rng(11).random(idx.shape[1]) >= 0.2
+        blocks = [list(b[b >= 0]) for b in idx[:, keep].T]
+    covered = np.zeros(s.n_u, dtype=bool)
+    for b in blocks:
+        covered[b] = True
+    return s, blocks, np.flatnonzero(~covered)
+
+
+@pytest.mark.parametrize("case", ["line3_free_dofs", "ragged_10pc_uncovered", "facet_3d_dropped"])
+def test_block_gauss_seidel_keeps_the_coupling_to_uncovered_dofs(hip_engine, case):
+    """Sweeps over blocks that leave dofs uncovered, from an iterate that is NOT zero there (the state of y in the
+    multiplicative MypreA after `y += M r`, templates/NavierStokesSIMPLE_iterative.py:380-381): the sequential sweep
+    of the oracle reads A(block, uncovered) y and leaves y unchanged at the uncovered dofs.  Colour-major layout
+    (the uncovered dofs are trailing columns of P A P^T) and the rows layout against the oracle to 1e-12 and against
+    each other bit for bit; the full MypreA with a middle operator; Luby colours in their own order."""
+    import hipla
+    from oracle import krylov_ref as kr
+    s, blocks, unc = _blocks_leaving_dofs_uncovered(case)
+    assert unc.size > 0 and unc.size < s.n_u // 4, unc.size
+    A = hipla.SparseMatrix.from_scipy(s.A)
+    G = hipla.BlockGaussSeidel(A, blocks)
+    assert G.layout == "colour-major" and G.ncolors >= 2 and G.n_uncovered == unc.size
+    rng = np.random.default_rng(5)
+    x, y0 = rng.standard_normal(s.n_u), rng.standard_normal(s.n_u)
+    assert np.abs(y0[unc]).min() > 0
+    X = hipla.Vector.from_numpy(x)
+    # the coupling matters here: dropping it would move the sweep by far more than the tolerance
+    y_cut = y0.copy()
+    y_cut[unc] = 0.0
+    ref_f = kr.block_gauss_seidel_sweep(s.A, G.idx_host, x, y0)
+    cut = kr.block_gauss_seidel_sweep(s.A, G.idx_host, x, y_cut)
+    cut[unc] = y0[unc]
+    assert relerr(cut, ref_f) > 1e-6
+    Y = hipla.Vector.from_numpy(y0)
+    G.Smooth(Y, X)
+    assert relerr(Y.numpy(), ref_f) < 1e-12
+    np.testing.assert_array_equal(Y.numpy()[unc], y0[unc])
+    G.SmoothBack(Y, X)
+    ref_b = kr.block_gauss_seidel_sweep(s.A, G.idx_host, x, ref_f, backward=True)
+    assert relerr(Y.numpy(), ref_b) < 1e-12
+    np.testing.assert_array_equal(Y.numpy()[unc], y0[unc])
+    # the symmetric operator starts from y = 0 and leaves 0 at the uncovered dofs
+    out = hipla.Vector.from_numpy(y0)
+    G.Mult(X, out)
+    assert relerr(out.numpy(), kr.symmetric_block_gauss_seidel(s.A, G.idx_host)(x)) < 1e-12
+    assert not out.numpy()[unc].any()
+    # rows layout, same colours: same bits
+    R = hipla.BlockGaussSeidel(A, blocks, colors=G.colors, layout="rows")
+    assert R.layout == "rows" and np.array_equal(R.idx_host, G.idx_host)
+    for op in ("Smooth", "SmoothBack", "Mult"):
+        ya, yb = hipla.Vector.from_numpy(y0), hipla.Vector.from_numpy(y0)
+        if op == "Mult":
+            G.Mult(X, ya), R.Mult(X, yb)
+        else:
+            getattr(G, op)(ya, X), getattr(R, op)(yb, X)
+        np.testing.assert_array_equal(ya.numpy(), yb.numpy())
+    # MypreA with GS=True: y = 0; Smooth; r = x - A y; y += M r; SmoothBack -- M a random SPD operator, so that the
+    # back sweep starts from an iterate that is non-zero at the uncovered dofs
+    S = sp.random(s.n_u, s.n_u, density=3.0 / s.n_u, random_state=np.random.RandomState(2), format="csr")
+    M = (S @ S.T + sp.diags(0.5 + rng.random(s.n_u))).tocsr()
+    M.sort_indices()
+    for layout in ("colour-major", "rows"):
+        GM = hipla.BlockGaussSeidel(A, blocks, colors=G.colors, layout=layout, middle=hipla.SparseMatrix.from_scipy(M))
+        got = hipla.Vector(s.n_u)
+        GM.Mult(X, got)
+        want = kr.mypre_a(s.A, GM.idx_host, lambda r: M @ r, gs=True)(x)
+        assert relerr(got.numpy(), want) < 1e-12, layout
+    # another proper colouring against ITS sequential order
+    L = hipla.BlockGaussSeidel(A, blocks, coloring_method="luby")
+    assert L.coloring_method == "luby"
+    yl = hipla.Vector.from_numpy(y0)
+    L.Smooth(yl, X)
+    assert relerr(yl.numpy(), kr.block_gauss_seidel_sweep(s.A, L.idx_host, x, y0)) < 1e-12
+    np.testing.assert_array_equal(yl.numpy()[unc], y0[unc])

@@ -1681,3 +1681,59 @@ def test_fused_cg_solver(hip_engine):
     x, errors = heat.conjugate_gradients_fused(M, rhs, tol=1e-10)
     assert len(errors) - 1 == int(d["cg_iterations"])
     np.testing.assert_allclose(errors, d["cg_history"], rtol=1e-8)
+
+
+def test_multiplicative_mypre_a_over_blocks_with_uncovered_dofs(hip_engine):
+    """BPCG v2 with the multiplicative MypreA (GS=True, templates/NavierStokesSIMPLE_iterative.py:376-381) over blocks
+    that leave velocity dofs uncovered (line blocks without the ones at the west wall, as blocks of free dofs only
+    are): after `y += aux r` the back sweep starts from an iterate that is non-zero at those dofs, and it must read
+    their coupling to the blocks.  The fused loop runs; history, iteration count and solution against kr.bpcg_v2 with
+    kr.mypre_a (sequential sweeps in the GPU's colour-major block order, the GPU's auxiliary term as a black box)."""
+    import hipla
+    from solvers.bramblepasciak_new import BpcgSession, BramblePasciakCG
+    from templates.NavierStokesSIMPLE_iterative import MypreA, auxiliary_space_preconditioner
+    s = mac_stokes(2, 16, 0.01)
+    idx = s.line_blocks(3)
+    west = np.concatenate([g[..., 0].ravel() for g in s.component_ids])
+    blocks = np.ascontiguousarray(idx[:, ~np.isin(idx, west).any(axis=0)])
+    f, g = s.rhs(0)
+    A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
+    _, _, aux = auxiliary_space_preconditioner(s)
+    preA = MypreA(None, Form(A), blocks, GS=True, aux=aux)
+    assert preA.n_uncovered > 0
+    preS = hipla.DiagonalMatrix(1.0 / s.mass)
+    fv, gv = hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g)
+    tol, maxsteps = 1e-9, 2000
+
+    def aux_apply(r):
+        y = hipla.Vector(s.n_u)
+        aux.Mult(hipla.Vector.from_numpy(r), y)
+        return y.numpy()
+
+    pa, ps = kr.mypre_a(s.A, preA.idx_host, aux_apply, gs=True), kr.diag_inverse(s.mass)
+    with contextlib.redirect_stdout(io.StringIO()):
+        ses = BpcgSession(Form(A), Form(B), None, fv, gv, preA, preS)
+    assert ses.fused is not None
+    k = kr.scale_factor(kr.lanczos_ritz(s.A, pa, tol=1e-3))
+    assert abs(k - ses.k) < 1e-8 * k
+    out = io.StringIO()
+    sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
+    with contextlib.redirect_stdout(out), fused_loops_counted() as counts:
+        it, _ = BramblePasciakCG(Form(A), Form(B), None, fv, gv, preA, preS, sol, tol=tol, maxsteps=maxsteps)
+    assert counts["bpcg2"] == 1, "the fused device loop did not run: %r" % (counts,)
+    hist = np.array([float(m) for m in re.findall(r"it =\s+\d+\s+err =\s+(\S+)", out.getvalue())])
+    it_ref, u_ref, p_ref, hist_ref, _ = kr.bpcg_v2(s.A, s.B, pa, ps, f, g, k, tol=tol, maxsteps=maxsteps)
+    w = min(20, len(hist), len(hist_ref))
+    np.testing.assert_allclose(hist[:w], hist_ref[:w], rtol=1e-8)
+    # the band of the other MypreA solver test (test_auxiliary_space_mypre_a_native_in_the_fused_loop): the oracle's
+    # sweeps solve the blocks with LAPACK, the GPU with packed inverses -- ~300 iterations drift by a few percent
+    assert abs(it - it_ref) <= max(3, int(0.05 * it_ref))
+    x_ref = np.concatenate([u_ref, p_ref])
+    assert np.linalg.norm(sol.numpy() - x_ref) < 1e-5 * np.linalg.norm(x_ref)
+    # (no bound on the saddle-point residual here: the uncovered dofs are reached by the auxiliary term only, and the
+    # stop test on the preconditioned functional fires with a true residual of ~10 % -- on the oracle's side as well,
+    # which is what this test pins)
+    b, K = np.concatenate([f, g]), s.saddle_matrix()
+    r, r_ref = np.linalg.norm(b - K @ sol.numpy()), np.linalg.norm(b - K @ x_ref)
+    assert abs(r - r_ref) < 1e-3 * r_ref + 1e-6 * np.linalg.norm(b)
+    assert 3 < it < 400

@@ -33,12 +33,9 @@ for name in (sys.argv[1:] or ["cfg2", "cfg3"]):
         for i in range(3):
             st.v[i] = vecs[i].data_ptr()
         st.z[0], st.z[1], st.p = vecs[3].data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr()
-        na, nb = C.c_int64(), C.c_int64()
-        eng._check(eng.lib.nss_lanczos_workspace(C.byref(st), C.byref(na), C.byref(nb)))
-        pa_, pb_ = eng.zeros(max(1, na.value)), eng.zeros(max(1, nb.value))
+        partials = fused.fit_partials(eng, st, eng.lib.nss_lanczos_workspace, ("A",))   # noqa: F841 (kept alive)
         scal, ctrl, hist = eng.zeros(8), torch.zeros(4, dtype=torch.int32, device=eng.device), eng.zeros(2 * 1000)
-        st.partials_a, st.partials_b, st.scal, st.ctrl, st.hist = (pa_.data_ptr(), pb_.data_ptr(), scal.data_ptr(),
-                                                                    ctrl.data_ptr(), hist.data_ptr())
+        st.scal, st.ctrl, st.hist = scal.data_ptr(), ctrl.data_ptr(), hist.data_ptr()
         eng._check(eng.lib.nss_lanczos_start(C.byref(st), eng.stream))
         eng._check(eng.lib.nss_lanczos_iterate(C.byref(st), 0, 50, eng.stream))
         torch.cuda.synchronize()
