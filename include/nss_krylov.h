@@ -247,6 +247,17 @@ NSS_API int nss_bjac_set_colors(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors,
  * same order as the two-launch form: same bits. */
 NSS_API int nss_bjac_set_colors_permuted(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors, const int32_t* h_color_ptr,
                                          const int32_t* h_color_rowptr, const int32_t* h_rowdof, const int32_t* h_ridx);
+/* Statically condensed form whose multiplicative MypreA sweeps over the Schur complement S (nss_bpcg2_t.sweep_A):
+ * attach the operators the fused BPCG loop folds into this handle's colour-major sweep (its entry, middle and exit).
+ * HT, H, inner, S: the loop's cond_HT, cond_H, cond_inner, sweep_A (the loop uses the attachment only for exactly
+ * these); HT_perm = P H^T (the rows of H^T at the block dofs in the colour-major row order, n_perm x n, original
+ * columns); H_perm = the rows of H at the dofs outside every block (ascending, n_uncovered rows) with columns renamed
+ * into the permuted numbering (n_perm + max(1, n_uncovered) columns); h_inner_diag[i] = the diagonal of A_ii^-1 at
+ * the i-th dof outside every block.  The caller checks the structure first (hipla/fused.py: condensed_fusable): H^T
+ * rows and S rows / columns only at block dofs, A_ii^-1 diagonal and H rows only outside them, H columns only at
+ * block dofs -- and keeps HT_perm and H_perm alive.  HT_perm == NULL detaches; nss_bjac_set_colors* detach too. */
+NSS_API int nss_bjac_set_condensed(nss_bjac_t j, nss_csr_t HT, nss_csr_t H, nss_csr_t inner, nss_csr_t S,
+                                   nss_csr_t HT_perm, nss_csr_t H_perm, const double* h_inner_diag);
 /* one sweep: colours ascending (backward == 0) or descending */
 NSS_API int nss_bjac_smooth_f64(nss_bjac_t j, double xscale, const double* x, double* y, int32_t backward,
                                 nss_stream_t stream);
@@ -394,7 +405,28 @@ typedef struct nss_bpcg2_s {
    * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
   int64_t plan_gen;
   int64_t cap_a, cap_b, cap_c;
+  /* the matrix of the residual `x - A y` between the two sweeps of the multiplicative MypreA (:379) -- NULL: the loop's
+   * own A (the uncondensed form).  The statically condensed form with MypreA(GS=True) (the reference's
+   * SolveInitial(iterative=True): `condense=True`, :188, :364-391) sweeps over the Schur complement S = blfA.mat, so
+   * it sets sweep_A = S (n_u x n_u, interior rows and columns empty) while A is the explicit product.  Only then may
+   * a multiplicative preconditioner come with cond_HT.  The preconditioner step of K1 is then the sequence
+   *   f = t0 + H^T t0;  t1 = 0; Smooth(t1, k f);  t2 = k f - S t1;  t1 += aux t2;  SmoothBack(t1, k f);
+   *   t1 += H t1;  t1 += A_ii^-1 f
+   * -- the statements of harmonic_extension() around MypreA.Mult, in their order: the same bits as
+   * the same operators applied one by one. */
+  nss_csr_t sweep_A;
 } nss_bpcg2_t;
+/* Which form the condensed multiplicative preconditioner step of K1 takes (process-wide; hipla reads NSS_COND_FUSE
+ * at load).  1: the FUSED forms whenever pre_bjac carries this state's condensed operators
+ * (nss_bjac_set_condensed) -- lift into the sweep's gather over P H^T, residual over P S P^T in the permuted numbering
+ * that also scatters the forward sweep, the dofs outside the blocks in a short kernel of their own, a gather of the
+ * block rows only (the trailing columns, which P S P^T never reads, are skipped), and one launch over the rows of H
+ * outside the blocks that applies extension and inner solve and scatters the backward sweep.  0 (default: the fused
+ * forms measured no faster -- n = 96: 6 % slower per iteration, profiles/condensed_mypre_a.md): the straightforward
+ * sequence written above (lift, gather, colours, scatter, residual, cycle, gather, colours, scatter, extension, inner).
+ * The two forms form the same products but sum the extension and the inner solve in their own expressions: results
+ * agree to rounding, not bit for bit. */
+NSS_API int nss_cond_fuse_mode(int32_t mode);
 
 enum {
   NSS_BPCG2_K1 = 1,    /* t0 = (q recurrence) + B^T s1 [, t1 = k dinv t0]; block-Jacobi: t1 = k J t0 */
@@ -601,7 +633,7 @@ NSS_API int nss_cg_poll(const nss_cg_t* s, int32_t* done, int32_t* it_final, int
  * appends hist[2j] = delta_j, hist[2j+1] = gamma_{j+1}: T = tridiag(gamma_1.., delta_0.., gamma_1..); the host
  * reads them once per batch of steps and solves the small eigenproblem.
  * preA = pre_scale * (pre_amg + (pre_diag | pre_bjac)) as in nss_bpcg2_t (additive MypreA, :383), or -- pre_bjac in
- * Gauss-Seidel mode together with pre_amg -- the multiplicative MypreA (:376-381) with this A in its residual.
+ * Gauss-Seidel mode together with pre_amg -- the multiplicative MypreA (:376-381) with this A (or sweep_A) in its residual.
  * scal: double[8]; ctrl: int32[4] = { stop, j_stop (-1: gamma_0 == 0), last_j, - }: stop is set by the breakdown
  * test gamma_{j+1} <= 1e-14 max(|delta_0|, |delta_j|), after which every kernel returns at once. */
 typedef struct nss_lanczos_s {
@@ -623,6 +655,10 @@ typedef struct nss_lanczos_s {
    * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
   int64_t plan_gen;
   int64_t cap_a, cap_b;
+  /* the matrix of the multiplicative preconditioner's residual `x - A y` (:379) -- NULL: this A.  The condensed form
+   * runs the Lanczos of its scale factor on the explicit product (I - H^T)(S + A_ii)(I - H) with MypreA over the
+   * Schur complement: sweep_A = S (n x n). */
+  nss_csr_t sweep_A;
 } nss_lanczos_t;
 NSS_API int nss_lanczos_workspace(const nss_lanczos_t* s, int64_t* partials_a, int64_t* partials_b);
 /* out[i] = the start vector's entry of global index offset + i (hipla/eigen.py::lanczos_start_values: a hash of the

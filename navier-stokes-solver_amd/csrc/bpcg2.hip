@@ -191,6 +191,90 @@ struct EpiAddGuarded {
   __device__ void finish(int, double*) const {}
 };
 
+// ---- fused condensed forms (multiplicative MypreA over the Schur complement; nss_bjac_set_condensed) ----------------
+// Structure the host checked when it attached the operators (hipla/fused.py: condensed_fusable): H^T has rows only at
+// block dofs, S has rows and columns only at block dofs, A_ii^-1 is diagonal with rows only at the dofs outside every
+// block, H has rows only there and columns only at block dofs.  Then the lifted vector equals t0 outside the blocks,
+// A_ii^-1 f = A_ii^-1 t0, and the trailing columns of P S P^T are never read: nothing gathers them.
+// Lift into the gather: xt[r] = t0[d] + (H^T t0)[d] (d = rowdof[r]) over P H^T; the sweep starts from yt = 0 on the rows.
+struct EpiCondLift {
+  const int32_t* __restrict__ ctrl;
+  const int32_t* __restrict__ rowdof;
+  const double* __restrict__ t0;
+  double* __restrict__ xt;
+  double* __restrict__ yt;
+  __device__ bool skip() const { return ctrl[C_DONE] != 0; }
+  struct Pre { double t0 = 0.0; };
+  __device__ Pre fetch(int r) const { return Pre{t0[rowdof[r]]}; }
+  __device__ void row(int r, double ax, const Pre& p) const {
+    xt[r] = p.t0 + ax;
+    yt[r] = 0.0;
+  }
+  __device__ void finish(int, double*) const {}
+};
+
+// Residual in the permuted numbering over P S P^T with yt: r[d] = k xt[r] - (S y)[d] and t1[d] = yt[r] (the scatter of
+// the forward sweep) in the original numbering
+struct EpiCondResidual {
+  const int32_t* __restrict__ ctrl;
+  const int32_t* __restrict__ rowdof;
+  double k;
+  const double* __restrict__ xt;
+  const double* __restrict__ yt;
+  double* __restrict__ r;
+  double* __restrict__ y;
+  __device__ bool skip() const { return ctrl[C_DONE] != 0; }
+  struct Pre { double x = 0.0, y = 0.0; };
+  __device__ Pre fetch(int i) const { return Pre{xt[i], yt[i]}; }
+  __device__ void row(int i, double ay, const Pre& p) const {
+    const int d = rowdof[i];
+    r[d] = fma(k, p.x, -ay);
+    y[d] = p.y;
+  }
+  __device__ void finish(int, double*) const {}
+};
+
+// the dofs outside every block: the lifted vector is t0 + 0 there and S has empty rows, so r = k f - 0 and y = 0
+__global__ __launch_bounds__(kBlock) void bpcg2_cond_outside_kernel(const int32_t* __restrict__ ctrl, int32_t count,
+                                                                     const int32_t* __restrict__ dofs, double k,
+                                                                     const double* __restrict__ t0, double* __restrict__ r,
+                                                                     double* __restrict__ y) {
+  if (ctrl[C_DONE] != 0) return;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= count) return;
+  const int d = dofs[i];
+  r[d] = fma(k, t0[d] + 0.0, -0.0);
+  y[d] = 0.0;
+}
+
+// Leave with the extension, over the rows of H outside the blocks (columns in the permuted numbering, operand yt):
+// t1[d] = (y[d] (+ (H y)[d] when non-zero)) + A_ii^-1[d] f[d] at d = dofs[i]; and -- every workgroup a slice -- the
+// scatter t1[rowdof[r]] = yt[r] of the backward sweep.  The two sets of rows are disjoint.
+struct EpiCondLeave {
+  const int32_t* __restrict__ ctrl;
+  const int32_t* __restrict__ dofs;
+  const double* __restrict__ dinner;
+  const double* __restrict__ t0;
+  double* __restrict__ t1;
+  const int32_t* __restrict__ rowdof;
+  const double* __restrict__ yt;
+  int32_t n_perm;
+  __device__ bool skip() const { return ctrl[C_DONE] != 0; }
+  struct Pre { double y = 0.0, f = 0.0, a = 0.0; };
+  __device__ Pre fetch(int i) const {
+    const int d = dofs[i];
+    return Pre{t1[d], t0[d], dinner[i]};
+  }
+  __device__ void row(int i, double hy, const Pre& p) const {
+    const double y = hy != 0.0 ? p.y + hy : p.y;
+    t1[dofs[i]] = y + (0.0 + p.a * (p.f + 0.0));
+  }
+  __device__ void finish(int, double*) const {
+    const int stride = gridDim.x * kBlock;
+    for (int r = blockIdx.x * kBlock + threadIdx.x; r < n_perm; r += stride) t1[rowdof[r]] = yt[r];
+  }
+};
+
 // y = A x, frozen once the loop has stopped (ghost rows of B)
 struct EpiGuardedStore {
   const int32_t* __restrict__ ctrl;
@@ -768,10 +852,17 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
               "bpcg2: the row-partitioned AMG replaces pre_amg, takes no condensed form, and must match n_u");
   NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels[0].n == s->n_u, "bpcg2: AMG size mismatch");
   // AMG (or auxiliary-space) term + a block-Jacobi handle in Gauss-Seidel mode = the MULTIPLICATIVE MypreA
-  // (GS=True, :376-381): sweep, residual, correction, back sweep.  Not with the condensed form.
-  NSS_REQUIRE(!(s->pre_amg && s->pre_bjac && s->pre_bjac->gs_mat && (s->cond_HT || s->pre_diag)),
-              "bpcg2: the multiplicative preconditioner (Gauss-Seidel sweeps around an AMG term) takes neither a "
-              "condensed form nor a point-Jacobi part");
+  // (GS=True, :376-381): sweep, residual, correction, back sweep.  With the condensed form only when its residual is
+  // formed with the matrix of the sweeps (sweep_A = the Schur complement), not with the loop's explicit product.
+  const bool multiplicative = s->pre_amg && s->pre_bjac && s->pre_bjac->gs_mat;
+  NSS_REQUIRE(!(multiplicative && ((s->cond_HT && !s->sweep_A) || s->pre_diag)),
+              "bpcg2: the multiplicative preconditioner (Gauss-Seidel sweeps around an AMG term) takes no point-Jacobi "
+              "part, and a condensed form only with sweep_A (the matrix of its sweeps)");
+  NSS_REQUIRE(!s->sweep_A || (multiplicative && !s->pre_dist_aux && !s->pre_dist_amg && !s->dist_compact &&
+                              !s->local_sums && !s->ghost_mode),
+              "bpcg2: sweep_A serves the single-GPU multiplicative preconditioner only");
+  NSS_REQUIRE(!s->sweep_A || (s->sweep_A->m == s->n_u && s->sweep_A->n == s->n_u),
+              "bpcg2: sweep_A must be n_u x n_u");
   NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n_u, "bpcg2: block-Jacobi size mismatch");
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "bpcg2: NULL work buffer");
@@ -836,7 +927,45 @@ static void gs_forward_from_zero(const nss_bpcg2_t& s, const double* src, hipStr
   bjac_smooth(*s.pre_bjac, s.k, src, s.t1, false, s.ctrl, st);
 }
 
+// Which form of the condensed multiplicative preconditioner step K1 runs (nss_cond_fuse_mode, NSS_COND_FUSE):
+// 1 the fused forms whenever the sweep's handle carries the condensed operators of this state, 0 (default) the
+// straightforward sequence: interleaved same-box A/B, 3-D grid, n = 48 -1.5 % per iteration with the fused forms (within
+// the spread), n = 96 +6 % (profiles/condensed_mypre_a.md) -- kept off, as NSS_DISPATCH_PLANES.
+static int g_cond_fuse_mode = 0;
+
+static bool cond_fused(const nss_bpcg2_t& s) {
+  const nss_bjac_s* j = s.pre_bjac;
+  return g_cond_fuse_mode == 1 && s.cond_HT && s.sweep_A && s.pre_amg && j && j->gs_permuted && j->cond_HTp &&
+         j->cond_key_HT == s.cond_HT && j->cond_key_H == s.cond_H && j->cond_key_inner == s.cond_inner &&
+         j->cond_key_S == s.sweep_A && j->n == s.n_u && j->n_uncovered > 0 && j->cond_Hp;
+}
+
+// harmonic_extension() around the multiplicative MypreA in the sweep's own numbering: lift into the gather, forward
+// colours, residual + scatter, the dofs outside the blocks, auxiliary cycle, gather of the rows, backward colours,
+// scatter + extension + inner solve.  8 + colours + cycle launches instead of 11 + colours + cycle, and no pass over the
+// trailing columns.
+static void bpcg2_cond_fused_step(const nss_bpcg2_t& s, hipStream_t st) {
+  const nss_bjac_s& j = *s.pre_bjac;
+  launch_csr_stream(*j.cond_HTp, s.t0, EpiCondLift{s.ctrl, j.rowdof, s.t0, j.xt, j.yt}, st);
+  bjac_sweep_permuted(j, s.k, false, s.ctrl, st, true);
+  launch_csr_stream(*j.gs_mat, j.yt, EpiCondResidual{s.ctrl, j.rowdof, s.k, j.xt, j.yt, s.t2, s.t1}, st);
+  if (j.n_uncovered > 0) {
+    hipLaunchKernelGGL(bpcg2_cond_outside_kernel, dim3((j.n_uncovered + kBlock - 1) / kBlock), dim3(kBlock), 0, st, s.ctrl,
+                       j.n_uncovered, j.covered, s.k, s.t0, s.t2, s.t1);
+    NSS_CHECK_LAUNCH();
+  }
+  amg_apply(*s.pre_amg, 1.0, s.t2, s.t1, st, s.ctrl, true);
+  bjac_gather_rows(j, s.t1, s.ctrl, st);
+  bjac_sweep_permuted(j, s.k, true, s.ctrl, st, false);
+  launch_csr_stream(*j.cond_Hp, j.yt,
+                    EpiCondLeave{s.ctrl, j.covered, j.cond_dinner, s.t0, s.t1, j.rowdof, j.yt, j.n_perm}, st);
+}
+
 void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st) {
+  if (cond_fused(s)) {
+    bpcg2_cond_fused_step(s, st);
+    return;
+  }
   const double* src = s.t0;
   if (s.cond_HT) {                                   // harmonic_extension(): lift the residual first
     launch_csr_stream(*s.cond_HT, s.t0, EpiLift{s.ctrl, s.t0, s.cond_f}, st);
@@ -864,8 +993,9 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st) {
     // multiplicative MypreA (GS=True, :376-381) applied to k * t0:
     //   y = 0; J.Smooth(y, x); r = x - A y; y += M r; J.SmoothBack(y, x)        (t2 is free here: the
     //   previous iteration's t2 was consumed by K1 / C1 and the A-SpMV has not written the new one yet)
+    //   (condensed form: src = the lifted t0, the residual with the matrix of the sweeps, S = sweep_A)
     gs_forward_from_zero(s, src, st);
-    launch_csr_stream(*s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
+    launch_csr_stream(s.sweep_A ? *s.sweep_A : *s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
     amg_apply(*s.pre_amg, 1.0, s.t2, s.t1, st, s.ctrl, true);
     bjac_smooth(*s.pre_bjac, s.k, src, s.t1, true, s.ctrl, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);   // (src again)
   } else if (s.pre_amg) {
@@ -1070,6 +1200,13 @@ int nss_bpcg2_c1_applies_preA(const nss_bpcg2_t* s, int32_t* yes) {
   return guarded([&] {
     NSS_REQUIRE(s && s->BT && yes, "bpcg2_c1_applies_preA: NULL argument");
     *yes = c1_applies_block_jacobi(*s) ? 1 : 0;
+  });
+}
+
+int nss_cond_fuse_mode(int32_t mode) {
+  return guarded([&] {
+    NSS_REQUIRE(mode == 0 || mode == 1, "cond_fuse_mode: 0 (straightforward sequence) or 1 (fused condensed forms)");
+    g_cond_fuse_mode = mode;
   });
 }
 

@@ -336,6 +336,9 @@ static void lz_check(const nss_lanczos_t* s) {
   NSS_REQUIRE(!(s->pre_diag && s->pre_bjac), "lanczos: pre_diag and pre_bjac are exclusive");
   NSS_REQUIRE(s->pre_diag || s->pre_bjac || s->pre_amg, "lanczos: no preconditioner");
   NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n, "lanczos: block preconditioner size mismatch");
+  NSS_REQUIRE(!s->sweep_A || (s->pre_amg && s->pre_bjac && s->pre_bjac->gs_mat),
+              "lanczos: sweep_A serves the multiplicative preconditioner only");
+  NSS_REQUIRE(!s->sweep_A || (s->sweep_A->m == s->n && s->sweep_A->n == s->n), "lanczos: sweep_A must be n x n");
   NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels.empty() || s->pre_amg->levels[0].n == s->n || s->pre_amg->T, "lanczos: AMG size mismatch");
   for (int i = 0; i < 3; ++i) NSS_REQUIRE(s->v[i] != nullptr, "lanczos: NULL vector");
   NSS_REQUIRE(s->z[0] && s->z[1] && s->p && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b,
@@ -360,7 +363,7 @@ static int lz_precondition(const nss_lanczos_t& s, const double* x, double* z, d
       NSS_HIP(hipMemsetAsync(z, 0, sizeof(double) * size_t(s.n), st));
       bjac_smooth(*s.pre_bjac, 1.0, x, z, false, done, st);
     }
-    launch_csr_stream(*s.A, z, EpiLzResidual{done, x, scratch}, st);
+    launch_csr_stream(s.sweep_A ? *s.sweep_A : *s.A, z, EpiLzResidual{done, x, scratch}, st);
     amg_apply(*s.pre_amg, 1.0, scratch, z, st, done, true);
     bjac_smooth(*s.pre_bjac, 1.0, x, z, true, done, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);
     if (s.pre_scale != 1.0) {

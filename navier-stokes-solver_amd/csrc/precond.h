@@ -39,6 +39,15 @@ struct nss_bjac_s {
   uint8_t* glen = nullptr;                // [n_perm] rows of its block
   double* ginv = nullptr;                 // [bs][n_perm]: ginv[k][r] = (A_bb^-1)(row r, k-th row of the block)
   double *xt = nullptr, *yt = nullptr;    // [n_perm + max(1, n_uncovered)]
+  // Statically condensed form whose MypreA sweeps over the Schur complement S (nss_bjac_set_condensed): the operators
+  // the fused BPCG loop folds into the sweep's entry, middle and exit (csrc/bpcg2.hip: the fused condensed forms).
+  // cond_key_* = the operators they were made from (the loop uses them only for exactly those); cond_HTp = P H^T (the
+  // rows of H^T at the block dofs in the colour-major numbering, original columns); cond_Hp = the rows of H at the
+  // dofs outside every block (in `covered` order) with columns renamed into the permuted numbering (n_perm +
+  // max(1, n_uncovered) columns); cond_dinner[i] = the diagonal of A_ii^-1 at covered[i].
+  const nss_csr_s *cond_key_HT = nullptr, *cond_key_H = nullptr, *cond_key_inner = nullptr, *cond_key_S = nullptr;
+  const nss_csr_s *cond_HTp = nullptr, *cond_Hp = nullptr;
+  double* cond_dinner = nullptr;
 };
 
 namespace nss {
@@ -68,5 +77,12 @@ void bjac_smooth(const nss_bjac_s& j, double xscale, const double* x, double* y,
                  hipStream_t st, int flags = 0);
 void bjac_symgs_apply(const nss_bjac_s& j, double xscale, const double* x, double* y, const int32_t* done,
                       hipStream_t st);
+// colour-major layout, for callers that fill / drain xt and yt themselves (the fused condensed forms of bpcg2.hip):
+// one sweep over the permuted copies as they stand (from_zero: yt holds zeros on the rows, the first colour is solved
+// without its pass over P A P^T), and the gather of y at the block dofs only (yt[r] = y[rowdof[r]], xt kept; the
+// trailing columns are not gathered -- for callers whose P A P^T has no entries in them)
+void bjac_sweep_permuted(const nss_bjac_s& j, double xscale, bool backward, const int32_t* done, hipStream_t st,
+                         bool from_zero);
+void bjac_gather_rows(const nss_bjac_s& j, const double* y, const int32_t* done, hipStream_t st);
 
 }  // namespace nss

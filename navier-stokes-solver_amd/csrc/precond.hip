@@ -373,6 +373,20 @@ static void gs_leave(const nss_bjac_s& j, double* y, const int32_t* done, hipStr
   NSS_CHECK_LAUNCH();
 }
 
+void bjac_sweep_permuted(const nss_bjac_s& j, double xscale, bool backward, const int32_t* done, hipStream_t st,
+                         bool from_zero) {
+  if (!j.gs_permuted) throw Error("bjac_sweep_permuted: not in the colour-major layout");
+  gs_sweep_permuted(j, xscale, backward, done, st, from_zero);
+}
+
+void bjac_gather_rows(const nss_bjac_s& j, const double* y, const int32_t* done, hipStream_t st) {
+  if (!j.gs_permuted) throw Error("bjac_gather_rows: not in the colour-major layout");
+  // n_unc = 0: rows only, and the one slot behind them (n_perm, allocated in every case) set to 0
+  hipLaunchKernelGGL(gs_enter_kernel, dim3(stream_grid(int64_t(j.n_perm) + 1, kBlock)), dim3(kBlock), 0, st, j.n_perm,
+                     j.rowdof, 0, (const int32_t*)nullptr, (const double*)nullptr, y, j.xt, j.yt, done);
+  NSS_CHECK_LAUNCH();
+}
+
 template <int BS>
 static void launch_bgs_solve(const nss_bjac_s& j, int c, double* y, const int32_t* done, hipStream_t st) {
   const int b0 = j.color_ptr[c], b1 = j.color_ptr[c + 1];
@@ -600,6 +614,7 @@ int nss_bjac_destroy(nss_bjac_t j) {
     (void)hipFree(j->ginv);
     (void)hipFree(j->xt);
     (void)hipFree(j->yt);
+    (void)hipFree(j->cond_dinner);
     delete j;
   });
 }
@@ -651,6 +666,7 @@ static void set_colors_common(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors, c
     NSS_HIP(hipMemcpy(j->ridx, h_ridx, sizeof(int32_t) * size_t(j->bs) * j->nblocks, hipMemcpyHostToDevice));
     j->gs_mat = a_perm;
     j->gs_permuted = false;
+    j->cond_HTp = j->cond_Hp = nullptr;                    // a new numbering drops the condensed operators
     j->color_ptr.assign(h_color_ptr, h_color_ptr + ncolors + 1);
     j->color_rowblk = crb;
     j->color_row.assign(h_color_rowptr, h_color_rowptr + ncolors + 1);
@@ -697,6 +713,7 @@ int nss_bjac_set_colors_permuted(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors
     j->gpos = j->glen = nullptr;
     j->ginv = j->xt = j->yt = nullptr;
     j->gs_permuted = false;
+    j->cond_HTp = j->cond_Hp = nullptr;                    // a new numbering drops the condensed operators
     NSS_HIP(hipMalloc(&j->gpos, std::max<size_t>(1, n_perm)));
     NSS_HIP(hipMalloc(&j->glen, std::max<size_t>(1, n_perm)));
     NSS_HIP(hipMalloc(&j->ginv, sizeof(double) * size_t(j->bs) * std::max<size_t>(1, n_perm)));
@@ -710,6 +727,35 @@ int nss_bjac_set_colors_permuted(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors
     NSS_HIP(hipDeviceSynchronize());
     j->n_perm = n_perm;
     j->gs_permuted = true;
+  });
+}
+
+int nss_bjac_set_condensed(nss_bjac_t j, nss_csr_t HT, nss_csr_t H, nss_csr_t inner, nss_csr_t S, nss_csr_t HT_perm,
+                           nss_csr_t H_perm, const double* h_inner_diag) {
+  return guarded([&] {
+    NSS_REQUIRE(j != nullptr, "bjac_set_condensed: NULL handle");
+    (void)hipFree(j->cond_dinner);
+    j->cond_dinner = nullptr;
+    j->cond_key_HT = j->cond_key_H = j->cond_key_inner = j->cond_key_S = nullptr;
+    j->cond_HTp = j->cond_Hp = nullptr;
+    if (!HT_perm) return;                                    // detach
+    NSS_REQUIRE(j->gs_permuted, "bjac_set_condensed: the handle must sweep in the colour-major layout");
+    NSS_REQUIRE(HT && H && inner && S && H_perm && (h_inner_diag || j->n_uncovered == 0), "bjac_set_condensed: NULL argument");
+    for (const nss_csr_s* m : {HT, H, inner, S})
+      NSS_REQUIRE(m->m == j->n && m->n == j->n, "bjac_set_condensed: H^T, H, A_ii^-1 and S must be n x n");
+    NSS_REQUIRE(HT_perm->m == j->n_perm && HT_perm->n == j->n, "bjac_set_condensed: P H^T must be n_perm x n");
+    NSS_REQUIRE(H_perm->m == j->n_uncovered && int64_t(H_perm->n) == int64_t(j->n_perm) + std::max(1, j->n_uncovered),
+                "bjac_set_condensed: the rows of H outside the blocks must be n_uncovered x (n_perm + max(1, n_uncovered))");
+    if (j->n_uncovered > 0) {
+      NSS_HIP(hipMalloc(&j->cond_dinner, sizeof(double) * size_t(j->n_uncovered)));
+      NSS_HIP(hipMemcpy(j->cond_dinner, h_inner_diag, sizeof(double) * size_t(j->n_uncovered), hipMemcpyHostToDevice));
+    }
+    j->cond_key_HT = HT;
+    j->cond_key_H = H;
+    j->cond_key_inner = inner;
+    j->cond_key_S = S;
+    j->cond_HTp = HT_perm;
+    j->cond_Hp = H_perm;
   });
 }
 

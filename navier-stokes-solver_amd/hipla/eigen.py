@@ -45,7 +45,8 @@ class _LanczosState:
                             + [("pre_scale", C.c_double), ("v", C.c_void_p * 3), ("z", C.c_void_p * 2), ("p", C.c_void_p),
                                ("scal", C.c_void_p), ("ctrl", C.c_void_p), ("hist", C.c_void_p),
                                ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("n", C.c_int32),
-                               ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64)])
+                               ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64),
+                               ("sweep_A", C.c_void_p)])
             cls._cls = LanczosState
         return cls._cls
 
@@ -60,11 +61,13 @@ def _mark(label):
         TRACE.append((label, time.perf_counter()))
 
 
-def _native_lanczos(mat, pre, start, tol, maxsteps, check_every):
+def _native_lanczos(mat, pre, start, tol, maxsteps, check_every, sweep_A=None):
     """The same recurrence resident on the device (csrc/lanczos.hip: nss_lanczos_*): per step an SpMV with the dot in
     its epilogue, one element-wise kernel, the preconditioner (+ dot) and two single-workgroup sums that also advance
     the scalars; the host reads the new (delta, gamma) pairs once per `check_every` steps.  Returns None when an
-    operand is not native to the HIP engine (the caller then runs the protocol recurrence)."""
+    operand is not native to the HIP engine (the caller then runs the protocol recurrence).  `sweep_A`: the matrix a
+    multiplicative MypreA sweeps over and forms its residual with when that is not `mat` (the condensed form: the
+    Schur complement, `mat` the explicit product)."""
     import ctypes as C
     from . import fused
     from .matrix import SparseMatrix
@@ -75,7 +78,10 @@ def _native_lanczos(mat, pre, start, tol, maxsteps, check_every):
     if getattr(eng, "name", "") != "hip-gfx950" or not hasattr(eng.lib, "nss_lanczos_iterate") or mat.height != mat.width:
         return None
     pa = fused.native_velocity_pre(pre)
-    if pa is None or (pa["multiplicative"] and pa["bjac"].mat is not mat):
+    if pa is None or (pa["multiplicative"] and pa["bjac"].mat is not (mat if sweep_A is None else sweep_A)):
+        return None
+    if sweep_A is not None and (not pa["multiplicative"] or not isinstance(sweep_A, SparseMatrix)
+                                or sweep_A.height != mat.height or sweep_A.width != mat.width):
         return None
     n = mat.height
     _mark("enter")
@@ -85,6 +91,7 @@ def _native_lanczos(mat, pre, start, tol, maxsteps, check_every):
     st.pre_bjac = pa["bjac"].handle.ptr if pa["bjac"] is not None else None
     st.pre_amg = pa["amg"].handle.ptr if pa["amg"] is not None else None
     st.pre_scale = float(pa["scale"])
+    st.sweep_A = sweep_A.handle.ptr if sweep_A is not None else None
     vecs = [eng.zeros(n) for _ in range(6)]
     eng.copy(start.buf, vecs[0])
     for i in range(3):
@@ -184,17 +191,24 @@ def _native_lanczos(mat, pre, start, tol, maxsteps, check_every):
     return ritz
 
 
-def lanczos_ritz(mat, pre, start, tol=1e-10, maxsteps=2000, check_every=5, dot=InnerProduct):
+def lanczos_ritz(mat, pre, start, tol=1e-10, maxsteps=2000, check_every=5, dot=InnerProduct, sweep_A=None, info=None):
     """Preconditioned Lanczos on ``mat`` with SPD (possibly range-restricted) ``pre``.
 
     r0 = start, z0 = pre r0, gamma0 = sqrt<z0,r0>; then for j = 0,1,..:
     p = mat z_j; delta_j = <p,z_j>; r_{j+1} = p - delta_j v_j - gamma_j v_{j-1};
     z_{j+1} = pre r_{j+1}; gamma_{j+1} = sqrt<z_{j+1}, r_{j+1}>.
     T = tridiag(gamma, delta, gamma); Ritz values = eig(T).  Stops when both
-    extreme Ritz values moved by < tol (relative) between two checks."""
+    extreme Ritz values moved by < tol (relative) between two checks.
+
+    `sweep_A` is passed to the native recurrence (see `_native_lanczos`; the protocol recurrence applies `pre` as
+    it is).  `info` (a dict) receives ``native``: whether the recurrence ran on the device-resident path."""
+    if info is not None:
+        info["native"] = False
     if dot is InnerProduct and getattr(start, "comm", None) is None:
-        native = _native_lanczos(mat, pre, start, tol, maxsteps, check_every)
+        native = _native_lanczos(mat, pre, start, tol, maxsteps, check_every, sweep_A)
         if native is not None:
+            if info is not None:
+                info["native"] = True
             return native
     v = start.CreateVector()
     v.data = start
@@ -242,11 +256,11 @@ def lanczos_ritz(mat, pre, start, tol=1e-10, maxsteps=2000, check_every=5, dot=I
     return ritz
 
 
-def EigenValues_Preconditioner(mat, pre, tol=1e-10, inner=InnerProduct):
+def EigenValues_Preconditioner(mat, pre, tol=1e-10, inner=InnerProduct, sweep_A=None, info=None):
     """Returns the Ritz values (ascending numpy array) of ``pre * mat``; callers use
     ``min``/``max`` (bramble_pasciak_cg.py:71,74).  ``inner`` is the (global) inner product;
     a row-partitioned operator exposes ``row_offset`` so that every rank fills its slice of
-    the same global start vector."""
+    the same global start vector.  `sweep_A`, `info`: see `lanczos_ritz`."""
     start = mat.CreateColVector()
     off = int(getattr(mat, "row_offset", 0))
 
@@ -263,4 +277,4 @@ def EigenValues_Preconditioner(mat, pre, tol=1e-10, inner=InnerProduct):
             off += len(c)
     else:
         fill(start, off)
-    return lanczos_ritz(mat, pre, start, tol=tol, dot=inner)
+    return lanczos_ritz(mat, pre, start, tol=tol, dot=inner, sweep_A=sweep_A, info=info)

@@ -39,7 +39,8 @@ class Bpcg2State(C.Structure):
                    ("ghost_t3", C.c_void_p), ("ghost_w1", C.c_void_p), ("ghost_minv", C.c_void_p),
                    ("local_sums", C.c_int32), ("pre_dist_amg", C.c_void_p), ("dist_compact", C.c_int32),
                    ("pre_dist_aux", C.c_void_p), ("p2p", C.c_void_p)]
-                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)])
+                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)]
+                + [("sweep_A", C.c_void_p)])
 
 
 class HaloStruct(C.Structure):
@@ -149,6 +150,72 @@ def _extension_is_in_place_safe(H):
     return not np.intersect1d(rows_with_entries, np.unique(col), assume_unique=True).size
 
 
+def condensed_fusable(bjac, condensed):
+    """Whether the fused condensed forms (csrc/bpcg2.hip, nss_cond_fuse_mode) hold for the multiplicative MypreA `bjac`
+    (a BlockGaussSeidel over S) and condensed = dict(HT, H, inner, S): (True, None) or (False, reason).  Structure
+    checked once, on the host: the sweep runs in the colour-major layout with dofs outside its blocks; H^T has rows only
+    at block dofs (the lifted vector is t0 outside them); S has rows and columns only at block dofs (its residual is
+    k f there, and P S P^T never reads its trailing columns); A_ii^-1 is diagonal with rows only outside the blocks
+    (A_ii^-1 f = A_ii^-1 t0); H has rows only outside the blocks and columns only at block dofs."""
+    if getattr(bjac, "layout", None) != "colour-major":
+        return False, "the sweep is not in the colour-major layout"
+    if bjac.mat is not condensed.get("S"):
+        return False, "the sweep is not over S"
+    n = bjac.n
+    inside = np.zeros(n, dtype=bool)
+    inside[bjac.idx_host[bjac.idx_host >= 0]] = True
+    if inside.all():
+        return False, "every dof is in a block"
+
+    def rows_cols(m):
+        rowptr, col, _ = m.host_csr()
+        return np.repeat(np.arange(m.height), np.diff(rowptr)), np.asarray(col)
+
+    r, c = rows_cols(condensed["HT"])
+    if not inside[r].all():
+        return False, "H^T has rows outside the blocks"
+    r, c = rows_cols(condensed["S"])
+    if not (inside[r].all() and inside[c].all()):
+        return False, "S has entries outside the blocks"
+    r, c = rows_cols(condensed["inner"])
+    if (r != c).any() or inside[r].any():
+        return False, "A_ii^-1 is not diagonal outside the blocks"
+    r, c = rows_cols(condensed["H"])
+    if inside[r].any() or not inside[c].all():
+        return False, "H does not map block dofs to the dofs outside the blocks"
+    return True, None
+
+
+def attach_condensed(bjac, condensed):
+    """Build P H^T and the rows of H outside the blocks in the sweep's numbering and attach them to its handle
+    (nss_bjac_set_condensed) when `condensed_fusable` holds.  Returns (attached, reason)."""
+    import scipy.sparse as sp
+    ok, why = condensed_fusable(bjac, condensed)
+    eng = bjac.engine
+    if not ok:
+        if hasattr(eng, "lib"):
+            eng._check(eng.lib.nss_bjac_set_condensed(bjac.handle.ptr, None, None, None, None, None, None, None))
+        return False, why
+    live = bjac.idx_host.T >= 0
+    rowdof = bjac.idx_host.T[live].astype(np.int64)                 # the sweep's permuted row order (BlockGaussSeidel)
+    n, n_perm = bjac.n, rowdof.size
+    outside = np.setdiff1d(np.arange(n, dtype=np.int64), rowdof)    # ascending: the handle's trailing order
+    colmap = np.empty(n, dtype=np.int64)
+    colmap[rowdof] = np.arange(n_perm)
+    colmap[outside] = n_perm + np.arange(outside.size)
+    HTp = SparseMatrix.from_scipy(condensed["HT"].to_scipy().tocsr()[rowdof], engine=eng)
+    Hrows = condensed["H"].to_scipy().tocsr()[outside].tocoo()
+    Hp = sp.csr_matrix((Hrows.data, (Hrows.row, colmap[Hrows.col])), shape=(outside.size, n_perm + max(1, outside.size)))
+    Hp.sort_indices()
+    Hp = SparseMatrix.from_scipy(Hp, engine=eng)
+    dinner = np.ascontiguousarray(condensed["inner"].to_scipy().diagonal()[outside], dtype=np.float64)
+    eng._check(eng.lib.nss_bjac_set_condensed(bjac.handle.ptr, condensed["HT"].handle.ptr, condensed["H"].handle.ptr,
+                                              condensed["inner"].handle.ptr, condensed["S"].handle.ptr, HTp.handle.ptr,
+                                              Hp.handle.ptr, dinner.ctypes.data))
+    bjac.cond_keep = (HTp, Hp)                                      # the handle points at them
+    return True, None
+
+
 def plan_stamp(eng, *mats):
     """Largest launch-plan generation (nss_csr_plan_generation) among raw ``nss_csr_t`` pointers (None skipped): what a
     loop state records in ``plan_gen`` when it sizes its dot partials.  A re-plan of a shared matrix
@@ -187,56 +254,85 @@ def _plain(v, n):
 class Bpcg2Loop:
     """Device-resident iteration of solvers/bramblepasciak_new.py:200-249."""
 
+    last_declined = None     # why the latest try_create returned None (one short string), None after a loop was made
+
     @classmethod
     def try_create(cls, matA, matB, matBT, preA_unscaled, k, preM, vecs, distributed=False, condensed=None,
                    dist_amg=None, ghost_rows_b=0, dist_aux=None):
         """`distributed`: the matrices are the local row blocks of a partitioned run -- their
         column spaces carry halo entries behind the owned ones and t1 / t4 / s1 are the owned
-        views of halo-extended buffers (same base pointer).  `condensed`: dict(HT, H, inner) of
-        `SparseMatrix` for a statically condensed form (matA is then the explicit product).
+        views of halo-extended buffers (same base pointer).  `condensed`: dict(HT, H, inner[, S]) of
+        `SparseMatrix` for a statically condensed form (matA is then the explicit product; S = the Schur
+        complement, the matrix a multiplicative MypreA sweeps over and forms its residual with).
         `ghost_rows_b` > 0: matB carries that many ghost pressure rows behind the slab's own (the compact
-        partitioned plan, nss_bpcg2_t.dist_compact)."""
+        partitioned plan, nss_bpcg2_t.dist_compact).  Returns None when an operand is not native, with the
+        reason in ``Bpcg2Loop.last_declined``."""
+        out = cls._try_create(matA, matB, matBT, preA_unscaled, k, preM, vecs, distributed, condensed, dist_amg,
+                              ghost_rows_b, dist_aux)
+        if isinstance(out, str):
+            cls.last_declined = out
+            return None
+        cls.last_declined = None
+        return out
+
+    @classmethod
+    def _try_create(cls, matA, matB, matBT, preA_unscaled, k, preM, vecs, distributed=False, condensed=None,
+                    dist_amg=None, ghost_rows_b=0, dist_aux=None):
+        """The loop, or the reason (a string) why not."""
         if not (isinstance(matA, SparseMatrix) and isinstance(matB, SparseMatrix) and isinstance(matBT, SparseMatrix)):
-            return None
+            return "A, B or B^T is not a SparseMatrix"
         eng = matA.engine
-        if not ENABLED or not _hip(eng):
-            return None
+        if not ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not _hip(eng):
+            return "not the HIP engine"
         n_u, n_p = matA.height, matB.height - int(ghost_rows_b)
         if matBT.height != n_u or (ghost_rows_b and not distributed):
-            return None
+            return "B^T does not match A"
         if not distributed and (matA.width != n_u or matB.width != n_u or matBT.width != n_p):
-            return None
+            return "matrix shapes do not match"
         if distributed and (matA.width < n_u or matB.width < n_u or matBT.width < n_p):
-            return None
+            return "matrix shapes do not match"
         pm = native_diag(preM)
         if dist_aux is not None:     # row-partitioned auxiliary-space term [+ Jacobi part | around Gauss-Seidel sweeps]
             pa = native_velocity_pre(preA_unscaled) if preA_unscaled is not None else None
             if pa is None:
                 pa = {"scale": 1.0, "amg": None, "diag": None, "bjac": None, "multiplicative": False}
             if pa["amg"] is not None or pa["multiplicative"] or not distributed or dist_amg is not None:
-                return None
+                return "partitioned auxiliary term with another AMG term"
         elif dist_amg is not None:   # row-partitioned V-cycle (native handle) [+ an additive Jacobi part]
             pa = native_velocity_pre(preA_unscaled) if preA_unscaled is not None else None
             if pa is None:
                 pa = {"scale": 1.0, "amg": None, "diag": None, "bjac": None, "multiplicative": False}
             if pa["amg"] is not None or pa["multiplicative"] or not distributed:
-                return None
+                return "partitioned V-cycle with another AMG term"
         else:
             pa = native_velocity_pre(preA_unscaled)
-        if pm is None or pa is None:
-            return None
-        if pa["multiplicative"] and (condensed is not None or distributed or pa["bjac"].mat is not matA):
-            return None                  # the sweeps' residual is formed with the loop's own A
+        if pm is None:
+            return "preM is not a (scaled) diagonal"
+        if pa is None:
+            return "preA is not native"
+        if pa["multiplicative"]:
+            # the sweeps' residual is formed with the loop's own A -- or, condensed, with the Schur complement S
+            if distributed:
+                return "multiplicative preA on a partitioned run"
+            if condensed is None and pa["bjac"].mat is not matA:
+                return "multiplicative preA sweeps over another matrix than A"
+            if condensed is not None and (condensed.get("S") is None or pa["bjac"].mat is not condensed["S"]):
+                return "multiplicative and condensed: the sweeps are not over the Schur complement S"
         sizes = {"u0": n_u, "d0": n_u, "w0": n_u, "s0": n_u, "z0": n_u, "q": n_u, "t0": n_u, "t1": n_u,
                  "t2": n_u, "t4": n_u, "u1": n_p, "d1": n_p, "w1": n_p, "s1": n_p, "t3": n_p}
         if any(not _plain(vecs.get(name), n) for name, n in sizes.items()):
-            return None
+            return "a work vector is not a plain Vector of its size"
         if condensed is not None:
-            if distributed or any(not isinstance(condensed.get(key), SparseMatrix) or condensed[key].height != n_u
-                                  or condensed[key].width != n_u for key in ("HT", "H", "inner")):
-                return None
+            if distributed:
+                return "condensed form on a partitioned run"
+            keys = ("HT", "H", "inner") + (("S",) if condensed.get("S") is not None else ())
+            if any(not isinstance(condensed.get(key), SparseMatrix) or condensed[key].height != n_u
+                   or condensed[key].width != n_u for key in keys):
+                return "condensed operators are not n_u x n_u SparseMatrix"
             if not _extension_is_in_place_safe(condensed["H"]):
-                return None
+                return "harmonic extension H maps into its own columns"
         return cls(eng, matA, matB, matBT, pa, k, pm, vecs, condensed, distributed, dist_amg, n_p, dist_aux)
 
     def __init__(self, eng, matA, matB, matBT, pa, k, pm, vecs, condensed=None, distributed=False, dist_amg=None,
@@ -249,6 +345,12 @@ class Bpcg2Loop:
             self.cond_f = eng.zeros(matA.height)
             st.cond_HT, st.cond_H = condensed["HT"].handle.ptr, condensed["H"].handle.ptr
             st.cond_inner, st.cond_f = condensed["inner"].handle.ptr, self.cond_f.data_ptr()
+            if pa["multiplicative"]:
+                st.sweep_A = condensed["S"].handle.ptr      # the residual between the sweeps: x - S y
+                # the fused condensed forms (nss_cond_fuse_mode) when the structure allows them: operators attached to
+                # the sweep's handle, kept alive with the loop; otherwise the straightforward sequence
+                self.cond_fusable, self.cond_fuse_declined = attach_condensed(pa["bjac"], condensed)
+                self.keep.append(pa["bjac"])
         # the rows of B multiply t1 - s0 (:212-213): with row blocks short enough both vectors are read from LDS copies
         self.pair_staged_b = (os.environ.get("NSS_PAIR_STAGE", "1") == "1" and hasattr(matB.handle, "plan_for_pairs")
                               and matB.handle.plan_for_pairs())

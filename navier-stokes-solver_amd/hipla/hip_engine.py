@@ -100,6 +100,8 @@ def _signatures():
         "nss_bjac_info": (C.c_int, [vp, c_i32_p, c_i32_p, c_i64_p, c_i64_p]),
         "nss_bjac_set_colors": (C.c_int, [vp, vp, i32, vp, vp, vp, vp]),
         "nss_bjac_set_colors_permuted": (C.c_int, [vp, vp, i32, vp, vp, vp, vp]),
+        "nss_bjac_set_condensed": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "nss_cond_fuse_mode": (C.c_int, [i32]),
         "nss_csr_create_cuts": (C.c_int, [i32, i32, i64, vp, vp, vp, i32, vp, C.POINTER(vp)]),
         "nss_bjac_smooth_f64": (C.c_int, [vp, dbl, vp, vp, i32, vp]),
         "nss_bjac_symgs_apply_f64": (C.c_int, [vp, dbl, vp, vp, vp]),
@@ -164,6 +166,8 @@ def load_library(path=None):
         fn.argtypes = args
     if os.environ.get("NSS_STREAM_LOADS") and hasattr(lib, "nss_stream_loads_mode"):     # measurements: -1 / 0 / 1
         lib.nss_stream_loads_mode(int(os.environ["NSS_STREAM_LOADS"]))
+    if os.environ.get("NSS_COND_FUSE") and hasattr(lib, "nss_cond_fuse_mode"):           # measurements: 0 / 1
+        lib.nss_cond_fuse_mode(int(os.environ["NSS_COND_FUSE"]))
     if os.environ.get("NSS_DISPATCH_PLANES") and hasattr(lib, "nss_csr_dispatch_mode"):   # measurements: -1 / 0 / T
         lib.nss_csr_dispatch_mode(int(os.environ["NSS_DISPATCH_PLANES"]), int(os.environ.get("NSS_DISPATCH_MIN_PERIOD", "0")),
                                   int(os.environ.get("NSS_DISPATCH_RUN", "0")))

@@ -8,14 +8,16 @@ Execution paths (both on the GPU): the fused device-resident loop behind the C A
 epilogues, alpha / beta / stop test stay on the device) when every operand is native;
 otherwise the operator protocol, statement for statement.
 
-Scope: the plain branch of ``harmonic_extension`` (:20) is the hot path.  The
-static-condensation branch (``blfA.condense``: :11-18, ``myAmatrix`` :84-103) is kept
-behind the same interface through the protocol but needs element-block operators from FE
-assembly."""
+Scope: both branches of ``harmonic_extension`` run in the fused loop.  The static-condensation
+branch (``blfA.condense``: :11-18, ``myAmatrix`` :84-103) multiplies with the explicit product
+(I - H^T)(S + A_ii)(I - H) and applies lift, preconditioner and extension natively -- with a
+Jacobi / block-Jacobi preA, or with the multiplicative MypreA over the Schur complement S
+(SURVEY.md section 8f row N2)."""
 
 from math import sqrt
 
 from hipla import BaseMatrix, BlockVector, IdentityMatrix, InnerProduct
+from hipla import fused
 from hipla.fused import Bpcg2Loop
 from hipla.la import EigenValues_Preconditioner
 from hipla.ngstd import Timer
@@ -91,7 +93,9 @@ class BpcgSession:
     """Everything the reference computes before its loop (solvers/bramblepasciak_new.py:105-198):
     scale factor, transformed right-hand side, initial defect ``d``, preconditioned residual
     ``w``, search direction ``s`` and ``wdn = <w,d>``.  ``fused`` is the device-resident loop
-    when the operands are native, else ``None``."""
+    when the operands are native, else ``None``; ``fused_declined`` says why not (one short string, ``None``
+    when the loop is fused).  ``lanczos_native``: whether the scale factor's Lanczos ran device-resident
+    (False also when ``k`` was given)."""
 
     def __init__(self, blfA, blfB, matC, f, g, preA_unscaled, preM, sol=None, initialize=True, k=None,
                  inner=InnerProduct, workspace=None):
@@ -108,10 +112,24 @@ class BpcgSession:
 
         self.timer_prep = Timer("BPCG-Preparation")
         self.timer_prep.Start()
+        # condensed form with the multiplicative MypreA over the Schur complement (the reference's default,
+        # templates/NavierStokesSIMPLE_iterative.py:188,364-391): the explicit product serves the Lanczos of k and
+        # the fused loop, both forming the sweeps' residual with S.  Every other combination keeps its k path.
+        explicit = lanczos_mat = lanczos_sweep = None
+        if matC is None and blfA.condense and fused.ENABLED:      # (the protocol path keeps the composite operator)
+            pa = fused.native_velocity_pre(preA_unscaled)
+            if pa is not None and pa["multiplicative"] and pa["bjac"].mat is blfA.mat:
+                explicit = _explicit_condensed_matrix(blfA)
+                if explicit is not None:
+                    lanczos_mat, lanczos_sweep = explicit, blfA.mat
+        self.lanczos_native = False
         if k is None:
             timer_prepev = Timer("BPCG-Preparation-EV")
             timer_prepev.Start()
-            lams = EigenValues_Preconditioner(mat=matA, pre=preA_unscaled, tol=1e-3, inner=inner)
+            info = {}
+            lams = EigenValues_Preconditioner(mat=matA if lanczos_mat is None else lanczos_mat, pre=preA_unscaled,
+                                              tol=1e-3, inner=inner, sweep_A=lanczos_sweep, info=info)
+            self.lanczos_native = bool(info.get("native", False))
             timer_prepev.Stop()
             k = 1. / min(lams) + 1e-3                   # :118
             print("condition", max(lams) / min(lams))
@@ -171,15 +189,22 @@ class BpcgSession:
         self.fused = None
         vecs = dict(u0=u[0], u1=u[1], d0=d[0], d1=d[1], w0=w[0], w1=w[1], s0=s[0], s1=s[1], z0=z[0],
                     q=self.As0, t0=t0, t1=t1, t2=t2, t3=t3, t4=t4)
-        if matC is None and not blfA.condense:
+        if matC is not None:
+            self.fused_declined = "matC is given (stabilised saddle point): no fused loop"
+        elif not blfA.condense:
             self.fused = Bpcg2Loop.try_create(matA, matB, self.matBT, preA_unscaled, k, preM, vecs)
-        elif matC is None:
-            explicit = _explicit_condensed_matrix(blfA)
-            if explicit is not None:
+            self.fused_declined = Bpcg2Loop.last_declined
+        else:
+            if explicit is None:
+                explicit = _explicit_condensed_matrix(blfA)
+            if explicit is None:
+                self.fused_declined = "condensed operators are not native (no explicit product)"
+            else:
                 self.fused = Bpcg2Loop.try_create(
                     explicit, matB, self.matBT, preA_unscaled, k, preM, vecs,
                     condensed=dict(HT=blfA.harmonic_extension_trans, H=blfA.harmonic_extension,
-                                   inner=blfA.inner_solve))
+                                   inner=blfA.inner_solve, S=blfA.mat))
+                self.fused_declined = Bpcg2Loop.last_declined
 
     def first_direction(self):
         """A s0 and z0 of iteration 0 (:202-203); the fused loop starts from these."""

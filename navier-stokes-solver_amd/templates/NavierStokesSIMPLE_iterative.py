@@ -36,10 +36,10 @@ import scipy.sparse as sp
 
 import hipla
 from hipla import BlockVector, CGSolver
-from discretizations import AssembledForm, SyntheticMesh, assemble, bdm_hybrid
+from discretizations import AssembledForm, CondensedForm, SyntheticMesh, assemble, bdm_hybrid
 from solvers.bramblepasciak_new import BramblePasciakCG
 
-__all__ = ["NavierStokes", "SyntheticMesh", "MypreA"]
+__all__ = ["NavierStokes", "SyntheticMesh", "MypreA", "coupling_blocks"]
 
 
 class ConvectionOperator(hipla.BaseMatrix):
@@ -122,6 +122,16 @@ def MypreA(space, a, jacblocks, GS, aux=None):
     return op if aux is None else aux + op
 
 
+def coupling_blocks(blocks, interior):
+    """The blocks (bs, nblocks; -1 = padding) restricted to the coupling dofs -- the ``FreeDofs(True)`` of a
+    condensed form (:360-362): interior entries become padding, padding last, blocks left empty are dropped."""
+    idx = np.array(blocks, dtype=np.int64, copy=True)
+    idx[(idx >= 0) & np.asarray(interior)[np.maximum(idx, 0)]] = -1
+    order = np.argsort(idx < 0, axis=0, kind="stable")  # padding last, the dofs of a block in their order
+    idx = np.take_along_axis(idx, order, axis=0)
+    return np.ascontiguousarray(idx[:, (idx >= 0).any(axis=0)], dtype=np.int32)
+
+
 class NavierStokes:
     def __init__(self, mesh, nu, inflow, outflow, wall, uin, timestep, order=2, volumeforce=None):
         self.mesh, self.nu, self.timestep, self.order = mesh, nu, timestep, order
@@ -174,10 +184,13 @@ class NavierStokes:
         return out
 
     def SolveInitial(self, timesteps=None, iterative=True, GS=True, tol=1e-10, maxsteps=100000, printrates=False,
-                     aux=True, amg=False):
+                     aux=True, amg=False, condense=False):
         """`aux`: build the auxiliary-space term of MypreA (:208-357) -- the reference always does; False
         keeps the block smoother alone.  `amg=True` (kept from round 1) puts a smoothed-aggregation
-        V-cycle on a.mat itself in the place of the auxiliary term."""
+        V-cycle on a.mat itself in the place of the auxiliary term.  `condense=True` solves as the reference's
+        default does (:188, ``condense=True, store_inner=True``): blfA is the statically condensed form, MypreA
+        sweeps over its Schur complement with blocks of coupling dofs only (:360-362), and BramblePasciakCG runs
+        the condensed branch of harmonic_extension."""
         if timesteps:                                     # pseudo time stepping to the Stokes state (:406-417)
             ops = self._time_stepping_operators()
             self.Project(self.gfu)
@@ -193,7 +206,14 @@ class NavierStokes:
             return
         if not iterative:
             raise NotImplementedError("sparse direct initial solve is not on the Krylov path")
-        blfA = AssembledForm(self.a.mat)
+        if condense and amg:
+            raise ValueError("SolveInitial: amg=True (a V-cycle on a.mat) does not combine with condense=True")
+        blocks = self.system.facet_blocks()
+        if condense:
+            blfA = CondensedForm(self.system)
+            blocks = coupling_blocks(blocks, blfA.interior)
+        else:
+            blfA = AssembledForm(self.a.mat)
         blfB = AssembledForm(self.b.mat)
         preM = hipla.Preconditioner(self.mp, "local")
         middle = None
@@ -201,7 +221,7 @@ class NavierStokes:
             middle = hipla.SmoothedAggregationAMG(blfA.mat)
         elif aux:
             self.transform, self.preAh1, middle = auxiliary_space_preconditioner(self.system)
-        preA = MypreA(self.V, blfA, self.system.facet_blocks(), GS=GS, aux=middle)
+        preA = self.preA = MypreA(self.V, blfA, blocks, GS=GS, aux=middle)
         sol = BlockVector([self.gfu, self.gfup])       # aliases the grid-function storage (:206)
         out = BramblePasciakCG(blfA, blfB, None, self.f.vec, self.g.vec, preA, preM, sol, initialize=False,
                                tol=tol, maxsteps=maxsteps, rel_err=True, printrates=printrates)
