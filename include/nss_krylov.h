@@ -520,6 +520,12 @@ typedef struct nss_dist_s* nss_dist_t;
  * the librccl already loaded in the process and creates its communication stream and events. */
 NSS_API int nss_dist_create(void* nccl_comm, int32_t nranks, int32_t rank, nss_dist_t* out);
 NSS_API int nss_dist_destroy(nss_dist_t d);
+/* A statically condensed form on slabs (nss_bpcg2_t.cond_* with dist_compact): the preconditioner step of C1,
+ * t1 = (I + E) preA (I + E^T) t0 + A_ii^-1 (I + E^T) t0, exchanges t0 over `lift` before the lift (E^T's owned coupling
+ * rows read t0 at ghost interior dofs) and the preconditioned vector over `ext` before the extension (E's owned interior
+ * rows read it at ghost coupling dofs).  Both halos are in the layout of A's operand; lift->ext must be t0, ext->ext
+ * t1.  The handle keeps copies of the descriptors (their host tables must outlive it).  NULL, NULL: none. */
+NSS_API int nss_dist_set_condensed(nss_dist_t d, const nss_halo_t* lift, const nss_halo_t* ext);
 /* iterations [it_begin, it_end) of the partitioned loop: per iteration 3 halo exchanges, the
  * phases of nss_bpcg2_phase split into interior / boundary row blocks, 2 all-reduces.
  * overlap: 0 = exchange then multiply on `stream`; 1 = interior rows overlap the exchange;
@@ -575,7 +581,11 @@ NSS_API int nss_p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const ns
 NSS_API int nss_p2p_connect(nss_p2p_t p, const void* h_blobs);
 NSS_API int nss_p2p_destroy(nss_p2p_t p);
 NSS_API int nss_p2p_allreduce_f64(nss_p2p_t p, const double* src, double* dst, nss_stream_t stream);
-NSS_API int nss_p2p_exchange(nss_p2p_t p, const nss_halo_t* halo, nss_stream_t stream);
+/* `channel`: the index of the halo's layout in nss_p2p_create's list.  The sequence number and the channel's exchange
+ * count advance on every call -- also where this rank's halo on the channel is empty -- so that every rank numbers its
+ * collectives alike; nss_p2p_counters reads them (seq, and the count of the first max_channels channels). */
+NSS_API int nss_p2p_exchange(nss_p2p_t p, int32_t channel, const nss_halo_t* halo, nss_stream_t stream);
+NSS_API int nss_p2p_counters(nss_p2p_t p, int64_t* seq, int32_t max_channels, int64_t* counts, int32_t* n_channels);
 NSS_API int nss_p2p_error(nss_p2p_t p, int32_t* timed_out, nss_stream_t stream);
 /* every exchange and every one-double all-reduce of the native loops that take this dist handle (MINRES, BPCG v1, the
  * eight-phase BPCG v2 plan) goes through the mailbox transport instead of RCCL (NULL detaches); BPCG v2 on the compact

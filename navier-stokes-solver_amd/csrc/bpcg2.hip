@@ -834,7 +834,9 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
     NSS_REQUIRE(s->ghost_map == nullptr && s->ghost_s0 == s->s0 + s->n_u && s->ghost_w0 == s->w0 + s->n_u &&
                     s->ghost_w1 == s->w1 + s->n_p && s->ghost_t3 == s->t3 + s->n_p && (s->ghost_p_n == 0 || s->ghost_minv),
                 "bpcg2: compact partitioned plan: ghost copies must sit behind the owned entries of s0, w0, w1, t3");
-    NSS_REQUIRE(!s->cond_HT, "bpcg2: compact partitioned plan takes no condensed form");
+    // a condensed form on slabs: E^T, E (and A_ii^-1) have the slab's rows and columns in the layout of A's operand
+    NSS_REQUIRE(!s->cond_HT || (s->cond_HT->n == s->A->n && s->cond_H->n == s->A->n && s->cond_inner->n <= s->A->n),
+                "bpcg2: compact partitioned plan: the condensed operators must have the columns of A's operand [owned | ghosts]");
     NSS_REQUIRE(!s->p2p || s->p2p->connected, "bpcg2: the mailbox transport is not connected");
   } else if (s->p2p) {
     throw Error("bpcg2: the mailbox transport (p2p) serves the compact partitioned plan only");
@@ -843,8 +845,11 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
   }
   NSS_REQUIRE(!(s->pre_diag && s->pre_bjac), "bpcg2: pre_diag and pre_bjac are exclusive");
   NSS_REQUIRE(s->pre_diag || s->pre_bjac || s->pre_amg || s->pre_dist_amg || s->pre_dist_aux, "bpcg2: no preconditioner for the velocity block");
-  NSS_REQUIRE(!s->pre_dist_aux || (!s->pre_amg && !s->pre_dist_amg && !s->cond_HT && s->pre_dist_aux->n_u == s->n_u),
-              "bpcg2: the row-partitioned auxiliary-space term replaces pre_amg / pre_dist_amg, takes no condensed form, and must match n_u");
+  NSS_REQUIRE(!s->pre_dist_aux || (!s->pre_amg && !s->pre_dist_amg && s->pre_dist_aux->n_u == s->n_u),
+              "bpcg2: the row-partitioned auxiliary-space term replaces pre_amg / pre_dist_amg and must match n_u");
+  NSS_REQUIRE(!s->pre_dist_aux || !s->cond_HT || (s->pre_bjac && s->pre_bjac->gs_mat && s->sweep_A && s->dist_compact),
+              "bpcg2: the row-partitioned auxiliary-space term takes a condensed form only in the multiplicative MypreA "
+              "over the slab rows of S (sweep_A) on the compact plan");
   NSS_REQUIRE(!s->pre_dist_aux || !(s->pre_bjac && s->pre_bjac->gs_mat) ||
                   (s->pre_dist_aux->has_halo_y && s->pre_dist_aux->halo_y.ext == s->t1),
               "bpcg2: the multiplicative partitioned MypreA needs the halo of t1 (nss_dist_aux_create: halo_y)");
@@ -858,11 +863,16 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
   NSS_REQUIRE(!(multiplicative && ((s->cond_HT && !s->sweep_A) || s->pre_diag)),
               "bpcg2: the multiplicative preconditioner (Gauss-Seidel sweeps around an AMG term) takes no point-Jacobi "
               "part, and a condensed form only with sweep_A (the matrix of its sweeps)");
+  const bool slab_multiplicative = s->pre_dist_aux && s->pre_bjac && s->pre_bjac->gs_mat;
   NSS_REQUIRE(!s->sweep_A || (multiplicative && !s->pre_dist_aux && !s->pre_dist_amg && !s->dist_compact &&
-                              !s->local_sums && !s->ghost_mode),
-              "bpcg2: sweep_A serves the single-GPU multiplicative preconditioner only");
-  NSS_REQUIRE(!s->sweep_A || (s->sweep_A->m == s->n_u && s->sweep_A->n == s->n_u),
-              "bpcg2: sweep_A must be n_u x n_u");
+                              !s->local_sums && !s->ghost_mode) ||
+                  (slab_multiplicative && s->cond_HT && s->dist_compact && !s->pre_amg && !s->pre_dist_amg),
+              "bpcg2: sweep_A serves the multiplicative preconditioner on one GPU, or on slabs the condensed one on the "
+              "compact plan");
+  NSS_REQUIRE(!s->sweep_A || (s->sweep_A->m == s->n_u && s->sweep_A->n == (s->dist_compact ? s->A->n : s->n_u)),
+              "bpcg2: sweep_A must have the rows and the operand layout of A");
+  NSS_REQUIRE(!s->cond_HT || !s->local_sums || s->dist_compact,
+              "bpcg2: a condensed form on slabs runs on the compact partitioned plan only");
   NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n_u, "bpcg2: block-Jacobi size mismatch");
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "bpcg2: NULL work buffer");
@@ -876,8 +886,11 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
   const bool cond = s->cond_HT || s->cond_H || s->cond_inner || s->cond_f;
   if (cond) {
     NSS_REQUIRE(s->cond_HT && s->cond_H && s->cond_inner && s->cond_f, "bpcg2: condensed form needs H^T, H, A_ii^-1 and a work vector");
-    for (const nss_csr_s* m : {s->cond_HT, s->cond_H, s->cond_inner})
-      NSS_REQUIRE(m->m == s->n_u && m->n == s->n_u, "bpcg2: condensed operators must be n_u x n_u");
+    const int32_t width = s->dist_compact ? s->A->n : s->n_u;     // slabs: [owned | ghosts] of A's operand
+    for (const nss_csr_s* m : {s->cond_HT, s->cond_H})
+      NSS_REQUIRE(m->m == s->n_u && m->n == width, "bpcg2: condensed operators must be n_u x n_u (slabs: n_u x A's operand)");
+    NSS_REQUIRE(s->cond_inner->m == s->n_u && s->cond_inner->n >= s->n_u && s->cond_inner->n <= width,
+                "bpcg2: the inner solve must be n_u x n_u");
   }
   NSS_REQUIRE(s->u0 && s->u1 && s->d0 && s->d1 && s->w0 && s->w1 && s->s0 && s->s1 && s->z0 && s->q && s->t0 &&
                   s->t1 && s->t2 && s->t3 && s->t4,
@@ -961,13 +974,28 @@ static void bpcg2_cond_fused_step(const nss_bpcg2_t& s, hipStream_t st) {
                     EpiCondLeave{s.ctrl, j.covered, j.cond_dinner, s.t0, s.t1, j.rowdof, j.yt, j.n_perm}, st);
 }
 
-void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st) {
+// condensed form on slabs: make the ghost tail of a halo-extended operand current, through the mailbox transport when
+// the loop has one (`channel`: 1 the lift, 2 the extension; 0 is t1's), else over the communicator handle (RCCL)
+static void cond_exchange(const nss_bpcg2_t& s, const nss_dist_s& d, const nss_halo_t& h, int channel, hipStream_t st) {
+  if (s.p2p) p2p_exchange(*s.p2p, channel, h, s.ctrl, st);
+  else exchange(d, h, st);
+}
+
+void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st, const nss_dist_s* d) {
   if (cond_fused(s)) {
     bpcg2_cond_fused_step(s, st);
     return;
   }
+  // condensed form on slabs (compact plan): t1 = (I + E) preA (I + E^T) t0 + A_ii^-1 (I + E^T) t0 with two exchanges --
+  // t0 before the lift (E^T's owned coupling rows read t0 at ghost interior dofs), y = preA(...) before the extension
+  // (E's owned interior rows read y at ghost coupling dofs)
+  const bool cond_slab = s.cond_HT && s.dist_compact;
+  if (cond_slab)
+    NSS_REQUIRE(d && d->has_cond, "bpcg2: a condensed form on slabs needs the native loop with its halos "
+                                  "(nss_bpcg2_iterate_dist, nss_dist_set_condensed)");
   const double* src = s.t0;
   if (s.cond_HT) {                                   // harmonic_extension(): lift the residual first
+    if (cond_slab) cond_exchange(s, *d, d->cond_lift, 1, st);
     launch_csr_stream(*s.cond_HT, s.t0, EpiLift{s.ctrl, s.t0, s.cond_f}, st);
     src = s.cond_f;
   }
@@ -975,10 +1003,12 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st) {
   if (s.pre_dist_aux && s.pre_bjac && s.pre_bjac->gs_mat) {
     // multiplicative MypreA on slabs (GS=True, :376-381): the sweeps run inside the slab (additive across slabs), the
     // residual between them with the partitioned A (halo exchange of the iterate), the auxiliary-space term on slabs
+    //   (condensed form: with S's slab diagonal block, sweep_A -- the matrix of the sweeps, which keeps the preconditioner
+    //   symmetric; it reads owned entries only, so the iterate is not exchanged)
     const nss_dist_aux_s& aux = *s.pre_dist_aux;
     gs_forward_from_zero(s, src, st);
-    exchange(*aux.d, aux.halo_y, st);
-    launch_csr_stream(*s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
+    if (!(s.cond_HT && s.sweep_A)) exchange(*aux.d, aux.halo_y, st);
+    launch_csr_stream(s.sweep_A ? *s.sweep_A : *s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
     dist_aux_apply(aux, 1.0, s.t2, s.t1, true, st, s.ctrl);
     bjac_smooth(*s.pre_bjac, s.k, src, s.t1, true, s.ctrl, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);   // (src again)
   } else if (s.pre_dist_aux) {                        // additive MypreA on slabs (:383)
@@ -1008,6 +1038,7 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st) {
     diag(0.0);                                       // uncondensed: rides in K1's epilogue
   }
   if (s.cond_HT) {
+    if (cond_slab) cond_exchange(s, *d, d->cond_ext, 2, st);
     launch_csr_stream(*s.cond_H, s.t1, EpiExtendInPlace{s.ctrl, s.t1}, st);         // t1 += H t1
     launch_csr_stream(*s.cond_inner, s.cond_f, EpiAddGuarded{s.ctrl, s.t1}, st);    // t1 += A_ii^-1 f
   }
@@ -1080,7 +1111,7 @@ bool c1_applies_block_jacobi(const nss_bpcg2_t& s) {
          !s.cond_HT && s.BT->jb_first && s.BT->jb_serial == s.pre_bjac->serial && s.pre_bjac->inv_sym && s.pre_bjac->run;
 }
 
-void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st) {
+void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const nss_dist_s* d) {
   const bool fold = fold_sums(s);
   switch (which) {
     case NSS_BPCG2C_C1: {
@@ -1101,7 +1132,7 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st) {
       else if (fold) NSS_C1(true, false, launch_csr_stream);
       else NSS_C1(false, false, launch_csr_stream);
 #undef NSS_C1
-      if (!fj) bpcg2_k1_finish(s, st);
+      if (!fj) bpcg2_k1_finish(s, st, d);
       break;
     }
     case NSS_BPCG2C_C23: {

@@ -25,6 +25,12 @@ struct nss_dist_s {
   // mailbox transport (nss_dist_attach_p2p): exchange() and the one-double all-reduces of every native partitioned
   // loop go through peer-mapped memory instead of RCCL (csrc/p2p.h)
   struct nss_p2p_s* p2p = nullptr;
+  // condensed form on slabs (nss_dist_set_condensed): the halo of t0, read by the lift E^T t0 on the owned coupling
+  // rows, and of the preconditioned vector y (= t1 before the extension), read by E y on the owned interior rows --
+  // both in the layout of the loop's A operand
+  nss_halo_t cond_lift{};
+  nss_halo_t cond_ext{};
+  bool has_cond = false;
 };
 
 
@@ -78,7 +84,8 @@ constexpr int kNcclSum = 0;
 
 void nccl_check(const nss_dist_s& d, int rc, const char* what);
 void check_halo(const nss_halo_t* h, const nss_csr_s& mat, const char* name);
-// halo exchange of one or two SpMV operands (one grouped send/recv phase) on stream `st`
+// halo exchange of one or two SpMV operands (one grouped send/recv phase) on stream `st`; over the mailbox transport
+// (nss_dist_attach_p2p) the first goes through channel 0, the second through channel 1
 void exchange(const nss_dist_s& d, const nss_halo_t& h, hipStream_t st, const nss_halo_t* second = nullptr);
 // dst = sum over the ranks of src (n doubles, device); without a communicator (one rank) a copy
 void allreduce_sum(const nss_dist_s& d, const double* src, double* dst, size_t n, hipStream_t st);

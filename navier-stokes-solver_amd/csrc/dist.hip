@@ -79,12 +79,12 @@ void exchange(const nss_dist_s& d, const nss_halo_t& h, hipStream_t st, const ns
       any = true;
       if (!p->direct) gather_launch(p->n_pack, p->send_idx, p->ext, p->sendbuf, st);
     }
-  if (!any || d.nranks <= 1) return;
-  if (d.p2p) {                       // mailbox transport: put + wait/copy per operand layout
-    for (const nss_halo_t* p : hs)
-      if (p && (p->n_send > 0 || p->n_recv > 0)) p2p_exchange(*d.p2p, *p, nullptr, st);
+  if (d.p2p && d.nranks > 1) {       // mailbox transport: put + wait/copy per operand layout, channels 0 and 1 -- also
+    for (int c = 0; c < 2; ++c)      // where this rank's halo is empty (the sequence numbers advance on every rank)
+      if (hs[c]) p2p_exchange(*d.p2p, c, *hs[c], nullptr, st);
     return;
   }
+  if (!any || d.nranks <= 1) return;
   nccl_check(d, d.GroupStart(), "ncclGroupStart");
   for (const nss_halo_t* p : hs) {
     if (!p) continue;
@@ -350,6 +350,24 @@ int nss_dist_attach_p2p(nss_dist_t d, nss_p2p_t p) {
   });
 }
 
+int nss_dist_set_condensed(nss_dist_t d, const nss_halo_t* lift, const nss_halo_t* ext) {
+  return guarded([&] {
+    NSS_REQUIRE(d != nullptr, "dist_set_condensed: NULL dist handle");
+    NSS_REQUIRE((lift == nullptr) == (ext == nullptr), "dist_set_condensed: both halos or neither");
+    if (lift == nullptr) {
+      d->cond_lift = nss_halo_t{};
+      d->cond_ext = nss_halo_t{};
+      d->has_cond = false;
+      return;
+    }
+    NSS_REQUIRE(lift->ext && ext->ext && lift->ext != ext->ext,
+                "dist_set_condensed: the lift (t0) and the extension (t1) need their own operand buffers");
+    d->cond_lift = *lift;
+    d->cond_ext = *ext;
+    d->has_cond = true;
+  });
+}
+
 int nss_dist_destroy(nss_dist_t d) {
   return guarded([&] {
     if (!d) return;
@@ -406,6 +424,13 @@ int nss_bpcg2_iterate_dist(const nss_bpcg2_t* s, nss_dist_t d, const nss_halo_t*
       // C4 . sum . all-reduce -- six launches and three collectives (eight-phase form: nine launches).
       check_halo(halo_t1, *s->A, "halo_t1");
       NSS_REQUIRE(halo_t1->ext == s->t1, "iterate_dist: the halo buffer is not the loop's SpMV operand t1");
+      if (s->cond_HT) {              // condensed form on slabs: two more exchanges inside C1's preconditioner step
+        NSS_REQUIRE(d->has_cond, "iterate_dist: a condensed form on slabs needs its halos (nss_dist_set_condensed)");
+        check_halo(&d->cond_lift, *s->A, "cond_lift");
+        check_halo(&d->cond_ext, *s->A, "cond_ext");
+        NSS_REQUIRE(d->cond_lift.ext == s->t0 && d->cond_ext.ext == s->t1,
+                    "iterate_dist: the condensed halos must be those of t0 (lift) and t1 (extension)");
+      }
       hipStream_t cs = as_stream(stream);
       for (int it = it_begin; it < it_end; ++it) {
         hipEvent_t* ev = d->prof_iters < d->prof_cap ? &d->prof_ev[size_t(d->prof_iters) * kProfMarks] : nullptr;
@@ -413,9 +438,9 @@ int nss_bpcg2_iterate_dist(const nss_bpcg2_t* s, nss_dist_t d, const nss_halo_t*
           if (ev) NSS_HIP(hipEventRecord(ev[i], cs));
         };
         mark(0);
-        bpcg2_cphase(*s, NSS_BPCG2C_C1, it, cs);           // + preA
+        bpcg2_cphase(*s, NSS_BPCG2C_C1, it, cs, d);        // + preA (condensed: lift, preA, extension)
         mark(1);
-        if (s->p2p) p2p_exchange(*s->p2p, *halo_t1, s->ctrl, cs);   // put + wait/copy through the landing zone
+        if (s->p2p) p2p_exchange(*s->p2p, 0, *halo_t1, s->ctrl, cs);   // put + wait/copy through the landing zone
         else exchange(*d, *halo_t1, cs);
         mark(2);
         bpcg2_cphase(*s, NSS_BPCG2C_C23, it, cs);

@@ -98,12 +98,11 @@ struct nss_p2p_s {
   int32_t* d_error = nullptr;
   int32_t* d_ticket = nullptr;               // [kP2pMaxSegments] workgroup tickets of the put kernel
   uint32_t seq = 0;                          // host counter of collectives issued
-  // One CHANNEL per operand layout this handle serves (bound at creation): its arrival flags (one per source rank),
-  // its landing zone, the own receive table and, after connect, where the peers want our segments.  A halo descriptor
-  // finds its channel by the identity of its host tables (h_send_off / h_recv_off): the loops pass copies of ONE
-  // descriptor per layout with only `ext` changed.
+  // One CHANNEL per operand layout this handle serves (bound at creation, numbered in the order of nss_p2p_create's
+  // halos): its arrival flags (one per source rank), its landing zone, the own receive table and, after connect, where
+  // the peers want our segments.  Every exchange names its channel by that index -- not by the identity of the
+  // descriptor's host tables, which copies of one descriptor share and which an empty halo does not have (NULL).
   struct Channel {
-    const void *key_send = nullptr, *key_recv = nullptr;
     int32_t n_owned = 0;
     size_t flags_off = 0, landing_off = 0;   // byte offsets inside the own region (flags_off is the same in every region)
     int64_t landing_doubles = 0;
@@ -115,18 +114,15 @@ struct nss_p2p_s {
   };
   std::vector<Channel> channels;
   bool connected = false;
-  const Channel* find(const nss_halo_t& h) const {
-    for (const Channel& c : channels)
-      if (c.key_send == (const void*)h.h_send_off && c.key_recv == (const void*)h.h_recv_off) return &c;
-    return nullptr;
-  }
   nss::P2pView view(uint32_t s) const { return nss::P2pView{mail, d_peer_mail, nranks, rank, s, d_error}; }
 };
 
 namespace nss {
-// halo exchange of `h` (direct sends only; one of the layouts the handle was created for) through its landing zone:
-// put + wait/copy on stream `st`
-void p2p_exchange(nss_p2p_s& p, const nss_halo_t& h, const int32_t* done, hipStream_t st);
+// halo exchange of `h` (direct sends only) over channel `channel` (the index of its layout at creation) through that
+// channel's landing zone: put + wait/copy on stream `st`.  The sequence number and the channel's count advance on every
+// call, also when this rank's halo on the channel is empty: every rank issues the same exchanges, so the counters stay
+// the same on every rank whatever the neighbourhood.
+void p2p_exchange(nss_p2p_s& p, int channel, const nss_halo_t& h, const int32_t* done, hipStream_t st);
 // dst[0] = sum over the ranks of src[0], the ranks' values added in rank order (one small launch)
 void p2p_allreduce(nss_p2p_s& p, const double* src, double* dst, hipStream_t st);
 }  // namespace nss

@@ -74,15 +74,24 @@ __global__ __launch_bounds__(kBlock) void p2p_wait_copy_kernel(WaitArgs a) {
     a.dst[i] = __builtin_nontemporal_load(a.landing + i);         // fine-grained memory: not cached
 }
 
-void p2p_exchange(nss_p2p_s& p, const nss_halo_t& h, const int32_t* done, hipStream_t st) {
+void p2p_exchange(nss_p2p_s& p, int channel, const nss_halo_t& h, const int32_t* done, hipStream_t st) {
   if (!p.connected) throw Error("p2p: not connected");
-  if (h.n_send == 0 && h.n_recv == 0) return;                     // no neighbour (one rank)
+  if (channel < 0 || channel >= int(p.channels.size()))
+    throw Error("p2p: no such channel (the halo layout was not registered when the transport was created)");
   if (h.n_send > 0 && !h.direct) throw Error("p2p: the halo must send contiguous runs of the operand (direct)");
   if (h.n_send > kP2pMaxSegments || h.n_recv > kP2pMaxSegments) throw Error("p2p: too many neighbours");
-  const nss_p2p_s::Channel* ch = p.find(h);
-  if (!ch) throw Error("p2p: this halo layout was not registered when the transport was created");
+  const nss_p2p_s::Channel* ch = &p.channels[size_t(channel)];
+  for (int i = 0; i < h.n_recv; ++i) {              // the halo must have the receive layout the channel was made for
+    const int q = h.h_recv_peer[i];
+    if (q < 0 || q >= p.nranks || ch->recv_cnt[size_t(q)] != h.h_recv_cnt[i] ||
+        ch->recv_off[size_t(q)] != h.h_recv_off[i] - ch->n_owned)
+      throw Error("p2p: the halo's receive layout is not the one of channel " + std::to_string(channel));
+  }
+  // advanced before anything can return: a rank with an empty halo on this channel still takes part in the numbering
+  // (its neighbours' all-reduces and later exchanges carry the same sequence numbers)
   const uint32_t seq = ++p.seq;
   const size_t par = size_t(ch->count++ & 1u);                  // which of the two landing zones this exchange uses
+  if (h.n_send == 0 && h.n_recv == 0) return;                     // no neighbour on this channel (one rank)
   if (h.n_send > 0) {
     PutArgs a{};
     int wg = 0;
@@ -177,8 +186,6 @@ int nss_p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t
         NSS_REQUIRE(halo != nullptr, "p2p_create: NULL halo");
         NSS_REQUIRE(halo->direct || halo->n_send == 0, "p2p_create: the halos must send contiguous runs (direct)");
         nss_p2p_s::Channel ch;
-        ch.key_send = halo->h_send_off;
-        ch.key_recv = halo->h_recv_off;
         ch.n_owned = n_owned[c];
         ch.recv_off.assign(size_t(nranks), -1);
         ch.recv_cnt.assign(size_t(nranks), 0);
@@ -302,10 +309,19 @@ int nss_p2p_allreduce_f64(nss_p2p_t p, const double* src, double* dst, nss_strea
   });
 }
 
-int nss_p2p_exchange(nss_p2p_t p, const nss_halo_t* halo, nss_stream_t stream) {
+int nss_p2p_exchange(nss_p2p_t p, int32_t channel, const nss_halo_t* halo, nss_stream_t stream) {
   return guarded([&] {
     NSS_REQUIRE(p && halo, "p2p_exchange: NULL argument");
-    p2p_exchange(*p, *halo, nullptr, as_stream(stream));
+    p2p_exchange(*p, channel, *halo, nullptr, as_stream(stream));
+  });
+}
+
+int nss_p2p_counters(nss_p2p_t p, int64_t* seq, int32_t max_channels, int64_t* counts, int32_t* n_channels) {
+  return guarded([&] {
+    NSS_REQUIRE(p && seq && n_channels && max_channels >= 0 && (counts || max_channels == 0), "p2p_counters: bad argument");
+    *seq = int64_t(p->seq);
+    *n_channels = int32_t(p->channels.size());
+    for (int c = 0; c < max_channels && c < int(p->channels.size()); ++c) counts[c] = int64_t(p->channels[size_t(c)].count);
   });
 }
 

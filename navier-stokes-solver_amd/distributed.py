@@ -218,7 +218,17 @@ class MailboxTransport:
 
     def exchange(self, which=0):
         import ctypes as C
-        self.engine._check(self.engine.lib.nss_p2p_exchange(self.handle, C.byref(self._halos[which]), self.engine.stream))
+        self.engine._check(self.engine.lib.nss_p2p_exchange(self.handle, int(which), C.byref(self._halos[which]),
+                                                            self.engine.stream))
+
+    def counters(self):
+        """(sequence number, exchange count per channel) of the host-side bookkeeping: the same on every rank after the
+        same collectives."""
+        import ctypes as C
+        seq, nch = C.c_int64(), C.c_int32()
+        counts = (C.c_int64 * 4)()
+        self.engine._check(self.engine.lib.nss_p2p_counters(self.handle, C.byref(seq), 4, counts, C.byref(nch)))
+        return int(seq.value), [int(counts[c]) for c in range(nch.value)]
 
     def timed_out(self):
         import ctypes as C
@@ -611,11 +621,13 @@ class DistributedAuxiliary(BaseMatrix):
 class DistributedMypreA(BaseMatrix):
     """``MypreA.Mult`` (templates/NavierStokesSIMPLE_iterative.py:375-383) on slabs, protocol form: `gs` = the block
     smoother of the slab's diagonal block (sweeps inside the slab, additive across slabs), `aux` = `DistributedAuxiliary`.
-    GS=True: y = 0; Smooth; r = x - A y with the PARTITIONED A; y += aux r; SmoothBack.  GS=False: y = (aux + J) x."""
+    GS=True: y = 0; Smooth; r = x - A y with the PARTITIONED A (or with `res`: the condensed form passes S's slab
+    diagonal block, the matrix the sweeps run over); y += aux r; SmoothBack.  GS=False: y = (aux + J) x."""
 
-    def __init__(self, ops, gs, aux, GS=True):
+    def __init__(self, ops, gs, aux, GS=True, res=None):
         super().__init__()
         self.ops, self.gs, self.aux, self.GS = ops, gs, aux, GS
+        self.res = res if res is not None else ops.A
         self._res = ops.A.CreateColVector()
 
     def Height(self):
@@ -633,7 +645,7 @@ class DistributedMypreA(BaseMatrix):
         if self.GS:
             y[:] = 0.0                                   # :377
             self.gs.Smooth(y, x)                         # :378
-            self._res.data = x - self.ops.A * y          # :379
+            self._res.data = x - self.res * y            # :379
             y.data += self.aux * self._res               # :380
             self.gs.SmoothBack(y, x)                     # :381
         else:
@@ -646,19 +658,89 @@ class DistributedMypreA(BaseMatrix):
         return self
 
 
+def explicit_condensed_product(parts, engine):
+    """(I - E^T)(S + A_ii)(I - E) of the global condensation `parts` (`StokesSystem.condense`) as a scipy CSR: the
+    product the single-GPU fused loop multiplies with (`_explicit_condensed_matrix`, two sparse products of the engine),
+    so that the slabs of one rank carry the same bits -- not `sysm.A`, which equals it only up to rounding."""
+    import types
+    from hipla.matrix import SparseMatrix as SM
+    from solvers.bramblepasciak_new import _explicit_condensed_matrix
+    form = types.SimpleNamespace(**{name: SM.from_scipy(parts[key], engine=engine) for name, key in (
+        ("mat", "mat"), ("inner_matrix", "inner_matrix"), ("harmonic_extension", "harmonic_extension"),
+        ("harmonic_extension_trans", "harmonic_extension_trans"), ("inner_solve", "inner_solve"))})
+    prod = _explicit_condensed_matrix(form)
+    if prod is None:                    # (an engine without the sparse product)
+        eye = sp.identity(parts["mat"].shape[0], format="csr")
+        out = ((eye - parts["harmonic_extension_trans"]) @ (parts["mat"] + parts["inner_matrix"])
+               @ (eye - parts["harmonic_extension"])).tocsr()
+    else:
+        out = sp.csr_matrix(prod.to_scipy())
+    out.sort_indices()
+    return out
+
+
+class DistributedCondensedForm:
+    """A statically condensed form on slabs -- what `discretizations.CondensedForm` is on one GPU: ``.mat`` (the Schur
+    complement S), ``.inner_matrix`` (A_ii), ``.inner_solve`` (A_ii^-1), ``.harmonic_extension`` (E) and
+    ``.harmonic_extension_trans`` (E^T), each the rank's velocity rows as a `DistSparseMatrix` on the velocity slab
+    partition (E and E^T with a one-layer halo across the cut, A_ii^-1 diagonal without one); ``.explicit`` = the row
+    slab of the explicit product (I - E^T)(S + A_ii)(I - E) (the scale factor's Lanczos multiplies with it).  The
+    reference's `BramblePasciakCG` / `BpcgSession` run on it through the operator protocol, as on `Form(ops.A)`."""
+
+    def __init__(self, ops, parts):
+        eng, comm, vel = ops.engine, ops.comm, ops.vel
+        self.condense = True
+        self.interior = parts["interior"]
+        self.mat = DistSparseMatrix(parts["mat"], vel, vel, comm, eng)
+        self.inner_matrix = DistSparseMatrix(parts["inner_matrix"], vel, vel, comm, eng)
+        self.inner_solve = DistSparseMatrix(parts["inner_solve"], vel, vel, comm, eng)
+        self.harmonic_extension = DistSparseMatrix(parts["harmonic_extension"], vel, vel, comm, eng)
+        self.harmonic_extension_trans = DistSparseMatrix(parts["harmonic_extension_trans"], vel, vel, comm, eng)
+        self.explicit = ops.A
+
+    def native_operators(self, slab_block):
+        """dict(HT, H, inner, S) of `SparseMatrix`: the slab rows with the columns in the layout of the explicit
+        product's operand (A's operand: [owned | ghosts], which receives every ghost these read) -- what the native
+        condensed preconditioner step multiplies (`Bpcg2Loop`, condensed=...).  S is `slab_block` (scipy CSR), the slab
+        diagonal block of S the sweeps run over: the multiplicative MypreA forms its residual with it
+        (`DistributedStokes`)."""
+        A = self.explicit
+        width = A.n_cols_owned + A.plan.n_ghost
+        block = sp.csr_matrix((slab_block.data, slab_block.indices, slab_block.indptr), shape=(slab_block.shape[0], width))
+        return dict(HT=b_in_layout_of_a(A, self.harmonic_extension_trans, A.engine),
+                    H=b_in_layout_of_a(A, self.harmonic_extension, A.engine),
+                    inner=b_in_layout_of_a(A, self.inner_solve, A.engine),
+                    S=SparseMatrix.from_scipy(block, engine=A.engine), slab=True)
+
+
 class DistributedStokes:
     """The operands of the Stokes solve on this rank: A, B, B^T as `DistSparseMatrix`,
     block-Jacobi / Jacobi preA (or, `pre="amg"`, the `DistributedAMG` cycle) and lumped-mass preM
-    restricted to the slab."""
+    restricted to the slab.
 
-    def __init__(self, sysm, blocks, comm, engine=None, partition=None, pre=None, aux_options=None):
+    `condense=True`: the statically condensed form (`StokesSystem.condense(seed)`, global -- its interior set is a global
+    independent set): ``A`` is then the row slab of the explicit product (I - E^T)(S + A_ii)(I - E), ``form`` the
+    `DistributedCondensedForm`, and preA works on S: block Jacobi over S's slab diagonal block, or the Gauss-Seidel
+    sweeps over it ("bgs", "mypre_a" -- additive across slabs; MypreA forms its residual with the partitioned S), point
+    Jacobi of S (zero on the interior dofs) without blocks.  MypreA forms the residual between its sweeps with S's
+    slab diagonal block -- the matrix of the sweeps -- not with the partitioned S: only then is it symmetric (with the
+    full S it is not, and on 3-D n = 6 its scale factor comes out negative: -0.0067 on two slabs, the solve diverges).
+    With one slab the block is S, the single-GPU MypreA.  The blocks are restricted to the coupling dofs
+    (`coupling_blocks`): the interior dofs stay uncovered on purpose, ``n_uncovered`` counts them per slab."""
+
+    def __init__(self, sysm, blocks, comm, engine=None, partition=None, pre=None, aux_options=None, condense=False,
+                 seed=0):
         self.comm = comm
         self.engine = engine if engine is not None else get_engine()
         r, size = comm.rank, comm.size
         vel, prs = partition if partition is not None else sysm.partition(size)
         self.vel, self.prs = np.asarray(vel, dtype=np.int64), np.asarray(prs, dtype=np.int64)
         self.sysm = sysm
+        self.condense = bool(condense)
+        if self.condense and pre not in (None, "bjac", "bgs", "mypre_a"):
+            raise ValueError("condense=True takes pre in (None, 'bjac', 'bgs', 'mypre_a'), not %r" % (pre,))
         self.n_u, self.n_p = int(self.vel[r + 1] - self.vel[r]), int(self.prs[r + 1] - self.prs[r])
+        parts = sysm.condense(seed) if self.condense else None
         BT = sysm.B.T.tocsr()
         BT.sort_indices()
         # Ghost pressure cells of B^T's operand and the velocity dofs their rows of B touch: B's and A's
@@ -672,7 +754,15 @@ class DistributedStokes:
         self.B = DistSparseMatrix(sysm.B, self.prs, self.vel, comm, self.engine, extra_ghosts=extra_v)
         # A's operand also receives the ghost columns of B's operand: the fused loop then derives the
         # ghosts of t4 = t1 - s0 locally instead of exchanging them (nss_bpcg2_t.ghost_mode)
-        self.A = DistSparseMatrix(sysm.A, self.vel, self.vel, comm, self.engine, extra_ghosts=self.B.plan.ghosts)
+        extra_a, a_global = self.B.plan.ghosts, sysm.A
+        if self.condense:
+            # ... and (condensed) those of S, E and E^T: the native step reads them all in the layout of A's operand
+            a_global = explicit_condensed_product(parts, self.engine)
+            for key in ("mat", "harmonic_extension", "harmonic_extension_trans"):
+                extra_a = np.union1d(extra_a, localize_rows(parts[key], (v0g, v1g), self.vel, r)[1])
+        self.A = DistSparseMatrix(a_global, self.vel, self.vel, comm, self.engine, extra_ghosts=extra_a)
+        self.form = DistributedCondensedForm(self, parts) if self.condense else None
+        self.S = self.form.mat if self.condense else None
         # rows of B of the ghost pressure cells, columns in the layout of B's operand
         cols = rows_gp.indices.astype(np.int64)
         own = (cols >= v0g) & (cols < v1g)
@@ -693,11 +783,16 @@ class DistributedStokes:
         self.BT = DistSparseMatrix(BT, self.vel, self.prs, comm, self.engine)
         self.B.attach_transpose(self.BT)
         v0, v1 = int(self.vel[r]), int(self.vel[r + 1])
-        # block-Jacobi on the diagonal block of the slab (blocks never straddle slabs)
-        a_diag = sp.csr_matrix(sysm.A[v0:v1, v0:v1])
+        # block-Jacobi on the diagonal block of the slab (blocks never straddle slabs); condensed: of S's
+        a_diag = sp.csr_matrix((parts["mat"] if self.condense else sysm.A)[v0:v1, v0:v1])
         a_diag.sort_indices()
         self.A_diag = SparseMatrix.from_scipy(a_diag, engine=self.engine)
+        self.a_diag_scipy = a_diag
+        self.n_uncovered = 0
         if blocks is not None:
+            if self.condense:
+                from templates.NavierStokesSIMPLE_iterative import coupling_blocks
+                blocks = coupling_blocks(blocks, parts["interior"])
             blocks = np.asarray(blocks, dtype=np.int64)
             live = blocks >= 0
             first = np.where(live, blocks, np.int64(1) << 62).min(axis=0)
@@ -708,17 +803,33 @@ class DistributedStokes:
             loc = blocks[:, mine]
             loc = np.where(loc >= 0, loc - v0, -1).astype(np.int32)
             self.local_blocks = np.ascontiguousarray(loc)
+            covered = np.zeros(self.n_u, dtype=bool)
+            covered[loc[loc >= 0]] = True
+            self.n_uncovered = int(self.n_u - covered.sum())      # owned dofs outside every slab-local block
+            if self.condense and not np.array_equal(~covered, parts["interior"][v0:v1]):
+                raise RuntimeError("condensed blocks on the slab: the dofs outside every block must be exactly the "
+                                   "owned interior dofs")
             if pre in ("bgs", "mypre_a"):
                 # multicolour block Gauss-Seidel INSIDE the slab, additive across slabs (a "hybrid" sweep: no exchange
                 # inside a sweep; with one slab it is the single-GPU sweep).  Colours: first fit in block order on the
                 # slab's own block graph -- what the same colouring gives on the slab-block-diagonal global graph.
                 from hipla import BlockGaussSeidel
                 self.preA = BlockGaussSeidel(self.A_diag, self.local_blocks)
+                # dofs outside every block (the interior ones of a condensed form) must be what the colour-major layout
+                # keeps as trailing columns -- gathered from y, never updated -- so that the slab sweep couples to them
+                # as the single-GPU sweep does
+                if getattr(self.preA, "layout", None) == "colour-major" and \
+                        getattr(self.preA, "n_uncovered", self.n_uncovered) != self.n_uncovered:
+                    raise RuntimeError("slab sweep: the colour-major layout keeps %d trailing columns, the slab has %d "
+                                       "uncovered dofs" % (self.preA.n_uncovered, self.n_uncovered))
             else:
                 self.preA = BlockJacobi(self.A_diag, self.local_blocks)
         else:
             from hipla import JacobiPreconditioner
-            self.preA = JacobiPreconditioner(self.A_diag)
+            # condensed: S has empty rows at the interior dofs -- point Jacobi on the coupling dofs only (zero on the
+            # interior ones, `CondensedForm.jacobi`)
+            self.preA = (JacobiPreconditioner(self.A_diag, freedofs=~parts["interior"][v0:v1]) if self.condense
+                         else JacobiPreconditioner(self.A_diag))
         if pre == "amg":
             self.preA = DistributedAMG(sysm.A, self.A)
         self.gs = self.aux = None
@@ -728,7 +839,8 @@ class DistributedStokes:
                 raise ValueError("pre='mypre_a' needs the facet blocks")
             self.gs = self.preA
             self.aux = DistributedAuxiliary(self, **(aux_options or {}))
-            self.preA = DistributedMypreA(self, self.gs, self.aux, GS=True)
+            # condensed: the residual with the slab block of S the sweeps run over (symmetric; no exchange)
+            self.preA = DistributedMypreA(self, self.gs, self.aux, GS=True, res=self.A_diag if self.condense else None)
         p0, p1 = int(self.prs[r]), int(self.prs[r + 1])
         self.preM = DiagonalMatrix(1.0 / sysm.mass[p0:p1], engine=self.engine)
         self.inner = DistInner(comm)
@@ -815,7 +927,7 @@ class DistributedBpcg2:
                         ("cphases", ("C4", "SUMW")), ("allreduce", 2))
 
     def __init__(self, sysm, f, g, blocks, dist, engine=None, comm=None, quiet=True, native=True, pre=None, plan=None,
-                 aux_options=None, transport=None):
+                 aux_options=None, transport=None, condense=False, k=None, seed=0):
         """`native=False` keeps the Python-driven schedule even when `comm` is an `RcclComm` (its
         collectives are then single ctypes calls into librccl between the device phases).
         `pre="amg"`: preA = the V-cycle with replicated coarse levels (`DistributedAMG`), applied inside the
@@ -827,7 +939,12 @@ class DistributedBpcg2:
         them with the partitioned A; applied natively inside the loop (RCCL communicator, as `pre="amg"`).
         `plan`: "compact" (default; NSS_DIST_PLAN overrides) = C1 / preA / exchange / C23 / sum / all-reduce / C4 /
         sum / all-reduce with every ghost kept by recurrence behind the owned entries of its vector; "classic" = the
-        eight-phase form (the only one with the interior / boundary overlap)."""
+        eight-phase form (the only one with the interior / boundary overlap).
+        `condense=True`: the statically condensed saddle system (`DistributedStokes(condense=True)`; `seed` picks its
+        interior set) for `pre` in (None, "bjac", "bgs", "mypre_a"), on the compact plan, natively over RCCL or -- not
+        with "mypre_a" -- over the mailbox transport: C1's preconditioner step exchanges t0 before the lift and the
+        preconditioned vector before the extension.  `k`: the scale factor, skipping its Lanczos (tests pin it).
+        ``declined``: why no native loop was made (None when it was)."""
         import contextlib
         self.want_native = bool(native)
         self.want_transport = transport          # "mailbox": csrc/p2p.h instead of RCCL inside the iterations
@@ -836,8 +953,16 @@ class DistributedBpcg2:
         from solvers.bramblepasciak_new import BpcgSession
         self.engine = engine if engine is not None else get_engine()
         self.comm = comm if comm is not None else TorchComm(dist, self.engine)
+        self.condense = bool(condense)
+        self.declined = None
+        if self.condense and pre not in (None, "bjac", "bgs", "mypre_a"):
+            raise ValueError("condense=True takes pre in (None, 'bjac', 'bgs', 'mypre_a'), not %r" % (pre,))
+        if self.condense and pre == "mypre_a" and transport == "mailbox":
+            raise ValueError("condense=True with pre='mypre_a' runs over RCCL only: the auxiliary-space term on slabs "
+                             "has no mailbox transport")
         ops = self.ops = DistributedStokes(sysm, blocks, self.comm, self.engine,
-                                           pre=pre if pre in ("bgs", "mypre_a") else None, aux_options=aux_options)
+                                           pre=pre if pre in ("bgs", "mypre_a") else None, aux_options=aux_options,
+                                           condense=self.condense, seed=seed)
         self.dist_amg = None
         if pre in ("amg", "amg+bjac"):
             self.dist_amg = DistributedAMG(sysm.A, ops.A)
@@ -857,11 +982,16 @@ class DistributedBpcg2:
         workspace = dict(t1=self.t1, t4=self.t4, s1=self.s1)
         if self.compact:       # ghost copies behind the owned entries: s0, w0 like A's operand, w1, t3 like B^T's
             workspace.update(s0=ops.A.operand(), w0=ops.A.operand(), w1=ops.BT.operand(), t3=ops.BT.operand())
+            if self.condense:  # the lift reads t0 on the ghost interior dofs
+                workspace.update(t0=ops.A.operand())
         sink = io.StringIO() if quiet or self.comm.rank != 0 else None
         with (contextlib.redirect_stdout(sink) if sink is not None else contextlib.nullcontext()):
-            ses = BpcgSession(Form(ops.A), Form(ops.B), None, fv, gv, ops.preA, ops.preM, sol=self.sol,
-                              initialize=True, inner=ops.inner, workspace=workspace)
+            ses = BpcgSession(ops.form if self.condense else Form(ops.A), Form(ops.B), None, fv, gv, ops.preA, ops.preM,
+                              sol=self.sol, initialize=True, inner=ops.inner, workspace=workspace, k=k)
         self.k, self.wdn, self.err0 = ses.k, ses.wdn, ses.err0
+        if self.condense and not (np.isfinite(self.k) and self.k > 0):
+            self.declined = "the scale factor k = %r is not positive: preA is not symmetric positive definite" % (self.k,)
+            raise ValueError("DistributedBpcg2(condense=True): " + self.declined)
         self.first_direction = ses.first_direction
         self._attach(dict(u0=ses.u[0], u1=ses.u[1], d0=ses.d[0], d1=ses.d[1], w0=ses.w[0], w1=ses.w[1],
                           s0=ses.s[0], s1=self.s1, z0=ses.z[0], q=ses.As0, t0=ses.t0, t1=self.t1, t2=ses.t2,
@@ -898,6 +1028,11 @@ class DistributedBpcg2:
         compact = getattr(self, "compact", False)
         matB = ops.b_extended() if compact else ops.B.local
         extra = dict(ghost_rows_b=int(ops.BT.plan.n_ghost)) if compact else {}
+        if getattr(self, "condense", False):
+            if not compact:
+                self.declined = "a condensed form on slabs runs on the compact plan only"
+                raise RuntimeError("fused distributed BPCG loop: " + self.declined)
+            extra["condensed"] = ops.form.native_operators(ops.a_diag_scipy)
         if getattr(ops, "aux", None) is not None:           # MypreA(GS=True) on slabs, natively inside the loop
             import ctypes as C
             comm_handle = getattr(self.comm, "comm", None)
@@ -920,7 +1055,8 @@ class DistributedBpcg2:
             self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, ops.preA, self.k, ops.preM, vecs,
                                              distributed=True, **extra)
         if self.loop is None:
-            raise RuntimeError("fused distributed BPCG loop needs the HIP engine and native operands")
+            self.declined = Bpcg2Loop.last_declined
+            raise RuntimeError("fused distributed BPCG loop needs the HIP engine and native operands (%s)" % self.declined)
         self.halo = {"s1": (ops.BT, self.s1), "t1": (ops.A, self.t1), "t4": (ops.B, self.t4)}
         if compact:
             self.ghost_mode = self._setup_ghosts_compact()
@@ -938,6 +1074,10 @@ class DistributedBpcg2:
         self.mailbox = None
         if getattr(self, "want_transport", None) == "mailbox":
             self.enable_mailbox()
+        if getattr(self, "condense", False) and self.native is None:
+            self.declined = ("a condensed form on slabs needs the native loop (an RCCL communicator or transport='mailbox'); "
+                             "with torch.distributed run BramblePasciakCG on ops.form")
+            raise RuntimeError("fused distributed BPCG loop: " + self.declined)
 
     def _setup_ghosts(self):
         """Ghost copies of s0 / w0 on the ghost columns of B's operand (nss_bpcg2_t.ghost_*): every
@@ -1026,6 +1166,8 @@ class DistributedBpcg2:
         halos = (ops.BT.native_halo(self.s1, interior.get("s1")), ops.A.native_halo(self.t1, interior.get("t1")),
                  ops.B.native_halo(self.t4, interior.get("t4")))      # (the compact plan uses the middle one only)
         self.native = (handle, halos)
+        if getattr(self, "condense", False):
+            self._set_condensed_halos(handle, (0, 0))
 
     def enable_mailbox(self):
         """Run the native compact loop over the mailbox transport (`MailboxTransport`): the all-reduces inside the sum
@@ -1042,9 +1184,23 @@ class DistributedBpcg2:
         eng._check(eng.lib.nss_dist_create(None, self.comm.size, self.comm.rank, C.byref(handle)))
         halo = self.ops.A.native_halo(self.t1, (0, 0))
         self.native = (handle, (None, halo, None))
-        self.mailbox = MailboxTransport(self.comm, eng, [(halo, self.ops.n_u)])
+        channels = [(halo, self.ops.n_u)]
+        if getattr(self, "condense", False):      # channels 1 (lift: t0) and 2 (extension: t1 before it)
+            lift, ext = self._set_condensed_halos(handle, (0, 0))
+            channels += [(lift, self.ops.n_u), (ext, self.ops.n_u)]
+        self.mailbox = MailboxTransport(self.comm, eng, channels)
         self.loop.state.p2p = self.mailbox.handle
         self.loop.keep.append(self.mailbox)
+
+    def _set_condensed_halos(self, handle, interior):
+        """nss_dist_set_condensed: the halos of t0 (the lift) and of t1 (the extension), both in the layout of A's
+        operand; kept alive with the native handle."""
+        import ctypes as C
+        lift = self.ops.A.native_halo(self.vecs["t0"], interior)
+        ext = self.ops.A.native_halo(self.t1, interior)
+        self.engine._check(self.engine.lib.nss_dist_set_condensed(handle, C.byref(lift), C.byref(ext)))
+        self._cond_halos = (lift, ext)
+        return lift, ext
 
     def close(self):
         if getattr(self, "mailbox", None) is not None:

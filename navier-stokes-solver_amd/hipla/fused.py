@@ -325,12 +325,27 @@ class Bpcg2Loop:
         if any(not _plain(vecs.get(name), n) for name, n in sizes.items()):
             return "a work vector is not a plain Vector of its size"
         if condensed is not None:
-            if distributed:
+            # on slabs the operators carry the columns of A's operand [owned | ghosts] (`slab`: built that way by
+            # distributed.DistributedCondensedForm.native_operators; the lift / extension exchange their operands)
+            if distributed and not condensed.get("slab"):
                 return "condensed form on a partitioned run"
+            if distributed and (dist_amg is not None or pa["amg"] is not None):
+                return "condensed form on a partitioned run with an AMG term"
+            if distributed and dist_aux is not None and not isinstance(pa["bjac"], BlockGaussSeidel):
+                return "condensed form on a partitioned run: the auxiliary-space term only inside the multiplicative MypreA"
+            width = matA.width if distributed else n_u
+
+            def misfit(key):
+                m = condensed.get(key)
+                if not isinstance(m, SparseMatrix) or m.height != n_u:
+                    return True
+                return not (n_u <= m.width <= width) if key == "inner" else m.width != width
+
             keys = ("HT", "H", "inner") + (("S",) if condensed.get("S") is not None else ())
-            if any(not isinstance(condensed.get(key), SparseMatrix) or condensed[key].height != n_u
-                   or condensed[key].width != n_u for key in keys):
+            if any(misfit(key) for key in keys):
                 return "condensed operators are not n_u x n_u SparseMatrix"
+            if distributed and dist_aux is not None and condensed.get("S") is None:
+                return "condensed MypreA on slabs: the sweeps' residual needs S (condensed['S'])"
             if not _extension_is_in_place_safe(condensed["H"]):
                 return "harmonic extension H maps into its own columns"
         return cls(eng, matA, matB, matBT, pa, k, pm, vecs, condensed, distributed, dist_amg, n_p, dist_aux)
@@ -342,9 +357,11 @@ class Bpcg2Loop:
         self.keep = [matA, matB, matBT, vecs, pa, pm, condensed]       # keep device memory alive
         st = Bpcg2State()
         if condensed is not None:
-            self.cond_f = eng.zeros(matA.height)
+            self.cond_f = eng.zeros(matA.width if distributed else matA.height)     # (slabs: A_ii^-1's operand width)
             st.cond_HT, st.cond_H = condensed["HT"].handle.ptr, condensed["H"].handle.ptr
             st.cond_inner, st.cond_f = condensed["inner"].handle.ptr, self.cond_f.data_ptr()
+            if distributed and dist_aux is not None:
+                st.sweep_A = condensed["S"].handle.ptr      # MypreA on slabs: the residual x - S_slab y between the sweeps
             if pa["multiplicative"]:
                 st.sweep_A = condensed["S"].handle.ptr      # the residual between the sweeps: x - S y
                 # the fused condensed forms (nss_cond_fuse_mode) when the structure allows them: operators attached to

@@ -58,7 +58,8 @@ def _signatures():
         "nss_p2p_connect": (C.c_int, [vp, vp]),
         "nss_p2p_destroy": (C.c_int, [vp]),
         "nss_p2p_allreduce_f64": (C.c_int, [vp, vp, vp, vp]),
-        "nss_p2p_exchange": (C.c_int, [vp, vp, vp]),
+        "nss_p2p_exchange": (C.c_int, [vp, i32, vp, vp]),
+        "nss_p2p_counters": (C.c_int, [vp, c_i64_p, i32, c_i64_p, c_i32_p]),
         "nss_p2p_error": (C.c_int, [vp, c_i32_p, vp]),
         "nss_dist_aux_create": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
         "nss_dist_aux_destroy": (C.c_int, [vp]),
@@ -87,6 +88,7 @@ def _signatures():
         "nss_csr_row_blocks": (C.c_int, [vp, vp, i64]),
         "nss_dist_create": (C.c_int, [vp, i32, i32, C.POINTER(vp)]),
         "nss_dist_destroy": (C.c_int, [vp]),
+        "nss_dist_set_condensed": (C.c_int, [vp, vp, vp]),
         "nss_dist_amg_create": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
         "nss_dist_amg_destroy": (C.c_int, [vp]),
         "nss_dist_amg_apply_f64": (C.c_int, [vp, dbl, vp, vp, vp]),

@@ -102,7 +102,9 @@ class BpcgSession:
         """``inner`` is the inner product (a row-partitioned run passes the all-reducing one);
         ``workspace`` may pre-allocate ``t1``, ``t4`` and ``s1`` (the SpMV operands of the loop)
         in halo-extended buffers -- and, for the compact partitioned plan, ``s0``, ``w0``, ``w1``, ``t3``
-        (vectors whose ghost copies sit behind their owned entries)."""
+        (vectors whose ghost copies sit behind their owned entries) and, condensed, ``t0`` (the lift reads its ghosts).
+        A partitioned condensed form (``blfA.explicit``: the row slab of the explicit product) gives the scale factor's
+        Lanczos that product, as the fused single-GPU run does."""
         self.blfA = blfA
         self.inner = inner
         workspace = workspace or {}
@@ -122,6 +124,8 @@ class BpcgSession:
                 explicit = _explicit_condensed_matrix(blfA)
                 if explicit is not None:
                     lanczos_mat, lanczos_sweep = explicit, blfA.mat
+        if lanczos_mat is None and blfA.condense and getattr(blfA, "explicit", None) is not None:
+            lanczos_mat = blfA.explicit
         self.lanczos_native = False
         if k is None:
             timer_prepev = Timer("BPCG-Preparation-EV")
@@ -156,7 +160,7 @@ class BpcgSession:
             w = BlockVector([workspace.get("w0", w[0]), workspace.get("w1", w[1])])
         self.d, self.w, self.v, self.z, self.z_old, self.s = d, w, v, z, z_old, s
 
-        t0 = self.t0 = blfA.mat.CreateColVector()
+        t0 = self.t0 = workspace["t0"] if "t0" in workspace else blfA.mat.CreateColVector()
         t1 = self.t1 = workspace["t1"] if "t1" in workspace else blfA.mat.CreateColVector()
         t2 = self.t2 = blfA.mat.CreateColVector()
         t3 = self.t3 = workspace["t3"] if "t3" in workspace else matB.CreateColVector()
