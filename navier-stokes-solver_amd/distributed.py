@@ -24,7 +24,7 @@ import os
 import numpy as np
 import scipy.sparse as sp
 
-from hipla import BaseMatrix, BlockJacobi, BlockMatrix, DiagonalMatrix, InnerProduct, SparseMatrix, Vector
+from hipla import BaseMatrix, BlockJacobi, BlockMatrix, DiagonalMatrix, InnerProduct, SparseMatrix, Vector, fused
 from hipla.engine import get_engine
 
 
@@ -244,6 +244,49 @@ class MailboxTransport:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+def dist_create(comm, engine, nccl_comm):
+    """A native dist handle (`nss_dist_t`) of this rank of `comm`: over `nccl_comm` (an `RcclComm`'s ncclComm_t), or
+    None for one that a `MailboxTransport` gets attached to."""
+    import ctypes as C
+    handle = C.c_void_p()
+    engine._check(engine.lib.nss_dist_create(nccl_comm, comm.size, comm.rank, C.byref(handle)))
+    return handle
+
+
+class NativeDist:
+    """The native transport of a partitioned loop that issues its iterations from C (``nss_*_iterate_dist``):
+    ``native`` = (dist handle, the halos the loop exchanges) and ``mailbox`` = the `MailboxTransport` attached to the
+    handle, both None until `open_native`.  `close` frees them in dependency order, the mailbox first."""
+
+    native = mailbox = None
+
+    def open_native(self, halos, nccl_comm=None, channels=None):
+        """A new dist handle over `nccl_comm` or -- given `channels`, a list of (`nss_halo_t`, owned entries) per
+        operand layout -- over a `MailboxTransport` of those channels."""
+        self.close()
+        self.native = (dist_create(self.comm, self.engine, None if channels is not None else nccl_comm), halos)
+        if channels is not None:
+            self.mailbox = MailboxTransport(self.comm, self.engine, channels)
+            self.mailbox.attach(self.native[0])
+
+    def close(self):
+        if self.mailbox is not None:
+            self.mailbox.close()
+            self.mailbox = None
+        if self.native is not None:
+            self.engine.lib.nss_dist_destroy(self.native[0])
+            self.native = None
+
+    def release(self):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.release()
         except Exception:
             pass
 
@@ -911,7 +954,7 @@ class DistributedStokes:
                 "BT_operand": self.BT.plan.n_ghost}
 
 
-class DistributedBpcg2:
+class DistributedBpcg2(NativeDist):
     """Row-partitioned Bramble-Pasciak CG (v2) on this rank: set-up through the operator
     protocol with distributed operands (halo + all_reduce inside ``Mult`` / inner product),
     iteration through the fused device phases (``nss_bpcg2_phase``) with one halo
@@ -1015,16 +1058,7 @@ class DistributedBpcg2:
         from hipla.fused import Bpcg2Loop
         ops = self.ops
         self.vecs = vecs
-        dist_amg = getattr(self, "dist_amg", None)
-        if dist_amg is not None:
-            import ctypes as C
-            comm_handle = getattr(self.comm, "comm", None)
-            if comm_handle is None:
-                raise RuntimeError("pre='amg' inside the fused partitioned loop needs the RCCL communicator "
-                                   "(with torch.distributed use BramblePasciakCG on the distributed operands)")
-            handle = C.c_void_p()
-            self.engine._check(self.engine.lib.nss_dist_create(comm_handle, self.comm.size, self.comm.rank, C.byref(handle)))
-            self._amg_dist_handle = handle
+        dist_amg, aux = getattr(self, "dist_amg", None), getattr(ops, "aux", None)
         compact = getattr(self, "compact", False)
         matB = ops.b_extended() if compact else ops.B.local
         extra = dict(ghost_rows_b=int(ops.BT.plan.n_ghost)) if compact else {}
@@ -1033,19 +1067,18 @@ class DistributedBpcg2:
                 self.declined = "a condensed form on slabs runs on the compact plan only"
                 raise RuntimeError("fused distributed BPCG loop: " + self.declined)
             extra["condensed"] = ops.form.native_operators(ops.a_diag_scipy)
-        if getattr(ops, "aux", None) is not None:           # MypreA(GS=True) on slabs, natively inside the loop
-            import ctypes as C
-            comm_handle = getattr(self.comm, "comm", None)
-            if comm_handle is None:
-                raise RuntimeError("pre='mypre_a' inside the fused partitioned loop needs the RCCL communicator "
-                                   "(with torch.distributed use BramblePasciakCG on the distributed operands)")
-            handle = C.c_void_p()
-            self.engine._check(self.engine.lib.nss_dist_create(comm_handle, self.comm.size, self.comm.rank, C.byref(handle)))
-            self._amg_dist_handle = handle
+        if dist_amg is not None or aux is not None:     # the V-cycle / auxiliary-space term issue their collectives from C
+            if getattr(self.comm, "comm", None) is None:
+                raise RuntimeError("pre=%r inside the fused partitioned loop needs the RCCL communicator (with "
+                                   "torch.distributed use BramblePasciakCG on the distributed operands)"
+                                   % ("amg" if aux is None else "mypre_a"))
+            self._amg_dist_handle = dist_create(self.comm, self.engine, self.comm.comm)
+        if aux is not None:                             # MypreA(GS=True) on slabs, natively inside the loop
             self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, ops.gs, self.k, ops.preM, vecs,
-                                             distributed=True, dist_aux=ops.aux.native_handle(handle, vecs["t1"]), **extra)
+                                             distributed=True, dist_aux=aux.native_handle(self._amg_dist_handle, vecs["t1"]),
+                                             **extra)
             if self.loop is not None:
-                self.loop.keep.append(ops.aux)
+                self.loop.keep.append(aux)
         elif dist_amg is not None:
             self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, self.jacobi_part, self.k, ops.preM,
                                              vecs, distributed=True, dist_amg=dist_amg.native_handle(self._amg_dist_handle),
@@ -1062,7 +1095,6 @@ class DistributedBpcg2:
             self.ghost_mode = self._setup_ghosts_compact()
         else:
             self.ghost_mode = os.environ.get("NSS_GHOST_T4", "1") == "1" and self._setup_ghosts()
-        self.native = None
         # 0: exchange, then one launch per SpMV, all on the compute stream.  1: exchange on a second
         # stream while the interior row blocks are multiplied.  Measured on one GPU at 1/8 of the
         # headline size (tools/partition_overhead.py): the split launches + cross-stream events of
@@ -1071,7 +1103,6 @@ class DistributedBpcg2:
         comm_handle = getattr(self.comm, "comm", None)         # RcclComm: an ncclComm_t
         if comm_handle is not None and getattr(self, "want_native", True) and hasattr(self.loop.lib, "nss_bpcg2_iterate_dist"):
             self.enable_native(comm_handle)
-        self.mailbox = None
         if getattr(self, "want_transport", None) == "mailbox":
             self.enable_mailbox()
         if getattr(self, "condense", False) and self.native is None:
@@ -1156,60 +1187,46 @@ class DistributedBpcg2:
     def enable_native(self, comm_handle, interior=None):
         """Issue the partitioned iterations from C (nss_bpcg2_iterate_dist): RCCL calls, halo
         packs, events and the interior/boundary split without Python in the loop."""
-        import ctypes as C
-        self.close()
-        handle = C.c_void_p()
-        eng = self.engine
-        eng._check(eng.lib.nss_dist_create(comm_handle, self.comm.size, self.comm.rank, C.byref(handle)))
-        ops = self.ops
-        interior = interior or {}
-        halos = (ops.BT.native_halo(self.s1, interior.get("s1")), ops.A.native_halo(self.t1, interior.get("t1")),
-                 ops.B.native_halo(self.t4, interior.get("t4")))      # (the compact plan uses the middle one only)
-        self.native = (handle, halos)
-        if getattr(self, "condense", False):
-            self._set_condensed_halos(handle, (0, 0))
+        ops, interior = self.ops, interior or {}
+        condensed = self._condensed_halos()
+        self.open_native((ops.BT.native_halo(self.s1, interior.get("s1")), ops.A.native_halo(self.t1, interior.get("t1")),
+                          ops.B.native_halo(self.t4, interior.get("t4"))),     # (the compact plan uses the middle one only)
+                         nccl_comm=comm_handle)
+        self._set_condensed_halos(condensed)
 
     def enable_mailbox(self):
         """Run the native compact loop over the mailbox transport (`MailboxTransport`): the all-reduces inside the sum
         kernels, the halo of t1 by put / wait-copy kernels -- no RCCL call in an iteration.  The set-up communicator
         (any `TorchComm`) only gathers the IPC blobs."""
-        import ctypes as C
         if not getattr(self, "compact", False):
             raise RuntimeError("the mailbox transport serves the compact partitioned plan")
         if self.ops.A.plan.n_ghost and not self.ops.A.plan.direct:
             raise RuntimeError("the mailbox transport needs contiguous send runs (slab partitions have them)")
-        self.close()
-        eng = self.engine
-        handle = C.c_void_p()
-        eng._check(eng.lib.nss_dist_create(None, self.comm.size, self.comm.rank, C.byref(handle)))
         halo = self.ops.A.native_halo(self.t1, (0, 0))
-        self.native = (handle, (None, halo, None))
-        channels = [(halo, self.ops.n_u)]
-        if getattr(self, "condense", False):      # channels 1 (lift: t0) and 2 (extension: t1 before it)
-            lift, ext = self._set_condensed_halos(handle, (0, 0))
-            channels += [(lift, self.ops.n_u), (ext, self.ops.n_u)]
-        self.mailbox = MailboxTransport(self.comm, eng, channels)
+        condensed = self._condensed_halos()        # channels 1 (lift: t0) and 2 (extension: t1 before it)
+        self.open_native((None, halo, None), channels=[(h, self.ops.n_u) for h in (halo,) + condensed])
+        self._set_condensed_halos(condensed)
         self.loop.state.p2p = self.mailbox.handle
         self.loop.keep.append(self.mailbox)
 
-    def _set_condensed_halos(self, handle, interior):
-        """nss_dist_set_condensed: the halos of t0 (the lift) and of t1 (the extension), both in the layout of A's
-        operand; kept alive with the native handle."""
+    def _condensed_halos(self):
+        """A condensed form's halos of t0 (the lift) and of t1 (the extension), both in the layout of A's operand; ()
+        without one."""
+        if not getattr(self, "condense", False):
+            return ()
+        return self.ops.A.native_halo(self.vecs["t0"], (0, 0)), self.ops.A.native_halo(self.t1, (0, 0))
+
+    def _set_condensed_halos(self, halos):
+        """nss_dist_set_condensed: the native handle gets the `_condensed_halos`, kept alive with it."""
         import ctypes as C
-        lift = self.ops.A.native_halo(self.vecs["t0"], interior)
-        ext = self.ops.A.native_halo(self.t1, interior)
-        self.engine._check(self.engine.lib.nss_dist_set_condensed(handle, C.byref(lift), C.byref(ext)))
-        self._cond_halos = (lift, ext)
-        return lift, ext
+        if halos:
+            self.engine._check(self.engine.lib.nss_dist_set_condensed(self.native[0], *(C.byref(h) for h in halos)))
+            self._cond_halos = halos
 
     def close(self):
-        if getattr(self, "mailbox", None) is not None:
+        if self.mailbox is not None:
             self.loop.state.p2p = None
-            self.mailbox.close()
-            self.mailbox = None
-        if getattr(self, "native", None) is not None:
-            self.engine.lib.nss_dist_destroy(self.native[0])
-            self.native = None
+        super().close()
 
     def release(self):
         """Free the native handles in dependency order: the loop's dist handle, the V-cycle's native handle (it
@@ -1225,12 +1242,6 @@ class DistributedBpcg2:
         if getattr(self, "_amg_dist_handle", None) is not None:
             self.engine.lib.nss_dist_destroy(self._amg_dist_handle)
             self._amg_dist_handle = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
     def start(self, tol, maxsteps, rel_err=True):
         self.first_direction()
@@ -1346,14 +1357,7 @@ class DistributedBpcg2:
         """Full solve; returns (it, converged).  Every rank takes the same decision because
         the all-reduced scalars are bit-identical on all ranks."""
         self.start(tol, maxsteps)
-        it, done, it_final = 0, False, 0
-        while it < maxsteps:
-            end = min(maxsteps, it + poll_every)
-            self.iterate(it, end)
-            it = end
-            done, it_final, _ = self.poll()
-            if done:
-                break
+        done, it_final, _ = fused.run_chunked(self.iterate, self.poll, 0, maxsteps, poll_every)
         return (it_final if done else maxsteps - 1), done
 
 
@@ -1374,7 +1378,7 @@ def b_in_layout_of_a(A, B, engine):
     return SparseMatrix.from_scipy(b_on_a, engine=engine)
 
 
-class Bpcg1DistLoop:
+class Bpcg1DistLoop(fused.FusedLoop, NativeDist):
     """Row-partitioned device loop of the textbook Bramble-Pasciak CG (bramble_pasciak_cg.py:110-143) behind
     `bramble_pasciak_cg(...)` called with distributed operands: the fused kernels of `nss_bpcg1_*` on this rank's
     slab; per iteration the exchange of d (both components in one grouped phase), of t2_u and of a_u, and two
@@ -1387,24 +1391,30 @@ class Bpcg1DistLoop:
 
     @classmethod
     def try_create(cls, a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs, native=None):
-        from hipla import fused
-        native = cls.NATIVE if native is None else native
-        if c_matrix is not None or not (isinstance(a_matrix, DistSparseMatrix) and isinstance(b_matrix, DistSparseMatrix)):
-            return None
+        return cls._decided(cls._try_create(a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs, native))
+
+    @classmethod
+    def _try_create(cls, a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs, native=None):
+        if c_matrix is not None:
+            return "C is given"
+        if not (isinstance(a_matrix, DistSparseMatrix) and isinstance(b_matrix, DistSparseMatrix)):
+            return "A or B is not a DistSparseMatrix"
         eng = a_matrix.engine
-        if not fused.ENABLED or not hasattr(getattr(eng, "lib", None), "nss_bpcg1_phases"):
-            return None
+        if not fused.ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not fused._hip(eng):
+            return "not the HIP engine"
         bt = b_matrix.T
         if not isinstance(bt, DistSparseMatrix):
-            return None
-        pa_d, pa_b, ps = fused.native_diag(pre_a), fused.native_bjac(pre_a), fused.native_diag(pre_s)
-        if ps is None or (pa_d is None and pa_b is None):
-            return None
-        return cls(eng, a_matrix, b_matrix, bt, pa_d, pa_b, ps, k, vecs, native)
+            return "B^T is not a DistSparseMatrix"
+        pa, ps = fused.pre_for("partitioned bpcg1", pre_a), fused.native_diag(pre_s)
+        if ps is None:
+            return "preS is not a (scaled) diagonal"
+        if pa is None:
+            return "preA is not native"
+        return cls(eng, a_matrix, b_matrix, bt, pa, ps, k, vecs, cls.NATIVE if native is None else native)
 
-    def __init__(self, eng, A, B, BT, pa_d, pa_b, ps, k, vecs, native):
-        import ctypes as C
-        from hipla.fused import Bpcg1Loop
+    def __init__(self, eng, A, B, BT, pa, ps, k, vecs, native):
         self.engine, self.comm, self.A, self.BT = eng, A.comm, A, BT
         self.B_onA = b_in_layout_of_a(A, B, eng)
         # the SpMV operands of the loop in halo-extended buffers (d_u, t2_u, a_u: layout of A's operand; d_p: B^T's)
@@ -1414,37 +1424,13 @@ class Bpcg1DistLoop:
         self.a0.data = vecs["a"][0]
         local = dict(vecs)
         local["d"], local["a"], local["t2"] = [self.d0, self.d1], [self.a0, vecs["a"][1]], [self.t20, vecs["t2"][1]]
-        self.loop = Bpcg1Loop(eng, A.local, self.B_onA, pa_d, pa_b, ps, k, local, BT=BT.local)
+        self.loop = fused.Bpcg1Loop(eng, A.local, self.B_onA, pa, ps, k, local, BT=BT.local)
         self.loop.state.local_sums = 1
-        self.loop.enqueue = self.enqueue
-        self.native = None
-        self.mailbox = None
-        comm_handle = getattr(self.comm, "comm", None)        # RcclComm: an ncclComm_t
-        if self.TRANSPORT == "mailbox" and hasattr(eng.lib, "nss_p2p_create"):
-            handle = C.c_void_p()
-            eng._check(eng.lib.nss_dist_create(None, self.comm.size, self.comm.rank, C.byref(handle)))
+        if self.TRANSPORT == "mailbox":
             halos = (A.native_halo(self.d0, (0, 0)), BT.native_halo(self.d1, (0, 0)))
-            self.mailbox = MailboxTransport(self.comm, eng, [(halos[0], A.n_cols_owned), (halos[1], BT.n_cols_owned)])
-            self.mailbox.attach(handle)
-            self.native = (handle, halos)
-        elif native and comm_handle is not None and hasattr(eng.lib, "nss_bpcg1_iterate_dist"):
-            handle = C.c_void_p()
-            eng._check(eng.lib.nss_dist_create(comm_handle, self.comm.size, self.comm.rank, C.byref(handle)))
-            self.native = (handle, (A.native_halo(self.d0), BT.native_halo(self.d1)))
-
-    def close(self):
-        if getattr(self, "native", None) is not None:
-            self.engine.lib.nss_dist_destroy(self.native[0])
-            self.native = None
-        if getattr(self, "mailbox", None) is not None:
-            self.mailbox.close()
-            self.mailbox = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self.open_native(halos, channels=[(halos[0], A.n_cols_owned), (halos[1], BT.n_cols_owned)])
+        elif native and getattr(self.comm, "comm", None) is not None:        # RcclComm: an ncclComm_t
+            self.open_native((A.native_halo(self.d0), BT.native_halo(self.d1)), nccl_comm=self.comm.comm)
 
     def enqueue(self, it_begin, it_end):
         import ctypes as C
@@ -1473,10 +1459,10 @@ class Bpcg1DistLoop:
             phases(5, 5, it)
 
     def run(self, rho, err0, tolerance, max_steps, poll_every=None):
-        return self.loop.run(rho, err0, tolerance, max_steps, poll_every)
+        return self.loop.run(rho, err0, tolerance, max_steps, poll_every, enqueue=self.enqueue, transport=self.mailbox)
 
 
-class DistributedMinres:
+class DistributedMinres(NativeDist):
     """Row-partitioned preconditioned MINRES (minres.py:12-149) on this rank, K = [[A, B^T], [B, 0]],
     C = diag(preA, preM): set-up through the operator protocol with distributed operands, iteration
     through the fused device kernels (`nss_minres_*`).  Per iteration ONE grouped halo exchange -- z0 in
@@ -1488,10 +1474,8 @@ class DistributedMinres:
 
     def __init__(self, sysm, f, g, blocks, dist, engine=None, comm=None, native=True, sol=None, initialize=True,
                  transport=None):
-        import ctypes as C
         from math import sqrt
         from hipla import BlockVector
-        from hipla.fused import MinresLoop, native_bjac, native_diag
         self.engine = eng = engine if engine is not None else get_engine()
         self.comm = comm if comm is not None else TorchComm(dist, eng)
         ops = self.ops = DistributedStokes(sysm, blocks, self.comm, eng)
@@ -1528,40 +1512,18 @@ class DistributedMinres:
         for ring in (v_ring, w_ring):
             for j in (0, 2) if ring is v_ring else (0, 1, 2):
                 ring[j][:] = 0.0
-        pa_d, pa_b, pm = native_diag(ops.preA), native_bjac(ops.preA), native_diag(ops.preM)
-        if pm is None or (pa_d is None and pa_b is None):
-            raise RuntimeError("DistributedMinres: preA must be a (block) Jacobi, preM diagonal")
-        self.loop = MinresLoop(eng, ops.A.local, self.B_onA, ops.BT.local, pa_d, pa_b, pm, u, v_ring, w_ring, z_ring, kz)
+        pa, pm = fused.pre_for("partitioned minres", ops.preA), fused.native_diag(ops.preM)
+        if pa is None or pm is None:
+            raise RuntimeError("DistributedMinres: preA must be an unscaled block Jacobi or a (scaled) Jacobi, preM "
+                               "diagonal")
+        self.loop = fused.MinresLoop(eng, ops.A.local, self.B_onA, ops.BT.local, pa, pm, u, v_ring, w_ring, z_ring, kz)
         self.loop.state.local_sums = 1
         self.z_ring = z_ring
-        self.native = None
-        self.mailbox = None
-        comm_handle = getattr(self.comm, "comm", None)        # RcclComm: an ncclComm_t
         if transport == "mailbox":        # the native loop over the mailbox transport (csrc/p2p.h), any set-up communicator
-            handle = C.c_void_p()
-            eng._check(eng.lib.nss_dist_create(None, self.comm.size, self.comm.rank, C.byref(handle)))
             halos = (ops.A.native_halo(z_ring[0][0], (0, 0)), ops.BT.native_halo(z_ring[0][1], (0, 0)))
-            self.mailbox = MailboxTransport(self.comm, eng, [(halos[0], ops.n_u), (halos[1], ops.n_p)])
-            self.mailbox.attach(handle)
-            self.native = (handle, halos)
-        elif native and comm_handle is not None and hasattr(eng.lib, "nss_minres_iterate_dist"):
-            handle = C.c_void_p()
-            eng._check(eng.lib.nss_dist_create(comm_handle, self.comm.size, self.comm.rank, C.byref(handle)))
-            self.native = (handle, (ops.A.native_halo(z_ring[0][0]), ops.BT.native_halo(z_ring[0][1])))
-
-    def close(self):
-        if getattr(self, "native", None) is not None:
-            self.engine.lib.nss_dist_destroy(self.native[0])
-            self.native = None
-        if getattr(self, "mailbox", None) is not None:
-            self.mailbox.close()
-            self.mailbox = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self.open_native(halos, channels=[(halos[0], ops.n_u), (halos[1], ops.n_p)])
+        elif native and getattr(self.comm, "comm", None) is not None:        # RcclComm: an ncclComm_t
+            self.open_native((ops.A.native_halo(z_ring[0][0]), ops.BT.native_halo(z_ring[0][1])), nccl_comm=self.comm.comm)
 
     def _iterate(self, k_begin, k_end):
         import ctypes as C
@@ -1585,28 +1547,6 @@ class DistributedMinres:
 
     def solve(self, tol=1e-7, maxsteps=100, poll_every=16):
         """Returns (u, errors, hit_relative_tol) as `MinRes` does (errors[0] == 1.0)."""
-        import ctypes as C
-        from hipla.fused import (M_C, M_C_OLD, M_ERR0, M_ETA_OLD, M_GAMMA, M_RES_OLD, M_TOL)
-        eng, loop, st = self.engine, self.loop, self.loop.state
-        loop.hist = eng.zeros(maxsteps + 2)
-        st.hist = loop.hist.data_ptr()
-        scal = np.zeros(64)
-        g = self.gamma
-        scal[M_GAMMA], scal[M_ETA_OLD], scal[M_C_OLD], scal[M_C] = g, g, 1.0, 1.0
-        scal[M_RES_OLD], scal[M_ERR0], scal[M_TOL] = g, g, tol
-        scal[16:19] = 1.0
-        eng.upload(scal, loop.scal)
-        loop.ctrl.zero_()
-        stop, k_stop, reason, last = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        k = 1
-        while k < maxsteps + 1:
-            end = min(maxsteps + 1, k + poll_every)
-            self._iterate(k, end)
-            k = end
-            eng._check(eng.lib.nss_minres_poll(C.byref(st), C.byref(stop), C.byref(k_stop), C.byref(reason),
-                                               C.byref(last), eng.stream))
-            if stop.value:
-                break
-        last_k = k_stop.value if stop.value else maxsteps
-        errors = [1.0] + [float(x) for x in eng.to_host(loop.hist)[1: last_k + 1]]
-        return self.u, errors, bool(stop.value and reason.value == 1)
+        errors, hit_rel = self.loop.run(self.gamma, tol, maxsteps, poll_every, enqueue=self._iterate,
+                                        transport=self.mailbox)
+        return self.u, errors, hit_rel

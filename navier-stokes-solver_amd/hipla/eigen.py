@@ -75,22 +75,20 @@ def _native_lanczos(mat, pre, start, tol, maxsteps, check_every, sweep_A=None):
     if not (NATIVE and fused.ENABLED and isinstance(mat, SparseMatrix) and isinstance(start, Vector)):
         return None
     eng = mat.engine
-    if getattr(eng, "name", "") != "hip-gfx950" or not hasattr(eng.lib, "nss_lanczos_iterate") or mat.height != mat.width:
+    if not fused._hip(eng) or mat.height != mat.width:
         return None
     pa = fused.native_velocity_pre(pre)
-    if pa is None or (pa["multiplicative"] and pa["bjac"].mat is not (mat if sweep_A is None else sweep_A)):
+    if pa is None or (pa.multiplicative and pa.bjac.mat is not (mat if sweep_A is None else sweep_A)):
         return None
-    if sweep_A is not None and (not pa["multiplicative"] or not isinstance(sweep_A, SparseMatrix)
+    if sweep_A is not None and (not pa.multiplicative or not isinstance(sweep_A, SparseMatrix)
                                 or sweep_A.height != mat.height or sweep_A.width != mat.width):
         return None
     n = mat.height
     _mark("enter")
     st = _LanczosState.get()()
     st.A = mat.handle.ptr
-    st.pre_diag = pa["diag"].d.data_ptr() if pa["diag"] is not None else None
-    st.pre_bjac = pa["bjac"].handle.ptr if pa["bjac"] is not None else None
-    st.pre_amg = pa["amg"].handle.ptr if pa["amg"] is not None else None
-    st.pre_scale = float(pa["scale"])
+    fused.write_pre(st, pa)
+    st.pre_scale = float(pa.scale)
     st.sweep_A = sweep_A.handle.ptr if sweep_A is not None else None
     vecs = [eng.zeros(n) for _ in range(6)]
     eng.copy(start.buf, vecs[0])

@@ -2,7 +2,7 @@
 
 ``*.try_create`` return a loop object when every operand is native to the HIP engine
 (CSR ``SparseMatrix`` blocks, Jacobi / block-Jacobi preconditioners, plain vectors) and
-``None`` otherwise -- the caller then drives the same algorithm through the operator
+``None`` otherwise (the reason in ``last_declined``) -- the caller then drives the same algorithm through the operator
 protocol (still on the GPU, one kernel per statement), which is what keeps user
 ``BaseMatrix`` subclasses working.
 
@@ -12,6 +12,7 @@ exactly the iteration where the reference would ``break``."""
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -61,61 +62,118 @@ def _hip(engine):
     return getattr(engine, "name", "") == "hip-gfx950" and hasattr(engine.lib, "nss_bpcg2_iterate")
 
 
-def native_diag(op):
-    """(scale, DiagonalMatrix) if `op` is a (scaled) diagonal preconditioner, else None."""
-    scale = 1.0
-    if isinstance(op, ScaledMatrix):
-        scale, op = op.scale, op.mat
-    if isinstance(op, DiagonalMatrix):
-        return scale, op
-    return None
+class PreParts(NamedTuple):
+    """What the fused loops apply natively for a preconditioner: ``scale * (amg + diag | bjac)`` with any of the three
+    absent -- the additive form of the reference's MypreA (templates/NavierStokesSIMPLE_iterative.py:383) -- or, with
+    `multiplicative`, the Gauss-Seidel sweeps of `bjac` around the (auxiliary-space) AMG `amg` in its middle (GS=True,
+    :376-381)."""
+    scale: float
+    diag: object
+    bjac: object
+    amg: object
+    multiplicative: bool
 
 
-def native_bjac(op):
-    """(scale, op) for a (scaled) block-Jacobi or symmetric block Gauss-Seidel preconditioner: both
-    own an ``nss_bjac_t`` handle (the latter in Gauss-Seidel mode), which the fused loops apply."""
-    scale = 1.0
-    if isinstance(op, ScaledMatrix):
-        scale, op = op.scale, op.mat
-    if isinstance(op, BlockGaussSeidel) and op.middle is not None:
-        return None                      # sweep + middle operator: protocol path
-    if isinstance(op, (BlockJacobi, BlockGaussSeidel)):
-        return scale, op
-    return None
+NO_PRE = PreParts(1.0, None, None, None, False)
 
 
 def native_velocity_pre(op):
-    """Decompose a velocity-block preconditioner into what the fused BPCG loop applies natively:
-    ``scale * (AMG + J)`` with J a point / block Jacobi (or block Gauss-Seidel when there is no AMG
-    term) -- the additive form of the reference's MypreA
-    (templates/NavierStokesSIMPLE_iterative.py:383).  Returns dict(scale, amg, diag, bjac) or None."""
+    """The `PreParts` of `op`, or None when the fused loops cannot apply it natively."""
     scale = 1.0
     if isinstance(op, ScaledMatrix):
         scale, op = op.scale, op.mat
+    if isinstance(op, BlockGaussSeidel) and isinstance(op.middle, SmoothedAggregationAMG):
+        return PreParts(scale, None, op, op.middle, True)
     parts = [op]
     if isinstance(op, SumMatrix):
         if op.sb != 1.0:
             return None
         parts = [op.a, op.b]
-    out = {"scale": scale, "amg": None, "diag": None, "bjac": None, "multiplicative": False}
-    if (len(parts) == 1 and isinstance(op, BlockGaussSeidel) and isinstance(op.middle, SmoothedAggregationAMG)):
-        # the multiplicative MypreA (GS=True, :376-381): sweep, residual, (auxiliary-space) AMG correction,
-        # back sweep -- composed natively by the fused BPCG loop
-        out.update(bjac=op, amg=op.middle, multiplicative=True)
-        return out
+    diag = bjac = amg = None
     for part in parts:
-        if isinstance(part, SmoothedAggregationAMG) and out["amg"] is None:
-            out["amg"] = part
-        elif isinstance(part, DiagonalMatrix) and out["diag"] is None and out["bjac"] is None:
-            out["diag"] = part
-        elif (isinstance(part, (BlockJacobi, BlockGaussSeidel)) and out["diag"] is None and out["bjac"] is None
+        if isinstance(part, SmoothedAggregationAMG) and amg is None:
+            amg = part
+        elif isinstance(part, DiagonalMatrix) and diag is None and bjac is None:
+            diag = part
+        elif (isinstance(part, (BlockJacobi, BlockGaussSeidel)) and diag is None and bjac is None
               and getattr(part, "middle", None) is None):
-            out["bjac"] = part
+            bjac = part
         else:
             return None
-    if out["amg"] is not None and isinstance(out["bjac"], BlockGaussSeidel):
+    if amg is not None and isinstance(bjac, BlockGaussSeidel):
         return None
-    return out
+    return PreParts(scale, diag, bjac, amg, False)
+
+
+def native_diag(op):
+    """The `PreParts` of a (scaled) diagonal preconditioner (preM, preS), else None."""
+    p = native_velocity_pre(op)
+    return p if p is not None and p.bjac is None and p.amg is None else None
+
+
+# The preconditioners each fused loop takes (BPCG v2 and the Lanczos check theirs against their other operands).
+# CG further declines a ScaledMatrix or a sum (CgLoop); the partitioned loops have no AMG term.
+ACCEPTS = {
+    "minres": lambda p: not p.multiplicative and (p.scale == 1.0 or (p.bjac is None and p.amg is None)),
+    "bpcg1": lambda p: not p.multiplicative and (p.scale == 1.0 or p.amg is None),     # the scale goes into k
+    "cg": lambda p: not p.multiplicative,
+    "partitioned minres": lambda p: p.amg is None and ACCEPTS["minres"](p),
+    "partitioned bpcg1": lambda p: p.amg is None and ACCEPTS["bpcg1"](p),
+}
+
+
+def pre_for(kind, op):
+    """The `PreParts` of `op` when the fused loop `kind` (a key of ``ACCEPTS``) applies it, else None."""
+    p = native_velocity_pre(op)
+    return p if p is not None and ACCEPTS[kind](p) else None
+
+
+def scaled_diag(p):
+    """The entries of ``p.scale * p.diag`` (p.diag's own buffer when the scale is 1)."""
+    return p.diag.d if p.scale == 1.0 else p.diag.d * p.scale
+
+
+def write_pre(st, p, scale_diag=False):
+    """Point the ``pre_diag`` / ``pre_bjac`` / ``pre_amg`` fields of loop state `st` at the parts of `p`.  `scale_diag`:
+    pre_diag gets ``scaled_diag(p)`` instead of p.diag's entries.  Returns the buffer pre_diag points at (None without a
+    diagonal), which the loop keeps alive."""
+    diag = None if p.diag is None else scaled_diag(p) if scale_diag else p.diag.d
+    st.pre_diag = diag.data_ptr() if diag is not None else None
+    st.pre_bjac = p.bjac.handle.ptr if p.bjac is not None else None
+    st.pre_amg = p.amg.handle.ptr if p.amg is not None else None
+    return diag
+
+
+def run_chunked(enqueue, poll, begin, end, poll_every, transport=None):
+    """Drive a fused loop over iterations [begin, end): `enqueue(a, b)` issues iterations [a, b) without waiting,
+    `poll_every` at a time, and `poll()` after each chunk drains the stream and returns a tuple whose first entry is the
+    stop flag.  `transport`: the `distributed.MailboxTransport` of a partitioned run, whose timeouts the loop's kernels
+    do not see: checked after each poll.  Returns the last poll result (one poll without iterations when the range is
+    empty)."""
+    it, out = begin, None
+    while it < end:
+        chunk_end = min(end, it + poll_every)
+        enqueue(it, chunk_end)
+        it = chunk_end
+        out = poll()
+        if transport is not None and transport.timed_out():
+            raise RuntimeError("mailbox transport: a peer did not arrive within the timeout (iteration %d)" % (it - 1))
+        if out[0]:
+            break
+    return out if out is not None else poll()
+
+
+class FusedLoop:
+    """The `try_create` convention of the fused loops: ``_try_create`` returns the loop or the reason (one short string)
+    why not, and `_decided` keeps that reason in ``last_declined`` (None after a loop was made)."""
+
+    last_declined = None
+
+    @classmethod
+    def _decided(cls, out):
+        declined = isinstance(out, str)
+        cls.last_declined = out if declined else None
+        return None if declined else out
 
 
 def plan_for_textbook_bpcg(a_matrix, pre_a):
@@ -125,21 +183,10 @@ def plan_for_textbook_bpcg(a_matrix, pre_a):
     that the launch of A's rows applies it in its epilogue.  No-op for anything that is not native."""
     if not ENABLED or not isinstance(a_matrix, SparseMatrix) or not hasattr(a_matrix.handle, "plan_for_blocks"):
         return
-    parts = native_velocity_pre(pre_a)
-    if parts is None or parts["amg"] is not None or parts["multiplicative"] or not isinstance(parts["bjac"], BlockJacobi):
+    pa = native_velocity_pre(pre_a)
+    if pa is None or pa.amg is not None or pa.multiplicative or not isinstance(pa.bjac, BlockJacobi):
         return
-    a_matrix.handle.plan_for_blocks(parts["bjac"].handle)
-
-
-def _amg_plus_jacobi(op):
-    """(amg, (1.0, diag) | None, (1.0, bjac) | None) when `op` is an unscaled AMG V-cycle, optionally
-    plus a point / block Jacobi (the additive MypreA); (None, None, None) otherwise."""
-    parts = native_velocity_pre(op)
-    if parts is None or parts["amg"] is None or parts["scale"] != 1.0 or parts["multiplicative"]:
-        return None, None, None
-    diag = (1.0, parts["diag"]) if parts["diag"] is not None else None
-    bjac = (1.0, parts["bjac"]) if parts["bjac"] is not None else None
-    return parts["amg"], diag, bjac
+    a_matrix.handle.plan_for_blocks(pa.bjac.handle)
 
 
 def _extension_is_in_place_safe(H):
@@ -251,10 +298,8 @@ def _plain(v, n):
     return isinstance(v, Vector) and v.size == n
 
 
-class Bpcg2Loop:
+class Bpcg2Loop(FusedLoop):
     """Device-resident iteration of solvers/bramblepasciak_new.py:200-249."""
-
-    last_declined = None     # why the latest try_create returned None (one short string), None after a loop was made
 
     @classmethod
     def try_create(cls, matA, matB, matBT, preA_unscaled, k, preM, vecs, distributed=False, condensed=None,
@@ -267,13 +312,8 @@ class Bpcg2Loop:
         `ghost_rows_b` > 0: matB carries that many ghost pressure rows behind the slab's own (the compact
         partitioned plan, nss_bpcg2_t.dist_compact).  Returns None when an operand is not native, with the
         reason in ``Bpcg2Loop.last_declined``."""
-        out = cls._try_create(matA, matB, matBT, preA_unscaled, k, preM, vecs, distributed, condensed, dist_amg,
-                              ghost_rows_b, dist_aux)
-        if isinstance(out, str):
-            cls.last_declined = out
-            return None
-        cls.last_declined = None
-        return out
+        return cls._decided(cls._try_create(matA, matB, matBT, preA_unscaled, k, preM, vecs, distributed, condensed,
+                                            dist_amg, ghost_rows_b, dist_aux))
 
     @classmethod
     def _try_create(cls, matA, matB, matBT, preA_unscaled, k, preM, vecs, distributed=False, condensed=None,
@@ -294,31 +334,26 @@ class Bpcg2Loop:
         if distributed and (matA.width < n_u or matB.width < n_u or matBT.width < n_p):
             return "matrix shapes do not match"
         pm = native_diag(preM)
+        pa = native_velocity_pre(preA_unscaled)
         if dist_aux is not None:     # row-partitioned auxiliary-space term [+ Jacobi part | around Gauss-Seidel sweeps]
-            pa = native_velocity_pre(preA_unscaled) if preA_unscaled is not None else None
-            if pa is None:
-                pa = {"scale": 1.0, "amg": None, "diag": None, "bjac": None, "multiplicative": False}
-            if pa["amg"] is not None or pa["multiplicative"] or not distributed or dist_amg is not None:
+            pa = pa or NO_PRE
+            if pa.amg is not None or pa.multiplicative or not distributed or dist_amg is not None:
                 return "partitioned auxiliary term with another AMG term"
         elif dist_amg is not None:   # row-partitioned V-cycle (native handle) [+ an additive Jacobi part]
-            pa = native_velocity_pre(preA_unscaled) if preA_unscaled is not None else None
-            if pa is None:
-                pa = {"scale": 1.0, "amg": None, "diag": None, "bjac": None, "multiplicative": False}
-            if pa["amg"] is not None or pa["multiplicative"] or not distributed:
+            pa = pa or NO_PRE
+            if pa.amg is not None or pa.multiplicative or not distributed:
                 return "partitioned V-cycle with another AMG term"
-        else:
-            pa = native_velocity_pre(preA_unscaled)
         if pm is None:
             return "preM is not a (scaled) diagonal"
         if pa is None:
             return "preA is not native"
-        if pa["multiplicative"]:
+        if pa.multiplicative:
             # the sweeps' residual is formed with the loop's own A -- or, condensed, with the Schur complement S
             if distributed:
                 return "multiplicative preA on a partitioned run"
-            if condensed is None and pa["bjac"].mat is not matA:
+            if condensed is None and pa.bjac.mat is not matA:
                 return "multiplicative preA sweeps over another matrix than A"
-            if condensed is not None and (condensed.get("S") is None or pa["bjac"].mat is not condensed["S"]):
+            if condensed is not None and (condensed.get("S") is None or pa.bjac.mat is not condensed["S"]):
                 return "multiplicative and condensed: the sweeps are not over the Schur complement S"
         sizes = {"u0": n_u, "d0": n_u, "w0": n_u, "s0": n_u, "z0": n_u, "q": n_u, "t0": n_u, "t1": n_u,
                  "t2": n_u, "t4": n_u, "u1": n_p, "d1": n_p, "w1": n_p, "s1": n_p, "t3": n_p}
@@ -329,9 +364,9 @@ class Bpcg2Loop:
             # distributed.DistributedCondensedForm.native_operators; the lift / extension exchange their operands)
             if distributed and not condensed.get("slab"):
                 return "condensed form on a partitioned run"
-            if distributed and (dist_amg is not None or pa["amg"] is not None):
+            if distributed and (dist_amg is not None or pa.amg is not None):
                 return "condensed form on a partitioned run with an AMG term"
-            if distributed and dist_aux is not None and not isinstance(pa["bjac"], BlockGaussSeidel):
+            if distributed and dist_aux is not None and not isinstance(pa.bjac, BlockGaussSeidel):
                 return "condensed form on a partitioned run: the auxiliary-space term only inside the multiplicative MypreA"
             width = matA.width if distributed else n_u
 
@@ -362,28 +397,22 @@ class Bpcg2Loop:
             st.cond_inner, st.cond_f = condensed["inner"].handle.ptr, self.cond_f.data_ptr()
             if distributed and dist_aux is not None:
                 st.sweep_A = condensed["S"].handle.ptr      # MypreA on slabs: the residual x - S_slab y between the sweeps
-            if pa["multiplicative"]:
+            if pa.multiplicative:
                 st.sweep_A = condensed["S"].handle.ptr      # the residual between the sweeps: x - S y
                 # the fused condensed forms (nss_cond_fuse_mode) when the structure allows them: operators attached to
                 # the sweep's handle, kept alive with the loop; otherwise the straightforward sequence
-                self.cond_fusable, self.cond_fuse_declined = attach_condensed(pa["bjac"], condensed)
-                self.keep.append(pa["bjac"])
+                self.cond_fusable, self.cond_fuse_declined = attach_condensed(pa.bjac, condensed)
+                self.keep.append(pa.bjac)
         # the rows of B multiply t1 - s0 (:212-213): with row blocks short enough both vectors are read from LDS copies
         self.pair_staged_b = (os.environ.get("NSS_PAIR_STAGE", "1") == "1" and hasattr(matB.handle, "plan_for_pairs")
                               and matB.handle.plan_for_pairs())
         # block Jacobi alone as preA: B^T's row blocks are planned around its blocks and C1 applies it in its epilogue
-        self.c1_applies_bjac = (pa["bjac"] is not None and pa["diag"] is None and pa["amg"] is None and condensed is None
-                                and hasattr(matBT.handle, "plan_for_blocks") and matBT.handle.plan_for_blocks(pa["bjac"].handle))
+        self.c1_applies_bjac = (pa.bjac is not None and pa.diag is None and pa.amg is None and condensed is None
+                                and hasattr(matBT.handle, "plan_for_blocks") and matBT.handle.plan_for_blocks(pa.bjac.handle))
         st.A, st.B, st.BT = matA.handle.ptr, matB.handle.ptr, matBT.handle.ptr
-        st.pre_diag = pa["diag"].d.data_ptr() if pa["diag"] is not None else None
-        st.pre_bjac = pa["bjac"].handle.ptr if pa["bjac"] is not None else None
-        st.pre_amg = pa["amg"].handle.ptr if pa["amg"] is not None else None
-        st.k = float(k) * pa["scale"]
-        mscale, mop = pm
-        if mscale != 1.0:
-            self.minv = mop.d * mscale
-        else:
-            self.minv = mop.d
+        write_pre(st, pa)
+        st.k = float(k) * pa.scale
+        self.minv = scaled_diag(pm)
         st.minv = self.minv.data_ptr()
         for name in ("u0", "u1", "d0", "d1", "w0", "w1", "s0", "s1", "z0", "q", "t0", "t1", "t2", "t3", "t4"):
             setattr(st, name, vecs[name].buf.data_ptr())
@@ -471,16 +500,8 @@ class Bpcg2Loop:
     def run(self, wdn, err0, tol, rel_err, maxsteps, poll_every=None):
         """Returns (it, history, converged) -- `it` as the reference's loop variable after
         the loop (index of the iteration whose stop test fired, or maxsteps-1)."""
-        poll_every = poll_every or POLL_EVERY
         self.start(wdn, err0, tol, rel_err, maxsteps)
-        it, done, it_final = 0, False, 0
-        while it < maxsteps:
-            end = min(maxsteps, it + poll_every)
-            self.enqueue(it, end)
-            it = end
-            done, it_final, _ = self.poll()
-            if done:
-                break
+        done, it_final, _ = run_chunked(self.enqueue, self.poll, 0, maxsteps, poll_every or POLL_EVERY)
         final = it_final if done else maxsteps - 1
         return final, self.history(final), done
 
@@ -503,61 +524,52 @@ def _block2(v, n_u, n_p):
     return (isinstance(v, BlockVector) and v.nblocks == 2 and _plain(v[0], n_u) and _plain(v[1], n_p))
 
 
-class MinresLoop:
+class MinresLoop(FusedLoop):
     """Device-resident iteration of minres.py:96-144 for K = [[A, B^T], [B, None]] and
     C = [[preA, None], [None, preS]] (the operands run.py:45-46 builds)."""
 
     @classmethod
     def try_create(cls, mat, pre, u, v_ring, w_ring, z_ring, kz):
+        return cls._decided(cls._try_create(mat, pre, u, v_ring, w_ring, z_ring, kz))
+
+    @classmethod
+    def _try_create(cls, mat, pre, u, v_ring, w_ring, z_ring, kz):
         if not (isinstance(mat, BlockMatrix) and isinstance(pre, BlockMatrix)):
-            return None
+            return "K or C is not a BlockMatrix"
         if (mat.nrows, mat.ncols) != (2, 2) or (pre.nrows, pre.ncols) != (2, 2):
-            return None
+            return "K or C is not 2 x 2"
         A, BT, B, C11 = mat[0, 0], mat[0, 1], mat[1, 0], mat[1, 1]
         if C11 is not None or pre[0, 1] is not None or pre[1, 0] is not None:
-            return None
+            return "K or C has another non-zero block"
         if not all(isinstance(m, SparseMatrix) for m in (A, BT, B)):
-            return None
+            return "A, B or B^T is not a SparseMatrix"
         eng = A.engine
-        if not ENABLED or not _hip(eng) or not hasattr(eng.lib, "nss_minres_iterate"):
-            return None
+        if not ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not _hip(eng):
+            return "not the HIP engine"
         n_u, n_p = A.height, B.height
         if (A.width, B.width, BT.height, BT.width) != (n_u, n_u, n_u, n_p):
-            return None
-        pa_d, pa_b, ps = native_diag(pre[0, 0]), native_bjac(pre[0, 0]), native_diag(pre[1, 1])
-        pa_amg = None
-        if pa_d is None and pa_b is None:
-            pa_amg, pa_d, pa_b = _amg_plus_jacobi(pre[0, 0])
-        if ps is None or (pa_d is None and pa_b is None and pa_amg is None):
-            return None
-        if pa_b is not None and pa_b[0] != 1.0:
-            return None                  # scaled block Jacobi: the protocol path handles it
+            return "matrix shapes do not match"
+        pa, ps = pre_for("minres", pre[0, 0]), native_diag(pre[1, 1])
+        if ps is None:
+            return "preS is not a (scaled) diagonal"
+        if pa is None:
+            return "preA is not native"
         vecs = [u, kz] + list(v_ring) + list(w_ring) + list(z_ring)
         if len(v_ring) != 3 or len(w_ring) != 3 or len(z_ring) != 2 or not all(_block2(x, n_u, n_p) for x in vecs):
-            return None
-        return cls(eng, A, B, BT, pa_d, pa_b, ps, u, v_ring, w_ring, z_ring, kz, pa_amg)
+            return "a work vector is not a plain BlockVector of its size"
+        return cls(eng, A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz)
 
-    def __init__(self, eng, A, B, BT, pa_d, pa_b, ps, u, v_ring, w_ring, z_ring, kz, pa_amg=None):
+    def __init__(self, eng, A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz):
+        """`pa`, `ps`: the `PreParts` of preA and preS (pre_for("minres"), native_diag)."""
         torch = eng.torch
         self.eng, self.lib = eng, eng.lib
-        self.keep = [A, B, BT, pa_d, pa_b, ps, u, v_ring, w_ring, z_ring, kz, pa_amg]
+        self.keep = [A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz]
         st = MinresState()
         st.A, st.B, st.BT = A.handle.ptr, B.handle.ptr, BT.handle.ptr
-        st.pre_amg = pa_amg.handle.ptr if pa_amg is not None else None
-
-        def scaled(pair):
-            scale, op = pair
-            return op.d if scale == 1.0 else op.d * scale
-
-        if pa_d is not None:
-            self.dinv = scaled(pa_d)
-            st.pre_diag, st.pre_bjac = self.dinv.data_ptr(), None
-        elif pa_b is not None:
-            scale, op = pa_b             # scale == 1.0 (try_create declines anything else)
-            st.pre_diag, st.pre_bjac = None, op.handle.ptr
-        else:
-            st.pre_diag, st.pre_bjac = None, None
-        self.minv = scaled(ps)
+        self.dinv = write_pre(st, pa, scale_diag=True)
+        self.minv = scaled_diag(ps)
         st.minv = self.minv.data_ptr()
         for c in range(2):
             st.u[c] = u[c].buf.data_ptr()
@@ -575,10 +587,20 @@ class MinresLoop:
         self.state = st
         self.hist = None
 
-    def run(self, gamma, tol, maxsteps, poll_every=None):
-        """Iterations k = 1.. as the reference's while loop.  Returns (errors, hit_relative_tol)."""
+    def enqueue(self, k_begin, k_end):
+        self.eng._check(self.lib.nss_minres_iterate(C.byref(self.state), k_begin, k_end, self.eng.stream))
+
+    def poll(self):
+        """Drain the stream; returns (stop, k_stop, reason)."""
+        stop, k_stop, reason, last = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self.eng._check(self.lib.nss_minres_poll(C.byref(self.state), C.byref(stop), C.byref(k_stop), C.byref(reason),
+                                                 C.byref(last), self.eng.stream))
+        return bool(stop.value), k_stop.value, reason.value
+
+    def run(self, gamma, tol, maxsteps, poll_every=None, enqueue=None, transport=None):
+        """Iterations k = 1.. as the reference's while loop.  Returns (errors, hit_relative_tol).  `enqueue`: the
+        schedule of a partitioned run (distributed.DistributedMinres), `transport`: its mailbox transport."""
         eng, st = self.eng, self.state
-        poll_every = poll_every or POLL_EVERY
         self.partials = fit_partials(eng, st, self.lib.nss_minres_workspace, ("A", "B", "BT"), self.partials)
         self.hist = eng.zeros(maxsteps + 2)
         st.hist = self.hist.data_ptr()
@@ -588,19 +610,11 @@ class MinresLoop:
         scal[16:19] = 1.0                   # factors of the (here: normalised) z, v, v_old -- see csrc/minres.hip
         eng.upload(scal, self.scal)
         self.ctrl.zero_()
-        stop, k_stop, reason, last = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        k = 1
-        while k < maxsteps + 1:
-            end = min(maxsteps + 1, k + poll_every)
-            eng._check(self.lib.nss_minres_iterate(C.byref(st), k, end, eng.stream))
-            k = end
-            eng._check(self.lib.nss_minres_poll(C.byref(st), C.byref(stop), C.byref(k_stop), C.byref(reason),
-                                                C.byref(last), eng.stream))
-            if stop.value:
-                break
-        last_k = k_stop.value if stop.value else maxsteps
+        stop, k_stop, reason = run_chunked(enqueue or self.enqueue, self.poll, 1, maxsteps + 1, poll_every or POLL_EVERY,
+                                           transport)
+        last_k = k_stop if stop else maxsteps
         errors = [1.0] + [float(x) for x in eng.to_host(self.hist)[1: last_k + 1]]
-        return errors, bool(stop.value and reason.value == 1)
+        return errors, bool(stop and reason == 1)
 
 
 class Bpcg1State(C.Structure):
@@ -613,56 +627,53 @@ class Bpcg1State(C.Structure):
                 + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)])
 
 
-class Bpcg1Loop:
+class Bpcg1Loop(FusedLoop):
     """Device-resident iteration of bramble_pasciak_cg.py:110-143."""
 
     @classmethod
     def try_create(cls, a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs):
-        if c_matrix is not None or not (isinstance(a_matrix, SparseMatrix) and isinstance(b_matrix, SparseMatrix)):
-            return None
+        return cls._decided(cls._try_create(a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs))
+
+    @classmethod
+    def _try_create(cls, a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs):
+        if c_matrix is not None:
+            return "C is given"
+        if not (isinstance(a_matrix, SparseMatrix) and isinstance(b_matrix, SparseMatrix)):
+            return "A or B is not a SparseMatrix"
         eng = a_matrix.engine
-        if not ENABLED or not _hip(eng) or not hasattr(eng.lib, "nss_bpcg1_iterate"):
-            return None
+        if not ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not _hip(eng):
+            return "not the HIP engine"
         n_u, n_p = a_matrix.height, b_matrix.height
         if a_matrix.width != n_u or b_matrix.width != n_u:
-            return None
-        pa_d, pa_b, ps = native_diag(pre_a), native_bjac(pre_a), native_diag(pre_s)
-        pa_amg = None
-        if pa_d is None and pa_b is None:
-            pa_amg, pa_d, pa_b = _amg_plus_jacobi(pre_a)
-        if ps is None or (pa_d is None and pa_b is None and pa_amg is None):
-            return None
+            return "matrix shapes do not match"
+        pa, ps = pre_for("bpcg1", pre_a), native_diag(pre_s)
+        if ps is None:
+            return "preS is not a (scaled) diagonal"
+        if pa is None:
+            return "preA is not native"
         if any(not _block2(vecs.get(name), n_u, n_p) for name in ("x", "r", "d", "a", "t1", "t2")):
-            return None
-        return cls(eng, a_matrix, b_matrix, pa_d, pa_b, ps, k, vecs, pa_amg)
+            return "a work vector is not a plain BlockVector of its size"
+        return cls(eng, a_matrix, b_matrix, pa, ps, k, vecs)
 
-    def __init__(self, eng, A, B, pa_d, pa_b, ps, k, vecs, pa_amg=None, BT=None):
-        """`BT`: the rows of B^T this process owns, when they are not the transpose of its B (row-partitioned
-        runs: distributed.Bpcg1DistLoop)."""
+    def __init__(self, eng, A, B, pa, ps, k, vecs, BT=None):
+        """`pa`, `ps`: the `PreParts` of preA and preS (pre_for("bpcg1"), native_diag).  `BT`: the rows of B^T this
+        process owns, when they are not the transpose of its B (row-partitioned runs: distributed.Bpcg1DistLoop)."""
         torch = eng.torch
         self.eng, self.lib = eng, eng.lib
         if BT is None:
             BT = B.CreateTranspose()
-        self.keep = [A, B, BT, pa_d, pa_b, ps, vecs, pa_amg]
+        self.keep = [A, B, BT, pa, ps, vecs]
         st = Bpcg1State()
         st.A, st.B, st.BT = A.handle.ptr, B.handle.ptr, BT.handle.ptr
-        st.pre_amg = pa_amg.handle.ptr if pa_amg is not None else None
-        scale = 1.0
-        if pa_d is not None:
-            scale, op = pa_d
-            st.pre_diag, st.pre_bjac = op.d.data_ptr(), None
-        elif pa_b is not None:
-            scale, op = pa_b
-            st.pre_diag, st.pre_bjac = None, op.handle.ptr
-            # block Jacobi alone: A's row blocks are planned around its blocks (small systems) and the launch of A's rows
-            # applies it in its epilogue (csrc/bpcg1.hip: EpiV1Rows)
-            if pa_amg is None and hasattr(A.handle, "plan_for_blocks"):
-                A.handle.plan_for_blocks(op.handle)
-        else:
-            st.pre_diag, st.pre_bjac = None, None
-        st.k = float(k) * scale
-        mscale, mop = ps
-        self.minv = mop.d if mscale == 1.0 else mop.d * mscale
+        write_pre(st, pa)
+        # block Jacobi alone: A's row blocks are planned around its blocks (small systems) and the launch of A's rows
+        # applies it in its epilogue (csrc/bpcg1.hip: EpiV1Rows)
+        if pa.bjac is not None and pa.amg is None and hasattr(A.handle, "plan_for_blocks"):
+            A.handle.plan_for_blocks(pa.bjac.handle)
+        st.k = float(k) * pa.scale
+        self.minv = scaled_diag(ps)
         st.minv = self.minv.data_ptr()
         for name in ("x", "r", "d", "a", "t1", "t2"):
             arr = getattr(st, name)
@@ -679,10 +690,17 @@ class Bpcg1Loop:
     def enqueue(self, it_begin, it_end):
         self.eng._check(self.lib.nss_bpcg1_iterate(C.byref(self.state), it_begin, it_end, self.eng.stream))
 
-    def run(self, rho, err0, tolerance, max_steps, poll_every=None):
-        """Returns (errors, converged): errors[i] = err_i/err_0 as appended at :118."""
+    def poll(self):
+        """Drain the stream; returns (stop, it_stop)."""
+        stop, it_stop, last = C.c_int32(), C.c_int32(), C.c_int32()
+        self.eng._check(self.lib.nss_bpcg1_poll(C.byref(self.state), C.byref(stop), C.byref(it_stop), C.byref(last),
+                                                self.eng.stream))
+        return bool(stop.value), it_stop.value
+
+    def run(self, rho, err0, tolerance, max_steps, poll_every=None, enqueue=None, transport=None):
+        """Returns (errors, converged): errors[i] = err_i/err_0 as appended at :118.  `enqueue`: the schedule of a
+        partitioned run (distributed.Bpcg1DistLoop), `transport`: its mailbox transport."""
         eng, st = self.eng, self.state
-        poll_every = poll_every or POLL_EVERY
         self.partials = fit_partials(eng, st, self.lib.nss_bpcg1_workspace, ("A", "B", "BT"), self.partials)
         self.hist = eng.zeros(max(1, max_steps))
         st.hist = self.hist.data_ptr()
@@ -690,17 +708,9 @@ class Bpcg1Loop:
         scal[0], scal[5], scal[6] = rho, err0, tolerance
         eng.upload(scal, self.scal)
         self.ctrl.zero_()
-        stop, it_stop, last = C.c_int32(), C.c_int32(), C.c_int32()
-        it = 0
-        while it < max_steps:
-            end = min(max_steps, it + poll_every)
-            self.enqueue(it, end)
-            it = end
-            eng._check(self.lib.nss_bpcg1_poll(C.byref(st), C.byref(stop), C.byref(it_stop), C.byref(last), eng.stream))
-            if stop.value:
-                break
-        count = it_stop.value + 1 if stop.value else max_steps
-        return [float(x) for x in eng.to_host(self.hist)[:count]], bool(stop.value)
+        stop, it_stop = run_chunked(enqueue or self.enqueue, self.poll, 0, max_steps, poll_every or POLL_EVERY, transport)
+        count = it_stop + 1 if stop else max_steps
+        return [float(x) for x in eng.to_host(self.hist)[:count]], stop
 
 
 class CgState(C.Structure):
@@ -710,39 +720,38 @@ class CgState(C.Structure):
                 + [("n", C.c_int32), ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64)])
 
 
-class CgLoop:
+class CgLoop(FusedLoop):
     """Device-resident preconditioned CG (``nss_cg_*``) behind `hipla.CGSolver`."""
 
     @classmethod
     def try_create(cls, mat, pre):
-        if not isinstance(mat, SparseMatrix) or mat.height != mat.width:
-            return None
-        eng = mat.engine
-        if not ENABLED or not _hip(eng) or not hasattr(eng.lib, "nss_cg_iterate"):
-            return None
-        kind = None
-        if pre is None:
-            kind = ("none", None)
-        elif isinstance(pre, DiagonalMatrix):
-            kind = ("diag", pre)
-        elif isinstance(pre, (BlockJacobi, BlockGaussSeidel)) and getattr(pre, "middle", None) is None:
-            kind = ("bjac", pre)
-        elif isinstance(pre, SmoothedAggregationAMG):
-            kind = ("amg", pre)
-        if kind is None:
-            return None
-        return cls(eng, mat, kind)
+        return cls._decided(cls._try_create(mat, pre))
 
-    def __init__(self, eng, mat, kind):
+    @classmethod
+    def _try_create(cls, mat, pre):
+        if not isinstance(mat, SparseMatrix) or mat.height != mat.width:
+            return "the matrix is not a square SparseMatrix"
+        eng = mat.engine
+        if not ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not _hip(eng):
+            return "not the HIP engine"
+        if isinstance(pre, (ScaledMatrix, SumMatrix)):
+            return "the preconditioner is scaled or a sum"
+        pa = NO_PRE if pre is None else pre_for("cg", pre)
+        if pa is None:
+            return "the preconditioner is not native"
+        return cls(eng, mat, pa)
+
+    def __init__(self, eng, mat, pa):
+        """`pa`: the `PreParts` of the preconditioner (NO_PRE: none)."""
         torch = eng.torch
-        self.eng, self.lib, self.mat, self.kind = eng, eng.lib, mat, kind
+        self.eng, self.lib, self.mat, self.pa = eng, eng.lib, mat, pa
         n = mat.height
         self.work = {name: eng.zeros(n) for name in ("r", "z", "p", "q")}
         st = CgState()
         st.A, st.n = mat.handle.ptr, n
-        st.pre_diag = kind[1].d.data_ptr() if kind[0] == "diag" else None
-        st.pre_bjac = kind[1].handle.ptr if kind[0] == "bjac" else None
-        st.pre_amg = kind[1].handle.ptr if kind[0] == "amg" else None
+        write_pre(st, pa)
         for name, buf in self.work.items():
             setattr(st, name, buf.data_ptr())
         self.partials = fit_partials(eng, st, self.lib.nss_cg_workspace, ("A",))
@@ -752,23 +761,31 @@ class CgLoop:
         self.state = st
         self.hist = None
 
+    def enqueue(self, it_begin, it_end):
+        self.eng._check(self.lib.nss_cg_iterate(C.byref(self.state), it_begin, it_end, self.eng.stream))
+
+    def poll(self):
+        """Drain the stream; returns (done, it_final)."""
+        done, it_final, last = C.c_int32(), C.c_int32(), C.c_int32()
+        self.eng._check(self.lib.nss_cg_poll(C.byref(self.state), C.byref(done), C.byref(it_final), C.byref(last),
+                                             self.eng.stream))
+        return bool(done.value), it_final.value
+
     def solve(self, b, x, precision, maxsteps, poll_every=None):
         """x = mat^-1 b from x = 0.  Returns (iterations, errors) with errors[0] = err0."""
         from math import sqrt
-        eng, st, w = self.eng, self.state, self.work
-        poll_every = poll_every or POLL_EVERY
+        eng, st, w, pa = self.eng, self.state, self.work, self.pa
         self.partials = fit_partials(eng, st, self.lib.nss_cg_workspace, ("A",), self.partials)
         eng.fill(x, 0.0)
         eng.copy(b, w["r"])
-        kind, pre = self.kind
-        if kind == "none":
-            eng.copy(w["r"], w["z"])
-        elif kind == "diag":
-            eng.diag_apply(pre.d, 1.0, w["r"], 0.0, w["z"])
-        elif kind == "bjac":
-            eng.bjac_apply(pre.handle, 1.0, w["r"], 0.0, w["z"])
+        if pa.diag is not None:
+            eng.diag_apply(pa.diag.d, 1.0, w["r"], 0.0, w["z"])
+        elif pa.bjac is not None:
+            eng.bjac_apply(pa.bjac.handle, 1.0, w["r"], 0.0, w["z"])
+        elif pa.amg is not None:
+            eng.amg_apply(pa.amg.handle, 1.0, w["r"], w["z"])
         else:
-            eng.amg_apply(pre.handle, 1.0, w["r"], w["z"])
+            eng.copy(w["r"], w["z"])
         eng.copy(w["z"], w["p"])
         rz = eng.dot(w["r"], w["z"])
         err0 = sqrt(abs(rz))
@@ -780,14 +797,6 @@ class CgLoop:
         scal[0], scal[3], scal[4] = rz, err0, precision
         eng.upload(scal, self.scal)
         self.ctrl.zero_()
-        done, it_final, last = C.c_int32(), C.c_int32(), C.c_int32()
-        it = 0
-        while it < maxsteps:
-            end = min(maxsteps, it + poll_every)
-            eng._check(self.lib.nss_cg_iterate(C.byref(st), it, end, eng.stream))
-            it = end
-            eng._check(self.lib.nss_cg_poll(C.byref(st), C.byref(done), C.byref(it_final), C.byref(last), eng.stream))
-            if done.value:
-                break
-        count = it_final.value + 1 if done.value else maxsteps
+        done, it_final = run_chunked(self.enqueue, self.poll, 0, maxsteps, poll_every or POLL_EVERY)
+        count = it_final + 1 if done else maxsteps
         return count, [err0] + [float(v) for v in eng.to_host(self.hist)[:count]]

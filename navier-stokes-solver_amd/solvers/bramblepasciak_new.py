@@ -120,7 +120,7 @@ class BpcgSession:
         explicit = lanczos_mat = lanczos_sweep = None
         if matC is None and blfA.condense and fused.ENABLED:      # (the protocol path keeps the composite operator)
             pa = fused.native_velocity_pre(preA_unscaled)
-            if pa is not None and pa["multiplicative"] and pa["bjac"].mat is blfA.mat:
+            if pa is not None and pa.multiplicative and pa.bjac.mat is blfA.mat:
                 explicit = _explicit_condensed_matrix(blfA)
                 if explicit is not None:
                     lanczos_mat, lanczos_sweep = explicit, blfA.mat

@@ -134,7 +134,8 @@ def _condensed_operands(dim=2, n=6):
 def test_fused_declined_reasons(numpy_engine, monkeypatch):
     """Bpcg2Loop.try_create says why it returns None -- here past the engine check, so that the reasons of the
     combinations still declined show: condensed on a partitioned run, a multiplicative MypreA that does not sweep over
-    the Schur complement, and (BpcgSession) a given matC."""
+    the Schur complement, and (BpcgSession) a given matC.  MinresLoop, Bpcg1Loop and CgLoop keep theirs the same
+    way."""
     import hipla
     from hipla import fused
     from solvers.bramblepasciak_new import BpcgSession
@@ -159,10 +160,44 @@ def test_fused_declined_reasons(numpy_engine, monkeypatch):
     bad = dict(vecs, t2=hipla.Vector(s.n_u + 1))
     assert Loop.try_create(explicit, B, BT, preA, 1.0, preM, bad, condensed=condensed) is None
     assert "work vector" in Loop.last_declined
+
+    # MINRES, BPCG v1 and CG say why as well
+    M, Bp1, Cg = fused.MinresLoop, fused.Bpcg1Loop, fused.CgLoop
+    A, bjac = explicit, hipla.BlockJacobi(explicit, s.line_blocks(3))
+    K = hipla.BlockMatrix([[A, BT], [B, None]])
+
+    def block(n_p=s.n_p):
+        return hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(n_p)])
+
+    def minres(pre_a, pre_s=preM, mat=K, u=None):
+        return M.try_create(mat, hipla.BlockMatrix([[pre_a, None], [None, pre_s]]), u or block(),
+                            [block() for _ in range(3)], [block() for _ in range(3)], [block() for _ in range(2)], block())
+
+    assert minres(2.0 * bjac) is None and M.last_declined == "preA is not native"
+    assert minres(preA) is None and M.last_declined == "preA is not native"
+    assert minres(bjac, pre_s=bjac) is None and M.last_declined == "preS is not a (scaled) diagonal"
+    assert minres(bjac, mat=hipla.BlockMatrix([[A, BT], [B, A]])) is None
+    assert M.last_declined == "K or C has another non-zero block"
+    assert minres(bjac, u=block(s.n_p + 1)) is None and "work vector" in M.last_declined
+    pair = {name: block() for name in ("x", "r", "d", "a", "t1", "t2")}
+    assert Bp1.try_create(A, B, A, bjac, preM, 1.0, pair) is None and Bp1.last_declined == "C is given"
+    assert Bp1.try_create(A, B, None, preA, preM, 1.0, pair) is None and Bp1.last_declined == "preA is not native"
+    assert Bp1.try_create(A, B, None, bjac, bjac, 1.0, pair) is None
+    assert Bp1.last_declined == "preS is not a (scaled) diagonal"
+    assert Bp1.try_create(A, B, None, bjac, preM, 1.0, dict(pair, t2=hipla.Vector(s.n_u))) is None
+    assert "work vector" in Bp1.last_declined
+    assert Cg.try_create(B, None) is None and Cg.last_declined == "the matrix is not a square SparseMatrix"
+    assert Cg.try_create(A, 2.0 * bjac) is None and Cg.last_declined == "the preconditioner is scaled or a sum"
+    assert Cg.try_create(A, preA) is None and Cg.last_declined == "the preconditioner is not native"
+
     monkeypatch.setattr(fused, "ENABLED", False)
     assert Loop.try_create(explicit, B, BT, preA, 1.0, preM, vecs, condensed=condensed) is None
     assert "ENABLED" in Loop.last_declined
+    assert minres(bjac) is None and "ENABLED" in M.last_declined
+    assert Bp1.try_create(A, B, None, bjac, preM, 1.0, pair) is None and "ENABLED" in Bp1.last_declined
+    assert Cg.try_create(A, None) is None and "ENABLED" in Cg.last_declined
     monkeypatch.undo()
+    assert Cg.try_create(A, bjac) is None and Cg.last_declined == "not the HIP engine"
 
     from discretizations import AssembledForm
     f, g = s.rhs(0)

@@ -27,7 +27,7 @@ for name in (sys.argv[1:] or ["cfg2", "cfg3"]):
     for mode, label in ((-1, "two-launch (by size)"), (0, "five-launch")):
         eng.lib.nss_lanczos_fold_mode(mode)
         st = eigen._LanczosState.get()()
-        st.A, st.pre_bjac, st.pre_scale, st.n = A.handle.ptr, pa["bjac"].handle.ptr, float(pa["scale"]), s.n_u
+        st.A, st.pre_bjac, st.pre_scale, st.n = A.handle.ptr, pa.bjac.handle.ptr, float(pa.scale), s.n_u
         vecs = [eng.zeros(s.n_u) for _ in range(6)]
         vecs[0].copy_(torch.from_numpy(eigen.lanczos_start_values(0, s.n_u)))
         for i in range(3):
