@@ -140,6 +140,18 @@ NSS_API int nss_stream_loads_mode(int32_t mode);
 /* copy the CSR arrays back to HOST buffers (rows+1 / nnz / nnz entries; sizes from nss_csr_info) */
 NSS_API int nss_csr_download(nss_csr_t a, int32_t* h_rowptr, int32_t* h_col, double* h_val);
 NSS_API int nss_csr_destroy(nss_csr_t a);
+/* fp32 value storage of preconditioner matrices (vectors and arithmetic stay fp64):
+ * nss_csr_round_f32: round the fp64 values of `a` to the nearest fp32, IN PLACE, keeping 8-byte storage (for a matrix the
+ *   caller owns alone: e.g. a copy from which block inverses of the rounded matrix are computed).
+ * nss_csr_narrow_f32: store the values of `a` 4 bytes wide, IN PLACE (each rounded to the nearest fp32; exact when they
+ *   already are).  Only the SpMV paths that have an fp32 form take such a matrix -- nss_csr_spmv_f64, the Gauss-Seidel
+ *   sweep of a handle whose permuted matrix it is, the AMG cycle (single and joint), the residual between the half-sweeps
+ *   of the multiplicative MypreA (nss_bpcg2_t / nss_lanczos_t sweep_A); every other path refuses it with an error.
+ *   Never narrow a matrix that something else shares.
+ * nss_csr_value_bytes: bytes of the stored value stream (8 or 4 per entry).  nss_csr_download widens fp32 values. */
+NSS_API int nss_csr_round_f32(nss_csr_t a, nss_stream_t stream);
+NSS_API int nss_csr_narrow_f32(nss_csr_t a, nss_stream_t stream);
+NSS_API int nss_csr_value_bytes(nss_csr_t a, int64_t* bytes);
 /* y = alpha * A x + beta * y   (beta == 0: y is not read).  x must not alias y. */
 NSS_API int nss_csr_spmv_f64(nss_csr_t a, double alpha, const double* x, double beta, double* y,
                              nss_stream_t stream);

@@ -32,19 +32,19 @@ static void cycle(const nss_amg_s& a, int l, const double* b, double* out, hipSt
                   double scale = 1.0, bool accumulate = false) {
   const AmgLevel& lv = a.levels[l];
   if (l == int(a.levels.size()) - 1) {
-    launch_csr_stream(*a.coarse_inverse, b, EpiAxpby{scale, accumulate ? 1.0 : 0.0, out, done}, st);   // x = A^-1 b
+    launch_csr_stream_any(*a.coarse_inverse, b, EpiAxpby{scale, accumulate ? 1.0 : 0.0, out, done}, st);   // x = A^-1 b
     return;
   }
   const int n = lv.n;
   hipLaunchKernelGGL(amg_diag_kernel, dim3(stream_grid(n, kBlock * 4)), dim3(kBlock), 0, st, n, a.omega, lv.dinv, b,
                      lv.x, done);
   NSS_CHECK_LAUNCH();
-  launch_csr_stream(*lv.A, lv.x, EpiResidual{b, lv.r, done}, st);
+  launch_csr_stream_any(*lv.A, lv.x, EpiResidual{b, lv.r, done}, st);
   const AmgLevel& next = a.levels[l + 1];
-  launch_csr_stream(*lv.R, lv.r, EpiAxpby{1.0, 0.0, next.b, done}, st);
+  launch_csr_stream_any(*lv.R, lv.r, EpiAxpby{1.0, 0.0, next.b, done}, st);
   cycle(a, l + 1, next.b, next.y, st, done);
-  launch_csr_stream(*lv.P, next.y, EpiAxpby{1.0, 1.0, lv.x, done}, st);
-  launch_csr_stream(*lv.A, lv.x, EpiJacobi{b, lv.x, lv.dinv, out, a.omega, scale, done, accumulate}, st);
+  launch_csr_stream_any(*lv.P, next.y, EpiAxpby{1.0, 1.0, lv.x, done}, st);
+  launch_csr_stream_any(*lv.A, lv.x, EpiJacobi{b, lv.x, lv.dinv, out, a.omega, scale, done, accumulate}, st);
 }
 
 
@@ -81,7 +81,8 @@ __global__ __launch_bounds__(kBlock) void multi_desc_kernel(int32_t nblk, const 
   desc[4 * b + 3] = rowptr[r1] - p0;
 }
 
-template <int K, int L, class Epi>
+// VT: the value type of the matrix (float: fp32 storage, nss_csr_narrow_f32; widened to fp64 at the product)
+template <int K, int L, class Epi, class VT = double>
 __global__ __launch_bounds__(kBlock) void csr_multi_kernel(CsrView a, const int32_t* __restrict__ desc,
                                                             const double* __restrict__ x, Epi epi) {
   __shared__ double prod[K * kMultiPlane];
@@ -93,6 +94,7 @@ __global__ __launch_bounds__(kBlock) void csr_multi_kernel(CsrView a, const int3
   const int b = a.blk0 + lb;
   const MultiDesc d = (MultiDesc)(desc + size_t(b) * 4);
   const int r0 = d[0], r1 = d[1], p0 = d[2], cnt = d[3];
+  const VT* __restrict__ vals = view_values<VT>(a);
   if (cnt <= kMultiChunk) {
     constexpr int kPF = 2;                                             // pairs per lane whose operands are prefetched
     constexpr int kLanePairs = kBlock / L;                             // pairs per pass of the workgroup
@@ -113,12 +115,13 @@ __global__ __launch_bounds__(kBlock) void csr_multi_kernel(CsrView a, const int3
     // all loads of the lane's entries are requested before the first product (as the single-vector stream kernel does)
     constexpr int kPer = kMultiChunk / kBlock;
     int cc[kPer];
-    double vv[kPer], xv[kPer][K];
+    VT vv[kPer];
+    double xv[kPer][K];
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
       const int i = tid + q * kBlock;
       cc[q] = i < cnt ? __builtin_nontemporal_load(a.col + p0 + i) : -1;
-      vv[q] = i < cnt ? __builtin_nontemporal_load(a.val + p0 + i) : 0.0;
+      vv[q] = i < cnt ? __builtin_nontemporal_load(vals + p0 + i) : VT(0);
     }
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void csr_multi_kernel(CsrView a, const int3
       const int i = tid + q * kBlock;
       if (i < cnt) {
 #pragma unroll
-        for (int k = 0; k < K; ++k) prod[k * kMultiPlane + i] = vv[q] * xv[q][k];
+        for (int k = 0; k < K; ++k) prod[k * kMultiPlane + i] = double(vv[q]) * xv[q][k];
       }
     }
     __syncthreads();
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void csr_multi_kernel(CsrView a, const int3
     for (int k = 0; k < K; ++k) acc[k] = 0.0;
     for (int i = tid; i < cnt; i += kBlock) {
       const int c = a.col[p0 + i];
-      const double v = a.val[p0 + i];
+      const double v = double(vals[p0 + i]);
 #pragma unroll
       for (int k = 0; k < K; ++k) acc[k] = fma(v, x[size_t(c) * K + k], acc[k]);
     }
@@ -253,12 +256,18 @@ template <int K, class Epi>
 static void launch_multi(const nss_amg_s& aux, const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st) {
   if (A.m == 0 || A.nblk == 0) return;
   const dim3 grid(nss_csr_s::grid(A.nblk)), block(kBlock);
-  const CsrView v = A.view(0, A.nblk, 0);
+  const CsrView v = A.view(0, A.nblk, 0, true);
   const int32_t* desc = multi_desc_of(aux, A);
   const double mean = double(A.nnz) / double(A.m);                     // lanes per (row, k) pair by the mean row length
-  if (mean >= 48.0) hipLaunchKernelGGL((csr_multi_kernel<K, 4, Epi>), grid, block, 0, st, v, desc, x, epi);
-  else if (mean >= 20.0) hipLaunchKernelGGL((csr_multi_kernel<K, 2, Epi>), grid, block, 0, st, v, desc, x, epi);
-  else hipLaunchKernelGGL((csr_multi_kernel<K, 1, Epi>), grid, block, 0, st, v, desc, x, epi);
+  if (A.val32) {                                                       // fp32 storage (level operators, P, R)
+    if (mean >= 48.0) hipLaunchKernelGGL((csr_multi_kernel<K, 4, Epi, float>), grid, block, 0, st, v, desc, x, epi);
+    else if (mean >= 20.0) hipLaunchKernelGGL((csr_multi_kernel<K, 2, Epi, float>), grid, block, 0, st, v, desc, x, epi);
+    else hipLaunchKernelGGL((csr_multi_kernel<K, 1, Epi, float>), grid, block, 0, st, v, desc, x, epi);
+  } else {
+    if (mean >= 48.0) hipLaunchKernelGGL((csr_multi_kernel<K, 4, Epi>), grid, block, 0, st, v, desc, x, epi);
+    else if (mean >= 20.0) hipLaunchKernelGGL((csr_multi_kernel<K, 2, Epi>), grid, block, 0, st, v, desc, x, epi);
+    else hipLaunchKernelGGL((csr_multi_kernel<K, 1, Epi>), grid, block, 0, st, v, desc, x, epi);
+  }
   NSS_CHECK_LAUNCH();
 }
 
@@ -290,7 +299,7 @@ static int g_amg_batch = 1;
 void amg_apply(const nss_amg_s& a, double bscale, const double* b, double* x, hipStream_t st, const int32_t* done,
                bool accumulate) {
   if (a.T) {                                         // auxiliary-space mode: x (+)= T (sum_c V_c) T^T (bscale b)
-    launch_csr_stream(*a.TT, b, EpiAxpby{bscale, 0.0, a.aux_r, done}, st);
+    launch_csr_stream_any(*a.TT, b, EpiAxpby{bscale, 0.0, a.aux_r, done}, st);
     if (!a.multi.empty() && g_amg_batch) {           // one shared hierarchy: all components in one cycle
       const nss_amg_s& h = *a.comps[0];
       const int64_t n0 = h.levels[0].n;
@@ -300,7 +309,7 @@ void amg_apply(const nss_amg_s& a, double bscale, const double* b, double* x, hi
     } else
     for (size_t c = 0; c < a.comps.size(); ++c)
       cycle(*a.comps[c], 0, a.aux_r + a.comp_off[c], a.aux_z + a.comp_off[c], st, done, 1.0);
-    launch_csr_stream(*a.T, a.aux_z, EpiAxpby{1.0, accumulate ? 1.0 : 0.0, x, done}, st);
+    launch_csr_stream_any(*a.T, a.aux_z, EpiAxpby{1.0, accumulate ? 1.0 : 0.0, x, done}, st);
     return;
   }
   cycle(a, 0, b, x, st, done, bscale, accumulate);

@@ -747,6 +747,7 @@ extern "C" {
 int nss_csr_transpose(nss_csr_t a, nss_csr_t* out) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && out != nullptr, "csr_transpose: NULL argument");
+    require_f64_values(a, "csr_transpose");
     *out = transpose(*a, nullptr);
   });
 }
@@ -754,6 +755,8 @@ int nss_csr_transpose(nss_csr_t a, nss_csr_t* out) {
 int nss_csr_spgemm(nss_csr_t x, nss_csr_t y, int64_t max_products_per_pass, nss_csr_t* out, nss_stream_t stream) {
   return guarded([&] {
     NSS_REQUIRE(x != nullptr && y != nullptr && out != nullptr, "csr_spgemm: NULL argument");
+    require_f64_values(x, "csr_spgemm");
+    require_f64_values(y, "csr_spgemm");
     const int64_t cap = max_products_per_pass > 0 ? max_products_per_pass : (int64_t(1) << 27);
     RawCsr c;
     spgemm(*x, *y, as_stream(stream), cap, c);
@@ -786,6 +789,7 @@ int nss_csr_select_rows(nss_csr_t a, int32_t nrows, const int32_t* d_rows, int32
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && out != nullptr && nrows >= 0 && (nrows == 0 || d_rows != nullptr),
                 "csr_select_rows: NULL argument");
+    require_f64_values(a, "csr_select_rows");
     NSS_REQUIRE(ncuts >= 0 && (ncuts == 0 || h_cuts != nullptr), "csr_select_rows: bad cuts");
     for (int i = 0; i < ncuts; ++i)
       NSS_REQUIRE(h_cuts[i] >= 0 && h_cuts[i] <= nrows && (i == 0 || h_cuts[i] >= h_cuts[i - 1]),
@@ -826,6 +830,7 @@ int nss_csr_permute(nss_csr_t a, int32_t nrows, const int32_t* d_rows, const int
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && out != nullptr && nrows >= 0 && (nrows == 0 || d_rows != nullptr) && d_colmap != nullptr,
                 "csr_permute: NULL argument");
+    require_f64_values(a, "csr_permute");
     NSS_REQUIRE(ncols_out >= 1 && max_rows >= 0, "csr_permute: bad shape");
     NSS_REQUIRE(ncuts >= 0 && (ncuts == 0 || h_cuts != nullptr), "csr_permute: bad cuts");
     for (int i = 0; i < ncuts; ++i)
@@ -951,7 +956,13 @@ int nss_csr_download(nss_csr_t a, int32_t* h_rowptr, int32_t* h_col, double* h_v
     NSS_HIP(hipMemcpy(h_rowptr, a->rowptr, sizeof(int32_t) * (size_t(a->m) + 1), hipMemcpyDeviceToHost));
     if (a->nnz > 0) {
       NSS_HIP(hipMemcpy(h_col, a->col, sizeof(int32_t) * a->nnz, hipMemcpyDeviceToHost));
-      NSS_HIP(hipMemcpy(h_val, a->val, sizeof(double) * a->nnz, hipMemcpyDeviceToHost));
+      if (a->val32) {                                    // fp32 storage: the stored values, widened
+        std::vector<float> v32(size_t(a->nnz));
+        NSS_HIP(hipMemcpy(v32.data(), a->val32, sizeof(float) * a->nnz, hipMemcpyDeviceToHost));
+        for (int64_t p = 0; p < a->nnz; ++p) h_val[p] = double(v32[size_t(p)]);
+      } else {
+        NSS_HIP(hipMemcpy(h_val, a->val, sizeof(double) * a->nnz, hipMemcpyDeviceToHost));
+      }
     }
   });
 }
@@ -961,6 +972,7 @@ int nss_amg_aggregate(nss_csr_t a, double theta, const int64_t* d_priority, int6
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && d_priority != nullptr && d_agg != nullptr && nagg_out != nullptr,
                 "amg_aggregate: NULL argument");
+    require_f64_values(a, "amg_aggregate");
     NSS_REQUIRE(a->m == a->n, "amg_aggregate: matrix must be square");
     hipStream_t st = as_stream(stream);
     const int32_t m = a->m;
@@ -1016,6 +1028,7 @@ int nss_amg_prolongator(nss_csr_t a, const int64_t* d_agg, int64_t nagg, double 
                         nss_stream_t stream) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && d_agg != nullptr && out != nullptr, "amg_prolongator: NULL argument");
+    require_f64_values(a, "amg_prolongator");
     NSS_REQUIRE(a->m == a->n && nagg > 0 && nagg < (int64_t(1) << 31), "amg_prolongator: bad sizes");
     hipStream_t st = as_stream(stream);
     const int32_t m = a->m;

@@ -1025,7 +1025,9 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st, const nss_dist_s* d) 
     //   previous iteration's t2 was consumed by K1 / C1 and the A-SpMV has not written the new one yet)
     //   (condensed form: src = the lifted t0, the residual with the matrix of the sweeps, S = sweep_A)
     gs_forward_from_zero(s, src, st);
-    launch_csr_stream(s.sweep_A ? *s.sweep_A : *s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
+    //   (fp32 storage: sweep_A = the handle's fp32 copy of the matrix of its sweeps -- the residual with the rounded
+    //   matrix keeps the operator symmetric)
+    launch_csr_stream_any(s.sweep_A ? *s.sweep_A : *s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
     amg_apply(*s.pre_amg, 1.0, s.t2, s.t1, st, s.ctrl, true);
     bjac_smooth(*s.pre_bjac, s.k, src, s.t1, true, s.ctrl, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);   // (src again)
   } else if (s.pre_amg) {

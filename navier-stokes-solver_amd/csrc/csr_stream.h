@@ -95,7 +95,16 @@ struct CsrView {
   int32_t mode;     // how the operand is reached: 0 = 4-byte columns, gather; 1 = 16-bit window-relative columns,
                     // gather; 2 = staged (LDS copy of the row block's operand segments, 16-bit positions);
                     // 3 = pair-staged (the segments of TWO vectors, each in one half of the LDS buffer)
+  const float* __restrict__ val32;      // the 4-byte value stream of a narrowed matrix (nss_csr_s::val32), else NULL
 };
+
+// the value stream of a view as the kernels' value type VT (double: `val`; float: `val32`, widened before the product)
+template <class VT>
+__device__ __forceinline__ const VT* view_values(const CsrView& a) {
+  static_assert(std::is_same<VT, double>::value || std::is_same<VT, float>::value, "values are fp64 or fp32");
+  if constexpr (std::is_same<VT, float>::value) return a.val32;
+  else return a.val;
+}
 
 }  // namespace nss
 
@@ -184,6 +193,10 @@ struct nss_csr_s {
   int32_t* fw_col = nullptr;
   double* fw_val = nullptr;
   int fw_state = 0;
+  // fp32 value storage (nss_csr_narrow_f32): the values rounded once to fp32 and stored 4 bytes wide in `val32`; `val`
+  // is then NULL.  Only the kernel paths instantiated for it take such a matrix (launch_csr_stream_any, the joint AMG
+  // cycle); every other path refuses it (view() without `narrow_ok`, require_f64_values) -- none reads it as doubles.
+  float* val32 = nullptr;
   uint64_t jb_serial = 0;
   // `stageable`: the kernel's operand functor is one stored vector that can be copied to LDS (XOp::kStageable);
   // `pairable`: it is an expression of two (XOp::kStageablePair)
@@ -193,19 +206,28 @@ struct nss_csr_s {
     return col16 ? 1 : 0;
   }
   // launch view of the row blocks [b0, b1)
-  nss::CsrView view(int b0, int b1, int mode) const {
+  nss::CsrView view(int b0, int b1, int mode, bool narrow_ok = false) const {
+    if (val32 && !narrow_ok)
+      throw nss::Error("invalid argument: this kernel path has no form for a matrix with fp32 values (nss_csr_narrow_f32)");
     const uint64_t magic = gb > 1 ? ~uint64_t(0) / uint64_t(gb) + 1 : 0;    // ceil(2^64 / gb)
     const bool full = b0 == 0 && b1 == nblk;
     return nss::CsrView{rowblk, rowptr, col, mode >= 2 ? pos16 : (mode == 1 ? col16 : nullptr), blkbase, blkseg,
                         (mode >= 2 && full) ? blkdisp : nullptr, val,
                         uint32_t(gb), uint32_t(nss::kBlock / gb), uint32_t(nss::kBlock % gb), magic, b0, b1 - b0,
-                        (b1 - b0 + nss::kXcds - 1) / nss::kXcds, mode};
+                        (b1 - b0 + nss::kXcds - 1) / nss::kXcds, mode, val32};
   }
   // one workgroup per row block, padded to a multiple of the XCD count
   static int grid(int count) { return ((count + nss::kXcds - 1) / nss::kXcds) * nss::kXcds; }
 };
 
 namespace nss {
+
+// set-up paths that read the values as doubles (transpose, products, permutations, AMG set-up, block inverses, ...)
+inline void require_f64_values(const nss_csr_s* a, const char* who) {
+  if (a != nullptr && a->val32 != nullptr)
+    throw Error(std::string("invalid argument: ") + who + ": the matrix stores fp32 values (nss_csr_narrow_f32); this path "
+                "takes fp64 matrices only");
+}
 
 // Build col16 / blkbase of a matrix whose device arrays and launch plan are complete (spmv.hip).
 void compress_columns(nss_csr_s& A, hipStream_t st);
@@ -323,7 +345,7 @@ struct RowPrefetch {
   typename EpiPre<Epi>::type pre[KPF];
 };
 
-template <class Epi, int CH, int IDX, bool GRP, int KPF>
+template <class Epi, int CH, int IDX, bool GRP, int KPF, class VT = double>
 __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __restrict__ x, Epi& epi, int b, int p0,
                                            int cnt, double* prod, double* red, int32_t* window,
                                            RowPrefetch<Epi, KPF>& pf, int rf, int rstep, int r1) {
@@ -332,7 +354,8 @@ __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __res
   constexpr int kPer = CH / kBlock;
   const int tid = threadIdx.x;
   int32_t c[kPer];                                       // column (IDX 0), else position inside the group
-  double v[kPer];
+  const VT* __restrict__ vals = view_values<VT>(a);
+  VT v[kPer];                                            // (fp32: widened to fp64 at the product)
   uint16_t c16[kPer];
   if (IDX == 1) {
     if (tid < kWindows) window[tid] = a.blkbase[b * kWindows + tid];
@@ -357,11 +380,11 @@ __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __res
 #if NSS_STREAM_NT
     if (IDX != 0 && !GRP) c16[k] = live ? __builtin_nontemporal_load(&a.col16[p0 + i]) : uint16_t(0);
     if (IDX == 0) c[k] = live ? __builtin_nontemporal_load(&a.col[p0 + i]) : 0;
-    v[k] = live ? __builtin_nontemporal_load(&a.val[p0 + i]) : 0.0;
+    v[k] = live ? __builtin_nontemporal_load(&vals[p0 + i]) : VT(0);
 #else
     if (IDX != 0 && !GRP) c16[k] = live ? a.col16[p0 + i] : uint16_t(0);
     if (IDX == 0) c[k] = live ? a.col[p0 + i] : 0;
-    v[k] = live ? a.val[p0 + i] : 0.0;
+    v[k] = live ? vals[p0 + i] : VT(0);
 #endif
   }
   // behind the matrix stream and in the same straight-line code (requested in front of it, the register
@@ -416,7 +439,7 @@ __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __res
   }
 #pragma unroll
   for (int k = 0; k < kPer; ++k)
-    if (tid + k * kBlock < cnt) prod[tid + k * kBlock] = v[k] * xv[k];
+    if (tid + k * kBlock < cnt) prod[tid + k * kBlock] = double(v[k]) * xv[k];
   return true;
 }
 
@@ -429,7 +452,7 @@ typedef const __attribute__((address_space(1))) void* GlobalSrc;
 // operators -- with alternative paths in one kernel hipcc's wait-count insertion turns conservative at the joins
 // and waits for vmcnt(0) in the middle of the matrix stream (seen in the ISA).  The one run-time branch left is
 // the staged kernel's fallback for row blocks that do not fit the LDS copy.
-template <int RG, class Epi, int IDX, int CH, bool GRP>
+template <int RG, class Epi, int IDX, int CH, bool GRP, class VT = double>
 __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* __restrict__ x, Epi& epi, int wg,
                                                 double* prod, double* red, int32_t* window) {
   using XOp = typename EpiX<Epi>::type;
@@ -517,7 +540,7 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
       constexpr int kPer = CH / kBlock;
       (void)kPer;
       // ---- phase 1: coalesced stream of (col, val), operand, stage products ------------
-      const bool go = csr_phase1<Epi, CH, IDX, GRP, kPF>(a, x, epi, b, p0, cnt, prod, red, window, pf, rf, kBlock / RG, r1);
+      const bool go = csr_phase1<Epi, CH, IDX, GRP, kPF, VT>(a, x, epi, b, p0, cnt, prod, red, window, pf, rf, kBlock / RG, r1);
       if (!go) return;                                     // the prologue ended the workgroup (uniform)
       __syncthreads();
       // ---- phase 2: per-row reduction from LDS -----------------------------------------
@@ -567,7 +590,8 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
       if (!EpiPrologue<Epi>::run(epi, red)) return;
       const XOp xop = EpiX<Epi>::get(epi, x);
       double acc = 0.0;
-      for (int i = tid; i < cnt; i += kBlock) acc = fma(a.val[p0 + i], xop(a.col[p0 + i]), acc);
+      const VT* __restrict__ vals = view_values<VT>(a);
+      for (int i = tid; i < cnt; i += kBlock) acc = fma(double(vals[p0 + i]), xop(a.col[p0 + i]), acc);
       const double sum = block_sum(acc, red);
       if (tid == 0) EpiPre<Epi>::row(epi, r0, sum, EpiPre<Epi>::fetch(epi, r0));
     }
@@ -575,13 +599,13 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
   epi.finish(b, red);  // one dot partial per row block
 }
 
-template <int RG, class Epi, int IDX = 0, int CH = kChunk, bool GRP = false>
+template <int RG, class Epi, int IDX = 0, int CH = kChunk, bool GRP = false, class VT = double>
 __global__ __launch_bounds__(kBlock) void csr_stream_kernel(CsrView a, const double* __restrict__ x, Epi epi) {
   __shared__ double prod[CH];
   __shared__ double red[kRedDoubles];
   __shared__ int32_t window[kWindows];
   if (epi.skip()) return;
-  csr_stream_body<RG, Epi, IDX, CH, GRP>(a, x, epi, int(blockIdx.x), prod, red, window);
+  csr_stream_body<RG, Epi, IDX, CH, GRP, VT>(a, x, epi, int(blockIdx.x), prod, red, window);
 }
 
 // Two matrices with the same launch-plan parameters in ONE launch: two SpMVs that do not depend on each other
@@ -697,7 +721,39 @@ inline void launch_csr_direct(const nss_csr_s& A, const double* x, const Epi& ep
   NSS_CHECK_LAUNCH();
 }
 
-// rows of the row blocks [b0, b1) (default: all)
+// the stream kernel over the row blocks [b0, b1) with value type VT (A is not empty and has no fixed-width copy)
+template <class Epi, class VT>
+inline void launch_csr_stream_vt(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0, int b1,
+                                 size_t dyn_lds) {
+  constexpr bool kCanStage = EpiX<Epi>::type::kStageable;
+  constexpr bool kCanPair = XPairable<typename EpiX<Epi>::type>::value;
+  const int mode = A.idx_mode(kCanStage, kCanPair);
+  const bool grp = mode != 0 && A.gb > 1;
+  const CsrView v = A.view(b0, b1, mode, std::is_same<VT, float>::value);
+  const dim3 grid(nss_csr_s::grid(b1 - b0)), block(kBlock);
+#define NSS_LAUNCH_ONE(N, CHK)                                                                                  \
+  if (mode == 2) {                                                                                               \
+    if constexpr (kCanStage) {                                                                                   \
+      if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, true, VT>), grid, block, dyn_lds, st, v, x, epi);     \
+      else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);        \
+    }                                                                                                            \
+  } else if (mode == 3) {                                                                                        \
+    if constexpr (kCanPair) {                                                                                    \
+      if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, true, VT>), grid, block, dyn_lds, st, v, x, epi);     \
+      else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);        \
+    }                                                                                                            \
+  } else if (mode == 1) {                                                                                        \
+    if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, true, VT>), grid, block, dyn_lds, st, v, x, epi);       \
+    else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);          \
+  } else {                                                                                                       \
+    hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 0, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);               \
+  }
+  NSS_FOR_PLAN(A, NSS_LAUNCH_ONE)
+#undef NSS_LAUNCH_ONE
+  NSS_CHECK_LAUNCH();
+}
+
+// rows of the row blocks [b0, b1) (default: all); fp64 values only (a narrowed matrix is refused: view())
 template <class Epi>
 inline void launch_csr_stream(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
                               int b1 = -1, size_t dyn_lds = 0) {
@@ -707,32 +763,24 @@ inline void launch_csr_stream(const nss_csr_s& A, const double* x, const Epi& ep
     launch_csr_direct(A, x, epi, st, b0, b1, dyn_lds);
     return;
   }
-  constexpr bool kCanStage = EpiX<Epi>::type::kStageable;
-  constexpr bool kCanPair = XPairable<typename EpiX<Epi>::type>::value;
-  const int mode = A.idx_mode(kCanStage, kCanPair);
-  const bool grp = mode != 0 && A.gb > 1;
-  const CsrView v = A.view(b0, b1, mode);
-  const dim3 grid(nss_csr_s::grid(b1 - b0)), block(kBlock);
-#define NSS_LAUNCH_ONE(N, CHK)                                                                                  \
-  if (mode == 2) {                                                                                               \
-    if constexpr (kCanStage) {                                                                                   \
-      if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, true>), grid, block, dyn_lds, st, v, x, epi);     \
-      else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, false>), grid, block, dyn_lds, st, v, x, epi);        \
-    }                                                                                                            \
-  } else if (mode == 3) {                                                                                        \
-    if constexpr (kCanPair) {                                                                                    \
-      if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, true>), grid, block, dyn_lds, st, v, x, epi);     \
-      else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, false>), grid, block, dyn_lds, st, v, x, epi);        \
-    }                                                                                                            \
-  } else if (mode == 1) {                                                                                        \
-    if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, true>), grid, block, dyn_lds, st, v, x, epi);       \
-    else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, false>), grid, block, dyn_lds, st, v, x, epi);          \
-  } else {                                                                                                       \
-    hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 0, CHK, false>), grid, block, dyn_lds, st, v, x, epi);               \
+  launch_csr_stream_vt<Epi, double>(A, x, epi, st, b0, b1, dyn_lds);
+}
+
+// as launch_csr_stream, and a matrix with fp32 values (nss_csr_s::val32) takes the fp32 instantiation.  Used only
+// where an fp32-storage preconditioner handle launches (the colour launches and residuals of the Gauss-Seidel sweep,
+// the single-vector AMG cycle, the residual between the half-sweeps, the plain SpMV): the value type is a template
+// parameter of the kernels, so every use doubles the instantiations of its epilogue.
+template <class Epi>
+inline void launch_csr_stream_any(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
+                                  int b1 = -1, size_t dyn_lds = 0) {
+  if (!A.val32) {
+    launch_csr_stream(A, x, epi, st, b0, b1, dyn_lds);
+    return;
   }
-  NSS_FOR_PLAN(A, NSS_LAUNCH_ONE)
-#undef NSS_LAUNCH_ONE
-  NSS_CHECK_LAUNCH();
+  if (b1 < 0) b1 = A.nblk;
+  if (A.m == 0 || b1 <= b0) return;
+  NSS_REQUIRE(!A.ell_col, "csr_stream: a matrix with fp32 values has no fixed-width copy");
+  launch_csr_stream_vt<Epi, float>(A, x, epi, st, b0, b1, dyn_lds);
 }
 
 // A and B in one launch when their launch plans agree (lanes per row, chunk) and the pair of column streams is
@@ -745,6 +793,7 @@ inline bool launch_csr_stream_dual(const nss_csr_s& A, const double* xa, const E
 #endif
   if (A.m == 0 || B.m == 0 || A.nblk == 0 || B.nblk == 0) return false;
   if (A.ell_col || B.ell_col) return false;               // row-per-lane kernel: a launch of its own
+  if (A.val32 || B.val32) return false;                   // fp32 values: the single-matrix launches (or their refusal)
   if (A.rg != B.rg || A.chunk != B.chunk) return false;
   constexpr bool kStageA = EpiX<EpiA>::type::kStageable, kStageB = EpiX<EpiB>::type::kStageable;
   constexpr bool kPairB = XPairable<typename EpiX<EpiB>::type>::value;

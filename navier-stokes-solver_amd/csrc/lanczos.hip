@@ -363,7 +363,7 @@ static int lz_precondition(const nss_lanczos_t& s, const double* x, double* z, d
       NSS_HIP(hipMemsetAsync(z, 0, sizeof(double) * size_t(s.n), st));
       bjac_smooth(*s.pre_bjac, 1.0, x, z, false, done, st);
     }
-    launch_csr_stream(s.sweep_A ? *s.sweep_A : *s.A, z, EpiLzResidual{done, x, scratch}, st);
+    launch_csr_stream_any(s.sweep_A ? *s.sweep_A : *s.A, z, EpiLzResidual{done, x, scratch}, st);
     amg_apply(*s.pre_amg, 1.0, scratch, z, st, done, true);
     bjac_smooth(*s.pre_bjac, 1.0, x, z, true, done, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);
     if (s.pre_scale != 1.0) {

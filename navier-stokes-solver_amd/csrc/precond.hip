@@ -357,7 +357,7 @@ static void gs_sweep_permuted(const nss_bjac_s& j, double xscale, bool backward,
       }
       continue;
     }
-    launch_csr_stream(*j.gs_mat, j.yt, epi, st, j.color_rowblk[c], j.color_rowblk[c + 1], sizeof(double) * kGsRows);
+    launch_csr_stream_any(*j.gs_mat, j.yt, epi, st, j.color_rowblk[c], j.color_rowblk[c + 1], sizeof(double) * kGsRows);
   }
 }
 
@@ -414,7 +414,7 @@ void bjac_smooth(const nss_bjac_s& j, double xscale, const double* x, double* y,
   const int nc = int(j.color_ptr.size()) - 1;
   for (int k = 0; k < nc; ++k) {
     const int c = backward ? nc - 1 - k : k;
-    launch_csr_stream(*j.gs_mat, y, EpiGsResidual{done, j.rowdof, x, j.res, xscale}, st, j.color_rowblk[c],
+    launch_csr_stream_any(*j.gs_mat, y, EpiGsResidual{done, j.rowdof, x, j.res, xscale}, st, j.color_rowblk[c],
                       j.color_rowblk[c + 1]);
     switch (j.bs) {
 #define NSS_GS(N) case N: launch_bgs_solve<N>(j, c, y, done, st); break;
@@ -510,6 +510,7 @@ extern "C" {
 int nss_bjac_create(nss_csr_t a, int32_t bs, int32_t nblocks, const int32_t* h_idx, nss_bjac_t* out) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && out != nullptr && h_idx != nullptr, "bjac_create: NULL argument");
+    require_f64_values(a, "bjac_create");
     NSS_REQUIRE(a->m == a->n, "bjac_create: matrix must be square");
     NSS_REQUIRE(bs >= 1 && bs <= kMaxBs, "bjac_create: 1 <= bs <= 16");
     NSS_REQUIRE(nblocks >= 1, "bjac_create: need at least one block");

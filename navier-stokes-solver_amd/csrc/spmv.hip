@@ -613,6 +613,7 @@ __global__ __launch_bounds__(kBlock) void ell_build_kernel(int32_t m, const int3
 
 static void direct_rows(nss_csr_s& A, hipStream_t st) {
 #if NSS_DIRECT_ROWS
+  if (A.val32) return;                                   // (fp32 values: the stream kernel only)
   if (A.m < g_direct_min_rows || A.nnz > int64_t(kDirectWidth) * A.m) return;
   int32_t* ecol = nullptr;
   double* eval = nullptr;
@@ -663,6 +664,17 @@ void compress_columns(nss_csr_s& A, hipStream_t st) {
   (void)A;
   (void)st;
 #endif
+}
+
+// fp64 values rounded to the nearest fp32, kept 8 bytes wide (out == in) or stored 4 bytes wide
+__global__ __launch_bounds__(kBlock) void round_f32_kernel(int64_t n, const double* __restrict__ in, double* out64,
+                                                            float* __restrict__ out32) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+    const float v = float(in[i]);
+    if (out32) out32[i] = v;
+    else out64[i] = double(v);
+  }
 }
 
 __global__ __launch_bounds__(kBlock) void csr_diag_kernel(int32_t m, const int32_t* __restrict__ rowptr,
@@ -739,6 +751,7 @@ int nss_csr_destroy(nss_csr_t a) {
     (void)hipFree(a->rowptr);
     (void)hipFree(a->col);
     (void)hipFree(a->val);
+    (void)hipFree(a->val32);
     (void)hipFree(a->rowblk);
     (void)hipFree(a->col16);
     (void)hipFree(a->blkbase);
@@ -813,6 +826,7 @@ namespace nss {
 bool fixed_width_copy(nss_csr_s& A) {
   if (A.fw_state != 0) return A.fw_state > 0;
   A.fw_state = -1;
+  if (A.val32) return false;                             // (no fp32 form of the epilogue copy)
   if (A.ell_col) {
     A.fw_col = A.ell_col;
     A.fw_val = A.ell_val;
@@ -960,7 +974,7 @@ int nss_csr_spmv_f64(nss_csr_t a, double alpha, const double* x, double beta, do
   return guarded([&] {
     NSS_REQUIRE(a != nullptr, "csr_spmv: NULL matrix");
     NSS_REQUIRE(x != y, "csr_spmv: x must not alias y");
-    launch_csr_stream(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
+    launch_csr_stream_any(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
   });
 }
 
@@ -1009,10 +1023,79 @@ int nss_csr_info(nss_csr_t a, int32_t* nrows, int32_t* ncols, int64_t* nnz, int3
     if (algorithmic_bytes && a->ell_col)      // fixed-width copy: 12 bytes per slot, no row pointers
       *algorithmic_bytes = int64_t(12) * nss::kDirectWidth * a->m + 8 * int64_t(a->n) + 8 * int64_t(a->m);
     else if (algorithmic_bytes)
-      *algorithmic_bytes = ((a->col16 || a->pos16) ? 8 * a->nnz + 2 * (a->nnz / a->gb) +
+      *algorithmic_bytes = ((a->col16 || a->pos16) ? 2 * (a->nnz / a->gb) +
                                                            int64_t(4) * (a->blkseg ? kSegWords : kWindows) * a->nblk
-                                                     : 12 * a->nnz) +
+                                                     : 4 * a->nnz) +
+                           (a->val32 ? 4 : 8) * a->nnz +
                            4 * (int64_t(a->m) + 1) + 8 * int64_t(a->n) + 8 * int64_t(a->m);
+  });
+}
+
+int nss_csr_round_f32(nss_csr_t a, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr, "csr_round_f32: NULL matrix");
+    require_f64_values(a, "csr_round_f32");
+    if (a->nnz == 0) return;
+    hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(a->nnz, kBlock * 4)), dim3(kBlock), 0, as_stream(stream), a->nnz,
+                       a->val, a->val, (float*)nullptr);
+    NSS_CHECK_LAUNCH();
+    if (a->ell_val) {                                    // (the fixed-width copy holds the values too; fw_val aliases it)
+      hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(int64_t(kDirectWidth) * a->m, kBlock * 4)), dim3(kBlock), 0,
+                         as_stream(stream), int64_t(kDirectWidth) * a->m, a->ell_val, a->ell_val, (float*)nullptr);
+      NSS_CHECK_LAUNCH();
+    }
+    if (a->fw_val && a->fw_val != a->ell_val) {
+      hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(int64_t(kDirectWidth) * a->m, kBlock * 4)), dim3(kBlock), 0,
+                         as_stream(stream), int64_t(kDirectWidth) * a->m, a->fw_val, a->fw_val, (float*)nullptr);
+      NSS_CHECK_LAUNCH();
+    }
+  });
+}
+
+int nss_csr_narrow_f32(nss_csr_t a, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr, "csr_narrow_f32: NULL matrix");
+    if (a->val32) return;                                // already narrow
+    float* v32 = nullptr;
+    NSS_HIP(hipMalloc(&v32, sizeof(float) * size_t(a->nnz + 4)));   // (+4 as `val`: paired loads may touch the end)
+    try {
+      NSS_HIP(hipMemsetAsync(v32, 0, sizeof(float) * size_t(a->nnz + 4), as_stream(stream)));
+      if (a->nnz > 0) {
+        hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(a->nnz, kBlock * 4)), dim3(kBlock), 0, as_stream(stream),
+                           a->nnz, a->val, (double*)nullptr, v32);
+        NSS_CHECK_LAUNCH();
+      }
+      NSS_HIP(hipStreamSynchronize(as_stream(stream)));
+      NSS_HIP(hipDeviceSynchronize());                   // no kernel may still read the arrays that go away
+    } catch (...) {
+      (void)hipFree(v32);
+      throw;
+    }
+    // the fp64 values and every copy of them go; the fixed-width copies have no fp32 form (the stream kernel takes
+    // the matrix), and none is built again (direct_rows, fixed_width_copy)
+    if (a->fw_val && a->fw_val != a->ell_val) {
+      (void)hipFree(a->fw_col);
+      (void)hipFree(a->fw_val);
+    }
+    a->fw_col = nullptr;
+    a->fw_val = nullptr;
+    a->fw_state = -1;
+    const bool had_ell = a->ell_col != nullptr;
+    (void)hipFree(a->ell_col);
+    (void)hipFree(a->ell_val);
+    a->ell_col = nullptr;
+    a->ell_val = nullptr;
+    (void)hipFree(a->val);
+    a->val = nullptr;
+    a->val32 = v32;
+    if (had_ell && a->blkseg && !a->blkdisp) build_dispatch(*a, nullptr);
+  });
+}
+
+int nss_csr_value_bytes(nss_csr_t a, int64_t* bytes) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr && bytes != nullptr, "csr_value_bytes: NULL argument");
+    *bytes = (a->val32 ? int64_t(sizeof(float)) : int64_t(sizeof(double))) * a->nnz;
   });
 }
 
@@ -1027,6 +1110,7 @@ int nss_csr_row_blocks(nss_csr_t a, int32_t* h_out, int64_t cap) {
 int nss_csr_diagonal(nss_csr_t a, double* diag_dev, nss_stream_t stream) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr, "csr_diagonal: NULL matrix");
+    require_f64_values(a, "csr_diagonal");
     if (a->m == 0) return;
     hipLaunchKernelGGL(csr_diag_kernel, dim3((a->m + kBlock - 1) / kBlock), dim3(kBlock), 0, as_stream(stream),
                        a->m, a->rowptr, a->col, a->val, diag_dev);

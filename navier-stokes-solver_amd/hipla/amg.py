@@ -29,7 +29,7 @@ import os
 import numpy as np
 import scipy.sparse as sp
 
-from .matrix import BaseMatrix, SparseMatrix
+from .matrix import BaseMatrix, SparseMatrix, check_storage, fp32_copy, value_bytes
 
 
 def _priorities(n, seed):
@@ -93,14 +93,26 @@ def build_hierarchy(mat, max_levels=10, coarse_size=2000, omega=2.0 / 3.0, seed=
         A = SparseMatrix.from_handle(eng.csr_spgemm(R.handle, AP), eng)
 
 
+def stored_levels(levels, storage):
+    """The levels the cycle applies: `levels` itself for "fp64"; for "fp32" the same levels with own fp32 copies of every
+    level operator, P and R (the smoother diagonals and the coarse inverse stay fp64, as computed)."""
+    if storage == "fp64":
+        return levels
+    return [dict(lv, **{key: fp32_copy(lv[key]) for key in ("A", "P", "R") if key in lv}) for lv in levels]
+
+
 class SmoothedAggregationAMG(BaseMatrix):
     """``y = V(x)``: one symmetric V(1,1)-cycle of the smoothed-aggregation hierarchy of `mat`
-    (a `SparseMatrix`), set up and applied on the engine."""
+    (a `SparseMatrix`), set up and applied on the engine.
 
-    def __init__(self, mat, max_levels=10, coarse_size=2000, omega=2.0 / 3.0, seed=0, theta=0.04):
+    `storage`: "fp64" (default) or "fp32" -- set-up as for "fp64", then the cycle applies fp32 copies of every level
+    operator, P and R (`applied_levels`; R = P^T stays exact, the cycle stays symmetric); `levels` keeps the fp64 set-up."""
+
+    def __init__(self, mat, max_levels=10, coarse_size=2000, omega=2.0 / 3.0, seed=0, theta=0.04, storage="fp64"):
         super().__init__()
         if not isinstance(mat, SparseMatrix):
             raise TypeError("SmoothedAggregationAMG needs a SparseMatrix")
+        self.storage = check_storage(storage)
         self.engine = mat.engine
         self.mat = mat
         self.n = mat.height
@@ -108,7 +120,12 @@ class SmoothedAggregationAMG(BaseMatrix):
         self.levels = build_hierarchy(mat, max_levels, coarse_size, omega, seed, theta)
         self.level_sizes = [lv["n"] for lv in self.levels]
         self.operator_complexity = sum(lv["A"].nnz for lv in self.levels) / mat.nnz
-        self.handle = self.engine.amg_create(self.levels, self.omega)
+        self.applied_levels = stored_levels(self.levels, storage)
+        self.handle = self.engine.amg_create(self.applied_levels, self.omega)
+
+    def value_bytes(self):
+        """Bytes of the matrix values one cycle streams per pass: level operators, P and R (the coarse inverse apart)."""
+        return sum(value_bytes(lv[key]) for lv in self.applied_levels for key in ("A", "P", "R") if key in lv)
 
     def Height(self):
         return self.n
@@ -137,8 +154,11 @@ class AuxiliarySpaceAMG(SmoothedAggregationAMG):
     fused Krylov loops apply it wherever they accept a V-cycle, alone or added to a (block) Jacobi
     (the additive ``MypreA``, :383)."""
 
-    def __init__(self, transform, components):
+    def __init__(self, transform, components, storage="fp64"):
+        """`storage`: "fp64" (default) or "fp32" -- T and T^T are applied as fp32 copies; the components keep the
+        storage they were built with (either is accepted)."""
         BaseMatrix.__init__(self)
+        self.storage = check_storage(storage)
         if not isinstance(transform, SparseMatrix) or not all(type(c) is SmoothedAggregationAMG for c in components):
             raise TypeError("AuxiliarySpaceAMG needs a SparseMatrix transform and plain V-cycles")
         if sum(c.n for c in components) != transform.width:
@@ -150,5 +170,15 @@ class AuxiliarySpaceAMG(SmoothedAggregationAMG):
         self.mat = None
         self.levels = []
         self.level_sizes = [c.level_sizes for c in components]
-        self.handle = self.engine.amg_create_auxiliary(transform.handle, self.transform_t.handle,
+        if storage == "fp32":
+            self.applied_transform, self.applied_transform_t = fp32_copy(transform), fp32_copy(self.transform_t)
+        else:
+            self.applied_transform, self.applied_transform_t = transform, self.transform_t
+        self.handle = self.engine.amg_create_auxiliary(self.applied_transform.handle, self.applied_transform_t.handle,
                                                        [c.handle for c in components])
+
+    def value_bytes(self):
+        """Bytes of the matrix values the term streams: T, T^T and the components' cycles (a shared hierarchy once)."""
+        comps = {id(c): c for c in self.components}
+        return (value_bytes(self.applied_transform) + value_bytes(self.applied_transform_t)
+                + sum(c.value_bytes() for c in comps.values()))

@@ -90,6 +90,8 @@ def _native_lanczos(mat, pre, start, tol, maxsteps, check_every, sweep_A=None):
     fused.write_pre(st, pa)
     st.pre_scale = float(pa.scale)
     st.sweep_A = sweep_A.handle.ptr if sweep_A is not None else None
+    if pa.multiplicative and fused.own_residual_matrix(pa.bjac) is not None:
+        st.sweep_A = fused.own_residual_matrix(pa.bjac).handle.ptr        # fp32 storage: the handle's own copy
     vecs = [eng.zeros(n) for _ in range(6)]
     eng.copy(start.buf, vecs[0])
     for i in range(3):

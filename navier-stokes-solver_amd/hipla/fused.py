@@ -105,6 +105,20 @@ def native_velocity_pre(op):
     return PreParts(scale, diag, bjac, amg, False)
 
 
+def own_residual_matrix(bjac):
+    """The matrix the residual between the half-sweeps of a multiplicative MypreA must be formed with when it is not the
+    loop's own (A, or S in the condensed form): the handle's fp32 copy of round32(A) / round32(S) under fp32 storage --
+    the residual with the rounded matrix keeps the operator symmetric.  None for fp64 storage."""
+    if getattr(bjac, "storage", "fp64") == "fp32":
+        return bjac.residual_mat
+    return None
+
+
+def fp32_storage(pa):
+    """Whether any part of the PreParts `pa` stores its matrices in fp32."""
+    return pa is not None and any(getattr(part, "storage", "fp64") == "fp32" for part in (pa.bjac, pa.amg))
+
+
 def native_diag(op):
     """The `PreParts` of a (scaled) diagonal preconditioner (preM, preS), else None."""
     p = native_velocity_pre(op)
@@ -238,6 +252,8 @@ def attach_condensed(bjac, condensed):
     (nss_bjac_set_condensed) when `condensed_fusable` holds.  Returns (attached, reason)."""
     import scipy.sparse as sp
     ok, why = condensed_fusable(bjac, condensed)
+    if ok and getattr(bjac, "storage", "fp64") == "fp32":
+        ok, why = False, "fp32 storage: the fused condensed forms have no fp32 kernels (the straightforward sequence runs)"
     eng = bjac.engine
     if not ok:
         if hasattr(eng, "lib"):
@@ -347,6 +363,8 @@ class Bpcg2Loop(FusedLoop):
             return "preM is not a (scaled) diagonal"
         if pa is None:
             return "preA is not native"
+        if distributed and fp32_storage(pa):
+            return "fp32 preconditioner storage on a partitioned run (the row-partitioned preconditioners are fp64)"
         if pa.multiplicative:
             # the sweeps' residual is formed with the loop's own A -- or, condensed, with the Schur complement S
             if distributed:
@@ -403,6 +421,9 @@ class Bpcg2Loop(FusedLoop):
                 # the sweep's handle, kept alive with the loop; otherwise the straightforward sequence
                 self.cond_fusable, self.cond_fuse_declined = attach_condensed(pa.bjac, condensed)
                 self.keep.append(pa.bjac)
+        if pa.multiplicative and not distributed and own_residual_matrix(pa.bjac) is not None:
+            # fp32 storage: the residual between the sweeps with the handle's fp32 copy of the matrix of its sweeps
+            st.sweep_A = own_residual_matrix(pa.bjac).handle.ptr
         # the rows of B multiply t1 - s0 (:212-213): with row blocks short enough both vectors are read from LDS copies
         self.pair_staged_b = (os.environ.get("NSS_PAIR_STAGE", "1") == "1" and hasattr(matB.handle, "plan_for_pairs")
                               and matB.handle.plan_for_pairs())

@@ -45,6 +45,9 @@ def _signatures():
         "nss_csr_transpose": (C.c_int, [vp, C.POINTER(vp)]),
         "nss_csr_spgemm": (C.c_int, [vp, vp, i64, C.POINTER(vp), vp]),
         "nss_csr_download": (C.c_int, [vp, vp, vp, vp]),
+        "nss_csr_round_f32": (C.c_int, [vp, vp]),
+        "nss_csr_narrow_f32": (C.c_int, [vp, vp]),
+        "nss_csr_value_bytes": (C.c_int, [vp, c_i64_p]),
         "nss_csr_index_width": (C.c_int, [vp, c_i32_p]),
         "nss_csr_index_group": (C.c_int, [vp, c_i32_p]),
         "nss_csr_operand_form": (C.c_int, [vp, c_i32_p]),
@@ -446,6 +449,21 @@ class HipEngine:
         self._check(self.lib.nss_csr_download(h.ptr, rowptr.ctypes.data, col.ctypes.data if h.nnz else None,
                                               val.ctypes.data if h.nnz else None))
         return rowptr, col, val
+
+    # ---- fp32 value storage of preconditioner matrices ----------------------------------------------------------
+    def csr_round_f32(self, h):
+        """Round the values of `h` (a matrix nobody else holds) to fp32 in place, keeping 8-byte storage."""
+        self._check(self.lib.nss_csr_round_f32(h.ptr, self.stream))
+
+    def csr_narrow_f32(self, h):
+        """Store the values of `h` (a matrix nobody else holds) 4 bytes wide, in place (`nss_csr_narrow_f32`)."""
+        self._check(self.lib.nss_csr_narrow_f32(h.ptr, self.stream))
+
+    def csr_value_bytes(self, h):
+        """Bytes of the stored value stream of `h` (8 or 4 per entry)."""
+        out = C.c_int64()
+        self._check(self.lib.nss_csr_value_bytes(h.ptr, C.byref(out)))
+        return out.value
 
     def csr_inverse_diagonal(self, h):
         """Device buffer 1 / diag(A)."""

@@ -488,6 +488,79 @@ class SparseMatrix(BaseMatrix):
         return BlockJacobi(self, blocks)
 
 
+# ---- fp32 value storage of preconditioner matrices -------------------------------------------------------------------
+# A preconditioner need not stream fp64 coefficients: with storage="fp32" every matrix it streams is rounded ONCE to
+# fp32 (entrywise: a symmetric matrix stays symmetric, R = P^T stays exact) and, on the HIP engine, stored 4 bytes wide;
+# vectors and arithmetic stay fp64.  The operator is then exactly the fp64 operator of the rounded matrices -- linear and
+# symmetric as before.  Engines without fp32 storage (the numpy checker) keep the rounded values in float64.
+STORAGES = ("fp64", "fp32")
+
+
+def check_storage(storage):
+    if storage not in STORAGES:
+        raise ValueError("storage: 'fp64' (default) or 'fp32' -- the value storage of the preconditioner's matrices; "
+                         "got %r" % (storage,))
+    return storage
+
+
+def round32(csr):
+    """scipy CSR matrix with every value rounded to the nearest fp32 (kept as float64)."""
+    out = csr.tocsr().copy()
+    out.data = out.data.astype(np.float32).astype(np.float64)
+    return out
+
+
+def rounded_copy(mat):
+    """An own copy of `mat` with its values rounded to fp32, stored as fp64 (`nss_csr_round_f32`)."""
+    eng = mat.engine
+    if hasattr(eng, "csr_round_f32"):
+        h = eng.csr_select_rows(mat.handle, np.arange(mat.height, dtype=np.int32))
+        eng.csr_round_f32(h)
+        return SparseMatrix.from_handle(h, eng)
+    return SparseMatrix.from_scipy(round32(mat.to_scipy()), engine=eng)
+
+
+def _has_fp32_storage(engine):
+    """Whether `engine` stores fp32 values (the HIP engine must: a missing entry point is an error, never a silent
+    fallback to fp64 storage of the rounded values); the numpy checker keeps them in float64."""
+    if hasattr(engine, "csr_narrow_f32") and hasattr(engine, "csr_value_bytes"):
+        return True
+    if getattr(engine, "name", "") == "hip-gfx950":
+        raise RuntimeError("the HIP engine lacks the fp32 storage entry points (nss_csr_narrow_f32)")
+    return False
+
+
+def narrow_in_place(mat, engine):
+    """Store the (already fp32-representable) values of `mat` (a SparseMatrix or an engine handle of `engine`), a
+    matrix nobody else holds, 4 bytes wide."""
+    handle = mat.handle if isinstance(mat, SparseMatrix) else mat
+    if _has_fp32_storage(engine):
+        engine.csr_narrow_f32(handle)
+    if isinstance(mat, SparseMatrix):
+        mat._host = None
+        mat._transpose = None
+    return mat
+
+
+def fp32_copy(mat):
+    """An own copy of `mat` with its values rounded to fp32 and stored 4 bytes wide (float64 on engines without fp32
+    storage)."""
+    return narrow_in_place(rounded_copy(mat), mat.engine)
+
+
+def value_bytes(mat, engine=None):
+    """Bytes of the stored value stream of a `SparseMatrix`, or of an engine handle of `engine`."""
+    if isinstance(mat, SparseMatrix):
+        engine, handle = mat.engine, mat.handle
+    elif engine is None:
+        raise TypeError("value_bytes of an engine handle needs its engine")
+    else:
+        handle = mat
+    if _has_fp32_storage(engine):
+        return engine.csr_value_bytes(handle)
+    return 8 * int(handle.mat.nnz)
+
+
 class DiagonalMatrix(BaseMatrix):
     """``y = diag(d) x`` with ``d`` resident in engine memory (``diag_scale_f64``)."""
 
@@ -622,7 +695,7 @@ class BlockGaussSeidel(BaseMatrix):
     (``nss_bjac_smooth_f64``); the ordering differs from NGSolve's mesh-facet order (upstream,
     not visible), so iteration counts are pinned against the build's own CPU oracle only."""
 
-    def __init__(self, mat, blocks, seed=0, colors=None, middle=None, layout=None, coloring_method=None):
+    def __init__(self, mat, blocks, seed=0, colors=None, middle=None, layout=None, coloring_method=None, storage="fp64"):
         """`colors` (one int per block) may be supplied when the system has already been
         re-ordered colour-major on the host (`coloring.colour_permutation`): the sweep then
         touches x, y and the inverse blocks contiguously.
@@ -639,12 +712,20 @@ class BlockGaussSeidel(BaseMatrix):
 
         `middle` (an operator M, e.g. the auxiliary-space term ``T @ AMG @ T.T``) reproduces the
         full ``MypreA.Mult`` of the reference with ``GS=True`` (:376-381):
-        ``y = 0; Smooth(y, x); r = x - A y; y += M r; SmoothBack(y, x)``."""
+        ``y = 0; Smooth(y, x); r = x - A y; y += M r; SmoothBack(y, x)``.
+
+        `storage`: "fp64" (default) or "fp32" -- the handle is built from ``round32(mat)`` (block inverses: fp64 inverses
+        of the rounded diagonal blocks), its sweep matrix then stores 4-byte values, and the residual between the
+        half-sweeps is formed with the handle's own fp32 copy of ``round32(mat)`` (`residual_mat`; kept only with a
+        `middle` term), never with `mat`: so the operator stays exactly symmetric.  `mat` itself is not touched."""
         super().__init__()
         from . import coloring
         self.engine = mat.engine
         self.mat = mat
         self.middle = middle
+        self.storage = check_storage(storage)
+        src = mat if storage == "fp64" else rounded_copy(mat)     # (the handle's own copy: narrowed at the end)
+        self.residual_mat = src
         self.n = mat.height
         import os
         base = BlockJacobi._as_table(blocks)
@@ -661,7 +742,7 @@ class BlockGaussSeidel(BaseMatrix):
             # Luby rounds (device): proper colourings by construction
             colors = self._device_colors(mat, base, seed, method)
         else:
-            graph = coloring.block_graph(mat.to_scipy(), base)
+            graph = coloring.block_graph(src.to_scipy(), base)
             if colors is None:
                 colors = coloring.color_blocks_greedy(graph) if method == "greedy" else coloring.color_blocks(graph, seed)
             colors = np.asarray(colors, dtype=np.int32)
@@ -673,7 +754,7 @@ class BlockGaussSeidel(BaseMatrix):
         self.color_ptr = ptr
         self.ncolors = int(ptr.size - 1)
         self.bs, self.nblocks = self.idx_host.shape
-        self.handle = self.engine.bjac_create(mat.handle, self.idx_host)
+        self.handle = self.engine.bjac_create(src.handle, self.idx_host)
         # rows of A re-ordered block by block in colour-major order (columns unchanged): the
         # residual of one colour becomes a streaming SpMV over a contiguous row range
         live = self.idx_host.T >= 0                                  # (nblocks, bs), block-major
@@ -695,21 +776,38 @@ class BlockGaussSeidel(BaseMatrix):
             colmap[rowdof] = np.arange(n_perm, dtype=np.int32)
             colmap[uncovered] = n_perm + np.arange(uncovered.size, dtype=np.int32)
             pos = (np.arange(n_perm, dtype=np.int64) - np.repeat(block_row0[:-1], rows_per_block)).astype(np.uint8)
-            self.perm_handle = self.engine.csr_permute(mat.handle, rowdof, colmap, n_perm + max(1, self.n_uncovered),
+            self.perm_handle = self.engine.csr_permute(src.handle, rowdof, colmap, n_perm + max(1, self.n_uncovered),
                                                        cuts=color_rowptr,
                                                        max_rows=256, row_pos=pos)
+            self._narrow()
             self.engine.bjac_set_colors_permuted(self.handle, self.perm_handle, ptr, color_rowptr, rowdof,
                                                  np.ascontiguousarray(ridx.T))
             return
         if hasattr(self.engine, "csr_select_rows"):
-            self.perm_handle = self.engine.csr_select_rows(mat.handle, rowdof, cuts=color_rowptr)
+            self.perm_handle = self.engine.csr_select_rows(src.handle, rowdof, cuts=color_rowptr)
         else:
-            perm = mat.to_scipy()[rowdof]
+            perm = src.to_scipy()[rowdof]
             perm.sort_indices()
             self.perm_handle = self.engine.csr_create(perm.shape[0], perm.shape[1], perm.indptr, perm.indices,
                                                       perm.data, cuts=color_rowptr)
+        self._narrow()
         self.engine.bjac_set_colors(self.handle, self.perm_handle, ptr, color_rowptr, rowdof,
                                     np.ascontiguousarray(ridx.T))
+
+    def _narrow(self):
+        """fp32 storage: the sweep matrix and, with a middle term, the residual copy (both the handle's own) store 4-byte
+        values; without a middle term nothing reads the copy after set-up, and it is released."""
+        if self.storage == "fp32":
+            narrow_in_place(self.perm_handle, self.engine)
+            if self.middle is None:
+                self.residual_mat = None
+            else:
+                narrow_in_place(self.residual_mat, self.engine)
+
+    def value_bytes(self):
+        """Bytes of the matrix values the operator streams: the sweep matrix, plus the residual matrix with a middle term."""
+        return (value_bytes(self.perm_handle, self.engine)
+                + (value_bytes(self.residual_mat) if self.middle is not None else 0))
 
     @staticmethod
     def _device_colors(mat, base, seed, method="luby"):
@@ -754,7 +852,7 @@ class BlockGaussSeidel(BaseMatrix):
         y[:] = 0.0                                                       # :377
         self.Smooth(y, x)                                                # :378
         res = x.CreateVector()
-        res.data = x - self.mat * y                                      # :379
+        res.data = x - self.residual_mat * y                             # :379 (fp32 storage: round32(mat))
         y.data += self.middle * res                                      # :380
         self.SmoothBack(y, x)                                            # :381
 
@@ -897,14 +995,20 @@ class Projector(BaseMatrix):
 _WARNED = {}
 
 
-def Preconditioner(form, kind, blocks=None, **_):
+def Preconditioner(form, kind, blocks=None, storage="fp64", **_):
     """``Preconditioner(blf, 'local')`` -> point Jacobi; ``'blockjacobi'`` -> additive block Jacobi
     over `blocks`; ``'h1amg'`` / ``'multigrid'`` -> the smoothed-aggregation V-cycle on the assembled
     matrix (`hipla.amg`).  ``'bddc'`` (stokes_hcurldiv.py:48, templates/...iterative.py:77,88,122,306)
     is NGSolve's domain-decomposition preconditioner built on its FE spaces; it has no algebraic
     counterpart here, and the same V-cycle is returned in its place -- a mesh-independent SPD
-    preconditioner for the same operator, with different iteration counts than the reference's."""
+    preconditioner for the same operator, with different iteration counts than the reference's.
+
+    `storage` ("fp64" | "fp32"): the value storage of the V-cycle's matrices (`SmoothedAggregationAMG`); the point and
+    block Jacobi preconditioners store no matrix of their own and take "fp64" only."""
+    check_storage(storage)
     mat = form.mat if hasattr(form, "mat") else form
+    if storage != "fp64" and kind not in ("h1amg", "multigrid", "bddc"):
+        raise ValueError("Preconditioner(..., %r): storage='fp32' exists for the AMG kinds only" % (kind,))
     if kind == "local":
         if blocks is not None:
             return BlockJacobi(mat, blocks)
@@ -921,5 +1025,5 @@ def Preconditioner(form, kind, blocks=None, **_):
             warnings.warn("Preconditioner(..., 'bddc'): NGSolve's BDDC needs its FE spaces; a smoothed-aggregation "
                           "V-cycle on the assembled matrix is used in its place (different iteration counts than "
                           "the reference's)", stacklevel=2)
-        return SmoothedAggregationAMG(mat)
+        return SmoothedAggregationAMG(mat, storage=storage)
     raise NotImplementedError("preconditioner %r is outside the hot-path scope (SURVEY.md section 8f)" % (kind,))

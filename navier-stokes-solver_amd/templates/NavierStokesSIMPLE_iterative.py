@@ -72,11 +72,12 @@ class ConvectionOperator(hipla.BaseMatrix):
         y.data = -self.div * flux
 
 
-def auxiliary_space_preconditioner(system, space=None):
+def auxiliary_space_preconditioner(system, space=None, storage="fp64"):
     """``transform`` and ``preAh1`` of the reference (:208-357) on the grid restatement of the auxiliary
     space: returns (transform, preAh1, aux) with ``preAh1 = sum_c emb_c @ Preconditioner(aH1_c, 'h1amg') @
     emb_c.T`` as the protocol composition the reference writes (:336-337,357) and ``aux`` = the same
-    operator ``transform @ preAh1 @ transform.T`` as one native handle (`hipla.AuxiliarySpaceAMG`)."""
+    operator ``transform @ preAh1 @ transform.T`` as one native handle (`hipla.AuxiliarySpaceAMG`).
+    `storage` ("fp64" | "fp32"): the value storage of the term's matrices (T, T^T, the V-cycles' operators)."""
     if space is None:                  # (`space`: an assembled `system.auxiliary_space()`, so that callers can time the
         space = system.auxiliary_space()   #  host assembly of the auxiliary operators apart from the preconditioner set-up)
     transform = hipla.SparseMatrix.from_scipy(space["transform"])
@@ -86,7 +87,7 @@ def auxiliary_space_preconditioner(system, space=None):
     for lap, rng in zip(space["laplacians"], space["ranges"]):
         if id(lap) not in built:       # components with the same boundary conditions share one matrix: one hierarchy
             aH1 = AssembledForm(hipla.SparseMatrix.from_scipy(lap))
-            built[id(lap)] = hipla.Preconditioner(aH1, "h1amg")          # :326-329,340-349
+            built[id(lap)] = hipla.Preconditioner(aH1, "h1amg", storage=storage)   # :326-329,340-349
         pre_c = built[id(lap)]
         emb = hipla.Embedding(ndof, rng)                                 # :334-335,353-355
         term = emb @ pre_c @ emb.T
@@ -97,12 +98,14 @@ def auxiliary_space_preconditioner(system, space=None):
         # measurement variant: ONE V-cycle on the slab-major stacked block-diagonal Laplacian (what the row-partitioned
         # form applies): a third of the launches on the launch-bound coarse levels, no shared hierarchy
         st = system.auxiliary_space_stacked()
-        stacked = hipla.Preconditioner(AssembledForm(hipla.SparseMatrix.from_scipy(st["laplacian"])), "h1amg")
-        return transform, preAh1, hipla.AuxiliarySpaceAMG(hipla.SparseMatrix.from_scipy(st["transform"]), [stacked])
-    return transform, preAh1, hipla.AuxiliarySpaceAMG(transform, comps)
+        stacked = hipla.Preconditioner(AssembledForm(hipla.SparseMatrix.from_scipy(st["laplacian"])), "h1amg",
+                                       storage=storage)
+        return transform, preAh1, hipla.AuxiliarySpaceAMG(hipla.SparseMatrix.from_scipy(st["transform"]), [stacked],
+                                                          storage=storage)
+    return transform, preAh1, hipla.AuxiliarySpaceAMG(transform, comps, storage=storage)
 
 
-def MypreA(space, a, jacblocks, GS, aux=None):
+def MypreA(space, a, jacblocks, GS, aux=None, storage="fp64"):
     """``MypreA(space, a, jacblocks, GS)`` of the reference
     (templates/NavierStokesSIMPLE_iterative.py:364-391); `aux` is the auxiliary-space term
     ``transform @ preAh1 @ transform.T`` (an `hipla.AuxiliarySpaceAMG`, or any operator), ``None`` = block
@@ -112,9 +115,13 @@ def MypreA(space, a, jacblocks, GS, aux=None):
     * ``GS=True``  -> ``y = 0; J.Smooth(y, x); r = x - A y; y += aux r; J.SmoothBack(y, x)`` (:376-381)
       over a multicolour block ordering (scope row N1).
     Both are native operands of the fused BPCG loop when `aux` is an `AuxiliarySpaceAMG` (or a
-    `SmoothedAggregationAMG`); other operators run through the protocol."""
+    `SmoothedAggregationAMG`); other operators run through the protocol.
+
+    `storage` ("fp64" | "fp32"): the value storage of the Gauss-Seidel handle's matrices (`hipla.BlockGaussSeidel`);
+    the additive block Jacobi stores no matrix and `aux` keeps the storage it was built with."""
+    hipla.matrix.check_storage(storage)
     if GS:
-        op = hipla.BlockGaussSeidel(a.mat, jacblocks, middle=aux)
+        op = hipla.BlockGaussSeidel(a.mat, jacblocks, middle=aux, storage=storage)
         op.space, op.GS = space, True
         return op
     op = hipla.BlockJacobi(a.mat, jacblocks)
@@ -184,13 +191,15 @@ class NavierStokes:
         return out
 
     def SolveInitial(self, timesteps=None, iterative=True, GS=True, tol=1e-10, maxsteps=100000, printrates=False,
-                     aux=True, amg=False, condense=False):
+                     aux=True, amg=False, condense=False, pre_storage="fp64"):
         """`aux`: build the auxiliary-space term of MypreA (:208-357) -- the reference always does; False
         keeps the block smoother alone.  `amg=True` (kept from round 1) puts a smoothed-aggregation
         V-cycle on a.mat itself in the place of the auxiliary term.  `condense=True` solves as the reference's
         default does (:188, ``condense=True, store_inner=True``): blfA is the statically condensed form, MypreA
         sweeps over its Schur complement with blocks of coupling dofs only (:360-362), and BramblePasciakCG runs
-        the condensed branch of harmonic_extension."""
+        the condensed branch of harmonic_extension.  `pre_storage="fp32"` stores the matrices of MypreA (the
+        Gauss-Seidel sweep, the auxiliary-space term or the V-cycle) with fp32 values; vectors, arithmetic and the
+        Krylov operator stay fp64."""
         if timesteps:                                     # pseudo time stepping to the Stokes state (:406-417)
             ops = self._time_stepping_operators()
             self.Project(self.gfu)
@@ -218,10 +227,10 @@ class NavierStokes:
         preM = hipla.Preconditioner(self.mp, "local")
         middle = None
         if amg:
-            middle = hipla.SmoothedAggregationAMG(blfA.mat)
+            middle = hipla.SmoothedAggregationAMG(blfA.mat, storage=pre_storage)
         elif aux:
-            self.transform, self.preAh1, middle = auxiliary_space_preconditioner(self.system)
-        preA = self.preA = MypreA(self.V, blfA, blocks, GS=GS, aux=middle)
+            self.transform, self.preAh1, middle = auxiliary_space_preconditioner(self.system, storage=pre_storage)
+        preA = self.preA = MypreA(self.V, blfA, blocks, GS=GS, aux=middle, storage=pre_storage)
         sol = BlockVector([self.gfu, self.gfup])       # aliases the grid-function storage (:206)
         out = BramblePasciakCG(blfA, blfB, None, self.f.vec, self.g.vec, preA, preM, sol, initialize=False,
                                tol=tol, maxsteps=maxsteps, rel_err=True, printrates=printrates)
