@@ -560,6 +560,9 @@ NSS_API int nss_dist_amg_create(nss_dist_t d, nss_csr_t a_loc, const nss_halo_t*
                                 nss_csr_t p_loc, const double* wdinv, nss_amg_t coarse, nss_dist_amg_t* out);
 NSS_API int nss_dist_amg_destroy(nss_dist_amg_t h);
 NSS_API int nss_dist_amg_apply_f64(nss_dist_amg_t h, double scale, const double* b, double* y, nss_stream_t stream);
+/* Over the mailbox transport (nss_dist_attach_p2p on the cycle's dist handle): the transport channel of halo_x's layout
+ * (default 0); the coarse all-reduce then needs the transport's vector zone of nc doubles (nss_p2p_create_vec). */
+NSS_API int nss_dist_amg_set_channel(nss_dist_amg_t h, int32_t channel);
 
 /* The auxiliary-space term `transform @ preAh1 @ transform.T` of MypreA (templates/NavierStokesSIMPLE_iterative.py:336-337,
  * 357,380,383) on slabs, applied natively inside the partitioned loops (the reference is single-process): tt_loc = the
@@ -572,6 +575,8 @@ NSS_API int nss_dist_aux_create(nss_dist_t d, nss_csr_t tt_loc, const nss_halo_t
                                 const nss_halo_t* halo_e, nss_dist_amg_t amg, const nss_halo_t* halo_y, nss_dist_aux_t* out);
 NSS_API int nss_dist_aux_destroy(nss_dist_aux_t h);
 NSS_API int nss_dist_aux_apply_f64(nss_dist_aux_t h, double scale, const double* b, double* y, nss_stream_t stream);
+/* Over the mailbox transport: the channels of the layouts of halo_x, halo_e and halo_y (default 0 each). */
+NSS_API int nss_dist_aux_set_channels(nss_dist_aux_t h, int32_t ch_x, int32_t ch_e, int32_t ch_y);
 
 /* ---- mailbox transport over xGMI (peer-mapped memory, no collective library) -----------------------------------
  * Every rank owns a small fine-grained region -- a mailbox of 2 x nranks word pairs, one arrival flag per source rank
@@ -590,9 +595,19 @@ NSS_API int nss_p2p_blob_bytes(int32_t nranks, int32_t nhalo, int64_t* bytes);
  * `ext` changed. */
 NSS_API int nss_p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t* const* halos,
                            const int32_t* n_owned, nss_p2p_t* out, void* h_blob);
+/* The same with a VECTOR ZONE for nss_p2p_allreduce_vec_f64 (and the n-double all-reduces of the native V-cycle):
+ * vec_n entries, rank q contributing only inside [vec_lo[q], vec_hi[q]) (HOST arrays of nranks; an empty range is
+ * allowed).  Every rank must pass the same vec_n, vec_lo and vec_hi: the zone has the same layout in every region and
+ * the blob is the one of nss_p2p_create. */
+NSS_API int nss_p2p_create_vec(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t* const* halos,
+                               const int32_t* n_owned, int64_t vec_n, const int64_t* vec_lo, const int64_t* vec_hi,
+                               nss_p2p_t* out, void* h_blob);
 NSS_API int nss_p2p_connect(nss_p2p_t p, const void* h_blobs);
 NSS_API int nss_p2p_destroy(nss_p2p_t p);
 NSS_API int nss_p2p_allreduce_f64(nss_p2p_t p, const double* src, double* dst, nss_stream_t stream);
+/* dst[0 .. vec_n) = sum over the ranks of src[0 .. vec_n), added in rank order (the same bits on every rank); rank q's
+ * src is read inside its contribution range only.  Device buffers; in place allowed. */
+NSS_API int nss_p2p_allreduce_vec_f64(nss_p2p_t p, const double* src, double* dst, nss_stream_t stream);
 /* `channel`: the index of the halo's layout in nss_p2p_create's list.  The sequence number and the channel's exchange
  * count advance on every call -- also where this rank's halo on the channel is empty -- so that every rank numbers its
  * collectives alike; nss_p2p_counters reads them (seq, and the count of the first max_channels channels). */
@@ -600,7 +615,8 @@ NSS_API int nss_p2p_exchange(nss_p2p_t p, int32_t channel, const nss_halo_t* hal
 NSS_API int nss_p2p_counters(nss_p2p_t p, int64_t* seq, int32_t max_channels, int64_t* counts, int32_t* n_channels);
 NSS_API int nss_p2p_error(nss_p2p_t p, int32_t* timed_out, nss_stream_t stream);
 /* every exchange and every one-double all-reduce of the native loops that take this dist handle (MINRES, BPCG v1, the
- * eight-phase BPCG v2 plan) goes through the mailbox transport instead of RCCL (NULL detaches); BPCG v2 on the compact
+ * eight-phase BPCG v2 plan, the partitioned V-cycle and auxiliary-space term -- whose coarse all-reduce needs the vector
+ * zone of nss_p2p_create_vec) goes through the mailbox transport instead of RCCL (NULL detaches); BPCG v2 on the compact
  * plan fuses its all-reduces into the sum kernels through nss_bpcg2_t.p2p instead */
 NSS_API int nss_dist_attach_p2p(nss_dist_t d, nss_p2p_t p);
 

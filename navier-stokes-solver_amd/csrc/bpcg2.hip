@@ -1007,7 +1007,7 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st, const nss_dist_s* d) 
     //   symmetric; it reads owned entries only, so the iterate is not exchanged)
     const nss_dist_aux_s& aux = *s.pre_dist_aux;
     gs_forward_from_zero(s, src, st);
-    if (!(s.cond_HT && s.sweep_A)) exchange(*aux.d, aux.halo_y, st);
+    if (!(s.cond_HT && s.sweep_A)) exchange_on(*aux.d, aux.ch_y, aux.halo_y, s.ctrl, st);
     launch_csr_stream(s.sweep_A ? *s.sweep_A : *s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
     dist_aux_apply(aux, 1.0, s.t2, s.t1, true, st, s.ctrl);
     bjac_smooth(*s.pre_bjac, s.k, src, s.t1, true, s.ctrl, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);   // (src again)

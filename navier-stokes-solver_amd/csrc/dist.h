@@ -46,6 +46,7 @@ struct nss_dist_amg_s {
   const double* wdinv = nullptr;       // omega / diag(A) on the slab
   const nss_amg_s* coarse = nullptr;   // levels 1.. (replicated)
   nss_halo_t halo{};                   // of the iterate x (ext = x's halo-extended buffer)
+  int32_t channel = 0;                 // mailbox transport: the channel of halo's layout (nss_dist_amg_set_channel)
   int32_t n = 0, nc = 0;
   double *res = nullptr, *rc = nullptr, *rc_local = nullptr, *ec = nullptr;   // work vectors (owned by the handle)
 };
@@ -64,6 +65,7 @@ struct nss_dist_aux_s {
   nss_halo_t halo_e{};                 // of the nodal correction
   nss_halo_t halo_y{};                 // of the loop's iterate t1 as A's operand (multiplicative form: residual x - A y)
   bool has_halo_y = false;
+  int32_t ch_x = 0, ch_e = 0, ch_y = 0;   // mailbox transport: the channels of the three halos (nss_dist_aux_set_channels)
   int32_t n_u = 0, n_nodes = 0;
   double* r_aux = nullptr;             // nodal work vector (owned by the handle)
 };
@@ -87,7 +89,13 @@ void check_halo(const nss_halo_t* h, const nss_csr_s& mat, const char* name);
 // halo exchange of one or two SpMV operands (one grouped send/recv phase) on stream `st`; over the mailbox transport
 // (nss_dist_attach_p2p) the first goes through channel 0, the second through channel 1
 void exchange(const nss_dist_s& d, const nss_halo_t& h, hipStream_t st, const nss_halo_t* second = nullptr);
-// dst = sum over the ranks of src (n doubles, device); without a communicator (one rank) a copy
-void allreduce_sum(const nss_dist_s& d, const double* src, double* dst, size_t n, hipStream_t st);
+// halo exchange of one operand over the channel the caller names: over the mailbox transport p2p_exchange on `channel`
+// (skipped on every rank once *done != 0), else exchange(d, h, st)
+void exchange_on(const nss_dist_s& d, int channel, const nss_halo_t& h, const int32_t* done, hipStream_t st);
+// dst = sum over the ranks of src (n doubles, device); without a communicator (one rank) a copy.  Over the mailbox
+// transport n == 1 is the one-double all-reduce and n > 1 needs the transport's vector zone (p2p_allreduce_vec, which
+// skips once *done != 0)
+void allreduce_sum(const nss_dist_s& d, const double* src, double* dst, size_t n, hipStream_t st,
+                   const int32_t* done = nullptr);
 
 }  // namespace nss

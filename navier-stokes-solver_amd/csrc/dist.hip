@@ -99,11 +99,25 @@ void exchange(const nss_dist_s& d, const nss_halo_t& h, hipStream_t st, const ns
   nccl_check(d, d.GroupEnd(), "ncclGroupEnd");
 }
 
-// dst[0 .. n) = sum over the ranks of src[0 .. n) (device pointers; out of place or in place)
-void allreduce_sum(const nss_dist_s& d, const double* src, double* dst, size_t n, hipStream_t st) {
+void exchange_on(const nss_dist_s& d, int channel, const nss_halo_t& h, const int32_t* done, hipStream_t st) {
   if (d.p2p && d.nranks > 1) {
-    if (n != 1) throw Error("dist: the mailbox transport all-reduces single doubles (vectors need the RCCL communicator)");
-    p2p_allreduce(*d.p2p, src, dst, st);
+    p2p_exchange(*d.p2p, channel, h, done, st);
+    return;
+  }
+  exchange(d, h, st);
+}
+
+// dst[0 .. n) = sum over the ranks of src[0 .. n) (device pointers; out of place or in place)
+void allreduce_sum(const nss_dist_s& d, const double* src, double* dst, size_t n, hipStream_t st, const int32_t* done) {
+  if (d.p2p && d.nranks > 1) {
+    if (n == 1) {
+      p2p_allreduce(*d.p2p, src, dst, st);
+      return;
+    }
+    if (d.p2p->vec_n == 0)
+      throw Error("dist: the mailbox transport all-reduces single doubles (vectors need the RCCL communicator)");
+    if (int64_t(n) != d.p2p->vec_n) throw Error("dist: the vector all-reduce is not of the size of the transport's vector zone");
+    p2p_allreduce_vec(*d.p2p, src, dst, done, st);
     return;
   }
   if (d.comm == nullptr) {
@@ -181,25 +195,26 @@ void dist_amg_apply(const nss_dist_amg_s& a, double scale, const double* b, doub
                     const int32_t* done) {
   double* x = a.halo.ext;                                                    // owned entries first
   diag_apply(a.n, a.wdinv, 1.0, b, 0.0, x, done, st);                        // pre-smoothing from zero
-  exchange(*a.d, a.halo, st);
+  exchange_on(*a.d, a.channel, a.halo, done, st);
   launch_csr_stream(*a.A, x, EpiResidual{b, a.res, done}, st);               // res = b - A x
   launch_csr_stream(*a.R, a.res, EpiAxpby{1.0, 0.0, a.rc_local, done}, st);  // this slab's share of R res
-  // out of place: once *done is set the kernels return at once but the collectives still run -- an in-place
-  // all-reduce would multiply the frozen rc by the number of ranks on every further iteration
-  allreduce_sum(*a.d, a.rc_local, a.rc, size_t(a.nc), st);
+  // out of place: once *done is set the kernels return at once but the RCCL collectives still run -- an in-place
+  // all-reduce would multiply the frozen rc by the number of ranks on every further iteration (the mailbox transport's
+  // vector all-reduce skips, as its exchanges do)
+  allreduce_sum(*a.d, a.rc_local, a.rc, size_t(a.nc), st, done);
   amg_apply(*a.coarse, 1.0, a.rc, a.ec, st, done);                           // levels 1.. on every rank
   launch_csr_stream(*a.P, a.ec, EpiAxpby{1.0, 1.0, x, done}, st);            // x += P e
-  exchange(*a.d, a.halo, st);
+  exchange_on(*a.d, a.channel, a.halo, done, st);
   launch_csr_stream(*a.A, x, EpiJacobi{b, x, a.wdinv, y, 1.0, scale, done}, st);   // y = scale (x + w D^-1 (b - A x))
 }
 
 void dist_aux_apply(const nss_dist_aux_s& a, double scale, const double* b, double* y, bool accumulate, hipStream_t st,
                     const int32_t* done) {
   NSS_HIP(hipMemcpyAsync(a.halo_x.ext, b, sizeof(double) * size_t(a.n_u), hipMemcpyDeviceToDevice, st));   // (scratch: unguarded)
-  exchange(*a.d, a.halo_x, st);
+  exchange_on(*a.d, a.ch_x, a.halo_x, done, st);
   launch_csr_stream(*a.TT, a.halo_x.ext, EpiAxpby{1.0, 0.0, a.r_aux, done}, st);                // transform.T
   dist_amg_apply(*a.amg, 1.0, a.r_aux, a.halo_e.ext, st, done);                                 // V-cycle on the stacked Laplacian
-  exchange(*a.d, a.halo_e, st);
+  exchange_on(*a.d, a.ch_e, a.halo_e, done, st);
   launch_csr_stream(*a.T, a.halo_e.ext, EpiAxpby{scale, accumulate ? 1.0 : 0.0, y, done}, st);  // transform
 }
 
@@ -238,6 +253,17 @@ int nss_dist_aux_create(nss_dist_t d, nss_csr_t tt_loc, const nss_halo_t* halo_x
       throw;
     }
     *out = h;
+  });
+}
+
+int nss_dist_aux_set_channels(nss_dist_aux_t h, int32_t ch_x, int32_t ch_e, int32_t ch_y) {
+  return guarded([&] {
+    NSS_REQUIRE(h != nullptr, "dist_aux_set_channels: NULL handle");
+    for (int32_t c : {ch_x, ch_e, ch_y})
+      NSS_REQUIRE(c >= 0 && c < kP2pMaxChannels, "dist_aux_set_channels: channel out of range");
+    h->ch_x = ch_x;
+    h->ch_e = ch_e;
+    h->ch_y = ch_y;
   });
 }
 
@@ -285,6 +311,14 @@ int nss_dist_amg_create(nss_dist_t d, nss_csr_t a_loc, const nss_halo_t* halo_x,
       throw;
     }
     *out = h;
+  });
+}
+
+int nss_dist_amg_set_channel(nss_dist_amg_t h, int32_t channel) {
+  return guarded([&] {
+    NSS_REQUIRE(h != nullptr, "dist_amg_set_channel: NULL handle");
+    NSS_REQUIRE(channel >= 0 && channel < kP2pMaxChannels, "dist_amg_set_channel: channel out of range");
+    h->channel = channel;
   });
 }
 

@@ -20,6 +20,21 @@
 // exchange e + 1 can arrive before this rank has copied exchange e out -- found by running the native BPCG v1 loop with
 // two ranks), never two: its put of exchange e + 2 follows its wait for e + 1, i.e. this rank's put of e + 1, which this
 // rank's stream orders behind its copy of e.
+//   vector all-reduce          (optional "vector zone", nss_p2p_create_vec): dst[0 .. n) = sum over the ranks of src, added
+//                              in rank order.  Every rank q contributes only inside one contiguous range [lo_q, hi_q)
+//                              registered at set-up (zero elsewhere; the ranges are the same on every rank); "put" copies
+//                              src[lo_q, hi_q) into segment q of every peer's vector zone and raises the peer's vector flag
+//                              of q, "wait + add" spins on the flags of all peers, then adds, per entry and in rank order,
+//                              the contributions of the ranks whose range covers it (skipping a rank = adding +0.0: no
+//                              partial sum is -0.0, so the bits are those of the plain rank-ordered sum).  Per rank this
+//                              moves (nranks - 1) (hi_q - lo_q) doubles -- about an all-gather -- instead of
+//                              (nranks - 1) n.  The zone exists twice, used alternately: a peer can be at most one vector
+//                              all-reduce ahead -- its put of v + 2 follows its wait for v + 1, which needs this rank's
+//                              put of v + 1, which this rank's stream orders behind its add of v (the last read of the
+//                              zone copy v and v + 2 share).  Once *done is set (the loop's stop flag, flipped by the
+//                              same iteration on every rank from all-reduced scalars) both kernels return at once, as the
+//                              exchanges of the compact loop do: every rank skips the same calls, nobody waits for a put
+//                              that is not coming, and the sequence numbers still advance on the host.
 #pragma once
 
 #include "nss_common.h"
@@ -113,6 +128,12 @@ struct nss_p2p_s {
     std::vector<int64_t> peer_land_off;      // per destination rank: BYTE offset inside ITS region where our segment goes
   };
   std::vector<Channel> channels;
+  // the vector zone (nss_p2p_create_vec; vec_n == 0: none): its layout depends only on (n, every rank's range), the
+  // same on every rank, so its flags and segments sit at the same byte offsets in every region (nothing in the blob)
+  int64_t vec_n = 0;
+  std::vector<int64_t> vec_lo, vec_hi, vec_off;   // per rank: contribution range, offset of its segment in the zone
+  size_t vec_flags_off = 0, vec_zone_off = 0, vec_zone_bytes = 0;
+  uint32_t vec_count = 0;                          // vector all-reduces issued so far (picks the zone copy)
   bool connected = false;
   nss::P2pView view(uint32_t s) const { return nss::P2pView{mail, d_peer_mail, nranks, rank, s, d_error}; }
 };
@@ -125,4 +146,7 @@ namespace nss {
 void p2p_exchange(nss_p2p_s& p, int channel, const nss_halo_t& h, const int32_t* done, hipStream_t st);
 // dst[0] = sum over the ranks of src[0], the ranks' values added in rank order (one small launch)
 void p2p_allreduce(nss_p2p_s& p, const double* src, double* dst, hipStream_t st);
+// dst[0 .. n) = sum over the ranks of src[0 .. n) through the vector zone (n = the zone's size; put + wait/add on `st`).
+// The sequence number advances on every call; with *done != 0 both kernels return at once (see the header comment).
+void p2p_allreduce_vec(nss_p2p_s& p, const double* src, double* dst, const int32_t* done, hipStream_t st);
 }  // namespace nss

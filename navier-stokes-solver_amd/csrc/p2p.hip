@@ -148,6 +148,95 @@ void p2p_allreduce(nss_p2p_s& p, const double* src, double* dst, hipStream_t st)
   NSS_CHECK_LAUNCH();
 }
 
+struct VecAddArgs {
+  const unsigned long long* flags;   // own vector flags, one per source rank
+  int64_t lo[kP2pMaxRanks], hi[kP2pMaxRanks], off[kP2pMaxRanks];
+  int32_t nranks, rank;
+  uint32_t seq;
+  const double* zone;                // the zone copy of this call
+  const double* src;                 // own contribution (read inside [lo[rank], hi[rank]) only)
+  double* dst;
+  int64_t n;
+  int32_t* error;
+  const int32_t* done;
+};
+
+__global__ __launch_bounds__(kBlock) void p2p_vec_wait_add_kernel(VecAddArgs a) {
+  if (a.done && a.done[0] != 0) return;
+  const int t = int(threadIdx.x);
+  if (t < a.nranks && t != a.rank) {
+    const unsigned long long* f = a.flags + t;
+    const unsigned long long t0 = wall_clock64();
+    while (p2p_load(f) < (unsigned long long)a.seq) {
+      if (wall_clock64() - t0 > kP2pTimeoutTicks) {
+        atomicExch(a.error, 1);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+  }
+  __threadfence_system();                                         // the flags before the data they announce
+  __syncthreads();
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += stride) {
+    double s = 0.0;
+    for (int q = 0; q < a.nranks; ++q) {                           // rank order: identical bits on every rank
+      if (i < a.lo[q] || i >= a.hi[q]) continue;                   // outside q's range its contribution is zero
+      s += q == a.rank ? a.src[i] : __builtin_nontemporal_load(a.zone + a.off[q] + (i - a.lo[q]));
+    }
+    a.dst[i] = s;
+  }
+}
+
+void p2p_allreduce_vec(nss_p2p_s& p, const double* src, double* dst, const int32_t* done, hipStream_t st) {
+  if (!p.connected) throw Error("p2p: not connected");
+  if (p.vec_n <= 0) throw Error("p2p: no vector zone (nss_p2p_create_vec)");
+  const uint32_t seq = ++p.seq;                                    // advanced on every rank, in the same order
+  const size_t par = size_t(p.vec_count++ & 1u);
+  const int me = p.rank;
+  const int64_t lo = p.vec_lo[size_t(me)], cnt = p.vec_hi[size_t(me)] - lo;
+  // put: segment `me` of every peer's zone copy `par`, then the peer's vector flag of `me` -- also for an empty range
+  // (one workgroup that only raises the flag); at most kP2pMaxSegments peers per launch
+  std::vector<int> peers;
+  for (int q = 0; q < p.nranks; ++q)
+    if (q != me) peers.push_back(q);
+  const int nwg = int(std::max<int64_t>(1, (cnt + kPutPerWg - 1) / kPutPerWg));
+  for (size_t first = 0; first < peers.size(); first += kP2pMaxSegments) {
+    PutArgs a{};
+    int wg = 0;
+    for (size_t i = first; i < peers.size() && i < first + kP2pMaxSegments; ++i) {
+      char* pr = p.peer_region[size_t(peers[i])];
+      double* pdst = reinterpret_cast<double*>(pr + p.vec_zone_off + par * p.vec_zone_bytes) + p.vec_off[size_t(me)];
+      unsigned long long* pflag = reinterpret_cast<unsigned long long*>(pr + p.vec_flags_off) + me;
+      a.seg[a.nseg++] = PutSeg{src + lo, pdst, pflag, int32_t(cnt), wg, nwg};
+      wg += nwg;
+    }
+    a.seq = seq;
+    a.ticket = p.d_ticket;
+    a.done = done;
+    hipLaunchKernelGGL(p2p_put_kernel, dim3(wg), dim3(kBlock), 0, st, a);
+    NSS_CHECK_LAUNCH();
+  }
+  VecAddArgs w{};
+  w.flags = reinterpret_cast<const unsigned long long*>(p.region + p.vec_flags_off);
+  for (int q = 0; q < p.nranks; ++q) {
+    w.lo[q] = p.vec_lo[size_t(q)];
+    w.hi[q] = p.vec_hi[size_t(q)];
+    w.off[q] = p.vec_off[size_t(q)];
+  }
+  w.nranks = p.nranks;
+  w.rank = me;
+  w.seq = seq;
+  w.zone = reinterpret_cast<const double*>(p.region + p.vec_zone_off + par * p.vec_zone_bytes);
+  w.src = src;
+  w.dst = dst;
+  w.n = p.vec_n;
+  w.error = p.d_error;
+  w.done = done;
+  hipLaunchKernelGGL(p2p_vec_wait_add_kernel, dim3(stream_grid(p.vec_n, kBlock * 4)), dim3(kBlock), 0, st, w);
+  NSS_CHECK_LAUNCH();
+}
+
 }  // namespace nss
 
 using namespace nss;
@@ -170,8 +259,12 @@ int nss_p2p_blob_bytes(int32_t nranks, int32_t nhalo, int64_t* bytes) {
   });
 }
 
-int nss_p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t* const* halos, const int32_t* n_owned,
-                   nss_p2p_t* out, void* h_blob) {
+}  // extern "C"
+
+namespace {
+// nss_p2p_create (vec_n == 0: the layout and blob of a transport without vector zone) and nss_p2p_create_vec
+int p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t* const* halos, const int32_t* n_owned,
+               int64_t vec_n, const int64_t* vec_lo, const int64_t* vec_hi, nss_p2p_t* out, void* h_blob) {
   return guarded([&] {
     NSS_REQUIRE(out && h_blob && halos && n_owned, "p2p_create: NULL argument");
     NSS_REQUIRE(nranks >= 1 && nranks <= kP2pMaxRanks && rank >= 0 && rank < nranks, "p2p_create: bad rank / size (at most 16 ranks)");
@@ -201,6 +294,25 @@ int nss_p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t
         ch.flags_off = off;
         off += flags_bytes();
         p->channels.push_back(ch);
+      }
+      if (vec_n > 0) {   // vector zone: flags, then two copies of the segments of all ranks (the same in every region)
+        NSS_REQUIRE(vec_lo && vec_hi, "p2p_create: NULL contribution range");
+        int64_t total = 0;
+        for (int q = 0; q < nranks; ++q) {
+          NSS_REQUIRE(0 <= vec_lo[q] && vec_lo[q] <= vec_hi[q] && vec_hi[q] <= vec_n,
+                      "p2p_create: contribution range outside [0, n)");
+          p->vec_lo.push_back(vec_lo[q]);
+          p->vec_hi.push_back(vec_hi[q]);
+          p->vec_off.push_back(total);
+          total += vec_hi[q] - vec_lo[q];
+        }
+        p->vec_n = vec_n;
+        p->vec_flags_off = off;
+        off += flags_bytes();
+        off = (off + 255) & ~size_t(255);
+        p->vec_zone_off = off;
+        p->vec_zone_bytes = (sizeof(double) * size_t(std::max<int64_t>(total, 1)) + 255) & ~size_t(255);
+        off += 2 * p->vec_zone_bytes;
       }
       // landing zones behind all flag rows; their sizes differ from rank to rank, so every rank publishes ITS offsets
       // relative to a layout that only depends on (nranks, nhalo): zone c starts at a 256-byte aligned offset that the
@@ -246,6 +358,20 @@ int nss_p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t
     }
     *out = p;
   });
+}
+}  // namespace
+
+extern "C" {
+
+int nss_p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t* const* halos, const int32_t* n_owned,
+                   nss_p2p_t* out, void* h_blob) {
+  return p2p_create(nranks, rank, nhalo, halos, n_owned, 0, nullptr, nullptr, out, h_blob);
+}
+
+int nss_p2p_create_vec(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t* const* halos, const int32_t* n_owned,
+                       int64_t vec_n, const int64_t* vec_lo, const int64_t* vec_hi, nss_p2p_t* out, void* h_blob) {
+  if (vec_n < 1) return guarded([] { throw Error("p2p_create_vec: the vector zone needs n >= 1"); });
+  return p2p_create(nranks, rank, nhalo, halos, n_owned, vec_n, vec_lo, vec_hi, out, h_blob);
 }
 
 int nss_p2p_connect(nss_p2p_t p, const void* h_blobs) {
@@ -306,6 +432,13 @@ int nss_p2p_allreduce_f64(nss_p2p_t p, const double* src, double* dst, nss_strea
   return guarded([&] {
     NSS_REQUIRE(p && src && dst, "p2p_allreduce: bad argument");
     p2p_allreduce(*p, src, dst, as_stream(stream));
+  });
+}
+
+int nss_p2p_allreduce_vec_f64(nss_p2p_t p, const double* src, double* dst, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(p && src && dst, "p2p_allreduce_vec: bad argument");
+    p2p_allreduce_vec(*p, src, dst, nullptr, as_stream(stream));
   });
 }
 

@@ -184,6 +184,62 @@ class TorchComm:
             self.dist.all_to_all_single(tail, send, output_split_sizes=outs, input_split_sizes=ins)
 
 
+P2P_MAX_CHANNELS = 4          # kP2pMaxChannels (csrc/p2p.h): operand layouts one transport serves
+
+
+def coarse_contribution_ranges(R, row_offsets):
+    """Per rank q of the row partition `row_offsets`: [lo_q, hi_q) = the first to one past the last non-empty row of
+    its share R[:, row_offsets[q]:row_offsets[q + 1]] of the restriction -- outside it the rank's share of the
+    restricted residual is zero (the contribution range of the mailbox transport's vector all-reduce).  (0, 0) for a
+    share without entries.  Every rank holds the global R (the hierarchy is replicated), so every rank computes every
+    rank's range without communication."""
+    R = sp.csc_matrix(R)
+    offs = np.asarray(row_offsets, dtype=np.int64)
+    lo, hi = np.zeros(offs.size - 1, dtype=np.int64), np.zeros(offs.size - 1, dtype=np.int64)
+    for q in range(offs.size - 1):
+        rows = R.indices[R.indptr[offs[q]]:R.indptr[offs[q + 1]]]
+        if rows.size:
+            lo[q], hi[q] = int(rows.min()), int(rows.max()) + 1
+    return lo, hi
+
+
+def mailbox_channels(halos):
+    """Channels of a `MailboxTransport` for `halos`, a list of (key, `nss_halo_t`, owned entries): one channel per
+    distinct key, numbered in order of first appearance.  The key is the halo plan of the operand layout (halos of one
+    `DistSparseMatrix` plan share a channel; a unique object gives a channel of its own): a ROLE, the same on every
+    rank, so every rank numbers its channels alike -- comparing the local receive tables would not (a rank without
+    ghosts has the same empty table on every layout).  Returns (channels [(halo, owned)], channel of each entry)."""
+    keys, chans, index = [], [], []
+    for key, h, n in halos:
+        for c, k in enumerate(keys):
+            if k is key:
+                index.append(c)
+                break
+        else:
+            keys.append(key)
+            chans.append((h, n))
+            index.append(len(keys) - 1)
+    if len(chans) > P2P_MAX_CHANNELS:
+        raise ValueError("the mailbox transport serves at most %d operand layouts, not %d" % (P2P_MAX_CHANNELS, len(chans)))
+    return chans, index
+
+
+def mailbox_layouts(ops, halo_t1, condensed=(), aux=None, aux_halos=None, V=None, v_halo=None):
+    """The (key, `nss_halo_t`, owned entries) list of a BPCG v2 run over the mailbox transport, for `mailbox_channels`:
+    t1 (A's operand: channel 0), a condensed form's lift and extension (channels of their own), then the
+    auxiliary-space term's halos `aux_halos` = (x: transform.T's operand, e: transform's operand, y: t1 as A's operand
+    or None) and the V-cycle's halo `v_halo` (the operand of `V.A`)."""
+    out = [(ops.A.plan, halo_t1, ops.n_u)] + [(object(), h, ops.n_u) for h in condensed]
+    if aux is not None:
+        hx, he, hy = aux_halos
+        out += [(aux.transform_t.plan, hx, aux.transform_t.plan.n_owned), (aux.transform.plan, he, aux.transform.plan.n_owned)]
+        if hy is not None:
+            out.append((ops.A.plan, hy, ops.n_u))
+    if V is not None:
+        out.append((V.A.plan, v_halo, V.A.plan.n_owned))
+    return out
+
+
 class MailboxTransport:
     """The mailbox transport of the native partitioned loops (csrc/p2p.h, `nss_p2p_*`): every rank owns a small
     fine-grained region -- all-reduce mailbox, and per operand LAYOUT the loop exchanges its arrival flags and a landing
@@ -191,9 +247,10 @@ class MailboxTransport:
     `halos`: list of (`nss_halo_t`, owned entries), one per layout (BPCG v2: t1; MINRES / BPCG v1: A's operand and B^T's
     operand); the loops may pass copies of these descriptors with only `ext` changed.  Set-up: create the region,
     gather everybody's blob (IPC handle + where each peer's segments are wanted) over the set-up communicator, map the
-    peers.  At most 16 ranks."""
+    peers.  At most 16 ranks.  `vector` = (n, lo, hi): a vector zone for `allreduce_vec` (and the coarse all-reduce of
+    the native V-cycle), rank q contributing inside [lo[q], hi[q]) only -- the same lists on every rank (checked)."""
 
-    def __init__(self, comm, engine, halos):
+    def __init__(self, comm, engine, halos, vector=None):
         import ctypes as C
         self.engine, self.comm = engine, comm
         self._halos = [h for h, _ in halos]
@@ -204,7 +261,20 @@ class MailboxTransport:
         self.handle = C.c_void_p()
         ptrs = (C.c_void_p * nh)(*[C.addressof(h) for h in self._halos])
         owned = (C.c_int32 * nh)(*[int(n) for _, n in halos])
-        engine._check(engine.lib.nss_p2p_create(comm.size, comm.rank, nh, ptrs, owned, C.byref(self.handle), blob))
+        self.vector_size = 0
+        if vector is None:
+            engine._check(engine.lib.nss_p2p_create(comm.size, comm.rank, nh, ptrs, owned, C.byref(self.handle), blob))
+        else:
+            n, lo, hi = int(vector[0]), [int(v) for v in vector[1]], [int(v) for v in vector[2]]
+            if len(lo) != comm.size or len(hi) != comm.size:
+                raise ValueError("MailboxTransport: one contribution range per rank")
+            mine = (n, tuple(lo), tuple(hi))       # every peer writes into our zone by ITS copy of this layout
+            if comm.size > 1 and any(o != mine for o in comm.gather_objects(mine)):
+                raise ValueError("MailboxTransport: the ranks disagree on the vector zone (size or contribution ranges)")
+            engine._check(engine.lib.nss_p2p_create_vec(comm.size, comm.rank, nh, ptrs, owned, n,
+                                                        (C.c_int64 * comm.size)(*lo), (C.c_int64 * comm.size)(*hi),
+                                                        C.byref(self.handle), blob))
+            self.vector_size = n
         blobs = comm.gather_objects(bytes(blob.raw)) if comm.size > 1 else [bytes(blob.raw)]
         engine._check(engine.lib.nss_p2p_connect(self.handle, b"".join(blobs)))
 
@@ -215,6 +285,12 @@ class MailboxTransport:
     def allreduce(self, src, dst):
         """dst[0] = sum over the ranks of src[0] (device buffers), the ranks' values added in rank order."""
         self.engine._check(self.engine.lib.nss_p2p_allreduce_f64(self.handle, src.data_ptr(), dst.data_ptr(), self.engine.stream))
+
+    def allreduce_vec(self, src, dst):
+        """dst = sum over the ranks of src (device buffers of the vector zone's size), added in rank order; this rank's
+        src is read inside its contribution range only."""
+        self.engine._check(self.engine.lib.nss_p2p_allreduce_vec_f64(self.handle, src.data_ptr(), dst.data_ptr(),
+                                                                    self.engine.stream))
 
     def exchange(self, which=0):
         import ctypes as C
@@ -264,13 +340,13 @@ class NativeDist:
 
     native = mailbox = None
 
-    def open_native(self, halos, nccl_comm=None, channels=None):
+    def open_native(self, halos, nccl_comm=None, channels=None, vector=None):
         """A new dist handle over `nccl_comm` or -- given `channels`, a list of (`nss_halo_t`, owned entries) per
-        operand layout -- over a `MailboxTransport` of those channels."""
+        operand layout, and optionally a `vector` zone -- over a `MailboxTransport` of those channels."""
         self.close()
         self.native = (dist_create(self.comm, self.engine, None if channels is not None else nccl_comm), halos)
         if channels is not None:
-            self.mailbox = MailboxTransport(self.comm, self.engine, channels)
+            self.mailbox = MailboxTransport(self.comm, self.engine, channels, vector)
             self.mailbox.attach(self.native[0])
 
     def close(self):
@@ -510,7 +586,8 @@ class DistributedAMG(BaseMatrix):
         self.dinv = DiagonalMatrix(self.omega / global_csr.diagonal()[r0:r1], engine=eng)   # w D^-1 on the slab
         self.coarse_levels = levels[1:]
         self.coarse = eng.amg_create(self.coarse_levels, self.omega)
-        nc = levels[1]["n"]
+        nc = self.nc = levels[1]["n"]
+        self.ranges = coarse_contribution_ranges(R, dist_A.row_offsets)     # of every rank's share of R res
         self.rc, self.ec = Vector(nc, engine=eng), Vector(nc, engine=eng)
         self.x0, self.res = dist_A.CreateRowVector(), dist_A.CreateColVector()
         self.n = r1 - r0
@@ -974,12 +1051,15 @@ class DistributedBpcg2(NativeDist):
         """`native=False` keeps the Python-driven schedule even when `comm` is an `RcclComm` (its
         collectives are then single ctypes calls into librccl between the device phases).
         `pre="amg"`: preA = the V-cycle with replicated coarse levels (`DistributedAMG`), applied inside the
-        native loop (needs the RCCL communicator: the cycle's exchanges and its coarse all-reduce are issued
-        from C); `pre="amg+bjac"` adds the block Jacobi (additive MypreA).
+        native loop (the RCCL communicator or transport="mailbox": the cycle's exchanges and its coarse all-reduce
+        are issued from C); `pre="amg+bjac"` adds the block Jacobi (additive MypreA).
         `pre="bgs"`: multicolour block Gauss-Seidel inside the slab, additive across slabs (no communication inside a
         sweep; any communicator).  `pre="mypre_a"`: the reference's default -- MypreA(GS=True): those sweeps around the
         auxiliary-space term on slabs (`DistributedAuxiliary`; `aux_options` go to its V-cycle), the residual between
-        them with the partitioned A; applied natively inside the loop (RCCL communicator, as `pre="amg"`).
+        them with the partitioned A; applied natively inside the loop (RCCL communicator or the mailbox, as `pre="amg"`).
+        `transport="mailbox"`: the native compact loop over `MailboxTransport` with any set-up communicator; with
+        "amg", "amg+bjac" and "mypre_a" the transport also carries the halos of the V-cycle and of the auxiliary-space
+        term (channels of their own operand layouts) and the coarse all-reduce (its vector zone).
         `plan`: "compact" (default; NSS_DIST_PLAN overrides) = C1 / preA / exchange / C23 / sum / all-reduce / C4 /
         sum / all-reduce with every ghost kept by recurrence behind the owned entries of its vector; "classic" = the
         eight-phase form (the only one with the interior / boundary overlap).
@@ -1068,11 +1148,13 @@ class DistributedBpcg2(NativeDist):
                 raise RuntimeError("fused distributed BPCG loop: " + self.declined)
             extra["condensed"] = ops.form.native_operators(ops.a_diag_scipy)
         if dist_amg is not None or aux is not None:     # the V-cycle / auxiliary-space term issue their collectives from C
-            if getattr(self.comm, "comm", None) is None:
-                raise RuntimeError("pre=%r inside the fused partitioned loop needs the RCCL communicator (with "
-                                   "torch.distributed use BramblePasciakCG on the distributed operands)"
-                                   % ("amg" if aux is None else "mypre_a"))
-            self._amg_dist_handle = dist_create(self.comm, self.engine, self.comm.comm)
+            mailbox = getattr(self, "want_transport", None) == "mailbox"
+            if getattr(self.comm, "comm", None) is None and not mailbox:
+                raise RuntimeError("pre=%r inside the fused partitioned loop needs the RCCL communicator or "
+                                   "transport='mailbox' (with torch.distributed use BramblePasciakCG on the distributed "
+                                   "operands)" % ("amg" if aux is None else "mypre_a"))
+            # over the mailbox transport the handle gets the transport in enable_mailbox (no RCCL inside an iteration)
+            self._amg_dist_handle = dist_create(self.comm, self.engine, None if mailbox else self.comm.comm)
         if aux is not None:                             # MypreA(GS=True) on slabs, natively inside the loop
             self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, ops.gs, self.k, ops.preM, vecs,
                                              distributed=True, dist_aux=aux.native_handle(self._amg_dist_handle, vecs["t1"]),
@@ -1197,15 +1279,34 @@ class DistributedBpcg2(NativeDist):
     def enable_mailbox(self):
         """Run the native compact loop over the mailbox transport (`MailboxTransport`): the all-reduces inside the sum
         kernels, the halo of t1 by put / wait-copy kernels -- no RCCL call in an iteration.  The set-up communicator
-        (any `TorchComm`) only gathers the IPC blobs."""
+        (any `TorchComm`) only gathers the IPC blobs.  With pre in ("amg", "amg+bjac", "mypre_a") the transport also
+        serves the V-cycle's dist handle (`_amg_dist_handle`): the halos of the V-cycle and of the auxiliary-space term
+        on the channels `mailbox_channels` gives their layouts, the coarse all-reduce through the vector zone."""
         if not getattr(self, "compact", False):
             raise RuntimeError("the mailbox transport serves the compact partitioned plan")
         if self.ops.A.plan.n_ghost and not self.ops.A.plan.direct:
             raise RuntimeError("the mailbox transport needs contiguous send runs (slab partitions have them)")
-        halo = self.ops.A.native_halo(self.t1, (0, 0))
+        ops, eng = self.ops, self.engine
+        halo = ops.A.native_halo(self.t1, (0, 0))
         condensed = self._condensed_halos()        # channels 1 (lift: t0) and 2 (extension: t1 before it)
-        self.open_native((None, halo, None), channels=[(h, self.ops.n_u) for h in (halo,) + condensed])
+        # the V-cycle / auxiliary-space term: their halos on channels of their operand layouts (the ones of A's operand
+        # on channel 0, t1's), their coarse all-reduce through the vector zone
+        dist_amg, aux = getattr(self, "dist_amg", None), getattr(ops, "aux", None)
+        V = aux.V if aux is not None else dist_amg
+        channels, index = mailbox_channels(mailbox_layouts(
+            ops, halo, condensed, aux, aux._native[1:4] if aux is not None else None, V,
+            V._native[1] if V is not None else None))
+        self.mailbox_channel_of = index
+        self.open_native((None, halo, None), channels=channels,
+                         vector=(V.nc, V.ranges[0], V.ranges[1]) if V is not None else None)
         self._set_condensed_halos(condensed)
+        if V is not None:                          # every dist handle of the run on the one transport: one `seq`
+            self.mailbox.attach(self._amg_dist_handle)
+            eng._check(eng.lib.nss_dist_amg_set_channel(V._native[0], index[-1]))
+        if aux is not None:
+            k = 1 + len(condensed)
+            eng._check(eng.lib.nss_dist_aux_set_channels(aux._native[0], index[k], index[k + 1],
+                                                         index[k + 2] if aux._native[3] is not None else 0))
         self.loop.state.p2p = self.mailbox.handle
         self.loop.keep.append(self.mailbox)
 
@@ -1357,7 +1458,7 @@ class DistributedBpcg2(NativeDist):
         """Full solve; returns (it, converged).  Every rank takes the same decision because
         the all-reduced scalars are bit-identical on all ranks."""
         self.start(tol, maxsteps)
-        done, it_final, _ = fused.run_chunked(self.iterate, self.poll, 0, maxsteps, poll_every)
+        done, it_final, _ = fused.run_chunked(self.iterate, self.poll, 0, maxsteps, poll_every, transport=self.mailbox)
         return (it_final if done else maxsteps - 1), done
 
 

@@ -57,6 +57,10 @@ def _signatures():
         "nss_csr_pair_mode": (C.c_int, [i32]),
         "nss_p2p_blob_bytes": (C.c_int, [i32, i32, c_i64_p]),
         "nss_p2p_create": (C.c_int, [i32, i32, i32, vp, vp, C.POINTER(vp), vp]),
+        "nss_p2p_create_vec": (C.c_int, [i32, i32, i32, vp, vp, C.c_int64, vp, vp, C.POINTER(vp), vp]),
+        "nss_p2p_allreduce_vec_f64": (C.c_int, [vp, vp, vp, vp]),
+        "nss_dist_amg_set_channel": (C.c_int, [vp, i32]),
+        "nss_dist_aux_set_channels": (C.c_int, [vp, i32, i32, i32]),
         "nss_dist_attach_p2p": (C.c_int, [vp, vp]),
         "nss_p2p_connect": (C.c_int, [vp, vp]),
         "nss_p2p_destroy": (C.c_int, [vp]),
