@@ -113,6 +113,20 @@ class HaloPlan:
         self.direct = all(q in self.send_runs for q in range(self.nranks) if self.send_counts[q])
         return self
 
+    def local_index(self, ids, missing):
+        """Global ids -> their index in this layout's operand ``[owned | ghosts]``.  RuntimeError(`missing`) when an id
+        is neither owned by this rank nor among the ghosts."""
+        ids = np.asarray(ids, dtype=np.int64)
+        c0, c1 = int(self.col_offsets[self.rank]), int(self.col_offsets[self.rank + 1])
+        own = (ids >= c0) & (ids < c1)
+        pos = np.searchsorted(self.ghosts, ids[~own])
+        if pos.size and not (self.n_ghost and np.array_equal(self.ghosts[np.minimum(pos, self.n_ghost - 1)], ids[~own])):
+            raise RuntimeError(missing)
+        out = np.empty(ids.shape, dtype=np.int64)
+        out[own] = ids[own] - c0
+        out[~own] = self.n_owned + pos
+        return out
+
 
 # --------------------------------------------------------------------------------------
 # communicators
@@ -204,39 +218,45 @@ def coarse_contribution_ranges(R, row_offsets):
 
 
 def mailbox_channels(halos):
-    """Channels of a `MailboxTransport` for `halos`, a list of (key, `nss_halo_t`, owned entries): one channel per
+    """Channels of a `MailboxTransport` for `halos`, a list of (name, key, `nss_halo_t`, owned entries): one channel per
     distinct key, numbered in order of first appearance.  The key is the halo plan of the operand layout (halos of one
     `DistSparseMatrix` plan share a channel; a unique object gives a channel of its own): a ROLE, the same on every
     rank, so every rank numbers its channels alike -- comparing the local receive tables would not (a rank without
-    ghosts has the same empty table on every layout).  Returns (channels [(halo, owned)], channel of each entry)."""
-    keys, chans, index = [], [], []
-    for key, h, n in halos:
+    ghosts has the same empty table on every layout).  Returns (channels [(halo, owned)], {name: channel} in the order
+    of the entries)."""
+    keys, chans, channel = [], [], {}
+    for name, key, h, n in halos:
+        if name in channel:
+            raise ValueError("mailbox_channels: two entries are named %r" % (name,))
         for c, k in enumerate(keys):
             if k is key:
-                index.append(c)
+                channel[name] = c
                 break
         else:
             keys.append(key)
             chans.append((h, n))
-            index.append(len(keys) - 1)
+            channel[name] = len(keys) - 1
     if len(chans) > P2P_MAX_CHANNELS:
         raise ValueError("the mailbox transport serves at most %d operand layouts, not %d" % (P2P_MAX_CHANNELS, len(chans)))
-    return chans, index
+    return chans, channel
 
 
 def mailbox_layouts(ops, halo_t1, condensed=(), aux=None, aux_halos=None, V=None, v_halo=None):
-    """The (key, `nss_halo_t`, owned entries) list of a BPCG v2 run over the mailbox transport, for `mailbox_channels`:
-    t1 (A's operand: channel 0), a condensed form's lift and extension (channels of their own), then the
-    auxiliary-space term's halos `aux_halos` = (x: transform.T's operand, e: transform's operand, y: t1 as A's operand
-    or None) and the V-cycle's halo `v_halo` (the operand of `V.A`)."""
-    out = [(ops.A.plan, halo_t1, ops.n_u)] + [(object(), h, ops.n_u) for h in condensed]
+    """The (name, key, `nss_halo_t`, owned entries) list of a BPCG v2 run over the mailbox transport, for
+    `mailbox_channels`: "t1" (A's operand: channel 0), a condensed form's "cond_lift" and "cond_ext" (channels of their
+    own), then the auxiliary-space term's halos `aux_halos` = (x: transform.T's operand, e: transform's operand, y: t1 as
+    A's operand or None) as "aux_x", "aux_e", "aux_y" and the V-cycle's halo `v_halo` (the operand of `V.A`) as
+    "vcycle"."""
+    out = [("t1", ops.A.plan, halo_t1, ops.n_u)]
+    out += [(name, object(), h, ops.n_u) for name, h in zip(("cond_lift", "cond_ext"), condensed)]
     if aux is not None:
         hx, he, hy = aux_halos
-        out += [(aux.transform_t.plan, hx, aux.transform_t.plan.n_owned), (aux.transform.plan, he, aux.transform.plan.n_owned)]
+        out += [("aux_x", aux.transform_t.plan, hx, aux.transform_t.plan.n_owned),
+                ("aux_e", aux.transform.plan, he, aux.transform.plan.n_owned)]
         if hy is not None:
-            out.append((ops.A.plan, hy, ops.n_u))
+            out.append(("aux_y", ops.A.plan, hy, ops.n_u))
     if V is not None:
-        out.append((V.A.plan, v_halo, V.A.plan.n_owned))
+        out.append(("vcycle", V.A.plan, v_halo, V.A.plan.n_owned))
     return out
 
 
@@ -317,6 +337,8 @@ class MailboxTransport:
             self.engine.lib.nss_p2p_destroy(self.handle)
             self.handle = None
 
+    destroy = close             # (as a `NativeDist` owns it)
+
     def __del__(self):
         try:
             self.close()
@@ -333,32 +355,70 @@ def dist_create(comm, engine, nccl_comm):
     return handle
 
 
+class NativeHandle:
+    """One native C handle with what belongs to it: ``handle``, the `nss_halo_t` descriptors it was given as attributes
+    by the name of the operand they serve (kept alive with it), ``dist`` = the dist handle it was created on (None for
+    a dist handle itself) and its destroy function.  `destroy` is idempotent."""
+
+    def __init__(self, handle, destroy, dist=None, **halos):
+        self.handle, self.dist, self._destroy = handle, dist, destroy
+        self.__dict__.update(halos)
+
+    def destroy(self):
+        if self.handle is not None:
+            self._destroy(self.handle)
+            self.handle = None
+
+
 class NativeDist:
-    """The native transport of a partitioned loop that issues its iterations from C (``nss_*_iterate_dist``):
-    ``native`` = (dist handle, the halos the loop exchanges) and ``mailbox`` = the `MailboxTransport` attached to the
-    handle, both None until `open_native`.  `close` frees them in dependency order, the mailbox first."""
+    """The native resources of a partitioned loop that issues its iterations from C (``nss_*_iterate_dist``):
+    ``native`` = the `NativeHandle` of the loop's dist handle with the halos the loop exchanges, ``mailbox`` = the
+    `MailboxTransport` attached to it, both None until `open_native`.  Every native handle made for the run is `own`ed
+    by it, in order of creation -- a handle may point into the ones made before it -- and `release` frees them in the
+    reverse order: nothing else destroys them."""
 
     native = mailbox = None
+    _owned = ()
+
+    def own(self, holder):
+        """`release` destroys `holder` (idempotent `destroy()`), before everything owned earlier."""
+        self._owned = [*self._owned, holder]
+        return holder
 
     def open_native(self, halos, nccl_comm=None, channels=None, vector=None):
-        """A new dist handle over `nccl_comm` or -- given `channels`, a list of (`nss_halo_t`, owned entries) per
-        operand layout, and optionally a `vector` zone -- over a `MailboxTransport` of those channels."""
+        """A new dist handle for the loop's `halos` (name -> `nss_halo_t` or None) over `nccl_comm` or -- given
+        `channels`, a list of (`nss_halo_t`, owned entries) per operand layout, and optionally a `vector` zone -- over
+        a `MailboxTransport` of those channels."""
         self.close()
-        self.native = (dist_create(self.comm, self.engine, None if channels is not None else nccl_comm), halos)
+        handle = dist_create(self.comm, self.engine, None if channels is not None else nccl_comm)
+        self.native = self.own(NativeHandle(handle, self.engine.lib.nss_dist_destroy, **halos))
         if channels is not None:
-            self.mailbox = MailboxTransport(self.comm, self.engine, channels, vector)
-            self.mailbox.attach(self.native[0])
+            self.mailbox = self.own(MailboxTransport(self.comm, self.engine, channels, vector))
+            self.mailbox.attach(handle)
+
+    def open_for(self, operands, transport, native):
+        """The transport of a loop that exchanges `operands`, name -> (`DistSparseMatrix`, its `HaloVector`): the
+        mailbox with one channel per operand when `transport` is "mailbox" (any set-up communicator), RCCL when `native`
+        and the communicator is an `RcclComm`, none otherwise (the host-driven schedule)."""
+        if transport == "mailbox":
+            halos = {name: m.native_halo(hv, (0, 0)) for name, (m, hv) in operands.items()}
+            self.open_native(halos, channels=[(halos[name], m.n_cols_owned) for name, (m, _) in operands.items()])
+        elif native and getattr(self.comm, "comm", None) is not None:        # RcclComm: an ncclComm_t
+            self.open_native({name: m.native_halo(hv) for name, (m, hv) in operands.items()}, nccl_comm=self.comm.comm)
 
     def close(self):
-        if self.mailbox is not None:
-            self.mailbox.close()
-            self.mailbox = None
-        if self.native is not None:
-            self.engine.lib.nss_dist_destroy(self.native[0])
-            self.native = None
+        """Free the loop's transport, the mailbox first (`open_native` makes a new one); what else the run owns stays."""
+        for holder in (self.mailbox, self.native):
+            if holder is not None:
+                holder.destroy()
+                self._owned.remove(holder)
+        self.mailbox = self.native = None
 
     def release(self):
         self.close()
+        for holder in reversed(self._owned):
+            holder.destroy()
+        self._owned = []
 
     def __del__(self):
         try:
@@ -591,13 +651,14 @@ class DistributedAMG(BaseMatrix):
         self.rc, self.ec = Vector(nc, engine=eng), Vector(nc, engine=eng)
         self.x0, self.res = dist_A.CreateRowVector(), dist_A.CreateColVector()
         self.n = r1 - r0
-        self._native = None
+        self.native = None
 
     def native_handle(self, dist_handle):
-        """`nss_dist_amg_t` of this cycle for the native partitioned loops (created once): the C loop then
-        issues the cycle's two halo exchanges and its coarse all-reduce itself."""
+        """`NativeHandle` of the `nss_dist_amg_t` of this cycle for the native partitioned loops (created once; halo
+        ``x``: the iterate as A's operand): the C loop then issues the cycle's two halo exchanges and its coarse
+        all-reduce itself.  The run that asked for it owns and destroys it (`NativeDist.own`)."""
         import ctypes as C
-        if self._native is None:
+        if self.native is None or self.native.handle is None:
             eng = self.engine
             self._x_native = self.A.operand()                      # the iterate, halo-extended
             halo = self.A.native_halo(self._x_native)
@@ -605,22 +666,14 @@ class DistributedAMG(BaseMatrix):
             eng._check(eng.lib.nss_dist_amg_create(dist_handle, self.A.local.handle.ptr, C.byref(halo),
                                                    self.R_loc.handle.ptr, self.P_loc.handle.ptr,
                                                    self.dinv.d.data_ptr(), self.coarse.ptr, C.byref(out)))
-            self._native = (out, halo, dist_handle)
-        return self._native[0]
+            self.native = NativeHandle(out, eng.lib.nss_dist_amg_destroy, dist=dist_handle, x=halo)
+        return self.native
 
     def native_apply(self, scale, b, y):
         """y = scale * V(b) through the native handle (tests)."""
         eng = self.engine
-        eng._check(eng.lib.nss_dist_amg_apply_f64(self._native[0], float(scale), b.buf.data_ptr(), y.buf.data_ptr(),
+        eng._check(eng.lib.nss_dist_amg_apply_f64(self.native.handle, float(scale), b.buf.data_ptr(), y.buf.data_ptr(),
                                                   eng.stream))
-
-    def __del__(self):
-        try:
-            if self._native is not None:
-                self.engine.lib.nss_dist_amg_destroy(self._native[0])
-                self._native = None
-        except Exception:
-            pass
 
     def Height(self):
         return self.n
@@ -679,7 +732,7 @@ class DistributedAuxiliary(BaseMatrix):
         self.level_sizes = self.V.level_sizes
         self.n = ops.n_u
         self._r, self._e = self.transform_t.CreateColVector(), self.transform_t.CreateColVector()
-        self._native = None
+        self.native = None
 
     def Height(self):
         return self.n
@@ -704,38 +757,26 @@ class DistributedAuxiliary(BaseMatrix):
         return self
 
     def native_handle(self, dist_handle, t1=None):
-        """`nss_dist_aux_t` (created once).  `t1`: the loop's iterate as A's operand (`HaloVector`), needed by the
-        multiplicative MypreA."""
+        """`NativeHandle` of the `nss_dist_aux_t` (created once; halos ``x``: transform.T's operand, ``e``: transform's,
+        ``y``: `t1` or None), made on the V-cycle's handle -- `self.V.native_handle(dist_handle)`, which the run owns
+        first.  `t1`: the loop's iterate as A's operand (`HaloVector`), needed by the multiplicative MypreA."""
         import ctypes as C
-        if self._native is None:
+        if self.native is None or self.native.handle is None:
             eng = self.engine
             self._x_native, self._e_native = self.transform_t.operand(), self.transform.operand()
             hx, he = self.transform_t.native_halo(self._x_native), self.transform.native_halo(self._e_native)
             hy = self.ops.A.native_halo(t1) if t1 is not None else None
             out = C.c_void_p()
             eng._check(eng.lib.nss_dist_aux_create(dist_handle, self.transform_t.local.handle.ptr, C.byref(hx),
-                                                   self.transform.local.handle.ptr, C.byref(he), self.V.native_handle(dist_handle),
+                                                   self.transform.local.handle.ptr, C.byref(he),
+                                                   self.V.native_handle(dist_handle).handle,
                                                    C.byref(hy) if hy is not None else None, C.byref(out)))
-            self._native = (out, hx, he, hy, dist_handle)
-        return self._native[0]
+            self.native = NativeHandle(out, eng.lib.nss_dist_aux_destroy, dist=dist_handle, x=hx, e=he, y=hy)
+        return self.native
 
     def native_apply(self, scale, b, y):
         eng = self.engine
-        eng._check(eng.lib.nss_dist_aux_apply_f64(self._native[0], float(scale), b.buf.data_ptr(), y.buf.data_ptr(), eng.stream))
-
-    def release(self):
-        if self._native is not None:
-            self.engine.lib.nss_dist_aux_destroy(self._native[0])
-            self._native = None
-        if getattr(self.V, "_native", None) is not None:
-            self.engine.lib.nss_dist_amg_destroy(self.V._native[0])
-            self.V._native = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+        eng._check(eng.lib.nss_dist_aux_apply_f64(self.native.handle, float(scale), b.buf.data_ptr(), y.buf.data_ptr(), eng.stream))
 
 
 class DistributedMypreA(BaseMatrix):
@@ -884,15 +925,7 @@ class DistributedStokes:
         self.form = DistributedCondensedForm(self, parts) if self.condense else None
         self.S = self.form.mat if self.condense else None
         # rows of B of the ghost pressure cells, columns in the layout of B's operand
-        cols = rows_gp.indices.astype(np.int64)
-        own = (cols >= v0g) & (cols < v1g)
-        newc = np.empty_like(cols)
-        newc[own] = cols[own] - v0g
-        pos = np.searchsorted(self.B.plan.ghosts, cols[~own])
-        if cols[~own].size and not np.array_equal(self.B.plan.ghosts[np.minimum(pos, self.B.plan.ghosts.size - 1)],
-                                                  cols[~own]):
-            raise RuntimeError("ghost rows of B reference columns outside B's operand")
-        newc[~own] = self.B.plan.n_owned + pos
+        newc = self.B.plan.local_index(rows_gp.indices, "ghost rows of B reference columns outside B's operand")
         self.ghost_p = ghost_p
         self._rows_gp, self._v_range = rows_gp, (v0g, v1g)
         self._b_ext = None
@@ -980,25 +1013,16 @@ class DistributedStokes:
         """Rows [this slab's pressure rows | rows of the ghost pressure cells of B^T's operand] of B with the
         columns numbered in the layout of A's operand ([owned | A's ghosts]): what the compact partitioned
         plan multiplies with `t1 - s0` formed on the fly (nss_bpcg2_t.dist_compact)."""
-        v0, v1 = self._v_range
-        n_u, ga = self.A.plan.n_owned, self.A.plan.ghosts
+        v0 = self._v_range[0]
 
         def on_a(cols_global):
-            cols = np.asarray(cols_global, dtype=np.int64)
-            own = (cols >= v0) & (cols < v1)
-            out = np.empty_like(cols)
-            out[own] = cols[own] - v0
-            pos = np.searchsorted(ga, cols[~own])
-            if cols[~own].size and (pos.max(initial=0) >= ga.size or not np.array_equal(ga[np.minimum(pos, ga.size - 1)], cols[~own])):
-                raise RuntimeError("a row of B references a column outside A's operand")
-            out[~own] = n_u + pos
-            return out.astype(np.int32)
+            return self.A.plan.local_index(cols_global, "a row of B references a column outside A's operand").astype(np.int32)
 
         loc = self.B.local_scipy                                    # columns in B's layout -> global -> A's layout
         cols_b = loc.indices.astype(np.int64)
         glob = np.where(cols_b < self.B.plan.n_owned, cols_b + v0,
                         self.B.plan.ghosts[np.maximum(cols_b - self.B.plan.n_owned, 0)] if self.B.plan.n_ghost else 0)
-        width = n_u + ga.size
+        width = self.A.plan.n_owned + self.A.plan.n_ghost
         own_rows = sp.csr_matrix((loc.data, on_a(glob), loc.indptr), shape=(loc.shape[0], width))
         gp = self._rows_gp
         ghost_rows = sp.csr_matrix((gp.data, on_a(gp.indices), gp.indptr), shape=(gp.shape[0], width))
@@ -1038,13 +1062,16 @@ class DistributedBpcg2(NativeDist):
     exchange (t1) and two all-reduces in between; the ghosts of the other two SpMV operands are kept
     current by redundant computation (nss_bpcg2_t.ghost_*)."""
 
-    # (kind, argument): device phases between two communication points go down in one C call
-    SCHEDULE = (("halo", "s1"), ("phases", ("K1", "K1")), ("halo", "t1"), ("phases", ("K2", "K2")),
-                ("halo", "t4"), ("phases", ("K3", "SUM1")), ("allreduce", 1), ("phases", ("ALPHA", "SUM2")),
-                ("allreduce", 2), ("phases", ("BETA", "K5")))
-    # the compact plan (default): 6 launches + 3 collectives per iteration instead of 9 + 3
-    SCHEDULE_COMPACT = (("cphases", ("C1", "C1")), ("halo", "t1"), ("cphases", ("C23", "SUMA")), ("allreduce", 1),
-                        ("cphases", ("C4", "SUMW")), ("allreduce", 2))
+    # The host-driven schedule, walked by `iterate` and `profile` alike: (segment, kind, argument) with `segment` = the
+    # index in `PHASE_NAMES` of the profile segment the step opens (it lasts until the next one opens), None for a step
+    # inside the current segment.  Device phases between two segment boundaries go down in one C call.
+    SCHEDULE = ((0, "halo", "s1"), (None, "phases", ("K1", "K1")), (1, "halo", "t1"), (2, "phases", ("K2", "K2")),
+                (3, "halo", "t4"), (None, "phases", ("K3", "SUM1")), (4, "allreduce", 1), (5, "phases", ("ALPHA", "SUM2")),
+                (6, "allreduce", 2), (7, "phases", ("BETA", "K5")))
+    # the compact plan (default): 6 launches + 3 collectives per iteration instead of 9 + 3 (segment 7 stays empty)
+    SCHEDULE_COMPACT = ((0, "cphases", ("C1", "C1")), (1, "halo", "t1"), (2, "cphases", ("C23", "C23")),
+                        (3, "cphases", ("SUMA", "SUMA")), (4, "allreduce", 1), (5, "cphases", ("C4", "SUMW")),
+                        (6, "allreduce", 2))
 
     def __init__(self, sysm, f, g, blocks, dist, engine=None, comm=None, quiet=True, native=True, pre=None, plan=None,
                  aux_options=None, transport=None, condense=False, k=None, seed=0):
@@ -1086,7 +1113,7 @@ class DistributedBpcg2(NativeDist):
         ops = self.ops = DistributedStokes(sysm, blocks, self.comm, self.engine,
                                            pre=pre if pre in ("bgs", "mypre_a") else None, aux_options=aux_options,
                                            condense=self.condense, seed=seed)
-        self.dist_amg = None
+        self.dist_amg = self.jacobi_part = None
         if pre in ("amg", "amg+bjac"):
             self.dist_amg = DistributedAMG(sysm.A, ops.A)
             self.jacobi_part = ops.preA if pre == "amg+bjac" else None
@@ -1102,6 +1129,8 @@ class DistributedBpcg2(NativeDist):
             raise ValueError("plan must be 'compact' or 'classic'")
         self.compact = plan == "compact" and ops.compact_layout_ok() and os.environ.get("NSS_GHOST_T4", "1") == "1" \
             and os.environ.get("NSS_GHOST_S1", "1") == "1"
+        self.schedule = self.SCHEDULE_COMPACT if self.compact else self.SCHEDULE
+        self.ghost_p_mode = False
         workspace = dict(t1=self.t1, t4=self.t4, s1=self.s1)
         if self.compact:       # ghost copies behind the owned entries: s0, w0 like A's operand, w1, t3 like B^T's
             workspace.update(s0=ops.A.operand(), w0=ops.A.operand(), w1=ops.BT.operand(), t3=ops.BT.operand())
@@ -1121,59 +1150,31 @@ class DistributedBpcg2(NativeDist):
                           t3=ses.t3, t4=self.t4))
         self.ses = ses
 
-    @classmethod
-    def from_state(cls, ops, k, wdn, err0, vecs):
-        """Attach the fused loop to an already prepared state (`vecs`: the owned slices of
-        u, d, w, s, z0, q = A s0; t1 / t4 / s1 must be `HaloVector`s of ops.A / ops.B / ops.BT)."""
-        self = cls.__new__(cls)
-        self.engine, self.comm, self.ops = ops.engine, ops.comm, ops
-        self.k, self.wdn, self.err0 = k, wdn, err0
-        self.t1, self.t4, self.s1 = vecs["t1"], vecs["t4"], vecs["s1"]
-        self.compact = False
-        self.first_direction = lambda: None
-        self._attach(vecs)
-        return self
-
     def _attach(self, vecs):
+        """The fused loop on the prepared state `vecs`, its ghost recurrences and its native transport."""
         from hipla.fused import Bpcg2Loop
         ops = self.ops
         self.vecs = vecs
-        dist_amg, aux = getattr(self, "dist_amg", None), getattr(ops, "aux", None)
-        compact = getattr(self, "compact", False)
-        matB = ops.b_extended() if compact else ops.B.local
-        extra = dict(ghost_rows_b=int(ops.BT.plan.n_ghost)) if compact else {}
-        if getattr(self, "condense", False):
-            if not compact:
+        matB = ops.b_extended() if self.compact else ops.B.local
+        extra = dict(ghost_rows_b=int(ops.BT.plan.n_ghost)) if self.compact else {}
+        if self.condense:
+            if not self.compact:
                 self.declined = "a condensed form on slabs runs on the compact plan only"
                 raise RuntimeError("fused distributed BPCG loop: " + self.declined)
             extra["condensed"] = ops.form.native_operators(ops.a_diag_scipy)
-        if dist_amg is not None or aux is not None:     # the V-cycle / auxiliary-space term issue their collectives from C
-            mailbox = getattr(self, "want_transport", None) == "mailbox"
-            if getattr(self.comm, "comm", None) is None and not mailbox:
-                raise RuntimeError("pre=%r inside the fused partitioned loop needs the RCCL communicator or "
-                                   "transport='mailbox' (with torch.distributed use BramblePasciakCG on the distributed "
-                                   "operands)" % ("amg" if aux is None else "mypre_a"))
-            # over the mailbox transport the handle gets the transport in enable_mailbox (no RCCL inside an iteration)
-            self._amg_dist_handle = dist_create(self.comm, self.engine, None if mailbox else self.comm.comm)
-        if aux is not None:                             # MypreA(GS=True) on slabs, natively inside the loop
-            self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, ops.gs, self.k, ops.preM, vecs,
-                                             distributed=True, dist_aux=aux.native_handle(self._amg_dist_handle, vecs["t1"]),
-                                             **extra)
-            if self.loop is not None:
-                self.loop.keep.append(aux)
-        elif dist_amg is not None:
-            self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, self.jacobi_part, self.k, ops.preM,
-                                             vecs, distributed=True, dist_amg=dist_amg.native_handle(self._amg_dist_handle),
-                                             **extra)
-            self.loop.keep.append(dist_amg)        # the object, not just its raw handle
-        else:
-            self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, ops.preA, self.k, ops.preM, vecs,
-                                             distributed=True, **extra)
+        pre = ops.preA
+        if ops.aux is not None:                         # MypreA(GS=True) on slabs, natively inside the loop
+            pre, extra["dist_aux"] = ops.gs, self._native_preconditioner().handle
+        elif self.dist_amg is not None:
+            pre, extra["dist_amg"] = self.jacobi_part, self._native_preconditioner().handle
+        self.loop = Bpcg2Loop.try_create(ops.A.local, matB, ops.BT.local, pre, self.k, ops.preM, vecs, distributed=True,
+                                         **extra)
         if self.loop is None:
             self.declined = Bpcg2Loop.last_declined
             raise RuntimeError("fused distributed BPCG loop needs the HIP engine and native operands (%s)" % self.declined)
+        self.loop.keep.append(ops.aux if ops.aux is not None else self.dist_amg)     # the object, not just its raw handle
         self.halo = {"s1": (ops.BT, self.s1), "t1": (ops.A, self.t1), "t4": (ops.B, self.t4)}
-        if compact:
+        if self.compact:
             self.ghost_mode = self._setup_ghosts_compact()
         else:
             self.ghost_mode = os.environ.get("NSS_GHOST_T4", "1") == "1" and self._setup_ghosts()
@@ -1183,24 +1184,40 @@ class DistributedBpcg2(NativeDist):
         # mode 1 cost 98 us per iteration -- more than the three small exchanges they hide.
         self.overlap = int(os.environ.get("NSS_OVERLAP", "0"))
         comm_handle = getattr(self.comm, "comm", None)         # RcclComm: an ncclComm_t
-        if comm_handle is not None and getattr(self, "want_native", True) and hasattr(self.loop.lib, "nss_bpcg2_iterate_dist"):
+        if comm_handle is not None and self.want_native and hasattr(self.loop.lib, "nss_bpcg2_iterate_dist"):
             self.enable_native(comm_handle)
-        if getattr(self, "want_transport", None) == "mailbox":
+        if self.want_transport == "mailbox":
             self.enable_mailbox()
-        if getattr(self, "condense", False) and self.native is None:
+        if self.condense and self.native is None:
             self.declined = ("a condensed form on slabs needs the native loop (an RCCL communicator or transport='mailbox'); "
                              "with torch.distributed run BramblePasciakCG on ops.form")
             raise RuntimeError("fused distributed BPCG loop: " + self.declined)
+
+    def _native_preconditioner(self):
+        """The native handle of the auxiliary-space term (`ops.aux`) or else of the V-cycle (`dist_amg`), which issue
+        their collectives from C.  Owned in the order the handles point into each other: the dist handle made for them,
+        the V-cycle, the auxiliary-space term on it."""
+        aux, mailbox = self.ops.aux, self.want_transport == "mailbox"
+        if getattr(self.comm, "comm", None) is None and not mailbox:
+            raise RuntimeError("pre=%r inside the fused partitioned loop needs the RCCL communicator or "
+                               "transport='mailbox' (with torch.distributed use BramblePasciakCG on the distributed "
+                               "operands)" % ("amg" if aux is None else "mypre_a"))
+        # over the mailbox transport the handle gets the transport in enable_mailbox (no RCCL inside an iteration)
+        on = self.own(NativeHandle(dist_create(self.comm, self.engine, None if mailbox else self.comm.comm),
+                                   self.engine.lib.nss_dist_destroy)).handle
+        native = self.own((aux.V if aux is not None else self.dist_amg).native_handle(on))
+        return native if aux is None else self.own(aux.native_handle(on, self.t1))
 
     def _setup_ghosts(self):
         """Ghost copies of s0 / w0 on the ghost columns of B's operand (nss_bpcg2_t.ghost_*): every
         ghost of B must also be a ghost of A's operand, which DistributedStokes arranges."""
         ops, eng = self.ops, self.engine
-        gb, ga = ops.B.plan.ghosts, ops.A.plan.ghosts
-        pos = np.searchsorted(ga, gb)
-        if gb.size and (pos.max(initial=0) >= ga.size or not np.array_equal(ga[np.minimum(pos, ga.size - 1)], gb)):
-            return False
-        self._ghost_map = eng.index_buffer((ops.A.plan.n_owned + pos).astype(np.int32))
+        gb = ops.B.plan.ghosts
+        try:
+            on_a = ops.A.plan.local_index(gb, "a ghost of B's operand is not among those of A's")
+        except RuntimeError:
+            return False                                 # (the eight-phase plan then exchanges t4 and s1)
+        self._ghost_map = eng.index_buffer(on_a.astype(np.int32))
         self._ghost_s0 = eng.zeros(max(1, gb.size))
         self._ghost_w0 = eng.zeros(max(1, gb.size))
         st = self.loop.state
@@ -1209,10 +1226,8 @@ class DistributedBpcg2(NativeDist):
         st.ghost_s0, st.ghost_w0 = self._ghost_s0.data_ptr(), self._ghost_w0.data_ptr()
         self._ghost_tmp = ops.B.operand()
         # pressure part: s1 on the ghost cells of B^T's operand (nss_bpcg2_t.ghost_p_*)
-        self.ghost_p_mode = False
-        gp = getattr(ops, "ghost_p", None)
-        if (os.environ.get("NSS_GHOST_S1", "1") == "1" and gp is not None
-                and np.array_equal(gp, ops.BT.plan.ghosts)):
+        gp = ops.ghost_p
+        if os.environ.get("NSS_GHOST_S1", "1") == "1" and np.array_equal(gp, ops.BT.plan.ghosts):
             self._ghost_b = SparseMatrix.from_scipy(ops.ghost_rows_B, engine=eng) if gp.size else None
             self._ghost_t3 = eng.zeros(max(1, gp.size))
             self._ghost_w1 = eng.zeros(max(1, gp.size))
@@ -1247,7 +1262,7 @@ class DistributedBpcg2(NativeDist):
     def _fill_ghosts(self):
         """Initial values of the ghost copies: one exchange each of s0 and w0 over B's halo plan."""
         ops, eng = self.ops, self.engine
-        if getattr(self, "compact", False):      # the vectors are operand buffers: exchange them in place, once
+        if self.compact:                         # the vectors are operand buffers: exchange them in place, once
             v = self.vecs
             for name, mat in (("s0", ops.A), ("w0", ops.A), ("s1", ops.BT), ("w1", ops.BT)):
                 mat.exchange(v[name])
@@ -1258,7 +1273,7 @@ class DistributedBpcg2(NativeDist):
             ops.B.exchange(self._ghost_tmp)
             if n_g:
                 eng.copy(eng.view(self._ghost_tmp.ext, n_own, n_own + n_g), eng.view(dst, 0, n_g))
-        if getattr(self, "ghost_p_mode", False):
+        if self.ghost_p_mode:
             n_own, n_g = ops.BT.plan.n_owned, ops.BT.plan.n_ghost
             ops.BT.exchange(self.s1)                                   # s1's ghost tail: once per solve
             eng.copy(self.vecs["w1"].buf, self._ghost_tmp_p.buf)
@@ -1271,49 +1286,48 @@ class DistributedBpcg2(NativeDist):
         packs, events and the interior/boundary split without Python in the loop."""
         ops, interior = self.ops, interior or {}
         condensed = self._condensed_halos()
-        self.open_native((ops.BT.native_halo(self.s1, interior.get("s1")), ops.A.native_halo(self.t1, interior.get("t1")),
-                          ops.B.native_halo(self.t4, interior.get("t4"))),     # (the compact plan uses the middle one only)
-                         nccl_comm=comm_handle)
+        self.open_native(dict(s1=ops.BT.native_halo(self.s1, interior.get("s1")),
+                              t1=ops.A.native_halo(self.t1, interior.get("t1")),      # (the compact plan uses this one only)
+                              t4=ops.B.native_halo(self.t4, interior.get("t4"))), nccl_comm=comm_handle)
         self._set_condensed_halos(condensed)
 
     def enable_mailbox(self):
         """Run the native compact loop over the mailbox transport (`MailboxTransport`): the all-reduces inside the sum
         kernels, the halo of t1 by put / wait-copy kernels -- no RCCL call in an iteration.  The set-up communicator
         (any `TorchComm`) only gathers the IPC blobs.  With pre in ("amg", "amg+bjac", "mypre_a") the transport also
-        serves the V-cycle's dist handle (`_amg_dist_handle`): the halos of the V-cycle and of the auxiliary-space term
+        serves the dist handle made for the V-cycle (`V.native.dist`): the halos of the V-cycle and of the auxiliary-space term
         on the channels `mailbox_channels` gives their layouts, the coarse all-reduce through the vector zone."""
-        if not getattr(self, "compact", False):
+        if not self.compact:
             raise RuntimeError("the mailbox transport serves the compact partitioned plan")
         if self.ops.A.plan.n_ghost and not self.ops.A.plan.direct:
             raise RuntimeError("the mailbox transport needs contiguous send runs (slab partitions have them)")
         ops, eng = self.ops, self.engine
         halo = ops.A.native_halo(self.t1, (0, 0))
-        condensed = self._condensed_halos()        # channels 1 (lift: t0) and 2 (extension: t1 before it)
+        condensed = self._condensed_halos()
         # the V-cycle / auxiliary-space term: their halos on channels of their operand layouts (the ones of A's operand
-        # on channel 0, t1's), their coarse all-reduce through the vector zone
-        dist_amg, aux = getattr(self, "dist_amg", None), getattr(ops, "aux", None)
-        V = aux.V if aux is not None else dist_amg
-        channels, index = mailbox_channels(mailbox_layouts(
-            ops, halo, condensed, aux, aux._native[1:4] if aux is not None else None, V,
-            V._native[1] if V is not None else None))
-        self.mailbox_channel_of = index
-        self.open_native((None, halo, None), channels=channels,
+        # on t1's), their coarse all-reduce through the vector zone
+        aux = ops.aux
+        V = aux.V if aux is not None else self.dist_amg
+        channels, channel = mailbox_channels(mailbox_layouts(
+            ops, halo, condensed, aux, (aux.native.x, aux.native.e, aux.native.y) if aux is not None else None, V,
+            V.native.x if V is not None else None))
+        self.mailbox_channel_of = list(channel.values())
+        self.open_native(dict(s1=None, t1=halo, t4=None), channels=channels,
                          vector=(V.nc, V.ranges[0], V.ranges[1]) if V is not None else None)
         self._set_condensed_halos(condensed)
         if V is not None:                          # every dist handle of the run on the one transport: one `seq`
-            self.mailbox.attach(self._amg_dist_handle)
-            eng._check(eng.lib.nss_dist_amg_set_channel(V._native[0], index[-1]))
+            self.mailbox.attach(V.native.dist)
+            eng._check(eng.lib.nss_dist_amg_set_channel(V.native.handle, channel["vcycle"]))
         if aux is not None:
-            k = 1 + len(condensed)
-            eng._check(eng.lib.nss_dist_aux_set_channels(aux._native[0], index[k], index[k + 1],
-                                                         index[k + 2] if aux._native[3] is not None else 0))
+            eng._check(eng.lib.nss_dist_aux_set_channels(aux.native.handle, channel["aux_x"], channel["aux_e"],
+                                                         channel.get("aux_y", 0)))
         self.loop.state.p2p = self.mailbox.handle
         self.loop.keep.append(self.mailbox)
 
     def _condensed_halos(self):
         """A condensed form's halos of t0 (the lift) and of t1 (the extension), both in the layout of A's operand; ()
         without one."""
-        if not getattr(self, "condense", False):
+        if not self.condense:
             return ()
         return self.ops.A.native_halo(self.vecs["t0"], (0, 0)), self.ops.A.native_halo(self.t1, (0, 0))
 
@@ -1321,28 +1335,13 @@ class DistributedBpcg2(NativeDist):
         """nss_dist_set_condensed: the native handle gets the `_condensed_halos`, kept alive with it."""
         import ctypes as C
         if halos:
-            self.engine._check(self.engine.lib.nss_dist_set_condensed(self.native[0], *(C.byref(h) for h in halos)))
+            self.engine._check(self.engine.lib.nss_dist_set_condensed(self.native.handle, *(C.byref(h) for h in halos)))
             self._cond_halos = halos
 
     def close(self):
         if self.mailbox is not None:
             self.loop.state.p2p = None
         super().close()
-
-    def release(self):
-        """Free the native handles in dependency order: the loop's dist handle, the V-cycle's native handle (it
-        points into the dist handle created for it), then that dist handle."""
-        self.close()
-        aux = getattr(getattr(self, "ops", None), "aux", None)
-        if aux is not None:
-            aux.release()
-        amg = getattr(self, "dist_amg", None)
-        if amg is not None and getattr(amg, "_native", None) is not None:
-            amg.engine.lib.nss_dist_amg_destroy(amg._native[0])
-            amg._native = None
-        if getattr(self, "_amg_dist_handle", None) is not None:
-            self.engine.lib.nss_dist_destroy(self._amg_dist_handle)
-            self._amg_dist_handle = None
 
     def start(self, tol, maxsteps, rel_err=True):
         self.first_direction()
@@ -1352,92 +1351,57 @@ class DistributedBpcg2(NativeDist):
 
     def iterate(self, it_begin, it_end):
         if self.native is not None:
-            self.loop.enqueue_dist(self.native[0], self.native[1], self.overlap, it_begin, it_end)
+            nat = self.native
+            self.loop.enqueue_dist(nat.handle, nat.s1, nat.t1, nat.t4, self.overlap, it_begin, it_end)
             return
-        loop, comm = self.loop, self.comm
         for it in range(it_begin, it_end):
-            for kind, what in (self.SCHEDULE_COMPACT if getattr(self, "compact", False) else self.SCHEDULE):
-                if kind == "cphases":
-                    loop.cphases(what[0], what[1], it)
-                    continue
-                if kind == "halo" and what == "t4" and self.ghost_mode:
-                    continue                             # t4's ghosts are derived from t1's in K2
-                if kind == "halo" and what == "s1" and getattr(self, "ghost_p_mode", False):
-                    continue                             # s1's ghosts follow their own recurrence
-                if kind == "phases":
-                    loop.phases(what[0], what[1], it)
-                elif kind == "halo":
+            self._issue(it)
+
+    def _issue(self, it, mark=None):
+        """Iteration `it` of the host-driven schedule; `mark(i)` is called where profile segment i opens."""
+        loop = self.loop
+        for segment, kind, what in self.schedule:
+            if mark is not None and segment is not None:
+                mark(segment)
+            if kind == "halo":
+                # t4's ghosts are derived from t1's, s1's follow their own recurrence
+                if not ((what == "t4" and self.ghost_mode) or (what == "s1" and self.ghost_p_mode)):
                     mat, hv = self.halo[what]
                     mat.exchange(hv)
-                else:                                    # local sum in scal[8 + what] -> global in scal[what]
-                    comm.allreduce_sum_into(loop.scal[8 + what:9 + what], loop.scal[what:what + 1])
+            elif kind == "allreduce":                    # local sum in scal[8 + what] -> global in scal[what]
+                self.comm.allreduce_sum_into(loop.scal[8 + what:9 + what], loop.scal[what:what + 1])
+            else:                                        # "phases" / "cphases" of the loop
+                getattr(loop, kind)(what[0], what[1], it)
 
     PHASE_NAMES = ("K1_BT_preA", "exchange_t1", "K2_A", "K3_B_sum", "allreduce_sKs", "K4_sum", "allreduce_wd", "K5")
     PHASE_NAMES_COMPACT = ("C1_BT_preA", "exchange_t1", "C23_A_B", "sum_sKs", "allreduce_sKs", "C4_sum", "allreduce_wd",
                            "unused")
 
     def phase_names(self):
-        return self.PHASE_NAMES_COMPACT if getattr(self, "compact", False) else self.PHASE_NAMES
+        return self.PHASE_NAMES_COMPACT if self.compact else self.PHASE_NAMES
 
     def profile(self, it_begin, iterations):
         """Per-phase device times (ms, averaged) of `iterations` further iterations.  Native loop: HIP
         events recorded by the C loop itself (nss_dist_profile_*); Python-driven schedule: torch events
-        around the same segments (includes the host's issue gaps)."""
+        at the segment boundaries of the schedule (includes the host's issue gaps)."""
         import ctypes as C
         eng = self.engine
         if self.native is not None:
-            eng._check(eng.lib.nss_dist_profile_begin(self.native[0], int(iterations)))
+            eng._check(eng.lib.nss_dist_profile_begin(self.native.handle, int(iterations)))
             self.iterate(it_begin, it_begin + iterations)
             out = (C.c_double * 8)()
             n = C.c_int32()
-            eng._check(eng.lib.nss_dist_profile_end(self.native[0], out, C.byref(n)))
+            eng._check(eng.lib.nss_dist_profile_end(self.native.handle, out, C.byref(n)))
             return dict(zip(self.phase_names(), [float(v) for v in out])), n.value
         torch = eng.torch
-        loop, comm = self.loop, self.comm
+        opened = 1 + max(segment for segment, _, _ in self.schedule if segment is not None)
         acc = [0.0] * 8
         marks = []
-        for it in range(it_begin, it_begin + (iterations if getattr(self, "compact", False) else 0)):
+        for it in range(it_begin, it_begin + iterations):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(9)]
-            ev[0].record()
-            loop.cphases("C1", "C1", it)
-            ev[1].record()
-            self.halo["t1"][0].exchange(self.halo["t1"][1])
-            ev[2].record()
-            loop.cphases("C23", "C23", it)
-            ev[3].record()
-            loop.cphases("SUMA", "SUMA", it)
-            ev[4].record()
-            comm.allreduce_sum_into(loop.scal[9:10], loop.scal[1:2])
-            ev[5].record()
-            loop.cphases("C4", "SUMW", it)
-            ev[6].record()
-            comm.allreduce_sum_into(loop.scal[10:11], loop.scal[2:3])
-            ev[7].record()
-            ev[8].record()
-            marks.append(ev)
-        for it in range(it_begin, it_begin + (0 if getattr(self, "compact", False) else iterations)):
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(9)]
-            ev[0].record()
-            if not getattr(self, "ghost_p_mode", False):
-                self.halo["s1"][0].exchange(self.halo["s1"][1])
-            loop.phases("K1", "K1", it)
-            ev[1].record()
-            self.halo["t1"][0].exchange(self.halo["t1"][1])
-            ev[2].record()
-            loop.phases("K2", "K2", it)
-            ev[3].record()
-            if not self.ghost_mode:
-                self.halo["t4"][0].exchange(self.halo["t4"][1])
-            loop.phases("K3", "SUM1", it)
-            ev[4].record()
-            comm.allreduce_sum_into(loop.scal[9:10], loop.scal[1:2])
-            ev[5].record()
-            loop.phases("ALPHA", "SUM2", it)
-            ev[6].record()
-            comm.allreduce_sum_into(loop.scal[10:11], loop.scal[2:3])
-            ev[7].record()
-            loop.phases("BETA", "K5", it)
-            ev[8].record()
+            self._issue(it, lambda segment: ev[segment].record())
+            for e in ev[opened:]:                        # the end of the last segment (and of the ones no step opens)
+                e.record()
             marks.append(ev)
         torch.cuda.synchronize()
         for ev in marks:
@@ -1466,15 +1430,12 @@ def b_in_layout_of_a(A, B, engine):
     """B's slab with its ghost columns numbered in the layout of A's operand (A's ghosts contain B's): the SpMVs
     with A and with B then multiply the SAME halo-extended buffer."""
     n_u, n_p = A.n_cols_owned, B.n_rows
-    gb, ga = B.plan.ghosts, A.plan.ghosts
-    pos = np.searchsorted(ga, gb)
-    if gb.size and (pos.max(initial=0) >= ga.size or not np.array_equal(ga[np.minimum(pos, ga.size - 1)], gb)):
-        raise RuntimeError("ghost columns of B are not among those of A's operand")
+    on_a = A.plan.local_index(B.plan.ghosts, "ghost columns of B are not among those of A's operand")
     loc = B.local_scipy
     cols = loc.indices.astype(np.int64)
     ghost = cols >= n_u
-    cols[ghost] = n_u + pos[cols[ghost] - n_u]
-    b_on_a = sp.csr_matrix((loc.data, cols.astype(np.int32), loc.indptr), shape=(n_p, n_u + ga.size))
+    cols[ghost] = on_a[cols[ghost] - n_u]
+    b_on_a = sp.csr_matrix((loc.data, cols.astype(np.int32), loc.indptr), shape=(n_p, n_u + A.plan.n_ghost))
     b_on_a.sort_indices()
     return SparseMatrix.from_scipy(b_on_a, engine=engine)
 
@@ -1527,18 +1488,14 @@ class Bpcg1DistLoop(fused.FusedLoop, NativeDist):
         local["d"], local["a"], local["t2"] = [self.d0, self.d1], [self.a0, vecs["a"][1]], [self.t20, vecs["t2"][1]]
         self.loop = fused.Bpcg1Loop(eng, A.local, self.B_onA, pa, ps, k, local, BT=BT.local)
         self.loop.state.local_sums = 1
-        if self.TRANSPORT == "mailbox":
-            halos = (A.native_halo(self.d0, (0, 0)), BT.native_halo(self.d1, (0, 0)))
-            self.open_native(halos, channels=[(halos[0], A.n_cols_owned), (halos[1], BT.n_cols_owned)])
-        elif native and getattr(self.comm, "comm", None) is not None:        # RcclComm: an ncclComm_t
-            self.open_native((A.native_halo(self.d0), BT.native_halo(self.d1)), nccl_comm=self.comm.comm)
+        self.open_for(dict(u=(A, self.d0), p=(BT, self.d1)), self.TRANSPORT, native)
 
     def enqueue(self, it_begin, it_end):
         import ctypes as C
         eng, loop, st = self.engine, self.loop, self.loop.state
         if self.native is not None:
-            handle, (hu, hp) = self.native
-            eng._check(eng.lib.nss_bpcg1_iterate_dist(C.byref(st), handle, C.byref(hu), C.byref(hp), int(it_begin),
+            nat = self.native
+            eng._check(eng.lib.nss_bpcg1_iterate_dist(C.byref(st), nat.handle, C.byref(nat.u), C.byref(nat.p), int(it_begin),
                                                       int(it_end), eng.stream))
             return
         A, BT, comm, scal = self.A, self.BT, self.comm, loop.scal
@@ -1620,18 +1577,14 @@ class DistributedMinres(NativeDist):
         self.loop = fused.MinresLoop(eng, ops.A.local, self.B_onA, ops.BT.local, pa, pm, u, v_ring, w_ring, z_ring, kz)
         self.loop.state.local_sums = 1
         self.z_ring = z_ring
-        if transport == "mailbox":        # the native loop over the mailbox transport (csrc/p2p.h), any set-up communicator
-            halos = (ops.A.native_halo(z_ring[0][0], (0, 0)), ops.BT.native_halo(z_ring[0][1], (0, 0)))
-            self.open_native(halos, channels=[(halos[0], ops.n_u), (halos[1], ops.n_p)])
-        elif native and getattr(self.comm, "comm", None) is not None:        # RcclComm: an ncclComm_t
-            self.open_native((ops.A.native_halo(z_ring[0][0]), ops.BT.native_halo(z_ring[0][1])), nccl_comm=self.comm.comm)
+        self.open_for(dict(u=(ops.A, z_ring[0][0]), p=(ops.BT, z_ring[0][1])), transport, native)
 
     def _iterate(self, k_begin, k_end):
         import ctypes as C
         eng, loop, st = self.engine, self.loop, self.loop.state
         if self.native is not None:
-            handle, (h0, h1) = self.native
-            eng._check(eng.lib.nss_minres_iterate_dist(C.byref(st), handle, C.byref(h0), C.byref(h1), int(k_begin),
+            nat = self.native
+            eng._check(eng.lib.nss_minres_iterate_dist(C.byref(st), nat.handle, C.byref(nat.u), C.byref(nat.p), int(k_begin),
                                                        int(k_end), eng.stream))
             return
         ops, comm = self.ops, self.comm

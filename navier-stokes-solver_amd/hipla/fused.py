@@ -496,12 +496,12 @@ class Bpcg2Loop(FusedLoop):
         self.eng._check(self.lib.nss_bpcg2_c1_applies_preA(C.byref(self.state), C.byref(out)))
         return bool(out.value)
 
-    def enqueue_dist(self, dist_handle, halos, overlap, it_begin, it_end):
-        """Row-partitioned iterations issued natively (nss_bpcg2_iterate_dist)."""
+    def enqueue_dist(self, dist_handle, s1, t1, t4, overlap, it_begin, it_end):
+        """Row-partitioned iterations issued natively (nss_bpcg2_iterate_dist); `s1`, `t1`, `t4`: the `HaloStruct` of
+        that operand, or None."""
         ref = lambda h: C.byref(h) if h is not None else None     # (compact plan: only the halo of t1 is used)
-        self.eng._check(self.lib.nss_bpcg2_iterate_dist(C.byref(self.state), dist_handle, ref(halos[0]),
-                                                        ref(halos[1]), ref(halos[2]), int(overlap),
-                                                        int(it_begin), int(it_end), self.eng.stream))
+        self.eng._check(self.lib.nss_bpcg2_iterate_dist(C.byref(self.state), dist_handle, ref(s1), ref(t1), ref(t4),
+                                                        int(overlap), int(it_begin), int(it_end), self.eng.stream))
 
     def poll(self):
         """Drain the stream; returns (done, it_final, last_it)."""

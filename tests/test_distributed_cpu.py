@@ -241,6 +241,39 @@ def test_halo_plan_bookkeeping():
     assert list(even_offsets(10, 3)) == [0, 3, 7, 10]
 
 
+@pytest.mark.parametrize("dim,n", [(2, 10), (3, 6)])
+def test_halo_plan_local_index_matches_a_dictionary(numpy_engine, dim, n):
+    """`HaloPlan.local_index` (global ids -> index in [owned | ghosts]) against a brute-force dictionary, for the three
+    operand layouts of every rank of a 3-way slab partition; an id outside the layout raises with the caller's message."""
+    s = mac_stokes(dim, n, 0.01)
+    with_ghosts = 0
+    for ops in _simulated_ranks(s, 3, numpy_engine):
+        for mat in (ops.A, ops.B, ops.BT):
+            plan = mat.plan
+            c0, c1 = int(plan.col_offsets[plan.rank]), int(plan.col_offsets[plan.rank + 1])
+            where = {g: i for i, g in enumerate(list(range(c0, c1)) + [int(g) for g in plan.ghosts])}
+            assert len(where) == plan.n_owned + plan.n_ghost
+            with_ghosts += plan.n_ghost > 0
+            ids = np.random.default_rng(plan.rank).permutation(np.array(list(where), dtype=np.int64))
+            ids = np.concatenate([ids, ids[:7]])                       # unsorted, with repeats
+            got = plan.local_index(ids, "unused")
+            assert got.shape == ids.shape
+            np.testing.assert_array_equal(got, [where[int(g)] for g in ids])
+            assert plan.local_index(np.zeros(0, dtype=np.int64), "unused").size == 0
+            outside = [g for g in range(int(plan.col_offsets[-1])) if g not in where]
+            assert outside                                             # (3 slabs: nobody sees every id)
+            for bad in (outside[0], outside[-1], outside[len(outside) // 2]):
+                with pytest.raises(RuntimeError, match="not in this layout"):
+                    plan.local_index(np.array([ids[0], bad, ids[1]]), "id %d is not in this layout" % bad)
+    assert with_ghosts >= 6                                            # (A's and B's operand on every rank)
+    # a layout without ghosts: every id that is not owned raises
+    from distributed import HaloPlan
+    alone = HaloPlan(1, 2, 5, [], [0, 5, 10])
+    np.testing.assert_array_equal(alone.local_index([9, 5], "unused"), [4, 0])
+    with pytest.raises(RuntimeError, match="nobody's ghost"):
+        alone.local_index([4], "nobody's ghost")
+
+
 def test_halo_plans_of_slab_partitions_send_contiguous_runs(numpy_engine):
     """Slab neighbours want (most of) one or two grid planes: after `densify_ghosts` every
     destination is served by ONE contiguous run of the owned entries, so the native loop sends

@@ -369,7 +369,7 @@ def test_native_partitioned_loop_split_and_streams_single_rank(hip_engine, tmp_p
                 run.enable_native(comm.comm, interior)
             else:
                 nb = run.ops.A.local.handle.info()["row_blocks"]
-                assert run.native[1][1].int_begin == 0 and run.native[1][1].int_end == nb      # no ghosts: all interior
+                assert run.native.t1.int_begin == 0 and run.native.t1.int_end == nb      # no ghosts: all interior
             run.overlap = overlap
             it, conv = run.solve(tol=tol, maxsteps=maxsteps, poll_every=16)
             assert conv and it == ref["it"]

@@ -23,7 +23,7 @@ import torch
 import torch.distributed as dist
 
 import hipla
-from distributed import DistributedBpcg2
+from distributed import DistributedBpcg2, NativeHandle
 from rccl_comm import RcclComm
 from staggered_grid import mac_stokes
 
@@ -98,8 +98,8 @@ class SlabRun(DistributedBpcg2):
         eng = self.engine
         eng._check(eng.lib.nss_dist_create(comm_handle, 1, 0, C.byref(handle)))
         ops = self.ops
-        halos = (ops.BT.native_halo(self.s1), ops.A.native_halo(self.t1), ops.B.native_halo(self.t4))
-        self.native = (handle, halos)
+        self.native = self.own(NativeHandle(handle, eng.lib.nss_dist_destroy, s1=ops.BT.native_halo(self.s1),
+                                            t1=ops.A.native_halo(self.t1), t4=ops.B.native_halo(self.t4)))
 
 
 def show(label, us, phases=None):
