@@ -341,6 +341,9 @@ __global__ __launch_bounds__(kBlock) void bpcg1_v6_kernel(const int32_t* __restr
 
 static int p_grid(const nss_bpcg1_t& s) { return stream_grid(int64_t(s.n_u) + s.n_p, kBlock * 4); }
 
+static PreA pre_a_of(const nss_bpcg1_t& s) {
+  return PreA{.n = s.n_u, .ncols = s.n_u, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A};
+}
 static void bpcg1_check(const nss_bpcg1_t* s) {
   NSS_REQUIRE(s != nullptr, "bpcg1: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "bpcg1: NULL matrix handle");
@@ -350,11 +353,7 @@ static void bpcg1_check(const nss_bpcg1_t* s) {
   else
     NSS_REQUIRE(s->A->n == s->n_u && s->B->n == s->n_u && s->BT->n == s->n_p, "bpcg1: matrix columns do not match");
   NSS_REQUIRE(!(s->local_sums && s->pre_amg), "bpcg1: the row-partitioned loop takes a (block) Jacobi preconditioner");
-  NSS_REQUIRE(!(s->pre_diag && s->pre_bjac), "bpcg1: pre_diag and pre_bjac are exclusive");
-  NSS_REQUIRE(s->pre_diag || s->pre_bjac || s->pre_amg, "bpcg1: no preconditioner for the velocity block");
-  NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels[0].n == s->n_u, "bpcg1: AMG size mismatch");
-  NSS_REQUIRE(!(s->pre_amg && s->pre_bjac && s->pre_bjac->gs_mat), "bpcg1: AMG + Gauss-Seidel mode is not additive");
-  NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n_u, "bpcg1: block-Jacobi size mismatch");
+  pre_a_check(pre_a_of(*s), "bpcg1", kPreAAdditiveOnly);
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "bpcg1: NULL work buffer");
   for (int c = 0; c < 2; ++c)
@@ -441,16 +440,8 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
     }
     launch_csr_stream(*s.BT, s.d[1], EpiV1b{s.ctrl, s.t1[0], s.t2[0], s.pre_amg ? nullptr : s.pre_diag, s.k}, st);
     }
-    if (s.pre_amg) {                                         // t2 = -k (AMG + J) t1 (t1 holds -K u here)
-      amg_apply(*s.pre_amg, -s.k, s.t1[0], s.t2[0], st);
-      if (s.pre_bjac) bjac_apply(*s.pre_bjac, -s.k, s.t1[0], 1.0, s.t2[0], s.ctrl, st);
-      if (s.pre_diag) {
-        const int rc = nss_diag_apply_f64(s.n_u, s.pre_diag, -s.k, s.t1[0], 1.0, s.t2[0], st);
-        if (rc != 0) throw Error(nss_last_error());
-      }
-    } else if (s.pre_bjac && !fused_j) {
-      bjac_apply(*s.pre_bjac, -s.k, s.t1[0], 0.0, s.t2[0], s.ctrl, st);
-    }
+    // t2 = -k preA t1 (t1 holds -K u here) where no epilogue above has formed it (point / fused block Jacobi alone)
+    if (s.pre_amg || (s.pre_bjac && !fused_j)) pre_a_apply(pre_a_of(s), -s.k, s.t1[0], s.t2[0], nullptr, s.ctrl, st);
   }
   if (on(2)) {
     if (dist) exchange(*dist->d, halo_of(dist->hu, s.t2[0]), st);

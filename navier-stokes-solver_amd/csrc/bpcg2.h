@@ -1,16 +1,10 @@
 #pragma once
 
-#include "amg.h"
-#include "precond.h"
+#include "pre_a.h"
 
 struct nss_dist_s;
 
 namespace nss {
-inline void bjac_apply_guarded(const nss_bjac_s& j, double k, const double* x, double* y, const int32_t* done,
-                               hipStream_t st) {
-  bjac_apply(j, k, x, 0.0, y, done, st);   // additive block Jacobi, or the symmetric GS sweep
-}
-
 // pieces of the fused BPCG iteration shared with the row-partitioned loop (dist.hip)
 void bpcg2_check_state(const nss_bpcg2_t* s);
 void bpcg2_phase(const nss_bpcg2_t& s, int which, int it, hipStream_t st);

@@ -8,7 +8,7 @@
 //   K1  rows of B^T :  [it>0] z0 -= a*t2 (:238, deferred), q = b*q + z0_old - a*t2 (:205),
 //                      s0 = b*s0 + w0 (:240-241, velocity part, deferred)
 //                      t0 = q + B^T s1 (:206-207);  Jacobi preA: t1 = k*dinv*t0 (:209)
-//   [J] block-Jacobi preA: t1 = k * J t0 (:209)
+//   [J] every other preA (block Jacobi, sweeps, V-cycle, MypreA): t1 = k * preA t0 (:209; pre_a_apply, pre_a.hip)
 //   K2  rows of A   :  t2 = A t1 (:210), t4 = t1 - s0 (:212), partial <s0, t2 - t0> (:218,222)
 //   K3  rows of B   :  t3 = B t4 (:213), partial <s1, t3> (:219,222)
 //   R1               :  as_s = sum of the partials (one workgroup, fixed order)
@@ -134,26 +134,6 @@ struct EpiK2 {
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < ghost_n; i += stride) ghost_t4[i] = t1[ghost_map[i]] - ghost_s0[i];
   }
 };
-
-// r = scale * x - A y  (multiplicative MypreA: residual between the two sweeps, :379)
-struct EpiScaledResidual {
-  const int32_t* __restrict__ ctrl;
-  double scale;
-  const double* __restrict__ x;
-  double* __restrict__ r;
-  __device__ bool skip() const { return ctrl[C_DONE] != 0; }
-  struct Pre { double x = 0.0; };
-  __device__ Pre fetch(int i) const { return Pre{x[i]}; }
-  __device__ void row(int i, double ay, const Pre& p) const { r[i] = fma(scale, p.x, -ay); }
-  __device__ void finish(int, double*) const {}
-};
-
-__global__ __launch_bounds__(kBlock) void bpcg2_zero_kernel(const int32_t* __restrict__ ctrl, int32_t n,
-                                                             double* __restrict__ y) {
-  if (ctrl[C_DONE] != 0) return;
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) y[i] = 0.0;
-}
 
 // condensed form: f = t0 + H^T t0
 struct EpiLift {
@@ -821,6 +801,13 @@ static void bpcg2_check_plan(const nss_bpcg2_t& s) {
   check_plan("bpcg2", plan_stamp({s.A, s.B, s.BT}), s.plan_gen, need, cap, 3);
 }
 
+// (on slabs the residual between the sweeps reads ghosts of t1, unless formed with S's slab diagonal block: sweep_A)
+static PreA pre_a_of(const nss_bpcg2_t& s) {
+  return PreA{.n = s.n_u, .ncols = s.dist_compact ? s.A->n : s.n_u, .diag = s.pre_diag, .bjac = s.pre_bjac,
+              .amg = s.pre_amg, .A = s.A, .sweep_A = s.sweep_A, .dist_amg = s.pre_dist_amg, .dist_aux = s.pre_dist_aux,
+              .exchange_y = s.pre_dist_aux && !(s.cond_HT && s.sweep_A)};
+}
+
 void bpcg2_check_state(const nss_bpcg2_t* s) {
   NSS_REQUIRE(s != nullptr, "bpcg2: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "bpcg2: NULL matrix handle");
@@ -843,37 +830,25 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
   } else {
     NSS_REQUIRE(s->B->m == s->n_p, "bpcg2: matrix row counts do not match n_p");
   }
-  NSS_REQUIRE(!(s->pre_diag && s->pre_bjac), "bpcg2: pre_diag and pre_bjac are exclusive");
-  NSS_REQUIRE(s->pre_diag || s->pre_bjac || s->pre_amg || s->pre_dist_amg || s->pre_dist_aux, "bpcg2: no preconditioner for the velocity block");
-  NSS_REQUIRE(!s->pre_dist_aux || (!s->pre_amg && !s->pre_dist_amg && s->pre_dist_aux->n_u == s->n_u),
-              "bpcg2: the row-partitioned auxiliary-space term replaces pre_amg / pre_dist_amg and must match n_u");
-  NSS_REQUIRE(!s->pre_dist_aux || !s->cond_HT || (s->pre_bjac && s->pre_bjac->gs_mat && s->sweep_A && s->dist_compact),
+  const PreA p = pre_a_of(*s);
+  pre_a_check(p, "bpcg2", kPreAMultiplicative | kPreASlabTerms);
+  // what ties the term to the loop's plan.  The multiplicative MypreA takes the condensed form only when its residual is
+  // formed with the matrix of the sweeps (sweep_A = the Schur complement), not with the loop's explicit product.
+  NSS_REQUIRE(!s->pre_dist_aux || !s->cond_HT || (p.multiplicative() && s->sweep_A && s->dist_compact),
               "bpcg2: the row-partitioned auxiliary-space term takes a condensed form only in the multiplicative MypreA "
               "over the slab rows of S (sweep_A) on the compact plan");
-  NSS_REQUIRE(!s->pre_dist_aux || !(s->pre_bjac && s->pre_bjac->gs_mat) ||
+  NSS_REQUIRE(!(s->pre_dist_aux && p.multiplicative()) ||
                   (s->pre_dist_aux->has_halo_y && s->pre_dist_aux->halo_y.ext == s->t1),
               "bpcg2: the multiplicative partitioned MypreA needs the halo of t1 (nss_dist_aux_create: halo_y)");
-  NSS_REQUIRE(!s->pre_dist_amg || (!s->pre_amg && !s->cond_HT && s->pre_dist_amg->n == s->n_u),
-              "bpcg2: the row-partitioned AMG replaces pre_amg, takes no condensed form, and must match n_u");
-  NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels[0].n == s->n_u, "bpcg2: AMG size mismatch");
-  // AMG (or auxiliary-space) term + a block-Jacobi handle in Gauss-Seidel mode = the MULTIPLICATIVE MypreA
-  // (GS=True, :376-381): sweep, residual, correction, back sweep.  With the condensed form only when its residual is
-  // formed with the matrix of the sweeps (sweep_A = the Schur complement), not with the loop's explicit product.
-  const bool multiplicative = s->pre_amg && s->pre_bjac && s->pre_bjac->gs_mat;
-  NSS_REQUIRE(!(multiplicative && ((s->cond_HT && !s->sweep_A) || s->pre_diag)),
-              "bpcg2: the multiplicative preconditioner (Gauss-Seidel sweeps around an AMG term) takes no point-Jacobi "
-              "part, and a condensed form only with sweep_A (the matrix of its sweeps)");
-  const bool slab_multiplicative = s->pre_dist_aux && s->pre_bjac && s->pre_bjac->gs_mat;
-  NSS_REQUIRE(!s->sweep_A || (multiplicative && !s->pre_dist_aux && !s->pre_dist_amg && !s->dist_compact &&
-                              !s->local_sums && !s->ghost_mode) ||
-                  (slab_multiplicative && s->cond_HT && s->dist_compact && !s->pre_amg && !s->pre_dist_amg),
+  NSS_REQUIRE(!s->pre_dist_amg || !s->cond_HT, "bpcg2: the row-partitioned AMG takes no condensed form");
+  NSS_REQUIRE(!(s->pre_amg && p.multiplicative() && s->cond_HT && !s->sweep_A),
+              "bpcg2: the multiplicative MypreA takes a condensed form only with sweep_A (the matrix of its sweeps)");
+  NSS_REQUIRE(!s->sweep_A || (s->pre_amg && !s->dist_compact && !s->local_sums && !s->ghost_mode) ||
+                  (s->pre_dist_aux && s->cond_HT && s->dist_compact),
               "bpcg2: sweep_A serves the multiplicative preconditioner on one GPU, or on slabs the condensed one on the "
               "compact plan");
-  NSS_REQUIRE(!s->sweep_A || (s->sweep_A->m == s->n_u && s->sweep_A->n == (s->dist_compact ? s->A->n : s->n_u)),
-              "bpcg2: sweep_A must have the rows and the operand layout of A");
   NSS_REQUIRE(!s->cond_HT || !s->local_sums || s->dist_compact,
               "bpcg2: a condensed form on slabs runs on the compact partitioned plan only");
-  NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n_u, "bpcg2: block-Jacobi size mismatch");
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "bpcg2: NULL work buffer");
   NSS_REQUIRE(!s->ghost_mode || s->ghost_n == 0 || ((s->ghost_map || s->dist_compact) && s->ghost_s0 && s->ghost_w0),
@@ -924,20 +899,6 @@ void bpcg2_spmv_phase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, i
     default:
       throw Error("bpcg2: not an SpMV phase");
   }
-}
-
-// t1 = k * preA_unscaled t0 for everything that is not fused into K1's epilogue:
-// [AMG V-cycle] + [block Jacobi / block Gauss-Seidel | point Jacobi]  (additive MypreA, :383)
-// t1 = 0; J.Smooth(t1, k src)  (:377-378).  Colour-major layout: t1 is not zeroed and gathered -- the sweep starts from
-// zeros of its own and its first colour needs no pass over A (precond.h: kGsFromZero)
-static void gs_forward_from_zero(const nss_bpcg2_t& s, const double* src, hipStream_t st) {
-  if (s.pre_bjac->gs_permuted) {
-    bjac_smooth(*s.pre_bjac, s.k, src, s.t1, false, s.ctrl, st, kGsFromZero);
-    return;
-  }
-  hipLaunchKernelGGL(bpcg2_zero_kernel, dim3((s.n_u + kBlock - 1) / kBlock), dim3(kBlock), 0, st, s.ctrl, s.n_u, s.t1);
-  NSS_CHECK_LAUNCH();
-  bjac_smooth(*s.pre_bjac, s.k, src, s.t1, false, s.ctrl, st);
 }
 
 // Which form of the condensed multiplicative preconditioner step K1 runs (nss_cond_fuse_mode, NSS_COND_FUSE):
@@ -999,46 +960,10 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st, const nss_dist_s* d) 
     launch_csr_stream(*s.cond_HT, s.t0, EpiLift{s.ctrl, s.t0, s.cond_f}, st);
     src = s.cond_f;
   }
-  auto diag = [&](double beta) { diag_apply(s.n_u, s.pre_diag, s.k, src, beta, s.t1, s.ctrl, st); };
-  if (s.pre_dist_aux && s.pre_bjac && s.pre_bjac->gs_mat) {
-    // multiplicative MypreA on slabs (GS=True, :376-381): the sweeps run inside the slab (additive across slabs), the
-    // residual between them with the partitioned A (halo exchange of the iterate), the auxiliary-space term on slabs
-    //   (condensed form: with S's slab diagonal block, sweep_A -- the matrix of the sweeps, which keeps the preconditioner
-    //   symmetric; it reads owned entries only, so the iterate is not exchanged)
-    const nss_dist_aux_s& aux = *s.pre_dist_aux;
-    gs_forward_from_zero(s, src, st);
-    if (!(s.cond_HT && s.sweep_A)) exchange_on(*aux.d, aux.ch_y, aux.halo_y, s.ctrl, st);
-    launch_csr_stream(s.sweep_A ? *s.sweep_A : *s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
-    dist_aux_apply(aux, 1.0, s.t2, s.t1, true, st, s.ctrl);
-    bjac_smooth(*s.pre_bjac, s.k, src, s.t1, true, s.ctrl, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);   // (src again)
-  } else if (s.pre_dist_aux) {                        // additive MypreA on slabs (:383)
-    dist_aux_apply(*s.pre_dist_aux, s.k, src, s.t1, false, st, s.ctrl);
-    if (s.pre_bjac) bjac_apply(*s.pre_bjac, s.k, src, 1.0, s.t1, s.ctrl, st);
-    if (s.pre_diag) diag(1.0);
-  } else if (s.pre_dist_amg) {                              // row-partitioned V-cycle (+ additive Jacobi part)
-    dist_amg_apply(*s.pre_dist_amg, s.k, src, s.t1, st, s.ctrl);
-    if (s.pre_bjac) bjac_apply(*s.pre_bjac, s.k, src, 1.0, s.t1, s.ctrl, st);
-    if (s.pre_diag) diag(1.0);
-  } else if (s.pre_amg && s.pre_bjac && s.pre_bjac->gs_mat) {
-    // multiplicative MypreA (GS=True, :376-381) applied to k * t0:
-    //   y = 0; J.Smooth(y, x); r = x - A y; y += M r; J.SmoothBack(y, x)        (t2 is free here: the
-    //   previous iteration's t2 was consumed by K1 / C1 and the A-SpMV has not written the new one yet)
-    //   (condensed form: src = the lifted t0, the residual with the matrix of the sweeps, S = sweep_A)
-    gs_forward_from_zero(s, src, st);
-    //   (fp32 storage: sweep_A = the handle's fp32 copy of the matrix of its sweeps -- the residual with the rounded
-    //   matrix keeps the operator symmetric)
-    launch_csr_stream_any(s.sweep_A ? *s.sweep_A : *s.A, s.t1, EpiScaledResidual{s.ctrl, s.k, src, s.t2}, st);
-    amg_apply(*s.pre_amg, 1.0, s.t2, s.t1, st, s.ctrl, true);
-    bjac_smooth(*s.pre_bjac, s.k, src, s.t1, true, s.ctrl, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);   // (src again)
-  } else if (s.pre_amg) {
-    amg_apply(*s.pre_amg, s.k, src, s.t1, st, s.ctrl);
-    if (s.pre_bjac) bjac_apply(*s.pre_bjac, s.k, src, 1.0, s.t1, s.ctrl, st);
-    if (s.pre_diag) diag(1.0);
-  } else if (s.pre_bjac) {
-    bjac_apply_guarded(*s.pre_bjac, s.k, src, s.t1, s.ctrl, st);
-  } else if (s.cond_HT) {
-    diag(0.0);                                       // uncondensed: rides in K1's epilogue
-  }
+  // t1 = k * preA src unless K1's epilogue has formed it (uncondensed, point Jacobi alone).  t2 is free here: the
+  // previous iteration's t2 was consumed by K1 / C1 and the A-SpMV has not written the new one yet
+  const PreA p = pre_a_of(s);
+  if (p.term() || p.bjac || s.cond_HT) pre_a_apply(p, s.k, src, s.t1, s.t2, s.ctrl, st);
   if (s.cond_HT) {
     if (cond_slab) cond_exchange(s, *d, d->cond_ext, 2, st);
     launch_csr_stream(*s.cond_H, s.t1, EpiExtendInPlace{s.ctrl, s.t1}, st);         // t1 += H t1

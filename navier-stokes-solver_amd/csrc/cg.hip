@@ -123,13 +123,13 @@ __global__ __launch_bounds__(kBlock) void cg_direction_kernel(CgArgs a) {
 
 static int cg_grid(const nss_cg_t& s) { return stream_grid(s.n, kBlock * 4); }
 
+static PreA pre_a_of(const nss_cg_t& s) {
+  return PreA{.n = s.n, .ncols = s.n, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A};
+}
 static void cg_check(const nss_cg_t* s) {
   NSS_REQUIRE(s != nullptr && s->A != nullptr, "cg: NULL state / matrix");
   NSS_REQUIRE(s->A->m == s->n && s->A->n == s->n, "cg: matrix does not match n");
-  NSS_REQUIRE(int(s->pre_diag != nullptr) + int(s->pre_bjac != nullptr) + int(s->pre_amg != nullptr) <= 1,
-              "cg: at most one preconditioner");
-  NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n, "cg: block preconditioner size mismatch");
-  NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels[0].n == s->n, "cg: AMG size mismatch");
+  pre_a_check(pre_a_of(*s), "cg", kPreAOnePartAtMost);
   NSS_REQUIRE(s->x && s->r && s->z && s->p && s->q && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b,
               "cg: NULL buffer");
   const int64_t need[2] = {s->A->nblk, std::max<int64_t>(cg_grid(*s), s->pre_bjac ? bjac_dot_grid(*s->pre_bjac) : 0)};
@@ -150,8 +150,7 @@ static void cg_iteration(const nss_cg_t& s, int it, hipStream_t st) {
     if (s.pre_bjac && !s.pre_bjac->gs_mat) {   // block Jacobi: <r, z> comes out of the apply kernel
       nb = bjac_apply_dot(*s.pre_bjac, 1.0, s.r, s.z, s.partials_b, s.ctrl, st);
     } else {
-      if (s.pre_bjac) bjac_apply(*s.pre_bjac, 1.0, s.r, 0.0, s.z, s.ctrl, st);
-      else amg_apply(*s.pre_amg, 1.0, s.r, s.z, st);
+      pre_a_apply(pre_a_of(s), 1.0, s.r, s.z, nullptr, s.ctrl, st);   // Gauss-Seidel sweep as an operator, or V-cycle
       hipLaunchKernelGGL(cg_dot_kernel, dim3(nb), dim3(kBlock), 0, st, s.ctrl, s.n, s.r, s.z, s.partials_b);
       NSS_CHECK_LAUNCH();
     }

@@ -13,8 +13,8 @@
 //   L3  element-wise : delta_j = dh / gamma_j^2 (lane 0 records it);
 //                      rh_{j+1} = ph / gamma_j - (delta_j / gamma_j) rh_j - (gamma_j / gamma_{j-1}) rh_{j-1}
 //                      [point Jacobi: zh_{j+1} = dinv rh_{j+1}, partial <zh_{j+1}, rh_{j+1}>]
-//   L4  preconditioner (block Jacobi with the dot in the same kernel / Gauss-Seidel / V-cycle / their additive or
-//                      multiplicative combination) + partial <zh_{j+1}, rh_{j+1}>
+//   L4  preconditioner (block Jacobi with the dot in the same kernel; else pre_a_apply, pre_a.hip: Gauss-Seidel /
+//                      V-cycle / their additive or multiplicative combination) + partial <zh_{j+1}, rh_{j+1}>
 //   L5  one workgroup: g2 = sum; gamma_{j+1} = sqrt|g2| recorded; breakdown test (gamma_{j+1} <= 1e-14 max(|delta_0|,
 //                      |delta_j|)) sets the stop flag, after which every kernel returns at once.
 // Small systems (both sums <= 1024 partials, block Jacobi over runs of consecutive dofs) run a step in TWO launches
@@ -149,18 +149,6 @@ __global__ __launch_bounds__(kBlock) void lanczos_dot_kernel(const int32_t* __re
   const double s = block_sum(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
-
-// r = x - A y (multiplicative MypreA: the residual between the two sweeps, :379)
-struct EpiLzResidual {
-  const int32_t* __restrict__ ctrl;
-  const double* __restrict__ x;
-  double* __restrict__ r;
-  __device__ bool skip() const { return ctrl[LC_STOP] != 0; }
-  struct Pre { double x = 0.0; };
-  __device__ Pre fetch(int i) const { return Pre{x[i]}; }
-  __device__ void row(int i, double ay, const Pre& pre) const { r[i] = pre.x - ay; }
-  __device__ void finish(int, double*) const {}
-};
 
 __global__ __launch_bounds__(kBlock) void lanczos_scale_kernel(const int32_t* __restrict__ ctrl, int32_t n, double a,
                                                                 double* __restrict__ x) {
@@ -330,16 +318,14 @@ static bool lz_fold_a(const nss_lanczos_t& s) { return g_lanczos_fold_mode == 1 
 
 static int64_t lz_partials_b(const nss_lanczos_t& s);
 
+static PreA pre_a_of(const nss_lanczos_t& s) {
+  return PreA{.n = s.n, .ncols = s.n, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A,
+              .sweep_A = s.sweep_A};
+}
 static void lz_check(const nss_lanczos_t* s) {
   NSS_REQUIRE(s != nullptr && s->A != nullptr, "lanczos: NULL state / matrix");
   NSS_REQUIRE(s->A->m == s->n && s->A->n == s->n, "lanczos: matrix does not match n");
-  NSS_REQUIRE(!(s->pre_diag && s->pre_bjac), "lanczos: pre_diag and pre_bjac are exclusive");
-  NSS_REQUIRE(s->pre_diag || s->pre_bjac || s->pre_amg, "lanczos: no preconditioner");
-  NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n, "lanczos: block preconditioner size mismatch");
-  NSS_REQUIRE(!s->sweep_A || (s->pre_amg && s->pre_bjac && s->pre_bjac->gs_mat),
-              "lanczos: sweep_A serves the multiplicative preconditioner only");
-  NSS_REQUIRE(!s->sweep_A || (s->sweep_A->m == s->n && s->sweep_A->n == s->n), "lanczos: sweep_A must be n x n");
-  NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels.empty() || s->pre_amg->levels[0].n == s->n || s->pre_amg->T, "lanczos: AMG size mismatch");
+  pre_a_check(pre_a_of(*s), "lanczos", kPreAMultiplicative);
   for (int i = 0; i < 3; ++i) NSS_REQUIRE(s->v[i] != nullptr, "lanczos: NULL vector");
   NSS_REQUIRE(s->z[0] && s->z[1] && s->p && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b,
               "lanczos: NULL buffer");
@@ -352,30 +338,15 @@ static void lz_check(const nss_lanczos_t* s) {
 // partials_b and returns their count.  `scratch` (n doubles) is free for the multiplicative form.
 static int lz_precondition(const nss_lanczos_t& s, const double* x, double* z, double* scratch, hipStream_t st) {
   const int32_t* done = s.ctrl;
-  const bool multiplicative = s.pre_amg && s.pre_bjac && s.pre_bjac->gs_mat;
-  if (!s.pre_amg && s.pre_bjac && !s.pre_bjac->gs_mat)          // block Jacobi: the dot comes out of the apply kernel
-    return bjac_apply_dot(*s.pre_bjac, s.pre_scale, x, z, s.partials_b, done, st);
-  if (multiplicative) {
-    // MypreA with GS=True (templates/NavierStokesSIMPLE_iterative.py:376-381): y = 0; Smooth; r = x - A y; y += M r; SmoothBack
-    if (s.pre_bjac->gs_permuted) {
-      bjac_smooth(*s.pre_bjac, 1.0, x, z, false, done, st, kGsFromZero);
-    } else {
-      NSS_HIP(hipMemsetAsync(z, 0, sizeof(double) * size_t(s.n), st));
-      bjac_smooth(*s.pre_bjac, 1.0, x, z, false, done, st);
-    }
-    launch_csr_stream_any(s.sweep_A ? *s.sweep_A : *s.A, z, EpiLzResidual{done, x, scratch}, st);
-    amg_apply(*s.pre_amg, 1.0, scratch, z, st, done, true);
-    bjac_smooth(*s.pre_bjac, 1.0, x, z, true, done, st, s.pre_bjac->gs_permuted ? kGsKeepX : 0);
-    if (s.pre_scale != 1.0) {
-      hipLaunchKernelGGL(lanczos_scale_kernel, dim3(lz_grid(s)), dim3(kBlock), 0, st, done, s.n, s.pre_scale, z);
-      NSS_CHECK_LAUNCH();
-    }
-  } else if (s.pre_amg) {                                       // V-cycle [+ Jacobi part]: the additive MypreA (:383)
-    amg_apply(*s.pre_amg, s.pre_scale, x, z, st, done);
-    if (s.pre_bjac) bjac_apply(*s.pre_bjac, s.pre_scale, x, 1.0, z, done, st);
-    if (s.pre_diag) diag_apply(s.n, s.pre_diag, s.pre_scale, x, 1.0, z, done, st);
-  } else {                                                      // symmetric Gauss-Seidel sweep as an operator
-    bjac_apply(*s.pre_bjac, s.pre_scale, x, 0.0, z, done, st);
+  const PreA p = pre_a_of(s);
+  if (!p.term() && p.bjac && !p.bjac->gs_mat)                   // block Jacobi: the dot comes out of the apply kernel
+    return bjac_apply_dot(*p.bjac, s.pre_scale, x, z, s.partials_b, done, st);
+  // the multiplicative MypreA is applied unscaled and its result scaled: the order the recorded Ritz values were made in
+  const bool scale_after = p.multiplicative();
+  pre_a_apply(p, scale_after ? 1.0 : s.pre_scale, x, z, scratch, done, st);
+  if (scale_after && s.pre_scale != 1.0) {
+    hipLaunchKernelGGL(lanczos_scale_kernel, dim3(lz_grid(s)), dim3(kBlock), 0, st, done, s.n, s.pre_scale, z);
+    NSS_CHECK_LAUNCH();
   }
   const int nb = lz_grid(s);
   hipLaunchKernelGGL(lanczos_dot_kernel, dim3(nb), dim3(kBlock), 0, st, done, s.n, z, x, s.partials_b);

@@ -475,6 +475,9 @@ static void minres_need(const nss_minres_t& s, int64_t* need) {
   need[2] = std::max<int64_t>(gu_fused, m_gu(s)) + m_gp(s);
 }
 
+static PreA pre_a_of(const nss_minres_t& s) {
+  return PreA{.n = s.n_u, .ncols = s.n_u, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A};
+}
 static void minres_check(const nss_minres_t* s) {
   NSS_REQUIRE(s != nullptr, "minres: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "minres: NULL matrix handle");
@@ -483,11 +486,7 @@ static void minres_check(const nss_minres_t* s) {
     NSS_REQUIRE(s->A->n >= s->n_u && s->B->n >= s->n_u && s->BT->n >= s->n_p, "minres: local matrix narrower than the slab");
   else
     NSS_REQUIRE(s->A->n == s->n_u && s->B->n == s->n_u && s->BT->n == s->n_p, "minres: matrix columns do not match n_u/n_p");
-  NSS_REQUIRE(!(s->pre_diag && s->pre_bjac), "minres: pre_diag and pre_bjac are exclusive");
-  NSS_REQUIRE(s->pre_diag || s->pre_bjac || s->pre_amg, "minres: no preconditioner for the velocity block");
-  NSS_REQUIRE(!s->pre_amg || s->pre_amg->levels[0].n == s->n_u, "minres: AMG size mismatch");
-  NSS_REQUIRE(!(s->pre_amg && s->pre_bjac && s->pre_bjac->gs_mat), "minres: AMG + Gauss-Seidel mode is not additive");
-  NSS_REQUIRE(!s->pre_bjac || s->pre_bjac->n == s->n_u, "minres: block-Jacobi size mismatch");
+  pre_a_check(pre_a_of(*s), "minres", kPreAAdditiveOnly);
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "minres: NULL work buffer");
   for (int c = 0; c < 2; ++c) {
@@ -581,22 +580,15 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
   NSS_CHECK_LAUNCH();
   }
   if (!fused && (s.pre_bjac || s.pre_amg)) {
-    const bool dot_in_apply = !s.pre_amg && !s.pre_bjac->gs_mat;
+    const bool dot_in_apply = !s.pre_amg && !s.pre_bjac->gs_mat;   // block Jacobi: <z_new, v_new> out of the apply kernel
     if (!on(3)) {                   // phases 4 / 5 issued on their own: the partial count of phase 3
       nb2 = dot_in_apply ? bjac_dot_grid(*s.pre_bjac) : m_dot_grid(s);
     } else
     // z_new[0] = preA v_new[0] outside the element-wise kernel; after the stop these launches only
     // touch ring slots nobody reads any more
     {
-    if (s.pre_amg) {
-      amg_apply(*s.pre_amg, 1.0, s.v[in][0], s.z[zn][0], st);
-      if (s.pre_bjac) bjac_apply(*s.pre_bjac, 1.0, s.v[in][0], 1.0, s.z[zn][0], nullptr, st);
-      if (s.pre_diag) diag_apply(s.n_u, s.pre_diag, 1.0, s.v[in][0], 1.0, s.z[zn][0], nullptr, st);
-    } else if (s.pre_bjac->gs_mat) {
-      bjac_apply(*s.pre_bjac, 1.0, s.v[in][0], 0.0, s.z[zn][0], nullptr, st);
-    } else {                          // block Jacobi: <z_new, v_new> comes out of the apply kernel
-      nb2 = bjac_apply_dot(*s.pre_bjac, 1.0, s.v[in][0], s.z[zn][0], s.partials_a, nullptr, st);
-    }
+    if (dot_in_apply) nb2 = bjac_apply_dot(*s.pre_bjac, 1.0, s.v[in][0], s.z[zn][0], s.partials_a, nullptr, st);
+    else pre_a_apply(pre_a_of(s), 1.0, s.v[in][0], s.z[zn][0], nullptr, nullptr, st);
     if (nb2 == 0) {
       nb2 = m_dot_grid(s);
       hipLaunchKernelGGL(minres_dot_kernel, dim3(nb2), dim3(kBlock), 0, st, s.ctrl, k, s.n_u, s.z[zn][0], s.v[in][0],
