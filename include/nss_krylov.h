@@ -661,6 +661,41 @@ NSS_API int nss_cg_workspace(const nss_cg_t* s, int64_t* partials_a, int64_t* pa
 NSS_API int nss_cg_iterate(const nss_cg_t* s, int32_t it_begin, int32_t it_end, nss_stream_t stream);
 NSS_API int nss_cg_poll(const nss_cg_t* s, int32_t* done, int32_t* it_final, int32_t* last_it,
                         nss_stream_t stream);
+/* The start of a solve from x = 0 without the host: x = 0, r = b, z = pre r, p = z, scal = { <r,z>, 0, 0, err0, tol },
+ * ctrl = { 0, -1, -1 }; a zero right-hand side sets done at once (it_final stays -1: no iterations).  hist must hold
+ * as many entries as iterations will be enqueued.  No synchronisation, no allocation. */
+NSS_API int nss_cg_start(const nss_cg_t* s, const double* b, double tol, nss_stream_t stream);
+
+/* ---- device-resident IMEX time step ------------------------------------------------------------
+ * The kernels of `NavierStokes.Advance` around the two inner CG solves (DoTimeStep / Project of the reference,
+ * templates/NavierStokesSIMPLE_iterative.py:424-443).  All fp64, deterministic (no atomics); `done` (device int32,
+ * may be NULL): every launch returns at once when it is non-zero.
+ *
+ * nss_step_flux_f64: flux[i] = adv_i avg_i - |adv_i| diff_i / 2 with adv = I_adv u, avg = Avg u, diff = Diff u, one
+ *   lane per flux point over the two-slot copies of the three matrices (built on the first call: set-up); fails when
+ *   a row of one of them holds more than two entries.  `flux` is meant to be the tail of one buffer [u | F].
+ * nss_step_rhs_f64: temp = f - AD uf for one CSR matrix AD = [A | D] and the operand uf = [u | F]
+ *   ( = conv(u) + f - A u with conv(u) = -D F ).
+ * nss_step_project_f64: out = raw - C phi (C = M_u^-1 B^T: two entries per row; out may be raw);  with u != NULL
+ *   u += tau out;  with partials != NULL (cap entries, >= the row blocks of C: nss_step_workspace) the row-block
+ *   partials of sum_r mass_r e_r^2, e = the updated u (u != NULL) or out, mass_r = 1 when mass is NULL.
+ * nss_step_divergence_f64: partials of |B u|^2 (cap entries); rows summed in CSR order with unfused products, i.e.
+ *   with the bits of a host CSR product.
+ * nss_step_record_f64: record[2 slot] = scale * sum(partials_energy), record[2 slot + 1] = sqrt(sum(partials_div))
+ *   (NaN when partials_div is NULL), summed by the fixed tree of the Krylov loops. */
+NSS_API int nss_step_flux_f64(nss_csr_t adv, nss_csr_t avg, nss_csr_t diff, const double* u, double* flux,
+                              const int32_t* done, nss_stream_t stream);
+NSS_API int nss_step_rhs_f64(nss_csr_t ad, const double* uf, const double* f, double* temp, const int32_t* done,
+                             nss_stream_t stream);
+NSS_API int nss_step_project_f64(nss_csr_t c, const double* phi, const double* raw, double* out, double* u, double tau,
+                                 const double* mass, double* partials, int64_t cap, const int32_t* done,
+                                 nss_stream_t stream);
+NSS_API int nss_step_divergence_f64(nss_csr_t b, const double* u, double* partials, int64_t cap, const int32_t* done,
+                                    nss_stream_t stream);
+NSS_API int nss_step_workspace(nss_csr_t c, nss_csr_t b, int64_t* partials_energy, int64_t* partials_div);
+NSS_API int nss_step_record_f64(const double* partials_energy, int64_t n_energy, const double* partials_div,
+                                int64_t n_div, double scale, double* record, int32_t slot, const int32_t* done,
+                                nss_stream_t stream);
 
 /* ---- device-resident preconditioned Lanczos: the scale factor k -------------------------------
  * Replaces the n-sized work AND the scalar recurrences of `EigenValues_Preconditioner(mat=A, pre=preA, tol=1e-3)`

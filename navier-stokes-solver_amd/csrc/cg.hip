@@ -121,6 +121,75 @@ __global__ __launch_bounds__(kBlock) void cg_direction_kernel(CgArgs a) {
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) a.p[i] = fma(beta, a.p[i], a.z[i]);
 }
 
+// Start of a solve from x = 0 on the device (nss_cg_start): x = 0, r = b; with a fused preconditioner also z = dinv r,
+// p = z and the partials of <r, z>
+__global__ __launch_bounds__(kBlock) void cg_start_kernel(CgArgs a, const double* __restrict__ b, int fused_pre) {
+  __shared__ double lds[kBlock / kWave];
+  const int stride = gridDim.x * kBlock;
+  double acc = 0.0;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
+    const double rn = b[i];
+    a.x[i] = 0.0;
+    a.r[i] = rn;
+    if (fused_pre) {
+      const double zn = a.dinv ? a.dinv[i] * rn : rn;
+      a.z[i] = zn;
+      a.p[i] = zn;
+      acc = fma(rn, zn, acc);
+    }
+  }
+  if (fused_pre) {
+    const double s = block_sum(acc, lds);
+    if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
+  }
+}
+
+// p = z and the partials of <r, z> behind a preconditioner that is a launch of its own
+__global__ __launch_bounds__(kBlock) void cg_start_direction_kernel(CgArgs a) {
+  __shared__ double lds[kBlock / kWave];
+  const int stride = gridDim.x * kBlock;
+  double acc = 0.0;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += stride) {
+    const double zn = a.z[i];
+    a.p[i] = zn;
+    acc = fma(a.r[i], zn, acc);
+  }
+  const double s = block_sum(acc, lds);
+  if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
+}
+
+// rz = the sum (the tree of cg_sum_kernel), err0, tol and a cleared control word; a zero right-hand side ends the solve
+// before its first iteration (done, it_final = -1: no iterations)
+__global__ __launch_bounds__(kCgSum) void cg_start_sum_kernel(int32_t* __restrict__ ctrl, int n,
+                                                               const double* __restrict__ part, double* __restrict__ scal,
+                                                               double tol) {
+  __shared__ double lds[kCgSum / kWave];
+  double a = 0.0, a2 = 0.0;
+  int i = threadIdx.x;
+  for (; i + kCgSum < n; i += 2 * kCgSum) {
+    a += part[i];
+    a2 += part[i + kCgSum];
+  }
+  for (; i < n; i += kCgSum) a += part[i];
+  const double s = wave_sum(a + a2);
+  if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < kCgSum / kWave; ++w) t += lds[w];
+    const double err0 = sqrt(fabs(t));
+    scal[G_RZ] = t;
+    scal[G_PQ] = 0.0;
+    scal[G_RZN] = 0.0;
+    scal[G_ERR0] = err0;
+    scal[G_TOL] = tol;
+    scal[G_RZ_ODD] = 0.0;
+    ctrl[GC_DONE] = err0 == 0.0 ? 1 : 0;
+    ctrl[GC_ITFINAL] = -1;
+    ctrl[GC_LAST] = -1;
+  }
+}
+
 static int cg_grid(const nss_cg_t& s) { return stream_grid(s.n, kBlock * 4); }
 
 static PreA pre_a_of(const nss_cg_t& s) {
@@ -172,6 +241,26 @@ int nss_cg_workspace(const nss_cg_t* s, int64_t* partials_a, int64_t* partials_b
     NSS_REQUIRE(s && s->A, "cg_workspace: NULL state / matrix");
     if (partials_a) *partials_a = s->A->nblk;
     if (partials_b) *partials_b = std::max<int64_t>(cg_grid(*s), s->pre_bjac ? bjac_dot_grid(*s->pre_bjac) : 0);
+  });
+}
+
+int nss_cg_start(const nss_cg_t* s, const double* b, double tol, nss_stream_t stream) {
+  return guarded([&] {
+    cg_check(s);
+    NSS_REQUIRE(b != nullptr && b != s->x && b != s->r, "cg_start: NULL right-hand side, or it aliases x / r");
+    hipStream_t st = as_stream(stream);
+    const bool fused_pre = !s->pre_bjac && !s->pre_amg;
+    CgArgs a{s->ctrl, s->scal, s->hist, s->n, 0, s->x, s->r, s->z, s->p, s->q, s->pre_diag, s->partials_b};
+    const int nb = cg_grid(*s);
+    hipLaunchKernelGGL(cg_start_kernel, dim3(nb), dim3(kBlock), 0, st, a, b, fused_pre ? 1 : 0);
+    NSS_CHECK_LAUNCH();
+    if (!fused_pre) {
+      pre_a_apply(pre_a_of(*s), 1.0, s->r, s->z, nullptr, nullptr, st);
+      hipLaunchKernelGGL(cg_start_direction_kernel, dim3(nb), dim3(kBlock), 0, st, a);
+      NSS_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(cg_start_sum_kernel, dim3(1), dim3(kCgSum), 0, st, s->ctrl, nb, s->partials_b, s->scal, tol);
+    NSS_CHECK_LAUNCH();
   });
 }
 

@@ -1,0 +1,217 @@
+// Kernels of the device-resident IMEX time step (`NavierStokes.Advance`; the reference's DoTimeStep / Project,
+// templates/NavierStokesSIMPLE_iterative.py:424-443).  One step is
+//
+//   F1  flux points     : F = adv*avg - |adv| diff / 2 with adv = I_adv u, avg = Avg u, diff = Diff u, written behind u
+//                         in ONE operand buffer [u | F]                                     (step_flux_kernel)
+//   F2  rows of [A | D] : temp = f - [A | D] [u | F]  ( = conv(u) + f - A u, conv = -D F )  (EpiStepRhs)
+//   ..  raw = mstar^-1 temp, phi = (B M^-1 B^T)^-1 B raw                                    (the fused CG loop, cg.hip)
+//   P1  rows of C       : out = raw - C phi;  u += tau out;  partials of <u, M u>           (EpiStepProject)
+//   P2  rows of B       : partials of |B u|^2                                               (step_div_kernel, optional)
+//   P3  one workgroup   : record[step] = { <u, M u> / 2, |B u| }                            (step_record_kernel)
+//
+// All fp64, no atomics: every sum is per-workgroup partials added by the fixed tree (fixed_sums_1024).
+#include "bpcg2.h"
+
+namespace nss {
+
+typedef int32_t int2v __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ bool step_done(const int32_t* done) { return done != nullptr && *done != 0; }
+
+// the row sum of a two-slot row as csr_direct_kernel forms it: 0 + p0 + p1, products rounded on their own
+__device__ __forceinline__ double two_slot_sum(const int2v& c, const dbl2v& v, double x0, double x1) {
+  double sum = 0.0;
+  if (c.x >= 0) sum += mul_unfused(v.x, x0);
+  if (c.y >= 0) sum += mul_unfused(v.y, x1);
+  return sum;
+}
+
+struct FluxOps {
+  const int32_t *adv_col, *avg_col, *diff_col;
+  const double *adv_val, *avg_val, *diff_val;
+};
+
+// F1: one lane per flux point.  The six slots of the three rows are requested first, then all six gathers of u, then the
+// arithmetic of upwind_flux_kernel (blas1.hip) on the three row sums.
+__global__ __launch_bounds__(kBlock) void step_flux_kernel(const int32_t* __restrict__ done, int32_t nflux, FluxOps m,
+                                                            const double* __restrict__ u, double* __restrict__ flux) {
+  if (step_done(done)) return;
+  const int stride = gridDim.x * kBlock;
+  for (int r = blockIdx.x * kBlock + threadIdx.x; r < nflux; r += stride) {
+    const int2v ca = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.adv_col) + r);
+    const int2v cm = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.avg_col) + r);
+    const int2v cj = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.diff_col) + r);
+    const dbl2v va = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.adv_val) + r);
+    const dbl2v vm = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.avg_val) + r);
+    const dbl2v vj = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.diff_val) + r);
+    const double a0 = ca.x >= 0 ? u[ca.x] : 0.0, a1 = ca.y >= 0 ? u[ca.y] : 0.0;
+    const double m0 = cm.x >= 0 ? u[cm.x] : 0.0, m1 = cm.y >= 0 ? u[cm.y] : 0.0;
+    const double j0 = cj.x >= 0 ? u[cj.x] : 0.0, j1 = cj.y >= 0 ? u[cj.y] : 0.0;
+    const double adv = two_slot_sum(ca, va, a0, a1);
+    const double avg = two_slot_sum(cm, vm, m0, m1);
+    const double dif = two_slot_sum(cj, vj, j0, j1);
+    NSS_ST(flux[r], fma(adv, avg, -0.5 * (fabs(adv) * dif)));
+  }
+}
+
+// F2: temp = f - (row of [A | D]) . [u | F]
+struct EpiStepRhs {
+  const int32_t* __restrict__ done;
+  const double* __restrict__ f;
+  double* __restrict__ out;
+  struct Pre { double f = 0.0; };
+  __device__ bool skip() const { return step_done(done); }
+  __device__ Pre fetch(int r) const { return Pre{f[r]}; }
+  __device__ void row(int r, double ax, const Pre& p) const { NSS_ST(out[r], p.f - ax); }
+  __device__ void finish(int, double*) const {}
+};
+
+// P1: out = raw - C phi (out may be raw itself);  with u: u += tau out;  partials of sum_r m_r e_r^2 over the row block,
+// e = the updated u, or out without u (m_r = 1 without mass)
+struct EpiStepProject {
+  const int32_t* __restrict__ done;
+  const double* raw;
+  double* out;
+  double* u;
+  const double* __restrict__ mass;
+  double tau;
+  double* __restrict__ partials;
+  double acc = 0.0;
+  struct Pre { double raw = 0.0, u = 0.0, m = 1.0; };
+  __device__ bool skip() const { return step_done(done); }
+  __device__ Pre fetch(int r) const { return Pre{raw[r], u ? u[r] : 0.0, mass ? mass[r] : 1.0}; }
+  __device__ void row(int r, double cphi, const Pre& p) {
+    const double t = p.raw - cphi;
+    out[r] = t;
+    double e = t;
+    if (u) {
+      e = fma(tau, t, p.u);
+      u[r] = e;
+    }
+    acc = fma(p.m * e, e, acc);
+  }
+  __device__ void finish(int b, double* lds) {
+    if (partials == nullptr) return;
+    const double s = block_sum(acc, lds);
+    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
+  }
+};
+
+// P2: partials of |B u|^2, one lane per row.  The row is summed entry after entry with products rounded on their own --
+// the order of a host CSR product -- because B u of a projected field is what cancellation leaves of terms 1e8 times
+// larger: summed in another order the diagnostic could not be checked against a host recomputation beyond a few digits.
+__global__ __launch_bounds__(kBlock) void step_div_kernel(const int32_t* __restrict__ done, int32_t m,
+                                                           const int32_t* __restrict__ rowptr,
+                                                           const int32_t* __restrict__ col, const double* __restrict__ val,
+                                                           const double* __restrict__ u, double* __restrict__ partials) {
+  __shared__ double lds[kBlock / kWave];
+  if (step_done(done)) return;
+  const int stride = gridDim.x * kBlock;
+  double acc = 0.0;
+  for (int r = blockIdx.x * kBlock + threadIdx.x; r < m; r += stride) {
+    const int s = rowptr[r], e = rowptr[r + 1];
+    double sum = 0.0;
+    for (int p = s; p < e; ++p) sum += mul_unfused(val[p], u[col[p]]);
+    acc = fma(sum, sum, acc);
+  }
+  const double t = block_sum(acc, lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// P3: record[2 slot] = scale * sum pk (the kinetic energy), record[2 slot + 1] = sqrt(sum pd) (NaN without pd)
+__global__ __launch_bounds__(kBlock) void step_record_kernel(const int32_t* __restrict__ done,
+                                                              const double* __restrict__ pk, int nk,
+                                                              const double* __restrict__ pd, int nd, double scale,
+                                                              double* __restrict__ record, int slot) {
+  __shared__ double lds[kRedDoubles];
+  if (step_done(done)) return;
+  const SumPair s = fixed_sums_1024(pk, nk, pd ? pd : pk, pd ? nd : 0, lds);
+  if (threadIdx.x == 0) {
+    record[2 * slot] = scale * s.a;
+    record[2 * slot + 1] = pd ? sqrt(s.b) : __builtin_nan("");
+  }
+}
+
+static int div_grid(const nss_csr_s& B) { return stream_grid(B.m, kBlock); }
+
+}  // namespace nss
+
+using namespace nss;
+
+extern "C" {
+
+int nss_step_flux_f64(nss_csr_t adv, nss_csr_t avg, nss_csr_t diff, const double* u, double* flux, const int32_t* done,
+                      nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(adv && avg && diff && u && flux, "step_flux: NULL argument");
+    NSS_REQUIRE(adv->m == avg->m && adv->m == diff->m && adv->n == avg->n && adv->n == diff->n,
+                "step_flux: adv, avg and diff differ in shape");
+    require_f64_values(adv, "step_flux");
+    require_f64_values(avg, "step_flux");
+    require_f64_values(diff, "step_flux");
+    NSS_REQUIRE(fixed_width_copy(*adv) && fixed_width_copy(*avg) && fixed_width_copy(*diff),
+                "step_flux: a row of adv, avg or diff has more than two entries");
+    if (adv->m == 0) return;
+    const FluxOps m{adv->fw_col, avg->fw_col, diff->fw_col, adv->fw_val, avg->fw_val, diff->fw_val};
+    hipLaunchKernelGGL(step_flux_kernel, dim3(stream_grid(adv->m, kBlock)), dim3(kBlock), 0, as_stream(stream), done,
+                       adv->m, m, u, flux);
+    NSS_CHECK_LAUNCH();
+  });
+}
+
+int nss_step_rhs_f64(nss_csr_t ad, const double* uf, const double* f, double* temp, const int32_t* done,
+                     nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(ad && uf && f && temp, "step_rhs: NULL argument");
+    NSS_REQUIRE(temp != uf && temp != f, "step_rhs: temp aliases an operand");
+    launch_csr_stream(*ad, uf, EpiStepRhs{done, f, temp}, as_stream(stream));
+  });
+}
+
+int nss_step_project_f64(nss_csr_t c, const double* phi, const double* raw, double* out, double* u, double tau,
+                         const double* mass, double* partials, int64_t cap, const int32_t* done, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(c && phi && raw && out, "step_project: NULL argument");
+    NSS_REQUIRE(u != out && u != raw, "step_project: u aliases raw / out");
+    require_f64_values(c, "step_project");
+    NSS_REQUIRE(fixed_width_copy(*c), "step_project: a row of C has more than two entries");
+    NSS_REQUIRE(partials == nullptr || cap >= c->nblk, "step_project: partials hold fewer entries than C has row blocks");
+    if (c->m == 0) return;
+    const EpiStepProject epi{done, raw, out, u, mass, tau, partials};
+    hipLaunchKernelGGL((csr_direct_kernel<EpiStepProject>), dim3(nss_csr_s::grid(c->nblk)), dim3(kBlock), 0,
+                       as_stream(stream), c->view(0, c->nblk, 0), c->fw_col, c->fw_val, phi, epi);
+    NSS_CHECK_LAUNCH();
+  });
+}
+
+int nss_step_divergence_f64(nss_csr_t b, const double* u, double* partials, int64_t cap, const int32_t* done,
+                            nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(b && u && partials, "step_divergence: NULL argument");
+    require_f64_values(b, "step_divergence");
+    NSS_REQUIRE(cap >= div_grid(*b), "step_divergence: partials hold fewer entries than nss_step_workspace asks for");
+    hipLaunchKernelGGL(step_div_kernel, dim3(div_grid(*b)), dim3(kBlock), 0, as_stream(stream), done, b->m, b->rowptr,
+                       b->col, b->val, u, partials);
+    NSS_CHECK_LAUNCH();
+  });
+}
+
+int nss_step_workspace(nss_csr_t c, nss_csr_t b, int64_t* partials_energy, int64_t* partials_div) {
+  return guarded([&] {
+    NSS_REQUIRE(c && b, "step_workspace: NULL matrix");
+    if (partials_energy) *partials_energy = c->nblk;
+    if (partials_div) *partials_div = div_grid(*b);
+  });
+}
+
+int nss_step_record_f64(const double* partials_energy, int64_t n_energy, const double* partials_div, int64_t n_div,
+                        double scale, double* record, int32_t slot, const int32_t* done, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(partials_energy && record && slot >= 0 && n_energy >= 0 && n_div >= 0, "step_record: bad argument");
+    hipLaunchKernelGGL(step_record_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), done, partials_energy,
+                       int(n_energy), partials_div, int(n_div), scale, record, int(slot));
+    NSS_CHECK_LAUNCH();
+  });
+}
+
+}  // extern "C"

@@ -131,6 +131,31 @@ class HaloPlan:
 # --------------------------------------------------------------------------------------
 # communicators
 # --------------------------------------------------------------------------------------
+_exit_hooked = False
+
+
+def _destroy_gloo_group_at_exit(dist):
+    """A gloo process group that is still alive when the interpreter shuts down is torn down after the modules its
+    threads use: a rank that had finished its work can then end in std::terminate ("terminate called without an active
+    exception", exit status -6; intermittent, a race of the shutdown order).  Destroy it in an exit handler instead, while
+    the interpreter is whole, unless the caller has done so.  Destroying a gloo group is local -- it closes this rank's
+    pairs and joins its threads, without waiting for a peer (tests/test_gloo_exit_cpu.py: a peer that is already gone) --
+    which is not so for RCCL: those groups are left to their owner."""
+    global _exit_hooked
+    if _exit_hooked:
+        return
+    _exit_hooked = True
+    import atexit
+
+    def destroy():
+        try:
+            if dist.is_initialized() and dist.get_backend() == "gloo":
+                dist.destroy_process_group()
+        except Exception:
+            pass
+    atexit.register(destroy)
+
+
 class TorchComm:
     """torch.distributed (RCCL on GPUs, gloo on CPUs).  Buffers are engine buffers: torch
     tensors for the HIP engine, numpy arrays (shared memory with torch) for the checker."""
@@ -143,6 +168,8 @@ class TorchComm:
         # gloo cannot move device buffers: stage them through the host (used when several
         # ranks share one GPU in the tests; the GPU box runs RCCL, which takes them directly)
         self.stage = dist.get_backend() == "gloo"
+        if self.stage:
+            _destroy_gloo_group_at_exit(dist)
 
     def _t(self, buf):
         return buf if isinstance(buf, self.torch.Tensor) else self.torch.from_numpy(buf)

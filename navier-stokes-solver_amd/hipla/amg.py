@@ -45,12 +45,25 @@ def _priorities(n, seed):
     return pri.view(np.int64)
 
 
-def _coarsest(A, omega, dense_limit):
-    """Coarsest-level solve as a matrix: the dense inverse while it is small, otherwise (coarsening
-    stalled on a large level) one damped-Jacobi step -- both symmetric positive definite."""
+def constants_pseudo_inverse(dense):
+    """The pseudo-inverse X of a symmetric positive semi-definite matrix L whose kernel is the constants (a Laplacian
+    without a Dirichlet boundary: the pressure operator B M_u^-1 B^T of an enclosed domain, and every Galerkin coarse
+    operator of it -- the tentative prolongator has unit entries, so P maps coarse constants to fine ones):
+    X = inv(L + e e^T / n) - e e^T / n with e = ones.  L X L = L, X e = 0, X symmetric; np.linalg.inv(L) itself is
+    meaningless there."""
+    n = dense.shape[0]
+    shift = np.full((n, n), 1.0 / n)
+    x = np.linalg.inv(dense + shift) - shift
+    return 0.5 * (x + x.T)
+
+
+def _coarsest(A, omega, dense_limit, nullspace=None):
+    """Coarsest-level solve as a matrix: the dense inverse while it is small (`nullspace="constants"`: the
+    pseudo-inverse on the complement of the constants), otherwise (coarsening stalled on a large level) one
+    damped-Jacobi step -- both symmetric positive (semi-)definite."""
     host = A.to_scipy()
     if A.height <= dense_limit:
-        dense = np.linalg.inv(host.toarray())
+        dense = constants_pseudo_inverse(host.toarray()) if nullspace == "constants" else np.linalg.inv(host.toarray())
         n = dense.shape[0]
         if np.count_nonzero(dense) == dense.size:     # (the usual case: the CSR arrays written directly -- scipy's
             # dense -> CSR conversion goes through nonzero() and a COO sort: 0.15 s for the 1487-row coarse level of cfg4)
@@ -64,10 +77,10 @@ def _coarsest(A, omega, dense_limit):
 
 
 def build_hierarchy(mat, max_levels=10, coarse_size=2000, omega=2.0 / 3.0, seed=0, theta=0.04,
-                    dense_limit=6000):
+                    dense_limit=6000, nullspace=None):
     """Levels, finest first: dict(n, A, dinv, P, R) and on the coarsest dict(n, A, dinv, inv); the
     operators are `SparseMatrix` objects resident in the engine, `dinv` an engine buffer.  `theta`
-    is the strength-of-connection threshold of the aggregation on the coarse levels."""
+    is the strength-of-connection threshold of the aggregation on the coarse levels; `nullspace`: see `_coarsest`."""
     eng = mat.engine
     levels = []
     A = mat
@@ -80,7 +93,7 @@ def build_hierarchy(mat, max_levels=10, coarse_size=2000, omega=2.0 / 3.0, seed=
             agg, nagg = eng.amg_aggregate(A.handle, theta if levels else 0.0, priority)
             last = nagg > 0.7 * n                         # stalled: stop here rather than stack levels
         if last:
-            entry["inv"] = _coarsest(A, omega, dense_limit)
+            entry["inv"] = _coarsest(A, omega, dense_limit, nullspace)
             levels.append(entry)
             if hasattr(eng, "scratch_trim"):
                 eng.scratch_trim()                        # the pooled temporaries of the sparse products
@@ -106,18 +119,26 @@ class SmoothedAggregationAMG(BaseMatrix):
     (a `SparseMatrix`), set up and applied on the engine.
 
     `storage`: "fp64" (default) or "fp32" -- set-up as for "fp64", then the cycle applies fp32 copies of every level
-    operator, P and R (`applied_levels`; R = P^T stays exact, the cycle stays symmetric); `levels` keeps the fp64 set-up."""
+    operator, P and R (`applied_levels`; R = P^T stays exact, the cycle stays symmetric); `levels` keeps the fp64 set-up.
 
-    def __init__(self, mat, max_levels=10, coarse_size=2000, omega=2.0 / 3.0, seed=0, theta=0.04, storage="fp64"):
+    `nullspace`: None (default: `mat` is non-singular) or "constants" -- `mat` is a Laplacian with the constants in its
+    kernel (the pressure operator of an enclosed domain): the coarsest level applies the pseudo-inverse on the complement
+    of the constants (`constants_pseudo_inverse`) instead of an inverse that does not exist."""
+
+    def __init__(self, mat, max_levels=10, coarse_size=2000, omega=2.0 / 3.0, seed=0, theta=0.04, storage="fp64",
+                 nullspace=None):
         super().__init__()
         if not isinstance(mat, SparseMatrix):
             raise TypeError("SmoothedAggregationAMG needs a SparseMatrix")
+        if nullspace not in (None, "constants"):
+            raise ValueError("SmoothedAggregationAMG: nullspace is None or \"constants\"")
         self.storage = check_storage(storage)
         self.engine = mat.engine
         self.mat = mat
         self.n = mat.height
         self.omega = float(omega)
-        self.levels = build_hierarchy(mat, max_levels, coarse_size, omega, seed, theta)
+        self.nullspace = nullspace
+        self.levels = build_hierarchy(mat, max_levels, coarse_size, omega, seed, theta, nullspace=nullspace)
         self.level_sizes = [lv["n"] for lv in self.levels]
         self.operator_complexity = sum(lv["A"].nnz for lv in self.levels) / mat.nnz
         self.applied_levels = stored_levels(self.levels, storage)

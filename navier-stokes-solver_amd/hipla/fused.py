@@ -821,3 +821,224 @@ class CgLoop(FusedLoop):
         done, it_final = run_chunked(self.enqueue, self.poll, 0, maxsteps, poll_every or POLL_EVERY)
         count = it_final + 1 if done else maxsteps
         return count, [err0] + [float(v) for v in eng.to_host(self.hist)[:count]]
+
+    def solve_resident(self, b, x, precision, maxsteps, poll_every=None):
+        """As `solve`, started on the device (``nss_cg_start``): no dot product on the host, no upload, no allocation
+        after the first call and no history download -- the only synchronisations are the polls.  Returns the iteration
+        count (0 for a zero right-hand side)."""
+        eng, st = self.eng, self.state
+        self.partials = fit_partials(eng, st, self.lib.nss_cg_workspace, ("A",), self.partials)
+        if self.hist is None or self.hist.numel() < max(1, maxsteps):
+            self.hist = eng.zeros(max(1, maxsteps))
+        st.hist, st.x = self.hist.data_ptr(), x.data_ptr()
+        eng._check(self.lib.nss_cg_start(C.byref(st), b.data_ptr(), float(precision), eng.stream))
+        done, it_final = run_chunked(self.enqueue, self.poll, 0, maxsteps, poll_every or POLL_EVERY)
+        return it_final + 1 if done else maxsteps
+
+
+def two_entry_rows(mat):
+    """Whether every row of the scipy CSR matrix `mat` holds at most two entries -- the shape the row-per-lane kernels
+    take (``nss::fixed_width_copy``): (True, None) or (False, reason)."""
+    longest = int(np.diff(mat.indptr).max()) if mat.shape[0] else 0
+    if longest > 2:
+        return False, "a row holds %d entries (the row-per-lane kernels take two)" % longest
+    return True, None
+
+
+def constants_in_kernel(lap):
+    """The test of oracle/krylov_ref.py::project for a pressure operator with the constants in its kernel (enclosed
+    domain): |L 1| <= 1e-12 sum |L|."""
+    return bool(np.linalg.norm(lap @ np.ones(lap.shape[0])) <= 1e-12 * abs(lap).sum())
+
+
+class StepRecord:
+    """What `NavierStokes.Advance` returns: one entry per step of `mstar_iterations`, `proj_iterations` (pseudo time
+    stepping: the two projections of a step added), `div_norm` = |B u| and `kinetic_energy` = <u, M_u u> / 2 after the
+    step (both None with ``diagnostics=False``); `declined`: why the statements ran instead of the device-resident
+    step (None when it ran); `flux_declined`: why the convection term ran through `ConvectionOperator`."""
+
+    def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None):
+        self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
+        self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
+        self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
+        self.declined, self.flux_declined = declined, flux_declined
+
+
+class TimeStepper(FusedLoop):
+    """Device-resident IMEX time stepping (``nss_step_*`` around two `CgLoop` solves): the statements of the reference's
+    DoTimeStep / Project (templates/NavierStokesSIMPLE_iterative.py:424-443) and of its pseudo time stepping (:406-417).
+
+    Per step: the flux kernel writes F behind u in the operand buffer [u | F]; one launch over the rows of [A | D] forms
+    temp = f - A u - D F; raw = mstar^-1 temp (CG from zero); rhs = B raw; phi = (B M_u^-1 B^T)^-1 rhs (CG from zero); one
+    launch over the rows of C = M_u^-1 B^T forms raw - C phi, u += timestep * that and the partials of <u, M_u u>; with
+    diagnostics one launch over the rows of B gives the partials of |B u|^2 and one workgroup writes the step's record.
+    Every buffer is allocated here, once; the only host synchronisations of a step are the polls of the two solves."""
+
+    PRECISION = (1e-4, 1e-8)          # CGSolver(..., precision=) of invmstar / invproj in the template
+    MAXSTEPS = (500, 5000)
+
+    @classmethod
+    def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None):
+        """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
+        `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
+        solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
+        the convection operators (`flux_declined`).  `shared`: a dict in which the stepper looks up, and leaves, the
+        device matrices that do not depend on `inner_pre` (mstar, Lp, C, adv, avg, diff, AD), so that the steppers of
+        one system -- and a caller that already holds `M_u + timestep A`, `B M_u^-1 B^T`, `M_u^-1 B^T` and passes them
+        under "mstar", "Lp", "C" -- keep them once.  Returns None with the reason in ``TimeStepper.last_declined``."""
+        return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared))
+
+    @classmethod
+    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared):
+        if inner_pre not in ("jacobi", "amg"):
+            raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
+        if not ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not isinstance(A, SparseMatrix) or not isinstance(B, SparseMatrix) or not isinstance(f, Vector):
+            return "A, B are not SparseMatrix operands or f is not a plain Vector"
+        if not _hip(A.engine) or not hasattr(A.engine.lib, "nss_step_flux_f64"):
+            return "not the HIP engine"
+        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, {} if shared is None else shared)
+
+    def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared):
+        import scipy.sparse as sp
+        from .matrix import JacobiPreconditioner
+        eng = self.eng = A.engine
+        self.lib, self.A, self.B, self.f, self.timestep = eng.lib, A, B, f, float(timestep)
+        self.n_u, self.n_p = A.height, B.height
+        m_u = np.asarray(m_u, dtype=np.float64)
+        # ---- the convection term: two-slot copies of adv / avg / diff and the rows of [A | D] ----
+        if "flux_declined" not in shared:
+            ops = system.convection_operators()
+            shared["flux_declined"] = next((key + ": " + why for key in ("adv", "avg", "diff")
+                                            for ok, why in [two_entry_rows(ops[key])] if not ok), None)
+            if shared["flux_declined"] is None:
+                for key in ("adv", "avg", "diff"):
+                    shared[key] = SparseMatrix.from_scipy(ops[key], engine=eng)
+                AD = sp.hstack([A.to_scipy(), ops["div"]], format="csr")
+                AD.sort_indices()
+                shared["AD"] = SparseMatrix.from_scipy(AD, engine=eng)
+        self.flux_declined = shared["flux_declined"]
+        if self.flux_declined is None:
+            self.adv, self.avg, self.diff, self.AD = (shared[key] for key in ("adv", "avg", "diff", "AD"))
+            self.nflux = self.adv.height
+            self.conv = None
+        else:
+            self.nflux = 0
+            self.conv = conv_operator()
+        self.uf = eng.zeros(self.n_u + self.nflux)          # the operand [u | F]
+        self.u = eng.view(self.uf, 0, self.n_u)
+        self.temp, self.raw, self.temp2 = eng.zeros(self.n_u), eng.zeros(self.n_u), eng.zeros(self.n_u)
+        self.rhs_p, self.phi = eng.zeros(self.n_p), eng.zeros(self.n_p)
+        # ---- the inner solves ----
+        if "mstar" not in shared:
+            shared["mstar"] = SparseMatrix.from_scipy((sp.diags(m_u) + self.timestep * A.to_scipy()).tocsr(), engine=eng)
+        if "C" not in shared:
+            shared["C"] = SparseMatrix.from_scipy((sp.diags(1.0 / m_u) @ B.to_scipy().T).tocsr(), engine=eng)
+        if "Lp" not in shared:
+            lap_p = (B.to_scipy() @ shared["C"].to_scipy()).tocsr()
+            lap_p.sort_indices()
+            shared["Lp"] = SparseMatrix.from_scipy(lap_p, engine=eng)
+        self.mstar, self.Lp, self.C = shared["mstar"], shared["Lp"], shared["C"]
+        if "singular" not in shared:
+            ok, why = two_entry_rows(self.C.to_scipy())
+            if not ok:
+                raise ValueError("TimeStepper: M_u^-1 B^T: " + why)
+            shared["singular"] = constants_in_kernel(self.Lp.to_scipy())
+        self.singular = shared["singular"]
+        if inner_pre == "amg":
+            self.pre_m = SmoothedAggregationAMG(self.mstar)
+            self.pre_p = SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
+        else:
+            self.pre_m, self.pre_p = JacobiPreconditioner(self.mstar), JacobiPreconditioner(self.Lp)
+        self.cg_m = CgLoop(eng, self.mstar, pre_for("cg", self.pre_m))
+        self.cg_p = CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
+        # ---- the record ----
+        uniform = bool(m_u.size) and bool((m_u == m_u[0]).all())
+        self.mass = None if uniform else eng.from_host(m_u)
+        self.energy_scale = 0.5 * (float(m_u[0]) if uniform else 1.0)
+        self.partials_e = self.partials_d = None
+        self._fit_partials()
+
+    def _fit_partials(self):
+        """The partials of the record for the CURRENT launch plan of C (row blocks) and the size of B."""
+        ne, nd = C.c_int64(), C.c_int64()
+        self.eng._check(self.lib.nss_step_workspace(self.C.handle.ptr, self.B.handle.ptr, C.byref(ne), C.byref(nd)))
+        if self.partials_e is None or self.partials_e.numel() < ne.value or self.partials_d.numel() < nd.value:
+            self.partials_e, self.partials_d = self.eng.zeros(max(1, ne.value)), self.eng.zeros(max(1, nd.value))
+        self.n_energy, self.n_div = ne.value, nd.value
+
+    # ---- the launches of a step -----------------------------------------------------------------------------------
+    def right_hand_side(self):
+        """temp = conv(u) + f - A u from the u part of the operand buffer."""
+        eng, lib = self.eng, self.lib
+        if self.flux_declined is None:
+            flux = eng.view(self.uf, self.n_u, self.n_u + self.nflux)
+            eng._check(lib.nss_step_flux_f64(self.adv.handle.ptr, self.avg.handle.ptr, self.diff.handle.ptr,
+                                             self.uf.data_ptr(), flux.data_ptr(), None, eng.stream))
+            eng._check(lib.nss_step_rhs_f64(self.AD.handle.ptr, self.uf.data_ptr(), self.f.buf.data_ptr(),
+                                            self.temp.data_ptr(), None, eng.stream))
+            return
+        u, temp = Vector(buf=self.u, engine=eng), Vector(buf=self.temp, engine=eng)
+        temp.data = self.conv * u
+        temp.data += self.f
+        temp.data += -self.A * u
+
+    def project(self, vel, out=None, update=None, energy=False):
+        """out = vel - C phi with phi = (B M_u^-1 B^T)^-1 B vel (`Project`; `out` None: in place); `update`:
+        u += timestep * out in the same launch; `energy`: also the partials of <e, M_u e>, e = the updated u, or out.
+        Returns the CG iterations."""
+        eng, lib = self.eng, self.lib
+        eng.csr_spmv(self.B.handle, 1.0, vel, 0.0, self.rhs_p)
+        its = self.cg_p.solve_resident(self.rhs_p, self.phi, self.precision[1], self.maxsteps[1])
+        eng._check(lib.nss_step_project_f64(self.C.handle.ptr, self.phi.data_ptr(), vel.data_ptr(),
+                                            (vel if out is None else out).data_ptr(),
+                                            update.data_ptr() if update is not None else None, self.timestep,
+                                            self.mass.data_ptr() if self.mass is not None else None,
+                                            self.partials_e.data_ptr() if energy else None, self.partials_e.numel(),
+                                            None, eng.stream))
+        return its
+
+    def write_record(self, record, slot, divergence=True):
+        eng, lib = self.eng, self.lib
+        if divergence:
+            eng._check(lib.nss_step_divergence_f64(self.B.handle.ptr, self.u.data_ptr(), self.partials_d.data_ptr(),
+                                                   self.partials_d.numel(), None, eng.stream))
+        eng._check(lib.nss_step_record_f64(self.partials_e.data_ptr(), self.n_energy,
+                                           self.partials_d.data_ptr() if divergence else None, self.n_div,
+                                           self.energy_scale, record.data_ptr(), slot, None, eng.stream))
+
+    def advance(self, gfu, gfup, nsteps, precision=None, maxsteps=None, diagnostics=True, pseudo=False):
+        """`nsteps` steps on the velocity `gfu` (pressure-like potential of the last projection -> `gfup`).
+        `precision` / `maxsteps`: one value for both inner solves, a pair (mstar, projection), or None = the template's."""
+        def pair(v, default):
+            return default if v is None else tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        self.precision = tuple(float(p) for p in pair(precision, self.PRECISION))
+        self.maxsteps = tuple(int(m) for m in pair(maxsteps, self.MAXSTEPS))
+        eng = self.eng
+        self._fit_partials()
+        nsteps = int(nsteps)
+        record = eng.zeros(2 * max(1, nsteps)) if diagnostics else None
+        eng.copy(gfu.buf, self.u)
+        its_m, its_p = [], []
+        if pseudo:
+            self.project(self.u)                                          # :407  Project(gfu)
+        for step in range(nsteps):
+            if pseudo:
+                eng.csr_spmv(self.A.handle, -1.0, self.u, 0.0, self.temp)         # :411  temp = -A u
+            else:
+                self.right_hand_side()                                            # :429-431
+            its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))   # :433
+            count = self.project(self.raw, out=self.temp2, update=self.u, energy=diagnostics and not pseudo)   # :434,438
+            if pseudo:
+                count += self.project(self.u, energy=diagnostics)                # :415  Project(gfu)
+            its_p.append(count)
+            if diagnostics:
+                self.write_record(record, step)
+        eng.copy(self.u, gfu.buf)
+        if nsteps or pseudo:
+            eng.copy(self.phi, gfup.buf)
+        if not diagnostics:
+            return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined)
+        host = eng.to_host(record).reshape(-1, 2)[:nsteps]               # the one read-back
+        return StepRecord(its_m, its_p, host[:, 1].copy(), host[:, 0].copy(), flux_declined=self.flux_declined)

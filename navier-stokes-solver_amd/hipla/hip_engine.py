@@ -121,6 +121,13 @@ def _signatures():
         "nss_cg_workspace": (C.c_int, [vp, c_i64_p, c_i64_p]),
         "nss_cg_iterate": (C.c_int, [vp, i32, i32, vp]),
         "nss_cg_poll": (C.c_int, [vp, c_i32_p, c_i32_p, c_i32_p, vp]),
+        "nss_cg_start": (C.c_int, [vp, vp, dbl, vp]),
+        "nss_step_flux_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "nss_step_rhs_f64": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "nss_step_project_f64": (C.c_int, [vp, vp, vp, vp, vp, dbl, vp, vp, i64, vp, vp]),
+        "nss_step_divergence_f64": (C.c_int, [vp, vp, vp, i64, vp, vp]),
+        "nss_step_workspace": (C.c_int, [vp, vp, c_i64_p, c_i64_p]),
+        "nss_step_record_f64": (C.c_int, [vp, i64, vp, i64, dbl, vp, i32, vp, vp]),
         "nss_bpcg1_phases": (C.c_int, [vp, i32, i32, i32, vp]),
         "nss_bpcg1_iterate_dist": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),
         "nss_bpcg2_workspace": (C.c_int, [vp, c_i64_p, c_i64_p, c_i64_p]),

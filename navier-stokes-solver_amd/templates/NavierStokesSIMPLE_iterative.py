@@ -205,13 +205,7 @@ class NavierStokes:
             self.Project(self.gfu)
             for it in range(timesteps):
                 print("it =", it)
-                temp = self.a.mat.CreateColVector()
-                temp2 = self.a.mat.CreateColVector()
-                temp.data = -self.a.mat * self.gfu
-                temp2.data = ops["invmstar"] * temp
-                self.Project(temp2)
-                self.gfu.data += self.timestep * temp2
-                self.Project(self.gfu)
+                self._pseudo_time_step(ops)
             return
         if not iterative:
             raise NotImplementedError("sparse direct initial solve is not on the Krylov path")
@@ -239,6 +233,19 @@ class NavierStokes:
         else:                                          # zero initial residual: bare vector (:191-192)
             self.stokes_bpcg_iterations, self.stokes_bpcg_time = 0, 0.0
 
+    def _pseudo_time_step(self, ops):
+        """One pseudo time step towards the Stokes state (:408-417): no convection, two projections.  Returns the
+        iterations of the two projection solves."""
+        temp = self.a.mat.CreateColVector()
+        temp2 = self.a.mat.CreateColVector()
+        temp.data = -self.a.mat * self.gfu
+        temp2.data = ops["invmstar"] * temp
+        self.Project(temp2)
+        count = ops["invproj"].iterations
+        self.gfu.data += self.timestep * temp2
+        self.Project(self.gfu)
+        return count + ops["invproj"].iterations
+
     def AddForce(self, force):
         """`force`: host array of nodal forces on the velocity dofs, added to f (:419-422)."""
         self.f.vec.data += hipla.Vector.from_numpy(np.asarray(force, dtype=np.float64))
@@ -264,3 +271,80 @@ class NavierStokes:
         rhs.data = self.b.mat * vel
         self.gfup.data = ops["invproj"] * rhs
         vel.data -= ops["correct"] * self.gfup
+
+    def Advance(self, nsteps, inner_pre="jacobi", precision=None, diagnostics=True, pseudo=False, maxsteps=None):
+        """`nsteps` IMEX steps (`pseudo=True`: the pseudo time stepping of ``SolveInitial(timesteps=nsteps)``) through
+        the device-resident stepper (`hipla.fused.TimeStepper`): the statements of `DoTimeStep` / `Project` in two
+        launches for the right-hand side and one for the projection tail, every buffer allocated once, a per-step
+        record on the device read back once.  Returns an `hipla.fused.StepRecord` (mstar_iterations,
+        proj_iterations, div_norm, kinetic_energy).
+
+        `inner_pre`: "jacobi" (what `DoTimeStep` uses) or "amg" -- a smoothed-aggregation V-cycle for both inner CG
+        solves; `precision` / `maxsteps`: None = those of `DoTimeStep` (1e-4 / 1e-8, 500 / 5000), one value for both
+        solves, or a pair; `diagnostics=False` skips |B u| and the kinetic energy.  When the stepper declines (no HIP
+        engine, ``hipla.fused.ENABLED`` off) the statements themselves run -- with Jacobi-CG, whatever `inner_pre` --
+        and the reason is in ``record.declined`` (and ``self.advance_declined``).
+
+        The steppers (one per `inner_pre`) share `M_u + timestep A`, `B M_u^-1 B^T` and `M_u^-1 B^T` with `DoTimeStep`
+        and the convection matrices with each other; what a stepper adds in HBM is its work vectors, the rows of
+        `[A | D]` -- a second copy of A, 12 bytes per non-zero -- and, for "amg", the two hierarchies.  Like
+        `DoTimeStep`, they keep the `timestep` of their first use: these operators are built once per object."""
+        from hipla import fused
+        from hipla.fused import StepRecord, TimeStepper
+        if inner_pre not in ("jacobi", "amg"):
+            raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
+        steppers = self.__dict__.setdefault("_steppers", {})
+        stepper = steppers.get(inner_pre) if fused.ENABLED else None
+        if stepper is None:
+            s = self.system
+            m_u = np.full(s.n_u, s.h ** s.dim * self.V.dofs_per_site ** 0)
+            if "_stepper_shared" not in self.__dict__:      # one copy of the operators for DoTimeStep and every stepper
+                ops = self._time_stepping_operators()
+                self._stepper_shared = dict(mstar=ops["mstar"], Lp=ops["Lp"], C=ops["correct"])
+            stepper = TimeStepper.try_create(s, self.a.mat, self.b.mat, self.f.vec, self.timestep, m_u, inner_pre,
+                                             conv_operator=lambda: self.conv_operator, shared=self._stepper_shared)
+            if stepper is not None:
+                steppers[inner_pre] = stepper
+        self.advance_declined = TimeStepper.last_declined if stepper is None else None
+        if stepper is not None:
+            return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics, pseudo)
+        return self._advance_by_statements(int(nsteps), precision, maxsteps, diagnostics, pseudo, StepRecord)
+
+    def _advance_by_statements(self, nsteps, precision, maxsteps, diagnostics, pseudo, record_type):
+        """`Advance` through `DoTimeStep` / `Project` themselves; the inner solvers take `precision` / `maxsteps` for
+        the duration of the call."""
+        import contextlib
+        import io
+        ops = self._time_stepping_operators()
+        solvers = (ops["invmstar"], ops["invproj"])
+        saved = [(sv.precision, sv.maxsteps) for sv in solvers]
+
+        def pair(v):
+            return (None, None) if v is None else tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        for sv, p, m in zip(solvers, pair(precision), pair(maxsteps)):
+            sv.precision = sv.precision if p is None else float(p)
+            sv.maxsteps = sv.maxsteps if m is None else int(m)
+        its_m, its_p, div, energy = [], [], [], []
+        mass_u = self.system.h ** self.system.dim
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                if pseudo:
+                    self.Project(self.gfu)
+                for _ in range(nsteps):
+                    if pseudo:
+                        count = self._pseudo_time_step(ops)
+                    else:
+                        self.DoTimeStep()
+                        count = ops["invproj"].iterations
+                    its_m.append(ops["invmstar"].iterations)
+                    its_p.append(count)
+                    if diagnostics:
+                        bu = self.b.mat.CreateColVector()
+                        bu.data = self.b.mat * self.gfu
+                        div.append(float(hipla.Norm(bu)))
+                        energy.append(0.5 * mass_u * float(hipla.InnerProduct(self.gfu, self.gfu)))
+        finally:
+            for sv, (p, m) in zip(solvers, saved):
+                sv.precision, sv.maxsteps = p, m
+        return record_type(its_m, its_p, np.array(div) if diagnostics else None,
+                           np.array(energy) if diagnostics else None, declined=self.advance_declined)

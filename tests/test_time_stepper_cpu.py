@@ -1,0 +1,134 @@
+"""Host side of the device-resident time stepping (no GPU): the C ABI of csrc/step.hip, the pseudo-inverse the AMG
+applies on the coarsest level of a singular Laplacian, the two-entries-per-row detection, and `Advance`'s decline path on
+the CPU checker engine."""
+
+import contextlib
+import io
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+from conftest import ROOT
+
+STEP_SYMBOLS = ("nss_step_flux_f64", "nss_step_rhs_f64", "nss_step_project_f64", "nss_step_divergence_f64",
+                "nss_step_workspace", "nss_step_record_f64", "nss_cg_start")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as entry
+    from hipla.hip_engine import LIB_PATH, load_library
+    if not os.path.exists(LIB_PATH):
+        entry.build()
+    return load_library()
+
+
+def test_header_declares_the_step_entry_points():
+    from test_cabi_symbols import declared_symbols
+    names = declared_symbols()
+    for must in STEP_SYMBOLS:
+        assert must in names, must
+
+
+def test_library_exports_the_step_entry_points(lib):
+    from hipla.hip_engine import LIB_PATH, _signatures
+    assert lib.nss_abi_version() == 1
+    dynamic = subprocess.run(["nm", "-D", "--defined-only", LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in dynamic.splitlines() if line.strip()}
+    for must in STEP_SYMBOLS:
+        assert hasattr(lib, must) and must in exported and must in _signatures(), must
+
+
+def test_step_entry_points_report_argument_errors(lib):
+    assert lib.nss_step_flux_f64(None, None, None, None, None, None, None) != 0 and b"step_flux" in lib.nss_last_error()
+    assert lib.nss_step_rhs_f64(None, None, None, None, None, None) != 0 and b"step_rhs" in lib.nss_last_error()
+    assert lib.nss_step_project_f64(None, None, None, None, None, 0.0, None, None, 0, None, None) != 0
+    assert lib.nss_step_divergence_f64(None, None, None, 0, None, None) != 0
+    assert lib.nss_step_workspace(None, None, None, None) != 0
+    assert lib.nss_step_record_f64(None, 0, None, 0, 1.0, None, 0, None, None) != 0
+    assert lib.nss_cg_start(None, None, 1e-8, None) != 0 and b"cg" in lib.nss_last_error()
+
+
+def neumann_laplacian(n):
+    """5-point Laplacian of an n x n grid with no Dirichlet boundary: symmetric, kernel = constants."""
+    t = sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(n, n)).tolil()
+    t[0, 0] = t[n - 1, n - 1] = 1.0
+    t = t.tocsr()
+    return (sp.kron(sp.identity(n), t) + sp.kron(t, sp.identity(n))).tocsr()
+
+
+def test_constants_pseudo_inverse():
+    from hipla.amg import constants_pseudo_inverse
+    fine = neumann_laplacian(6)
+    agg = (np.arange(36) // 6 // 2) * 3 + (np.arange(36) % 6) // 2          # 2 x 2 aggregates
+    tent = sp.csr_matrix((np.ones(36), (np.arange(36), agg)), shape=(36, 9))
+    prol = tent - (2.0 / 3.0) * (sp.diags(1.0 / fine.diagonal()) @ fine @ tent)   # the smoothed prolongator
+    coarse = (prol.T @ fine @ prol).toarray()
+    for lap in (fine.toarray(), coarse):
+        n = lap.shape[0]
+        ones = np.ones(n)
+        assert np.linalg.norm(lap @ ones) <= 1e-12 * abs(lap).sum()          # singular: the constants
+        x = constants_pseudo_inverse(lap)
+        assert np.abs(lap @ x @ lap - lap).max() <= 1e-10 * np.abs(lap).max()
+        assert np.abs(x @ ones).max() <= 1e-10 * np.abs(x).max()
+        assert np.array_equal(x, x.T)
+        rhs = lap @ np.random.default_rng(0).standard_normal(n)               # consistent right-hand side
+        assert np.linalg.norm(lap @ (x @ rhs) - rhs) <= 1e-10 * np.linalg.norm(rhs)
+
+
+def test_two_entry_row_detection():
+    from hipla.fused import constants_in_kernel, two_entry_rows
+    from staggered_grid import mac_stokes
+    for s in (mac_stokes(2, 6), mac_stokes(3, 5), mac_stokes(2, 5).inflate(3), mac_stokes(3, 4).inflate(3)):
+        ops = s.convection_operators()
+        for key in ("adv", "avg", "diff"):
+            assert two_entry_rows(ops[key]) == (True, None), key
+        bt = (sp.diags(np.full(s.n_u, s.h ** -s.dim)) @ s.B.T).tocsr()
+        assert two_entry_rows(bt) == (True, None)                            # C = M_u^-1 B^T of the projection tail
+        assert constants_in_kernel((s.B @ bt).tocsr())                       # the all-wall cavity
+        ok, why = two_entry_rows(ops["div"])
+        assert not ok and "entries" in why
+    wide = sp.csr_matrix(np.array([[1.0, 0.0, 2.0, 0.0], [1.0, 1.0, 1.0, 0.0], [0.0, 0.0, 0.0, 0.0]]))
+    ok, why = two_entry_rows(wide)
+    assert not ok and "3 entries" in why
+    assert two_entry_rows(sp.csr_matrix((0, 4))) == (True, None)
+    assert not constants_in_kernel(sp.identity(4, format="csr"))
+
+
+def test_advance_declines_on_the_checker_engine(numpy_engine):
+    """Not the HIP engine: Advance runs DoTimeStep / the pseudo-time statements, reports why, and gives their results."""
+    import hipla
+    from templates.NavierStokesSIMPLE_iterative import NavierStokes, SyntheticMesh
+
+    def fresh():
+        ns = NavierStokes(SyntheticMesh(0.2, dim=2), nu=0.01, inflow="inlet", outflow="outlet", wall="wall|cyl", uin=None,
+                          timestep=0.05, order=1)
+        ns.AddForce(np.random.default_rng(8).standard_normal(ns.system.n_u))
+        ns.gfu.data = hipla.Vector.from_numpy(np.random.default_rng(2).standard_normal(ns.system.n_u))
+        return ns
+
+    ns, twin = fresh(), fresh()
+    rec = ns.Advance(2)
+    with contextlib.redirect_stdout(io.StringIO()):
+        twin.DoTimeStep()
+        twin.DoTimeStep()
+    assert rec.declined == "not the HIP engine" == ns.advance_declined
+    assert np.array_equal(ns.gfu.numpy(), twin.gfu.numpy())
+    s, u = ns.system, ns.gfu.numpy()
+    assert len(rec.mstar_iterations) == len(rec.proj_iterations) == 2 and (rec.proj_iterations > 0).all()
+    assert abs(rec.div_norm[-1] - np.linalg.norm(s.B @ u)) <= 1e-9 * np.linalg.norm(s.B @ u)
+    assert abs(rec.kinetic_energy[-1] - 0.5 * s.h ** s.dim * (u @ u)) <= 1e-12 * (u @ u)
+    ops = ns._time_stepping_operators()
+    assert (ops["invmstar"].precision, ops["invproj"].precision) == (1e-4, 1e-8)     # restored
+
+    ns, twin = fresh(), fresh()
+    rec = ns.Advance(2, pseudo=True, diagnostics=False)
+    with contextlib.redirect_stdout(io.StringIO()):
+        twin.SolveInitial(timesteps=2)
+    assert rec.declined and rec.div_norm is None and rec.kinetic_energy is None
+    assert np.array_equal(ns.gfu.numpy(), twin.gfu.numpy())
+    with pytest.raises(ValueError):
+        ns.Advance(1, inner_pre="ilu")

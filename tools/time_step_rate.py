@@ -1,0 +1,134 @@
+"""Per-step time of the device-resident IMEX step against the statements, same box, same process:
+
+    timeout -k 10 600 python tools/time_step_rate.py --grid 64 --out profiles/time_stepper_n64.json && \\
+    timeout -k 10 1100 python tools/time_step_rate.py --grid 136 --out profiles/time_stepper_n136.json
+
+Three runs on twins of one 3-D system (SyntheticMesh(1/grid, dim=3), order 1, nu = 0.01, timestep = 0.05; seeded force
+and start field, scaled so that the explicit convection term stays stable over the run: the acceleration f / m_u and the
+start velocity are both of size 0.02, |u| timestep / h below 0.3 up to grid 136 -- with an unscaled N(0, 1) force the field
+overflows within eight steps and the inner solves would run on NaN): `Advance(inner_pre="jacobi")`, `Advance(inner_pre="amg")` and `DoTimeStep()` -- the statements, whose
+code path this stepper does not touch.  After `--warmup` steps each, `--rounds` interleaved windows of `--steps` steps
+(DoTimeStep window, jacobi window, amg window, ...): per-step wall time (host clock around a window that ends in a
+device synchronise) and device time (events around the window), median and spread (max - min) of the windows, and the
+inner iteration counts of the last window.  Every window checks that the velocity is finite and that no inner solve ran
+into its iteration cap.  Prints one markdown table and one JSON line (also written to --out)."""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "navier-stokes-solver_amd"))
+
+import numpy as np
+
+import hipla
+
+
+ACCELERATION = 0.02     # size of f / m_u and of the start velocity
+
+
+def fresh(mesh, v0):
+    from templates.NavierStokesSIMPLE_iterative import NavierStokes
+    ns = NavierStokes(mesh, nu=0.01, inflow="inlet", outflow="outlet", wall="wall|cyl", uin=None, timestep=0.05, order=1)
+    s = ns.system
+    force = ACCELERATION * s.h ** s.dim * np.random.default_rng(8).standard_normal(s.n_u)
+    ns.f.vec.data = hipla.Vector.from_numpy(force)
+    ns.gfu.data = hipla.Vector.from_numpy(v0)
+    return ns
+
+
+def check(ns, mstar_its, proj_its, caps=(500, 5000)):
+    u = ns.gfu.numpy()
+    if not np.isfinite(u).all():
+        raise RuntimeError("the velocity is not finite: nothing to time")
+    if max(mstar_its) >= caps[0] or max(proj_its) >= caps[1]:
+        raise RuntimeError("an inner solve ran into its iteration cap: %s %s" % (mstar_its, proj_its))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from templates.NavierStokesSIMPLE_iterative import SyntheticMesh
+    eng = hipla.get_engine()                      # (no GPU: raises -- a timing needs the device)
+    mesh = SyntheticMesh(1.0 / args.grid, dim=3)
+    from discretizations import bdm_hybrid, system_of
+    s = system_of(bdm_hybrid(1, 10)[0](mesh, velocity_dirichlet="inlet|wall|cyl")[0], 0.01)   # (cached on the mesh)
+    v0 = ACCELERATION * np.random.default_rng(2).standard_normal(s.n_u)
+
+    runs = {}
+    for name in ("DoTimeStep", "jacobi", "amg"):
+        ns = fresh(mesh, v0)
+        ops = ns._time_stepping_operators() if name == "DoTimeStep" else None
+        last = {}
+
+        def window(k, ns=ns, name=name, ops=ops, last=last):
+            if name == "DoTimeStep":
+                ms, ps = [], []
+                with contextlib.redirect_stdout(io.StringIO()):
+                    for _ in range(k):
+                        ns.DoTimeStep()
+                        ms.append(ops["invmstar"].iterations)
+                        ps.append(ops["invproj"].iterations)
+                last["mstar"], last["proj"] = ms, ps
+            else:
+                rec = ns.Advance(k, inner_pre=name)
+                if rec.declined:
+                    raise RuntimeError("Advance declined: %s" % rec.declined)
+                last["mstar"], last["proj"] = rec.mstar_iterations.tolist(), rec.proj_iterations.tolist()
+            last["ns"] = ns
+        eng.synchronize()
+        t0 = time.perf_counter()
+        window(args.warmup)
+        eng.synchronize()
+        runs[name] = dict(window=window, last=last, wall=[], device=[], first_s=time.perf_counter() - t0)
+
+    for _ in range(args.rounds):                   # interleaved windows
+        for r in runs.values():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            a.record()
+            r["window"](args.steps)
+            b.record()
+            torch.cuda.synchronize()
+            r["wall"].append(1e3 * (time.perf_counter() - t0) / args.steps)
+            r["device"].append(a.elapsed_time(b) / args.steps)
+            check(r["last"]["ns"], r["last"]["mstar"], r["last"]["proj"])      # (outside the timed window)
+
+    result = {"grid": args.grid, "n_u": int(s.n_u), "n_p": int(s.n_p), "steps": args.steps, "rounds": args.rounds,
+              "device": eng.device_info()["arch"], "u_max_end": float(np.abs(runs["jacobi"]["last"]["ns"].gfu.numpy()).max())}
+    for name, r in runs.items():
+        result[name] = {"wall_ms_per_step": float(np.median(r["wall"])), "wall_spread_ms": float(np.ptp(r["wall"])),
+                        "device_ms_per_step": float(np.median(r["device"])), "device_spread_ms": float(np.ptp(r["device"])),
+                        "wall_windows_ms": r["wall"], "device_windows_ms": r["device"],
+                        "first_call_s": r["first_s"], "mstar_iterations": r["last"]["mstar"],
+                        "proj_iterations": r["last"]["proj"]}
+    base = result["DoTimeStep"]["wall_ms_per_step"]
+    for name in ("jacobi", "amg"):
+        result[name]["wall_ratio_to_DoTimeStep"] = result[name]["wall_ms_per_step"] / base
+    print("3-D n=%d (%d velocity, %d pressure dofs), %d windows of %d steps" % (args.grid, s.n_u, s.n_p, args.rounds, args.steps))
+    print("| run | wall ms / step (spread) | device ms / step (spread) | mstar its | proj its |\n|---|---|---|---|---|")
+    for name in runs:
+        d = result[name]
+        print("| %s | %.2f (%.2f) | %.2f (%.2f) | %s | %s |" % (name, d["wall_ms_per_step"], d["wall_spread_ms"],
+                                                               d["device_ms_per_step"], d["device_spread_ms"],
+                                                               d["mstar_iterations"], d["proj_iterations"]))
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
