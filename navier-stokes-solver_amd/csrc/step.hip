@@ -149,9 +149,9 @@ int nss_step_flux_f64(nss_csr_t adv, nss_csr_t avg, nss_csr_t diff, const double
     require_f64_values(adv, "step_flux");
     require_f64_values(avg, "step_flux");
     require_f64_values(diff, "step_flux");
+    if (adv->m == 0) return;                               // (no flux points: there is no two-slot copy to build)
     NSS_REQUIRE(fixed_width_copy(*adv) && fixed_width_copy(*avg) && fixed_width_copy(*diff),
                 "step_flux: a row of adv, avg or diff has more than two entries");
-    if (adv->m == 0) return;
     const FluxOps m{adv->fw_col, avg->fw_col, diff->fw_col, adv->fw_val, avg->fw_val, diff->fw_val};
     hipLaunchKernelGGL(step_flux_kernel, dim3(stream_grid(adv->m, kBlock)), dim3(kBlock), 0, as_stream(stream), done,
                        adv->m, m, u, flux);
@@ -174,9 +174,9 @@ int nss_step_project_f64(nss_csr_t c, const double* phi, const double* raw, doub
     NSS_REQUIRE(c && phi && raw && out, "step_project: NULL argument");
     NSS_REQUIRE(u != out && u != raw, "step_project: u aliases raw / out");
     require_f64_values(c, "step_project");
+    if (c->m == 0) return;                                 // (no rows: there is no two-slot copy to build)
     NSS_REQUIRE(fixed_width_copy(*c), "step_project: a row of C has more than two entries");
     NSS_REQUIRE(partials == nullptr || cap >= c->nblk, "step_project: partials hold fewer entries than C has row blocks");
-    if (c->m == 0) return;
     const EpiStepProject epi{done, raw, out, u, mass, tau, partials};
     hipLaunchKernelGGL((csr_direct_kernel<EpiStepProject>), dim3(nss_csr_s::grid(c->nblk)), dim3(kBlock), 0,
                        as_stream(stream), c->view(0, c->nblk, 0), c->fw_col, c->fw_val, phi, epi);

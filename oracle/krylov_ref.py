@@ -532,6 +532,45 @@ def cg(M, b, pre=None, tol=1e-10, maxsteps=1000):
     return x, np.array(hist)
 
 
+# ---- the fixed summation tree of the fused loops (restates csrc/nss_common.h::fixed_sums_1024) -----
+def fixed_sum_1024(pa):
+    """Sum of `pa` in the order of the LOOP formulation of ``fixed_sums_1024`` (csrc/nss_common.h), every addition
+    rounded once: 1024 virtual lanes; lane v owns pa[v], pa[v + 1024], ...; while four more of its terms exist they go
+    to four strided accumulators a0 .. a3, the up to three left over are added to a0 one after the other; the lane's
+    value is (a0 + a1) + (a2 + a3); the 64 lanes of a virtual wave are summed by the xor butterfly with offsets
+    32, 16, ... 1; the 16 wave sums are added to 0.0 in wave order.  The device code holds a second formulation for
+    at most 4096 terms (all loads first) that claims these bits too."""
+    pa = np.asarray(pa, dtype=np.float64)
+    lanes, wave = 1024, 64
+    n = pa.size
+    rows = 4 * ((n + 4 * lanes - 1) // (4 * lanes))
+    x = np.zeros(rows * lanes)
+    x[:n] = pa
+    x = x.reshape(rows, lanes)                                     # x[k, v] = pa[v + 1024 k]
+    terms = (n - np.arange(lanes) + lanes - 1) // lanes            # terms of lane v
+    strided = 4 * (terms // 4)                                     # ... of which the strided loop takes these
+    acc = np.zeros((4, lanes))
+    for k in range(rows):
+        full = k < strided
+        acc[k % 4][full] += x[k][full]
+        tail = (k >= strided) & (k < terms)
+        acc[0][tail] += x[k][tail]
+    v = ((acc[0] + acc[1]) + (acc[2] + acc[3])).reshape(lanes // wave, wave)
+    off = wave // 2
+    while off > 0:
+        v = v + v[:, np.arange(wave) ^ off]
+        off //= 2
+    total = 0.0
+    for w in range(lanes // wave):
+        total += float(v[w, 0])
+    return total
+
+
+def fixed_sums_1024(pa, pb):
+    """(total of pa, total of pb) as ``fixed_sums_1024`` returns them: each by the tree of `fixed_sum_1024`."""
+    return fixed_sum_1024(pa), fixed_sum_1024(pb)
+
+
 # ---- smoothed-aggregation set-up (restates csrc/amg_setup.hip; scope row N3) -----------------------
 def _neighbour_max(g, values):
     """max over graph neighbours of `values` (0 for isolated nodes)."""

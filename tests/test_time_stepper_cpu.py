@@ -98,6 +98,28 @@ def test_two_entry_row_detection():
     assert not constants_in_kernel(sp.identity(4, format="csr"))
 
 
+SUM_LENGTHS = (0, 1, 63, 64, 65, 1023, 1024, 1025, 4095, 4096, 4097, 8193, 35000)
+
+
+@pytest.mark.parametrize("n", SUM_LENGTHS)
+def test_fixed_tree_restatement_against_fsum(n):
+    """oracle `fixed_sums_1024` -- the restatement of the device's summation tree that tests/test_step_kernels_gpu.py
+    compares bit for bit -- is a sum: against math.fsum to 1e-13 * sum |x| (the tree is at most 25 additions deep:
+    25 * 2^-53 = 3e-15), signed and non-negative terms, on both sides of every change of shape (one wave, one term
+    per lane, four per lane: the strided loop's first trip, a second trip, many)."""
+    from math import fsum
+    from oracle import krylov_ref as kr
+    rng = np.random.default_rng(100 + n)
+    x, y = rng.standard_normal(n), rng.random(n)
+    sx, sy = kr.fixed_sums_1024(x, y)
+    assert abs(sx - fsum(x)) <= 1e-13 * fsum(np.abs(x))
+    assert abs(sy - fsum(y)) <= 1e-13 * fsum(y)
+    assert kr.fixed_sums_1024(y, x) == (sy, sx)
+    assert (sy > 0.0) if n else (sx, sy) == (0.0, 0.0)
+    ints = np.arange(1, n + 1, dtype=np.float64)                  # exact in every order: n (n + 1) / 2
+    assert kr.fixed_sum_1024(ints) == n * (n + 1) / 2
+
+
 def test_advance_declines_on_the_checker_engine(numpy_engine):
     """Not the HIP engine: Advance runs DoTimeStep / the pseudo-time statements, reports why, and gives their results."""
     import hipla

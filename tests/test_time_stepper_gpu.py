@@ -114,6 +114,43 @@ def test_one_step_against_the_oracle(hip_engine, dim, inner_pre):
 
 
 @pytest.mark.parametrize("inner_pre", ["jacobi", "amg"])
+def test_one_step_with_non_uniform_mass(hip_engine, inner_pre):
+    """One `advance` of a `TimeStepper` made with a NON-uniform lumped mass m_u = h^2 (0.5 + random) -- the `mass`
+    operand of the projection launch, energy_scale = 0.5 -- against `kr.do_time_step` with the same m_u: the bounds of
+    test_one_step_against_the_oracle; kinetic_energy[0] = u . (m_u u) / 2 to 1e-12, visibly not h^2 |u|^2 / 2."""
+    from math import fsum
+    import hipla
+    from hipla.fused import TimeStepper
+    from staggered_grid import mac_stokes
+    s = mac_stokes(2, 14, 0.01)
+    rng = np.random.default_rng(14)
+    m_u = s.h ** 2 * (0.5 + rng.random(s.n_u))
+    f = np.random.default_rng(8).standard_normal(s.n_u)
+    A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
+    st = TimeStepper.try_create(s, A, B, hipla.Vector.from_numpy(f), 0.05, m_u, inner_pre=inner_pre)
+    assert st is not None and st.flux_declined is None, (TimeStepper.last_declined, st and st.flux_declined)
+    assert st.mass is not None and st.energy_scale == 0.5
+    assert np.array_equal(hip_engine.to_host(st.mass), m_u)
+    u0 = kr.project(s.B, m_u, np.random.default_rng(2).standard_normal(s.n_u))[0]
+    cops = s.convection_operators()
+    want = kr.do_time_step(s.A, s.B, m_u, 0.05, u0, f, lambda u: kr.upwind_convection(cops, u))
+    gfu, gfup = hipla.Vector.from_numpy(u0), hipla.Vector(s.n_p)
+    rec = st.advance(gfu, gfup, 1, **TIGHT)
+    u = gfu.numpy()
+    errs = (rel(hip_engine.to_host(st.temp), want["temp"]), rel(hip_engine.to_host(st.raw), want["temp2_unprojected"]),
+            rel(hip_engine.to_host(st.temp2), want["temp2"]), rel(u, want["u"]))
+    energy, unweighted = 0.5 * fsum(u * (m_u * u)), 0.5 * s.h ** 2 * fsum(u * u)
+    print(inner_pre, errs, rec.mstar_iterations, rec.proj_iterations, "energy", rec.kinetic_energy[0], energy, unweighted)
+    assert errs[0] < 1e-13
+    assert errs[1] < 1e-9
+    assert errs[2] < 1e-8
+    assert errs[3] < 1e-8
+    assert rec.mstar_iterations[0] < 5000 and rec.proj_iterations[0] < 20000
+    assert abs(rec.kinetic_energy[0] - energy) <= 1e-12 * energy
+    assert abs(unweighted - energy) > 1e-3 * energy
+
+
+@pytest.mark.parametrize("inner_pre", ["jacobi", "amg"])
 def test_default_precision(hip_engine, inner_pre):
     """With the reference's inner precision the step agrees with the oracle to 1e-4 and |B u| obeys the bound of
     test_time_stepping_on_gpu."""
