@@ -697,6 +697,32 @@ NSS_API int nss_step_record_f64(const double* partials_energy, int64_t n_energy,
                                 int64_t n_div, double scale, double* record, int32_t slot, const int32_t* done,
                                 nss_stream_t stream);
 
+/* ---- device-resident heat exponential integrator -------------------------------------------------
+ * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
+ * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:
+ * vector k is basis[k * ld .. k * ld + n) with an even plane stride ld >= n and a 16-byte aligned base, so that every
+ * vector is a contiguous operand of the CG loop and the SpMV.  All fp64, no atomics: sums are per-workgroup partials
+ * added by the fixed tree of the Krylov loops, on grids that depend on n alone -- the same bits every run.  `work`:
+ * device doubles, at least what nss_heat_workspace reports (work_cap = its capacity); no call synchronises.
+ *
+ * nss_mgs_f64: `tries` passes of modified Gram-Schmidt in the reference's order -- for column j and every i < j:
+ *   c = <b_i, b_j> / <b_i, b_i>, b_j -= c b_i; then b_j *= 1 / |b_j|.  A projection launch applies the previous pair's
+ *   update while it accumulates the next pair's two sums (b_j is read and written once per pair); every scalar stays on
+ *   the device.  norms (device, tries * d doubles): norms[t * d + j] = <b_j, b_j> of pass t BEFORE the normalisation
+ *   (norms[0] = |b_0|^2 of the input; a zero or non-finite entry tells a zero or rank-deficient basis).
+ * nss_galerkin_f64: g (device, d * d doubles, row-major) = V^T (M V) for the square CSR matrix M in one pass over its
+ *   rows: per row the d products w_k = sum_c M[r, c] V[c, k] from one read of the row, then g[a][k] += V[r, a] w_k.
+ *   Refuses a matrix with fp32 values (nss_csr_narrow_f32).
+ * nss_basis_combine_f64: y = sum_{i<d} h_coeff[i] V_i in one pass, evaluated left to right (nss_lincomb_f64 stops at
+ *   four terms); y (16-byte aligned) may be V_0. */
+NSS_API int nss_heat_workspace(int64_t n, int32_t d, int64_t* work_doubles);
+NSS_API int nss_mgs_f64(int64_t n, int32_t d, int64_t ld, double* basis, int32_t tries, double* norms, double* work,
+                        int64_t work_cap, nss_stream_t stream);
+NSS_API int nss_galerkin_f64(nss_csr_t m, int32_t d, int64_t ld, const double* basis, double* g, double* work,
+                             int64_t work_cap, nss_stream_t stream);
+NSS_API int nss_basis_combine_f64(int64_t n, int32_t d, int64_t ld, const double* basis, const double* h_coeff,
+                                  double* y, nss_stream_t stream);
+
 /* ---- device-resident preconditioned Lanczos: the scale factor k -------------------------------
  * Replaces the n-sized work AND the scalar recurrences of `EigenValues_Preconditioner(mat=A, pre=preA, tol=1e-3)`
  * (call sites bramble_pasciak_cg.py:68-74, solvers/bramblepasciak_new.py:111-122; the reference times it inside

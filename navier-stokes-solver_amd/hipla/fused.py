@@ -1042,3 +1042,110 @@ class TimeStepper(FusedLoop):
             return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined)
         host = eng.to_host(record).reshape(-1, 2)[:nsteps]               # the one read-back
         return StepRecord(its_m, its_p, host[:, 1].copy(), host[:, 0].copy(), flux_declined=self.flux_declined)
+
+
+class HeatRecord:
+    """What `heat.evolve` returns beside the temperature: `steps`; `cg_iterations[step, i]` = iterations of the i-th
+    inner solve of the step; `orthogonality[step]` = the largest entry of |V^T V - I| after the orthonormalisation (None
+    without ``diagnostics``); `declined`: why the statements ran through the protocol instead of the device-resident
+    step (None when it ran)."""
+
+    def __init__(self, cg_iterations, orthogonality, declined=None):
+        self.steps = len(cg_iterations)
+        self.cg_iterations = np.array([list(row) for row in cg_iterations], dtype=np.int64).reshape(self.steps, -1) \
+            if self.steps and len(cg_iterations[0]) else np.zeros((self.steps, 0), dtype=np.int64)
+        self.orthogonality = None if orthogonality is None else np.asarray(orthogonality, dtype=np.float64)
+        self.declined = declined
+
+
+class HeatIntegrator(FusedLoop):
+    """Device-resident step of the heat exponential integrator (``nss_mgs_f64`` / ``nss_galerkin_f64`` /
+    ``nss_basis_combine_f64`` around `CgLoop` solves): the statements of the reference's heat.py:87-142.
+
+    The basis lives in ONE buffer of d planes (plane k = vector k, stride `ld`); plane 0 holds the temperature between
+    steps.  Per step: d - 1 sub-steps (SpMV with K, CG from zero with ``M + time_step K``, one AXPY into the next plane),
+    the Gram-Schmidt chain, two Galerkin launches, ONE read-back of the norms and the two d x d matrices, the small
+    implicit Runge-Kutta step on the host, and one launch that combines the planes into plane 0 with the d coefficients
+    as kernel arguments.  Every buffer is allocated here, once; a step waits for the host in the polls of its solves and
+    in that read-back."""
+
+    TRIES = 3                 # orthonormalize(basis, tries=3)
+
+    @classmethod
+    def try_create(cls, K, M, heat, pre, dimension, diagnostics=False):
+        """`K`, `M`, `heat`: `SparseMatrix` (diffusion, mass, ``M + time_step K``); `pre`: the preconditioner of the inner
+        solves (a protocol operator).  Returns None with the reason in ``HeatIntegrator.last_declined``."""
+        return cls._decided(cls._try_create(K, M, heat, pre, dimension, diagnostics))
+
+    @classmethod
+    def _try_create(cls, K, M, heat, pre, dimension, diagnostics):
+        if not ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not all(isinstance(m, SparseMatrix) and m.height == m.width == K.height for m in (K, M, heat)):
+            return "K, M, heat are not square SparseMatrix operands of one size"
+        if not _hip(K.engine) or not hasattr(K.engine.lib, "nss_mgs_f64"):
+            return "not the HIP engine"
+        if not 1 <= dimension <= 8:
+            return "the subspace dimension is not in 1 .. 8"
+        pa = pre_for("cg", pre)
+        if pa is None or isinstance(pre, (ScaledMatrix, SumMatrix)):
+            return "the preconditioner is not native"
+        return cls(K, M, heat, pa, dimension, diagnostics)
+
+    def __init__(self, K, M, heat, pa, dimension, diagnostics):
+        eng = self.eng = K.engine
+        self.lib, self.K, self.M, self.heat = eng.lib, K, M, heat
+        n, d = K.height, int(dimension)
+        self.n, self.d = n, d
+        self.ld = -(-n // 32) * 32                           # planes start on 256-byte boundaries
+        self.basis = eng.zeros(d * self.ld)
+        self.planes = [eng.view(self.basis, k * self.ld, k * self.ld + n) for k in range(d)]
+        self.res, self.sol = eng.zeros(n), eng.zeros(n)
+        self.cg = CgLoop(eng, heat, pa)
+        self.eye = None
+        if diagnostics:
+            import scipy.sparse as sp
+            self.eye = SparseMatrix.from_scipy(sp.identity(n, format="csr"), engine=eng)
+        # what a step reads back: [norms (TRIES * d) | V^T K V | V^T M V | V^T V (diagnostics)]
+        self.out = eng.zeros(self.TRIES * d + (3 if diagnostics else 2) * d * d)
+        count = C.c_int64()
+        eng._check(self.lib.nss_heat_workspace(n, d, C.byref(count)))
+        self.work = eng.zeros(count.value)
+
+    def load(self, temperature):
+        self.eng.upload(np.asarray(temperature, dtype=np.float64), self.planes[0])
+
+    def temperature(self):
+        return self.eng.to_host(self.planes[0]).copy()
+
+    def _galerkin(self, mat, slot):
+        eng, d = self.eng, self.d
+        g = eng.view(self.out, self.TRIES * d + slot * d * d, self.TRIES * d + (slot + 1) * d * d)
+        eng._check(self.lib.nss_galerkin_f64(mat.handle.ptr, d, self.ld, self.basis.data_ptr(), g.data_ptr(),
+                                             self.work.data_ptr(), self.work.numel(), eng.stream))
+
+    def build_subspace(self, dt, precision, maxsteps):
+        """Planes 1 .. d - 1 from plane 0 (heat.py:95-98), the orthonormalisation (:100) and the Galerkin matrices
+        (:109-118).  Returns (CG iterations, norms[TRIES, d], V^T K V, V^T M V, V^T V or None) after the one read-back."""
+        eng, lib, d, planes = self.eng, self.lib, self.d, self.planes
+        its = []
+        for i in range(1, d):
+            eng.csr_spmv(self.K.handle, 1.0, planes[i - 1], 0.0, self.res)
+            its.append(self.cg.solve_resident(self.res, self.sol, precision, maxsteps))
+            eng.lincomb(planes[i], [(1.0, planes[i - 1]), (-dt, self.sol)])
+        eng._check(lib.nss_mgs_f64(self.n, d, self.ld, self.basis.data_ptr(), self.TRIES, self.out.data_ptr(),
+                                   self.work.data_ptr(), self.work.numel(), eng.stream))
+        self._galerkin(self.K, 0)
+        self._galerkin(self.M, 1)
+        if self.eye is not None:
+            self._galerkin(self.eye, 2)
+        host = eng.to_host(self.out)                                       # the one read-back
+        norms = host[:self.TRIES * d].reshape(self.TRIES, d)
+        mats = host[self.TRIES * d:].reshape(-1, d, d)
+        return its, norms, mats[0], mats[1], mats[2] if self.eye is not None else None
+
+    def combine(self, coefficients):
+        """plane 0 = sum_i coefficients[i] * plane i (heat.py:140-142)."""
+        coeff = (C.c_double * self.d)(*[float(c) for c in coefficients])
+        self.eng._check(self.lib.nss_basis_combine_f64(self.n, self.d, self.ld, self.basis.data_ptr(), coeff,
+                                                       self.planes[0].data_ptr(), self.eng.stream))

@@ -490,3 +490,14 @@ def diffusion_2d(n=64, dt=1e-3):
     m = m.tocsr()
     m.sort_indices()
     return m
+
+
+def diffusion_operators_2d(n=64):
+    """The two operators of `diffusion_2d` apart, in its scaling: ``(K, m)`` with K the 5-point diffusion matrix
+    ``T / h^2`` (CSR) and m the lumped mass diagonal (ones), so that ``diffusion_2d(n, dt) == diag(m) + dt * K`` entry
+    for entry (the operators of the heat integrator: heat.py:43-52 of the reference)."""
+    h = 1.0 / (n + 1)
+    t = sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(n, n))
+    k = ((sp.kron(sp.identity(n), t) + sp.kron(t, sp.identity(n))) / (h * h)).tocsr()
+    k.sort_indices()
+    return k, np.ones(n * n)
