@@ -168,10 +168,7 @@ struct EpiV3 {  // y += A x ; partial <d, y>
     y[r] = t;
     acc = fma(p.d, t, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
 struct EpiV5 {
@@ -190,10 +187,7 @@ struct EpiV5 {
     t1p[r] = t;
     acc = fma(t, p.rp, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
 constexpr int kPSum = 1024;
@@ -306,8 +300,7 @@ __global__ __launch_bounds__(kBlock) void bpcg1_v4_kernel(V4Args a) {
     a.rp[i] = fma(-alpha, ld1s<NT>(&a.t1p[i]), ld1s<NT>(&a.rp[i]));
     a.ap[i] = fma(-alpha, ld1s<NT>(&a.t2p[i]), ld1s<NT>(&a.ap[i]));
   }
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
+  store_block_partial(acc, blockIdx.x, a.partials, lds);
 }
 
 // fold: rho_new = sum(pc) + sum(pb), beta = rho_new / rho evaluated by every workgroup; workgroup 0 records them and
@@ -341,9 +334,6 @@ __global__ __launch_bounds__(kBlock) void bpcg1_v6_kernel(const int32_t* __restr
 
 static int p_grid(const nss_bpcg1_t& s) { return stream_grid(int64_t(s.n_u) + s.n_p, kBlock * 4); }
 
-static PreA pre_a_of(const nss_bpcg1_t& s) {
-  return PreA{.n = s.n_u, .ncols = s.n_u, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A};
-}
 static void bpcg1_check(const nss_bpcg1_t* s) {
   NSS_REQUIRE(s != nullptr, "bpcg1: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "bpcg1: NULL matrix handle");
@@ -353,7 +343,7 @@ static void bpcg1_check(const nss_bpcg1_t* s) {
   else
     NSS_REQUIRE(s->A->n == s->n_u && s->B->n == s->n_u && s->BT->n == s->n_p, "bpcg1: matrix columns do not match");
   NSS_REQUIRE(!(s->local_sums && s->pre_amg), "bpcg1: the row-partitioned loop takes a (block) Jacobi preconditioner");
-  pre_a_check(pre_a_of(*s), "bpcg1", kPreAAdditiveOnly);
+  pre_a_check(pre_a_of(*s, s->n_u), "bpcg1", kPreAAdditiveOnly);
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "bpcg1: NULL work buffer");
   for (int c = 0; c < 2; ++c)
@@ -441,7 +431,7 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
     launch_csr_stream(*s.BT, s.d[1], EpiV1b{s.ctrl, s.t1[0], s.t2[0], s.pre_amg ? nullptr : s.pre_diag, s.k}, st);
     }
     // t2 = -k preA t1 (t1 holds -K u here) where no epilogue above has formed it (point / fused block Jacobi alone)
-    if (s.pre_amg || (s.pre_bjac && !fused_j)) pre_a_apply(pre_a_of(s), -s.k, s.t1[0], s.t2[0], nullptr, s.ctrl, st);
+    if (s.pre_amg || (s.pre_bjac && !fused_j)) pre_a_apply(pre_a_of(s, s.n_u), -s.k, s.t1[0], s.t2[0], nullptr, s.ctrl, st);
   }
   if (on(2)) {
     if (dist) exchange(*dist->d, halo_of(dist->hu, s.t2[0]), st);
@@ -530,8 +520,7 @@ int nss_bpcg1_iterate_dist(const nss_bpcg1_t* s, nss_dist_t d, const nss_halo_t*
 
 int nss_bpcg1_fold_mode(int32_t mode) {
   return guarded([&] {
-    NSS_REQUIRE(mode >= -1 && mode <= 1, "bpcg1_fold_mode: -1 (by size), 0 (never) or 1 (whenever B^T has a fixed-width copy)");
-    g_bpcg1_fold_mode = mode;
+    set_mode(g_bpcg1_fold_mode, mode, -1, 1, "bpcg1_fold_mode: -1 (by size), 0 (never) or 1 (whenever B^T has a fixed-width copy)");
   });
 }
 
@@ -539,8 +528,7 @@ int nss_bpcg1_poll(const nss_bpcg1_t* s, int32_t* stop, int32_t* it_stop, int32_
   return guarded([&] {
     NSS_REQUIRE(s && s->ctrl, "bpcg1_poll: NULL state");
     int32_t h[4] = {0, 0, 0, 0};
-    NSS_HIP(hipMemcpyAsync(h, s->ctrl, sizeof h, hipMemcpyDeviceToHost, as_stream(stream)));
-    NSS_HIP(hipStreamSynchronize(as_stream(stream)));
+    poll_ctrl(s->ctrl, as_stream(stream), h);
     if (stop) *stop = h[PC_STOP];
     if (it_stop) *it_stop = h[PC_ITSTOP];
     if (last_it) *last_it = h[PC_LAST];

@@ -1,5 +1,6 @@
 #pragma once
 
+#include "loop_parts.h"
 #include "pre_a.h"
 
 struct nss_dist_s;

@@ -127,8 +127,7 @@ struct EpiK2 {
     acc = fma(p.s0, at1 - p.t0, acc);
   }
   __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
+    store_block_partial(acc, b, partials, lds);
     // ghost_n > 0 only in a launch that is ordered after the arrival of t1's ghosts
     const int stride = gridDim.x * kBlock;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < ghost_n; i += stride) ghost_t4[i] = t1[ghost_map[i]] - ghost_s0[i];
@@ -277,10 +276,7 @@ struct EpiK3 {
     NSS_ST2(t3[r], bt4);
     acc = fma(p.s1, bt4, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
 // local sum of the partials of K2 and K3 (or of K4 when nb == 0) into scal[slot]: one workgroup,
@@ -451,8 +447,7 @@ __global__ __launch_bounds__(kBlock) void bpcg2_k4_kernel(K4Args a) {
       a.ghost_w1[i] = fma(-alpha, a.ghost_minv[i] * a.ghost_t3[i], a.ghost_w1[i]);
     return;
   }
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) a.partials[wg] = s;
+  store_block_partial(acc, wg, a.partials, lds);
 }
 
 // K5: beta = wdn / wd (:236) by every lane; lane 0 of workgroup 0 also keeps the books: history
@@ -687,10 +682,7 @@ struct EpiK2c {
     NSS_ST(t2[r], at1);
     acc = fma(p.s0, at1 - p.t0, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
 // C23, rows of B: K3 multiplying with t4 = t1 - s0 formed on the fly (:212-213) and storing
@@ -736,10 +728,7 @@ struct EpiK3c {
     NSS_ST2(t3[r], bt4);
     if (r < n_own) acc = fma(sv, bt4, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
 static int k4_gu(const nss_bpcg2_t& s) { return (s.n_u + kK4PerBlock - 1) / kK4PerBlock; }
@@ -1149,8 +1138,7 @@ int nss_bpcg2_cphases(const nss_bpcg2_t* s, int32_t first, int32_t last, int32_t
 
 int nss_bpcg2_fuse_block_jacobi(int32_t mode) {
   return guarded([&] {
-    NSS_REQUIRE(mode >= -1 && mode <= 1, "bpcg2_fuse_block_jacobi: -1 (by size), 0 (never) or 1 (whenever B^T is planned for it)");
-    g_fuse_bjac = mode;
+    set_mode(g_fuse_bjac, mode, -1, 1, "bpcg2_fuse_block_jacobi: -1 (by size), 0 (never) or 1 (whenever B^T is planned for it)");
   });
 }
 
@@ -1163,15 +1151,13 @@ int nss_bpcg2_c1_applies_preA(const nss_bpcg2_t* s, int32_t* yes) {
 
 int nss_cond_fuse_mode(int32_t mode) {
   return guarded([&] {
-    NSS_REQUIRE(mode == 0 || mode == 1, "cond_fuse_mode: 0 (straightforward sequence) or 1 (fused condensed forms)");
-    g_cond_fuse_mode = mode;
+    set_mode(g_cond_fuse_mode, mode, 0, 1, "cond_fuse_mode: 0 (straightforward sequence) or 1 (fused condensed forms)");
   });
 }
 
 int nss_bpcg2_fold_mode(int32_t mode) {
   return guarded([&] {
-    NSS_REQUIRE(mode >= -1 && mode <= 1, "bpcg2_fold_mode: -1 (automatic), 0 (never) or 1 (always)");
-    g_fold_mode = mode;
+    set_mode(g_fold_mode, mode, -1, 1, "bpcg2_fold_mode: -1 (automatic), 0 (never) or 1 (always)");
   });
 }
 
@@ -1198,8 +1184,7 @@ int nss_bpcg2_poll(const nss_bpcg2_t* s, int32_t* done, int32_t* it_final, int32
       NSS_CHECK_LAUNCH();
     }
     int32_t h[4] = {0, 0, 0, 0};
-    NSS_HIP(hipMemcpyAsync(h, s->ctrl, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, as_stream(stream)));
-    NSS_HIP(hipStreamSynchronize(as_stream(stream)));
+    poll_ctrl(s->ctrl, as_stream(stream), h);
     // 2: alpha = wd / 0 breakdown; 3: a peer of the mailbox transport did not arrive in time
     if (done) *done = h[C_DONE] ? (h[C_BREAKDOWN] == 3 ? 3 : (h[C_BREAKDOWN] ? 2 : 1)) : 0;
     if (it_final) *it_final = h[C_IT_FINAL];

@@ -28,31 +28,16 @@ struct EpiCgQ {
     q[r] = ap;
     acc = fma(pre.p, ap, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
-constexpr int kCgSum = 1024;
-__global__ __launch_bounds__(kCgSum) void cg_sum_kernel(const int32_t* __restrict__ ctrl, int n,
-                                                         const double* __restrict__ part, double* __restrict__ scal,
-                                                         int slot) {
-  __shared__ double lds[kCgSum / kWave];
+__global__ __launch_bounds__(kLoopSum) void cg_sum_kernel(const int32_t* __restrict__ ctrl, int n,
+                                                          const double* __restrict__ part, double* __restrict__ scal,
+                                                          int slot) {
+  __shared__ double lds[kLoopSum / kWave];
   if (ctrl[GC_DONE] != 0) return;
-  double a = 0.0, a2 = 0.0;
-  int i = threadIdx.x;
-  for (; i + kCgSum < n; i += 2 * kCgSum) {
-    a += part[i];
-    a2 += part[i + kCgSum];
-  }
-  for (; i < n; i += kCgSum) a += part[i];
-  const double s = wave_sum(a + a2);
-  if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
+  const double t = sum_partials_1024(part, n, lds);
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < kCgSum / kWave; ++w) t += lds[w];
     scal[slot] = t;
   }
 }
@@ -84,22 +69,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(CgArgs a, int fused_p
       acc = fma(rn, zn, acc);
     }
   }
-  if (fused_pre) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void cg_dot_kernel(const int32_t* __restrict__ ctrl, int32_t n,
-                                                         const double* __restrict__ x, const double* __restrict__ y,
-                                                         double* __restrict__ partials) {
-  __shared__ double lds[kBlock / kWave];
-  if (ctrl[GC_DONE] != 0) return;
-  const int stride = gridDim.x * kBlock;
-  double acc = 0.0;
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) acc = fma(x[i], y[i], acc);
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+  if (fused_pre) store_block_partial(acc, blockIdx.x, a.partials, lds);
 }
 
 // p = z + beta p; one lane: history, stop test, rz of the next iteration
@@ -138,10 +108,7 @@ __global__ __launch_bounds__(kBlock) void cg_start_kernel(CgArgs a, const double
       acc = fma(rn, zn, acc);
     }
   }
-  if (fused_pre) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
-  }
+  if (fused_pre) store_block_partial(acc, blockIdx.x, a.partials, lds);
 }
 
 // p = z and the partials of <r, z> behind a preconditioner that is a launch of its own
@@ -154,29 +121,17 @@ __global__ __launch_bounds__(kBlock) void cg_start_direction_kernel(CgArgs a) {
     a.p[i] = zn;
     acc = fma(a.r[i], zn, acc);
   }
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
+  store_block_partial(acc, blockIdx.x, a.partials, lds);
 }
 
-// rz = the sum (the tree of cg_sum_kernel), err0, tol and a cleared control word; a zero right-hand side ends the solve
+// rz = the sum, err0, tol and a cleared control word; a zero right-hand side ends the solve
 // before its first iteration (done, it_final = -1: no iterations)
-__global__ __launch_bounds__(kCgSum) void cg_start_sum_kernel(int32_t* __restrict__ ctrl, int n,
-                                                               const double* __restrict__ part, double* __restrict__ scal,
-                                                               double tol) {
-  __shared__ double lds[kCgSum / kWave];
-  double a = 0.0, a2 = 0.0;
-  int i = threadIdx.x;
-  for (; i + kCgSum < n; i += 2 * kCgSum) {
-    a += part[i];
-    a2 += part[i + kCgSum];
-  }
-  for (; i < n; i += kCgSum) a += part[i];
-  const double s = wave_sum(a + a2);
-  if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
+__global__ __launch_bounds__(kLoopSum) void cg_start_sum_kernel(int32_t* __restrict__ ctrl, int n,
+                                                                const double* __restrict__ part, double* __restrict__ scal,
+                                                                double tol) {
+  __shared__ double lds[kLoopSum / kWave];
+  const double t = sum_partials_1024(part, n, lds);
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < kCgSum / kWave; ++w) t += lds[w];
     const double err0 = sqrt(fabs(t));
     scal[G_RZ] = t;
     scal[G_PQ] = 0.0;
@@ -192,13 +147,10 @@ __global__ __launch_bounds__(kCgSum) void cg_start_sum_kernel(int32_t* __restric
 
 static int cg_grid(const nss_cg_t& s) { return stream_grid(s.n, kBlock * 4); }
 
-static PreA pre_a_of(const nss_cg_t& s) {
-  return PreA{.n = s.n, .ncols = s.n, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A};
-}
 static void cg_check(const nss_cg_t* s) {
   NSS_REQUIRE(s != nullptr && s->A != nullptr, "cg: NULL state / matrix");
   NSS_REQUIRE(s->A->m == s->n && s->A->n == s->n, "cg: matrix does not match n");
-  pre_a_check(pre_a_of(*s), "cg", kPreAOnePartAtMost);
+  pre_a_check(pre_a_of(*s, s->n), "cg", kPreAOnePartAtMost);
   NSS_REQUIRE(s->x && s->r && s->z && s->p && s->q && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b,
               "cg: NULL buffer");
   const int64_t need[2] = {s->A->nblk, std::max<int64_t>(cg_grid(*s), s->pre_bjac ? bjac_dot_grid(*s->pre_bjac) : 0)};
@@ -208,7 +160,7 @@ static void cg_check(const nss_cg_t* s) {
 
 static void cg_iteration(const nss_cg_t& s, int it, hipStream_t st) {
   launch_csr_stream(*s.A, s.p, EpiCgQ{s.ctrl, s.p, s.q, s.partials_a}, st);
-  hipLaunchKernelGGL(cg_sum_kernel, dim3(1), dim3(kCgSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal, int(G_PQ));
+  hipLaunchKernelGGL(cg_sum_kernel, dim3(1), dim3(kLoopSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal, int(G_PQ));
   NSS_CHECK_LAUNCH();
   const bool fused_pre = !s.pre_bjac && !s.pre_amg;
   CgArgs a{s.ctrl, s.scal, s.hist, s.n, it, s.x, s.r, s.z, s.p, s.q, s.pre_diag, s.partials_b};
@@ -219,12 +171,11 @@ static void cg_iteration(const nss_cg_t& s, int it, hipStream_t st) {
     if (s.pre_bjac && !s.pre_bjac->gs_mat) {   // block Jacobi: <r, z> comes out of the apply kernel
       nb = bjac_apply_dot(*s.pre_bjac, 1.0, s.r, s.z, s.partials_b, s.ctrl, st);
     } else {
-      pre_a_apply(pre_a_of(s), 1.0, s.r, s.z, nullptr, s.ctrl, st);   // Gauss-Seidel sweep as an operator, or V-cycle
-      hipLaunchKernelGGL(cg_dot_kernel, dim3(nb), dim3(kBlock), 0, st, s.ctrl, s.n, s.r, s.z, s.partials_b);
-      NSS_CHECK_LAUNCH();
+      pre_a_apply(pre_a_of(s, s.n), 1.0, s.r, s.z, nullptr, s.ctrl, st);   // Gauss-Seidel sweep as an operator, or V-cycle
+      launch_dot_partials(StopWord{s.ctrl, GC_DONE}, nb, s.n, s.r, s.z, s.partials_b, st);
     }
   }
-  hipLaunchKernelGGL(cg_sum_kernel, dim3(1), dim3(kCgSum), 0, st, s.ctrl, nb, s.partials_b, s.scal, int(G_RZN));
+  hipLaunchKernelGGL(cg_sum_kernel, dim3(1), dim3(kLoopSum), 0, st, s.ctrl, nb, s.partials_b, s.scal, int(G_RZN));
   NSS_CHECK_LAUNCH();
   hipLaunchKernelGGL(cg_direction_kernel, dim3(cg_grid(s)), dim3(kBlock), 0, st, a);
   NSS_CHECK_LAUNCH();
@@ -255,11 +206,11 @@ int nss_cg_start(const nss_cg_t* s, const double* b, double tol, nss_stream_t st
     hipLaunchKernelGGL(cg_start_kernel, dim3(nb), dim3(kBlock), 0, st, a, b, fused_pre ? 1 : 0);
     NSS_CHECK_LAUNCH();
     if (!fused_pre) {
-      pre_a_apply(pre_a_of(*s), 1.0, s->r, s->z, nullptr, nullptr, st);
+      pre_a_apply(pre_a_of(*s, s->n), 1.0, s->r, s->z, nullptr, nullptr, st);
       hipLaunchKernelGGL(cg_start_direction_kernel, dim3(nb), dim3(kBlock), 0, st, a);
       NSS_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(cg_start_sum_kernel, dim3(1), dim3(kCgSum), 0, st, s->ctrl, nb, s->partials_b, s->scal, tol);
+    hipLaunchKernelGGL(cg_start_sum_kernel, dim3(1), dim3(kLoopSum), 0, st, s->ctrl, nb, s->partials_b, s->scal, tol);
     NSS_CHECK_LAUNCH();
   });
 }
@@ -275,8 +226,7 @@ int nss_cg_poll(const nss_cg_t* s, int32_t* done, int32_t* it_final, int32_t* la
   return guarded([&] {
     NSS_REQUIRE(s && s->ctrl, "cg_poll: NULL state");
     int32_t h[4] = {0, 0, 0, 0};
-    NSS_HIP(hipMemcpyAsync(h, s->ctrl, sizeof h, hipMemcpyDeviceToHost, as_stream(stream)));
-    NSS_HIP(hipStreamSynchronize(as_stream(stream)));
+    poll_ctrl(s->ctrl, as_stream(stream), h);
     if (done) *done = h[GC_DONE];
     if (it_final) *it_final = h[GC_ITFINAL];
     if (last_it) *last_it = h[GC_LAST];

@@ -21,6 +21,7 @@
 // All fp64, no atomics: every sum is per-workgroup partials added in a fixed order (fixed_sums_1024), the grids depend
 // on n alone -- the same bits every run.
 #include "csr_stream.h"
+#include "loop_parts.h"
 
 namespace nss {
 
@@ -87,12 +88,8 @@ __global__ __launch_bounds__(kBlock) void mgs_kernel(int64_t n, double* bj, cons
     }
   }
   if constexpr (ACC != 0) {
-    const double a = block_sum(acc_a, lds);
-    if (threadIdx.x == 0) pa_out[blockIdx.x] = a;
-    if constexpr (ACC == 1) {
-      const double b = block_sum(acc_b, lds);
-      if (threadIdx.x == 0) pb_out[blockIdx.x] = b;
-    }
+    store_block_partial(acc_a, blockIdx.x, pa_out, lds);
+    if constexpr (ACC == 1) store_block_partial(acc_b, blockIdx.x, pb_out, lds);
   }
 }
 

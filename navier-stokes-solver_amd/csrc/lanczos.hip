@@ -45,34 +45,19 @@ struct EpiLanczosP {
     p[r] = az;
     acc = fma(az, pre.z, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
-constexpr int kLzSum = 1024;
 // scal[slot] = sum of the partials; MODE 1: the books of step j (gamma_{j+1}, history entry, breakdown test);
 // MODE 2: the start (gamma_0 = sqrt|sum|; 0 stops everything: the operator annihilates the start vector)
 template <int MODE>
-__global__ __launch_bounds__(kLzSum) void lanczos_sum_kernel(int32_t* __restrict__ ctrl, int n, const double* __restrict__ part,
-                                                              double* __restrict__ scal, int slot, int j,
-                                                              double* __restrict__ hist) {
-  __shared__ double lds[kLzSum / kWave];
+__global__ __launch_bounds__(kLoopSum) void lanczos_sum_kernel(int32_t* __restrict__ ctrl, int n, const double* __restrict__ part,
+                                                               double* __restrict__ scal, int slot, int j,
+                                                               double* __restrict__ hist) {
+  __shared__ double lds[kLoopSum / kWave];
   if (ctrl[LC_STOP] != 0) return;
-  double a = 0.0, a2 = 0.0;
-  int i = threadIdx.x;
-  for (; i + kLzSum < n; i += 2 * kLzSum) {
-    a += part[i];
-    a2 += part[i + kLzSum];
-  }
-  for (; i < n; i += kLzSum) a += part[i];
-  const double s = wave_sum(a + a2);
-  if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
+  const double t = sum_partials_1024(part, n, lds);
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < kLzSum / kWave; ++w) t += lds[w];
     scal[slot] = t;
     if (MODE == 2) {
       const double gamma0 = sqrt(fabs(t));
@@ -132,22 +117,7 @@ __global__ __launch_bounds__(kBlock) void lanczos_combine_kernel(LzArgs a, int f
       acc = fma(zn, r, acc);
     }
   }
-  if (fused_pre) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void lanczos_dot_kernel(const int32_t* __restrict__ ctrl, int32_t n,
-                                                              const double* __restrict__ x, const double* __restrict__ y,
-                                                              double* __restrict__ partials) {
-  __shared__ double lds[kBlock / kWave];
-  if (ctrl[LC_STOP] != 0) return;
-  const int stride = gridDim.x * kBlock;
-  double acc = 0.0;
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) acc = fma(x[i], y[i], acc);
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+  if (fused_pre) store_block_partial(acc, blockIdx.x, a.partials, lds);
 }
 
 __global__ __launch_bounds__(kBlock) void lanczos_scale_kernel(const int32_t* __restrict__ ctrl, int32_t n, double a,
@@ -296,8 +266,7 @@ __global__ __launch_bounds__(kBlock) void lanczos_fused_kernel(LzFusedArgs a) {
       }
     }
   }
-  const double part = block_sum(acc, lds);
-  if (threadIdx.x == 0) a.pout[blockIdx.x] = part;
+  store_block_partial(acc, blockIdx.x, a.pout, lds);
 }
 
 constexpr int kLzFoldMax = 1024;      // partials per sum up to which every workgroup redoes the sum (as kFoldMax, bpcg2.hip)
@@ -319,8 +288,9 @@ static bool lz_fold_a(const nss_lanczos_t& s) { return g_lanczos_fold_mode == 1 
 static int64_t lz_partials_b(const nss_lanczos_t& s);
 
 static PreA pre_a_of(const nss_lanczos_t& s) {
-  return PreA{.n = s.n, .ncols = s.n, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A,
-              .sweep_A = s.sweep_A};
+  PreA p = pre_a_of(s, s.n);
+  p.sweep_A = s.sweep_A;
+  return p;
 }
 static void lz_check(const nss_lanczos_t* s) {
   NSS_REQUIRE(s != nullptr && s->A != nullptr, "lanczos: NULL state / matrix");
@@ -349,8 +319,7 @@ static int lz_precondition(const nss_lanczos_t& s, const double* x, double* z, d
     NSS_CHECK_LAUNCH();
   }
   const int nb = lz_grid(s);
-  hipLaunchKernelGGL(lanczos_dot_kernel, dim3(nb), dim3(kBlock), 0, st, done, s.n, z, x, s.partials_b);
-  NSS_CHECK_LAUNCH();
+  launch_dot_partials(StopWord{done, LC_STOP}, nb, s.n, z, x, s.partials_b, st);
   return nb;
 }
 
@@ -370,7 +339,7 @@ static void lz_step(const nss_lanczos_t& s, int j, bool last, hipStream_t st) {
   if (lz_fused(s)) {
     const bool fold_a = lz_fold_a(s);
     if (!fold_a) {
-      hipLaunchKernelGGL((lanczos_sum_kernel<0>), dim3(1), dim3(kLzSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal,
+      hipLaunchKernelGGL((lanczos_sum_kernel<0>), dim3(1), dim3(kLoopSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal,
                          int(L_DH), j, s.hist);
       NSS_CHECK_LAUNCH();
     }
@@ -391,7 +360,7 @@ static void lz_step(const nss_lanczos_t& s, int j, bool last, hipStream_t st) {
     }
     return;
   }
-  hipLaunchKernelGGL((lanczos_sum_kernel<0>), dim3(1), dim3(kLzSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal,
+  hipLaunchKernelGGL((lanczos_sum_kernel<0>), dim3(1), dim3(kLoopSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal,
                      int(L_DH), j, s.hist);
   NSS_CHECK_LAUNCH();
   const bool fused_pre = s.pre_diag && !s.pre_amg;
@@ -399,7 +368,7 @@ static void lz_step(const nss_lanczos_t& s, int j, bool last, hipStream_t st) {
   hipLaunchKernelGGL(lanczos_combine_kernel, dim3(lz_grid(s)), dim3(kBlock), 0, st, a, fused_pre ? 1 : 0);
   NSS_CHECK_LAUNCH();
   const int nb = fused_pre ? lz_grid(s) : lz_precondition(s, v_new, z_new, s.p, st);    // (p is free from here on)
-  hipLaunchKernelGGL((lanczos_sum_kernel<1>), dim3(1), dim3(kLzSum), 0, st, s.ctrl, nb, s.partials_b, s.scal,
+  hipLaunchKernelGGL((lanczos_sum_kernel<1>), dim3(1), dim3(kLoopSum), 0, st, s.ctrl, nb, s.partials_b, s.scal,
                      int(L_G2), j, s.hist);
   NSS_CHECK_LAUNCH();
 }
@@ -552,12 +521,11 @@ int nss_lanczos_start(const nss_lanczos_t* s, nss_stream_t stream) {
     if (s->pre_diag && !s->pre_amg) {
       diag_apply(s->n, s->pre_diag, s->pre_scale, s->v[0], 0.0, s->z[0], nullptr, st);
       nb = lz_grid(*s);
-      hipLaunchKernelGGL(lanczos_dot_kernel, dim3(nb), dim3(kBlock), 0, st, s->ctrl, s->n, s->z[0], s->v[0], s->partials_b);
-      NSS_CHECK_LAUNCH();
+      launch_dot_partials(StopWord{s->ctrl, LC_STOP}, nb, s->n, s->z[0], s->v[0], s->partials_b, st);
     } else {
       nb = lz_precondition(*s, s->v[0], s->z[0], s->p, st);
     }
-    hipLaunchKernelGGL((lanczos_sum_kernel<2>), dim3(1), dim3(kLzSum), 0, st, s->ctrl, nb, s->partials_b, s->scal,
+    hipLaunchKernelGGL((lanczos_sum_kernel<2>), dim3(1), dim3(kLoopSum), 0, st, s->ctrl, nb, s->partials_b, s->scal,
                        int(L_G2), 0, s->hist);
     NSS_CHECK_LAUNCH();
   });
@@ -582,8 +550,7 @@ int nss_lanczos_start_values(int64_t offset, int64_t n, double* out, nss_stream_
 
 int nss_lanczos_fold_mode(int32_t mode) {
   return guarded([&] {
-    NSS_REQUIRE(mode >= -1 && mode <= 1, "lanczos_fold_mode: -1 (by size), 0 (never) or 1 (whenever the operands allow)");
-    g_lanczos_fold_mode = mode;
+    set_mode(g_lanczos_fold_mode, mode, -1, 1, "lanczos_fold_mode: -1 (by size), 0 (never) or 1 (whenever the operands allow)");
   });
 }
 
@@ -591,8 +558,7 @@ int nss_lanczos_poll(const nss_lanczos_t* s, int32_t* stop, int32_t* j_stop, int
   return guarded([&] {
     NSS_REQUIRE(s && s->ctrl, "lanczos_poll: NULL state");
     int32_t h[4] = {0, 0, 0, 0};
-    NSS_HIP(hipMemcpyAsync(h, s->ctrl, sizeof h, hipMemcpyDeviceToHost, as_stream(stream)));
-    NSS_HIP(hipStreamSynchronize(as_stream(stream)));
+    poll_ctrl(s->ctrl, as_stream(stream), h);
     if (stop) *stop = h[LC_STOP];
     if (j_stop) *j_stop = h[LC_JSTOP];
     if (last_j) *last_j = h[LC_LAST];

@@ -100,10 +100,7 @@ struct EpiMAccDot {  // y (+)= A (scale * x) ; partial <y, scale * z>
     y[r] = t;
     acc = fma(t, p.z * sz, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
 // rows of A with the row of B^T z1 added in the epilogue: kz0 = B^T (sz z1) + A (sz z0), partial <kz0, sz z0>.
@@ -143,10 +140,7 @@ struct EpiMRowsA {
     y[r] = t;
     acc = fma(t, p.z * sz, acc);
   }
-  __device__ void finish(int b, double* lds) {
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
-  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
 
 constexpr int kMScal = 32;          // doubles per scalar set; set of iteration k at scal + ((k - 1) & 1) * kMScal
@@ -297,23 +291,15 @@ __global__ __launch_bounds__(kBlock) void minres_m3_kernel(MK4Args a) {
       }
     }
   }
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) a.partials[wg] = s;
+  store_block_partial(acc, wg, a.partials, lds);
 }
 
-// partial <x, y> of the velocity block after a preconditioner apply that is not fused
-__global__ __launch_bounds__(kBlock) void minres_dot_kernel(const int32_t* __restrict__ ctrl, int k, int32_t n,
-                                                             const double* __restrict__ x,
-                                                             const double* __restrict__ y,
-                                                             double* __restrict__ partials) {
-  __shared__ double lds[kRedDoubles];
-  if (minres_skip(ctrl, k)) return;
-  const int stride = gridDim.x * kBlock;
-  double acc = 0.0;
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) acc = fma(x[i], y[i], acc);
-  const double s = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
+// the stop test of dot_partials_kernel: <z_new, v_new> of the velocity block after a preconditioner apply that is not fused
+struct MinresSkip {
+  const int32_t* __restrict__ ctrl;
+  int k;
+  __device__ bool operator()() const { return minres_skip(ctrl, k); }
+};
 
 struct MK5Args {
   int32_t* ctrl;
@@ -475,9 +461,6 @@ static void minres_need(const nss_minres_t& s, int64_t* need) {
   need[2] = std::max<int64_t>(gu_fused, m_gu(s)) + m_gp(s);
 }
 
-static PreA pre_a_of(const nss_minres_t& s) {
-  return PreA{.n = s.n_u, .ncols = s.n_u, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A};
-}
 static void minres_check(const nss_minres_t* s) {
   NSS_REQUIRE(s != nullptr, "minres: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "minres: NULL matrix handle");
@@ -486,7 +469,7 @@ static void minres_check(const nss_minres_t* s) {
     NSS_REQUIRE(s->A->n >= s->n_u && s->B->n >= s->n_u && s->BT->n >= s->n_p, "minres: local matrix narrower than the slab");
   else
     NSS_REQUIRE(s->A->n == s->n_u && s->B->n == s->n_u && s->BT->n == s->n_p, "minres: matrix columns do not match n_u/n_p");
-  pre_a_check(pre_a_of(*s), "minres", kPreAAdditiveOnly);
+  pre_a_check(pre_a_of(*s, s->n_u), "minres", kPreAAdditiveOnly);
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "minres: NULL work buffer");
   for (int c = 0; c < 2; ++c) {
@@ -588,12 +571,10 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
     // touch ring slots nobody reads any more
     {
     if (dot_in_apply) nb2 = bjac_apply_dot(*s.pre_bjac, 1.0, s.v[in][0], s.z[zn][0], s.partials_a, nullptr, st);
-    else pre_a_apply(pre_a_of(s), 1.0, s.v[in][0], s.z[zn][0], nullptr, nullptr, st);
+    else pre_a_apply(pre_a_of(s, s.n_u), 1.0, s.v[in][0], s.z[zn][0], nullptr, nullptr, st);
     if (nb2 == 0) {
       nb2 = m_dot_grid(s);
-      hipLaunchKernelGGL(minres_dot_kernel, dim3(nb2), dim3(kBlock), 0, st, s.ctrl, k, s.n_u, s.z[zn][0], s.v[in][0],
-                         s.partials_a);
-      NSS_CHECK_LAUNCH();
+      launch_dot_partials(MinresSkip{s.ctrl, k}, nb2, s.n_u, s.z[zn][0], s.v[in][0], s.partials_a, st);
     }
     }
   }
@@ -666,15 +647,13 @@ int nss_minres_iterate_dist(const nss_minres_t* s, nss_dist_t d, const nss_halo_
 
 int nss_minres_fold_mode(int32_t mode) {
   return guarded([&] {
-    NSS_REQUIRE(mode >= -1 && mode <= 1, "minres_fold_mode: -1 (automatic), 0 (never) or 1 (always)");
-    g_minres_fold_mode = mode;
+    set_mode(g_minres_fold_mode, mode, -1, 1, "minres_fold_mode: -1 (automatic), 0 (never) or 1 (always)");
   });
 }
 
 int nss_minres_fuse_mode(int32_t mode) {
   return guarded([&] {
-    NSS_REQUIRE(mode >= -1 && mode <= 2, "minres_fuse_mode: -1 (automatic), 0 (never), 1 (always) or 2 (merged rows only)");
-    g_minres_fuse_mode = mode;
+    set_mode(g_minres_fuse_mode, mode, -1, 2, "minres_fuse_mode: -1 (automatic), 0 (never), 1 (always) or 2 (merged rows only)");
   });
 }
 
@@ -683,8 +662,7 @@ int nss_minres_poll(const nss_minres_t* s, int32_t* stop, int32_t* k_stop, int32
   return guarded([&] {
     NSS_REQUIRE(s && s->ctrl, "minres_poll: NULL state");
     int32_t h[4] = {0, 0, 0, 0};
-    NSS_HIP(hipMemcpyAsync(h, s->ctrl, sizeof h, hipMemcpyDeviceToHost, as_stream(stream)));
-    NSS_HIP(hipStreamSynchronize(as_stream(stream)));
+    poll_ctrl(s->ctrl, as_stream(stream), h);
     if (stop) *stop = h[MC_STOP];
     if (k_stop) *k_stop = h[MC_KSTOP];
     if (reason) *reason = h[MC_REASON];

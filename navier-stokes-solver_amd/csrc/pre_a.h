@@ -10,7 +10,7 @@ struct nss_dist_aux_s;
 
 namespace nss {
 
-// A view of a loop state's preconditioner fields, built on the stack (pre_a_of next to each loop's check); owns nothing.
+// A view of a loop state's preconditioner fields, built on the stack (pre_a_of); owns nothing.
 struct PreA {
   int64_t n = 0;                              // velocity rows
   int64_t ncols = 0;                          // columns of A's operand (slabs: [owned | ghosts]; else n)
@@ -27,6 +27,13 @@ struct PreA {
   bool multiplicative() const { return (amg || dist_aux) && bjac && bjac->gs_mat; }
   const nss_csr_s& residual_A() const { return sweep_A ? *sweep_A : *A; }
 };
+
+// the view of a loop state that names its fields pre_diag, pre_bjac, pre_amg and A, with `n` velocity rows (cg, minres,
+// bpcg1; lanczos adds its sweep_A; bpcg2 lists its slab fields itself)
+template <class State>
+PreA pre_a_of(const State& s, int64_t n) {
+  return PreA{.n = n, .ncols = n, .diag = s.pre_diag, .bjac = s.pre_bjac, .amg = s.pre_amg, .A = s.A};
+}
 
 // throws "<loop>: ..." for a combination the loop does not take; `allows`: what it takes beyond the additive form
 // k (term + Jacobi part) and its parts alone

@@ -91,9 +91,7 @@ struct EpiStepProject {
     acc = fma(p.m * e, e, acc);
   }
   __device__ void finish(int b, double* lds) {
-    if (partials == nullptr) return;
-    const double s = block_sum(acc, lds);
-    if (threadIdx.x == 0 && b >= 0) partials[b] = s;
+    if (partials != nullptr) store_block_partial(acc, b, partials, lds);
   }
 };
 
@@ -114,8 +112,7 @@ __global__ __launch_bounds__(kBlock) void step_div_kernel(const int32_t* __restr
     for (int p = s; p < e; ++p) sum += mul_unfused(val[p], u[col[p]]);
     acc = fma(sum, sum, acc);
   }
-  const double t = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  store_block_partial(acc, blockIdx.x, partials, lds);
 }
 
 // P3: record[2 slot] = scale * sum pk (the kinetic energy), record[2 slot + 1] = sqrt(sum pd) (NaN without pd)

@@ -1489,10 +1489,8 @@ class Bpcg1DistLoop(fused.FusedLoop, NativeDist):
         if not (isinstance(a_matrix, DistSparseMatrix) and isinstance(b_matrix, DistSparseMatrix)):
             return "A or B is not a DistSparseMatrix"
         eng = a_matrix.engine
-        if not fused.ENABLED:
-            return "fused loops disabled (hipla.fused.ENABLED)"
-        if not fused._hip(eng):
-            return "not the HIP engine"
+        if (declined := cls._engine_declined(eng)) is not None:
+            return declined
         bt = b_matrix.T
         if not isinstance(bt, DistSparseMatrix):
             return "B^T is not a DistSparseMatrix"

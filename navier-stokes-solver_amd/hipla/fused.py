@@ -189,6 +189,13 @@ class FusedLoop:
         cls.last_declined = out if declined else None
         return None if declined else out
 
+    @staticmethod
+    def _engine_declined(eng):
+        """The reason why no fused loop runs on `eng`, or None."""
+        if not ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        return None if _hip(eng) else "not the HIP engine"
+
 
 def plan_for_textbook_bpcg(a_matrix, pre_a):
     """Launch plans the fused textbook BPCG loop wants, made BEFORE anything multiplies with the matrices (the scale
@@ -338,10 +345,8 @@ class Bpcg2Loop(FusedLoop):
         if not (isinstance(matA, SparseMatrix) and isinstance(matB, SparseMatrix) and isinstance(matBT, SparseMatrix)):
             return "A, B or B^T is not a SparseMatrix"
         eng = matA.engine
-        if not ENABLED:
-            return "fused loops disabled (hipla.fused.ENABLED)"
-        if not _hip(eng):
-            return "not the HIP engine"
+        if (declined := cls._engine_declined(eng)) is not None:
+            return declined
         n_u, n_p = matA.height, matB.height - int(ghost_rows_b)
         if matBT.height != n_u or (ghost_rows_b and not distributed):
             return "B^T does not match A"
@@ -565,10 +570,8 @@ class MinresLoop(FusedLoop):
         if not all(isinstance(m, SparseMatrix) for m in (A, BT, B)):
             return "A, B or B^T is not a SparseMatrix"
         eng = A.engine
-        if not ENABLED:
-            return "fused loops disabled (hipla.fused.ENABLED)"
-        if not _hip(eng):
-            return "not the HIP engine"
+        if (declined := cls._engine_declined(eng)) is not None:
+            return declined
         n_u, n_p = A.height, B.height
         if (A.width, B.width, BT.height, BT.width) != (n_u, n_u, n_u, n_p):
             return "matrix shapes do not match"
@@ -662,10 +665,8 @@ class Bpcg1Loop(FusedLoop):
         if not (isinstance(a_matrix, SparseMatrix) and isinstance(b_matrix, SparseMatrix)):
             return "A or B is not a SparseMatrix"
         eng = a_matrix.engine
-        if not ENABLED:
-            return "fused loops disabled (hipla.fused.ENABLED)"
-        if not _hip(eng):
-            return "not the HIP engine"
+        if (declined := cls._engine_declined(eng)) is not None:
+            return declined
         n_u, n_p = a_matrix.height, b_matrix.height
         if a_matrix.width != n_u or b_matrix.width != n_u:
             return "matrix shapes do not match"
@@ -753,10 +754,8 @@ class CgLoop(FusedLoop):
         if not isinstance(mat, SparseMatrix) or mat.height != mat.width:
             return "the matrix is not a square SparseMatrix"
         eng = mat.engine
-        if not ENABLED:
-            return "fused loops disabled (hipla.fused.ENABLED)"
-        if not _hip(eng):
-            return "not the HIP engine"
+        if (declined := cls._engine_declined(eng)) is not None:
+            return declined
         if isinstance(pre, (ScaledMatrix, SumMatrix)):
             return "the preconditioner is scaled or a sum"
         pa = NO_PRE if pre is None else pre_for("cg", pre)

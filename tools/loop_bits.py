@@ -1,0 +1,240 @@
+"""Every number the device-resident loops produce on a fixed list of cases, from the library given on the command line:
+
+    timeout -k 10 600 python tools/loop_bits.py build/parent/libnsskrylov.so build/bits/parent.npz &&
+    timeout -k 10 600 python tools/loop_bits.py navier-stokes-solver_amd/libnsskrylov.so build/bits/new.npz &&
+    python tools/loop_bits.py --compare build/bits/parent.npz build/bits/new.npz
+
+One process per library; `--compare` needs no GPU, prints every array that is not equal bit for bit (`np.array_equal`)
+and exits 1 if there is one.  What a change that must not move a bit (a refactor of the loops' shared parts) is checked
+with.  The cases sit on the edges of the sum trees, not on the workload:
+
+* CG and Lanczos on the tridiagonal SPD matrix with n = 1000, 1024 * 1024, 1024 * 1025, 1024 * 2049 rows -- 1, 1024,
+  1025, 2049 partials in the sums of their element-wise kernels (one below / above each trip count of the paired loop of
+  `sum_partials_1024` and of its tail) --, 5 iterations.  CG through `solve` and through `solve_resident`, without a
+  preconditioner and with point Jacobi at every size, with block Jacobi, the Gauss-Seidel sweeps and a V-cycle at
+  n = 1000; Lanczos with point Jacobi at every size, with block Jacobi (five-launch and two-launch step) and the
+  Gauss-Seidel sweeps at n = 1000.
+* MINRES, BPCG v1 and BPCG v2 (`enqueue` and `enqueue_classic`) on the 3-D staggered-grid Stokes system with n = 10,
+  point and block Jacobi, fold_mode 0 and 1, 10 iterations; MINRES also with the Gauss-Seidel sweeps (its stand-alone dot).
+* `Advance(2)` on the 3-D grid with maxh = 0.1 and one `heat.evolve` step at n = 16.
+
+Saved per case: histories, final solution vectors, the loop's scalar words."""
+import contextlib
+import ctypes as C
+import io
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "navier-stokes-solver_amd"))
+
+import numpy as np
+import scipy.sparse as sp
+
+CG_SIZES = (1000, 1024 * 1024, 1024 * 1025, 1024 * 2049)
+
+
+def compare(path_a, path_b):
+    a, b = np.load(path_a), np.load(path_b)
+    differ = sorted(set(a.files) ^ set(b.files))
+    differ += [k for k in a.files if k in b.files and not np.array_equal(a[k], b[k], equal_nan=True)]
+    print("%d arrays in %s, %d in %s, %d differ" % (len(a.files), path_a, len(b.files), path_b, len(differ)))
+    for k in differ:
+        print("  differs:", k)
+    return 1 if differ or not a.files else 0
+
+
+class Form:
+    def __init__(self, mat):
+        self.mat, self.condense = mat, False
+
+
+def tridiagonal(n):
+    return sp.diags([-1.0, 2.5, -1.0], [-1, 0, 1], shape=(n, n), format="csr")
+
+
+def tridiagonal_pres(hipla, A, n):
+    blocks = [list(range(i, min(i + 4, n))) for i in range(0, n, 4)]
+    pres = {"none": None, "jacobi": hipla.JacobiPreconditioner(A)}
+    if n == CG_SIZES[0]:
+        pres.update(bjac=hipla.BlockJacobi(A, blocks), bgs=hipla.BlockGaussSeidel(A, blocks),
+                    amg=hipla.SmoothedAggregationAMG(A, coarse_size=60))
+    return pres
+
+
+def cg_cases(hipla, fused, eng, out):
+    for n in CG_SIZES:
+        A = hipla.SparseMatrix.from_scipy(tridiagonal(n))
+        b = eng.from_host(np.random.default_rng(n).standard_normal(n))
+        for name, pre in tridiagonal_pres(hipla, A, n).items():
+            loop = fused.CgLoop.try_create(A, pre)
+            assert loop is not None, fused.CgLoop.last_declined
+            key = "cg_n%d_%s_" % (n, name)
+            x = eng.zeros(n)
+            count, errs = loop.solve(b, x, 0.0, 5)
+            out[key + "solve_hist"], out[key + "solve_x"] = np.array(errs), eng.to_host(x).copy()
+            out[key + "solve_scal"] = eng.to_host(loop.scal).copy()
+            x = eng.zeros(n)
+            assert loop.solve_resident(b, x, 0.0, 5) == count == 5
+            out[key + "resident_hist"], out[key + "resident_x"] = eng.to_host(loop.hist)[:5].copy(), eng.to_host(x).copy()
+            out[key + "resident_scal"] = eng.to_host(loop.scal).copy()
+
+
+def lanczos_steps(fused, eigen, eng, A, pre, steps=5):
+    """`steps` steps of the device-resident recurrence (hipla/eigen.py::_native_lanczos without its convergence checks):
+    the (delta, gamma) history, the scalar words and the three ring vectors."""
+    n = A.height
+    pa = fused.native_velocity_pre(pre)
+    st = eigen._LanczosState.get()()
+    st.A, st.n, st.pre_scale = A.handle.ptr, n, float(pa.scale)
+    keep = fused.write_pre(st, pa)                                                   # noqa: F841 (kept alive)
+    vecs = [eng.zeros(n) for _ in range(6)]
+    eng.lanczos_start_values(vecs[0], 0)
+    for i in range(3):
+        st.v[i] = vecs[i].data_ptr()
+    st.z[0], st.z[1], st.p = vecs[3].data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr()
+    partials = fused.fit_partials(eng, st, eng.lib.nss_lanczos_workspace, ("A",))    # noqa: F841 (kept alive)
+    scal, hist = eng.zeros(8), eng.zeros(2 * steps)
+    ctrl = eng.torch.zeros(4, dtype=eng.torch.int32, device=eng.device)
+    st.scal, st.ctrl, st.hist = scal.data_ptr(), ctrl.data_ptr(), hist.data_ptr()
+    eng._check(eng.lib.nss_lanczos_start(C.byref(st), eng.stream))
+    eng._check(eng.lib.nss_lanczos_iterate(C.byref(st), 0, steps, eng.stream))
+    return [eng.to_host(hist).copy(), eng.to_host(scal).copy()] + [eng.to_host(v).copy() for v in vecs[:3]]
+
+
+def lanczos_cases(hipla, fused, eng, out):
+    from hipla import eigen
+    for n in CG_SIZES:
+        A = hipla.SparseMatrix.from_scipy(tridiagonal(n))
+        for name, pre in tridiagonal_pres(hipla, A, n).items():
+            if name in ("none", "amg"):
+                continue
+            for mode in ((0, 1) if name == "bjac" else (0,)):        # block Jacobi: five-launch and two-launch step
+                eng._check(eng.lib.nss_lanczos_fold_mode(mode))
+                try:
+                    got = lanczos_steps(fused, eigen, eng, A, pre)
+                finally:
+                    eng._check(eng.lib.nss_lanczos_fold_mode(-1))
+                for part, value in zip(("hist", "scal", "v0", "v1", "v2"), got):
+                    out["lanczos_n%d_%s_fold%d_%s" % (n, name, mode, part)] = value
+
+
+@contextlib.contextmanager
+def loop_kept(cls, kept):
+    """`kept[0]` = the loop whose `run` an entry point called (its scalar words are read afterwards)."""
+    orig = cls.run
+    del kept[:]
+
+    def run(self, *a, **kw):
+        kept[:] = [self]
+        return orig(self, *a, **kw)
+    cls.run = run
+    try:
+        yield
+    finally:
+        cls.run = orig
+
+
+def stokes_cases(hipla, fused, eng, out, iterations=10):
+    from bramble_pasciak_cg import bramble_pasciak_cg
+    from minres import MinRes
+    from solvers.bramblepasciak_new import BpcgSession
+    from staggered_grid import mac_stokes
+    s = mac_stokes(3, 10, 0.01)
+    f, g = s.rhs(0)
+    A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
+    preS = hipla.DiagonalMatrix(1.0 / s.mass)
+    blocks = s.line_blocks(3)
+    pres = {"jacobi": hipla.JacobiPreconditioner(A), "bjac": hipla.BlockJacobi(A, blocks),
+            "bgs": hipla.BlockGaussSeidel(A, blocks)}
+    lib, kept, quiet = eng.lib, [], io.StringIO()
+
+    def rhs():
+        return hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g)
+
+    for name, preA in pres.items():
+        for mode in (0, 1):
+            key = "%s_fold%d_" % (name, mode)
+            for setter in (lib.nss_minres_fold_mode, lib.nss_bpcg1_fold_mode, lib.nss_bpcg2_fold_mode):
+                eng._check(setter(mode))
+            try:
+                K = hipla.BlockMatrix([[A, B.T], [B, None]])
+                Cm = hipla.BlockMatrix([[preA, None], [None, preS]])
+                with contextlib.redirect_stdout(quiet), loop_kept(fused.MinresLoop, kept):
+                    u, errors = MinRes(mat=K, pre=Cm, rhs=hipla.BlockVector(list(rhs())), maxsteps=iterations, tol=1e-300,
+                                       printrates=False)
+                assert kept, fused.MinresLoop.last_declined
+                out["minres_" + key + "hist"], out["minres_" + key + "x"] = np.array(errors), u.numpy().copy()
+                out["minres_" + key + "scal"] = eng.to_host(kept[0].scal).copy()
+                if name == "bgs":
+                    continue
+                with contextlib.redirect_stdout(quiet), loop_kept(fused.Bpcg1Loop, kept):
+                    sol, errors = bramble_pasciak_cg(A, B, None, preA, preS, *rhs(), tolerance=0.0, max_steps=iterations,
+                                                     print_rates=False)
+                assert kept, fused.Bpcg1Loop.last_declined
+                out["bpcg1_" + key + "hist"], out["bpcg1_" + key + "x"] = np.array(errors), sol.numpy().copy()
+                out["bpcg1_" + key + "scal"] = eng.to_host(kept[0].scal).copy()
+                for form in ("compact", "classic"):
+                    sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
+                    with contextlib.redirect_stdout(quiet):
+                        ses = BpcgSession(Form(A), Form(B), None, *rhs(), preA, preS, sol=sol)
+                    loop = ses.fused
+                    assert loop is not None, fused.Bpcg2Loop.last_declined
+                    ses.first_direction()
+                    loop.start(ses.wdn, ses.err0, 0.0, True, iterations)
+                    (loop.enqueue_classic if form == "classic" else loop.enqueue)(0, iterations)
+                    done, _, last = loop.poll()
+                    assert not done and last == iterations - 1
+                    tag = "bpcg2_" + form + "_" + key
+                    out[tag + "hist"], out[tag + "x"] = loop.history(last).copy(), sol.numpy().copy()
+                    out[tag + "scal"] = eng.to_host(loop.scal).copy()
+            finally:
+                for setter in (lib.nss_minres_fold_mode, lib.nss_bpcg1_fold_mode, lib.nss_bpcg2_fold_mode):
+                    setter(-1)
+
+
+def step_cases(hipla, out):
+    import heat
+    from templates.NavierStokesSIMPLE_iterative import NavierStokes, SyntheticMesh
+    ns = NavierStokes(SyntheticMesh(0.1, dim=3), nu=0.01, inflow="inlet", outflow="outlet", wall="wall|cyl", uin=None,
+                      timestep=0.05, order=1)
+    rng = np.random.default_rng(8)
+    ns.AddForce(1e-4 * rng.standard_normal(ns.system.n_u))
+    ns.gfu.data = hipla.Vector.from_numpy(1e-2 * rng.standard_normal(ns.system.n_u))
+    rec = ns.Advance(2)
+    assert rec.declined is None, rec.declined
+    out["advance_u"] = ns.gfu.numpy().copy()
+    out["advance_iterations"] = np.stack([rec.mstar_iterations, rec.proj_iterations])
+    out["advance_record"] = np.stack([rec.div_norm, rec.kinetic_energy])
+    start = heat.sum_of_unit_square_laplace_eigenfunctions([(1, 1), (2, 1), (1, 3), (3, 3), (2, 3), (4, 5), (5, 2)], 16)
+    temperature, _, record = heat.evolve(start, 1e-2, 1e-2, n=16, maxsteps=400, diagnostics=True)
+    assert record.declined is None and record.steps == 1, (record.declined, record.steps)
+    out["heat_temperature"], out["heat_iterations"] = np.asarray(temperature).copy(), record.cg_iterations
+    out["heat_orthogonality"] = record.orthogonality
+
+
+def main(argv):
+    if len(argv) == 4 and argv[1] == "--compare":
+        return compare(argv[2], argv[3])
+    if len(argv) != 3:
+        print(__doc__)
+        return 2
+    from hipla import hip_engine
+    hip_engine.LIB_PATH = os.path.abspath(argv[1])        # what `load_library()` opens for the engine
+    import hipla
+    from hipla import fused
+    hipla.set_engine(None)
+    eng = hipla.get_engine()
+    out = {}
+    cg_cases(hipla, fused, eng, out)
+    lanczos_cases(hipla, fused, eng, out)
+    stokes_cases(hipla, fused, eng, out)
+    step_cases(hipla, out)
+    os.makedirs(os.path.dirname(os.path.abspath(argv[2])), exist_ok=True)
+    np.savez(argv[2], **out)
+    print("%d arrays from %s -> %s" % (len(out), hip_engine.LIB_PATH, argv[2]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
