@@ -697,6 +697,27 @@ NSS_API int nss_step_record_f64(const double* partials_energy, int64_t n_energy,
                                 int64_t n_div, double scale, double* record, int32_t slot, const int32_t* done,
                                 nss_stream_t stream);
 
+/* ---- scalar transport in the device-resident time step -------------------------------------------
+ * The kernels `NavierStokes.AddScalar` adds to a step of `Advance`: a cell-centred scalar T carried by the face
+ * velocities u (M_p dT/dt = q - K T - B G), with the Boussinesq force f_eff = f + w_b (avg T - t_ref).  All fp64, no
+ * atomics; `done` as for the nss_step_* kernels.
+ *
+ * nss_scalar_flux_f64: per face r (row of avg and diff, at most two entries each; their two-slot copies are built on
+ *   the first call: set-up)  G[r] = u[r] (avg T)_r - |u[r]| (diff T)_r / 2, the donor-cell flux, and with w_b != NULL
+ *   f_eff[r] = f[r] + w_b[r] ((avg T)_r - t_ref); w_b == NULL (the passive scalar) reads no f and writes no f_eff.
+ *   Fails when a row holds more than two entries.  `G` is meant to be the tail of one buffer [T | G].
+ * nss_scalar_update_f64: T += tau delta; with w != NULL also partials[workgroup] of <w, T> over the updated T (cap
+ *   entries, at least what nss_scalar_workspace reports for n); w and partials are both NULL or both given.
+ * nss_scalar_record_f64: record[slot] = c0 - sum(partials[0 .. n)), summed by the fixed tree of the Krylov loops. */
+NSS_API int nss_scalar_flux_f64(nss_csr_t avg, nss_csr_t diff, const double* w_b, const double* u, const double* f,
+                                const double* T, double t_ref, double* G, double* f_eff, const int32_t* done,
+                                nss_stream_t stream);
+NSS_API int nss_scalar_workspace(int64_t n, int64_t* partials);
+NSS_API int nss_scalar_update_f64(int64_t n, double tau, const double* delta, double* T, const double* w,
+                                  double* partials, int64_t cap, const int32_t* done, nss_stream_t stream);
+NSS_API int nss_scalar_record_f64(const double* partials, int64_t n, double c0, double* record, int32_t slot,
+                                  const int32_t* done, nss_stream_t stream);
+
 /* ---- device-resident heat exponential integrator -------------------------------------------------
  * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
  * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:

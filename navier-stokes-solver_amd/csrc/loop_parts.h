@@ -36,6 +36,19 @@ __device__ __forceinline__ double sum_partials_1024(const double* __restrict__ p
   return t;
 }
 
+// ---- the parts the kernels of the time step share (step.hip, scalar.hip) ----
+typedef int32_t int2v __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ bool step_done(const int32_t* done) { return done != nullptr && *done != 0; }
+
+// the row sum of a two-slot row as csr_direct_kernel forms it: 0 + p0 + p1, products rounded on their own
+__device__ __forceinline__ double two_slot_sum(const int2v& c, const dbl2v& v, double x0, double x1) {
+  double sum = 0.0;
+  if (c.x >= 0) sum += mul_unfused(v.x, x0);
+  if (c.y >= 0) sum += mul_unfused(v.y, x1);
+  return sum;
+}
+
 // the stop test of a loop that freezes once one control word is set (cg, lanczos)
 struct StopWord {
   const int32_t* __restrict__ ctrl;

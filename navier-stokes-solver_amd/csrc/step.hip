@@ -14,18 +14,6 @@
 
 namespace nss {
 
-typedef int32_t int2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool step_done(const int32_t* done) { return done != nullptr && *done != 0; }
-
-// the row sum of a two-slot row as csr_direct_kernel forms it: 0 + p0 + p1, products rounded on their own
-__device__ __forceinline__ double two_slot_sum(const int2v& c, const dbl2v& v, double x0, double x1) {
-  double sum = 0.0;
-  if (c.x >= 0) sum += mul_unfused(v.x, x0);
-  if (c.y >= 0) sum += mul_unfused(v.y, x1);
-  return sum;
-}
-
 struct FluxOps {
   const int32_t *adv_col, *avg_col, *diff_col;
   const double *adv_val, *avg_val, *diff_val;

@@ -854,13 +854,18 @@ class StepRecord:
     """What `NavierStokes.Advance` returns: one entry per step of `mstar_iterations`, `proj_iterations` (pseudo time
     stepping: the two projections of a step added), `div_norm` = |B u| and `kinetic_energy` = <u, M_u u> / 2 after the
     step (both None with ``diagnostics=False``); `declined`: why the statements ran instead of the device-resident
-    step (None when it ran); `flux_declined`: why the convection term ran through `ConvectionOperator`."""
+    step (None when it ran); `flux_declined`: why the convection term ran through `ConvectionOperator`.  With a scalar
+    (`NavierStokes.AddScalar`): `scalar_iterations` of the temperature solve and `wall_flux` = the heat entering through
+    the scalar's `flux_wall` after the step (None without a scalar / without diagnostics)."""
 
-    def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None):
+    def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
+                 scalar_iterations=None, wall_flux=None):
         self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
         self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
         self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
         self.declined, self.flux_declined = declined, flux_declined
+        self.scalar_iterations = None if scalar_iterations is None else np.asarray(scalar_iterations, dtype=np.int64)
+        self.wall_flux = wall_flux
 
 
 class TimeStepper(FusedLoop):
@@ -968,19 +973,21 @@ class TimeStepper(FusedLoop):
         self.n_energy, self.n_div = ne.value, nd.value
 
     # ---- the launches of a step -----------------------------------------------------------------------------------
-    def right_hand_side(self):
-        """temp = conv(u) + f - A u from the u part of the operand buffer."""
+    def right_hand_side(self, f=None):
+        """temp = conv(u) + f - A u from the u part of the operand buffer; `f`: the force of this step (a buffer: the
+        f_eff of a buoyant scalar), None = the stepper's f."""
         eng, lib = self.eng, self.lib
+        f = self.f.buf if f is None else f
         if self.flux_declined is None:
             flux = eng.view(self.uf, self.n_u, self.n_u + self.nflux)
             eng._check(lib.nss_step_flux_f64(self.adv.handle.ptr, self.avg.handle.ptr, self.diff.handle.ptr,
                                              self.uf.data_ptr(), flux.data_ptr(), None, eng.stream))
-            eng._check(lib.nss_step_rhs_f64(self.AD.handle.ptr, self.uf.data_ptr(), self.f.buf.data_ptr(),
+            eng._check(lib.nss_step_rhs_f64(self.AD.handle.ptr, self.uf.data_ptr(), f.data_ptr(),
                                             self.temp.data_ptr(), None, eng.stream))
             return
         u, temp = Vector(buf=self.u, engine=eng), Vector(buf=self.temp, engine=eng)
         temp.data = self.conv * u
-        temp.data += self.f
+        temp.data += Vector(buf=f, engine=eng)
         temp.data += -self.A * u
 
     def project(self, vel, out=None, update=None, energy=False):
@@ -1007,9 +1014,12 @@ class TimeStepper(FusedLoop):
                                            self.partials_d.data_ptr() if divergence else None, self.n_div,
                                            self.energy_scale, record.data_ptr(), slot, None, eng.stream))
 
-    def advance(self, gfu, gfup, nsteps, precision=None, maxsteps=None, diagnostics=True, pseudo=False):
+    def advance(self, gfu, gfup, nsteps, precision=None, maxsteps=None, diagnostics=True, pseudo=False, scalar=None,
+                temperature=None):
         """`nsteps` steps on the velocity `gfu` (pressure-like potential of the last projection -> `gfup`).
-        `precision` / `maxsteps`: one value for both inner solves, a pair (mstar, projection), or None = the template's."""
+        `precision` / `maxsteps`: one value for both inner solves, a pair (mstar, projection), or None = the template's.
+        `scalar`: a `ScalarStepper` -- every step then begins with its flux launch on (u^n, T^n), the velocity step
+        takes its f_eff for f (a buoyant scalar), and its temperature step follows; `temperature`: the `Vector` of T."""
         def pair(v, default):
             return default if v is None else tuple(v) if isinstance(v, (tuple, list)) else (v, v)
         self.precision = tuple(float(p) for p in pair(precision, self.PRECISION))
@@ -1017,6 +1027,10 @@ class TimeStepper(FusedLoop):
         eng = self.eng
         self._fit_partials()
         nsteps = int(nsteps)
+        if scalar is not None:
+            if pseudo:
+                raise ValueError("advance: the pseudo time stepping carries no scalar")
+            return self._advance_with_scalar(scalar, temperature, gfu, gfup, nsteps, diagnostics)
         record = eng.zeros(2 * max(1, nsteps)) if diagnostics else None
         eng.copy(gfu.buf, self.u)
         its_m, its_p = [], []
@@ -1041,6 +1055,122 @@ class TimeStepper(FusedLoop):
             return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined)
         host = eng.to_host(record).reshape(-1, 2)[:nsteps]               # the one read-back
         return StepRecord(its_m, its_p, host[:, 1].copy(), host[:, 0].copy(), flux_declined=self.flux_declined)
+
+    def _advance_with_scalar(self, scalar, temperature, gfu, gfup, nsteps, diagnostics):
+        """The loop of `advance` with the launches of `scalar` around the velocity step.  The velocity record and the
+        scalar's share one device buffer ([2 nsteps | nsteps]) and one read-back."""
+        eng = self.eng
+        record = eng.zeros(3 * max(1, nsteps)) if diagnostics else None
+        record_s = eng.view(record, 2 * max(1, nsteps), 3 * max(1, nsteps)) if diagnostics else None
+        eng.copy(gfu.buf, self.u)
+        scalar.load(temperature)
+        its_m, its_p, its_s = [], [], []
+        for step in range(nsteps):
+            self.right_hand_side(scalar.flux(self.u))                             # S1, F1, F2
+            its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))
+            its_p.append(self.project(self.raw, out=self.temp2, update=self.u, energy=diagnostics))
+            if diagnostics:
+                self.write_record(record, step)
+            its_s.append(scalar.step(record_s if scalar.records else None, step))  # S2, the solve, S3, S4
+        eng.copy(self.u, gfu.buf)
+        if nsteps:
+            eng.copy(self.phi, gfup.buf)
+        scalar.store(temperature)
+        if not diagnostics:
+            return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined, scalar_iterations=its_s)
+        host = eng.to_host(record)                                                # the one read-back
+        vel = host[:2 * max(1, nsteps)].reshape(-1, 2)[:nsteps]
+        wall = host[2 * max(1, nsteps):][:nsteps].copy() if scalar.records else None
+        return StepRecord(its_m, its_p, vel[:, 1].copy(), vel[:, 0].copy(), flux_declined=self.flux_declined,
+                          scalar_iterations=its_s, wall_flux=wall)
+
+
+class ScalarStepper:
+    """The scalar part of a device-resident step (``nss_scalar_*`` around one `CgLoop` solve), driven by
+    `TimeStepper.advance`: M_p dT/dt = q - K T - B G with the donor-cell flux G of T through the faces and, for a
+    buoyant scalar, the force f_eff = f + w_b (avg T - t_ref) of the velocity step.
+
+    Per step: the flux launch on (u^n, T^n) writes G behind T in the operand buffer [T | G] (and f_eff); after the
+    velocity step one launch over the rows of [K | B] forms temp_T = q - K T - B G; delta = (M_p + timestep K)^-1 temp_T
+    (CG from zero); one launch does T += timestep delta with the partials of <w, T>, one workgroup writes the heat
+    entering through the flux wall, c0 - <w, T>.  Every buffer is allocated here, once.  Beyond the vectors the scalar
+    costs in HBM: avg and diff (two two-slot copies, 48 bytes per face), M_p + timestep K, and [K | B] -- a second copy
+    of K and one of B, 12 bytes per non-zero (B: 24 bytes per face)."""
+
+    PRECISION, MAXSTEPS = 1e-4, 500          # those of invmstar: the same kind of operator
+
+    def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
+                 maxsteps=None, shared=None):
+        """`ops`: `StokesSystem.scalar_operators(...)`; `B`: the divergence (`SparseMatrix`); `f`: the force `Vector`
+        the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
+        (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
+        `inner_pre`."""
+        import scipy.sparse as sp
+        from .matrix import JacobiPreconditioner
+        shared = {} if shared is None else shared
+        self.eng, self.lib, self.f, self.timestep, self.t_ref = eng, eng.lib, f, float(timestep), float(t_ref)
+        self.n_u, self.n_p = ops["avg"].shape
+        self.precision = self.PRECISION if precision is None else float(precision)
+        self.maxsteps = self.MAXSTEPS if maxsteps is None else int(maxsteps)
+        if "avg" not in shared:
+            for key in ("avg", "diff"):
+                ok, why = two_entry_rows(ops[key])
+                if not ok:
+                    raise ValueError("ScalarStepper: %s: %s" % (key, why))
+                shared[key] = SparseMatrix.from_scipy(ops[key], engine=eng)
+            KB = sp.hstack([ops["K"], B.to_scipy()], format="csr")
+            KB.sort_indices()
+            shared["KB"] = SparseMatrix.from_scipy(KB, engine=eng)
+            shared["mstar"] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + self.timestep * ops["K"]).tocsr(), engine=eng)
+            shared["q"] = eng.from_host(np.asarray(ops["q"], dtype=np.float64))
+            shared["w_b"] = None if w_b is None else eng.from_host(np.asarray(w_b, dtype=np.float64))
+            shared["w"] = None if flux is None else eng.from_host(np.asarray(flux[1], dtype=np.float64))
+        self.avg, self.diff, self.KB, self.mstar = (shared[key] for key in ("avg", "diff", "KB", "mstar"))
+        self.q, self.w_b, self.w = shared["q"], shared["w_b"], shared["w"]
+        self.c0 = 0.0 if flux is None else float(flux[0])
+        self.records = flux is not None
+        self.tg = eng.zeros(self.n_p + self.n_u)             # the operand [T | G]
+        self.T = eng.view(self.tg, 0, self.n_p)
+        self.G = eng.view(self.tg, self.n_p, self.n_p + self.n_u)
+        self.f_eff = None if w_b is None else eng.zeros(self.n_u)
+        self.temp, self.delta = eng.zeros(self.n_p), eng.zeros(self.n_p)
+        self.pre = SmoothedAggregationAMG(self.mstar) if inner_pre == "amg" else JacobiPreconditioner(self.mstar)
+        self.cg = CgLoop(eng, self.mstar, pre_for("cg", self.pre))
+        count = C.c_int64()
+        eng._check(self.lib.nss_scalar_workspace(self.n_p, C.byref(count)))
+        self.n_partials = count.value
+        self.partials = eng.zeros(max(1, count.value)) if self.records else None
+
+    def load(self, temperature):
+        self.eng.copy(temperature.buf, self.T)
+
+    def store(self, temperature):
+        self.eng.copy(self.T, temperature.buf)
+
+    def flux(self, u):
+        """S1 on (u, T): G, and for a buoyant scalar f_eff.  Returns the force buffer of the velocity step (None: f)."""
+        eng = self.eng
+        eng._check(self.lib.nss_scalar_flux_f64(self.avg.handle.ptr, self.diff.handle.ptr,
+                                                None if self.w_b is None else self.w_b.data_ptr(), u.data_ptr(),
+                                                self.f.buf.data_ptr(), self.T.data_ptr(), self.t_ref, self.G.data_ptr(),
+                                                None if self.f_eff is None else self.f_eff.data_ptr(), None, eng.stream))
+        return self.f_eff
+
+    def step(self, record, slot):
+        """S2, the solve, S3 and (with `record`) S4.  Returns the CG iterations."""
+        eng, lib = self.eng, self.lib
+        eng._check(lib.nss_step_rhs_f64(self.KB.handle.ptr, self.tg.data_ptr(), self.q.data_ptr(), self.temp.data_ptr(),
+                                        None, eng.stream))
+        its = self.cg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
+        write = record is not None
+        eng._check(lib.nss_scalar_update_f64(self.n_p, self.timestep, self.delta.data_ptr(), self.T.data_ptr(),
+                                             self.w.data_ptr() if write else None,
+                                             self.partials.data_ptr() if write else None,
+                                             self.partials.numel() if write else 0, None, eng.stream))
+        if write:
+            eng._check(lib.nss_scalar_record_f64(self.partials.data_ptr(), self.n_partials, self.c0, record.data_ptr(),
+                                                 slot, None, eng.stream))
+        return its
 
 
 class HeatRecord:

@@ -128,6 +128,10 @@ def _signatures():
         "nss_step_divergence_f64": (C.c_int, [vp, vp, vp, i64, vp, vp]),
         "nss_step_workspace": (C.c_int, [vp, vp, c_i64_p, c_i64_p]),
         "nss_step_record_f64": (C.c_int, [vp, i64, vp, i64, dbl, vp, i32, vp, vp]),
+        "nss_scalar_flux_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp]),
+        "nss_scalar_workspace": (C.c_int, [i64, c_i64_p]),
+        "nss_scalar_update_f64": (C.c_int, [i64, dbl, vp, vp, vp, vp, i64, vp, vp]),
+        "nss_scalar_record_f64": (C.c_int, [vp, i64, dbl, vp, i32, vp, vp]),
         "nss_heat_workspace": (C.c_int, [i64, i32, c_i64_p]),
         "nss_mgs_f64": (C.c_int, [i64, i32, i64, vp, i32, vp, vp, i64, vp]),
         "nss_galerkin_f64": (C.c_int, [vp, i32, i64, vp, vp, vp, i64, vp]),

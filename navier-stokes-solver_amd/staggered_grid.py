@@ -280,6 +280,120 @@ class StokesSystem:
                 out[g[idx]] = -hface * total
         return out
 
+    def _wall(self, wall):
+        """(array axis, first or last index) of the wall named "x-", "x+", "y-", ... in the [slab, ..., x] order."""
+        names = "xyz"[:self.dim]
+        if len(wall) != 2 or wall[0] not in names or wall[1] not in "-+":
+            raise ValueError("wall %r: the walls are %s" % (wall, ", ".join(a + s for a in names for s in "-+")))
+        return self.dim - 1 - names.index(wall[0]), 0 if wall[1] == "-" else -1
+
+    def scalar_operators(self, kappa, dirichlet):
+        """Sparse operators of a cell-centred scalar T (a temperature) carried by the face velocities:
+
+            M_p dT/dt = q - K T - B G,      G = u * (avg T) - 1/2 |u| * (diff T),
+
+        with K = kappa times the 5-/7-point negative Laplacian integrated over the cell (entries ~ kappa h^(d-2),
+        like A), G the donor-cell flux through the faces -- on the MAC grid the advecting velocity at face r IS the dof
+        u_r -- and B the divergence (already scaled by h^(d-1)).  `dirichlet` maps wall names ("x-", "x+", "y-", "y+",
+        "z-", "z+") to wall temperatures: ghost-cell reflection, ghost = 2 T_w - T_in, so the diagonal gains one more
+        kappa h^(d-2) and q holds 2 kappa h^(d-2) T_w in the cells next to the wall; every wall not named is insulated
+        (no term).  Wall faces are not dofs and carry no convective flux (u.n = 0), Dirichlet walls included.
+
+        Returns dict(K, q, avg, diff, mass, wall_flux): avg = (1/2, 1/2) and diff = (-1, +1) on the cells (lo, hi) of
+        every face along the positive direction of its normal (n_u x n_p, two entries per row), mass = the lumped cell
+        mass h^d, and wall_flux(wall) -> (c0, w) with the heat entering through that Dirichlet wall = c0 - <w, T>
+        ( = the sum over the adjacent cells of 2 kappa h^(d-2) (T_w - T_c) )."""
+        if self.block_size != 1:
+            raise ValueError("scalar_operators: plain (not inflated) systems only")
+        dim, n = self.dim, self.n
+        ck = float(kappa) * self.h ** (dim - 2)
+        pid = np.arange(self.n_p, dtype=np.int64).reshape((n,) * dim)
+        rows, cols, vals = [], [], []
+        diag = np.zeros((n,) * dim)
+        for ax in range(dim):
+            lo, hi = _shift_slices(dim, ax)
+            rows += [pid[lo].ravel(), pid[hi].ravel()]
+            cols += [pid[hi].ravel(), pid[lo].ravel()]
+            off = np.full(pid[lo].size, -ck)
+            vals += [off, off]
+            diag[lo] += ck
+            diag[hi] += ck
+        q = np.zeros((n,) * dim)
+        walls = {}
+        for wall, t_wall in dirichlet.items():
+            ax, end = self._wall(wall)
+            sel = [slice(None)] * dim
+            sel[ax] = end
+            diag[tuple(sel)] += 2.0 * ck
+            q[tuple(sel)] += 2.0 * ck * float(t_wall)
+            walls[wall] = (pid[tuple(sel)].ravel(), float(t_wall))
+        rows.append(pid.ravel())
+        cols.append(pid.ravel())
+        vals.append(diag.ravel())
+        K = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))),
+                          shape=(self.n_p, self.n_p)).tocsr()
+        K.sort_indices()
+        rows, cols, v_avg, v_diff = [], [], [], []
+        for c, g in enumerate(self.component_ids):
+            lo, hi = _shift_slices(dim, _axis_of_component(dim, c))
+            for cells, sign in ((pid[lo], -1.0), (pid[hi], 1.0)):
+                rows.append(g.ravel())
+                cols.append(cells.ravel())
+                v_avg.append(np.full(g.size, 0.5))
+                v_diff.append(np.full(g.size, sign))
+        rows, cols = np.concatenate(rows), np.concatenate(cols)
+        avg = sp.coo_matrix((np.concatenate(v_avg), (rows, cols)), shape=(self.n_u, self.n_p)).tocsr()
+        diff = sp.coo_matrix((np.concatenate(v_diff), (rows, cols)), shape=(self.n_u, self.n_p)).tocsr()
+        avg.sort_indices()
+        diff.sort_indices()
+
+        def wall_flux(wall):
+            if wall not in walls:
+                raise ValueError("wall_flux: %r is not a Dirichlet wall of this scalar" % (wall,))
+            cells, t_wall = walls[wall]
+            w = np.zeros(self.n_p)
+            w[cells] = 2.0 * ck
+            return 2.0 * ck * t_wall * cells.size, w
+
+        return {"K": K, "q": q.ravel(), "avg": avg, "diff": diff, "mass": self.mass, "wall_flux": wall_flux}
+
+    def buoyancy_weights(self, buoyancy):
+        """w_b of the Boussinesq force f_eff = f + w_b * (avg T - T_ref): beta_c h^d on the faces of component c for
+        `buoyancy` = (beta_x, beta_y[, beta_z])."""
+        if self.block_size != 1:
+            raise ValueError("buoyancy_weights: plain (not inflated) systems only")
+        if len(buoyancy) != self.dim:
+            raise ValueError("buoyancy: one coefficient per direction (%d)" % self.dim)
+        w = np.zeros(self.n_u)
+        for beta, g in zip(buoyancy, self.component_ids):
+            w[g.ravel()] = float(beta) * self.h ** self.dim
+        return w
+
+    def scalar_convection_reference(self, u, T):
+        """-B G of `scalar_operators` by direct loops over the cells (small plain cases; the check of the signs of avg
+        and diff against B): the donor-cell fluxes through the 2 d faces of every cell, zero through wall faces."""
+        if self.block_size != 1:
+            raise ValueError("scalar_convection_reference: plain (not inflated) systems only")
+        dim, n = self.dim, self.n
+        hface = self.h ** (dim - 1)
+        T = np.asarray(T, dtype=np.float64).reshape((n,) * dim)
+        out = np.zeros((n,) * dim)
+        for cell in np.ndindex(*(n,) * dim):
+            total = 0.0
+            for c, g in enumerate(self.component_ids):
+                ax = _axis_of_component(dim, c)
+                for side in (1, -1):                       # upper / lower face of the cell along ax
+                    nb = list(cell)
+                    nb[ax] += side
+                    if nb[ax] < 0 or nb[ax] >= n:
+                        continue                           # wall: no flux
+                    lo, hi = (cell, tuple(nb)) if side == 1 else (tuple(nb), cell)
+                    vel = u[g[lo]]                         # face m of component c lies between cells m and m + 1
+                    flux = vel * 0.5 * (T[lo] + T[hi]) - 0.5 * abs(vel) * (T[hi] - T[lo])
+                    total += side * flux
+            out[cell] = -hface * total
+        return out.ravel()
+
     def auxiliary_space(self):
         """The auxiliary space of the reference's ``MypreA`` restated on the grid
         (templates/NavierStokesSIMPLE_iterative.py:150-157,208-357): one P1-like *nodal* scalar space

@@ -139,6 +139,39 @@ def coupling_blocks(blocks, interior):
     return np.ascontiguousarray(idx[:, (idx >= 0).any(axis=0)], dtype=np.int32)
 
 
+class ScalarField:
+    """What `NavierStokes.AddScalar` keeps: the protocol operands of the scalar's statements in `DoTimeStep` (K, avg,
+    diff, q, the CG inverse of M_p + timestep K, the buoyancy weights as a diagonal matrix) and what a device-resident
+    `hipla.fused.ScalarStepper` is made from."""
+
+    def __init__(self, system, b_mat, timestep, kappa, dirichlet, buoyancy, t_ref, precision, maxsteps, flux_wall):
+        from hipla.fused import ScalarStepper
+        self.ops = ops = system.scalar_operators(kappa, dirichlet)
+        self.t_ref = float(t_ref)
+        self.precision = ScalarStepper.PRECISION if precision is None else float(precision)
+        self.maxsteps = ScalarStepper.MAXSTEPS if maxsteps is None else int(maxsteps)
+        self.w_b = None if buoyancy is None else system.buoyancy_weights(buoyancy)
+        if flux_wall is None and dirichlet:
+            flux_wall = next(iter(dirichlet))
+        self.flux_wall = flux_wall
+        self.flux = None if flux_wall is None else ops["wall_flux"](flux_wall)
+        self.K, self.avg, self.diff = (hipla.SparseMatrix.from_scipy(ops[k]) for k in ("K", "avg", "diff"))
+        self.q = hipla.Vector.from_numpy(ops["q"])
+        self.mstar = hipla.SparseMatrix.from_scipy((sp.diags(ops["mass"]) + timestep * ops["K"]).tocsr())
+        self.inv = CGSolver(self.mstar, pre=hipla.JacobiPreconditioner(self.mstar), precision=self.precision,
+                            maxsteps=self.maxsteps)
+        self.Wb = None if self.w_b is None else hipla.DiagonalMatrix(self.w_b)
+        self.tref_u = hipla.Vector.from_numpy(np.full(system.n_u, self.t_ref))
+        self.w = None if self.flux is None else hipla.Vector.from_numpy(self.flux[1])
+        self.avgT, self.difT, self.G, self.f_eff = (self.avg.CreateColVector() for _ in range(4))
+        self.temp, self.delta = b_mat.CreateColVector(), b_mat.CreateColVector()
+        self.steppers, self.shared = {}, {}
+
+    def wall_flux(self, temperature):
+        """The heat entering through `flux_wall`: c0 - <w, T>."""
+        return self.flux[0] - float(hipla.InnerProduct(self.w, temperature))
+
+
 class NavierStokes:
     def __init__(self, mesh, nu, inflow, outflow, wall, uin, timestep, order=2, volumeforce=None):
         self.mesh, self.nu, self.timestep, self.order = mesh, nu, timestep, order
@@ -151,6 +184,7 @@ class NavierStokes:
         self.stokes_bpcg_time = None
         self._conv_operator = None        # explicit convection term of the IMEX step (:106-113), built on first use
         self._stepping = None
+        self._scalar = None               # the transported scalar (`AddScalar`)
 
     @property
     def conv_operator(self):
@@ -250,18 +284,65 @@ class NavierStokes:
         """`force`: host array of nodal forces on the velocity dofs, added to f (:419-422)."""
         self.f.vec.data += hipla.Vector.from_numpy(np.asarray(force, dtype=np.float64))
 
+    def AddScalar(self, kappa, dirichlet=None, buoyancy=None, t_ref=0.0, initial=None, precision=None, maxsteps=None,
+                  flux_wall=None):
+        """Carry a cell-centred scalar T (a temperature) with the flow: M_p dT/dt = q - K T - B G with diffusivity
+        `kappa`, the donor-cell flux G of T through the faces (the face velocities are the velocity dofs) and implicit
+        diffusion; `DoTimeStep` and `Advance` then advance T with u, coupled explicitly (first order, like the
+        convection term).  Plain systems only (``ValueError`` for an inflated one).
+
+        `dirichlet`: wall name ("x-", "x+", "y-", "y+", "z-", "z+") -> wall temperature; every other wall is insulated.
+        `buoyancy` = (beta_x, beta_y[, beta_z]): the Boussinesq force, f + beta_c h^d (avg T - `t_ref`) on the faces of
+        component c, takes the place of f in the momentum equation; None = a passive scalar.  `initial`: host array of
+        n_p cell values (None: `t_ref` everywhere).  `precision` / `maxsteps` of the temperature solve: None = those of
+        invmstar (1e-4, 500).  `flux_wall`: the Dirichlet wall whose heat flux `Advance` records (None: the first one
+        given).  The scalar is `self.temperature`; `AddForce` keeps working: f is read every step."""
+        dirichlet = dict(dirichlet or {})
+        self._scalar = ScalarField(self.system, self.b.mat, self.timestep, kappa, dirichlet, buoyancy, t_ref, precision,
+                                   maxsteps, flux_wall)
+        start = np.full(self.system.n_p, float(t_ref)) if initial is None else np.asarray(initial, dtype=np.float64)
+        if start.shape != (self.system.n_p,):
+            raise ValueError("AddScalar: initial holds %s values, the grid has %d cells" % (start.shape, self.system.n_p))
+        self.temperature = hipla.Vector.from_numpy(start)
+
+    def _scalar_flux(self):
+        """The first statements of a step with a scalar, on (u^n, T^n): G = u * (avg T) - |u| * (diff T) / 2 and the
+        force of the step, f + w_b * (avg T - t_ref) (f itself for a passive scalar)."""
+        sc = self._scalar
+        sc.avgT.data = sc.avg * self.temperature
+        sc.difT.data = sc.diff * self.temperature
+        sc.G.engine.upwind_flux(self.gfu.buf, sc.avgT.buf, sc.difT.buf, sc.G.buf)
+        if sc.Wb is None:
+            return self.f.vec
+        sc.avgT.data -= sc.tref_u
+        sc.f_eff.data = self.f.vec + sc.Wb * sc.avgT
+        return sc.f_eff
+
+    def _scalar_step(self):
+        """The last statements of a step with a scalar: temp_T = q - K T - B G;  delta = (M_p + timestep K)^-1 temp_T;
+        T += timestep * delta."""
+        sc = self._scalar
+        sc.temp.data = sc.q - sc.K * self.temperature
+        sc.temp.data -= self.b.mat * sc.G
+        sc.delta.data = sc.inv * sc.temp
+        self.temperature.data += self.timestep * sc.delta
+
     def DoTimeStep(self):
         """One IMEX step (:424-438): temp = conv(u) + f - A u;  temp2 = invmstar temp;
-        Project(temp2);  u += timestep * temp2."""
+        Project(temp2);  u += timestep * temp2.  With a scalar (`AddScalar`) its flux and force statements come first
+        and its own step last."""
         ops = self._time_stepping_operators()
+        force = self.f.vec if self._scalar is None else self._scalar_flux()
         temp = self.a.mat.CreateColVector()
         temp2 = self.a.mat.CreateColVector()
         temp.data = self.conv_operator * self.gfu        # :429
-        temp.data += self.f.vec
+        temp.data += force
         temp.data += -self.a.mat * self.gfu
         temp2.data = ops["invmstar"] * temp
         self.Project(temp2)
         self.gfu.data += self.timestep * temp2
+        if self._scalar is not None:
+            self._scalar_step()
 
     def Project(self, vel):
         """Make `vel` discretely divergence-free (:440-443): phi = (B M_u^-1 B^T)^-1 B vel;
@@ -277,7 +358,8 @@ class NavierStokes:
         the device-resident stepper (`hipla.fused.TimeStepper`): the statements of `DoTimeStep` / `Project` in two
         launches for the right-hand side and one for the projection tail, every buffer allocated once, a per-step
         record on the device read back once.  Returns an `hipla.fused.StepRecord` (mstar_iterations,
-        proj_iterations, div_norm, kinetic_energy).
+        proj_iterations, div_norm, kinetic_energy; with a scalar -- `AddScalar` -- also scalar_iterations and
+        wall_flux, and `pseudo=True` raises ``ValueError``).
 
         `inner_pre`: "jacobi" (what `DoTimeStep` uses) or "amg" -- a smoothed-aggregation V-cycle for both inner CG
         solves; `precision` / `maxsteps`: None = those of `DoTimeStep` (1e-4 / 1e-8, 500 / 5000), one value for both
@@ -293,6 +375,8 @@ class NavierStokes:
         from hipla.fused import StepRecord, TimeStepper
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
+        if pseudo and self._scalar is not None:
+            raise ValueError("Advance: the pseudo time stepping carries no scalar")
         steppers = self.__dict__.setdefault("_steppers", {})
         stepper = steppers.get(inner_pre) if fused.ENABLED else None
         if stepper is None:
@@ -306,6 +390,15 @@ class NavierStokes:
             if stepper is not None:
                 steppers[inner_pre] = stepper
         self.advance_declined = TimeStepper.last_declined if stepper is None else None
+        if stepper is not None and self._scalar is not None:
+            sc = self._scalar
+            if inner_pre not in sc.steppers:
+                from hipla.fused import ScalarStepper
+                sc.steppers[inner_pre] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
+                                                       inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
+                                                       shared=sc.shared)
+            return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics,
+                                   scalar=sc.steppers[inner_pre], temperature=self.temperature)
         if stepper is not None:
             return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics, pseudo)
         return self._advance_by_statements(int(nsteps), precision, maxsteps, diagnostics, pseudo, StepRecord)
@@ -325,6 +418,8 @@ class NavierStokes:
             sv.precision = sv.precision if p is None else float(p)
             sv.maxsteps = sv.maxsteps if m is None else int(m)
         its_m, its_p, div, energy = [], [], [], []
+        sc = self._scalar
+        its_s, wall = ([], []) if sc is not None else (None, None)
         mass_u = self.system.h ** self.system.dim
         try:
             with contextlib.redirect_stdout(io.StringIO()):
@@ -338,6 +433,10 @@ class NavierStokes:
                         count = ops["invproj"].iterations
                     its_m.append(ops["invmstar"].iterations)
                     its_p.append(count)
+                    if sc is not None:
+                        its_s.append(sc.inv.iterations)
+                        if diagnostics and sc.flux is not None:
+                            wall.append(sc.wall_flux(self.temperature))
                     if diagnostics:
                         bu = self.b.mat.CreateColVector()
                         bu.data = self.b.mat * self.gfu
@@ -347,4 +446,6 @@ class NavierStokes:
             for sv, (p, m) in zip(solvers, saved):
                 sv.precision, sv.maxsteps = p, m
         return record_type(its_m, its_p, np.array(div) if diagnostics else None,
-                           np.array(energy) if diagnostics else None, declined=self.advance_declined)
+                           np.array(energy) if diagnostics else None, declined=self.advance_declined,
+                           scalar_iterations=its_s,
+                           wall_flux=np.array(wall) if sc is not None and diagnostics and sc.flux is not None else None)

@@ -1,0 +1,48 @@
+"""numpy / scipy restatement of ONE coupled step of velocity and scalar (`NavierStokes.AddScalar`) with exact inner
+solves (`spsolve`) -- a helper of the scalar-transport tests, not a test.  It shares nothing with the product but the
+matrices of `StokesSystem`:
+
+    G      = u * (avg T) - |u| * (diff T) / 2                    donor-cell flux of T through the faces, on (u^n, T^n)
+    f_eff  = f + w_b * (avg T - t_ref)                           (f without buoyancy)
+    temp   = conv(u) + f_eff - A u;   raw = (M_u + tau A)^-1 temp
+    phi    = (B M_u^-1 B^T)^+ B raw;  temp2 = raw - M_u^-1 B^T phi;  u += tau temp2
+    temp_T = q - K T - B G;           delta = (M_p + tau K)^-1 temp_T;  T += tau delta
+    wall_flux = c0 - <w, T>           of the new T"""
+
+import numpy as np
+import scipy.sparse as sp
+from scipy.sparse.linalg import spsolve
+
+
+def pinned_solve(lap, rhs):
+    """A solution of the singular, consistent system lap x = rhs (kernel = constants): x[0] = 0."""
+    x = np.zeros(lap.shape[0])
+    x[1:] = spsolve(sp.csc_matrix(lap[1:][:, 1:]), rhs[1:])
+    return x
+
+
+def coupled_step(system, tau, u, T, f, kappa, dirichlet, buoyancy=None, t_ref=0.0, flux_wall=None):
+    s = system
+    ops = s.scalar_operators(kappa, dirichlet)
+    mass_u = s.h ** s.dim
+    avg_t, dif_t = ops["avg"] @ T, ops["diff"] @ T
+    G = u * avg_t - 0.5 * np.abs(u) * dif_t
+    f_eff = f.copy() if buoyancy is None else f + s.buoyancy_weights(buoyancy) * (avg_t - t_ref)
+    cops = s.convection_operators()
+    adv = cops["adv"] @ u
+    conv = -(cops["div"] @ (adv * (cops["avg"] @ u) - 0.5 * np.abs(adv) * (cops["diff"] @ u)))
+    temp = conv + f_eff - s.A @ u
+    raw = spsolve(sp.csc_matrix(mass_u * sp.identity(s.n_u) + tau * s.A), temp)
+    correct = (s.B.T / mass_u).tocsr()
+    phi = pinned_solve((s.B @ correct).tocsr(), s.B @ raw)
+    temp2 = raw - correct @ phi
+    u_new = u + tau * temp2
+    temp_t = ops["q"] - ops["K"] @ T - s.B @ G
+    delta = spsolve(sp.csc_matrix(sp.diags(ops["mass"]) + tau * ops["K"]), temp_t)
+    T_new = T + tau * delta
+    out = dict(G=G, f_eff=f_eff, temp=temp, raw=raw, temp2=temp2, u=u_new, temp_T=temp_t, delta=delta, T=T_new)
+    wall = flux_wall if flux_wall is not None else next(iter(dirichlet), None)
+    if wall is not None:
+        c0, w = ops["wall_flux"](wall)
+        out["wall_flux"] = c0 - w @ T_new
+    return out
