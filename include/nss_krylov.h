@@ -152,6 +152,26 @@ NSS_API int nss_csr_destroy(nss_csr_t a);
 NSS_API int nss_csr_round_f32(nss_csr_t a, nss_stream_t stream);
 NSS_API int nss_csr_narrow_f32(nss_csr_t a, nss_stream_t stream);
 NSS_API int nss_csr_value_bytes(nss_csr_t a, int64_t* bytes);
+/* Value codes (value-indexed CSR, lossless): a matrix with at most 256 distinct 64-bit value PATTERNS (-0.0 and +0.0 are
+ * two, NaN payloads are kept) -- every operator of a uniform grid has a handful -- additionally stores one byte per
+ * entry, the index of its value in a dictionary of 256 doubles (sorted by bit pattern: deterministic codes).  The kernels
+ * that have a coded form (nss_csr_spmv_f64, C1 and C23 of the compact BPCG v2 plan) then stream 1 byte per entry
+ * instead of 8 and multiply dict[code] * x from an LDS copy of the dictionary: the same doubles, the same products in
+ * the same order, identical bits.  The 8-byte values STAY (1 byte per entry of extra memory): every set-up path and
+ * every other kernel keeps reading them, and re-plans keep the codes.  nss_csr_round_f32 / nss_csr_narrow_f32 drop them.
+ * nss_csr_code_values: set-up only (counts the patterns on the device, gives up at the 257th: *coded = 0 and nothing
+ *   changes; synchronises `stream`).  A matrix with grouped column indices (nss_csr_index_group > 1) is not
+ *   coded either (*coded = 0: the grouped kernels have no coded form).  Once coded, nss_csr_value_bytes is 1 per entry and nss_csr_info prices the
+ *   value stream at 1 byte per entry plus the 2-KiB dictionary per row block (form 3: rows x (8 + 2)).
+ * nss_csr_drop_value_codes: back to the uncoded state (set-up only, synchronises the device).
+ * nss_csr_value_code_mode: process-wide override: -1 = automatic (the default), 0 = never (coded matrices stream their
+ *   8-byte values and report so), 1 = whenever a matrix admits codes.
+ * nss_csr_value_codes_wanted: what a loop set-up should do for a system whose largest matrix has `rows` rows: the mode,
+ *   and in automatic mode a size rule (from 2^19 rows on: below, the loops are bound by launches, not bytes). */
+NSS_API int nss_csr_code_values(nss_csr_t a, int32_t* coded, nss_stream_t stream);
+NSS_API int nss_csr_drop_value_codes(nss_csr_t a);
+NSS_API int nss_csr_value_code_mode(int32_t mode);
+NSS_API int nss_csr_value_codes_wanted(int64_t rows, int32_t* wanted);
 /* y = alpha * A x + beta * y   (beta == 0: y is not read).  x must not alias y. */
 NSS_API int nss_csr_spmv_f64(nss_csr_t a, double alpha, const double* x, double beta, double* y,
                              nss_stream_t stream);

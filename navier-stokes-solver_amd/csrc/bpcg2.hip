@@ -1043,10 +1043,11 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
                                        s.s1, s.w1, s.dist_compact ? s.ghost_n : 0, s.ghost_s0, s.ghost_w0,                 \
                                        fj ? s.BT->jb_first : nullptr, fj ? s.BT->jb_order : nullptr, fj ? J->run : nullptr, fj ? J->inv_sym : nullptr,   \
                                        fj ? J->nblocks : 0, fj ? J->bs : 0}, st, 0, -1, lds)
-      if (nt && fold) NSS_C1(true, true, launch_csr_direct);
-      else if (nt) NSS_C1(false, true, launch_csr_direct);
-      else if (fold) NSS_C1(true, false, launch_csr_stream);
-      else NSS_C1(false, false, launch_csr_stream);
+      // (the _coded launchers: a matrix with value codes streams them, nss_csr_code_values; same bits)
+      if (nt && fold) NSS_C1(true, true, launch_csr_direct_coded);
+      else if (nt) NSS_C1(false, true, launch_csr_direct_coded);
+      else if (fold) NSS_C1(true, false, launch_csr_stream_coded);
+      else NSS_C1(false, false, launch_csr_stream_coded);
 #undef NSS_C1
       if (!fj) bpcg2_k1_finish(s, st, d);
       break;
@@ -1054,9 +1055,10 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
     case NSS_BPCG2C_C23: {
       EpiK2c ea{s.ctrl, s.t0, s.s0, s.t2, s.partials_a};
       EpiK3c eb{s.ctrl, s.scal, s.t1, s.s0, s.s1, s.w1, s.t3, s.partials_b, it, s.n_p};
-      if (!launch_csr_stream_dual(*s.A, s.t1, ea, *s.B, s.t1, eb, st)) {   // launch plans differ: two launches
-        launch_csr_stream(*s.A, s.t1, ea, st);
-        launch_csr_stream(*s.B, s.t1, eb, st);
+      // (coded form of the shared launch only when BOTH matrices hold value codes; each of the two launches by itself)
+      if (!launch_csr_stream_dual<EpiK2c, EpiK3c, true>(*s.A, s.t1, ea, *s.B, s.t1, eb, st)) {   // launch plans differ: two launches
+        launch_csr_stream_coded(*s.A, s.t1, ea, st);
+        launch_csr_stream_coded(*s.B, s.t1, eb, st);
       }
       break;
     }

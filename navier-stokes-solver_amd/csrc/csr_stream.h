@@ -75,6 +75,12 @@ constexpr int kSegPre = 6, kSegOff = 18;
 constexpr int kSegBlock = 31;        // dispatch-ordered copy of the table: the row block this slot stands for
 
 bool pair_staging_enabled();     // nss_csr_pair_mode (tests, measurements)
+bool value_codes_enabled();      // nss_csr_value_code_mode != 0
+
+// Value type of a coded matrix (nss_csr_s::val8): the stream is one byte per entry, the index of the entry's value in
+// a dictionary of at most kDictSize doubles that the kernel holds in LDS.  Same doubles, same products.
+struct Coded8 {};
+constexpr int kDictSize = 256;
 
 struct CsrView {
   const int32_t* __restrict__ rowblk;
@@ -96,15 +102,53 @@ struct CsrView {
                     // gather; 2 = staged (LDS copy of the row block's operand segments, 16-bit positions);
                     // 3 = pair-staged (the segments of TWO vectors, each in one half of the LDS buffer)
   const float* __restrict__ val32;      // the 4-byte value stream of a narrowed matrix (nss_csr_s::val32), else NULL
+  const uint8_t* __restrict__ val8;     // the 1-byte value codes of a coded matrix (nss_csr_s::val8), else NULL
+  const double* __restrict__ dict;      // ... and its kDictSize values
 };
 
 // the value stream of a view as the kernels' value type VT (double: `val`; float: `val32`, widened before the product)
 template <class VT>
-__device__ __forceinline__ const VT* view_values(const CsrView& a) {
-  static_assert(std::is_same<VT, double>::value || std::is_same<VT, float>::value, "values are fp64 or fp32");
+struct StoredValue { using type = VT; };
+template <>
+struct StoredValue<Coded8> { using type = uint8_t; };
+template <class VT>
+__device__ __forceinline__ const typename StoredValue<VT>::type* view_values(const CsrView& a) {
+  static_assert(std::is_same<VT, double>::value || std::is_same<VT, float>::value || std::is_same<VT, Coded8>::value,
+                "values are fp64, fp32 or codes");
   if constexpr (std::is_same<VT, float>::value) return a.val32;
+  else if constexpr (std::is_same<VT, Coded8>::value) return a.val8;
   else return a.val;
 }
+// a stored value as the double that enters the product (`dict`: the LDS copy of the dictionary, coded form only)
+template <class VT>
+__device__ __forceinline__ double value_of(typename StoredValue<VT>::type v, const double* dict) {
+  if constexpr (std::is_same<VT, Coded8>::value) return dict[v];
+  else return double(v);
+}
+// The LDS copy of the dictionary: static storage of the coded instantiations only (2 KiB beside the 16-KiB product
+// buffer: 8 workgroups per CU still fit the 160 KiB).
+template <class VT>
+struct DictLds {
+  static __device__ __forceinline__ double* get() { return nullptr; }
+  static __device__ __forceinline__ void request(const CsrView&, double*) {}
+};
+typedef __attribute__((address_space(3))) void* LdsDst;
+typedef const __attribute__((address_space(1))) void* GlobalSrc;
+template <>
+struct DictLds<Coded8> {
+  static __device__ __forceinline__ double* get() {
+    __shared__ alignas(16) double dict[kDictSize];         // (destination of 16-byte LDS-DMA)
+    return dict;
+  }
+  // dictionary -> LDS by LDS-DMA (no VGPR destination: nothing for the register allocator to recycle in the middle of
+  // the matrix stream): waves 0 and 1 move 64 x 16 bytes each.  Requested AHEAD of the matrix stream; the caller
+  // waits for vmcnt(0) and passes a barrier before the first read.
+  static __device__ __forceinline__ void request(const CsrView& a, double* dict) {
+    const int wave = int(threadIdx.x) / 64, lane = int(threadIdx.x) % 64;
+    if (wave < kDictSize / 128)
+      __builtin_amdgcn_global_load_lds((GlobalSrc)(a.dict + wave * 128 + 2 * lane), (LdsDst)(dict + wave * 128), 16, 0, 0);
+  }
+};
 
 }  // namespace nss
 
@@ -197,7 +241,21 @@ struct nss_csr_s {
   // is then NULL.  Only the kernel paths instantiated for it take such a matrix (launch_csr_stream_any, the joint AMG
   // cycle); every other path refuses it (view() without `narrow_ok`, require_f64_values) -- none reads it as doubles.
   float* val32 = nullptr;
+  // Value codes (nss_csr_code_values): a matrix with at most kDictSize distinct 64-bit value patterns -- every operator
+  // of a uniform grid has a handful -- also holds val8, one byte per entry in CSR order (padded like `val`), and `dict`,
+  // the kDictSize doubles the codes index (sorted by bit pattern, unused slots 0).  The kernels instantiated for it
+  // (value type Coded8) stream 1 byte per entry instead of 8 and multiply dict[code] * x: the same doubles, the same
+  // products in the same order.  `val` STAYS: every set-up path and every kernel without a coded form reads it, and the
+  // codes are per entry in CSR order, so re-plans keep them.  ell_code: the two slots' codes of the fixed-width copy,
+  // one 16-bit word per row (slot 0 in the low byte), built with ell_col.  Writers of `val` drop the codes.
+  uint8_t* val8 = nullptr;
+  double* dict = nullptr;
+  uint16_t* ell_code = nullptr;
+  int32_t dict_count = 0;
   uint64_t jb_serial = 0;
+  // the kernels with a coded form take it (the grouped column streams have none: nss_csr_code_values refuses such a
+  // matrix, and one that a re-plan groups later reads `val` again and reports so)
+  bool coded() const { return val8 != nullptr && gb == 1 && nss::value_codes_enabled(); }
   // `stageable`: the kernel's operand functor is one stored vector that can be copied to LDS (XOp::kStageable);
   // `pairable`: it is an expression of two (XOp::kStageablePair)
   int idx_mode(bool stageable = true, bool pairable = false) const {
@@ -214,7 +272,7 @@ struct nss_csr_s {
     return nss::CsrView{rowblk, rowptr, col, mode >= 2 ? pos16 : (mode == 1 ? col16 : nullptr), blkbase, blkseg,
                         (mode >= 2 && full) ? blkdisp : nullptr, val,
                         uint32_t(gb), uint32_t(nss::kBlock / gb), uint32_t(nss::kBlock % gb), magic, b0, b1 - b0,
-                        (b1 - b0 + nss::kXcds - 1) / nss::kXcds, mode, val32};
+                        (b1 - b0 + nss::kXcds - 1) / nss::kXcds, mode, val32, val8, dict};
   }
   // one workgroup per row block, padded to a multiple of the XCD count
   static int grid(int count) { return ((count + nss::kXcds - 1) / nss::kXcds) * nss::kXcds; }
@@ -348,14 +406,17 @@ struct RowPrefetch {
 template <class Epi, int CH, int IDX, bool GRP, int KPF, class VT = double>
 __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __restrict__ x, Epi& epi, int b, int p0,
                                            int cnt, double* prod, double* red, int32_t* window,
-                                           RowPrefetch<Epi, KPF>& pf, int rf, int rstep, int r1) {
+                                           RowPrefetch<Epi, KPF>& pf, int rf, int rstep, int r1,
+                                           const double* dict = nullptr) {
+  constexpr bool kCoded = std::is_same<VT, Coded8>::value;
+  using SV = typename StoredValue<VT>::type;
   static_assert(IDX != 0 || !GRP, "grouped column stream needs a 16-bit form");
   using XOp = typename EpiX<Epi>::type;
   constexpr int kPer = CH / kBlock;
   const int tid = threadIdx.x;
   int32_t c[kPer];                                       // column (IDX 0), else position inside the group
-  const VT* __restrict__ vals = view_values<VT>(a);
-  VT v[kPer];                                            // (fp32: widened to fp64 at the product)
+  const SV* __restrict__ vals = view_values<VT>(a);
+  SV v[kPer];                                            // (fp32: widened to fp64 at the product; codes: looked up there)
   uint16_t c16[kPer];
   if (IDX == 1) {
     if (tid < kWindows) window[tid] = a.blkbase[b * kWindows + tid];
@@ -380,11 +441,11 @@ __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __res
 #if NSS_STREAM_NT
     if (IDX != 0 && !GRP) c16[k] = live ? __builtin_nontemporal_load(&a.col16[p0 + i]) : uint16_t(0);
     if (IDX == 0) c[k] = live ? __builtin_nontemporal_load(&a.col[p0 + i]) : 0;
-    v[k] = live ? __builtin_nontemporal_load(&vals[p0 + i]) : VT(0);
+    v[k] = live ? __builtin_nontemporal_load(&vals[p0 + i]) : SV(0);
 #else
     if (IDX != 0 && !GRP) c16[k] = live ? a.col16[p0 + i] : uint16_t(0);
     if (IDX == 0) c[k] = live ? a.col[p0 + i] : 0;
-    v[k] = live ? vals[p0 + i] : VT(0);
+    v[k] = live ? vals[p0 + i] : SV(0);
 #endif
   }
   // behind the matrix stream and in the same straight-line code (requested in front of it, the register
@@ -436,15 +497,19 @@ __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __res
       __builtin_assume(c[k] >= 0);
       xv[k] = (tid + k * kBlock < cnt) ? xop(c[k]) : 0.0;
     }
+    if constexpr (kCoded) {
+      // the gathering forms have no barrier between the stream and the products: the dictionary's LDS-DMA (requested
+      // ahead of the stream) is awaited by its waves and published here, with the gather already in flight
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
   }
+  // (coded, staged forms: the wait and the first barrier above have published the dictionary too)
 #pragma unroll
   for (int k = 0; k < kPer; ++k)
-    if (tid + k * kBlock < cnt) prod[tid + k * kBlock] = double(v[k]) * xv[k];
+    if (tid + k * kBlock < cnt) prod[tid + k * kBlock] = value_of<VT>(v[k], dict) * xv[k];
   return true;
 }
-
-typedef __attribute__((address_space(3))) void* LdsDst;
-typedef const __attribute__((address_space(1))) void* GlobalSrc;
 
 // One workgroup = one row block: `wg` is the workgroup's index inside this launch's grid part.
 // IDX / GRP: the form of the column stream (csr_phase1).  They are template parameters of the kernels: a run-time
@@ -470,8 +535,10 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
     // reuse-aware dispatch order: slot lb of the dispatch-ordered table names its row block (uniform scalar load)
     if (a.blkdisp != nullptr) b = ((ConstI32)(a.blkdisp + size_t(lb) * kSegWords))[kSegBlock];
   }
+  double* const dict = DictLds<VT>::get();
   if (b >= 0) {
     int r0 = 0, r1 = 0, p0 = 0, cnt = 0;
+    DictLds<VT>::request(a, dict);                          // (coded form) ahead of everything else
     if constexpr (IDX >= 2) {
       // One descriptor per row block instead of the rowblk -> rowptr chain.  It must arrive through SCALAR loads
       // (the run table then sits in SGPRs); the constant address space makes the loads invariant, and a uniform
@@ -540,7 +607,7 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
       constexpr int kPer = CH / kBlock;
       (void)kPer;
       // ---- phase 1: coalesced stream of (col, val), operand, stage products ------------
-      const bool go = csr_phase1<Epi, CH, IDX, GRP, kPF, VT>(a, x, epi, b, p0, cnt, prod, red, window, pf, rf, kBlock / RG, r1);
+      const bool go = csr_phase1<Epi, CH, IDX, GRP, kPF, VT>(a, x, epi, b, p0, cnt, prod, red, window, pf, rf, kBlock / RG, r1, dict);
       if (!go) return;                                     // the prologue ended the workgroup (uniform)
       __syncthreads();
       // ---- phase 2: per-row reduction from LDS -----------------------------------------
@@ -590,8 +657,12 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
       if (!EpiPrologue<Epi>::run(epi, red)) return;
       const XOp xop = EpiX<Epi>::get(epi, x);
       double acc = 0.0;
-      const VT* __restrict__ vals = view_values<VT>(a);
-      for (int i = tid; i < cnt; i += kBlock) acc = fma(double(vals[p0 + i]), xop(a.col[p0 + i]), acc);
+      const typename StoredValue<VT>::type* __restrict__ vals = view_values<VT>(a);
+      if constexpr (std::is_same<VT, Coded8>::value) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the dictionary's LDS-DMA, then published
+        __syncthreads();
+      }
+      for (int i = tid; i < cnt; i += kBlock) acc = fma(value_of<VT>(vals[p0 + i], dict), xop(a.col[p0 + i]), acc);
       const double sum = block_sum(acc, red);
       if (tid == 0) EpiPre<Epi>::row(epi, r0, sum, EpiPre<Epi>::fetch(epi, r0));
     }
@@ -617,7 +688,7 @@ __global__ __launch_bounds__(kBlock) void csr_stream_kernel(CsrView a, const dou
 #ifndef NSS_DUAL_SECOND_FIRST
 #define NSS_DUAL_SECOND_FIRST 1
 #endif
-template <int RG, class EpiA, class EpiB, int IDXA, int IDXB, int CH, bool GRP>
+template <int RG, class EpiA, class EpiB, int IDXA, int IDXB, int CH, bool GRP, class VT = double>
 __global__ __launch_bounds__(kBlock) void csr_stream_dual_kernel(CsrView a, CsrView b, int grid_a, int grid_b,
                                                                   const double* __restrict__ xa,
                                                                   const double* __restrict__ xb, EpiA ea, EpiB eb) {
@@ -633,10 +704,10 @@ __global__ __launch_bounds__(kBlock) void csr_stream_dual_kernel(CsrView a, CsrV
 #endif
   if (first) {
     if (ea.skip()) return;
-    csr_stream_body<RG, EpiA, IDXA, CH, (GRP && IDXA != 0)>(a, xa, ea, wg, prod, red, window);
+    csr_stream_body<RG, EpiA, IDXA, CH, (GRP && IDXA != 0), VT>(a, xa, ea, wg, prod, red, window);
   } else {
     if (eb.skip()) return;
-    csr_stream_body<RG, EpiB, IDXB, CH, (GRP && IDXB != 0)>(b, xb, eb, wg, prod, red, window);
+    csr_stream_body<RG, EpiB, IDXB, CH, (GRP && IDXB != 0), VT>(b, xb, eb, wg, prod, red, window);
   }
 }
 
@@ -646,31 +717,39 @@ __global__ __launch_bounds__(kBlock) void csr_stream_dual_kernel(CsrView a, CsrV
 // operands -- are requested before the prologue; the operand is gathered (two entries per row: nothing to
 // stage).  The row sum is formed exactly as the stream kernel forms it (0 + p0 + p1, products rounded on their
 // own: mul_unfused), so both kernels give identical bits.
-template <class Epi>
+// Coded form (VT = Coded8): the row's 16-bit code word (`ecode`) instead of the two 8-byte values, both values from the
+// LDS copy of the dictionary -- 10 bytes per row instead of 24.
+template <class Epi, class VT = double>
 __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int32_t* __restrict__ ecol,
                                                             const double* __restrict__ eval,
+                                                            const uint16_t* __restrict__ ecode,
                                                             const double* __restrict__ x, Epi epi) {
   static_assert(kDirectWidth == 2, "csr_direct_kernel is written for two slots per row");
   using XOp = typename EpiX<Epi>::type;
+  constexpr bool kCoded = std::is_same<VT, Coded8>::value;
   __shared__ double red[kRedDoubles];
+  double* const dict = DictLds<VT>::get();
   if (epi.skip()) return;
   const int tid = threadIdx.x, wg = int(blockIdx.x);
   const int lb = (wg & (kXcds - 1)) * a.per_xcd + (wg >> 3);
   const int b = lb < a.nblk ? a.blk0 + lb : -1;
   if (b >= 0) {
+    DictLds<VT>::request(a, dict);                            // (coded form) ahead of the rows' loads
     const int r0 = a.rowblk[b], r1 = a.rowblk[b + 1];
     for (int base = r0; base < r1; base += kDirectRows) {     // (one trip: the plan caps such blocks at kDirectRows rows)
       constexpr int kRows = kDirectRows / kBlock;
       typedef int32_t int2v __attribute__((ext_vector_type(2)));
       int2v c[kRows];
       dbl2v v[kRows];
+      uint16_t code[kRows];
       typename EpiPre<Epi>::type pre[kRows];
 #pragma unroll
       for (int q = 0; q < kRows; ++q) {
         const int r = base + tid + q * kBlock;
         const bool live = r < r1;
         c[q] = live ? __builtin_nontemporal_load(reinterpret_cast<const int2v*>(ecol) + r) : int2v{-1, -1};
-        v[q] = live ? __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(eval) + r) : dbl2v{0.0, 0.0};
+        if constexpr (kCoded) code[q] = live ? __builtin_nontemporal_load(ecode + r) : uint16_t(0);
+        else v[q] = live ? __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(eval) + r) : dbl2v{0.0, 0.0};
         pre[q] = live ? EpiPre<Epi>::fetch(epi, r) : typename EpiPre<Epi>::type{};
       }
       if (base == r0 && !EpiPrologue<Epi>::run(epi, red)) return;   // uniform over the workgroup
@@ -680,6 +759,14 @@ __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int
       for (int q = 0; q < kRows; ++q) {
         x0[q] = c[q].x >= 0 ? xop(c[q].x) : 0.0;
         x1[q] = c[q].y >= 0 ? xop(c[q].y) : 0.0;
+      }
+      if constexpr (kCoded) {
+        // the one barrier of the coded form: the dictionary's LDS-DMA is awaited by its waves and published, with
+        // the operand gather already in flight
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kRows; ++q) v[q] = dbl2v{dict[code[q] & 0xff], dict[code[q] >> 8]};
       }
 #pragma unroll
       for (int q = 0; q < kRows; ++q) {
@@ -717,7 +804,24 @@ inline void launch_csr_direct(const nss_csr_s& A, const double* x, const Epi& ep
   if (A.m == 0 || b1 <= b0) return;
   if (!A.ell_col) throw Error("csr_direct: the matrix has no fixed-width copy");
   hipLaunchKernelGGL((csr_direct_kernel<Epi>), dim3(nss_csr_s::grid(b1 - b0)), dim3(kBlock), dyn_lds, st, A.view(b0, b1, 0),
-                     A.ell_col, A.ell_val, x, epi);
+                     A.ell_col, A.ell_val, (const uint16_t*)nullptr, x, epi);
+  NSS_CHECK_LAUNCH();
+}
+
+// ... and its coded form where the matrix holds value codes (only for the epilogues of the flagship loop and the plain
+// SpMV: every use doubles the instantiations of its epilogue)
+template <class Epi>
+inline void launch_csr_direct_coded(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
+                                    int b1 = -1, size_t dyn_lds = 0) {
+  if (!(A.coded() && A.ell_code)) {
+    launch_csr_direct(A, x, epi, st, b0, b1, dyn_lds);
+    return;
+  }
+  if (b1 < 0) b1 = A.nblk;
+  if (A.m == 0 || b1 <= b0) return;
+  if (!A.ell_col) throw Error("csr_direct: the matrix has no fixed-width copy");
+  hipLaunchKernelGGL((csr_direct_kernel<Epi, Coded8>), dim3(nss_csr_s::grid(b1 - b0)), dim3(kBlock), dyn_lds, st,
+                     A.view(b0, b1, 0), A.ell_col, A.ell_val, A.ell_code, x, epi);
   NSS_CHECK_LAUNCH();
 }
 
@@ -731,6 +835,20 @@ inline void launch_csr_stream_vt(const nss_csr_s& A, const double* x, const Epi&
   const bool grp = mode != 0 && A.gb > 1;
   const CsrView v = A.view(b0, b1, mode, std::is_same<VT, float>::value);
   const dim3 grid(nss_csr_s::grid(b1 - b0)), block(kBlock);
+  if constexpr (std::is_same<VT, Coded8>::value) {           // (callers check A.coded(): one index per entry)
+#define NSS_LAUNCH_ONE(N, CHK)                                                                                  \
+  if (mode == 2) {                                                                                               \
+    if constexpr (kCanStage) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi); \
+  } else if (mode == 3) {                                                                                        \
+    if constexpr (kCanPair) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);  \
+  } else if (mode == 1) {                                                                                        \
+    hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);     \
+  } else {                                                                                                       \
+    hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 0, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);     \
+  }
+    NSS_FOR_PLAN(A, NSS_LAUNCH_ONE)
+#undef NSS_LAUNCH_ONE
+  } else {
 #define NSS_LAUNCH_ONE(N, CHK)                                                                                  \
   if (mode == 2) {                                                                                               \
     if constexpr (kCanStage) {                                                                                   \
@@ -750,6 +868,7 @@ inline void launch_csr_stream_vt(const nss_csr_s& A, const double* x, const Epi&
   }
   NSS_FOR_PLAN(A, NSS_LAUNCH_ONE)
 #undef NSS_LAUNCH_ONE
+  }
   NSS_CHECK_LAUNCH();
 }
 
@@ -764,6 +883,25 @@ inline void launch_csr_stream(const nss_csr_s& A, const double* x, const Epi& ep
     return;
   }
   launch_csr_stream_vt<Epi, double>(A, x, epi, st, b0, b1, dyn_lds);
+}
+
+// as launch_csr_stream, and a coded matrix (nss_csr_s::coded) streams its value codes: the stream kernel's Coded8
+// instantiation or the coded row-per-lane kernel.  Used only by the launches of the flagship loop (C1, C23) and the
+// plain SpMV: the value type is a template parameter, so every use doubles the instantiations of its epilogue.
+template <class Epi>
+inline void launch_csr_stream_coded(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
+                                    int b1 = -1, size_t dyn_lds = 0) {
+  if (!A.coded() || A.val32) {
+    launch_csr_stream(A, x, epi, st, b0, b1, dyn_lds);
+    return;
+  }
+  if (A.ell_col) {
+    launch_csr_direct_coded(A, x, epi, st, b0, b1, dyn_lds);
+    return;
+  }
+  if (b1 < 0) b1 = A.nblk;
+  if (A.m == 0 || b1 <= b0) return;
+  launch_csr_stream_vt<Epi, Coded8>(A, x, epi, st, b0, b1, dyn_lds);
 }
 
 // as launch_csr_stream, and a matrix with fp32 values (nss_csr_s::val32) takes the fp32 instantiation.  Used only
@@ -785,7 +923,8 @@ inline void launch_csr_stream_any(const nss_csr_s& A, const double* x, const Epi
 
 // A and B in one launch when their launch plans agree (lanes per row, chunk) and the pair of column streams is
 // one of the instantiated ones; returns false (nothing launched) otherwise -- the caller then issues two launches.
-template <class EpiA, class EpiB>
+// CODED: instantiate the coded form too, taken when BOTH matrices are coded (otherwise both halves read `val`).
+template <class EpiA, class EpiB, bool CODED = false>
 inline bool launch_csr_stream_dual(const nss_csr_s& A, const double* xa, const EpiA& ea, const nss_csr_s& B,
                                    const double* xb, const EpiB& eb, hipStream_t st, size_t dyn_lds = 0) {
 #ifdef NSS_NO_DUAL        // measurements: the two halves as launches of their own
@@ -805,6 +944,32 @@ inline bool launch_csr_stream_dual(const nss_csr_s& A, const double* xa, const E
   const CsrView va = A.view(0, A.nblk, ma), vb = B.view(0, B.nblk, mb);
   const int ga = nss_csr_s::grid(A.nblk), gb = nss_csr_s::grid(B.nblk);
   const dim3 grid(ga + gb), block(kBlock);
+  if constexpr (CODED) {
+    // both halves stream value codes (never grouped: nss_csr_s::coded)
+    if (A.coded() && B.coded()) {
+#define NSS_DUAL_GO(N, CHK, IA, IB) \
+  hipLaunchKernelGGL((csr_stream_dual_kernel<N, EpiA, EpiB, IA, IB, CHK, false, Coded8>), grid, block, dyn_lds, st, va, vb, ga, gb, xa, xb, ea, eb)
+#define NSS_LAUNCH_DUAL_ONE(N, CHK)                                                        \
+  if (ma == 0) {                                                                            \
+    NSS_DUAL_GO(N, CHK, 0, 0);                                                              \
+  } else if (ma == 2 && mb == 2) {                                                          \
+    if constexpr (kStageA && kStageB) { NSS_DUAL_GO(N, CHK, 2, 2); }                        \
+  } else if (ma == 2 && mb == 3) {                                                          \
+    if constexpr (kStageA && kPairB) { NSS_DUAL_GO(N, CHK, 2, 3); }                         \
+  } else if (ma == 2) {                                                                     \
+    if constexpr (kStageA) { NSS_DUAL_GO(N, CHK, 2, 1); }                                   \
+  } else if (mb == 2) {                                                                     \
+    if constexpr (kStageB) { NSS_DUAL_GO(N, CHK, 1, 2); }                                   \
+  } else {                                                                                  \
+    NSS_DUAL_GO(N, CHK, 1, 1);                                                              \
+  }
+      NSS_FOR_PLAN(A, NSS_LAUNCH_DUAL_ONE)
+#undef NSS_LAUNCH_DUAL_ONE
+#undef NSS_DUAL_GO
+      NSS_CHECK_LAUNCH();
+      return true;
+    }
+  }
 #define NSS_DUAL_GO(N, CHK, IA, IB, G) \
   hipLaunchKernelGGL((csr_stream_dual_kernel<N, EpiA, EpiB, IA, IB, CHK, G>), grid, block, dyn_lds, st, va, vb, ga, gb, xa, xb, ea, eb)
 #define NSS_DUAL_PAIR(N, CHK, IA, IB) \

@@ -26,6 +26,23 @@ static int64_t g_direct_min_rows = NSS_DIRECT_MIN_ROWS;   // nss_csr_direct_rows
 static int g_pair_mode = -1;
 bool pair_staging_enabled() { return g_pair_mode != 0; }
 
+// Value codes (nss_csr_code_values): -1 by size, 0 never (coded matrices read `val` again), 1 whenever a matrix
+// admits them (nss_csr_value_code_mode).  By size: the coded kernels stream 7 bytes per entry less and pay one 2-KiB
+// dictionary load per workgroup (the gathering forms and the row-per-lane kernel: one more barrier) -- that pays where
+// the iteration is bound by bytes, not by launches.  Measured with the BPCG v2 loop (profiles/r04_ab_value_codes.txt,
+// one box, this library in automatic mode alternated with the parent's): 1.0e7 DoF (7.5e6 rows, coded) +12 %; 1.0e6 DoF
+// (2-D, 6.6e5 rows, coded) +5 %; 1.0e5 DoF (2-D, 6.7e4 rows, left uncoded) unchanged.  Forced on at 1.0e5 DoF has NOT
+// been measured with these kernels -- only with a tried and removed variant of the coded phase 1 (four entries per
+// load), whose gathering forms lost 0.9 % there inside a +-3 % spread.  The threshold sits between the two smaller
+// sizes, at the 2^19 rows from which the loop's vectors no longer fit the memory-side cache; WHERE between 6.7e4 and
+// 6.6e5 rows coding starts to pay is unmeasured.  nss_csr_value_codes_wanted() applies it to the rows of the largest
+// matrix of a loop.
+#ifndef NSS_VALUE_CODES_MIN_ROWS
+#define NSS_VALUE_CODES_MIN_ROWS (1 << 19)
+#endif
+static int g_value_code_mode = -1;
+bool value_codes_enabled() { return g_value_code_mode != 0; }
+
 bool direct_rows_candidate(int32_t m, const int32_t* rowptr) {
 #if NSS_DIRECT_ROWS
   if (m < g_direct_min_rows) return false;
@@ -611,6 +628,161 @@ __global__ __launch_bounds__(kBlock) void ell_build_kernel(int32_t m, const int3
   }
 }
 
+// ---- value codes ----------------------------------------------------------------------------------------------
+constexpr int kCodeSlots = 1024;                          // open-addressing table (power of two, 4 x the dictionary)
+constexpr uint64_t kCodeEmpty = ~uint64_t(0);             // free slot; the value with this very pattern is flagged apart
+// state[0]: distinct patterns inserted, state[1]: gave up (a 257th pattern, or the table is full), state[2]: the
+// pattern kCodeEmpty occurs
+__global__ __launch_bounds__(kBlock) void code_collect_kernel(int64_t n, const double* __restrict__ val,
+                                                               unsigned long long* table, int32_t* state) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  unsigned long long last = 0;                            // the pattern this lane has just seen: nothing to do
+  bool seen = false;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(val[i]);
+    if (seen && bits == last) continue;
+    seen = true;
+    last = bits;
+    if (__atomic_load_n(&state[1], __ATOMIC_RELAXED) != 0) return;     // a 257th pattern has shown up: give up
+    if (bits == kCodeEmpty) {
+      if (atomicExch(&state[2], 1) == 0 && atomicAdd(&state[0], 1) >= kDictSize) atomicExch(&state[1], 1);
+      continue;
+    }
+    uint32_t h = uint32_t((bits * 0x9E3779B97F4A7C15ull) >> 54) & (kCodeSlots - 1);
+    int probes = 0;
+    for (; probes < kCodeSlots; ++probes, h = (h + 1) & (kCodeSlots - 1)) {
+      unsigned long long cur = __atomic_load_n(&table[h], __ATOMIC_RELAXED);
+      if (cur == bits) break;
+      if (cur == kCodeEmpty) {
+        cur = atomicCAS(&table[h], kCodeEmpty, bits);
+        if (cur == kCodeEmpty) {                          // this lane inserted the pattern
+          if (atomicAdd(&state[0], 1) >= kDictSize) atomicExch(&state[1], 1);
+          break;
+        }
+        if (cur == bits) break;
+      }
+    }
+    if (probes == kCodeSlots) atomicExch(&state[1], 1);   // full table (more than kDictSize patterns in flight at once)
+  }
+}
+
+// val8[i] = position of val[i]'s pattern among the `count` ascending patterns of `keys`
+__global__ __launch_bounds__(kBlock) void code_assign_kernel(int64_t n, const double* __restrict__ val,
+                                                              const unsigned long long* __restrict__ keys, int count,
+                                                              uint8_t* __restrict__ val8) {
+  __shared__ unsigned long long k[kDictSize];
+  k[threadIdx.x] = int(threadIdx.x) < count ? keys[threadIdx.x] : ~0ull;
+  __syncthreads();
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(val[i]);
+    int lo = 0, hi = count;                               // first position with k[pos] >= bits: the pattern itself
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (k[mid] < bits) lo = mid + 1;
+      else hi = mid;
+    }
+    val8[i] = uint8_t(lo);
+  }
+}
+
+// the code word of every row of the fixed-width copy: slot 0 in the low byte, slot 1 in the high byte (unused slots 0)
+__global__ __launch_bounds__(kBlock) void ell_code_kernel(int32_t m, const int32_t* __restrict__ rowptr,
+                                                           const uint8_t* __restrict__ val8, uint16_t* __restrict__ ecode) {
+  static_assert(kDirectWidth == 2, "one 16-bit code word per row");
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t r = int64_t(blockIdx.x) * kBlock + threadIdx.x; r < m; r += stride) {
+    const int s = rowptr[r], e = rowptr[r + 1];
+    const uint32_t c0 = s < e ? val8[s] : 0u, c1 = s + 1 < e ? val8[s + 1] : 0u;
+    ecode[r] = uint16_t(c0 | (c1 << 8));
+  }
+}
+
+// ell_code of a coded matrix that holds the fixed-width copy (built wherever that copy is built)
+static void build_ell_code(nss_csr_s& A, hipStream_t st) {
+  (void)hipFree(A.ell_code);
+  A.ell_code = nullptr;
+  if (!A.val8 || !A.ell_col || A.m == 0) return;
+  NSS_HIP(hipMalloc(&A.ell_code, sizeof(uint16_t) * size_t(A.m)));
+  hipLaunchKernelGGL(ell_code_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.val8,
+                     A.ell_code);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipStreamSynchronize(st));
+}
+
+// the codes go (a writer of `val`, nss_csr_drop_value_codes): every kernel reads `val` again
+static void drop_value_codes(nss_csr_s& A) {
+  if (!A.val8) return;
+  NSS_HIP(hipDeviceSynchronize());                       // no kernel may still read the arrays that go away
+  (void)hipFree(A.val8);
+  (void)hipFree(A.dict);
+  (void)hipFree(A.ell_code);
+  A.val8 = nullptr;
+  A.dict = nullptr;
+  A.ell_code = nullptr;
+  A.dict_count = 0;
+}
+
+static bool code_values(nss_csr_s& A, hipStream_t st) {
+  if (A.val8) return true;
+  if (A.val32 || !A.val || A.nnz == 0) return false;     // (fp32 storage has its own narrow form)
+  if (A.gb > 1) return false;                            // grouped column stream: its kernels have no coded form
+  unsigned long long* table = nullptr;
+  int32_t* state = nullptr;
+  uint8_t* val8 = nullptr;
+  double* dict = nullptr;
+  try {
+    NSS_HIP(hipMalloc(&table, sizeof(unsigned long long) * (kCodeSlots + kDictSize)));   // the table, then the sorted keys
+    NSS_HIP(hipMalloc(&state, sizeof(int32_t) * 4));
+    NSS_HIP(hipMemsetAsync(table, 0xff, sizeof(unsigned long long) * kCodeSlots, st));
+    NSS_HIP(hipMemsetAsync(state, 0, sizeof(int32_t) * 4, st));
+    hipLaunchKernelGGL(code_collect_kernel, dim3(stream_grid(A.nnz, kBlock * 8)), dim3(kBlock), 0, st, A.nnz, A.val, table,
+                       state);
+    NSS_CHECK_LAUNCH();
+    int32_t h_state[4] = {0, 1, 0, 0};
+    std::vector<unsigned long long> h_table(kCodeSlots);
+    NSS_HIP(hipMemcpyAsync(h_state, state, sizeof h_state, hipMemcpyDeviceToHost, st));
+    NSS_HIP(hipMemcpyAsync(h_table.data(), table, sizeof(unsigned long long) * kCodeSlots, hipMemcpyDeviceToHost, st));
+    NSS_HIP(hipStreamSynchronize(st));
+    std::vector<unsigned long long> keys;
+    if (h_state[1] == 0) {
+      for (unsigned long long k : h_table)
+        if (k != kCodeEmpty) keys.push_back(k);
+      if (h_state[2] != 0) keys.push_back(kCodeEmpty);
+      std::sort(keys.begin(), keys.end());               // ascending bit patterns: the codes do not depend on the race
+    }
+    if (h_state[1] == 0 && !keys.empty() && keys.size() <= size_t(kDictSize)) {
+      std::vector<unsigned long long> h_dict(kDictSize, 0ull);                // (unused slots: +0.0)
+      std::copy(keys.begin(), keys.end(), h_dict.begin());
+      NSS_HIP(hipMalloc(&dict, sizeof(double) * kDictSize));
+      NSS_HIP(hipMalloc(&val8, size_t(A.nnz) + 4));                          // padded like `val`
+      NSS_HIP(hipMemsetAsync(val8, 0, size_t(A.nnz) + 4, st));
+      NSS_HIP(hipMemcpyAsync(dict, h_dict.data(), sizeof(double) * kDictSize, hipMemcpyHostToDevice, st));
+      NSS_HIP(hipMemcpyAsync(table + kCodeSlots, keys.data(), sizeof(unsigned long long) * keys.size(),
+                             hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(code_assign_kernel, dim3(stream_grid(A.nnz, kBlock * 8)), dim3(kBlock), 0, st, A.nnz, A.val,
+                         table + kCodeSlots, int(keys.size()), val8);
+      NSS_CHECK_LAUNCH();
+      NSS_HIP(hipStreamSynchronize(st));                 // (h_dict / keys leave scope)
+      A.val8 = val8;
+      A.dict = dict;
+      A.dict_count = int32_t(keys.size());
+      val8 = nullptr;
+      dict = nullptr;
+      build_ell_code(A, st);
+    }
+  } catch (...) {
+    (void)hipFree(table);
+    (void)hipFree(state);
+    (void)hipFree(val8);
+    (void)hipFree(dict);
+    throw;
+  }
+  (void)hipFree(table);
+  (void)hipFree(state);
+  return A.val8 != nullptr;
+}
+
 static void direct_rows(nss_csr_s& A, hipStream_t st) {
 #if NSS_DIRECT_ROWS
   if (A.val32) return;                                   // (fp32 values: the stream kernel only)
@@ -634,6 +806,7 @@ static void direct_rows(nss_csr_s& A, hipStream_t st) {
       A.ell_val = eval;
       ecol = nullptr;
       eval = nullptr;
+      build_ell_code(A, st);                             // (a re-plan of a coded matrix)
     }
   } catch (...) {
     (void)hipFree(ecol);
@@ -752,6 +925,9 @@ int nss_csr_destroy(nss_csr_t a) {
     (void)hipFree(a->col);
     (void)hipFree(a->val);
     (void)hipFree(a->val32);
+    (void)hipFree(a->val8);
+    (void)hipFree(a->dict);
+    (void)hipFree(a->ell_code);
     (void)hipFree(a->rowblk);
     (void)hipFree(a->col16);
     (void)hipFree(a->blkbase);
@@ -799,8 +975,9 @@ static void replan(nss_csr_s& A, int products, int max_rows = 0, const uint8_t* 
   NSS_HIP(hipMalloc(&rowblk, sizeof(int32_t) * blk.size()));
   NSS_HIP(hipMemcpy(rowblk, blk.data(), sizeof(int32_t) * blk.size(), hipMemcpyHostToDevice));
   for (void* p : {(void*)A.rowblk, (void*)A.col16, (void*)A.blkbase, (void*)A.blkseg, (void*)A.pos16, (void*)A.ell_col,
-                  (void*)A.ell_val, (void*)A.blkdisp})
+                  (void*)A.ell_val, (void*)A.blkdisp, (void*)A.ell_code})    // (val8 / dict stay: per entry in CSR order)
     (void)hipFree(p);
+  A.ell_code = nullptr;
   A.blkdisp = nullptr;
   A.disp_period = 0.0;
   A.disp_planes = 0;
@@ -974,7 +1151,9 @@ int nss_csr_spmv_f64(nss_csr_t a, double alpha, const double* x, double beta, do
   return guarded([&] {
     NSS_REQUIRE(a != nullptr, "csr_spmv: NULL matrix");
     NSS_REQUIRE(x != y, "csr_spmv: x must not alias y");
-    launch_csr_stream_any(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
+    // (the one user of EpiAxpby with a coded form; launch_csr_stream_any and its other users keep reading `val`)
+    if (a->val32) launch_csr_stream_any(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
+    else launch_csr_stream_coded(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
   });
 }
 
@@ -1020,13 +1199,18 @@ int nss_csr_info(nss_csr_t a, int32_t* nrows, int32_t* ncols, int64_t* nnz, int3
     // bases per row block, or 4-byte columns -- what the plain SpMV of this matrix streams), the row
     // pointers, x once and y once.  (The CSR fp64/int32 textbook figure is 12 nnz + ...; pricing a
     // launch that streams 10 bytes per entry at 12 would overstate its bandwidth.)
-    if (algorithmic_bytes && a->ell_col)      // fixed-width copy: 12 bytes per slot, no row pointers
+    // A coded matrix (nss_csr_code_values) streams 1 byte per entry and the 2-KiB dictionary once per row block.
+    const bool coded = a->coded() && !a->val32;
+    if (algorithmic_bytes && a->ell_col && coded && a->ell_code)   // 8 bytes of columns + one 16-bit code word per row
+      *algorithmic_bytes = int64_t(4 * nss::kDirectWidth + 2) * a->m + int64_t(sizeof(double)) * kDictSize * a->nblk +
+                           8 * int64_t(a->n) + 8 * int64_t(a->m);
+    else if (algorithmic_bytes && a->ell_col)      // fixed-width copy: 12 bytes per slot, no row pointers
       *algorithmic_bytes = int64_t(12) * nss::kDirectWidth * a->m + 8 * int64_t(a->n) + 8 * int64_t(a->m);
     else if (algorithmic_bytes)
       *algorithmic_bytes = ((a->col16 || a->pos16) ? 2 * (a->nnz / a->gb) +
                                                            int64_t(4) * (a->blkseg ? kSegWords : kWindows) * a->nblk
                                                      : 4 * a->nnz) +
-                           (a->val32 ? 4 : 8) * a->nnz +
+                           (coded ? a->nnz + int64_t(sizeof(double)) * kDictSize * a->nblk : (a->val32 ? 4 : 8) * a->nnz) +
                            4 * (int64_t(a->m) + 1) + 8 * int64_t(a->n) + 8 * int64_t(a->m);
   });
 }
@@ -1036,6 +1220,7 @@ int nss_csr_round_f32(nss_csr_t a, nss_stream_t stream) {
     NSS_REQUIRE(a != nullptr, "csr_round_f32: NULL matrix");
     require_f64_values(a, "csr_round_f32");
     if (a->nnz == 0) return;
+    drop_value_codes(*a);                                // (a writer of `val`)
     hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(a->nnz, kBlock * 4)), dim3(kBlock), 0, as_stream(stream), a->nnz,
                        a->val, a->val, (float*)nullptr);
     NSS_CHECK_LAUNCH();
@@ -1056,6 +1241,7 @@ int nss_csr_narrow_f32(nss_csr_t a, nss_stream_t stream) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr, "csr_narrow_f32: NULL matrix");
     if (a->val32) return;                                // already narrow
+    drop_value_codes(*a);                                // (`val` goes)
     float* v32 = nullptr;
     NSS_HIP(hipMalloc(&v32, sizeof(float) * size_t(a->nnz + 4)));   // (+4 as `val`: paired loads may touch the end)
     try {
@@ -1095,7 +1281,36 @@ int nss_csr_narrow_f32(nss_csr_t a, nss_stream_t stream) {
 int nss_csr_value_bytes(nss_csr_t a, int64_t* bytes) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && bytes != nullptr, "csr_value_bytes: NULL argument");
-    *bytes = (a->val32 ? int64_t(sizeof(float)) : int64_t(sizeof(double))) * a->nnz;
+    *bytes = (a->val32 ? int64_t(sizeof(float)) : a->coded() ? int64_t(1) : int64_t(sizeof(double))) * a->nnz;
+  });
+}
+
+int nss_csr_code_values(nss_csr_t a, int32_t* coded, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr, "csr_code_values: NULL matrix");
+    const bool ok = code_values(*a, as_stream(stream));
+    if (coded) *coded = ok ? 1 : 0;
+  });
+}
+
+int nss_csr_drop_value_codes(nss_csr_t a) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr, "csr_drop_value_codes: NULL matrix");
+    drop_value_codes(*a);
+  });
+}
+
+int nss_csr_value_code_mode(int32_t mode) {
+  return guarded([&] {
+    NSS_REQUIRE(mode >= -1 && mode <= 1, "csr_value_code_mode: -1 (automatic), 0 (never) or 1 (whenever possible)");
+    g_value_code_mode = mode;
+  });
+}
+
+int nss_csr_value_codes_wanted(int64_t rows, int32_t* wanted) {
+  return guarded([&] {
+    NSS_REQUIRE(wanted != nullptr, "csr_value_codes_wanted: NULL argument");
+    *wanted = g_value_code_mode == 1 || (g_value_code_mode < 0 && rows >= int64_t(NSS_VALUE_CODES_MIN_ROWS)) ? 1 : 0;
   });
 }
 

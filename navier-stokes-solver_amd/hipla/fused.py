@@ -210,6 +210,35 @@ def plan_for_textbook_bpcg(a_matrix, pre_a):
     a_matrix.handle.plan_for_blocks(pa.bjac.handle)
 
 
+def code_values_together(eng, mats):
+    """One-byte value codes (nss_csr_code_values) for ALL of `mats` or for none of them: a matrix with more than 256
+    distinct value patterns leaves the others as they were.  Whether to try at all is the library's decision
+    (nss_csr_value_codes_wanted: the NSS_VALUE_CODES override, else by the rows of the largest matrix).  Returns
+    whether every matrix holds codes now."""
+    lib = eng.lib
+    if not all(hasattr(lib, name) for name in ("nss_csr_code_values", "nss_csr_value_codes_wanted")):
+        return False                                 # (older A/B builds of the library)
+    if not all(isinstance(m, SparseMatrix) and hasattr(m.handle, "code_values") for m in mats):
+        return False
+    wanted = C.c_int32()
+    eng._check(lib.nss_csr_value_codes_wanted(max(m.height for m in mats), C.byref(wanted)))
+    if not wanted.value:
+        return False
+    newly = []
+    for m in mats:
+        was_coded = m.handle.value_bytes() == m.handle.nnz
+        # coded means: its kernels stream the codes now (value_bytes says what they read), not merely that codes exist
+        if not (m.handle.code_values() and m.handle.value_bytes() == m.handle.nnz):
+            for h in newly:                          # all or nothing: what this call coded goes again
+                h.drop_value_codes()
+            if not was_coded:
+                m.handle.drop_value_codes()
+            return False
+        if not was_coded:
+            newly.append(m.handle)
+    return True
+
+
 def _extension_is_in_place_safe(H):
     """`t1 += H t1` runs in place on the device: the rows of H that hold entries (interior dofs) must
     not appear among its columns (coupling dofs)."""
@@ -435,6 +464,9 @@ class Bpcg2Loop(FusedLoop):
         # block Jacobi alone as preA: B^T's row blocks are planned around its blocks and C1 applies it in its epilogue
         self.c1_applies_bjac = (pa.bjac is not None and pa.diag is None and pa.amg is None and condensed is None
                                 and hasattr(matBT.handle, "plan_for_blocks") and matBT.handle.plan_for_blocks(pa.bjac.handle))
+        # one-byte value codes for A, B and B^T (C1 / C23 then stream 1 byte per entry instead of 8: same bits) on the
+        # single-GPU compact plan, all or nothing: info() and the launches stay consistent
+        self.value_coded = (condensed is None and not distributed and code_values_together(eng, (matA, matB, matBT)))
         st.A, st.B, st.BT = matA.handle.ptr, matB.handle.ptr, matBT.handle.ptr
         write_pre(st, pa)
         st.k = float(k) * pa.scale

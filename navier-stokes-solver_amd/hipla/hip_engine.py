@@ -48,6 +48,10 @@ def _signatures():
         "nss_csr_round_f32": (C.c_int, [vp, vp]),
         "nss_csr_narrow_f32": (C.c_int, [vp, vp]),
         "nss_csr_value_bytes": (C.c_int, [vp, c_i64_p]),
+        "nss_csr_code_values": (C.c_int, [vp, c_i32_p, vp]),
+        "nss_csr_drop_value_codes": (C.c_int, [vp]),
+        "nss_csr_value_code_mode": (C.c_int, [i32]),
+        "nss_csr_value_codes_wanted": (C.c_int, [i64, c_i32_p]),
         "nss_csr_index_width": (C.c_int, [vp, c_i32_p]),
         "nss_csr_index_group": (C.c_int, [vp, c_i32_p]),
         "nss_csr_operand_form": (C.c_int, [vp, c_i32_p]),
@@ -190,6 +194,8 @@ def load_library(path=None):
         fn.argtypes = args
     if os.environ.get("NSS_STREAM_LOADS") and hasattr(lib, "nss_stream_loads_mode"):     # measurements: -1 / 0 / 1
         lib.nss_stream_loads_mode(int(os.environ["NSS_STREAM_LOADS"]))
+    if os.environ.get("NSS_VALUE_CODES") and hasattr(lib, "nss_csr_value_code_mode"):    # measurements: -1 / 0 / 1
+        lib.nss_csr_value_code_mode(int(os.environ["NSS_VALUE_CODES"]))
     if os.environ.get("NSS_COND_FUSE") and hasattr(lib, "nss_cond_fuse_mode"):           # measurements: 0 / 1
         lib.nss_cond_fuse_mode(int(os.environ["NSS_COND_FUSE"]))
     if os.environ.get("NSS_DISPATCH_PLANES") and hasattr(lib, "nss_csr_dispatch_mode"):   # measurements: -1 / 0 / T
@@ -248,6 +254,25 @@ class _CsrHandle:
                            else lib.nss_csr_pair_staged(self.ptr, C.byref(out)))
         return bool(out.value)
 
+    def code_values(self):
+        """Store one-byte value codes beside the values when the matrix has at most 256 distinct value patterns
+        (nss_csr_code_values, set-up only); returns whether it holds codes now."""
+        lib = self.engine.lib
+        if not hasattr(lib, "nss_csr_code_values"):                  # (absent in older A/B builds)
+            return False
+        out = C.c_int32()
+        self.engine._check(lib.nss_csr_code_values(self.ptr, C.byref(out), self.engine.stream))
+        return bool(out.value)
+
+    def drop_value_codes(self):
+        self.engine._check(self.engine.lib.nss_csr_drop_value_codes(self.ptr))
+
+    def value_bytes(self):
+        """Bytes of the value stream the kernels read: 8, 4 (fp32 storage) or 1 (value codes) per entry."""
+        out = C.c_int64()
+        self.engine._check(self.engine.lib.nss_csr_value_bytes(self.ptr, C.byref(out)))
+        return out.value
+
     def info(self):
         lib = self.engine.lib
         m, n, nb, rg = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -266,7 +291,7 @@ class _CsrHandle:
                 "dispatch_period": period.value, "dispatch_planes": planes.value,
                 "rows": m.value, "cols": n.value, "nnz": nnz.value, "row_blocks": nb.value,
                 "lanes_per_row": rg.value, "algorithmic_bytes": nbytes.value, "index_bytes": width.value,
-                "index_group": group.value}
+                "index_group": group.value, "value_bytes": self.value_bytes()}
 
     def __del__(self):
         try:
