@@ -32,19 +32,19 @@ static void cycle(const nss_amg_s& a, int l, const double* b, double* out, hipSt
                   double scale = 1.0, bool accumulate = false) {
   const AmgLevel& lv = a.levels[l];
   if (l == int(a.levels.size()) - 1) {
-    launch_csr_stream_any(*a.coarse_inverse, b, EpiAxpby{scale, accumulate ? 1.0 : 0.0, out, done}, st);   // x = A^-1 b
+    launch_csr<kF32>(*a.coarse_inverse, b, EpiAxpby{scale, accumulate ? 1.0 : 0.0, out, done}, st);   // x = A^-1 b
     return;
   }
   const int n = lv.n;
   hipLaunchKernelGGL(amg_diag_kernel, dim3(stream_grid(n, kBlock * 4)), dim3(kBlock), 0, st, n, a.omega, lv.dinv, b,
                      lv.x, done);
   NSS_CHECK_LAUNCH();
-  launch_csr_stream_any(*lv.A, lv.x, EpiResidual{b, lv.r, done}, st);
+  launch_csr<kF32>(*lv.A, lv.x, EpiResidual{b, lv.r, done}, st);
   const AmgLevel& next = a.levels[l + 1];
-  launch_csr_stream_any(*lv.R, lv.r, EpiAxpby{1.0, 0.0, next.b, done}, st);
+  launch_csr<kF32>(*lv.R, lv.r, EpiAxpby{1.0, 0.0, next.b, done}, st);
   cycle(a, l + 1, next.b, next.y, st, done);
-  launch_csr_stream_any(*lv.P, next.y, EpiAxpby{1.0, 1.0, lv.x, done}, st);
-  launch_csr_stream_any(*lv.A, lv.x, EpiJacobi{b, lv.x, lv.dinv, out, a.omega, scale, done, accumulate}, st);
+  launch_csr<kF32>(*lv.P, next.y, EpiAxpby{1.0, 1.0, lv.x, done}, st);
+  launch_csr<kF32>(*lv.A, lv.x, EpiJacobi{b, lv.x, lv.dinv, out, a.omega, scale, done, accumulate}, st);
 }
 
 
@@ -299,7 +299,7 @@ static int g_amg_batch = 1;
 void amg_apply(const nss_amg_s& a, double bscale, const double* b, double* x, hipStream_t st, const int32_t* done,
                bool accumulate) {
   if (a.T) {                                         // auxiliary-space mode: x (+)= T (sum_c V_c) T^T (bscale b)
-    launch_csr_stream_any(*a.TT, b, EpiAxpby{bscale, 0.0, a.aux_r, done}, st);
+    launch_csr<kF32>(*a.TT, b, EpiAxpby{bscale, 0.0, a.aux_r, done}, st);
     if (!a.multi.empty() && g_amg_batch) {           // one shared hierarchy: all components in one cycle
       const nss_amg_s& h = *a.comps[0];
       const int64_t n0 = h.levels[0].n;
@@ -309,7 +309,7 @@ void amg_apply(const nss_amg_s& a, double bscale, const double* b, double* x, hi
     } else
     for (size_t c = 0; c < a.comps.size(); ++c)
       cycle(*a.comps[c], 0, a.aux_r + a.comp_off[c], a.aux_z + a.comp_off[c], st, done, 1.0);
-    launch_csr_stream_any(*a.T, a.aux_z, EpiAxpby{1.0, accumulate ? 1.0 : 0.0, x, done}, st);
+    launch_csr<kF32>(*a.T, a.aux_z, EpiAxpby{1.0, accumulate ? 1.0 : 0.0, x, done}, st);
     return;
   }
   cycle(a, 0, b, x, st, done, bscale, accumulate);

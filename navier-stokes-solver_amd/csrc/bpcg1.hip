@@ -416,19 +416,19 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
                          fused_j ? s.A->jb_order : nullptr, fused_j ? J->run : nullptr, fused_j ? J->inv_sym : nullptr,
                          fused_j ? J->nblocks : 0, fused_j ? J->bs : 0};
       const EpiV1c e1c{s.ctrl, s.t1[1], s.t2[1], top, s.scal, s.hist, it};
-      if (!launch_csr_stream_dual(*s.A, s.d[0], e1, *s.B, s.d[0], e1c, st, lds)) {
-        launch_csr_stream(*s.A, s.d[0], e1, st, 0, -1, lds);    // (opens the iteration; the second launch repeats the
-        launch_csr_stream(*s.B, s.d[0], e1c, st);               //  test from the same scalars: same outcome)
+      if (!launch_csr_dual(*s.A, s.d[0], e1, *s.B, s.d[0], e1c, st, lds)) {
+        launch_csr(*s.A, s.d[0], e1, st, 0, -1, lds);    // (opens the iteration; the second launch repeats the
+        launch_csr(*s.B, s.d[0], e1c, st);               //  test from the same scalars: same outcome)
       }
     } else {
     // V1a and V1c multiply the same operand (du) and do not depend on each other: one launch
     const EpiStore1 e1a{s.ctrl, s.t1[0]};
     const EpiV1c e1c{s.ctrl, s.t1[1], s.t2[1]};
-    if (!launch_csr_stream_dual(*s.A, s.d[0], e1a, *s.B, s.d[0], e1c, st)) {
-      launch_csr_stream(*s.A, s.d[0], e1a, st);
-      launch_csr_stream(*s.B, s.d[0], e1c, st);
+    if (!launch_csr_dual(*s.A, s.d[0], e1a, *s.B, s.d[0], e1c, st)) {
+      launch_csr(*s.A, s.d[0], e1a, st);
+      launch_csr(*s.B, s.d[0], e1c, st);
     }
-    launch_csr_stream(*s.BT, s.d[1], EpiV1b{s.ctrl, s.t1[0], s.t2[0], s.pre_amg ? nullptr : s.pre_diag, s.k}, st);
+    launch_csr(*s.BT, s.d[1], EpiV1b{s.ctrl, s.t1[0], s.t2[0], s.pre_amg ? nullptr : s.pre_diag, s.k}, st);
     }
     // t2 = -k preA t1 (t1 holds -K u here) where no epilogue above has formed it (point / fused block Jacobi alone)
     if (s.pre_amg || (s.pre_bjac && !fused_j)) pre_a_apply(pre_a_of(s, s.n_u), -s.k, s.t1[0], s.t2[0], nullptr, s.ctrl, st);
@@ -437,9 +437,9 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
     if (dist) exchange(*dist->d, halo_of(dist->hu, s.t2[0]), st);
     // V3a and V3b (operand t2u) likewise
     const EpiV3 e3a{s.ctrl, s.t1[0], s.d[0], s.partials_a}, e3b{s.ctrl, s.t1[1], s.d[1], s.partials_b};
-    if (!launch_csr_stream_dual(*s.A, s.t2[0], e3a, *s.B, s.t2[0], e3b, st)) {
-      launch_csr_stream(*s.A, s.t2[0], e3a, st);
-      launch_csr_stream(*s.B, s.t2[0], e3b, st);
+    if (!launch_csr_dual(*s.A, s.t2[0], e3a, *s.B, s.t2[0], e3b, st)) {
+      launch_csr(*s.A, s.t2[0], e3a, st);
+      launch_csr(*s.B, s.t2[0], e3b, st);
     }
     if (!fast) scalar_step(s, 1, it, kPSum, s.A->nblk, s.partials_a, s.B->nblk, s.partials_b, st);
     if (dist) allreduce_sum(*dist->d, s.scal + P_DSUM_LOC, s.scal + P_DSUM, 1, st);
@@ -455,7 +455,7 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
   }
   if (on(4)) {
     if (dist) exchange(*dist->d, halo_of(dist->hu, s.a[0]), st);
-    launch_csr_stream(*s.B, s.a[0], EpiV5{s.ctrl, s.a[1], s.minv, s.r[1], s.t1[1], s.partials_b}, st);
+    launch_csr(*s.B, s.a[0], EpiV5{s.ctrl, s.a[1], s.minv, s.r[1], s.t1[1], s.partials_b}, st);
     if (!fast) scalar_step(s, 2, it, kPSum, p_grid(s), s.partials_c, s.B->nblk, s.partials_b, st);
     if (dist) allreduce_sum(*dist->d, s.scal + P_RHON_LOC, s.scal + P_RHON, 1, st);
   }

@@ -871,18 +871,18 @@ void bpcg2_spmv_phase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, i
       // the point-Jacobi apply rides in the epilogue unless an AMG term comes first
       EpiK1 e{s.ctrl, s.scal, s.u0, s.q, s.z0, s.t2, s.s0, s.w0, s.t0, s.t1,
               (s.pre_amg || s.pre_dist_amg || s.pre_dist_aux || s.cond_HT) ? nullptr : s.pre_diag, s.k, it};
-      launch_csr_stream(*s.BT, s.s1, e, st, b0, b1);
+      launch_csr(*s.BT, s.s1, e, st, b0, b1);
       break;
     }
     case NSS_BPCG2_K2: {
       EpiK2 e{s.ctrl, s.t0, s.t1, s.s0, s.t2, s.t4, s.partials_a, (s.ghost_mode && ghost_tail) ? s.ghost_n : 0, s.ghost_map,
               s.ghost_s0, s.t4 + s.n_u};
-      launch_csr_stream(*s.A, s.t1, e, st, b0, b1);
+      launch_csr(*s.A, s.t1, e, st, b0, b1);
       break;
     }
     case NSS_BPCG2_K3: {
       EpiK3 e{s.ctrl, s.s1, s.t3, s.partials_b};
-      launch_csr_stream(*s.B, s.t4, e, st, b0, b1);
+      launch_csr(*s.B, s.t4, e, st, b0, b1);
       break;
     }
     default:
@@ -909,9 +909,9 @@ static bool cond_fused(const nss_bpcg2_t& s) {
 // trailing columns.
 static void bpcg2_cond_fused_step(const nss_bpcg2_t& s, hipStream_t st) {
   const nss_bjac_s& j = *s.pre_bjac;
-  launch_csr_stream(*j.cond_HTp, s.t0, EpiCondLift{s.ctrl, j.rowdof, s.t0, j.xt, j.yt}, st);
+  launch_csr(*j.cond_HTp, s.t0, EpiCondLift{s.ctrl, j.rowdof, s.t0, j.xt, j.yt}, st);
   bjac_sweep_permuted(j, s.k, false, s.ctrl, st, true);
-  launch_csr_stream(*j.gs_mat, j.yt, EpiCondResidual{s.ctrl, j.rowdof, s.k, j.xt, j.yt, s.t2, s.t1}, st);
+  launch_csr(*j.gs_mat, j.yt, EpiCondResidual{s.ctrl, j.rowdof, s.k, j.xt, j.yt, s.t2, s.t1}, st);
   if (j.n_uncovered > 0) {
     hipLaunchKernelGGL(bpcg2_cond_outside_kernel, dim3((j.n_uncovered + kBlock - 1) / kBlock), dim3(kBlock), 0, st, s.ctrl,
                        j.n_uncovered, j.covered, s.k, s.t0, s.t2, s.t1);
@@ -920,7 +920,7 @@ static void bpcg2_cond_fused_step(const nss_bpcg2_t& s, hipStream_t st) {
   amg_apply(*s.pre_amg, 1.0, s.t2, s.t1, st, s.ctrl, true);
   bjac_gather_rows(j, s.t1, s.ctrl, st);
   bjac_sweep_permuted(j, s.k, true, s.ctrl, st, false);
-  launch_csr_stream(*j.cond_Hp, j.yt,
+  launch_csr(*j.cond_Hp, j.yt,
                     EpiCondLeave{s.ctrl, j.covered, j.cond_dinner, s.t0, s.t1, j.rowdof, j.yt, j.n_perm}, st);
 }
 
@@ -946,7 +946,7 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st, const nss_dist_s* d) 
   const double* src = s.t0;
   if (s.cond_HT) {                                   // harmonic_extension(): lift the residual first
     if (cond_slab) cond_exchange(s, *d, d->cond_lift, 1, st);
-    launch_csr_stream(*s.cond_HT, s.t0, EpiLift{s.ctrl, s.t0, s.cond_f}, st);
+    launch_csr(*s.cond_HT, s.t0, EpiLift{s.ctrl, s.t0, s.cond_f}, st);
     src = s.cond_f;
   }
   // t1 = k * preA src unless K1's epilogue has formed it (uncondensed, point Jacobi alone).  t2 is free here: the
@@ -955,8 +955,8 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st, const nss_dist_s* d) 
   if (p.term() || p.bjac || s.cond_HT) pre_a_apply(p, s.k, src, s.t1, s.t2, s.ctrl, st);
   if (s.cond_HT) {
     if (cond_slab) cond_exchange(s, *d, d->cond_ext, 2, st);
-    launch_csr_stream(*s.cond_H, s.t1, EpiExtendInPlace{s.ctrl, s.t1}, st);         // t1 += H t1
-    launch_csr_stream(*s.cond_inner, s.cond_f, EpiAddGuarded{s.ctrl, s.t1}, st);    // t1 += A_ii^-1 f
+    launch_csr(*s.cond_H, s.t1, EpiExtendInPlace{s.ctrl, s.t1}, st);         // t1 += H t1
+    launch_csr(*s.cond_inner, s.cond_f, EpiAddGuarded{s.ctrl, s.t1}, st);    // t1 += A_ii^-1 f
   }
 }
 
@@ -984,7 +984,7 @@ void bpcg2_phase(const nss_bpcg2_t& s, int which, int it, hipStream_t st) {
     case NSS_BPCG2_K4:
       if (s.dist_compact) throw Error("bpcg2: a state laid out for the compact partitioned plan takes the compact phases only");
       if (s.ghost_p_mode && s.ghost_p_n > 0)     // t3 on the ghost pressure rows (t4 and its ghosts are complete)
-        launch_csr_stream(*s.ghost_b, s.t4, EpiGuardedStore{s.ctrl, s.ghost_t3}, st);
+        launch_csr(*s.ghost_b, s.t4, EpiGuardedStore{s.ctrl, s.ghost_t3}, st);
       launch_k4(s, it, false, st);
       break;
     case NSS_BPCG2_SUM2:
@@ -1039,15 +1039,15 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
       const nss_bjac_s* J = s.pre_bjac;
       const size_t lds = fj ? sizeof(double) * kBlockRows : 0;
 #define NSS_C1(FOLD, NT, LAUNCH)                                                                                       \
-  LAUNCH(*s.BT, s.s1, EpiK1c<FOLD, NT>{close_args(s, FOLD), s.u0, s.q, s.z0, s.t2, s.s0, s.w0, s.t0, s.t1, dinv, s.k, it, \
+  LAUNCH<kCodes>(*s.BT, s.s1, EpiK1c<FOLD, NT>{close_args(s, FOLD), s.u0, s.q, s.z0, s.t2, s.s0, s.w0, s.t0, s.t1, dinv, s.k, it, \
                                        s.s1, s.w1, s.dist_compact ? s.ghost_n : 0, s.ghost_s0, s.ghost_w0,                 \
                                        fj ? s.BT->jb_first : nullptr, fj ? s.BT->jb_order : nullptr, fj ? J->run : nullptr, fj ? J->inv_sym : nullptr,   \
                                        fj ? J->nblocks : 0, fj ? J->bs : 0}, st, 0, -1, lds)
-      // (the _coded launchers: a matrix with value codes streams them, nss_csr_code_values; same bits)
-      if (nt && fold) NSS_C1(true, true, launch_csr_direct_coded);
-      else if (nt) NSS_C1(false, true, launch_csr_direct_coded);
-      else if (fold) NSS_C1(true, false, launch_csr_stream_coded);
-      else NSS_C1(false, false, launch_csr_stream_coded);
+      // (kCodes: a matrix with value codes streams them, nss_csr_code_values; same bits)
+      if (nt && fold) NSS_C1(true, true, launch_csr_direct);
+      else if (nt) NSS_C1(false, true, launch_csr_direct);
+      else if (fold) NSS_C1(true, false, launch_csr);
+      else NSS_C1(false, false, launch_csr);
 #undef NSS_C1
       if (!fj) bpcg2_k1_finish(s, st, d);
       break;
@@ -1056,9 +1056,9 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
       EpiK2c ea{s.ctrl, s.t0, s.s0, s.t2, s.partials_a};
       EpiK3c eb{s.ctrl, s.scal, s.t1, s.s0, s.s1, s.w1, s.t3, s.partials_b, it, s.n_p};
       // (coded form of the shared launch only when BOTH matrices hold value codes; each of the two launches by itself)
-      if (!launch_csr_stream_dual<EpiK2c, EpiK3c, true>(*s.A, s.t1, ea, *s.B, s.t1, eb, st)) {   // launch plans differ: two launches
-        launch_csr_stream_coded(*s.A, s.t1, ea, st);
-        launch_csr_stream_coded(*s.B, s.t1, eb, st);
+      if (!launch_csr_dual<kCodes>(*s.A, s.t1, ea, *s.B, s.t1, eb, st)) {   // launch plans differ: two launches
+        launch_csr<kCodes>(*s.A, s.t1, ea, st);
+        launch_csr<kCodes>(*s.B, s.t1, eb, st);
       }
       break;
     }

@@ -159,7 +159,7 @@ static void cg_check(const nss_cg_t* s) {
 }
 
 static void cg_iteration(const nss_cg_t& s, int it, hipStream_t st) {
-  launch_csr_stream(*s.A, s.p, EpiCgQ{s.ctrl, s.p, s.q, s.partials_a}, st);
+  launch_csr(*s.A, s.p, EpiCgQ{s.ctrl, s.p, s.q, s.partials_a}, st);
   hipLaunchKernelGGL(cg_sum_kernel, dim3(1), dim3(kLoopSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal, int(G_PQ));
   NSS_CHECK_LAUNCH();
   const bool fused_pre = !s.pre_bjac && !s.pre_amg;

@@ -19,6 +19,8 @@
 // blockIdx -> row-block map is XCD-aware: workgroups b and b+8 share an XCD (round-robin
 // dispatch), so XCD i walks its own contiguous eighth of the rows and its private 4 MiB
 // L2 keeps one window of x instead of all eight L2s caching the same window.
+// Host side: launch_csr<FORMS> (one matrix), launch_csr_dual<FORMS> (two matrices in one launch) pick the instantiation
+// -- value form, kernel, column form, lanes per row -- for a matrix; every launch of the library goes through them.
 #pragma once
 
 #include <type_traits>
@@ -238,7 +240,7 @@ struct nss_csr_s {
   double* fw_val = nullptr;
   int fw_state = 0;
   // fp32 value storage (nss_csr_narrow_f32): the values rounded once to fp32 and stored 4 bytes wide in `val32`; `val`
-  // is then NULL.  Only the kernel paths instantiated for it take such a matrix (launch_csr_stream_any, the joint AMG
+  // is then NULL.  Only the kernel paths instantiated for it take such a matrix (launch_csr with kF32, the joint AMG
   // cycle); every other path refuses it (view() without `narrow_ok`, require_f64_values) -- none reads it as doubles.
   float* val32 = nullptr;
   // Value codes (nss_csr_code_values): a matrix with at most kDictSize distinct 64-bit value patterns -- every operator
@@ -783,150 +785,108 @@ __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int
   epi.finish(b, red);
 }
 
-// one instantiation per lanes-per-row value of the launch plan
-#define NSS_FOR_PLAN(A, ONE)                                                                      \
-  switch ((A).rg) {                                                                                \
-    case 1: ONE(1, kChunk) break;                                                                  \
-    case 2: ONE(2, kChunk) break;                                                                  \
-    case 4: ONE(4, kChunk) break;                                                                  \
-    case 8: ONE(8, kChunk) break;                                                                  \
-    case 16: ONE(16, kChunk) break;                                                                \
-    case 32: ONE(32, kChunk) break;                                                                \
-    case 64: ONE(64, kChunk) break;                                                                \
-    default: throw Error("csr_stream: bad lanes-per-row in the launch plan");                      \
-  }
+// Value forms a launch site instantiates besides fp64 (the FORMS argument of the launchers below).  The value type is a
+// template parameter of the kernels, so every form a site asks for adds a full set of instantiations of its epilogue:
+// kF32 only where an fp32-storage preconditioner handle launches (the colour launches and residuals of the
+// Gauss-Seidel sweep, the single-vector AMG cycle, the residual between the half-sweeps), kCodes only in the launches
+// of the flagship loop (C1, C23), both in the plain SpMV.  A matrix in a form its site did not ask for takes the fp64
+// path: a coded matrix reads `val`, a narrowed one is refused (view()).
+enum : unsigned { kF64 = 0, kF32 = 1, kCodes = 2 };
 
-// the row-per-lane kernel alone (A must hold the fixed-width copy): for epilogue variants that only exist for it
-template <class Epi>
-inline void launch_csr_direct(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
-                              int b1 = -1, size_t dyn_lds = 0) {
-  if (b1 < 0) b1 = A.nblk;
-  if (A.m == 0 || b1 <= b0) return;
-  if (!A.ell_col) throw Error("csr_direct: the matrix has no fixed-width copy");
-  hipLaunchKernelGGL((csr_direct_kernel<Epi>), dim3(nss_csr_s::grid(b1 - b0)), dim3(kBlock), dyn_lds, st, A.view(b0, b1, 0),
-                     A.ell_col, A.ell_val, (const uint16_t*)nullptr, x, epi);
-  NSS_CHECK_LAUNCH();
-}
+template <int I>
+using Idx = std::integral_constant<int, I>;
+template <class VT>
+struct ValueTag { using type = VT; };
+// value types with grouped forms of the 16-bit column streams (a coded matrix is never grouped: nss_csr_s::coded)
+template <class VT>
+constexpr bool kHasGroupedForms = !std::is_same<VT, Coded8>::value;
 
-// ... and its coded form where the matrix holds value codes (only for the epilogues of the flagship loop and the plain
-// SpMV: every use doubles the instantiations of its epilogue)
-template <class Epi>
-inline void launch_csr_direct_coded(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
-                                    int b1 = -1, size_t dyn_lds = 0) {
-  if (!(A.coded() && A.ell_code)) {
-    launch_csr_direct(A, x, epi, st, b0, b1, dyn_lds);
-    return;
+// f(Idx<RG>) for the lanes-per-row value RG of the launch plan: one instantiation per value
+template <class F>
+inline void for_plan_lanes(const nss_csr_s& A, F&& f) {
+  switch (A.rg) {
+    case 1: f(Idx<1>{}); break;
+    case 2: f(Idx<2>{}); break;
+    case 4: f(Idx<4>{}); break;
+    case 8: f(Idx<8>{}); break;
+    case 16: f(Idx<16>{}); break;
+    case 32: f(Idx<32>{}); break;
+    case 64: f(Idx<64>{}); break;
+    default: throw Error("csr_stream: bad lanes-per-row in the launch plan");
   }
-  if (b1 < 0) b1 = A.nblk;
-  if (A.m == 0 || b1 <= b0) return;
-  if (!A.ell_col) throw Error("csr_direct: the matrix has no fixed-width copy");
-  hipLaunchKernelGGL((csr_direct_kernel<Epi, Coded8>), dim3(nss_csr_s::grid(b1 - b0)), dim3(kBlock), dyn_lds, st,
-                     A.view(b0, b1, 0), A.ell_col, A.ell_val, A.ell_code, x, epi);
-  NSS_CHECK_LAUNCH();
 }
 
 // the stream kernel over the row blocks [b0, b1) with value type VT (A is not empty and has no fixed-width copy)
-template <class Epi, class VT>
-inline void launch_csr_stream_vt(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0, int b1,
-                                 size_t dyn_lds) {
+template <class VT, class Epi>
+inline void launch_csr_stream_kernel(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0, int b1,
+                                     size_t dyn_lds) {
   constexpr bool kCanStage = EpiX<Epi>::type::kStageable;
   constexpr bool kCanPair = XPairable<typename EpiX<Epi>::type>::value;
   const int mode = A.idx_mode(kCanStage, kCanPair);
   const bool grp = mode != 0 && A.gb > 1;
   const CsrView v = A.view(b0, b1, mode, std::is_same<VT, float>::value);
   const dim3 grid(nss_csr_s::grid(b1 - b0)), block(kBlock);
-  if constexpr (std::is_same<VT, Coded8>::value) {           // (callers check A.coded(): one index per entry)
-#define NSS_LAUNCH_ONE(N, CHK)                                                                                  \
-  if (mode == 2) {                                                                                               \
-    if constexpr (kCanStage) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi); \
-  } else if (mode == 3) {                                                                                        \
-    if constexpr (kCanPair) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);  \
-  } else if (mode == 1) {                                                                                        \
-    hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);     \
-  } else {                                                                                                       \
-    hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 0, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);     \
-  }
-    NSS_FOR_PLAN(A, NSS_LAUNCH_ONE)
-#undef NSS_LAUNCH_ONE
-  } else {
-#define NSS_LAUNCH_ONE(N, CHK)                                                                                  \
-  if (mode == 2) {                                                                                               \
-    if constexpr (kCanStage) {                                                                                   \
-      if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, true, VT>), grid, block, dyn_lds, st, v, x, epi);     \
-      else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 2, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);        \
-    }                                                                                                            \
-  } else if (mode == 3) {                                                                                        \
-    if constexpr (kCanPair) {                                                                                    \
-      if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, true, VT>), grid, block, dyn_lds, st, v, x, epi);     \
-      else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 3, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);        \
-    }                                                                                                            \
-  } else if (mode == 1) {                                                                                        \
-    if (grp) hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, true, VT>), grid, block, dyn_lds, st, v, x, epi);       \
-    else hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 1, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);          \
-  } else {                                                                                                       \
-    hipLaunchKernelGGL((csr_stream_kernel<N, Epi, 0, CHK, false, VT>), grid, block, dyn_lds, st, v, x, epi);               \
-  }
-  NSS_FOR_PLAN(A, NSS_LAUNCH_ONE)
-#undef NSS_LAUNCH_ONE
-  }
+  for_plan_lanes(A, [&](auto lanes) {
+    const auto go = [&](auto idx) {     // ONE form of the column stream, grouped where the stream is and VT can be
+      constexpr int RG = decltype(lanes)::value, IDX = decltype(idx)::value;
+      constexpr bool kGrp = IDX != 0 && kHasGroupedForms<VT>;     // (false: both lines name the same instantiation)
+      if (kGrp && grp) hipLaunchKernelGGL((csr_stream_kernel<RG, Epi, IDX, kChunk, kGrp, VT>), grid, block, dyn_lds, st, v, x, epi);
+      else hipLaunchKernelGGL((csr_stream_kernel<RG, Epi, IDX, kChunk, false, VT>), grid, block, dyn_lds, st, v, x, epi);
+    };
+    if (mode == 2) { if constexpr (kCanStage) go(Idx<2>{}); }
+    else if (mode == 3) { if constexpr (kCanPair) go(Idx<3>{}); }
+    else if (mode == 1) go(Idx<1>{});
+    else go(Idx<0>{});
+  });
   NSS_CHECK_LAUNCH();
 }
 
-// rows of the row blocks [b0, b1) (default: all); fp64 values only (a narrowed matrix is refused: view())
-template <class Epi>
-inline void launch_csr_stream(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
+// A x into `epi` over the rows of the row blocks [b0, b1) (default: all), by the kernel and in the value form that the
+// matrix holds and FORMS allows: fp32 values (nss_csr_s::val32) under kF32, value codes (nss_csr_s::coded) under
+// kCodes, else fp64; the row-per-lane kernel where the matrix has the fixed-width copy, else the stream kernel.
+// DIRECT_ONLY (launch_csr_direct): instantiate the row-per-lane kernel alone.
+template <unsigned FORMS = kF64, bool DIRECT_ONLY = false, class Epi>
+inline void launch_csr(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0, int b1 = -1,
+                       size_t dyn_lds = 0) {
+  constexpr bool kF32Form = (FORMS & kF32) != 0 && !DIRECT_ONLY, kCodedForm = (FORMS & kCodes) != 0;
+  using CodedVT = std::conditional_t<kCodedForm, Coded8, double>;     // (form not asked for: the fp64 kernels either way)
+  if (b1 < 0) b1 = A.nblk;
+  if (A.m == 0 || b1 <= b0) return;
+  if constexpr (kF32Form) {
+    if (A.val32) {
+      NSS_REQUIRE(!A.ell_col, "csr_stream: a matrix with fp32 values has no fixed-width copy");
+      launch_csr_stream_kernel<float>(A, x, epi, st, b0, b1, dyn_lds);
+      return;
+    }
+  }
+  if (DIRECT_ONLY && !A.ell_col) throw Error("csr_direct: the matrix has no fixed-width copy");
+  if (A.ell_col) {
+    const dim3 grid(nss_csr_s::grid(b1 - b0)), block(kBlock);
+    const CsrView v = A.view(b0, b1, 0);
+    if (kCodedForm && A.coded() && A.ell_code)
+      hipLaunchKernelGGL((csr_direct_kernel<Epi, CodedVT>), grid, block, dyn_lds, st, v, A.ell_col, A.ell_val, A.ell_code, x, epi);
+    else
+      hipLaunchKernelGGL((csr_direct_kernel<Epi>), grid, block, dyn_lds, st, v, A.ell_col, A.ell_val, (const uint16_t*)nullptr, x, epi);
+    NSS_CHECK_LAUNCH();
+  } else if constexpr (!DIRECT_ONLY) {
+    if (kCodedForm && A.coded() && !A.val32) launch_csr_stream_kernel<CodedVT>(A, x, epi, st, b0, b1, dyn_lds);
+    else launch_csr_stream_kernel<double>(A, x, epi, st, b0, b1, dyn_lds);
+  }
+}
+
+// the row-per-lane kernel alone (A must hold the fixed-width copy): for epilogue variants that only exist for it
+template <unsigned FORMS = kF64, class Epi>
+inline void launch_csr_direct(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
                               int b1 = -1, size_t dyn_lds = 0) {
-  if (b1 < 0) b1 = A.nblk;
-  if (A.m == 0 || b1 <= b0) return;
-  if (A.ell_col) {
-    launch_csr_direct(A, x, epi, st, b0, b1, dyn_lds);
-    return;
-  }
-  launch_csr_stream_vt<Epi, double>(A, x, epi, st, b0, b1, dyn_lds);
-}
-
-// as launch_csr_stream, and a coded matrix (nss_csr_s::coded) streams its value codes: the stream kernel's Coded8
-// instantiation or the coded row-per-lane kernel.  Used only by the launches of the flagship loop (C1, C23) and the
-// plain SpMV: the value type is a template parameter, so every use doubles the instantiations of its epilogue.
-template <class Epi>
-inline void launch_csr_stream_coded(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
-                                    int b1 = -1, size_t dyn_lds = 0) {
-  if (!A.coded() || A.val32) {
-    launch_csr_stream(A, x, epi, st, b0, b1, dyn_lds);
-    return;
-  }
-  if (A.ell_col) {
-    launch_csr_direct_coded(A, x, epi, st, b0, b1, dyn_lds);
-    return;
-  }
-  if (b1 < 0) b1 = A.nblk;
-  if (A.m == 0 || b1 <= b0) return;
-  launch_csr_stream_vt<Epi, Coded8>(A, x, epi, st, b0, b1, dyn_lds);
-}
-
-// as launch_csr_stream, and a matrix with fp32 values (nss_csr_s::val32) takes the fp32 instantiation.  Used only
-// where an fp32-storage preconditioner handle launches (the colour launches and residuals of the Gauss-Seidel sweep,
-// the single-vector AMG cycle, the residual between the half-sweeps, the plain SpMV): the value type is a template
-// parameter of the kernels, so every use doubles the instantiations of its epilogue.
-template <class Epi>
-inline void launch_csr_stream_any(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0,
-                                  int b1 = -1, size_t dyn_lds = 0) {
-  if (!A.val32) {
-    launch_csr_stream(A, x, epi, st, b0, b1, dyn_lds);
-    return;
-  }
-  if (b1 < 0) b1 = A.nblk;
-  if (A.m == 0 || b1 <= b0) return;
-  NSS_REQUIRE(!A.ell_col, "csr_stream: a matrix with fp32 values has no fixed-width copy");
-  launch_csr_stream_vt<Epi, float>(A, x, epi, st, b0, b1, dyn_lds);
+  launch_csr<FORMS, true>(A, x, epi, st, b0, b1, dyn_lds);
 }
 
 // A and B in one launch when their launch plans agree (lanes per row, chunk) and the pair of column streams is
 // one of the instantiated ones; returns false (nothing launched) otherwise -- the caller then issues two launches.
-// CODED: instantiate the coded form too, taken when BOTH matrices are coded (otherwise both halves read `val`).
-template <class EpiA, class EpiB, bool CODED = false>
-inline bool launch_csr_stream_dual(const nss_csr_s& A, const double* xa, const EpiA& ea, const nss_csr_s& B,
-                                   const double* xb, const EpiB& eb, hipStream_t st, size_t dyn_lds = 0) {
+// FORMS & kCodes: instantiate the coded form too, taken when BOTH matrices are coded (otherwise both halves read `val`).
+template <unsigned FORMS = kF64, class EpiA, class EpiB>
+inline bool launch_csr_dual(const nss_csr_s& A, const double* xa, const EpiA& ea, const nss_csr_s& B, const double* xb,
+                            const EpiB& eb, hipStream_t st, size_t dyn_lds = 0) {
 #ifdef NSS_NO_DUAL        // measurements: the two halves as launches of their own
   return false;
 #endif
@@ -944,56 +904,29 @@ inline bool launch_csr_stream_dual(const nss_csr_s& A, const double* xa, const E
   const CsrView va = A.view(0, A.nblk, ma), vb = B.view(0, B.nblk, mb);
   const int ga = nss_csr_s::grid(A.nblk), gb = nss_csr_s::grid(B.nblk);
   const dim3 grid(ga + gb), block(kBlock);
-  if constexpr (CODED) {
-    // both halves stream value codes (never grouped: nss_csr_s::coded)
-    if (A.coded() && B.coded()) {
-#define NSS_DUAL_GO(N, CHK, IA, IB) \
-  hipLaunchKernelGGL((csr_stream_dual_kernel<N, EpiA, EpiB, IA, IB, CHK, false, Coded8>), grid, block, dyn_lds, st, va, vb, ga, gb, xa, xb, ea, eb)
-#define NSS_LAUNCH_DUAL_ONE(N, CHK)                                                        \
-  if (ma == 0) {                                                                            \
-    NSS_DUAL_GO(N, CHK, 0, 0);                                                              \
-  } else if (ma == 2 && mb == 2) {                                                          \
-    if constexpr (kStageA && kStageB) { NSS_DUAL_GO(N, CHK, 2, 2); }                        \
-  } else if (ma == 2 && mb == 3) {                                                          \
-    if constexpr (kStageA && kPairB) { NSS_DUAL_GO(N, CHK, 2, 3); }                         \
-  } else if (ma == 2) {                                                                     \
-    if constexpr (kStageA) { NSS_DUAL_GO(N, CHK, 2, 1); }                                   \
-  } else if (mb == 2) {                                                                     \
-    if constexpr (kStageB) { NSS_DUAL_GO(N, CHK, 1, 2); }                                   \
-  } else {                                                                                  \
-    NSS_DUAL_GO(N, CHK, 1, 1);                                                              \
-  }
-      NSS_FOR_PLAN(A, NSS_LAUNCH_DUAL_ONE)
-#undef NSS_LAUNCH_DUAL_ONE
-#undef NSS_DUAL_GO
-      NSS_CHECK_LAUNCH();
-      return true;
-    }
-  }
-#define NSS_DUAL_GO(N, CHK, IA, IB, G) \
-  hipLaunchKernelGGL((csr_stream_dual_kernel<N, EpiA, EpiB, IA, IB, CHK, G>), grid, block, dyn_lds, st, va, vb, ga, gb, xa, xb, ea, eb)
-#define NSS_DUAL_PAIR(N, CHK, IA, IB) \
-  if (grp) NSS_DUAL_GO(N, CHK, IA, IB, true); else NSS_DUAL_GO(N, CHK, IA, IB, false);
-#define NSS_LAUNCH_DUAL_ONE(N, CHK)                                                        \
-  if (ma == 0) {                                                                            \
-    NSS_DUAL_GO(N, CHK, 0, 0, false);                                                       \
-  } else if (ma == 2 && mb == 2) {                                                          \
-    if constexpr (kStageA && kStageB) { NSS_DUAL_PAIR(N, CHK, 2, 2) }                       \
-  } else if (ma == 2 && mb == 3) {                                                          \
-    if constexpr (kStageA && kPairB) { NSS_DUAL_PAIR(N, CHK, 2, 3) }                        \
-  } else if (ma == 2) {                                                                     \
-    if constexpr (kStageA) { NSS_DUAL_PAIR(N, CHK, 2, 1) }                                  \
-  } else if (mb == 2) {                                                                     \
-    if constexpr (kStageB) { NSS_DUAL_PAIR(N, CHK, 1, 2) }                                  \
-  } else {                                                                                  \
-    NSS_DUAL_PAIR(N, CHK, 1, 1)                                                             \
-  }
-  NSS_FOR_PLAN(A, NSS_LAUNCH_DUAL_ONE)
-#undef NSS_LAUNCH_DUAL_ONE
-#undef NSS_DUAL_PAIR
-#undef NSS_DUAL_GO
-  NSS_CHECK_LAUNCH();
-  return true;
+  const auto ladder = [&](auto vt) {
+    using VT = typename decltype(vt)::type;
+    for_plan_lanes(A, [&](auto lanes) {
+      const auto go = [&](auto ia, auto ib) {     // ONE pair of column streams, grouped where one is and VT can be
+        constexpr int RG = decltype(lanes)::value, IA = decltype(ia)::value, IB = decltype(ib)::value;
+        constexpr bool kGrp = IA != 0 && kHasGroupedForms<VT>;
+        if (kGrp && grp) hipLaunchKernelGGL((csr_stream_dual_kernel<RG, EpiA, EpiB, IA, IB, kChunk, kGrp, VT>), grid, block, dyn_lds, st, va, vb, ga, gb, xa, xb, ea, eb);
+        else hipLaunchKernelGGL((csr_stream_dual_kernel<RG, EpiA, EpiB, IA, IB, kChunk, false, VT>), grid, block, dyn_lds, st, va, vb, ga, gb, xa, xb, ea, eb);
+      };
+      if (ma == 0) go(Idx<0>{}, Idx<0>{});
+      else if (ma == 2 && mb == 2) { if constexpr (kStageA && kStageB) go(Idx<2>{}, Idx<2>{}); }
+      else if (ma == 2 && mb == 3) { if constexpr (kStageA && kPairB) go(Idx<2>{}, Idx<3>{}); }
+      else if (ma == 2) { if constexpr (kStageA) go(Idx<2>{}, Idx<1>{}); }
+      else if (mb == 2) { if constexpr (kStageB) go(Idx<1>{}, Idx<2>{}); }
+      else go(Idx<1>{}, Idx<1>{});
+    });
+    NSS_CHECK_LAUNCH();
+    return true;
+  };
+  constexpr bool kCodedForm = (FORMS & kCodes) != 0;
+  if (kCodedForm && A.coded() && B.coded())               // both halves stream value codes
+    return ladder(ValueTag<std::conditional_t<kCodedForm, Coded8, double>>{});
+  return ladder(ValueTag<double>{});
 }
 
 // y = alpha * A x + beta * y

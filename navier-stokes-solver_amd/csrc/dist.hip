@@ -196,26 +196,26 @@ void dist_amg_apply(const nss_dist_amg_s& a, double scale, const double* b, doub
   double* x = a.halo.ext;                                                    // owned entries first
   diag_apply(a.n, a.wdinv, 1.0, b, 0.0, x, done, st);                        // pre-smoothing from zero
   exchange_on(*a.d, a.channel, a.halo, done, st);
-  launch_csr_stream(*a.A, x, EpiResidual{b, a.res, done}, st);               // res = b - A x
-  launch_csr_stream(*a.R, a.res, EpiAxpby{1.0, 0.0, a.rc_local, done}, st);  // this slab's share of R res
+  launch_csr(*a.A, x, EpiResidual{b, a.res, done}, st);               // res = b - A x
+  launch_csr(*a.R, a.res, EpiAxpby{1.0, 0.0, a.rc_local, done}, st);  // this slab's share of R res
   // out of place: once *done is set the kernels return at once but the RCCL collectives still run -- an in-place
   // all-reduce would multiply the frozen rc by the number of ranks on every further iteration (the mailbox transport's
   // vector all-reduce skips, as its exchanges do)
   allreduce_sum(*a.d, a.rc_local, a.rc, size_t(a.nc), st, done);
   amg_apply(*a.coarse, 1.0, a.rc, a.ec, st, done);                           // levels 1.. on every rank
-  launch_csr_stream(*a.P, a.ec, EpiAxpby{1.0, 1.0, x, done}, st);            // x += P e
+  launch_csr(*a.P, a.ec, EpiAxpby{1.0, 1.0, x, done}, st);            // x += P e
   exchange_on(*a.d, a.channel, a.halo, done, st);
-  launch_csr_stream(*a.A, x, EpiJacobi{b, x, a.wdinv, y, 1.0, scale, done}, st);   // y = scale (x + w D^-1 (b - A x))
+  launch_csr(*a.A, x, EpiJacobi{b, x, a.wdinv, y, 1.0, scale, done}, st);   // y = scale (x + w D^-1 (b - A x))
 }
 
 void dist_aux_apply(const nss_dist_aux_s& a, double scale, const double* b, double* y, bool accumulate, hipStream_t st,
                     const int32_t* done) {
   NSS_HIP(hipMemcpyAsync(a.halo_x.ext, b, sizeof(double) * size_t(a.n_u), hipMemcpyDeviceToDevice, st));   // (scratch: unguarded)
   exchange_on(*a.d, a.ch_x, a.halo_x, done, st);
-  launch_csr_stream(*a.TT, a.halo_x.ext, EpiAxpby{1.0, 0.0, a.r_aux, done}, st);                // transform.T
+  launch_csr(*a.TT, a.halo_x.ext, EpiAxpby{1.0, 0.0, a.r_aux, done}, st);                // transform.T
   dist_amg_apply(*a.amg, 1.0, a.r_aux, a.halo_e.ext, st, done);                                 // V-cycle on the stacked Laplacian
   exchange_on(*a.d, a.ch_e, a.halo_e, done, st);
-  launch_csr_stream(*a.T, a.halo_e.ext, EpiAxpby{scale, accumulate ? 1.0 : 0.0, y, done}, st);  // transform
+  launch_csr(*a.T, a.halo_e.ext, EpiAxpby{scale, accumulate ? 1.0 : 0.0, y, done}, st);  // transform
 }
 
 }  // namespace nss

@@ -335,7 +335,7 @@ static void lz_step(const nss_lanczos_t& s, int j, bool last, hipStream_t st) {
   double* v_new = s.v[(j + 1) % 3];
   double* z = s.z[j % 2];
   double* z_new = s.z[(j + 1) % 2];
-  launch_csr_stream(*s.A, z, EpiLanczosP{s.ctrl, z, s.p, s.partials_a}, st);
+  launch_csr(*s.A, z, EpiLanczosP{s.ctrl, z, s.p, s.partials_a}, st);
   if (lz_fused(s)) {
     const bool fold_a = lz_fold_a(s);
     if (!fold_a) {

@@ -515,17 +515,17 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
   EpiMAccDot e_b{s.ctrl, k, 0, s.kz[1], s.z[zc][1], s.partials_b, set};
   if (m_merged_rows(s)) {                   // one launch: rows of A (+ their row of B^T z1) and rows of B
     EpiMRowsA e_a{s.ctrl, k, s.kz[0], s.z[zc][0], s.partials_a, set, s.BT->fw_col, s.BT->fw_val, s.z[zc][1]};
-    if (!launch_csr_stream_dual(*s.A, s.z[zc][0], e_a, *s.B, s.z[zc][0], e_b, st)) {
-      launch_csr_stream(*s.A, s.z[zc][0], e_a, st);
-      launch_csr_stream(*s.B, s.z[zc][0], e_b, st);
+    if (!launch_csr_dual(*s.A, s.z[zc][0], e_a, *s.B, s.z[zc][0], e_b, st)) {
+      launch_csr(*s.A, s.z[zc][0], e_a, st);
+      launch_csr(*s.B, s.z[zc][0], e_b, st);
     }
   } else {
   EpiMStore e_bt{s.ctrl, k, s.kz[0], set};
-  if (!launch_csr_stream_dual(*s.BT, s.z[zc][1], e_bt, *s.B, s.z[zc][0], e_b, st)) {
-    launch_csr_stream(*s.BT, s.z[zc][1], e_bt, st);
-    launch_csr_stream(*s.B, s.z[zc][0], e_b, st);
+  if (!launch_csr_dual(*s.BT, s.z[zc][1], e_bt, *s.B, s.z[zc][0], e_b, st)) {
+    launch_csr(*s.BT, s.z[zc][1], e_bt, st);
+    launch_csr(*s.B, s.z[zc][0], e_b, st);
   }
-  launch_csr_stream(*s.A, s.z[zc][0], EpiMAccDot{s.ctrl, k, 1, s.kz[0], s.z[zc][0], s.partials_a, set}, st);
+  launch_csr(*s.A, s.z[zc][0], EpiMAccDot{s.ctrl, k, 1, s.kz[0], s.z[zc][0], s.partials_a, set}, st);
   }
   }
   if (on(2) && !fold) {

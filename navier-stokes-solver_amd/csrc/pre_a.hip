@@ -70,7 +70,7 @@ void pre_a_apply(const PreA& p, double scale, const double* x, double* y, double
       bjac_smooth(j, scale, x, y, false, done, st);
     }
     if (p.exchange_y) exchange_on(*p.dist_aux->d, p.dist_aux->ch_y, p.dist_aux->halo_y, done, st);
-    launch_csr_stream_any(p.residual_A(), y, EpiScaledResidual{done, scale, x, scratch}, st);
+    launch_csr<kF32>(p.residual_A(), y, EpiScaledResidual{done, scale, x, scratch}, st);
     term_apply(p, 1.0, scratch, y, true, done, st);
     bjac_smooth(j, scale, x, y, true, done, st, j.gs_permuted ? kGsKeepX : 0);   // (x again)
   } else if (p.term()) {                             // additive MypreA (:383): term + Jacobi part

@@ -357,7 +357,7 @@ static void gs_sweep_permuted(const nss_bjac_s& j, double xscale, bool backward,
       }
       continue;
     }
-    launch_csr_stream_any(*j.gs_mat, j.yt, epi, st, j.color_rowblk[c], j.color_rowblk[c + 1], sizeof(double) * kGsRows);
+    launch_csr<kF32>(*j.gs_mat, j.yt, epi, st, j.color_rowblk[c], j.color_rowblk[c + 1], sizeof(double) * kGsRows);
   }
 }
 
@@ -414,7 +414,7 @@ void bjac_smooth(const nss_bjac_s& j, double xscale, const double* x, double* y,
   const int nc = int(j.color_ptr.size()) - 1;
   for (int k = 0; k < nc; ++k) {
     const int c = backward ? nc - 1 - k : k;
-    launch_csr_stream_any(*j.gs_mat, y, EpiGsResidual{done, j.rowdof, x, j.res, xscale}, st, j.color_rowblk[c],
+    launch_csr<kF32>(*j.gs_mat, y, EpiGsResidual{done, j.rowdof, x, j.res, xscale}, st, j.color_rowblk[c],
                       j.color_rowblk[c + 1]);
     switch (j.bs) {
 #define NSS_GS(N) case N: launch_bgs_solve<N>(j, c, y, done, st); break;

@@ -1151,9 +1151,8 @@ int nss_csr_spmv_f64(nss_csr_t a, double alpha, const double* x, double beta, do
   return guarded([&] {
     NSS_REQUIRE(a != nullptr, "csr_spmv: NULL matrix");
     NSS_REQUIRE(x != y, "csr_spmv: x must not alias y");
-    // (the one user of EpiAxpby with a coded form; launch_csr_stream_any and its other users keep reading `val`)
-    if (a->val32) launch_csr_stream_any(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
-    else launch_csr_stream_coded(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
+    // (the one user of EpiAxpby with a coded form; its other users keep reading `val`)
+    launch_csr<kF32 | kCodes>(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
   });
 }
 

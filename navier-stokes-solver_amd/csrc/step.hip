@@ -149,7 +149,7 @@ int nss_step_rhs_f64(nss_csr_t ad, const double* uf, const double* f, double* te
   return guarded([&] {
     NSS_REQUIRE(ad && uf && f && temp, "step_rhs: NULL argument");
     NSS_REQUIRE(temp != uf && temp != f, "step_rhs: temp aliases an operand");
-    launch_csr_stream(*ad, uf, EpiStepRhs{done, f, temp}, as_stream(stream));
+    launch_csr(*ad, uf, EpiStepRhs{done, f, temp}, as_stream(stream));
   });
 }
 

@@ -84,6 +84,33 @@ def test_narrowed_matrix_spmv_readback_and_refusals(hip_engine):
         hip_engine.bjac_create(A32.handle, s.line_blocks(3))
 
 
+def test_narrowed_spmv_over_the_lanes_per_row_regimes_and_a_grouped_matrix(hip_engine):
+    """The fp32 stream kernel at every lanes-per-row value of the launch plan, in every column form and with one 16-bit
+    index per group of columns (the preconditioners only reach a few of them): against scipy on the rounded values, to
+    the tolerance of the narrowed SpMV above."""
+    import lane_regimes
+    inflated = mac_stokes(3, 6).inflate(6).A                     # block-structured: runs of 6 consecutive columns
+    seen, forms, groups = set(), set(), set()
+    for name, make, lanes, form in lane_regimes.CASES + [("inflated", lambda: inflated, 4, None)]:
+        mat = make()
+        h = hip_engine.csr_create(mat.shape[0], mat.shape[1], mat.indptr, mat.indices, mat.data)
+        hip_engine.csr_narrow_f32(h)
+        info = h.info()
+        assert info["lanes_per_row"] == lanes == lane_regimes.plan_lanes(mat.nnz / mat.shape[0]), (name, info)
+        assert info["value_bytes"] == 4 * mat.nnz and form in (None, info["operand_form"]), (name, info)
+        x = np.random.default_rng(lanes).standard_normal(mat.shape[1])
+        xb, yb = hip_engine.zeros(h.n), hip_engine.zeros(h.m)
+        hip_engine.upload(x, xb)
+        hip_engine.csr_spmv(h, 1.0, xb, 0.0, yb)
+        hip_engine.synchronize()
+        assert _rel(hip_engine.to_host(yb), _round32(mat) @ x) <= 1e-14, name
+        seen.add(info["lanes_per_row"])
+        forms.add(info["operand_form"])
+        groups.add(info["index_group"])
+    assert forms >= {"gather32", "gather16", "staged"} and groups == {1, 6}
+    assert seen == {1, 2, 4, 8, 16, 32, 64}
+
+
 def test_amg_and_auxiliary_fp32_against_the_rounded_build(hip_engine):
     """The fp32 V-cycle and auxiliary-space term against the numpy checker engine's rounded build (same hierarchy:
     the device set-up reproduces the host one bit for bit) -- to 1e-12."""

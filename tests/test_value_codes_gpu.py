@@ -94,6 +94,27 @@ def test_plain_spmv_coded_equals_uncoded_twin(hip_engine, value_codes_default, d
         assert same_bits(spmv(hip_engine, coded, x, y0), spmv(hip_engine, plain, x, y0)), name
 
 
+def test_coded_spmv_over_the_lanes_per_row_regimes_and_column_forms(hip_engine, value_codes_default):
+    """The coded stream kernel at every lanes-per-row value of the launch plan and in every column form (the loops only
+    reach it with the short rows of the Stokes blocks): identical bits to the uncoded twin."""
+    import lane_regimes
+    seen, forms = set(), set()
+    for name, make, lanes, form in lane_regimes.CASES:
+        mat = make()
+        assert distinct_patterns(mat) < 256 and lane_regimes.plan_lanes(mat.nnz / mat.shape[0]) == lanes, name
+        x, y0 = operands(mat)
+        plain, coded = upload(hip_engine, mat), upload(hip_engine, mat)
+        assert coded.code_values(), name
+        info = coded.info()
+        assert info["lanes_per_row"] == lanes and info["operand_form"] == form, (name, info)
+        assert info["value_bytes"] == info["nnz"] == mat.nnz and plain.info()["value_bytes"] == 8 * mat.nnz, (name, info)
+        assert same_bits(spmv(hip_engine, coded, x, y0), spmv(hip_engine, plain, x, y0)), name
+        seen.add(info["lanes_per_row"])
+        forms.add(info["operand_form"])
+    assert forms == {"gather32", "gather16", "staged"}
+    assert seen == {1, 2, 4, 8, 16, 32, 64}
+
+
 # ---- 2. dictionary edges -------------------------------------------------------------------------------------------
 def random_csr(rng, values, rows=3001, cols=3500, long_row=None):
     """short rows (some empty) whose values are drawn from `values`, every one of them at least once"""
