@@ -254,7 +254,32 @@ NSS_API int nss_bjac_destroy(nss_bjac_t j);
 /* y[dofs] = alpha * J x + beta * y[dofs]; dofs in no block: y = beta*y (0 if beta == 0) */
 NSS_API int nss_bjac_apply_f64(nss_bjac_t j, double alpha, const double* x, double beta, double* y,
                                nss_stream_t stream);
+/* y = alpha * J x (dofs in no block: 0) and, from the same registers, the per-workgroup partial sums of <y, x> into
+ * partials[0 .. *count) (device, `capacity` doubles): the apply the CG, MINRES and Lanczos loops launch when the dot
+ * product rides along.  Block-Jacobi mode only.  An inspection entry point for tests: the loops call the routine
+ * behind it directly. */
+NSS_API int nss_bjac_apply_dot_f64(nss_bjac_t j, double alpha, const double* x, double* y, double* partials,
+                                   int32_t capacity, int32_t* count, nss_stream_t stream);
 NSS_API int nss_bjac_info(nss_bjac_t j, int32_t* bs, int32_t* nblocks, int64_t* n, int64_t* algorithmic_bytes);
+/* Block codes.  On a structured grid nearly every inverse block is the same few doubles.  A block-Jacobi handle whose
+ * blocks -- the entries the apply kernel reads, compared as 64-bit patterns (-0.0 and +0.0 differ) -- take at most 256
+ * distinct values, with a dictionary (distinct blocks x doubles per block x 8 bytes) of at most 16 KiB, can stream one
+ * byte per block instead of the block: nss_bjac_apply_f64 and every loop that applies the handle as a stand-alone
+ * launch then read the block from an LDS copy of the dictionary.  Same doubles, same products: identical bits.
+ * nss_bjac_code_blocks: set-up only (hashes and compares the blocks on the device); *coded = 0 and nothing changed on
+ *   the handle when the blocks do not fit or the handle is in Gauss-Seidel mode.  The stored inverses stay.
+ * nss_bjac_block_code_mode: process-wide override: -1 = by size (the default: from 2^19 blocks on), 0 = never,
+ *   1 = whenever the handle holds codes.
+ * nss_bjac_block_codes: the distinct blocks (0: no codes) and the bytes one apply streams in the form the current mode
+ *   launches (nss_bjac_info's algorithmic_bytes prices the dense blocks in every form).
+ * nss_bjac_download_block_codes: the codes (nblocks bytes) and the dictionary (n_codes x doubles per block, the
+ *   entries of a block in the order of the stored form: packed upper triangle by rows, or the full block by rows) to the
+ *   host, and the doubles per block; each pointer may be NULL.  Fails on a handle without codes.  For tests and
+ *   inspection only: it synchronises the device, nothing on a hot path may call it. */
+NSS_API int nss_bjac_code_blocks(nss_bjac_t j, int32_t* coded, nss_stream_t stream);
+NSS_API int nss_bjac_block_code_mode(int32_t mode);
+NSS_API int nss_bjac_block_codes(nss_bjac_t j, int32_t* n_codes, int64_t* streamed_bytes);
+NSS_API int nss_bjac_download_block_codes(nss_bjac_t j, uint8_t* h_code, double* h_dict, int32_t* doubles_per_block);
 /* multiplicative block Gauss-Seidel sweeps `jacobi.Smooth(y, x)` / `jacobi.SmoothBack(y, x)`
  * (templates/NavierStokesSIMPLE_iterative.py:376-381) over a
  * MULTICOLOUR block ordering: the handle's blocks [h_color_ptr[c], h_color_ptr[c+1]) carry colour

@@ -83,6 +83,12 @@ bool value_codes_enabled();      // nss_csr_value_code_mode != 0
 // a dictionary of at most kDictSize doubles that the kernel holds in LDS.  Same doubles, same products.
 struct Coded8 {};
 constexpr int kDictSize = 256;
+// The distinct-pattern collector of the codes (spmv.hip), also run over the block hashes of nss_bjac_code_blocks: the
+// ascending distinct 64-bit patterns of val[0 .. n) (false at the 257th), and the position of every entry's pattern
+// among them.  Set-up only; both synchronise the stream.
+bool collect_patterns(int64_t n, const double* val, std::vector<unsigned long long>& keys, hipStream_t st);
+void assign_pattern_codes(int64_t n, const double* val, const std::vector<unsigned long long>& keys, uint8_t* codes,
+                          hipStream_t st);
 
 struct CsrView {
   const int32_t* __restrict__ rowblk;

@@ -15,6 +15,12 @@ struct nss_bjac_s {
   double* inv = nullptr;       // [bs*bs][nblocks]
   double* inv_sym = nullptr;   // [bs*(bs+1)/2][nblocks]: upper triangles, when every inverse block is
                                // symmetric (A symmetric): the apply kernel then reads ~half the bytes
+  // Block codes (nss_bjac_code_blocks): with at most 256 distinct inverse blocks -- compared as the 64-bit patterns
+  // of the entries the apply kernel reads -- the apply streams one byte per block and holds the distinct blocks in LDS
+  // (bjac_apply_coded_kernel); inv / inv_sym stay for every other reader.  Same doubles, same products.
+  uint8_t* code = nullptr;     // [nblocks]: the block's position in dict
+  double* dict = nullptr;      // [n_codes][dict_doubles]: the distinct blocks, entries in the order of inv_sym / inv
+  int32_t n_codes = 0, dict_doubles = 0;   // dict_doubles = bs (bs + 1) / 2 (inv_sym) or bs * bs (inv)
   int32_t* covered = nullptr;  // dofs that belong to no block (count: n_uncovered)
   int32_t n_uncovered = 0;
   // multicolour Gauss-Seidel mode (nss_bjac_set_colors): blocks are stored colour-major
@@ -53,6 +59,9 @@ struct nss_bjac_s {
 namespace nss {
 
 constexpr int kMaxBs = 16;
+// Largest dictionary of the coded apply: 160 KiB of LDS per CU over the 8 resident 256-lane workgroups of the uncoded
+// kernel, less its static reduction scratch, rounded down to a power of two
+constexpr int kBjacDictBytes = 16 << 10;
 constexpr int kGsRows = 256;     // rows per row block of the permuted Gauss-Seidel matrix (their residuals: 2 KiB of LDS)
 
 // y[dofs] = alpha * J x + beta * y[dofs]; returns immediately on the device when
@@ -63,6 +72,8 @@ void bjac_apply(const nss_bjac_s& j, double alpha, const double* x, double beta,
 // partial sums of <y, x> into partials[0 .. bjac_dot_grid(j)); returns that count.  Block-Jacobi
 // mode only.  Saves the separate dot pass (two vector reads and a launch) after the apply.
 int bjac_dot_grid(const nss_bjac_s& j);
+// whether bjac_apply / bjac_apply_dot launch the coded kernel for this handle (nss_bjac_block_code_mode)
+bool bjac_coded(const nss_bjac_s& j);
 int bjac_apply_dot(const nss_bjac_s& j, double alpha, const double* x, double* y, double* partials, const int32_t* done,
                    hipStream_t st);
 

@@ -8,6 +8,8 @@
 // blocks are laid out along the grid.  No MFMA: the op is 2 flop per 8 bytes.
 #include "precond.h"
 
+#include "code_keys.h"
+
 #include <string>
 #include <vector>
 
@@ -183,6 +185,220 @@ __global__ __launch_bounds__(kBlock) void bjac_apply_kernel(int32_t nb, const in
     const double t = block_sum(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
   }
+}
+
+// ---- block codes (nss_bjac_code_blocks) ------------------------------------------------------------------------
+// Whether the apply takes the coded form: -1 by size, 0 never, 1 whenever the handle holds codes
+// (nss_bjac_block_code_mode).  By size: the coded kernel streams 8 * dict_doubles - 1 bytes per block less and pays the
+// dictionary copy and one barrier per workgroup; NSS_BLOCK_CODES_MIN_BLOCKS is the block count from which that was
+// measured to pay with the BPCG v2 loop ("Block codes").
+#ifndef NSS_BLOCK_CODES_MIN_BLOCKS
+#define NSS_BLOCK_CODES_MIN_BLOCKS (1 << 19)
+#endif
+static int g_block_code_mode = -1;
+bool bjac_coded(const nss_bjac_s& j) {
+  if (!j.code || j.gs_mat) return false;
+  return g_block_code_mode == 1 || (g_block_code_mode < 0 && j.nblocks >= int32_t(NSS_BLOCK_CODES_MIN_BLOCKS));
+}
+
+// The coded twin of bjac_apply_sym_kernel (SYM) / bjac_apply_kernel: the entries of the block come from the LDS copy
+// of the dictionary, dict[code[b]][t], instead of packed[t][b] / inv[t][b].  The dictionary is requested first, the
+// index word, code and x of the lane's first block behind it, and one barrier publishes the copy; the grid-stride loop
+// has none.  Same fma chains in the same order as the uncoded kernels: same bits in y and in the partials.
+constexpr int kBjacDictRegs = kBjacDictBytes / int(sizeof(double)) / kBlock;
+template <int BS, bool SYM, bool NT>
+__global__ __launch_bounds__(kBlock) void bjac_apply_coded_kernel(int32_t nb, const int32_t* __restrict__ idx,
+                                                                   const int32_t* __restrict__ run,
+                                                                   const uint8_t* __restrict__ code,
+                                                                   const double* __restrict__ dict, int32_t nd,
+                                                                   double alpha, const double* __restrict__ x,
+                                                                   double beta, double* __restrict__ y,
+                                                                   const int32_t* __restrict__ done,
+                                                                   double* __restrict__ partials) {
+  constexpr int D = SYM ? BS * (BS + 1) / 2 : BS * BS;
+  extern __shared__ __align__(16) double bj_dict[];        // nd = n_codes * D doubles
+  __shared__ double red[kBlock / kWave];
+  if (done && done[0] != 0) return;
+  double dreg[kBjacDictRegs];
+#pragma unroll
+  for (int k = 0; k < kBjacDictRegs; ++k) {
+    const int i = k * kBlock + int(threadIdx.x);
+    dreg[k] = i < nd ? dict[i] : 0.0;
+  }
+  const int stride = gridDim.x * kBlock;
+  int32_t dof[BS];
+  double xv[BS];
+  int cd = 0;
+  auto fetch = [&](int b) {
+    if (run) {                                   // consecutive dofs: one word per block
+      const int32_t w = run[b], first = w >> 5, len = w & 31;
+#pragma unroll
+      for (int c = 0; c < BS; ++c) dof[c] = c < len ? first + c : -1;
+    } else {
+#pragma unroll
+      for (int c = 0; c < BS; ++c) dof[c] = idx[size_t(c) * nb + b];
+    }
+    if constexpr (NT) cd = __builtin_nontemporal_load(&code[b]);
+    else cd = code[b];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) xv[c] = dof[c] >= 0 ? x[dof[c]] : 0.0;
+  };
+  int b = blockIdx.x * kBlock + threadIdx.x;
+  if (b < nb) fetch(b);
+#pragma unroll
+  for (int k = 0; k < kBjacDictRegs; ++k) {
+    const int i = k * kBlock + int(threadIdx.x);
+    if (i < nd) bj_dict[i] = dreg[k];
+  }
+  __syncthreads();
+  double acc = 0.0;                              // partial <y, x> of this lane (partials != NULL)
+  while (b < nb) {
+    const double* m = bj_dict + cd * D;
+    if constexpr (SYM) {
+      double s[BS];
+#pragma unroll
+      for (int c = 0; c < BS; ++c) s[c] = 0.0;
+      int t = 0;
+#pragma unroll
+      for (int r = 0; r < BS; ++r) {
+#pragma unroll
+        for (int c = r; c < BS; ++c, ++t) {
+          const double mm = m[t];
+          s[r] = fma(mm, xv[c], s[r]);
+          if (c > r) s[c] = fma(mm, xv[r], s[c]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < BS; ++r) {
+        if (dof[r] >= 0) {
+          double v = alpha * s[r];
+          if (beta != 0.0) v = fma(beta, y[dof[r]], v);
+          y[dof[r]] = v;
+          acc = fma(v, xv[r], acc);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < BS; ++r) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < BS; ++c) s = fma(m[r * BS + c], xv[c], s);
+        if (dof[r] >= 0) {
+          double t = alpha * s;
+          if (beta != 0.0) t = fma(beta, y[dof[r]], t);
+          y[dof[r]] = t;
+          acc = fma(t, xv[r], acc);
+        }
+      }
+    }
+    b += stride;
+    if (b < nb) fetch(b);
+  }
+  if (partials) {
+    const double t = block_sum(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  }
+}
+
+// detection: one 64-bit hash per block over the patterns of its `d` entries src[t][b] ...
+__global__ __launch_bounds__(kBlock) void bjac_hash_kernel(int32_t nb, int d, const double* __restrict__ src,
+                                                            double* __restrict__ hash) {
+  const int stride = gridDim.x * kBlock;
+  for (int b = blockIdx.x * kBlock + threadIdx.x; b < nb; b += stride) {
+    unsigned long long h = 0x9E3779B97F4A7C15ull;
+    for (int t = 0; t < d; ++t) {
+      h = (h ^ (unsigned long long)__double_as_longlong(src[size_t(t) * nb + b])) * 0xFF51AFD7ED558CCDull;
+      h ^= h >> 32;
+    }
+    hash[b] = __longlong_as_double((long long)h);          // (carried as a double: the collector reads patterns)
+  }
+}
+
+// ... the first block of every code ...
+__global__ __launch_bounds__(kBlock) void bjac_rep_kernel(int32_t nb, const uint8_t* __restrict__ code, int32_t* rep) {
+  const int stride = gridDim.x * kBlock;
+  for (int b = blockIdx.x * kBlock + threadIdx.x; b < nb; b += stride) {
+    int32_t* slot = &rep[code[b]];
+    if (b < __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMin(slot, b);
+  }
+}
+
+// ... its entries as the dictionary entry of the code ...
+__global__ __launch_bounds__(kBlock) void bjac_dict_kernel(int32_t nb, int d, int n_codes, const double* __restrict__ src,
+                                                            const int32_t* __restrict__ rep, double* __restrict__ dict) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_codes * d) return;
+  dict[i] = src[size_t(i % d) * nb + rep[i / d]];
+}
+
+// ... and every block against the dictionary entry of its code, bit for bit (a difference: two blocks with one hash)
+__global__ __launch_bounds__(kBlock) void bjac_verify_kernel(int32_t nb, int d, const double* __restrict__ src,
+                                                              const uint8_t* __restrict__ code,
+                                                              const double* __restrict__ dict, int32_t* differ) {
+  const int stride = gridDim.x * kBlock;
+  for (int b = blockIdx.x * kBlock + threadIdx.x; b < nb; b += stride) {
+    const double* e = dict + size_t(code[b]) * d;
+    bool same = true;
+    for (int t = 0; t < d; ++t) same = same && __double_as_longlong(src[size_t(t) * nb + b]) == __double_as_longlong(e[t]);
+    if (!same) atomicExch(differ, 1);
+  }
+}
+
+// codes and dictionary of the handle's inverse blocks; false (handle unchanged) when they do not fit
+static bool code_blocks(nss_bjac_s& j, hipStream_t st) {
+  if (j.code) return true;
+  if (j.gs_mat || j.nblocks < 1) return false;             // Gauss-Seidel mode: the sweeps read ginv / inv
+  const double* src = j.inv_sym ? j.inv_sym : j.inv;
+  const int d = j.inv_sym ? j.bs * (j.bs + 1) / 2 : j.bs * j.bs;
+  const int32_t nb = j.nblocks;
+  double* hash = nullptr;
+  uint8_t* code = nullptr;
+  int32_t* rep = nullptr;                                  // kDictSize first blocks, then the verdict of the comparison
+  double* dict = nullptr;
+  bool ok = false;
+  int n_codes = 0;
+  try {
+    NSS_HIP(hipMalloc(&hash, sizeof(double) * size_t(nb)));
+    hipLaunchKernelGGL(bjac_hash_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, d, src, hash);
+    NSS_CHECK_LAUNCH();
+    std::vector<unsigned long long> keys;                  // ascending hashes: the codes do not depend on scheduling
+    if (collect_patterns(nb, hash, keys, st) && block_dictionary_fits(keys.size(), d, size_t(kBjacDictBytes))) {
+      n_codes = int(keys.size());
+      NSS_HIP(hipMalloc(&code, size_t(nb)));
+      NSS_HIP(hipMalloc(&rep, sizeof(int32_t) * (kDictSize + 1)));
+      NSS_HIP(hipMalloc(&dict, sizeof(double) * size_t(n_codes) * d));
+      assign_pattern_codes(nb, hash, keys, code, st);
+      NSS_HIP(hipMemsetAsync(rep, 0x7f, sizeof(int32_t) * kDictSize, st));
+      NSS_HIP(hipMemsetAsync(rep + kDictSize, 0, sizeof(int32_t), st));
+      hipLaunchKernelGGL(bjac_rep_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, code, rep);
+      NSS_CHECK_LAUNCH();
+      hipLaunchKernelGGL(bjac_dict_kernel, dim3((n_codes * d + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nb, d, n_codes,
+                         src, rep, dict);
+      NSS_CHECK_LAUNCH();
+      hipLaunchKernelGGL(bjac_verify_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, d, src, code, dict,
+                         rep + kDictSize);
+      NSS_CHECK_LAUNCH();
+      int32_t differ = 1;
+      NSS_HIP(hipMemcpyAsync(&differ, rep + kDictSize, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      NSS_HIP(hipStreamSynchronize(st));
+      ok = differ == 0;
+    }
+  } catch (...) {
+    for (void* p : {(void*)hash, (void*)code, (void*)rep, (void*)dict}) (void)hipFree(p);
+    throw;
+  }
+  (void)hipFree(hash);
+  (void)hipFree(rep);
+  if (!ok) {
+    (void)hipFree(code);
+    (void)hipFree(dict);
+    return false;
+  }
+  j.code = code;
+  j.dict = dict;
+  j.n_codes = n_codes;
+  j.dict_doubles = d;
+  return true;
 }
 
 // dofs that belong to no block: y = beta * y
@@ -446,11 +662,29 @@ void bjac_symgs_apply(const nss_bjac_s& j, double xscale, const double* x, doubl
   bjac_smooth(j, xscale, x, y, true, done, st);                      // jacobi.SmoothBack(y, x)  (:381)
 }
 
+template <int BS, bool SYM>
+static void launch_bjac_coded(const nss_bjac_s& j, double alpha, const double* x, double beta, double* y,
+                              const int32_t* done, double* partials, hipStream_t st) {
+  const int grid = bjac_dot_grid(j);
+  const int32_t nd = j.n_codes * j.dict_doubles;
+  const size_t lds = sizeof(double) * size_t(nd);
+  if (stream_vector_loads(j.n))
+    hipLaunchKernelGGL((bjac_apply_coded_kernel<BS, SYM, true>), dim3(grid), dim3(kBlock), lds, st, j.nblocks, j.idx, j.run,
+                       j.code, j.dict, nd, alpha, x, beta, y, done, partials);
+  else
+    hipLaunchKernelGGL((bjac_apply_coded_kernel<BS, SYM, false>), dim3(grid), dim3(kBlock), lds, st, j.nblocks, j.idx, j.run,
+                       j.code, j.dict, nd, alpha, x, beta, y, done, partials);
+}
+
 template <int BS>
 static void launch_bjac(const nss_bjac_s& j, double alpha, const double* x, double beta, double* y,
                         const int32_t* done, double* partials, hipStream_t st) {
   const int grid = bjac_dot_grid(j);
-  if (j.inv_sym && stream_vector_loads(j.n))
+  if (bjac_coded(j) && j.inv_sym)
+    launch_bjac_coded<BS, true>(j, alpha, x, beta, y, done, partials, st);
+  else if (bjac_coded(j))
+    launch_bjac_coded<BS, false>(j, alpha, x, beta, y, done, partials, st);
+  else if (j.inv_sym && stream_vector_loads(j.n))
     hipLaunchKernelGGL((bjac_apply_sym_kernel<BS, true>), dim3(grid), dim3(kBlock), 0, st, j.nblocks, j.idx, j.run,
                        j.inv_sym, alpha, x, beta, y, done, partials);
   else if (j.inv_sym)
@@ -606,6 +840,8 @@ int nss_bjac_destroy(nss_bjac_t j) {
     (void)hipFree(j->inv);
     (void)hipFree(j->inv_sym);
     (void)hipFree(j->run);
+    (void)hipFree(j->code);
+    (void)hipFree(j->dict);
     (void)hipFree(j->covered);
     (void)hipFree(j->rowdof);
     (void)hipFree(j->ridx);
@@ -625,6 +861,17 @@ int nss_bjac_apply_f64(nss_bjac_t j, double alpha, const double* x, double beta,
     NSS_REQUIRE(j != nullptr, "bjac_apply: NULL handle");
     NSS_REQUIRE(x != y, "bjac_apply: x must not alias y");
     bjac_apply(*j, alpha, x, beta, y, nullptr, as_stream(stream));
+  });
+}
+
+int nss_bjac_apply_dot_f64(nss_bjac_t j, double alpha, const double* x, double* y, double* partials, int32_t capacity,
+                           int32_t* count, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(j != nullptr && x != nullptr && y != nullptr && partials != nullptr, "bjac_apply_dot: NULL argument");
+    NSS_REQUIRE(x != y, "bjac_apply_dot: x must not alias y");
+    NSS_REQUIRE(capacity >= bjac_dot_grid(*j), "bjac_apply_dot: partials too short");
+    const int n = bjac_apply_dot(*j, alpha, x, y, partials, nullptr, as_stream(stream));
+    if (count) *count = n;
   });
 }
 
@@ -784,6 +1031,47 @@ int nss_bjac_info(nss_bjac_t j, int32_t* bs, int32_t* nblocks, int64_t* n, int64
     if (nblocks) *nblocks = j->nblocks;
     if (n) *n = j->n;
     if (algorithmic_bytes) *algorithmic_bytes = 8 * int64_t(j->nblocks) * j->bs * j->bs + 16 * j->n;
+  });
+}
+
+int nss_bjac_code_blocks(nss_bjac_t j, int32_t* coded, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(j != nullptr, "bjac_code_blocks: NULL handle");
+    const bool ok = code_blocks(*j, as_stream(stream));
+    if (coded) *coded = ok ? 1 : 0;
+  });
+}
+
+int nss_bjac_block_code_mode(int32_t mode) {
+  return guarded([&] {
+    NSS_REQUIRE(mode >= -1 && mode <= 1, "bjac_block_code_mode: -1 (by size), 0 (never) or 1 (whenever the handle holds codes)");
+    g_block_code_mode = mode;
+  });
+}
+
+int nss_bjac_block_codes(nss_bjac_t j, int32_t* n_codes, int64_t* streamed_bytes) {
+  return guarded([&] {
+    NSS_REQUIRE(j != nullptr, "bjac_block_codes: NULL handle");
+    if (n_codes) *n_codes = j->n_codes;
+    if (streamed_bytes) {
+      const bool coded = bjac_coded(*j);
+      // the index stream: the run word where the kernel takes it (the uncoded non-symmetric kernel reads idx), else idx
+      const int64_t index = j->run && (coded || j->inv_sym) ? 4 : 4 * int64_t(j->bs);
+      const int64_t d = j->inv_sym ? int64_t(j->bs) * (j->bs + 1) / 2 : int64_t(j->bs) * j->bs;
+      *streamed_bytes = coded ? int64_t(j->nblocks) * (1 + index) + 8 * int64_t(j->n_codes) * j->dict_doubles + 16 * j->n
+                              : int64_t(j->nblocks) * (8 * d + index) + 16 * j->n;
+    }
+  });
+}
+
+int nss_bjac_download_block_codes(nss_bjac_t j, uint8_t* h_code, double* h_dict, int32_t* doubles_per_block) {
+  return guarded([&] {
+    NSS_REQUIRE(j != nullptr, "bjac_download_block_codes: NULL handle");
+    NSS_REQUIRE(j->code != nullptr, "bjac_download_block_codes: the handle holds no codes");
+    if (doubles_per_block) *doubles_per_block = j->dict_doubles;
+    if (h_code) NSS_HIP(hipMemcpy(h_code, j->code, size_t(j->nblocks), hipMemcpyDeviceToHost));
+    if (h_dict)
+      NSS_HIP(hipMemcpy(h_dict, j->dict, sizeof(double) * size_t(j->n_codes) * j->dict_doubles, hipMemcpyDeviceToHost));
   });
 }
 

@@ -1,5 +1,6 @@
 // CSR matrix handles (upload, launch plan) and the plain alpha/beta SpMV entry point.
 #include "bpcg2.h"
+#include "code_keys.h"
 #include "csr_stream.h"
 #include "precond.h"
 
@@ -629,8 +630,6 @@ __global__ __launch_bounds__(kBlock) void ell_build_kernel(int32_t m, const int3
 }
 
 // ---- value codes ----------------------------------------------------------------------------------------------
-constexpr int kCodeSlots = 1024;                          // open-addressing table (power of two, 4 x the dictionary)
-constexpr uint64_t kCodeEmpty = ~uint64_t(0);             // free slot; the value with this very pattern is flagged apart
 // state[0]: distinct patterns inserted, state[1]: gave up (a 257th pattern, or the table is full), state[2]: the
 // pattern kCodeEmpty occurs
 __global__ __launch_bounds__(kBlock) void code_collect_kernel(int64_t n, const double* __restrict__ val,
@@ -723,64 +722,79 @@ static void drop_value_codes(nss_csr_s& A) {
   A.dict_count = 0;
 }
 
-static bool code_values(nss_csr_s& A, hipStream_t st) {
-  if (A.val8) return true;
-  if (A.val32 || !A.val || A.nnz == 0) return false;     // (fp32 storage has its own narrow form)
-  if (A.gb > 1) return false;                            // grouped column stream: its kernels have no coded form
+// The distinct 64-bit patterns of val[0 .. n), ascending (so that codes do not depend on the race of the insertions);
+// false -- keys empty -- at the 257th.  Synchronises the stream.
+bool collect_patterns(int64_t n, const double* val, std::vector<unsigned long long>& keys, hipStream_t st) {
+  keys.clear();
+  if (n <= 0) return false;
   unsigned long long* table = nullptr;
   int32_t* state = nullptr;
-  uint8_t* val8 = nullptr;
-  double* dict = nullptr;
+  int32_t h_state[4] = {0, 1, 0, 0};
+  std::vector<unsigned long long> h_table(kCodeSlots);
   try {
-    NSS_HIP(hipMalloc(&table, sizeof(unsigned long long) * (kCodeSlots + kDictSize)));   // the table, then the sorted keys
+    NSS_HIP(hipMalloc(&table, sizeof(unsigned long long) * kCodeSlots));
     NSS_HIP(hipMalloc(&state, sizeof(int32_t) * 4));
     NSS_HIP(hipMemsetAsync(table, 0xff, sizeof(unsigned long long) * kCodeSlots, st));
     NSS_HIP(hipMemsetAsync(state, 0, sizeof(int32_t) * 4, st));
-    hipLaunchKernelGGL(code_collect_kernel, dim3(stream_grid(A.nnz, kBlock * 8)), dim3(kBlock), 0, st, A.nnz, A.val, table,
-                       state);
+    hipLaunchKernelGGL(code_collect_kernel, dim3(stream_grid(n, kBlock * 8)), dim3(kBlock), 0, st, n, val, table, state);
     NSS_CHECK_LAUNCH();
-    int32_t h_state[4] = {0, 1, 0, 0};
-    std::vector<unsigned long long> h_table(kCodeSlots);
     NSS_HIP(hipMemcpyAsync(h_state, state, sizeof h_state, hipMemcpyDeviceToHost, st));
     NSS_HIP(hipMemcpyAsync(h_table.data(), table, sizeof(unsigned long long) * kCodeSlots, hipMemcpyDeviceToHost, st));
     NSS_HIP(hipStreamSynchronize(st));
-    std::vector<unsigned long long> keys;
-    if (h_state[1] == 0) {
-      for (unsigned long long k : h_table)
-        if (k != kCodeEmpty) keys.push_back(k);
-      if (h_state[2] != 0) keys.push_back(kCodeEmpty);
-      std::sort(keys.begin(), keys.end());               // ascending bit patterns: the codes do not depend on the race
-    }
-    if (h_state[1] == 0 && !keys.empty() && keys.size() <= size_t(kDictSize)) {
-      std::vector<unsigned long long> h_dict(kDictSize, 0ull);                // (unused slots: +0.0)
-      std::copy(keys.begin(), keys.end(), h_dict.begin());
-      NSS_HIP(hipMalloc(&dict, sizeof(double) * kDictSize));
-      NSS_HIP(hipMalloc(&val8, size_t(A.nnz) + 4));                          // padded like `val`
-      NSS_HIP(hipMemsetAsync(val8, 0, size_t(A.nnz) + 4, st));
-      NSS_HIP(hipMemcpyAsync(dict, h_dict.data(), sizeof(double) * kDictSize, hipMemcpyHostToDevice, st));
-      NSS_HIP(hipMemcpyAsync(table + kCodeSlots, keys.data(), sizeof(unsigned long long) * keys.size(),
-                             hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(code_assign_kernel, dim3(stream_grid(A.nnz, kBlock * 8)), dim3(kBlock), 0, st, A.nnz, A.val,
-                         table + kCodeSlots, int(keys.size()), val8);
-      NSS_CHECK_LAUNCH();
-      NSS_HIP(hipStreamSynchronize(st));                 // (h_dict / keys leave scope)
-      A.val8 = val8;
-      A.dict = dict;
-      A.dict_count = int32_t(keys.size());
-      val8 = nullptr;
-      dict = nullptr;
-      build_ell_code(A, st);
-    }
   } catch (...) {
     (void)hipFree(table);
     (void)hipFree(state);
-    (void)hipFree(val8);
-    (void)hipFree(dict);
     throw;
   }
   (void)hipFree(table);
   (void)hipFree(state);
-  return A.val8 != nullptr;
+  return code_keys_from_table(h_table.data(), kCodeSlots, h_state, size_t(kDictSize), keys);
+}
+
+// codes[i] = position of val[i]'s pattern in `keys` (from collect_patterns).  Synchronises the stream.
+void assign_pattern_codes(int64_t n, const double* val, const std::vector<unsigned long long>& keys, uint8_t* codes,
+                          hipStream_t st) {
+  unsigned long long* d_keys = nullptr;
+  try {
+    NSS_HIP(hipMalloc(&d_keys, sizeof(unsigned long long) * kDictSize));
+    NSS_HIP(hipMemcpyAsync(d_keys, keys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(code_assign_kernel, dim3(stream_grid(n, kBlock * 8)), dim3(kBlock), 0, st, n, val, d_keys,
+                       int(keys.size()), codes);
+    NSS_CHECK_LAUNCH();
+    NSS_HIP(hipStreamSynchronize(st));
+  } catch (...) {
+    (void)hipFree(d_keys);
+    throw;
+  }
+  (void)hipFree(d_keys);
+}
+
+static bool code_values(nss_csr_s& A, hipStream_t st) {
+  if (A.val8) return true;
+  if (A.val32 || !A.val || A.nnz == 0) return false;     // (fp32 storage has its own narrow form)
+  if (A.gb > 1) return false;                            // grouped column stream: its kernels have no coded form
+  std::vector<unsigned long long> keys;
+  if (!collect_patterns(A.nnz, A.val, keys, st)) return false;
+  uint8_t* val8 = nullptr;
+  double* dict = nullptr;
+  try {
+    std::vector<unsigned long long> h_dict(kDictSize, 0ull);                  // (unused slots: +0.0)
+    std::copy(keys.begin(), keys.end(), h_dict.begin());
+    NSS_HIP(hipMalloc(&dict, sizeof(double) * kDictSize));
+    NSS_HIP(hipMalloc(&val8, size_t(A.nnz) + 4));                            // padded like `val`
+    NSS_HIP(hipMemsetAsync(val8, 0, size_t(A.nnz) + 4, st));
+    NSS_HIP(hipMemcpyAsync(dict, h_dict.data(), sizeof(double) * kDictSize, hipMemcpyHostToDevice, st));
+    assign_pattern_codes(A.nnz, A.val, keys, val8, st);                      // (synchronises: h_dict may leave scope)
+  } catch (...) {
+    (void)hipFree(val8);
+    (void)hipFree(dict);
+    throw;
+  }
+  A.val8 = val8;
+  A.dict = dict;
+  A.dict_count = int32_t(keys.size());
+  build_ell_code(A, st);
+  return true;
 }
 
 static void direct_rows(nss_csr_s& A, hipStream_t st) {

@@ -110,7 +110,12 @@ def _signatures():
         "nss_bjac_create": (C.c_int, [vp, i32, i32, vp, C.POINTER(vp)]),
         "nss_bjac_destroy": (C.c_int, [vp]),
         "nss_bjac_apply_f64": (C.c_int, [vp, dbl, vp, dbl, vp, vp]),
+        "nss_bjac_apply_dot_f64": (C.c_int, [vp, dbl, vp, vp, vp, i32, c_i32_p, vp]),
         "nss_bjac_info": (C.c_int, [vp, c_i32_p, c_i32_p, c_i64_p, c_i64_p]),
+        "nss_bjac_code_blocks": (C.c_int, [vp, c_i32_p, vp]),
+        "nss_bjac_block_code_mode": (C.c_int, [i32]),
+        "nss_bjac_block_codes": (C.c_int, [vp, c_i32_p, c_i64_p]),
+        "nss_bjac_download_block_codes": (C.c_int, [vp, vp, vp, c_i32_p]),
         "nss_bjac_set_colors": (C.c_int, [vp, vp, i32, vp, vp, vp, vp]),
         "nss_bjac_set_colors_permuted": (C.c_int, [vp, vp, i32, vp, vp, vp, vp]),
         "nss_bjac_set_condensed": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -196,6 +201,8 @@ def load_library(path=None):
         lib.nss_stream_loads_mode(int(os.environ["NSS_STREAM_LOADS"]))
     if os.environ.get("NSS_VALUE_CODES") and hasattr(lib, "nss_csr_value_code_mode"):    # measurements: -1 / 0 / 1
         lib.nss_csr_value_code_mode(int(os.environ["NSS_VALUE_CODES"]))
+    if os.environ.get("NSS_BLOCK_CODES") and hasattr(lib, "nss_bjac_block_code_mode"):   # measurements: -1 / 0 / 1
+        lib.nss_bjac_block_code_mode(int(os.environ["NSS_BLOCK_CODES"]))
     if os.environ.get("NSS_COND_FUSE") and hasattr(lib, "nss_cond_fuse_mode"):           # measurements: 0 / 1
         lib.nss_cond_fuse_mode(int(os.environ["NSS_COND_FUSE"]))
     if os.environ.get("NSS_DISPATCH_PLANES") and hasattr(lib, "nss_csr_dispatch_mode"):   # measurements: -1 / 0 / T
@@ -310,6 +317,36 @@ class _BjacHandle:
         nbytes = C.c_int64()
         self.engine._check(self.engine.lib.nss_bjac_info(self.ptr, None, None, None, nbytes))
         return nbytes.value
+
+    def code_blocks(self):
+        """Store one-byte block codes and the dictionary of the distinct inverse blocks beside the inverses when there
+        are at most 256 of them and the dictionary fits 16 KiB (nss_bjac_code_blocks, set-up only); returns whether the
+        handle holds codes now."""
+        lib = self.engine.lib
+        if not hasattr(lib, "nss_bjac_code_blocks"):                 # (absent in older A/B builds)
+            return False
+        out = C.c_int32()
+        self.engine._check(lib.nss_bjac_code_blocks(self.ptr, C.byref(out), self.engine.stream))
+        return bool(out.value)
+
+    def block_codes(self):
+        """(distinct blocks -- 0 without codes --, bytes one apply streams in the form the current mode launches)."""
+        n_codes, nbytes = C.c_int32(), C.c_int64()
+        if not hasattr(self.engine.lib, "nss_bjac_block_codes"):     # (absent in older A/B builds)
+            raise NssError("this library has no block codes")
+        self.engine._check(self.engine.lib.nss_bjac_block_codes(self.ptr, C.byref(n_codes), C.byref(nbytes)))
+        return n_codes.value, nbytes.value
+
+    def download_block_codes(self):
+        """(codes uint8[nblocks], dictionary float64[n_codes, doubles per block]) of a handle that holds codes."""
+        lib = self.engine.lib
+        n_codes, _ = self.block_codes()
+        d = C.c_int32()
+        self.engine._check(lib.nss_bjac_download_block_codes(self.ptr, None, None, C.byref(d)))
+        code = np.zeros(self.nblocks, dtype=np.uint8)
+        dict_ = np.zeros((n_codes, d.value), dtype=np.float64)
+        self.engine._check(lib.nss_bjac_download_block_codes(self.ptr, code.ctypes.data, dict_.ctypes.data, None))
+        return code, dict_
 
     def __del__(self):
         try:
@@ -665,6 +702,17 @@ class HipEngine:
             raise ValueError("bjac_smooth shape mismatch")
         self._check(self.lib.nss_bjac_smooth_f64(h.ptr, xscale, x.data_ptr(), y.data_ptr(), int(bool(backward)),
                                                  self.stream))
+
+    def bjac_apply_dot(self, h, alpha, x, y):
+        """y = alpha * J x and the per-workgroup partial sums of <y, x> (nss_bjac_apply_dot_f64), as a host array."""
+        if x.numel() != h.n or y.numel() != h.n:
+            raise ValueError("bjac_apply_dot shape mismatch")
+        cap = (h.nblocks + 255) // 256
+        partials, count = self.zeros(cap), C.c_int32()
+        self._check(self.lib.nss_bjac_apply_dot_f64(h.ptr, alpha, x.data_ptr(), y.data_ptr(), partials.data_ptr(), cap,
+                                                    C.byref(count), self.stream))
+        self.synchronize()
+        return self.to_host(partials)[:count.value].copy()
 
     def bjac_apply(self, h, alpha, x, beta, y):
         if x.shape[0] != h.n or y.shape[0] != h.n:

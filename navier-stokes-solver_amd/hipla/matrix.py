@@ -636,6 +636,9 @@ class BlockJacobi(BaseMatrix):
             raise ValueError("BlockJacobi blocks must be disjoint and in range")
         self.idx_host = idx
         self.handle = self.engine.bjac_create(mat.handle, idx)
+        # one-byte block codes when the inverse blocks repeat (nss_bjac_code_blocks; set-up only, the apply picks the form)
+        # (the handle of the numpy engine of the oracle has no codes)
+        self.block_coded = hasattr(self.handle, "code_blocks") and self.handle.code_blocks()
 
     @staticmethod
     def _as_table(blocks):
