@@ -106,7 +106,7 @@ struct EpiV1Rows {
   double* top_hist;
   int it;
   // block Jacobi applied here (A planned around its blocks, nss_csr_plan_for_blocks): t2u = -k J t1u from the LDS copy
-  // of this row block's t1u, one lane per Jacobi block, the arithmetic of bjac_apply_sym_kernel (identical bits)
+  // of this row block's t1u, one lane per Jacobi block (bjac_rows_from_lds, bjac_block.h)
   const int32_t* __restrict__ jb_first = nullptr;    // nullptr: not fused
   const int32_t* __restrict__ jb_order = nullptr;
   const int32_t* __restrict__ jb_run = nullptr;
@@ -137,20 +137,8 @@ struct EpiV1Rows {
     if (!jb_first || b < 0) return;                      // (uniform over the workgroup)
     extern __shared__ double v1_t1u[];
     __syncthreads();
-    const int j1 = jb_first[b + 1];
-    for (int pos = jb_first[b] + int(threadIdx.x); pos < j1; pos += kBlock) {
-      const int jb = jb_order[pos];
-      const int32_t w = jb_run[jb], first = w >> 5, len = w & 31;
-      for (int i = 0; i < len; ++i) {
-        double s = 0.0;
-        for (int j = 0; j < len; ++j) {
-          const int lo = i < j ? i : j, hi = i < j ? j : i;
-          const int tri = lo * jb_bs - (lo * (lo - 1)) / 2 + (hi - lo);        // upper triangle, row-major
-          s = fma(jb_packed[size_t(tri) * jb_count + jb], v1_t1u[(first + j) & (kBlockRows - 1)], s);
-        }
-        t2u[first + i] = -k * s;
-      }
-    }
+    bjac_rows_from_lds(jb_first, jb_order, jb_run, jb_packed, jb_count, jb_bs, b, v1_t1u,
+                       [&](int i, double s) { t2u[i] = -k * s; });
   }
 };
 

@@ -573,7 +573,7 @@ struct EpiK1c {
   double* __restrict__ ghost_s0 = nullptr;
   const double* __restrict__ ghost_w0 = nullptr;
   // block Jacobi applied here (B^T planned around its blocks, nss_csr_plan_for_blocks): t1 = k J t0 from the LDS copy
-  // of this row block's t0, one lane per Jacobi block, the arithmetic of bjac_apply_sym_kernel (row i: the chain
+  // of this row block's t0, one lane per Jacobi block (bjac_rows_from_lds, bjac_block.h: row i is the chain
   // fma(M_ij, x_j, .) over j ascending) -- no launch of its own, t0 is not read back
   const int32_t* __restrict__ jb_first = nullptr;    // nullptr: not fused
   const int32_t* __restrict__ jb_order = nullptr;
@@ -646,20 +646,8 @@ struct EpiK1c {
     if (jb_first && b >= 0) {                            // (uniform over the workgroup)
       extern __shared__ double k1_t0[];
       __syncthreads();
-      const int j1 = jb_first[b + 1];
-      for (int pos = jb_first[b] + int(threadIdx.x); pos < j1; pos += kBlock) {
-        const int jb = jb_order[pos];
-        const int32_t w = jb_run[jb], first = w >> 5, len = w & 31;
-        for (int i = 0; i < len; ++i) {
-          double s = 0.0;
-          for (int j = 0; j < len; ++j) {
-            const int lo = i < j ? i : j, hi = i < j ? j : i;
-            const int tri = lo * jb_bs - (lo * (lo - 1)) / 2 + (hi - lo);      // upper triangle, row-major
-            s = fma(jb_packed[size_t(tri) * jb_count + jb], k1_t0[(first + j) & (kBlockRows - 1)], s);
-          }
-          t1[first + i] = k * s;
-        }
-      }
+      bjac_rows_from_lds(jb_first, jb_order, jb_run, jb_packed, jb_count, jb_bs, b, k1_t0,
+                         [&](int i, double s) { t1[i] = k * s; });
     }
     if (it == 0 || ghost_n == 0) return;
     const int stride = gridDim.x * kBlock;

@@ -151,7 +151,7 @@ struct LzFusedArgs {
   double *v_new, *z_new;
   double pre_scale;
   int32_t nblocks;
-  const int32_t* run;          // first dof * 32 + length of a block
+  const int32_t* run;          // run word of a block (bjac_block.h)
   const double* packed;        // upper triangles of the inverse blocks, [BS (BS + 1) / 2][nblocks]
   const double* pa;            // partials of <ph, zh_j> (na == 0: a stand-alone sum has left the total in scal[L_DH])
   int32_t na;
@@ -192,8 +192,8 @@ __global__ __launch_bounds__(kBlock) void lanczos_books_kernel(int32_t* ctrl, do
   lz_close_step(ctrl, scal, hist, j, s.b, threadIdx.x == 0, &gamma);
 }
 
-// one lane per block of <= BS consecutive dofs: rh_{j+1} (L3), zh_{j+1} = pre_scale * J rh_{j+1} with the arithmetic of
-// bjac_apply_sym_kernel, the partial of their dot
+// one lane per block of <= BS consecutive dofs: rh_{j+1} (L3), zh_{j+1} = pre_scale * J rh_{j+1} (bjac_sym_product,
+// bjac_block.h), the partial of their dot
 template <int BS>
 __global__ __launch_bounds__(kBlock) void lanczos_fused_kernel(LzFusedArgs a) {
   __shared__ double lds[kRedDoubles];
@@ -205,9 +205,9 @@ __global__ __launch_bounds__(kBlock) void lanczos_fused_kernel(LzFusedArgs a) {
   int32_t first = 0, len = 0;
   double bp[BS], bv[BS], bvo[BS], m[T];
   if (live) {
-    const int32_t w = a.run[b];
-    first = w >> 5;
-    len = w & 31;
+    const BjacRun w = bjac_unpack_run(a.run[b]);
+    first = w.first;
+    len = w.len;
 #pragma unroll
     for (int c = 0; c < BS; ++c) {
       const bool in = c < len;
@@ -245,17 +245,8 @@ __global__ __launch_bounds__(kBlock) void lanczos_fused_kernel(LzFusedArgs a) {
       r[c] = fma(cb, bv[c], ca * bp[c]);
       if (a.j > 0) r[c] = fma(cc, bvo[c], r[c]);
       if (c >= len) r[c] = 0.0;
-      sum[c] = 0.0;
     }
-    int t = 0;
-#pragma unroll
-    for (int q = 0; q < BS; ++q) {
-#pragma unroll
-      for (int c = q; c < BS; ++c, ++t) {
-        sum[q] = fma(m[t], r[c], sum[q]);
-        if (c > q) sum[c] = fma(m[t], r[q], sum[c]);
-      }
-    }
+    bjac_sym_product<BS>([&](int t) { return m[t]; }, r, sum);
 #pragma unroll
     for (int c = 0; c < BS; ++c) {
       if (c < len) {
@@ -347,12 +338,10 @@ static void lz_step(const nss_lanczos_t& s, int j, bool last, hipStream_t st) {
     const int g = lz_fused_grid(s);
     LzFusedArgs a{s.ctrl, s.scal, s.hist, s.n, j, s.p, v, v_old, v_new, z_new, s.pre_scale, J.nblocks, J.run, J.inv_sym,
                   s.partials_a, fold_a ? s.A->nblk : 0, lz_half(s, j), g, lz_half(s, j + 1)};
-    switch (J.bs) {
-#define NSS_LZ(N) case N: hipLaunchKernelGGL((lanczos_fused_kernel<N>), dim3(g), dim3(kBlock), 0, st, a); break;
-      NSS_LZ(1) NSS_LZ(2) NSS_LZ(3) NSS_LZ(4) NSS_LZ(5) NSS_LZ(6) NSS_LZ(7) NSS_LZ(8)
-#undef NSS_LZ
-      default: throw Error("lanczos: unsupported block size");
-    }
+    with_block_size(J.bs, "lanczos", [&](auto bs) {
+      if constexpr (bs() <= kLzFusedBs) hipLaunchKernelGGL((lanczos_fused_kernel<bs()>), dim3(g), dim3(kBlock), 0, st, a);
+      else throw Error("lanczos: unsupported block size");           // (lz_fused admits kLzFusedBs rows at the most)
+    });
     NSS_CHECK_LAUNCH();
     if (last) {        // the books of this step for the host; the next batch repeats them bit for bit
       hipLaunchKernelGGL(lanczos_books_kernel, dim3(1), dim3(kBlock), 0, st, s.ctrl, s.scal, s.hist, j + 1, lz_half(s, j + 1), g);

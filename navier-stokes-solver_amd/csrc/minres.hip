@@ -188,7 +188,7 @@ __device__ __forceinline__ double m3_delta(const MK4Args& a, double* lds) {
 
 // BS == 0: the velocity part is element-wise (point Jacobi when a.dinv, else v_new only);
 // BS > 0: one lane per block of <= BS consecutive dofs, z_new0 = J v_new0 from the packed symmetric
-// inverse blocks (the arithmetic of bjac_apply_sym_kernel)
+// inverse blocks (bjac_sym_product, bjac_block.h)
 template <int BS, bool NT>
 __global__ __launch_bounds__(kBlock) void minres_m3_kernel(MK4Args a) {
   __shared__ double lds[kRedDoubles];
@@ -215,9 +215,9 @@ __global__ __launch_bounds__(kBlock) void minres_m3_kernel(MK4Args a) {
   int32_t first = 0, len = 0;
   double bkz[B], bv[B], bvo[B];
   if (live) {
-    const int32_t w = a.run[blk];
-    first = w >> 5;
-    len = w & 31;
+    const BjacRun w = bjac_unpack_run(a.run[blk]);
+    first = w.first;
+    len = w.len;
 #pragma unroll
     for (int c = 0; c < B; ++c) {
       const bool in = c < len;
@@ -270,18 +270,8 @@ __global__ __launch_bounds__(kBlock) void minres_m3_kernel(MK4Args a) {
         a.vn0[first + c] = vn;
       }
       xv[c] = vn;
-      sv[c] = 0.0;
     }
-    int t = 0;
-#pragma unroll
-    for (int r = 0; r < B; ++r) {
-#pragma unroll
-      for (int c = r; c < B; ++c, ++t) {
-        const double m = a.packed[size_t(t) * a.nblocks + blk];
-        sv[r] = fma(m, xv[c], sv[r]);
-        if (c > r) sv[c] = fma(m, xv[r], sv[c]);
-      }
-    }
+    bjac_sym_product<B>([&](int t) { return a.packed[size_t(t) * a.nblocks + blk]; }, xv, sv);
 #pragma unroll
     for (int r = 0; r < B; ++r) {
       if (r < len) {
@@ -552,13 +542,7 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
   if (!fused) {
     launch_m3<0>(a4, g3, st);
   } else {
-    switch (s.pre_bjac->bs) {
-#define NSS_M3(N) case N: launch_m3<N>(a4, g3, st); break;
-      NSS_M3(1) NSS_M3(2) NSS_M3(3) NSS_M3(4) NSS_M3(5) NSS_M3(6) NSS_M3(7) NSS_M3(8)
-      NSS_M3(9) NSS_M3(10) NSS_M3(11) NSS_M3(12) NSS_M3(13) NSS_M3(14) NSS_M3(15) NSS_M3(16)
-#undef NSS_M3
-      default: throw Error("minres: unsupported block size");
-    }
+    with_block_size(s.pre_bjac->bs, "minres", [&](auto bs) { launch_m3<bs()>(a4, g3, st); });
   }
   NSS_CHECK_LAUNCH();
   }

@@ -1,8 +1,10 @@
 // Block-Jacobi handle shared by the preconditioner entry points and the fused loops.
 #pragma once
 
-#include "csr_stream.h"
+#include "bjac_block.h"
 
+#include <string>
+#include <type_traits>
 #include <vector>
 
 struct nss_bjac_s {
@@ -10,7 +12,7 @@ struct nss_bjac_s {
   int32_t bs = 0, nblocks = 0;
   int64_t n = 0;
   int32_t* idx = nullptr;      // [bs][nblocks], -1 = padding
-  int32_t* run = nullptr;      // [nblocks]: first dof * 32 + length, when every block is a run of
+  int32_t* run = nullptr;      // [nblocks]: run words (bjac_pack_run), when every block is a run of
                                // consecutive dofs (4 bytes per block instead of 4 per dof)
   double* inv = nullptr;       // [bs*bs][nblocks]
   double* inv_sym = nullptr;   // [bs*(bs+1)/2][nblocks]: upper triangles, when every inverse block is
@@ -63,6 +65,36 @@ constexpr int kMaxBs = 16;
 // kernel, less its static reduction scratch, rounded down to a power of two
 constexpr int kBjacDictBytes = 16 << 10;
 constexpr int kGsRows = 256;     // rows per row block of the permuted Gauss-Seidel matrix (their residuals: 2 KiB of LDS)
+
+// f(std::integral_constant<int, bs>{}) for 1 <= bs <= kMaxBs: the block size as a template argument of what f launches
+template <class F>
+void with_block_size(int bs, const char* what, F&& f) {
+  switch (bs) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 11: return f(std::integral_constant<int, 11>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 13: return f(std::integral_constant<int, 13>{});
+    case 14: return f(std::integral_constant<int, 14>{});
+    case 15: return f(std::integral_constant<int, 15>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    default: throw Error(std::string(what) + ": unsupported block size");
+  }
+}
+// the same for a flag (the streaming-load argument of the apply kernels)
+template <class F>
+void with_bool(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 // y[dofs] = alpha * J x + beta * y[dofs]; returns immediately on the device when
 // `done` (device int, may be NULL) is non-zero.

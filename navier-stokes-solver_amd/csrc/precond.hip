@@ -112,38 +112,12 @@ __global__ __launch_bounds__(kBlock) void bjac_apply_sym_kernel(int32_t nb, cons
   for (int b = blockIdx.x * kBlock + threadIdx.x; b < nb; b += stride) {
     int32_t dof[BS];
     double xv[BS], s[BS];
-    if (run) {                                   // consecutive dofs: one word per block
-      const int32_t w = run[b], first = w >> 5, len = w & 31;
+    bjac_block_dofs<BS>(run, idx, nb, b, dof);
 #pragma unroll
-      for (int c = 0; c < BS; ++c) dof[c] = c < len ? first + c : -1;
-    } else {
+    for (int c = 0; c < BS; ++c) xv[c] = dof[c] >= 0 ? x[dof[c]] : 0.0;
+    bjac_sym_product<BS>([&](int t) { return ld1s<NT>(&packed[size_t(t) * nb + b]); }, xv, s);
 #pragma unroll
-      for (int c = 0; c < BS; ++c) dof[c] = idx[size_t(c) * nb + b];
-    }
-#pragma unroll
-    for (int c = 0; c < BS; ++c) {
-      xv[c] = dof[c] >= 0 ? x[dof[c]] : 0.0;
-      s[c] = 0.0;
-    }
-    int t = 0;
-#pragma unroll
-    for (int r = 0; r < BS; ++r) {
-#pragma unroll
-      for (int c = r; c < BS; ++c, ++t) {
-        const double m = ld1s<NT>(&packed[size_t(t) * nb + b]);
-        s[r] = fma(m, xv[c], s[r]);
-        if (c > r) s[c] = fma(m, xv[r], s[c]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      if (dof[r] >= 0) {
-        double v = alpha * s[r];
-        if (beta != 0.0) v = fma(beta, y[dof[r]], v);
-        y[dof[r]] = v;
-        acc = fma(v, xv[r], acc);
-      }
-    }
+    for (int r = 0; r < BS; ++r) acc = bjac_store(dof[r], s[r], xv[r], alpha, beta, y, acc);
   }
   if (partials) {
     const double t = block_sum(acc, red);
@@ -164,22 +138,12 @@ __global__ __launch_bounds__(kBlock) void bjac_apply_kernel(int32_t nb, const in
   for (int b = blockIdx.x * kBlock + threadIdx.x; b < nb; b += stride) {
     int32_t dof[BS];
     double xv[BS];
-#pragma unroll
-    for (int c = 0; c < BS; ++c) dof[c] = idx[size_t(c) * nb + b];
+    bjac_block_dofs<BS>(nullptr, idx, nb, b, dof);
 #pragma unroll
     for (int c = 0; c < BS; ++c) xv[c] = dof[c] >= 0 ? x[dof[c]] : 0.0;
+    const auto m = [&](int t) { return inv[size_t(t) * nb + b]; };
 #pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      double s = 0.0;
-#pragma unroll
-      for (int c = 0; c < BS; ++c) s = fma(inv[(size_t(r) * BS + c) * nb + b], xv[c], s);
-      if (dof[r] >= 0) {
-        double t = alpha * s;
-        if (beta != 0.0) t = fma(beta, y[dof[r]], t);
-        y[dof[r]] = t;
-        acc = fma(t, xv[r], acc);
-      }
-    }
+    for (int r = 0; r < BS; ++r) acc = bjac_store(dof[r], bjac_full_row<BS>(m, r, xv), xv[r], alpha, beta, y, acc);
   }
   if (partials) {
     const double t = block_sum(acc, red);
@@ -204,7 +168,7 @@ bool bjac_coded(const nss_bjac_s& j) {
 // The coded twin of bjac_apply_sym_kernel (SYM) / bjac_apply_kernel: the entries of the block come from the LDS copy
 // of the dictionary, dict[code[b]][t], instead of packed[t][b] / inv[t][b].  The dictionary is requested first, the
 // index word, code and x of the lane's first block behind it, and one barrier publishes the copy; the grid-stride loop
-// has none.  Same fma chains in the same order as the uncoded kernels: same bits in y and in the partials.
+// has none.  The chains are those of the uncoded kernels (bjac_block.h): same bits in y and in the partials.
 constexpr int kBjacDictRegs = kBjacDictBytes / int(sizeof(double)) / kBlock;
 template <int BS, bool SYM, bool NT>
 __global__ __launch_bounds__(kBlock) void bjac_apply_coded_kernel(int32_t nb, const int32_t* __restrict__ idx,
@@ -230,14 +194,7 @@ __global__ __launch_bounds__(kBlock) void bjac_apply_coded_kernel(int32_t nb, co
   double xv[BS];
   int cd = 0;
   auto fetch = [&](int b) {
-    if (run) {                                   // consecutive dofs: one word per block
-      const int32_t w = run[b], first = w >> 5, len = w & 31;
-#pragma unroll
-      for (int c = 0; c < BS; ++c) dof[c] = c < len ? first + c : -1;
-    } else {
-#pragma unroll
-      for (int c = 0; c < BS; ++c) dof[c] = idx[size_t(c) * nb + b];
-    }
+    bjac_block_dofs<BS>(run, idx, nb, b, dof);
     if constexpr (NT) cd = __builtin_nontemporal_load(&code[b]);
     else cd = code[b];
 #pragma unroll
@@ -253,43 +210,16 @@ __global__ __launch_bounds__(kBlock) void bjac_apply_coded_kernel(int32_t nb, co
   __syncthreads();
   double acc = 0.0;                              // partial <y, x> of this lane (partials != NULL)
   while (b < nb) {
-    const double* m = bj_dict + cd * D;
+    const double* e = bj_dict + cd * D;
+    const auto m = [&](int t) { return e[t]; };
     if constexpr (SYM) {
       double s[BS];
+      bjac_sym_product<BS>(m, xv, s);
 #pragma unroll
-      for (int c = 0; c < BS; ++c) s[c] = 0.0;
-      int t = 0;
-#pragma unroll
-      for (int r = 0; r < BS; ++r) {
-#pragma unroll
-        for (int c = r; c < BS; ++c, ++t) {
-          const double mm = m[t];
-          s[r] = fma(mm, xv[c], s[r]);
-          if (c > r) s[c] = fma(mm, xv[r], s[c]);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < BS; ++r) {
-        if (dof[r] >= 0) {
-          double v = alpha * s[r];
-          if (beta != 0.0) v = fma(beta, y[dof[r]], v);
-          y[dof[r]] = v;
-          acc = fma(v, xv[r], acc);
-        }
-      }
+      for (int r = 0; r < BS; ++r) acc = bjac_store(dof[r], s[r], xv[r], alpha, beta, y, acc);
     } else {
 #pragma unroll
-      for (int r = 0; r < BS; ++r) {
-        double s = 0.0;
-#pragma unroll
-        for (int c = 0; c < BS; ++c) s = fma(m[r * BS + c], xv[c], s);
-        if (dof[r] >= 0) {
-          double t = alpha * s;
-          if (beta != 0.0) t = fma(beta, y[dof[r]], t);
-          y[dof[r]] = t;
-          acc = fma(t, xv[r], acc);
-        }
-      }
+      for (int r = 0; r < BS; ++r) acc = bjac_store(dof[r], bjac_full_row<BS>(m, r, xv), xv[r], alpha, beta, y, acc);
     }
     b += stride;
     if (b < nb) fetch(b);
@@ -451,10 +381,8 @@ __global__ __launch_bounds__(kBlock) void bgs_solve_kernel(int32_t b0, int32_t b
   for (int r = 0; r < BS; ++r) {
     const int dof = idx[size_t(r) * nb + b];
     if (dof < 0) continue;
-    double s = 0.0;
-#pragma unroll
-    for (int c = 0; c < BS; ++c) s = fma(inv[(size_t(r) * BS + c) * nb + b], rv[c], s);
-    y[dof] += s;
+    const double s = bjac_full_row<BS>([&](int t) { return inv[size_t(t) * nb + b]; }, r, rv);
+    y[dof] = s + y[dof];                 // (s first: the operand order of the kernel before bjac_block.h, same sum)
   }
 }
 
@@ -632,13 +560,7 @@ void bjac_smooth(const nss_bjac_s& j, double xscale, const double* x, double* y,
     const int c = backward ? nc - 1 - k : k;
     launch_csr<kF32>(*j.gs_mat, y, EpiGsResidual{done, j.rowdof, x, j.res, xscale}, st, j.color_rowblk[c],
                       j.color_rowblk[c + 1]);
-    switch (j.bs) {
-#define NSS_GS(N) case N: launch_bgs_solve<N>(j, c, y, done, st); break;
-      NSS_GS(1) NSS_GS(2) NSS_GS(3) NSS_GS(4) NSS_GS(5) NSS_GS(6) NSS_GS(7) NSS_GS(8)
-      NSS_GS(9) NSS_GS(10) NSS_GS(11) NSS_GS(12) NSS_GS(13) NSS_GS(14) NSS_GS(15) NSS_GS(16)
-#undef NSS_GS
-      default: throw Error("bjac_smooth: unsupported block size");
-    }
+    with_block_size(j.bs, "bjac_smooth", [&](auto bs) { launch_bgs_solve<bs()>(j, c, y, done, st); });
     NSS_CHECK_LAUNCH();
   }
 }
@@ -665,15 +587,12 @@ void bjac_symgs_apply(const nss_bjac_s& j, double xscale, const double* x, doubl
 template <int BS, bool SYM>
 static void launch_bjac_coded(const nss_bjac_s& j, double alpha, const double* x, double beta, double* y,
                               const int32_t* done, double* partials, hipStream_t st) {
-  const int grid = bjac_dot_grid(j);
   const int32_t nd = j.n_codes * j.dict_doubles;
-  const size_t lds = sizeof(double) * size_t(nd);
-  if (stream_vector_loads(j.n))
-    hipLaunchKernelGGL((bjac_apply_coded_kernel<BS, SYM, true>), dim3(grid), dim3(kBlock), lds, st, j.nblocks, j.idx, j.run,
-                       j.code, j.dict, nd, alpha, x, beta, y, done, partials);
-  else
-    hipLaunchKernelGGL((bjac_apply_coded_kernel<BS, SYM, false>), dim3(grid), dim3(kBlock), lds, st, j.nblocks, j.idx, j.run,
-                       j.code, j.dict, nd, alpha, x, beta, y, done, partials);
+  with_bool(stream_vector_loads(j.n), [&](auto nt) {
+    hipLaunchKernelGGL((bjac_apply_coded_kernel<BS, SYM, nt()>), dim3(bjac_dot_grid(j)), dim3(kBlock),
+                       sizeof(double) * size_t(nd), st, j.nblocks, j.idx, j.run, j.code, j.dict, nd, alpha, x, beta, y,
+                       done, partials);
+  });
 }
 
 template <int BS>
@@ -684,12 +603,11 @@ static void launch_bjac(const nss_bjac_s& j, double alpha, const double* x, doub
     launch_bjac_coded<BS, true>(j, alpha, x, beta, y, done, partials, st);
   else if (bjac_coded(j))
     launch_bjac_coded<BS, false>(j, alpha, x, beta, y, done, partials, st);
-  else if (j.inv_sym && stream_vector_loads(j.n))
-    hipLaunchKernelGGL((bjac_apply_sym_kernel<BS, true>), dim3(grid), dim3(kBlock), 0, st, j.nblocks, j.idx, j.run,
-                       j.inv_sym, alpha, x, beta, y, done, partials);
   else if (j.inv_sym)
-    hipLaunchKernelGGL((bjac_apply_sym_kernel<BS, false>), dim3(grid), dim3(kBlock), 0, st, j.nblocks, j.idx, j.run,
-                       j.inv_sym, alpha, x, beta, y, done, partials);
+    with_bool(stream_vector_loads(j.n), [&](auto nt) {
+      hipLaunchKernelGGL((bjac_apply_sym_kernel<BS, nt()>), dim3(grid), dim3(kBlock), 0, st, j.nblocks, j.idx, j.run,
+                         j.inv_sym, alpha, x, beta, y, done, partials);
+    });
   else
     hipLaunchKernelGGL((bjac_apply_kernel<BS>), dim3(grid), dim3(kBlock), 0, st, j.nblocks, j.idx, j.inv, alpha, x,
                        beta, y, done, partials);
@@ -720,13 +638,7 @@ static void bjac_apply_impl(const nss_bjac_s& j, double alpha, const double* x, 
     bjac_symgs_apply(j, alpha, x, y, done, st);
     return;
   }
-  switch (j.bs) {
-#define NSS_BJ(N) case N: launch_bjac<N>(j, alpha, x, beta, y, done, partials, st); break;
-    NSS_BJ(1) NSS_BJ(2) NSS_BJ(3) NSS_BJ(4) NSS_BJ(5) NSS_BJ(6) NSS_BJ(7) NSS_BJ(8)
-    NSS_BJ(9) NSS_BJ(10) NSS_BJ(11) NSS_BJ(12) NSS_BJ(13) NSS_BJ(14) NSS_BJ(15) NSS_BJ(16)
-#undef NSS_BJ
-    default: throw Error("bjac_apply: unsupported block size");
-  }
+  with_block_size(j.bs, "bjac_apply", [&](auto bs) { launch_bjac<bs()>(j, alpha, x, beta, y, done, partials, st); });
   NSS_CHECK_LAUNCH();
   if (j.n_uncovered > 0) {
     hipLaunchKernelGGL(bjac_uncovered_kernel, dim3((j.n_uncovered + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
@@ -789,7 +701,7 @@ int nss_bjac_create(nss_csr_t a, int32_t bs, int32_t nblocks, const int32_t* h_i
             const int32_t d = h_idx[size_t(c) * nblocks + b];
             all_runs = c < len ? d == first + c : d < 0;
           }
-          runs[b] = first * 32 + len;
+          runs[b] = bjac_pack_run(first, len);
         }
         if (all_runs) {
           NSS_HIP(hipMalloc(&j->run, sizeof(int32_t) * size_t(nblocks)));

@@ -1099,11 +1099,12 @@ int nss_csr_plan_for_blocks(nss_csr_t a, nss_bjac_t j, int32_t* planned) {
     // the blocks in row order (callers number them as they like: the lines of one velocity component after the other)
     std::vector<int32_t> order(run.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = int32_t(i);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return (run[size_t(x)] >> 5) < (run[size_t(y)] >> 5); });
+    const auto first_dof = [&](int32_t jb) { return bjac_unpack_run(run[size_t(jb)]).first; };
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return first_dof(x) < first_dof(y); });
     std::vector<uint8_t> row_pos(size_t(a->m), 0);
     int64_t next = 0;
     for (int32_t jb : order) {
-      const int32_t first = run[size_t(jb)] >> 5, len = run[size_t(jb)] & 31;
+      const auto [first, len] = bjac_unpack_run(run[size_t(jb)]);
       if (first != next || len < 1 || first + len > a->m) return;          // the blocks do not tile the rows: no fusion
       for (int c = 0; c < len; ++c) row_pos[size_t(first + c)] = uint8_t(c);
       next = first + len;
@@ -1115,9 +1116,9 @@ int nss_csr_plan_for_blocks(nss_csr_t a, nss_bjac_t j, int32_t* planned) {
     std::vector<int32_t> first_of(blk.size());
     size_t b = 0;
     for (size_t i = 0; i < blk.size(); ++i) {
-      while (b < order.size() && (run[size_t(order[b])] >> 5) < blk[i]) ++b;
+      while (b < order.size() && first_dof(order[b]) < blk[i]) ++b;
       // (a forced cut of the matrix inside a Jacobi block, or one over-long row: the plan stands, without the fusion)
-      if (!(i + 1 == blk.size() ? b == order.size() : (b < order.size() && (run[size_t(order[b])] >> 5) == blk[i]))) return;
+      if (!(i + 1 == blk.size() ? b == order.size() : (b < order.size() && first_dof(order[b]) == blk[i]))) return;
       if (i > 0 && blk[i] - blk[i - 1] > kBlockRows) return;
       first_of[i] = int32_t(b);
     }

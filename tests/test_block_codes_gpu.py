@@ -108,7 +108,7 @@ def stored_doubles(bs, symmetric):
 
 
 # ---- 1. apply bits over block sizes and both stored forms -------------------------------------------------------------
-@pytest.mark.parametrize("bs", [1, 2, 3, 5, 12, 16])
+@pytest.mark.parametrize("bs", list(range(1, 17)))
 @pytest.mark.parametrize("symmetric", [True, False])
 def test_apply_bits_over_block_sizes_and_forms(hip_engine, block_codes_default, bs, symmetric):
     lib = block_codes_default
