@@ -763,6 +763,33 @@ NSS_API int nss_scalar_update_f64(int64_t n, double tau, const double* delta, do
 NSS_API int nss_scalar_record_f64(const double* partials, int64_t n, double c0, double* record, int32_t slot,
                                   const int32_t* done, nss_stream_t stream);
 
+/* ---- second-order limited convection fluxes -------------------------------------------------------
+ * Limited twins of nss_step_flux_f64 and nss_scalar_flux_f64: the transported quantity q is read through one stencil row
+ * per point, `stencil` = device int32[4 n], 16-byte aligned, row r = (ll, lo, hi, hh): the entries of q the point sits
+ * between (lo on the side of the smaller coordinate, hi) and the far ones beyond them; -1 = absent.  PRECONDITION:
+ * every entry is -1 or a valid index of q (the kernels do not check the range).  With the advecting value a:
+ *
+ *   a >= 0:  U = q_lo, D = q_hi, UU = q_ll        a < 0:  U = q_hi, D = q_lo, UU = q_hh
+ *   s = phi(U - UU, D - U) if UU is present, else 0;     F = a * (U + s / 2)
+ *
+ * `limiter`: 0 donor cell (phi = 0), 1 minmod (phi(p, q) = p q > 0 ? (|p| < |q| ? p : q) : 0), 2 van Leer
+ * (phi(p, q) = p q > 0 ? 2 p q / (p + q) : 0).  An absent lo or hi counts as the value 0 (a wall); an absent far
+ * value leaves the point donor-cell for that flow direction.  All fp64, no atomics, one lane per point; `done` as for
+ * the nss_step_* kernels.
+ *
+ * nss_step_flux_limited_f64: q = u, a = (adv u)_r through the two-slot copy of adv (built on the first call: set-up;
+ *   fails when a row holds more than two entries, when adv stores fp32 values or when nflux is not its row count);
+ *   flux[r] = F.  `flux` is meant to be the tail of one buffer [u | F] and must not be u.  48 bytes per point.
+ * nss_scalar_flux_limited_f64: q = T, a = u[r]; G[r] = F and, with w_b != NULL, f_eff[r] = f[r] + w_b[r] ((T_lo +
+ *   T_hi) / 2 - t_ref); w_b == NULL reads no f and writes no f_eff.  No output may alias u or T.  32 bytes per face,
+ *   56 with w_b.
+ * nflux == 0 / nface == 0 returns 0 and launches nothing. */
+NSS_API int nss_step_flux_limited_f64(nss_csr_t adv, const int32_t* stencil, int64_t nflux, int32_t limiter,
+                                      const double* u, double* flux, const int32_t* done, nss_stream_t stream);
+NSS_API int nss_scalar_flux_limited_f64(const int32_t* stencil, int64_t nface, int32_t limiter, const double* w_b,
+                                        const double* u, const double* f, const double* T, double t_ref, double* G,
+                                        double* f_eff, const int32_t* done, nss_stream_t stream);
+
 /* ---- device-resident heat exponential integrator -------------------------------------------------
  * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
  * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:

@@ -882,22 +882,46 @@ def constants_in_kernel(lap):
     return bool(np.linalg.norm(lap @ np.ones(lap.shape[0])) <= 1e-12 * abs(lap).sum())
 
 
+CONVECTION_SCHEMES = {"upwind": 0, "minmod": 1, "vanleer": 2}      # scheme -> `limiter` of nss_*_flux_limited_f64
+
+
+def check_convection(scheme, who):
+    if scheme not in CONVECTION_SCHEMES:
+        raise ValueError("%s: convection is \"upwind\", \"minmod\" or \"vanleer\", not %r" % (who, scheme))
+    return scheme
+
+
+def upload_stencil(eng, stencil, n):
+    """The (rows, 4) stencil of a limited flux launch as device int32 (16-byte aligned: a fresh allocation), after the
+    range check the kernels leave to the caller: -1 <= entry < n."""
+    st = np.ascontiguousarray(stencil, dtype=np.int32)
+    if st.ndim != 2 or st.shape[1] != 4:
+        raise ValueError("stencil: an int array (rows, 4), not %s" % (st.shape,))
+    if st.size and (st.min() < -1 or st.max() >= n):
+        raise ValueError("stencil: entries outside -1 .. %d" % (n - 1))
+    buf = eng.torch.from_numpy(st if st.size else np.full((1, 4), -1, dtype=np.int32)).to(eng.device)
+    assert buf.data_ptr() % 16 == 0
+    return buf
+
+
 class StepRecord:
     """What `NavierStokes.Advance` returns: one entry per step of `mstar_iterations`, `proj_iterations` (pseudo time
     stepping: the two projections of a step added), `div_norm` = |B u| and `kinetic_energy` = <u, M_u u> / 2 after the
     step (both None with ``diagnostics=False``); `declined`: why the statements ran instead of the device-resident
     step (None when it ran); `flux_declined`: why the convection term ran through `ConvectionOperator`.  With a scalar
     (`NavierStokes.AddScalar`): `scalar_iterations` of the temperature solve and `wall_flux` = the heat entering through
-    the scalar's `flux_wall` after the step (None without a scalar / without diagnostics)."""
+    the scalar's `flux_wall` after the step (None without a scalar / without diagnostics).  `convection`: the scheme
+    of the momentum flux ("upwind" | "minmod" | "vanleer")."""
 
     def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
-                 scalar_iterations=None, wall_flux=None):
+                 scalar_iterations=None, wall_flux=None, convection="upwind"):
         self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
         self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
         self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
         self.declined, self.flux_declined = declined, flux_declined
         self.scalar_iterations = None if scalar_iterations is None else np.asarray(scalar_iterations, dtype=np.int64)
         self.wall_flux = wall_flux
+        self.convection = convection
 
 
 class TimeStepper(FusedLoop):
@@ -914,29 +938,37 @@ class TimeStepper(FusedLoop):
     MAXSTEPS = (500, 5000)
 
     @classmethod
-    def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None):
+    def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
+                   convection="upwind"):
         """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
         `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
         solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
         the convection operators (`flux_declined`).  `shared`: a dict in which the stepper looks up, and leaves, the
         device matrices that do not depend on `inner_pre` (mstar, Lp, C, adv, avg, diff, AD), so that the steppers of
         one system -- and a caller that already holds `M_u + timestep A`, `B M_u^-1 B^T`, `M_u^-1 B^T` and passes them
-        under "mstar", "Lp", "C" -- keep them once.  Returns None with the reason in ``TimeStepper.last_declined``."""
-        return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared))
+        under "mstar", "Lp", "C" -- keep them once.  `convection`: "upwind" (donor cell, first order) or the
+        second-order limited "minmod" / "vanleer": F1 then is the limited launch over `system.convection_stencil()`
+        (uploaded once, `shared["stencil"]`; avg and diff are not uploaded) and everything after it is unchanged.
+        Explicit Euler with the limiters wants timestep * sum_faces |u_f| / h <= 1/2 per cell.
+        Returns None with the reason in ``TimeStepper.last_declined``."""
+        return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection))
 
     @classmethod
-    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared):
+    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection):
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
+        check_convection(convection, "TimeStepper")
         if not ENABLED:
             return "fused loops disabled (hipla.fused.ENABLED)"
         if not isinstance(A, SparseMatrix) or not isinstance(B, SparseMatrix) or not isinstance(f, Vector):
             return "A, B are not SparseMatrix operands or f is not a plain Vector"
         if not _hip(A.engine) or not hasattr(A.engine.lib, "nss_step_flux_f64"):
             return "not the HIP engine"
-        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, {} if shared is None else shared)
+        if convection != "upwind" and not hasattr(A.engine.lib, "nss_step_flux_limited_f64"):
+            return "the library has no limited flux kernel"
+        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, {} if shared is None else shared, convection)
 
-    def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared):
+    def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind"):
         import scipy.sparse as sp
         from .matrix import JacobiPreconditioner
         eng = self.eng = A.engine
@@ -944,20 +976,34 @@ class TimeStepper(FusedLoop):
         self.n_u, self.n_p = A.height, B.height
         m_u = np.asarray(m_u, dtype=np.float64)
         # ---- the convection term: two-slot copies of adv / avg / diff and the rows of [A | D] ----
+        self.convection, self.stencil = convection, None
+        limited = convection != "upwind"
+        ops = None
         if "flux_declined" not in shared:
             ops = system.convection_operators()
             shared["flux_declined"] = next((key + ": " + why for key in ("adv", "avg", "diff")
                                             for ok, why in [two_entry_rows(ops[key])] if not ok), None)
-            if shared["flux_declined"] is None:
-                for key in ("adv", "avg", "diff"):
+        self.flux_declined = shared["flux_declined"]
+        if self.flux_declined is None:
+            for key in ("adv",) if limited else ("adv", "avg", "diff"):
+                if key not in shared:
+                    ops = system.convection_operators() if ops is None else ops
                     shared[key] = SparseMatrix.from_scipy(ops[key], engine=eng)
+            if "AD" not in shared:
+                ops = system.convection_operators() if ops is None else ops
                 AD = sp.hstack([A.to_scipy(), ops["div"]], format="csr")
                 AD.sort_indices()
                 shared["AD"] = SparseMatrix.from_scipy(AD, engine=eng)
-        self.flux_declined = shared["flux_declined"]
-        if self.flux_declined is None:
-            self.adv, self.avg, self.diff, self.AD = (shared[key] for key in ("adv", "avg", "diff", "AD"))
+            if limited and "stencil" not in shared:
+                shared["stencil"] = upload_stencil(eng, system.convection_stencil(), self.n_u)
+            self.adv, self.AD = shared["adv"], shared["AD"]
             self.nflux = self.adv.height
+            if limited:
+                self.stencil = shared["stencil"]
+                if self.stencil.shape[0] != max(1, self.nflux):
+                    raise ValueError("TimeStepper: the stencil holds %d rows, adv %d" % (self.stencil.shape[0], self.nflux))
+            else:
+                self.avg, self.diff = shared["avg"], shared["diff"]
             self.conv = None
         else:
             self.nflux = 0
@@ -1012,8 +1058,13 @@ class TimeStepper(FusedLoop):
         f = self.f.buf if f is None else f
         if self.flux_declined is None:
             flux = eng.view(self.uf, self.n_u, self.n_u + self.nflux)
-            eng._check(lib.nss_step_flux_f64(self.adv.handle.ptr, self.avg.handle.ptr, self.diff.handle.ptr,
-                                             self.uf.data_ptr(), flux.data_ptr(), None, eng.stream))
+            if self.stencil is None:
+                eng._check(lib.nss_step_flux_f64(self.adv.handle.ptr, self.avg.handle.ptr, self.diff.handle.ptr,
+                                                 self.uf.data_ptr(), flux.data_ptr(), None, eng.stream))
+            else:
+                eng._check(lib.nss_step_flux_limited_f64(self.adv.handle.ptr, self.stencil.data_ptr(), self.nflux,
+                                                         CONVECTION_SCHEMES[self.convection], self.uf.data_ptr(),
+                                                         flux.data_ptr(), None, eng.stream))
             eng._check(lib.nss_step_rhs_f64(self.AD.handle.ptr, self.uf.data_ptr(), f.data_ptr(),
                                             self.temp.data_ptr(), None, eng.stream))
             return
@@ -1084,9 +1135,10 @@ class TimeStepper(FusedLoop):
         if nsteps or pseudo:
             eng.copy(self.phi, gfup.buf)
         if not diagnostics:
-            return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined)
+            return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined, convection=self.convection)
         host = eng.to_host(record).reshape(-1, 2)[:nsteps]               # the one read-back
-        return StepRecord(its_m, its_p, host[:, 1].copy(), host[:, 0].copy(), flux_declined=self.flux_declined)
+        return StepRecord(its_m, its_p, host[:, 1].copy(), host[:, 0].copy(), flux_declined=self.flux_declined,
+                          convection=self.convection)
 
     def _advance_with_scalar(self, scalar, temperature, gfu, gfup, nsteps, diagnostics):
         """The loop of `advance` with the launches of `scalar` around the velocity step.  The velocity record and the
@@ -1109,12 +1161,13 @@ class TimeStepper(FusedLoop):
             eng.copy(self.phi, gfup.buf)
         scalar.store(temperature)
         if not diagnostics:
-            return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined, scalar_iterations=its_s)
+            return StepRecord(its_m, its_p, None, None, flux_declined=self.flux_declined, convection=self.convection,
+                              scalar_iterations=its_s)
         host = eng.to_host(record)                                                # the one read-back
         vel = host[:2 * max(1, nsteps)].reshape(-1, 2)[:nsteps]
         wall = host[2 * max(1, nsteps):][:nsteps].copy() if scalar.records else None
         return StepRecord(its_m, its_p, vel[:, 1].copy(), vel[:, 0].copy(), flux_declined=self.flux_declined,
-                          scalar_iterations=its_s, wall_flux=wall)
+                          convection=self.convection, scalar_iterations=its_s, wall_flux=wall)
 
 
 class ScalarStepper:
@@ -1127,16 +1180,19 @@ class ScalarStepper:
     (CG from zero); one launch does T += timestep delta with the partials of <w, T>, one workgroup writes the heat
     entering through the flux wall, c0 - <w, T>.  Every buffer is allocated here, once.  Beyond the vectors the scalar
     costs in HBM: avg and diff (two two-slot copies, 48 bytes per face), M_p + timestep K, and [K | B] -- a second copy
-    of K and one of B, 12 bytes per non-zero (B: 24 bytes per face)."""
+    of K and one of B, 12 bytes per non-zero (B: 24 bytes per face).  With a limited `convection` the flux is
+    `staggered_grid.limited_flux` over the scalar stencil (16 bytes per face) and avg / diff are not uploaded."""
 
     PRECISION, MAXSTEPS = 1e-4, 500          # those of invmstar: the same kind of operator
 
     def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
-                 maxsteps=None, shared=None):
+                 maxsteps=None, shared=None, convection="upwind", stencil=None):
         """`ops`: `StokesSystem.scalar_operators(...)`; `B`: the divergence (`SparseMatrix`); `f`: the force `Vector`
         the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
         (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
-        `inner_pre`."""
+        `inner_pre`.  `convection`: "upwind", or "minmod" / "vanleer" with `stencil` = `StokesSystem.scalar_stencil()`
+        (host array, uploaded once under `shared["stencil"]`): S1 then is the limited launch, avg and diff are not
+        uploaded, and the rest of the step is unchanged."""
         import scipy.sparse as sp
         from .matrix import JacobiPreconditioner
         shared = {} if shared is None else shared
@@ -1144,12 +1200,25 @@ class ScalarStepper:
         self.n_u, self.n_p = ops["avg"].shape
         self.precision = self.PRECISION if precision is None else float(precision)
         self.maxsteps = self.MAXSTEPS if maxsteps is None else int(maxsteps)
-        if "avg" not in shared:
+        self.convection, self.stencil = check_convection(convection, "ScalarStepper"), None
+        if convection != "upwind":
+            if not hasattr(eng.lib, "nss_scalar_flux_limited_f64"):
+                raise ValueError("ScalarStepper: the library has no limited flux kernel")
+            if "stencil" not in shared:
+                if stencil is None or np.shape(stencil) != (self.n_u, 4):
+                    raise ValueError("ScalarStepper: convection=%r wants the (n_u, 4) scalar stencil" % (convection,))
+                shared["stencil"] = upload_stencil(eng, stencil, self.n_p)
+            self.stencil = shared["stencil"]
+        else:
             for key in ("avg", "diff"):
+                if key in shared:
+                    continue
                 ok, why = two_entry_rows(ops[key])
                 if not ok:
                     raise ValueError("ScalarStepper: %s: %s" % (key, why))
                 shared[key] = SparseMatrix.from_scipy(ops[key], engine=eng)
+            self.avg, self.diff = shared["avg"], shared["diff"]
+        if "KB" not in shared:
             KB = sp.hstack([ops["K"], B.to_scipy()], format="csr")
             KB.sort_indices()
             shared["KB"] = SparseMatrix.from_scipy(KB, engine=eng)
@@ -1157,7 +1226,7 @@ class ScalarStepper:
             shared["q"] = eng.from_host(np.asarray(ops["q"], dtype=np.float64))
             shared["w_b"] = None if w_b is None else eng.from_host(np.asarray(w_b, dtype=np.float64))
             shared["w"] = None if flux is None else eng.from_host(np.asarray(flux[1], dtype=np.float64))
-        self.avg, self.diff, self.KB, self.mstar = (shared[key] for key in ("avg", "diff", "KB", "mstar"))
+        self.KB, self.mstar = shared["KB"], shared["mstar"]
         self.q, self.w_b, self.w = shared["q"], shared["w_b"], shared["w"]
         self.c0 = 0.0 if flux is None else float(flux[0])
         self.records = flux is not None
@@ -1182,6 +1251,12 @@ class ScalarStepper:
     def flux(self, u):
         """S1 on (u, T): G, and for a buoyant scalar f_eff.  Returns the force buffer of the velocity step (None: f)."""
         eng = self.eng
+        if self.stencil is not None:
+            eng._check(self.lib.nss_scalar_flux_limited_f64(
+                self.stencil.data_ptr(), self.n_u, CONVECTION_SCHEMES[self.convection],
+                None if self.w_b is None else self.w_b.data_ptr(), u.data_ptr(), self.f.buf.data_ptr(), self.T.data_ptr(),
+                self.t_ref, self.G.data_ptr(), None if self.f_eff is None else self.f_eff.data_ptr(), None, eng.stream))
+            return self.f_eff
         eng._check(self.lib.nss_scalar_flux_f64(self.avg.handle.ptr, self.diff.handle.ptr,
                                                 None if self.w_b is None else self.w_b.data_ptr(), u.data_ptr(),
                                                 self.f.buf.data_ptr(), self.T.data_ptr(), self.t_ref, self.G.data_ptr(),

@@ -62,6 +62,85 @@ def _shift_slices(ndim, axis):
     return tuple(lo), tuple(hi)
 
 
+LIMITERS = {"donor": 0, "minmod": 1, "vanleer": 2}       # the codes of the flux kernels (`limiter` of nss_*_flux_limited_f64)
+
+
+def _line_stencil(g, ax, count, first):
+    """(ll, lo, hi, hh) = the ids of `g` at k + first .. k + first + 3 along array axis `ax` for k = 0 .. count-1, -1
+    outside; int32 (points, 4), the points in the C order of g's shape with `count` entries along `ax`."""
+    size = g.shape[ax]
+    cols = []
+    for off in range(4):
+        at = np.arange(count) + first + off
+        ids = np.take(g, np.clip(at, 0, size - 1), axis=ax)
+        shape = [1] * g.ndim
+        shape[ax] = count
+        cols.append(np.where(((at >= 0) & (at < size)).reshape(shape), ids, -1).ravel())
+    return np.stack(cols, axis=1).astype(np.int32)
+
+
+def _inflate_stencil(st, b):
+    if b == 1:
+        return st
+    rep = np.where(st[:, None, :] >= 0, st[:, None, :] * b + np.arange(b, dtype=np.int32)[None, :, None], -1)
+    return np.ascontiguousarray(rep.reshape(-1, 4), dtype=np.int32)
+
+
+def limited_flux(stencil, adv, q, limiter):
+    """The second-order limited upwind flux at every row of `stencil` (int (n, 4): ll, lo, hi, hh into q, -1 absent)
+    for the advecting velocities `adv` (n):
+
+        a >= 0:  U = q_lo, D = q_hi, UU = q_ll        a < 0:  U = q_hi, D = q_lo, UU = q_hh
+        s = phi(U - UU, D - U) if UU exists, else 0;   F = a * (U + s / 2)
+
+    with phi = 0 ("donor"), p q > 0 ? (|p| < |q| ? p : q) : 0 ("minmod"), p q > 0 ? 2 p q / (p + q) : 0 ("vanleer").
+    An absent lo or hi is a wall and counts as 0; an absent far value leaves the point donor-cell for that flow
+    direction.  F is continuous across every branch.  Explicit Euler with these limiters is bounded for
+    tau * sum_faces |u_f| / h <= 1/2 per cell."""
+    if limiter not in LIMITERS:
+        raise ValueError("limiter %r: one of %s" % (limiter, ", ".join(LIMITERS)))
+    st = np.asarray(stencil)
+    a = np.asarray(adv, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64)
+    if q.size == 0:
+        q = np.zeros(1)
+    ll, lo, hi, hh = (np.where(st[:, k] >= 0, q[np.maximum(st[:, k], 0)], 0.0) for k in range(4))
+    pos = a >= 0
+    U, D = np.where(pos, lo, hi), np.where(pos, hi, lo)
+    UU, far = np.where(pos, ll, hh), np.where(pos, st[:, 0], st[:, 3]) >= 0
+    p, r = U - UU, D - U
+    same = far & (p * r > 0)
+    if limiter == "donor":
+        s = np.zeros_like(a)
+    elif limiter == "minmod":
+        s = np.where(same, np.where(np.abs(p) < np.abs(r), p, r), 0.0)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = np.where(same, 2.0 * p * r / np.where(same, p + r, 1.0), 0.0)
+    return a * (U + 0.5 * s)
+
+
+def _limited_point(a, q_ll, q_lo, q_hi, q_hh, limiter):
+    """`limited_flux` at one point, by branches; None = absent."""
+    if limiter not in LIMITERS:
+        raise ValueError("limiter %r: one of %s" % (limiter, ", ".join(LIMITERS)))
+    q_lo = 0.0 if q_lo is None else q_lo
+    q_hi = 0.0 if q_hi is None else q_hi
+    if a >= 0:
+        up, down, far = q_lo, q_hi, q_ll
+    else:
+        up, down, far = q_hi, q_lo, q_hh
+    slope = 0.0
+    if far is not None and limiter != "donor":
+        p, r = up - far, down - up
+        if p * r > 0:
+            if limiter == "minmod":
+                slope = p if abs(p) < abs(r) else r
+            else:
+                slope = 2.0 * p * r / (p + r)
+    return a * (up + slope / 2)
+
+
 @dataclass
 class StokesSystem:
     dim: int
@@ -278,6 +357,114 @@ class StokesSystem:
                         flux = adv * 0.5 * (u_lo + u_hi) - 0.5 * abs(adv) * (u_hi - u_lo)
                         total += side * flux
                 out[g[idx]] = -hface * total
+        return out
+
+    # ---- second-order limited convection: the four-point stencils and their evaluations ------------------------------
+    def convection_stencil(self):
+        """int32 (nflux, 4): the dofs (ll, lo, hi, hh) of the transported component along the flux direction at
+        every flux point, in the flux-point order of `convection_operators` (row r of avg is 1/2 at lo and hi, row r of
+        diff is -1 at lo and +1 at hi); -1 = absent (beyond a wall).  In an inflated system copy k of dof c is
+        c * block_size + k and the rows follow the Kronecker product's."""
+        dim, n = self.dim, self.n
+        parts = []
+        for c, g in enumerate(self.component_ids):
+            axc = _axis_of_component(dim, c)
+            for axd in range(dim):
+                # flux point k along axd: axd == axc: between faces k - 1 | k (k = 0 .. n-1 of n-1 faces);
+                # otherwise between dofs k | k + 1 (k = 0 .. n-2 of n dofs)
+                count, first = (n, -2) if axd == axc else (n - 1, -1)
+                parts.append(_line_stencil(g, axd, count, first))
+        st = np.concatenate(parts, axis=0)
+        return _inflate_stencil(st, self.block_size)
+
+    def scalar_stencil(self):
+        """int32 (n_u, 4): the cells (ll, lo, hi, hh) of every face along its normal, consistent with avg and diff of
+        `scalar_operators` (1/2, 1/2 and -1, +1 at lo, hi); -1 = absent.  Plain systems only."""
+        if self.block_size != 1:
+            raise ValueError("scalar_stencil: plain (not inflated) systems only")
+        dim, n = self.dim, self.n
+        pid = np.arange(self.n_p, dtype=np.int64).reshape((n,) * dim)
+        st = -np.ones((self.n_u, 4), dtype=np.int32)
+        for c, g in enumerate(self.component_ids):
+            # face m lies between cells m | m + 1 (m = 0 .. n-2 of n cells)
+            st[g.ravel()] = _line_stencil(pid, _axis_of_component(dim, c), n - 1, -1)
+        return st
+
+    def _limited_tables(self):
+        if "_limited" not in self.__dict__:
+            ops = self.convection_operators()
+            self._limited = (self.convection_stencil(), ops["adv"], ops["div"])
+        return self._limited
+
+    def limited_convection(self, u, limiter):
+        """conv(u) = -D F with the limited fluxes F = `limited_flux`(convection_stencil, I_adv u, u, limiter)."""
+        stencil, adv, div = self._limited_tables()
+        u = np.asarray(u, dtype=np.float64)
+        return -(div @ limited_flux(stencil, adv @ u, u, limiter))
+
+    def limited_convection_reference(self, u, limiter):
+        """`limited_convection` by direct loops over the grid, written without the stencil tables (small plain cases)."""
+        if self.block_size != 1:
+            raise ValueError("limited_convection_reference: plain (not inflated) systems only")
+        dim, n = self.dim, self.n
+        hface = self.h ** (dim - 1)
+        out = np.zeros(self.n_u)
+        comps = self.component_ids
+        axes = [_axis_of_component(dim, c) for c in range(dim)]
+
+        def val(c, idx):                                   # u_c at face multi-index idx, None outside
+            g = comps[c]
+            if any(i < 0 or i >= g.shape[a] for a, i in enumerate(idx)):
+                return None
+            return u[g[tuple(idx)]]
+
+        def moved(idx, ax, by):
+            nb = list(idx)
+            nb[ax] += by
+            return nb
+
+        for c, g in enumerate(comps):
+            axc = axes[c]
+            for idx in np.ndindex(*g.shape):
+                total = 0.0
+                for axd in range(dim):
+                    for side in (1, -1):                   # upper / lower face of the control volume along axd
+                        lo = list(idx) if side == 1 else moved(idx, axd, -1)
+                        hi = moved(lo, axd, 1)
+                        u_lo, u_hi = val(c, lo), val(c, hi)
+                        if axd == axc:
+                            adv = 0.5 * ((u_lo or 0.0) + (u_hi or 0.0))
+                        else:
+                            if u_lo is None or u_hi is None:
+                                continue                   # wall: no flux
+                            e = axes.index(axd)
+                            ie = list(lo)                  # component e at (lo along axd; idx, idx + 1 along axc)
+                            adv = 0.5 * ((val(e, ie) or 0.0) + (val(e, moved(ie, axc, 1)) or 0.0))
+                        flux = _limited_point(adv, val(c, moved(lo, axd, -1)), u_lo, u_hi, val(c, moved(hi, axd, 1)),
+                                              limiter)
+                        total += side * flux
+                out[g[idx]] = -hface * total
+        return out
+
+    def limited_scalar_flux_reference(self, u, T, limiter):
+        """The limited flux G of a cell-centred T through every face (n_u values) by direct loops, written without the
+        stencil tables (small plain cases)."""
+        if self.block_size != 1:
+            raise ValueError("limited_scalar_flux_reference: plain (not inflated) systems only")
+        dim, n = self.dim, self.n
+        T = np.asarray(T, dtype=np.float64).reshape((n,) * dim)
+        out = np.zeros(self.n_u)
+
+        def cell(idx):
+            return T[tuple(idx)] if all(0 <= i < n for i in idx) else None
+
+        for c, g in enumerate(self.component_ids):
+            ax = _axis_of_component(dim, c)
+            for face in np.ndindex(*g.shape):              # face m of component c lies between cells m and m + 1
+                at = [list(face) for _ in range(4)]
+                for k, by in enumerate((-1, 0, 1, 2)):
+                    at[k][ax] += by
+                out[g[face]] = _limited_point(u[g[face]], *(cell(i) for i in at), limiter)
         return out
 
     def _wall(self, wall):

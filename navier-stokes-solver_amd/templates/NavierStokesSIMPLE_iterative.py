@@ -26,7 +26,8 @@ reference's orchestration restated on the staggered-grid operators: ``invmstar``
 ``M_u + timestep * A`` (:85-96), ``Project`` = pressure projection through CG on ``B M_u^-1 B^T``
 (:115-144,440-443), explicit Euler update ``u += timestep * temp2`` (:438), and the explicit
 convection term ``conv_operator * gfu`` (:106-113,427-431): conservative upwind fluxes
-(``ConvectionOperator``: three SpMVs, the donor-cell flux kernel, one SpMV).
+(``ConvectionOperator``: three SpMVs, the donor-cell flux kernel, one SpMV), or with
+``NavierStokes(..., convection="minmod" | "vanleer")`` second-order limited upwind fluxes (one stencil launch, one SpMV).
 
 Out of scope: the MCS/HDG assembly itself and the sparse direct branch
 ``iterative=False`` (raises ``NotImplementedError``)."""
@@ -47,12 +48,32 @@ class ConvectionOperator(hipla.BaseMatrix):
     *nonlinear* map u -> conv(u), weak form of -div(u (x) u) with upwind fluxes, used as
     ``temp.data = conv_operator * gfu.vec`` (:429).  On the staggered grid: donor-cell fluxes
     ``F = adv*avg - |adv|*diff/2`` with ``adv = I_adv u``, ``avg = Avg u``, ``diff = Diff u`` (three
-    SpMVs), then ``conv = -D F`` (one SpMV); all on the device."""
+    SpMVs), then ``conv = -D F`` (one SpMV); all on the device.
 
-    def __init__(self, system):
+    `scheme` "minmod" / "vanleer": the second-order limited fluxes ``F = adv * (U + s / 2)`` of
+    `staggered_grid.limited_flux` over `system.convection_stencil()` -- one launch of ``nss_step_flux_limited_f64``,
+    then ``-D F``; an engine without that entry point (the checker engine), or an `adv` the kernel refuses (a row of
+    more than two entries, which no grid of this package produces), evaluates `system.limited_convection` on the host
+    and uploads the result."""
+
+    def __init__(self, system, scheme="upwind"):
         super().__init__()
+        from hipla.fused import check_convection
+        self.scheme = check_convection(scheme, "ConvectionOperator")
         ops = system.convection_operators()
         self.n = system.n_u
+        self.stencil = None
+        if scheme != "upwind":
+            self.system = system
+            self.adv, self.div = (hipla.SparseMatrix.from_scipy(ops[k]) for k in ("adv", "div"))
+            self._flux = self.adv.CreateColVector()
+            eng = self._flux.engine
+            from hipla.fused import two_entry_rows
+            self._native = hasattr(getattr(eng, "lib", None), "nss_step_flux_limited_f64") and two_entry_rows(ops["adv"])[0]
+            if self._native:
+                from hipla.fused import upload_stencil
+                self.stencil = upload_stencil(eng, system.convection_stencil(), self.n)
+            return
         self.adv, self.avg, self.diff, self.div = (hipla.SparseMatrix.from_scipy(ops[k])
                                                    for k in ("adv", "avg", "diff", "div"))
         self._work = [self.adv.CreateColVector() for _ in range(4)]
@@ -64,6 +85,17 @@ class ConvectionOperator(hipla.BaseMatrix):
         return self.n
 
     def Mult(self, x, y):
+        if self.scheme != "upwind":
+            if not self._native:
+                y.data = hipla.Vector.from_numpy(self.system.limited_convection(x.numpy(), self.scheme))
+                return
+            from hipla.fused import CONVECTION_SCHEMES
+            flux, eng = self._flux, self._flux.engine
+            eng._check(eng.lib.nss_step_flux_limited_f64(self.adv.handle.ptr, self.stencil.data_ptr(), self.adv.height,
+                                                         CONVECTION_SCHEMES[self.scheme], x.buf.data_ptr(),
+                                                         flux.buf.data_ptr(), None, eng.stream))
+            y.data = -self.div * flux
+            return
         adv, avg, diff, flux = self._work
         adv.data = self.adv * x
         avg.data = self.avg * x
@@ -144,9 +176,13 @@ class ScalarField:
     diff, q, the CG inverse of M_p + timestep K, the buoyancy weights as a diagonal matrix) and what a device-resident
     `hipla.fused.ScalarStepper` is made from."""
 
-    def __init__(self, system, b_mat, timestep, kappa, dirichlet, buoyancy, t_ref, precision, maxsteps, flux_wall):
-        from hipla.fused import ScalarStepper
+    def __init__(self, system, b_mat, timestep, kappa, dirichlet, buoyancy, t_ref, precision, maxsteps, flux_wall,
+                 convection="upwind"):
+        from hipla.fused import ScalarStepper, check_convection
+        self.convection = check_convection(convection, "AddScalar")
         self.ops = ops = system.scalar_operators(kappa, dirichlet)
+        self.stencil = system.scalar_stencil() if convection != "upwind" else None    # host array; uploaded on first use
+        self.stencil_dev = None
         self.t_ref = float(t_ref)
         self.precision = ScalarStepper.PRECISION if precision is None else float(precision)
         self.maxsteps = ScalarStepper.MAXSTEPS if maxsteps is None else int(maxsteps)
@@ -173,7 +209,13 @@ class ScalarField:
 
 
 class NavierStokes:
-    def __init__(self, mesh, nu, inflow, outflow, wall, uin, timestep, order=2, volumeforce=None):
+    def __init__(self, mesh, nu, inflow, outflow, wall, uin, timestep, order=2, volumeforce=None, convection="upwind"):
+        """`convection`: the scheme of the explicit convection term in `DoTimeStep` and `Advance` -- "upwind" (donor
+        cell, first order: numerical viscosity about |u| h / 2) or the second-order limited "minmod" / "vanleer"
+        (`staggered_grid.limited_flux`; first order remains at the one flux point per grid line and direction next to
+        each wall).  Explicit Euler with the limiters wants timestep * sum_faces |u_f| / h <= 1/2 per cell."""
+        from hipla.fused import check_convection
+        self.convection = check_convection(convection, "NavierStokes")
         self.mesh, self.nu, self.timestep, self.order = mesh, nu, timestep, order
         self.inflow, self.outflow, self.wall, self.uin = inflow, outflow, wall, uin
         self.V, self.Q = bdm_hybrid(order, 10)[0](mesh, velocity_dirichlet=inflow + "|" + wall)
@@ -189,7 +231,7 @@ class NavierStokes:
     @property
     def conv_operator(self):
         if self._conv_operator is None:
-            self._conv_operator = ConvectionOperator(self.system)
+            self._conv_operator = ConvectionOperator(self.system, self.convection)
         return self._conv_operator
 
     @conv_operator.setter
@@ -285,7 +327,7 @@ class NavierStokes:
         self.f.vec.data += hipla.Vector.from_numpy(np.asarray(force, dtype=np.float64))
 
     def AddScalar(self, kappa, dirichlet=None, buoyancy=None, t_ref=0.0, initial=None, precision=None, maxsteps=None,
-                  flux_wall=None):
+                  flux_wall=None, convection=None):
         """Carry a cell-centred scalar T (a temperature) with the flow: M_p dT/dt = q - K T - B G with diffusivity
         `kappa`, the donor-cell flux G of T through the faces (the face velocities are the velocity dofs) and implicit
         diffusion; `DoTimeStep` and `Advance` then advance T with u, coupled explicitly (first order, like the
@@ -296,10 +338,11 @@ class NavierStokes:
         component c, takes the place of f in the momentum equation; None = a passive scalar.  `initial`: host array of
         n_p cell values (None: `t_ref` everywhere).  `precision` / `maxsteps` of the temperature solve: None = those of
         invmstar (1e-4, 500).  `flux_wall`: the Dirichlet wall whose heat flux `Advance` records (None: the first one
-        given).  The scalar is `self.temperature`; `AddForce` keeps working: f is read every step."""
+        given).  `convection`: the scheme of G, "upwind" | "minmod" | "vanleer" as for the constructor (None: the
+        velocity's).  The scalar is `self.temperature`; `AddForce` keeps working: f is read every step."""
         dirichlet = dict(dirichlet or {})
         self._scalar = ScalarField(self.system, self.b.mat, self.timestep, kappa, dirichlet, buoyancy, t_ref, precision,
-                                   maxsteps, flux_wall)
+                                   maxsteps, flux_wall, self.convection if convection is None else convection)
         start = np.full(self.system.n_p, float(t_ref)) if initial is None else np.asarray(initial, dtype=np.float64)
         if start.shape != (self.system.n_p,):
             raise ValueError("AddScalar: initial holds %s values, the grid has %d cells" % (start.shape, self.system.n_p))
@@ -310,13 +353,33 @@ class NavierStokes:
         force of the step, f + w_b * (avg T - t_ref) (f itself for a passive scalar)."""
         sc = self._scalar
         sc.avgT.data = sc.avg * self.temperature
-        sc.difT.data = sc.diff * self.temperature
-        sc.G.engine.upwind_flux(self.gfu.buf, sc.avgT.buf, sc.difT.buf, sc.G.buf)
+        if sc.convection == "upwind":
+            sc.difT.data = sc.diff * self.temperature
+            sc.G.engine.upwind_flux(self.gfu.buf, sc.avgT.buf, sc.difT.buf, sc.G.buf)
+        else:
+            self._limited_scalar_flux(sc)
         if sc.Wb is None:
             return self.f.vec
         sc.avgT.data -= sc.tref_u
         sc.f_eff.data = self.f.vec + sc.Wb * sc.avgT
         return sc.f_eff
+
+    def _limited_scalar_flux(self, sc):
+        """G by the scalar's limited scheme: one passive launch of ``nss_scalar_flux_limited_f64``, or -- an engine
+        without it -- `limited_flux` on the host, uploaded."""
+        eng = sc.G.engine
+        if not hasattr(getattr(eng, "lib", None), "nss_scalar_flux_limited_f64"):
+            from staggered_grid import limited_flux
+            sc.G.data = hipla.Vector.from_numpy(limited_flux(sc.stencil, self.gfu.numpy(), self.temperature.numpy(),
+                                                             sc.convection))
+            return
+        from hipla.fused import CONVECTION_SCHEMES, upload_stencil
+        if sc.stencil_dev is None:
+            sc.stencil_dev = upload_stencil(eng, sc.stencil, self.system.n_p)
+        eng._check(eng.lib.nss_scalar_flux_limited_f64(sc.stencil_dev.data_ptr(), self.system.n_u,
+                                                       CONVECTION_SCHEMES[sc.convection], None, self.gfu.buf.data_ptr(),
+                                                       None, self.temperature.buf.data_ptr(), 0.0, sc.G.buf.data_ptr(),
+                                                       None, None, eng.stream))
 
     def _scalar_step(self):
         """The last statements of a step with a scalar: temp_T = q - K T - B G;  delta = (M_p + timestep K)^-1 temp_T;
@@ -386,7 +449,8 @@ class NavierStokes:
                 ops = self._time_stepping_operators()
                 self._stepper_shared = dict(mstar=ops["mstar"], Lp=ops["Lp"], C=ops["correct"])
             stepper = TimeStepper.try_create(s, self.a.mat, self.b.mat, self.f.vec, self.timestep, m_u, inner_pre,
-                                             conv_operator=lambda: self.conv_operator, shared=self._stepper_shared)
+                                             conv_operator=lambda: self.conv_operator, shared=self._stepper_shared,
+                                             convection=self.convection)
             if stepper is not None:
                 steppers[inner_pre] = stepper
         self.advance_declined = TimeStepper.last_declined if stepper is None else None
@@ -396,7 +460,7 @@ class NavierStokes:
                 from hipla.fused import ScalarStepper
                 sc.steppers[inner_pre] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
                                                        inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
-                                                       shared=sc.shared)
+                                                       shared=sc.shared, convection=sc.convection, stencil=sc.stencil)
             return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics,
                                    scalar=sc.steppers[inner_pre], temperature=self.temperature)
         if stepper is not None:
@@ -447,5 +511,5 @@ class NavierStokes:
                 sv.precision, sv.maxsteps = p, m
         return record_type(its_m, its_p, np.array(div) if diagnostics else None,
                            np.array(energy) if diagnostics else None, declined=self.advance_declined,
-                           scalar_iterations=its_s,
+                           scalar_iterations=its_s, convection=self.convection,
                            wall_flux=np.array(wall) if sc is not None and diagnostics and sc.flux is not None else None)

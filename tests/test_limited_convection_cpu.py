@@ -1,0 +1,343 @@
+"""Second-order limited convection (minmod, van Leer) on the host: the four-point stencils of `StokesSystem` against
+the operators they stand beside, the vectorised `limited_flux` against direct loops over the grid, the order of accuracy
+and the bounds of the scheme, the statement path of `NavierStokes(convection=)` on the checker engine, and the C ABI of
+csrc/limited.hip (header, exports, argument errors).  No GPU."""
+
+import contextlib
+import io
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+from conftest import ROOT
+from oracle import krylov_ref as kr
+
+LIMITED_SYMBOLS = ("nss_step_flux_limited_f64", "nss_scalar_flux_limited_f64")
+SCHEMES = ("donor", "minmod", "vanleer")
+
+
+def systems():
+    from staggered_grid import mac_stokes
+    return {"2d-5": mac_stokes(2, 5), "2d-6": mac_stokes(2, 6), "3d-4": mac_stokes(3, 4),
+            "2d-5-inflated-3": mac_stokes(2, 5).inflate(3)}
+
+
+def from_stencil(stencil, n, weights):
+    """The two-entry matrix with `weights` at (lo, hi) of every stencil row, absent entries left out."""
+    rows = np.repeat(np.arange(stencil.shape[0]), 2)
+    cols = stencil[:, 1:3].ravel()
+    vals = np.tile(np.asarray(weights, dtype=np.float64), stencil.shape[0])
+    keep = cols >= 0
+    mat = sp.coo_matrix((vals[keep], (rows[keep], cols[keep])), shape=(stencil.shape[0], n)).tocsr()
+    mat.sort_indices()
+    return mat
+
+
+def same_matrix(a, b):
+    return a.shape == b.shape and np.array_equal(a.indptr, b.indptr) and np.array_equal(a.indices, b.indices) \
+        and np.array_equal(a.data, b.data)
+
+
+# ---- 1. the stencils ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["2d-5", "2d-6", "3d-4", "2d-5-inflated-3"])
+def test_stencils_rebuild_avg_and_diff_exactly(case):
+    """avg (1/2, 1/2) and diff (-1, +1) rebuilt from columns (lo, hi) of `convection_stencil()` ARE those of
+    `convection_operators()` (same rows, same order, same bits); the far columns continue the line: where both exist
+    ll, lo, hi, hh are equally spaced ids' positions (checked through the line direction: lo - ll == hi - lo == hh - hi
+    for plain systems, whose ids are affine along a grid line).  The same for `scalar_stencil()`."""
+    s = systems()[case]
+    ops = s.convection_operators()
+    st = s.convection_stencil()
+    assert st.dtype == np.int32 and st.shape == (ops["adv"].shape[0], 4)
+    assert st.min() >= -1 and st.max() < s.n_u
+    assert same_matrix(from_stencil(st, s.n_u, (0.5, 0.5)), ops["avg"])
+    assert same_matrix(from_stencil(st, s.n_u, (-1.0, 1.0)), ops["diff"])
+    full = (st >= 0).all(axis=1)
+    assert full.any() and (st[:, 0] < 0).any() and (st[:, 3] < 0).any()
+    d = np.diff(st[full].astype(np.int64), axis=1)
+    assert (d[:, 0] == d[:, 1]).all() and (d[:, 1] == d[:, 2]).all() and (d[:, 0] > 0).all()
+    if s.block_size > 1:
+        plain = systems()[case.split("-inflated")[0]].convection_stencil().astype(np.int64)
+        b = s.block_size
+        want = np.where(plain[:, None, :] >= 0, plain[:, None, :] * b + np.arange(b)[None, :, None], -1).reshape(-1, 4)
+        assert np.array_equal(st, want)
+        with pytest.raises(ValueError):
+            s.scalar_stencil()
+        return
+    sops = s.scalar_operators(1.0, {})
+    ss = s.scalar_stencil()
+    assert ss.dtype == np.int32 and ss.shape == (s.n_u, 4) and ss.min() >= -1 and ss.max() < s.n_p
+    assert (ss[:, 1:3] >= 0).all()                                  # every face dof lies between two cells
+    assert same_matrix(from_stencil(ss, s.n_p, (0.5, 0.5)), sops["avg"])
+    assert same_matrix(from_stencil(ss, s.n_p, (-1.0, 1.0)), sops["diff"])
+    full = (ss >= 0).all(axis=1)
+    d = np.diff(ss[full].astype(np.int64), axis=1)
+    assert (d[:, 0] == d[:, 1]).all() and (d[:, 1] == d[:, 2]).all()
+
+
+# ---- 2. vectorised against direct loops ----------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["2d-5", "2d-6", "3d-4"])
+def test_vectorised_evaluations_against_direct_loops(case):
+    """`limited_convection` against `limited_convection_reference` to 1e-14 of |D| |F|-scale (|D| applied to
+    |adv| (|q_ll| + |q_lo| + |q_hi| + |q_hh|)), `limited_flux` on the scalar stencil against
+    `limited_scalar_flux_reference` likewise, limiter "donor" against `convection_reference` to the same bound; the
+    limiters change the result visibly."""
+    from staggered_grid import limited_flux
+    s = systems()[case]
+    rng = np.random.default_rng(len(case) + s.n)
+    u, T = rng.standard_normal(s.n_u), rng.standard_normal(s.n_p)
+    ops = s.convection_operators()
+    st = s.convection_stencil()
+    q = np.where(st >= 0, np.abs(u)[np.maximum(st, 0)], 0.0).sum(axis=1)
+    scale = abs(ops["div"]) @ (np.abs(ops["adv"] @ u) * q)
+    got = {lim: s.limited_convection(u, lim) for lim in SCHEMES}
+    for lim in SCHEMES:
+        err = np.abs(got[lim] - s.limited_convection_reference(u, lim))
+        assert (err <= 1e-14 * scale.max()).all(), (lim, err.max(), scale.max())
+    assert (np.abs(got["donor"] - s.convection_reference(u)) <= 1e-14 * scale.max()).all()
+    assert np.linalg.norm(got["minmod"] - got["donor"]) > 1e-2 * np.linalg.norm(got["donor"])
+    assert np.linalg.norm(got["vanleer"] - got["minmod"]) > 1e-3 * np.linalg.norm(got["donor"])
+    ss = s.scalar_stencil()
+    tq = np.where(ss >= 0, np.abs(T)[np.maximum(ss, 0)], 0.0).sum(axis=1)
+    flux = {lim: limited_flux(ss, u, T, lim) for lim in SCHEMES}
+    for lim in SCHEMES:
+        err = np.abs(flux[lim] - s.limited_scalar_flux_reference(u, T, lim))
+        assert (err <= 1e-14 * np.abs(u) * tq).all(), (lim, err.max())
+    sops = s.scalar_operators(1.0, {})
+    donor = u * (sops["avg"] @ T) - 0.5 * np.abs(u) * (sops["diff"] @ T)
+    assert (np.abs(flux["donor"] - donor) <= 1e-14 * np.abs(u) * tq).all()
+    assert np.linalg.norm(flux["vanleer"] - flux["donor"]) > 1e-2 * np.linalg.norm(donor)
+    with pytest.raises(ValueError):
+        limited_flux(ss, u, T, "superbee")
+    with pytest.raises(ValueError):
+        s.limited_convection_reference(u, "superbee")
+
+
+def test_inflated_copies_are_advected_by_themselves():
+    """In an inflated system copy k of the field is the plain system's evaluation on u[k::b]."""
+    s = systems()["2d-5-inflated-3"]
+    plain = systems()["2d-5"]
+    u = np.random.default_rng(3).standard_normal(s.n_u)
+    for lim in ("minmod", "vanleer"):
+        got = s.limited_convection(u, lim)
+        for k in range(3):
+            want = plain.limited_convection(u[k::3], lim)
+            assert np.abs(got[k::3] - want).max() <= 1e-14 * np.abs(want).max()
+
+
+# ---- 3. order of accuracy ------------------------------------------------------------------------------------------
+def truncation_error(n, limiter):
+    """Mean |B G / h^2 - u . grad T| over the cells of the 2-D grid: face velocities from the node stream function
+    psi = sin^2(pi x) sin^2(pi y) / pi (discretely divergence-free, zero on the walls), T = cos(pi x) cos(2 pi y) +
+    0.3 sin(2 pi x) at the cell centres, the exact velocity and gradient at the cell centres."""
+    from staggered_grid import limited_flux, mac_stokes
+    s = mac_stokes(2, n)
+    h, pi = s.h, np.pi
+    X, Y = np.meshgrid(np.arange(n + 1) * h, np.arange(n + 1) * h)          # nodes [j, i]
+    psi = np.sin(pi * X) ** 2 * np.sin(pi * Y) ** 2 / pi
+    gu, gv = s.component_ids
+    u = np.zeros(s.n_u)
+    u[gu] = (psi[1:, 1:-1] - psi[:-1, 1:-1]) / h                              # u = Delta_y psi / h
+    u[gv] = -(psi[1:-1, 1:] - psi[1:-1, :-1]) / h                             # v = -Delta_x psi / h
+    assert np.abs(s.B @ u).max() <= 1e-14 * h
+    Xc, Yc = np.meshgrid((np.arange(n) + 0.5) * h, (np.arange(n) + 0.5) * h)
+    T = np.cos(pi * Xc) * np.cos(2 * pi * Yc) + 0.3 * np.sin(2 * pi * Xc)
+    G = limited_flux(s.scalar_stencil(), u, T.ravel(), limiter)
+    ue, ve = np.sin(pi * Xc) ** 2 * np.sin(2 * pi * Yc), -np.sin(2 * pi * Xc) * np.sin(pi * Yc) ** 2
+    Tx = -pi * np.sin(pi * Xc) * np.cos(2 * pi * Yc) + 0.6 * pi * np.cos(2 * pi * Xc)
+    Ty = -2 * pi * np.cos(pi * Xc) * np.sin(2 * pi * Yc)
+    return float(np.abs((s.B @ G) / h ** 2 - (ue * Tx + ve * Ty).ravel()).mean())
+
+
+def test_order_of_accuracy():
+    """Observed order >= 1.7 for both limiters, between 0.8 and 1.2 for donor, and the limited error at n = 32 at most
+    a quarter of donor's.  What the product's operators give (n = 16 -> 32; n = 64 for the record):
+
+        donor    0.30391 -> 0.15231 (-> 0.07619)   order 1.00
+        minmod   0.08039 -> 0.02132 (-> 0.00553)   order 1.91
+        vanleer  0.07624 -> 0.02026 (-> 0.00526)   order 1.91"""
+    err = {lim: (truncation_error(16, lim), truncation_error(32, lim)) for lim in SCHEMES}
+    order = {lim: float(np.log2(e[0] / e[1])) for lim, e in err.items()}
+    print(err, order)
+    assert 0.8 <= order["donor"] <= 1.2
+    for lim in ("minmod", "vanleer"):
+        assert order[lim] >= 1.7, (lim, order[lim])
+        assert err[lim][1] <= 0.25 * err["donor"][1]
+    assert abs(err["donor"][0] - 0.304) < 1e-3 and abs(err["vanleer"][1] - 0.0203) < 1e-4     # the recorded values
+
+
+# ---- 4. bounds and conservation ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [12, 32])
+def test_bounds_and_conservation(n):
+    """300 explicit steps T -= tau B G / h^d of a seeded 0 / 1 field in a seeded discretely divergence-free velocity
+    (random node stream function, zero on the walls), all walls insulated, tau / h * max_cell sum_faces |u_f| = 0.25:
+    T stays inside [0, 1] to 1e-12 and sum T is kept to 1e-12 sum T0, for donor, minmod and van Leer."""
+    from staggered_grid import limited_flux, mac_stokes
+    s = mac_stokes(2, n)
+    h = s.h
+    rng = np.random.default_rng(100 + n)
+    psi = np.zeros((n + 1, n + 1))
+    psi[1:-1, 1:-1] = rng.standard_normal((n - 1, n - 1))
+    gu, gv = s.component_ids
+    u = np.zeros(s.n_u)
+    u[gu] = (psi[1:, 1:-1] - psi[:-1, 1:-1]) / h
+    u[gv] = -(psi[1:-1, 1:] - psi[1:-1, :-1]) / h
+    assert np.abs(s.B @ u).max() <= 1e-13 * h * np.abs(u).max()
+    per_cell = (abs(s.B) @ np.abs(u)) / h                           # sum over the faces of a cell of |u_f|  (B ~ +-h)
+    tau = 0.25 * h / per_cell.max()
+    T0 = (rng.random(s.n_p) < 0.5).astype(np.float64)
+    assert 0 < T0.sum() < s.n_p
+    ss = s.scalar_stencil()
+    for lim in SCHEMES:
+        T = T0.copy()
+        low, high = 0.0, 1.0
+        for _ in range(300):
+            T -= tau * (s.B @ limited_flux(ss, u, T, lim)) / h ** 2
+            low, high = min(low, T.min()), max(high, T.max())
+        print(n, lim, low, high - 1.0, abs(T.sum() - T0.sum()) / T0.sum())
+        assert low >= -1e-12 and high <= 1.0 + 1e-12, (lim, low, high)
+        assert abs(T.sum() - T0.sum()) <= 1e-12 * T0.sum()
+        assert np.abs(T - T0).max() > 0.1                           # (the field did move)
+
+
+# ---- 5. the statement path on the checker engine --------------------------------------------------------------------
+def fresh(scheme=None, order=0, dim=2, **scalar):
+    """`scheme`: the velocity's (None: the constructor's default); `scalar`: the arguments of AddScalar, its own
+    `convection` among them."""
+    import hipla
+    from templates.NavierStokesSIMPLE_iterative import NavierStokes, SyntheticMesh
+    extra = {} if scheme is None else {"convection": scheme}
+    ns = NavierStokes(SyntheticMesh(0.2 if dim == 2 else 0.25, dim=dim), nu=0.01, inflow="inlet", outflow="outlet",
+                      wall="wall|cyl", uin=None, timestep=0.05, order=order, **extra)
+    s = ns.system
+    ns.AddForce(0.1 * np.random.default_rng(8).standard_normal(s.n_u))
+    ns.gfu.data = hipla.Vector.from_numpy(0.1 * np.random.default_rng(2).standard_normal(s.n_u))
+    if scalar:
+        ns.AddScalar(initial=np.random.default_rng(6).random(s.n_p), precision=1e-14, maxsteps=5000, **scalar)
+    ops = ns._time_stepping_operators()
+    ops["invmstar"] = hipla.CGSolver(ops["mstar"], pre=hipla.JacobiPreconditioner(ops["mstar"]), precision=1e-14, maxsteps=5000)
+    ops["invproj"] = hipla.CGSolver(ops["Lp"], pre=hipla.JacobiPreconditioner(ops["Lp"]), precision=1e-14, maxsteps=20000)
+    return ns
+
+
+def rel(a, b):
+    return np.linalg.norm(a - b) / np.linalg.norm(b)
+
+
+@pytest.mark.parametrize("dim,order", [(2, 0), (3, 0), (2, 1)])
+@pytest.mark.parametrize("scheme", ["minmod", "vanleer"])
+def test_do_time_step_against_the_oracle_with_limited_convection(numpy_engine, scheme, dim, order):
+    """`DoTimeStep()` of `NavierStokes(convection=scheme)` with converged inner solves against `kr.do_time_step` with
+    conv = `limited_convection`: u to 1e-8 (the bound of tests/test_scalar_transport_cpu.py behind two solves), the
+    convection term itself to 1e-13; `Advance` (declined: the same statements) gives the same bits and names the
+    scheme; the scheme matters (the upwind twin differs)."""
+    import hipla
+    ns, twin, upwind = fresh(scheme, order, dim), fresh(scheme, order, dim), fresh(None, order, dim)
+    s = ns.system
+    assert (s.block_size == 1) == (order == 0)
+    u0, f = ns.gfu.numpy(), ns.f.vec.numpy()
+    m_u = np.full(s.n_u, s.h ** s.dim)
+    want = kr.do_time_step(s.A, s.B, m_u, ns.timestep, u0, f, lambda u: s.limited_convection(u, scheme))
+    y = hipla.Vector(s.n_u)
+    y.data = ns.conv_operator * ns.gfu
+    conv = s.limited_convection(u0, scheme)
+    assert np.abs(y.numpy() - conv).max() <= 1e-13 * np.abs(conv).max()
+    with contextlib.redirect_stdout(io.StringIO()):
+        ns.DoTimeStep()
+        upwind.DoTimeStep()
+    assert rel(ns.gfu.numpy(), want["u"]) < 1e-8
+    assert rel(upwind.gfu.numpy(), want["u"]) > 1e-6
+    rec = twin.Advance(1, precision=1e-14, maxsteps=(5000, 20000))
+    assert rec.declined == "not the HIP engine" and rec.convection == scheme
+    assert np.array_equal(twin.gfu.numpy(), ns.gfu.numpy())
+    assert upwind.Advance(1).convection == "upwind"
+
+
+@pytest.mark.parametrize("scheme", ["minmod", "vanleer"])
+def test_scalar_statements_use_the_scalar_scheme(numpy_engine, scheme):
+    """`_scalar_flux` of a limited scalar gives `limited_flux` on the scalar stencil (1e-13) and the unchanged force
+    statement; `convection=None` of `AddScalar` takes the velocity's scheme, a given one overrides it."""
+    from staggered_grid import limited_flux
+    args = dict(kappa=0.8, dirichlet={"x-": 1.0, "x+": 0.0}, buoyancy=(0.0, 40.0), t_ref=0.5)
+    ns = fresh(scheme, **args)
+    s = ns.system
+    assert ns._scalar.convection == scheme and ns._scalar.stencil is not None
+    u, T, f = ns.gfu.numpy(), ns.temperature.numpy(), ns.f.vec.numpy()
+    force = ns._scalar_flux()
+    want = limited_flux(s.scalar_stencil(), u, T, scheme)
+    assert rel(ns._scalar.G.numpy(), want) < 1e-13
+    sops = s.scalar_operators(0.8, args["dirichlet"])
+    assert rel(force.numpy(), f + s.buoyancy_weights((0.0, 40.0)) * (sops["avg"] @ T - 0.5)) < 1e-13
+    with contextlib.redirect_stdout(io.StringIO()):
+        ns.DoTimeStep()
+    assert np.isfinite(ns.temperature.numpy()).all() and rel(ns.temperature.numpy(), T) > 1e-4
+    mixed = fresh(None, **dict(args, convection=scheme))
+    assert mixed.convection == "upwind" and mixed._scalar.convection == scheme
+    mixed._scalar_flux()
+    assert rel(mixed._scalar.G.numpy(), want) < 1e-13
+    back = fresh(scheme, **dict(args, convection="upwind"))
+    assert back._scalar.convection == "upwind" and back._scalar.stencil is None
+    back._scalar_flux()
+    donor = u * (sops["avg"] @ T) - 0.5 * np.abs(u) * (sops["diff"] @ T)
+    assert rel(back._scalar.G.numpy(), donor) < 1e-13
+
+
+def test_scheme_names_and_the_default_object(numpy_engine):
+    """An unknown scheme raises ValueError wherever one is named; a default object is an "upwind" one and holds no
+    stencil."""
+    from hipla.fused import StepRecord
+    from templates.NavierStokesSIMPLE_iterative import ConvectionOperator, NavierStokes, SyntheticMesh
+    with pytest.raises(ValueError):
+        fresh("superbee")
+    with pytest.raises(ValueError):
+        fresh("donor")                                              # (the kernels' name of "upwind" is not public)
+    ns = fresh()
+    with pytest.raises(ValueError):
+        ns.AddScalar(1.0, convection="quick")
+    with pytest.raises(ValueError):
+        ConvectionOperator(ns.system, "quick")
+    assert ns.convection == "upwind" and ns.conv_operator.scheme == "upwind" and ns.conv_operator.stencil is None
+    ns.AddScalar(1.0, dirichlet={"x-": 1.0})
+    assert ns._scalar.convection == "upwind" and ns._scalar.stencil is None
+    assert StepRecord([1], [1], None, None).convection == "upwind"
+    import inspect
+    params = list(inspect.signature(NavierStokes.__init__).parameters)
+    assert params[-1] == "convection"                               # last: every positional call keeps its meaning
+    assert list(inspect.signature(NavierStokes.AddScalar).parameters)[-1] == "convection"
+    assert SyntheticMesh is not None
+
+
+# ---- 6. header and exports -----------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as entry
+    from hipla.hip_engine import LIB_PATH, load_library
+    if not os.path.exists(LIB_PATH):
+        entry.build()
+    return load_library()
+
+
+def test_header_declares_the_limited_entry_points():
+    with open(os.path.join(ROOT, "include", "nss_krylov.h")) as fh:
+        header = fh.read()
+    for must in LIMITED_SYMBOLS:
+        assert re.search(r"NSS_API\s+int\s+%s\s*\(" % must, header), must
+
+
+def test_library_exports_the_limited_entry_points(lib):
+    from hipla.hip_engine import LIB_PATH, _signatures
+    dynamic = subprocess.run(["nm", "-D", "--defined-only", LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in dynamic.splitlines() if line.strip()}
+    for must in LIMITED_SYMBOLS:
+        assert hasattr(lib, must) and must in exported and must in _signatures(), must
+
+
+def test_limited_entry_points_report_argument_errors(lib):
+    assert lib.nss_step_flux_limited_f64(None, None, 0, 0, None, None, None, None) != 0
+    assert b"step_flux_limited" in lib.nss_last_error()
+    assert lib.nss_scalar_flux_limited_f64(None, 0, 0, None, None, None, None, 0.0, None, None, None, None) != 0
+    assert b"scalar_flux_limited" in lib.nss_last_error()
