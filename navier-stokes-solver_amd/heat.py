@@ -133,12 +133,12 @@ def evolve(initial_temperature, end_time, time_step, n=64, subspace_dimension=5,
     `initial_temperature`: host array of length n^2 (`sum_of_unit_square_laplace_eigenfunctions`); `operators`:
     ``(K, m)`` -- a scipy matrix and a lumped mass diagonal -- instead of `diffusion_operators_2d(n)` (another grid, a
     non-uniform mass).  `diagnostics`: also record the largest entry of |V^T V - I| per step; `on_step(step)`: called
-    after every step.  Returns ``(temperature, time, record)`` with a `hipla.fused.HeatRecord`: on the HIP engine the
-    step runs device-resident (`hipla.fused.HeatIntegrator`); otherwise (no HIP engine, ``hipla.fused.ENABLED`` off) the
+    after every step.  Returns ``(temperature, time, record)`` with a `hipla.stepping.HeatRecord`: on the HIP engine the
+    step runs device-resident (`hipla.stepping.HeatIntegrator`); otherwise (no HIP engine, ``hipla.fused.ENABLED`` off) the
     same statements run through the protocol and ``record.declined`` says why.  A zero or rank-deficient basis raises
     `ValueError` naming the step."""
     import scipy.sparse as sp
-    from hipla import fused
+    from hipla.stepping import HeatIntegrator, HeatRecord
     from hipla.matrix import JacobiPreconditioner
     if inner_pre not in ("jacobi", "amg"):
         raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
@@ -160,7 +160,7 @@ def evolve(initial_temperature, end_time, time_step, n=64, subspace_dimension=5,
     iterations, orthogonality = [], [] if diagnostics else None
     time, step = 0, 0
 
-    integrator = fused.HeatIntegrator.try_create(diffusion, mass, heat, pre, d, diagnostics)
+    integrator = HeatIntegrator.try_create(diffusion, mass, heat, pre, d, diagnostics)
     if integrator is not None:
         integrator.load(start)
         while time < end_time:
@@ -175,9 +175,9 @@ def evolve(initial_temperature, end_time, time_step, n=64, subspace_dimension=5,
             if on_step is not None:
                 on_step(step)
             step += 1
-        return integrator.temperature(), time, fused.HeatRecord(iterations, orthogonality)
+        return integrator.temperature(), time, HeatRecord(iterations, orthogonality)
 
-    declined = fused.HeatIntegrator.last_declined
+    declined = HeatIntegrator.last_declined
     heat_inverse = hipla.CGSolver(heat, pre=pre, precision=precision, maxsteps=maxsteps)
     temperature = hipla.Vector.from_numpy(start)
     residual, solution = temperature.CreateVector(), temperature.CreateVector()
@@ -219,7 +219,7 @@ def evolve(initial_temperature, end_time, time_step, n=64, subspace_dimension=5,
         if on_step is not None:
             on_step(step)
         step += 1
-    return temperature.numpy().copy(), time, fused.HeatRecord(iterations, orthogonality, declined=declined)
+    return temperature.numpy().copy(), time, HeatRecord(iterations, orthogonality, declined=declined)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ IdentityMatrix, Vector, InnerProduct, Norm, Projector; plus ``hipla.la`` and
 ``hipla.ngstd`` submodules shaped like ``ngsolve.la`` / ``ngsolve.ngstd``.
 """
 
-from . import la, ngstd
+from . import fused, la, ngstd    # noqa: F401  (fused before hipla.stepping: it re-exports that module's names)
 from .engine import EngineUnavailable, get_engine, set_engine
 from .la import *  # noqa: F401,F403
 from .ngstd import SetHeapSize, TaskManager, Timer

@@ -1,0 +1,533 @@
+"""Host side of the device-resident integrators in time: the IMEX step of `NavierStokes.Advance` (`TimeStepper`, with a
+scalar `ScalarStepper`; C ABI ``nss_step_*`` / ``nss_scalar_*``) and the heat exponential integrator (`HeatIntegrator`),
+each around `fused.CgLoop` solves.  They follow the `try_create` convention of the fused Krylov loops (hipla/fused.py)
+and read its switch, ``fused.ENABLED``, when `try_create` is called."""
+
+import ctypes as C
+
+import numpy as np
+
+from . import fused
+from .amg import SmoothedAggregationAMG
+from .fused import CgLoop, FusedLoop, _hip, pre_for
+from .matrix import JacobiPreconditioner, ScaledMatrix, SparseMatrix, SumMatrix
+from .vector import Vector
+
+
+def two_entry_rows(mat):
+    """Whether every row of the scipy CSR matrix `mat` holds at most two entries -- the shape the row-per-lane kernels
+    take (``nss::fixed_width_copy``): (True, None) or (False, reason)."""
+    longest = int(np.diff(mat.indptr).max()) if mat.shape[0] else 0
+    if longest > 2:
+        return False, "a row holds %d entries (the row-per-lane kernels take two)" % longest
+    return True, None
+
+
+def constants_in_kernel(lap):
+    """The test of oracle/krylov_ref.py::project for a pressure operator with the constants in its kernel (enclosed
+    domain): |L 1| <= 1e-12 sum |L|."""
+    return bool(np.linalg.norm(lap @ np.ones(lap.shape[0])) <= 1e-12 * abs(lap).sum())
+
+
+CONVECTION_SCHEMES = {"upwind": 0, "minmod": 1, "vanleer": 2}      # scheme -> `limiter` of nss_*_flux_limited_f64
+
+
+def check_convection(scheme, who):
+    if scheme not in CONVECTION_SCHEMES:
+        raise ValueError("%s: convection is \"upwind\", \"minmod\" or \"vanleer\", not %r" % (who, scheme))
+    return scheme
+
+
+def upload_stencil(eng, stencil, n):
+    """The (rows, 4) stencil of a limited flux launch as device int32 (16-byte aligned: a fresh allocation), after the
+    range check the kernels leave to the caller: -1 <= entry < n."""
+    st = np.ascontiguousarray(stencil, dtype=np.int32)
+    if st.ndim != 2 or st.shape[1] != 4:
+        raise ValueError("stencil: an int array (rows, 4), not %s" % (st.shape,))
+    if st.size and (st.min() < -1 or st.max() >= n):
+        raise ValueError("stencil: entries outside -1 .. %d" % (n - 1))
+    buf = eng.torch.from_numpy(st if st.size else np.full((1, 4), -1, dtype=np.int32)).to(eng.device)
+    assert buf.data_ptr() % 16 == 0
+    return buf
+
+
+def pair(v, default=(None, None)):
+    """`precision` / `maxsteps` of `Advance` as (mstar, projection): one value for both, a pair, or None = `default`."""
+    return default if v is None else tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _ptr(buf):
+    return None if buf is None else buf.data_ptr()
+
+
+class ConvectiveFlux:
+    """The convective flux of one transported quantity under one `scheme`: "upwind" launches the donor-cell kernel over
+    two-slot copies of the operators, "minmod" / "vanleer" the limited kernel over the uploaded stencil (avg and diff are
+    then not uploaded).  The device operands are looked up in, and left in, `shared` ("adv", "avg", "diff", "stencil"),
+    so that the objects of one system keep them once; `launch` is the package's one caller of the two `KERNELS`."""
+
+    avg = diff = stencil = None
+
+    @classmethod
+    def available(cls, eng, scheme):
+        """Whether the engine's library has the kernel of `scheme`."""
+        return hasattr(getattr(eng, "lib", None), cls.KERNELS[scheme != "upwind"])
+
+    @staticmethod
+    def declined(ops, keys=("adv", "avg", "diff")):
+        """Why the row-per-lane kernels refuse `ops`: the first of `keys` with a row of more than two entries, or None."""
+        return next((key + ": " + why for key in keys for ok, why in [two_entry_rows(ops[key])] if not ok), None)
+
+
+class MomentumFlux(ConvectiveFlux):
+    """F1, from `system.convection_operators()` (`ops`: those, when the caller holds them) / `convection_stencil()`."""
+
+    KERNELS = ("nss_step_flux_f64", "nss_step_flux_limited_f64")
+
+    def __init__(self, eng, system, scheme, shared, ops=None):
+        self.eng, self.scheme = eng, scheme
+        for key in ("adv", "avg", "diff") if scheme == "upwind" else ("adv",):
+            if key not in shared:
+                ops = system.convection_operators() if ops is None else ops
+                shared[key] = SparseMatrix.from_scipy(ops[key], engine=eng)
+        self.adv = shared["adv"]
+        self.nflux = self.adv.height
+        if scheme == "upwind":
+            self.avg, self.diff = shared["avg"], shared["diff"]
+            return
+        if "stencil" not in shared:
+            shared["stencil"] = upload_stencil(eng, system.convection_stencil(), self.adv.width)
+        self.stencil = shared["stencil"]
+        if self.stencil.shape[0] != max(1, self.nflux):
+            raise ValueError("TimeStepper: the stencil holds %d rows, adv %d" % (self.stencil.shape[0], self.nflux))
+
+    def launch(self, u, flux):
+        """flux = F(u); device buffers of adv's width and height."""
+        eng, tail = self.eng, (u.data_ptr(), flux.data_ptr(), None, self.eng.stream)
+        if self.stencil is None:
+            eng._check(eng.lib.nss_step_flux_f64(self.adv.handle.ptr, self.avg.handle.ptr, self.diff.handle.ptr, *tail))
+        else:
+            eng._check(eng.lib.nss_step_flux_limited_f64(self.adv.handle.ptr, self.stencil.data_ptr(), self.nflux,
+                                                         CONVECTION_SCHEMES[self.scheme], *tail))
+
+
+class ScalarFlux(ConvectiveFlux):
+    """S1, from avg and diff of `ops` = `StokesSystem.scalar_operators(...)` / the host array `scalar_stencil()`."""
+
+    KERNELS = ("nss_scalar_flux_f64", "nss_scalar_flux_limited_f64")
+
+    def __init__(self, eng, ops, scheme, stencil, shared):
+        self.eng, self.scheme = eng, check_convection(scheme, "ScalarStepper")
+        self.n_u, self.n_p = ops["avg"].shape
+        if scheme != "upwind":
+            if not self.available(eng, scheme):
+                raise ValueError("ScalarStepper: the library has no limited flux kernel")
+            if "stencil" not in shared:
+                if stencil is None or np.shape(stencil) != (self.n_u, 4):
+                    raise ValueError("ScalarStepper: convection=%r wants the (n_u, 4) scalar stencil" % (scheme,))
+                shared["stencil"] = upload_stencil(eng, stencil, self.n_p)
+            self.stencil = shared["stencil"]
+            return
+        missing = [key for key in ("avg", "diff") if key not in shared]
+        if self.declined(ops, missing):
+            raise ValueError("ScalarStepper: " + self.declined(ops, missing))
+        shared.update((key, SparseMatrix.from_scipy(ops[key], engine=eng)) for key in missing)
+        self.avg, self.diff = shared["avg"], shared["diff"]
+
+    def launch(self, u, f, T, t_ref, G, w_b=None, f_eff=None):
+        """G = the flux of `T` carried by `u`; with the weights `w_b` also f_eff = f + w_b (avg T - t_ref).  Buffers."""
+        eng = self.eng
+        tail = (_ptr(w_b), u.data_ptr(), _ptr(f), T.data_ptr(), t_ref, G.data_ptr(), _ptr(f_eff), None, eng.stream)
+        if self.stencil is None:
+            eng._check(eng.lib.nss_scalar_flux_f64(self.avg.handle.ptr, self.diff.handle.ptr, *tail))
+        else:
+            eng._check(eng.lib.nss_scalar_flux_limited_f64(self.stencil.data_ptr(), self.n_u,
+                                                           CONVECTION_SCHEMES[self.scheme], *tail))
+
+
+class StepRecord:
+    """What `NavierStokes.Advance` returns: one entry per step of `mstar_iterations`, `proj_iterations` (pseudo time
+    stepping: the two projections of a step added), `div_norm` = |B u| and `kinetic_energy` = <u, M_u u> / 2 after the
+    step (both None with ``diagnostics=False``); `declined`: why the statements ran instead of the device-resident
+    step (None when it ran); `flux_declined`: why the convection term ran through `ConvectionOperator`.  With a scalar
+    (`NavierStokes.AddScalar`): `scalar_iterations` of the temperature solve and `wall_flux` = the heat entering through
+    its `flux_wall` after the step (None without a scalar / diagnostics).  `convection`: the momentum flux's scheme."""
+
+    def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
+                 scalar_iterations=None, wall_flux=None, convection="upwind"):
+        self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
+        self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
+        self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
+        self.declined, self.flux_declined = declined, flux_declined
+        self.scalar_iterations = None if scalar_iterations is None else np.asarray(scalar_iterations, dtype=np.int64)
+        self.wall_flux = wall_flux
+        self.convection = convection
+
+
+class TimeStepper(FusedLoop):
+    """Device-resident IMEX time stepping (``nss_step_*`` around two `CgLoop` solves): the statements of the reference's
+    DoTimeStep / Project (templates/NavierStokesSIMPLE_iterative.py:424-443) and of its pseudo time stepping (:406-417).
+
+    Per step: the flux kernel writes F behind u in the operand buffer [u | F]; one launch over the rows of [A | D] forms
+    temp = f - A u - D F; raw = mstar^-1 temp (CG from zero); rhs = B raw; phi = (B M_u^-1 B^T)^-1 rhs (CG from zero); one
+    launch over the rows of C = M_u^-1 B^T forms raw - C phi, u += timestep * that and the partials of <u, M_u u>; with
+    diagnostics one launch over the rows of B gives the partials of |B u|^2 and one workgroup writes the step's record.
+    Every buffer is allocated here, once; the only host synchronisations of a step are the polls of the two solves."""
+
+    PRECISION, MAXSTEPS = (1e-4, 1e-8), (500, 5000)        # those of the template's CGSolvers invmstar / invproj
+    momentum_flux = adv = avg = diff = stencil = None      # with `flux_declined`: no flux object, no flux operands
+    nflux = 0
+
+    @classmethod
+    def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
+                   convection="upwind"):
+        """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
+        `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
+        solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
+        the convection operators (`flux_declined`).  `shared`: a dict in which the stepper looks up, and leaves, the
+        device matrices that do not depend on `inner_pre` (mstar, Lp, C, adv, avg, diff, AD), so that the steppers of
+        one system -- and a caller that already holds `M_u + timestep A`, `B M_u^-1 B^T`, `M_u^-1 B^T` and passes them
+        under "mstar", "Lp", "C" -- keep them once.  `convection`: the scheme of F1 (`MomentumFlux`), "upwind" (donor
+        cell, first order) or the second-order limited "minmod" / "vanleer".  Returns None, the reason in `last_declined`."""
+        return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection))
+
+    @classmethod
+    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection):
+        if inner_pre not in ("jacobi", "amg"):
+            raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
+        check_convection(convection, "TimeStepper")
+        if not fused.ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not isinstance(A, SparseMatrix) or not isinstance(B, SparseMatrix) or not isinstance(f, Vector):
+            return "A, B are not SparseMatrix operands or f is not a plain Vector"
+        if not _hip(A.engine) or not MomentumFlux.available(A.engine, "upwind"):
+            return "not the HIP engine"
+        if not MomentumFlux.available(A.engine, convection):
+            return "the library has no limited flux kernel"
+        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, {} if shared is None else shared, convection)
+
+    def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind"):
+        import scipy.sparse as sp
+        eng = self.eng = A.engine
+        self.lib, self.A, self.B, self.f, self.timestep = eng.lib, A, B, f, float(timestep)
+        self.n_u, self.n_p = A.height, B.height
+        m_u = np.asarray(m_u, dtype=np.float64)
+        # ---- the convection term: the flux object of the scheme and the rows of [A | D] ----
+        self.convection = convection
+        ops = None if {"flux_declined", "AD"} <= shared.keys() else system.convection_operators()
+        if "flux_declined" not in shared:
+            shared["flux_declined"] = MomentumFlux.declined(ops)
+        self.flux_declined = shared["flux_declined"]
+        if self.flux_declined is None:
+            mf = self.momentum_flux = MomentumFlux(eng, system, convection, shared, ops)
+            if "AD" not in shared:
+                AD = sp.hstack([A.to_scipy(), ops["div"]], format="csr")
+                AD.sort_indices()
+                shared["AD"] = SparseMatrix.from_scipy(AD, engine=eng)
+            self.AD, self.conv = shared["AD"], None
+            self.adv, self.avg, self.diff, self.stencil, self.nflux = mf.adv, mf.avg, mf.diff, mf.stencil, mf.nflux
+        else:
+            self.conv = conv_operator()
+        self.uf = eng.zeros(self.n_u + self.nflux)          # the operand [u | F]
+        self.u, self.F = eng.view(self.uf, 0, self.n_u), eng.view(self.uf, self.n_u, self.n_u + self.nflux)
+        self.temp, self.raw, self.temp2 = eng.zeros(self.n_u), eng.zeros(self.n_u), eng.zeros(self.n_u)
+        self.rhs_p, self.phi = eng.zeros(self.n_p), eng.zeros(self.n_p)
+        # ---- the inner solves ----
+        if "mstar" not in shared:
+            shared["mstar"] = SparseMatrix.from_scipy((sp.diags(m_u) + self.timestep * A.to_scipy()).tocsr(), engine=eng)
+        if "C" not in shared:
+            shared["C"] = SparseMatrix.from_scipy((sp.diags(1.0 / m_u) @ B.to_scipy().T).tocsr(), engine=eng)
+        if "Lp" not in shared:
+            lap_p = (B.to_scipy() @ shared["C"].to_scipy()).tocsr()
+            lap_p.sort_indices()
+            shared["Lp"] = SparseMatrix.from_scipy(lap_p, engine=eng)
+        self.mstar, self.Lp, self.C = shared["mstar"], shared["Lp"], shared["C"]
+        if "singular" not in shared:
+            ok, why = two_entry_rows(self.C.to_scipy())
+            if not ok:
+                raise ValueError("TimeStepper: M_u^-1 B^T: " + why)
+            shared["singular"] = constants_in_kernel(self.Lp.to_scipy())
+        self.singular = shared["singular"]
+        if inner_pre == "amg":
+            self.pre_m = SmoothedAggregationAMG(self.mstar)
+            self.pre_p = SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
+        else:
+            self.pre_m, self.pre_p = JacobiPreconditioner(self.mstar), JacobiPreconditioner(self.Lp)
+        self.cg_m = CgLoop(eng, self.mstar, pre_for("cg", self.pre_m))
+        self.cg_p = CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
+        # ---- the record ----
+        uniform = bool(m_u.size) and bool((m_u == m_u[0]).all())
+        self.mass = None if uniform else eng.from_host(m_u)
+        self.energy_scale = 0.5 * (float(m_u[0]) if uniform else 1.0)
+        self.partials_e = self.partials_d = None
+        self._fit_partials()
+
+    def _fit_partials(self):
+        """The partials of the record for the CURRENT launch plan of C (row blocks) and the size of B."""
+        ne, nd = C.c_int64(), C.c_int64()
+        self.eng._check(self.lib.nss_step_workspace(self.C.handle.ptr, self.B.handle.ptr, C.byref(ne), C.byref(nd)))
+        if self.partials_e is None or self.partials_e.numel() < ne.value or self.partials_d.numel() < nd.value:
+            self.partials_e, self.partials_d = self.eng.zeros(max(1, ne.value)), self.eng.zeros(max(1, nd.value))
+        self.n_energy, self.n_div = ne.value, nd.value
+
+    # ---- the launches of a step -----------------------------------------------------------------------------------
+    def right_hand_side(self, f=None):
+        """temp = conv(u) + f - A u from the u part of the operand buffer; `f`: the force of this step (a buffer: the
+        f_eff of a buoyant scalar), None = the stepper's f."""
+        eng, lib = self.eng, self.lib
+        f = self.f.buf if f is None else f
+        if self.flux_declined is None:
+            self.momentum_flux.launch(self.u, self.F)
+            eng._check(lib.nss_step_rhs_f64(self.AD.handle.ptr, self.uf.data_ptr(), f.data_ptr(),
+                                            self.temp.data_ptr(), None, eng.stream))
+            return
+        u, temp = Vector(buf=self.u, engine=eng), Vector(buf=self.temp, engine=eng)
+        temp.data = self.conv * u
+        temp.data += Vector(buf=f, engine=eng)
+        temp.data += -self.A * u
+
+    def project(self, vel, out=None, update=None, energy=False):
+        """out = vel - C phi with phi = (B M_u^-1 B^T)^-1 B vel (`Project`; `out` None: in place); `update`:
+        u += timestep * out in the same launch; `energy`: also the partials of <e, M_u e>, e = the updated u, or out.
+        Returns the CG iterations."""
+        eng, lib = self.eng, self.lib
+        eng.csr_spmv(self.B.handle, 1.0, vel, 0.0, self.rhs_p)
+        its = self.cg_p.solve_resident(self.rhs_p, self.phi, self.precision[1], self.maxsteps[1])
+        eng._check(lib.nss_step_project_f64(self.C.handle.ptr, self.phi.data_ptr(), vel.data_ptr(),
+                                            (vel if out is None else out).data_ptr(), _ptr(update), self.timestep,
+                                            _ptr(self.mass), self.partials_e.data_ptr() if energy else None,
+                                            self.partials_e.numel(), None, eng.stream))
+        return its
+
+    def write_record(self, record, slot):
+        eng, lib = self.eng, self.lib
+        eng._check(lib.nss_step_divergence_f64(self.B.handle.ptr, self.u.data_ptr(), self.partials_d.data_ptr(),
+                                               self.partials_d.numel(), None, eng.stream))
+        eng._check(lib.nss_step_record_f64(self.partials_e.data_ptr(), self.n_energy, self.partials_d.data_ptr(),
+                                           self.n_div, self.energy_scale, record.data_ptr(), slot, None, eng.stream))
+
+    def advance(self, gfu, gfup, nsteps, precision=None, maxsteps=None, diagnostics=True, pseudo=False, scalar=None,
+                temperature=None):
+        """`nsteps` steps on the velocity `gfu` (pressure-like potential of the last projection -> `gfup`).
+        `precision` / `maxsteps`: one value for both inner solves, a pair (mstar, projection), or None = the template's.
+        `scalar`: a `ScalarStepper` -- every step then begins with its flux launch on (u^n, T^n), the velocity step
+        takes its f_eff for f (a buoyant scalar), and its temperature step follows; `temperature`: the `Vector` of T."""
+        self.precision = tuple(float(p) for p in pair(precision, self.PRECISION))
+        self.maxsteps = tuple(int(m) for m in pair(maxsteps, self.MAXSTEPS))
+        eng = self.eng
+        self._fit_partials()
+        nsteps = int(nsteps)
+        if scalar is not None and pseudo:
+            raise ValueError("advance: the pseudo time stepping carries no scalar")
+        slots = max(1, nsteps)                 # the record: [2 slots] of the velocity | [slots] of the scalar
+        record = eng.zeros((2 if scalar is None else 3) * slots) if diagnostics else None
+        record_s = eng.view(record, 2 * slots, 3 * slots) if diagnostics and scalar is not None and scalar.records else None
+        eng.copy(gfu.buf, self.u)
+        if scalar is not None:
+            eng.copy(temperature.buf, scalar.T)
+        its_m, its_p, its_s = [], [], None if scalar is None else []
+        if pseudo:
+            self.project(self.u)                                          # :407  Project(gfu)
+        for step in range(nsteps):
+            if pseudo:
+                eng.csr_spmv(self.A.handle, -1.0, self.u, 0.0, self.temp)         # :411  temp = -A u
+            else:
+                self.right_hand_side(None if scalar is None else scalar.flux(self.u))     # (S1,) F1, F2  :429-431
+            its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))   # :433
+            count = self.project(self.raw, out=self.temp2, update=self.u, energy=diagnostics and not pseudo)   # :434,438
+            if pseudo:
+                count += self.project(self.u, energy=diagnostics)                # :415  Project(gfu)
+            its_p.append(count)
+            if diagnostics:
+                self.write_record(record, step)
+            if scalar is not None:
+                its_s.append(scalar.step(record_s, step))                         # S2, the solve, S3, S4
+        eng.copy(self.u, gfu.buf)
+        if nsteps or pseudo:
+            eng.copy(self.phi, gfup.buf)
+        if scalar is not None:
+            eng.copy(scalar.T, temperature.buf)
+        div = energy = wall = None
+        if diagnostics:
+            host = eng.to_host(record)                                    # the one read-back
+            vel = host[:2 * slots].reshape(-1, 2)[:nsteps]
+            div, energy = vel[:, 1].copy(), vel[:, 0].copy()
+            if record_s is not None:
+                wall = host[2 * slots:][:nsteps].copy()
+        return StepRecord(its_m, its_p, div, energy, flux_declined=self.flux_declined, convection=self.convection,
+                          scalar_iterations=its_s, wall_flux=wall)
+
+
+class ScalarStepper:
+    """The scalar part of a device-resident step (``nss_scalar_*`` around one `CgLoop` solve), driven by
+    `TimeStepper.advance`: M_p dT/dt = q - K T - B G with the donor-cell flux G of T through the faces and, for a
+    buoyant scalar, the force f_eff = f + w_b (avg T - t_ref) of the velocity step.
+
+    Per step: the flux launch on (u^n, T^n) writes G behind T in the operand buffer [T | G] (and f_eff); after the
+    velocity step one launch over the rows of [K | B] forms temp_T = q - K T - B G; delta = (M_p + timestep K)^-1 temp_T
+    (CG from zero); one launch does T += timestep delta with the partials of <w, T>, one workgroup writes the heat
+    entering through the flux wall, c0 - <w, T>.  Every buffer is allocated here, once (the cost in HBM: DESIGN.md 12)."""
+
+    PRECISION, MAXSTEPS = 1e-4, 500          # those of invmstar: the same kind of operator
+
+    def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
+                 maxsteps=None, shared=None, convection="upwind", stencil=None):
+        """`ops`: `StokesSystem.scalar_operators(...)`; `B`: the divergence (`SparseMatrix`); `f`: the force `Vector`
+        the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
+        (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
+        `inner_pre`.  `convection`, `stencil`: the scheme of S1 and, for a limited one, `scalar_stencil()` (`ScalarFlux`)."""
+        import scipy.sparse as sp
+        shared = {} if shared is None else shared
+        self.eng, self.lib, self.f, self.timestep, self.t_ref = eng, eng.lib, f, float(timestep), float(t_ref)
+        self.n_u, self.n_p = ops["avg"].shape
+        self.precision = self.PRECISION if precision is None else float(precision)
+        self.maxsteps = self.MAXSTEPS if maxsteps is None else int(maxsteps)
+        sf = self.scalar_flux = ScalarFlux(eng, ops, convection, stencil, shared)
+        self.convection, self.stencil, self.avg, self.diff = sf.scheme, sf.stencil, sf.avg, sf.diff
+        if "KB" not in shared:
+            KB = sp.hstack([ops["K"], B.to_scipy()], format="csr")
+            KB.sort_indices()
+            shared["KB"] = SparseMatrix.from_scipy(KB, engine=eng)
+            shared["mstar"] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + self.timestep * ops["K"]).tocsr(), engine=eng)
+            shared["q"] = eng.from_host(np.asarray(ops["q"], dtype=np.float64))
+            shared["w_b"] = None if w_b is None else eng.from_host(np.asarray(w_b, dtype=np.float64))
+            shared["w"] = None if flux is None else eng.from_host(np.asarray(flux[1], dtype=np.float64))
+        self.KB, self.mstar, self.q, self.w_b, self.w = (shared[key] for key in ("KB", "mstar", "q", "w_b", "w"))
+        self.c0, self.records = (0.0 if flux is None else float(flux[0])), flux is not None
+        self.tg = eng.zeros(self.n_p + self.n_u)             # the operand [T | G]
+        self.T, self.G = eng.view(self.tg, 0, self.n_p), eng.view(self.tg, self.n_p, self.n_p + self.n_u)
+        self.f_eff = None if w_b is None else eng.zeros(self.n_u)
+        self.temp, self.delta = eng.zeros(self.n_p), eng.zeros(self.n_p)
+        self.pre = SmoothedAggregationAMG(self.mstar) if inner_pre == "amg" else JacobiPreconditioner(self.mstar)
+        self.cg = CgLoop(eng, self.mstar, pre_for("cg", self.pre))
+        count = C.c_int64()
+        eng._check(self.lib.nss_scalar_workspace(self.n_p, C.byref(count)))
+        self.n_partials = count.value
+        self.partials = eng.zeros(max(1, count.value)) if self.records else None
+
+    def flux(self, u):
+        """S1 on (u, T): G, and for a buoyant scalar f_eff.  Returns the force buffer of the velocity step (None: f)."""
+        self.scalar_flux.launch(u, self.f.buf, self.T, self.t_ref, self.G, self.w_b, self.f_eff)
+        return self.f_eff
+
+    def step(self, record, slot):
+        """S2, the solve, S3 and (with `record`) S4.  Returns the CG iterations."""
+        eng, lib = self.eng, self.lib
+        eng._check(lib.nss_step_rhs_f64(self.KB.handle.ptr, self.tg.data_ptr(), self.q.data_ptr(), self.temp.data_ptr(),
+                                        None, eng.stream))
+        its = self.cg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
+        write = record is not None
+        eng._check(lib.nss_scalar_update_f64(self.n_p, self.timestep, self.delta.data_ptr(), self.T.data_ptr(),
+                                             _ptr(self.w if write else None), _ptr(self.partials if write else None),
+                                             self.partials.numel() if write else 0, None, eng.stream))
+        if write:
+            eng._check(lib.nss_scalar_record_f64(self.partials.data_ptr(), self.n_partials, self.c0, record.data_ptr(),
+                                                 slot, None, eng.stream))
+        return its
+
+
+class HeatRecord:
+    """What `heat.evolve` returns beside the temperature: `steps`; `cg_iterations[step, i]` = iterations of the i-th
+    inner solve of the step; `orthogonality[step]` = the largest entry of |V^T V - I| after the orthonormalisation (None
+    without ``diagnostics``); `declined`: why the statements ran through the protocol instead of the device-resident
+    step (None when it ran)."""
+
+    def __init__(self, cg_iterations, orthogonality, declined=None):
+        self.steps = len(cg_iterations)
+        self.cg_iterations = np.array([list(row) for row in cg_iterations], dtype=np.int64).reshape(self.steps, -1) \
+            if self.steps and len(cg_iterations[0]) else np.zeros((self.steps, 0), dtype=np.int64)
+        self.orthogonality = None if orthogonality is None else np.asarray(orthogonality, dtype=np.float64)
+        self.declined = declined
+
+
+class HeatIntegrator(FusedLoop):
+    """Device-resident step of the heat exponential integrator (``nss_mgs_f64`` / ``nss_galerkin_f64`` /
+    ``nss_basis_combine_f64`` around `CgLoop` solves): the statements of the reference's heat.py:87-142.
+
+    The basis lives in ONE buffer of d planes (plane k = vector k, stride `ld`); plane 0 holds the temperature between
+    steps.  Per step: d - 1 sub-steps (SpMV with K, CG from zero with ``M + time_step K``, one AXPY into the next plane),
+    the Gram-Schmidt chain, two Galerkin launches, ONE read-back of the norms and the two d x d matrices, the small
+    implicit Runge-Kutta step on the host, and one launch that combines the planes into plane 0 with the d coefficients
+    as kernel arguments.  Every buffer is allocated here, once; a step waits for the host in the polls of its solves and
+    in that read-back."""
+
+    TRIES = 3                 # orthonormalize(basis, tries=3)
+
+    @classmethod
+    def try_create(cls, K, M, heat, pre, dimension, diagnostics=False):
+        """`K`, `M`, `heat`: `SparseMatrix` (diffusion, mass, ``M + time_step K``); `pre`: the preconditioner of the inner
+        solves (a protocol operator).  Returns None with the reason in ``HeatIntegrator.last_declined``."""
+        return cls._decided(cls._try_create(K, M, heat, pre, dimension, diagnostics))
+
+    @classmethod
+    def _try_create(cls, K, M, heat, pre, dimension, diagnostics):
+        if not fused.ENABLED:
+            return "fused loops disabled (hipla.fused.ENABLED)"
+        if not all(isinstance(m, SparseMatrix) and m.height == m.width == K.height for m in (K, M, heat)):
+            return "K, M, heat are not square SparseMatrix operands of one size"
+        if not _hip(K.engine) or not hasattr(K.engine.lib, "nss_mgs_f64"):
+            return "not the HIP engine"
+        if not 1 <= dimension <= 8:
+            return "the subspace dimension is not in 1 .. 8"
+        pa = pre_for("cg", pre)
+        if pa is None or isinstance(pre, (ScaledMatrix, SumMatrix)):
+            return "the preconditioner is not native"
+        return cls(K, M, heat, pa, dimension, diagnostics)
+
+    def __init__(self, K, M, heat, pa, dimension, diagnostics):
+        eng = self.eng = K.engine
+        self.lib, self.K, self.M, self.heat = eng.lib, K, M, heat
+        n, d = K.height, int(dimension)
+        self.n, self.d = n, d
+        self.ld = -(-n // 32) * 32                           # planes start on 256-byte boundaries
+        self.basis = eng.zeros(d * self.ld)
+        self.planes = [eng.view(self.basis, k * self.ld, k * self.ld + n) for k in range(d)]
+        self.res, self.sol = eng.zeros(n), eng.zeros(n)
+        self.cg = CgLoop(eng, heat, pa)
+        self.eye = None
+        if diagnostics:
+            import scipy.sparse as sp
+            self.eye = SparseMatrix.from_scipy(sp.identity(n, format="csr"), engine=eng)
+        # what a step reads back: [norms (TRIES * d) | V^T K V | V^T M V | V^T V (diagnostics)]
+        self.out = eng.zeros(self.TRIES * d + (3 if diagnostics else 2) * d * d)
+        count = C.c_int64()
+        eng._check(self.lib.nss_heat_workspace(n, d, C.byref(count)))
+        self.work = eng.zeros(count.value)
+
+    def load(self, temperature):
+        self.eng.upload(np.asarray(temperature, dtype=np.float64), self.planes[0])
+
+    def temperature(self):
+        return self.eng.to_host(self.planes[0]).copy()
+
+    def _galerkin(self, mat, slot):
+        eng, d = self.eng, self.d
+        g = eng.view(self.out, self.TRIES * d + slot * d * d, self.TRIES * d + (slot + 1) * d * d)
+        eng._check(self.lib.nss_galerkin_f64(mat.handle.ptr, d, self.ld, self.basis.data_ptr(), g.data_ptr(),
+                                             self.work.data_ptr(), self.work.numel(), eng.stream))
+
+    def build_subspace(self, dt, precision, maxsteps):
+        """Planes 1 .. d - 1 from plane 0 (heat.py:95-98), the orthonormalisation (:100) and the Galerkin matrices
+        (:109-118).  Returns (CG iterations, norms[TRIES, d], V^T K V, V^T M V, V^T V or None) after the one read-back."""
+        eng, lib, d, planes = self.eng, self.lib, self.d, self.planes
+        its = []
+        for i in range(1, d):
+            eng.csr_spmv(self.K.handle, 1.0, planes[i - 1], 0.0, self.res)
+            its.append(self.cg.solve_resident(self.res, self.sol, precision, maxsteps))
+            eng.lincomb(planes[i], [(1.0, planes[i - 1]), (-dt, self.sol)])
+        eng._check(lib.nss_mgs_f64(self.n, d, self.ld, self.basis.data_ptr(), self.TRIES, self.out.data_ptr(),
+                                   self.work.data_ptr(), self.work.numel(), eng.stream))
+        self._galerkin(self.K, 0)
+        self._galerkin(self.M, 1)
+        if self.eye is not None:
+            self._galerkin(self.eye, 2)
+        host = eng.to_host(self.out)                                       # the one read-back
+        norms = host[:self.TRIES * d].reshape(self.TRIES, d)
+        mats = host[self.TRIES * d:].reshape(-1, d, d)
+        return its, norms, mats[0], mats[1], mats[2] if self.eye is not None else None
+
+    def combine(self, coefficients):
+        """plane 0 = sum_i coefficients[i] * plane i (heat.py:140-142)."""
+        coeff = (C.c_double * self.d)(*[float(c) for c in coefficients])
+        self.eng._check(self.lib.nss_basis_combine_f64(self.n, self.d, self.ld, self.basis.data_ptr(), coeff,
+                                                       self.planes[0].data_ptr(), self.eng.stream))

@@ -36,7 +36,8 @@ import numpy as np
 import scipy.sparse as sp
 
 import hipla
-from hipla import BlockVector, CGSolver
+from hipla import BlockVector, CGSolver, fused
+from hipla.stepping import MomentumFlux, ScalarFlux, ScalarStepper, StepRecord, TimeStepper, check_convection, pair
 from discretizations import AssembledForm, CondensedForm, SyntheticMesh, assemble, bdm_hybrid
 from solvers.bramblepasciak_new import BramblePasciakCG
 
@@ -51,28 +52,24 @@ class ConvectionOperator(hipla.BaseMatrix):
     SpMVs), then ``conv = -D F`` (one SpMV); all on the device.
 
     `scheme` "minmod" / "vanleer": the second-order limited fluxes ``F = adv * (U + s / 2)`` of
-    `staggered_grid.limited_flux` over `system.convection_stencil()` -- one launch of ``nss_step_flux_limited_f64``,
-    then ``-D F``; an engine without that entry point (the checker engine), or an `adv` the kernel refuses (a row of
-    more than two entries, which no grid of this package produces), evaluates `system.limited_convection` on the host
-    and uploads the result."""
+    `staggered_grid.limited_flux` over `system.convection_stencil()` -- one launch of a `hipla.stepping.MomentumFlux`,
+    then ``-D F``; an engine without that kernel (the checker engine), or an `adv` the kernel refuses (a row of more than
+    two entries, which no grid of this package produces), evaluates `system.limited_convection` on the host, uploaded."""
 
     def __init__(self, system, scheme="upwind"):
         super().__init__()
-        from hipla.fused import check_convection
         self.scheme = check_convection(scheme, "ConvectionOperator")
         ops = system.convection_operators()
         self.n = system.n_u
-        self.stencil = None
+        self.stencil = self.flux = None
         if scheme != "upwind":
             self.system = system
-            self.adv, self.div = (hipla.SparseMatrix.from_scipy(ops[k]) for k in ("adv", "div"))
-            self._flux = self.adv.CreateColVector()
-            eng = self._flux.engine
-            from hipla.fused import two_entry_rows
-            self._native = hasattr(getattr(eng, "lib", None), "nss_step_flux_limited_f64") and two_entry_rows(ops["adv"])[0]
-            if self._native:
-                from hipla.fused import upload_stencil
-                self.stencil = upload_stencil(eng, system.convection_stencil(), self.n)
+            self.div = hipla.SparseMatrix.from_scipy(ops["div"])
+            eng = self.div.engine
+            if MomentumFlux.available(eng, scheme) and MomentumFlux.declined(ops, ("adv",)) is None:
+                self.flux = MomentumFlux(eng, system, scheme, {}, ops)
+                self.stencil = self.flux.stencil
+                self._work = self.flux.adv.CreateColVector()
             return
         self.adv, self.avg, self.diff, self.div = (hipla.SparseMatrix.from_scipy(ops[k])
                                                    for k in ("adv", "avg", "diff", "div"))
@@ -86,15 +83,11 @@ class ConvectionOperator(hipla.BaseMatrix):
 
     def Mult(self, x, y):
         if self.scheme != "upwind":
-            if not self._native:
+            if self.flux is None:
                 y.data = hipla.Vector.from_numpy(self.system.limited_convection(x.numpy(), self.scheme))
                 return
-            from hipla.fused import CONVECTION_SCHEMES
-            flux, eng = self._flux, self._flux.engine
-            eng._check(eng.lib.nss_step_flux_limited_f64(self.adv.handle.ptr, self.stencil.data_ptr(), self.adv.height,
-                                                         CONVECTION_SCHEMES[self.scheme], x.buf.data_ptr(),
-                                                         flux.buf.data_ptr(), None, eng.stream))
-            y.data = -self.div * flux
+            self.flux.launch(x.buf, self._work.buf)
+            y.data = -self.div * self._work
             return
         adv, avg, diff, flux = self._work
         adv.data = self.adv * x
@@ -174,15 +167,14 @@ def coupling_blocks(blocks, interior):
 class ScalarField:
     """What `NavierStokes.AddScalar` keeps: the protocol operands of the scalar's statements in `DoTimeStep` (K, avg,
     diff, q, the CG inverse of M_p + timestep K, the buoyancy weights as a diagonal matrix) and what a device-resident
-    `hipla.fused.ScalarStepper` is made from."""
+    `hipla.stepping.ScalarStepper` is made from."""
 
     def __init__(self, system, b_mat, timestep, kappa, dirichlet, buoyancy, t_ref, precision, maxsteps, flux_wall,
                  convection="upwind"):
-        from hipla.fused import ScalarStepper, check_convection
         self.convection = check_convection(convection, "AddScalar")
         self.ops = ops = system.scalar_operators(kappa, dirichlet)
         self.stencil = system.scalar_stencil() if convection != "upwind" else None    # host array; uploaded on first use
-        self.stencil_dev = None
+        self.device_flux = None           # the `ScalarFlux` of `DoTimeStep`'s limited G, over `shared`
         self.t_ref = float(t_ref)
         self.precision = ScalarStepper.PRECISION if precision is None else float(precision)
         self.maxsteps = ScalarStepper.MAXSTEPS if maxsteps is None else int(maxsteps)
@@ -214,7 +206,6 @@ class NavierStokes:
         cell, first order: numerical viscosity about |u| h / 2) or the second-order limited "minmod" / "vanleer"
         (`staggered_grid.limited_flux`; first order remains at the one flux point per grid line and direction next to
         each wall).  Explicit Euler with the limiters wants timestep * sum_faces |u_f| / h <= 1/2 per cell."""
-        from hipla.fused import check_convection
         self.convection = check_convection(convection, "NavierStokes")
         self.mesh, self.nu, self.timestep, self.order = mesh, nu, timestep, order
         self.inflow, self.outflow, self.wall, self.uin = inflow, outflow, wall, uin
@@ -365,21 +356,17 @@ class NavierStokes:
         return sc.f_eff
 
     def _limited_scalar_flux(self, sc):
-        """G by the scalar's limited scheme: one passive launch of ``nss_scalar_flux_limited_f64``, or -- an engine
-        without it -- `limited_flux` on the host, uploaded."""
+        """G by the scalar's limited scheme: one passive launch of a `ScalarFlux` over `sc.shared` (the device stencil of
+        the scalar steppers), or -- an engine without the kernel -- `limited_flux` on the host, uploaded."""
         eng = sc.G.engine
-        if not hasattr(getattr(eng, "lib", None), "nss_scalar_flux_limited_f64"):
+        if not ScalarFlux.available(eng, sc.convection):
             from staggered_grid import limited_flux
             sc.G.data = hipla.Vector.from_numpy(limited_flux(sc.stencil, self.gfu.numpy(), self.temperature.numpy(),
                                                              sc.convection))
             return
-        from hipla.fused import CONVECTION_SCHEMES, upload_stencil
-        if sc.stencil_dev is None:
-            sc.stencil_dev = upload_stencil(eng, sc.stencil, self.system.n_p)
-        eng._check(eng.lib.nss_scalar_flux_limited_f64(sc.stencil_dev.data_ptr(), self.system.n_u,
-                                                       CONVECTION_SCHEMES[sc.convection], None, self.gfu.buf.data_ptr(),
-                                                       None, self.temperature.buf.data_ptr(), 0.0, sc.G.buf.data_ptr(),
-                                                       None, None, eng.stream))
+        if sc.device_flux is None:
+            sc.device_flux = ScalarFlux(eng, sc.ops, sc.convection, sc.stencil, sc.shared)
+        sc.device_flux.launch(self.gfu.buf, None, self.temperature.buf, 0.0, sc.G.buf)
 
     def _scalar_step(self):
         """The last statements of a step with a scalar: temp_T = q - K T - B G;  delta = (M_p + timestep K)^-1 temp_T;
@@ -418,9 +405,9 @@ class NavierStokes:
 
     def Advance(self, nsteps, inner_pre="jacobi", precision=None, diagnostics=True, pseudo=False, maxsteps=None):
         """`nsteps` IMEX steps (`pseudo=True`: the pseudo time stepping of ``SolveInitial(timesteps=nsteps)``) through
-        the device-resident stepper (`hipla.fused.TimeStepper`): the statements of `DoTimeStep` / `Project` in two
+        the device-resident stepper (`hipla.stepping.TimeStepper`): the statements of `DoTimeStep` / `Project` in two
         launches for the right-hand side and one for the projection tail, every buffer allocated once, a per-step
-        record on the device read back once.  Returns an `hipla.fused.StepRecord` (mstar_iterations,
+        record on the device read back once.  Returns an `hipla.stepping.StepRecord` (mstar_iterations,
         proj_iterations, div_norm, kinetic_energy; with a scalar -- `AddScalar` -- also scalar_iterations and
         wall_flux, and `pseudo=True` raises ``ValueError``).
 
@@ -434,8 +421,6 @@ class NavierStokes:
         and the convection matrices with each other; what a stepper adds in HBM is its work vectors, the rows of
         `[A | D]` -- a second copy of A, 12 bytes per non-zero -- and, for "amg", the two hierarchies.  Like
         `DoTimeStep`, they keep the `timestep` of their first use: these operators are built once per object."""
-        from hipla import fused
-        from hipla.fused import StepRecord, TimeStepper
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
         if pseudo and self._scalar is not None:
@@ -457,7 +442,6 @@ class NavierStokes:
         if stepper is not None and self._scalar is not None:
             sc = self._scalar
             if inner_pre not in sc.steppers:
-                from hipla.fused import ScalarStepper
                 sc.steppers[inner_pre] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
                                                        inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
                                                        shared=sc.shared, convection=sc.convection, stencil=sc.stencil)
@@ -475,9 +459,6 @@ class NavierStokes:
         ops = self._time_stepping_operators()
         solvers = (ops["invmstar"], ops["invproj"])
         saved = [(sv.precision, sv.maxsteps) for sv in solvers]
-
-        def pair(v):
-            return (None, None) if v is None else tuple(v) if isinstance(v, (tuple, list)) else (v, v)
         for sv, p, m in zip(solvers, pair(precision), pair(maxsteps)):
             sv.precision = sv.precision if p is None else float(p)
             sv.maxsteps = sv.maxsteps if m is None else int(m)

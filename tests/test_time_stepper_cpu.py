@@ -154,3 +154,61 @@ def test_advance_declines_on_the_checker_engine(numpy_engine):
     assert np.array_equal(ns.gfu.numpy(), twin.gfu.numpy())
     with pytest.raises(ValueError):
         ns.Advance(1, inner_pre="ilu")
+
+
+# ---- Advance(0) on the decline path: the contracts of tests/test_time_stepper_gpu.py without a device ----------------
+def declined_case(scalar=None):
+    """`scalar`: None, "wall" (a buoyant scalar whose Dirichlet wall is recorded) or "no wall" (buoyant, insulated)."""
+    import hipla
+    from templates.NavierStokesSIMPLE_iterative import NavierStokes, SyntheticMesh
+    ns = NavierStokes(SyntheticMesh(0.2, dim=2), nu=0.01, inflow="inlet", outflow="outlet", wall="wall|cyl", uin=None,
+                      timestep=0.05, order=0)
+    s = ns.system
+    ns.AddForce(0.1 * np.random.default_rng(8).standard_normal(s.n_u))
+    ns.gfu.data = hipla.Vector.from_numpy(0.1 * np.random.default_rng(2).standard_normal(s.n_u))
+    ns.gfup.data = hipla.Vector.from_numpy(np.random.default_rng(11).standard_normal(s.n_p))
+    if scalar is not None:
+        ns.AddScalar(0.8, dirichlet={"x-": 1.0, "x+": 0.0} if scalar == "wall" else None, buoyancy=(0.0, 40.0), t_ref=0.5,
+                     initial=np.random.default_rng(6).random(s.n_p))
+    return ns
+
+
+@pytest.mark.parametrize("scalar,diagnostics", [(None, True), (None, False), ("wall", True), ("wall", False),
+                                                ("no wall", True)])
+def test_advance_zero_steps_by_statements(numpy_engine, scalar, diagnostics):
+    """Advance(0) through `_advance_by_statements`: gfu, gfup and the temperature bit-unchanged; the record's arrays
+    empty with the dtypes of Advance(1); None for the diagnostics without `diagnostics`, for the scalar's arrays without
+    a scalar and for wall_flux without a flux wall."""
+    ns = declined_case(scalar)
+    u0, p0 = ns.gfu.numpy().copy(), ns.gfup.numpy().copy()
+    T0 = None if scalar is None else ns.temperature.numpy().copy()
+    rec = ns.Advance(0, diagnostics=diagnostics)
+    assert rec.declined == "not the HIP engine"
+    assert np.array_equal(ns.gfu.numpy(), u0) and np.array_equal(ns.gfup.numpy(), p0)
+    assert scalar is None or np.array_equal(ns.temperature.numpy(), T0)
+    one = ns.Advance(1, diagnostics=diagnostics)
+    for name in ("mstar_iterations", "proj_iterations", "div_norm", "kinetic_energy", "scalar_iterations", "wall_flux"):
+        got, ref = getattr(rec, name), getattr(one, name)
+        if ref is None:
+            assert got is None, name
+        else:
+            assert isinstance(got, np.ndarray) and got.shape == (0,) and got.dtype == ref.dtype and ref.shape == (1,), name
+    assert (one.div_norm is None) == (one.kinetic_energy is None) == (not diagnostics)
+    assert (one.scalar_iterations is None) == (scalar is None)
+    assert (one.wall_flux is None) == (scalar != "wall" or not diagnostics)
+
+
+def test_advance_zero_pseudo_steps_project_by_statements(numpy_engine):
+    """Advance(0, pseudo=True) on the decline path is the leading Project(gfu): gfu agrees with `Project` on a twin to
+    1e-8 (the bound of the device test), gfup is written, the record is empty."""
+    ns, twin = declined_case(), declined_case()
+    v0, p0 = ns.gfu.numpy().copy(), ns.gfup.numpy().copy()
+    rec = ns.Advance(0, pseudo=True)
+    twin.Project(twin.gfu)
+    assert rec.declined == "not the HIP engine"
+    assert np.linalg.norm(ns.gfu.numpy() - twin.gfu.numpy()) < 1e-8 * np.linalg.norm(twin.gfu.numpy())
+    assert np.linalg.norm(ns.gfu.numpy() - v0) > 1e-2 * np.linalg.norm(v0)         # (the projection moved the field)
+    assert not np.array_equal(ns.gfup.numpy(), p0) and np.isfinite(ns.gfup.numpy()).all()
+    assert len(rec.mstar_iterations) == len(rec.proj_iterations) == len(rec.div_norm) == len(rec.kinetic_energy) == 0
+    with pytest.raises(ValueError):
+        declined_case("wall").Advance(0, pseudo=True)

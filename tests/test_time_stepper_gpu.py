@@ -337,3 +337,95 @@ def test_decline_path(hip_engine):
     assert len(rec.mstar_iterations) == len(rec.proj_iterations) == len(rec.div_norm) == len(rec.kinetic_energy) == 2
     rec = ns.Advance(1)                                     # switched on again: the device-resident step
     assert rec.declined is None and ns.advance_declined is None
+
+
+# ---- Advance(0): no step, and everything around the loop ------------------------------------------------------------
+RECORD_ARRAYS = ("mstar_iterations", "proj_iterations", "div_norm", "kinetic_energy", "scalar_iterations", "wall_flux")
+
+
+def small(scalar=None):
+    """The 2-D grid of tests/test_limited_convection_gpu.py::fresh_scalar("2d") (n = 8, a plain system), damped the same
+    way.  `scalar`: None, "wall" (a buoyant scalar whose Dirichlet wall is recorded) or "no wall" (buoyant, insulated)."""
+    import hipla
+    from templates.NavierStokesSIMPLE_iterative import NavierStokes, SyntheticMesh
+    ns = NavierStokes(SyntheticMesh(1.0 / 8, dim=2), nu=0.01, inflow="inlet", outflow="outlet", wall="wall|cyl", uin=None,
+                      timestep=0.05, order=0)
+    s = ns.system
+    assert s.block_size == 1 and s.n == 8
+    ns.f.vec.data = hipla.Vector.from_numpy(1e-4 * np.random.default_rng(8).standard_normal(s.n_u))
+    set_velocity(ns, 1e-2 * start_velocity(s))
+    if scalar is not None:
+        ns.AddScalar(0.8, dirichlet={"x-": 1.0, "x+": 0.0} if scalar == "wall" else None, buoyancy=(0.0, 0.5), t_ref=0.5,
+                     initial=np.random.default_rng(6).random(s.n_p))
+    return ns
+
+
+def mark_potential(ns):
+    """A seeded, non-zero gfup: what a call that must not write it leaves bit for bit."""
+    import hipla
+    ns.gfup.data = hipla.Vector.from_numpy(np.random.default_rng(11).standard_normal(ns.system.n_p))
+    return ns.gfup.numpy().copy()
+
+
+def check_empty_record(rec, one, diagnostics, scalar):
+    """`rec` of Advance(0) against `one` of Advance(1) on the same object: empty arrays of the same dtypes, None where
+    `one` holds None -- and that is where it must: the diagnostics without `diagnostics`, the scalar's arrays without a
+    scalar, the wall flux without a flux wall."""
+    assert rec.declined is None and one.declined is None
+    for name in RECORD_ARRAYS:
+        got, ref = getattr(rec, name), getattr(one, name)
+        if ref is None:
+            assert got is None, name
+        else:
+            assert isinstance(got, np.ndarray) and got.shape == (0,) and got.dtype == ref.dtype and ref.shape == (1,), name
+    assert (one.div_norm is None) == (one.kinetic_energy is None) == (not diagnostics)
+    assert (one.scalar_iterations is None) == (scalar is None)
+    assert (one.wall_flux is None) == (scalar != "wall" or not diagnostics)
+
+
+@pytest.mark.parametrize("diagnostics", [True, False])
+@pytest.mark.parametrize("grid", ["2d", "3d"])
+def test_advance_zero_steps(hip_engine, grid, diagnostics):
+    """Advance(0) without a scalar: gfu and gfup bit-unchanged, the record's arrays empty with the dtypes of Advance(1),
+    div_norm and kinetic_energy None with diagnostics=False."""
+    ns = small() if grid == "2d" else fresh()
+    if grid == "3d":
+        set_velocity(ns, start_velocity(ns.system))
+    u0, p0 = ns.gfu.numpy().copy(), mark_potential(ns)
+    rec = ns.Advance(0, diagnostics=diagnostics)
+    assert np.array_equal(ns.gfu.numpy(), u0) and np.array_equal(ns.gfup.numpy(), p0)
+    check_empty_record(rec, ns.Advance(1, diagnostics=diagnostics), diagnostics, None)
+
+
+@pytest.mark.parametrize("scalar,diagnostics", [("wall", True), ("wall", False), ("no wall", True)])
+def test_advance_zero_steps_with_a_buoyant_scalar(hip_engine, scalar, diagnostics):
+    """Advance(0) with a buoyant scalar: gfu, gfup and the temperature bit-unchanged; scalar_iterations and wall_flux
+    empty as well, wall_flux None without a flux wall (and without diagnostics)."""
+    ns = small(scalar)
+    u0, p0, T0 = ns.gfu.numpy().copy(), mark_potential(ns), ns.temperature.numpy().copy()
+    rec = ns.Advance(0, diagnostics=diagnostics)
+    assert np.array_equal(ns.gfu.numpy(), u0) and np.array_equal(ns.gfup.numpy(), p0)
+    assert np.array_equal(ns.temperature.numpy(), T0)
+    one = ns.Advance(1, diagnostics=diagnostics)
+    check_empty_record(rec, one, diagnostics, scalar)
+    assert not np.array_equal(ns.temperature.numpy(), T0)           # (the scalar is live: one step moves it)
+
+
+@pytest.mark.parametrize("grid", ["2d", "3d"])
+def test_advance_zero_pseudo_steps_project(hip_engine, grid):
+    """Advance(0, pseudo=True) is the leading Project(gfu) of the pseudo time stepping: gfu agrees with `Project` on a
+    twin to 1e-8 (both with converged solves, the bound and the twin of test_five_steps_against_do_time_step), gfup is
+    written, the record is empty."""
+    ns, twin = (small(), tighten(small())) if grid == "2d" else (fresh(), tighten(fresh()))
+    v0 = np.random.default_rng(2).standard_normal(ns.system.n_u)
+    set_velocity(ns, v0)
+    set_velocity(twin, v0)
+    p0 = mark_potential(ns)
+    rec = ns.Advance(0, pseudo=True, **TIGHT)
+    twin.Project(twin.gfu)
+    err = rel(ns.gfu.numpy(), twin.gfu.numpy())
+    print("pseudo, no step", grid, err, rel(ns.gfup.numpy(), twin.gfup.numpy()))
+    assert err < 1e-8
+    assert rel(ns.gfu.numpy(), v0) > 1e-2                            # (the projection moved the field)
+    assert not np.array_equal(ns.gfup.numpy(), p0) and np.isfinite(ns.gfup.numpy()).all()
+    check_empty_record(rec, ns.Advance(1, pseudo=True, **TIGHT), True, None)
