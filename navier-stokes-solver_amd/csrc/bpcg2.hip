@@ -507,6 +507,19 @@ struct CloseArgs {
   int32_t fold;
 };
 
+// A word of ctrl / scal that no workgroup of the running launch writes, read through a SCALAR load: the constant
+// address space makes a uniform load an s_load, which neither occupies the vector memory counter nor makes hipcc wait
+// for the vector loads in flight around it.  (Written by earlier launches only: the scalar cache is invalidated at
+// every kernel start.  The words workgroup 0 of C1 writes -- S_BETA, wd_slot(it), hist, ctrl[C_LAST_IT ... C_DONE] --
+// are read by no workgroup of the same launch, except C_DONE in skip(), where either value gives the same result:
+// a workgroup that misses it computes the same `stop`.)
+__device__ __forceinline__ int32_t uniform_i32(const int32_t* p, int i) {
+  return ((const int32_t __attribute__((address_space(4)))*)p)[i];
+}
+__device__ __forceinline__ double uniform_f64(const double* p, int i) {
+  return ((const double __attribute__((address_space(4)))*)p)[i];
+}
+
 // The books of iteration it - 1, evaluated by every workgroup of C1(it) from the same inputs (what K5
 // did with one lane): wdn, beta = wdn / wd (:236), history entry (:243), stop test (:246), wd of the next
 // iteration.  Workgroup 0 records them.  Returns false when the loop stops at iteration it - 1.
@@ -515,11 +528,12 @@ __device__ __forceinline__ bool close_iteration(const CloseArgs& a, int it, doub
   const int prev = it - 1;
   double wdn;
   if constexpr (FOLD) wdn = fixed_sum_1024(a.partials_c, a.nc, a.partials_c, 0, lds);
-  else wdn = a.scal[S_WDN];
-  const double wd = a.scal[wd_slot(prev)];
+  else wdn = uniform_f64(a.scal, S_WDN);
+  const double wd = uniform_f64(a.scal, wd_slot(prev));
   const double beta = wdn / wd;
   const double err = sqrt(fabs(wd));
-  const double bound = a.scal[S_TOL] * (a.scal[S_REL] != 0.0 ? a.scal[S_ERR0] : 1.0);
+  const double rel = uniform_f64(a.scal, S_REL), err0 = uniform_f64(a.scal, S_ERR0);
+  const double bound = uniform_f64(a.scal, S_TOL) * (rel != 0.0 ? err0 : 1.0);
   const bool stop = err < bound;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     a.scal[S_BETA] = beta;
@@ -551,7 +565,10 @@ __global__ __launch_bounds__(kBlock) void bpcg2_close_kernel(CloseArgs a) {
 // C1: K1 with the books of the previous iteration in front and the operand beta * s1 + w1 on the fly.
 // FOLD (short sums) is a template parameter: the registers of the in-kernel sum must not cost the
 // bandwidth-bound large systems their occupancy.
-template <bool FOLD, bool NT = false>
+// IT0: whether this is iteration 0, where the host's knowledge is a template argument -- 1: it is, 0: it is not, -1: `it`
+// decides at run time.  The launches of the row-per-lane kernel name it: there every load under a run-time `it ? .. : ..`
+// is a branch with a wait of its own between two loads (csr_stream.h); the stream-kernel forms stay one per FOLD.
+template <bool FOLD, bool NT = false, int IT0 = -1>
 struct EpiK1c {
   CloseArgs cl;
   double* __restrict__ u0;
@@ -582,11 +599,14 @@ struct EpiK1c {
   int32_t jb_count = 0, jb_bs = 0;
   double alpha = 0.0, beta = 0.0;
   bool pending = false;
-  __device__ bool skip() const { return cl.ctrl[C_DONE] != 0; }
+  // ctrl and scal are read through scalar loads (uniform_i32 / uniform_f64): no vector load and wait in front of the
+  // rows' loads or between them and the gathers
+  __device__ bool first() const { return IT0 < 0 ? it == 0 : IT0 == 1; }
+  __device__ bool skip() const { return uniform_i32(cl.ctrl, C_DONE) != 0; }
   __device__ bool prologue(double* lds) {
-    if (it == 0) return true;
-    alpha = cl.scal[S_ALPHA];
-    pending = cl.ctrl[C_PENDING] == it;
+    if (first()) return true;
+    alpha = uniform_f64(cl.scal, S_ALPHA);
+    pending = uniform_i32(cl.ctrl, C_PENDING) == it;
     return close_iteration<FOLD>(cl, it, lds, &beta);
   }
   struct X {
@@ -599,34 +619,36 @@ struct EpiK1c {
     __device__ const double* ptr() const { return s1; }
     __device__ const double* ptr2() const { return w1; }
     __device__ double pair(double s, double w) const { return first ? s : fma(beta, s, w); }
-    __device__ double operator()(int c) const { return first ? s1[c] : fma(beta, s1[c], w1[c]); }   // :240-241
+    // :240-241 (IT0 known: no branch, hence no wait, between two gathers)
+    __device__ double operator()(int c) const {
+      if constexpr (IT0 == 1) return s1[c];
+      else if constexpr (IT0 == 0) return fma(beta, s1[c], w1[c]);
+      else return first ? s1[c] : fma(beta, s1[c], w1[c]);
+    }
   };
-  __device__ X xop(const double*) const { return X{s1, w1, beta, it == 0}; }
-  // the row's six read-only operands are requested before the matrix stream (and before alpha / beta
-  // are known: the prologue runs later)
-  // requesting the row's six operands before the matrix stream costs 12 registers (occupancy 8 -> 6 waves per
-  // SIMD) and measured 0.7 % slower at 1e7 DoF, no different at 1e5 (profiles/r02_ab_k1_prefetch.txt): off
-#ifndef NSS_K1C_PREFETCH
-#define NSS_K1C_PREFETCH 0
-#endif
-
-#if NSS_K1C_PREFETCH
-  struct Pre { double q = 0.0, z0 = 0.0, t2 = 0.0, s0 = 0.0, w0 = 0.0, u0 = 0.0; };
-  __device__ Pre fetch(int r) const {
-    if (it == 0) return Pre{q[r], 0.0, 0.0, 0.0, 0.0, 0.0};
-    return Pre{q[r], z0[r], t2[r], s0[r], w0[r], u0[r]};
+  __device__ X xop(const double*) const { return X{s1, w1, beta, first()}; }
+  // The row's six read-only operands.  NT: q, z0, t2, w0, u0 are read here and nowhere else before they are
+  // rewritten -- streaming loads keep them out of the XCD L2s (s0 stays: the rows of A and B read it next).
+  // Row-per-lane kernel (DirectPre, csr_stream.h): all six requested with the front loads, before alpha, beta and
+  // `pending` are known, and without a condition -- a load under `pending ? .. : 0` is a branch that hipcc closes with a
+  // wait.  What that reads for nothing: u0 in the one C1 that follows a flush (poll); every other iteration applies the
+  // deferred update.  (Iteration 0 needs q alone: IT0.)  +24 registers for two rows there.
+  // Stream kernel: loaded late, in row() -- up front they cost it 12 registers (occupancy 8 -> 6 waves per SIMD) and
+  // measured 0.7 % slower at 1e7 DoF, no different at 1e5 (profiles/r02_ab_k1_prefetch.txt).
+  struct Ops { double q, z0, t2, s0, w0, u0; };
+  using DirectPre = Ops;
+  __device__ Ops fetch_direct(int r) const {
+    if constexpr (IT0 == 1) return Ops{ld1s<NT>(q + r), 0.0, 0.0, 0.0, 0.0, 0.0};
+    else return Ops{ld1s<NT>(q + r), ld1s<NT>(z0 + r), ld1s<NT>(t2 + r), s0[r], ld1s<NT>(w0 + r), ld1s<NT>(u0 + r)};
   }
-  __device__ void row(int r, double bts, const Pre& p) const {
-#else
-  struct PreLate { double q, z0, t2, s0, w0, u0; };
   __device__ void row(int r, double bts) const {
-    // NT: q, z0, t2, w0, u0 are read here and nowhere else before they are rewritten -- streaming loads keep
-    // them out of the XCD L2s (s0 stays: the rows of A and B read it next)
-    const PreLate p{ld1s<NT>(q + r), it ? ld1s<NT>(z0 + r) : 0.0, it ? ld1s<NT>(t2 + r) : 0.0, it ? s0[r] : 0.0,
-                    it ? ld1s<NT>(w0 + r) : 0.0, (it && pending) ? ld1s<NT>(u0 + r) : 0.0};
-#endif
+    const bool it = !first();
+    row(r, bts, Ops{ld1s<NT>(q + r), it ? ld1s<NT>(z0 + r) : 0.0, it ? ld1s<NT>(t2 + r) : 0.0, it ? s0[r] : 0.0,
+                    it ? ld1s<NT>(w0 + r) : 0.0, (it && pending) ? ld1s<NT>(u0 + r) : 0.0});
+  }
+  __device__ void row(int r, double bts, const Ops& p) const {
     double qv = p.q;
-    if (it != 0) {
+    if (!first()) {
       const double zo = p.z0, t2v = p.t2, so = p.s0;
       if (pending) NSS_ST(u0[r], fma(alpha, so, p.u0));    // deferred u += alpha s of iteration it - 1
       qv = fma(-alpha, t2v, fma(beta, qv, zo));
@@ -649,7 +671,7 @@ struct EpiK1c {
       bjac_rows_from_lds(jb_first, jb_order, jb_run, jb_packed, jb_count, jb_bs, b, k1_t0,
                          [&](int i, double s) { t1[i] = k * s; });
     }
-    if (it == 0 || ghost_n == 0) return;
+    if (first() || ghost_n == 0) return;
     const int stride = gridDim.x * kBlock;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < ghost_n; i += stride) ghost_s0[i] = fma(beta, ghost_s0[i], ghost_w0[i]);
   }
@@ -1026,16 +1048,26 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
       const bool fj = c1_applies_block_jacobi(s);
       const nss_bjac_s* J = s.pre_bjac;
       const size_t lds = fj ? sizeof(double) * kBlockRows : 0;
-#define NSS_C1(FOLD, NT, LAUNCH)                                                                                       \
-  LAUNCH<kCodes>(*s.BT, s.s1, EpiK1c<FOLD, NT>{close_args(s, FOLD), s.u0, s.q, s.z0, s.t2, s.s0, s.w0, s.t0, s.t1, dinv, s.k, it, \
+#define NSS_C1(FOLD, NT, IT0, LAUNCH)                                                                                  \
+  LAUNCH<kCodes>(*s.BT, s.s1, EpiK1c<FOLD, NT, IT0>{close_args(s, FOLD), s.u0, s.q, s.z0, s.t2, s.s0, s.w0, s.t0, s.t1, dinv, s.k, it, \
                                        s.s1, s.w1, s.dist_compact ? s.ghost_n : 0, s.ghost_s0, s.ghost_w0,                 \
                                        fj ? s.BT->jb_first : nullptr, fj ? s.BT->jb_order : nullptr, fj ? J->run : nullptr, fj ? J->inv_sym : nullptr,   \
                                        fj ? J->nblocks : 0, fj ? J->bs : 0}, st, 0, -1, lds)
       // (kCodes: a matrix with value codes streams them, nss_csr_code_values; same bits)
-      if (nt && fold) NSS_C1(true, true, launch_csr_direct);
-      else if (nt) NSS_C1(false, true, launch_csr_direct);
-      else if (fold) NSS_C1(true, false, launch_csr);
-      else NSS_C1(false, false, launch_csr);
+      if (s.BT->ell_col) {     // the row-per-lane kernel, with "iteration 0" as a template argument (EpiK1c)
+        const int sel = (fold ? 4 : 0) + (nt ? 2 : 0) + (it == 0 ? 1 : 0);
+        switch (sel) {
+          case 0: NSS_C1(false, false, 0, launch_csr_direct); break;
+          case 1: NSS_C1(false, false, 1, launch_csr_direct); break;
+          case 2: NSS_C1(false, true, 0, launch_csr_direct); break;
+          case 3: NSS_C1(false, true, 1, launch_csr_direct); break;
+          case 4: NSS_C1(true, false, 0, launch_csr_direct); break;
+          case 5: NSS_C1(true, false, 1, launch_csr_direct); break;
+          case 6: NSS_C1(true, true, 0, launch_csr_direct); break;
+          default: NSS_C1(true, true, 1, launch_csr_direct); break;
+        }
+      } else if (fold) NSS_C1(true, false, -1, launch_csr);
+      else NSS_C1(false, false, -1, launch_csr);
 #undef NSS_C1
       if (!fj) bpcg2_k1_finish(s, st, d);
       break;

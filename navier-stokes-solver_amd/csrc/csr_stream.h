@@ -719,74 +719,129 @@ __global__ __launch_bounds__(kBlock) void csr_stream_dual_kernel(CsrView a, CsrV
   }
 }
 
+// The row-per-lane kernel's view of the Pre / fetch interface: an epilogue may keep its up-front operands for that
+// kernel alone -- struct DirectPre; fetch_direct(r); row(r, ax, const DirectPre&) -- where the stream kernel is better
+// off loading them late (EpiK1c: 12 registers there cost it occupancy).  Without DirectPre: as EpiPre.
+template <class E, class = void>
+struct EpiDirectPre : EpiPre<E> {};
+template <class E>
+struct EpiDirectPre<E, std::void_t<typename E::DirectPre>> {
+  using type = typename E::DirectPre;
+  static __device__ type fetch(const E& e, int r) { return e.fetch_direct(r); }
+  static __device__ void row(E& e, int r, double ax, const type& p) { e.row(r, ax, p); }
+};
+
 // Row-per-lane kernel for the fixed-width copy (nss_csr_s::ell_col): workgroup = one row block of at most
 // kDirectRows rows, lane t takes rows r0 + t and r0 + t + 256 (unit stride across the lanes; giving a lane two
-// CONSECUTIVE rows instead makes every per-row access of the epilogue a stride-2 access: C1 +35 %).  All loads of both rows -- slots, epilogue
-// operands -- are requested before the prologue; the operand is gathered (two entries per row: nothing to
-// stage).  The row sum is formed exactly as the stream kernel forms it (0 + p0 + p1, products rounded on their
-// own: mul_unfused), so both kernels give identical bits.
+// CONSECUTIVE rows instead makes every per-row access of the epilogue a stride-2 access: C1 +35 %).  The operand is
+// gathered (two entries per row: nothing to stage).  The row sum is formed exactly as the stream kernel forms it
+// (0 + p0 + p1, products rounded on their own: mul_unfused), so both kernels give identical bits.
 // Coded form (VT = Coded8): the row's 16-bit code word (`ecode`) instead of the two 8-byte values, both values from the
 // LDS copy of the dictionary -- 10 bytes per row instead of 24.
+//
+// A workgroup makes THREE dependent memory rounds: (1) column pairs, code words / values and the epilogue's operands of
+// both rows, (2) the eight operand gathers, (3) the stores.  For that the rows' code is straight-line from the first
+// load to the last gather -- hipcc closes every branch that holds a load (`live ? load : default`, `c >= 0 ? x[c] : 0`)
+// with s_waitcnt vmcnt(0), and the earlier form of this kernel made about eleven rounds that way (seen in the ISA,
+// profiles/r06_c1_rounds.md):
+//  * the row-block bounds come through scalar loads (constant address space, as csr_stream_body reads blkseg);
+//  * ONE uniform branch separates full row blocks (all but the last of a matrix: no per-lane predicate at all) from
+//    partial ones, whose loads go to a clamped valid row -- only row() is predicated there;
+//  * padding slots (column -1) gather from column 0 and the product is discarded by a select: the sum is
+//    0 + (p0 or 0) + (p1 or 0), the same bits as skipping the addition (0 + p is never -0, and s + 0 == s then);
+//  * the epilogue's prologue runs behind the front loads; its own reads should be scalar loads (EpiK1c);
+//  * coded form: the one wait and barrier that publish the dictionary stand behind the gathers, where every load of the
+//    workgroup is in flight.
+// base_first: this call is the row block's first (it requests the dictionary and runs the prologue).
+template <bool FULL, class Epi, class VT>
+__device__ __forceinline__ bool csr_direct_rows(const CsrView& a, const int32_t* __restrict__ ecol,
+                                                const double* __restrict__ eval, const uint16_t* __restrict__ ecode,
+                                                const double* __restrict__ x, Epi& epi, int base, int r1, bool base_first,
+                                                double* red, double* dict) {
+  using XOp = typename EpiX<Epi>::type;
+  using Pre = EpiDirectPre<Epi>;
+  constexpr bool kCoded = std::is_same<VT, Coded8>::value;
+  constexpr int kRows = kDirectRows / kBlock;
+  typedef int32_t int2v __attribute__((ext_vector_type(2)));
+  const int tid = threadIdx.x;
+  int rl[kRows];                                              // the row every load of slot q goes to
+#pragma unroll
+  for (int q = 0; q < kRows; ++q) {
+    const int r = base + tid + q * kBlock;
+    rl[q] = FULL ? r : (r < r1 ? r : r1 - 1);
+  }
+  int2v c[kRows];
+  dbl2v v[kRows];
+  uint16_t code[kRows];
+  typename Pre::type pre[kRows];
+#pragma unroll
+  for (int q = 0; q < kRows; ++q) c[q] = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(ecol) + rl[q]);
+#pragma unroll
+  for (int q = 0; q < kRows; ++q) {
+    if constexpr (kCoded) code[q] = __builtin_nontemporal_load(ecode + rl[q]);
+    else v[q] = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(eval) + rl[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < kRows; ++q) pre[q] = Pre::fetch(epi, rl[q]);
+  // (coded form) the dictionary's copy is requested BEHIND the rows' loads: the request sits in a branch of its own
+  // (two of the four waves make it), and in front hipcc made every wave wait for it at the join before the first load
+  if (base_first) DictLds<VT>::request(a, dict);
+  if (base_first && !EpiPrologue<Epi>::run(epi, red)) return false;   // uniform over the workgroup
+  const XOp xop = EpiX<Epi>::get(epi, x);
+  double x0[kRows], x1[kRows];
+#pragma unroll
+  for (int q = 0; q < kRows; ++q) {
+    x0[q] = xop(c[q].x >= 0 ? c[q].x : 0);
+    x1[q] = xop(c[q].y >= 0 ? c[q].y : 0);
+  }
+  if constexpr (kCoded) {
+    // the one barrier of the coded form: the dictionary's LDS-DMA is awaited by its waves and published, with
+    // every load of the workgroup in flight.  (Reading the two entries as gathers from the 2-KiB table in global
+    // memory instead -- no LDS, no barrier -- measured the same: profiles/r06_ab_c1_rounds.txt.)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kRows; ++q) v[q] = dbl2v{dict[code[q] & 0xff], dict[code[q] >> 8]};
+  }
+#pragma unroll
+  for (int q = 0; q < kRows; ++q) {
+    const int r = base + tid + q * kBlock;
+    const double p0 = mul_unfused(v[q].x, x0[q]), p1 = mul_unfused(v[q].y, x1[q]);
+    double sum = 0.0;
+    sum += c[q].x >= 0 ? p0 : 0.0;
+    sum += c[q].y >= 0 ? p1 : 0.0;
+    if (FULL || r < r1) Pre::row(epi, r, sum, pre[q]);
+  }
+  return true;
+}
+
 template <class Epi, class VT = double>
 __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int32_t* __restrict__ ecol,
                                                             const double* __restrict__ eval,
                                                             const uint16_t* __restrict__ ecode,
                                                             const double* __restrict__ x, Epi epi) {
   static_assert(kDirectWidth == 2, "csr_direct_kernel is written for two slots per row");
-  using XOp = typename EpiX<Epi>::type;
-  constexpr bool kCoded = std::is_same<VT, Coded8>::value;
   __shared__ double red[kRedDoubles];
   double* const dict = DictLds<VT>::get();
   if (epi.skip()) return;
-  const int tid = threadIdx.x, wg = int(blockIdx.x);
+  const int wg = int(blockIdx.x);
   const int lb = (wg & (kXcds - 1)) * a.per_xcd + (wg >> 3);
   const int b = lb < a.nblk ? a.blk0 + lb : -1;
   if (b >= 0) {
-    DictLds<VT>::request(a, dict);                            // (coded form) ahead of the rows' loads
-    const int r0 = a.rowblk[b], r1 = a.rowblk[b + 1];
-    for (int base = r0; base < r1; base += kDirectRows) {     // (one trip: the plan caps such blocks at kDirectRows rows)
-      constexpr int kRows = kDirectRows / kBlock;
-      typedef int32_t int2v __attribute__((ext_vector_type(2)));
-      int2v c[kRows];
-      dbl2v v[kRows];
-      uint16_t code[kRows];
-      typename EpiPre<Epi>::type pre[kRows];
-#pragma unroll
-      for (int q = 0; q < kRows; ++q) {
-        const int r = base + tid + q * kBlock;
-        const bool live = r < r1;
-        c[q] = live ? __builtin_nontemporal_load(reinterpret_cast<const int2v*>(ecol) + r) : int2v{-1, -1};
-        if constexpr (kCoded) code[q] = live ? __builtin_nontemporal_load(ecode + r) : uint16_t(0);
-        else v[q] = live ? __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(eval) + r) : dbl2v{0.0, 0.0};
-        pre[q] = live ? EpiPre<Epi>::fetch(epi, r) : typename EpiPre<Epi>::type{};
-      }
-      if (base == r0 && !EpiPrologue<Epi>::run(epi, red)) return;   // uniform over the workgroup
-      const XOp xop = EpiX<Epi>::get(epi, x);
-      double x0[kRows], x1[kRows];
-#pragma unroll
-      for (int q = 0; q < kRows; ++q) {
-        x0[q] = c[q].x >= 0 ? xop(c[q].x) : 0.0;
-        x1[q] = c[q].y >= 0 ? xop(c[q].y) : 0.0;
-      }
-      if constexpr (kCoded) {
-        // the one barrier of the coded form: the dictionary's LDS-DMA is awaited by its waves and published, with
-        // the operand gather already in flight
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < kRows; ++q) v[q] = dbl2v{dict[code[q] & 0xff], dict[code[q] >> 8]};
-      }
-#pragma unroll
-      for (int q = 0; q < kRows; ++q) {
-        const int r = base + tid + q * kBlock;
-        if (r < r1) {
-          double sum = 0.0;
-          if (c[q].x >= 0) sum += mul_unfused(v[q].x, x0[q]);
-          if (c[q].y >= 0) sum += mul_unfused(v[q].y, x1[q]);
-          EpiPre<Epi>::row(epi, r, sum, pre[q]);
-        }
-      }
+    typedef const int32_t __attribute__((address_space(4))) * ConstI32;
+    const ConstI32 rb = (ConstI32)(a.rowblk + b);             // uniform, invariant: scalar loads
+    const int r0 = rb[0], r1 = rb[1];
+    bool go = true;
+    if (r1 - r0 == kDirectRows) {
+      go = csr_direct_rows<true, Epi, VT>(a, ecol, eval, ecode, x, epi, r0, r1, true, red, dict);
+    } else if (r1 - r0 < kDirectRows) {
+      if (r1 > r0) go = csr_direct_rows<false, Epi, VT>(a, ecol, eval, ecode, x, epi, r0, r1, true, red, dict);
+    } else {
+      // (the plan caps the row blocks of such a matrix at kDirectRows rows; a longer one is walked in pieces)
+      for (int base = r0; go && base < r1; base += kDirectRows)
+        go = csr_direct_rows<false, Epi, VT>(a, ecol, eval, ecode, x, epi, base, r1, base == r0, red, dict);
     }
+    if (!go) return;                                          // the prologue ended the workgroup (uniform)
   }
   epi.finish(b, red);
 }

@@ -801,6 +801,7 @@ static void direct_rows(nss_csr_s& A, hipStream_t st) {
 #if NSS_DIRECT_ROWS
   if (A.val32) return;                                   // (fp32 values: the stream kernel only)
   if (A.m < g_direct_min_rows || A.nnz > int64_t(kDirectWidth) * A.m) return;
+  if (A.n == 0) return;                                  // (csr_direct_kernel gathers padding slots from column 0)
   int32_t* ecol = nullptr;
   double* eval = nullptr;
   int32_t* wide = nullptr;
