@@ -9,6 +9,8 @@ Matrices and block-Jacobi inverses are owned by the library.
 There is no fallback: if the shared library or the GPU is missing this module raises
 `EngineUnavailable`."""
 
+import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -199,32 +201,84 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if os.environ.get("NSS_STREAM_LOADS") and hasattr(lib, "nss_stream_loads_mode"):     # measurements: -1 / 0 / 1
-        lib.nss_stream_loads_mode(int(os.environ["NSS_STREAM_LOADS"]))
-    if os.environ.get("NSS_VALUE_CODES") and hasattr(lib, "nss_csr_value_code_mode"):    # measurements: -1 / 0 / 1
-        lib.nss_csr_value_code_mode(int(os.environ["NSS_VALUE_CODES"]))
-    if os.environ.get("NSS_BLOCK_CODES") and hasattr(lib, "nss_bjac_block_code_mode"):   # measurements: -1 / 0 / 1
-        lib.nss_bjac_block_code_mode(int(os.environ["NSS_BLOCK_CODES"]))
-    if os.environ.get("NSS_COND_FUSE") and hasattr(lib, "nss_cond_fuse_mode"):           # measurements: 0 / 1
-        lib.nss_cond_fuse_mode(int(os.environ["NSS_COND_FUSE"]))
-    if os.environ.get("NSS_DISPATCH_PLANES") and hasattr(lib, "nss_csr_dispatch_mode"):   # measurements: -1 / 0 / T
-        lib.nss_csr_dispatch_mode(int(os.environ["NSS_DISPATCH_PLANES"]), int(os.environ.get("NSS_DISPATCH_MIN_PERIOD", "0")),
-                                  int(os.environ.get("NSS_DISPATCH_RUN", "0")))
-    if os.environ.get("NSS_FOLD_SUMS"):                                                   # measurements: -1 / 0 / 1
-        for name in ("nss_bpcg2_fold_mode", "nss_minres_fold_mode", "nss_bpcg1_fold_mode"):
-            if hasattr(lib, name):
-                getattr(lib, name)(int(os.environ["NSS_FOLD_SUMS"]))
-    if os.environ.get("NSS_FUSE_BJAC") and hasattr(lib, "nss_bpcg2_fuse_block_jacobi"):   # measurements: 0 / 1
-        lib.nss_bpcg2_fuse_block_jacobi(int(os.environ["NSS_FUSE_BJAC"]))
-    if os.environ.get("NSS_AMG_BATCH") and hasattr(lib, "nss_amg_batch_components"):      # measurements: 0 / 1
-        lib.nss_amg_batch_components(int(os.environ["NSS_AMG_BATCH"]))
-    if os.environ.get("NSS_LANCZOS_FOLD") and hasattr(lib, "nss_lanczos_fold_mode"):      # measurements: -1 / 0 / 1
-        lib.nss_lanczos_fold_mode(int(os.environ["NSS_LANCZOS_FOLD"]))
+    _apply_environment(lib)
     return lib
 
 
 class NssError(RuntimeError):
     pass
+
+
+# ---- process-wide plan overrides ---------------------------------------------------------------------------------------
+# The list of record of the switches that choose between kernel plans (what each value means: include/nss_krylov.h at
+# the setter).  `default`: the arguments that mean "library default"; `env`: the variable load_library() reads -- unset
+# or empty: nothing is set --, then companions that supply the further arguments (0 when unset).
+Override = collections.namedtuple("Override", "setter default env")
+_FOLD = ("NSS_FOLD_SUMS",)
+OVERRIDES = {
+    "stream_loads": Override("nss_stream_loads_mode", (-1,), ("NSS_STREAM_LOADS",)),
+    "value_codes": Override("nss_csr_value_code_mode", (-1,), ("NSS_VALUE_CODES",)),
+    "block_codes": Override("nss_bjac_block_code_mode", (-1,), ("NSS_BLOCK_CODES",)),
+    "cond_fuse": Override("nss_cond_fuse_mode", (0,), ("NSS_COND_FUSE",)),
+    "dispatch": Override("nss_csr_dispatch_mode", (-2, 0, 0),
+                         ("NSS_DISPATCH_PLANES", "NSS_DISPATCH_MIN_PERIOD", "NSS_DISPATCH_RUN")),
+    "bpcg2_fold": Override("nss_bpcg2_fold_mode", (-1,), _FOLD),
+    "minres_fold": Override("nss_minres_fold_mode", (-1,), _FOLD),
+    "bpcg1_fold": Override("nss_bpcg1_fold_mode", (-1,), _FOLD),
+    "fuse_bjac": Override("nss_bpcg2_fuse_block_jacobi", (-1,), ("NSS_FUSE_BJAC",)),
+    "amg_batch": Override("nss_amg_batch_components", (1,), ("NSS_AMG_BATCH",)),
+    "lanczos_fold": Override("nss_lanczos_fold_mode", (-1,), ("NSS_LANCZOS_FOLD",)),
+    "minres_fuse": Override("nss_minres_fuse_mode", (-1,), ()),
+    "pair_stage": Override("nss_csr_pair_mode", (-1,), ()),
+    "direct_rows": Override("nss_csr_direct_rows_threshold", (-1,), ()),
+}
+# The arguments in force: the library has no getters, so every set goes through _set_override.
+_in_force = {name: o.default for name, o in OVERRIDES.items()}
+
+
+def _set_override(lib, name, args):
+    rc = getattr(lib, OVERRIDES[name].setter)(*args)
+    if rc == 0:                          # a refused value changes nothing in the library
+        _in_force[name] = args
+    return rc
+
+
+def _apply_environment(lib):
+    for name, o in OVERRIDES.items():
+        if o.env and os.environ.get(o.env[0]) and hasattr(lib, o.setter):     # (absent in older A/B builds)
+            companions = tuple(int(os.environ.get(v, "0")) for v in o.env[1:])
+            _set_override(lib, name, (int(os.environ[o.env[0]]),) + companions)
+
+
+@contextlib.contextmanager
+def overrides(lib, **values):
+    """Set the named switches of OVERRIDES (an int, or a tuple for a setter of several arguments) for the block; on
+    exit each is back at the arguments that were in force on entry, which need not be the library default.  A value the
+    library refuses raises NssError after what this call had already set is put back."""
+    wanted = {}
+    for name, value in values.items():
+        args = tuple(int(a) for a in (value if isinstance(value, (tuple, list)) else (value,)))
+        if name not in OVERRIDES or len(args) != len(OVERRIDES[name].default):
+            raise TypeError("no plan override %s taking %d argument(s)" % (name, len(args)))
+        wanted[name] = args
+    entry = {}
+    try:
+        for name, args in wanted.items():
+            before = _in_force[name]
+            if _set_override(lib, name, args) != 0:
+                raise NssError(lib.nss_last_error().decode("utf-8", "replace"))
+            entry[name] = before
+        yield
+    finally:
+        for name, args in entry.items():
+            _set_override(lib, name, args)
+
+
+def reset_overrides(lib):
+    """Every switch back to the library default of the table."""
+    for name, o in OVERRIDES.items():
+        if hasattr(lib, o.setter):
+            _set_override(lib, name, o.default)
 
 
 class _CsrHandle:
@@ -412,6 +466,10 @@ class HipEngine:
 
     def synchronize(self):
         self._check(self.lib.nss_stream_synchronize(self.stream))
+
+    def overrides(self, **values):
+        """`with eng.overrides(value_codes=1, direct_rows=0): ...` -- see the module's overrides()."""
+        return overrides(self.lib, **values)
 
     # ---- buffers -----------------------------------------------------------------------
     def zeros(self, n):

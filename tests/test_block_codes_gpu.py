@@ -29,19 +29,6 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
-@pytest.fixture
-def block_codes_default(hip_engine):
-    """every test leaves the process-wide overrides at their defaults"""
-    lib = hip_engine.lib
-    try:
-        yield lib
-    finally:
-        lib.nss_bjac_block_code_mode(-1)
-        lib.nss_csr_value_code_mode(-1)
-        lib.nss_bpcg2_fuse_block_jacobi(-1)
-        lib.nss_stream_loads_mode(-1)
-
-
 def distinct_blocks(bs, count, symmetric, seed=0):
     """`count` well-conditioned bs x bs blocks: SPD, or -- not symmetric -- with an inverse that is not symmetric either"""
     rng = np.random.default_rng(seed)
@@ -72,7 +59,7 @@ def jacobi(A, table):
 
 
 def apply_both(eng, handle, n, alpha, beta, seed=1):
-    """(y of apply, y of apply_dot, its partials) with the current mode"""
+    """(y of apply, y of apply_dot, its partials) with the mode in force"""
     rng = np.random.default_rng(seed)
     x, y0 = rng.standard_normal(n), rng.standard_normal(n)
     xb, yb, zb = eng.zeros(n), eng.zeros(n), eng.zeros(n)
@@ -85,22 +72,19 @@ def apply_both(eng, handle, n, alpha, beta, seed=1):
     return eng.to_host(yb).copy(), eng.to_host(zb).copy(), partials
 
 
-def assert_twins_agree(eng, lib, handle, n, betas=(0.0, 0.625), alpha=-1.75):
+def assert_twins_agree(eng, handle, n, betas=(0.0, 0.625), alpha=-1.75):
     """stream loads 1: the kernels with the non-temporal loads -- of the code bytes in the coded one -- that the
     automatic mode takes from 20 MiB per vector on (the headline's form); -1: the plain loads of these sizes"""
     for stream_loads in (-1, 1):
-        assert lib.nss_stream_loads_mode(stream_loads) == 0
         for beta in betas:
-            assert lib.nss_bjac_block_code_mode(1) == 0
-            coded = apply_both(eng, handle, n, alpha, beta)
-            assert lib.nss_bjac_block_code_mode(0) == 0
-            plain = apply_both(eng, handle, n, alpha, beta)
+            with eng.overrides(stream_loads=stream_loads, block_codes=1):
+                coded = apply_both(eng, handle, n, alpha, beta)
+            with eng.overrides(stream_loads=stream_loads, block_codes=0):
+                plain = apply_both(eng, handle, n, alpha, beta)
             for a, b in zip(coded, plain):
                 assert same_bits(a, b), (stream_loads, beta)
             assert np.all(np.isfinite(coded[0])) and np.any(coded[0] != 0.0)
             assert len(coded[2]) == (handle.nblocks + 255) // 256
-    assert lib.nss_bjac_block_code_mode(-1) == 0
-    assert lib.nss_stream_loads_mode(-1) == 0
 
 
 def stored_doubles(bs, symmetric):
@@ -110,8 +94,7 @@ def stored_doubles(bs, symmetric):
 # ---- 1. apply bits over block sizes and both stored forms -------------------------------------------------------------
 @pytest.mark.parametrize("bs", list(range(1, 17)))
 @pytest.mark.parametrize("symmetric", [True, False])
-def test_apply_bits_over_block_sizes_and_forms(hip_engine, block_codes_default, bs, symmetric):
-    lib = block_codes_default
+def test_apply_bits_over_block_sizes_and_forms(hip_engine, bs, symmetric):
     blocks = distinct_blocks(bs, 5, symmetric)
     pick = np.random.default_rng(2).integers(0, 5, size=300)
     pick[:5] = np.arange(5)
@@ -124,21 +107,21 @@ def test_apply_bits_over_block_sizes_and_forms(hip_engine, block_codes_default, 
     assert dict_.shape == (5, d)                                       # packed form for the symmetric matrix, bs > 1
     assert np.array_equal(code[pick == pick[0]], np.full((pick == pick[0]).sum(), code[0]))
     assert len(np.unique(code)) == 5
-    assert_twins_agree(hip_engine, lib, J.handle, A.shape[0])
+    assert_twins_agree(hip_engine, J.handle, A.shape[0])
 
 
 # ---- 2. index forms and edges -------------------------------------------------------------------------------------------
-def test_ragged_line_ends(hip_engine, block_codes_default):
+def test_ragged_line_ends(hip_engine):
     s = mac_stokes(3, 8)
     table = s.line_blocks(3)
     assert np.any(table < 0)                                           # padded blocks
     J = jacobi(s.A, table)
     assert J.block_coded and 1 <= J.handle.block_codes()[0] <= 256
     assert table.shape[1] % 256 != 0
-    assert_twins_agree(hip_engine, block_codes_default, J.handle, s.n_u)
+    assert_twins_agree(hip_engine, J.handle, s.n_u)
 
 
-def test_scattered_dofs_take_the_index_table(hip_engine, block_codes_default):
+def test_scattered_dofs_take_the_index_table(hip_engine):
     blocks = distinct_blocks(3, 5, True)
     pick = np.random.default_rng(3).integers(0, 5, size=300)
     A, table = block_system(blocks, pick)
@@ -149,76 +132,76 @@ def test_scattered_dofs_take_the_index_table(hip_engine, block_codes_default):
     assert np.any(np.diff(table2, axis=0) != 1)                        # no block is a run: no run words
     J = jacobi(A2, table2)
     assert J.block_coded and J.handle.block_codes()[0] == len(np.unique(pick))
-    assert_twins_agree(hip_engine, block_codes_default, J.handle, A.shape[0])
+    assert_twins_agree(hip_engine, J.handle, A.shape[0])
 
 
-def test_uncovered_dofs(hip_engine, block_codes_default):
+def test_uncovered_dofs(hip_engine):
     blocks = distinct_blocks(3, 5, True)
     pick = np.random.default_rng(5).integers(0, 5, size=300)
     A, table = block_system(blocks, pick, extra=37)
     J = jacobi(A, table[:, :290])                                      # the last ten blocks and the extra dofs: in no block
     assert J.block_coded
-    assert_twins_agree(hip_engine, block_codes_default, J.handle, A.shape[0])
-    assert block_codes_default.nss_bjac_block_code_mode(1) == 0
-    y = apply_both(hip_engine, J.handle, A.shape[0], 2.0, 0.0)[0]
+    assert_twins_agree(hip_engine, J.handle, A.shape[0])
+    with hip_engine.overrides(block_codes=1):
+        y = apply_both(hip_engine, J.handle, A.shape[0], 2.0, 0.0)[0]
     assert np.all(y[290 * 3:] == 0.0)
 
 
 @pytest.mark.parametrize("nblocks", [1, 255, 256, 257, 513])
-def test_block_counts_around_the_workgroup(hip_engine, block_codes_default, nblocks):
+def test_block_counts_around_the_workgroup(hip_engine, nblocks):
     blocks = distinct_blocks(3, 5, True)
     pick = np.random.default_rng(6).integers(0, 5, size=nblocks)
     A, table = block_system(blocks, pick)
     J = jacobi(A, table)
     assert J.block_coded and J.handle.block_codes()[0] == len(np.unique(pick))
-    assert_twins_agree(hip_engine, block_codes_default, J.handle, A.shape[0])
+    assert_twins_agree(hip_engine, J.handle, A.shape[0])
 
 
 # ---- 3. refusals ------------------------------------------------------------------------------------------------------
-def assert_refused_and_unchanged(eng, lib, J, n):
+def assert_refused_and_unchanged(eng, J, n):
     assert not J.block_coded and not J.handle.code_blocks()
     n_codes, nbytes = J.handle.block_codes()
     assert n_codes == 0
     with pytest.raises(Exception):
         J.handle.download_block_codes()
-    assert lib.nss_bjac_block_code_mode(1) == 0
-    forced = apply_both(eng, J.handle, n, -1.75, 0.625)
-    assert J.handle.block_codes() == (0, nbytes)
-    assert lib.nss_bjac_block_code_mode(0) == 0
-    plain = apply_both(eng, J.handle, n, -1.75, 0.625)
+    with eng.overrides(block_codes=1):
+        forced = apply_both(eng, J.handle, n, -1.75, 0.625)
+        assert J.handle.block_codes() == (0, nbytes)
+    with eng.overrides(block_codes=0):
+        plain = apply_both(eng, J.handle, n, -1.75, 0.625)
     for a, b in zip(forced, plain):
         assert same_bits(a, b)
 
 
-def test_the_257th_block_is_refused(hip_engine, block_codes_default):
+def test_the_257th_block_is_refused(hip_engine):
     for count in (256, 257):
         blocks = [np.array([[1.0 + k]]) for k in range(count)]         # 1 / (1 + k): all different
         A, table = block_system(blocks, np.arange(count))
         J = jacobi(A, table)
         if count == 256:
             assert J.block_coded and J.handle.block_codes()[0] == 256
-            assert_twins_agree(hip_engine, block_codes_default, J.handle, A.shape[0])
+            assert_twins_agree(hip_engine, J.handle, A.shape[0])
         else:
-            assert_refused_and_unchanged(hip_engine, block_codes_default, J, A.shape[0])
+            assert_refused_and_unchanged(hip_engine, J, A.shape[0])
 
 
-def test_a_dictionary_over_the_budget_is_refused(hip_engine, block_codes_default):
+def test_a_dictionary_over_the_budget_is_refused(hip_engine):
     blocks = distinct_blocks(16, 40, True)
     assert 40 * stored_doubles(16, True) * 8 > DICT_BUDGET
     A, table = block_system(blocks, np.arange(80) % 40)
     J = jacobi(A, table)
-    assert_refused_and_unchanged(hip_engine, block_codes_default, J, A.shape[0])
+    assert_refused_and_unchanged(hip_engine, J, A.shape[0])
     blocks = distinct_blocks(16, 15, True)                             # 15 x 136 x 8 = 16320 bytes: the largest that fits
     A, table = block_system(blocks, np.arange(80) % 15)
     J = jacobi(A, table)
     assert J.block_coded and J.handle.block_codes()[0] == 15
-    assert_twins_agree(hip_engine, block_codes_default, J.handle, A.shape[0])
+    assert_twins_agree(hip_engine, J.handle, A.shape[0])
     blocks = distinct_blocks(16, 16, True)                             # 16 x 136 x 8 = 17408 bytes
     A, table = block_system(blocks, np.arange(80) % 16)
-    assert_refused_and_unchanged(hip_engine, block_codes_default, jacobi(A, table), A.shape[0])
+    assert_refused_and_unchanged(hip_engine, jacobi(A, table), A.shape[0])
 
 
-def test_a_gauss_seidel_handle_is_left_alone(hip_engine, block_codes_default):
+def test_a_gauss_seidel_handle_is_left_alone(hip_engine):
     import hipla
     s = mac_stokes(3, 8)
     A = hipla.SparseMatrix.from_scipy(s.A)
@@ -227,12 +210,12 @@ def test_a_gauss_seidel_handle_is_left_alone(hip_engine, block_codes_default):
     before, after = hipla.Vector(s.n_u), hipla.Vector(s.n_u)
     gs.Mult(x, before)
     assert not gs.handle.code_blocks() and gs.handle.block_codes()[0] == 0
-    assert block_codes_default.nss_bjac_block_code_mode(1) == 0
-    gs.Mult(x, after)
+    with hip_engine.overrides(block_codes=1):
+        gs.Mult(x, after)
     assert same_bits(before.numpy(), after.numpy())
 
 
-def test_the_sign_of_a_zero_makes_another_block(hip_engine, block_codes_default):
+def test_the_sign_of_a_zero_makes_another_block(hip_engine):
     """diag(-2, 4) inverts to [[-0.5, -0.0], [+0.0, 0.25]] (the pivot row is scaled by -0.5); with a (0, 1) entry of two
     denormal steps the elimination leaves fma(tiny, 0.25, -0.0) = +0.0 there and nothing else differs.  A third, plainly
     non-symmetric block keeps the handle in the full-block form, which holds that entry."""
@@ -252,11 +235,11 @@ def test_the_sign_of_a_zero_makes_another_block(hip_engine, block_codes_default)
     x, y = dict_[code[0]], dict_[code[1]]
     assert np.array_equal(x, y) and not same_bits(x, y)                # equal as values, different as patterns
     assert np.signbit(x[1]) and not np.signbit(y[1]) and x[1] == 0.0 and y[1] == 0.0
-    assert_twins_agree(hip_engine, block_codes_default, J.handle, A.shape[0])
+    assert_twins_agree(hip_engine, J.handle, A.shape[0])
 
 
 # ---- 4. determinism ---------------------------------------------------------------------------------------------------
-def test_two_handles_of_one_matrix_hold_the_same_codes(hip_engine, block_codes_default):
+def test_two_handles_of_one_matrix_hold_the_same_codes(hip_engine):
     s = mac_stokes(3, 8)
     table = s.line_blocks(3)
     first, second = jacobi(s.A, table), jacobi(s.A, table)
@@ -267,10 +250,9 @@ def test_two_handles_of_one_matrix_hold_the_same_codes(hip_engine, block_codes_d
 
 
 # ---- 5. through the loops -----------------------------------------------------------------------------------------------
-def run_loop(eng, s, which, mode, nit=30):
+def run_loop(s, which, nit=30):
+    """(error history, solution) of `nit` iterations with the overrides in force"""
     import hipla
-    lib = eng.lib
-    assert lib.nss_bjac_block_code_mode(mode) == 0
     A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
     preA, preM = hipla.BlockJacobi(A, s.line_blocks(3)), hipla.DiagonalMatrix(1.0 / s.mass)
     assert preA.block_coded
@@ -300,14 +282,14 @@ def run_loop(eng, s, which, mode, nit=30):
 @pytest.mark.parametrize("dim,n", [(3, 8), (2, 12)])
 @pytest.mark.parametrize("which", ["bpcg2", "minres", "bpcg1"])
 @pytest.mark.parametrize("stream_loads", [-1, 1])
-def test_loops_with_codes_equal_loops_without(hip_engine, block_codes_default, dim, n, which, stream_loads):
+def test_loops_with_codes_equal_loops_without(hip_engine, dim, n, which, stream_loads):
     """stream_loads 1: the non-temporal forms of the kernels, as at the headline size"""
-    lib = block_codes_default
-    assert lib.nss_bpcg2_fuse_block_jacobi(0) == 0                      # BPCG v2: the stand-alone apply runs
-    assert lib.nss_stream_loads_mode(stream_loads) == 0
     s = mac_stokes(dim, n)
-    coded = run_loop(hip_engine, s, which, 1)
-    plain = run_loop(hip_engine, s, which, 0)
+    with hip_engine.overrides(fuse_bjac=0, stream_loads=stream_loads):   # BPCG v2: the stand-alone apply runs
+        with hip_engine.overrides(block_codes=1):
+            coded = run_loop(s, which)
+        with hip_engine.overrides(block_codes=0):
+            plain = run_loop(s, which)
     assert len(coded[0]) >= 10 and np.all(np.isfinite(coded[0])) and np.all(np.isfinite(coded[1]))
     for a, b in zip(coded, plain):
         assert same_bits(a, b)
@@ -315,8 +297,7 @@ def test_loops_with_codes_equal_loops_without(hip_engine, block_codes_default, d
 
 # ---- 6. reporting -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", ["runs-packed", "table-packed", "runs-full", "bs1"])
-def test_reported_bytes(hip_engine, block_codes_default, case):
-    lib = block_codes_default
+def test_reported_bytes(hip_engine, case):
     bs = 1 if case == "bs1" else 3
     symmetric = case != "runs-full"
     blocks = distinct_blocks(bs, 5, symmetric)
@@ -331,14 +312,13 @@ def test_reported_bytes(hip_engine, block_codes_default, case):
     runs = case != "table-packed"
     before = J.handle.algorithmic_bytes()
     assert before == 8 * nb * bs * bs + 16 * n                          # nss_bjac_info prices the dense blocks in every form
-    assert lib.nss_bjac_block_code_mode(1) == 0
-    assert J.handle.block_codes() == (5, nb * (1 + (4 if runs else 4 * bs)) + 5 * d * 8 + 16 * n)
-    assert lib.nss_bjac_block_code_mode(0) == 0
+    with hip_engine.overrides(block_codes=1):
+        assert J.handle.block_codes() == (5, nb * (1 + (4 if runs else 4 * bs)) + 5 * d * 8 + 16 * n)
     # the stored form: the packed kernel takes the run word, the full-block kernel the index table
     index = 4 if runs and d != bs * bs else 4 * bs
-    assert J.handle.block_codes() == (5, nb * (8 * d + index) + 16 * n)
-    assert lib.nss_bjac_block_code_mode(-1) == 0                         # by size: 300 blocks stay uncoded
-    assert J.handle.block_codes() == (5, nb * (8 * d + index) + 16 * n)
+    for mode in (0, -1):                                                # -1, by size: 300 blocks stay uncoded
+        with hip_engine.overrides(block_codes=mode):
+            assert J.handle.block_codes() == (5, nb * (8 * d + index) + 16 * n)
     assert J.handle.algorithmic_bytes() == before
 
 

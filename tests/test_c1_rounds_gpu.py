@@ -26,20 +26,6 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
-@pytest.fixture
-def overrides(hip_engine):
-    """every test leaves the process-wide overrides at their defaults"""
-    lib = hip_engine.lib
-    try:
-        yield lib
-    finally:
-        lib.nss_csr_value_code_mode(-1)
-        lib.nss_csr_direct_rows_threshold(-1)
-        lib.nss_bpcg2_fuse_block_jacobi(-1)
-        lib.nss_stream_loads_mode(-1)
-        lib.nss_bjac_block_code_mode(-1)
-
-
 def upload(eng, csr):
     csr = sp.csr_matrix(csr)
     csr.sort_indices()
@@ -89,15 +75,14 @@ def spmv_matrices():
 
 # ---- 1. plain SpMV: row-per-lane kernel against the stream kernel ----------------------------------------------------
 @pytest.mark.parametrize("coded", [False, True])
-def test_rows_kernel_spmv_equals_stream_kernel(hip_engine, overrides, coded):
-    lib = overrides
+def test_rows_kernel_spmv_equals_stream_kernel(hip_engine, coded):
     for name, mat, blocks in spmv_matrices():
         rng = np.random.default_rng(11)
         x, y0 = rng.standard_normal(mat.shape[1]), rng.standard_normal(mat.shape[0])
-        assert lib.nss_csr_direct_rows_threshold(-1) == 0
-        stream = upload(hip_engine, mat)
-        assert lib.nss_csr_direct_rows_threshold(0) == 0
-        rows = upload(hip_engine, mat)
+        with hip_engine.overrides(direct_rows=-1):
+            stream = upload(hip_engine, mat)
+        with hip_engine.overrides(direct_rows=0):
+            rows = upload(hip_engine, mat)
         if coded:
             assert stream.code_values() and rows.code_values(), name
         assert rows.info()["operand_form"] == "rows" and stream.info()["operand_form"] != "rows", name
@@ -142,17 +127,13 @@ def systems():
 @pytest.mark.parametrize("pre,fuse", [("block", 0), ("block", 1), ("point", 0)])
 @pytest.mark.parametrize("codes", [0, 1])
 @pytest.mark.parametrize("nt", [0, 1])
-def test_loop_with_rows_kernel_c1_equals_stream_kernel_c1(hip_engine, overrides, systems, dim, n, pre, fuse, codes, nt):
-    lib = overrides
+def test_loop_with_rows_kernel_c1_equals_stream_kernel_c1(hip_engine, systems, dim, n, pre, fuse, codes, nt):
     s = systems[(dim, n)]
-    assert lib.nss_bpcg2_fuse_block_jacobi(fuse) == 0
-    assert lib.nss_csr_value_code_mode(codes) == 0
-    assert lib.nss_bjac_block_code_mode(codes) == 0
-    assert lib.nss_stream_loads_mode(nt) == 0
-    assert lib.nss_csr_direct_rows_threshold(-1) == 0
-    stream = run_loop(hip_engine, s, pre)
-    assert lib.nss_csr_direct_rows_threshold(0) == 0
-    rows = run_loop(hip_engine, s, pre)
+    plans = dict(fuse_bjac=fuse, value_codes=codes, block_codes=codes, stream_loads=nt)
+    with hip_engine.overrides(direct_rows=-1, **plans):
+        stream = run_loop(hip_engine, s, pre)
+    with hip_engine.overrides(direct_rows=0, **plans):
+        rows = run_loop(hip_engine, s, pre)
     assert rows[3]["operand_form"] == "rows" and stream[3]["operand_form"] != "rows"
     assert rows[3]["value_bytes"] == (1 if codes else 8) * rows[3]["nnz"]
     assert rows[4] == stream[4] == bool(fuse)
@@ -161,20 +142,17 @@ def test_loop_with_rows_kernel_c1_equals_stream_kernel_c1(hip_engine, overrides,
         assert same_bits(a, b)
 
 
-def test_loop_with_full_row_blocks(hip_engine, overrides):
+def test_loop_with_full_row_blocks(hip_engine):
     """1.06e6 velocity rows: B^T has 512-row blocks, so C1 takes the body without a per-lane predicate; in two parts,
     compared with the uninterrupted loop whose C1 is the stream kernel"""
-    lib = overrides
     s = mac_stokes(2, 730, 0.01)
     assert s.n_u > FULL_BLOCK_ROWS
-    assert lib.nss_bpcg2_fuse_block_jacobi(0) == 0
-    assert lib.nss_csr_value_code_mode(1) == 0
-    assert lib.nss_stream_loads_mode(1) == 0
-    assert lib.nss_csr_direct_rows_threshold(0) == 0
-    rows = run_loop(hip_engine, s, "block", chunks=((0, 5), (5, NIT)))
+    plans = dict(fuse_bjac=0, value_codes=1, stream_loads=1)
+    with hip_engine.overrides(direct_rows=0, **plans):
+        rows = run_loop(hip_engine, s, "block", chunks=((0, 5), (5, NIT)))
     assert rows[3]["operand_form"] == "rows" and rows[3]["row_blocks"] >= 2048
-    assert lib.nss_csr_direct_rows_threshold(-1) == 0
-    stream = run_loop(hip_engine, s, "block")
+    with hip_engine.overrides(direct_rows=-1, **plans):
+        stream = run_loop(hip_engine, s, "block")
     assert stream[3]["operand_form"] != "rows"
     assert np.all(np.isfinite(rows[0])) and rows[0][-1] < rows[0][0]
     for a, b in zip(rows[:3], stream[:3]):
@@ -183,21 +161,18 @@ def test_loop_with_full_row_blocks(hip_engine, overrides):
 
 @pytest.mark.parametrize("dim,n", [(3, 12), (2, 40)])
 @pytest.mark.parametrize("codes", [0, 1])
-def test_loop_in_two_parts_equals_the_uninterrupted_loop(hip_engine, overrides, systems, dim, n, codes):
+def test_loop_in_two_parts_equals_the_uninterrupted_loop(hip_engine, systems, dim, n, codes):
     """(0, 5), poll(), (5, 12): the poll applies the deferred velocity update, so C1 of iteration 5 finds nothing
     pending (its u0 is loaded and not used); iteration 0 takes the body of its own; the last poll flushes."""
-    lib = overrides
     s = systems[(dim, n)]
-    assert lib.nss_bpcg2_fuse_block_jacobi(0) == 0
-    assert lib.nss_csr_value_code_mode(codes) == 0
-    assert lib.nss_stream_loads_mode(1) == 0
-    assert lib.nss_csr_direct_rows_threshold(0) == 0
-    whole = run_loop(hip_engine, s, "block")
-    parts = run_loop(hip_engine, s, "block", chunks=((0, 5), (5, NIT)))
+    plans = dict(fuse_bjac=0, value_codes=codes, stream_loads=1)
+    with hip_engine.overrides(direct_rows=0, **plans):
+        whole = run_loop(hip_engine, s, "block")
+        parts = run_loop(hip_engine, s, "block", chunks=((0, 5), (5, NIT)))
     assert whole[3]["operand_form"] == "rows" and parts[3]["operand_form"] == "rows"
     for a, b in zip(parts[:3], whole[:3]):
         assert same_bits(a, b)
-    assert lib.nss_csr_direct_rows_threshold(-1) == 0
-    stream = run_loop(hip_engine, s, "block", chunks=((0, 5), (5, NIT)))
+    with hip_engine.overrides(direct_rows=-1, **plans):
+        stream = run_loop(hip_engine, s, "block", chunks=((0, 5), (5, NIT)))
     for a, b in zip(parts[:3], stream[:3]):
         assert same_bits(a, b)

@@ -167,11 +167,9 @@ def test_condensed_fused_forms_against_straightforward_sequence(hip_engine, dim,
     s = mac_stokes(dim, n, 0.01)
     f, g = s.rhs(0)
     blfA, blfB, preA, preM = _operands(s)
-    lib = hip_engine.lib
     applies, counts = {}, {}
-    try:
-        for mode in (1, 0):
-            hip_engine._check(lib.nss_cond_fuse_mode(mode))
+    for mode in (1, 0):
+        with hip_engine.overrides(cond_fuse=mode):
             with contextlib.redirect_stdout(io.StringIO()):
                 ses = BpcgSession(blfA, blfB, None, hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g), preA,
                                   preM, k=1.7)
@@ -184,8 +182,6 @@ def test_condensed_fused_forms_against_straightforward_sequence(hip_engine, dim,
             it, _, _, runs = _solve(s, blfA, blfB, preA, preM, 1e-9, 3000)
             assert runs == 1
             counts[mode] = it
-    finally:
-        hip_engine._check(lib.nss_cond_fuse_mode(0))            # the default
     scale = np.abs(applies[0]).max()
     assert scale > 0
     assert np.abs(applies[1] - applies[0]).max() <= 1e-13 * scale

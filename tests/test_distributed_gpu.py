@@ -434,33 +434,30 @@ def test_native_partitioned_minres_single_rank(hip_engine, tmp_path, pre):
     s = mac_stokes(3, 12, 0.01)
     f, g = s.rhs(0)
     tol, maxsteps = 1e-8, 4000
-    lib = hip_engine.lib
     dist.init_process_group("gloo", init_method="file://" + str(tmp_path / "rdv"), rank=0, world_size=1)
     try:
         comm = RcclComm(dist, hip_engine)
         # fuse mode 0: rows of B^T in their own launch half; 2: inside the launch of A's rows (round 3; the slab's
         # fixed-width copy of B^T indexes z1's [owned | ghosts] layout) -- the block Jacobi apart in both
         for fuse, native in ((0, True), (0, False), (2, True)):
-            assert lib.nss_minres_fold_mode(0) == 0 and lib.nss_minres_fuse_mode(fuse) == 0
-            ref = single_gpu_minres(s, pre, tol, maxsteps)
-            run = DistributedMinres(s, f, g, s.line_blocks(3) if pre == "bjac" else None, dist, hip_engine, comm=comm,
-                                    native=native)
-            assert (run.native is not None) == native
-            u, errors, rel = run.solve(tol=tol, maxsteps=maxsteps, poll_every=16)
-            assert rel
-            np.testing.assert_array_equal(np.array(errors), ref["errors"])
-            np.testing.assert_array_equal(u[0].numpy(), ref["u"])
-            np.testing.assert_array_equal(u[1].numpy(), ref["p"])
-            before = hip_engine.to_host(run.loop.scal).copy()
-            run._iterate(len(errors), len(errors) + 9)                  # after the stop: no-ops on the device
-            torch.cuda.synchronize()
-            np.testing.assert_array_equal(hip_engine.to_host(run.loop.scal), before)
-            np.testing.assert_array_equal(u[0].numpy(), ref["u"])
-            run.close()
+            with hip_engine.overrides(minres_fold=0, minres_fuse=fuse):
+                ref = single_gpu_minres(s, pre, tol, maxsteps)
+                run = DistributedMinres(s, f, g, s.line_blocks(3) if pre == "bjac" else None, dist, hip_engine, comm=comm,
+                                        native=native)
+                assert (run.native is not None) == native
+                u, errors, rel = run.solve(tol=tol, maxsteps=maxsteps, poll_every=16)
+                assert rel
+                np.testing.assert_array_equal(np.array(errors), ref["errors"])
+                np.testing.assert_array_equal(u[0].numpy(), ref["u"])
+                np.testing.assert_array_equal(u[1].numpy(), ref["p"])
+                before = hip_engine.to_host(run.loop.scal).copy()
+                run._iterate(len(errors), len(errors) + 9)                  # after the stop: no-ops on the device
+                torch.cuda.synchronize()
+                np.testing.assert_array_equal(hip_engine.to_host(run.loop.scal), before)
+                np.testing.assert_array_equal(u[0].numpy(), ref["u"])
+                run.close()
         comm.close()
     finally:
-        lib.nss_minres_fold_mode(-1)
-        lib.nss_minres_fuse_mode(-1)
         dist.destroy_process_group()
 
 
@@ -492,30 +489,29 @@ def test_native_partitioned_bpcg1_single_rank(hip_engine, tmp_path, pre):
         # (the single-GPU loop would plan A's row blocks around the Jacobi blocks and apply them in the epilogue of A's
         # rows: another partition of the partial sums of <d, t1>.  Held to the slab's launch plan for the bit comparison;
         # the merged rows of B^T stay on in both.)
-        assert hip_engine.lib.nss_bpcg2_fuse_block_jacobi(0) == 0
-        ref = single_gpu_bpcg1(s, pre, tol, maxsteps)
-        comm = RcclComm(dist, hip_engine)
-        ops = DistributedStokes(s, s.line_blocks(3) if pre == "bjac" else None, comm, hip_engine)
-        for native in (True, False):
-            distributed.Bpcg1DistLoop.NATIVE = native
-            fv, gv = ops.vectors(f, g)
-            with contextlib.redirect_stdout(io.StringIO()):
-                x, errors = bramble_pasciak_cg(ops.A, ops.B, None, ops.preA, ops.preM, fv, gv, tolerance=tol,
-                                               max_steps=maxsteps, print_rates=False)
-            run = loops[-1]
-            assert run is not None and (run.native is not None) == native
-            np.testing.assert_array_equal(np.array(errors), ref["errors"])
-            np.testing.assert_array_equal(x[0].numpy(), ref["u"])
-            np.testing.assert_array_equal(x[1].numpy(), ref["p"])
-            before = hip_engine.to_host(run.loop.scal).copy()
-            run.enqueue(len(errors), len(errors) + 9)                   # after the stop: no-ops on the device
-            torch.cuda.synchronize()
-            np.testing.assert_array_equal(hip_engine.to_host(run.loop.scal), before)
-            np.testing.assert_array_equal(x[0].numpy(), ref["u"])
-            run.close()
-        comm.close()
+        with hip_engine.overrides(fuse_bjac=0):
+            ref = single_gpu_bpcg1(s, pre, tol, maxsteps)
+            comm = RcclComm(dist, hip_engine)
+            ops = DistributedStokes(s, s.line_blocks(3) if pre == "bjac" else None, comm, hip_engine)
+            for native in (True, False):
+                distributed.Bpcg1DistLoop.NATIVE = native
+                fv, gv = ops.vectors(f, g)
+                with contextlib.redirect_stdout(io.StringIO()):
+                    x, errors = bramble_pasciak_cg(ops.A, ops.B, None, ops.preA, ops.preM, fv, gv, tolerance=tol,
+                                                   max_steps=maxsteps, print_rates=False)
+                run = loops[-1]
+                assert run is not None and (run.native is not None) == native
+                np.testing.assert_array_equal(np.array(errors), ref["errors"])
+                np.testing.assert_array_equal(x[0].numpy(), ref["u"])
+                np.testing.assert_array_equal(x[1].numpy(), ref["p"])
+                before = hip_engine.to_host(run.loop.scal).copy()
+                run.enqueue(len(errors), len(errors) + 9)                   # after the stop: no-ops on the device
+                torch.cuda.synchronize()
+                np.testing.assert_array_equal(hip_engine.to_host(run.loop.scal), before)
+                np.testing.assert_array_equal(x[0].numpy(), ref["u"])
+                run.close()
+            comm.close()
     finally:
-        hip_engine.lib.nss_bpcg2_fuse_block_jacobi(-1)
         distributed.Bpcg1DistLoop.NATIVE = True
         distributed.Bpcg1DistLoop.try_create = classmethod(orig)
         dist.destroy_process_group()

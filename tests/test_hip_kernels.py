@@ -173,7 +173,6 @@ def test_spmv_row_per_lane_kernel(hip_engine):
     by the row-per-lane kernel from a fixed-width copy: same bits as the stream kernel, empty and one-entry rows
     included; the threshold is a run-time knob so that small cases reach it."""
     import hipla
-    lib = hip_engine.lib
     s = mac_stokes(3, 14)
     bt = s.B.T.tocsr()
     rng = np.random.default_rng(8)
@@ -187,11 +186,8 @@ def test_spmv_row_per_lane_kernel(hip_engine):
         y0 = rng.standard_normal(mat.shape[0])
         out = {}
         for name, rows in (("stream", -1), ("rows", 0)):
-            assert lib.nss_csr_direct_rows_threshold(rows) == 0
-            try:
+            with hip_engine.overrides(direct_rows=rows):
                 M = hipla.SparseMatrix.from_scipy(mat)
-            finally:
-                lib.nss_csr_direct_rows_threshold(-1)
             assert (M.handle.info()["operand_form"] == "rows") == (name == "rows"), M.handle.info()
             X, Y = hipla.Vector.from_numpy(x), hipla.Vector.from_numpy(y0)
             hip_engine.csr_spmv(M.handle, -1.5, X.buf, 0.25, Y.buf)

@@ -411,12 +411,9 @@ def test_streaming_loads_do_not_change_a_bit(hip_engine, name):
     from bramble_pasciak_cg import bramble_pasciak_cg
     from minres import MinRes
     from solvers.bramblepasciak_new import BramblePasciakCG
-    lib = hip_engine.lib
     results = {}
-    assert lib.nss_csr_direct_rows_threshold(0) == 0
-    try:
-        for mode in (0, 1):
-            assert lib.nss_stream_loads_mode(mode) == 0
+    for mode in (0, 1):
+        with hip_engine.overrides(direct_rows=0, stream_loads=mode):
             for solver in ("bpcg2", "bpcg1", "minres"):
                 d = np.load(golden_path("%s_%s" % (name, solver)))
                 c, blfA, A, B, preA, preS = case_operands(d)
@@ -444,9 +441,6 @@ def test_streaming_loads_do_not_change_a_bit(hip_engine, name):
                 check = d["history"] if solver == "bpcg2" else d["errors"]
                 check_history(hist, check, d["window"])
                 results[mode, solver] = (hist, x)
-    finally:
-        lib.nss_stream_loads_mode(-1)
-        lib.nss_csr_direct_rows_threshold(-1)
     for solver in ("bpcg2", "bpcg1", "minres"):
         np.testing.assert_array_equal(results[1, solver][0], results[0, solver][0])
         np.testing.assert_array_equal(results[1, solver][1], results[0, solver][1])
@@ -462,11 +456,9 @@ def test_row_per_lane_kernel_in_the_fused_loops(hip_engine, name):
     from bramble_pasciak_cg import bramble_pasciak_cg
     from minres import MinRes
     from solvers.bramblepasciak_new import BramblePasciakCG
-    lib = hip_engine.lib
     results = {}
     for mode, rows in (("stream", -1), ("rows", 0)):
-        assert lib.nss_csr_direct_rows_threshold(rows) == 0
-        try:
+        with hip_engine.overrides(direct_rows=rows):
             for solver in ("bpcg2", "bpcg1", "minres"):
                 d = np.load(golden_path("%s_%s" % (name, solver)))
                 c, blfA, A, B, preA, preS = case_operands(d)
@@ -493,8 +485,6 @@ def test_row_per_lane_kernel_in_the_fused_loops(hip_engine, name):
                         hist, x = np.array(errors), u.numpy()
                 assert counts[solver] == 1
                 results[mode, solver] = (hist, x)
-        finally:
-            lib.nss_csr_direct_rows_threshold(-1)
     for solver in ("bpcg2", "bpcg1", "minres"):
         np.testing.assert_array_equal(results["rows", solver][0], results["stream", solver][0])
         np.testing.assert_array_equal(results["rows", solver][1], results["stream", solver][1])
@@ -515,7 +505,6 @@ def test_compact_plan_equals_eight_phase_form_bit_for_bit(hip_engine, case):
     d = np.load(golden_path(case))
     c, blfA, A, B, preA, preS = case_operands(d)
     s = c.system
-    lib = hip_engine.lib
 
     def run(form, nit, tol):
         sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
@@ -537,26 +526,23 @@ def test_compact_plan_equals_eight_phase_form_bit_for_bit(hip_engine, case):
         final = it_final if done else nit - 1
         return done, final, loop.history(final).copy(), sol.numpy(), hip_engine.to_host(loop.scal).copy()
 
-    try:
-        free = run("classic", 40, 0.0)
-        k_stop = int(np.argmin(free[2][:30]))              # the stop test fires first at this iteration ...
-        tol_stop = free[2][k_stop] * (1.0 + 1e-12) / float(d["err0"]) if k_stop > 0 else 0.0
-        for tol in (tol_stop, 0.0):
-            ref = run("classic", 40, tol)
-            if tol > 0.0:
-                assert ref[0] and 0 < ref[1] <= k_stop + 1, (ref[:2], k_stop)   # ... (tested one iteration late, :243-247)
-            assert np.all(np.isfinite(ref[2])) and len(ref[2]) == ref[1] + 1
-            for mode in (1, 0, -1):
-                assert lib.nss_bpcg2_fold_mode(mode) == 0
+    free = run("classic", 40, 0.0)
+    k_stop = int(np.argmin(free[2][:30]))              # the stop test fires first at this iteration ...
+    tol_stop = free[2][k_stop] * (1.0 + 1e-12) / float(d["err0"]) if k_stop > 0 else 0.0
+    for tol in (tol_stop, 0.0):
+        ref = run("classic", 40, tol)
+        if tol > 0.0:
+            assert ref[0] and 0 < ref[1] <= k_stop + 1, (ref[:2], k_stop)   # ... (tested one iteration late, :243-247)
+        assert np.all(np.isfinite(ref[2])) and len(ref[2]) == ref[1] + 1
+        for mode in (1, 0, -1):
+            with hip_engine.overrides(bpcg2_fold=mode):
                 got = run("compact", 40, tol)
-                assert got[0] == ref[0] and got[1] == ref[1], (mode, tol, got[:2], ref[:2])
-                np.testing.assert_array_equal(got[2], ref[2])           # history
-                np.testing.assert_array_equal(got[3], ref[3])           # solution
-                np.testing.assert_array_equal(got[4][:5], ref[4][:5])   # wd, as_s, wdn, alpha, beta
-        w = min(int(d["window"]), 40)
-        np.testing.assert_allclose(ref[2][:w], d["history"][:w], rtol=1e-8)
-    finally:
-        lib.nss_bpcg2_fold_mode(-1)
+            assert got[0] == ref[0] and got[1] == ref[1], (mode, tol, got[:2], ref[:2])
+            np.testing.assert_array_equal(got[2], ref[2])           # history
+            np.testing.assert_array_equal(got[3], ref[3])           # solution
+            np.testing.assert_array_equal(got[4][:5], ref[4][:5])   # wd, as_s, wdn, alpha, beta
+    w = min(int(d["window"]), 40)
+    np.testing.assert_allclose(ref[2][:w], d["history"][:w], rtol=1e-8)
 
 
 @pytest.mark.parametrize("dim,n,inflate,bs", [(3, 20, 1, 3), (2, 90, 1, 3), (2, 40, 1, 2), (2, 24, 4, 1), (3, 56, 1, 3)])
@@ -573,50 +559,46 @@ def test_block_jacobi_applied_in_the_epilogue_of_c1(hip_engine, dim, n, inflate,
     if inflate > 1:
         s = s.inflate(inflate)
     f, g = s.rhs(0)
-    lib = hip_engine.lib
     xp = hipla.Vector.from_numpy(np.random.default_rng(2).standard_normal(s.n_p))
     BT0 = hipla.SparseMatrix.from_scipy(s.B.T.tocsr())
     y0 = hipla.Vector(s.n_u)
     y0.data = BT0 * xp
 
     def run(fuse, blocks, nit=30):
-        hip_engine._check(lib.nss_bpcg2_fuse_block_jacobi(1 if fuse else 0))      # (-1, the default: by size)
-        A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
-        preA = hipla.BlockJacobi(A, blocks)
-        sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
-        with contextlib.redirect_stdout(io.StringIO()):
-            ses = BpcgSession(Form(A), Form(B), None, hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g), preA,
-                              hipla.DiagonalMatrix(1.0 / s.mass), sol=sol)
-        loop = ses.fused
-        ses.first_direction()
-        loop.start(ses.wdn, ses.err0, 0.0, True, nit)
-        loop.enqueue(0, nit)
-        loop.poll()
-        y = hipla.Vector(s.n_u)
-        y.data = ses.matBT * xp
-        assert loop.c1_applies_preA() == (bool(fuse) and loop.c1_applies_bjac)
-        return loop.history(nit - 1).copy(), sol.numpy(), y.numpy(), loop.c1_applies_bjac
+        with hip_engine.overrides(fuse_bjac=1 if fuse else 0):                      # (-1, the default: by size)
+            A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
+            preA = hipla.BlockJacobi(A, blocks)
+            sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
+            with contextlib.redirect_stdout(io.StringIO()):
+                ses = BpcgSession(Form(A), Form(B), None, hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g), preA,
+                                  hipla.DiagonalMatrix(1.0 / s.mass), sol=sol)
+            loop = ses.fused
+            ses.first_direction()
+            loop.start(ses.wdn, ses.err0, 0.0, True, nit)
+            loop.enqueue(0, nit)
+            loop.poll()
+            y = hipla.Vector(s.n_u)
+            y.data = ses.matBT * xp
+            assert loop.c1_applies_preA() == (bool(fuse) and loop.c1_applies_bjac)
+            return loop.history(nit - 1).copy(), sol.numpy(), y.numpy(), loop.c1_applies_bjac
 
-    try:
-        blocks = s.line_blocks(bs)
-        apart = run(False, blocks)
-        fused = run(True, blocks)
-        assert fused[3] and not apart[3]                     # (mode 0: B^T is not even re-planned)
-        np.testing.assert_array_equal(fused[2], y0.numpy())                  # (i)
-        np.testing.assert_array_equal(fused[0], apart[0])                    # (ii)
-        np.testing.assert_array_equal(fused[1], apart[1])
-        assert np.all(np.isfinite(fused[0])) and fused[0][-1] < fused[0][0]
-        if dim == 2 and n == 40:
-            rev = np.ascontiguousarray(np.asarray(blocks)[:, ::-1])          # any block numbering: taken in row order
-            a, b = run(False, rev), run(True, rev)
-            assert b[3] and not a[3]
-            np.testing.assert_array_equal(a[0], b[0])
-            np.testing.assert_array_equal(a[1], b[1])
-            fewer = np.ascontiguousarray(np.asarray(blocks)[:, :-1])         # (iii) a dof in no block: declined
-            declined = run(True, fewer)
-            assert not declined[3] and np.all(np.isfinite(declined[0]))
-    finally:
-        lib.nss_bpcg2_fuse_block_jacobi(-1)
+    blocks = s.line_blocks(bs)
+    apart = run(False, blocks)
+    fused = run(True, blocks)
+    assert fused[3] and not apart[3]                     # (mode 0: B^T is not even re-planned)
+    np.testing.assert_array_equal(fused[2], y0.numpy())                  # (i)
+    np.testing.assert_array_equal(fused[0], apart[0])                    # (ii)
+    np.testing.assert_array_equal(fused[1], apart[1])
+    assert np.all(np.isfinite(fused[0])) and fused[0][-1] < fused[0][0]
+    if dim == 2 and n == 40:
+        rev = np.ascontiguousarray(np.asarray(blocks)[:, ::-1])          # any block numbering: taken in row order
+        a, b = run(False, rev), run(True, rev)
+        assert b[3] and not a[3]
+        np.testing.assert_array_equal(a[0], b[0])
+        np.testing.assert_array_equal(a[1], b[1])
+        fewer = np.ascontiguousarray(np.asarray(blocks)[:, :-1])         # (iii) a dof in no block: declined
+        declined = run(True, fewer)
+        assert not declined[3] and np.all(np.isfinite(declined[0]))
 
 
 @pytest.mark.parametrize("dim,n,inflate", [(3, 16, 1), (2, 40, 1), (3, 6, 12)])
@@ -633,7 +615,6 @@ def test_pair_staged_operands_give_identical_bits(hip_engine, dim, n, inflate):
     if inflate > 1:
         s = s.inflate(inflate)
     f, g = s.rhs(0)
-    lib = hip_engine.lib
     x = hipla.Vector.from_numpy(np.random.default_rng(1).standard_normal(s.n_u))
     B0 = hipla.SparseMatrix.from_scipy(s.B)
     y0 = hipla.Vector(s.n_p)
@@ -656,13 +637,10 @@ def test_pair_staged_operands_give_identical_bits(hip_engine, dim, n, inflate):
         y.data = B * x                                  # the re-planned B, plain SpMV
         return loop.history(nit - 1).copy(), sol.numpy(), B.handle.info(), ses.matBT.handle.info(), y.numpy(), loop
 
-    try:
-        assert lib.nss_csr_pair_mode(0) == 0
+    with hip_engine.overrides(pair_stage=0):
         gathered = run()
-        assert lib.nss_csr_pair_mode(-1) == 0
+    with hip_engine.overrides(pair_stage=-1):
         paired = run()
-    finally:
-        lib.nss_csr_pair_mode(-1)
     np.testing.assert_array_equal(paired[4], y0.numpy())                 # (i)
     np.testing.assert_array_equal(gathered[4], y0.numpy())
     np.testing.assert_array_equal(paired[0], gathered[0])                # (ii) history
@@ -744,18 +722,14 @@ def test_two_launch_lanczos_step_for_small_systems(hip_engine):
     import scipy.sparse as sp
     import hipla
     from hipla import eigen
-    lib = hip_engine.lib
 
     def ritz(A, pre, mode, tol=1e-3, check_every=5):
-        hip_engine._check(lib.nss_lanczos_fold_mode(mode))
-        try:
+        with hip_engine.overrides(lanczos_fold=mode):
             start = A.CreateColVector()
             start.set_from(eigen.lanczos_start_values(0, len(start)))
             out = eigen._native_lanczos(A, pre, start, tol, 400, check_every)
             assert out is not None
             return out
-        finally:
-            hip_engine._check(lib.nss_lanczos_fold_mode(-1))
 
     for n in (10, 48):
         s = mac_stokes(3, n, 0.01)
@@ -803,48 +777,44 @@ def test_reuse_aware_dispatch_order_changes_no_bit(hip_engine):
     from solvers.bramblepasciak_new import BpcgSession
     s = mac_stokes(3, 40, 0.01)
     f, g = s.rhs(0)
-    lib = hip_engine.lib
     x = np.random.default_rng(1).standard_normal(s.n_u)
 
     def run(planes, nit=25):
-        assert lib.nss_csr_dispatch_mode(planes, 0, 5 if planes == 8 else 0) == 0
-        A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
-        ya, yb = hipla.Vector(s.n_u), hipla.Vector(s.n_p)
-        xv = hipla.Vector.from_numpy(x)
-        ya.data = A * xv
-        yb.data = B * xv
-        preA = hipla.BlockJacobi(A, s.line_blocks(3))
-        preS = hipla.DiagonalMatrix(1.0 / s.mass)
-        sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
-        with contextlib.redirect_stdout(io.StringIO()):
-            ses = BpcgSession(Form(A), Form(B), None, hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g), preA, preS,
-                              sol=sol)
-            ses.first_direction()
-            ses.fused.start(ses.wdn, ses.err0, 0.0, True, nit)
-            ses.fused.enqueue(0, nit)
-            ses.fused.poll()
-            K = hipla.BlockMatrix([[A, B.T], [B, None]])
-            Cm = hipla.BlockMatrix([[preA, None], [None, preS]])
-            u, errors = MinRes(mat=K, pre=Cm, rhs=hipla.BlockVector([hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g)]),
-                               maxsteps=nit, tol=0.0, printrates=False)
-        return dict(ya=ya.numpy(), yb=yb.numpy(), hist=ses.fused.history(nit - 1).copy(), sol=sol.numpy(),
-                    minres=np.array(errors), a=A.handle.info(), b=B.handle.info())
+        with hip_engine.overrides(dispatch=(planes, 0, 5 if planes == 8 else 0)):
+            A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
+            ya, yb = hipla.Vector(s.n_u), hipla.Vector(s.n_p)
+            xv = hipla.Vector.from_numpy(x)
+            ya.data = A * xv
+            yb.data = B * xv
+            preA = hipla.BlockJacobi(A, s.line_blocks(3))
+            preS = hipla.DiagonalMatrix(1.0 / s.mass)
+            sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
+            with contextlib.redirect_stdout(io.StringIO()):
+                ses = BpcgSession(Form(A), Form(B), None, hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g), preA, preS,
+                                  sol=sol)
+                ses.first_direction()
+                ses.fused.start(ses.wdn, ses.err0, 0.0, True, nit)
+                ses.fused.enqueue(0, nit)
+                ses.fused.poll()
+                K = hipla.BlockMatrix([[A, B.T], [B, None]])
+                Cm = hipla.BlockMatrix([[preA, None], [None, preS]])
+                u, errors = MinRes(mat=K, pre=Cm, rhs=hipla.BlockVector([hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g)]),
+                                   maxsteps=nit, tol=0.0, printrates=False)
+            return dict(ya=ya.numpy(), yb=yb.numpy(), hist=ses.fused.history(nit - 1).copy(), sol=sol.numpy(),
+                        minres=np.array(errors), a=A.handle.info(), b=B.handle.info())
 
-    try:
-        ref = run(0)
-        assert ref["a"]["dispatch_period"] == 0.0 and ref["a"]["operand_form"] == "staged"
-        np.testing.assert_allclose(ref["ya"], s.A @ x, rtol=1e-13, atol=1e-13)
-        for planes in (3, 8):
-            got = run(planes)
-            rows_per_block = s.n_u / got["a"]["row_blocks"]
-            slab = s.velocity_slab_offsets[1] - s.velocity_slab_offsets[0]
-            assert got["a"]["dispatch_planes"] == planes
-            assert abs(got["a"]["dispatch_period"] - slab / rows_per_block) < 0.05 * slab / rows_per_block + 2
-            for key in ("ya", "yb", "hist", "sol", "minres"):
-                np.testing.assert_array_equal(got[key], ref[key])
-        assert np.all(np.isfinite(ref["hist"]))
-    finally:
-        lib.nss_csr_dispatch_mode(-2, 0, 0)
+    ref = run(0)
+    assert ref["a"]["dispatch_period"] == 0.0 and ref["a"]["operand_form"] == "staged"
+    np.testing.assert_allclose(ref["ya"], s.A @ x, rtol=1e-13, atol=1e-13)
+    for planes in (3, 8):
+        got = run(planes)
+        rows_per_block = s.n_u / got["a"]["row_blocks"]
+        slab = s.velocity_slab_offsets[1] - s.velocity_slab_offsets[0]
+        assert got["a"]["dispatch_planes"] == planes
+        assert abs(got["a"]["dispatch_period"] - slab / rows_per_block) < 0.05 * slab / rows_per_block + 2
+        for key in ("ya", "yb", "hist", "sol", "minres"):
+            np.testing.assert_array_equal(got[key], ref[key])
+    assert np.all(np.isfinite(ref["hist"]))
 
 
 @pytest.mark.parametrize("case", ["stokes3d_n10_bjac_minres", "stokes2d_n24_jacobi_minres",
@@ -859,19 +829,15 @@ def test_minres_sum_placement_gives_identical_bits(hip_engine, case):
     c, _, A, B, preA, preS = case_operands(d)
     K = hipla.BlockMatrix([[A, B.T], [B, None]])
     Cm = hipla.BlockMatrix([[preA, None], [None, preS]])
-    lib = hip_engine.lib
     outs = []
-    try:
-        for mode in (1, 0):
-            assert lib.nss_minres_fold_mode(mode) == 0
+    for mode in (1, 0):
+        with hip_engine.overrides(minres_fold=mode):
             with contextlib.redirect_stdout(io.StringIO()), fused_loops_counted() as counts:
                 u, errors = MinRes(mat=K, pre=Cm, rhs=hipla.BlockVector([hipla.Vector.from_numpy(c.f),
                                                                          hipla.Vector.from_numpy(c.g)]),
                                    maxsteps=int(d["maxsteps"]), tol=float(d["tol"]), printrates=False)
             assert counts["minres"] == 1
             outs.append((np.array(errors), u.numpy()))
-    finally:
-        lib.nss_minres_fold_mode(-1)
     np.testing.assert_array_equal(outs[0][0], outs[1][0])
     np.testing.assert_array_equal(outs[0][1], outs[1][1])
     check_history(outs[0][0], d["errors"], d["window"])
@@ -891,18 +857,14 @@ def test_bpcg1_small_system_form_gives_identical_bits(hip_engine, case):
     d = np.load(golden_path(case))
     c, _, A, B, preA, preS = case_operands(d)
     fv, gv = hipla.Vector.from_numpy(c.f), hipla.Vector.from_numpy(c.g)
-    lib = hip_engine.lib
     outs = {}
-    try:
-        for mode in (0, 1):
-            assert lib.nss_bpcg1_fold_mode(mode) == 0
+    for mode in (0, 1):
+        with hip_engine.overrides(bpcg1_fold=mode):
             with contextlib.redirect_stdout(io.StringIO()), fused_loops_counted() as counts:
                 sol, errors = bramble_pasciak_cg(A, B, None, preA, preS, fv, gv, tolerance=float(d["tol"]),
                                                  max_steps=int(d["maxsteps"]), print_rates=False)
             assert counts["bpcg1"] == 1
             outs[mode] = (np.array(errors), sol.numpy())
-    finally:
-        lib.nss_bpcg1_fold_mode(-1)
     np.testing.assert_array_equal(outs[1][0], outs[0][0])
     np.testing.assert_array_equal(outs[1][1], outs[0][1])
     check_history(outs[1][0], d["errors"], d["window"])
@@ -925,19 +887,15 @@ def test_minres_merged_launches_give_identical_bits(hip_engine, case):
     c, _, A, B, preA, preS = case_operands(d)
     K = hipla.BlockMatrix([[A, B.T], [B, None]])
     Cm = hipla.BlockMatrix([[preA, None], [None, preS]])
-    lib = hip_engine.lib
     outs = {}
-    try:
-        for mode in (0, 2, 1):
-            assert lib.nss_minres_fuse_mode(mode) == 0
+    for mode in (0, 2, 1):
+        with hip_engine.overrides(minres_fuse=mode):
             with contextlib.redirect_stdout(io.StringIO()), fused_loops_counted() as counts:
                 u, errors = MinRes(mat=K, pre=Cm, rhs=hipla.BlockVector([hipla.Vector.from_numpy(c.f),
                                                                          hipla.Vector.from_numpy(c.g)]),
                                    maxsteps=int(d["maxsteps"]), tol=float(d["tol"]), printrates=False)
             assert counts["minres"] == 1
             outs[mode] = (np.array(errors), u.numpy())
-    finally:
-        lib.nss_minres_fuse_mode(-1)
     np.testing.assert_array_equal(outs[2][0], outs[0][0])
     np.testing.assert_array_equal(outs[2][1], outs[0][1])
     w = min(25, len(outs[1][0]), len(outs[0][0]))           # (rounding differences grow along a Krylov history)
@@ -1601,30 +1559,28 @@ def test_components_sharing_a_hierarchy_are_cycled_together(hip_engine):
     import hipla
     from solvers.bramblepasciak_new import BpcgSession
     from templates.NavierStokesSIMPLE_iterative import MypreA, auxiliary_space_preconditioner
-    lib = hip_engine.lib
-    try:
-        for dim, n, min_levels in ((2, 300, 3), (3, 40, 2)):
-            s = mac_stokes(dim, n, 0.01)
-            _, _, aux = auxiliary_space_preconditioner(s)
-            assert len(set(id(c) for c in aux.components)) == 1 and len(aux.components) == dim
-            assert len(aux.components[0].level_sizes) >= min_levels, aux.components[0].level_sizes
-            x = hipla.Vector.from_numpy(np.random.default_rng(3).standard_normal(s.n_u))
-            out = {}
-            for on in (0, 1):
-                hip_engine._check(lib.nss_amg_batch_components(on))
+    for dim, n, min_levels in ((2, 300, 3), (3, 40, 2)):
+        s = mac_stokes(dim, n, 0.01)
+        _, _, aux = auxiliary_space_preconditioner(s)
+        assert len(set(id(c) for c in aux.components)) == 1 and len(aux.components) == dim
+        assert len(aux.components[0].level_sizes) >= min_levels, aux.components[0].level_sizes
+        x = hipla.Vector.from_numpy(np.random.default_rng(3).standard_normal(s.n_u))
+        out = {}
+        for on in (0, 1):
+            with hip_engine.overrides(amg_batch=on):
                 y = hipla.Vector(s.n_u)
                 aux.Mult(x, y)
                 z = hipla.Vector.from_numpy(np.ones(s.n_u))
                 aux.MultAdd(0.5, x, z)
                 out[on] = (y.numpy(), z.numpy())
-            for a, b in zip(out[0], out[1]):
-                assert np.linalg.norm(a - b) <= 1e-13 * np.linalg.norm(a)
-            # ... and inside the fused loop (multiplicative MypreA: the term is applied to the residual between the sweeps)
-            f, g = s.rhs(0)
-            A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
-            hist = {}
-            for on in (0, 1):
-                hip_engine._check(lib.nss_amg_batch_components(on))
+        for a, b in zip(out[0], out[1]):
+            assert np.linalg.norm(a - b) <= 1e-13 * np.linalg.norm(a)
+        # ... and inside the fused loop (multiplicative MypreA: the term is applied to the residual between the sweeps)
+        f, g = s.rhs(0)
+        A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
+        hist = {}
+        for on in (0, 1):
+            with hip_engine.overrides(amg_batch=on):
                 preA = MypreA(None, Form(A), s.line_blocks(3), GS=True, aux=aux)
                 sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
                 with contextlib.redirect_stdout(io.StringIO()):
@@ -1636,10 +1592,8 @@ def test_components_sharing_a_hierarchy_are_cycled_together(hip_engine):
                 ses.fused.enqueue(0, 25)
                 ses.fused.poll()
                 hist[on] = ses.fused.history(24).copy()
-            np.testing.assert_allclose(hist[1], hist[0], rtol=1e-9)
-            assert hist[1][-1] < 1e-1 * hist[1][0]
-    finally:
-        lib.nss_amg_batch_components(1)
+        np.testing.assert_allclose(hist[1], hist[0], rtol=1e-9)
+        assert hist[1][-1] < 1e-1 * hist[1][0]
 
 
 def test_fused_cg_solver(hip_engine):

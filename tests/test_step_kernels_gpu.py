@@ -88,11 +88,8 @@ def upload(eng, mat, rows_form=False):
     import hipla
     if not rows_form:
         return hipla.SparseMatrix.from_scipy(mat)
-    assert eng.lib.nss_csr_direct_rows_threshold(0) == 0
-    try:
+    with eng.overrides(direct_rows=0):
         return hipla.SparseMatrix.from_scipy(mat)
-    finally:
-        eng.lib.nss_csr_direct_rows_threshold(-1)
 
 
 def flag(eng, value):

@@ -61,29 +61,15 @@ def expected_bytes(info):
     return index + nnz + DICT_BYTES * nblk + 4 * (m + 1) + 8 * n + 8 * m
 
 
-@pytest.fixture
-def value_codes_default(hip_engine):
-    """every test leaves the process-wide overrides at their defaults"""
-    lib = hip_engine.lib
-    try:
-        yield lib
-    finally:
-        lib.nss_csr_value_code_mode(-1)
-        lib.nss_csr_direct_rows_threshold(-1)
-        lib.nss_bpcg2_fuse_block_jacobi(-1)
-        lib.nss_stream_loads_mode(-1)
-
-
 # ---- 1. plain SpMV ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dim,n", [(3, 12), (2, 40)])
 @pytest.mark.parametrize("rows_kernel", [False, True])
-def test_plain_spmv_coded_equals_uncoded_twin(hip_engine, value_codes_default, dim, n, rows_kernel):
-    lib = value_codes_default
+def test_plain_spmv_coded_equals_uncoded_twin(hip_engine, dim, n, rows_kernel):
     s = mac_stokes(dim, n)
-    assert lib.nss_csr_direct_rows_threshold(0 if rows_kernel else -1) == 0
     for name, mat in (("A", s.A), ("B", s.B), ("BT", s.B.T.tocsr())):
         x, y0 = operands(mat)
-        plain, coded = upload(hip_engine, mat), upload(hip_engine, mat)
+        with hip_engine.overrides(direct_rows=0 if rows_kernel else -1):
+            plain, coded = upload(hip_engine, mat), upload(hip_engine, mat)
         assert coded.code_values()
         info = coded.info()
         assert info["value_bytes"] == info["nnz"] and plain.info()["value_bytes"] == 8 * info["nnz"]
@@ -94,7 +80,7 @@ def test_plain_spmv_coded_equals_uncoded_twin(hip_engine, value_codes_default, d
         assert same_bits(spmv(hip_engine, coded, x, y0), spmv(hip_engine, plain, x, y0)), name
 
 
-def test_coded_spmv_over_the_lanes_per_row_regimes_and_column_forms(hip_engine, value_codes_default):
+def test_coded_spmv_over_the_lanes_per_row_regimes_and_column_forms(hip_engine):
     """The coded stream kernel at every lanes-per-row value of the launch plan and in every column form (the loops only
     reach it with the short rows of the Stokes blocks): identical bits to the uncoded twin."""
     import lane_regimes
@@ -139,7 +125,7 @@ def distinct_patterns(csr):
 
 
 @pytest.mark.parametrize("case", ["256", "257", "signed_zeros", "long_row"])
-def test_dictionary_edges(hip_engine, value_codes_default, case):
+def test_dictionary_edges(hip_engine, case):
     rng = np.random.default_rng(7)
     long_row = None
     if case in ("256", "257"):
@@ -173,7 +159,7 @@ def test_dictionary_edges(hip_engine, value_codes_default, case):
 
 # ---- 3. set-up paths -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("how", ["round", "narrow"])
-def test_writers_of_the_values_drop_the_codes(hip_engine, value_codes_default, how):
+def test_writers_of_the_values_drop_the_codes(hip_engine, how):
     s = mac_stokes(2, 40)
     # values that are not fp32 numbers, so that the rounding changes them
     mat = sp.csr_matrix(s.A * (1.0 / 3.0))
@@ -190,42 +176,39 @@ def test_writers_of_the_values_drop_the_codes(hip_engine, value_codes_default, h
 
 
 @pytest.mark.parametrize("rows_kernel", [False, True])
-def test_replans_keep_the_codes(hip_engine, value_codes_default, rows_kernel):
+def test_replans_keep_the_codes(hip_engine, rows_kernel):
     import hipla
-    lib = value_codes_default
-    assert lib.nss_csr_direct_rows_threshold(0 if rows_kernel else -1) == 0
-    assert lib.nss_bpcg2_fuse_block_jacobi(1) == 0
-    s = mac_stokes(2, 40)
-    A = hipla.SparseMatrix.from_scipy(s.A)
-    B, BT = hipla.SparseMatrix.from_scipy(s.B), hipla.SparseMatrix.from_scipy(s.B.T.tocsr())
-    pre = hipla.BlockJacobi(A, s.line_blocks(2))
-    for mat, host, blocks in ((B, s.B, False), (BT, s.B.T.tocsr(), True)):
-        x, y0 = operands(host)
-        want = spmv(hip_engine, upload(hip_engine, host), x, y0)
-        h = mat.handle
-        assert h.code_values()
-        assert same_bits(spmv(hip_engine, h, x, y0), want)
-        gen = h.plan_generation()
-        if blocks:
-            assert h.plan_for_blocks(pre.handle)
-            assert h.plan_generation() != gen          # (it really was re-planned, the fixed-width copy rebuilt)
-        else:
-            h.plan_for_pairs()
-        info = h.info()
-        assert info["value_bytes"] == info["nnz"] and info["algorithmic_bytes"] == expected_bytes(info)
-        assert same_bits(spmv(hip_engine, h, x, y0), want)
-        assert same_bits(hip_engine.csr_to_host(h)[2], sp.csr_matrix(host).data)
+    with hip_engine.overrides(direct_rows=0 if rows_kernel else -1, fuse_bjac=1):
+        s = mac_stokes(2, 40)
+        A = hipla.SparseMatrix.from_scipy(s.A)
+        B, BT = hipla.SparseMatrix.from_scipy(s.B), hipla.SparseMatrix.from_scipy(s.B.T.tocsr())
+        pre = hipla.BlockJacobi(A, s.line_blocks(2))
+        for mat, host, blocks in ((B, s.B, False), (BT, s.B.T.tocsr(), True)):
+            x, y0 = operands(host)
+            want = spmv(hip_engine, upload(hip_engine, host), x, y0)
+            h = mat.handle
+            assert h.code_values()
+            assert same_bits(spmv(hip_engine, h, x, y0), want)
+            gen = h.plan_generation()
+            if blocks:
+                assert h.plan_for_blocks(pre.handle)
+                assert h.plan_generation() != gen          # (it really was re-planned, the fixed-width copy rebuilt)
+            else:
+                h.plan_for_pairs()
+            info = h.info()
+            assert info["value_bytes"] == info["nnz"] and info["algorithmic_bytes"] == expected_bytes(info)
+            assert same_bits(spmv(hip_engine, h, x, y0), want)
+            assert same_bits(hip_engine.csr_to_host(h)[2], sp.csr_matrix(host).data)
 
 
 # ---- 4. reporting --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rows_kernel", [False, True])
-def test_reported_bytes_of_a_coded_matrix(hip_engine, value_codes_default, rows_kernel):
-    lib = value_codes_default
-    assert lib.nss_csr_direct_rows_threshold(0 if rows_kernel else -1) == 0
+def test_reported_bytes_of_a_coded_matrix(hip_engine, rows_kernel):
     s = mac_stokes(3, 12)
     forms = set()
     for mat in (s.A, s.B, s.B.T.tocsr(), random_csr(np.random.default_rng(3), [1.0, 2.0, 4.0])):
-        h = upload(hip_engine, mat)
+        with hip_engine.overrides(direct_rows=0 if rows_kernel else -1):
+            h = upload(hip_engine, mat)
         before = h.info()
         assert before["value_bytes"] == 8 * before["nnz"]
         assert h.code_values()
@@ -234,17 +217,16 @@ def test_reported_bytes_of_a_coded_matrix(hip_engine, value_codes_default, rows_
         assert info["value_bytes"] == info["nnz"]
         assert info["algorithmic_bytes"] == expected_bytes(info)
         assert info["algorithmic_bytes"] < before["algorithmic_bytes"]
-        assert lib.nss_csr_value_code_mode(0) == 0                      # never: the kernels read the 8-byte values again
-        assert h.info() == before
-        assert lib.nss_csr_value_code_mode(-1) == 0
+        with hip_engine.overrides(value_codes=0):                       # never: the kernels read the 8-byte values again
+            assert h.info() == before
     assert ("rows" in forms) == rows_kernel
 
 
 # ---- 5. / 6. the loop ------------------------------------------------------------------------------------------------
-def run_bpcg(hip_engine, s, mode, pre, nit=30):
+def run_bpcg(s, pre, nit=30):
+    """(error history, u, p, what the three matrices report) of `nit` iterations with the overrides in force"""
     import hipla
     from solvers.bramblepasciak_new import BramblePasciakCG
-    assert hip_engine.lib.nss_csr_value_code_mode(mode) == 0
     A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
     preA = hipla.JacobiPreconditioner(A) if pre == "point" else hipla.BlockJacobi(A, s.line_blocks(3))
     f, g = s.rhs(0)
@@ -262,20 +244,17 @@ def run_bpcg(hip_engine, s, mode, pre, nit=30):
 @pytest.mark.parametrize("dim,n", [(3, 12), (2, 40)])
 @pytest.mark.parametrize("pre,fuse", [("block", 0), ("point", 0), ("block", 1)])
 @pytest.mark.parametrize("rows_kernel", [False, True])
-def test_loop_with_codes_equals_loop_without(hip_engine, value_codes_default, dim, n, pre, fuse, rows_kernel):
+def test_loop_with_codes_equals_loop_without(hip_engine, dim, n, pre, fuse, rows_kernel):
     """rows_kernel: B^T takes the row-per-lane kernel and C1 its streaming-load variant, as at the headline size"""
-    lib = value_codes_default
-    assert lib.nss_bpcg2_fuse_block_jacobi(fuse) == 0
-    if rows_kernel:
-        assert lib.nss_csr_direct_rows_threshold(0) == 0
-        assert lib.nss_stream_loads_mode(1) == 0
+    plans = dict(fuse_bjac=fuse, direct_rows=0, stream_loads=1) if rows_kernel else dict(fuse_bjac=fuse)
     s = mac_stokes(dim, n)
-    coded = run_bpcg(hip_engine, s, 1, pre)
-    assert lib.nss_csr_value_code_mode(1) == 0
+    with hip_engine.overrides(value_codes=1, **plans):
+        coded = run_bpcg(s, pre)
     for info in coded[3]:                                                # the coded run really was coded
         assert info["value_bytes"] == info["nnz"], info
     assert (coded[3][2]["operand_form"] == "rows") == rows_kernel
-    plain = run_bpcg(hip_engine, s, 0, pre)
+    with hip_engine.overrides(value_codes=0, **plans):
+        plain = run_bpcg(s, pre)
     for info in plain[3]:
         assert info["value_bytes"] == 8 * info["nnz"], info
     assert len(coded[0]) >= 30 and np.all(np.isfinite(coded[0])) and coded[0][-1] < coded[0][0]
@@ -283,15 +262,15 @@ def test_loop_with_codes_equals_loop_without(hip_engine, value_codes_default, di
         assert same_bits(a, b)
 
 
-def test_all_or_nothing(hip_engine, value_codes_default):
-    lib = value_codes_default
+def test_all_or_nothing(hip_engine):
     s = mac_stokes(3, 8).inflate(12)
     assert distinct_patterns(sp.csr_matrix(s.A)) > 256
-    forced = run_bpcg(hip_engine, s, 1, "point")
-    assert lib.nss_csr_value_code_mode(1) == 0
+    with hip_engine.overrides(value_codes=1):
+        forced = run_bpcg(s, "point")
     for info in forced[3]:                                               # A does not qualify: nobody is coded
         assert info["value_bytes"] == 8 * info["nnz"], info
-    plain = run_bpcg(hip_engine, s, 0, "point")
+    with hip_engine.overrides(value_codes=0):
+        plain = run_bpcg(s, "point")
     for a, b in zip(forced[:3], plain[:3]):
         assert same_bits(a, b)
     # B has few patterns but one column index per group of entries: the grouped kernels have no coded form, so it is

@@ -36,10 +36,9 @@ for dim, n in [(2, 60), (2, 120), (2, 183), (2, 300), (2, 577), (3, 40), (3, 68)
 
     best = {}
     for mode in (0, 1, -1):
-        eng.lib.nss_bpcg1_fold_mode(mode)
-        run(20)
-        best[mode] = min((run(k2) - run(k1)) / (k2 - k1) for _ in range(3)) * 1e6
-    eng.lib.nss_bpcg1_fold_mode(-1)
+        with eng.overrides(bpcg1_fold=mode):
+            run(20)
+            best[mode] = min((run(k2) - run(k1)) / (k2 - k1) for _ in range(3)) * 1e6
     print("%d-D n=%-4d %9d DoF: mode 0 %7.1f us / iteration | mode 1 %7.1f us | %+5.1f %%   (default rule: %.1f us)"
           % (dim, n, s.ndof, best[0], best[1], 100.0 * (best[1] / best[0] - 1.0), best[-1]))
     del preA, preS, A, B

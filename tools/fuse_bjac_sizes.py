@@ -30,28 +30,27 @@ for dim, n in CASES:
     f, g = s.rhs(0)
     A, B = hipla.SparseMatrix.from_scipy(s.A), hipla.SparseMatrix.from_scipy(s.B)
     sol = hipla.BlockVector([hipla.Vector(s.n_u), hipla.Vector(s.n_p)])
-    eng.lib.nss_bpcg2_fuse_block_jacobi(1)                 # (B^T is planned around the blocks at every size)
-    with contextlib.redirect_stdout(io.StringIO()):
-        ses = BpcgSession(Form(A), Form(B), None, hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g),
-                          hipla.BlockJacobi(A, s.line_blocks(3)), hipla.DiagonalMatrix(1.0 / s.mass), sol=sol)
-    loop = ses.fused
-    assert loop.c1_applies_bjac
-    ses.first_direction()
-    its = 2000 if s.ndof < 2e6 else 300
-    loop.start(ses.wdn, ses.err0, 0.0, True, 8 * its + 100)
-    loop.enqueue(0, 50)
+    with eng.overrides(fuse_bjac=1):                       # (B^T is planned around the blocks at every size)
+        with contextlib.redirect_stdout(io.StringIO()):
+            ses = BpcgSession(Form(A), Form(B), None, hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g),
+                              hipla.BlockJacobi(A, s.line_blocks(3)), hipla.DiagonalMatrix(1.0 / s.mass), sol=sol)
+        loop = ses.fused
+        assert loop.c1_applies_bjac
+        ses.first_direction()
+        its = 2000 if s.ndof < 2e6 else 300
+        loop.start(ses.wdn, ses.err0, 0.0, True, 8 * its + 100)
+        loop.enqueue(0, 50)
     best = {0: 1e9, 1: 1e9}
     it = 50
     for rep in range(3):
         for on in (0, 1):
-            eng.lib.nss_bpcg2_fuse_block_jacobi(on)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            loop.enqueue(it, it + its)
-            torch.cuda.synchronize()
-            best[on] = min(best[on], 1e6 * (time.perf_counter() - t0) / its)
-            it += its
-    eng.lib.nss_bpcg2_fuse_block_jacobi(-1)
+            with eng.overrides(fuse_bjac=on):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                loop.enqueue(it, it + its)
+                torch.cuda.synchronize()
+                best[on] = min(best[on], 1e6 * (time.perf_counter() - t0) / its)
+                it += its
     print("%d-D n=%-4d %9d DoF  folds sums %-5s: stand-alone apply %7.1f us / iteration | in C1 %7.1f us | %+5.1f %%"
           % (dim, n, s.ndof, bool(loop.folds_sums()), best[0], best[1], 100.0 * (best[1] / best[0] - 1.0))
           + ("   [default: in C1]" if loop.c1_applies_preA() else ""))

@@ -25,29 +25,28 @@ for name in (sys.argv[1:] or ["cfg2", "cfg3"]):
     pre = hipla.BlockJacobi(A, s.line_blocks(3))
     pa = fused.native_velocity_pre(pre)
     for mode, label in ((-1, "two-launch (by size)"), (0, "five-launch")):
-        eng.lib.nss_lanczos_fold_mode(mode)
-        st = eigen._LanczosState.get()()
-        st.A, st.pre_bjac, st.pre_scale, st.n = A.handle.ptr, pa.bjac.handle.ptr, float(pa.scale), s.n_u
-        vecs = [eng.zeros(s.n_u) for _ in range(6)]
-        vecs[0].copy_(torch.from_numpy(eigen.lanczos_start_values(0, s.n_u)))
-        for i in range(3):
-            st.v[i] = vecs[i].data_ptr()
-        st.z[0], st.z[1], st.p = vecs[3].data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr()
-        partials = fused.fit_partials(eng, st, eng.lib.nss_lanczos_workspace, ("A",))   # noqa: F841 (kept alive)
-        scal, ctrl, hist = eng.zeros(8), torch.zeros(4, dtype=torch.int32, device=eng.device), eng.zeros(2 * 1000)
-        st.scal, st.ctrl, st.hist = scal.data_ptr(), ctrl.data_ptr(), hist.data_ptr()
-        eng._check(eng.lib.nss_lanczos_start(C.byref(st), eng.stream))
-        eng._check(eng.lib.nss_lanczos_iterate(C.byref(st), 0, 50, eng.stream))
-        torch.cuda.synchronize()
-        N = 400
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        t0 = time.perf_counter()
-        eng._check(eng.lib.nss_lanczos_iterate(C.byref(st), 50, 50 + N, eng.stream))
-        t_host = time.perf_counter() - t0
-        e1.record()
-        torch.cuda.synchronize()
-        t_all = time.perf_counter() - t0
-        print("%s %-22s: host enqueue %.1f us/step, device %.1f us/step, wall %.1f us/step (stop flag %d)"
-              % (name, label, 1e6 * t_host / N, 1e3 * e0.elapsed_time(e1) / N, 1e6 * t_all / N, int(ctrl[0])))
-    eng.lib.nss_lanczos_fold_mode(-1)
+        with eng.overrides(lanczos_fold=mode):
+            st = eigen._LanczosState.get()()
+            st.A, st.pre_bjac, st.pre_scale, st.n = A.handle.ptr, pa.bjac.handle.ptr, float(pa.scale), s.n_u
+            vecs = [eng.zeros(s.n_u) for _ in range(6)]
+            vecs[0].copy_(torch.from_numpy(eigen.lanczos_start_values(0, s.n_u)))
+            for i in range(3):
+                st.v[i] = vecs[i].data_ptr()
+            st.z[0], st.z[1], st.p = vecs[3].data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr()
+            partials = fused.fit_partials(eng, st, eng.lib.nss_lanczos_workspace, ("A",))   # noqa: F841 (kept alive)
+            scal, ctrl, hist = eng.zeros(8), torch.zeros(4, dtype=torch.int32, device=eng.device), eng.zeros(2 * 1000)
+            st.scal, st.ctrl, st.hist = scal.data_ptr(), ctrl.data_ptr(), hist.data_ptr()
+            eng._check(eng.lib.nss_lanczos_start(C.byref(st), eng.stream))
+            eng._check(eng.lib.nss_lanczos_iterate(C.byref(st), 0, 50, eng.stream))
+            torch.cuda.synchronize()
+            N = 400
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            t0 = time.perf_counter()
+            eng._check(eng.lib.nss_lanczos_iterate(C.byref(st), 50, 50 + N, eng.stream))
+            t_host = time.perf_counter() - t0
+            e1.record()
+            torch.cuda.synchronize()
+            t_all = time.perf_counter() - t0
+            print("%s %-22s: host enqueue %.1f us/step, device %.1f us/step, wall %.1f us/step (stop flag %d)"
+                  % (name, label, 1e6 * t_host / N, 1e3 * e0.elapsed_time(e1) / N, 1e6 * t_all / N, int(ctrl[0])))

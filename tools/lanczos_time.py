@@ -25,18 +25,17 @@ for name in (sys.argv[1:] or ["cfg2", "cfg3", "cfg4"]):
     eng = hipla.get_engine()
     for mode in ("native", "five-launch", "protocol"):
         eigen.NATIVE = mode != "protocol"
-        eng.lib.nss_lanczos_fold_mode(0 if mode == "five-launch" else -1)     # native: the two-launch step by size
-        eigen.EigenValues_Preconditioner(mat=A, pre=pre, tol=1e-3)        # warm-up (workspaces, kernels)
-        best = 1e9
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            lams = eigen.EigenValues_Preconditioner(mat=A, pre=pre, tol=1e-3)
-            torch.cuda.synchronize()
-            best = min(best, time.perf_counter() - t0)
-        out[mode] = (best, len(lams), float(lams.min()), float(lams.max()))
+        with eng.overrides(lanczos_fold=0 if mode == "five-launch" else -1):   # native: the two-launch step by size
+            eigen.EigenValues_Preconditioner(mat=A, pre=pre, tol=1e-3)        # warm-up (workspaces, kernels)
+            best = 1e9
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                lams = eigen.EigenValues_Preconditioner(mat=A, pre=pre, tol=1e-3)
+                torch.cuda.synchronize()
+                best = min(best, time.perf_counter() - t0)
+            out[mode] = (best, len(lams), float(lams.min()), float(lams.max()))
     eigen.NATIVE = True
-    eng.lib.nss_lanczos_fold_mode(-1)
     (tn, kn, lo_n, hi_n), (tp, kp, lo_p, hi_p), (t5, k5, _, _) = out["native"], out["protocol"], out["five-launch"]
     print("%s (%d rows): device-resident %.1f ms (%d steps, %.1f us/step; five-launch steps only: %.1f ms, %d steps) | "
           "protocol %.1f ms (%d steps) | x %.2f | lambda_min rel. diff %.1e"

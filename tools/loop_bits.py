@@ -110,11 +110,8 @@ def lanczos_cases(hipla, fused, eng, out):
             if name in ("none", "amg"):
                 continue
             for mode in ((0, 1) if name == "bjac" else (0,)):        # block Jacobi: five-launch and two-launch step
-                eng._check(eng.lib.nss_lanczos_fold_mode(mode))
-                try:
+                with eng.overrides(lanczos_fold=mode):
                     got = lanczos_steps(fused, eigen, eng, A, pre)
-                finally:
-                    eng._check(eng.lib.nss_lanczos_fold_mode(-1))
                 for part, value in zip(("hist", "scal", "v0", "v1", "v2"), got):
                     out["lanczos_n%d_%s_fold%d_%s" % (n, name, mode, part)] = value
 
@@ -147,7 +144,7 @@ def stokes_cases(hipla, fused, eng, out, iterations=10):
     blocks = s.line_blocks(3)
     pres = {"jacobi": hipla.JacobiPreconditioner(A), "bjac": hipla.BlockJacobi(A, blocks),
             "bgs": hipla.BlockGaussSeidel(A, blocks)}
-    lib, kept, quiet = eng.lib, [], io.StringIO()
+    kept, quiet = [], io.StringIO()
 
     def rhs():
         return hipla.Vector.from_numpy(f), hipla.Vector.from_numpy(g)
@@ -155,9 +152,7 @@ def stokes_cases(hipla, fused, eng, out, iterations=10):
     for name, preA in pres.items():
         for mode in (0, 1):
             key = "%s_fold%d_" % (name, mode)
-            for setter in (lib.nss_minres_fold_mode, lib.nss_bpcg1_fold_mode, lib.nss_bpcg2_fold_mode):
-                eng._check(setter(mode))
-            try:
+            with eng.overrides(minres_fold=mode, bpcg1_fold=mode, bpcg2_fold=mode):
                 K = hipla.BlockMatrix([[A, B.T], [B, None]])
                 Cm = hipla.BlockMatrix([[preA, None], [None, preS]])
                 with contextlib.redirect_stdout(quiet), loop_kept(fused.MinresLoop, kept):
@@ -188,9 +183,6 @@ def stokes_cases(hipla, fused, eng, out, iterations=10):
                     tag = "bpcg2_" + form + "_" + key
                     out[tag + "hist"], out[tag + "x"] = loop.history(last).copy(), sol.numpy().copy()
                     out[tag + "scal"] = eng.to_host(loop.scal).copy()
-            finally:
-                for setter in (lib.nss_minres_fold_mode, lib.nss_bpcg1_fold_mode, lib.nss_bpcg2_fold_mode):
-                    setter(-1)
 
 
 def step_cases(hipla, out):
