@@ -790,6 +790,37 @@ NSS_API int nss_scalar_flux_limited_f64(const int32_t* stencil, int64_t nface, i
                                         const double* u, const double* f, const double* T, double t_ref, double* G,
                                         double* f_eff, const int32_t* done, nss_stream_t stream);
 
+/* ---- flux launches of the second-order IMEX step (CN-AB2) -------------------------------------------
+ * The four flux launches above with the two-step extrapolation in their epilogue.  Each takes its twin's arguments; the
+ * twin's output (flux, G) is now the history `prev` / `G_prev`, read and rewritten in place, and the extrapolated value
+ * the right-hand-side launch reads goes to `ext` / `G_ext`.  Per point r, with F the twin's flux (its bits):
+ *
+ *   ext[r] = w_new F + w_old prev[r];   prev[r] = F
+ *
+ * and for a buoyant scalar (w_b != NULL), with b = w_b[r] ((avg T)_r - t_ref), resp. w_b[r] ((T_lo + T_hi) / 2 - t_ref):
+ *
+ *   f_eff[r] = f[r] + w_new b + w_old b_prev[r];   b_prev[r] = b
+ *
+ * (w_new, w_old) is (1, 0) on a quantity's first step and (3/2, -1/2) afterwards.  w_old == 0 does not read the
+ * histories (they may hold anything, NaN included).  prev, ext (G_prev, G_ext, b_prev, f_eff) must not overlap one
+ * another, u or T (the limited scalar form does not know the length of T and compares its first entry only); w_b ==
+ * NULL reads no f and touches neither f_eff nor b_prev, which may then be NULL.  Everything else -- `done`, nflux == 0 /
+ * nface == 0, the two-entry rows, the 16-byte aligned stencil and its PRECONDITION -- as for the twins.  Bytes per
+ * point: the twin's + 16 (donor 96, limited 64; scalar 80 / 48), the buoyant scalar forms + 16 more for b_prev. */
+NSS_API int nss_step_flux_ab2_f64(nss_csr_t adv, nss_csr_t avg, nss_csr_t diff, const double* u, double w_new,
+                                  double w_old, double* prev, double* ext, const int32_t* done, nss_stream_t stream);
+NSS_API int nss_step_flux_limited_ab2_f64(nss_csr_t adv, const int32_t* stencil, int64_t nflux, int32_t limiter,
+                                          const double* u, double w_new, double w_old, double* prev, double* ext,
+                                          const int32_t* done, nss_stream_t stream);
+NSS_API int nss_scalar_flux_ab2_f64(nss_csr_t avg, nss_csr_t diff, const double* w_b, const double* u, const double* f,
+                                    const double* T, double t_ref, double w_new, double w_old, double* G_prev,
+                                    double* G_ext, double* b_prev, double* f_eff, const int32_t* done,
+                                    nss_stream_t stream);
+NSS_API int nss_scalar_flux_limited_ab2_f64(const int32_t* stencil, int64_t nface, int32_t limiter, const double* w_b,
+                                            const double* u, const double* f, const double* T, double t_ref,
+                                            double w_new, double w_old, double* G_prev, double* G_ext, double* b_prev,
+                                            double* f_eff, const int32_t* done, nss_stream_t stream);
+
 /* ---- device-resident heat exponential integrator -------------------------------------------------
  * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
  * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:

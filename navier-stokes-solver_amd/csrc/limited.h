@@ -35,4 +35,27 @@ __device__ __forceinline__ double limited_face(double a, const int4v& c, double 
   return a * (up + 0.5 * s);
 }
 
+// ---- what the limited launches and their extrapolating forms (limited.hip, ab2.hip) share ----
+// S1' runs grid-stride over at most this many workgroups, as S1 (scalar.hip): one pass covers 2^20 faces
+constexpr int kLimitedScalarBlocks = 4096;
+
+// A gather that no branch guards: an absent entry (-1) reads element 0, which exists, and its value is dropped in
+// registers.  Guarded by `c >= 0 ? q[c] : 0` every gather sits in a branch of its own, and the wait counts the compiler
+// can prove across those branches make the later gathers wait for the earlier ones.
+__device__ __forceinline__ int present(int32_t c) { return c < 0 ? 0 : c; }
+__device__ __forceinline__ double or_zero(int32_t c, double v) { return c >= 0 ? v : 0.0; }
+
+// All of a lane's loads are in flight before the first value is used.  Left alone the compiler sinks the far gathers
+// into the branch behind the sign of a and the presence of the far entry (seen in S1': ll and hh requested after u[r] had
+// arrived) -- the dependent second round of loads that DESIGN.md section 2 measured as the cost of the old SpMV.
+__device__ __forceinline__ void loads_in_flight(double a, double b, double c, double d, double e, double f = 0.0,
+                                                double g = 0.0) {
+  asm volatile("" ::"v"(a), "v"(b), "v"(c), "v"(d), "v"(e), "v"(f), "v"(g));
+}
+// (the extrapolating forms add the history reads: up to nine values)
+__device__ __forceinline__ void loads_in_flight(double a, double b, double c, double d, double e, double f, double g,
+                                                double h, double i) {
+  asm volatile("" ::"v"(a), "v"(b), "v"(c), "v"(d), "v"(e), "v"(f), "v"(g), "v"(h), "v"(i));
+}
+
 }  // namespace nss

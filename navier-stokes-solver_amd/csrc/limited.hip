@@ -12,23 +12,6 @@
 
 namespace nss {
 
-// S1' runs grid-stride over at most this many workgroups, as S1 (scalar.hip): one pass covers 2^20 faces
-constexpr int kLimitedScalarBlocks = 4096;
-
-// A gather that no branch guards: an absent entry (-1) reads element 0, which exists, and its value is dropped in
-// registers.  Guarded by `c >= 0 ? q[c] : 0` every gather sits in a branch of its own, and the wait counts the compiler
-// can prove across those branches make the later gathers wait for the earlier ones.
-__device__ __forceinline__ int present(int32_t c) { return c < 0 ? 0 : c; }
-__device__ __forceinline__ double or_zero(int32_t c, double v) { return c >= 0 ? v : 0.0; }
-
-// All of a lane's loads are in flight before the first value is used.  Left alone the compiler sinks the far gathers
-// into the branch behind the sign of a and the presence of the far entry (seen in S1': ll and hh requested after u[r] had
-// arrived) -- the dependent second round of loads that DESIGN.md section 2 measured as the cost of the old SpMV.
-__device__ __forceinline__ void loads_in_flight(double a, double b, double c, double d, double e, double f = 0.0,
-                                                double g = 0.0) {
-  asm volatile("" ::"v"(a), "v"(b), "v"(c), "v"(d), "v"(e), "v"(f), "v"(g));
-}
-
 // F1': one lane per flux point.  The stencil row and the two slots of adv are requested first, then all six gathers of
 // u -- the four stencil values whatever the sign of a, so that no load waits for a -- then the selection in registers.
 template <int LIM>

@@ -49,6 +49,11 @@ __device__ __forceinline__ double two_slot_sum(const int2v& c, const dbl2v& v, d
   return sum;
 }
 
+// the donor-cell flux of the three row sums, as step_flux_kernel and scalar_flux_kernel write it
+__device__ __forceinline__ double donor_flux(double adv, double avg, double dif) {
+  return fma(adv, avg, -0.5 * (fabs(adv) * dif));
+}
+
 // the stop test of a loop that freezes once one control word is set (cg, lanczos)
 struct StopWord {
   const int32_t* __restrict__ ctrl;

@@ -142,6 +142,10 @@ def _signatures():
         "nss_scalar_flux_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp]),
         "nss_step_flux_limited_f64": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, vp]),
         "nss_scalar_flux_limited_f64": (C.c_int, [vp, i64, i32, vp, vp, vp, vp, dbl, vp, vp, vp, vp]),
+        "nss_step_flux_ab2_f64": (C.c_int, [vp, vp, vp, vp, dbl, dbl, vp, vp, vp, vp]),
+        "nss_step_flux_limited_ab2_f64": (C.c_int, [vp, vp, i64, i32, vp, dbl, dbl, vp, vp, vp, vp]),
+        "nss_scalar_flux_ab2_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp]),
+        "nss_scalar_flux_limited_ab2_f64": (C.c_int, [vp, i64, i32, vp, vp, vp, vp, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         "nss_scalar_workspace": (C.c_int, [i64, c_i64_p]),
         "nss_scalar_update_f64": (C.c_int, [i64, dbl, vp, vp, vp, vp, i64, vp, vp]),
         "nss_scalar_record_f64": (C.c_int, [vp, i64, dbl, vp, i32, vp, vp]),

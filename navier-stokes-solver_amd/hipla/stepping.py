@@ -38,6 +38,41 @@ def check_convection(scheme, who):
     return scheme
 
 
+TIME_SCHEMES = ("euler", "cnab2")
+
+
+def check_time_scheme(scheme, who):
+    if scheme not in TIME_SCHEMES:
+        raise ValueError("%s: time_scheme is \"euler\" or \"cnab2\", not %r" % (who, scheme))
+    return scheme
+
+
+class TimeHistory:
+    """The two-step history of a `time_scheme="cnab2"` object, in flux form: `F_prev` (momentum flux, n_F), `G_prev`
+    (scalar flux, n_u) and `b_prev` (buoyancy force, n_u) as `Vector`s (None until the quantity has stepped), with one
+    "valid" flag per quantity -- a quantity without valid history takes the weights (1, 0), i.e. one Euler-extrapolated
+    step, a quantity with it (3/2, -1/2).  `DoTimeStep` and `Advance` read and write the same object."""
+
+    QUANTITIES = ("momentum", "scalar")
+
+    def __init__(self):
+        self.F_prev = self.G_prev = self.b_prev = None
+        self.valid = dict.fromkeys(self.QUANTITIES, False)
+
+    def weights(self, quantity):
+        return (1.5, -0.5) if self.valid[quantity] else (1.0, 0.0)
+
+    def reset(self, quantity=None):
+        for key in self.QUANTITIES if quantity is None else (quantity,):
+            self.valid[key] = False
+
+    def vector(self, name, n, engine):
+        """The history `Vector` `name` of length `n`, allocated (zero) on first use."""
+        if getattr(self, name) is None or len(getattr(self, name)) != n:
+            setattr(self, name, Vector(buf=engine.zeros(n), engine=engine))
+        return getattr(self, name)
+
+
 def upload_stencil(eng, stencil, n):
     """The (rows, 4) stencil of a limited flux launch as device int32 (16-byte aligned: a fresh allocation), after the
     range check the kernels leave to the caller: -1 <= entry < n."""
@@ -64,9 +99,15 @@ class ConvectiveFlux:
     """The convective flux of one transported quantity under one `scheme`: "upwind" launches the donor-cell kernel over
     two-slot copies of the operators, "minmod" / "vanleer" the limited kernel over the uploaded stencil (avg and diff are
     then not uploaded).  The device operands are looked up in, and left in, `shared` ("adv", "avg", "diff", "stencil"),
-    so that the objects of one system keep them once; `launch` is the package's one caller of the two `KERNELS`."""
+    so that the objects of one system keep them once; `launch` is the package's one caller of the two `KERNELS`,
+    `launch_ab2` of their extrapolating twins `KERNELS_AB2` (csrc/ab2.hip)."""
 
     avg = diff = stencil = None
+
+    @classmethod
+    def available_ab2(cls, eng, scheme):
+        """Whether the engine's library has the extrapolating kernel of `scheme`."""
+        return hasattr(getattr(eng, "lib", None), cls.KERNELS_AB2[scheme != "upwind"])
 
     @classmethod
     def available(cls, eng, scheme):
@@ -83,6 +124,7 @@ class MomentumFlux(ConvectiveFlux):
     """F1, from `system.convection_operators()` (`ops`: those, when the caller holds them) / `convection_stencil()`."""
 
     KERNELS = ("nss_step_flux_f64", "nss_step_flux_limited_f64")
+    KERNELS_AB2 = ("nss_step_flux_ab2_f64", "nss_step_flux_limited_ab2_f64")
 
     def __init__(self, eng, system, scheme, shared, ops=None):
         self.eng, self.scheme = eng, scheme
@@ -110,11 +152,21 @@ class MomentumFlux(ConvectiveFlux):
             eng._check(eng.lib.nss_step_flux_limited_f64(self.adv.handle.ptr, self.stencil.data_ptr(), self.nflux,
                                                          CONVECTION_SCHEMES[self.scheme], *tail))
 
+    def launch_ab2(self, u, weights, prev, ext):
+        """F = F(u);  ext = w_new F + w_old prev;  prev = F.  `weights` = (w_new, w_old); w_old == 0 reads no `prev`."""
+        eng, tail = self.eng, (u.data_ptr(), weights[0], weights[1], prev.data_ptr(), ext.data_ptr(), None, self.eng.stream)
+        if self.stencil is None:
+            eng._check(eng.lib.nss_step_flux_ab2_f64(self.adv.handle.ptr, self.avg.handle.ptr, self.diff.handle.ptr, *tail))
+        else:
+            eng._check(eng.lib.nss_step_flux_limited_ab2_f64(self.adv.handle.ptr, self.stencil.data_ptr(), self.nflux,
+                                                             CONVECTION_SCHEMES[self.scheme], *tail))
+
 
 class ScalarFlux(ConvectiveFlux):
     """S1, from avg and diff of `ops` = `StokesSystem.scalar_operators(...)` / the host array `scalar_stencil()`."""
 
     KERNELS = ("nss_scalar_flux_f64", "nss_scalar_flux_limited_f64")
+    KERNELS_AB2 = ("nss_scalar_flux_ab2_f64", "nss_scalar_flux_limited_ab2_f64")
 
     def __init__(self, eng, ops, scheme, stencil, shared):
         self.eng, self.scheme = eng, check_convection(scheme, "ScalarStepper")
@@ -144,6 +196,18 @@ class ScalarFlux(ConvectiveFlux):
             eng._check(eng.lib.nss_scalar_flux_limited_f64(self.stencil.data_ptr(), self.n_u,
                                                            CONVECTION_SCHEMES[self.scheme], *tail))
 
+    def launch_ab2(self, u, f, T, t_ref, weights, G_prev, G_ext, w_b=None, b_prev=None, f_eff=None):
+        """G = the flux of `T` carried by `u`;  G_ext = w_new G + w_old G_prev;  G_prev = G; with the weights `w_b` also
+        b = w_b (avg T - t_ref), f_eff = f + w_new b + w_old b_prev, b_prev = b.  `weights` = (w_new, w_old)."""
+        eng = self.eng
+        tail = (_ptr(w_b), u.data_ptr(), _ptr(f), T.data_ptr(), t_ref, weights[0], weights[1], G_prev.data_ptr(),
+                G_ext.data_ptr(), _ptr(b_prev), _ptr(f_eff), None, eng.stream)
+        if self.stencil is None:
+            eng._check(eng.lib.nss_scalar_flux_ab2_f64(self.avg.handle.ptr, self.diff.handle.ptr, *tail))
+        else:
+            eng._check(eng.lib.nss_scalar_flux_limited_ab2_f64(self.stencil.data_ptr(), self.n_u,
+                                                               CONVECTION_SCHEMES[self.scheme], *tail))
+
 
 class StepRecord:
     """What `NavierStokes.Advance` returns: one entry per step of `mstar_iterations`, `proj_iterations` (pseudo time
@@ -151,10 +215,11 @@ class StepRecord:
     step (both None with ``diagnostics=False``); `declined`: why the statements ran instead of the device-resident
     step (None when it ran); `flux_declined`: why the convection term ran through `ConvectionOperator`.  With a scalar
     (`NavierStokes.AddScalar`): `scalar_iterations` of the temperature solve and `wall_flux` = the heat entering through
-    its `flux_wall` after the step (None without a scalar / diagnostics).  `convection`: the momentum flux's scheme."""
+    its `flux_wall` after the step (None without a scalar / diagnostics).  `convection`: the momentum flux's scheme;
+    `time_scheme`: "euler" or "cnab2" (the pseudo time stepping is a relaxation and records "euler")."""
 
     def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
-                 scalar_iterations=None, wall_flux=None, convection="upwind"):
+                 scalar_iterations=None, wall_flux=None, convection="upwind", time_scheme="euler"):
         self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
         self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
         self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
@@ -162,6 +227,7 @@ class StepRecord:
         self.scalar_iterations = None if scalar_iterations is None else np.asarray(scalar_iterations, dtype=np.int64)
         self.wall_flux = wall_flux
         self.convection = convection
+        self.time_scheme = time_scheme
 
 
 class TimeStepper(FusedLoop):
@@ -172,7 +238,12 @@ class TimeStepper(FusedLoop):
     temp = f - A u - D F; raw = mstar^-1 temp (CG from zero); rhs = B raw; phi = (B M_u^-1 B^T)^-1 rhs (CG from zero); one
     launch over the rows of C = M_u^-1 B^T forms raw - C phi, u += timestep * that and the partials of <u, M_u u>; with
     diagnostics one launch over the rows of B gives the partials of |B u|^2 and one workgroup writes the step's record.
-    Every buffer is allocated here, once; the only host synchronisations of a step are the polls of the two solves."""
+    Every buffer is allocated here, once; the only host synchronisations of a step are the polls of the two solves.
+
+    `time_scheme="cnab2"` (second order): the operand is [u | F_ext | q] with the accumulated
+    pressure q, the flux launch is the extrapolating one (F_ext = w_new F + w_old F_prev, F_prev = F), one launch over the
+    rows of [A | D | B^T] forms temp = f - A u - D F_ext - B^T q, mstar is M_u + timestep/2 A, and one AXPY does
+    q += phi after the projection tail.  `advance` then takes the object's `TimeHistory`."""
 
     PRECISION, MAXSTEPS = (1e-4, 1e-8), (500, 5000)        # those of the template's CGSolvers invmstar / invproj
     momentum_flux = adv = avg = diff = stencil = None      # with `flux_declined`: no flux object, no flux operands
@@ -180,7 +251,7 @@ class TimeStepper(FusedLoop):
 
     @classmethod
     def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
-                   convection="upwind"):
+                   convection="upwind", time_scheme="euler"):
         """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
         `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
         solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
@@ -188,14 +259,18 @@ class TimeStepper(FusedLoop):
         device matrices that do not depend on `inner_pre` (mstar, Lp, C, adv, avg, diff, AD), so that the steppers of
         one system -- and a caller that already holds `M_u + timestep A`, `B M_u^-1 B^T`, `M_u^-1 B^T` and passes them
         under "mstar", "Lp", "C" -- keep them once.  `convection`: the scheme of F1 (`MomentumFlux`), "upwind" (donor
-        cell, first order) or the second-order limited "minmod" / "vanleer".  Returns None, the reason in `last_declined`."""
-        return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection))
+        cell, first order) or the second-order limited "minmod" / "vanleer".  `time_scheme`: "euler" or "cnab2"; a "cnab2"
+        stepper keeps its matrices under keys of their own ("mhalf", "ADBt") and declines when the flux kernel declines the
+        convection operators.  Returns None, the reason in `last_declined`."""
+        return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection,
+                                            time_scheme))
 
     @classmethod
-    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection):
+    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme):
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
         check_convection(convection, "TimeStepper")
+        check_time_scheme(time_scheme, "TimeStepper")
         if not fused.ENABLED:
             return "fused loops disabled (hipla.fused.ENABLED)"
         if not isinstance(A, SparseMatrix) or not isinstance(B, SparseMatrix) or not isinstance(f, Vector):
@@ -204,44 +279,60 @@ class TimeStepper(FusedLoop):
             return "not the HIP engine"
         if not MomentumFlux.available(A.engine, convection):
             return "the library has no limited flux kernel"
-        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, {} if shared is None else shared, convection)
+        shared = {} if shared is None else shared
+        if time_scheme == "cnab2":
+            if not MomentumFlux.available_ab2(A.engine, convection):
+                return "the library has no extrapolating flux kernel"
+            if "flux_declined" not in shared:
+                shared["flux_declined"] = MomentumFlux.declined(system.convection_operators())
+            if shared["flux_declined"] is not None:
+                return "cnab2: the flux kernel declines the convection operators: " + shared["flux_declined"]
+        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme)
 
-    def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind"):
+    def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind",
+                 time_scheme="euler"):
         import scipy.sparse as sp
         eng = self.eng = A.engine
+        self.time_scheme = time_scheme
+        cnab2 = time_scheme == "cnab2"
+        rows_key, mstar_key = ("ADBt", "mhalf") if cnab2 else ("AD", "mstar")
         self.lib, self.A, self.B, self.f, self.timestep = eng.lib, A, B, f, float(timestep)
         self.n_u, self.n_p = A.height, B.height
         m_u = np.asarray(m_u, dtype=np.float64)
         # ---- the convection term: the flux object of the scheme and the rows of [A | D] ----
         self.convection = convection
-        ops = None if {"flux_declined", "AD"} <= shared.keys() else system.convection_operators()
+        ops = None if {"flux_declined", rows_key} <= shared.keys() else system.convection_operators()
         if "flux_declined" not in shared:
             shared["flux_declined"] = MomentumFlux.declined(ops)
         self.flux_declined = shared["flux_declined"]
         if self.flux_declined is None:
             mf = self.momentum_flux = MomentumFlux(eng, system, convection, shared, ops)
-            if "AD" not in shared:
-                AD = sp.hstack([A.to_scipy(), ops["div"]], format="csr")
+            if rows_key not in shared:              # [A | D], or [A | D | B^T] over the operand [u | F_ext | q]
+                AD = sp.hstack([A.to_scipy(), ops["div"]] + ([B.to_scipy().T] if cnab2 else []), format="csr")
                 AD.sort_indices()
-                shared["AD"] = SparseMatrix.from_scipy(AD, engine=eng)
-            self.AD, self.conv = shared["AD"], None
+                shared[rows_key] = SparseMatrix.from_scipy(AD, engine=eng)
+            self.AD, self.conv = shared[rows_key], None
             self.adv, self.avg, self.diff, self.stencil, self.nflux = mf.adv, mf.avg, mf.diff, mf.stencil, mf.nflux
         else:
             self.conv = conv_operator()
-        self.uf = eng.zeros(self.n_u + self.nflux)          # the operand [u | F]
+        self.uf = eng.zeros(self.n_u + self.nflux + (self.n_p if cnab2 else 0))      # the operand [u | F] or [u | F_ext | q]
         self.u, self.F = eng.view(self.uf, 0, self.n_u), eng.view(self.uf, self.n_u, self.n_u + self.nflux)
+        if cnab2:
+            self.q = eng.view(self.uf, self.n_u + self.nflux, self.n_u + self.nflux + self.n_p)
+            self.F_prev = eng.zeros(max(1, self.nflux))
         self.temp, self.raw, self.temp2 = eng.zeros(self.n_u), eng.zeros(self.n_u), eng.zeros(self.n_u)
         self.rhs_p, self.phi = eng.zeros(self.n_p), eng.zeros(self.n_p)
         # ---- the inner solves ----
-        if "mstar" not in shared:
-            shared["mstar"] = SparseMatrix.from_scipy((sp.diags(m_u) + self.timestep * A.to_scipy()).tocsr(), engine=eng)
+        if mstar_key not in shared:                 # M_u + timestep A, or the half-step operator M_u + timestep/2 A
+            theta = 0.5 * self.timestep if cnab2 else self.timestep
+            shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(m_u) + theta * A.to_scipy()).tocsr(), engine=eng)
         if "C" not in shared:
             shared["C"] = SparseMatrix.from_scipy((sp.diags(1.0 / m_u) @ B.to_scipy().T).tocsr(), engine=eng)
         if "Lp" not in shared:
             lap_p = (B.to_scipy() @ shared["C"].to_scipy()).tocsr()
             lap_p.sort_indices()
             shared["Lp"] = SparseMatrix.from_scipy(lap_p, engine=eng)
-        self.mstar, self.Lp, self.C = shared["mstar"], shared["Lp"], shared["C"]
+        self.mstar, self.Lp, self.C = shared[mstar_key], shared["Lp"], shared["C"]
         if "singular" not in shared:
             ok, why = two_entry_rows(self.C.to_scipy())
             if not ok:
@@ -277,7 +368,10 @@ class TimeStepper(FusedLoop):
         eng, lib = self.eng, self.lib
         f = self.f.buf if f is None else f
         if self.flux_declined is None:
-            self.momentum_flux.launch(self.u, self.F)
+            if self.time_scheme == "cnab2":
+                self.momentum_flux.launch_ab2(self.u, self.weights, self.F_prev, self.F)
+            else:
+                self.momentum_flux.launch(self.u, self.F)
             eng._check(lib.nss_step_rhs_f64(self.AD.handle.ptr, self.uf.data_ptr(), f.data_ptr(),
                                             self.temp.data_ptr(), None, eng.stream))
             return
@@ -307,11 +401,13 @@ class TimeStepper(FusedLoop):
                                            self.n_div, self.energy_scale, record.data_ptr(), slot, None, eng.stream))
 
     def advance(self, gfu, gfup, nsteps, precision=None, maxsteps=None, diagnostics=True, pseudo=False, scalar=None,
-                temperature=None):
+                temperature=None, history=None):
         """`nsteps` steps on the velocity `gfu` (pressure-like potential of the last projection -> `gfup`).
         `precision` / `maxsteps`: one value for both inner solves, a pair (mstar, projection), or None = the template's.
         `scalar`: a `ScalarStepper` -- every step then begins with its flux launch on (u^n, T^n), the velocity step
-        takes its f_eff for f (a buoyant scalar), and its temperature step follows; `temperature`: the `Vector` of T."""
+        takes its f_eff for f (a buoyant scalar), and its temperature step follows; `temperature`: the `Vector` of T.
+        A "cnab2" stepper: `gfup` is the accumulated pressure q, copied into the operand on entry and out on exit, and
+        `history` the object's `TimeHistory`, copied in and out once (the valid flags are updated)."""
         self.precision = tuple(float(p) for p in pair(precision, self.PRECISION))
         self.maxsteps = tuple(int(m) for m in pair(maxsteps, self.MAXSTEPS))
         eng = self.eng
@@ -319,18 +415,34 @@ class TimeStepper(FusedLoop):
         nsteps = int(nsteps)
         if scalar is not None and pseudo:
             raise ValueError("advance: the pseudo time stepping carries no scalar")
+        cnab2 = self.time_scheme == "cnab2"
+        if cnab2 and (pseudo or history is None):
+            raise ValueError("advance: a \"cnab2\" stepper takes the object's history and does no pseudo time stepping")
+        if cnab2 and scalar is not None and scalar.time_scheme != "cnab2":
+            raise ValueError("advance: the scalar stepper is not a \"cnab2\" one")
         slots = max(1, nsteps)                 # the record: [2 slots] of the velocity | [slots] of the scalar
         record = eng.zeros((2 if scalar is None else 3) * slots) if diagnostics else None
         record_s = eng.view(record, 2 * slots, 3 * slots) if diagnostics and scalar is not None and scalar.records else None
         eng.copy(gfu.buf, self.u)
         if scalar is not None:
             eng.copy(temperature.buf, scalar.T)
+        if cnab2:
+            eng.copy(gfup.buf, self.q)
+            if history.valid["momentum"] and self.nflux:
+                eng.copy(history.F_prev.buf, eng.view(self.F_prev, 0, self.nflux))
+            if scalar is not None:
+                scalar.load_history(history)
         its_m, its_p, its_s = [], [], None if scalar is None else []
         if pseudo:
             self.project(self.u)                                          # :407  Project(gfu)
         for step in range(nsteps):
             if pseudo:
                 eng.csr_spmv(self.A.handle, -1.0, self.u, 0.0, self.temp)         # :411  temp = -A u
+            elif cnab2:
+                self.weights = history.weights("momentum") if step == 0 else (1.5, -0.5)
+                force = None if scalar is None else \
+                    scalar.flux_ab2(self.u, history.weights("scalar") if step == 0 else (1.5, -0.5))
+                self.right_hand_side(force)
             else:
                 self.right_hand_side(None if scalar is None else scalar.flux(self.u))     # (S1,) F1, F2  :429-431
             its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))   # :433
@@ -338,12 +450,21 @@ class TimeStepper(FusedLoop):
             if pseudo:
                 count += self.project(self.u, energy=diagnostics)                # :415  Project(gfu)
             its_p.append(count)
+            if cnab2:
+                eng.lincomb(self.q, [(1.0, self.q), (1.0, self.phi)])             # q += phi
             if diagnostics:
                 self.write_record(record, step)
             if scalar is not None:
                 its_s.append(scalar.step(record_s, step))                         # S2, the solve, S3, S4
         eng.copy(self.u, gfu.buf)
-        if nsteps or pseudo:
+        if cnab2 and nsteps:
+            eng.copy(self.q, gfup.buf)
+            if self.nflux:
+                eng.copy(eng.view(self.F_prev, 0, self.nflux), history.vector("F_prev", self.nflux, eng).buf)
+            history.valid["momentum"] = True
+            if scalar is not None:
+                scalar.store_history(history)
+        elif not cnab2 and (nsteps or pseudo):
             eng.copy(self.phi, gfup.buf)
         if scalar is not None:
             eng.copy(scalar.T, temperature.buf)
@@ -355,7 +476,7 @@ class TimeStepper(FusedLoop):
             if record_s is not None:
                 wall = host[2 * slots:][:nsteps].copy()
         return StepRecord(its_m, its_p, div, energy, flux_declined=self.flux_declined, convection=self.convection,
-                          scalar_iterations=its_s, wall_flux=wall)
+                          scalar_iterations=its_s, wall_flux=wall, time_scheme=self.time_scheme)
 
 
 class ScalarStepper:
@@ -366,18 +487,25 @@ class ScalarStepper:
     Per step: the flux launch on (u^n, T^n) writes G behind T in the operand buffer [T | G] (and f_eff); after the
     velocity step one launch over the rows of [K | B] forms temp_T = q - K T - B G; delta = (M_p + timestep K)^-1 temp_T
     (CG from zero); one launch does T += timestep delta with the partials of <w, T>, one workgroup writes the heat
-    entering through the flux wall, c0 - <w, T>.  Every buffer is allocated here, once (the cost in HBM: DESIGN.md 12)."""
+    entering through the flux wall, c0 - <w, T>.  Every buffer is allocated here, once (the cost in HBM: DESIGN.md 12).
+
+    `time_scheme="cnab2"`: the flux launch is the extrapolating one (G_ext behind T, f_eff = the force of the step, the
+    histories G_prev and b_prev), and the solve is with M_p + timestep/2 K (key "mhalf")."""
 
     PRECISION, MAXSTEPS = 1e-4, 500          # those of invmstar: the same kind of operator
 
     def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
-                 maxsteps=None, shared=None, convection="upwind", stencil=None):
+                 maxsteps=None, shared=None, convection="upwind", stencil=None, time_scheme="euler"):
         """`ops`: `StokesSystem.scalar_operators(...)`; `B`: the divergence (`SparseMatrix`); `f`: the force `Vector`
         the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
         (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
         `inner_pre`.  `convection`, `stencil`: the scheme of S1 and, for a limited one, `scalar_stencil()` (`ScalarFlux`)."""
         import scipy.sparse as sp
         shared = {} if shared is None else shared
+        self.time_scheme = check_time_scheme(time_scheme, "ScalarStepper")
+        cnab2 = time_scheme == "cnab2"
+        if cnab2 and not ScalarFlux.available_ab2(eng, convection):
+            raise ValueError("ScalarStepper: the library has no extrapolating flux kernel")
         self.eng, self.lib, self.f, self.timestep, self.t_ref = eng, eng.lib, f, float(timestep), float(t_ref)
         self.n_u, self.n_p = ops["avg"].shape
         self.precision = self.PRECISION if precision is None else float(precision)
@@ -388,15 +516,21 @@ class ScalarStepper:
             KB = sp.hstack([ops["K"], B.to_scipy()], format="csr")
             KB.sort_indices()
             shared["KB"] = SparseMatrix.from_scipy(KB, engine=eng)
-            shared["mstar"] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + self.timestep * ops["K"]).tocsr(), engine=eng)
             shared["q"] = eng.from_host(np.asarray(ops["q"], dtype=np.float64))
             shared["w_b"] = None if w_b is None else eng.from_host(np.asarray(w_b, dtype=np.float64))
             shared["w"] = None if flux is None else eng.from_host(np.asarray(flux[1], dtype=np.float64))
-        self.KB, self.mstar, self.q, self.w_b, self.w = (shared[key] for key in ("KB", "mstar", "q", "w_b", "w"))
+        mstar_key = "mhalf" if cnab2 else "mstar"
+        if mstar_key not in shared:                 # M_p + timestep K, or the half-step operator M_p + timestep/2 K
+            theta = 0.5 * self.timestep if cnab2 else self.timestep
+            shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + theta * ops["K"]).tocsr(), engine=eng)
+        self.KB, self.mstar, self.q, self.w_b, self.w = (shared[key] for key in ("KB", mstar_key, "q", "w_b", "w"))
         self.c0, self.records = (0.0 if flux is None else float(flux[0])), flux is not None
         self.tg = eng.zeros(self.n_p + self.n_u)             # the operand [T | G]
         self.T, self.G = eng.view(self.tg, 0, self.n_p), eng.view(self.tg, self.n_p, self.n_p + self.n_u)
         self.f_eff = None if w_b is None else eng.zeros(self.n_u)
+        if cnab2:
+            self.G_prev = eng.zeros(self.n_u)
+            self.b_prev = None if w_b is None else eng.zeros(self.n_u)
         self.temp, self.delta = eng.zeros(self.n_p), eng.zeros(self.n_p)
         self.pre = SmoothedAggregationAMG(self.mstar) if inner_pre == "amg" else JacobiPreconditioner(self.mstar)
         self.cg = CgLoop(eng, self.mstar, pre_for("cg", self.pre))
@@ -409,6 +543,24 @@ class ScalarStepper:
         """S1 on (u, T): G, and for a buoyant scalar f_eff.  Returns the force buffer of the velocity step (None: f)."""
         self.scalar_flux.launch(u, self.f.buf, self.T, self.t_ref, self.G, self.w_b, self.f_eff)
         return self.f_eff
+
+    def flux_ab2(self, u, weights):
+        """S1 of a "cnab2" step: G_ext behind T, the histories, and for a buoyant scalar the force of the step in f_eff."""
+        self.scalar_flux.launch_ab2(u, self.f.buf, self.T, self.t_ref, weights, self.G_prev, self.G, self.w_b, self.b_prev,
+                                    self.f_eff)
+        return self.f_eff
+
+    def load_history(self, history):
+        if history.valid["scalar"]:
+            self.eng.copy(history.G_prev.buf, self.G_prev)
+            if self.b_prev is not None:
+                self.eng.copy(history.b_prev.buf, self.b_prev)
+
+    def store_history(self, history):
+        self.eng.copy(self.G_prev, history.vector("G_prev", self.n_u, self.eng).buf)
+        if self.b_prev is not None:
+            self.eng.copy(self.b_prev, history.vector("b_prev", self.n_u, self.eng).buf)
+        history.valid["scalar"] = True
 
     def step(self, record, slot):
         """S2, the solve, S3 and (with `record`) S4.  Returns the CG iterations."""

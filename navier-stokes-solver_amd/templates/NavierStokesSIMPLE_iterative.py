@@ -28,6 +28,9 @@ reference's orchestration restated on the staggered-grid operators: ``invmstar``
 convection term ``conv_operator * gfu`` (:106-113,427-431): conservative upwind fluxes
 (``ConvectionOperator``: three SpMVs, the donor-cell flux kernel, one SpMV), or with
 ``NavierStokes(..., convection="minmod" | "vanleer")`` second-order limited upwind fluxes (one stencil launch, one SpMV).
+``NavierStokes(..., time_scheme="cnab2")`` makes the step second order in time (not in the reference): Crank-Nicolson
+for the viscous term, two-step Adams-Bashforth for convection and buoyancy, an incremental pressure in ``gfup``
+(`NavierStokes._do_time_step_cnab2`).
 
 Out of scope: the MCS/HDG assembly itself and the sparse direct branch
 ``iterative=False`` (raises ``NotImplementedError``)."""
@@ -37,7 +40,8 @@ import scipy.sparse as sp
 
 import hipla
 from hipla import BlockVector, CGSolver, fused
-from hipla.stepping import MomentumFlux, ScalarFlux, ScalarStepper, StepRecord, TimeStepper, check_convection, pair
+from hipla.stepping import (MomentumFlux, ScalarFlux, ScalarStepper, StepRecord, TimeHistory, TimeStepper,
+                            check_convection, check_time_scheme, pair)
 from discretizations import AssembledForm, CondensedForm, SyntheticMesh, assemble, bdm_hybrid
 from solvers.bramblepasciak_new import BramblePasciakCG
 
@@ -80,6 +84,24 @@ class ConvectionOperator(hipla.BaseMatrix):
 
     def Width(self):
         return self.n
+
+    def Flux(self, x, flux):
+        """flux = F(x), the flux vector (length n_F) before ``-D``: ``Mult`` is ``y = -D F(x)``.  The second-order time
+        stepping keeps its history in this form."""
+        if self.scheme != "upwind":
+            if self.flux is None:
+                from staggered_grid import limited_flux
+                stencil, adv, _ = self.system._limited_tables()
+                u = x.numpy()
+                flux.data = hipla.Vector.from_numpy(limited_flux(stencil, adv @ u, u, self.scheme))
+                return
+            self.flux.launch(x.buf, flux.buf)
+            return
+        adv, avg, diff, _ = self._work
+        adv.data = self.adv * x
+        avg.data = self.avg * x
+        diff.data = self.diff * x
+        flux.engine.upwind_flux(adv.buf, avg.buf, diff.buf, flux.buf)
 
     def Mult(self, x, y):
         if self.scheme != "upwind":
@@ -170,8 +192,9 @@ class ScalarField:
     `hipla.stepping.ScalarStepper` is made from."""
 
     def __init__(self, system, b_mat, timestep, kappa, dirichlet, buoyancy, t_ref, precision, maxsteps, flux_wall,
-                 convection="upwind"):
+                 convection="upwind", time_scheme="euler"):
         self.convection = check_convection(convection, "AddScalar")
+        self.time_scheme = time_scheme
         self.ops = ops = system.scalar_operators(kappa, dirichlet)
         self.stencil = system.scalar_stencil() if convection != "upwind" else None    # host array; uploaded on first use
         self.device_flux = None           # the `ScalarFlux` of `DoTimeStep`'s limited G, over `shared`
@@ -188,6 +211,11 @@ class ScalarField:
         self.mstar = hipla.SparseMatrix.from_scipy((sp.diags(ops["mass"]) + timestep * ops["K"]).tocsr())
         self.inv = CGSolver(self.mstar, pre=hipla.JacobiPreconditioner(self.mstar), precision=self.precision,
                             maxsteps=self.maxsteps)
+        if time_scheme == "cnab2":        # the half-step operator M_p + timestep/2 K, next to mstar
+            self.mhalf = hipla.SparseMatrix.from_scipy((sp.diags(ops["mass"]) + 0.5 * timestep * ops["K"]).tocsr())
+            self.inv_half = CGSolver(self.mhalf, pre=hipla.JacobiPreconditioner(self.mhalf), precision=self.precision,
+                                     maxsteps=self.maxsteps)
+            self.G_ext, self.b = self.avg.CreateColVector(), self.avg.CreateColVector()
         self.Wb = None if self.w_b is None else hipla.DiagonalMatrix(self.w_b)
         self.tref_u = hipla.Vector.from_numpy(np.full(system.n_u, self.t_ref))
         self.w = None if self.flux is None else hipla.Vector.from_numpy(self.flux[1])
@@ -195,18 +223,39 @@ class ScalarField:
         self.temp, self.delta = b_mat.CreateColVector(), b_mat.CreateColVector()
         self.steppers, self.shared = {}, {}
 
+    @property
+    def solver(self):
+        """The CG inverse of the scheme's operator: M_p + timestep K, or M_p + timestep/2 K."""
+        return self.inv_half if self.time_scheme == "cnab2" else self.inv
+
     def wall_flux(self, temperature):
         """The heat entering through `flux_wall`: c0 - <w, T>."""
         return self.flux[0] - float(hipla.InnerProduct(self.w, temperature))
 
 
 class NavierStokes:
-    def __init__(self, mesh, nu, inflow, outflow, wall, uin, timestep, order=2, volumeforce=None, convection="upwind"):
+    def __init__(self, mesh, nu, inflow, outflow, wall, uin, timestep, order=2, volumeforce=None, time_scheme="euler",
+                 convection="upwind"):
         """`convection`: the scheme of the explicit convection term in `DoTimeStep` and `Advance` -- "upwind" (donor
         cell, first order: numerical viscosity about |u| h / 2) or the second-order limited "minmod" / "vanleer"
         (`staggered_grid.limited_flux`; first order remains at the one flux point per grid line and direction next to
-        each wall).  Explicit Euler with the limiters wants timestep * sum_faces |u_f| / h <= 1/2 per cell."""
+        each wall).  Explicit Euler with the limiters wants timestep * sum_faces |u_f| / h <= 1/2 per cell.
+
+        `time_scheme`: "euler" (the reference's step: explicit Euler convection and buoyancy, backward Euler viscosity,
+        a non-incremental projection -- first order in time) or "cnab2" (second order: Adams-Bashforth 2 extrapolation
+        of the convective flux and the buoyancy, Crank-Nicolson viscosity and diffusion, an incremental projection whose
+        accumulated pressure lives in `gfup`, in the sign convention `SolveInitial` leaves there).  `DoTimeStep`,
+        `Advance` and `AddScalar` follow it; `Advance(pseudo=True)` and `SolveInitial(timesteps=)` are a relaxation and
+        ignore it.  "cnab2" keeps a two-step history (`F_prev`, `G_prev`, `b_prev`, `ResetTimeHistory`) and tolerates a
+        smaller convective CFL number than "euler" (README).  Pass `time_scheme` and `convection` by keyword: the
+        one stands in front of the other only because `convection` is pinned as the last parameter.  The inner solvers
+        keep their defaults: the 1e-4 of the velocity solve puts a floor under the accuracy of a step, and second order
+        shows only with `precision` (of `Advance`, of `AddScalar`) at or below the accuracy wanted."""
         self.convection = check_convection(convection, "NavierStokes")
+        self.time_scheme = check_time_scheme(time_scheme, "NavierStokes")
+        self._history = TimeHistory() if time_scheme == "cnab2" else None
+        self.last_stages = None
+        self._stepping_cnab2 = None       # the operators "cnab2" adds to `_time_stepping_operators`, built on first use
         self.mesh, self.nu, self.timestep, self.order = mesh, nu, timestep, order
         self.inflow, self.outflow, self.wall, self.uin = inflow, outflow, wall, uin
         self.V, self.Q = bdm_hybrid(order, 10)[0](mesh, velocity_dirichlet=inflow + "|" + wall)
@@ -246,6 +295,44 @@ class NavierStokes:
             self._stepping = dict(invmstar=invmstar, invproj=invproj, correct=hipla.SparseMatrix.from_scipy(bt_scaled),
                                   mstar=mstar, Lp=Lp)
         return self._stepping
+
+    def _cnab2_operators(self):
+        """What `time_scheme="cnab2"` adds to `_time_stepping_operators`: mhalf = M_u + timestep/2 A with its CG inverse
+        (the precision and maxsteps of invmstar), D (the flux divergence) and B^T."""
+        if self._stepping_cnab2 is None:
+            s = self.system
+            m_u = np.full(s.n_u, s.h ** s.dim * self.V.dofs_per_site ** 0)
+            mhalf = hipla.SparseMatrix.from_scipy((sp.diags(m_u) + 0.5 * self.timestep * s.A).tocsr())
+            invmhalf = CGSolver(mhalf, pre=hipla.JacobiPreconditioner(mhalf), precision=1e-4, maxsteps=500)
+            self._stepping_cnab2 = dict(mhalf=mhalf, invmhalf=invmhalf,
+                                        div=hipla.SparseMatrix.from_scipy(s.convection_operators()["div"]),
+                                        Bt=hipla.SparseMatrix.from_scipy(s.B.T.tocsr()))
+        return self._stepping_cnab2
+
+    def _momentum_solver(self, pseudo=False):
+        """(dict, key) of the CG inverse of the velocity solve: invmstar, or invmhalf of a "cnab2" step."""
+        if self.time_scheme == "cnab2" and not pseudo:
+            return self._cnab2_operators(), "invmhalf"
+        return self._time_stepping_operators(), "invmstar"
+
+    # ---- the two-step history of "cnab2" (None / False for "euler") ----
+    @property
+    def F_prev(self):
+        return None if self._history is None else self._history.F_prev
+
+    @property
+    def G_prev(self):
+        return None if self._history is None else self._history.G_prev
+
+    @property
+    def b_prev(self):
+        return None if self._history is None else self._history.b_prev
+
+    def ResetTimeHistory(self):
+        """Forget the two-step history: the next step of every quantity extrapolates with (1, 0), as a first step
+        does.  The accumulated pressure in `gfup` is left alone.  (For "euler" there is nothing to forget.)"""
+        if self._history is not None:
+            self._history.reset()
 
     @property
     def velocity(self):
@@ -330,10 +417,14 @@ class NavierStokes:
         n_p cell values (None: `t_ref` everywhere).  `precision` / `maxsteps` of the temperature solve: None = those of
         invmstar (1e-4, 500).  `flux_wall`: the Dirichlet wall whose heat flux `Advance` records (None: the first one
         given).  `convection`: the scheme of G, "upwind" | "minmod" | "vanleer" as for the constructor (None: the
-        velocity's).  The scalar is `self.temperature`; `AddForce` keeps working: f is read every step."""
+        velocity's).  The scalar is `self.temperature`; `AddForce` keeps working: f is read every step.  The scalar
+        follows the object's `time_scheme`; added after some steps it starts with the weights (1, 0) of a first step."""
         dirichlet = dict(dirichlet or {})
         self._scalar = ScalarField(self.system, self.b.mat, self.timestep, kappa, dirichlet, buoyancy, t_ref, precision,
-                                   maxsteps, flux_wall, self.convection if convection is None else convection)
+                                   maxsteps, flux_wall, self.convection if convection is None else convection,
+                                   self.time_scheme)
+        if self._history is not None:
+            self._history.reset("scalar")
         start = np.full(self.system.n_p, float(t_ref)) if initial is None else np.asarray(initial, dtype=np.float64)
         if start.shape != (self.system.n_p,):
             raise ValueError("AddScalar: initial holds %s values, the grid has %d cells" % (start.shape, self.system.n_p))
@@ -381,6 +472,8 @@ class NavierStokes:
         """One IMEX step (:424-438): temp = conv(u) + f - A u;  temp2 = invmstar temp;
         Project(temp2);  u += timestep * temp2.  With a scalar (`AddScalar`) its flux and force statements come first
         and its own step last."""
+        if self.time_scheme == "cnab2":
+            return self._do_time_step_cnab2()
         ops = self._time_stepping_operators()
         force = self.f.vec if self._scalar is None else self._scalar_flux()
         temp = self.a.mat.CreateColVector()
@@ -393,6 +486,77 @@ class NavierStokes:
         self.gfu.data += self.timestep * temp2
         if self._scalar is not None:
             self._scalar_step()
+
+    def _extrapolate(self, now, prev, weights, out):
+        """out = w_new now + w_old prev;  prev = now  (w_old == 0: `prev` is not read)."""
+        w_new, w_old = weights
+        if w_old:
+            out.data = w_new * now + w_old * prev
+        else:
+            out.data = w_new * now
+        prev.data = now
+
+    def _do_time_step_cnab2(self):
+        """One step of `time_scheme="cnab2"`, with (w_new, w_old) = (1, 0) on a quantity's first step and (3/2, -1/2)
+        afterwards and q = `gfup`, the accumulated pressure:
+
+            F = flux(u^n);  F_ext = w_new F + w_old F_prev;  F_prev = F
+            temp = f_step - A u^n - D F_ext - B^T q;   raw = (M_u + timestep/2 A)^-1 temp
+            phi = (B M_u^-1 B^T)^-1 B raw;   u^{n+1} = u^n + timestep (raw - M_u^-1 B^T phi);   q += phi
+
+        With a scalar, before: G_ext and b = w_b (avg T^n - t_ref) extrapolated the same way, f_step = f + b_ext; after:
+        delta = (M_p + timestep/2 K)^-1 (q_T - K T^n - B G_ext);  T^{n+1} = T^n + timestep delta.  `Project` is not
+        called: it overwrites `gfup`."""
+        conv = self.conv_operator
+        if not hasattr(conv, "Flux"):
+            raise ValueError("DoTimeStep: time_scheme=\"cnab2\" keeps its history in flux form and wants a conv_operator "
+                             "with Flux(u, F)")
+        ops, half, hist, eng = self._time_stepping_operators(), self._cnab2_operators(), self._history, self.gfu.engine
+        force = self.f.vec if self._scalar is None else self._scalar_flux_cnab2()
+        F, F_ext = half["div"].CreateRowVector(), half["div"].CreateRowVector()
+        conv.Flux(self.gfu, F)
+        self._extrapolate(F, hist.vector("F_prev", len(F), eng), hist.weights("momentum"), F_ext)
+        hist.valid["momentum"] = True
+        temp, raw, temp2 = (self.a.mat.CreateColVector() for _ in range(3))
+        rhs, phi = self.b.mat.CreateColVector(), self.gfup.CreateVector()
+        temp.data = force - self.a.mat * self.gfu
+        temp.data -= half["div"] * F_ext
+        temp.data -= half["Bt"] * self.gfup
+        raw.data = half["invmhalf"] * temp
+        rhs.data = self.b.mat * raw
+        phi.data = ops["invproj"] * rhs
+        temp2.data = raw - ops["correct"] * phi
+        self.gfup.data += phi
+        self.gfu.data += self.timestep * temp2
+        self.last_stages = dict(F_ext=F_ext, temp=temp, raw=raw, phi=phi, temp2=temp2)      # of the last step, for checks
+        if self._scalar is not None:
+            sc = self._scalar
+            sc.temp.data = sc.q - sc.K * self.temperature
+            sc.temp.data -= self.b.mat * sc.G_ext
+            sc.delta.data = sc.inv_half * sc.temp
+            self.temperature.data += self.timestep * sc.delta
+
+    def _scalar_flux_cnab2(self):
+        """The scalar's first statements of a "cnab2" step on (u^n, T^n): G into G_ext / G_prev, and the force of the
+        step, f + w_new b + w_old b_prev with b = w_b (avg T - t_ref) (f itself for a passive scalar)."""
+        sc, hist, eng = self._scalar, self._history, self.gfu.engine
+        weights = hist.weights("scalar")
+        sc.avgT.data = sc.avg * self.temperature
+        if sc.convection == "upwind":
+            sc.difT.data = sc.diff * self.temperature
+            sc.G.engine.upwind_flux(self.gfu.buf, sc.avgT.buf, sc.difT.buf, sc.G.buf)
+        else:
+            self._limited_scalar_flux(sc)
+        self._extrapolate(sc.G, hist.vector("G_prev", len(sc.G), eng), weights, sc.G_ext)
+        force = self.f.vec
+        if sc.Wb is not None:
+            sc.avgT.data -= sc.tref_u
+            sc.b.data = sc.Wb * sc.avgT
+            self._extrapolate(sc.b, hist.vector("b_prev", len(sc.b), eng), weights, sc.f_eff)
+            sc.f_eff.data += self.f.vec
+            force = sc.f_eff
+        hist.valid["scalar"] = True
+        return force
 
     def Project(self, vel):
         """Make `vel` discretely divergence-free (:440-443): phi = (B M_u^-1 B^T)^-1 B vel;
@@ -420,35 +584,46 @@ class NavierStokes:
         The steppers (one per `inner_pre`) share `M_u + timestep A`, `B M_u^-1 B^T` and `M_u^-1 B^T` with `DoTimeStep`
         and the convection matrices with each other; what a stepper adds in HBM is its work vectors, the rows of
         `[A | D]` -- a second copy of A, 12 bytes per non-zero -- and, for "amg", the two hierarchies.  Like
-        `DoTimeStep`, they keep the `timestep` of their first use: these operators are built once per object."""
+        `DoTimeStep`, they keep the `timestep` of their first use: these operators are built once per object.
+
+        `time_scheme="cnab2"`: the stepper runs the statements of `_do_time_step_cnab2`; it shares `M_u + timestep/2 A`
+        with `DoTimeStep`, keeps `[A | D | B^T]` in the place of `[A | D]` and reads and writes
+        the object's history and `gfup`, so that `DoTimeStep` and `Advance` can be mixed freely.  It declines when the flux
+        kernel declines the convection operators.  `pseudo=True` runs the "euler" stepper's relaxation, as ever."""
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
         if pseudo and self._scalar is not None:
             raise ValueError("Advance: the pseudo time stepping carries no scalar")
         steppers = self.__dict__.setdefault("_steppers", {})
-        stepper = steppers.get(inner_pre) if fused.ENABLED else None
+        scheme = "euler" if pseudo else self.time_scheme
+        key = inner_pre if scheme == self.time_scheme else (inner_pre, scheme)
+        stepper = steppers.get(key) if fused.ENABLED else None
         if stepper is None:
             s = self.system
             m_u = np.full(s.n_u, s.h ** s.dim * self.V.dofs_per_site ** 0)
             if "_stepper_shared" not in self.__dict__:      # one copy of the operators for DoTimeStep and every stepper
                 ops = self._time_stepping_operators()
                 self._stepper_shared = dict(mstar=ops["mstar"], Lp=ops["Lp"], C=ops["correct"])
+                if self.time_scheme == "cnab2":
+                    self._stepper_shared["mhalf"] = self._cnab2_operators()["mhalf"]
             stepper = TimeStepper.try_create(s, self.a.mat, self.b.mat, self.f.vec, self.timestep, m_u, inner_pre,
                                              conv_operator=lambda: self.conv_operator, shared=self._stepper_shared,
-                                             convection=self.convection)
+                                             convection=self.convection, time_scheme=scheme)
             if stepper is not None:
-                steppers[inner_pre] = stepper
+                steppers[key] = stepper
         self.advance_declined = TimeStepper.last_declined if stepper is None else None
         if stepper is not None and self._scalar is not None:
             sc = self._scalar
             if inner_pre not in sc.steppers:
                 sc.steppers[inner_pre] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
                                                        inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
-                                                       shared=sc.shared, convection=sc.convection, stencil=sc.stencil)
+                                                       shared=sc.shared, convection=sc.convection, stencil=sc.stencil,
+                                                       time_scheme=self.time_scheme)
             return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics,
-                                   scalar=sc.steppers[inner_pre], temperature=self.temperature)
+                                   scalar=sc.steppers[inner_pre], temperature=self.temperature, history=self._history)
         if stepper is not None:
-            return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics, pseudo)
+            return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics, pseudo,
+                                   history=None if pseudo else self._history)
         return self._advance_by_statements(int(nsteps), precision, maxsteps, diagnostics, pseudo, StepRecord)
 
     def _advance_by_statements(self, nsteps, precision, maxsteps, diagnostics, pseudo, record_type):
@@ -457,7 +632,8 @@ class NavierStokes:
         import contextlib
         import io
         ops = self._time_stepping_operators()
-        solvers = (ops["invmstar"], ops["invproj"])
+        held, name = self._momentum_solver(pseudo)
+        solvers = (held[name], ops["invproj"])
         saved = [(sv.precision, sv.maxsteps) for sv in solvers]
         for sv, p, m in zip(solvers, pair(precision), pair(maxsteps)):
             sv.precision = sv.precision if p is None else float(p)
@@ -476,10 +652,10 @@ class NavierStokes:
                     else:
                         self.DoTimeStep()
                         count = ops["invproj"].iterations
-                    its_m.append(ops["invmstar"].iterations)
+                    its_m.append(solvers[0].iterations)
                     its_p.append(count)
                     if sc is not None:
-                        its_s.append(sc.inv.iterations)
+                        its_s.append(sc.solver.iterations)
                         if diagnostics and sc.flux is not None:
                             wall.append(sc.wall_flux(self.temperature))
                     if diagnostics:
@@ -493,4 +669,5 @@ class NavierStokes:
         return record_type(its_m, its_p, np.array(div) if diagnostics else None,
                            np.array(energy) if diagnostics else None, declined=self.advance_declined,
                            scalar_iterations=its_s, convection=self.convection,
+                           time_scheme="euler" if pseudo else self.time_scheme,
                            wall_flux=np.array(wall) if sc is not None and diagnostics and sc.flux is not None else None)

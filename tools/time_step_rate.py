@@ -11,7 +11,9 @@ code path this stepper does not touch.  After `--warmup` steps each, `--rounds` 
 (DoTimeStep window, jacobi window, amg window, ...): per-step wall time (host clock around a window that ends in a
 device synchronise) and device time (events around the window), median and spread (max - min) of the windows, and the
 inner iteration counts of the last window.  Every window checks that the velocity is finite and that no inner solve ran
-into its iteration cap.  Prints one markdown table and one JSON line (also written to --out)."""
+into its iteration cap.  `--time-scheme cnab2` times the second-order scheme instead; `--time-scheme both` interleaves the
+windows of both schemes (runs "jacobi", "amg", "DoTimeStep" and "cnab2-jacobi", "cnab2-amg", "cnab2-DoTimeStep") and adds
+the ratio cnab2 / euler of every pair.  Prints one markdown table and one JSON line (also written to --out)."""
 import argparse
 import contextlib
 import io
@@ -31,9 +33,10 @@ import hipla
 ACCELERATION = 0.02     # size of f / m_u and of the start velocity
 
 
-def fresh(mesh, v0):
+def fresh(mesh, v0, time_scheme="euler"):
     from templates.NavierStokesSIMPLE_iterative import NavierStokes
-    ns = NavierStokes(mesh, nu=0.01, inflow="inlet", outflow="outlet", wall="wall|cyl", uin=None, timestep=0.05, order=1)
+    ns = NavierStokes(mesh, nu=0.01, inflow="inlet", outflow="outlet", wall="wall|cyl", uin=None, timestep=0.05, order=1,
+                      time_scheme=time_scheme)
     s = ns.system
     force = ACCELERATION * s.h ** s.dim * np.random.default_rng(8).standard_normal(s.n_u)
     ns.f.vec.data = hipla.Vector.from_numpy(force)
@@ -55,6 +58,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--time-scheme", choices=("euler", "cnab2", "both"), default="euler")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -66,22 +70,26 @@ def main():
     v0 = ACCELERATION * np.random.default_rng(2).standard_normal(s.n_u)
 
     runs = {}
-    for name in ("DoTimeStep", "jacobi", "amg"):
-        ns = fresh(mesh, v0)
-        ops = ns._time_stepping_operators() if name == "DoTimeStep" else None
+    schemes = ("euler", "cnab2") if args.time_scheme == "both" else (args.time_scheme,)
+    prefix = {scheme: "cnab2-" if scheme == "cnab2" and len(schemes) == 2 else "" for scheme in schemes}
+    for scheme, kind in [(scheme, kind) for kind in ("DoTimeStep", "jacobi", "amg") for scheme in schemes]:
+        name = prefix[scheme] + kind
+        ns = fresh(mesh, v0, scheme)
+        ops = ns._time_stepping_operators() if kind == "DoTimeStep" else None
         last = {}
 
-        def window(k, ns=ns, name=name, ops=ops, last=last):
-            if name == "DoTimeStep":
+        def window(k, ns=ns, kind=kind, ops=ops, last=last):
+            if kind == "DoTimeStep":
                 ms, ps = [], []
+                held, key = ns._momentum_solver()
                 with contextlib.redirect_stdout(io.StringIO()):
                     for _ in range(k):
                         ns.DoTimeStep()
-                        ms.append(ops["invmstar"].iterations)
+                        ms.append(held[key].iterations)
                         ps.append(ops["invproj"].iterations)
                 last["mstar"], last["proj"] = ms, ps
             else:
-                rec = ns.Advance(k, inner_pre=name)
+                rec = ns.Advance(k, inner_pre=kind)
                 if rec.declined:
                     raise RuntimeError("Advance declined: %s" % rec.declined)
                 last["mstar"], last["proj"] = rec.mstar_iterations.tolist(), rec.proj_iterations.tolist()
@@ -106,16 +114,23 @@ def main():
             check(r["last"]["ns"], r["last"]["mstar"], r["last"]["proj"])      # (outside the timed window)
 
     result = {"grid": args.grid, "n_u": int(s.n_u), "n_p": int(s.n_p), "steps": args.steps, "rounds": args.rounds,
-              "device": eng.device_info()["arch"], "u_max_end": float(np.abs(runs["jacobi"]["last"]["ns"].gfu.numpy()).max())}
+              "time_scheme": args.time_scheme, "device": eng.device_info()["arch"],
+              "u_max_end": float(np.abs(runs[prefix[schemes[-1]] + "jacobi"]["last"]["ns"].gfu.numpy()).max())}
     for name, r in runs.items():
         result[name] = {"wall_ms_per_step": float(np.median(r["wall"])), "wall_spread_ms": float(np.ptp(r["wall"])),
                         "device_ms_per_step": float(np.median(r["device"])), "device_spread_ms": float(np.ptp(r["device"])),
                         "wall_windows_ms": r["wall"], "device_windows_ms": r["device"],
                         "first_call_s": r["first_s"], "mstar_iterations": r["last"]["mstar"],
                         "proj_iterations": r["last"]["proj"]}
-    base = result["DoTimeStep"]["wall_ms_per_step"]
-    for name in ("jacobi", "amg"):
-        result[name]["wall_ratio_to_DoTimeStep"] = result[name]["wall_ms_per_step"] / base
+    for scheme in schemes:
+        base = result[prefix[scheme] + "DoTimeStep"]["wall_ms_per_step"]
+        for kind in ("jacobi", "amg"):
+            result[prefix[scheme] + kind]["wall_ratio_to_DoTimeStep"] = result[prefix[scheme] + kind]["wall_ms_per_step"] / base
+    if len(schemes) == 2:
+        for kind in ("DoTimeStep", "jacobi", "amg"):
+            for clock in ("wall", "device"):
+                result["cnab2-" + kind][clock + "_ratio_to_euler"] = \
+                    result["cnab2-" + kind][clock + "_ms_per_step"] / result[kind][clock + "_ms_per_step"]
     print("3-D n=%d (%d velocity, %d pressure dofs), %d windows of %d steps" % (args.grid, s.n_u, s.n_p, args.rounds, args.steps))
     print("| run | wall ms / step (spread) | device ms / step (spread) | mstar its | proj its |\n|---|---|---|---|---|")
     for name in runs:
