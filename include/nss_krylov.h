@@ -701,6 +701,10 @@ typedef struct nss_cg_s {
    * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
   int64_t plan_gen;
   int64_t cap_a, cap_b;
+  /* the shifted operator: with shift_sigma != 0 the loop solves with m + shift_sigma A in the place of A, m_r =
+   * shift_mass[r], or shift_m0 when shift_mass is NULL (uniform lumped mass), and takes pre_diag only.  All zero: A. */
+  const double* shift_mass;
+  double shift_m0, shift_sigma;
 } nss_cg_t;
 NSS_API int nss_cg_workspace(const nss_cg_t* s, int64_t* partials_a, int64_t* partials_b);
 NSS_API int nss_cg_iterate(const nss_cg_t* s, int32_t it_begin, int32_t it_end, nss_stream_t stream);
@@ -710,6 +714,10 @@ NSS_API int nss_cg_poll(const nss_cg_t* s, int32_t* done, int32_t* it_final, int
  * ctrl = { 0, -1, -1 }; a zero right-hand side sets done at once (it_final stays -1: no iterations).  hist must hold
  * as many entries as iterations will be enqueued.  No synchronisation, no allocation. */
 NSS_API int nss_cg_start(const nss_cg_t* s, const double* b, double tol, nss_stream_t stream);
+/* dinv[i] = 1 / fma(sigma, diag[i], m_i), m_i = mass[i] or m0 (mass NULL): the point-Jacobi preconditioner of the
+ * shifted operator, written into the buffer pre_diag names, one launch per step size. */
+NSS_API int nss_cg_shift_jacobi_f64(int64_t n, const double* mass, double m0, double sigma, const double* diag,
+                                    double* dinv, nss_stream_t stream);
 
 /* ---- device-resident IMEX time step ------------------------------------------------------------
  * The kernels of `NavierStokes.Advance` around the two inner CG solves (DoTimeStep / Project of the reference,
@@ -727,7 +735,10 @@ NSS_API int nss_cg_start(const nss_cg_t* s, const double* b, double tol, nss_str
  * nss_step_divergence_f64: partials of |B u|^2 (cap entries); rows summed in CSR order with unfused products, i.e.
  *   with the bits of a host CSR product.
  * nss_step_record_f64: record[2 slot] = scale * sum(partials_energy), record[2 slot + 1] = sqrt(sum(partials_div))
- *   (NaN when partials_div is NULL), summed by the fixed tree of the Krylov loops. */
+ *   (NaN when partials_div is NULL), summed by the fixed tree of the Krylov loops.
+ * nss_step_cfl_f64: out[slot] = max_r w_r sum_p |val_p| |u[col_p]| over the rows of b, w_r = inv_mass[r] or `scale`
+ *   (inv_mass NULL) -- the CFL number of u per unit of step size; rows summed in CSR order with unfused products; a row
+ *   value that is not finite (NaN included) gives +inf.  partials: cap entries, >= nss_step_cfl_workspace. */
 NSS_API int nss_step_flux_f64(nss_csr_t adv, nss_csr_t avg, nss_csr_t diff, const double* u, double* flux,
                               const int32_t* done, nss_stream_t stream);
 NSS_API int nss_step_rhs_f64(nss_csr_t ad, const double* uf, const double* f, double* temp, const int32_t* done,
@@ -738,6 +749,9 @@ NSS_API int nss_step_project_f64(nss_csr_t c, const double* phi, const double* r
 NSS_API int nss_step_divergence_f64(nss_csr_t b, const double* u, double* partials, int64_t cap, const int32_t* done,
                                     nss_stream_t stream);
 NSS_API int nss_step_workspace(nss_csr_t c, nss_csr_t b, int64_t* partials_energy, int64_t* partials_div);
+NSS_API int nss_step_cfl_workspace(nss_csr_t b, int64_t* partials);
+NSS_API int nss_step_cfl_f64(nss_csr_t b, const double* u, const double* inv_mass, double scale, double* partials,
+                             int64_t cap, double* out, int32_t slot, const int32_t* done, nss_stream_t stream);
 NSS_API int nss_step_record_f64(const double* partials_energy, int64_t n_energy, const double* partials_div,
                                 int64_t n_div, double scale, double* record, int32_t slot, const int32_t* done,
                                 nss_stream_t stream);

@@ -1,12 +1,15 @@
 // Fused, device-resident preconditioned conjugate gradients (the reference's inner solver
 // `CGSolver`, templates/NavierStokesSIMPLE_iterative.py:92,130; BASELINE config 1).
 //
-//   C1  rows of A    : q = A p, partial <p, q>
+//   C1  rows of A    : q = A p, partial <p, q>      (shifted loop: q = m p + sigma A p, EpiCgShiftQ)
 //   S1  one workgroup: <p,q> = sum
 //   C2  element-wise : alpha = rz / <p,q>;  x += alpha p;  r -= alpha q;  [z = dinv r, partial <r,z>]
 //   [P] block Jacobi / Gauss-Seidel / AMG: z = pre r, then partial <r, z>
 //   S2  one workgroup: rz_new = sum
 //   C3  element-wise : beta = rz_new / rz;  p = z + beta p;  one lane: history, stop test
+#include <cfloat>
+#include <cmath>
+
 #include "bpcg2.h"
 
 namespace nss {
@@ -30,6 +33,36 @@ struct EpiCgQ {
   }
   __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
 };
+
+// C1 of a shifted loop: q = m p + sigma (A p) with m_r = mass[r], or m0 without a mass vector (uniform lumped mass) --
+// the operator M + sigma A of a time step read from A itself, so that one matrix serves every step size
+struct EpiCgShiftQ {
+  const int32_t* __restrict__ ctrl;
+  const double* __restrict__ p;
+  const double* __restrict__ mass;
+  double m0, sigma;
+  double* __restrict__ q;
+  double* __restrict__ partials;
+  double acc = 0.0;
+  __device__ bool skip() const { return ctrl[GC_DONE] != 0; }
+  struct Pre { double p = 0.0, m = 0.0; };
+  __device__ Pre fetch(int r) const { return Pre{p[r], mass ? mass[r] : m0}; }
+  __device__ void row(int r, double ap, const Pre& pre) {
+    const double v = fma(sigma, ap, pre.m * pre.p);
+    q[r] = v;
+    acc = fma(pre.p, v, acc);
+  }
+  __device__ void finish(int b, double* lds) { store_block_partial(acc, b, partials, lds); }
+};
+
+// dinv = 1 / (m + sigma diag(A)): the point-Jacobi preconditioner of the shifted operator
+__global__ __launch_bounds__(kBlock) void cg_shift_jacobi_kernel(int32_t n, const double* __restrict__ mass, double m0,
+                                                                 double sigma, const double* __restrict__ diag,
+                                                                 double* __restrict__ dinv) {
+  const int stride = gridDim.x * kBlock;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    dinv[i] = 1.0 / fma(sigma, diag[i], mass ? mass[i] : m0);
+}
 
 __global__ __launch_bounds__(kLoopSum) void cg_sum_kernel(const int32_t* __restrict__ ctrl, int n,
                                                           const double* __restrict__ part, double* __restrict__ scal,
@@ -153,13 +186,19 @@ static void cg_check(const nss_cg_t* s) {
   pre_a_check(pre_a_of(*s, s->n), "cg", kPreAOnePartAtMost);
   NSS_REQUIRE(s->x && s->r && s->z && s->p && s->q && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b,
               "cg: NULL buffer");
+  NSS_REQUIRE(s->shift_sigma == 0.0 || (std::isfinite(s->shift_sigma) && !s->pre_bjac && !s->pre_amg),
+              "cg: a shifted loop takes a finite sigma and the point-Jacobi preconditioner only");
   const int64_t need[2] = {s->A->nblk, std::max<int64_t>(cg_grid(*s), s->pre_bjac ? bjac_dot_grid(*s->pre_bjac) : 0)};
   const int64_t cap[2] = {s->cap_a, s->cap_b};     // (need = nss_cg_workspace)
   check_plan("cg", plan_stamp({s->A}), s->plan_gen, need, cap, 2);
 }
 
 static void cg_iteration(const nss_cg_t& s, int it, hipStream_t st) {
-  launch_csr(*s.A, s.p, EpiCgQ{s.ctrl, s.p, s.q, s.partials_a}, st);
+  if (s.shift_sigma == 0.0)
+    launch_csr(*s.A, s.p, EpiCgQ{s.ctrl, s.p, s.q, s.partials_a}, st);
+  else
+    launch_csr<kF32 | kCodes>(*s.A, s.p, EpiCgShiftQ{s.ctrl, s.p, s.shift_mass, s.shift_m0, s.shift_sigma, s.q, s.partials_a},
+                              st);      // (every value form of A: a step's operator may be stored in fp32 or as codes)
   hipLaunchKernelGGL(cg_sum_kernel, dim3(1), dim3(kLoopSum), 0, st, s.ctrl, s.A->nblk, s.partials_a, s.scal, int(G_PQ));
   NSS_CHECK_LAUNCH();
   const bool fused_pre = !s.pre_bjac && !s.pre_amg;
@@ -219,6 +258,17 @@ int nss_cg_iterate(const nss_cg_t* s, int32_t it_begin, int32_t it_end, nss_stre
   return guarded([&] {
     cg_check(s);
     for (int it = it_begin; it < it_end; ++it) cg_iteration(*s, it, as_stream(stream));
+  });
+}
+
+int nss_cg_shift_jacobi_f64(int64_t n, const double* mass, double m0, double sigma, const double* diag, double* dinv,
+                            nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(n >= 0 && n <= INT32_MAX && diag && dinv, "cg_shift_jacobi: NULL argument, or n outside int32");
+    if (n == 0) return;
+    hipLaunchKernelGGL(cg_shift_jacobi_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, as_stream(stream),
+                       int32_t(n), mass, m0, sigma, diag, dinv);
+    NSS_CHECK_LAUNCH();
   });
 }
 

@@ -8,8 +8,14 @@
 //   P1  rows of C       : out = raw - C phi;  u += tau out;  partials of <u, M u>           (EpiStepProject)
 //   P2  rows of B       : partials of |B u|^2                                               (step_div_kernel, optional)
 //   P3  one workgroup   : record[step] = { <u, M u> / 2, |B u| }                            (step_record_kernel)
+// and, for a variable step, at the head
+//   R1  rows of B       : per workgroup max_r w_r sum_p |B_rp| |u_p|                            (step_cfl_kernel)
+//   R2  one workgroup   : rates[step] = the maximum                                             (step_cfl_max_kernel)
 //
 // All fp64, no atomics: every sum is per-workgroup partials added by the fixed tree (fixed_sums_1024).
+#include <cfloat>
+#include <cmath>
+
 #include "bpcg2.h"
 
 namespace nss {
@@ -117,6 +123,59 @@ __global__ __launch_bounds__(kBlock) void step_record_kernel(const int32_t* __re
   }
 }
 
+// Maximum over a kBlock-thread workgroup of values that are not NaN, valid in thread 0.  `lds`: kBlock / kWave doubles.
+__device__ __forceinline__ double block_max(double v, double* lds) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
+  if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = lds[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / kWave; ++w) t = fmax(t, lds[w]);
+  return t;
+}
+
+// the rate of one row, w * sum, with anything that is not finite (NaN included, which fmax would drop) as +inf
+__device__ __forceinline__ double cfl_rate(double w, double sum) {
+  const double v = mul_unfused(w, sum);
+  return v <= DBL_MAX ? v : __builtin_inf();
+}
+
+// R1: per workgroup the maximum of w_r sum_p |val_p| |u[col_p]| over the rows of B (w_r = inv_mass[r], or scale), one
+// lane per row, summed entry after entry with products rounded on their own like step_div_kernel: the value can be
+// compared for equality with a host CSR product.  On the plain grid this is max_cell sum_faces |u_f| / h.
+__global__ __launch_bounds__(kBlock) void step_cfl_kernel(const int32_t* __restrict__ done, int32_t m,
+                                                           const int32_t* __restrict__ rowptr,
+                                                           const int32_t* __restrict__ col, const double* __restrict__ val,
+                                                           const double* __restrict__ u,
+                                                           const double* __restrict__ inv_mass, double scale,
+                                                           double* __restrict__ partials) {
+  __shared__ double lds[kBlock / kWave];
+  if (step_done(done)) return;
+  const int stride = gridDim.x * kBlock;
+  double top = 0.0;
+  for (int r = blockIdx.x * kBlock + threadIdx.x; r < m; r += stride) {
+    const int s = rowptr[r], e = rowptr[r + 1];
+    double sum = 0.0;
+    for (int p = s; p < e; ++p) sum += mul_unfused(fabs(val[p]), fabs(u[col[p]]));
+    top = fmax(top, cfl_rate(inv_mass ? inv_mass[r] : scale, sum));
+  }
+  top = block_max(top, lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = top;
+}
+
+// R2: out[slot] = the maximum of the n partials, by one workgroup (the order does not matter for a maximum)
+__global__ __launch_bounds__(kBlock) void step_cfl_max_kernel(const int32_t* __restrict__ done,
+                                                               const double* __restrict__ partials, int n,
+                                                               double* __restrict__ out, int slot) {
+  __shared__ double lds[kBlock / kWave];
+  if (step_done(done)) return;
+  double top = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) top = fmax(top, partials[i]);
+  top = block_max(top, lds);
+  if (threadIdx.x == 0) out[slot] = top;
+}
+
 static int div_grid(const nss_csr_s& B) { return stream_grid(B.m, kBlock); }
 
 }  // namespace nss
@@ -186,6 +245,29 @@ int nss_step_workspace(nss_csr_t c, nss_csr_t b, int64_t* partials_energy, int64
     NSS_REQUIRE(c && b, "step_workspace: NULL matrix");
     if (partials_energy) *partials_energy = c->nblk;
     if (partials_div) *partials_div = div_grid(*b);
+  });
+}
+
+int nss_step_cfl_workspace(nss_csr_t b, int64_t* partials) {
+  return guarded([&] {
+    NSS_REQUIRE(b && partials, "step_cfl_workspace: NULL argument");
+    *partials = div_grid(*b);
+  });
+}
+
+int nss_step_cfl_f64(nss_csr_t b, const double* u, const double* inv_mass, double scale, double* partials, int64_t cap,
+                     double* out, int32_t slot, const int32_t* done, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(b && u && partials && out && slot >= 0, "step_cfl: NULL argument or a negative slot");
+    require_f64_values(b, "step_cfl");
+    const int grid = div_grid(*b);
+    NSS_REQUIRE(cap >= grid, "step_cfl: partials hold fewer entries than nss_step_cfl_workspace asks for");
+    hipLaunchKernelGGL(step_cfl_kernel, dim3(grid), dim3(kBlock), 0, as_stream(stream), done, b->m, b->rowptr, b->col,
+                       b->val, u, inv_mass, scale, partials);
+    NSS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(step_cfl_max_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), done, partials, grid, out,
+                       int(slot));
+    NSS_CHECK_LAUNCH();
   });
 }
 

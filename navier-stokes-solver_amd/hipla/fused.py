@@ -771,7 +771,8 @@ class CgState(C.Structure):
     """ctypes mirror of ``nss_cg_t`` (include/nss_krylov.h)."""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "pre_diag", "pre_bjac", "pre_amg", "x", "r", "z", "p", "q",
                                            "scal", "ctrl", "hist", "partials_a", "partials_b")]
-                + [("n", C.c_int32), ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64)])
+                + [("n", C.c_int32), ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64)]
+                + [("shift_mass", C.c_void_p), ("shift_m0", C.c_double), ("shift_sigma", C.c_double)])
 
 
 class CgLoop(FusedLoop):
@@ -795,11 +796,24 @@ class CgLoop(FusedLoop):
             return "the preconditioner is not native"
         return cls(eng, mat, pa)
 
-    def __init__(self, eng, mat, pa):
-        """`pa`: the `PreParts` of the preconditioner (NO_PRE: none)."""
+    def __init__(self, eng, mat, pa, shift=None):
+        """`pa`: the `PreParts` of the preconditioner (NO_PRE: none).  `shift` = (mass, diag): the loop solves with
+        ``M + sigma mat`` read from `mat` itself (the shifted C1 of csrc/cg.hip), sigma given by `set_shift` before the
+        first solve; `mass`: host array of the lumped mass (uniform: passed by value) and `diag`: device buffer, the
+        diagonal of `mat`.  A shifted loop takes the point-Jacobi preconditioner of its operator, which `set_shift`
+        writes, and no other (`pa` is ignored)."""
         torch = eng.torch
-        self.eng, self.lib, self.mat, self.pa = eng, eng.lib, mat, pa
         n = mat.height
+        self.shift = self.sigma = None
+        if shift is not None:
+            from types import SimpleNamespace
+            mass, diag = np.asarray(shift[0], dtype=np.float64), shift[1]
+            if mass.shape != (n,) or diag.numel() != n:
+                raise ValueError("CgLoop: the shift wants the mass and the diagonal of the matrix, %d entries each" % n)
+            uniform = bool(n) and bool((mass == mass[0]).all())
+            self.shift = (None if uniform else eng.from_host(mass), float(mass[0]) if uniform else 0.0, diag)
+            pa = PreParts(1.0, SimpleNamespace(d=eng.zeros(n)), None, None, False)
+        self.eng, self.lib, self.mat, self.pa = eng, eng.lib, mat, pa
         self.work = {name: eng.zeros(n) for name in ("r", "z", "p", "q")}
         st = CgState()
         st.A, st.n = mat.handle.ptr, n
@@ -810,10 +824,31 @@ class CgLoop(FusedLoop):
         self.scal = eng.zeros(8)
         self.ctrl = torch.zeros(4, dtype=torch.int32, device=eng.device)
         st.scal, st.ctrl = self.scal.data_ptr(), self.ctrl.data_ptr()
+        if self.shift is not None:
+            st.shift_mass = None if self.shift[0] is None else self.shift[0].data_ptr()
+            st.shift_m0 = self.shift[1]
         self.state = st
         self.hist = None
 
+    def set_shift(self, sigma):
+        """The operator becomes M + `sigma` mat: writes the state's sigma and the Jacobi preconditioner
+        1 / (m + sigma diag) (one element-wise launch).  Nothing happens when `sigma` is the current one."""
+        if self.shift is None:
+            raise ValueError("CgLoop.set_shift: the loop was made without a shift")
+        sigma = float(sigma)
+        if not (sigma > 0.0 and np.isfinite(sigma)):
+            raise ValueError("CgLoop.set_shift: sigma is positive and finite, not %r" % (sigma,))
+        if sigma == self.sigma:
+            return
+        mass, m0, diag = self.shift
+        self.eng._check(self.lib.nss_cg_shift_jacobi_f64(self.mat.height, None if mass is None else mass.data_ptr(), m0,
+                                                         sigma, diag.data_ptr(), self.pa.diag.d.data_ptr(),
+                                                         self.eng.stream))
+        self.state.shift_sigma = self.sigma = sigma
+
     def enqueue(self, it_begin, it_end):
+        if self.shift is not None and self.sigma is None:
+            raise ValueError("CgLoop: a shifted loop wants set_shift(sigma) before its first solve")
         self.eng._check(self.lib.nss_cg_iterate(C.byref(self.state), it_begin, it_end, self.eng.stream))
 
     def poll(self):

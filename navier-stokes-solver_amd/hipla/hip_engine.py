@@ -133,11 +133,14 @@ def _signatures():
         "nss_cg_iterate": (C.c_int, [vp, i32, i32, vp]),
         "nss_cg_poll": (C.c_int, [vp, c_i32_p, c_i32_p, c_i32_p, vp]),
         "nss_cg_start": (C.c_int, [vp, vp, dbl, vp]),
+        "nss_cg_shift_jacobi_f64": (C.c_int, [i64, vp, dbl, dbl, vp, vp, vp]),
         "nss_step_flux_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "nss_step_rhs_f64": (C.c_int, [vp, vp, vp, vp, vp, vp]),
         "nss_step_project_f64": (C.c_int, [vp, vp, vp, vp, vp, dbl, vp, vp, i64, vp, vp]),
         "nss_step_divergence_f64": (C.c_int, [vp, vp, vp, i64, vp, vp]),
         "nss_step_workspace": (C.c_int, [vp, vp, c_i64_p, c_i64_p]),
+        "nss_step_cfl_workspace": (C.c_int, [vp, c_i64_p]),
+        "nss_step_cfl_f64": (C.c_int, [vp, vp, vp, dbl, vp, i64, vp, i32, vp, vp]),
         "nss_step_record_f64": (C.c_int, [vp, i64, vp, i64, dbl, vp, i32, vp, vp]),
         "nss_scalar_flux_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp]),
         "nss_step_flux_limited_f64": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, vp]),

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import fused
 from .amg import SmoothedAggregationAMG
-from .fused import CgLoop, FusedLoop, _hip, pre_for
+from .fused import NO_PRE, CgLoop, FusedLoop, _hip, pre_for
 from .matrix import JacobiPreconditioner, ScaledMatrix, SparseMatrix, SumMatrix
 from .vector import Vector
 
@@ -51,26 +51,104 @@ class TimeHistory:
     """The two-step history of a `time_scheme="cnab2"` object, in flux form: `F_prev` (momentum flux, n_F), `G_prev`
     (scalar flux, n_u) and `b_prev` (buoyancy force, n_u) as `Vector`s (None until the quantity has stepped), with one
     "valid" flag per quantity -- a quantity without valid history takes the weights (1, 0), i.e. one Euler-extrapolated
-    step, a quantity with it (3/2, -1/2).  `DoTimeStep` and `Advance` read and write the same object."""
+    step, a quantity with it (3/2, -1/2).  `DoTimeStep` and `Advance` read and write the same object.
+
+    `tau_prev`: the size of the last step (None until a step has run, and after `reset()`); a step of size `tau` then
+    extrapolates with the variable-step weights (1 + r/2, -r/2), r = tau / tau_prev -- (3/2, -1/2) exactly for r == 1.  An
+    "euler" object keeps a `TimeHistory` for `tau_prev` alone (the growth limit of the step-size controller)."""
 
     QUANTITIES = ("momentum", "scalar")
 
     def __init__(self):
         self.F_prev = self.G_prev = self.b_prev = None
         self.valid = dict.fromkeys(self.QUANTITIES, False)
+        self.tau_prev = None
 
-    def weights(self, quantity):
-        return (1.5, -0.5) if self.valid[quantity] else (1.0, 0.0)
+    @staticmethod
+    def ab2_weights(valid, tau=None, tau_prev=None):
+        """(w_new, w_old) of a step of size `tau` behind one of size `tau_prev` (either None: equal steps)."""
+        if not valid:
+            return (1.0, 0.0)
+        r = 1.0 if tau is None or tau_prev is None else float(tau) / float(tau_prev)
+        return (1.0 + r / 2, -r / 2)
+
+    def weights(self, quantity, tau=None):
+        return self.ab2_weights(self.valid[quantity], tau, self.tau_prev)
 
     def reset(self, quantity=None):
         for key in self.QUANTITIES if quantity is None else (quantity,):
             self.valid[key] = False
+        if quantity is None:
+            self.tau_prev = None
 
     def vector(self, name, n, engine):
         """The history `Vector` `name` of length `n`, allocated (zero) on first use."""
         if getattr(self, name) is None or len(getattr(self, name)) != n:
             setattr(self, name, Vector(buf=engine.zeros(n), engine=engine))
         return getattr(self, name)
+
+
+def check_step_size(tau, who):
+    """`tau` as a float; ``ValueError`` unless it is positive and finite."""
+    tau = float(tau)
+    if not (tau > 0.0 and np.isfinite(tau)):
+        raise ValueError("%s: a step size is positive and finite, not %r" % (who, tau))
+    return tau
+
+
+def choose_timestep(rate, cfl, max_timestep, previous=None, growth=1.25, remaining=None):
+    """The step size of a CFL-controlled step, on the host: (tau, code) with
+
+        tau = min(max_timestep, cfl / rate [rate > 0], growth * previous [previous is not None])
+
+    and `code` the binding term, "max", "cfl" or "growth" (ties in that order).  `rate`: the CFL number of the state per
+    unit of step size (`NavierStokes.CflRate`); `previous`: the size of the last step.  With `remaining` (the time left
+    of a duration): a tau >= remaining (1 - 1e-12) becomes `remaining`, code "end".  A rate that is not finite raises
+    ``FloatingPointError``."""
+    rate = float(rate)
+    if not np.isfinite(rate):
+        raise FloatingPointError("choose_timestep: the CFL rate is %r" % (rate,))
+    tau, code = float(max_timestep), "max"
+    if rate > 0.0 and cfl / rate < tau:
+        tau, code = cfl / rate, "cfl"
+    if previous is not None and growth * previous < tau:
+        tau, code = growth * previous, "growth"
+    if remaining is not None and tau >= remaining * (1.0 - 1e-12):
+        tau, code = float(remaining), "end"
+    return tau, code
+
+
+class StepController:
+    """The arguments `cfl`, `max_timestep`, `growth`, `duration` of a CFL-controlled `Advance`, and the clock of one call:
+    `next(rate, previous)` returns (tau, code) of the next step, or None when the duration has been reached."""
+
+    def __init__(self, cfl, max_timestep, growth=1.25, duration=None):
+        self.cfl, self.max_timestep, self.growth = float(cfl), check_step_size(max_timestep, "Advance"), float(growth)
+        self.duration = None if duration is None else float(duration)
+        if not (self.cfl > 0.0 and np.isfinite(self.cfl)):
+            raise ValueError("Advance: cfl is positive and finite, not %r" % (cfl,))
+        if not self.growth >= 1.0:
+            raise ValueError("Advance: growth is at least 1, not %r" % (growth,))
+        if self.duration is not None and not (self.duration > 0.0 and np.isfinite(self.duration)):
+            raise ValueError("Advance: duration is positive and finite, not %r" % (duration,))
+        self.time, self.ended = 0.0, False
+
+    def next(self, rate, previous):
+        if self.ended:
+            return None
+        remaining = None if self.duration is None else self.duration - self.time
+        tau, code = choose_timestep(rate, self.cfl, self.max_timestep, previous, self.growth, remaining)
+        self.ended = code == "end"
+        self.time = self.duration if self.ended else self.time + tau
+        return tau, code
+
+
+def variable_record(taus, rates, codes):
+    """The fields `timestep`, `time`, `cfl`, `limited_by` of a variable-step `StepRecord` from the step sizes, the rates
+    of the states the steps started from, and the controller's codes (None: prescribed steps)."""
+    taus = np.asarray(taus, dtype=np.float64)
+    return dict(timestep=taus, time=np.cumsum(taus), cfl=taus * np.asarray(rates, dtype=np.float64)[:len(taus)],
+                limited_by=None if codes is None else list(codes))
 
 
 def upload_stencil(eng, stencil, n):
@@ -216,10 +294,14 @@ class StepRecord:
     step (None when it ran); `flux_declined`: why the convection term ran through `ConvectionOperator`.  With a scalar
     (`NavierStokes.AddScalar`): `scalar_iterations` of the temperature solve and `wall_flux` = the heat entering through
     its `flux_wall` after the step (None without a scalar / diagnostics).  `convection`: the momentum flux's scheme;
-    `time_scheme`: "euler" or "cnab2" (the pseudo time stepping is a relaxation and records "euler")."""
+    `time_scheme`: "euler" or "cnab2" (the pseudo time stepping is a relaxation and records "euler").  With a
+    variable-step argument of `Advance` (None otherwise): `timestep` = the step sizes tau_n, `time` = their running sum
+    within the call, `cfl` = tau_n * rate(u^n), and with `cfl=` also `limited_by` = the codes of `choose_timestep`."""
 
     def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
-                 scalar_iterations=None, wall_flux=None, convection="upwind", time_scheme="euler"):
+                 scalar_iterations=None, wall_flux=None, convection="upwind", time_scheme="euler", timestep=None,
+                 time=None, cfl=None, limited_by=None):
+        self.timestep, self.time, self.cfl, self.limited_by = timestep, time, cfl, limited_by
         self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
         self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
         self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
@@ -228,6 +310,36 @@ class StepRecord:
         self.wall_flux = wall_flux
         self.convection = convection
         self.time_scheme = time_scheme
+
+
+class CflRate:
+    """The CFL rate kernel (``nss_step_cfl_f64``): max_r w_r sum_p |B_rp| |u_p| over the rows of `B`, w = 1 / `m_p` (host
+    array of the lumped pressure mass; None: ones; uniform: passed by value) -- on the plain grid
+    max_cell sum_faces |u_f| / h, the CFL number of u per unit of step size."""
+
+    def __init__(self, eng, B, m_p=None):
+        self.eng, self.lib, self.B = eng, eng.lib, B
+        w = np.ones(B.height) if m_p is None else 1.0 / np.asarray(m_p, dtype=np.float64)
+        if w.shape != (B.height,):
+            raise ValueError("CflRate: the mass holds %s entries, B %d rows" % (w.shape, B.height))
+        uniform = bool(w.size) and bool((w == w[0]).all())
+        self.inv_mass, self.scale = (None, float(w[0])) if uniform else (eng.from_host(w), 0.0)
+        count = C.c_int64()
+        eng._check(self.lib.nss_step_cfl_workspace(B.handle.ptr, C.byref(count)))
+        self.partials = eng.zeros(max(1, count.value))
+        self.out = eng.zeros(1)
+
+    def launch(self, u, out, slot):
+        """out[slot] = the rate of the device buffer `u`."""
+        eng = self.eng
+        eng._check(self.lib.nss_step_cfl_f64(self.B.handle.ptr, u.data_ptr(), _ptr(self.inv_mass), self.scale,
+                                             self.partials.data_ptr(), self.partials.numel(), out.data_ptr(), slot, None,
+                                             eng.stream))
+
+    def __call__(self, u):
+        """The rate of the device buffer `u`, read back."""
+        self.launch(u, self.out, 0)
+        return float(self.eng.to_host(self.out)[0])
 
 
 class TimeStepper(FusedLoop):
@@ -251,7 +363,7 @@ class TimeStepper(FusedLoop):
 
     @classmethod
     def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
-                   convection="upwind", time_scheme="euler"):
+                   convection="upwind", time_scheme="euler", variable=False, m_p=None):
         """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
         `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
         solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
@@ -261,14 +373,19 @@ class TimeStepper(FusedLoop):
         under "mstar", "Lp", "C" -- keep them once.  `convection`: the scheme of F1 (`MomentumFlux`), "upwind" (donor
         cell, first order) or the second-order limited "minmod" / "vanleer".  `time_scheme`: "euler" or "cnab2"; a "cnab2"
         stepper keeps its matrices under keys of their own ("mhalf", "ADBt") and declines when the flux kernel declines the
-        convection operators.  Returns None, the reason in `last_declined`."""
+        convection operators.  `variable`: a variable-step stepper -- no mstar / mhalf: the velocity solve runs the shifted
+        `CgLoop` over `A` with sigma = tau_n ("euler") or tau_n / 2 ("cnab2"), Jacobi only; `m_p`: host array, the lumped
+        pressure mass of the rate kernel (None: ones).  Returns None, the reason in `last_declined`."""
         return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection,
-                                            time_scheme))
+                                            time_scheme, variable, m_p))
 
     @classmethod
-    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme):
+    def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme,
+                    variable=False, m_p=None):
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
+        if variable and inner_pre != "jacobi":
+            raise ValueError("a variable-step stepper takes inner_pre=\"jacobi\": a hierarchy belongs to one step size")
         check_convection(convection, "TimeStepper")
         check_time_scheme(time_scheme, "TimeStepper")
         if not fused.ENABLED:
@@ -287,13 +404,16 @@ class TimeStepper(FusedLoop):
                 shared["flux_declined"] = MomentumFlux.declined(system.convection_operators())
             if shared["flux_declined"] is not None:
                 return "cnab2: the flux kernel declines the convection operators: " + shared["flux_declined"]
-        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme)
+        if variable and not hasattr(A.engine.lib, "nss_step_cfl_f64"):
+            return "the library has no CFL rate kernel"
+        return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme, variable,
+                   m_p)
 
     def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind",
-                 time_scheme="euler"):
+                 time_scheme="euler", variable=False, m_p=None):
         import scipy.sparse as sp
         eng = self.eng = A.engine
-        self.time_scheme = time_scheme
+        self.time_scheme, self.variable = time_scheme, bool(variable)
         cnab2 = time_scheme == "cnab2"
         rows_key, mstar_key = ("ADBt", "mhalf") if cnab2 else ("AD", "mstar")
         self.lib, self.A, self.B, self.f, self.timestep = eng.lib, A, B, f, float(timestep)
@@ -323,7 +443,7 @@ class TimeStepper(FusedLoop):
         self.temp, self.raw, self.temp2 = eng.zeros(self.n_u), eng.zeros(self.n_u), eng.zeros(self.n_u)
         self.rhs_p, self.phi = eng.zeros(self.n_p), eng.zeros(self.n_p)
         # ---- the inner solves ----
-        if mstar_key not in shared:                 # M_u + timestep A, or the half-step operator M_u + timestep/2 A
+        if not variable and mstar_key not in shared:   # M_u + timestep A, or the half-step operator M_u + timestep/2 A
             theta = 0.5 * self.timestep if cnab2 else self.timestep
             shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(m_u) + theta * A.to_scipy()).tocsr(), engine=eng)
         if "C" not in shared:
@@ -332,19 +452,26 @@ class TimeStepper(FusedLoop):
             lap_p = (B.to_scipy() @ shared["C"].to_scipy()).tocsr()
             lap_p.sort_indices()
             shared["Lp"] = SparseMatrix.from_scipy(lap_p, engine=eng)
-        self.mstar, self.Lp, self.C = shared[mstar_key], shared["Lp"], shared["C"]
+        self.mstar, self.Lp, self.C = None if variable else shared[mstar_key], shared["Lp"], shared["C"]
         if "singular" not in shared:
             ok, why = two_entry_rows(self.C.to_scipy())
             if not ok:
                 raise ValueError("TimeStepper: M_u^-1 B^T: " + why)
             shared["singular"] = constants_in_kernel(self.Lp.to_scipy())
         self.singular = shared["singular"]
-        if inner_pre == "amg":
-            self.pre_m = SmoothedAggregationAMG(self.mstar)
-            self.pre_p = SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
+        if variable:                                # the shifted loop over A: M_u + sigma A for the sigma of each step
+            if "diagA" not in shared:
+                shared["diagA"] = eng.from_host(A.to_scipy().diagonal())
+            self.pre_m, self.pre_p = None, JacobiPreconditioner(self.Lp)
+            self.cg_m = CgLoop(eng, A, NO_PRE, shift=(m_u, shared["diagA"]))
+            self.rate = CflRate(eng, B, m_p)
         else:
-            self.pre_m, self.pre_p = JacobiPreconditioner(self.mstar), JacobiPreconditioner(self.Lp)
-        self.cg_m = CgLoop(eng, self.mstar, pre_for("cg", self.pre_m))
+            if inner_pre == "amg":
+                self.pre_m = SmoothedAggregationAMG(self.mstar)
+                self.pre_p = SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
+            else:
+                self.pre_m, self.pre_p = JacobiPreconditioner(self.mstar), JacobiPreconditioner(self.Lp)
+            self.cg_m = CgLoop(eng, self.mstar, pre_for("cg", self.pre_m))
         self.cg_p = CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
         # ---- the record ----
         uniform = bool(m_u.size) and bool((m_u == m_u[0]).all())
@@ -380,15 +507,17 @@ class TimeStepper(FusedLoop):
         temp.data += Vector(buf=f, engine=eng)
         temp.data += -self.A * u
 
-    def project(self, vel, out=None, update=None, energy=False):
+    def project(self, vel, out=None, update=None, energy=False, tau=None):
         """out = vel - C phi with phi = (B M_u^-1 B^T)^-1 B vel (`Project`; `out` None: in place); `update`:
-        u += timestep * out in the same launch; `energy`: also the partials of <e, M_u e>, e = the updated u, or out.
+        u += tau * out in the same launch (`tau` None: the stepper's timestep); `energy`: also the partials of
+        <e, M_u e>, e = the updated u, or out.
         Returns the CG iterations."""
         eng, lib = self.eng, self.lib
         eng.csr_spmv(self.B.handle, 1.0, vel, 0.0, self.rhs_p)
         its = self.cg_p.solve_resident(self.rhs_p, self.phi, self.precision[1], self.maxsteps[1])
         eng._check(lib.nss_step_project_f64(self.C.handle.ptr, self.phi.data_ptr(), vel.data_ptr(),
-                                            (vel if out is None else out).data_ptr(), _ptr(update), self.timestep,
+                                            (vel if out is None else out).data_ptr(), _ptr(update),
+                                            self.timestep if tau is None else tau,
                                             _ptr(self.mass), self.partials_e.data_ptr() if energy else None,
                                             self.partials_e.numel(), None, eng.stream))
         return its
@@ -401,13 +530,18 @@ class TimeStepper(FusedLoop):
                                            self.n_div, self.energy_scale, record.data_ptr(), slot, None, eng.stream))
 
     def advance(self, gfu, gfup, nsteps, precision=None, maxsteps=None, diagnostics=True, pseudo=False, scalar=None,
-                temperature=None, history=None):
+                temperature=None, history=None, timesteps=None, controller=None, clock=None):
         """`nsteps` steps on the velocity `gfu` (pressure-like potential of the last projection -> `gfup`).
         `precision` / `maxsteps`: one value for both inner solves, a pair (mstar, projection), or None = the template's.
         `scalar`: a `ScalarStepper` -- every step then begins with its flux launch on (u^n, T^n), the velocity step
         takes its f_eff for f (a buoyant scalar), and its temperature step follows; `temperature`: the `Vector` of T.
         A "cnab2" stepper: `gfup` is the accumulated pressure q, copied into the operand on entry and out on exit, and
-        `history` the object's `TimeHistory`, copied in and out once (the valid flags are updated)."""
+        `history` the object's `TimeHistory`, copied in and out once (the valid flags are updated).
+
+        A variable-step stepper takes `timesteps` (`nsteps` prescribed sizes) or `controller` (a `StepController`) and
+        `clock`, the `TimeHistory` that holds `tau_prev` (`history` itself for "cnab2").  Every step begins with the rate
+        launch on u^n into rates[step]; with a controller the host reads that one double back and chooses tau_n.  The
+        sigma of the shifted solves, tau_n and the AB2 weights (1 + r/2, -r/2) go to the launches by value."""
         self.precision = tuple(float(p) for p in pair(precision, self.PRECISION))
         self.maxsteps = tuple(int(m) for m in pair(maxsteps, self.MAXSTEPS))
         eng = self.eng
@@ -420,8 +554,21 @@ class TimeStepper(FusedLoop):
             raise ValueError("advance: a \"cnab2\" stepper takes the object's history and does no pseudo time stepping")
         if cnab2 and scalar is not None and scalar.time_scheme != "cnab2":
             raise ValueError("advance: the scalar stepper is not a \"cnab2\" one")
-        slots = max(1, nsteps)                 # the record: [2 slots] of the velocity | [slots] of the scalar
-        record = eng.zeros((2 if scalar is None else 3) * slots) if diagnostics else None
+        if self.variable != (timesteps is not None or controller is not None):
+            raise ValueError("advance: a variable-step stepper, and no other, takes timesteps or a controller")
+        if self.variable and (pseudo or (clock is None and history is None)):
+            raise ValueError("advance: variable steps want the clock and do no pseudo time stepping")
+        if self.variable and scalar is not None and not scalar.variable:
+            raise ValueError("advance: the scalar stepper is not a variable-step one")
+        if timesteps is not None:
+            timesteps = [check_step_size(t, "advance") for t in timesteps]
+            if len(timesteps) != nsteps or controller is not None:
+                raise ValueError("advance: timesteps holds one size per step, and excludes a controller")
+        slots = max(1, nsteps)                 # the record: [2 slots] of the velocity | [slots] of the scalar | [slots] rates
+        nrec = (2 if scalar is None else 3) * slots if diagnostics else 0
+        buf = eng.zeros(nrec + (slots if self.variable else 0)) if diagnostics or self.variable else None
+        record = eng.view(buf, 0, nrec) if diagnostics else None
+        rates = eng.view(buf, nrec, nrec + slots) if self.variable else None
         record_s = eng.view(record, 2 * slots, 3 * slots) if diagnostics and scalar is not None and scalar.records else None
         eng.copy(gfu.buf, self.u)
         if scalar is not None:
@@ -433,20 +580,44 @@ class TimeStepper(FusedLoop):
             if scalar is not None:
                 scalar.load_history(history)
         its_m, its_p, its_s = [], [], None if scalar is None else []
+        taus, codes, failure = [], None if controller is None else [], None
+        clock = history if clock is None else clock                       # ("euler": the caller's, or none)
+        tau_prev = None if clock is None else clock.tau_prev
+        valid = dict(history.valid) if cnab2 else None
         if pseudo:
             self.project(self.u)                                          # :407  Project(gfu)
         for step in range(nsteps):
+            tau = None                                                    # (None: the stepper's own timestep)
+            if self.variable:
+                self.rate.launch(self.u, rates, step)                     # R1, R2 on u^n
+                if controller is None:
+                    tau = timesteps[step]
+                else:
+                    try:
+                        chosen = controller.next(float(eng.to_host(eng.view(rates, step, step + 1))[0]), tau_prev)
+                    except FloatingPointError as err:
+                        failure = err
+                        break
+                    if chosen is None:
+                        break
+                    tau = chosen[0]
+                    codes.append(chosen[1])
+                taus.append(tau)
+                self.cg_m.set_shift(0.5 * tau if cnab2 else tau)
             if pseudo:
                 eng.csr_spmv(self.A.handle, -1.0, self.u, 0.0, self.temp)         # :411  temp = -A u
             elif cnab2:
-                self.weights = history.weights("momentum") if step == 0 else (1.5, -0.5)
+                size = self.timestep if tau is None else tau
+                self.weights = TimeHistory.ab2_weights(valid["momentum"], size, tau_prev)
                 force = None if scalar is None else \
-                    scalar.flux_ab2(self.u, history.weights("scalar") if step == 0 else (1.5, -0.5))
+                    scalar.flux_ab2(self.u, TimeHistory.ab2_weights(valid["scalar"], size, tau_prev))
+                valid = dict.fromkeys(valid, True)
                 self.right_hand_side(force)
             else:
                 self.right_hand_side(None if scalar is None else scalar.flux(self.u))     # (S1,) F1, F2  :429-431
             its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))   # :433
-            count = self.project(self.raw, out=self.temp2, update=self.u, energy=diagnostics and not pseudo)   # :434,438
+            count = self.project(self.raw, out=self.temp2, update=self.u, energy=diagnostics and not pseudo,
+                                 tau=tau)                                                                       # :434,438
             if pseudo:
                 count += self.project(self.u, energy=diagnostics)                # :415  Project(gfu)
             its_p.append(count)
@@ -455,7 +626,12 @@ class TimeStepper(FusedLoop):
             if diagnostics:
                 self.write_record(record, step)
             if scalar is not None:
-                its_s.append(scalar.step(record_s, step))                         # S2, the solve, S3, S4
+                its_s.append(scalar.step(record_s, step, tau))                    # S2, the solve, S3, S4
+            if not pseudo:
+                tau_prev = self.timestep if tau is None else tau
+        nsteps = len(its_m)                                               # (a duration may end the call early)
+        if clock is not None and nsteps:
+            clock.tau_prev = tau_prev
         eng.copy(self.u, gfu.buf)
         if cnab2 and nsteps:
             eng.copy(self.q, gfup.buf)
@@ -468,15 +644,21 @@ class TimeStepper(FusedLoop):
             eng.copy(self.phi, gfup.buf)
         if scalar is not None:
             eng.copy(scalar.T, temperature.buf)
+        if failure is not None:                                           # the state of the last finished step is back
+            raise failure
         div = energy = wall = None
-        if diagnostics:
-            host = eng.to_host(record)                                    # the one read-back
-            vel = host[:2 * slots].reshape(-1, 2)[:nsteps]
-            div, energy = vel[:, 1].copy(), vel[:, 0].copy()
-            if record_s is not None:
-                wall = host[2 * slots:][:nsteps].copy()
+        extra = {}
+        if buf is not None:
+            host = eng.to_host(buf)                                       # the one read-back
+            if diagnostics:
+                vel = host[:2 * slots].reshape(-1, 2)[:nsteps]
+                div, energy = vel[:, 1].copy(), vel[:, 0].copy()
+                if record_s is not None:
+                    wall = host[2 * slots:3 * slots][:nsteps].copy()
+            if self.variable:
+                extra = variable_record(taus, host[nrec:], codes)
         return StepRecord(its_m, its_p, div, energy, flux_declined=self.flux_declined, convection=self.convection,
-                          scalar_iterations=its_s, wall_flux=wall, time_scheme=self.time_scheme)
+                          scalar_iterations=its_s, wall_flux=wall, time_scheme=self.time_scheme, **extra)
 
 
 class ScalarStepper:
@@ -495,13 +677,18 @@ class ScalarStepper:
     PRECISION, MAXSTEPS = 1e-4, 500          # those of invmstar: the same kind of operator
 
     def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
-                 maxsteps=None, shared=None, convection="upwind", stencil=None, time_scheme="euler"):
+                 maxsteps=None, shared=None, convection="upwind", stencil=None, time_scheme="euler", variable=False):
         """`ops`: `StokesSystem.scalar_operators(...)`; `B`: the divergence (`SparseMatrix`); `f`: the force `Vector`
         the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
         (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
-        `inner_pre`.  `convection`, `stencil`: the scheme of S1 and, for a limited one, `scalar_stencil()` (`ScalarFlux`)."""
+        `inner_pre`.  `convection`, `stencil`: the scheme of S1 and, for a limited one, `scalar_stencil()` (`ScalarFlux`).
+        `variable`: a variable-step stepper -- no mstar / mhalf: the shifted `CgLoop` over K ("K" of `shared`, uploaded
+        when missing) with the sigma of each step, Jacobi only."""
         import scipy.sparse as sp
         shared = {} if shared is None else shared
+        self.variable = bool(variable)
+        if variable and inner_pre != "jacobi":
+            raise ValueError("ScalarStepper: a variable-step stepper takes inner_pre=\"jacobi\"")
         self.time_scheme = check_time_scheme(time_scheme, "ScalarStepper")
         cnab2 = time_scheme == "cnab2"
         if cnab2 and not ScalarFlux.available_ab2(eng, convection):
@@ -520,10 +707,16 @@ class ScalarStepper:
             shared["w_b"] = None if w_b is None else eng.from_host(np.asarray(w_b, dtype=np.float64))
             shared["w"] = None if flux is None else eng.from_host(np.asarray(flux[1], dtype=np.float64))
         mstar_key = "mhalf" if cnab2 else "mstar"
-        if mstar_key not in shared:                 # M_p + timestep K, or the half-step operator M_p + timestep/2 K
+        if variable:
+            if "K" not in shared:
+                shared["K"] = SparseMatrix.from_scipy(sp.csr_matrix(ops["K"]), engine=eng)
+            if "diagK" not in shared:
+                shared["diagK"] = eng.from_host(sp.csr_matrix(ops["K"]).diagonal())
+        elif mstar_key not in shared:               # M_p + timestep K, or the half-step operator M_p + timestep/2 K
             theta = 0.5 * self.timestep if cnab2 else self.timestep
             shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + theta * ops["K"]).tocsr(), engine=eng)
-        self.KB, self.mstar, self.q, self.w_b, self.w = (shared[key] for key in ("KB", mstar_key, "q", "w_b", "w"))
+        self.KB, self.q, self.w_b, self.w = (shared[key] for key in ("KB", "q", "w_b", "w"))
+        self.mstar = None if variable else shared[mstar_key]
         self.c0, self.records = (0.0 if flux is None else float(flux[0])), flux is not None
         self.tg = eng.zeros(self.n_p + self.n_u)             # the operand [T | G]
         self.T, self.G = eng.view(self.tg, 0, self.n_p), eng.view(self.tg, self.n_p, self.n_p + self.n_u)
@@ -532,8 +725,12 @@ class ScalarStepper:
             self.G_prev = eng.zeros(self.n_u)
             self.b_prev = None if w_b is None else eng.zeros(self.n_u)
         self.temp, self.delta = eng.zeros(self.n_p), eng.zeros(self.n_p)
-        self.pre = SmoothedAggregationAMG(self.mstar) if inner_pre == "amg" else JacobiPreconditioner(self.mstar)
-        self.cg = CgLoop(eng, self.mstar, pre_for("cg", self.pre))
+        if variable:
+            self.pre = None
+            self.cg = CgLoop(eng, shared["K"], NO_PRE, shift=(ops["mass"], shared["diagK"]))
+        else:
+            self.pre = SmoothedAggregationAMG(self.mstar) if inner_pre == "amg" else JacobiPreconditioner(self.mstar)
+            self.cg = CgLoop(eng, self.mstar, pre_for("cg", self.pre))
         count = C.c_int64()
         eng._check(self.lib.nss_scalar_workspace(self.n_p, C.byref(count)))
         self.n_partials = count.value
@@ -562,14 +759,17 @@ class ScalarStepper:
             self.eng.copy(self.b_prev, history.vector("b_prev", self.n_u, self.eng).buf)
         history.valid["scalar"] = True
 
-    def step(self, record, slot):
-        """S2, the solve, S3 and (with `record`) S4.  Returns the CG iterations."""
+    def step(self, record, slot, tau=None):
+        """S2, the solve, S3 and (with `record`) S4; `tau`: the size of a variable step (None: the stepper's timestep).
+        Returns the CG iterations."""
         eng, lib = self.eng, self.lib
+        if self.variable:
+            self.cg.set_shift(0.5 * tau if self.time_scheme == "cnab2" else tau)
         eng._check(lib.nss_step_rhs_f64(self.KB.handle.ptr, self.tg.data_ptr(), self.q.data_ptr(), self.temp.data_ptr(),
                                         None, eng.stream))
         its = self.cg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
         write = record is not None
-        eng._check(lib.nss_scalar_update_f64(self.n_p, self.timestep, self.delta.data_ptr(), self.T.data_ptr(),
+        eng._check(lib.nss_scalar_update_f64(self.n_p, self.timestep if tau is None else tau, self.delta.data_ptr(), self.T.data_ptr(),
                                              _ptr(self.w if write else None), _ptr(self.partials if write else None),
                                              self.partials.numel() if write else 0, None, eng.stream))
         if write:

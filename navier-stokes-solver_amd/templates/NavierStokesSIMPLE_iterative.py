@@ -30,7 +30,9 @@ convection term ``conv_operator * gfu`` (:106-113,427-431): conservative upwind 
 ``NavierStokes(..., convection="minmod" | "vanleer")`` second-order limited upwind fluxes (one stencil launch, one SpMV).
 ``NavierStokes(..., time_scheme="cnab2")`` makes the step second order in time (not in the reference): Crank-Nicolson
 for the viscous term, two-step Adams-Bashforth for convection and buoyancy, an incremental pressure in ``gfup``
-(`NavierStokes._do_time_step_cnab2`).
+(`NavierStokes._do_time_step_cnab2`).  ``CflRate()`` reports the CFL number of the current velocity
+per unit of step size; ``DoTimeStep(timestep=)``, ``Advance(timesteps=)`` and ``Advance(cfl=)`` take steps of other
+sizes than the constructor's, the last one chosen from that rate (not in the reference).
 
 Out of scope: the MCS/HDG assembly itself and the sparse direct branch
 ``iterative=False`` (raises ``NotImplementedError``)."""
@@ -40,8 +42,8 @@ import scipy.sparse as sp
 
 import hipla
 from hipla import BlockVector, CGSolver, fused
-from hipla.stepping import (MomentumFlux, ScalarFlux, ScalarStepper, StepRecord, TimeHistory, TimeStepper,
-                            check_convection, check_time_scheme, pair)
+from hipla.stepping import (CflRate, MomentumFlux, ScalarFlux, ScalarStepper, StepController, StepRecord, TimeHistory,
+                            TimeStepper, check_convection, check_step_size, check_time_scheme, pair, variable_record)
 from discretizations import AssembledForm, CondensedForm, SyntheticMesh, assemble, bdm_hybrid
 from solvers.bramblepasciak_new import BramblePasciakCG
 
@@ -222,11 +224,27 @@ class ScalarField:
         self.avgT, self.difT, self.G, self.f_eff = (self.avg.CreateColVector() for _ in range(4))
         self.temp, self.delta = b_mat.CreateColVector(), b_mat.CreateColVector()
         self.steppers, self.shared = {}, {}
+        self.by_step = {}                 # step size -> the CG inverse of M_p + theta K (`DoTimeStep(timestep=)`)
+        self.last_solver = None
 
     @property
     def solver(self):
         """The CG inverse of the scheme's operator: M_p + timestep K, or M_p + timestep/2 K."""
         return self.inv_half if self.time_scheme == "cnab2" else self.inv
+
+    def solver_for(self, tau):
+        """The CG inverse for a step of size `tau` (None: the object's own), at the precision of `solver`; built with
+        Jacobi-CG on the host on first use and kept by step size."""
+        if tau is None:
+            self.last_solver = self.solver
+            return self.solver
+        if tau not in self.by_step:
+            theta = 0.5 * tau if self.time_scheme == "cnab2" else tau
+            mat = hipla.SparseMatrix.from_scipy((sp.diags(self.ops["mass"]) + theta * self.ops["K"]).tocsr())
+            self.by_step[tau] = CGSolver(mat, pre=hipla.JacobiPreconditioner(mat))
+        inv = self.last_solver = self.by_step[tau]
+        inv.precision, inv.maxsteps = self.solver.precision, self.solver.maxsteps
+        return inv
 
     def wall_flux(self, temperature):
         """The heat entering through `flux_wall`: c0 - <w, T>."""
@@ -254,6 +272,10 @@ class NavierStokes:
         self.convection = check_convection(convection, "NavierStokes")
         self.time_scheme = check_time_scheme(time_scheme, "NavierStokes")
         self._history = TimeHistory() if time_scheme == "cnab2" else None
+        self._clock = self._history or TimeHistory()      # holds `tau_prev`, the size of the last step, for both schemes
+        self._by_step = {}                # step size -> the CG inverse of M_u + theta A (`DoTimeStep(timestep=)`)
+        self._last_momentum_solver = None
+        self._cfl_rate = None
         self.last_stages = None
         self._stepping_cnab2 = None       # the operators "cnab2" adds to `_time_stepping_operators`, built on first use
         self.mesh, self.nu, self.timestep, self.order = mesh, nu, timestep, order
@@ -333,6 +355,44 @@ class NavierStokes:
         does.  The accumulated pressure in `gfup` is left alone.  (For "euler" there is nothing to forget.)"""
         if self._history is not None:
             self._history.reset()
+        self._clock.tau_prev = None
+
+    def CflRate(self):
+        """max_r (|B| |u|)_r / (M_p)_r of the current `gfu`: on the plain grid max_cell sum_faces |u_f| / h, so that
+        `timestep * CflRate()` is the quantity of the README's stability limits.  One kernel over the rows of B on the HIP
+        engine (one double read back), numpy otherwise."""
+        eng = self.gfu.engine
+        if fused.ENABLED and hasattr(getattr(eng, "lib", None), "nss_step_cfl_f64") and \
+                isinstance(self.b.mat, hipla.SparseMatrix):
+            if self._cfl_rate is None:
+                self._cfl_rate = CflRate(eng, self.b.mat, self.system.mass)
+            return self._cfl_rate(self.gfu.buf)
+        rate = (abs(self.system.B) @ np.abs(self.gfu.numpy())) / self.system.mass
+        return float(np.inf) if not np.isfinite(rate).all() else float(rate.max(initial=0.0))
+
+    def _momentum_solver_for(self, tau):
+        """The CG inverse of the velocity solve for a step of size `tau` (None: the object's own operators), at the
+        precision of the object's own; built with Jacobi-CG on the host on first use and kept by step size."""
+        held, name = self._momentum_solver()
+        if tau is None:
+            self._last_momentum_solver = held[name]
+            return held[name]
+        if tau not in self._by_step:
+            s = self.system
+            theta = 0.5 * tau if self.time_scheme == "cnab2" else tau
+            mat = hipla.SparseMatrix.from_scipy((sp.diags(np.full(s.n_u, s.h ** s.dim * self.V.dofs_per_site ** 0))
+                                                 + theta * s.A).tocsr())
+            self._by_step[tau] = CGSolver(mat, pre=hipla.JacobiPreconditioner(mat))
+        inv = self._last_momentum_solver = self._by_step[tau]
+        inv.precision, inv.maxsteps = held[name].precision, held[name].maxsteps
+        return inv
+
+    def _step_size(self, timestep):
+        """`timestep` of `DoTimeStep` as the key of the operators: None for the object's own step size."""
+        if timestep is None:
+            return None
+        tau = check_step_size(timestep, "DoTimeStep")
+        return None if tau == self.timestep else tau
 
     @property
     def velocity(self):
@@ -459,21 +519,27 @@ class NavierStokes:
             sc.device_flux = ScalarFlux(eng, sc.ops, sc.convection, sc.stencil, sc.shared)
         sc.device_flux.launch(self.gfu.buf, None, self.temperature.buf, 0.0, sc.G.buf)
 
-    def _scalar_step(self):
+    def _scalar_step(self, tau=None):
         """The last statements of a step with a scalar: temp_T = q - K T - B G;  delta = (M_p + timestep K)^-1 temp_T;
         T += timestep * delta."""
         sc = self._scalar
         sc.temp.data = sc.q - sc.K * self.temperature
         sc.temp.data -= self.b.mat * sc.G
-        sc.delta.data = sc.inv * sc.temp
-        self.temperature.data += self.timestep * sc.delta
+        sc.delta.data = sc.solver_for(tau) * sc.temp
+        self.temperature.data += (self.timestep if tau is None else tau) * sc.delta
 
-    def DoTimeStep(self):
+    def DoTimeStep(self, timestep=None):
         """One IMEX step (:424-438): temp = conv(u) + f - A u;  temp2 = invmstar temp;
         Project(temp2);  u += timestep * temp2.  With a scalar (`AddScalar`) its flux and force statements come first
-        and its own step last."""
+        and its own step last.
+
+        `timestep`: the size of this step (None: the object's).  Another size than the object's solves with
+        `M_u + theta A` (and the scalar's operator) for that size, built with Jacobi-CG at the precisions of the object's
+        own solvers on first use and kept by step size; "cnab2" extrapolates with the variable-step weights
+        (1 + r/2, -r/2), r = timestep / the size of the last step."""
+        tau = self._step_size(timestep)
         if self.time_scheme == "cnab2":
-            return self._do_time_step_cnab2()
+            return self._do_time_step_cnab2(tau)
         ops = self._time_stepping_operators()
         force = self.f.vec if self._scalar is None else self._scalar_flux()
         temp = self.a.mat.CreateColVector()
@@ -481,11 +547,12 @@ class NavierStokes:
         temp.data = self.conv_operator * self.gfu        # :429
         temp.data += force
         temp.data += -self.a.mat * self.gfu
-        temp2.data = ops["invmstar"] * temp
+        temp2.data = self._momentum_solver_for(tau) * temp
         self.Project(temp2)
-        self.gfu.data += self.timestep * temp2
+        self.gfu.data += (self.timestep if tau is None else tau) * temp2
         if self._scalar is not None:
-            self._scalar_step()
+            self._scalar_step(tau)
+        self._clock.tau_prev = self.timestep if tau is None else tau
 
     def _extrapolate(self, now, prev, weights, out):
         """out = w_new now + w_old prev;  prev = now  (w_old == 0: `prev` is not read)."""
@@ -496,7 +563,7 @@ class NavierStokes:
             out.data = w_new * now
         prev.data = now
 
-    def _do_time_step_cnab2(self):
+    def _do_time_step_cnab2(self, tau=None):
         """One step of `time_scheme="cnab2"`, with (w_new, w_old) = (1, 0) on a quantity's first step and (3/2, -1/2)
         afterwards and q = `gfup`, the accumulated pressure:
 
@@ -506,41 +573,44 @@ class NavierStokes:
 
         With a scalar, before: G_ext and b = w_b (avg T^n - t_ref) extrapolated the same way, f_step = f + b_ext; after:
         delta = (M_p + timestep/2 K)^-1 (q_T - K T^n - B G_ext);  T^{n+1} = T^n + timestep delta.  `Project` is not
-        called: it overwrites `gfup`."""
+        called: it overwrites `gfup`.  `tau`: the size of this step (None: `timestep`, the object's); behind a step of
+        another size the weights are (1 + r/2, -r/2), r = this size / that one, and `tau` stands for `timestep` above."""
+        size = self.timestep if tau is None else tau
         conv = self.conv_operator
         if not hasattr(conv, "Flux"):
             raise ValueError("DoTimeStep: time_scheme=\"cnab2\" keeps its history in flux form and wants a conv_operator "
                              "with Flux(u, F)")
         ops, half, hist, eng = self._time_stepping_operators(), self._cnab2_operators(), self._history, self.gfu.engine
-        force = self.f.vec if self._scalar is None else self._scalar_flux_cnab2()
+        force = self.f.vec if self._scalar is None else self._scalar_flux_cnab2(size)
         F, F_ext = half["div"].CreateRowVector(), half["div"].CreateRowVector()
         conv.Flux(self.gfu, F)
-        self._extrapolate(F, hist.vector("F_prev", len(F), eng), hist.weights("momentum"), F_ext)
+        self._extrapolate(F, hist.vector("F_prev", len(F), eng), hist.weights("momentum", size), F_ext)
         hist.valid["momentum"] = True
         temp, raw, temp2 = (self.a.mat.CreateColVector() for _ in range(3))
         rhs, phi = self.b.mat.CreateColVector(), self.gfup.CreateVector()
         temp.data = force - self.a.mat * self.gfu
         temp.data -= half["div"] * F_ext
         temp.data -= half["Bt"] * self.gfup
-        raw.data = half["invmhalf"] * temp
+        raw.data = self._momentum_solver_for(tau) * temp
         rhs.data = self.b.mat * raw
         phi.data = ops["invproj"] * rhs
         temp2.data = raw - ops["correct"] * phi
         self.gfup.data += phi
-        self.gfu.data += self.timestep * temp2
+        self.gfu.data += size * temp2
         self.last_stages = dict(F_ext=F_ext, temp=temp, raw=raw, phi=phi, temp2=temp2)      # of the last step, for checks
         if self._scalar is not None:
             sc = self._scalar
             sc.temp.data = sc.q - sc.K * self.temperature
             sc.temp.data -= self.b.mat * sc.G_ext
-            sc.delta.data = sc.inv_half * sc.temp
-            self.temperature.data += self.timestep * sc.delta
+            sc.delta.data = sc.solver_for(tau) * sc.temp
+            self.temperature.data += size * sc.delta
+        hist.tau_prev = size
 
-    def _scalar_flux_cnab2(self):
+    def _scalar_flux_cnab2(self, size=None):
         """The scalar's first statements of a "cnab2" step on (u^n, T^n): G into G_ext / G_prev, and the force of the
         step, f + w_new b + w_old b_prev with b = w_b (avg T - t_ref) (f itself for a passive scalar)."""
         sc, hist, eng = self._scalar, self._history, self.gfu.engine
-        weights = hist.weights("scalar")
+        weights = hist.weights("scalar", size)
         sc.avgT.data = sc.avg * self.temperature
         if sc.convection == "upwind":
             sc.difT.data = sc.diff * self.temperature
@@ -567,7 +637,8 @@ class NavierStokes:
         self.gfup.data = ops["invproj"] * rhs
         vel.data -= ops["correct"] * self.gfup
 
-    def Advance(self, nsteps, inner_pre="jacobi", precision=None, diagnostics=True, pseudo=False, maxsteps=None):
+    def Advance(self, nsteps, inner_pre="jacobi", precision=None, diagnostics=True, pseudo=False, maxsteps=None, *,
+                timesteps=None, cfl=None, max_timestep=None, growth=1.25, duration=None):
         """`nsteps` IMEX steps (`pseudo=True`: the pseudo time stepping of ``SolveInitial(timesteps=nsteps)``) through
         the device-resident stepper (`hipla.stepping.TimeStepper`): the statements of `DoTimeStep` / `Project` in two
         launches for the right-hand side and one for the projection tail, every buffer allocated once, a per-step
@@ -589,14 +660,42 @@ class NavierStokes:
         `time_scheme="cnab2"`: the stepper runs the statements of `_do_time_step_cnab2`; it shares `M_u + timestep/2 A`
         with `DoTimeStep`, keeps `[A | D | B^T]` in the place of `[A | D]` and reads and writes
         the object's history and `gfup`, so that `DoTimeStep` and `Advance` can be mixed freely.  It declines when the flux
-        kernel declines the convection operators.  `pseudo=True` runs the "euler" stepper's relaxation, as ever."""
+        kernel declines the convection operators.  `pseudo=True` runs the "euler" stepper's relaxation, as ever.
+
+        Variable steps: `timesteps` = `nsteps` prescribed sizes, or `cfl` = the target for
+        tau_n * `CflRate()` of u^n, with tau_n = min(`max_timestep` (None: the constructor's `timestep`), cfl / rate,
+        `growth` (1.25) times the last step) chosen by `hipla.stepping.choose_timestep`; `duration` ends the call when the
+        time reaches it -- the last step is shortened to land on it, `nsteps` stays the cap.  The record then has
+        `timestep`, `time`, `cfl` and (with `cfl=`) `limited_by`.  These steps run through steppers of their own, which
+        solve with `M_u + sigma A` read from A itself (the shifted CG loop), Jacobi only: ``ValueError`` with
+        `inner_pre="amg"` (a hierarchy belongs to one step size) or `pseudo=True`.  "cnab2" extrapolates with the weights
+        (1 + r/2, -r/2), r = tau_n / tau_{n-1}.  A rate that is not finite leaves the state of the last finished step in
+        `gfu` and raises ``FloatingPointError``.  Fixed and variable calls and `DoTimeStep` mix freely."""
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
         if pseudo and self._scalar is not None:
             raise ValueError("Advance: the pseudo time stepping carries no scalar")
+        nsteps = int(nsteps)
+        variable = timesteps is not None or cfl is not None
+        controller = None
+        if timesteps is not None and cfl is not None:
+            raise ValueError("Advance: timesteps and cfl exclude each other")
+        if cfl is None and not (duration is None and growth == 1.25 and max_timestep is None):
+            raise ValueError("Advance: duration, growth and max_timestep belong to cfl=")
+        if variable and (inner_pre == "amg" or pseudo):
+            raise ValueError("Advance: variable steps take inner_pre=\"jacobi\" (a hierarchy belongs to one step size) "
+                             "and no pseudo time stepping")
+        if timesteps is not None:
+            timesteps = [check_step_size(t, "Advance") for t in timesteps]
+            if len(timesteps) != nsteps:
+                raise ValueError("Advance: timesteps holds %d sizes for %d steps" % (len(timesteps), nsteps))
+        if cfl is not None:
+            controller = StepController(cfl, self.timestep if max_timestep is None else max_timestep,
+                                        growth, duration)
         steppers = self.__dict__.setdefault("_steppers", {})
         scheme = "euler" if pseudo else self.time_scheme
         key = inner_pre if scheme == self.time_scheme else (inner_pre, scheme)
+        key = ("variable", key) if variable else key
         stepper = steppers.get(key) if fused.ENABLED else None
         if stepper is None:
             s = self.system
@@ -608,27 +707,34 @@ class NavierStokes:
                     self._stepper_shared["mhalf"] = self._cnab2_operators()["mhalf"]
             stepper = TimeStepper.try_create(s, self.a.mat, self.b.mat, self.f.vec, self.timestep, m_u, inner_pre,
                                              conv_operator=lambda: self.conv_operator, shared=self._stepper_shared,
-                                             convection=self.convection, time_scheme=scheme)
+                                             convection=self.convection, time_scheme=scheme, variable=variable,
+                                             m_p=self.system.mass)
             if stepper is not None:
                 steppers[key] = stepper
         self.advance_declined = TimeStepper.last_declined if stepper is None else None
         if stepper is not None and self._scalar is not None:
             sc = self._scalar
-            if inner_pre not in sc.steppers:
-                sc.steppers[inner_pre] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
-                                                       inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
-                                                       shared=sc.shared, convection=sc.convection, stencil=sc.stencil,
-                                                       time_scheme=self.time_scheme)
+            skey = "variable" if variable else inner_pre
+            if skey not in sc.steppers:
+                sc.steppers[skey] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
+                                                  inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
+                                                  shared=sc.shared, convection=sc.convection, stencil=sc.stencil,
+                                                  time_scheme=self.time_scheme, variable=variable)
             return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics,
-                                   scalar=sc.steppers[inner_pre], temperature=self.temperature, history=self._history)
+                                   scalar=sc.steppers[skey], temperature=self.temperature, history=self._history,
+                                   timesteps=timesteps, controller=controller, clock=self._clock)
         if stepper is not None:
             return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics, pseudo,
-                                   history=None if pseudo else self._history)
-        return self._advance_by_statements(int(nsteps), precision, maxsteps, diagnostics, pseudo, StepRecord)
+                                   history=None if pseudo else self._history, timesteps=timesteps, controller=controller,
+                                   clock=None if pseudo else self._clock)
+        return self._advance_by_statements(nsteps, precision, maxsteps, diagnostics, pseudo, StepRecord, timesteps,
+                                           controller)
 
-    def _advance_by_statements(self, nsteps, precision, maxsteps, diagnostics, pseudo, record_type):
+    def _advance_by_statements(self, nsteps, precision, maxsteps, diagnostics, pseudo, record_type, timesteps=None,
+                               controller=None):
         """`Advance` through `DoTimeStep` / `Project` themselves; the inner solvers take `precision` / `maxsteps` for
-        the duration of the call."""
+        the duration of the call.  With `timesteps` or a `controller`: the same sizes, or the same controller on
+        `CflRate()`, through `DoTimeStep(timestep=tau_n)`."""
         import contextlib
         import io
         ops = self._time_stepping_operators()
@@ -639,6 +745,8 @@ class NavierStokes:
             sv.precision = sv.precision if p is None else float(p)
             sv.maxsteps = sv.maxsteps if m is None else int(m)
         its_m, its_p, div, energy = [], [], [], []
+        variable = timesteps is not None or controller is not None
+        taus, rates, codes = [], [], None if controller is None else []
         sc = self._scalar
         its_s, wall = ([], []) if sc is not None else (None, None)
         mass_u = self.system.h ** self.system.dim
@@ -646,16 +754,28 @@ class NavierStokes:
             with contextlib.redirect_stdout(io.StringIO()):
                 if pseudo:
                     self.Project(self.gfu)
-                for _ in range(nsteps):
+                for step in range(nsteps):
                     if pseudo:
                         count = self._pseudo_time_step(ops)
+                    elif variable:
+                        rate = self.CflRate()
+                        chosen = (timesteps[step], None) if controller is None else \
+                            controller.next(rate, self._clock.tau_prev)
+                        if chosen is None:
+                            break
+                        taus.append(chosen[0])
+                        rates.append(rate)
+                        if controller is not None:
+                            codes.append(chosen[1])
+                        self.DoTimeStep(timestep=chosen[0])
+                        count = ops["invproj"].iterations
                     else:
                         self.DoTimeStep()
                         count = ops["invproj"].iterations
-                    its_m.append(solvers[0].iterations)
+                    its_m.append(solvers[0].iterations if pseudo else self._last_momentum_solver.iterations)
                     its_p.append(count)
                     if sc is not None:
-                        its_s.append(sc.solver.iterations)
+                        its_s.append(sc.last_solver.iterations)
                         if diagnostics and sc.flux is not None:
                             wall.append(sc.wall_flux(self.temperature))
                     if diagnostics:
@@ -670,4 +790,5 @@ class NavierStokes:
                            np.array(energy) if diagnostics else None, declined=self.advance_declined,
                            scalar_iterations=its_s, convection=self.convection,
                            time_scheme="euler" if pseudo else self.time_scheme,
+                           **(variable_record(taus, rates, codes) if variable else {}),
                            wall_flux=np.array(wall) if sc is not None and diagnostics and sc.flux is not None else None)
