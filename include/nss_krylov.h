@@ -835,6 +835,37 @@ NSS_API int nss_scalar_flux_limited_ab2_f64(const int32_t* stencil, int64_t nfac
                                             double w_new, double w_old, double* G_prev, double* G_ext, double* b_prev,
                                             double* f_eff, const int32_t* done, nss_stream_t stream);
 
+/* ---- fast diagonalisation of a Kronecker-sum operator ---------------------------------------------
+ * The direct pressure projection of `NavierStokes.SetProjection("fdm")` (not in the reference, whose projection is the
+ * CG solve of templates/NavierStokesSIMPLE_iterative.py:130,440-443): on a tensor-product grid of dim = 2 or 3 axes,
+ * extents e_a, cells in lexicographic order with the last axis fastest, an operator L = sum_a I (x) T_a (x) I with
+ * T_a = Q_a diag(lambda_a) Q_a^T is inverted by 2 dim contractions along one axis each (csrc/fdm.hip).  All fp64, no
+ * atomics, every sum over j ascending: the same bits every run.  Every shape is checked before anything is launched
+ * or allocated: an extent below 1 and more than 2^31 - 1 cells are refused.
+ *
+ * nss_fdm_contract_f64: one contraction, Y[o, i, c] = sum_j M[i, j] X[o, j, c] (transpose = 0) or sum_j M[j, i] X[o, j, c]
+ *   (transpose != 0); X, Y: DEVICE, contiguous (outer, n, inner), distinct buffers; M: DEVICE, row-major n x n.
+ * nss_fdm_contract_scaled_f64: the same with the diagonal scaling in its epilogue: Y of cell p is multiplied by
+ *   1 / s, s = (lambda_0[p_0] + lambda_1[p_1]) + lambda_2[p_2] of the multi-index of p in h_extents (HOST, dim entries,
+ *   their product outer * n * inner), or by 0 where |s| <= null_threshold; lam: DEVICE, the dim eigenvalue vectors one
+ *   after the other.
+ * nss_fdm_create: uploads h_Q[a] (HOST, row-major e_a x e_a, eigenvectors in columns) and h_lambda[a] (HOST, e_a) and
+ *   allocates the two work buffers of prod e_a doubles a solve ping-pongs between.
+ * nss_fdm_solve_f64: phi = Q [1 / s] Q^T rhs with Q = Q_0 (x) .. (x) Q_{dim-1}: dim launches with Q_a^T (the scaling
+ *   rides on the last of them), dim launches with Q_a, on `stream`, no synchronisation.  rhs (DEVICE) is not
+ *   modified; phi (DEVICE) may not be rhs.  Two solves with one handle in flight at once share the work buffers:
+ *   order them on one stream. */
+typedef struct nss_fdm_s* nss_fdm_t;
+NSS_API int nss_fdm_contract_f64(int64_t outer, int64_t n, int64_t inner, const double* M, int32_t transpose,
+                                 const double* x, double* y, nss_stream_t stream);
+NSS_API int nss_fdm_contract_scaled_f64(int64_t outer, int64_t n, int64_t inner, const double* M, int32_t transpose,
+                                        const double* x, double* y, int32_t dim, const int64_t* h_extents,
+                                        const double* lam, double null_threshold, nss_stream_t stream);
+NSS_API int nss_fdm_create(int32_t dim, const int64_t* h_extents, const double* const* h_Q,
+                           const double* const* h_lambda, double null_threshold, nss_fdm_t* out);
+NSS_API int nss_fdm_destroy(nss_fdm_t h);
+NSS_API int nss_fdm_solve_f64(nss_fdm_t h, const double* rhs, double* phi, nss_stream_t stream);
+
 /* ---- device-resident heat exponential integrator -------------------------------------------------
  * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
  * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:

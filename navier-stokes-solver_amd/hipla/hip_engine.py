@@ -152,6 +152,11 @@ def _signatures():
         "nss_scalar_workspace": (C.c_int, [i64, c_i64_p]),
         "nss_scalar_update_f64": (C.c_int, [i64, dbl, vp, vp, vp, vp, i64, vp, vp]),
         "nss_scalar_record_f64": (C.c_int, [vp, i64, dbl, vp, i32, vp, vp]),
+        "nss_fdm_contract_f64": (C.c_int, [i64, i64, i64, vp, i32, vp, vp, vp]),
+        "nss_fdm_contract_scaled_f64": (C.c_int, [i64, i64, i64, vp, i32, vp, vp, i32, c_i64_p, vp, dbl, vp]),
+        "nss_fdm_create": (C.c_int, [i32, c_i64_p, C.POINTER(vp), C.POINTER(vp), dbl, C.POINTER(vp)]),
+        "nss_fdm_destroy": (C.c_int, [vp]),
+        "nss_fdm_solve_f64": (C.c_int, [vp, vp, vp, vp]),
         "nss_heat_workspace": (C.c_int, [i64, i32, c_i64_p]),
         "nss_mgs_f64": (C.c_int, [i64, i32, i64, vp, i32, vp, vp, i64, vp]),
         "nss_galerkin_f64": (C.c_int, [vp, i32, i64, vp, vp, vp, i64, vp]),

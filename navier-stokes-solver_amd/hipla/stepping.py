@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import fused
+from . import fdm, fused
 from .amg import SmoothedAggregationAMG
 from .fused import NO_PRE, CgLoop, FusedLoop, _hip, pre_for
 from .matrix import JacobiPreconditioner, ScaledMatrix, SparseMatrix, SumMatrix
@@ -296,12 +296,15 @@ class StepRecord:
     its `flux_wall` after the step (None without a scalar / diagnostics).  `convection`: the momentum flux's scheme;
     `time_scheme`: "euler" or "cnab2" (the pseudo time stepping is a relaxation and records "euler").  With a
     variable-step argument of `Advance` (None otherwise): `timestep` = the step sizes tau_n, `time` = their running sum
-    within the call, `cfl` = tau_n * rate(u^n), and with `cfl=` also `limited_by` = the codes of `choose_timestep`."""
+    within the call, `cfl` = tau_n * rate(u^n), and with `cfl=` also `limited_by` = the codes of `choose_timestep`.
+    `projection`: "cg", or "fdm" -- the direct solve of `NavierStokes.SetProjection("fdm")`, whose `proj_iterations` are
+    all zero."""
 
     def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
                  scalar_iterations=None, wall_flux=None, convection="upwind", time_scheme="euler", timestep=None,
-                 time=None, cfl=None, limited_by=None):
+                 time=None, cfl=None, limited_by=None, projection="cg"):
         self.timestep, self.time, self.cfl, self.limited_by = timestep, time, cfl, limited_by
+        self.projection = projection
         self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
         self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
         self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
@@ -355,7 +358,10 @@ class TimeStepper(FusedLoop):
     `time_scheme="cnab2"` (second order): the operand is [u | F_ext | q] with the accumulated
     pressure q, the flux launch is the extrapolating one (F_ext = w_new F + w_old F_prev, F_prev = F), one launch over the
     rows of [A | D | B^T] forms temp = f - A u - D F_ext - B^T q, mstar is M_u + timestep/2 A, and one AXPY does
-    q += phi after the projection tail.  `advance` then takes the object's `TimeHistory`."""
+    q += phi after the projection tail.  `advance` then takes the object's `TimeHistory`.
+
+    `projection="fdm"`: phi comes from the 2 dim launches of ``nss_fdm_solve_f64`` in the place of
+    the second CG -- no iteration, no poll; the step then waits for the host in the velocity solve alone."""
 
     PRECISION, MAXSTEPS = (1e-4, 1e-8), (500, 5000)        # those of the template's CGSolvers invmstar / invproj
     momentum_flux = adv = avg = diff = stencil = None      # with `flux_declined`: no flux object, no flux operands
@@ -363,7 +369,7 @@ class TimeStepper(FusedLoop):
 
     @classmethod
     def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
-                   convection="upwind", time_scheme="euler", variable=False, m_p=None):
+                   convection="upwind", time_scheme="euler", variable=False, m_p=None, projection="cg"):
         """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
         `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
         solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
@@ -375,15 +381,32 @@ class TimeStepper(FusedLoop):
         stepper keeps its matrices under keys of their own ("mhalf", "ADBt") and declines when the flux kernel declines the
         convection operators.  `variable`: a variable-step stepper -- no mstar / mhalf: the velocity solve runs the shifted
         `CgLoop` over `A` with sigma = tau_n ("euler") or tau_n / 2 ("cnab2"), Jacobi only; `m_p`: host array, the lumped
-        pressure mass of the rate kernel (None: ones).  Returns None, the reason in `last_declined`."""
+        pressure mass of the rate kernel (None: ones).  `projection`: "cg", or "fdm" -- `project` then launches the direct
+        solve ``nss_fdm_solve_f64`` of a `hipla.fdm.FastDiagonalization` of Lp over the extents (system.n,) * system.dim,
+        kept under "fdm" in `shared` (built when missing; the stepper declines with the reason when Lp is no Kronecker
+        sum), and neither `cg_p` nor `pre_p` -- for "amg": the hierarchy of Lp -- is built.  Returns None, the reason in
+        `last_declined`."""
         return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection,
-                                            time_scheme, variable, m_p))
+                                            time_scheme, variable, m_p, projection))
+
+    @staticmethod
+    def _projection_matrices(eng, B, m_u, shared):
+        """C = M_u^-1 B^T and Lp = B C into `shared`, where missing."""
+        import scipy.sparse as sp
+        if "C" not in shared:
+            shared["C"] = SparseMatrix.from_scipy((sp.diags(1.0 / m_u) @ B.to_scipy().T).tocsr(), engine=eng)
+        if "Lp" not in shared:
+            lap_p = (B.to_scipy() @ shared["C"].to_scipy()).tocsr()
+            lap_p.sort_indices()
+            shared["Lp"] = SparseMatrix.from_scipy(lap_p, engine=eng)
 
     @classmethod
     def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme,
-                    variable=False, m_p=None):
+                    variable=False, m_p=None, projection="cg"):
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
+        if projection not in ("cg", "fdm"):
+            raise ValueError("projection is \"cg\" or \"fdm\"")
         if variable and inner_pre != "jacobi":
             raise ValueError("a variable-step stepper takes inner_pre=\"jacobi\": a hierarchy belongs to one step size")
         check_convection(convection, "TimeStepper")
@@ -406,14 +429,26 @@ class TimeStepper(FusedLoop):
                 return "cnab2: the flux kernel declines the convection operators: " + shared["flux_declined"]
         if variable and not hasattr(A.engine.lib, "nss_step_cfl_f64"):
             return "the library has no CFL rate kernel"
+        if projection == "fdm" and shared.get("fdm") is None:
+            if not fdm.available(A.engine):
+                return "the library has no fast diagonalisation"
+            cls._projection_matrices(A.engine, B, np.asarray(m_u, dtype=np.float64), shared)
+            made = fdm.FastDiagonalization.try_create(shared["Lp"], (system.n,) * system.dim, A.engine)
+            if made is None:
+                return "fdm: " + fdm.FastDiagonalization.last_declined
+            shared["fdm"] = made
         return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme, variable,
-                   m_p)
+                   m_p, projection)
 
     def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind",
-                 time_scheme="euler", variable=False, m_p=None):
+                 time_scheme="euler", variable=False, m_p=None, projection="cg"):
         import scipy.sparse as sp
         eng = self.eng = A.engine
         self.time_scheme, self.variable = time_scheme, bool(variable)
+        self.projection = projection
+        self.fdm = shared["fdm"] if projection == "fdm" else None
+        if self.fdm is not None and self.fdm.handle is None:
+            raise ValueError("TimeStepper: the FastDiagonalization holds no device handle")
         cnab2 = time_scheme == "cnab2"
         rows_key, mstar_key = ("ADBt", "mhalf") if cnab2 else ("AD", "mstar")
         self.lib, self.A, self.B, self.f, self.timestep = eng.lib, A, B, f, float(timestep)
@@ -446,12 +481,7 @@ class TimeStepper(FusedLoop):
         if not variable and mstar_key not in shared:   # M_u + timestep A, or the half-step operator M_u + timestep/2 A
             theta = 0.5 * self.timestep if cnab2 else self.timestep
             shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(m_u) + theta * A.to_scipy()).tocsr(), engine=eng)
-        if "C" not in shared:
-            shared["C"] = SparseMatrix.from_scipy((sp.diags(1.0 / m_u) @ B.to_scipy().T).tocsr(), engine=eng)
-        if "Lp" not in shared:
-            lap_p = (B.to_scipy() @ shared["C"].to_scipy()).tocsr()
-            lap_p.sort_indices()
-            shared["Lp"] = SparseMatrix.from_scipy(lap_p, engine=eng)
+        self._projection_matrices(eng, B, m_u, shared)
         self.mstar, self.Lp, self.C = None if variable else shared[mstar_key], shared["Lp"], shared["C"]
         if "singular" not in shared:
             ok, why = two_entry_rows(self.C.to_scipy())
@@ -459,20 +489,23 @@ class TimeStepper(FusedLoop):
                 raise ValueError("TimeStepper: M_u^-1 B^T: " + why)
             shared["singular"] = constants_in_kernel(self.Lp.to_scipy())
         self.singular = shared["singular"]
+        direct = self.fdm is not None               # the projection is the direct solve: no cg_p, no pre_p
         if variable:                                # the shifted loop over A: M_u + sigma A for the sigma of each step
             if "diagA" not in shared:
                 shared["diagA"] = eng.from_host(A.to_scipy().diagonal())
-            self.pre_m, self.pre_p = None, JacobiPreconditioner(self.Lp)
+            self.pre_m, self.pre_p = None, None if direct else JacobiPreconditioner(self.Lp)
             self.cg_m = CgLoop(eng, A, NO_PRE, shift=(m_u, shared["diagA"]))
             self.rate = CflRate(eng, B, m_p)
         else:
             if inner_pre == "amg":
                 self.pre_m = SmoothedAggregationAMG(self.mstar)
-                self.pre_p = SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
+                self.pre_p = None if direct else \
+                    SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
             else:
-                self.pre_m, self.pre_p = JacobiPreconditioner(self.mstar), JacobiPreconditioner(self.Lp)
+                self.pre_m = JacobiPreconditioner(self.mstar)
+                self.pre_p = None if direct else JacobiPreconditioner(self.Lp)
             self.cg_m = CgLoop(eng, self.mstar, pre_for("cg", self.pre_m))
-        self.cg_p = CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
+        self.cg_p = None if direct else CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
         # ---- the record ----
         uniform = bool(m_u.size) and bool((m_u == m_u[0]).all())
         self.mass = None if uniform else eng.from_host(m_u)
@@ -511,10 +544,13 @@ class TimeStepper(FusedLoop):
         """out = vel - C phi with phi = (B M_u^-1 B^T)^-1 B vel (`Project`; `out` None: in place); `update`:
         u += tau * out in the same launch (`tau` None: the stepper's timestep); `energy`: also the partials of
         <e, M_u e>, e = the updated u, or out.
-        Returns the CG iterations."""
+        Returns the CG iterations (0 for the direct solve of a "fdm" stepper, which ignores precision and maxsteps)."""
         eng, lib = self.eng, self.lib
         eng.csr_spmv(self.B.handle, 1.0, vel, 0.0, self.rhs_p)
-        its = self.cg_p.solve_resident(self.rhs_p, self.phi, self.precision[1], self.maxsteps[1])
+        if self.fdm is not None:
+            its = self.fdm.solve_resident(self.rhs_p, self.phi)
+        else:
+            its = self.cg_p.solve_resident(self.rhs_p, self.phi, self.precision[1], self.maxsteps[1])
         eng._check(lib.nss_step_project_f64(self.C.handle.ptr, self.phi.data_ptr(), vel.data_ptr(),
                                             (vel if out is None else out).data_ptr(), _ptr(update),
                                             self.timestep if tau is None else tau,
@@ -658,7 +694,8 @@ class TimeStepper(FusedLoop):
             if self.variable:
                 extra = variable_record(taus, host[nrec:], codes)
         return StepRecord(its_m, its_p, div, energy, flux_declined=self.flux_declined, convection=self.convection,
-                          scalar_iterations=its_s, wall_flux=wall, time_scheme=self.time_scheme, **extra)
+                          scalar_iterations=its_s, wall_flux=wall, time_scheme=self.time_scheme,
+                          projection=self.projection, **extra)
 
 
 class ScalarStepper:

@@ -33,6 +33,8 @@ for the viscous term, two-step Adams-Bashforth for convection and buoyancy, an i
 (`NavierStokes._do_time_step_cnab2`).  ``CflRate()`` reports the CFL number of the current velocity
 per unit of step size; ``DoTimeStep(timestep=)``, ``Advance(timesteps=)`` and ``Advance(cfl=)`` take steps of other
 sizes than the constructor's, the last one chosen from that rate (not in the reference).
+``SetProjection("fdm")`` replaces the CG solve of the projection by the direct solve of the fast diagonalisation method
+(`hipla.FastDiagonalization`; not in the reference).
 
 Out of scope: the MCS/HDG assembly itself and the sparse direct branch
 ``iterative=False`` (raises ``NotImplementedError``)."""
@@ -41,7 +43,7 @@ import numpy as np
 import scipy.sparse as sp
 
 import hipla
-from hipla import BlockVector, CGSolver, fused
+from hipla import BlockVector, CGSolver, FastDiagonalization, fused
 from hipla.stepping import (CflRate, MomentumFlux, ScalarFlux, ScalarStepper, StepController, StepRecord, TimeHistory,
                             TimeStepper, check_convection, check_step_size, check_time_scheme, pair, variable_record)
 from discretizations import AssembledForm, CondensedForm, SyntheticMesh, assemble, bdm_hybrid
@@ -289,6 +291,39 @@ class NavierStokes:
         self._conv_operator = None        # explicit convection term of the IMEX step (:106-113), built on first use
         self._stepping = None
         self._scalar = None               # the transported scalar (`AddScalar`)
+        self._projection = "cg"           # how `invproj` solves (`SetProjection`)
+        self._fdm = None                  # the `FastDiagonalization` of Lp, built by the first SetProjection("fdm")
+
+    @property
+    def projection(self):
+        """"cg" or "fdm": see `SetProjection`."""
+        return self._projection
+
+    def SetProjection(self, kind):
+        """How the pressure projection phi = (B M_u^-1 B^T)^-1 B vel is solved, from now on and in every entry point
+        (`Project`, `DoTimeStep`, `Advance`, the pseudo time stepping): "cg" (the default: the reference's Jacobi-CG to
+        1e-8, or what `Advance(inner_pre=)` asks for) or "fdm", the direct solve of the fast diagonalisation method --
+        `hipla.FastDiagonalization` of Lp over the extents (n,) * dim, built here on first use; ``ValueError`` with the
+        reason when Lp is not a Kronecker sum over these extents.  With "fdm" the projection reports 0 iterations and
+        ignores its entries of `precision` and `maxsteps`.  For the enclosed cavity the potential has mean zero: `gfup`
+        differs from the CG path's by a constant, the velocity does not (M_u^-1 B^T annihilates constants).
+        `SetProjection("cg")` puts the CG solver itself back."""
+        if kind not in ("cg", "fdm"):
+            raise ValueError("SetProjection: the projection is \"cg\" or \"fdm\", not %r" % (kind,))
+        if kind == "fdm" and self._fdm is None:
+            ops, s = self._time_stepping_operators(), self.system
+            made = FastDiagonalization.try_create(ops["Lp"], (s.n,) * s.dim)
+            if made is None:
+                raise ValueError("SetProjection: " + FastDiagonalization.last_declined)
+            self._fdm = made
+        self._projection = kind
+        ops = self._stepping              # (built above for "fdm"; None: no solver to swap yet)
+        if ops is None:
+            return
+        if kind == "fdm" and ops["invproj"] is not self._fdm:
+            self._invproj_cg, ops["invproj"] = ops["invproj"], self._fdm
+        elif kind == "cg" and ops["invproj"] is self._fdm:
+            ops["invproj"] = self._invproj_cg
 
     @property
     def conv_operator(self):
@@ -670,7 +705,12 @@ class NavierStokes:
         solve with `M_u + sigma A` read from A itself (the shifted CG loop), Jacobi only: ``ValueError`` with
         `inner_pre="amg"` (a hierarchy belongs to one step size) or `pseudo=True`.  "cnab2" extrapolates with the weights
         (1 + r/2, -r/2), r = tau_n / tau_{n-1}.  A rate that is not finite leaves the state of the last finished step in
-        `gfu` and raises ``FloatingPointError``.  Fixed and variable calls and `DoTimeStep` mix freely."""
+        `gfu` and raises ``FloatingPointError``.  Fixed and variable calls and `DoTimeStep` mix freely.
+
+        After `SetProjection("fdm")` the steppers (their own, keyed by the projection too) launch the direct solve of the
+        object's `FastDiagonalization` in the place of the projection's CG: ``record.projection == "fdm"``,
+        `proj_iterations` all zero, the projection entries of `precision` and `maxsteps` ignored, and for
+        `inner_pre="amg"` no hierarchy of the pressure operator."""
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
         if pseudo and self._scalar is not None:
@@ -696,6 +736,7 @@ class NavierStokes:
         scheme = "euler" if pseudo else self.time_scheme
         key = inner_pre if scheme == self.time_scheme else (inner_pre, scheme)
         key = ("variable", key) if variable else key
+        key = (key, "fdm") if self._projection == "fdm" else key
         stepper = steppers.get(key) if fused.ENABLED else None
         if stepper is None:
             s = self.system
@@ -705,10 +746,12 @@ class NavierStokes:
                 self._stepper_shared = dict(mstar=ops["mstar"], Lp=ops["Lp"], C=ops["correct"])
                 if self.time_scheme == "cnab2":
                     self._stepper_shared["mhalf"] = self._cnab2_operators()["mhalf"]
+            if self._projection == "fdm":
+                self._stepper_shared.setdefault("fdm", self._fdm)
             stepper = TimeStepper.try_create(s, self.a.mat, self.b.mat, self.f.vec, self.timestep, m_u, inner_pre,
                                              conv_operator=lambda: self.conv_operator, shared=self._stepper_shared,
                                              convection=self.convection, time_scheme=scheme, variable=variable,
-                                             m_p=self.system.mass)
+                                             m_p=self.system.mass, projection=self._projection)
             if stepper is not None:
                 steppers[key] = stepper
         self.advance_declined = TimeStepper.last_declined if stepper is None else None
@@ -789,6 +832,6 @@ class NavierStokes:
         return record_type(its_m, its_p, np.array(div) if diagnostics else None,
                            np.array(energy) if diagnostics else None, declined=self.advance_declined,
                            scalar_iterations=its_s, convection=self.convection,
-                           time_scheme="euler" if pseudo else self.time_scheme,
+                           time_scheme="euler" if pseudo else self.time_scheme, projection=self._projection,
                            **(variable_record(taus, rates, codes) if variable else {}),
                            wall_flux=np.array(wall) if sc is not None and diagnostics and sc.flux is not None else None)
