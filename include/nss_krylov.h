@@ -200,6 +200,18 @@ NSS_API int nss_csr_operand_form(nss_csr_t a, int32_t* form);
  * bits: only the partition of the rows into workgroups changes. */
 NSS_API int nss_csr_plan_for_blocks(nss_csr_t a, nss_bjac_t j, int32_t* planned);
 NSS_API int nss_csr_plan_for_pairs(nss_csr_t a, int32_t* pair_staged);
+/* Row slots: a matrix that is coded (nss_csr_code_values, codes in force), staged (form 2), one lane per row, without
+ * fp32 values or a dispatch-ordered table, and whose rows hold at most 8 entries can keep an eight-slot copy of itself
+ * -- per row one 16-byte word of staged positions and one 8-byte word of codes, 24 bytes per row of extra device memory
+ * beside the CSR arrays, which every other launch site keeps reading.  Two launch sites then take a row-per-lane
+ * kernel that holds a row's products in registers (csrc/csr_stream.h: csr_slots_kernel): nss_csr_spmv_f64 and C23 of
+ * nss_bpcg2_iterate (when both A and B hold a copy).  Identical bits to the stream kernel.  The copy belongs to ONE launch
+ * plan: every re-plan drops it, and a writer of the values drops it with the codes.  Set-up only (synchronises the device).
+ * mode 1: build wherever the matrix is eligible; -1: build where the codes are there by their size rule (automatic
+ * nss_csr_value_code_mode and at least 2^19 rows: the regime that is bound by bytes), leave alone a copy that exists
+ * and a handle that was refused; 0: drop the copy and refuse later -1 calls (until a call with mode 1); 2: only ask.
+ * *valid = whether a copy for the current launch plan exists that the kernels take now. */
+NSS_API int nss_csr_plan_row_slots(nss_csr_t a, int32_t mode, int32_t* valid);
 /* Launch-plan generation of `a`: 0 for the plan made at upload; every re-plan (the two calls above, and the joint
  * cycle of nss_amg_create_auxiliary over the matrices of its hierarchies) takes a fresh, larger value from one
  * process-wide counter.  A re-plan changes the row-block count, hence the dot partials every fused loop writes: each
@@ -541,6 +553,9 @@ NSS_API int nss_bpcg2_fold_mode(int32_t mode);
  * planned for it (tests, A/B runs).  nss_bpcg2_c1_applies_preA: what the next C1 of this state will do. */
 NSS_API int nss_bpcg2_fuse_block_jacobi(int32_t mode);
 NSS_API int nss_bpcg2_c1_applies_preA(const nss_bpcg2_t* s, int32_t* yes);
+/* what the next C23 of nss_bpcg2_iterate launches: 0 = the stream kernels over A and B in one launch, 1 = the row-slot
+ * kernels in one launch (both matrices hold a valid copy: nss_csr_plan_row_slots), 2 = two launches */
+NSS_API int nss_bpcg2_c23_form(const nss_bpcg2_t* s, int32_t* form);
 /* wait for the stream and read ctrl: done (0 running, 1 stop test fired, 2 breakdown
  * <s, K s> == 0 where the reference raises ZeroDivisionError, :226), iteration at which it
  * happened, last iteration whose history entry was written */

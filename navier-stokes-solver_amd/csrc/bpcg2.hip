@@ -1037,6 +1037,13 @@ bool c1_applies_block_jacobi(const nss_bpcg2_t& s) {
          !s.cond_HT && s.BT->jb_first && s.BT->jb_serial == s.pre_bjac->serial && s.pre_bjac->inv_sym && s.pre_bjac->run;
 }
 
+// C23 by the row-slot kernels: the single-GPU compact plan only (the slab loops and the condensed forms keep the stream
+// kernels), and only with BOTH matrices in that form
+static bool c23_row_slots(const nss_bpcg2_t& s) {
+  return !s.dist_compact && !s.ghost_mode && !s.ghost_p_mode && !s.local_sums && !s.cond_HT && takes_row_slots<EpiK2c>(*s.A) &&
+         takes_row_slots<EpiK3c>(*s.B);
+}
+
 void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const nss_dist_s* d) {
   const bool fold = fold_sums(s);
   switch (which) {
@@ -1075,6 +1082,8 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
     case NSS_BPCG2C_C23: {
       EpiK2c ea{s.ctrl, s.t0, s.s0, s.t2, s.partials_a};
       EpiK3c eb{s.ctrl, s.scal, s.t1, s.s0, s.s1, s.w1, s.t3, s.partials_b, it, s.n_p};
+      // single GPU, both matrices with a valid row-slot copy (nss_csr_plan_row_slots): the row-per-lane kernels, same bits
+      if (c23_row_slots(s) && launch_csr_slots_dual(*s.A, s.t1, ea, *s.B, s.t1, eb, st)) break;
       // (coded form of the shared launch only when BOTH matrices hold value codes; each of the two launches by itself)
       if (!launch_csr_dual<kCodes>(*s.A, s.t1, ea, *s.B, s.t1, eb, st)) {   // launch plans differ: two launches
         launch_csr<kCodes>(*s.A, s.t1, ea, st);
@@ -1168,6 +1177,16 @@ int nss_bpcg2_c1_applies_preA(const nss_bpcg2_t* s, int32_t* yes) {
   return guarded([&] {
     NSS_REQUIRE(s && s->BT && yes, "bpcg2_c1_applies_preA: NULL argument");
     *yes = c1_applies_block_jacobi(*s) ? 1 : 0;
+  });
+}
+
+int nss_bpcg2_c23_form(const nss_bpcg2_t* s, int32_t* form) {
+  return guarded([&] {
+    NSS_REQUIRE(s && s->A && s->B && form, "bpcg2_c23_form: NULL argument");
+    int ma = 0, mb = 0;
+    if (c23_row_slots(*s)) *form = 1;
+    else *form = csr_dual_forms(*s->A, *s->B, EpiX<EpiK2c>::type::kStageable, EpiX<EpiK3c>::type::kStageable,
+                                XPairable<EpiX<EpiK3c>::type>::value, &ma, &mb) ? 0 : 2;
   });
 }
 

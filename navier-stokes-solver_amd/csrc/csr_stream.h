@@ -21,6 +21,9 @@
 // L2 keeps one window of x instead of all eight L2s caching the same window.
 // Host side: launch_csr<FORMS> (one matrix), launch_csr_dual<FORMS> (two matrices in one launch) pick the instantiation
 // -- value form, kernel, column form, lanes per row -- for a matrix; every launch of the library goes through them.
+// Two further kernel forms serve short rows, one lane per row and no product buffer: csr_direct_kernel (at most two
+// entries per row, gathered operand; launch_csr takes it by itself) and csr_slots_kernel (coded matrices with at most
+// eight entries per row, staged operand; launch_csr_slots / launch_csr_slots_dual, asked for by two launch sites).
 #pragma once
 
 #include <type_traits>
@@ -68,6 +71,8 @@ constexpr int kDirectWidth = 2;        // entries per row of the fixed-width cop
 #define NSS_DIRECT_ROWS_PER_LANE 2
 #endif
 constexpr int kDirectRows = NSS_DIRECT_ROWS_PER_LANE * 256;   // rows per row block of such a matrix
+constexpr int kSlotWidth = 8;          // entries per row of the row-slot copy (csr_slots_kernel)
+constexpr unsigned kSlotPad = 0xffffu; // staged position of an unused slot (real positions are below the chunk)
 // Staged operand (nss_csr_s::blkseg): per row block at most kSegMax runs of consecutive columns, together at
 // most `chunk` columns (the LDS copy shares the product buffer), copied to LDS by LDS-DMA ahead of the matrix
 // stream.
@@ -260,10 +265,25 @@ struct nss_csr_s {
   double* dict = nullptr;
   uint16_t* ell_code = nullptr;
   int32_t dict_count = 0;
+  // Row slots (nss_csr_plan_row_slots): the eight-slot copy of a coded, staged matrix whose rows hold at most
+  // kSlotWidth entries, for the row-per-lane kernel of the staged operand (csr_slots_kernel).  Per row one aligned
+  // 16-byte word of kSlotWidth 16-bit staged positions (the values of pos16, CSR entry order, kSlotPad in unused slots)
+  // and one aligned 8-byte word of kSlotWidth value codes: 24 bytes per row where the CSR streams take 3 len + 4.  The
+  // positions are relative to the operand runs of ONE launch plan: slot_gen is the plan generation the copy was built
+  // for, replan() frees it, and a launcher takes it only through row_slots().  slot_state -1: refused by the caller
+  // (mode 0), automatic requests leave the handle alone.
+  uint16_t* slot_pos = nullptr;
+  uint8_t* slot_code = nullptr;
+  int64_t slot_gen = -1;
+  int slot_state = 0;
   uint64_t jb_serial = 0;
   // the kernels with a coded form take it (the grouped column streams have none: nss_csr_code_values refuses such a
   // matrix, and one that a re-plan groups later reads `val` again and reports so)
   bool coded() const { return val8 != nullptr && gb == 1 && nss::value_codes_enabled(); }
+  // a copy built for the current launch plan whose codes the kernels may read: the row-slot kernels take the matrix
+  bool row_slots() const {
+    return slot_pos != nullptr && slot_gen == plan_gen && coded() && blkseg && !ell_col && !val32 && !blkdisp && rg == 1;
+  }
   // `stageable`: the kernel's operand functor is one stored vector that can be copied to LDS (XOp::kStageable);
   // `pairable`: it is an expression of two (XOp::kStageablePair)
   int idx_mode(bool stageable = true, bool pairable = false) const {
@@ -519,6 +539,57 @@ __device__ __forceinline__ bool csr_phase1(const CsrView& a, const double* __res
   return true;
 }
 
+typedef const int32_t __attribute__((address_space(4))) * ConstI32;   // uniform, invariant reads: scalar loads
+
+// The operand runs of one row block -> LDS, by LDS-DMA (`d`: the block's descriptor, `total`: its word 5): a wave
+// instruction moves 64 x 16 bytes = 128 consecutive staged positions to wave-uniform base + 16 * lane; each lane
+// supplies the source address of its pair (segments start at even positions and have even lengths: spmv.hip).
+// IDX 2: the runs of the operand vector -> buf[0, total); IDX 3 (total <= CH / 2): the first vector's runs ->
+// buf[0, CH / 2), the second's -> buf[CH / 2, CH).  ptr() / ptr2() only: the epilogue's prologue has not run yet.  The
+// copies are tracked by vmcnt: every wave waits for its own before the barrier that publishes them.  Shared by the
+// stream kernel (the buffer then takes the products) and the row-slot kernel.
+template <class Epi, int IDX, int CH>
+__device__ __forceinline__ void stage_operand_runs(ConstI32 d, int total, const Epi& epi, const double* __restrict__ x,
+                                                   double* prod) {
+  using XOp = typename EpiX<Epi>::type;
+  const int tid = threadIdx.x;
+  int32_t seg_pre[kSegMax - 1], seg_off[kSegMax];
+#pragma unroll
+  for (int s = 0; s < kSegMax - 1; ++s) seg_pre[s] = d[kSegPre + s];
+#pragma unroll
+  for (int s = 0; s < kSegMax; ++s) seg_off[s] = d[kSegOff + s];
+  const int wave = tid / kWave, lane = tid % kWave;
+  if constexpr (IDX == 2) {
+    const double* __restrict__ src = EpiX<Epi>::get(epi, x).ptr();
+#pragma unroll
+    for (int j = 0; j < CH / (2 * kBlock); ++j) {
+      const int base = j * 2 * kBlock + wave * 2 * kWave;
+      const int pos = base + 2 * lane;
+      int o = seg_off[0];
+#pragma unroll
+      for (int s = 1; s < kSegMax; ++s) o = pos >= seg_pre[s - 1] ? seg_off[s] : o;
+      if (pos < total) __builtin_amdgcn_global_load_lds((GlobalSrc)(src + pos + o), (LdsDst)(prod + base), 16, 0, 0);
+    }
+  } else {
+    // pair: total <= CH / 2; the first vector's segments -> prod[0, CH/2), the second's -> prod[CH/2, CH)
+    const XOp x0 = EpiX<Epi>::get(epi, x);
+    const double* __restrict__ src1 = x0.ptr();
+    const double* __restrict__ src2 = x0.ptr2();
+#pragma unroll
+    for (int j = 0; j < CH / (4 * kBlock); ++j) {
+      const int base = j * 2 * kBlock + wave * 2 * kWave;
+      const int pos = base + 2 * lane;
+      int o = seg_off[0];
+#pragma unroll
+      for (int s = 1; s < kSegMax; ++s) o = pos >= seg_pre[s - 1] ? seg_off[s] : o;
+      if (pos < total) {
+        __builtin_amdgcn_global_load_lds((GlobalSrc)(src1 + pos + o), (LdsDst)(prod + base), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((GlobalSrc)(src2 + pos + o), (LdsDst)(prod + CH / 2 + base), 16, 0, 0);
+      }
+    }
+  }
+}
+
 // One workgroup = one row block: `wg` is the workgroup's index inside this launch's grid part.
 // IDX / GRP: the form of the column stream (csr_phase1).  They are template parameters of the kernels: a run-time
 // selection inside one kernel was tried (a fifth of the instantiations) and lost 6-10 % on the short-row
@@ -538,7 +609,6 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
   // the hardware dispatcher balances the tail better).
   const int lb = (wg & (kXcds - 1)) * a.per_xcd + (wg >> 3);
   int b = lb < a.nblk ? a.blk0 + lb : -1;
-  typedef const int32_t __attribute__((address_space(4))) * ConstI32;
   if constexpr (IDX >= 2) {
     // reuse-aware dispatch order: slot lb of the dispatch-ordered table names its row block (uniform scalar load)
     if (a.blkdisp != nullptr) b = ((ConstI32)(a.blkdisp + size_t(lb) * kSegWords))[kSegBlock];
@@ -560,45 +630,8 @@ __device__ __forceinline__ void csr_stream_body(const CsrView& a, const double* 
       cnt = d[3];
       const int total = d[5];                              // 0 for a row block that is one over-long row
       // The operand segments of this row block -> LDS (the product buffer, until every lane has taken its
-      // values), by LDS-DMA: a wave instruction moves 64 x 16 bytes = 128 consecutive staged positions to
-      // wave-uniform base + 16 * lane; each lane supplies the source address of its pair (segments start at
-      // even positions and have even lengths: spmv.hip).  Issued BEFORE the matrix stream, on which it does
-      // not depend; ptr() only: the prologue has not run yet.
-      int32_t seg_pre[kSegMax - 1], seg_off[kSegMax];
-#pragma unroll
-      for (int s = 0; s < kSegMax - 1; ++s) seg_pre[s] = d[kSegPre + s];
-#pragma unroll
-      for (int s = 0; s < kSegMax; ++s) seg_off[s] = d[kSegOff + s];
-      const int wave = tid / kWave, lane = tid % kWave;
-      if constexpr (IDX == 2) {
-        const double* __restrict__ src = EpiX<Epi>::get(epi, x).ptr();
-#pragma unroll
-        for (int j = 0; j < CH / (2 * kBlock); ++j) {
-          const int base = j * 2 * kBlock + wave * 2 * kWave;
-          const int pos = base + 2 * lane;
-          int o = seg_off[0];
-#pragma unroll
-          for (int s = 1; s < kSegMax; ++s) o = pos >= seg_pre[s - 1] ? seg_off[s] : o;
-          if (pos < total) __builtin_amdgcn_global_load_lds((GlobalSrc)(src + pos + o), (LdsDst)(prod + base), 16, 0, 0);
-        }
-      } else {
-        // pair: total <= CH / 2; the first vector's segments -> prod[0, CH/2), the second's -> prod[CH/2, CH)
-        const XOp x0 = EpiX<Epi>::get(epi, x);
-        const double* __restrict__ src1 = x0.ptr();
-        const double* __restrict__ src2 = x0.ptr2();
-#pragma unroll
-        for (int j = 0; j < CH / (4 * kBlock); ++j) {
-          const int base = j * 2 * kBlock + wave * 2 * kWave;
-          const int pos = base + 2 * lane;
-          int o = seg_off[0];
-#pragma unroll
-          for (int s = 1; s < kSegMax; ++s) o = pos >= seg_pre[s - 1] ? seg_off[s] : o;
-          if (pos < total) {
-            __builtin_amdgcn_global_load_lds((GlobalSrc)(src1 + pos + o), (LdsDst)(prod + base), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((GlobalSrc)(src2 + pos + o), (LdsDst)(prod + CH / 2 + base), 16, 0, 0);
-          }
-        }
-      }
+      // values).  Issued BEFORE the matrix stream, on which it does not depend.
+      stage_operand_runs<Epi, IDX, CH>(d, total, epi, x, prod);
     } else {
       r0 = a.rowblk[b];
       r1 = a.rowblk[b + 1];
@@ -828,7 +861,6 @@ __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int
   const int lb = (wg & (kXcds - 1)) * a.per_xcd + (wg >> 3);
   const int b = lb < a.nblk ? a.blk0 + lb : -1;
   if (b >= 0) {
-    typedef const int32_t __attribute__((address_space(4))) * ConstI32;
     const ConstI32 rb = (ConstI32)(a.rowblk + b);             // uniform, invariant: scalar loads
     const int r0 = rb[0], r1 = rb[1];
     bool go = true;
@@ -844,6 +876,135 @@ __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int
     if (!go) return;                                          // the prologue ended the workgroup (uniform)
   }
   epi.finish(b, red);
+}
+
+// Row-per-lane kernel with the STAGED operand, for the row-slot copy of a coded matrix (nss_csr_s::slot_pos): the third
+// kernel form.  With value codes a row block of 256 rows x 7 entries is 5 KB of matrix beside 9 KB of vectors, and the
+// stream form -- sixteen 1- and 2-byte loads per lane, three barriers, every product written to and read back from LDS,
+// a dependent per-row LDS loop -- is built for rows of 82 entries.  Here lane t takes rows r0 + t, r0 + t + 256, ...
+// one piece of 256 rows after the other (the stream kernel's lane -> row map at one lane per row, so `acc` and the
+// block partial are its too), holds the row's eight staged positions and codes in registers (one 16-byte and one
+// 8-byte load), and makes THREE dependent memory rounds: (1) descriptor, LDS-DMA of the operand runs, slot words,
+// epilogue operands, dictionary; (2) one wait + one barrier, eight LDS reads of the operand, eight of the dictionary;
+// (3) the stores.  Straight-line from the first load to the last product, as csr_direct_rows: one uniform branch between
+// full and partial pieces, partial ones load from a clamped valid row and predicate only row(); a padding slot reads
+// LDS position 0 and its product is discarded by a select.
+// Bits: the stream kernel adds prod[s] ... prod[e - 1] in order to 0.0, each a product rounded by its store; here the
+// products are rounded by mul_unfused and added in slot order, + 0.0 for an unused slot -- 0 + p is never -0, so
+// s + 0.0 == s for every partial sum.
+// LDS: the operand copy (CH doubles), the dictionary, `red`; no product buffer, no window table.
+typedef uint32_t uint4v __attribute__((ext_vector_type(4)));
+typedef uint32_t uint2v __attribute__((ext_vector_type(2)));
+
+template <bool FULL, class Epi, int IDX, int CH>
+__device__ __forceinline__ bool csr_slots_rows(const CsrView& a, const uint4v* __restrict__ spos,
+                                               const uint2v* __restrict__ scode, const double* __restrict__ x, Epi& epi,
+                                               int base, int r1, bool base_first, const double* xlds, double* red,
+                                               double* dict) {
+  using XOp = typename EpiX<Epi>::type;
+  using Pre = EpiPre<Epi>;
+  static_assert(kSlotWidth == 8, "csr_slots_rows is written for eight slots per row");
+  const int r = base + int(threadIdx.x);
+  const int rl = FULL ? r : (r < r1 ? r : r1 - 1);            // the row every load goes to
+  const uint4v pw = __builtin_nontemporal_load(spos + rl);
+  const uint2v cw = __builtin_nontemporal_load(scode + rl);
+  const typename Pre::type pre = Pre::fetch(epi, rl);
+  // behind the rows' loads (csr_direct_rows: in front, every wave waits for the two requesting waves' branch)
+  if (base_first) DictLds<Coded8>::request(a, dict);
+  if (base_first && !EpiPrologue<Epi>::run(epi, red)) return false;   // uniform over the workgroup
+  const XOp xop = EpiX<Epi>::get(epi, x);
+  // the one wait and barrier: the LDS-DMA copies (operand runs, dictionary) are awaited by their waves and published
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const uint32_t w[4] = {pw.x, pw.y, pw.z, pw.w};
+  const uint32_t cws[2] = {cw.x, cw.y};
+  bool live[kSlotWidth];
+  double xv[kSlotWidth], v[kSlotWidth];
+#pragma unroll
+  for (int k = 0; k < kSlotWidth; ++k) {
+    const uint32_t p = (w[k / 2] >> (16 * (k % 2))) & 0xffffu;
+    live[k] = p != kSlotPad;
+    const int q = live[k] ? int(p) : 0;
+    if constexpr (IDX == 3) xv[k] = xop.pair(xlds[q], xlds[CH / 2 + q]);
+    else xv[k] = xop.value(xlds[q]);
+    v[k] = dict[(cws[k / 4] >> (8 * (k % 4))) & 0xffu];
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int k = 0; k < kSlotWidth; ++k) {
+    const double p = mul_unfused(v[k], xv[k]);
+    sum += live[k] ? p : 0.0;
+  }
+  if (FULL || r < r1) Pre::row(epi, r, sum, pre);
+  return true;
+}
+
+// one workgroup = one row block (`wg`: the workgroup's index inside this launch's grid part; the stream kernel's map)
+template <class Epi, int IDX, int CH>
+__device__ __forceinline__ void csr_slots_body(const CsrView& a, const uint4v* __restrict__ spos,
+                                               const uint2v* __restrict__ scode, const double* __restrict__ x, Epi& epi,
+                                               int wg, double* xlds, double* red, double* dict) {
+  using XOp = typename EpiX<Epi>::type;
+  static_assert(IDX == 2 || IDX == 3, "the row-slot kernel takes the staged forms only");
+  static_assert(IDX != 2 || XOp::kStageable, "staged form with an operand that cannot be copied to LDS");
+  static_assert(IDX != 3 || XPairable<XOp>::value, "pair-staged form with an operand that is not a pair of vectors");
+  const int lb = (wg & (kXcds - 1)) * a.per_xcd + (wg >> 3);
+  const int b = lb < a.nblk ? a.blk0 + lb : -1;
+  if (b >= 0) {
+    const ConstI32 d = (ConstI32)(a.blkseg + size_t(b) * kSegWords);   // scalar loads (see csr_stream_body)
+    const int r0 = d[0], r1 = d[1], total = d[5];
+    stage_operand_runs<Epi, IDX, CH>(d, total, epi, x, xlds);
+    bool go = true;
+    if (r1 - r0 == kBlock) {
+      go = csr_slots_rows<true, Epi, IDX, CH>(a, spos, scode, x, epi, r0, r1, true, xlds, red, dict);
+    } else if (r1 - r0 < kBlock) {
+      if (r1 > r0) go = csr_slots_rows<false, Epi, IDX, CH>(a, spos, scode, x, epi, r0, r1, true, xlds, red, dict);
+    } else {
+      // rows of few entries: a row block of up to kMaxRowsPerBlock rows is walked in pieces (the operand copy stays)
+      for (int base = r0; go && base < r1; base += kBlock)
+        go = csr_slots_rows<false, Epi, IDX, CH>(a, spos, scode, x, epi, base, r1, base == r0, xlds, red, dict);
+    }
+    if (!go) return;                                          // the prologue ended the workgroup (uniform)
+  }
+  epi.finish(b, red);  // one dot partial per row block, in the stream kernel's slot
+}
+
+template <class Epi, int IDX, int CH = kChunk>
+__global__ __launch_bounds__(kBlock) void csr_slots_kernel(CsrView a, const uint4v* __restrict__ spos,
+                                                           const uint2v* __restrict__ scode,
+                                                           const double* __restrict__ x, Epi epi) {
+  __shared__ alignas(16) double xlds[CH];
+  __shared__ double red[kRedDoubles];
+  double* const dict = DictLds<Coded8>::get();
+  if (epi.skip()) return;
+  csr_slots_body<Epi, IDX, CH>(a, spos, scode, x, epi, int(blockIdx.x), xlds, red, dict);
+}
+
+// two matrices in one launch, the second one's workgroups first (csr_stream_dual_kernel)
+template <class EpiA, class EpiB, int IDXA, int IDXB, int CH = kChunk>
+__global__ __launch_bounds__(kBlock) void csr_slots_dual_kernel(CsrView a, CsrView b, const uint4v* __restrict__ apos,
+                                                                const uint2v* __restrict__ acode,
+                                                                const uint4v* __restrict__ bpos,
+                                                                const uint2v* __restrict__ bcode, int grid_a, int grid_b,
+                                                                const double* __restrict__ xa,
+                                                                const double* __restrict__ xb, EpiA ea, EpiB eb) {
+  __shared__ alignas(16) double xlds[CH];
+  __shared__ double red[kRedDoubles];
+  double* const dict = DictLds<Coded8>::get();
+#if NSS_DUAL_SECOND_FIRST
+  const bool first = int(blockIdx.x) >= grid_b;
+  const int wg = first ? int(blockIdx.x) - grid_b : int(blockIdx.x);
+#else
+  const bool first = int(blockIdx.x) < grid_a;
+  const int wg = first ? int(blockIdx.x) : int(blockIdx.x) - grid_a;
+#endif
+  if (first) {
+    if (ea.skip()) return;
+    csr_slots_body<EpiA, IDXA, CH>(a, apos, acode, xa, ea, wg, xlds, red, dict);
+  } else {
+    if (eb.skip()) return;
+    csr_slots_body<EpiB, IDXB, CH>(b, bpos, bcode, xb, eb, wg, xlds, red, dict);
+  }
 }
 
 // Value forms a launch site instantiates besides fp64 (the FORMS argument of the launchers below).  The value type is a
@@ -942,12 +1103,10 @@ inline void launch_csr_direct(const nss_csr_s& A, const double* x, const Epi& ep
   launch_csr<FORMS, true>(A, x, epi, st, b0, b1, dyn_lds);
 }
 
-// A and B in one launch when their launch plans agree (lanes per row, chunk) and the pair of column streams is
-// one of the instantiated ones; returns false (nothing launched) otherwise -- the caller then issues two launches.
-// FORMS & kCodes: instantiate the coded form too, taken when BOTH matrices are coded (otherwise both halves read `val`).
-template <unsigned FORMS = kF64, class EpiA, class EpiB>
-inline bool launch_csr_dual(const nss_csr_s& A, const double* xa, const EpiA& ea, const nss_csr_s& B, const double* xb,
-                            const EpiB& eb, hipStream_t st, size_t dyn_lds = 0) {
+// whether launch_csr_dual takes A and B in one launch, and the column-stream forms of the two halves (stage_a, stage_b,
+// pair_b: what the operands of the two epilogues admit)
+inline bool csr_dual_forms(const nss_csr_s& A, const nss_csr_s& B, bool stage_a, bool stage_b, bool pair_b, int* ma_out,
+                           int* mb_out) {
 #ifdef NSS_NO_DUAL        // measurements: the two halves as launches of their own
   return false;
 #endif
@@ -955,12 +1114,25 @@ inline bool launch_csr_dual(const nss_csr_s& A, const double* xa, const EpiA& ea
   if (A.ell_col || B.ell_col) return false;               // row-per-lane kernel: a launch of its own
   if (A.val32 || B.val32) return false;                   // fp32 values: the single-matrix launches (or their refusal)
   if (A.rg != B.rg || A.chunk != B.chunk) return false;
-  constexpr bool kStageA = EpiX<EpiA>::type::kStageable, kStageB = EpiX<EpiB>::type::kStageable;
-  constexpr bool kPairB = XPairable<typename EpiX<EpiB>::type>::value;
-  const int ma = A.idx_mode(kStageA);
-  int mb = B.idx_mode(kStageB, kPairB);
+  const int ma = A.idx_mode(stage_a);
+  int mb = B.idx_mode(stage_b, pair_b);
   if (mb == 3 && ma != 2) mb = B.col16 ? 1 : 0;           // the pair-staged half is only instantiated beside a staged one
   if ((ma == 0) != (mb == 0)) return false;               // a 4-byte stream only pairs with a 4-byte stream
+  *ma_out = ma;
+  *mb_out = mb;
+  return true;
+}
+
+// A and B in one launch when their launch plans agree (lanes per row, chunk) and the pair of column streams is
+// one of the instantiated ones; returns false (nothing launched) otherwise -- the caller then issues two launches.
+// FORMS & kCodes: instantiate the coded form too, taken when BOTH matrices are coded (otherwise both halves read `val`).
+template <unsigned FORMS = kF64, class EpiA, class EpiB>
+inline bool launch_csr_dual(const nss_csr_s& A, const double* xa, const EpiA& ea, const nss_csr_s& B, const double* xb,
+                            const EpiB& eb, hipStream_t st, size_t dyn_lds = 0) {
+  constexpr bool kStageA = EpiX<EpiA>::type::kStageable, kStageB = EpiX<EpiB>::type::kStageable;
+  constexpr bool kPairB = XPairable<typename EpiX<EpiB>::type>::value;
+  int ma = 0, mb = 0;
+  if (!csr_dual_forms(A, B, kStageA, kStageB, kPairB, &ma, &mb)) return false;
   const bool grp = ma != 0 && (A.gb > 1 || B.gb > 1);     // the grouped decode also reads a one-per-entry stream (gb == 1)
   const CsrView va = A.view(0, A.nblk, ma), vb = B.view(0, B.nblk, mb);
   const int ga = nss_csr_s::grid(A.nblk), gb = nss_csr_s::grid(B.nblk);
@@ -988,6 +1160,58 @@ inline bool launch_csr_dual(const nss_csr_s& A, const double* xa, const EpiA& ea
   if (kCodedForm && A.coded() && B.coded())               // both halves stream value codes
     return ladder(ValueTag<std::conditional_t<kCodedForm, Coded8, double>>{});
   return ladder(ValueTag<double>{});
+}
+
+// ---- the row-slot kernels: taken by exactly two launch sites (nss_csr_spmv_f64, C23 of nss_bpcg2_iterate) --------------
+// the staged form an epilogue's operand takes in the row-slot kernel: 2 (one stored vector), 3 (a pair), 0 (none)
+template <class Epi>
+constexpr int slots_idx() {
+  return EpiX<Epi>::type::kStageable ? 2 : (XPairable<typename EpiX<Epi>::type>::value ? 3 : 0);
+}
+// whether a launch of `Epi` over all rows of A goes to the row-slot kernel NOW: a copy valid for the current launch plan
+// and codes in force (nss_csr_s::row_slots), and the staged form of this operand in force (pair mode)
+template <class Epi>
+inline bool takes_row_slots(const nss_csr_s& A) {
+  constexpr int IDX = slots_idx<Epi>();
+  if (IDX == 0 || A.m == 0 || A.nblk == 0 || !A.row_slots()) return false;
+  return A.idx_mode(EpiX<Epi>::type::kStageable, XPairable<typename EpiX<Epi>::type>::value) == IDX;
+}
+inline const uint4v* slot_positions(const nss_csr_s& A) { return reinterpret_cast<const uint4v*>(A.slot_pos); }
+inline const uint2v* slot_codes(const nss_csr_s& A) { return reinterpret_cast<const uint2v*>(A.slot_code); }
+
+// A x into `epi` by the row-slot kernel; false (nothing launched) when A does not take it
+template <class Epi>
+inline bool launch_csr_slots(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st) {
+  constexpr int IDX = slots_idx<Epi>();
+  if constexpr (IDX == 0) return false;
+  else {
+    if (!takes_row_slots<Epi>(A)) return false;
+    hipLaunchKernelGGL((csr_slots_kernel<Epi, IDX>), dim3(nss_csr_s::grid(A.nblk)), dim3(kBlock), 0, st,
+                       A.view(0, A.nblk, IDX), slot_positions(A), slot_codes(A), x, epi);
+    NSS_CHECK_LAUNCH();
+    return true;
+  }
+}
+
+// A and B in one launch of the row-slot kernels when both take them; false (nothing launched) otherwise
+template <class EpiA, class EpiB>
+inline bool launch_csr_slots_dual(const nss_csr_s& A, const double* xa, const EpiA& ea, const nss_csr_s& B,
+                                  const double* xb, const EpiB& eb, hipStream_t st) {
+  constexpr int IA = slots_idx<EpiA>(), IB = slots_idx<EpiB>();
+  if constexpr (IA == 0 || IB == 0) return false;
+  else {
+    if (!takes_row_slots<EpiA>(A) || !takes_row_slots<EpiB>(B)) return false;
+#ifdef NSS_NO_DUAL        // measurements: the two halves as launches of their own
+    return launch_csr_slots(A, xa, ea, st) && launch_csr_slots(B, xb, eb, st);
+#else
+    const int ga = nss_csr_s::grid(A.nblk), gb = nss_csr_s::grid(B.nblk);
+    hipLaunchKernelGGL((csr_slots_dual_kernel<EpiA, EpiB, IA, IB>), dim3(ga + gb), dim3(kBlock), 0, st,
+                       A.view(0, A.nblk, IA), B.view(0, B.nblk, IB), slot_positions(A), slot_codes(A), slot_positions(B),
+                       slot_codes(B), ga, gb, xa, xb, ea, eb);
+    NSS_CHECK_LAUNCH();
+    return true;
+#endif
+  }
 }
 
 // y = alpha * A x + beta * y

@@ -709,10 +709,94 @@ static void build_ell_code(nss_csr_s& A, hipStream_t st) {
   NSS_HIP(hipStreamSynchronize(st));
 }
 
+// ---- row slots (nss_csr_s::slot_pos) ---------------------------------------------------------------------------------
+// the two slot words of every row from the staged positions and the codes of its entries, in CSR order; unused slots:
+// position kSlotPad, code 0.  A row with more than kSlotWidth entries raises *wide (its words hold the first eight).
+__global__ __launch_bounds__(kBlock) void slot_build_kernel(int32_t m, const int32_t* __restrict__ rowptr,
+                                                             const uint16_t* __restrict__ pos16,
+                                                             const uint8_t* __restrict__ val8, uint16_t* __restrict__ spos,
+                                                             uint8_t* __restrict__ scode, int32_t* __restrict__ wide) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t r = int64_t(blockIdx.x) * kBlock + threadIdx.x; r < m; r += stride) {
+    const int s = rowptr[r], len = rowptr[r + 1] - s;
+    if (len > kSlotWidth) atomicOr(wide, 1);
+    uint32_t pw[kSlotWidth / 2], cw[kSlotWidth / 4];
+#pragma unroll
+    for (int k = 0; k < kSlotWidth / 2; ++k) pw[k] = 0;
+#pragma unroll
+    for (int k = 0; k < kSlotWidth / 4; ++k) cw[k] = 0;
+#pragma unroll
+    for (int k = 0; k < kSlotWidth; ++k) {
+      const bool has = k < len;
+      const uint32_t p = has ? uint32_t(pos16[s + k]) : kSlotPad;
+      const uint32_t c = has ? uint32_t(val8[s + k]) : 0u;
+      pw[k / 2] |= p << (16 * (k % 2));
+      cw[k / 4] |= c << (8 * (k % 4));
+    }
+    uint4v* const pout = reinterpret_cast<uint4v*>(spos) + r;
+    uint2v* const cout = reinterpret_cast<uint2v*>(scode) + r;
+    *pout = uint4v{pw[0], pw[1], pw[2], pw[3]};
+    *cout = uint2v{cw[0], cw[1]};
+  }
+}
+
+static void drop_row_slots(nss_csr_s& A) {
+  (void)hipFree(A.slot_pos);
+  (void)hipFree(A.slot_code);
+  A.slot_pos = nullptr;
+  A.slot_code = nullptr;
+  A.slot_gen = -1;
+}
+
+// what the row-slot kernel needs besides rows of at most kSlotWidth entries (which the build finds out)
+static bool row_slots_candidate(const nss_csr_s& A) {
+  return A.m > 0 && A.nnz > 0 && A.coded() && A.blkseg && A.pos16 && !A.ell_col && !A.val32 && !A.blkdisp && A.rg == 1 &&
+         A.nnz <= int64_t(kSlotWidth) * A.m;
+}
+
+// the copy for the current launch plan; false (and no copy) when the matrix is not eligible.  Synchronises the stream.
+static bool build_row_slots(nss_csr_s& A, hipStream_t st) {
+  if (A.slot_pos && A.slot_gen == A.plan_gen) return A.row_slots();
+  NSS_HIP(hipDeviceSynchronize());                       // (a stale copy goes: no kernel may still read it)
+  drop_row_slots(A);
+  if (!row_slots_candidate(A)) return false;
+  uint16_t* spos = nullptr;
+  uint8_t* scode = nullptr;
+  int32_t* wide = nullptr;
+  int32_t h_wide = 1;
+  try {
+    NSS_HIP(hipMalloc(&spos, sizeof(uint16_t) * kSlotWidth * size_t(A.m)));
+    NSS_HIP(hipMalloc(&scode, size_t(kSlotWidth) * size_t(A.m)));
+    NSS_HIP(hipMalloc(&wide, sizeof(int32_t)));
+    NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(slot_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.pos16,
+                       A.val8, spos, scode, wide);
+    NSS_CHECK_LAUNCH();
+    NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    NSS_HIP(hipStreamSynchronize(st));
+  } catch (...) {
+    (void)hipFree(spos);
+    (void)hipFree(scode);
+    (void)hipFree(wide);
+    throw;
+  }
+  (void)hipFree(wide);
+  if (h_wide != 0) {                                     // a row of more than kSlotWidth entries
+    (void)hipFree(spos);
+    (void)hipFree(scode);
+    return false;
+  }
+  A.slot_pos = spos;
+  A.slot_code = scode;
+  A.slot_gen = A.plan_gen;
+  return A.row_slots();
+}
+
 // the codes go (a writer of `val`, nss_csr_drop_value_codes): every kernel reads `val` again
 static void drop_value_codes(nss_csr_s& A) {
   if (!A.val8) return;
   NSS_HIP(hipDeviceSynchronize());                       // no kernel may still read the arrays that go away
+  drop_row_slots(A);                                     // (a copy of the codes)
   (void)hipFree(A.val8);
   (void)hipFree(A.dict);
   (void)hipFree(A.ell_code);
@@ -943,6 +1027,8 @@ int nss_csr_destroy(nss_csr_t a) {
     (void)hipFree(a->val8);
     (void)hipFree(a->dict);
     (void)hipFree(a->ell_code);
+    (void)hipFree(a->slot_pos);
+    (void)hipFree(a->slot_code);
     (void)hipFree(a->rowblk);
     (void)hipFree(a->col16);
     (void)hipFree(a->blkbase);
@@ -993,6 +1079,7 @@ static void replan(nss_csr_s& A, int products, int max_rows = 0, const uint8_t* 
                   (void*)A.ell_val, (void*)A.blkdisp, (void*)A.ell_code})    // (val8 / dict stay: per entry in CSR order)
     (void)hipFree(p);
   A.ell_code = nullptr;
+  drop_row_slots(A);                                     // (staged positions of the plan that goes)
   A.blkdisp = nullptr;
   A.disp_period = 0.0;
   A.disp_planes = 0;
@@ -1073,6 +1160,26 @@ int nss_csr_plan_for_pairs(nss_csr_t a, int32_t* pair_staged) {
       if (!a->pair_ok) replan(*a, before);               // wide operators: shorter blocks do not help; back to the full plan
     }
     if (pair_staged) *pair_staged = (a->blkseg && a->pair_ok) ? 1 : 0;
+  });
+}
+
+int nss_csr_plan_row_slots(nss_csr_t a, int32_t mode, int32_t* valid) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr, "csr_plan_row_slots: NULL matrix");
+    NSS_REQUIRE(mode >= -1 && mode <= 2, "csr_plan_row_slots: -1 (by the size rule of the value codes), 0 (drop and refuse), 1 (build) or 2 (ask)");
+    if (mode == 0) {
+      if (a->slot_pos) NSS_HIP(hipDeviceSynchronize());  // no kernel may still read the arrays that go away
+      drop_row_slots(*a);
+      a->slot_state = -1;
+    } else if (mode == 1) {
+      a->slot_state = 0;
+      build_row_slots(*a, nullptr);
+    } else if (mode == -1 && a->slot_state >= 0 && !a->row_slots()) {
+      // automatic: where the codes are there by their size rule, not forced by the override -- the regime the form was
+      // measured in (bound by bytes, not by launches)
+      if (g_value_code_mode < 0 && a->m >= int64_t(NSS_VALUE_CODES_MIN_ROWS)) build_row_slots(*a, nullptr);
+    }
+    if (valid) *valid = a->row_slots() ? 1 : 0;
   });
 }
 
@@ -1168,7 +1275,9 @@ int nss_csr_spmv_f64(nss_csr_t a, double alpha, const double* x, double beta, do
     NSS_REQUIRE(a != nullptr, "csr_spmv: NULL matrix");
     NSS_REQUIRE(x != y, "csr_spmv: x must not alias y");
     // (the one user of EpiAxpby with a coded form; its other users keep reading `val`)
-    launch_csr<kF32 | kCodes>(*a, x, EpiAxpby{alpha, beta, y}, as_stream(stream));
+    const EpiAxpby epi{alpha, beta, y};
+    if (launch_csr_slots(*a, x, epi, as_stream(stream))) return;       // (a valid row-slot copy: same bits)
+    launch_csr<kF32 | kCodes>(*a, x, epi, as_stream(stream));
   });
 }
 
@@ -1215,6 +1324,9 @@ int nss_csr_info(nss_csr_t a, int32_t* nrows, int32_t* ncols, int64_t* nnz, int3
     // pointers, x once and y once.  (The CSR fp64/int32 textbook figure is 12 nnz + ...; pricing a
     // launch that streams 10 bytes per entry at 12 would overstate its bandwidth.)
     // A coded matrix (nss_csr_code_values) streams 1 byte per entry and the 2-KiB dictionary once per row block.
+    // A row-slot copy (nss_csr_plan_row_slots) does not change the figure: its 24 bytes per row stand for the 3 bytes
+    // per entry and 4 per row of the CSR streams, and at seven entries per row the two agree within 0.5 % (the Stokes
+    // blocks of the 1e7-DoF case: 240.2 against 241.3 MB over A and B), so the launch stays priced as the CSR stream.
     const bool coded = a->coded() && !a->val32;
     if (algorithmic_bytes && a->ell_col && coded && a->ell_code)   // 8 bytes of columns + one 16-bit code word per row
       *algorithmic_bytes = int64_t(4 * nss::kDirectWidth + 2) * a->m + int64_t(sizeof(double)) * kDictSize * a->nblk +

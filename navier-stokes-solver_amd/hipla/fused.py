@@ -467,6 +467,10 @@ class Bpcg2Loop(FusedLoop):
         # one-byte value codes for A, B and B^T (C1 / C23 then stream 1 byte per entry instead of 8: same bits) on the
         # single-GPU compact plan, all or nothing: info() and the launches stay consistent
         self.value_coded = (condensed is None and not distributed and code_values_together(eng, (matA, matB, matBT)))
+        # the row-per-lane form of C23 (eight-slot copies of A and B) where the size rule coded the matrices: the plans
+        # are settled now, and a copy belongs to one plan
+        self.row_slots = (self.value_coded and all(hasattr(m.handle, "plan_row_slots") for m in (matA, matB))
+                          and all([m.handle.plan_row_slots(-1) for m in (matA, matB)]))
         st.A, st.B, st.BT = matA.handle.ptr, matB.handle.ptr, matBT.handle.ptr
         write_pre(st, pa)
         st.k = float(k) * pa.scale
@@ -532,6 +536,13 @@ class Bpcg2Loop(FusedLoop):
         out = C.c_int32()
         self.eng._check(self.lib.nss_bpcg2_c1_applies_preA(C.byref(self.state), C.byref(out)))
         return bool(out.value)
+
+    def c23_form(self):
+        """What the next C23 of `enqueue` launches (nss_bpcg2_c23_form): 0 = the stream kernels in one launch, 1 = the
+        row-slot kernels in one launch, 2 = two launches."""
+        out = C.c_int32()
+        self.eng._check(self.lib.nss_bpcg2_c23_form(C.byref(self.state), C.byref(out)))
+        return out.value
 
     def enqueue_dist(self, dist_handle, s1, t1, t4, overlap, it_begin, it_end):
         """Row-partitioned iterations issued natively (nss_bpcg2_iterate_dist); `s1`, `t1`, `t4`: the `HaloStruct` of

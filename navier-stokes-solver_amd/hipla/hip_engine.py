@@ -60,6 +60,7 @@ def _signatures():
         "nss_csr_plan_for_pairs": (C.c_int, [vp, c_i32_p]),
         "nss_csr_pair_staged": (C.c_int, [vp, c_i32_p]),
         "nss_csr_plan_generation": (C.c_int, [vp, c_i64_p]),
+        "nss_csr_plan_row_slots": (C.c_int, [vp, i32, c_i32_p]),
         "nss_csr_pair_mode": (C.c_int, [i32]),
         "nss_p2p_blob_bytes": (C.c_int, [i32, i32, c_i64_p]),
         "nss_p2p_create": (C.c_int, [i32, i32, i32, vp, vp, C.POINTER(vp), vp]),
@@ -186,6 +187,7 @@ def _signatures():
         "nss_amg_batch_components": (C.c_int, [i32]),
         "nss_bpcg2_fuse_block_jacobi": (C.c_int, [i32]),
         "nss_bpcg2_c1_applies_preA": (C.c_int, [vp, c_i32_p]),
+        "nss_bpcg2_c23_form": (C.c_int, [vp, c_i32_p]),
         "nss_csr_plan_for_blocks": (C.c_int, [vp, vp, c_i32_p]),
         "nss_lanczos_start_values": (C.c_int, [i64, i64, vp, vp]),
         "nss_tridiag_extremes": (C.c_int, [vp, vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -329,6 +331,18 @@ class _CsrHandle:
                            else lib.nss_csr_pair_staged(self.ptr, C.byref(out)))
         return bool(out.value)
 
+    def plan_row_slots(self, mode=1):
+        """The eight-slot copy of a coded, staged matrix with at most 8 entries per row for the row-per-lane kernel of
+        the staged operand (nss_csr_plan_row_slots, set-up only).  mode 1: build wherever the matrix is eligible; -1:
+        only where the value codes' size rule coded it, and leave a refused handle alone; 0: drop the copy and refuse
+        later -1 calls; None: only ask.  Returns whether a copy valid for the current launch plan exists."""
+        lib = self.engine.lib
+        if not hasattr(lib, "nss_csr_plan_row_slots"):               # (absent in older A/B builds)
+            return False
+        out = C.c_int32()
+        self.engine._check(lib.nss_csr_plan_row_slots(self.ptr, 2 if mode is None else int(mode), C.byref(out)))
+        return bool(out.value)
+
     def code_values(self):
         """Store one-byte value codes beside the values when the matrix has at most 256 distinct value patterns
         (nss_csr_code_values, set-up only); returns whether it holds codes now."""
@@ -366,7 +380,7 @@ class _CsrHandle:
                 "dispatch_period": period.value, "dispatch_planes": planes.value,
                 "rows": m.value, "cols": n.value, "nnz": nnz.value, "row_blocks": nb.value,
                 "lanes_per_row": rg.value, "algorithmic_bytes": nbytes.value, "index_bytes": width.value,
-                "index_group": group.value, "value_bytes": self.value_bytes()}
+                "index_group": group.value, "value_bytes": self.value_bytes(), "row_slots": self.plan_row_slots(None)}
 
     def __del__(self):
         try:

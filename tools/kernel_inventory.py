@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Inventory of the gfx950 device code in the objects of a build: per object file the functions and kernel
 descriptors of its code object with their sizes and a hash of their bytes, and the number of instantiations of the
-three CSR kernels.  With a second directory: the differences between the two builds (none: "identical").
+CSR kernels.  With a second directory: the differences between the two builds (none: "identical").
 
     make -C navier-stokes-solver_amd/csrc -j8
     python tools/kernel_inventory.py navier-stokes-solver_amd/csrc [csrc of another build]
@@ -15,7 +15,7 @@ import sys
 import tempfile
 
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/llvm/bin")
-KERNELS = ("csr_stream_kernel", "csr_stream_dual_kernel", "csr_direct_kernel")
+KERNELS = ("csr_stream_kernel", "csr_stream_dual_kernel", "csr_direct_kernel", "csr_slots_kernel", "csr_slots_dual_kernel")
 
 
 def inventory(obj):
