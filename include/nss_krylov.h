@@ -133,6 +133,10 @@ NSS_API int nss_graph_color_greedy(nss_csr_t g, nss_csr_t g_transposed, int32_t*
 /* the set-up entry points (nss_csr_spgemm, nss_csr_transpose, nss_amg_*) keep their multi-GB
  * temporaries in a pool between calls; this returns the unused ones to the driver */
 NSS_API int nss_scratch_trim(void);
+/* device memory the library holds at this moment: handles, their derived arrays, the set-up pool (until
+ * nss_scratch_trim) and the process-wide reduction scratch.  Not counted: memory of the caller (torch's allocator)
+ * and the IPC region of the mailbox transport.  Either pointer may be NULL. */
+NSS_API int nss_device_memory(int64_t* live_bytes, int64_t* live_allocations);
 /* Streaming (non-temporal) loads of the vector operands the fused loops do not read again before they are
  * rewritten: -1 = automatic (from 20 MB per vector on: they pay when the vectors do not fit the caches and cost
  * when they do), 0 = never, 1 = always.  Same bits either way. */

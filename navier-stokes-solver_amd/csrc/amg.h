@@ -9,17 +9,17 @@
 namespace nss {
 struct AmgLevel {
   int32_t n = 0;
-  const nss_csr_s* A = nullptr;
+  const nss_csr_s* A = nullptr;      // the operators and the diagonal are the caller's (nss_amg_level_t)
   const nss_csr_s* P = nullptr;
   const nss_csr_s* R = nullptr;
   const double* dinv = nullptr;
-  double *x = nullptr, *r = nullptr, *b = nullptr, *y = nullptr;   // work vectors of the level
+  DeviceBuffer<double> x, r, b, y;   // work vectors of the level
 };
 }  // namespace nss
 
 struct nss_amg_s {
   std::vector<nss::AmgLevel> levels;
-  const nss_csr_s* coarse_inverse = nullptr;
+  const nss_csr_s* coarse_inverse = nullptr;   // (the caller's, like T, TT and the component handles below)
   double omega = 2.0 / 3.0;
   // Auxiliary-space mode (nss_amg_create_auxiliary): x -> T (sum_c E_c V_c E_c^T) T^T x, the term
   // `transform @ preAh1 @ transform.T` of the reference's MypreA
@@ -30,13 +30,13 @@ struct nss_amg_s {
   const nss_csr_s* TT = nullptr;
   std::vector<const nss_amg_s*> comps;
   std::vector<int32_t> comp_off;     // comps.size() + 1 offsets into the stacked auxiliary vector
-  double *aux_r = nullptr, *aux_z = nullptr;
+  nss::DeviceBuffer<double> aux_r, aux_z;
   // Components that share ONE hierarchy (the same Laplacian with the same boundary conditions for every velocity
   // component: the usual case) are cycled TOGETHER: every level operator is read once for all K right-hand sides
   // (amg.hip: csr_multi_kernel).  The cycle's internal vectors are interleaved [row][K]; the stacked auxiliary vectors
   // at its two ends are addressed with strides.  Work vectors per level of the shared hierarchy (K * n doubles each):
   struct MultiLevel {
-    double *x = nullptr, *r = nullptr, *b = nullptr, *y = nullptr;
+    nss::DeviceBuffer<double> x, r, b, y;
   };
   std::vector<MultiLevel> multi;     // empty: components are cycled one after the other
   // one 16-byte descriptor {first row, end row, first entry, entries} per row block of every matrix the joint cycle
@@ -46,7 +46,7 @@ struct nss_amg_s {
     const nss_csr_s* mat;
     int64_t plan_gen;                // generation of the launch plan the descriptors were made from (checked at
                                      // every launch: a freed and re-allocated rowblk can come back at the same address)
-    int32_t* desc;
+    nss::DeviceBuffer<int32_t> desc;
   };
   std::vector<MultiDesc> multi_desc;
 };

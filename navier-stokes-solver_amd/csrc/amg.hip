@@ -13,6 +13,7 @@
 // an SPD preconditioner for the Bramble-Pasciak CG.
 #include "amg.h"
 
+#include <memory>
 #include <vector>
 
 namespace nss {
@@ -326,42 +327,37 @@ int nss_amg_create(int32_t nlevels, const nss_amg_level_t* h_levels, nss_csr_t c
   return guarded([&] {
     NSS_REQUIRE(out && h_levels && coarse_inverse, "amg_create: NULL argument");
     NSS_REQUIRE(nlevels >= 1 && nlevels <= 32, "amg_create: 1 <= nlevels <= 32");
-    nss_amg_s* a = new nss_amg_s;
-    try {
-      a->omega = omega;
-      a->coarse_inverse = coarse_inverse;
-      for (int l = 0; l < nlevels; ++l) {
-        const nss_amg_level_t& in = h_levels[l];
-        NSS_REQUIRE(in.A && in.dinv, "amg_create: level without operator / diagonal");
-        NSS_REQUIRE(in.A->m == in.A->n, "amg_create: level operator must be square");
-        AmgLevel lv;
-        lv.n = in.A->m;
-        lv.A = in.A;
-        lv.dinv = in.dinv;
-        if (l + 1 < nlevels) {
-          NSS_REQUIRE(in.P && in.R, "amg_create: missing transfer operators");
-          const nss_csr_s* nextA = h_levels[l + 1].A;
-          NSS_REQUIRE(nextA && in.P->m == lv.n && in.P->n == nextA->m && in.R->m == nextA->m && in.R->n == lv.n,
-                      "amg_create: transfer operator shapes do not chain");
-          lv.P = in.P;
-          lv.R = in.R;
-        }
-        a->levels.push_back(lv);
+    std::unique_ptr<nss_amg_s> a(new nss_amg_s);
+    a->omega = omega;
+    a->coarse_inverse = coarse_inverse;
+    for (int l = 0; l < nlevels; ++l) {
+      const nss_amg_level_t& in = h_levels[l];
+      NSS_REQUIRE(in.A && in.dinv, "amg_create: level without operator / diagonal");
+      NSS_REQUIRE(in.A->m == in.A->n, "amg_create: level operator must be square");
+      AmgLevel lv;
+      lv.n = in.A->m;
+      lv.A = in.A;
+      lv.dinv = in.dinv;
+      if (l + 1 < nlevels) {
+        NSS_REQUIRE(in.P && in.R, "amg_create: missing transfer operators");
+        const nss_csr_s* nextA = h_levels[l + 1].A;
+        NSS_REQUIRE(nextA && in.P->m == lv.n && in.P->n == nextA->m && in.R->m == nextA->m && in.R->n == lv.n,
+                    "amg_create: transfer operator shapes do not chain");
+        lv.P = in.P;
+        lv.R = in.R;
       }
-      NSS_REQUIRE(coarse_inverse->m == a->levels.back().n && coarse_inverse->n == a->levels.back().n,
-                  "amg_create: coarse inverse has the wrong size");
-      for (auto& lv : a->levels) {
-        const size_t bytes = sizeof(double) * size_t(std::max(1, lv.n));
-        NSS_HIP(hipMalloc(&lv.x, bytes));
-        NSS_HIP(hipMalloc(&lv.r, bytes));
-        NSS_HIP(hipMalloc(&lv.b, bytes));
-        NSS_HIP(hipMalloc(&lv.y, bytes));
-      }
-    } catch (...) {
-      nss_amg_destroy(a);
-      throw;
+      a->levels.push_back(std::move(lv));
     }
-    *out = a;
+    NSS_REQUIRE(coarse_inverse->m == a->levels.back().n && coarse_inverse->n == a->levels.back().n,
+                "amg_create: coarse inverse has the wrong size");
+    for (auto& lv : a->levels) {
+      const size_t count = size_t(std::max(1, lv.n));
+      lv.x.alloc(count);
+      lv.r.alloc(count);
+      lv.b.alloc(count);
+      lv.y.alloc(count);
+    }
+    *out = a.release();
   });
 }
 
@@ -370,94 +366,69 @@ int nss_amg_create_auxiliary(nss_csr_t T, nss_csr_t TT, int32_t ncomp, const nss
     NSS_REQUIRE(out && T && TT && h_comps, "amg_create_auxiliary: NULL argument");
     NSS_REQUIRE(ncomp >= 1 && ncomp <= 16, "amg_create_auxiliary: 1 <= ncomp <= 16");
     NSS_REQUIRE(TT->m == T->n && TT->n == T->m, "amg_create_auxiliary: TT is not the transpose shape of T");
-    nss_amg_s* a = new nss_amg_s;
-    try {
-      a->T = T;
-      a->TT = TT;
-      int64_t off = 0;
-      a->comp_off.push_back(0);
-      for (int c = 0; c < ncomp; ++c) {
-        NSS_REQUIRE(h_comps[c] != nullptr && h_comps[c]->T == nullptr && !h_comps[c]->levels.empty(),
-                    "amg_create_auxiliary: components must be plain V-cycle handles");
-        a->comps.push_back(h_comps[c]);
-        off += h_comps[c]->levels[0].n;
-        a->comp_off.push_back(int32_t(off));
-      }
-      NSS_REQUIRE(off == T->n, "amg_create_auxiliary: component sizes do not add up to the columns of T");
-      AmgLevel lv;
-      lv.n = T->m;
-      a->levels.push_back(lv);
-      const size_t bytes = sizeof(double) * size_t(std::max<int64_t>(1, off));
-      NSS_HIP(hipMalloc(&a->aux_r, bytes));
-      NSS_HIP(hipMalloc(&a->aux_z, bytes));
-      bool shared = ncomp == 2 || ncomp == 3;
-      for (int c = 1; c < ncomp; ++c) shared = shared && h_comps[c] == h_comps[0];
-      if (shared && h_comps[0]->levels.size() >= 2) {
-        // every level operator is read once for all components: row blocks of at most kMultiChunk products (the plan
-        // of the matrices changes -- set-up only; per-row sums of the single-vector kernels keep their bits).  This
-        // RE-PLANS the shared hierarchy in place: each matrix gets a new plan generation, so loop states holding one of
-        // them refuse until they re-size their partials, and the descriptors below record the generation they were
-        // made for (multi_desc_of)
-        const nss_amg_s& h = *h_comps[0];
-        for (const AmgLevel& lv : h.levels) {
-          replan_row_blocks(*const_cast<nss_csr_s*>(lv.A), kMultiChunk);
-          if (lv.P) replan_row_blocks(*const_cast<nss_csr_s*>(lv.P), kMultiChunk);
-          if (lv.R) replan_row_blocks(*const_cast<nss_csr_s*>(lv.R), kMultiChunk);
-        }
-        replan_row_blocks(*const_cast<nss_csr_s*>(h.coarse_inverse), kMultiChunk);
-        auto describe = [&](const nss_csr_s* M) {
-          if (!M || M->nblk == 0) return;
-          int32_t* desc = nullptr;
-          NSS_HIP(hipMalloc(&desc, sizeof(int32_t) * 4 * size_t(M->nblk)));
-          a->multi_desc.push_back({M, M->plan_gen, desc});
-          hipLaunchKernelGGL(multi_desc_kernel, dim3((M->nblk + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, M->nblk,
-                             M->rowblk, M->rowptr, desc);
-          NSS_CHECK_LAUNCH();
-        };
-        for (const AmgLevel& lv : h.levels) {
-          describe(lv.A);
-          describe(lv.P);
-          describe(lv.R);
-        }
-        describe(h.coarse_inverse);
-        NSS_HIP(hipDeviceSynchronize());
-        a->multi.resize(h.levels.size());
-        for (size_t l = 0; l < h.levels.size(); ++l) {
-          const size_t lb = sizeof(double) * size_t(ncomp) * size_t(std::max(1, h.levels[l].n));
-          NSS_HIP(hipMalloc(&a->multi[l].x, lb));
-          NSS_HIP(hipMalloc(&a->multi[l].r, lb));
-          NSS_HIP(hipMalloc(&a->multi[l].b, lb));
-          NSS_HIP(hipMalloc(&a->multi[l].y, lb));
-        }
-      }
-    } catch (...) {
-      nss_amg_destroy(a);
-      throw;
+    std::unique_ptr<nss_amg_s> a(new nss_amg_s);
+    a->T = T;
+    a->TT = TT;
+    int64_t off = 0;
+    a->comp_off.push_back(0);
+    for (int c = 0; c < ncomp; ++c) {
+      NSS_REQUIRE(h_comps[c] != nullptr && h_comps[c]->T == nullptr && !h_comps[c]->levels.empty(),
+                  "amg_create_auxiliary: components must be plain V-cycle handles");
+      a->comps.push_back(h_comps[c]);
+      off += h_comps[c]->levels[0].n;
+      a->comp_off.push_back(int32_t(off));
     }
-    *out = a;
+    NSS_REQUIRE(off == T->n, "amg_create_auxiliary: component sizes do not add up to the columns of T");
+    AmgLevel lv;
+    lv.n = T->m;
+    a->levels.push_back(std::move(lv));
+    a->aux_r.alloc(size_t(std::max<int64_t>(1, off)));
+    a->aux_z.alloc(size_t(std::max<int64_t>(1, off)));
+    bool shared = ncomp == 2 || ncomp == 3;
+    for (int c = 1; c < ncomp; ++c) shared = shared && h_comps[c] == h_comps[0];
+    if (shared && h_comps[0]->levels.size() >= 2) {
+      // every level operator is read once for all components: row blocks of at most kMultiChunk products (the plan
+      // of the matrices changes -- set-up only; per-row sums of the single-vector kernels keep their bits).  This
+      // RE-PLANS the shared hierarchy in place: each matrix gets a new plan generation, so loop states holding one of
+      // them refuse until they re-size their partials, and the descriptors below record the generation they were
+      // made for (multi_desc_of)
+      const nss_amg_s& h = *h_comps[0];
+      for (const AmgLevel& lv : h.levels) {
+        replan_row_blocks(*const_cast<nss_csr_s*>(lv.A), kMultiChunk);
+        if (lv.P) replan_row_blocks(*const_cast<nss_csr_s*>(lv.P), kMultiChunk);
+        if (lv.R) replan_row_blocks(*const_cast<nss_csr_s*>(lv.R), kMultiChunk);
+      }
+      replan_row_blocks(*const_cast<nss_csr_s*>(h.coarse_inverse), kMultiChunk);
+      auto describe = [&](const nss_csr_s* M) {
+        if (!M || M->nblk == 0) return;
+        DeviceBuffer<int32_t> desc(4 * size_t(M->nblk));
+        hipLaunchKernelGGL(multi_desc_kernel, dim3((M->nblk + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, M->nblk,
+                           M->rowblk, M->rowptr, desc);
+        NSS_CHECK_LAUNCH();
+        a->multi_desc.push_back({M, M->plan_gen, std::move(desc)});
+      };
+      for (const AmgLevel& lv : h.levels) {
+        describe(lv.A);
+        describe(lv.P);
+        describe(lv.R);
+      }
+      describe(h.coarse_inverse);
+      NSS_HIP(hipDeviceSynchronize());
+      a->multi.resize(h.levels.size());
+      for (size_t l = 0; l < h.levels.size(); ++l) {
+        const size_t count = size_t(ncomp) * size_t(std::max(1, h.levels[l].n));
+        a->multi[l].x.alloc(count);
+        a->multi[l].r.alloc(count);
+        a->multi[l].b.alloc(count);
+        a->multi[l].y.alloc(count);
+      }
+    }
+    *out = a.release();
   });
 }
 
 int nss_amg_destroy(nss_amg_t a) {
-  return guarded([&] {
-    if (!a) return;
-    (void)hipFree(a->aux_r);
-    (void)hipFree(a->aux_z);
-    for (auto& e : a->multi_desc) (void)hipFree(e.desc);
-    for (auto& m : a->multi) {
-      (void)hipFree(m.x);
-      (void)hipFree(m.r);
-      (void)hipFree(m.b);
-      (void)hipFree(m.y);
-    }
-    for (auto& lv : a->levels) {
-      (void)hipFree(lv.x);
-      (void)hipFree(lv.r);
-      (void)hipFree(lv.b);
-      (void)hipFree(lv.y);
-    }
-    delete a;
-  });
+  return guarded([&] { delete a; });
 }
 
 int nss_amg_batch_components(int32_t on) {

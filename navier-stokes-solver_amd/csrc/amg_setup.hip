@@ -23,6 +23,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -35,7 +36,9 @@ namespace {
 // hipFree of such blocks cost far more than the kernels that use them (cfg5: 4.7 of 5.9 s of the
 // hierarchy build were allocation calls).  Temporaries therefore come from a grow-only list of
 // cached blocks that lives until nss_scratch_trim(); results that are handed to a CSR handle are
-// plain hipMalloc allocations of exactly their size.
+// DeviceBuffers of exactly their size.  The pool lives as long as the process and is never destroyed
+// with device memory in it by a destructor: its blocks are raw pointers, taken and returned through
+// device_alloc / device_free.
 struct ScratchPool {
   struct Block {
     void* p;
@@ -51,8 +54,7 @@ struct ScratchPool {
       best->used = true;
       return best->p;
     }
-    void* p = nullptr;
-    NSS_HIP(hipMalloc(&p, bytes));
+    void* p = device_alloc(bytes);
     blocks.push_back({p, bytes, true});
     return p;
   }
@@ -64,7 +66,7 @@ struct ScratchPool {
     std::vector<Block> keep;
     for (Block& b : blocks) {
       if (b.used) keep.push_back(b);
-      else (void)hipFree(b.p);
+      else device_free(b.p);
     }
     blocks.swap(keep);
   }
@@ -75,15 +77,14 @@ inline ScratchPool& pool() {
 }
 
 template <class T>
-struct Dev {  // owning device array; `result` arrays can be handed to a CSR handle with take()
+struct Dev {  // a temporary from the pool (results that go to a CSR handle are DeviceBuffers)
   T* p = nullptr;
   size_t n = 0;
-  bool result = false;
   Dev() = default;
-  explicit Dev(size_t count, bool is_result = false) : result(is_result) { alloc(count); }
+  explicit Dev(size_t count) { alloc(count); }
   Dev(const Dev&) = delete;
   Dev& operator=(const Dev&) = delete;
-  Dev(Dev&& o) noexcept : p(o.p), n(o.n), result(o.result) {
+  Dev(Dev&& o) noexcept : p(o.p), n(o.n) {
     o.p = nullptr;
     o.n = 0;
   }
@@ -91,23 +92,12 @@ struct Dev {  // owning device array; `result` arrays can be handed to a CSR han
   void alloc(size_t count) {
     release();
     n = count;
-    if (!count) return;
-    if (result) NSS_HIP(hipMalloc(&p, sizeof(T) * count));
-    else p = static_cast<T*>(pool().get(sizeof(T) * count));
+    if (count) p = static_cast<T*>(pool().get(sizeof(T) * count));
   }
   void release() {
-    if (p) {
-      if (result) (void)hipFree(p);
-      else pool().put(p);
-    }
+    if (p) pool().put(p);
     p = nullptr;
     n = 0;
-  }
-  T* take() {   // only for result arrays
-    T* q = p;
-    p = nullptr;
-    n = 0;
-    return q;
   }
 };
 
@@ -510,16 +500,17 @@ __global__ __launch_bounds__(kBlock) void row_copy_kernel(int32_t m, const int32
 
 // Build the handle around device arrays (ownership passes to the handle).  col / val must have
 // been allocated with 4 spare entries (see nss_csr_create_cuts).
-nss_csr_s* adopt_csr(int32_t m, int32_t n, int64_t nnz, Dev<int32_t>& rowptr, Dev<int32_t>& col, Dev<double>& val,
-                     const int32_t* cuts = nullptr, int ncuts = 0, int max_rows = 0, const uint8_t* row_pos = nullptr) {
+nss_csr_s* adopt_csr(int32_t m, int32_t n, int64_t nnz, DeviceBuffer<int32_t>& rowptr, DeviceBuffer<int32_t>& col,
+                     DeviceBuffer<double>& val, const int32_t* cuts = nullptr, int ncuts = 0, int max_rows = 0,
+                     const uint8_t* row_pos = nullptr) {
   std::vector<int32_t> h_rowptr(size_t(m) + 1);
-  NSS_HIP(hipMemcpy(h_rowptr.data(), rowptr.p, sizeof(int32_t) * (size_t(m) + 1), hipMemcpyDeviceToHost));
+  NSS_HIP(hipMemcpy(h_rowptr.data(), rowptr.get(), sizeof(int32_t) * (size_t(m) + 1), hipMemcpyDeviceToHost));
   std::vector<int32_t> blk;
   int32_t rg = 1, chunk = kChunk;
   plan_row_blocks(m, nnz, h_rowptr.data(), &rg, &chunk, blk, cuts, ncuts, kChunk, max_rows, row_pos);
-  Dev<int32_t> rowblk(blk.size(), true);
-  NSS_HIP(hipMemcpy(rowblk.p, blk.data(), sizeof(int32_t) * blk.size(), hipMemcpyHostToDevice));
-  nss_csr_s* A = new nss_csr_s;
+  DeviceBuffer<int32_t> rowblk(blk.size());
+  NSS_HIP(hipMemcpy(rowblk.get(), blk.data(), sizeof(int32_t) * blk.size(), hipMemcpyHostToDevice));
+  std::unique_ptr<nss_csr_s> A(new nss_csr_s);
   A->m = m;
   A->n = n;
   A->nnz = nnz;
@@ -527,24 +518,19 @@ nss_csr_s* adopt_csr(int32_t m, int32_t n, int64_t nnz, Dev<int32_t>& rowptr, De
   A->chunk = chunk;
   if (cuts && ncuts > 0) A->cuts.assign(cuts, cuts + ncuts);
   A->nblk = int32_t(blk.size()) - 1;
-  A->rowptr = rowptr.take();
-  A->col = col.take();
-  A->val = val.take();
-  A->rowblk = rowblk.take();
-  try {
-    compress_columns(*A, nullptr);
-  } catch (...) {
-    nss_csr_destroy(A);
-    throw;
-  }
-  return A;
+  A->rowptr = std::move(rowptr);
+  A->col = std::move(col);
+  A->val = std::move(val);
+  A->rowblk = std::move(rowblk);
+  compress_columns(*A, nullptr);
+  return A.release();
 }
 
 struct RawCsr {
   int32_t m = 0, n = 0;
   int64_t nnz = 0;
-  Dev<int32_t> rowptr{0, true}, col{0, true};
-  Dev<double> val{0, true};
+  DeviceBuffer<int32_t> rowptr, col;
+  DeviceBuffer<double> val;
   nss_csr_s* adopt() { return adopt_csr(m, n, nnz, rowptr, col, val); }
 };
 
@@ -553,24 +539,24 @@ static void drop_zeros(RawCsr& c, hipStream_t st) {
   if (c.nnz == 0) return;
   Dev<int32_t> flag(size_t(c.nnz) + 1), pos(size_t(c.nnz) + 1);
   NSS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int32_t) * (size_t(c.nnz) + 1), st));
-  hipLaunchKernelGGL(nonzero_flag_kernel, dim3(grid_for(c.nnz)), dim3(kBlock), 0, st, c.nnz, c.val.p, flag.p);
+  hipLaunchKernelGGL(nonzero_flag_kernel, dim3(grid_for(c.nnz)), dim3(kBlock), 0, st, c.nnz, c.val.get(), flag.p);
   NSS_CHECK_LAUNCH();
   exclusive_sum(flag.p, pos.p, size_t(c.nnz) + 1, st);
   const int64_t kept = fetch(pos.p + c.nnz, st);
   if (kept == c.nnz) return;
-  Dev<int32_t> rowptr(size_t(c.m) + 1, true), col(size_t(kept) + 4, true);
-  Dev<double> val(size_t(kept) + 4, true);
-  NSS_HIP(hipMemsetAsync(col.p, 0, sizeof(int32_t) * (size_t(kept) + 4), st));
-  NSS_HIP(hipMemsetAsync(val.p, 0, sizeof(double) * (size_t(kept) + 4), st));
-  hipLaunchKernelGGL(compact_kernel, dim3(grid_for(c.nnz)), dim3(kBlock), 0, st, c.nnz, flag.p, pos.p, c.col.p,
-                     c.val.p, col.p, val.p);
-  hipLaunchKernelGGL(remap_rowptr_kernel, dim3(grid_for(int64_t(c.m) + 1)), dim3(kBlock), 0, st, c.m, c.rowptr.p,
-                     pos.p, rowptr.p);
+  DeviceBuffer<int32_t> rowptr(size_t(c.m) + 1), col(size_t(kept) + 4);
+  DeviceBuffer<double> val(size_t(kept) + 4);
+  NSS_HIP(hipMemsetAsync(col.get(), 0, sizeof(int32_t) * (size_t(kept) + 4), st));
+  NSS_HIP(hipMemsetAsync(val.get(), 0, sizeof(double) * (size_t(kept) + 4), st));
+  hipLaunchKernelGGL(compact_kernel, dim3(grid_for(c.nnz)), dim3(kBlock), 0, st, c.nnz, flag.p, pos.p, c.col.get(),
+                     c.val.get(), col.get(), val.get());
+  hipLaunchKernelGGL(remap_rowptr_kernel, dim3(grid_for(int64_t(c.m) + 1)), dim3(kBlock), 0, st, c.m, c.rowptr.get(),
+                     pos.p, rowptr.get());
   NSS_CHECK_LAUNCH();
   NSS_HIP(hipStreamSynchronize(st));
-  std::swap(c.rowptr.p, rowptr.p);
-  std::swap(c.col.p, col.p);
-  std::swap(c.val.p, val.p);
+  c.rowptr = std::move(rowptr);
+  c.col = std::move(col);
+  c.val = std::move(val);
   c.nnz = kept;
 }
 
@@ -643,8 +629,8 @@ static void spgemm(const nss_csr_s& X, const nss_csr_s& Y, hipStream_t st, int64
                                     st));
   Dev<char> sort_tmp(sort_bytes);
   const uint64_t cmask = (uint64_t(1) << cbits) - 1;
-  Dev<int32_t> out_rowptr(size_t(m) + 1, true);
-  NSS_HIP(hipMemsetAsync(out_rowptr.p, 0, sizeof(int32_t) * (size_t(m) + 1), st));
+  DeviceBuffer<int32_t> out_rowptr(size_t(m) + 1);
+  NSS_HIP(hipMemsetAsync(out_rowptr.get(), 0, sizeof(int32_t) * (size_t(m) + 1), st));
 
   int64_t nnz = 0;
   for (Chunk& c : chunks) {
@@ -665,7 +651,7 @@ static void spgemm(const nss_csr_s& X, const nss_csr_s& Y, hipStream_t st, int64
     c.runs = fetch(pos.p + count, st);
     NSS_REQUIRE(nnz + c.runs < (int64_t(1) << 31), "spgemm: result has more than 2^31 non-zeros");
     hipLaunchKernelGGL(chunk_rowptr_kernel, dim3(grid_for(int64_t(c.rb - c.ra) + 1)), dim3(kBlock), 0, st, c.ra, c.rb,
-                       roff.p, off0, pos.p, nnz, out_rowptr.p);
+                       roff.p, off0, pos.p, nnz, out_rowptr.get());
     NSS_CHECK_LAUNCH();
     if (c.runs > 0) {
       c.col.alloc(size_t(c.runs));
@@ -680,41 +666,42 @@ static void spgemm(const nss_csr_s& X, const nss_csr_s& Y, hipStream_t st, int64
     NSS_HIP(hipStreamSynchronize(st));
   }
   // one chunk: its arrays are the result (re-allocated with the 4 spare entries); several: concatenate
-  Dev<int32_t> out_col(size_t(nnz) + 4, true);
-  Dev<double> out_val(size_t(nnz) + 4, true);
-  NSS_HIP(hipMemsetAsync(out_col.p, 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
-  NSS_HIP(hipMemsetAsync(out_val.p, 0, sizeof(double) * (size_t(nnz) + 4), st));
+  DeviceBuffer<int32_t> out_col(size_t(nnz) + 4);
+  DeviceBuffer<double> out_val(size_t(nnz) + 4);
+  NSS_HIP(hipMemsetAsync(out_col.get(), 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
+  NSS_HIP(hipMemsetAsync(out_val.get(), 0, sizeof(double) * (size_t(nnz) + 4), st));
   int64_t at = 0;
   for (Chunk& c : chunks) {
     if (c.runs == 0) continue;
-    NSS_HIP(hipMemcpyAsync(out_col.p + at, c.col.p, sizeof(int32_t) * c.runs, hipMemcpyDeviceToDevice, st));
-    NSS_HIP(hipMemcpyAsync(out_val.p + at, c.val.p, sizeof(double) * c.runs, hipMemcpyDeviceToDevice, st));
+    NSS_HIP(hipMemcpyAsync(out_col.get() + at, c.col.p, sizeof(int32_t) * c.runs, hipMemcpyDeviceToDevice, st));
+    NSS_HIP(hipMemcpyAsync(out_val.get() + at, c.val.p, sizeof(double) * c.runs, hipMemcpyDeviceToDevice, st));
     at += c.runs;
   }
   NSS_HIP(hipStreamSynchronize(st));
   result.m = m;
   result.n = Y.n;
   result.nnz = nnz;
-  std::swap(result.rowptr.p, out_rowptr.p);
-  std::swap(result.col.p, out_col.p);
-  std::swap(result.val.p, out_val.p);
+  result.rowptr = std::move(out_rowptr);
+  result.col = std::move(out_col);
+  result.val = std::move(out_val);
 }
 
 static nss_csr_s* transpose(const nss_csr_s& A, hipStream_t st) {
   const int32_t m = A.m, n = A.n;
   const int64_t nnz = A.nnz;
   NSS_REQUIRE(nnz < (int64_t(1) << 32), "transpose: too many non-zeros");
-  Dev<int32_t> cnt(size_t(n) + 1), trow(size_t(n) + 1, true);
+  Dev<int32_t> cnt(size_t(n) + 1);
+  DeviceBuffer<int32_t> trow(size_t(n) + 1);
   NSS_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (size_t(n) + 1), st));
-  Dev<int32_t> tcol(size_t(nnz) + 4, true);
-  Dev<double> tval(size_t(nnz) + 4, true);
-  NSS_HIP(hipMemsetAsync(tcol.p, 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
-  NSS_HIP(hipMemsetAsync(tval.p, 0, sizeof(double) * (size_t(nnz) + 4), st));
+  DeviceBuffer<int32_t> tcol(size_t(nnz) + 4);
+  DeviceBuffer<double> tval(size_t(nnz) + 4);
+  NSS_HIP(hipMemsetAsync(tcol.get(), 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
+  NSS_HIP(hipMemsetAsync(tval.get(), 0, sizeof(double) * (size_t(nnz) + 4), st));
   if (nnz > 0) {
     hipLaunchKernelGGL(histogram_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, A.col, cnt.p);
     NSS_CHECK_LAUNCH();
   }
-  exclusive_sum(cnt.p, trow.p, size_t(n) + 1, st);
+  exclusive_sum(cnt.p, trow.get(), size_t(n) + 1, st);
   if (nnz > 0) {
     Dev<int32_t> rows{size_t(nnz)};
     Dev<uint32_t> idx_a{size_t(nnz)}, idx_b{size_t(nnz)};
@@ -724,14 +711,14 @@ static nss_csr_s* transpose(const nss_csr_s& A, hipStream_t st) {
     NSS_CHECK_LAUNCH();
     hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, idx_a.p);
     NSS_CHECK_LAUNCH();
-    const uint32_t* key_a = reinterpret_cast<const uint32_t*>(A.col);
+    const uint32_t* key_a = reinterpret_cast<const uint32_t*>(A.col.get());
     const int end_bit = bits_for(uint64_t(std::max(n, 1)));
     size_t bytes = 0;
     NSS_HIP(rocprim::radix_sort_pairs(nullptr, bytes, key_a, key_b.p, idx_a.p, idx_b.p, size_t(nnz), 0, end_bit, st));
     Dev<char> tmp(bytes);
     NSS_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, key_a, key_b.p, idx_a.p, idx_b.p, size_t(nnz), 0, end_bit, st));
-    hipLaunchKernelGGL(permute_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, idx_b.p, rows.p, A.val, tcol.p,
-                       tval.p);
+    hipLaunchKernelGGL(permute_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, idx_b.p, rows.p, A.val, tcol.get(),
+                       tval.get());
     NSS_CHECK_LAUNCH();
     NSS_HIP(hipStreamSynchronize(st));
   }
@@ -769,14 +756,14 @@ int nss_csr_ones_like(nss_csr_t a, nss_csr_t* out, nss_stream_t stream) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr && out != nullptr, "csr_ones_like: NULL argument");
     hipStream_t st = as_stream(stream);
-    Dev<int32_t> rowptr(size_t(a->m) + 1, true), col(size_t(a->nnz) + 4, true);
-    Dev<double> val(size_t(a->nnz) + 4, true);
-    NSS_HIP(hipMemcpyAsync(rowptr.p, a->rowptr, sizeof(int32_t) * (size_t(a->m) + 1), hipMemcpyDeviceToDevice, st));
-    NSS_HIP(hipMemsetAsync(col.p, 0, sizeof(int32_t) * (size_t(a->nnz) + 4), st));
-    NSS_HIP(hipMemsetAsync(val.p, 0, sizeof(double) * (size_t(a->nnz) + 4), st));
+    DeviceBuffer<int32_t> rowptr(size_t(a->m) + 1), col(size_t(a->nnz) + 4);
+    DeviceBuffer<double> val(size_t(a->nnz) + 4);
+    NSS_HIP(hipMemcpyAsync(rowptr.get(), a->rowptr, sizeof(int32_t) * (size_t(a->m) + 1), hipMemcpyDeviceToDevice, st));
+    NSS_HIP(hipMemsetAsync(col.get(), 0, sizeof(int32_t) * (size_t(a->nnz) + 4), st));
+    NSS_HIP(hipMemsetAsync(val.get(), 0, sizeof(double) * (size_t(a->nnz) + 4), st));
     if (a->nnz > 0) {
-      NSS_HIP(hipMemcpyAsync(col.p, a->col, sizeof(int32_t) * a->nnz, hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(ones_kernel, dim3(grid_for(a->nnz)), dim3(kBlock), 0, st, a->nnz, val.p);
+      NSS_HIP(hipMemcpyAsync(col.get(), a->col, sizeof(int32_t) * a->nnz, hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(ones_kernel, dim3(grid_for(a->nnz)), dim3(kBlock), 0, st, a->nnz, val.get());
       NSS_CHECK_LAUNCH();
     }
     NSS_HIP(hipStreamSynchronize(st));
@@ -795,21 +782,22 @@ int nss_csr_select_rows(nss_csr_t a, int32_t nrows, const int32_t* d_rows, int32
       NSS_REQUIRE(h_cuts[i] >= 0 && h_cuts[i] <= nrows && (i == 0 || h_cuts[i] >= h_cuts[i - 1]),
                   "csr_select_rows: cuts must be ascending row positions");
     hipStream_t st = as_stream(stream);
-    Dev<int32_t> len(size_t(nrows) + 1), rowptr(size_t(nrows) + 1, true);
+    Dev<int32_t> len(size_t(nrows) + 1);
+    DeviceBuffer<int32_t> rowptr(size_t(nrows) + 1);
     NSS_HIP(hipMemsetAsync(len.p, 0, sizeof(int32_t) * (size_t(nrows) + 1), st));
     if (nrows > 0) {
       hipLaunchKernelGGL(row_length_kernel, dim3(grid_for(nrows)), dim3(kBlock), 0, st, nrows, a->rowptr, d_rows, len.p);
       NSS_CHECK_LAUNCH();
     }
-    exclusive_sum(len.p, rowptr.p, size_t(nrows) + 1, st);
-    const int64_t nnz = fetch(rowptr.p + nrows, st);
-    Dev<int32_t> col(size_t(nnz) + 4, true);
-    Dev<double> val(size_t(nnz) + 4, true);
-    NSS_HIP(hipMemsetAsync(col.p, 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
-    NSS_HIP(hipMemsetAsync(val.p, 0, sizeof(double) * (size_t(nnz) + 4), st));
+    exclusive_sum(len.p, rowptr.get(), size_t(nrows) + 1, st);
+    const int64_t nnz = fetch(rowptr.get() + nrows, st);
+    DeviceBuffer<int32_t> col(size_t(nnz) + 4);
+    DeviceBuffer<double> val(size_t(nnz) + 4);
+    NSS_HIP(hipMemsetAsync(col.get(), 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
+    NSS_HIP(hipMemsetAsync(val.get(), 0, sizeof(double) * (size_t(nnz) + 4), st));
     if (nrows > 0 && nnz > 0) {
       hipLaunchKernelGGL(row_copy_kernel, dim3((nrows + kBlock / 8 - 1) / (kBlock / 8)), dim3(kBlock), 0, st, nrows,
-                         a->rowptr, a->col, a->val, d_rows, rowptr.p, col.p, val.p);
+                         a->rowptr, a->col, a->val, d_rows, rowptr.get(), col.get(), val.get());
       NSS_CHECK_LAUNCH();
     }
     NSS_HIP(hipStreamSynchronize(st));
@@ -837,22 +825,23 @@ int nss_csr_permute(nss_csr_t a, int32_t nrows, const int32_t* d_rows, const int
       NSS_REQUIRE(h_cuts[i] >= 0 && h_cuts[i] <= nrows && (i == 0 || h_cuts[i] >= h_cuts[i - 1]),
                   "csr_permute: cuts must be ascending row positions");
     hipStream_t st = as_stream(stream);
-    Dev<int32_t> len(size_t(nrows) + 1), rowptr(size_t(nrows) + 1, true);
+    Dev<int32_t> len(size_t(nrows) + 1);
+    DeviceBuffer<int32_t> rowptr(size_t(nrows) + 1);
     NSS_HIP(hipMemsetAsync(len.p, 0, sizeof(int32_t) * (size_t(nrows) + 1), st));
     if (nrows > 0) {
       hipLaunchKernelGGL(row_length_kernel, dim3(grid_for(nrows)), dim3(kBlock), 0, st, nrows, a->rowptr, d_rows, len.p);
       NSS_CHECK_LAUNCH();
     }
-    exclusive_sum(len.p, rowptr.p, size_t(nrows) + 1, st);
-    const int64_t nnz = fetch(rowptr.p + nrows, st);
-    Dev<int32_t> col(size_t(nnz) + 4, true);
-    Dev<double> val(size_t(nnz) + 4, true);
-    NSS_HIP(hipMemsetAsync(col.p, 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
-    NSS_HIP(hipMemsetAsync(val.p, 0, sizeof(double) * (size_t(nnz) + 4), st));
+    exclusive_sum(len.p, rowptr.get(), size_t(nrows) + 1, st);
+    const int64_t nnz = fetch(rowptr.get() + nrows, st);
+    DeviceBuffer<int32_t> col(size_t(nnz) + 4);
+    DeviceBuffer<double> val(size_t(nnz) + 4);
+    NSS_HIP(hipMemsetAsync(col.get(), 0, sizeof(int32_t) * (size_t(nnz) + 4), st));
+    NSS_HIP(hipMemsetAsync(val.get(), 0, sizeof(double) * (size_t(nnz) + 4), st));
     if (nrows > 0 && nnz > 0) {
       hipLaunchKernelGGL(row_copy_kernel, dim3((nrows + kBlock / 8 - 1) / (kBlock / 8)), dim3(kBlock), 0, st, nrows,
-                         a->rowptr, a->col, a->val, d_rows, rowptr.p, col.p, val.p);
-      hipLaunchKernelGGL(map_columns_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, d_colmap, col.p);
+                         a->rowptr, a->col, a->val, d_rows, rowptr.get(), col.get(), val.get());
+      hipLaunchKernelGGL(map_columns_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, d_colmap, col.get());
       NSS_CHECK_LAUNCH();
     }
     NSS_HIP(hipStreamSynchronize(st));
@@ -1033,35 +1022,31 @@ int nss_amg_prolongator(nss_csr_t a, const int64_t* d_agg, int64_t nagg, double 
     hipStream_t st = as_stream(stream);
     const int32_t m = a->m;
     // tentative prolongator T as a CSR matrix: row i has the single entry (agg[i], 1)
-    Dev<int32_t> trow(size_t(m) + 1, true), tcol(size_t(m) + 4, true);
-    Dev<double> tval(size_t(m) + 4, true);
+    DeviceBuffer<int32_t> trow(size_t(m) + 1), tcol(size_t(m) + 4);
+    DeviceBuffer<double> tval(size_t(m) + 4);
     {
       Dev<unsigned long long> bad(1);
       NSS_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), st));
-      NSS_HIP(hipMemsetAsync(tcol.p, 0, sizeof(int32_t) * (size_t(m) + 4), st));
-      NSS_HIP(hipMemsetAsync(tval.p, 0, sizeof(double) * (size_t(m) + 4), st));
-      hipLaunchKernelGGL(tentative_kernel, dim3(grid_for(int64_t(m) + 1)), dim3(kBlock), 0, st, m, d_agg, nagg, trow.p,
-                         tcol.p, tval.p, bad.p);
+      NSS_HIP(hipMemsetAsync(tcol.get(), 0, sizeof(int32_t) * (size_t(m) + 4), st));
+      NSS_HIP(hipMemsetAsync(tval.get(), 0, sizeof(double) * (size_t(m) + 4), st));
+      hipLaunchKernelGGL(tentative_kernel, dim3(grid_for(int64_t(m) + 1)), dim3(kBlock), 0, st, m, d_agg, nagg, trow.get(),
+                         tcol.get(), tval.get(), bad.p);
       NSS_CHECK_LAUNCH();
       NSS_REQUIRE(fetch(bad.p, st) == 0, "amg_prolongator: aggregate id out of range");
     }
-    nss_csr_s* T = adopt_csr(m, int32_t(nagg), m, trow, tcol, tval);
     RawCsr p;
-    try {
-      spgemm(*a, *T, st, int64_t(1) << 27, p);            // A T: the products are a_ik * 1
+    {
+      const std::unique_ptr<nss_csr_s> T(adopt_csr(m, int32_t(nagg), m, trow, tcol, tval));
+      spgemm(*a, *T, st, int64_t(1) << 27, p);              // A T: the products are a_ik * 1
       Dev<double> diag(m);
       hipLaunchKernelGGL(diag_kernel, dim3(grid_for(m)), dim3(kBlock), 0, st, m, a->rowptr, a->col, a->val, diag.p,
                          (double*)nullptr);
-      hipLaunchKernelGGL(smooth_prolongator_kernel, dim3(grid_for(m)), dim3(kBlock), 0, st, m, p.rowptr.p, p.col.p,
-                         p.val.p, diag.p, d_agg, omega);
+      hipLaunchKernelGGL(smooth_prolongator_kernel, dim3(grid_for(m)), dim3(kBlock), 0, st, m, p.rowptr.get(), p.col.get(),
+                         p.val.get(), diag.p, d_agg, omega);
       NSS_CHECK_LAUNCH();
       NSS_HIP(hipStreamSynchronize(st));
       drop_zeros(p, st);
-    } catch (...) {
-      nss_csr_destroy(T);
-      throw;
     }
-    nss_csr_destroy(T);
     *out = p.adopt();
   });
 }

@@ -7,7 +7,10 @@
 // back to 8-byte accesses.
 #include "nss_common.h"
 
+#include <atomic>
 #include <cstring>
+#include <mutex>
+#include <unordered_map>
 
 namespace nss {
 
@@ -24,11 +27,53 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+// ---- the library's device memory (device_buffer.h) -----------------------------------------------------------------
+// Every allocation of the library passes here; the table of live allocations gives device_free the size that hipFree
+// does not tell.  Leaked on purpose, like scratch(): nothing of it is destroyed at process exit.
+namespace {
+struct LiveMemory {
+  std::mutex lock;
+  std::unordered_map<void*, size_t> bytes_of;
+  int64_t bytes = 0;
+};
+LiveMemory& live_memory() {
+  static LiveMemory* const live = new LiveMemory;
+  return *live;
+}
+}  // namespace
+
+void* device_alloc(size_t bytes) {
+  void* p = nullptr;
+  NSS_HIP(hipMalloc(&p, bytes));
+  if (p) {
+    LiveMemory& live = live_memory();
+    std::lock_guard<std::mutex> hold(live.lock);
+    live.bytes_of[p] = bytes;
+    live.bytes += int64_t(bytes);
+  }
+  return p;
+}
+
+void device_free(void* p) noexcept {
+  if (!p) return;
+  {
+    LiveMemory& live = live_memory();
+    std::lock_guard<std::mutex> hold(live.lock);
+    const auto it = live.bytes_of.find(p);
+    if (it != live.bytes_of.end()) {
+      live.bytes -= int64_t(it->second);
+      live.bytes_of.erase(it);
+    }
+  }
+  (void)hipFree(p);
+}
+
+// (process lifetime: raw pointers, never freed)
 Scratch& scratch() {
   static Scratch s;
   if (!s.partials) {
-    NSS_HIP(hipMalloc(&s.partials, sizeof(double) * Scratch::kMaxPartials));
-    NSS_HIP(hipMalloc(&s.result, sizeof(double) * 8));
+    s.partials = static_cast<double*>(device_alloc(sizeof(double) * Scratch::kMaxPartials));
+    s.result = static_cast<double*>(device_alloc(sizeof(double) * 8));
     NSS_HIP(hipHostMalloc(&s.host, sizeof(double) * 8, hipHostMallocDefault));
   }
   return s;
@@ -275,6 +320,15 @@ extern "C" {
 int nss_abi_version(void) { return NSS_ABI_VERSION; }
 
 const char* nss_last_error(void) { return g_error; }
+
+int nss_device_memory(int64_t* live_bytes, int64_t* live_allocations) {
+  return guarded([&] {
+    LiveMemory& live = live_memory();
+    std::lock_guard<std::mutex> hold(live.lock);
+    if (live_bytes) *live_bytes = live.bytes;
+    if (live_allocations) *live_allocations = int64_t(live.bytes_of.size());
+  });
+}
 
 int nss_stream_loads_mode(int32_t mode) {
   return guarded([&] {

@@ -168,10 +168,10 @@ struct DictLds<Coded8> {
 struct nss_csr_s {
   int32_t m = 0, n = 0;
   int64_t nnz = 0;
-  int32_t* rowptr = nullptr;
-  int32_t* col = nullptr;
-  double* val = nullptr;
-  int32_t* rowblk = nullptr;
+  nss::DeviceBuffer<int32_t> rowptr;
+  nss::DeviceBuffer<int32_t> col;
+  nss::DeviceBuffer<double> val;
+  nss::DeviceBuffer<int32_t> rowblk;
   int32_t nblk = 0;
   int32_t rg = 1;
   int32_t chunk = nss::kChunk;   // products the kernels' LDS buffer holds (the template parameter CH)
@@ -187,8 +187,8 @@ struct nss_csr_s {
   // 4 bits of window number + 12 bits of offset, decoded through the block's 16 window bases
   // (held in LDS), instead of the 4-byte index: 2 bytes per non-zero less HBM traffic, same
   // products in the same order.  `col` is kept for the set-up kernels and rows longer than a chunk.
-  uint16_t* col16 = nullptr;
-  int32_t* blkbase = nullptr;
+  nss::DeviceBuffer<uint16_t> col16;
+  nss::DeviceBuffer<int32_t> blkbase;
   // Staged operand (preferred where the kernel's operand is one stored vector).  Measured on gfx950
   // (tools/spmv_probe.py, profiles/r02_gather_probe.txt): what keeps the stream kernel at ~5 TB/s is not the
   // bytes of the x gather but the gather itself, a second round of per-lane loads that can only be issued when
@@ -202,8 +202,8 @@ struct nss_csr_s {
   // reads the operand from LDS: no window decode, no dependent gather.  Same products, same order, same results.
   // A matrix is staged only when every one of its row blocks fits.  The window form is kept beside it for
   // kernels whose operand is an expression of two vectors (they gather).
-  uint16_t* pos16 = nullptr;
-  int32_t* blkseg = nullptr;
+  nss::DeviceBuffer<uint16_t> pos16;
+  nss::DeviceBuffer<int32_t> blkseg;
   // Reuse-aware dispatch order (grid operators beyond ~1e7 rows).  XCD i walks its contiguous eighth of the row
   // blocks; the operand runs a block stages besides its own neighbourhood -- the grid planes above and below --
   // are staged again by the blocks P positions further down the walk (P = row blocks per plane).  Up to ~200
@@ -213,7 +213,7 @@ struct nss_csr_s {
   // back, then b + 1, b + 1 + P, ...: the re-reads are adjacent in time.  Only the workgroup -> row block map
   // changes: per-row sums and the per-block dot-partial slots, hence all bits, stay.  Built at upload from the run
   // starts (spmv.hip: build_dispatch); full-range launches of the staged forms use it.
-  int32_t* blkdisp = nullptr;
+  nss::DeviceBuffer<int32_t> blkdisp;
   double disp_period = 0.0;      // P (row blocks), 0: natural order
   int32_t disp_planes = 0;       // T
   // Pair-staged operand: kernels whose operand is an expression of TWO stored vectors (t1 - s0 in the rows of B,
@@ -233,27 +233,30 @@ struct nss_csr_s {
   // csr_direct_kernel: one lane per row, no LDS staging, every load of a lane's rows requested up front -- the
   // stream kernel spends most of a 2-entry-per-row launch in its per-row phase (1024 rows per workgroup, four
   // passes, the epilogue's loads of each pass behind the previous one's stores).
-  int32_t* ell_col = nullptr;
-  double* ell_val = nullptr;
+  nss::DeviceBuffer<int32_t> ell_col;
+  nss::DeviceBuffer<double> ell_val;
   // Row blocks planned around the blocks of ONE block-Jacobi handle (nss_csr_plan_for_blocks: every row block holds
   // whole Jacobi blocks and at most kBlockRows rows): a kernel over the rows of this matrix can then apply that
   // preconditioner to its own result in the epilogue -- the row block's results pass through LDS, lanes take one
   // Jacobi block each (the fused BPCG loop: t1 = k J t0 inside C1, no launch of its own and no re-read of t0).
   // jb_order = the Jacobi blocks in row order (callers number them as they like); jb_first[b] = position in jb_order of
   // the first Jacobi block of row block b (nblk + 1 entries); jb_serial = nss_bjac_s::serial of that handle.
-  int32_t* jb_first = nullptr;
-  int32_t* jb_order = nullptr;
+  nss::DeviceBuffer<int32_t> jb_first;
+  nss::DeviceBuffer<int32_t> jb_order;
   // Fixed-width copy for EPILOGUE use (nss::fixed_width_copy, built on first request): the kDirectWidth (column,
   // value) slots per row of a matrix with at most that many entries per row, whatever its size -- a kernel over the
   // rows of ANOTHER matrix with the same row count can then add this matrix's row product from registers (fused
-  // MINRES: B^T z1 inside the rows of A).  Aliases ell_col / ell_val when those exist.  fw_state: 0 not tried, 1, -1.
-  int32_t* fw_col = nullptr;
+  // MINRES: B^T z1 inside the rows of A).  fw_col / fw_val are views, not owners: of ell_col / ell_val when those
+  // exist, else of fw_own_col / fw_own_val, the handle's own copy.  fw_state: 0 not tried, 1, -1.
+  const int32_t* fw_col = nullptr;
   double* fw_val = nullptr;
+  nss::DeviceBuffer<int32_t> fw_own_col;
+  nss::DeviceBuffer<double> fw_own_val;
   int fw_state = 0;
   // fp32 value storage (nss_csr_narrow_f32): the values rounded once to fp32 and stored 4 bytes wide in `val32`; `val`
   // is then NULL.  Only the kernel paths instantiated for it take such a matrix (launch_csr with kF32, the joint AMG
   // cycle); every other path refuses it (view() without `narrow_ok`, require_f64_values) -- none reads it as doubles.
-  float* val32 = nullptr;
+  nss::DeviceBuffer<float> val32;
   // Value codes (nss_csr_code_values): a matrix with at most kDictSize distinct 64-bit value patterns -- every operator
   // of a uniform grid has a handful -- also holds val8, one byte per entry in CSR order (padded like `val`), and `dict`,
   // the kDictSize doubles the codes index (sorted by bit pattern, unused slots 0).  The kernels instantiated for it
@@ -261,9 +264,9 @@ struct nss_csr_s {
   // products in the same order.  `val` STAYS: every set-up path and every kernel without a coded form reads it, and the
   // codes are per entry in CSR order, so re-plans keep them.  ell_code: the two slots' codes of the fixed-width copy,
   // one 16-bit word per row (slot 0 in the low byte), built with ell_col.  Writers of `val` drop the codes.
-  uint8_t* val8 = nullptr;
-  double* dict = nullptr;
-  uint16_t* ell_code = nullptr;
+  nss::DeviceBuffer<uint8_t> val8;
+  nss::DeviceBuffer<double> dict;
+  nss::DeviceBuffer<uint16_t> ell_code;
   int32_t dict_count = 0;
   // Row slots (nss_csr_plan_row_slots): the eight-slot copy of a coded, staged matrix whose rows hold at most
   // kSlotWidth entries, for the row-per-lane kernel of the staged operand (csr_slots_kernel).  Per row one aligned
@@ -272,8 +275,8 @@ struct nss_csr_s {
   // positions are relative to the operand runs of ONE launch plan: slot_gen is the plan generation the copy was built
   // for, replan() frees it, and a launcher takes it only through row_slots().  slot_state -1: refused by the caller
   // (mode 0), automatic requests leave the handle alone.
-  uint16_t* slot_pos = nullptr;
-  uint8_t* slot_code = nullptr;
+  nss::DeviceBuffer<uint16_t> slot_pos;
+  nss::DeviceBuffer<uint8_t> slot_code;
   int64_t slot_gen = -1;
   int slot_state = 0;
   uint64_t jb_serial = 0;
@@ -1176,8 +1179,8 @@ inline bool takes_row_slots(const nss_csr_s& A) {
   if (IDX == 0 || A.m == 0 || A.nblk == 0 || !A.row_slots()) return false;
   return A.idx_mode(EpiX<Epi>::type::kStageable, XPairable<typename EpiX<Epi>::type>::value) == IDX;
 }
-inline const uint4v* slot_positions(const nss_csr_s& A) { return reinterpret_cast<const uint4v*>(A.slot_pos); }
-inline const uint2v* slot_codes(const nss_csr_s& A) { return reinterpret_cast<const uint2v*>(A.slot_code); }
+inline const uint4v* slot_positions(const nss_csr_s& A) { return reinterpret_cast<const uint4v*>(A.slot_pos.get()); }
+inline const uint2v* slot_codes(const nss_csr_s& A) { return reinterpret_cast<const uint2v*>(A.slot_code.get()); }
 
 // A x into `epi` by the row-slot kernel; false (nothing launched) when A does not take it
 template <class Epi>

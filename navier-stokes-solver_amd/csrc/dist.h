@@ -48,7 +48,7 @@ struct nss_dist_amg_s {
   nss_halo_t halo{};                   // of the iterate x (ext = x's halo-extended buffer)
   int32_t channel = 0;                 // mailbox transport: the channel of halo's layout (nss_dist_amg_set_channel)
   int32_t n = 0, nc = 0;
-  double *res = nullptr, *rc = nullptr, *rc_local = nullptr, *ec = nullptr;   // work vectors (owned by the handle)
+  nss::DeviceBuffer<double> res, rc, rc_local, ec;   // work vectors
 };
 
 // The auxiliary-space term of MypreA, transform @ V(L) @ transform.T (templates/NavierStokesSIMPLE_iterative.py:336-337,
@@ -67,7 +67,7 @@ struct nss_dist_aux_s {
   bool has_halo_y = false;
   int32_t ch_x = 0, ch_e = 0, ch_y = 0;   // mailbox transport: the channels of the three halos (nss_dist_aux_set_channels)
   int32_t n_u = 0, n_nodes = 0;
-  double* r_aux = nullptr;             // nodal work vector (owned by the handle)
+  nss::DeviceBuffer<double> r_aux;     // nodal work vector
 };
 
 namespace nss {

@@ -21,6 +21,8 @@
 
 #include <dlfcn.h>
 
+#include <memory>
+
 namespace nss {
 
 // marks of one profiled iteration: segment i = [mark i, mark i + 1)
@@ -233,26 +235,21 @@ int nss_dist_aux_create(nss_dist_t d, nss_csr_t tt_loc, const nss_halo_t* halo_x
     check_halo(halo_x, *tt_loc, "dist_aux halo_x");
     check_halo(halo_e, *t_loc, "dist_aux halo_e");
     NSS_REQUIRE(amg->d == d, "dist_aux_create: the V-cycle belongs to another communicator handle");
-    nss_dist_aux_s* h = new nss_dist_aux_s;
-    try {
-      h->d = d;
-      h->TT = tt_loc;
-      h->T = t_loc;
-      h->amg = amg;
-      h->halo_x = *halo_x;
-      h->halo_e = *halo_e;
-      if (halo_y) {
-        h->halo_y = *halo_y;
-        h->has_halo_y = true;
-      }
-      h->n_u = n_u;
-      h->n_nodes = n_nodes;
-      NSS_HIP(hipMalloc(&h->r_aux, sizeof(double) * size_t(std::max(1, n_nodes))));
-    } catch (...) {
-      nss_dist_aux_destroy(h);
-      throw;
+    std::unique_ptr<nss_dist_aux_s> h(new nss_dist_aux_s);
+    h->d = d;
+    h->TT = tt_loc;
+    h->T = t_loc;
+    h->amg = amg;
+    h->halo_x = *halo_x;
+    h->halo_e = *halo_e;
+    if (halo_y) {
+      h->halo_y = *halo_y;
+      h->has_halo_y = true;
     }
-    *out = h;
+    h->n_u = n_u;
+    h->n_nodes = n_nodes;
+    h->r_aux.alloc(size_t(std::max(1, n_nodes)));
+    *out = h.release();
   });
 }
 
@@ -268,11 +265,7 @@ int nss_dist_aux_set_channels(nss_dist_aux_t h, int32_t ch_x, int32_t ch_e, int3
 }
 
 int nss_dist_aux_destroy(nss_dist_aux_t h) {
-  return guarded([&] {
-    if (!h) return;
-    (void)hipFree(h->r_aux);
-    delete h;
-  });
+  return guarded([&] { delete h; });
 }
 
 int nss_dist_aux_apply_f64(nss_dist_aux_t h, double scale, const double* b, double* y, nss_stream_t stream) {
@@ -291,26 +284,21 @@ int nss_dist_amg_create(nss_dist_t d, nss_csr_t a_loc, const nss_halo_t* halo_x,
     NSS_REQUIRE(a_loc->n >= n && r_loc->m == nc && r_loc->n == n && p_loc->m == n && p_loc->n == nc,
                 "dist_amg_create: operator shapes do not chain");
     check_halo(halo_x, *a_loc, "dist_amg halo");
-    nss_dist_amg_s* h = new nss_dist_amg_s;
-    try {
-      h->d = d;
-      h->A = a_loc;
-      h->R = r_loc;
-      h->P = p_loc;
-      h->wdinv = wdinv;
-      h->coarse = coarse;
-      h->halo = *halo_x;
-      h->n = n;
-      h->nc = nc;
-      NSS_HIP(hipMalloc(&h->res, sizeof(double) * size_t(std::max(1, n))));
-      NSS_HIP(hipMalloc(&h->rc, sizeof(double) * size_t(std::max(1, nc))));
-      NSS_HIP(hipMalloc(&h->rc_local, sizeof(double) * size_t(std::max(1, nc))));
-      NSS_HIP(hipMalloc(&h->ec, sizeof(double) * size_t(std::max(1, nc))));
-    } catch (...) {
-      nss_dist_amg_destroy(h);
-      throw;
-    }
-    *out = h;
+    std::unique_ptr<nss_dist_amg_s> h(new nss_dist_amg_s);
+    h->d = d;
+    h->A = a_loc;
+    h->R = r_loc;
+    h->P = p_loc;
+    h->wdinv = wdinv;
+    h->coarse = coarse;
+    h->halo = *halo_x;
+    h->n = n;
+    h->nc = nc;
+    h->res.alloc(size_t(std::max(1, n)));
+    h->rc.alloc(size_t(std::max(1, nc)));
+    h->rc_local.alloc(size_t(std::max(1, nc)));
+    h->ec.alloc(size_t(std::max(1, nc)));
+    *out = h.release();
   });
 }
 
@@ -323,14 +311,7 @@ int nss_dist_amg_set_channel(nss_dist_amg_t h, int32_t channel) {
 }
 
 int nss_dist_amg_destroy(nss_dist_amg_t h) {
-  return guarded([&] {
-    if (!h) return;
-    (void)hipFree(h->res);
-    (void)hipFree(h->rc);
-    (void)hipFree(h->rc_local);
-    (void)hipFree(h->ec);
-    delete h;
-  });
+  return guarded([&] { delete h; });
 }
 
 int nss_dist_amg_apply_f64(nss_dist_amg_t h, double scale, const double* b, double* y, nss_stream_t stream) {
@@ -344,35 +325,30 @@ int nss_dist_create(void* nccl_comm, int32_t nranks, int32_t rank, nss_dist_t* o
   return guarded([&] {
     NSS_REQUIRE(out != nullptr, "dist_create: out is NULL");
     NSS_REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, "dist_create: bad rank / size");
-    nss_dist_s* d = new nss_dist_s;
-    try {
-      d->comm = nccl_comm;
-      d->nranks = nranks;
-      d->rank = rank;
-      if (nccl_comm) {
-        for (const char* name : {"librccl.so.1", "librccl.so"}) {
-          d->lib = dlopen(name, RTLD_NOW | RTLD_NOLOAD);
-          if (!d->lib) d->lib = dlopen(name, RTLD_NOW);
-          if (d->lib) break;
-        }
-        if (!d->lib) throw Error("dist_create: cannot open librccl");
-        resolve(d->lib, "ncclAllReduce", d->AllReduce);
-        resolve(d->lib, "ncclSend", d->Send);
-        resolve(d->lib, "ncclRecv", d->Recv);
-        resolve(d->lib, "ncclGroupStart", d->GroupStart);
-        resolve(d->lib, "ncclGroupEnd", d->GroupEnd);
-        resolve(d->lib, "ncclGetErrorString", d->GetErrorString);
+    std::unique_ptr<nss_dist_s, int (*)(nss_dist_t)> d(new nss_dist_s, nss_dist_destroy);   // (destroys the events and the stream)
+    d->comm = nccl_comm;
+    d->nranks = nranks;
+    d->rank = rank;
+    if (nccl_comm) {
+      for (const char* name : {"librccl.so.1", "librccl.so"}) {
+        d->lib = dlopen(name, RTLD_NOW | RTLD_NOLOAD);
+        if (!d->lib) d->lib = dlopen(name, RTLD_NOW);
+        if (d->lib) break;
       }
-      NSS_HIP(hipStreamCreateWithFlags(&d->xstream, hipStreamNonBlocking));
-      for (int i = 0; i < 3; ++i) {
-        NSS_HIP(hipEventCreateWithFlags(&d->ev_ready[i], hipEventDisableTiming));
-        NSS_HIP(hipEventCreateWithFlags(&d->ev_halo[i], hipEventDisableTiming));
-      }
-    } catch (...) {
-      nss_dist_destroy(d);
-      throw;
+      if (!d->lib) throw Error("dist_create: cannot open librccl");
+      resolve(d->lib, "ncclAllReduce", d->AllReduce);
+      resolve(d->lib, "ncclSend", d->Send);
+      resolve(d->lib, "ncclRecv", d->Recv);
+      resolve(d->lib, "ncclGroupStart", d->GroupStart);
+      resolve(d->lib, "ncclGroupEnd", d->GroupEnd);
+      resolve(d->lib, "ncclGetErrorString", d->GetErrorString);
     }
-    *out = d;
+    NSS_HIP(hipStreamCreateWithFlags(&d->xstream, hipStreamNonBlocking));
+    for (int i = 0; i < 3; ++i) {
+      NSS_HIP(hipEventCreateWithFlags(&d->ev_ready[i], hipEventDisableTiming));
+      NSS_HIP(hipEventCreateWithFlags(&d->ev_halo[i], hipEventDisableTiming));
+    }
+    *out = d.release();
   });
 }
 

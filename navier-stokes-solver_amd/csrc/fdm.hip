@@ -27,6 +27,7 @@
 // Per pass over N = outer n inner cells: 16 N bytes (X read once per tile row of i, i.e. ceil(n / 64) times, the
 // re-reads from L2; M from L2) and 2 n N flops.
 #include <cmath>
+#include <memory>
 
 #include "nss_common.h"
 
@@ -196,16 +197,10 @@ struct nss_fdm_s {
   int dim = 0;
   int64_t ext[3] = {1, 1, 1};
   int64_t cells = 0;
-  double* Q[3] = {nullptr, nullptr, nullptr};              // device, row-major ext[a] x ext[a]
-  double* lam = nullptr;                                   // device, the d eigenvalue vectors one after the other
-  double* work[2] = {nullptr, nullptr};                    // device, `cells` doubles each
-  FdmScale scale{};
-
-  ~nss_fdm_s() {
-    for (double* p : Q) (void)hipFree(p);
-    (void)hipFree(lam);
-    for (double* p : work) (void)hipFree(p);
-  }
+  DeviceBuffer<double> Q[3];                               // device, row-major ext[a] x ext[a]
+  DeviceBuffer<double> lam;                                // device, the d eigenvalue vectors one after the other
+  DeviceBuffer<double> work[2];                            // device, `cells` doubles each
+  FdmScale scale{};                                        // (its lam[] point into `lam`)
 };
 
 extern "C" {
@@ -253,31 +248,26 @@ int nss_fdm_create(int32_t dim, const int64_t* h_extents, const double* const* h
     const int64_t cells = fdm_cells(h_extents, dim, "fdm_create");
     for (int a = 0; a < dim; ++a) NSS_REQUIRE(h_Q[a] && h_lambda[a], "fdm_create: NULL factor");
     *out = nullptr;
-    auto* h = new nss_fdm_s();
-    try {
-      h->dim = dim;
-      h->cells = cells;
-      int64_t total = 0;
-      for (int a = 0; a < dim; ++a) total += (h->ext[a] = h_extents[a]);
-      NSS_HIP(hipMalloc(&h->lam, sizeof(double) * size_t(total)));
-      h->scale.dim = dim;
-      h->scale.threshold = null_threshold;
-      int64_t at = 0;
-      for (int a = 0; a < dim; ++a) {
-        const size_t e = size_t(h->ext[a]);
-        NSS_HIP(hipMalloc(&h->Q[a], sizeof(double) * e * e));
-        NSS_HIP(hipMemcpy(h->Q[a], h_Q[a], sizeof(double) * e * e, hipMemcpyHostToDevice));
-        NSS_HIP(hipMemcpy(h->lam + at, h_lambda[a], sizeof(double) * e, hipMemcpyHostToDevice));
-        h->scale.lam[a] = h->lam + at;
-        h->scale.ext[a] = int32_t(e);
-        at += int64_t(e);
-      }
-      for (double*& w : h->work) NSS_HIP(hipMalloc(&w, sizeof(double) * size_t(cells)));
-    } catch (...) {
-      delete h;
-      throw;
+    std::unique_ptr<nss_fdm_s> h(new nss_fdm_s);
+    h->dim = dim;
+    h->cells = cells;
+    int64_t total = 0;
+    for (int a = 0; a < dim; ++a) total += (h->ext[a] = h_extents[a]);
+    h->lam.alloc(size_t(total));
+    h->scale.dim = dim;
+    h->scale.threshold = null_threshold;
+    int64_t at = 0;
+    for (int a = 0; a < dim; ++a) {
+      const size_t e = size_t(h->ext[a]);
+      h->Q[a].alloc(e * e);
+      NSS_HIP(hipMemcpy(h->Q[a], h_Q[a], sizeof(double) * e * e, hipMemcpyHostToDevice));
+      NSS_HIP(hipMemcpy(h->lam + at, h_lambda[a], sizeof(double) * e, hipMemcpyHostToDevice));
+      h->scale.lam[a] = h->lam + at;
+      h->scale.ext[a] = int32_t(e);
+      at += int64_t(e);
     }
-    *out = h;
+    for (DeviceBuffer<double>& w : h->work) w.alloc(size_t(cells));
+    *out = h.release();
   });
 }
 

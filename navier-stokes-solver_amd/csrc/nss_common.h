@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../../include/nss_krylov.h"
+#include "device_buffer.h"
 
 // Non-temporal stores for vectors that are written once and next read by a later kernel: they do not
 // allocate in the 4-MiB XCD L2s, which the SpMV kernels need for the gathered x window.  Levels

@@ -105,13 +105,14 @@ __device__ __forceinline__ double p2p_allreduce_sum(const P2pView& v, double loc
 // host side of the transport (p2p.hip)
 struct nss_p2p_s {
   int32_t nranks = 1, rank = 0;
-  char* region = nullptr;                    // own fine-grained region
+  char* region = nullptr;                    // own fine-grained region (hipExtMallocWithFlags; nss_p2p_destroy frees it
+                                             // after the peers' mappings are closed)
   size_t region_bytes = 0;
   unsigned long long* mail = nullptr;        // region + 0
-  std::vector<char*> peer_region;            // mapped peers (own: region)
-  unsigned long long** d_peer_mail = nullptr;   // device array [nranks]
-  int32_t* d_error = nullptr;
-  int32_t* d_ticket = nullptr;               // [kP2pMaxSegments] workgroup tickets of the put kernel
+  std::vector<char*> peer_region;            // mapped peers (own: region), opened and closed by IPC handle: not owned
+  nss::DeviceBuffer<unsigned long long*> d_peer_mail;   // device array [nranks]
+  nss::DeviceBuffer<int32_t> d_error;
+  nss::DeviceBuffer<int32_t> d_ticket;       // [kP2pMaxSegments] workgroup tickets of the put kernel
   uint32_t seq = 0;                          // host counter of collectives issued
   // One CHANNEL per operand layout this handle serves (bound at creation, numbered in the order of nss_p2p_create's
   // halos): its arrival flags (one per source rank), its landing zone, the own receive table and, after connect, where

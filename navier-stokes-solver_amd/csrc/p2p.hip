@@ -3,6 +3,7 @@
 #include "dist.h"
 
 #include <cstring>
+#include <memory>
 
 namespace nss {
 
@@ -269,94 +270,89 @@ int p2p_create(int32_t nranks, int32_t rank, int32_t nhalo, const nss_halo_t* co
     NSS_REQUIRE(out && h_blob && halos && n_owned, "p2p_create: NULL argument");
     NSS_REQUIRE(nranks >= 1 && nranks <= kP2pMaxRanks && rank >= 0 && rank < nranks, "p2p_create: bad rank / size (at most 16 ranks)");
     NSS_REQUIRE(nhalo >= 1 && nhalo <= kP2pMaxChannels, "p2p_create: 1 .. 4 operand layouts");
-    nss_p2p_s* p = new nss_p2p_s;
-    try {
-      p->nranks = nranks;
-      p->rank = rank;
-      size_t off = mail_bytes(nranks);
-      for (int c = 0; c < nhalo; ++c) {
-        const nss_halo_t* halo = halos[c];
-        NSS_REQUIRE(halo != nullptr, "p2p_create: NULL halo");
-        NSS_REQUIRE(halo->direct || halo->n_send == 0, "p2p_create: the halos must send contiguous runs (direct)");
-        nss_p2p_s::Channel ch;
-        ch.n_owned = n_owned[c];
-        ch.recv_off.assign(size_t(nranks), -1);
-        ch.recv_cnt.assign(size_t(nranks), 0);
-        int64_t total = 0;
-        for (int i = 0; i < halo->n_recv; ++i) {
-          const int q = halo->h_recv_peer[i];
-          NSS_REQUIRE(q >= 0 && q < nranks && q != rank, "p2p_create: bad source rank");
-          ch.recv_off[size_t(q)] = halo->h_recv_off[i] - n_owned[c];
-          ch.recv_cnt[size_t(q)] = halo->h_recv_cnt[i];
-          total += halo->h_recv_cnt[i];
-        }
-        ch.landing_doubles = std::max<int64_t>(total, 1);
-        ch.flags_off = off;
-        off += flags_bytes();
-        p->channels.push_back(ch);
+    std::unique_ptr<nss_p2p_s, int (*)(nss_p2p_t)> p(new nss_p2p_s, nss_p2p_destroy);   // (unmaps and frees the region)
+    p->nranks = nranks;
+    p->rank = rank;
+    size_t off = mail_bytes(nranks);
+    for (int c = 0; c < nhalo; ++c) {
+      const nss_halo_t* halo = halos[c];
+      NSS_REQUIRE(halo != nullptr, "p2p_create: NULL halo");
+      NSS_REQUIRE(halo->direct || halo->n_send == 0, "p2p_create: the halos must send contiguous runs (direct)");
+      nss_p2p_s::Channel ch;
+      ch.n_owned = n_owned[c];
+      ch.recv_off.assign(size_t(nranks), -1);
+      ch.recv_cnt.assign(size_t(nranks), 0);
+      int64_t total = 0;
+      for (int i = 0; i < halo->n_recv; ++i) {
+        const int q = halo->h_recv_peer[i];
+        NSS_REQUIRE(q >= 0 && q < nranks && q != rank, "p2p_create: bad source rank");
+        ch.recv_off[size_t(q)] = halo->h_recv_off[i] - n_owned[c];
+        ch.recv_cnt[size_t(q)] = halo->h_recv_cnt[i];
+        total += halo->h_recv_cnt[i];
       }
-      if (vec_n > 0) {   // vector zone: flags, then two copies of the segments of all ranks (the same in every region)
-        NSS_REQUIRE(vec_lo && vec_hi, "p2p_create: NULL contribution range");
-        int64_t total = 0;
-        for (int q = 0; q < nranks; ++q) {
-          NSS_REQUIRE(0 <= vec_lo[q] && vec_lo[q] <= vec_hi[q] && vec_hi[q] <= vec_n,
-                      "p2p_create: contribution range outside [0, n)");
-          p->vec_lo.push_back(vec_lo[q]);
-          p->vec_hi.push_back(vec_hi[q]);
-          p->vec_off.push_back(total);
-          total += vec_hi[q] - vec_lo[q];
-        }
-        p->vec_n = vec_n;
-        p->vec_flags_off = off;
-        off += flags_bytes();
-        off = (off + 255) & ~size_t(255);
-        p->vec_zone_off = off;
-        p->vec_zone_bytes = (sizeof(double) * size_t(std::max<int64_t>(total, 1)) + 255) & ~size_t(255);
-        off += 2 * p->vec_zone_bytes;
-      }
-      // landing zones behind all flag rows; their sizes differ from rank to rank, so every rank publishes ITS offsets
-      // relative to a layout that only depends on (nranks, nhalo): zone c starts at a 256-byte aligned offset that the
-      // OWNER computes -- the sender needs the owner's value, which travels in the blob
-      for (int c = 0; c < nhalo; ++c) {
-        off = (off + 255) & ~size_t(255);
-        p->channels[size_t(c)].landing_off = off;
-        p->channels[size_t(c)].zone_bytes = (sizeof(double) * size_t(p->channels[size_t(c)].landing_doubles) + 255) & ~size_t(255);
-        off += 2 * p->channels[size_t(c)].zone_bytes;
-      }
-      p->region_bytes = off;
-      // fine-grained device memory: remote stores become visible to this GPU's loads without cache maintenance
-      void* mem = nullptr;
-      NSS_HIP(hipExtMallocWithFlags(&mem, p->region_bytes, hipDeviceMallocFinegrained));
-      p->region = static_cast<char*>(mem);
-      NSS_HIP(hipMemset(p->region, 0, p->region_bytes));
-      p->mail = reinterpret_cast<unsigned long long*>(p->region);
-      NSS_HIP(hipMalloc(&p->d_error, sizeof(int32_t)));
-      NSS_HIP(hipMemset(p->d_error, 0, sizeof(int32_t)));
-      NSS_HIP(hipMalloc(&p->d_ticket, sizeof(int32_t) * kP2pMaxSegments));
-      NSS_HIP(hipMemset(p->d_ticket, 0, sizeof(int32_t) * kP2pMaxSegments));
-      NSS_HIP(hipDeviceSynchronize());
-      hipIpcMemHandle_t handle;
-      NSS_HIP(hipIpcGetMemHandle(&handle, p->region));
-      static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-      char* blob = static_cast<char*>(h_blob);
-      std::memcpy(blob, &handle, 64);
-      for (int c = 0; c < nhalo; ++c) {
-        // what the senders need: where (in bytes from the start of MY region) rank q's segment goes, and how long it is
-        std::vector<int64_t> where(size_t(nranks), -1);
-        for (int q = 0; q < nranks; ++q)
-          if (p->channels[size_t(c)].recv_off[size_t(q)] >= 0)
-            where[size_t(q)] = int64_t(p->channels[size_t(c)].landing_off) + 8 * p->channels[size_t(c)].recv_off[size_t(q)];
-        char* at = blob + 64 + chan_blob(nranks) * c;
-        std::memcpy(at, where.data(), sizeof(int64_t) * size_t(nranks));
-        std::memcpy(at + 8 * size_t(nranks), p->channels[size_t(c)].recv_cnt.data(), sizeof(int64_t) * size_t(nranks));
-        const int64_t zb = int64_t(p->channels[size_t(c)].zone_bytes);
-        std::memcpy(at + 16 * size_t(nranks), &zb, sizeof(int64_t));
-      }
-    } catch (...) {
-      nss_p2p_destroy(p);
-      throw;
+      ch.landing_doubles = std::max<int64_t>(total, 1);
+      ch.flags_off = off;
+      off += flags_bytes();
+      p->channels.push_back(ch);
     }
-    *out = p;
+    if (vec_n > 0) {   // vector zone: flags, then two copies of the segments of all ranks (the same in every region)
+      NSS_REQUIRE(vec_lo && vec_hi, "p2p_create: NULL contribution range");
+      int64_t total = 0;
+      for (int q = 0; q < nranks; ++q) {
+        NSS_REQUIRE(0 <= vec_lo[q] && vec_lo[q] <= vec_hi[q] && vec_hi[q] <= vec_n,
+                    "p2p_create: contribution range outside [0, n)");
+        p->vec_lo.push_back(vec_lo[q]);
+        p->vec_hi.push_back(vec_hi[q]);
+        p->vec_off.push_back(total);
+        total += vec_hi[q] - vec_lo[q];
+      }
+      p->vec_n = vec_n;
+      p->vec_flags_off = off;
+      off += flags_bytes();
+      off = (off + 255) & ~size_t(255);
+      p->vec_zone_off = off;
+      p->vec_zone_bytes = (sizeof(double) * size_t(std::max<int64_t>(total, 1)) + 255) & ~size_t(255);
+      off += 2 * p->vec_zone_bytes;
+    }
+    // landing zones behind all flag rows; their sizes differ from rank to rank, so every rank publishes ITS offsets
+    // relative to a layout that only depends on (nranks, nhalo): zone c starts at a 256-byte aligned offset that the
+    // OWNER computes -- the sender needs the owner's value, which travels in the blob
+    for (int c = 0; c < nhalo; ++c) {
+      off = (off + 255) & ~size_t(255);
+      p->channels[size_t(c)].landing_off = off;
+      p->channels[size_t(c)].zone_bytes = (sizeof(double) * size_t(p->channels[size_t(c)].landing_doubles) + 255) & ~size_t(255);
+      off += 2 * p->channels[size_t(c)].zone_bytes;
+    }
+    p->region_bytes = off;
+    // fine-grained device memory: remote stores become visible to this GPU's loads without cache maintenance
+    void* mem = nullptr;
+    NSS_HIP(hipExtMallocWithFlags(&mem, p->region_bytes, hipDeviceMallocFinegrained));
+    p->region = static_cast<char*>(mem);
+    NSS_HIP(hipMemset(p->region, 0, p->region_bytes));
+    p->mail = reinterpret_cast<unsigned long long*>(p->region);
+    p->d_error.alloc(1);
+    NSS_HIP(hipMemset(p->d_error, 0, sizeof(int32_t)));
+    p->d_ticket.alloc(kP2pMaxSegments);
+    NSS_HIP(hipMemset(p->d_ticket, 0, sizeof(int32_t) * kP2pMaxSegments));
+    NSS_HIP(hipDeviceSynchronize());
+    hipIpcMemHandle_t handle;
+    NSS_HIP(hipIpcGetMemHandle(&handle, p->region));
+    static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
+    char* blob = static_cast<char*>(h_blob);
+    std::memcpy(blob, &handle, 64);
+    for (int c = 0; c < nhalo; ++c) {
+      // what the senders need: where (in bytes from the start of MY region) rank q's segment goes, and how long it is
+      std::vector<int64_t> where(size_t(nranks), -1);
+      for (int q = 0; q < nranks; ++q)
+        if (p->channels[size_t(c)].recv_off[size_t(q)] >= 0)
+          where[size_t(q)] = int64_t(p->channels[size_t(c)].landing_off) + 8 * p->channels[size_t(c)].recv_off[size_t(q)];
+      char* at = blob + 64 + chan_blob(nranks) * c;
+      std::memcpy(at, where.data(), sizeof(int64_t) * size_t(nranks));
+      std::memcpy(at + 8 * size_t(nranks), p->channels[size_t(c)].recv_cnt.data(), sizeof(int64_t) * size_t(nranks));
+      const int64_t zb = int64_t(p->channels[size_t(c)].zone_bytes);
+      std::memcpy(at + 16 * size_t(nranks), &zb, sizeof(int64_t));
+    }
+    *out = p.release();
   });
 }
 }  // namespace
@@ -408,7 +404,7 @@ int nss_p2p_connect(nss_p2p_t p, const void* h_blobs) {
       }
       mails[size_t(q)] = reinterpret_cast<unsigned long long*>(p->peer_region[size_t(q)]);
     }
-    NSS_HIP(hipMalloc(&p->d_peer_mail, sizeof(unsigned long long*) * size_t(p->nranks)));
+    p->d_peer_mail.alloc(size_t(p->nranks));
     NSS_HIP(hipMemcpy(p->d_peer_mail, mails.data(), sizeof(unsigned long long*) * size_t(p->nranks), hipMemcpyHostToDevice));
     p->connected = true;
   });
@@ -420,10 +416,7 @@ int nss_p2p_destroy(nss_p2p_t p) {
     (void)hipDeviceSynchronize();
     for (int q = 0; q < int(p->peer_region.size()); ++q)
       if (q != p->rank && p->peer_region[size_t(q)]) (void)hipIpcCloseMemHandle(p->peer_region[size_t(q)]);
-    (void)hipFree(p->region);
-    (void)hipFree(p->d_peer_mail);
-    (void)hipFree(p->d_error);
-    (void)hipFree(p->d_ticket);
+    (void)hipFree(p->region);                              // (hipExtMallocWithFlags: not counted by nss_device_memory)
     delete p;
   });
 }

@@ -11,28 +11,28 @@ struct nss_bjac_s {
   uint64_t serial = 0;         // unique per handle (matrices planned around its blocks remember it: nss_csr_s::jb_serial)
   int32_t bs = 0, nblocks = 0;
   int64_t n = 0;
-  int32_t* idx = nullptr;      // [bs][nblocks], -1 = padding
-  int32_t* run = nullptr;      // [nblocks]: run words (bjac_pack_run), when every block is a run of
-                               // consecutive dofs (4 bytes per block instead of 4 per dof)
-  double* inv = nullptr;       // [bs*bs][nblocks]
-  double* inv_sym = nullptr;   // [bs*(bs+1)/2][nblocks]: upper triangles, when every inverse block is
-                               // symmetric (A symmetric): the apply kernel then reads ~half the bytes
+  nss::DeviceBuffer<int32_t> idx;       // [bs][nblocks], -1 = padding
+  nss::DeviceBuffer<int32_t> run;       // [nblocks]: run words (bjac_pack_run), when every block is a run of
+                                        // consecutive dofs (4 bytes per block instead of 4 per dof)
+  nss::DeviceBuffer<double> inv;        // [bs*bs][nblocks]
+  nss::DeviceBuffer<double> inv_sym;    // [bs*(bs+1)/2][nblocks]: upper triangles, when every inverse block is
+                                        // symmetric (A symmetric): the apply kernel then reads ~half the bytes
   // Block codes (nss_bjac_code_blocks): with at most 256 distinct inverse blocks -- compared as the 64-bit patterns
   // of the entries the apply kernel reads -- the apply streams one byte per block and holds the distinct blocks in LDS
   // (bjac_apply_coded_kernel); inv / inv_sym stay for every other reader.  Same doubles, same products.
-  uint8_t* code = nullptr;     // [nblocks]: the block's position in dict
-  double* dict = nullptr;      // [n_codes][dict_doubles]: the distinct blocks, entries in the order of inv_sym / inv
+  nss::DeviceBuffer<uint8_t> code;      // [nblocks]: the block's position in dict
+  nss::DeviceBuffer<double> dict;       // [n_codes][dict_doubles]: the distinct blocks, entries ordered as in inv_sym / inv
   int32_t n_codes = 0, dict_doubles = 0;   // dict_doubles = bs (bs + 1) / 2 (inv_sym) or bs * bs (inv)
-  int32_t* covered = nullptr;  // dofs that belong to no block (count: n_uncovered)
+  nss::DeviceBuffer<int32_t> covered;   // dofs that belong to no block (count: n_uncovered)
   int32_t n_uncovered = 0;
   // multicolour Gauss-Seidel mode (nss_bjac_set_colors): blocks are stored colour-major
-  const nss_csr_s* gs_mat = nullptr;      // rows of A permuted block by block, colour-major
+  const nss_csr_s* gs_mat = nullptr;      // rows of A permuted block by block, colour-major (the caller's handle)
   std::vector<int32_t> color_ptr;         // ncolors + 1 block offsets (host)
   std::vector<int32_t> color_rowblk;      // ncolors + 1 row-block offsets into gs_mat's launch plan (host)
   std::vector<int32_t> color_row;         // ncolors + 1 row offsets of the colours in the permuted numbering (host)
-  int32_t* rowdof = nullptr;              // device: original dof of permuted row r
-  int32_t* ridx = nullptr;                // device [bs][nblocks]: permuted row of a block entry, -1 = padding
-  double* res = nullptr;                  // device: residual of the colour being swept (permuted rows)
+  nss::DeviceBuffer<int32_t> rowdof;      // device: original dof of permuted row r
+  nss::DeviceBuffer<int32_t> ridx;        // device [bs][nblocks]: permuted row of a block entry, -1 = padding
+  nss::DeviceBuffer<double> res;          // device: residual of the colour being swept (permuted rows)
   // Colour-major layout INSIDE the sweep (nss_bjac_set_colors_permuted): gs_mat is P A P^T -- rows and columns in the
   // colour-major block order; the dofs that belong to no block (`covered`, ascending) are the trailing columns
   // n_perm .. n_perm + n_uncovered - 1, gathered from y on every entry and never updated or scattered (with every dof
@@ -43,19 +43,20 @@ struct nss_bjac_s {
   // through LDS).  Everything a colour touches of its own is contiguous.
   bool gs_permuted = false;
   int32_t n_perm = 0;
-  uint8_t* gpos = nullptr;                // [n_perm] position of the row inside its block
-  uint8_t* glen = nullptr;                // [n_perm] rows of its block
-  double* ginv = nullptr;                 // [bs][n_perm]: ginv[k][r] = (A_bb^-1)(row r, k-th row of the block)
-  double *xt = nullptr, *yt = nullptr;    // [n_perm + max(1, n_uncovered)]
+  nss::DeviceBuffer<uint8_t> gpos;        // [n_perm] position of the row inside its block
+  nss::DeviceBuffer<uint8_t> glen;        // [n_perm] rows of its block
+  nss::DeviceBuffer<double> ginv;         // [bs][n_perm]: ginv[k][r] = (A_bb^-1)(row r, k-th row of the block)
+  nss::DeviceBuffer<double> xt, yt;       // [n_perm + max(1, n_uncovered)]
   // Statically condensed form whose MypreA sweeps over the Schur complement S (nss_bjac_set_condensed): the operators
   // the fused BPCG loop folds into the sweep's entry, middle and exit (csrc/bpcg2.hip: the fused condensed forms).
   // cond_key_* = the operators they were made from (the loop uses them only for exactly those); cond_HTp = P H^T (the
   // rows of H^T at the block dofs in the colour-major numbering, original columns); cond_Hp = the rows of H at the
   // dofs outside every block (in `covered` order) with columns renamed into the permuted numbering (n_perm +
-  // max(1, n_uncovered) columns); cond_dinner[i] = the diagonal of A_ii^-1 at covered[i].
+  // max(1, n_uncovered) columns); cond_dinner[i] = the diagonal of A_ii^-1 at covered[i].  The six matrices are the
+  // caller's handles; only cond_dinner is this handle's memory.
   const nss_csr_s *cond_key_HT = nullptr, *cond_key_H = nullptr, *cond_key_inner = nullptr, *cond_key_S = nullptr;
   const nss_csr_s *cond_HTp = nullptr, *cond_Hp = nullptr;
-  double* cond_dinner = nullptr;
+  nss::DeviceBuffer<double> cond_dinner;
 };
 
 namespace nss {

@@ -10,6 +10,7 @@
 
 #include "code_keys.h"
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -281,51 +282,35 @@ static bool code_blocks(nss_bjac_s& j, hipStream_t st) {
   const double* src = j.inv_sym ? j.inv_sym : j.inv;
   const int d = j.inv_sym ? j.bs * (j.bs + 1) / 2 : j.bs * j.bs;
   const int32_t nb = j.nblocks;
-  double* hash = nullptr;
-  uint8_t* code = nullptr;
-  int32_t* rep = nullptr;                                  // kDictSize first blocks, then the verdict of the comparison
-  double* dict = nullptr;
-  bool ok = false;
-  int n_codes = 0;
-  try {
-    NSS_HIP(hipMalloc(&hash, sizeof(double) * size_t(nb)));
-    hipLaunchKernelGGL(bjac_hash_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, d, src, hash);
-    NSS_CHECK_LAUNCH();
-    std::vector<unsigned long long> keys;                  // ascending hashes: the codes do not depend on scheduling
-    if (collect_patterns(nb, hash, keys, st) && block_dictionary_fits(keys.size(), d, size_t(kBjacDictBytes))) {
-      n_codes = int(keys.size());
-      NSS_HIP(hipMalloc(&code, size_t(nb)));
-      NSS_HIP(hipMalloc(&rep, sizeof(int32_t) * (kDictSize + 1)));
-      NSS_HIP(hipMalloc(&dict, sizeof(double) * size_t(n_codes) * d));
-      assign_pattern_codes(nb, hash, keys, code, st);
-      NSS_HIP(hipMemsetAsync(rep, 0x7f, sizeof(int32_t) * kDictSize, st));
-      NSS_HIP(hipMemsetAsync(rep + kDictSize, 0, sizeof(int32_t), st));
-      hipLaunchKernelGGL(bjac_rep_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, code, rep);
-      NSS_CHECK_LAUNCH();
-      hipLaunchKernelGGL(bjac_dict_kernel, dim3((n_codes * d + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nb, d, n_codes,
-                         src, rep, dict);
-      NSS_CHECK_LAUNCH();
-      hipLaunchKernelGGL(bjac_verify_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, d, src, code, dict,
-                         rep + kDictSize);
-      NSS_CHECK_LAUNCH();
-      int32_t differ = 1;
-      NSS_HIP(hipMemcpyAsync(&differ, rep + kDictSize, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      NSS_HIP(hipStreamSynchronize(st));
-      ok = differ == 0;
-    }
-  } catch (...) {
-    for (void* p : {(void*)hash, (void*)code, (void*)rep, (void*)dict}) (void)hipFree(p);
-    throw;
-  }
-  (void)hipFree(hash);
-  (void)hipFree(rep);
-  if (!ok) {
-    (void)hipFree(code);
-    (void)hipFree(dict);
-    return false;
-  }
-  j.code = code;
-  j.dict = dict;
+  DeviceBuffer<double> hash, dict;
+  DeviceBuffer<uint8_t> code;
+  DeviceBuffer<int32_t> rep;                               // kDictSize first blocks, then the verdict of the comparison
+  hash.alloc(size_t(nb));
+  hipLaunchKernelGGL(bjac_hash_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, d, src, hash);
+  NSS_CHECK_LAUNCH();
+  std::vector<unsigned long long> keys;                    // ascending hashes: the codes do not depend on scheduling
+  if (!collect_patterns(nb, hash, keys, st) || !block_dictionary_fits(keys.size(), d, size_t(kBjacDictBytes))) return false;
+  const int n_codes = int(keys.size());
+  code.alloc(size_t(nb));
+  rep.alloc(kDictSize + 1);
+  dict.alloc(size_t(n_codes) * d);
+  assign_pattern_codes(nb, hash, keys, code, st);
+  NSS_HIP(hipMemsetAsync(rep, 0x7f, sizeof(int32_t) * kDictSize, st));
+  NSS_HIP(hipMemsetAsync(rep + kDictSize, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(bjac_rep_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, code, rep);
+  NSS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(bjac_dict_kernel, dim3((n_codes * d + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nb, d, n_codes, src,
+                     rep, dict);
+  NSS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(bjac_verify_kernel, dim3(stream_grid(nb, kBlock)), dim3(kBlock), 0, st, nb, d, src, code, dict,
+                     rep + kDictSize);
+  NSS_CHECK_LAUNCH();
+  int32_t differ = 1;
+  NSS_HIP(hipMemcpyAsync(&differ, rep + kDictSize, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipStreamSynchronize(st));
+  if (differ != 0) return false;
+  j.code = std::move(code);
+  j.dict = std::move(dict);
   j.n_codes = n_codes;
   j.dict_doubles = d;
   return true;
@@ -672,100 +657,70 @@ int nss_bjac_create(nss_csr_t a, int32_t bs, int32_t nblocks, const int32_t* h_i
     std::vector<int32_t> uncovered;
     for (int32_t d = 0; d < a->m; ++d)
       if (!seen[d]) uncovered.push_back(d);
-    nss_bjac_s* j = new nss_bjac_s;
-    int32_t* singular = nullptr;
-    try {
-      static uint64_t next_serial = 0;
-      j->serial = ++next_serial;
-      j->bs = bs;
-      j->nblocks = nblocks;
-      j->n = a->m;
-      j->n_uncovered = int32_t(uncovered.size());
-      NSS_HIP(hipMalloc(&j->idx, sizeof(int32_t) * size_t(bs) * nblocks));
-      NSS_HIP(hipMalloc(&j->inv, sizeof(double) * size_t(bs) * bs * nblocks));
-      NSS_HIP(hipMemcpy(j->idx, h_idx, sizeof(int32_t) * size_t(bs) * nblocks, hipMemcpyHostToDevice));
-      if (!uncovered.empty()) {
-        NSS_HIP(hipMalloc(&j->covered, sizeof(int32_t) * uncovered.size()));
-        NSS_HIP(hipMemcpy(j->covered, uncovered.data(), sizeof(int32_t) * uncovered.size(), hipMemcpyHostToDevice));
-      }
-      {   // blocks that are runs of consecutive dofs (padding last): one packed word per block
-        std::vector<int32_t> runs{};
-        runs.resize(size_t(nblocks));
-        bool all_runs = a->m < (1 << 26);
-        for (int32_t b = 0; b < nblocks && all_runs; ++b) {
-          const int32_t first = h_idx[b];
-          int len = 0;
-          while (len < bs && h_idx[size_t(len) * nblocks + b] >= 0) ++len;
-          all_runs = first >= 0 && len > 0;
-          for (int c = 0; c < bs && all_runs; ++c) {
-            const int32_t d = h_idx[size_t(c) * nblocks + b];
-            all_runs = c < len ? d == first + c : d < 0;
-          }
-          runs[b] = bjac_pack_run(first, len);
-        }
-        if (all_runs) {
-          NSS_HIP(hipMalloc(&j->run, sizeof(int32_t) * size_t(nblocks)));
-          NSS_HIP(hipMemcpy(j->run, runs.data(), sizeof(int32_t) * size_t(nblocks), hipMemcpyHostToDevice));
-        }
-      }
-      NSS_HIP(hipMalloc(&singular, sizeof(int32_t)));
-      NSS_HIP(hipMemset(singular, 0, sizeof(int32_t)));
-      hipLaunchKernelGGL(bjac_setup_kernel, dim3((nblocks + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, bs,
-                         nblocks, j->idx, a->rowptr, a->col, a->val, j->inv, singular);
-      NSS_CHECK_LAUNCH();
-      int32_t nsing = 0;
-      NSS_HIP(hipMemcpy(&nsing, singular, sizeof(int32_t), hipMemcpyDeviceToHost));
-      (void)hipFree(singular);
-      singular = nullptr;
-      if (nsing > 0) throw Error("bjac_create: " + std::to_string(nsing) + " singular diagonal block(s)");
-#if NSS_BJAC_SYM
-      if (bs > 1) {   // symmetric inverses (A symmetric): keep the packed upper triangles for the apply kernel
-        NSS_HIP(hipMalloc(&singular, sizeof(int32_t)));
-        NSS_HIP(hipMemset(singular, 0, sizeof(int32_t)));
-        NSS_HIP(hipMalloc(&j->inv_sym, sizeof(double) * size_t(bs) * (bs + 1) / 2 * nblocks));
-        hipLaunchKernelGGL(bjac_pack_sym_kernel, dim3((nblocks + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, bs,
-                           nblocks, j->inv, j->inv_sym, singular);
-        NSS_CHECK_LAUNCH();
-        int32_t nasym = 0;
-        NSS_HIP(hipMemcpy(&nasym, singular, sizeof(int32_t), hipMemcpyDeviceToHost));
-        (void)hipFree(singular);
-        singular = nullptr;
-        if (nasym > 0) {
-          (void)hipFree(j->inv_sym);
-          j->inv_sym = nullptr;
-        }
-      }
-#endif
-    } catch (...) {
-      (void)hipFree(singular);
-      nss_bjac_destroy(j);
-      throw;
+    std::unique_ptr<nss_bjac_s> j(new nss_bjac_s);
+    DeviceBuffer<int32_t> singular;
+    static uint64_t next_serial = 0;
+    j->serial = ++next_serial;
+    j->bs = bs;
+    j->nblocks = nblocks;
+    j->n = a->m;
+    j->n_uncovered = int32_t(uncovered.size());
+    j->idx.alloc(size_t(bs) * nblocks);
+    j->inv.alloc(size_t(bs) * bs * nblocks);
+    NSS_HIP(hipMemcpy(j->idx, h_idx, sizeof(int32_t) * size_t(bs) * nblocks, hipMemcpyHostToDevice));
+    if (!uncovered.empty()) {
+      j->covered.alloc(uncovered.size());
+      NSS_HIP(hipMemcpy(j->covered, uncovered.data(), sizeof(int32_t) * uncovered.size(), hipMemcpyHostToDevice));
     }
-    *out = j;
+    {   // blocks that are runs of consecutive dofs (padding last): one packed word per block
+      std::vector<int32_t> runs{};
+      runs.resize(size_t(nblocks));
+      bool all_runs = a->m < (1 << 26);
+      for (int32_t b = 0; b < nblocks && all_runs; ++b) {
+        const int32_t first = h_idx[b];
+        int len = 0;
+        while (len < bs && h_idx[size_t(len) * nblocks + b] >= 0) ++len;
+        all_runs = first >= 0 && len > 0;
+        for (int c = 0; c < bs && all_runs; ++c) {
+          const int32_t d = h_idx[size_t(c) * nblocks + b];
+          all_runs = c < len ? d == first + c : d < 0;
+        }
+        runs[b] = bjac_pack_run(first, len);
+      }
+      if (all_runs) {
+        j->run.alloc(size_t(nblocks));
+        NSS_HIP(hipMemcpy(j->run, runs.data(), sizeof(int32_t) * size_t(nblocks), hipMemcpyHostToDevice));
+      }
+    }
+    singular.alloc(1);
+    NSS_HIP(hipMemset(singular, 0, sizeof(int32_t)));
+    hipLaunchKernelGGL(bjac_setup_kernel, dim3((nblocks + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, bs,
+                       nblocks, j->idx, a->rowptr, a->col, a->val, j->inv, singular);
+    NSS_CHECK_LAUNCH();
+    int32_t nsing = 0;
+    NSS_HIP(hipMemcpy(&nsing, singular, sizeof(int32_t), hipMemcpyDeviceToHost));
+    singular.reset();
+    if (nsing > 0) throw Error("bjac_create: " + std::to_string(nsing) + " singular diagonal block(s)");
+#if NSS_BJAC_SYM
+    if (bs > 1) {   // symmetric inverses (A symmetric): keep the packed upper triangles for the apply kernel
+      singular.alloc(1);
+      NSS_HIP(hipMemset(singular, 0, sizeof(int32_t)));
+      j->inv_sym.alloc(size_t(bs) * (bs + 1) / 2 * nblocks);
+      hipLaunchKernelGGL(bjac_pack_sym_kernel, dim3((nblocks + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, bs,
+                         nblocks, j->inv, j->inv_sym, singular);
+      NSS_CHECK_LAUNCH();
+      int32_t nasym = 0;
+      NSS_HIP(hipMemcpy(&nasym, singular, sizeof(int32_t), hipMemcpyDeviceToHost));
+      singular.reset();
+      if (nasym > 0) j->inv_sym.reset();
+    }
+#endif
+    *out = j.release();
   });
 }
 
 int nss_bjac_destroy(nss_bjac_t j) {
-  return guarded([&] {
-    if (!j) return;
-    (void)hipFree(j->idx);
-    (void)hipFree(j->inv);
-    (void)hipFree(j->inv_sym);
-    (void)hipFree(j->run);
-    (void)hipFree(j->code);
-    (void)hipFree(j->dict);
-    (void)hipFree(j->covered);
-    (void)hipFree(j->rowdof);
-    (void)hipFree(j->ridx);
-    (void)hipFree(j->res);
-    (void)hipFree(j->gpos);
-    (void)hipFree(j->glen);
-    (void)hipFree(j->ginv);
-    (void)hipFree(j->xt);
-    (void)hipFree(j->yt);
-    (void)hipFree(j->cond_dinner);
-    delete j;
-  });
+  return guarded([&] { delete j; });
 }
 
 int nss_bjac_apply_f64(nss_bjac_t j, double alpha, const double* x, double beta, double* y, nss_stream_t stream) {
@@ -814,14 +769,9 @@ static void set_colors_common(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors, c
                   "bjac_set_colors: a row block of the permuted matrix spans two colours (create it with cuts)");
       crb[c] = int32_t(pos);
     }
-    (void)hipFree(j->rowdof);
-    (void)hipFree(j->ridx);
-    (void)hipFree(j->res);
-    j->rowdof = j->ridx = nullptr;
-    j->res = nullptr;
-    NSS_HIP(hipMalloc(&j->rowdof, sizeof(int32_t) * std::max<size_t>(1, a_perm->m)));
-    NSS_HIP(hipMalloc(&j->ridx, sizeof(int32_t) * size_t(j->bs) * j->nblocks));
-    NSS_HIP(hipMalloc(&j->res, sizeof(double) * std::max<size_t>(1, a_perm->m)));
+    j->rowdof.alloc(std::max<size_t>(1, a_perm->m));      // (alloc frees what the previous numbering left)
+    j->ridx.alloc(size_t(j->bs) * j->nblocks);
+    j->res.alloc(std::max<size_t>(1, a_perm->m));
     NSS_HIP(hipMemcpy(j->rowdof, h_rowdof, sizeof(int32_t) * a_perm->m, hipMemcpyHostToDevice));
     NSS_HIP(hipMemcpy(j->ridx, h_ridx, sizeof(int32_t) * size_t(j->bs) * j->nblocks, hipMemcpyHostToDevice));
     j->gs_mat = a_perm;
@@ -869,16 +819,13 @@ int nss_bjac_set_colors_permuted(nss_bjac_t j, nss_csr_t a_perm, int32_t ncolors
       NSS_REQUIRE(rb[k + 1] - rb[k] <= kGsRows, "bjac_set_colors_permuted: a row block of the permuted matrix has more than 256 rows");
       NSS_REQUIRE(starts[size_t(rb[k])] == 1, "bjac_set_colors_permuted: a row block of the permuted matrix splits a Gauss-Seidel block");
     }
-    for (void* p : {(void*)j->gpos, (void*)j->glen, (void*)j->ginv, (void*)j->xt, (void*)j->yt}) (void)hipFree(p);
-    j->gpos = j->glen = nullptr;
-    j->ginv = j->xt = j->yt = nullptr;
     j->gs_permuted = false;
     j->cond_HTp = j->cond_Hp = nullptr;                    // a new numbering drops the condensed operators
-    NSS_HIP(hipMalloc(&j->gpos, std::max<size_t>(1, n_perm)));
-    NSS_HIP(hipMalloc(&j->glen, std::max<size_t>(1, n_perm)));
-    NSS_HIP(hipMalloc(&j->ginv, sizeof(double) * size_t(j->bs) * std::max<size_t>(1, n_perm)));
-    NSS_HIP(hipMalloc(&j->xt, sizeof(double) * n_ext));
-    NSS_HIP(hipMalloc(&j->yt, sizeof(double) * n_ext));
+    j->gpos.alloc(std::max<size_t>(1, n_perm));
+    j->glen.alloc(std::max<size_t>(1, n_perm));
+    j->ginv.alloc(size_t(j->bs) * std::max<size_t>(1, n_perm));
+    j->xt.alloc(n_ext);
+    j->yt.alloc(n_ext);
     NSS_HIP(hipMemset(j->xt, 0, sizeof(double) * n_ext));
     NSS_HIP(hipMemset(j->yt, 0, sizeof(double) * n_ext));
     hipLaunchKernelGGL(gs_pack_inverse_kernel, dim3((j->nblocks + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, j->bs,
@@ -894,8 +841,7 @@ int nss_bjac_set_condensed(nss_bjac_t j, nss_csr_t HT, nss_csr_t H, nss_csr_t in
                            nss_csr_t H_perm, const double* h_inner_diag) {
   return guarded([&] {
     NSS_REQUIRE(j != nullptr, "bjac_set_condensed: NULL handle");
-    (void)hipFree(j->cond_dinner);
-    j->cond_dinner = nullptr;
+    j->cond_dinner.reset();
     j->cond_key_HT = j->cond_key_H = j->cond_key_inner = j->cond_key_S = nullptr;
     j->cond_HTp = j->cond_Hp = nullptr;
     if (!HT_perm) return;                                    // detach
@@ -907,7 +853,7 @@ int nss_bjac_set_condensed(nss_bjac_t j, nss_csr_t HT, nss_csr_t H, nss_csr_t in
     NSS_REQUIRE(H_perm->m == j->n_uncovered && int64_t(H_perm->n) == int64_t(j->n_perm) + std::max(1, j->n_uncovered),
                 "bjac_set_condensed: the rows of H outside the blocks must be n_uncovered x (n_perm + max(1, n_uncovered))");
     if (j->n_uncovered > 0) {
-      NSS_HIP(hipMalloc(&j->cond_dinner, sizeof(double) * size_t(j->n_uncovered)));
+      j->cond_dinner.alloc(size_t(j->n_uncovered));
       NSS_HIP(hipMemcpy(j->cond_dinner, h_inner_diag, sizeof(double) * size_t(j->n_uncovered), hipMemcpyHostToDevice));
     }
     j->cond_key_HT = HT;

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <memory>
 #include <vector>
 
 namespace nss {
@@ -316,23 +317,16 @@ __global__ __launch_bounds__(kBlock) void col_group_pack_kernel(int64_t ngroups,
 #endif
 
 // one 16-bit index per group of gb entries: `*stream` is replaced by its packed form
-static void pack_groups(uint16_t** stream, int64_t nnz, int gb, hipStream_t st) {
-  if (!*stream) return;
+static void pack_groups(DeviceBuffer<uint16_t>& stream, int64_t nnz, int gb, hipStream_t st) {
+  if (!stream) return;
   const int64_t ngroups = nnz / gb;
-  uint16_t* packed = nullptr;
-  try {
-    NSS_HIP(hipMalloc(&packed, sizeof(uint16_t) * (size_t(ngroups) + 8)));
-    NSS_HIP(hipMemsetAsync(packed, 0, sizeof(uint16_t) * (size_t(ngroups) + 8), st));
-    hipLaunchKernelGGL(col_group_pack_kernel, dim3(stream_grid(ngroups, kBlock * 4)), dim3(kBlock), 0, st, ngroups, gb,
-                       *stream, packed);
-    NSS_CHECK_LAUNCH();
-    NSS_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipFree(packed);
-    throw;
-  }
-  (void)hipFree(*stream);
-  *stream = packed;
+  DeviceBuffer<uint16_t> packed(size_t(ngroups) + 8);
+  NSS_HIP(hipMemsetAsync(packed, 0, sizeof(uint16_t) * (size_t(ngroups) + 8), st));
+  hipLaunchKernelGGL(col_group_pack_kernel, dim3(stream_grid(ngroups, kBlock * 4)), dim3(kBlock), 0, st, ngroups, gb,
+                     stream, packed);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipStreamSynchronize(st));
+  stream = std::move(packed);
 }
 
 // Largest gb in 16 .. 2 for which the matrix is made of aligned runs of gb consecutive columns: keep one
@@ -356,29 +350,22 @@ static void group_columns(nss_csr_s& A, hipStream_t st) {
       if (p % gb != 0 && h_col[size_t(p)] != h_col[size_t(p) - 1] + 1) return false;
     return true;
   };
-  int32_t* bad = nullptr;
-  try {
-    NSS_HIP(hipMalloc(&bad, sizeof(int32_t)));
-    for (int gb = 16; gb >= 2; --gb) {
-      if (A.nnz % gb != 0 || !plausible(gb)) continue;
-      NSS_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-      hipLaunchKernelGGL(col_group_check_kernel, dim3(stream_grid(A.nnz, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.nnz,
-                         A.rowptr, A.col, gb, bad);
-      NSS_CHECK_LAUNCH();
-      int32_t h_bad = 1;
-      NSS_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      NSS_HIP(hipStreamSynchronize(st));
-      if (h_bad != 0) continue;
-      pack_groups(&A.col16, A.nnz, gb, st);
-      pack_groups(&A.pos16, A.nnz, gb, st);
-      A.gb = gb;
-      break;
-    }
-  } catch (...) {
-    (void)hipFree(bad);
-    throw;
+  DeviceBuffer<int32_t> bad(1);
+  for (int gb = 16; gb >= 2; --gb) {
+    if (A.nnz % gb != 0 || !plausible(gb)) continue;
+    NSS_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(col_group_check_kernel, dim3(stream_grid(A.nnz, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.nnz,
+                       A.rowptr, A.col, gb, bad);
+    NSS_CHECK_LAUNCH();
+    int32_t h_bad = 1;
+    NSS_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    NSS_HIP(hipStreamSynchronize(st));
+    if (h_bad != 0) continue;
+    pack_groups(A.col16, A.nnz, gb, st);
+    pack_groups(A.pos16, A.nnz, gb, st);
+    A.gb = gb;
+    break;
   }
-  (void)hipFree(bad);
 #else
   (void)A;
   (void)st;
@@ -396,38 +383,26 @@ static void group_columns(nss_csr_s& A, hipStream_t st) {
 static void stage_columns(nss_csr_s& A, hipStream_t st) {
 #if NSS_STAGE_X
   if (A.nnz < int64_t(NSS_STAGE_MIN_MEAN) * A.m) return;
-  int32_t* desc = nullptr;
-  int32_t* nbad = nullptr;            // [0] row blocks that do not fit, [1] largest number of staged columns of a block
-  uint16_t* p16 = nullptr;
+  DeviceBuffer<int32_t> desc;
+  DeviceBuffer<int32_t> nbad;         // [0] row blocks that do not fit, [1] largest number of staged columns of a block
+  DeviceBuffer<uint16_t> p16;
   A.pair_ok = false;
-  try {
-    NSS_HIP(hipMalloc(&desc, sizeof(int32_t) * size_t(A.nblk) * kSegWords));
-    NSS_HIP(hipMalloc(&nbad, 2 * sizeof(int32_t)));
-    NSS_HIP(hipMalloc(&p16, sizeof(uint16_t) * (size_t(A.nnz) + 8)));
-    NSS_HIP(hipMemsetAsync(nbad, 0, 2 * sizeof(int32_t), st));
-    NSS_HIP(hipMemsetAsync(p16, 0, sizeof(uint16_t) * (size_t(A.nnz) + 8), st));
-    hipLaunchKernelGGL(seg_build_kernel, dim3(A.nblk), dim3(kBlock), 0, st, A.nblk, A.rowblk, A.rowptr, A.col, A.chunk,
-                       A.n, desc, p16, nbad, nbad + 1);
-    NSS_CHECK_LAUNCH();
-    int32_t h_bad[2] = {0, 0};
-    NSS_HIP(hipMemcpyAsync(h_bad, nbad, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    NSS_HIP(hipStreamSynchronize(st));
-    if (h_bad[0] == 0) {              // every row block fits (the staged kernels have no per-block fallback)
-      A.pos16 = p16;
-      A.blkseg = desc;
-      A.pair_ok = h_bad[1] <= A.chunk / 2;
-      p16 = nullptr;
-      desc = nullptr;
-    }
-  } catch (...) {
-    (void)hipFree(desc);
-    (void)hipFree(nbad);
-    (void)hipFree(p16);
-    throw;
+  desc.alloc(size_t(A.nblk) * kSegWords);
+  nbad.alloc(2);
+  p16.alloc(size_t(A.nnz) + 8);
+  NSS_HIP(hipMemsetAsync(nbad, 0, 2 * sizeof(int32_t), st));
+  NSS_HIP(hipMemsetAsync(p16, 0, sizeof(uint16_t) * (size_t(A.nnz) + 8), st));
+  hipLaunchKernelGGL(seg_build_kernel, dim3(A.nblk), dim3(kBlock), 0, st, A.nblk, A.rowblk, A.rowptr, A.col, A.chunk,
+                     A.n, desc, p16, nbad, nbad + 1);
+  NSS_CHECK_LAUNCH();
+  int32_t h_bad[2] = {0, 0};
+  NSS_HIP(hipMemcpyAsync(h_bad, nbad, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipStreamSynchronize(st));
+  if (h_bad[0] == 0) {                // every row block fits (the staged kernels have no per-block fallback)
+    A.pos16 = std::move(p16);
+    A.blkseg = std::move(desc);
+    A.pair_ok = h_bad[1] <= A.chunk / 2;
   }
-  (void)hipFree(desc);
-  (void)hipFree(nbad);
-  (void)hipFree(p16);
 #else
   (void)A;
   (void)st;
@@ -561,55 +536,34 @@ static void build_dispatch(nss_csr_s& A, hipStream_t st) {
       }
     }
   }
-  int32_t* dev = nullptr;
-  NSS_HIP(hipMalloc(&dev, sizeof(int32_t) * table.size()));
-  try {
-    NSS_HIP(hipMemcpy(dev, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
-  } catch (...) {
-    (void)hipFree(dev);
-    throw;
-  }
-  A.blkdisp = dev;
+  DeviceBuffer<int32_t> dev(table.size());
+  NSS_HIP(hipMemcpy(dev, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
+  A.blkdisp = std::move(dev);
   A.disp_period = period;
   A.disp_planes = planes;
 }
 
 // 16-bit window form: A.col16 / A.blkbase when every row block fits kWindows windows.
 static void window_columns(nss_csr_s& A, hipStream_t st) {
-  int32_t* base = nullptr;
-  int32_t* wide = nullptr;
-  uint16_t* c16 = nullptr;
-  try {
-    NSS_HIP(hipMalloc(&base, sizeof(int32_t) * size_t(A.nblk) * kWindows));
-    NSS_HIP(hipMalloc(&wide, sizeof(int32_t)));
-    NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(col_windows_kernel, dim3((A.nblk + kBlock - 1) / kBlock), dim3(kBlock), 0, st, A.nblk, A.rowblk,
-                       A.rowptr, A.col, A.chunk, base, wide);
-    NSS_CHECK_LAUNCH();
-    int32_t h_wide = 0;
-    NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    NSS_HIP(hipStreamSynchronize(st));
-    if (h_wide == 0) {
-      NSS_HIP(hipMalloc(&c16, sizeof(uint16_t) * (size_t(A.nnz) + 8)));
-      NSS_HIP(hipMemsetAsync(c16, 0, sizeof(uint16_t) * (size_t(A.nnz) + 8), st));
-      hipLaunchKernelGGL(col_pack16_kernel, dim3(A.nblk), dim3(kBlock), 0, st, A.nblk, A.rowblk, A.rowptr, A.col,
-                         A.chunk, base, c16);
-      NSS_CHECK_LAUNCH();
-      NSS_HIP(hipStreamSynchronize(st));
-      A.col16 = c16;
-      A.blkbase = base;
-      c16 = nullptr;
-      base = nullptr;
-    }
-  } catch (...) {
-    (void)hipFree(base);
-    (void)hipFree(wide);
-    (void)hipFree(c16);
-    throw;
-  }
-  (void)hipFree(base);
-  (void)hipFree(wide);
-  (void)hipFree(c16);
+  DeviceBuffer<int32_t> base, wide;
+  base.alloc(size_t(A.nblk) * kWindows);
+  wide.alloc(1);
+  NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(col_windows_kernel, dim3((A.nblk + kBlock - 1) / kBlock), dim3(kBlock), 0, st, A.nblk, A.rowblk,
+                     A.rowptr, A.col, A.chunk, base, wide);
+  NSS_CHECK_LAUNCH();
+  int32_t h_wide = 0;
+  NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipStreamSynchronize(st));
+  if (h_wide != 0) return;
+  DeviceBuffer<uint16_t> c16(size_t(A.nnz) + 8);
+  NSS_HIP(hipMemsetAsync(c16, 0, sizeof(uint16_t) * (size_t(A.nnz) + 8), st));
+  hipLaunchKernelGGL(col_pack16_kernel, dim3(A.nblk), dim3(kBlock), 0, st, A.nblk, A.rowblk, A.rowptr, A.col, A.chunk,
+                     base, c16);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipStreamSynchronize(st));
+  A.col16 = std::move(c16);
+  A.blkbase = std::move(base);
 }
 
 // fixed-width copy: kDirectWidth (column, value) pairs per row, column -1 where the row is shorter
@@ -699,10 +653,9 @@ __global__ __launch_bounds__(kBlock) void ell_code_kernel(int32_t m, const int32
 
 // ell_code of a coded matrix that holds the fixed-width copy (built wherever that copy is built)
 static void build_ell_code(nss_csr_s& A, hipStream_t st) {
-  (void)hipFree(A.ell_code);
-  A.ell_code = nullptr;
+  A.ell_code.reset();
   if (!A.val8 || !A.ell_col || A.m == 0) return;
-  NSS_HIP(hipMalloc(&A.ell_code, sizeof(uint16_t) * size_t(A.m)));
+  A.ell_code.alloc(size_t(A.m));
   hipLaunchKernelGGL(ell_code_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.val8,
                      A.ell_code);
   NSS_CHECK_LAUNCH();
@@ -741,10 +694,8 @@ __global__ __launch_bounds__(kBlock) void slot_build_kernel(int32_t m, const int
 }
 
 static void drop_row_slots(nss_csr_s& A) {
-  (void)hipFree(A.slot_pos);
-  (void)hipFree(A.slot_code);
-  A.slot_pos = nullptr;
-  A.slot_code = nullptr;
+  A.slot_pos.reset();
+  A.slot_code.reset();
   A.slot_gen = -1;
 }
 
@@ -760,34 +711,22 @@ static bool build_row_slots(nss_csr_s& A, hipStream_t st) {
   NSS_HIP(hipDeviceSynchronize());                       // (a stale copy goes: no kernel may still read it)
   drop_row_slots(A);
   if (!row_slots_candidate(A)) return false;
-  uint16_t* spos = nullptr;
-  uint8_t* scode = nullptr;
-  int32_t* wide = nullptr;
+  DeviceBuffer<uint16_t> spos;
+  DeviceBuffer<uint8_t> scode;
+  DeviceBuffer<int32_t> wide;
   int32_t h_wide = 1;
-  try {
-    NSS_HIP(hipMalloc(&spos, sizeof(uint16_t) * kSlotWidth * size_t(A.m)));
-    NSS_HIP(hipMalloc(&scode, size_t(kSlotWidth) * size_t(A.m)));
-    NSS_HIP(hipMalloc(&wide, sizeof(int32_t)));
-    NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(slot_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.pos16,
-                       A.val8, spos, scode, wide);
-    NSS_CHECK_LAUNCH();
-    NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    NSS_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipFree(spos);
-    (void)hipFree(scode);
-    (void)hipFree(wide);
-    throw;
-  }
-  (void)hipFree(wide);
-  if (h_wide != 0) {                                     // a row of more than kSlotWidth entries
-    (void)hipFree(spos);
-    (void)hipFree(scode);
-    return false;
-  }
-  A.slot_pos = spos;
-  A.slot_code = scode;
+  spos.alloc(kSlotWidth * size_t(A.m));
+  scode.alloc(size_t(kSlotWidth) * size_t(A.m));
+  wide.alloc(1);
+  NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(slot_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.pos16,
+                     A.val8, spos, scode, wide);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipStreamSynchronize(st));
+  if (h_wide != 0) return false;                         // a row of more than kSlotWidth entries
+  A.slot_pos = std::move(spos);
+  A.slot_code = std::move(scode);
   A.slot_gen = A.plan_gen;
   return A.row_slots();
 }
@@ -797,12 +736,9 @@ static void drop_value_codes(nss_csr_s& A) {
   if (!A.val8) return;
   NSS_HIP(hipDeviceSynchronize());                       // no kernel may still read the arrays that go away
   drop_row_slots(A);                                     // (a copy of the codes)
-  (void)hipFree(A.val8);
-  (void)hipFree(A.dict);
-  (void)hipFree(A.ell_code);
-  A.val8 = nullptr;
-  A.dict = nullptr;
-  A.ell_code = nullptr;
+  A.val8.reset();
+  A.dict.reset();
+  A.ell_code.reset();
   A.dict_count = 0;
 }
 
@@ -811,46 +747,31 @@ static void drop_value_codes(nss_csr_s& A) {
 bool collect_patterns(int64_t n, const double* val, std::vector<unsigned long long>& keys, hipStream_t st) {
   keys.clear();
   if (n <= 0) return false;
-  unsigned long long* table = nullptr;
-  int32_t* state = nullptr;
+  DeviceBuffer<unsigned long long> table;
+  DeviceBuffer<int32_t> state;
   int32_t h_state[4] = {0, 1, 0, 0};
   std::vector<unsigned long long> h_table(kCodeSlots);
-  try {
-    NSS_HIP(hipMalloc(&table, sizeof(unsigned long long) * kCodeSlots));
-    NSS_HIP(hipMalloc(&state, sizeof(int32_t) * 4));
-    NSS_HIP(hipMemsetAsync(table, 0xff, sizeof(unsigned long long) * kCodeSlots, st));
-    NSS_HIP(hipMemsetAsync(state, 0, sizeof(int32_t) * 4, st));
-    hipLaunchKernelGGL(code_collect_kernel, dim3(stream_grid(n, kBlock * 8)), dim3(kBlock), 0, st, n, val, table, state);
-    NSS_CHECK_LAUNCH();
-    NSS_HIP(hipMemcpyAsync(h_state, state, sizeof h_state, hipMemcpyDeviceToHost, st));
-    NSS_HIP(hipMemcpyAsync(h_table.data(), table, sizeof(unsigned long long) * kCodeSlots, hipMemcpyDeviceToHost, st));
-    NSS_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipFree(table);
-    (void)hipFree(state);
-    throw;
-  }
-  (void)hipFree(table);
-  (void)hipFree(state);
+  table.alloc(kCodeSlots);
+  state.alloc(4);
+  NSS_HIP(hipMemsetAsync(table, 0xff, sizeof(unsigned long long) * kCodeSlots, st));
+  NSS_HIP(hipMemsetAsync(state, 0, sizeof(int32_t) * 4, st));
+  hipLaunchKernelGGL(code_collect_kernel, dim3(stream_grid(n, kBlock * 8)), dim3(kBlock), 0, st, n, val, table, state);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipMemcpyAsync(h_state, state, sizeof h_state, hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipMemcpyAsync(h_table.data(), table, sizeof(unsigned long long) * kCodeSlots, hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipStreamSynchronize(st));
   return code_keys_from_table(h_table.data(), kCodeSlots, h_state, size_t(kDictSize), keys);
 }
 
 // codes[i] = position of val[i]'s pattern in `keys` (from collect_patterns).  Synchronises the stream.
 void assign_pattern_codes(int64_t n, const double* val, const std::vector<unsigned long long>& keys, uint8_t* codes,
                           hipStream_t st) {
-  unsigned long long* d_keys = nullptr;
-  try {
-    NSS_HIP(hipMalloc(&d_keys, sizeof(unsigned long long) * kDictSize));
-    NSS_HIP(hipMemcpyAsync(d_keys, keys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(code_assign_kernel, dim3(stream_grid(n, kBlock * 8)), dim3(kBlock), 0, st, n, val, d_keys,
-                       int(keys.size()), codes);
-    NSS_CHECK_LAUNCH();
-    NSS_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipFree(d_keys);
-    throw;
-  }
-  (void)hipFree(d_keys);
+  DeviceBuffer<unsigned long long> d_keys(kDictSize);
+  NSS_HIP(hipMemcpyAsync(d_keys, keys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(code_assign_kernel, dim3(stream_grid(n, kBlock * 8)), dim3(kBlock), 0, st, n, val, d_keys,
+                     int(keys.size()), codes);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipStreamSynchronize(st));
 }
 
 static bool code_values(nss_csr_s& A, hipStream_t st) {
@@ -859,23 +780,17 @@ static bool code_values(nss_csr_s& A, hipStream_t st) {
   if (A.gb > 1) return false;                            // grouped column stream: its kernels have no coded form
   std::vector<unsigned long long> keys;
   if (!collect_patterns(A.nnz, A.val, keys, st)) return false;
-  uint8_t* val8 = nullptr;
-  double* dict = nullptr;
-  try {
-    std::vector<unsigned long long> h_dict(kDictSize, 0ull);                  // (unused slots: +0.0)
-    std::copy(keys.begin(), keys.end(), h_dict.begin());
-    NSS_HIP(hipMalloc(&dict, sizeof(double) * kDictSize));
-    NSS_HIP(hipMalloc(&val8, size_t(A.nnz) + 4));                            // padded like `val`
-    NSS_HIP(hipMemsetAsync(val8, 0, size_t(A.nnz) + 4, st));
-    NSS_HIP(hipMemcpyAsync(dict, h_dict.data(), sizeof(double) * kDictSize, hipMemcpyHostToDevice, st));
-    assign_pattern_codes(A.nnz, A.val, keys, val8, st);                      // (synchronises: h_dict may leave scope)
-  } catch (...) {
-    (void)hipFree(val8);
-    (void)hipFree(dict);
-    throw;
-  }
-  A.val8 = val8;
-  A.dict = dict;
+  DeviceBuffer<uint8_t> val8;
+  DeviceBuffer<double> dict;
+  std::vector<unsigned long long> h_dict(kDictSize, 0ull);                    // (unused slots: +0.0)
+  std::copy(keys.begin(), keys.end(), h_dict.begin());
+  dict.alloc(kDictSize);
+  val8.alloc(size_t(A.nnz) + 4);                                              // padded like `val`
+  NSS_HIP(hipMemsetAsync(val8, 0, size_t(A.nnz) + 4, st));
+  NSS_HIP(hipMemcpyAsync(dict, h_dict.data(), sizeof(double) * kDictSize, hipMemcpyHostToDevice, st));
+  assign_pattern_codes(A.nnz, A.val, keys, val8, st);                        // (synchronises before h_dict leaves scope)
+  A.val8 = std::move(val8);
+  A.dict = std::move(dict);
   A.dict_count = int32_t(keys.size());
   build_ell_code(A, st);
   return true;
@@ -886,36 +801,23 @@ static void direct_rows(nss_csr_s& A, hipStream_t st) {
   if (A.val32) return;                                   // (fp32 values: the stream kernel only)
   if (A.m < g_direct_min_rows || A.nnz > int64_t(kDirectWidth) * A.m) return;
   if (A.n == 0) return;                                  // (csr_direct_kernel gathers padding slots from column 0)
-  int32_t* ecol = nullptr;
-  double* eval = nullptr;
-  int32_t* wide = nullptr;
-  try {
-    NSS_HIP(hipMalloc(&ecol, sizeof(int32_t) * size_t(A.m) * kDirectWidth));
-    NSS_HIP(hipMalloc(&eval, sizeof(double) * size_t(A.m) * kDirectWidth));
-    NSS_HIP(hipMalloc(&wide, sizeof(int32_t)));
-    NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(ell_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.col,
-                       A.val, ecol, eval, wide);
-    NSS_CHECK_LAUNCH();
-    int32_t h_wide = 1;
-    NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    NSS_HIP(hipStreamSynchronize(st));
-    if (h_wide == 0) {
-      A.ell_col = ecol;
-      A.ell_val = eval;
-      ecol = nullptr;
-      eval = nullptr;
-      build_ell_code(A, st);                             // (a re-plan of a coded matrix)
-    }
-  } catch (...) {
-    (void)hipFree(ecol);
-    (void)hipFree(eval);
-    (void)hipFree(wide);
-    throw;
+  DeviceBuffer<int32_t> ecol, wide;
+  DeviceBuffer<double> eval;
+  ecol.alloc(size_t(A.m) * kDirectWidth);
+  eval.alloc(size_t(A.m) * kDirectWidth);
+  wide.alloc(1);
+  NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(ell_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.col,
+                     A.val, ecol, eval, wide);
+  NSS_CHECK_LAUNCH();
+  int32_t h_wide = 1;
+  NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipStreamSynchronize(st));
+  if (h_wide == 0) {
+    A.ell_col = std::move(ecol);
+    A.ell_val = std::move(eval);
+    build_ell_code(A, st);                               // (a re-plan of a coded matrix)
   }
-  (void)hipFree(ecol);
-  (void)hipFree(eval);
-  (void)hipFree(wide);
 #else
   (void)A;
   (void)st;
@@ -987,68 +889,64 @@ int nss_csr_create_cuts(int32_t nrows, int32_t ncols, int64_t nnz, const int32_t
       NSS_REQUIRE(h_rowptr[r + 1] >= h_rowptr[r], "csr_create: rowptr not monotone");
     for (int64_t p = 0; p < nnz; ++p)
       NSS_REQUIRE(h_col[p] >= 0 && h_col[p] < ncols, "csr_create: column index out of range");
-    nss_csr_s* A = new nss_csr_s;
-    try {
-      A->m = nrows;
-      A->n = ncols;
-      A->nnz = nnz;
-      std::vector<int32_t> blk;
-      plan_row_blocks(nrows, nnz, h_rowptr, &A->rg, &A->chunk, blk, h_cuts, ncuts);
-      A->cuts.assign(h_cuts, h_cuts + ncuts);
-      A->nblk = int32_t(blk.size()) - 1;
-      NSS_HIP(hipMalloc(&A->rowptr, sizeof(int32_t) * (size_t(nrows) + 1)));
-      NSS_HIP(hipMalloc(&A->col, sizeof(int32_t) * (nnz + 4)));   // +4: paired loads may touch one entry past the end
-      NSS_HIP(hipMalloc(&A->val, sizeof(double) * (nnz + 4)));
-      NSS_HIP(hipMalloc(&A->rowblk, sizeof(int32_t) * blk.size()));
-      NSS_HIP(hipMemcpy(A->rowptr, h_rowptr, sizeof(int32_t) * (size_t(nrows) + 1), hipMemcpyHostToDevice));
-      NSS_HIP(hipMemset(A->col, 0, sizeof(int32_t) * (nnz + 4)));
-      NSS_HIP(hipMemset(A->val, 0, sizeof(double) * (nnz + 4)));
-      if (nnz > 0) {
-        NSS_HIP(hipMemcpy(A->col, h_col, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
-        NSS_HIP(hipMemcpy(A->val, h_val, sizeof(double) * nnz, hipMemcpyHostToDevice));
-      }
-      NSS_HIP(hipMemcpy(A->rowblk, blk.data(), sizeof(int32_t) * blk.size(), hipMemcpyHostToDevice));
-      compress_columns(*A, nullptr);
-    } catch (...) {
-      nss_csr_destroy(A);
-      throw;
+    std::unique_ptr<nss_csr_s> A(new nss_csr_s);
+    A->m = nrows;
+    A->n = ncols;
+    A->nnz = nnz;
+    std::vector<int32_t> blk;
+    plan_row_blocks(nrows, nnz, h_rowptr, &A->rg, &A->chunk, blk, h_cuts, ncuts);
+    A->cuts.assign(h_cuts, h_cuts + ncuts);
+    A->nblk = int32_t(blk.size()) - 1;
+    A->rowptr.alloc(size_t(nrows) + 1);
+    A->col.alloc(size_t(nnz) + 4);                         // +4: paired loads may touch one entry past the end
+    A->val.alloc(size_t(nnz) + 4);
+    A->rowblk.alloc(blk.size());
+    NSS_HIP(hipMemcpy(A->rowptr, h_rowptr, sizeof(int32_t) * (size_t(nrows) + 1), hipMemcpyHostToDevice));
+    NSS_HIP(hipMemset(A->col, 0, sizeof(int32_t) * (nnz + 4)));
+    NSS_HIP(hipMemset(A->val, 0, sizeof(double) * (nnz + 4)));
+    if (nnz > 0) {
+      NSS_HIP(hipMemcpy(A->col, h_col, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
+      NSS_HIP(hipMemcpy(A->val, h_val, sizeof(double) * nnz, hipMemcpyHostToDevice));
     }
-    *out = A;
+    NSS_HIP(hipMemcpy(A->rowblk, blk.data(), sizeof(int32_t) * blk.size(), hipMemcpyHostToDevice));
+    compress_columns(*A, nullptr);
+    *out = A.release();
   });
 }
 
 int nss_csr_destroy(nss_csr_t a) {
-  return guarded([&] {
-    if (!a) return;
-    (void)hipFree(a->rowptr);
-    (void)hipFree(a->col);
-    (void)hipFree(a->val);
-    (void)hipFree(a->val32);
-    (void)hipFree(a->val8);
-    (void)hipFree(a->dict);
-    (void)hipFree(a->ell_code);
-    (void)hipFree(a->slot_pos);
-    (void)hipFree(a->slot_code);
-    (void)hipFree(a->rowblk);
-    (void)hipFree(a->col16);
-    (void)hipFree(a->blkbase);
-    (void)hipFree(a->blkseg);
-    (void)hipFree(a->blkdisp);
-    (void)hipFree(a->pos16);
-    (void)hipFree(a->ell_col);
-    (void)hipFree(a->ell_val);
-    (void)hipFree(a->jb_first);
-    (void)hipFree(a->jb_order);
-    if (a->fw_col != a->ell_col) {
-      (void)hipFree(a->fw_col);
-      (void)hipFree(a->fw_val);
-    }
-    delete a;
-  });
+  return guarded([&] { delete a; });
 }
 
 // process-wide source of launch-plan generations (nss_csr_s::plan_gen); set-up is single-threaded per process
 static int64_t g_plan_generation = 0;
+
+// Every array that belongs to ONE launch plan goes, with the scalars that describe it; the caller has synchronised the
+// device.  val8 / dict stay: they are per entry in CSR order.
+static void drop_plan_forms(nss_csr_s& A) {
+  A.rowblk.reset();
+  A.col16.reset();
+  A.blkbase.reset();
+  A.blkseg.reset();
+  A.pos16.reset();
+  A.blkdisp.reset();
+  A.disp_period = 0.0;
+  A.disp_planes = 0;
+  A.gb = 1;
+  A.pair_ok = false;
+  A.ell_col.reset();
+  A.ell_val.reset();
+  A.ell_code.reset();
+  A.jb_first.reset();                                    // a plan around Jacobi blocks ends with the plan
+  A.jb_order.reset();
+  A.jb_serial = 0;
+  A.fw_col = nullptr;                                    // (views of ell_col / ell_val or of the own copy)
+  A.fw_val = nullptr;
+  A.fw_own_col.reset();
+  A.fw_own_val.reset();
+  A.fw_state = 0;
+  drop_row_slots(A);                                     // (staged positions of the plan that goes)
+}
 
 // new launch plan with at most `products` products per row block; every derived column stream is rebuilt
 static void replan(nss_csr_s& A, int products, int max_rows = 0, const uint8_t* row_pos = nullptr,
@@ -1060,38 +958,10 @@ static void replan(nss_csr_s& A, int products, int max_rows = 0, const uint8_t* 
   int32_t rg = 1, chunk = kChunk;
   plan_row_blocks(A.m, A.nnz, h_rowptr.data(), &rg, &chunk, blk, A.cuts.data(), int(A.cuts.size()), products, max_rows,
                   row_pos);
-  if (A.fw_col != A.ell_col) {                            // (an own fixed-width copy; an alias of ell_col goes with it below)
-    (void)hipFree(A.fw_col);
-    (void)hipFree(A.fw_val);
-  }
-  A.fw_col = nullptr;
-  A.fw_val = nullptr;
-  A.fw_state = 0;
-  (void)hipFree(A.jb_first);                             // a plan around Jacobi blocks ends with the plan
-  (void)hipFree(A.jb_order);
-  A.jb_first = nullptr;
-  A.jb_order = nullptr;
-  A.jb_serial = 0;
-  int32_t* rowblk = nullptr;
-  NSS_HIP(hipMalloc(&rowblk, sizeof(int32_t) * blk.size()));
+  DeviceBuffer<int32_t> rowblk(blk.size());
   NSS_HIP(hipMemcpy(rowblk, blk.data(), sizeof(int32_t) * blk.size(), hipMemcpyHostToDevice));
-  for (void* p : {(void*)A.rowblk, (void*)A.col16, (void*)A.blkbase, (void*)A.blkseg, (void*)A.pos16, (void*)A.ell_col,
-                  (void*)A.ell_val, (void*)A.blkdisp, (void*)A.ell_code})    // (val8 / dict stay: per entry in CSR order)
-    (void)hipFree(p);
-  A.ell_code = nullptr;
-  drop_row_slots(A);                                     // (staged positions of the plan that goes)
-  A.blkdisp = nullptr;
-  A.disp_period = 0.0;
-  A.disp_planes = 0;
-  A.rowblk = rowblk;
-  A.col16 = nullptr;
-  A.blkbase = nullptr;
-  A.blkseg = nullptr;
-  A.pos16 = nullptr;
-  A.ell_col = nullptr;
-  A.ell_val = nullptr;
-  A.gb = 1;
-  A.pair_ok = false;
+  drop_plan_forms(A);
+  A.rowblk = std::move(rowblk);
   A.rg = rg;                                             // (unchanged: the lanes-per-row rule does not see `products`)
   A.nblk = int32_t(blk.size()) - 1;
   A.blk_products = products;
@@ -1113,33 +983,22 @@ bool fixed_width_copy(nss_csr_s& A) {
     return true;
   }
   if (A.m == 0 || A.nnz > int64_t(kDirectWidth) * A.m) return false;
-  int32_t* ecol = nullptr;
-  double* eval = nullptr;
-  int32_t* wide = nullptr;
+  DeviceBuffer<int32_t> ecol, wide;
+  DeviceBuffer<double> eval;
   int32_t h_wide = 1;
-  try {
-    NSS_HIP(hipMalloc(&ecol, sizeof(int32_t) * size_t(A.m) * kDirectWidth));
-    NSS_HIP(hipMalloc(&eval, sizeof(double) * size_t(A.m) * kDirectWidth));
-    NSS_HIP(hipMalloc(&wide, sizeof(int32_t)));
-    NSS_HIP(hipMemset(wide, 0, sizeof(int32_t)));
-    hipLaunchKernelGGL(ell_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, nullptr, A.m, A.rowptr, A.col,
-                       A.val, ecol, eval, wide);
-    NSS_CHECK_LAUNCH();
-    NSS_HIP(hipMemcpy(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost));
-  } catch (...) {
-    (void)hipFree(ecol);
-    (void)hipFree(eval);
-    (void)hipFree(wide);
-    throw;
-  }
-  (void)hipFree(wide);
-  if (h_wide != 0) {
-    (void)hipFree(ecol);
-    (void)hipFree(eval);
-    return false;
-  }
-  A.fw_col = ecol;
-  A.fw_val = eval;
+  ecol.alloc(size_t(A.m) * kDirectWidth);
+  eval.alloc(size_t(A.m) * kDirectWidth);
+  wide.alloc(1);
+  NSS_HIP(hipMemset(wide, 0, sizeof(int32_t)));
+  hipLaunchKernelGGL(ell_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, nullptr, A.m, A.rowptr, A.col,
+                     A.val, ecol, eval, wide);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipMemcpy(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (h_wide != 0) return false;
+  A.fw_own_col = std::move(ecol);
+  A.fw_own_val = std::move(eval);
+  A.fw_col = A.fw_own_col;
+  A.fw_val = A.fw_own_val;
   A.fw_state = 1;
   return true;
 }
@@ -1230,9 +1089,9 @@ int nss_csr_plan_for_blocks(nss_csr_t a, nss_bjac_t j, int32_t* planned) {
       if (i > 0 && blk[i] - blk[i - 1] > kBlockRows) return;
       first_of[i] = int32_t(b);
     }
-    NSS_HIP(hipMalloc(&a->jb_first, sizeof(int32_t) * first_of.size()));
+    a->jb_first.alloc(first_of.size());
     NSS_HIP(hipMemcpy(a->jb_first, first_of.data(), sizeof(int32_t) * first_of.size(), hipMemcpyHostToDevice));
-    NSS_HIP(hipMalloc(&a->jb_order, sizeof(int32_t) * order.size()));
+    a->jb_order.alloc(order.size());
     NSS_HIP(hipMemcpy(a->jb_order, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice));
     a->jb_serial = j->serial;
     if (planned) *planned = 1;
@@ -1351,14 +1210,14 @@ int nss_csr_round_f32(nss_csr_t a, nss_stream_t stream) {
     hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(a->nnz, kBlock * 4)), dim3(kBlock), 0, as_stream(stream), a->nnz,
                        a->val, a->val, (float*)nullptr);
     NSS_CHECK_LAUNCH();
-    if (a->ell_val) {                                    // (the fixed-width copy holds the values too; fw_val aliases it)
+    if (a->ell_val) {                                    // (the fixed-width copy holds the values too; fw_val views it)
       hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(int64_t(kDirectWidth) * a->m, kBlock * 4)), dim3(kBlock), 0,
                          as_stream(stream), int64_t(kDirectWidth) * a->m, a->ell_val, a->ell_val, (float*)nullptr);
       NSS_CHECK_LAUNCH();
     }
-    if (a->fw_val && a->fw_val != a->ell_val) {
+    if (a->fw_own_val) {                                 // (the handle's own copy: never beside ell_val)
       hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(int64_t(kDirectWidth) * a->m, kBlock * 4)), dim3(kBlock), 0,
-                         as_stream(stream), int64_t(kDirectWidth) * a->m, a->fw_val, a->fw_val, (float*)nullptr);
+                         as_stream(stream), int64_t(kDirectWidth) * a->m, a->fw_own_val, a->fw_own_val, (float*)nullptr);
       NSS_CHECK_LAUNCH();
     }
   });
@@ -1369,38 +1228,27 @@ int nss_csr_narrow_f32(nss_csr_t a, nss_stream_t stream) {
     NSS_REQUIRE(a != nullptr, "csr_narrow_f32: NULL matrix");
     if (a->val32) return;                                // already narrow
     drop_value_codes(*a);                                // (`val` goes)
-    float* v32 = nullptr;
-    NSS_HIP(hipMalloc(&v32, sizeof(float) * size_t(a->nnz + 4)));   // (+4 as `val`: paired loads may touch the end)
-    try {
-      NSS_HIP(hipMemsetAsync(v32, 0, sizeof(float) * size_t(a->nnz + 4), as_stream(stream)));
-      if (a->nnz > 0) {
-        hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(a->nnz, kBlock * 4)), dim3(kBlock), 0, as_stream(stream),
-                           a->nnz, a->val, (double*)nullptr, v32);
-        NSS_CHECK_LAUNCH();
-      }
-      NSS_HIP(hipStreamSynchronize(as_stream(stream)));
-      NSS_HIP(hipDeviceSynchronize());                   // no kernel may still read the arrays that go away
-    } catch (...) {
-      (void)hipFree(v32);
-      throw;
+    DeviceBuffer<float> v32(size_t(a->nnz + 4));          // (+4 as `val`: paired loads may touch the end)
+    NSS_HIP(hipMemsetAsync(v32, 0, sizeof(float) * size_t(a->nnz + 4), as_stream(stream)));
+    if (a->nnz > 0) {
+      hipLaunchKernelGGL(round_f32_kernel, dim3(stream_grid(a->nnz, kBlock * 4)), dim3(kBlock), 0, as_stream(stream),
+                         a->nnz, a->val, (double*)nullptr, v32);
+      NSS_CHECK_LAUNCH();
     }
+    NSS_HIP(hipStreamSynchronize(as_stream(stream)));
+    NSS_HIP(hipDeviceSynchronize());                     // no kernel may still read the arrays that go away
     // the fp64 values and every copy of them go; the fixed-width copies have no fp32 form (the stream kernel takes
     // the matrix), and none is built again (direct_rows, fixed_width_copy)
-    if (a->fw_val && a->fw_val != a->ell_val) {
-      (void)hipFree(a->fw_col);
-      (void)hipFree(a->fw_val);
-    }
     a->fw_col = nullptr;
     a->fw_val = nullptr;
+    a->fw_own_col.reset();
+    a->fw_own_val.reset();
     a->fw_state = -1;
     const bool had_ell = a->ell_col != nullptr;
-    (void)hipFree(a->ell_col);
-    (void)hipFree(a->ell_val);
-    a->ell_col = nullptr;
-    a->ell_val = nullptr;
-    (void)hipFree(a->val);
-    a->val = nullptr;
-    a->val32 = v32;
+    a->ell_col.reset();
+    a->ell_val.reset();
+    a->val.reset();
+    a->val32 = std::move(v32);
     if (had_ell && a->blkseg && !a->blkdisp) build_dispatch(*a, nullptr);
   });
 }

@@ -86,6 +86,7 @@ def _signatures():
         "nss_csr_dispatch_info": (C.c_int, [vp, C.POINTER(dbl), c_i32_p]),
         "nss_csr_direct_rows_threshold": (C.c_int, [i64]),
         "nss_scratch_trim": (C.c_int, []),
+        "nss_device_memory": (C.c_int, [c_i64_p, c_i64_p]),
         "nss_stream_loads_mode": (C.c_int, [i32]),
         "nss_csr_ones_like": (C.c_int, [vp, C.POINTER(vp), vp]),
         "nss_graph_color": (C.c_int, [vp, vp, vp, vp, c_i32_p, vp]),
