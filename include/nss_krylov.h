@@ -885,6 +885,41 @@ NSS_API int nss_fdm_create(int32_t dim, const int64_t* h_extents, const double* 
 NSS_API int nss_fdm_destroy(nss_fdm_t h);
 NSS_API int nss_fdm_solve_f64(nss_fdm_t h, const double* rhs, double* phi, nss_stream_t stream);
 
+/* ---- fast diagonalisation on the components of an interleaved vector -------------------------------
+ * The direct velocity and scalar solves of `NavierStokes.SetImplicitSolve("fdm")` (csrc/fdm_components.hip; DESIGN.md
+ * section 17).  A vector of n_total doubles holds ncomp (1 .. 3) components; component c is an array over its dim (2 or
+ * 3) extents e_a, its entry (k, j, i) at base_c + k * pitch + j * e_2 + i (two axes: (k, i) at base_c + k * pitch + i):
+ * contiguous inside a slab, slabs `pitch` apart, one pitch for all components.  On component c the operator is
+ * m_c I + sigma sum_a I (x) T_a (x) I with T_a = Q_a diag(lambda_a) Q_a^T, and
+ *
+ *   out_c = Q [ 1 / (m_c + sigma ((lambda_0[k] + lambda_1[j]) + lambda_2[i])) ] Q^T rhs_c,    Q = Q_0 (x) .. (x) Q_{dim-1}.
+ *
+ * All fp64, no atomics, every sum over j ascending with the tile of nss_fdm_contract_f64: the same bits every run, and
+ * the bits a one-component handle gives for that component alone.
+ *
+ * nss_fdmc_create: h_base (HOST, ncomp), h_extents (HOST, ncomp * dim, component-major), h_Q / h_lambda (HOST, ncomp * dim
+ *   pointers to HOST arrays: row-major e_a x e_a with the eigenvectors in columns, and e_a eigenvalues), h_mass (HOST,
+ *   ncomp).  Refused: ncomp outside 1 .. 3, dim outside 2 .. 3, n_total or pitch outside 1 .. 2^31 - 1, an extent below
+ *   1, a component with more than one slab whose slab is longer than the pitch, a component that does not fit inside
+ *   [0, n_total), two components that overlap, a mass that is not positive.  Allocates the factors and two work buffers
+ *   of n_total doubles.
+ * nss_fdmc_solve_f64: dim launches with Q_a^T (the shifted scaling rides on the last of them), dim launches with Q_a,
+ *   every launch over all components, on `stream`, no synchronisation.  sigma: by value, >= 0 and finite -- one handle
+ *   serves every step size.  rhs (DEVICE, n_total) is not modified; out (DEVICE, n_total, not rhs) receives the entries
+ *   of the components, every other entry keeps its bits.  Solves with one handle share its work buffers: order them on
+ *   one stream.
+ * nss_fdmc_pass_f64: one batched pass along `axis` (0 .. dim - 1) from src to dst (DEVICE, n_total, distinct), with Q_a
+ *   (transpose = 0) or Q_a^T; `scaled`: the entries are multiplied by the factor above for `sigma`.  The entries
+ *   outside the components are neither read nor written. */
+typedef struct nss_fdmc_s* nss_fdmc_t;
+NSS_API int nss_fdmc_create(int32_t ncomp, int32_t dim, int64_t n_total, const int64_t* h_base, int64_t pitch,
+                            const int64_t* h_extents, const double* const* h_Q, const double* const* h_lambda,
+                            const double* h_mass, nss_fdmc_t* out);
+NSS_API int nss_fdmc_destroy(nss_fdmc_t h);
+NSS_API int nss_fdmc_solve_f64(nss_fdmc_t h, double sigma, const double* rhs, double* out, nss_stream_t stream);
+NSS_API int nss_fdmc_pass_f64(nss_fdmc_t h, int32_t axis, int32_t transpose, int32_t scaled, double sigma,
+                              const double* src, double* dst, nss_stream_t stream);
+
 /* ---- device-resident heat exponential integrator -------------------------------------------------
  * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
  * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:

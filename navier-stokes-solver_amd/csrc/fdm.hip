@@ -29,15 +29,10 @@
 #include <cmath>
 #include <memory>
 
+#include "fdm_tile.h"
 #include "nss_common.h"
 
 namespace nss {
-
-constexpr int kFdmTile = 64;      // outputs per workgroup and direction
-constexpr int kFdmStep = 16;      // j per K-step
-constexpr int kFdmReg = 4;        // register tile per lane and direction: kFdmTile / 16
-constexpr int kFdmLoads = kFdmTile * kFdmStep / kBlock;      // elements of one LDS tile per lane: 4
-constexpr int kFdmRow = kFdmTile + 1;                        // LDS row stride in doubles (odd: the transposing stores)
 
 // the diagonal scaling of the epilogue; dim == 0: none
 struct FdmScale {
@@ -63,15 +58,13 @@ __device__ __forceinline__ double fdm_multiplier(const FdmScale& sc, uint32_t p)
 }
 
 // Grid: one dimension, tiles of q fastest, then tiles of i, then o.  q is the tile direction that is not i: the cell
-// index c (LINES = false, nq = inner, one o per workgroup) or the line index o (LINES = true, nq = outer).
+// index c (LINES = false, nq = inner, one o per workgroup) or the line index o (LINES = true, nq = outer).  The tile
+// body is fdm_tile.h's.
 template <bool LINES>
 __global__ __launch_bounds__(kBlock) void fdm_contract_kernel(int32_t n, int32_t nq, int32_t tiles_q, int32_t tiles_i,
                                                                const double* __restrict__ M, int32_t transpose,
                                                                const double* __restrict__ X, double* __restrict__ Y,
                                                                FdmScale sc) {
-  __shared__ double Ms[kFdmStep][kFdmRow];                 // Ms[k][ii] = Mop[i0 + ii][j0 + k]
-  __shared__ double Xs[kFdmStep][kFdmRow];                 // Xs[k][qq] = X(q0 + qq, j0 + k)
-  const int tid = threadIdx.x;
   const int64_t blk = blockIdx.x;
   const int32_t q0 = int32_t(blk % tiles_q) * kFdmTile;
   const int32_t i0 = int32_t((blk / tiles_q) % tiles_i) * kFdmTile;
@@ -79,83 +72,10 @@ __global__ __launch_bounds__(kBlock) void fdm_contract_kernel(int32_t n, int32_t
   // element (q, j) of X and (q, i) of Y: base + q * sq + j * sj
   const int64_t base = LINES ? 0 : o * int64_t(n) * nq;
   const int64_t sq = LINES ? n : 1, sj = LINES ? 1 : nq;
-
-  // which elements of the two tiles this lane loads: l = 0 .. kFdmLoads - 1
-  //   along j (16 per row of the tile): k = tid % 16, other = tid / 16 + 16 l
-  //   along the other direction (64):   other = tid % 64, k = tid / 64 + 4 l
-  const int k_j = tid & (kFdmStep - 1), r_j = tid >> 4;
-  const int r_o = tid & (kFdmTile - 1), k_o = tid >> 6;
-  double mreg[kFdmLoads], xreg[kFdmLoads];
-
-  auto fetch = [&](int32_t j0) {
-#pragma unroll
-    for (int l = 0; l < kFdmLoads; ++l) {
-      {   // M: rows of M are contiguous along j without transpose, along i with it
-        const int k = transpose ? k_o + 4 * l : k_j, ii = transpose ? r_o : r_j + 16 * l;
-        const int32_t i = i0 + ii, j = j0 + k;
-        const bool in = i < n && j < n;
-        mreg[l] = in ? M[transpose ? int64_t(j) * n + i : int64_t(i) * n + j] : 0.0;
-      }
-      {   // X: contiguous along j for LINES, along q otherwise
-        const int k = LINES ? k_j : k_o + 4 * l, qq = LINES ? r_j + 16 * l : r_o;
-        const int32_t q = q0 + qq, j = j0 + k;
-        const bool in = q < nq && j < n;
-        xreg[l] = in ? X[base + q * sq + j * sj] : 0.0;
-      }
-    }
-  };
-  auto stage = [&]() {
-#pragma unroll
-    for (int l = 0; l < kFdmLoads; ++l) {
-      Ms[transpose ? k_o + 4 * l : k_j][transpose ? r_o : r_j + 16 * l] = mreg[l];
-      Xs[LINES ? k_j : k_o + 4 * l][LINES ? r_j + 16 * l : r_o] = xreg[l];
-    }
-  };
-
-  // the register tile: the direction along which Y is contiguous (q, or i for LINES) goes with tid % 16
-  const int tx = tid & 15, ty = tid >> 4;
-  const int il = LINES ? tx : ty, ql = LINES ? ty : tx;
-  double acc[kFdmReg][kFdmReg];                            // [i][q]
-#pragma unroll
-  for (int a = 0; a < kFdmReg; ++a)
-#pragma unroll
-    for (int b = 0; b < kFdmReg; ++b) acc[a][b] = 0.0;
-
-  fetch(0);
-  for (int32_t j0 = 0; j0 < n; j0 += kFdmStep) {
-    __syncthreads();                                       // the previous step's reads of LDS are done
-    stage();
-    __syncthreads();
-    if (j0 + kFdmStep < n) fetch(j0 + kFdmStep);
-#pragma unroll
-    for (int k = 0; k < kFdmStep; ++k) {
-      double mi[kFdmReg], xq[kFdmReg];
-#pragma unroll
-      for (int t = 0; t < kFdmReg; ++t) {
-        mi[t] = Ms[k][il + 16 * t];
-        xq[t] = Xs[k][ql + 16 * t];
-      }
-#pragma unroll
-      for (int a = 0; a < kFdmReg; ++a)
-#pragma unroll
-        for (int b = 0; b < kFdmReg; ++b) acc[a][b] = fma(mi[a], xq[b], acc[a][b]);
-    }
-  }
-
-#pragma unroll
-  for (int a = 0; a < kFdmReg; ++a) {
-    const int32_t i = i0 + il + 16 * a;
-#pragma unroll
-    for (int b = 0; b < kFdmReg; ++b) {
-      const int32_t q = q0 + ql + 16 * b;
-      if (i < n && q < nq) {
-        const int64_t p = base + q * sq + i * sj;
-        double v = acc[a][b];
-        if (sc.dim) v *= fdm_multiplier(sc, uint32_t(p));
-        Y[p] = v;
-      }
-    }
-  }
+  auto at = [=](int32_t q) { return base + q * sq; };
+  fdm_tile<LINES>(n, nq, q0, i0, M, transpose, X, Y, sj, sj, at, at, [&](int32_t q, int32_t i, double v) {
+    return sc.dim ? v * fdm_multiplier(sc, uint32_t(base + q * sq + i * sj)) : v;
+  });
 }
 
 constexpr int64_t kFdmMaxCells = 2147483647;              // 2^31 - 1

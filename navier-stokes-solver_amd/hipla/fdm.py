@@ -8,7 +8,12 @@ tensor-product grid,
 2 d dense contractions along one grid axis each, no iteration, no tolerance.  The pressure operator B M_u^-1 B^T of every
 system of this package is of that form.  `fdm_factors` finds the factors on the host and checks
 them against the matrix entry by entry; `FastDiagonalization` applies the inverse -- ``nss_fdm_solve_f64`` on the HIP
-engine (csrc/fdm.hip), the numpy restatement of the same formula on any other."""
+engine (csrc/fdm.hip), the numpy restatement of the same formula on any other.
+
+The velocity operator and the scalar's diffusion operator have the same structure per component of their vector:
+`component_factors` finds the factors of every component and checks the layout the kernel addresses, and
+`ComponentFastDiagonalization` applies ``(diag(mass) + sigma mat)^-1`` for any sigma with one set of factors --
+``nss_fdmc_solve_f64`` (csrc/fdm_components.hip) or the numpy restatement."""
 
 import ctypes as C
 
@@ -215,6 +220,232 @@ class FastDiagonalization(BaseMatrix, FusedLoop):
         y.data = Vector.from_numpy(self.factors.solve(x.numpy()), engine=y.engine)
 
     MultTrans = Mult          # Lp symmetric
+
+    @property
+    def T(self):
+        return self
+
+
+# ---- the shifted solve on the components of an interleaved vector ------------------------------
+class ComponentFactors:
+    """What `component_factors` returns: `n_total`; `pitch` (the distance of two slabs, one for all components); per
+    component `bases`, `extents`, `ids` (the flat id arrays), `factors` (its `FdmFactors`) and `masses` (its uniform
+    lumped mass)."""
+
+    def __init__(self, n_total, pitch, bases, ids, factors, masses):
+        self.n_total, self.pitch, self.bases = int(n_total), int(pitch), [int(b) for b in bases]
+        self.ids, self.factors, self.masses = ids, factors, [float(m) for m in masses]
+        self.extents = [f.extents for f in factors]
+
+    @property
+    def dim(self):
+        return self.factors[0].dim
+
+    def solve(self, rhs, sigma):
+        """The numpy restatement of ``(diag(mass) + sigma mat)^-1 rhs``: per component Q_a^T along every axis, the
+        scaling by 1 / (m + sigma sums()), Q_a along every axis."""
+        rhs = np.asarray(rhs, dtype=np.float64)
+        out = rhs.copy()
+        for ids, f, m in zip(self.ids, self.factors, self.masses):
+            w = rhs[ids].reshape(f.extents)
+            for a, q in enumerate(f.Q):
+                w = np.moveaxis(np.tensordot(q.T, w, axes=(1, a)), 0, a)
+            w = w * (1.0 / (m + sigma * f.sums()))
+            for a, q in enumerate(f.Q):
+                w = np.moveaxis(np.tensordot(q, w, axes=(1, a)), 0, a)
+            out[ids] = np.ascontiguousarray(w).reshape(-1)
+        return out
+
+
+def _affine_layout(components, n_total):
+    """(bases, pitch) of id arrays whose entry (k, j, i) is base + k * pitch + j * e_2 + i, or the reason why not."""
+    bases, pitches, slabs = [], set(), []
+    dims = {g.ndim for g in components}
+    if len(dims) != 1 or not dims <= {2, 3}:
+        return "the components are not all arrays over two, or all over three, axes"
+    for c, g in enumerate(components):
+        if g.size == 0 or g.min() < 0 or g.max() >= n_total:
+            return "component %d is empty or holds ids outside 0 .. %d" % (c, n_total - 1)
+        slab = int(np.prod(g.shape[1:], dtype=np.int64))
+        base = int(g.flat[0])
+        pitch = int(g[(1,) + (0,) * (g.ndim - 1)]) - base if g.shape[0] > 1 else slab
+        want = base + np.arange(g.shape[0], dtype=np.int64).reshape((-1,) + (1,) * (g.ndim - 1)) * pitch \
+            + np.arange(slab, dtype=np.int64).reshape(g.shape[1:])
+        if not np.array_equal(g, want):
+            return "the ids of component %d are not affine: base + k * pitch + j * e_2 + i" % c
+        if g.shape[0] > 1:
+            if pitch < slab:
+                return "the slabs of component %d overlap (pitch %d, %d entries per slab)" % (c, pitch, slab)
+            pitches.add(pitch)
+        bases.append(base)
+        slabs.append(slab)
+    if len(pitches) > 1:
+        return "the components have different pitches: %s" % sorted(pitches)
+    return bases, (pitches.pop() if pitches else max(slabs))
+
+
+def component_factors(mat, components, mass):
+    """The factors of ``diag(mass) + sigma mat`` for the direct solve on components: (`ComponentFactors`, None), or
+    (None, reason) -- nothing is raised.  `mat`: scipy sparse, square; `components`: integer id arrays shaped by their
+    grid extents (`StokesSystem.component_ids`, or ``[np.arange(n_p).reshape((n,) * dim)]`` for a cell-centred scalar);
+    `mass`: the lumped mass, one value or one per row.  Declined unless the ids are affine in (base, pitch) with one pitch,
+    the components are disjoint and cover every row, no entry of `mat` couples two components, every component's
+    sub-matrix passes `fdm_factors` over its extents, the mass is constant and positive on each component, and no sum of
+    eigenvalues is below -TOLERANCE max |sum| (the operator is positive semi-definite on it)."""
+    try:
+        return _component_factors(mat, components, mass)
+    except Exception as err:                                # the promise of the docstring: a reason, never a raise
+        return None, "%s: %s" % (type(err).__name__, err)
+
+
+def _component_factors(mat, components, mass):
+    import scipy.sparse as sp
+    if not sp.issparse(mat) or mat.shape[0] != mat.shape[1]:
+        return None, "the matrix is not sparse and square"
+    n_total = mat.shape[0]
+    if n_total > 2 ** 31 - 1:
+        return None, "more than 2^31 - 1 rows"
+    components = [np.asarray(g) for g in components]
+    if not 1 <= len(components) <= 3 or not all(np.issubdtype(g.dtype, np.integer) for g in components):
+        return None, "the components are not one to three integer id arrays"
+    components = [g.astype(np.int64) for g in components]
+    layout = _affine_layout(components, n_total)
+    if isinstance(layout, str):
+        return None, layout
+    bases, pitch = layout
+    flat = [np.ascontiguousarray(g.reshape(-1)) for g in components]
+    label = np.full(n_total, -1, dtype=np.int64)
+    for c, ids in enumerate(flat):
+        if (label[ids] >= 0).any():
+            return None, "component %d overlaps an earlier one" % c
+        label[ids] = c
+    if (label < 0).any():
+        return None, "the components miss %d of the %d rows (the first: row %d)" \
+            % (int((label < 0).sum()), n_total, int(np.flatnonzero(label < 0)[0]))
+    coo = sp.coo_matrix(mat)
+    coupling = (label[coo.row] != label[coo.col]) & (coo.data != 0)
+    if coupling.any():
+        at = int(np.flatnonzero(coupling)[0])
+        return None, "the entry (%d, %d) couples the components %d and %d" \
+            % (coo.row[at], coo.col[at], label[coo.row[at]], label[coo.col[at]])
+    m = np.asarray(mass, dtype=np.float64)
+    m = np.full(n_total, float(m)) if m.ndim == 0 else m
+    if m.shape != (n_total,):
+        return None, "the mass holds %s entries for %d rows" % (m.shape, n_total)
+    csr = sp.csr_matrix(mat)
+    factors, masses = [], []
+    for c, (g, ids) in enumerate(zip(components, flat)):
+        mc = m[ids]
+        if not (np.isfinite(mc).all() and (mc == mc[0]).all() and mc[0] > 0.0):
+            return None, "the mass is not constant and positive on component %d" % c
+        made, why = fdm_factors(csr[ids][:, ids], g.shape)
+        if made is None:
+            return None, "component %d: %s" % (c, why)
+        sums = made.sums()
+        if sums.min() < -TOLERANCE * abs(sums).max():
+            return None, "component %d has the eigenvalue sum %.3g, below -%g max |sum|" % (c, sums.min(), TOLERANCE)
+        factors.append(made)
+        masses.append(mc[0])
+    return ComponentFactors(n_total, pitch, bases, flat, factors, masses), None
+
+
+class _FdmcHandle(_FdmHandle):
+    def __del__(self):
+        try:
+            if self.ptr:
+                self.engine.lib.nss_fdmc_destroy(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+
+def create_component_handle(eng, cf):
+    """The ``nss_fdmc_t`` of the `ComponentFactors` `cf` on the HIP engine `eng`."""
+    ncomp, d = len(cf.factors), cf.dim
+    base = (C.c_int64 * ncomp)(*cf.bases)
+    ext = (C.c_int64 * (ncomp * d))(*[e for f in cf.factors for e in f.extents])
+    qs = (C.c_void_p * (ncomp * d))(*[q.ctypes.data for f in cf.factors for q in f.Q])
+    lams = (C.c_void_p * (ncomp * d))(*[w.ctypes.data for f in cf.factors for w in f.lam])
+    mass = (C.c_double * ncomp)(*cf.masses)
+    out = C.c_void_p()
+    eng._check(eng.lib.nss_fdmc_create(ncomp, d, cf.n_total, base, cf.pitch, ext, qs, lams, mass, C.byref(out)))
+    return _FdmcHandle(eng, out)
+
+
+def components_available(eng):
+    """Whether `eng` is the HIP engine with the component entry points."""
+    return _hip(eng) and hasattr(getattr(eng, "lib", None), "nss_fdmc_solve_f64")
+
+
+class ComponentFastDiagonalization(BaseMatrix, FusedLoop):
+    """``y = (diag(mass) + sigma mat)^-1 x`` by fast diagonalisation on the components of the vector, for a `mat` that
+    `component_factors` accepts (``ValueError`` with the reason otherwise; `try_create` returns None instead, the reason in
+    ``ComponentFastDiagonalization.last_declined``).  `mat`: a `SparseMatrix` or scipy sparse.  `sigma` is a property: the
+    factors do not depend on it, so one object serves every step size.  On the HIP engine `Mult` is
+    ``nss_fdmc_solve_f64`` (2 dim launches for all components, no host synchronisation); on any other engine the numpy
+    restatement of the same formula.
+
+    A direct solve: `iterations` is 0, and `precision` / `maxsteps` are there to be set and are ignored, so that the
+    object can stand where a `CGSolver` stands."""
+
+    iterations = 0
+
+    @classmethod
+    def try_create(cls, mat, components, mass, sigma, engine=None):
+        factors, why = component_factors(mat.to_scipy() if isinstance(mat, SparseMatrix) else mat, components, mass)
+        return cls._decided(why if factors is None else cls(mat, components, mass, sigma, engine, factors))
+
+    def __init__(self, mat, components, mass, sigma, engine=None, factors=None):
+        super().__init__()
+        if factors is None:
+            factors, why = component_factors(mat.to_scipy() if isinstance(mat, SparseMatrix) else mat, components, mass)
+            if factors is None:
+                raise ValueError("ComponentFastDiagonalization: " + why)
+        if engine is None:
+            from .engine import get_engine
+            engine = mat.engine if isinstance(mat, SparseMatrix) else get_engine()
+        self.engine, self.factors = engine, factors
+        self.n = factors.n_total
+        self.sigma = sigma
+        self.precision, self.maxsteps, self.errors = None, None, []
+        self.handle = create_component_handle(engine, factors) if components_available(engine) else None
+
+    @property
+    def sigma(self):
+        return self._sigma
+
+    @sigma.setter
+    def sigma(self, value):
+        value = float(value)
+        if not (value >= 0.0 and np.isfinite(value)):
+            raise ValueError("ComponentFastDiagonalization: sigma is non-negative and finite, not %r" % (value,))
+        self._sigma = value
+
+    def Height(self):
+        return self.n
+
+    def Width(self):
+        return self.n
+
+    def solve_resident(self, rhs, out, sigma=None):
+        """out = (diag(mass) + sigma mat)^-1 rhs on device buffers of the HIP engine (distinct ones); `sigma` None: the
+        object's.  Returns the iterations: 0."""
+        eng = self.engine
+        eng._check(eng.lib.nss_fdmc_solve_f64(self.handle.ptr, self._sigma if sigma is None else float(sigma),
+                                              rhs.data_ptr(), out.data_ptr(), eng.stream))
+        return 0
+
+    def Mult(self, x, y):
+        if len(x) != self.n or len(y) != self.n:
+            raise ValueError("ComponentFastDiagonalization: the operator is %d x %d, x holds %d and y %d entries"
+                             % (self.n, self.n, len(x), len(y)))
+        if self.handle is not None and isinstance(x, Vector) and isinstance(y, Vector):
+            src = x.Copy() if self.engine.overlaps(x.buf, y.buf) else x
+            self.solve_resident(src.buf, y.buf)
+            return
+        y.data = Vector.from_numpy(self.factors.solve(x.numpy(), self._sigma), engine=y.engine)
+
+    MultTrans = Mult          # symmetric
 
     @property
     def T(self):

@@ -298,13 +298,14 @@ class StepRecord:
     variable-step argument of `Advance` (None otherwise): `timestep` = the step sizes tau_n, `time` = their running sum
     within the call, `cfl` = tau_n * rate(u^n), and with `cfl=` also `limited_by` = the codes of `choose_timestep`.
     `projection`: "cg", or "fdm" -- the direct solve of `NavierStokes.SetProjection("fdm")`, whose `proj_iterations` are
-    all zero."""
+    all zero.  `implicit`: "cg", or "fdm" -- the direct velocity and scalar solves of `NavierStokes.SetImplicitSolve("fdm")`,
+    whose `mstar_iterations` and `scalar_iterations` are all zero."""
 
     def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
                  scalar_iterations=None, wall_flux=None, convection="upwind", time_scheme="euler", timestep=None,
-                 time=None, cfl=None, limited_by=None, projection="cg"):
+                 time=None, cfl=None, limited_by=None, projection="cg", implicit="cg"):
         self.timestep, self.time, self.cfl, self.limited_by = timestep, time, cfl, limited_by
-        self.projection = projection
+        self.projection, self.implicit = projection, implicit
         self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
         self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
         self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
@@ -361,7 +362,11 @@ class TimeStepper(FusedLoop):
     q += phi after the projection tail.  `advance` then takes the object's `TimeHistory`.
 
     `projection="fdm"`: phi comes from the 2 dim launches of ``nss_fdm_solve_f64`` in the place of
-    the second CG -- no iteration, no poll; the step then waits for the host in the velocity solve alone."""
+    the second CG -- no iteration, no poll; the step then waits for the host in the velocity solve alone.
+
+    `implicit="fdm"`: raw comes from the 2 dim launches of ``nss_fdmc_solve_f64`` in the place of
+    the first CG, for every step size through the sigma of the launch; with both switches at "fdm" a fixed-step call has
+    no host poll between its first launch and its read-back."""
 
     PRECISION, MAXSTEPS = (1e-4, 1e-8), (500, 5000)        # those of the template's CGSolvers invmstar / invproj
     momentum_flux = adv = avg = diff = stencil = None      # with `flux_declined`: no flux object, no flux operands
@@ -369,7 +374,7 @@ class TimeStepper(FusedLoop):
 
     @classmethod
     def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
-                   convection="upwind", time_scheme="euler", variable=False, m_p=None, projection="cg"):
+                   convection="upwind", time_scheme="euler", variable=False, m_p=None, projection="cg", implicit="cg"):
         """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
         `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
         solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
@@ -384,10 +389,14 @@ class TimeStepper(FusedLoop):
         pressure mass of the rate kernel (None: ones).  `projection`: "cg", or "fdm" -- `project` then launches the direct
         solve ``nss_fdm_solve_f64`` of a `hipla.fdm.FastDiagonalization` of Lp over the extents (system.n,) * system.dim,
         kept under "fdm" in `shared` (built when missing; the stepper declines with the reason when Lp is no Kronecker
-        sum), and neither `cg_p` nor `pre_p` -- for "amg": the hierarchy of Lp -- is built.  Returns None, the reason in
-        `last_declined`."""
+        sum), and neither `cg_p` nor `pre_p` -- for "amg": the hierarchy of Lp -- is built.  `implicit`: "cg", or "fdm" -- the
+        velocity solve then launches ``nss_fdmc_solve_f64`` of a `hipla.fdm.ComponentFastDiagonalization` of A over
+        `system.component_ids`, kept under "fdm_u" in `shared` (built when missing; the stepper declines with the reason
+        when A does not factor), with sigma = the step size ("euler") or half of it ("cnab2"): no mstar / mhalf, no `cg_m`,
+        no `pre_m` and no hierarchy of the velocity operator are built, and a variable-step stepper takes any `inner_pre`,
+        which then concerns a "cg" projection alone.  Returns None, the reason in `last_declined`."""
         return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection,
-                                            time_scheme, variable, m_p, projection))
+                                            time_scheme, variable, m_p, projection, implicit))
 
     @staticmethod
     def _projection_matrices(eng, B, m_u, shared):
@@ -402,12 +411,14 @@ class TimeStepper(FusedLoop):
 
     @classmethod
     def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme,
-                    variable=False, m_p=None, projection="cg"):
+                    variable=False, m_p=None, projection="cg", implicit="cg"):
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
         if projection not in ("cg", "fdm"):
             raise ValueError("projection is \"cg\" or \"fdm\"")
-        if variable and inner_pre != "jacobi":
+        if implicit not in ("cg", "fdm"):
+            raise ValueError("implicit is \"cg\" or \"fdm\"")
+        if variable and inner_pre != "jacobi" and implicit != "fdm":
             raise ValueError("a variable-step stepper takes inner_pre=\"jacobi\": a hierarchy belongs to one step size")
         check_convection(convection, "TimeStepper")
         check_time_scheme(time_scheme, "TimeStepper")
@@ -437,18 +448,29 @@ class TimeStepper(FusedLoop):
             if made is None:
                 return "fdm: " + fdm.FastDiagonalization.last_declined
             shared["fdm"] = made
+        if implicit == "fdm" and shared.get("fdm_u") is None:
+            if not fdm.components_available(A.engine):
+                return "the library has no fast diagonalisation on components"
+            made = fdm.ComponentFastDiagonalization.try_create(A, system.component_ids, np.asarray(m_u, dtype=np.float64),
+                                                               float(timestep), A.engine)
+            if made is None:
+                return "fdm: " + fdm.ComponentFastDiagonalization.last_declined
+            shared["fdm_u"] = made
         return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme, variable,
-                   m_p, projection)
+                   m_p, projection, implicit)
 
     def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind",
-                 time_scheme="euler", variable=False, m_p=None, projection="cg"):
+                 time_scheme="euler", variable=False, m_p=None, projection="cg", implicit="cg"):
         import scipy.sparse as sp
         eng = self.eng = A.engine
         self.time_scheme, self.variable = time_scheme, bool(variable)
-        self.projection = projection
+        self.projection, self.implicit = projection, implicit
         self.fdm = shared["fdm"] if projection == "fdm" else None
         if self.fdm is not None and self.fdm.handle is None:
             raise ValueError("TimeStepper: the FastDiagonalization holds no device handle")
+        self.fdm_u = shared["fdm_u"] if implicit == "fdm" else None
+        if self.fdm_u is not None and self.fdm_u.handle is None:
+            raise ValueError("TimeStepper: the ComponentFastDiagonalization holds no device handle")
         cnab2 = time_scheme == "cnab2"
         rows_key, mstar_key = ("ADBt", "mhalf") if cnab2 else ("AD", "mstar")
         self.lib, self.A, self.B, self.f, self.timestep = eng.lib, A, B, f, float(timestep)
@@ -478,11 +500,12 @@ class TimeStepper(FusedLoop):
         self.temp, self.raw, self.temp2 = eng.zeros(self.n_u), eng.zeros(self.n_u), eng.zeros(self.n_u)
         self.rhs_p, self.phi = eng.zeros(self.n_p), eng.zeros(self.n_p)
         # ---- the inner solves ----
-        if not variable and mstar_key not in shared:   # M_u + timestep A, or the half-step operator M_u + timestep/2 A
+        direct_m = self.fdm_u is not None           # the velocity solve is the direct one: no mstar, no cg_m, no pre_m
+        if not variable and not direct_m and mstar_key not in shared:   # M_u + timestep A, or M_u + timestep/2 A
             theta = 0.5 * self.timestep if cnab2 else self.timestep
             shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(m_u) + theta * A.to_scipy()).tocsr(), engine=eng)
         self._projection_matrices(eng, B, m_u, shared)
-        self.mstar, self.Lp, self.C = None if variable else shared[mstar_key], shared["Lp"], shared["C"]
+        self.mstar, self.Lp, self.C = None if variable or direct_m else shared[mstar_key], shared["Lp"], shared["C"]
         if "singular" not in shared:
             ok, why = two_entry_rows(self.C.to_scipy())
             if not ok:
@@ -490,7 +513,13 @@ class TimeStepper(FusedLoop):
             shared["singular"] = constants_in_kernel(self.Lp.to_scipy())
         self.singular = shared["singular"]
         direct = self.fdm is not None               # the projection is the direct solve: no cg_p, no pre_p
-        if variable:                                # the shifted loop over A: M_u + sigma A for the sigma of each step
+        if direct_m:                                # (`inner_pre` concerns a "cg" projection alone)
+            self.pre_m = self.cg_m = None
+            self.pre_p = None if direct else JacobiPreconditioner(self.Lp) if inner_pre != "amg" else \
+                SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
+            if variable:
+                self.rate = CflRate(eng, B, m_p)
+        elif variable:                              # the shifted loop over A: M_u + sigma A for the sigma of each step
             if "diagA" not in shared:
                 shared["diagA"] = eng.from_host(A.to_scipy().diagonal())
             self.pre_m, self.pre_p = None, None if direct else JacobiPreconditioner(self.Lp)
@@ -639,7 +668,8 @@ class TimeStepper(FusedLoop):
                     tau = chosen[0]
                     codes.append(chosen[1])
                 taus.append(tau)
-                self.cg_m.set_shift(0.5 * tau if cnab2 else tau)
+                if self.cg_m is not None:
+                    self.cg_m.set_shift(0.5 * tau if cnab2 else tau)
             if pseudo:
                 eng.csr_spmv(self.A.handle, -1.0, self.u, 0.0, self.temp)         # :411  temp = -A u
             elif cnab2:
@@ -651,7 +681,11 @@ class TimeStepper(FusedLoop):
                 self.right_hand_side(force)
             else:
                 self.right_hand_side(None if scalar is None else scalar.flux(self.u))     # (S1,) F1, F2  :429-431
-            its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))   # :433
+            if self.fdm_u is not None:              # (the pseudo time stepping is an "euler" stepper's: sigma = timestep)
+                size = self.timestep if tau is None else tau
+                its_m.append(self.fdm_u.solve_resident(self.temp, self.raw, 0.5 * size if cnab2 else size))
+            else:
+                its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))   # :433
             count = self.project(self.raw, out=self.temp2, update=self.u, energy=diagnostics and not pseudo,
                                  tau=tau)                                                                       # :434,438
             if pseudo:
@@ -695,7 +729,7 @@ class TimeStepper(FusedLoop):
                 extra = variable_record(taus, host[nrec:], codes)
         return StepRecord(its_m, its_p, div, energy, flux_declined=self.flux_declined, convection=self.convection,
                           scalar_iterations=its_s, wall_flux=wall, time_scheme=self.time_scheme,
-                          projection=self.projection, **extra)
+                          projection=self.projection, implicit=self.implicit, **extra)
 
 
 class ScalarStepper:
@@ -714,17 +748,24 @@ class ScalarStepper:
     PRECISION, MAXSTEPS = 1e-4, 500          # those of invmstar: the same kind of operator
 
     def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
-                 maxsteps=None, shared=None, convection="upwind", stencil=None, time_scheme="euler", variable=False):
+                 maxsteps=None, shared=None, convection="upwind", stencil=None, time_scheme="euler", variable=False,
+                 implicit="cg", extents=None):
         """`ops`: `StokesSystem.scalar_operators(...)`; `B`: the divergence (`SparseMatrix`); `f`: the force `Vector`
         the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
         (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
         `inner_pre`.  `convection`, `stencil`: the scheme of S1 and, for a limited one, `scalar_stencil()` (`ScalarFlux`).
         `variable`: a variable-step stepper -- no mstar / mhalf: the shifted `CgLoop` over K ("K" of `shared`, uploaded
-        when missing) with the sigma of each step, Jacobi only."""
+        when missing) with the sigma of each step, Jacobi only.  `implicit`: "cg", or "fdm" -- the solve launches
+        ``nss_fdmc_solve_f64`` of the `hipla.fdm.ComponentFastDiagonalization` of K over the cells, kept under "fdm_T" in
+        `shared` (built when missing, over the grid `extents`; ``ValueError`` with the reason when K does not factor),
+        with the sigma of each step: no mstar / mhalf, no `cg`, no `pre`, any `inner_pre`."""
         import scipy.sparse as sp
         shared = {} if shared is None else shared
         self.variable = bool(variable)
-        if variable and inner_pre != "jacobi":
+        if implicit not in ("cg", "fdm"):
+            raise ValueError("ScalarStepper: implicit is \"cg\" or \"fdm\"")
+        self.implicit = implicit
+        if variable and inner_pre != "jacobi" and implicit != "fdm":
             raise ValueError("ScalarStepper: a variable-step stepper takes inner_pre=\"jacobi\"")
         self.time_scheme = check_time_scheme(time_scheme, "ScalarStepper")
         cnab2 = time_scheme == "cnab2"
@@ -744,7 +785,18 @@ class ScalarStepper:
             shared["w_b"] = None if w_b is None else eng.from_host(np.asarray(w_b, dtype=np.float64))
             shared["w"] = None if flux is None else eng.from_host(np.asarray(flux[1], dtype=np.float64))
         mstar_key = "mhalf" if cnab2 else "mstar"
-        if variable:
+        if implicit == "fdm":
+            if shared.get("fdm_T") is None:
+                if extents is None or int(np.prod(extents, dtype=np.int64)) != self.n_p:
+                    raise ValueError("ScalarStepper: implicit=\"fdm\" wants the grid extents of the %d cells" % self.n_p)
+                made = fdm.ComponentFastDiagonalization.try_create(
+                    sp.csr_matrix(ops["K"]), [np.arange(self.n_p).reshape(tuple(extents))], ops["mass"], self.timestep, eng)
+                if made is None:
+                    raise ValueError("ScalarStepper: fdm: " + fdm.ComponentFastDiagonalization.last_declined)
+                shared["fdm_T"] = made
+            if shared["fdm_T"].handle is None:
+                raise ValueError("ScalarStepper: the ComponentFastDiagonalization holds no device handle")
+        elif variable:
             if "K" not in shared:
                 shared["K"] = SparseMatrix.from_scipy(sp.csr_matrix(ops["K"]), engine=eng)
             if "diagK" not in shared:
@@ -753,7 +805,8 @@ class ScalarStepper:
             theta = 0.5 * self.timestep if cnab2 else self.timestep
             shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + theta * ops["K"]).tocsr(), engine=eng)
         self.KB, self.q, self.w_b, self.w = (shared[key] for key in ("KB", "q", "w_b", "w"))
-        self.mstar = None if variable else shared[mstar_key]
+        self.fdm = shared["fdm_T"] if implicit == "fdm" else None
+        self.mstar = None if variable or self.fdm is not None else shared[mstar_key]
         self.c0, self.records = (0.0 if flux is None else float(flux[0])), flux is not None
         self.tg = eng.zeros(self.n_p + self.n_u)             # the operand [T | G]
         self.T, self.G = eng.view(self.tg, 0, self.n_p), eng.view(self.tg, self.n_p, self.n_p + self.n_u)
@@ -762,7 +815,9 @@ class ScalarStepper:
             self.G_prev = eng.zeros(self.n_u)
             self.b_prev = None if w_b is None else eng.zeros(self.n_u)
         self.temp, self.delta = eng.zeros(self.n_p), eng.zeros(self.n_p)
-        if variable:
+        if self.fdm is not None:
+            self.pre = self.cg = None
+        elif variable:
             self.pre = None
             self.cg = CgLoop(eng, shared["K"], NO_PRE, shift=(ops["mass"], shared["diagK"]))
         else:
@@ -800,11 +855,16 @@ class ScalarStepper:
         """S2, the solve, S3 and (with `record`) S4; `tau`: the size of a variable step (None: the stepper's timestep).
         Returns the CG iterations."""
         eng, lib = self.eng, self.lib
-        if self.variable:
-            self.cg.set_shift(0.5 * tau if self.time_scheme == "cnab2" else tau)
+        size = self.timestep if tau is None else tau
+        sigma = 0.5 * size if self.time_scheme == "cnab2" else size
+        if self.variable and self.cg is not None:
+            self.cg.set_shift(sigma)
         eng._check(lib.nss_step_rhs_f64(self.KB.handle.ptr, self.tg.data_ptr(), self.q.data_ptr(), self.temp.data_ptr(),
                                         None, eng.stream))
-        its = self.cg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
+        if self.fdm is not None:
+            its = self.fdm.solve_resident(self.temp, self.delta, sigma)
+        else:
+            its = self.cg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
         write = record is not None
         eng._check(lib.nss_scalar_update_f64(self.n_p, self.timestep if tau is None else tau, self.delta.data_ptr(), self.T.data_ptr(),
                                              _ptr(self.w if write else None), _ptr(self.partials if write else None),

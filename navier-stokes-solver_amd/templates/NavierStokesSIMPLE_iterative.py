@@ -34,7 +34,8 @@ for the viscous term, two-step Adams-Bashforth for convection and buoyancy, an i
 per unit of step size; ``DoTimeStep(timestep=)``, ``Advance(timesteps=)`` and ``Advance(cfl=)`` take steps of other
 sizes than the constructor's, the last one chosen from that rate (not in the reference).
 ``SetProjection("fdm")`` replaces the CG solve of the projection by the direct solve of the fast diagonalisation method
-(`hipla.FastDiagonalization`; not in the reference).
+(`hipla.FastDiagonalization`; not in the reference).  ``SetImplicitSolve("fdm")`` does the same for
+the velocity solve and the scalar's (`hipla.ComponentFastDiagonalization`; not in the reference).
 
 Out of scope: the MCS/HDG assembly itself and the sparse direct branch
 ``iterative=False`` (raises ``NotImplementedError``)."""
@@ -43,7 +44,7 @@ import numpy as np
 import scipy.sparse as sp
 
 import hipla
-from hipla import BlockVector, CGSolver, FastDiagonalization, fused
+from hipla import BlockVector, CGSolver, ComponentFastDiagonalization, FastDiagonalization, fused
 from hipla.stepping import (CflRate, MomentumFlux, ScalarFlux, ScalarStepper, StepController, StepRecord, TimeHistory,
                             TimeStepper, check_convection, check_step_size, check_time_scheme, pair, variable_record)
 from discretizations import AssembledForm, CondensedForm, SyntheticMesh, assemble, bdm_hybrid
@@ -199,6 +200,9 @@ class ScalarField:
                  convection="upwind", time_scheme="euler"):
         self.convection = check_convection(convection, "AddScalar")
         self.time_scheme = time_scheme
+        self.timestep = timestep
+        self.implicit = "cg"              # how `solver_for` solves (`NavierStokes.SetImplicitSolve`)
+        self.extents = (system.n,) * system.dim
         self.ops = ops = system.scalar_operators(kappa, dirichlet)
         self.stencil = system.scalar_stencil() if convection != "upwind" else None    # host array; uploaded on first use
         self.device_flux = None           # the `ScalarFlux` of `DoTimeStep`'s limited G, over `shared`
@@ -236,7 +240,13 @@ class ScalarField:
 
     def solver_for(self, tau):
         """The CG inverse for a step of size `tau` (None: the object's own), at the precision of `solver`; built with
-        Jacobi-CG on the host on first use and kept by step size."""
+        Jacobi-CG on the host on first use and kept by step size.  With `implicit` at "fdm": the one direct solve of
+        `direct_solver()`, with the sigma of the step."""
+        if self.implicit == "fdm":
+            size = self.timestep if tau is None else tau
+            inv = self.last_solver = self.direct_solver()
+            inv.sigma = 0.5 * size if self.time_scheme == "cnab2" else size
+            return inv
         if tau is None:
             self.last_solver = self.solver
             return self.solver
@@ -247,6 +257,18 @@ class ScalarField:
         inv = self.last_solver = self.by_step[tau]
         inv.precision, inv.maxsteps = self.solver.precision, self.solver.maxsteps
         return inv
+
+    def direct_solver(self):
+        """The `ComponentFastDiagonalization` of K over the cells ("fdm_T" of `shared`, which the scalar steppers read),
+        built on first use; ``ValueError`` with the reason when K does not factor."""
+        if self.shared.get("fdm_T") is None:
+            cells = np.arange(int(np.prod(self.extents))).reshape(self.extents)
+            made = ComponentFastDiagonalization.try_create(sp.csr_matrix(self.ops["K"]), [cells], self.ops["mass"],
+                                                           self.timestep)
+            if made is None:
+                raise ValueError("SetImplicitSolve: the scalar: " + ComponentFastDiagonalization.last_declined)
+            self.shared["fdm_T"] = made
+        return self.shared["fdm_T"]
 
     def wall_flux(self, temperature):
         """The heat entering through `flux_wall`: c0 - <w, T>."""
@@ -293,6 +315,8 @@ class NavierStokes:
         self._scalar = None               # the transported scalar (`AddScalar`)
         self._projection = "cg"           # how `invproj` solves (`SetProjection`)
         self._fdm = None                  # the `FastDiagonalization` of Lp, built by the first SetProjection("fdm")
+        self._implicit = "cg"             # how the velocity and the scalar solve (`SetImplicitSolve`)
+        self._fdm_u = None                # the `ComponentFastDiagonalization` of A, built by the first SetImplicitSolve("fdm")
 
     @property
     def projection(self):
@@ -324,6 +348,44 @@ class NavierStokes:
             self._invproj_cg, ops["invproj"] = ops["invproj"], self._fdm
         elif kind == "cg" and ops["invproj"] is self._fdm:
             ops["invproj"] = self._invproj_cg
+
+    @property
+    def implicit_solve(self):
+        """"cg" or "fdm": see `SetImplicitSolve`."""
+        return self._implicit
+
+    def SetImplicitSolve(self, kind):
+        """How the implicit solves of a step -- raw = (M_u + sigma A)^-1 temp of the velocity and, with a scalar,
+        delta = (M_p + sigma K)^-1 temp_T -- are done, from now on and in every entry point (`DoTimeStep`,
+        `DoTimeStep(timestep=)`, `Advance` in all its modes, the pseudo time stepping): "cg" (the default: Jacobi-CG to
+        1e-4, or what `Advance(inner_pre=, precision=)` and `AddScalar(precision=)` ask for) or "fdm", the direct solve
+        by fast diagonalisation on the velocity components -- `hipla.ComponentFastDiagonalization` of A over
+        `system.component_ids`, built here on first use, and of K over the cells when `AddScalar` has been called or is
+        called later; ``ValueError`` with the reason when a system does not factor (an inflated system with order > 0
+        and a permuted one do not).  The factors do not depend on sigma: the one object serves "euler" (sigma = the step
+        size), "cnab2" (half of it) and every size of a variable step, so nothing is built per step size and
+        `Advance(timesteps= | cfl=)` takes any `inner_pre`.  The solves report 0 iterations and ignore their `precision`
+        and `maxsteps`.
+
+        The direct solve is exact to rounding, where the default CG stops at a relative residual of 1e-4: results differ
+        from the default path at that level.  That is a difference in stopping, not in the operator -- against CG solves
+        at 1e-12 the two paths agree to 1e-9.  `SetImplicitSolve("cg")` puts the CG solvers back; an object that never
+        calls this method, or is back at "cg", keeps the bits of the CG path in every entry point."""
+        if kind not in ("cg", "fdm"):
+            raise ValueError("SetImplicitSolve: the implicit solve is \"cg\" or \"fdm\", not %r" % (kind,))
+        if kind == "fdm":
+            if self._fdm_u is None:
+                s = self.system
+                m_u = np.full(s.n_u, s.h ** s.dim * self.V.dofs_per_site ** 0)
+                made = ComponentFastDiagonalization.try_create(self.a.mat, s.component_ids, m_u, self.timestep)
+                if made is None:
+                    raise ValueError("SetImplicitSolve: " + ComponentFastDiagonalization.last_declined)
+                self._fdm_u = made
+            if self._scalar is not None:
+                self._scalar.direct_solver()
+        self._implicit = kind
+        if self._scalar is not None:
+            self._scalar.implicit = kind
 
     @property
     def conv_operator(self):
@@ -405,10 +467,17 @@ class NavierStokes:
         rate = (abs(self.system.B) @ np.abs(self.gfu.numpy())) / self.system.mass
         return float(np.inf) if not np.isfinite(rate).all() else float(rate.max(initial=0.0))
 
-    def _momentum_solver_for(self, tau):
+    def _momentum_solver_for(self, tau, pseudo=False):
         """The CG inverse of the velocity solve for a step of size `tau` (None: the object's own operators), at the
-        precision of the object's own; built with Jacobi-CG on the host on first use and kept by step size."""
-        held, name = self._momentum_solver()
+        precision of the object's own; built with Jacobi-CG on the host on first use and kept by step size.  After
+        `SetImplicitSolve("fdm")`: the one direct solve, with the sigma of the step.  `pseudo`: the solve of a pseudo
+        time step, M_u + timestep A whatever the scheme."""
+        if self._implicit == "fdm":
+            size = self.timestep if tau is None else tau
+            inv = self._last_momentum_solver = self._fdm_u
+            inv.sigma = 0.5 * size if self.time_scheme == "cnab2" and not pseudo else size
+            return inv
+        held, name = self._momentum_solver(pseudo)
         if tau is None:
             self._last_momentum_solver = held[name]
             return held[name]
@@ -488,7 +557,7 @@ class NavierStokes:
         temp = self.a.mat.CreateColVector()
         temp2 = self.a.mat.CreateColVector()
         temp.data = -self.a.mat * self.gfu
-        temp2.data = ops["invmstar"] * temp
+        temp2.data = self._momentum_solver_for(None, pseudo=True) * temp      # invmstar, or the direct solve
         self.Project(temp2)
         count = ops["invproj"].iterations
         self.gfu.data += self.timestep * temp2
@@ -518,6 +587,9 @@ class NavierStokes:
         self._scalar = ScalarField(self.system, self.b.mat, self.timestep, kappa, dirichlet, buoyancy, t_ref, precision,
                                    maxsteps, flux_wall, self.convection if convection is None else convection,
                                    self.time_scheme)
+        if self._implicit == "fdm":       # (`SetImplicitSolve` came first: the scalar follows it)
+            self._scalar.direct_solver()
+            self._scalar.implicit = "fdm"
         if self._history is not None:
             self._history.reset("scalar")
         start = np.full(self.system.n_p, float(t_ref)) if initial is None else np.asarray(initial, dtype=np.float64)
@@ -710,7 +782,14 @@ class NavierStokes:
         After `SetProjection("fdm")` the steppers (their own, keyed by the projection too) launch the direct solve of the
         object's `FastDiagonalization` in the place of the projection's CG: ``record.projection == "fdm"``,
         `proj_iterations` all zero, the projection entries of `precision` and `maxsteps` ignored, and for
-        `inner_pre="amg"` no hierarchy of the pressure operator."""
+        `inner_pre="amg"` no hierarchy of the pressure operator.
+
+        After `SetImplicitSolve("fdm")` the steppers (keyed by that switch as well) launch the direct solves of the
+        object's `ComponentFastDiagonalization` in the place of the velocity's and the scalar's CG:
+        ``record.implicit == "fdm"``, `mstar_iterations` and `scalar_iterations` all zero, no mstar, CG loop,
+        preconditioner or velocity hierarchy in the stepper, and variable steps with any `inner_pre`, which then concerns
+        a "cg" projection alone.  With both switches at "fdm" a fixed-step call does not wait for the host between its
+        first launch and its read-back."""
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
         if pseudo and self._scalar is not None:
@@ -722,7 +801,7 @@ class NavierStokes:
             raise ValueError("Advance: timesteps and cfl exclude each other")
         if cfl is None and not (duration is None and growth == 1.25 and max_timestep is None):
             raise ValueError("Advance: duration, growth and max_timestep belong to cfl=")
-        if variable and (inner_pre == "amg" or pseudo):
+        if variable and ((inner_pre == "amg" and self._implicit != "fdm") or pseudo):
             raise ValueError("Advance: variable steps take inner_pre=\"jacobi\" (a hierarchy belongs to one step size) "
                              "and no pseudo time stepping")
         if timesteps is not None:
@@ -737,6 +816,7 @@ class NavierStokes:
         key = inner_pre if scheme == self.time_scheme else (inner_pre, scheme)
         key = ("variable", key) if variable else key
         key = (key, "fdm") if self._projection == "fdm" else key
+        key = (key, "implicit fdm") if self._implicit == "fdm" else key
         stepper = steppers.get(key) if fused.ENABLED else None
         if stepper is None:
             s = self.system
@@ -748,21 +828,26 @@ class NavierStokes:
                     self._stepper_shared["mhalf"] = self._cnab2_operators()["mhalf"]
             if self._projection == "fdm":
                 self._stepper_shared.setdefault("fdm", self._fdm)
+            if self._implicit == "fdm":
+                self._stepper_shared.setdefault("fdm_u", self._fdm_u)
             stepper = TimeStepper.try_create(s, self.a.mat, self.b.mat, self.f.vec, self.timestep, m_u, inner_pre,
                                              conv_operator=lambda: self.conv_operator, shared=self._stepper_shared,
                                              convection=self.convection, time_scheme=scheme, variable=variable,
-                                             m_p=self.system.mass, projection=self._projection)
+                                             m_p=self.system.mass, projection=self._projection,
+                                             implicit=self._implicit)
             if stepper is not None:
                 steppers[key] = stepper
         self.advance_declined = TimeStepper.last_declined if stepper is None else None
         if stepper is not None and self._scalar is not None:
             sc = self._scalar
             skey = "variable" if variable else inner_pre
+            skey = (skey, "implicit fdm") if self._implicit == "fdm" else skey
             if skey not in sc.steppers:
                 sc.steppers[skey] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
                                                   inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
                                                   shared=sc.shared, convection=sc.convection, stencil=sc.stencil,
-                                                  time_scheme=self.time_scheme, variable=variable)
+                                                  time_scheme=self.time_scheme, variable=variable,
+                                                  implicit=self._implicit, extents=sc.extents)
             return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics,
                                    scalar=sc.steppers[skey], temperature=self.temperature, history=self._history,
                                    timesteps=timesteps, controller=controller, clock=self._clock)
@@ -781,8 +866,11 @@ class NavierStokes:
         import contextlib
         import io
         ops = self._time_stepping_operators()
-        held, name = self._momentum_solver(pseudo)
-        solvers = (held[name], ops["invproj"])
+        if self._implicit == "fdm":       # (the direct solve takes precision and maxsteps, and ignores them)
+            solvers = (self._fdm_u, ops["invproj"])
+        else:
+            held, name = self._momentum_solver(pseudo)
+            solvers = (held[name], ops["invproj"])
         saved = [(sv.precision, sv.maxsteps) for sv in solvers]
         for sv, p, m in zip(solvers, pair(precision), pair(maxsteps)):
             sv.precision = sv.precision if p is None else float(p)
@@ -833,5 +921,5 @@ class NavierStokes:
                            np.array(energy) if diagnostics else None, declined=self.advance_declined,
                            scalar_iterations=its_s, convection=self.convection,
                            time_scheme="euler" if pseudo else self.time_scheme, projection=self._projection,
-                           **(variable_record(taus, rates, codes) if variable else {}),
+                           implicit=self._implicit, **(variable_record(taus, rates, codes) if variable else {}),
                            wall_flux=np.array(wall) if sc is not None and diagnostics and sc.flux is not None else None)
