@@ -364,6 +364,7 @@ typedef struct nss_amg_level_s {
   const double* dinv;   /* DEVICE: inverse diagonal of A (n)                        */
 } nss_amg_level_t;
 typedef struct nss_amg_s* nss_amg_t;
+typedef struct nss_fdmi_s* nss_fdmi_t;  /* fast-diagonalisation inverse of the velocity block (nss_fdmi_create) */
 NSS_API int nss_amg_create(int32_t nlevels, const nss_amg_level_t* h_levels, nss_csr_t coarse_inverse,
                            double omega, nss_amg_t* out);
 /* Auxiliary-space preconditioner term  x -> T (sum_c E_c V_c E_c^T) T^T x  as an nss_amg_t: the
@@ -478,6 +479,10 @@ typedef struct nss_bpcg2_s {
    * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
   int64_t plan_gen;
   int64_t cap_a, cap_b, cap_c;
+  /* the exact inverse of A by fast diagonalisation (nss_fdmi_create) as preA -- or NULL.  Exclusive with pre_diag,
+   * pre_bjac and every term; one GPU, no condensed form (the contraction spans the slabs, and the Schur
+   * complement is no Kronecker sum). */
+  nss_fdmi_t pre_fdm;
   /* the matrix of the residual `x - A y` between the two sweeps of the multiplicative MypreA (:379) -- NULL: the loop's
    * own A (the uncondensed form).  The statically condensed form with MypreA(GS=True) (the reference's
    * SolveInitial(iterative=True): `condense=True`, :188, :364-391) sweeps over the Schur complement S = blfA.mat, so
@@ -920,6 +925,43 @@ NSS_API int nss_fdmc_solve_f64(nss_fdmc_t h, double sigma, const double* rhs, do
 NSS_API int nss_fdmc_pass_f64(nss_fdmc_t h, int32_t axis, int32_t transpose, int32_t scaled, double sigma,
                               const double* src, double* dst, nss_stream_t stream);
 
+/* ---- the exact inverse of the velocity block by fast diagonalisation, for the fused loops ---------------
+ * `hipla.FastDiagonalizationInverse`, `NavierStokes.SolveInitial(pre="fdm")` (csrc/fdm_inverse.hip; DESIGN.md section
+ * 18).  The vector, its components and their factors are those of nss_fdmc_create; there is no mass:
+ *
+ *   y_c = scale * Q [ 1 / ((lambda_0[k] + lambda_1[j]) + lambda_2[i]) ] Q^T x_c,    Q = Q_0 (x) .. (x) Q_{dim-1}.
+ *
+ * Every launch takes `done` (DEVICE int32, may be NULL) and returns before its first load when it is non-zero: the
+ * contract of every launch inside the fused loops.  All fp64, no atomics, the same bits every run.  Two tile bodies
+ * compute the contractions: the FMA tile of nss_fdm_contract_f64 (every sum over j ascending, one FMA per term) and a
+ * tile on the fp64 matrix cores (v_mfma_f64_16x16x4_f64: a sum runs over j in groups of four, each group added to the
+ * accumulator by one instruction).  That the two give the same bits is not promised (on the MI355X they have been
+ * measured to); both obey the dot-product bound of n terms.
+ *
+ * nss_fdmi_create: the arguments and refusals of nss_fdmc_create without h_mass; refused as well: an eigenvalue that
+ *   is not finite, a component whose least sum of eigenvalues is not positive (a singular operator has no inverse).
+ * nss_fdmi_apply_f64: dim launches with Q_a^T (the scaling by scale / sum rides on the last of them), dim launches with
+ *   Q_a, every launch over all components, on `stream`, no synchronisation.  x (DEVICE, n_total) is not modified;
+ *   y (DEVICE, n_total, not x) receives the entries of the components, every other entry keeps its bits.  Applies with
+ *   one handle share its work buffers: order them on one stream.
+ * nss_fdmi_contract_f64: one contraction on its own, with the tile `tile` (as the mode of nss_fdmi_set_tile):
+ *   Y(q, i) = sum_j Mop[i][j] X(q, j), Mop = M (DEVICE, row-major n x n; transpose = 0) or M^T.  lines = 0: X and Y are
+ *   n x nq row-major (q contiguous); lines != 0: nq x n row-major (j and i contiguous).  x, y: DEVICE, distinct;
+ *   n * nq <= 2^31 - 1.
+ * nss_fdmi_set_tile: the tile of this handle's applies from now on: -1 the library's choice (the default: the
+ *   matrix-core tile at every extent -- it was nowhere slower, profiles/fdm_stokes.md), 0 the FMA tile, 1 the
+ *   matrix-core tile.  A property of the handle, not of the process: two preconditioners may differ. */
+NSS_API int nss_fdmi_create(int32_t ncomp, int32_t dim, int64_t n_total, const int64_t* h_base, int64_t pitch,
+                            const int64_t* h_extents, const double* const* h_Q, const double* const* h_lambda,
+                            nss_fdmi_t* out);
+NSS_API int nss_fdmi_destroy(nss_fdmi_t h);
+NSS_API int nss_fdmi_apply_f64(nss_fdmi_t h, double scale, const double* x, double* y, const int32_t* done,
+                               nss_stream_t stream);
+NSS_API int nss_fdmi_contract_f64(int64_t n, int64_t nq, int32_t lines, int32_t tile, const double* M,
+                                  int32_t transpose, const double* x, double* y, const int32_t* done,
+                                  nss_stream_t stream);
+NSS_API int nss_fdmi_set_tile(nss_fdmi_t h, int32_t mode);
+
 /* ---- device-resident heat exponential integrator -------------------------------------------------
  * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
  * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:
@@ -977,6 +1019,9 @@ typedef struct nss_lanczos_s {
    * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
   int64_t plan_gen;
   int64_t cap_a, cap_b;
+  /* the exact inverse of A by fast diagonalisation (nss_fdmi_create) as preA -- or NULL.  Exclusive with pre_diag,
+   * pre_bjac and every term: pre * A = I, the run breaks down after one step with the Ritz value pre_scale. */
+  nss_fdmi_t pre_fdm;
   /* the matrix of the multiplicative preconditioner's residual `x - A y` (:379) -- NULL: this A.  The condensed form
    * runs the Lanczos of its scale factor on the explicit product (I - H^T)(S + A_ii)(I - H) with MypreA over the
    * Schur complement: sweep_A = S (n x n). */
@@ -1041,6 +1086,14 @@ typedef struct nss_minres_s {
    * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
   int64_t plan_gen;
   int64_t cap_a, cap_b, cap_c;
+  /* the exact inverse of A by fast diagonalisation (nss_fdmi_create) as preA -- or NULL.  Exclusive with pre_diag,
+   * pre_bjac and every term; one GPU (local_sums == 0).  preA = pre_fdm_scale * A^-1: this loop carries no k, so the
+   * scale is a field of its own, finite and not zero (1 for the plain inverse; a state with pre_fdm and the scale 0 is
+   * refused).  The scale rides in the epilogue of the apply.  As with every preconditioner this loop applies in
+   * launches of its own, the apply is issued without the stop word: after the stop it writes ring slots that nobody
+   * reads any more. */
+  nss_fdmi_t pre_fdm;
+  double pre_fdm_scale;
 } nss_minres_t;
 
 NSS_API int nss_minres_workspace(const nss_minres_t* s, int64_t* partials_a, int64_t* partials_b,
@@ -1101,6 +1154,9 @@ typedef struct nss_bpcg1_s {
    * state (before any launch) when plan_gen is no longer current or a cap_* is below what the workspace asks for. */
   int64_t plan_gen;
   int64_t cap_a, cap_b, cap_c;
+  /* the exact inverse of A by fast diagonalisation (nss_fdmi_create) as preA -- or NULL.  Exclusive with pre_diag,
+   * pre_bjac and every term; one GPU (local_sums == 0). */
+  nss_fdmi_t pre_fdm;
 } nss_bpcg1_t;
 
 NSS_API int nss_bpcg1_workspace(const nss_bpcg1_t* s, int64_t* partials_a, int64_t* partials_b,

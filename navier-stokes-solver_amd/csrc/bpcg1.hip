@@ -322,6 +322,12 @@ __global__ __launch_bounds__(kBlock) void bpcg1_v6_kernel(const int32_t* __restr
 
 static int p_grid(const nss_bpcg1_t& s) { return stream_grid(int64_t(s.n_u) + s.n_p, kBlock * 4); }
 
+static PreA pre_a_of(const nss_bpcg1_t& s) {
+  PreA p = pre_a_of(s, s.n_u);
+  p.fdm = s.pre_fdm;
+  return p;
+}
+
 static void bpcg1_check(const nss_bpcg1_t* s) {
   NSS_REQUIRE(s != nullptr, "bpcg1: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "bpcg1: NULL matrix handle");
@@ -331,7 +337,8 @@ static void bpcg1_check(const nss_bpcg1_t* s) {
   else
     NSS_REQUIRE(s->A->n == s->n_u && s->B->n == s->n_u && s->BT->n == s->n_p, "bpcg1: matrix columns do not match");
   NSS_REQUIRE(!(s->local_sums && s->pre_amg), "bpcg1: the row-partitioned loop takes a (block) Jacobi preconditioner");
-  pre_a_check(pre_a_of(*s, s->n_u), "bpcg1", kPreAAdditiveOnly);
+  pre_a_check(pre_a_of(*s), "bpcg1", kPreAAdditiveOnly);
+  NSS_REQUIRE(!(s->local_sums && s->pre_fdm), "bpcg1: pre_fdm (fast diagonalisation) runs on one GPU");
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "bpcg1: NULL work buffer");
   for (int c = 0; c < 2; ++c)
@@ -419,7 +426,8 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
     launch_csr(*s.BT, s.d[1], EpiV1b{s.ctrl, s.t1[0], s.t2[0], s.pre_amg ? nullptr : s.pre_diag, s.k}, st);
     }
     // t2 = -k preA t1 (t1 holds -K u here) where no epilogue above has formed it (point / fused block Jacobi alone)
-    if (s.pre_amg || (s.pre_bjac && !fused_j)) pre_a_apply(pre_a_of(s, s.n_u), -s.k, s.t1[0], s.t2[0], nullptr, s.ctrl, st);
+    if (s.pre_amg || s.pre_fdm || (s.pre_bjac && !fused_j))
+      pre_a_apply(pre_a_of(s), -s.k, s.t1[0], s.t2[0], nullptr, s.ctrl, st);
   }
   if (on(2)) {
     if (dist) exchange(*dist->d, halo_of(dist->hu, s.t2[0]), st);

@@ -804,7 +804,7 @@ static void bpcg2_check_plan(const nss_bpcg2_t& s) {
 static PreA pre_a_of(const nss_bpcg2_t& s) {
   return PreA{.n = s.n_u, .ncols = s.dist_compact ? s.A->n : s.n_u, .diag = s.pre_diag, .bjac = s.pre_bjac,
               .amg = s.pre_amg, .A = s.A, .sweep_A = s.sweep_A, .dist_amg = s.pre_dist_amg, .dist_aux = s.pre_dist_aux,
-              .exchange_y = s.pre_dist_aux && !(s.cond_HT && s.sweep_A)};
+              .exchange_y = s.pre_dist_aux && !(s.cond_HT && s.sweep_A), .fdm = s.pre_fdm};
 }
 
 void bpcg2_check_state(const nss_bpcg2_t* s) {
@@ -831,6 +831,8 @@ void bpcg2_check_state(const nss_bpcg2_t* s) {
   }
   const PreA p = pre_a_of(*s);
   pre_a_check(p, "bpcg2", kPreAMultiplicative | kPreASlabTerms);
+  NSS_REQUIRE(!s->pre_fdm || (!s->local_sums && !s->dist_compact && !s->ghost_mode && !s->cond_HT),
+              "bpcg2: pre_fdm (fast diagonalisation) runs on one GPU and takes no condensed form");
   // what ties the term to the loop's plan.  The multiplicative MypreA takes the condensed form only when its residual is
   // formed with the matrix of the sweeps (sweep_A = the Schur complement), not with the loop's explicit product.
   NSS_REQUIRE(!s->pre_dist_aux || !s->cond_HT || (p.multiplicative() && s->sweep_A && s->dist_compact),
@@ -962,7 +964,7 @@ void bpcg2_k1_finish(const nss_bpcg2_t& s, hipStream_t st, const nss_dist_s* d) 
   // t1 = k * preA src unless K1's epilogue has formed it (uncondensed, point Jacobi alone).  t2 is free here: the
   // previous iteration's t2 was consumed by K1 / C1 and the A-SpMV has not written the new one yet
   const PreA p = pre_a_of(s);
-  if (p.term() || p.bjac || s.cond_HT) pre_a_apply(p, s.k, src, s.t1, s.t2, s.ctrl, st);
+  if (p.term() || p.bjac || p.fdm || s.cond_HT) pre_a_apply(p, s.k, src, s.t1, s.t2, s.ctrl, st);
   if (s.cond_HT) {
     if (cond_slab) cond_exchange(s, *d, d->cond_ext, 2, st);
     launch_csr(*s.cond_H, s.t1, EpiExtendInPlace{s.ctrl, s.t1}, st);         // t1 += H t1

@@ -27,12 +27,11 @@
 #include <cmath>
 #include <memory>
 
+#include "fdm_layout.h"
 #include "fdm_tile.h"
 #include "nss_common.h"
 
 namespace nss {
-
-constexpr int kFdmcMaxComp = 3;
 
 // one component of one pass, by value in the kernel arguments
 struct FdmcComp {
@@ -111,12 +110,6 @@ __global__ __launch_bounds__(kBlock) void fdmc_pass_kernel(FdmcPass p, const dou
   });
 }
 
-constexpr int64_t kFdmcMaxTotal = 2147483647;             // 2^31 - 1
-
-static int64_t floor_div(int64_t a, int64_t b) {          // b > 0
-  return a / b - ((a % b != 0) && (a < 0));
-}
-
 }  // namespace nss
 
 using namespace nss;
@@ -134,7 +127,7 @@ struct nss_fdmc_s {
 };
 
 // the internal axis of the caller's axis a
-static int fdmc_axis(int dim, int a) { return dim == 3 ? a : 2 * a; }
+static int fdmc_axis(int dim, int a) { return fdm_internal_axis(dim, a); }
 
 // one batched pass; the arguments have been checked
 static void fdmc_launch(const nss_fdmc_s& h, int axis, int transpose, int scaled, double sigma, const double* src,
@@ -178,41 +171,20 @@ int nss_fdmc_create(int32_t ncomp, int32_t dim, int64_t n_total, const int64_t* 
   return guarded([&] {
     NSS_REQUIRE(h_base && h_extents && h_Q && h_lambda && h_mass && out, "fdmc_create: NULL argument");
     *out = nullptr;
-    NSS_REQUIRE(ncomp >= 1 && ncomp <= kFdmcMaxComp, "fdmc_create: ncomp is 1, 2 or 3");
-    NSS_REQUIRE(dim == 2 || dim == 3, "fdmc_create: dim is 2 or 3");
-    NSS_REQUIRE(n_total >= 1 && n_total <= kFdmcMaxTotal, "fdmc_create: n_total is not in 1 .. 2^31 - 1");
-    NSS_REQUIRE(pitch >= 1 && pitch <= kFdmcMaxTotal, "fdmc_create: the pitch is not in 1 .. 2^31 - 1");
+    // the layout, its checks and the overlap arithmetic: fdm_layout.h (shared with nss_fdmi_create)
+    const FdmLayout lay = fdm_layout_checked("fdmc_create", ncomp, dim, n_total, h_base, pitch, h_extents, h_Q, h_lambda);
     std::unique_ptr<nss_fdmc_s> h(new nss_fdmc_s);
     h->ncomp = ncomp;
     h->dim = dim;
     h->n_total = n_total;
     h->pitch = pitch;
-    int64_t slab[kFdmcMaxComp];                            // the entries of a component in one slab
     for (int c = 0; c < ncomp; ++c) {
-      const std::string who = "fdmc_create: component " + std::to_string(c);
-      for (int a = 0; a < dim; ++a) {
-        const int64_t e = h_extents[c * dim + a];
-        NSS_REQUIRE(e >= 1 && e <= n_total, who + ": an extent is not in 1 .. n_total");
-        NSS_REQUIRE(h_Q[c * dim + a] && h_lambda[c * dim + a], who + ": NULL factor");
-        h->ext[c][fdmc_axis(dim, a)] = int32_t(e);
-      }
-      NSS_REQUIRE(h_mass[c] > 0.0 && std::isfinite(h_mass[c]), who + ": the mass is not positive and finite");
+      NSS_REQUIRE(h_mass[c] > 0.0 && std::isfinite(h_mass[c]),
+                  "fdmc_create: component " + std::to_string(c) + ": the mass is not positive and finite");
       h->mass[c] = h_mass[c];
-      h->base[c] = h_base[c];
-      slab[c] = int64_t(h->ext[c][1]) * h->ext[c][2];      // (below 2^62)
-      NSS_REQUIRE(h->ext[c][0] == 1 || slab[c] <= pitch, who + ": a slab of it is longer than the pitch");
-      NSS_REQUIRE(h_base[c] >= 0 && slab[c] <= n_total && h_base[c] <= n_total - slab[c] &&
-                      (h->ext[c][0] - 1) * pitch <= n_total - slab[c] - h_base[c],
-                  who + " does not fit inside [0, n_total)");
+      h->base[c] = lay.base[c];
+      for (int a = 0; a < 3; ++a) h->ext[c][a] = lay.ext[c][a];
     }
-    // two components overlap when slab ka of a and slab kb = ka + m of b do: -slab_b < (base_b - base_a) + m pitch < slab_a
-    for (int a = 0; a < ncomp; ++a)
-      for (int b = a + 1; b < ncomp; ++b) {
-        const int64_t d = h->base[b] - h->base[a];
-        const int64_t lo = std::max<int64_t>(-(h->ext[a][0] - 1), -floor_div(slab[b] - 1 + d, pitch));
-        const int64_t hi = std::min<int64_t>(h->ext[b][0] - 1, floor_div(slab[a] - 1 - d, pitch));
-        NSS_REQUIRE(lo > hi, "fdmc_create: components " + std::to_string(a) + " and " + std::to_string(b) + " overlap");
-      }
     for (int c = 0; c < ncomp; ++c) {
       int64_t total = 0;
       for (int a = 0; a < dim; ++a) total += h_extents[c * dim + a];

@@ -281,6 +281,7 @@ static int64_t lz_partials_b(const nss_lanczos_t& s);
 static PreA pre_a_of(const nss_lanczos_t& s) {
   PreA p = pre_a_of(s, s.n);
   p.sweep_A = s.sweep_A;
+  p.fdm = s.pre_fdm;
   return p;
 }
 static void lz_check(const nss_lanczos_t* s) {

@@ -451,6 +451,12 @@ static void minres_need(const nss_minres_t& s, int64_t* need) {
   need[2] = std::max<int64_t>(gu_fused, m_gu(s)) + m_gp(s);
 }
 
+static PreA pre_a_of(const nss_minres_t& s) {
+  PreA p = pre_a_of(s, s.n_u);
+  p.fdm = s.pre_fdm;
+  return p;
+}
+
 static void minres_check(const nss_minres_t* s) {
   NSS_REQUIRE(s != nullptr, "minres: NULL state");
   NSS_REQUIRE(s->A && s->B && s->BT, "minres: NULL matrix handle");
@@ -459,7 +465,10 @@ static void minres_check(const nss_minres_t* s) {
     NSS_REQUIRE(s->A->n >= s->n_u && s->B->n >= s->n_u && s->BT->n >= s->n_p, "minres: local matrix narrower than the slab");
   else
     NSS_REQUIRE(s->A->n == s->n_u && s->B->n == s->n_u && s->BT->n == s->n_p, "minres: matrix columns do not match n_u/n_p");
-  pre_a_check(pre_a_of(*s, s->n_u), "minres", kPreAAdditiveOnly);
+  pre_a_check(pre_a_of(*s), "minres", kPreAAdditiveOnly);
+  NSS_REQUIRE(!(s->local_sums && s->pre_fdm), "minres: pre_fdm (fast diagonalisation) runs on one GPU");
+  NSS_REQUIRE(!s->pre_fdm || (std::isfinite(s->pre_fdm_scale) && s->pre_fdm_scale != 0.0),
+              "minres: pre_fdm wants pre_fdm_scale finite and not zero (1 for the plain inverse)");
   NSS_REQUIRE(s->minv && s->scal && s->ctrl && s->hist && s->partials_a && s->partials_b && s->partials_c,
               "minres: NULL work buffer");
   for (int c = 0; c < 2; ++c) {
@@ -546,8 +555,9 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
   }
   NSS_CHECK_LAUNCH();
   }
-  if (!fused && (s.pre_bjac || s.pre_amg)) {
-    const bool dot_in_apply = !s.pre_amg && !s.pre_bjac->gs_mat;   // block Jacobi: <z_new, v_new> out of the apply kernel
+  if (!fused && (s.pre_bjac || s.pre_amg || s.pre_fdm)) {
+    // block Jacobi: <z_new, v_new> out of the apply kernel
+    const bool dot_in_apply = !s.pre_amg && !s.pre_fdm && !s.pre_bjac->gs_mat;
     if (!on(3)) {                   // phases 4 / 5 issued on their own: the partial count of phase 3
       nb2 = dot_in_apply ? bjac_dot_grid(*s.pre_bjac) : m_dot_grid(s);
     } else
@@ -555,7 +565,7 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
     // touch ring slots nobody reads any more
     {
     if (dot_in_apply) nb2 = bjac_apply_dot(*s.pre_bjac, 1.0, s.v[in][0], s.z[zn][0], s.partials_a, nullptr, st);
-    else pre_a_apply(pre_a_of(s, s.n_u), 1.0, s.v[in][0], s.z[zn][0], nullptr, nullptr, st);
+    else pre_a_apply(pre_a_of(s), s.pre_fdm ? s.pre_fdm_scale : 1.0, s.v[in][0], s.z[zn][0], nullptr, nullptr, st);
     if (nb2 == 0) {
       nb2 = m_dot_grid(s);
       launch_dot_partials(MinresSkip{s.ctrl, k}, nb2, s.n_u, s.z[zn][0], s.v[in][0], s.partials_a, st);

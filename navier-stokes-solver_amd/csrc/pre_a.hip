@@ -1,5 +1,6 @@
 // One check and one apply routine of the velocity preconditioner for the five device loops (pre_a.h).
 #include "dist.h"
+#include "fdm_inverse.h"
 
 namespace nss {
 
@@ -27,6 +28,12 @@ void pre_a_check(const PreA& p, const char* loop, int allows) {
   const std::string who = std::string(loop) + ": ";
   const int terms = int(p.amg != nullptr) + int(p.dist_amg != nullptr) + int(p.dist_aux != nullptr);
   const int parts = int(p.diag != nullptr) + int(p.bjac != nullptr) + terms;
+  if (p.fdm) {
+    NSS_REQUIRE(parts == 0 && !p.sweep_A,
+                who + "pre_fdm (the inverse by fast diagonalisation) is exclusive with pre_diag, pre_bjac and every term");
+    NSS_REQUIRE(fdmi_rows(*p.fdm) == p.n && p.ncols == p.n, who + "fast-diagonalisation size mismatch");
+    return;
+  }
   if (allows & kPreAOnePartAtMost) {
     NSS_REQUIRE(parts <= 1, who + "at most one preconditioner");
   } else {
@@ -56,7 +63,9 @@ static void term_apply(const PreA& p, double bscale, const double* b, double* y,
 
 void pre_a_apply(const PreA& p, double scale, const double* x, double* y, double* scratch, const int32_t* done,
                  hipStream_t st) {
-  if (p.multiplicative()) {
+  if (p.fdm) {
+    fdmi_apply(*p.fdm, scale, x, y, done, st);
+  } else if (p.multiplicative()) {
     // MypreA with GS=True (:376-381): y = 0; J.Smooth(y, x); r = x - A y; y += M r; J.SmoothBack(y, x), applied to scale x.
     // On slabs the sweeps run inside the slab (additive across slabs); the residual is formed with the matrix of the
     // sweeps (fp32 storage: the handle's fp32 copy of it), which keeps the operator symmetric.

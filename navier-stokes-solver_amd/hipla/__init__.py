@@ -11,9 +11,11 @@ IdentityMatrix, Vector, InnerProduct, Norm, Projector; plus ``hipla.la`` and
 from . import fused, la, ngstd    # noqa: F401  (fused before hipla.stepping: it re-exports that module's names)
 from .engine import EngineUnavailable, get_engine, set_engine
 from .la import *  # noqa: F401,F403
-from .fdm import ComponentFastDiagonalization, FastDiagonalization, component_factors, fdm_factors
+from .fdm import (ComponentFastDiagonalization, FastDiagonalization, FastDiagonalizationInverse, component_factors,
+                  fdm_factors, inverse_factors)
 from .ngstd import SetHeapSize, TaskManager, Timer
 
 __all__ = list(la.__all__) + ["la", "ngstd", "TaskManager", "Timer", "SetHeapSize",
                               "get_engine", "set_engine", "EngineUnavailable", "FastDiagonalization", "fdm_factors",
-                              "ComponentFastDiagonalization", "component_factors"]
+                              "ComponentFastDiagonalization", "component_factors", "FastDiagonalizationInverse",
+                              "inverse_factors"]

@@ -46,7 +46,7 @@ class _LanczosState:
                                ("scal", C.c_void_p), ("ctrl", C.c_void_p), ("hist", C.c_void_p),
                                ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("n", C.c_int32),
                                ("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64),
-                               ("sweep_A", C.c_void_p)])
+                               ("pre_fdm", C.c_void_p), ("sweep_A", C.c_void_p)])
             cls._cls = LanczosState
         return cls._cls
 

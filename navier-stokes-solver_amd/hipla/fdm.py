@@ -13,9 +13,15 @@ engine (csrc/fdm.hip), the numpy restatement of the same formula on any other.
 The velocity operator and the scalar's diffusion operator have the same structure per component of their vector:
 `component_factors` finds the factors of every component and checks the layout the kernel addresses, and
 `ComponentFastDiagonalization` applies ``(diag(mass) + sigma mat)^-1`` for any sigma with one set of factors --
-``nss_fdmc_solve_f64`` (csrc/fdm_components.hip) or the numpy restatement."""
+``nss_fdmc_solve_f64`` (csrc/fdm_components.hip) or the numpy restatement.
+
+Without a mass the same factors give the inverse of the velocity operator itself: `inverse_factors` runs the checks of
+`component_factors` and asks that the operator be definite, and `FastDiagonalizationInverse` applies ``mat^-1`` as a
+preconditioner of the Stokes solvers -- ``nss_fdmi_apply_f64`` (csrc/fdm_inverse.hip), inside the
+fused loops on the HIP engine, or the numpy restatement."""
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -292,13 +298,27 @@ def component_factors(mat, components, mass):
     the components are disjoint and cover every row, no entry of `mat` couples two components, every component's
     sub-matrix passes `fdm_factors` over its extents, the mass is constant and positive on each component, and no sum of
     eigenvalues is below -TOLERANCE max |sum| (the operator is positive semi-definite on it)."""
+    if mass is None:
+        return None, "no mass (the pure inverse: inverse_factors)"
     try:
         return _component_factors(mat, components, mass)
     except Exception as err:                                # the promise of the docstring: a reason, never a raise
         return None, "%s: %s" % (type(err).__name__, err)
 
 
+def inverse_factors(mat, components):
+    """The factors of ``mat^-1`` on components: (`ComponentFactors` with the masses 0, None), or (None, reason) -- nothing
+    is raised.  The checks of `component_factors` without a mass (layout, coverage, no coupling, `fdm_factors` per
+    component); declined as well when a sum of eigenvalues is not above TOLERANCE max |sum|: `mat` must be definite.  The
+    velocity operator of an enclosed cavity is; a singular operator has no inverse to offer."""
+    try:
+        return _component_factors(mat, components, None)
+    except Exception as err:                                # the promise of the docstring: a reason, never a raise
+        return None, "%s: %s" % (type(err).__name__, err)
+
+
 def _component_factors(mat, components, mass):
+    """`mass` None: the factors of the pure inverse (`inverse_factors`)."""
     import scipy.sparse as sp
     if not sp.issparse(mat) or mat.shape[0] != mat.shape[1]:
         return None, "the matrix is not sparse and square"
@@ -328,7 +348,8 @@ def _component_factors(mat, components, mass):
         at = int(np.flatnonzero(coupling)[0])
         return None, "the entry (%d, %d) couples the components %d and %d" \
             % (coo.row[at], coo.col[at], label[coo.row[at]], label[coo.col[at]])
-    m = np.asarray(mass, dtype=np.float64)
+    pure = mass is None
+    m = np.zeros(n_total) if pure else np.asarray(mass, dtype=np.float64)
     m = np.full(n_total, float(m)) if m.ndim == 0 else m
     if m.shape != (n_total,):
         return None, "the mass holds %s entries for %d rows" % (m.shape, n_total)
@@ -336,12 +357,15 @@ def _component_factors(mat, components, mass):
     factors, masses = [], []
     for c, (g, ids) in enumerate(zip(components, flat)):
         mc = m[ids]
-        if not (np.isfinite(mc).all() and (mc == mc[0]).all() and mc[0] > 0.0):
+        if not pure and not (np.isfinite(mc).all() and (mc == mc[0]).all() and mc[0] > 0.0):
             return None, "the mass is not constant and positive on component %d" % c
         made, why = fdm_factors(csr[ids][:, ids], g.shape)
         if made is None:
             return None, "component %d: %s" % (c, why)
         sums = made.sums()
+        if pure and not sums.min() > TOLERANCE * abs(sums).max():
+            return None, "component %d has the eigenvalue sum %.3g, not above %g max |sum|: the operator is not definite " \
+                "and has no inverse" % (c, sums.min(), TOLERANCE)
         if sums.min() < -TOLERANCE * abs(sums).max():
             return None, "component %d has the eigenvalue sum %.3g, below -%g max |sum|" % (c, sums.min(), TOLERANCE)
         factors.append(made)
@@ -444,6 +468,111 @@ class ComponentFastDiagonalization(BaseMatrix, FusedLoop):
             self.solve_resident(src.buf, y.buf)
             return
         y.data = Vector.from_numpy(self.factors.solve(x.numpy(), self._sigma), engine=y.engine)
+
+    MultTrans = Mult          # symmetric
+
+    @property
+    def T(self):
+        return self
+
+
+# ---- the pure inverse as a preconditioner of the Stokes solvers ---------------------------------
+class _FdmiHandle(_FdmHandle):
+    def __del__(self):
+        try:
+            if self.ptr:
+                self.engine.lib.nss_fdmi_destroy(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+
+def create_inverse_handle(eng, cf):
+    """The ``nss_fdmi_t`` of the `ComponentFactors` `cf` (of `inverse_factors`) on the HIP engine `eng`."""
+    ncomp, d = len(cf.factors), cf.dim
+    base = (C.c_int64 * ncomp)(*cf.bases)
+    ext = (C.c_int64 * (ncomp * d))(*[e for f in cf.factors for e in f.extents])
+    qs = (C.c_void_p * (ncomp * d))(*[q.ctypes.data for f in cf.factors for q in f.Q])
+    lams = (C.c_void_p * (ncomp * d))(*[w.ctypes.data for f in cf.factors for w in f.lam])
+    out = C.c_void_p()
+    eng._check(eng.lib.nss_fdmi_create(ncomp, d, cf.n_total, base, cf.pitch, ext, qs, lams, C.byref(out)))
+    return _FdmiHandle(eng, out)
+
+
+def inverse_available(eng):
+    """Whether `eng` is the HIP engine with the entry points of the inverse."""
+    return _hip(eng) and hasattr(getattr(eng, "lib", None), "nss_fdmi_apply_f64")
+
+
+class FastDiagonalizationInverse(BaseMatrix, FusedLoop):
+    """``y = mat^-1 x`` by fast diagonalisation on the components of the vector, for a `mat` that `inverse_factors` accepts
+    (``ValueError`` with the reason otherwise; `try_create` returns None instead, the reason in
+    ``FastDiagonalizationInverse.last_declined``).  `mat`: a `SparseMatrix` or scipy sparse; `components`: the id arrays
+    (`StokesSystem.component_ids`).  Symmetric: ``.T`` is the object itself.
+
+    The exact inverse of the velocity block as ``preA`` of `BramblePasciakCG`, `bramble_pasciak_cg` and `MinRes`: on the
+    HIP engine the fused loops apply it themselves (``nss_fdmi_apply_f64``: 2 dim launches for all components, a scale in
+    the epilogue, no host synchronisation), and `Mult` is the same call; on any other engine `Mult` is the numpy
+    restatement, ``ComponentFactors.solve(x, 1.0)`` with the masses 0.
+
+    `tile` picks the tile body of the native contractions (``nss_fdmi_set_tile``): -1 the library's choice, 0 the FMA tile
+    of csrc/fdm_tile.h, 1 the matrix-core tile of csrc/fdm_tile_mfma.h.  It is a property of the object, not of the
+    process; a new object starts from the environment variable ``NSS_FDM_TILE`` (unset or empty: -1)."""
+
+    @classmethod
+    def try_create(cls, mat, components, engine=None):
+        factors, why = inverse_factors(mat.to_scipy() if isinstance(mat, SparseMatrix) else mat, components)
+        return cls._decided(why if factors is None else cls(mat, components, engine, factors))
+
+    def __init__(self, mat, components, engine=None, factors=None):
+        super().__init__()
+        if factors is None:
+            factors, why = inverse_factors(mat.to_scipy() if isinstance(mat, SparseMatrix) else mat, components)
+            if factors is None:
+                raise ValueError("FastDiagonalizationInverse: " + why)
+        if engine is None:
+            from .engine import get_engine
+            engine = mat.engine if isinstance(mat, SparseMatrix) else get_engine()
+        self.engine, self.factors = engine, factors
+        self.n = factors.n_total
+        self.handle = create_inverse_handle(engine, factors) if inverse_available(engine) else None
+        self._tile = -1
+        self.tile = int(os.environ.get("NSS_FDM_TILE") or -1)
+
+    @property
+    def tile(self):
+        return self._tile
+
+    @tile.setter
+    def tile(self, mode):
+        mode = int(mode)
+        if mode not in (-1, 0, 1):
+            raise ValueError("FastDiagonalizationInverse: the tile is -1 (the library's choice), 0 (FMA) or 1 (matrix "
+                             "cores), not %r" % (mode,))
+        if self.handle is not None:
+            self.engine._check(self.engine.lib.nss_fdmi_set_tile(self.handle.ptr, mode))
+        self._tile = mode
+
+    def Height(self):
+        return self.n
+
+    def Width(self):
+        return self.n
+
+    def apply_resident(self, x, y, scale=1.0):
+        """y = scale mat^-1 x on device buffers of the HIP engine (distinct ones)."""
+        eng = self.engine
+        eng._check(eng.lib.nss_fdmi_apply_f64(self.handle.ptr, float(scale), x.data_ptr(), y.data_ptr(), None, eng.stream))
+
+    def Mult(self, x, y):
+        if len(x) != self.n or len(y) != self.n:
+            raise ValueError("FastDiagonalizationInverse: the operator is %d x %d, x holds %d and y %d entries"
+                             % (self.n, self.n, len(x), len(y)))
+        if self.handle is not None and isinstance(x, Vector) and isinstance(y, Vector):
+            src = x.Copy() if self.engine.overlaps(x.buf, y.buf) else x
+            self.apply_resident(src.buf, y.buf)
+            return
+        y.data = Vector.from_numpy(self.factors.solve(x.numpy(), 1.0), engine=y.engine)
 
     MultTrans = Mult          # symmetric
 

@@ -41,7 +41,7 @@ class Bpcg2State(C.Structure):
                    ("local_sums", C.c_int32), ("pre_dist_amg", C.c_void_p), ("dist_compact", C.c_int32),
                    ("pre_dist_aux", C.c_void_p), ("p2p", C.c_void_p)]
                 + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)]
-                + [("sweep_A", C.c_void_p)])
+                + [("pre_fdm", C.c_void_p), ("sweep_A", C.c_void_p)])
 
 
 class HaloStruct(C.Structure):
@@ -66,12 +66,13 @@ class PreParts(NamedTuple):
     """What the fused loops apply natively for a preconditioner: ``scale * (amg + diag | bjac)`` with any of the three
     absent -- the additive form of the reference's MypreA (templates/NavierStokesSIMPLE_iterative.py:383) -- or, with
     `multiplicative`, the Gauss-Seidel sweeps of `bjac` around the (auxiliary-space) AMG `amg` in its middle (GS=True,
-    :376-381)."""
+    :376-381).  Or, alone, ``scale * fdm``: the exact inverse by fast diagonalisation (`FastDiagonalizationInverse`)."""
     scale: float
     diag: object
     bjac: object
     amg: object
     multiplicative: bool
+    fdm: object = None
 
 
 NO_PRE = PreParts(1.0, None, None, None, False)
@@ -84,6 +85,9 @@ def native_velocity_pre(op):
         scale, op = op.scale, op.mat
     if isinstance(op, BlockGaussSeidel) and isinstance(op.middle, SmoothedAggregationAMG):
         return PreParts(scale, None, op, op.middle, True)
+    from .fdm import FastDiagonalizationInverse              # (fdm.py imports this module)
+    if isinstance(op, FastDiagonalizationInverse):
+        return PreParts(scale, None, None, None, False, op) if op.handle is not None else None
     parts = [op]
     if isinstance(op, SumMatrix):
         if op.sb != 1.0:
@@ -122,17 +126,19 @@ def fp32_storage(pa):
 def native_diag(op):
     """The `PreParts` of a (scaled) diagonal preconditioner (preM, preS), else None."""
     p = native_velocity_pre(op)
-    return p if p is not None and p.bjac is None and p.amg is None else None
+    return p if p is not None and p.bjac is None and p.amg is None and p.fdm is None else None
 
 
 # The preconditioners each fused loop takes (BPCG v2 and the Lanczos check theirs against their other operands).
-# CG further declines a ScaledMatrix or a sum (CgLoop); the partitioned loops have no AMG term.
+# CG further declines a ScaledMatrix or a sum (CgLoop); the partitioned loops have no AMG term.  The inverse by fast
+# diagonalisation (p.fdm) goes with any scale into MINRES and the textbook BPCG, and never into the partitioned loops
+# (its contractions span the slabs) or into CG (an exact inverse of the loop's own operator).
 ACCEPTS = {
     "minres": lambda p: not p.multiplicative and (p.scale == 1.0 or (p.bjac is None and p.amg is None)),
     "bpcg1": lambda p: not p.multiplicative and (p.scale == 1.0 or p.amg is None),     # the scale goes into k
-    "cg": lambda p: not p.multiplicative,
-    "partitioned minres": lambda p: p.amg is None and ACCEPTS["minres"](p),
-    "partitioned bpcg1": lambda p: p.amg is None and ACCEPTS["bpcg1"](p),
+    "cg": lambda p: not p.multiplicative and p.fdm is None,
+    "partitioned minres": lambda p: p.amg is None and p.fdm is None and ACCEPTS["minres"](p),
+    "partitioned bpcg1": lambda p: p.amg is None and p.fdm is None and ACCEPTS["bpcg1"](p),
 }
 
 
@@ -148,13 +154,16 @@ def scaled_diag(p):
 
 
 def write_pre(st, p, scale_diag=False):
-    """Point the ``pre_diag`` / ``pre_bjac`` / ``pre_amg`` fields of loop state `st` at the parts of `p`.  `scale_diag`:
+    """Point the ``pre_diag`` / ``pre_bjac`` / ``pre_amg`` (/ ``pre_fdm``, where the state has it) fields of loop state
+    `st` at the parts of `p`.  `scale_diag`:
     pre_diag gets ``scaled_diag(p)`` instead of p.diag's entries.  Returns the buffer pre_diag points at (None without a
     diagonal), which the loop keeps alive."""
     diag = None if p.diag is None else scaled_diag(p) if scale_diag else p.diag.d
     st.pre_diag = diag.data_ptr() if diag is not None else None
     st.pre_bjac = p.bjac.handle.ptr if p.bjac is not None else None
     st.pre_amg = p.amg.handle.ptr if p.amg is not None else None
+    if hasattr(type(st), "pre_fdm"):
+        st.pre_fdm = p.fdm.handle.ptr if p.fdm is not None else None
     return diag
 
 
@@ -397,6 +406,10 @@ class Bpcg2Loop(FusedLoop):
             return "preM is not a (scaled) diagonal"
         if pa is None:
             return "preA is not native"
+        if pa.fdm is not None and (distributed or dist_amg is not None or dist_aux is not None):
+            return "fast diagonalisation on a partitioned run (the contractions span the slabs)"
+        if pa.fdm is not None and condensed is not None:
+            return "fast diagonalisation with a condensed form (the Schur complement is no Kronecker sum)"
         if distributed and fp32_storage(pa):
             return "fp32 preconditioner storage on a partitioned run (the row-partitioned preconditioners are fp64)"
         if pa.multiplicative:
@@ -583,7 +596,8 @@ class MinresState(C.Structure):
                    ("scal", C.c_void_p), ("ctrl", C.c_void_p), ("hist", C.c_void_p),
                    ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("partials_c", C.c_void_p),
                    ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)]
-                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)])
+                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)]
+                + [("pre_fdm", C.c_void_p), ("pre_fdm_scale", C.c_double)])
 
 
 (M_DELTA, M_GAMMA, M_G2, M_ETA_OLD, M_C_OLD, M_C, M_S_OLD, M_S, M_RES_OLD, M_ERR0, M_TOL) = range(11)
@@ -636,6 +650,7 @@ class MinresLoop(FusedLoop):
         st = MinresState()
         st.A, st.B, st.BT = A.handle.ptr, B.handle.ptr, BT.handle.ptr
         self.dinv = write_pre(st, pa, scale_diag=True)
+        st.pre_fdm_scale = float(pa.scale)
         self.minv = scaled_diag(ps)
         st.minv = self.minv.data_ptr()
         for c in range(2):
@@ -691,7 +706,8 @@ class Bpcg1State(C.Structure):
                 + [("scal", C.c_void_p), ("ctrl", C.c_void_p), ("hist", C.c_void_p),
                    ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("partials_c", C.c_void_p),
                    ("k", C.c_double), ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)]
-                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)])
+                + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)]
+                + [("pre_fdm", C.c_void_p)])
 
 
 class Bpcg1Loop(FusedLoop):

@@ -164,6 +164,11 @@ def _signatures():
         "nss_fdmc_destroy": (C.c_int, [vp]),
         "nss_fdmc_solve_f64": (C.c_int, [vp, dbl, vp, vp, vp]),
         "nss_fdmc_pass_f64": (C.c_int, [vp, i32, i32, i32, dbl, vp, vp, vp]),
+        "nss_fdmi_create": (C.c_int, [i32, i32, i64, c_i64_p, i64, c_i64_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+        "nss_fdmi_destroy": (C.c_int, [vp]),
+        "nss_fdmi_apply_f64": (C.c_int, [vp, dbl, vp, vp, vp, vp]),
+        "nss_fdmi_contract_f64": (C.c_int, [i64, i64, i32, i32, vp, i32, vp, vp, vp, vp]),
+        "nss_fdmi_set_tile": (C.c_int, [vp, i32]),
         "nss_heat_workspace": (C.c_int, [i64, i32, c_i64_p]),
         "nss_mgs_f64": (C.c_int, [i64, i32, i64, vp, i32, vp, vp, i64, vp]),
         "nss_galerkin_f64": (C.c_int, [vp, i32, i64, vp, vp, vp, i64, vp]),

@@ -998,13 +998,16 @@ class Projector(BaseMatrix):
 _WARNED = {}
 
 
-def Preconditioner(form, kind, blocks=None, storage="fp64", **_):
+def Preconditioner(form, kind, blocks=None, storage="fp64", components=None, **_):
     """``Preconditioner(blf, 'local')`` -> point Jacobi; ``'blockjacobi'`` -> additive block Jacobi
     over `blocks`; ``'h1amg'`` / ``'multigrid'`` -> the smoothed-aggregation V-cycle on the assembled
     matrix (`hipla.amg`).  ``'bddc'`` (stokes_hcurldiv.py:48, templates/...iterative.py:77,88,122,306)
     is NGSolve's domain-decomposition preconditioner built on its FE spaces; it has no algebraic
     counterpart here, and the same V-cycle is returned in its place -- a mesh-independent SPD
     preconditioner for the same operator, with different iteration counts than the reference's.
+    ``'fdm'`` -> the exact inverse by fast diagonalisation over `components` (the id arrays of
+    `StokesSystem.component_ids`): `hipla.FastDiagonalizationInverse`, ``ValueError`` with the reason when the
+    matrix does not factor.
 
     `storage` ("fp64" | "fp32"): the value storage of the V-cycle's matrices (`SmoothedAggregationAMG`); the point and
     block Jacobi preconditioners store no matrix of their own and take "fp64" only."""
@@ -1012,6 +1015,11 @@ def Preconditioner(form, kind, blocks=None, storage="fp64", **_):
     mat = form.mat if hasattr(form, "mat") else form
     if storage != "fp64" and kind not in ("h1amg", "multigrid", "bddc"):
         raise ValueError("Preconditioner(..., %r): storage='fp32' exists for the AMG kinds only" % (kind,))
+    if kind == "fdm":
+        if components is None:
+            raise ValueError("Preconditioner(..., 'fdm') needs components=")
+        from .fdm import FastDiagonalizationInverse
+        return FastDiagonalizationInverse(mat, components)
     if kind == "local":
         if blocks is not None:
             return BlockJacobi(mat, blocks)

@@ -509,7 +509,7 @@ class NavierStokes:
         return out
 
     def SolveInitial(self, timesteps=None, iterative=True, GS=True, tol=1e-10, maxsteps=100000, printrates=False,
-                     aux=True, amg=False, condense=False, pre_storage="fp64"):
+                     aux=True, amg=False, condense=False, pre_storage="fp64", pre="mypre_a"):
         """`aux`: build the auxiliary-space term of MypreA (:208-357) -- the reference always does; False
         keeps the block smoother alone.  `amg=True` (kept from round 1) puts a smoothed-aggregation
         V-cycle on a.mat itself in the place of the auxiliary term.  `condense=True` solves as the reference's
@@ -517,7 +517,17 @@ class NavierStokes:
         sweeps over its Schur complement with blocks of coupling dofs only (:360-362), and BramblePasciakCG runs
         the condensed branch of harmonic_extension.  `pre_storage="fp32"` stores the matrices of MypreA (the
         Gauss-Seidel sweep, the auxiliary-space term or the V-cycle) with fp32 values; vectors, arithmetic and the
-        Krylov operator stay fp64."""
+        Krylov operator stay fp64.
+
+        `pre`: the velocity preconditioner.  "mypre_a" (the default) is the reference's MypreA as described above.
+        "fdm" takes the exact inverse of a.mat by fast diagonalisation (`hipla.FastDiagonalizationInverse` over
+        `system.component_ids`) in its place: no hierarchy, colouring or permutation is built, and
+        the iteration works on the pressure Schur complement alone (about 20 to 30 iterations whatever the grid).
+        ``ValueError`` with the reason for a system that does not factor (an inflated one, `order` > 0, or a permuted
+        one), and for `condense=True`, `amg=True` or `pre_storage="fp32"`, which have no meaning for it.  `GS` and `aux`
+        shape MypreA alone: with "fdm" they have no effect."""
+        if pre not in ("mypre_a", "fdm"):
+            raise ValueError("SolveInitial: pre is \"mypre_a\" or \"fdm\", not %r" % (pre,))
         if timesteps:                                     # pseudo time stepping to the Stokes state (:406-417)
             ops = self._time_stepping_operators()
             self.Project(self.gfu)
@@ -529,6 +539,8 @@ class NavierStokes:
             raise NotImplementedError("sparse direct initial solve is not on the Krylov path")
         if condense and amg:
             raise ValueError("SolveInitial: amg=True (a V-cycle on a.mat) does not combine with condense=True")
+        if pre == "fdm":
+            return self._solve_initial_fdm(tol, maxsteps, printrates, amg, condense, pre_storage)
         blocks = self.system.facet_blocks()
         if condense:
             blfA = CondensedForm(self.system)
@@ -549,6 +561,27 @@ class NavierStokes:
         if isinstance(out, tuple):
             self.stokes_bpcg_iterations, self.stokes_bpcg_time = out
         else:                                          # zero initial residual: bare vector (:191-192)
+            self.stokes_bpcg_iterations, self.stokes_bpcg_time = 0, 0.0
+
+    def _solve_initial_fdm(self, tol, maxsteps, printrates, amg, condense, pre_storage):
+        """`SolveInitial(pre="fdm")`: BramblePasciakCG with the exact inverse of a.mat as preA and the Jacobi preM."""
+        for given, name, why in ((condense, "condense=True", "the condensed Schur complement is no Kronecker sum"),
+                                 (amg, "amg=True", "there is no term to put a V-cycle in"),
+                                 (pre_storage != "fp64", "pre_storage=\"fp32\"", "the factors are stored in fp64")):
+            if given:
+                raise ValueError("SolveInitial(pre=\"fdm\"): %s does not combine with it (%s)" % (name, why))
+        preA = hipla.FastDiagonalizationInverse.try_create(self.a.mat, self.system.component_ids)
+        if preA is None:
+            raise ValueError("SolveInitial(pre=\"fdm\"): " + hipla.FastDiagonalizationInverse.last_declined)
+        self.preA = preA
+        preM = hipla.Preconditioner(self.mp, "local")
+        sol = BlockVector([self.gfu, self.gfup])
+        out = BramblePasciakCG(AssembledForm(self.a.mat), AssembledForm(self.b.mat), None, self.f.vec, self.g.vec, preA,
+                               preM, sol, initialize=False, tol=tol, maxsteps=maxsteps, rel_err=True,
+                               printrates=printrates)
+        if isinstance(out, tuple):
+            self.stokes_bpcg_iterations, self.stokes_bpcg_time = out
+        else:
             self.stokes_bpcg_iterations, self.stokes_bpcg_time = 0, 0.0
 
     def _pseudo_time_step(self, ops):
