@@ -206,16 +206,29 @@ NSS_API int nss_csr_plan_for_blocks(nss_csr_t a, nss_bjac_t j, int32_t* planned)
 NSS_API int nss_csr_plan_for_pairs(nss_csr_t a, int32_t* pair_staged);
 /* Row slots: a matrix that is coded (nss_csr_code_values, codes in force), staged (form 2), one lane per row, without
  * fp32 values or a dispatch-ordered table, and whose rows hold at most 8 entries can keep an eight-slot copy of itself
- * -- per row one 16-byte word of staged positions and one 8-byte word of codes, 24 bytes per row of extra device memory
- * beside the CSR arrays, which every other launch site keeps reading.  Two launch sites then take a row-per-lane
+ * -- per row one 16-byte and one 4-byte word that hold eight 11-bit staged positions, the row length and the eight
+ * codes (csrc/packed_rows.h), 20 bytes per row of extra device memory beside the CSR arrays, which every other launch
+ * site keeps reading.  Two launch sites then take a row-per-lane
  * kernel that holds a row's products in registers (csrc/csr_stream.h: csr_slots_kernel): nss_csr_spmv_f64 and C23 of
  * nss_bpcg2_iterate (when both A and B hold a copy).  Identical bits to the stream kernel.  The copy belongs to ONE launch
  * plan: every re-plan drops it, and a writer of the values drops it with the codes.  Set-up only (synchronises the device).
  * mode 1: build wherever the matrix is eligible; -1: build where the codes are there by their size rule (automatic
  * nss_csr_value_code_mode and at least 2^19 rows: the regime that is bound by bytes), leave alone a copy that exists
- * and a handle that was refused; 0: drop the copy and refuse later -1 calls (until a call with mode 1); 2: only ask.
+ * and a handle that was refused; 0: drop the copy and refuse later -1 calls (until a call with mode 1); 2: only ask;
+ * 3 (tests, measurements): as 1, but 24-byte rows -- eight 16-bit positions and eight codes -- for the same kernels
+ * and the same bits; C23 takes the row-slot kernels only when A and B hold the same layout.
  * *valid = whether a copy for the current launch plan exists that the kernels take now. */
 NSS_API int nss_csr_plan_row_slots(nss_csr_t a, int32_t mode, int32_t* valid);
+/* 16-bit columns of the coded fixed-width copy (form 3 with value codes: B^T of the staggered grid).  Where every row
+ * block's live columns span at most 65534, the matrix also holds one 32-bit word per row -- both columns as 16-bit
+ * offsets from the row block's smallest live column, 0xffff in a padding slot -- and a base per row block, and the
+ * coded row-per-lane kernel of nss_csr_spmv_f64 and of C1 of nss_bpcg2_iterate streams 6 bytes per row instead of 10.
+ * Same products, same bits.  Built with the codes (all or nothing per matrix) and rebuilt by every re-plan; the 32-bit
+ * columns stay for every other reader.  Set-up only (synchronises the device).  mode 0: drop them and refuse later
+ * builds; 1: build (again) where the matrix admits them; 2: only ask.  *narrow = whether the kernels take them now. */
+NSS_API int nss_csr_narrow_direct_columns(nss_csr_t a, int32_t mode, int32_t* narrow);
+/* bytes per row the row-slot kernels stream from the copy of `a`: 20, 24, or 0 without a copy they take now */
+NSS_API int nss_csr_row_slot_bytes(nss_csr_t a, int32_t* bytes);
 /* Launch-plan generation of `a`: 0 for the plan made at upload; every re-plan (the two calls above, and the joint
  * cycle of nss_amg_create_auxiliary over the matrices of its hierarchies) takes a fresh, larger value from one
  * process-wide counter.  A re-plan changes the row-block count, hence the dot partials every fused loop writes: each
@@ -464,6 +477,11 @@ typedef struct nss_bpcg2_s {
    * w1_g and t3_g with the rows of B in C23 (ghost rows add nothing to the dot partials), w0_g and w1_g in C4.
    * 0: the eight-phase layout described above. */
   int32_t dist_compact;
+  /* != 0: every entry of minv has the 64-bit pattern of minv[0] (the lumped mass of a uniform grid), and C4 of the
+   * single-GPU plans takes that one value (a scalar load) instead of streaming minv -- the same product, the same bits.
+   * Set by nss_bpcg2_uniform_diagonal only, valid while the entries of minv stay as they were; 0: minv is streamed.
+   * Row-partitioned states stream minv and ghost_minv.  (The field fills what was padding: no other offset moves.) */
+  int32_t minv_uniform;
   /* row-partitioned runs: the auxiliary-space term of MypreA on slabs (nss_dist_aux_create), alone, added to a (block)
    * Jacobi part (additive MypreA, :383) or -- pre_bjac in Gauss-Seidel mode -- inside the multiplicative MypreA
    * (:376-381) whose sweeps run inside the slab (additive across slabs) and whose residual uses the partitioned A;
@@ -494,6 +512,11 @@ typedef struct nss_bpcg2_s {
    * the same operators applied one by one. */
   nss_csr_t sweep_A;
 } nss_bpcg2_t;
+/* Decide whether all n_p entries of s->minv have one 64-bit pattern (so -0.0 and +0.0 differ, and one ulp differs) and
+ * record the answer in s->minv_uniform: one launch, the result read once (synchronises the stream).
+ * To be called where the loop takes minv -- once per solve, again whenever the entries may have changed.  mode 0: clear
+ * the field without looking (minv is streamed). */
+NSS_API int nss_bpcg2_uniform_diagonal(nss_bpcg2_t* s, int32_t mode, nss_stream_t stream);
 /* Which form the condensed multiplicative preconditioner step of K1 takes (process-wide; hipla reads NSS_COND_FUSE
  * at load).  1: the FUSED forms whenever pre_bjac carries this state's condensed operators
  * (nss_bjac_set_condensed) -- lift into the sweep's gather over P H^T, residual over P S P^T in the permuted numbering

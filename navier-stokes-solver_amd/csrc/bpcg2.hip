@@ -339,7 +339,11 @@ struct K4Args {
 // 5.5 TB/s for <= 2048 striding workgroups).
 constexpr int kK4PerBlock = 2 * kBlock;
 
-template <bool VEC2, bool FOLD, bool NT>
+// UNIF: the lumped-mass diagonal is one double in every entry (a uniform grid; nss_bpcg2_t::minv_uniform) and comes as
+// one value -- minv[0] through a scalar load (constant address space: no vector-memory request, nothing for hipcc to
+// wait for) --: the pressure lanes do not request minv.  A template parameter -- a run-time `uniform ? value : load` is
+// a branch around a load, which hipcc closes with a wait.  Same product minv * t3, same fma: same bits.
+template <bool VEC2, bool FOLD, bool NT, bool UNIF = false>
 __global__ __launch_bounds__(kBlock) void bpcg2_k4_kernel(K4Args a) {
   __shared__ double lds[kRedDoubles];
   if (a.ctrl[C_DONE] != 0) return;
@@ -347,6 +351,8 @@ __global__ __launch_bounds__(kBlock) void bpcg2_k4_kernel(K4Args a) {
   const int wg0 = blockIdx.x;
   const int e0 = ((wg0 < a.gu ? wg0 : wg0 - a.gu) * kBlock + int(threadIdx.x)) * 2;
   double2 q0{}, q1{}, q2{}, q3{}, q4{}, q5{};
+  double minv_value = 0.0;
+  if constexpr (UNIF) minv_value = ((const double __attribute__((address_space(4)))*)a.minv)[0];
   const bool vec_u = VEC2 && wg0 < a.gu && e0 + 1 < a.n_u;
   const bool vec_p = VEC2 && wg0 >= a.gu && wg0 < a.gu + a.gp && e0 + 1 < a.n_p;
   // NT: streaming loads for everything that is dead or rewritten after this kernel (t0, t1, t3, d, u1) or next
@@ -360,7 +366,8 @@ __global__ __launch_bounds__(kBlock) void bpcg2_k4_kernel(K4Args a) {
   } else if (vec_p) {
     q0 = ld2(a.s1 + e0);
     q1 = ld2s<NT>(a.t3 + e0);
-    q2 = ld2s<NT>(a.minv + e0);
+    if constexpr (UNIF) q2 = double2{minv_value, minv_value};
+    else q2 = ld2s<NT>(a.minv + e0);
     q3 = ld2s<NT>(a.u1 + e0);
     q4 = ld2s<NT>(a.d1 + e0);
     q5 = ld2(a.w1 + e0);
@@ -433,7 +440,8 @@ __global__ __launch_bounds__(kBlock) void bpcg2_k4_kernel(K4Args a) {
         const double sv = a.s1[i], t3v = a.t3[i];
         a.u1[i] = fma(alpha, sv, a.u1[i]);
         const double dn = fma(-alpha, t3v, a.d1[i]);
-        const double wn = fma(-alpha, a.minv[i] * t3v, a.w1[i]);
+        const double mv = UNIF ? minv_value : a.minv[i];
+        const double wn = fma(-alpha, mv * t3v, a.w1[i]);
         a.d1[i] = dn;
         a.w1[i] = wn;
         acc = fma(wn, dn, acc);
@@ -777,7 +785,13 @@ static void launch_k4(const nss_bpcg2_t& s, int it, bool fold, hipStream_t st) {
                         (const void*)s.minv})
     vec = vec && aligned16(p);
   const bool nt = vec && stream_vector_loads(s.n_u);
-  if (vec && fold && nt) hipLaunchKernelGGL((bpcg2_k4_kernel<true, true, true>), dim3(grid), dim3(kBlock), 0, st, a);
+  // the diagonal by value: the single-GPU compact plan (the ghost rows of the slab plans keep ghost_minv)
+  const bool unif = vec && s.minv_uniform != 0 && !s.ghost_mode && !s.ghost_p_mode && !s.local_sums && !s.dist_compact;
+  if (unif && fold && nt) hipLaunchKernelGGL((bpcg2_k4_kernel<true, true, true, true>), dim3(grid), dim3(kBlock), 0, st, a);
+  else if (unif && fold) hipLaunchKernelGGL((bpcg2_k4_kernel<true, true, false, true>), dim3(grid), dim3(kBlock), 0, st, a);
+  else if (unif && nt) hipLaunchKernelGGL((bpcg2_k4_kernel<true, false, true, true>), dim3(grid), dim3(kBlock), 0, st, a);
+  else if (unif) hipLaunchKernelGGL((bpcg2_k4_kernel<true, false, false, true>), dim3(grid), dim3(kBlock), 0, st, a);
+  else if (vec && fold && nt) hipLaunchKernelGGL((bpcg2_k4_kernel<true, true, true>), dim3(grid), dim3(kBlock), 0, st, a);
   else if (vec && fold) hipLaunchKernelGGL((bpcg2_k4_kernel<true, true, false>), dim3(grid), dim3(kBlock), 0, st, a);
   else if (vec && nt) hipLaunchKernelGGL((bpcg2_k4_kernel<true, false, true>), dim3(grid), dim3(kBlock), 0, st, a);
   else if (vec) hipLaunchKernelGGL((bpcg2_k4_kernel<true, false, false>), dim3(grid), dim3(kBlock), 0, st, a);
@@ -1057,8 +1071,8 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
       const bool fj = c1_applies_block_jacobi(s);
       const nss_bjac_s* J = s.pre_bjac;
       const size_t lds = fj ? sizeof(double) * kBlockRows : 0;
-#define NSS_C1(FOLD, NT, IT0, LAUNCH)                                                                                  \
-  LAUNCH<kCodes>(*s.BT, s.s1, EpiK1c<FOLD, NT, IT0>{close_args(s, FOLD), s.u0, s.q, s.z0, s.t2, s.s0, s.w0, s.t0, s.t1, dinv, s.k, it, \
+#define NSS_C1(FOLD, NT, IT0, LAUNCH, FORMS)                                                                                  \
+  LAUNCH<FORMS>(*s.BT, s.s1, EpiK1c<FOLD, NT, IT0>{close_args(s, FOLD), s.u0, s.q, s.z0, s.t2, s.s0, s.w0, s.t0, s.t1, dinv, s.k, it, \
                                        s.s1, s.w1, s.dist_compact ? s.ghost_n : 0, s.ghost_s0, s.ghost_w0,                 \
                                        fj ? s.BT->jb_first : nullptr, fj ? s.BT->jb_order : nullptr, fj ? J->run : nullptr, fj ? J->inv_sym : nullptr,   \
                                        fj ? J->nblocks : 0, fj ? J->bs : 0}, st, 0, -1, lds)
@@ -1066,17 +1080,17 @@ void bpcg2_cphase(const nss_bpcg2_t& s, int which, int it, hipStream_t st, const
       if (s.BT->ell_col) {     // the row-per-lane kernel, with "iteration 0" as a template argument (EpiK1c)
         const int sel = (fold ? 4 : 0) + (nt ? 2 : 0) + (it == 0 ? 1 : 0);
         switch (sel) {
-          case 0: NSS_C1(false, false, 0, launch_csr_direct); break;
-          case 1: NSS_C1(false, false, 1, launch_csr_direct); break;
-          case 2: NSS_C1(false, true, 0, launch_csr_direct); break;
-          case 3: NSS_C1(false, true, 1, launch_csr_direct); break;
-          case 4: NSS_C1(true, false, 0, launch_csr_direct); break;
-          case 5: NSS_C1(true, false, 1, launch_csr_direct); break;
-          case 6: NSS_C1(true, true, 0, launch_csr_direct); break;
-          default: NSS_C1(true, true, 1, launch_csr_direct); break;
+          case 0: NSS_C1(false, false, 0, launch_csr_direct, kCodes | kCol16); break;
+          case 1: NSS_C1(false, false, 1, launch_csr_direct, kCodes | kCol16); break;
+          case 2: NSS_C1(false, true, 0, launch_csr_direct, kCodes | kCol16); break;
+          case 3: NSS_C1(false, true, 1, launch_csr_direct, kCodes | kCol16); break;
+          case 4: NSS_C1(true, false, 0, launch_csr_direct, kCodes | kCol16); break;
+          case 5: NSS_C1(true, false, 1, launch_csr_direct, kCodes | kCol16); break;
+          case 6: NSS_C1(true, true, 0, launch_csr_direct, kCodes | kCol16); break;
+          default: NSS_C1(true, true, 1, launch_csr_direct, kCodes | kCol16); break;
         }
-      } else if (fold) NSS_C1(true, false, -1, launch_csr);
-      else NSS_C1(false, false, -1, launch_csr);
+      } else if (fold) NSS_C1(true, false, -1, launch_csr, kCodes);
+      else NSS_C1(false, false, -1, launch_csr, kCodes);
 #undef NSS_C1
       if (!fj) bpcg2_k1_finish(s, st, d);
       break;
@@ -1189,6 +1203,36 @@ int nss_bpcg2_c23_form(const nss_bpcg2_t* s, int32_t* form) {
     if (c23_row_slots(*s)) *form = 1;
     else *form = csr_dual_forms(*s->A, *s->B, EpiX<EpiK2c>::type::kStageable, EpiX<EpiK3c>::type::kStageable,
                                 XPairable<EpiX<EpiK3c>::type>::value, &ma, &mb) ? 0 : 2;
+  });
+}
+
+// *differs (zero on entry) != 0 when some entry of x[0 .. n) has another 64-bit pattern than x[0]
+__global__ __launch_bounds__(kBlock) void uniform_pattern_kernel(int64_t n, const unsigned long long* __restrict__ x,
+                                                                  int32_t* __restrict__ differs) {
+  const unsigned long long first = x[0];
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  bool other = false;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) other = other || x[i] != first;
+  if (other) atomicOr(differs, 1);
+}
+
+int nss_bpcg2_uniform_diagonal(nss_bpcg2_t* s, int32_t mode, nss_stream_t stream) {
+  return guarded([&] {
+    NSS_REQUIRE(s != nullptr && mode >= 0 && mode <= 1, "bpcg2_uniform_diagonal: NULL state, or a mode other than 0 (off) and 1 (detect)");
+    s->minv_uniform = 0;
+    if (mode == 0 || s->n_p <= 0) return;
+    NSS_REQUIRE(s->minv != nullptr, "bpcg2_uniform_diagonal: NULL minv");
+    hipStream_t st = as_stream(stream);
+    DeviceBuffer<int32_t> differs;
+    int32_t h_differs = 1;
+    differs.alloc(1);
+    NSS_HIP(hipMemsetAsync(differs, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(uniform_pattern_kernel, dim3(stream_grid(s->n_p, kBlock * 4)), dim3(kBlock), 0, st, int64_t(s->n_p),
+                       reinterpret_cast<const unsigned long long*>(s->minv), differs.get());
+    NSS_CHECK_LAUNCH();
+    NSS_HIP(hipMemcpyAsync(&h_differs, differs, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    NSS_HIP(hipStreamSynchronize(st));
+    s->minv_uniform = h_differs == 0 ? 1 : 0;
   });
 }
 

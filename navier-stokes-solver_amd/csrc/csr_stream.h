@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "nss_common.h"
+#include "packed_rows.h"
 
 #include <initializer_list>
 #include <string>
@@ -72,7 +73,8 @@ constexpr int kDirectWidth = 2;        // entries per row of the fixed-width cop
 #endif
 constexpr int kDirectRows = NSS_DIRECT_ROWS_PER_LANE * 256;   // rows per row block of such a matrix
 constexpr int kSlotWidth = 8;          // entries per row of the row-slot copy (csr_slots_kernel)
-constexpr unsigned kSlotPad = 0xffffu; // staged position of an unused slot (real positions are below the chunk)
+constexpr unsigned kSlotPad = 0xffffu; // staged position of an unused slot in the 24-byte layout of the copy
+static_assert(kChunk <= int(kPackedPosLimit), "the packed row slots hold staged positions of 11 bits");
 // Staged operand (nss_csr_s::blkseg): per row block at most kSegMax runs of consecutive columns, together at
 // most `chunk` columns (the LDS copy shares the product buffer), copied to LDS by LDS-DMA ahead of the matrix
 // stream.
@@ -268,10 +270,22 @@ struct nss_csr_s {
   nss::DeviceBuffer<double> dict;
   nss::DeviceBuffer<uint16_t> ell_code;
   int32_t dict_count = 0;
+  // 16-bit columns of the coded fixed-width copy (built with ell_code when EVERY row block's live columns span at most
+  // 65534): ell_col16 holds one word per row, both columns as offsets from ell_base[b], the smallest live column of row
+  // block b (packed_rows.h).  The coded row-per-lane kernel then streams 6 bytes per row instead of 10; ell_col stays
+  // for every other reader.  Belongs to one launch plan (the bases are per row block) and goes with ell_col.
+  // ell16_state -1: refused by the caller (nss_csr_narrow_direct_columns), later builds leave the handle alone.
+  nss::DeviceBuffer<uint32_t> ell_col16;
+  nss::DeviceBuffer<int32_t> ell_base;
+  int ell16_state = 0;
+  bool direct_col16() const { return ell_col16 != nullptr && ell_base != nullptr && ell_code != nullptr && coded(); }
   // Row slots (nss_csr_plan_row_slots): the eight-slot copy of a coded, staged matrix whose rows hold at most
   // kSlotWidth entries, for the row-per-lane kernel of the staged operand (csr_slots_kernel).  Per row one aligned
-  // 16-byte word of kSlotWidth 16-bit staged positions (the values of pos16, CSR entry order, kSlotPad in unused slots)
-  // and one aligned 8-byte word of kSlotWidth value codes: 24 bytes per row where the CSR streams take 3 len + 4.  The
+  // 16-byte word in slot_pos and one 4-byte word in slot_code, together the packed row of packed_rows.h (slot_packed):
+  // eight 11-bit staged positions (the values of pos16, CSR entry order), the row length and the eight value codes, 20
+  // bytes per row where the CSR streams take 3 len + 4.  nss_csr_plan_row_slots(3) builds the copy in the 24-byte
+  // layout instead (measurements, tests): the 16-byte word holds eight 16-bit positions, kSlotPad in unused slots, and
+  // slot_code one 8-byte word of codes per row.  The
   // positions are relative to the operand runs of ONE launch plan: slot_gen is the plan generation the copy was built
   // for, replan() frees it, and a launcher takes it only through row_slots().  slot_state -1: refused by the caller
   // (mode 0), automatic requests leave the handle alone.
@@ -279,6 +293,7 @@ struct nss_csr_s {
   nss::DeviceBuffer<uint8_t> slot_code;
   int64_t slot_gen = -1;
   int slot_state = 0;
+  bool slot_packed = false;
   uint64_t jb_serial = 0;
   // the kernels with a coded form take it (the grouped column streams have none: nss_csr_code_values refuses such a
   // matrix, and one that a re-plan groups later reads `val` again and reports so)
@@ -788,15 +803,19 @@ struct EpiDirectPre<E, std::void_t<typename E::DirectPre>> {
 //  * the epilogue's prologue runs behind the front loads; its own reads should be scalar loads (EpiK1c);
 //  * coded form: the one wait and barrier that publish the dictionary stand behind the gathers, where every load of the
 //    workgroup is in flight.
+// C16 (coded form only; nss_csr_s::ell_col16): `ecol` holds one 32-bit word per row, the two columns as 16-bit offsets
+// from the row block's window base `cbase` (packed_rows.h) -- 6 bytes per row instead of 10.  The base is a scalar
+// load beside the row-block bounds; a padding slot gathers from the base column.
 // base_first: this call is the row block's first (it requests the dictionary and runs the prologue).
-template <bool FULL, class Epi, class VT>
+template <bool FULL, class Epi, class VT, bool C16>
 __device__ __forceinline__ bool csr_direct_rows(const CsrView& a, const int32_t* __restrict__ ecol,
                                                 const double* __restrict__ eval, const uint16_t* __restrict__ ecode,
                                                 const double* __restrict__ x, Epi& epi, int base, int r1, bool base_first,
-                                                double* red, double* dict) {
+                                                double* red, double* dict, int cbase) {
   using XOp = typename EpiX<Epi>::type;
   using Pre = EpiDirectPre<Epi>;
   constexpr bool kCoded = std::is_same<VT, Coded8>::value;
+  static_assert(!C16 || kCoded, "16-bit columns belong to the coded fixed-width copy");
   constexpr int kRows = kDirectRows / kBlock;
   typedef int32_t int2v __attribute__((ext_vector_type(2)));
   const int tid = threadIdx.x;
@@ -807,11 +826,15 @@ __device__ __forceinline__ bool csr_direct_rows(const CsrView& a, const int32_t*
     rl[q] = FULL ? r : (r < r1 ? r : r1 - 1);
   }
   int2v c[kRows];
+  uint32_t cw[kRows];
   dbl2v v[kRows];
   uint16_t code[kRows];
   typename Pre::type pre[kRows];
 #pragma unroll
-  for (int q = 0; q < kRows; ++q) c[q] = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(ecol) + rl[q]);
+  for (int q = 0; q < kRows; ++q) {
+    if constexpr (C16) cw[q] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(ecol) + rl[q]);
+    else c[q] = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(ecol) + rl[q]);
+  }
 #pragma unroll
   for (int q = 0; q < kRows; ++q) {
     if constexpr (kCoded) code[q] = __builtin_nontemporal_load(ecode + rl[q]);
@@ -827,8 +850,13 @@ __device__ __forceinline__ bool csr_direct_rows(const CsrView& a, const int32_t*
   double x0[kRows], x1[kRows];
 #pragma unroll
   for (int q = 0; q < kRows; ++q) {
-    x0[q] = xop(c[q].x >= 0 ? c[q].x : 0);
-    x1[q] = xop(c[q].y >= 0 ? c[q].y : 0);
+    if constexpr (C16) {
+      x0[q] = xop(col16_gather_column(cw[q], 0, cbase));
+      x1[q] = xop(col16_gather_column(cw[q], 1, cbase));
+    } else {
+      x0[q] = xop(c[q].x >= 0 ? c[q].x : 0);
+      x1[q] = xop(c[q].y >= 0 ? c[q].y : 0);
+    }
   }
   if constexpr (kCoded) {
     // the one barrier of the coded form: the dictionary's LDS-DMA is awaited by its waves and published, with
@@ -844,17 +872,23 @@ __device__ __forceinline__ bool csr_direct_rows(const CsrView& a, const int32_t*
     const int r = base + tid + q * kBlock;
     const double p0 = mul_unfused(v[q].x, x0[q]), p1 = mul_unfused(v[q].y, x1[q]);
     double sum = 0.0;
-    sum += c[q].x >= 0 ? p0 : 0.0;
-    sum += c[q].y >= 0 ? p1 : 0.0;
+    if constexpr (C16) {
+      sum += col16_live(cw[q], 0) ? p0 : 0.0;
+      sum += col16_live(cw[q], 1) ? p1 : 0.0;
+    } else {
+      sum += c[q].x >= 0 ? p0 : 0.0;
+      sum += c[q].y >= 0 ? p1 : 0.0;
+    }
     if (FULL || r < r1) Pre::row(epi, r, sum, pre[q]);
   }
   return true;
 }
 
-template <class Epi, class VT = double>
+template <class Epi, class VT = double, bool C16 = false>
 __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int32_t* __restrict__ ecol,
                                                             const double* __restrict__ eval,
                                                             const uint16_t* __restrict__ ecode,
+                                                            const int32_t* __restrict__ ebase,
                                                             const double* __restrict__ x, Epi epi) {
   static_assert(kDirectWidth == 2, "csr_direct_kernel is written for two slots per row");
   __shared__ double red[kRedDoubles];
@@ -866,15 +900,17 @@ __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int
   if (b >= 0) {
     const ConstI32 rb = (ConstI32)(a.rowblk + b);             // uniform, invariant: scalar loads
     const int r0 = rb[0], r1 = rb[1];
+    int cbase = 0;                                            // window base of the 16-bit columns: a scalar load too
+    if constexpr (C16) cbase = ((ConstI32)(ebase + b))[0];
     bool go = true;
     if (r1 - r0 == kDirectRows) {
-      go = csr_direct_rows<true, Epi, VT>(a, ecol, eval, ecode, x, epi, r0, r1, true, red, dict);
+      go = csr_direct_rows<true, Epi, VT, C16>(a, ecol, eval, ecode, x, epi, r0, r1, true, red, dict, cbase);
     } else if (r1 - r0 < kDirectRows) {
-      if (r1 > r0) go = csr_direct_rows<false, Epi, VT>(a, ecol, eval, ecode, x, epi, r0, r1, true, red, dict);
+      if (r1 > r0) go = csr_direct_rows<false, Epi, VT, C16>(a, ecol, eval, ecode, x, epi, r0, r1, true, red, dict, cbase);
     } else {
       // (the plan caps the row blocks of such a matrix at kDirectRows rows; a longer one is walked in pieces)
       for (int base = r0; go && base < r1; base += kDirectRows)
-        go = csr_direct_rows<false, Epi, VT>(a, ecol, eval, ecode, x, epi, base, r1, base == r0, red, dict);
+        go = csr_direct_rows<false, Epi, VT, C16>(a, ecol, eval, ecode, x, epi, base, r1, base == r0, red, dict, cbase);
     }
     if (!go) return;                                          // the prologue ended the workgroup (uniform)
   }
@@ -887,30 +923,40 @@ __global__ __launch_bounds__(kBlock) void csr_direct_kernel(CsrView a, const int
 // a dependent per-row LDS loop -- is built for rows of 82 entries.  Here lane t takes rows r0 + t, r0 + t + 256, ...
 // one piece of 256 rows after the other (the stream kernel's lane -> row map at one lane per row, so `acc` and the
 // block partial are its too), holds the row's eight staged positions and codes in registers (one 16-byte and one
-// 8-byte load), and makes THREE dependent memory rounds: (1) descriptor, LDS-DMA of the operand runs, slot words,
+// 4-byte load of the packed row, packed_rows.h: 20 bytes; PK false: 16 + 8 bytes, the layout the form was introduced
+// with, kept for tests and measurements), and makes THREE dependent memory rounds: (1) descriptor, LDS-DMA of the operand runs, slot words,
 // epilogue operands, dictionary; (2) one wait + one barrier, eight LDS reads of the operand, eight of the dictionary;
 // (3) the stores.  Straight-line from the first load to the last product, as csr_direct_rows: one uniform branch between
-// full and partial pieces, partial ones load from a clamped valid row and predicate only row(); a padding slot reads
-// LDS position 0 and its product is discarded by a select.
+// full and partial pieces, partial ones load from a clamped valid row and predicate only row(); a padding slot (k at or
+// behind the row length; PK false: position kSlotPad) reads LDS position 0 and its product is discarded by a select.
+// The packed words are unpacked behind the barrier, where the wave has them anyway.
 // Bits: the stream kernel adds prod[s] ... prod[e - 1] in order to 0.0, each a product rounded by its store; here the
 // products are rounded by mul_unfused and added in slot order, + 0.0 for an unused slot -- 0 + p is never -0, so
 // s + 0.0 == s for every partial sum.
 // LDS: the operand copy (CH doubles), the dictionary, `red`; no product buffer, no window table.
 typedef uint32_t uint4v __attribute__((ext_vector_type(4)));
 typedef uint32_t uint2v __attribute__((ext_vector_type(2)));
+// the second word of a row: the eight codes (8 bytes), or, PK, the last word of the packed row (packed_rows.h)
+template <bool PK>
+struct SlotTail { using type = uint2v; };
+template <>
+struct SlotTail<true> { using type = uint32_t; };
 
-template <bool FULL, class Epi, int IDX, int CH>
+template <bool FULL, bool PK, class Epi, int IDX, int CH>
 __device__ __forceinline__ bool csr_slots_rows(const CsrView& a, const uint4v* __restrict__ spos,
-                                               const uint2v* __restrict__ scode, const double* __restrict__ x, Epi& epi,
+                                               const typename SlotTail<PK>::type* __restrict__ scode,
+                                               const double* __restrict__ x, Epi& epi,
                                                int base, int r1, bool base_first, const double* xlds, double* red,
                                                double* dict) {
   using XOp = typename EpiX<Epi>::type;
   using Pre = EpiPre<Epi>;
   static_assert(kSlotWidth == 8, "csr_slots_rows is written for eight slots per row");
+  static_assert(!PK || (kSlotWidth == kPackedSlots && CH <= int(kPackedPosLimit)),
+                "a staged position must fit the 11 bits of the packed row words");
   const int r = base + int(threadIdx.x);
   const int rl = FULL ? r : (r < r1 ? r : r1 - 1);            // the row every load goes to
   const uint4v pw = __builtin_nontemporal_load(spos + rl);
-  const uint2v cw = __builtin_nontemporal_load(scode + rl);
+  const typename SlotTail<PK>::type cw = __builtin_nontemporal_load(scode + rl);
   const typename Pre::type pre = Pre::fetch(epi, rl);
   // behind the rows' loads (csr_direct_rows: in front, every wave waits for the two requesting waves' branch)
   if (base_first) DictLds<Coded8>::request(a, dict);
@@ -919,18 +965,35 @@ __device__ __forceinline__ bool csr_slots_rows(const CsrView& a, const uint4v* _
   // the one wait and barrier: the LDS-DMA copies (operand runs, dictionary) are awaited by their waves and published
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  const uint32_t w[4] = {pw.x, pw.y, pw.z, pw.w};
-  const uint32_t cws[2] = {cw.x, cw.y};
   bool live[kSlotWidth];
+  int q[kSlotWidth];
+  uint32_t code[kSlotWidth];
+  if constexpr (PK) {
+    const uint32_t u[5] = {pw.x, pw.y, pw.z, pw.w, cw};
+    const uint32_t len = packed_slot_len(u);
+#pragma unroll
+    for (int k = 0; k < kSlotWidth; ++k) {
+      live[k] = uint32_t(k) < len;
+      q[k] = int(packed_slot_pos(u, k));                      // (0 in an unused slot)
+      code[k] = packed_slot_code(u, k);
+    }
+  } else {
+    const uint32_t w[4] = {pw.x, pw.y, pw.z, pw.w};
+    const uint32_t cws[2] = {cw.x, cw.y};
+#pragma unroll
+    for (int k = 0; k < kSlotWidth; ++k) {
+      const uint32_t p = (w[k / 2] >> (16 * (k % 2))) & 0xffffu;
+      live[k] = p != kSlotPad;
+      q[k] = live[k] ? int(p) : 0;
+      code[k] = (cws[k / 4] >> (8 * (k % 4))) & 0xffu;
+    }
+  }
   double xv[kSlotWidth], v[kSlotWidth];
 #pragma unroll
   for (int k = 0; k < kSlotWidth; ++k) {
-    const uint32_t p = (w[k / 2] >> (16 * (k % 2))) & 0xffffu;
-    live[k] = p != kSlotPad;
-    const int q = live[k] ? int(p) : 0;
-    if constexpr (IDX == 3) xv[k] = xop.pair(xlds[q], xlds[CH / 2 + q]);
-    else xv[k] = xop.value(xlds[q]);
-    v[k] = dict[(cws[k / 4] >> (8 * (k % 4))) & 0xffu];
+    if constexpr (IDX == 3) xv[k] = xop.pair(xlds[q[k]], xlds[CH / 2 + q[k]]);
+    else xv[k] = xop.value(xlds[q[k]]);
+    v[k] = dict[code[k]];
   }
   double sum = 0.0;
 #pragma unroll
@@ -943,9 +1006,10 @@ __device__ __forceinline__ bool csr_slots_rows(const CsrView& a, const uint4v* _
 }
 
 // one workgroup = one row block (`wg`: the workgroup's index inside this launch's grid part; the stream kernel's map)
-template <class Epi, int IDX, int CH>
+template <bool PK, class Epi, int IDX, int CH>
 __device__ __forceinline__ void csr_slots_body(const CsrView& a, const uint4v* __restrict__ spos,
-                                               const uint2v* __restrict__ scode, const double* __restrict__ x, Epi& epi,
+                                               const typename SlotTail<PK>::type* __restrict__ scode,
+                                               const double* __restrict__ x, Epi& epi,
                                                int wg, double* xlds, double* red, double* dict) {
   using XOp = typename EpiX<Epi>::type;
   static_assert(IDX == 2 || IDX == 3, "the row-slot kernel takes the staged forms only");
@@ -959,36 +1023,37 @@ __device__ __forceinline__ void csr_slots_body(const CsrView& a, const uint4v* _
     stage_operand_runs<Epi, IDX, CH>(d, total, epi, x, xlds);
     bool go = true;
     if (r1 - r0 == kBlock) {
-      go = csr_slots_rows<true, Epi, IDX, CH>(a, spos, scode, x, epi, r0, r1, true, xlds, red, dict);
+      go = csr_slots_rows<true, PK, Epi, IDX, CH>(a, spos, scode, x, epi, r0, r1, true, xlds, red, dict);
     } else if (r1 - r0 < kBlock) {
-      if (r1 > r0) go = csr_slots_rows<false, Epi, IDX, CH>(a, spos, scode, x, epi, r0, r1, true, xlds, red, dict);
+      if (r1 > r0) go = csr_slots_rows<false, PK, Epi, IDX, CH>(a, spos, scode, x, epi, r0, r1, true, xlds, red, dict);
     } else {
       // rows of few entries: a row block of up to kMaxRowsPerBlock rows is walked in pieces (the operand copy stays)
       for (int base = r0; go && base < r1; base += kBlock)
-        go = csr_slots_rows<false, Epi, IDX, CH>(a, spos, scode, x, epi, base, r1, base == r0, xlds, red, dict);
+        go = csr_slots_rows<false, PK, Epi, IDX, CH>(a, spos, scode, x, epi, base, r1, base == r0, xlds, red, dict);
     }
     if (!go) return;                                          // the prologue ended the workgroup (uniform)
   }
   epi.finish(b, red);  // one dot partial per row block, in the stream kernel's slot
 }
 
-template <class Epi, int IDX, int CH = kChunk>
+template <class Epi, int IDX, bool PK, int CH = kChunk>
 __global__ __launch_bounds__(kBlock) void csr_slots_kernel(CsrView a, const uint4v* __restrict__ spos,
-                                                           const uint2v* __restrict__ scode,
+                                                           const typename SlotTail<PK>::type* __restrict__ scode,
                                                            const double* __restrict__ x, Epi epi) {
   __shared__ alignas(16) double xlds[CH];
   __shared__ double red[kRedDoubles];
   double* const dict = DictLds<Coded8>::get();
   if (epi.skip()) return;
-  csr_slots_body<Epi, IDX, CH>(a, spos, scode, x, epi, int(blockIdx.x), xlds, red, dict);
+  csr_slots_body<PK, Epi, IDX, CH>(a, spos, scode, x, epi, int(blockIdx.x), xlds, red, dict);
 }
 
 // two matrices in one launch, the second one's workgroups first (csr_stream_dual_kernel)
-template <class EpiA, class EpiB, int IDXA, int IDXB, int CH = kChunk>
+template <class EpiA, class EpiB, int IDXA, int IDXB, bool PK, int CH = kChunk>
 __global__ __launch_bounds__(kBlock) void csr_slots_dual_kernel(CsrView a, CsrView b, const uint4v* __restrict__ apos,
-                                                                const uint2v* __restrict__ acode,
+                                                                const typename SlotTail<PK>::type* __restrict__ acode,
                                                                 const uint4v* __restrict__ bpos,
-                                                                const uint2v* __restrict__ bcode, int grid_a, int grid_b,
+                                                                const typename SlotTail<PK>::type* __restrict__ bcode,
+                                                                int grid_a, int grid_b,
                                                                 const double* __restrict__ xa,
                                                                 const double* __restrict__ xb, EpiA ea, EpiB eb) {
   __shared__ alignas(16) double xlds[CH];
@@ -1003,10 +1068,10 @@ __global__ __launch_bounds__(kBlock) void csr_slots_dual_kernel(CsrView a, CsrVi
 #endif
   if (first) {
     if (ea.skip()) return;
-    csr_slots_body<EpiA, IDXA, CH>(a, apos, acode, xa, ea, wg, xlds, red, dict);
+    csr_slots_body<PK, EpiA, IDXA, CH>(a, apos, acode, xa, ea, wg, xlds, red, dict);
   } else {
     if (eb.skip()) return;
-    csr_slots_body<EpiB, IDXB, CH>(b, bpos, bcode, xb, eb, wg, xlds, red, dict);
+    csr_slots_body<PK, EpiB, IDXB, CH>(b, bpos, bcode, xb, eb, wg, xlds, red, dict);
   }
 }
 
@@ -1016,7 +1081,9 @@ __global__ __launch_bounds__(kBlock) void csr_slots_dual_kernel(CsrView a, CsrVi
 // Gauss-Seidel sweep, the single-vector AMG cycle, the residual between the half-sweeps), kCodes only in the launches
 // of the flagship loop (C1, C23), both in the plain SpMV.  A matrix in a form its site did not ask for takes the fp64
 // path: a coded matrix reads `val`, a narrowed one is refused (view()).
-enum : unsigned { kF64 = 0, kF32 = 1, kCodes = 2 };
+// kCol16 (with kCodes): also the 16-bit-column form of the coded row-per-lane kernel (nss_csr_s::ell_col16) -- only C1 of
+// the flagship loop and the plain SpMV ask for it.
+enum : unsigned { kF64 = 0, kF32 = 1, kCodes = 2, kCol16 = 4 };
 
 template <int I>
 using Idx = std::integral_constant<int, I>;
@@ -1074,6 +1141,7 @@ template <unsigned FORMS = kF64, bool DIRECT_ONLY = false, class Epi>
 inline void launch_csr(const nss_csr_s& A, const double* x, const Epi& epi, hipStream_t st, int b0 = 0, int b1 = -1,
                        size_t dyn_lds = 0) {
   constexpr bool kF32Form = (FORMS & kF32) != 0 && !DIRECT_ONLY, kCodedForm = (FORMS & kCodes) != 0;
+  constexpr bool kCol16Form = kCodedForm && (FORMS & kCol16) != 0;
   using CodedVT = std::conditional_t<kCodedForm, Coded8, double>;     // (form not asked for: the fp64 kernels either way)
   if (b1 < 0) b1 = A.nblk;
   if (A.m == 0 || b1 <= b0) return;
@@ -1088,10 +1156,14 @@ inline void launch_csr(const nss_csr_s& A, const double* x, const Epi& epi, hipS
   if (A.ell_col) {
     const dim3 grid(nss_csr_s::grid(b1 - b0)), block(kBlock);
     const CsrView v = A.view(b0, b1, 0);
-    if (kCodedForm && A.coded() && A.ell_code)
-      hipLaunchKernelGGL((csr_direct_kernel<Epi, CodedVT>), grid, block, dyn_lds, st, v, A.ell_col, A.ell_val, A.ell_code, x, epi);
+    const int32_t* const none = nullptr;
+    if (kCol16Form && A.direct_col16())
+      hipLaunchKernelGGL((csr_direct_kernel<Epi, CodedVT, kCol16Form>), grid, block, dyn_lds, st, v,
+                         reinterpret_cast<const int32_t*>(A.ell_col16.get()), A.ell_val, A.ell_code, A.ell_base, x, epi);
+    else if (kCodedForm && A.coded() && A.ell_code)
+      hipLaunchKernelGGL((csr_direct_kernel<Epi, CodedVT>), grid, block, dyn_lds, st, v, A.ell_col, A.ell_val, A.ell_code, none, x, epi);
     else
-      hipLaunchKernelGGL((csr_direct_kernel<Epi>), grid, block, dyn_lds, st, v, A.ell_col, A.ell_val, (const uint16_t*)nullptr, x, epi);
+      hipLaunchKernelGGL((csr_direct_kernel<Epi>), grid, block, dyn_lds, st, v, A.ell_col, A.ell_val, (const uint16_t*)nullptr, none, x, epi);
     NSS_CHECK_LAUNCH();
   } else if constexpr (!DIRECT_ONLY) {
     if (kCodedForm && A.coded() && !A.val32) launch_csr_stream_kernel<CodedVT>(A, x, epi, st, b0, b1, dyn_lds);
@@ -1180,7 +1252,16 @@ inline bool takes_row_slots(const nss_csr_s& A) {
   return A.idx_mode(EpiX<Epi>::type::kStageable, XPairable<typename EpiX<Epi>::type>::value) == IDX;
 }
 inline const uint4v* slot_positions(const nss_csr_s& A) { return reinterpret_cast<const uint4v*>(A.slot_pos.get()); }
-inline const uint2v* slot_codes(const nss_csr_s& A) { return reinterpret_cast<const uint2v*>(A.slot_code.get()); }
+template <bool PK>
+inline const typename SlotTail<PK>::type* slot_codes(const nss_csr_s& A) {
+  return reinterpret_cast<const typename SlotTail<PK>::type*>(A.slot_code.get());
+}
+// f(bool_constant<PK>) for the layout of the copy
+template <class F>
+inline void for_slot_layout(bool packed, F&& f) {
+  if (packed) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 // A x into `epi` by the row-slot kernel; false (nothing launched) when A does not take it
 template <class Epi>
@@ -1189,8 +1270,11 @@ inline bool launch_csr_slots(const nss_csr_s& A, const double* x, const Epi& epi
   if constexpr (IDX == 0) return false;
   else {
     if (!takes_row_slots<Epi>(A)) return false;
-    hipLaunchKernelGGL((csr_slots_kernel<Epi, IDX>), dim3(nss_csr_s::grid(A.nblk)), dim3(kBlock), 0, st,
-                       A.view(0, A.nblk, IDX), slot_positions(A), slot_codes(A), x, epi);
+    for_slot_layout(A.slot_packed, [&](auto pk) {
+      constexpr bool PK = decltype(pk)::value;
+      hipLaunchKernelGGL((csr_slots_kernel<Epi, IDX, PK>), dim3(nss_csr_s::grid(A.nblk)), dim3(kBlock), 0, st,
+                         A.view(0, A.nblk, IDX), slot_positions(A), slot_codes<PK>(A), x, epi);
+    });
     NSS_CHECK_LAUNCH();
     return true;
   }
@@ -1204,13 +1288,17 @@ inline bool launch_csr_slots_dual(const nss_csr_s& A, const double* xa, const Ep
   if constexpr (IA == 0 || IB == 0) return false;
   else {
     if (!takes_row_slots<EpiA>(A) || !takes_row_slots<EpiB>(B)) return false;
+    if (A.slot_packed != B.slot_packed) return false;     // (one of the copies in the 24-byte layout: stream kernels)
 #ifdef NSS_NO_DUAL        // measurements: the two halves as launches of their own
     return launch_csr_slots(A, xa, ea, st) && launch_csr_slots(B, xb, eb, st);
 #else
     const int ga = nss_csr_s::grid(A.nblk), gb = nss_csr_s::grid(B.nblk);
-    hipLaunchKernelGGL((csr_slots_dual_kernel<EpiA, EpiB, IA, IB>), dim3(ga + gb), dim3(kBlock), 0, st,
-                       A.view(0, A.nblk, IA), B.view(0, B.nblk, IB), slot_positions(A), slot_codes(A), slot_positions(B),
-                       slot_codes(B), ga, gb, xa, xb, ea, eb);
+    for_slot_layout(A.slot_packed, [&](auto pk) {
+      constexpr bool PK = decltype(pk)::value;
+      hipLaunchKernelGGL((csr_slots_dual_kernel<EpiA, EpiB, IA, IB, PK>), dim3(ga + gb), dim3(kBlock), 0, st,
+                         A.view(0, A.nblk, IA), B.view(0, B.nblk, IB), slot_positions(A), slot_codes<PK>(A),
+                         slot_positions(B), slot_codes<PK>(B), ga, gb, xa, xb, ea, eb);
+    });
     NSS_CHECK_LAUNCH();
     return true;
 #endif

@@ -651,20 +651,90 @@ __global__ __launch_bounds__(kBlock) void ell_code_kernel(int32_t m, const int32
   }
 }
 
-// ell_code of a coded matrix that holds the fixed-width copy (built wherever that copy is built)
+// 16-bit columns of the fixed-width copy (nss_csr_s::ell_col16), one workgroup per row block: the window base -- the
+// smallest live column of the block, 0 without one -- to ebase[b], and every row's two columns as offsets from it
+// (packed_rows.h).  A block whose live columns span more than the window raises *wide (its words are not written).
+__global__ __launch_bounds__(kBlock) void ell_col16_kernel(int32_t nblk, const int32_t* __restrict__ rowblk,
+                                                            const int32_t* __restrict__ ecol, int32_t* __restrict__ ebase,
+                                                            uint32_t* __restrict__ ecol16, int32_t* __restrict__ wide) {
+  static_assert(kDirectWidth == 2, "two 16-bit columns per word");
+  __shared__ int32_t lo, hi;
+  for (int b = blockIdx.x; b < nblk; b += gridDim.x) {
+    const int r0 = rowblk[b], r1 = rowblk[b + 1];
+    if (threadIdx.x == 0) {
+      lo = INT32_MAX;
+      hi = -1;
+    }
+    __syncthreads();
+    for (int r = r0 + int(threadIdx.x); r < r1; r += kBlock)
+      for (int j = 0; j < kDirectWidth; ++j) {
+        const int32_t c = ecol[size_t(r) * kDirectWidth + j];
+        if (c >= 0) {
+          atomicMin(&lo, c);
+          atomicMax(&hi, c);
+        }
+      }
+    __syncthreads();
+    const int32_t base = col16_window_base(lo, hi);
+    const bool fits = col16_window_fits(lo, hi);
+    if (threadIdx.x == 0) {
+      ebase[b] = base;
+      if (!fits) atomicOr(wide, 1);
+    }
+    if (fits)
+      for (int r = r0 + int(threadIdx.x); r < r1; r += kBlock)
+        ecol16[r] = pack_col16_pair(ecol[size_t(r) * kDirectWidth], ecol[size_t(r) * kDirectWidth + 1], base);
+    __syncthreads();                                       // (lo, hi are reset for the next block)
+  }
+}
+
+static void drop_direct_col16(nss_csr_s& A) {
+  A.ell_col16.reset();
+  A.ell_base.reset();
+}
+
+// ell_col16 / ell_base of a coded matrix with the fixed-width copy, all or nothing: only when every row block fits the
+// window, and not for a handle whose caller refused them.  Synchronises the stream.
+static void build_direct_col16(nss_csr_s& A, hipStream_t st) {
+  drop_direct_col16(A);
+  if (!A.ell_code || !A.ell_col || A.nblk == 0 || A.ell16_state < 0) return;
+  DeviceBuffer<uint32_t> col16;
+  DeviceBuffer<int32_t> base, wide;
+  int32_t h_wide = 1;
+  col16.alloc(size_t(A.m));
+  base.alloc(size_t(A.nblk));
+  wide.alloc(1);
+  NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(ell_col16_kernel, dim3(std::min(A.nblk, 1 << 16)), dim3(kBlock), 0, st, A.nblk, A.rowblk, A.ell_col,
+                     base, col16, wide);
+  NSS_CHECK_LAUNCH();
+  NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  NSS_HIP(hipStreamSynchronize(st));
+  if (h_wide != 0) return;                               // some row block's window is too wide: the 32-bit columns stay
+  A.ell_col16 = std::move(col16);
+  A.ell_base = std::move(base);
+}
+
+// ell_code of a coded matrix that holds the fixed-width copy (built wherever that copy is built), and with it the 16-bit
+// columns where the matrix admits them
 static void build_ell_code(nss_csr_s& A, hipStream_t st) {
   A.ell_code.reset();
+  drop_direct_col16(A);
   if (!A.val8 || !A.ell_col || A.m == 0) return;
   A.ell_code.alloc(size_t(A.m));
   hipLaunchKernelGGL(ell_code_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.val8,
                      A.ell_code);
   NSS_CHECK_LAUNCH();
   NSS_HIP(hipStreamSynchronize(st));
+  build_direct_col16(A, st);
 }
 
 // ---- row slots (nss_csr_s::slot_pos) ---------------------------------------------------------------------------------
-// the two slot words of every row from the staged positions and the codes of its entries, in CSR order; unused slots:
-// position kSlotPad, code 0.  A row with more than kSlotWidth entries raises *wide (its words hold the first eight).
+// the two slot words of every row from the staged positions and the codes of its entries, in CSR order.  PK: the packed
+// row of packed_rows.h, four words to spos and the fifth to scode; else eight 16-bit positions and eight codes, unused
+// slots: position kSlotPad, code 0.  A row with more than kSlotWidth entries raises *wide (its words hold the first
+// eight; PK: nothing is written for a row that does not pack).
+template <bool PK>
 __global__ __launch_bounds__(kBlock) void slot_build_kernel(int32_t m, const int32_t* __restrict__ rowptr,
                                                              const uint16_t* __restrict__ pos16,
                                                              const uint8_t* __restrict__ val8, uint16_t* __restrict__ spos,
@@ -673,23 +743,40 @@ __global__ __launch_bounds__(kBlock) void slot_build_kernel(int32_t m, const int
   for (int64_t r = int64_t(blockIdx.x) * kBlock + threadIdx.x; r < m; r += stride) {
     const int s = rowptr[r], len = rowptr[r + 1] - s;
     if (len > kSlotWidth) atomicOr(wide, 1);
-    uint32_t pw[kSlotWidth / 2], cw[kSlotWidth / 4];
+    if constexpr (PK) {
+      uint32_t pos[kSlotWidth], code[kSlotWidth];
 #pragma unroll
-    for (int k = 0; k < kSlotWidth / 2; ++k) pw[k] = 0;
+      for (int k = 0; k < kSlotWidth; ++k) {
+        const bool has = k < len;
+        pos[k] = has ? uint32_t(pos16[s + k]) : 0u;
+        code[k] = has ? uint32_t(val8[s + k]) : 0u;
+      }
+      PackedSlotRow row;
+      if (pack_slot_row(len, pos, code, &row)) {
+        reinterpret_cast<uint4v*>(spos)[r] = uint4v{row.u[0], row.u[1], row.u[2], row.u[3]};
+        reinterpret_cast<uint32_t*>(scode)[r] = row.u[4];
+      } else {
+        atomicOr(wide, 1);
+      }
+    } else {
+      uint32_t pw[kSlotWidth / 2], cw[kSlotWidth / 4];
 #pragma unroll
-    for (int k = 0; k < kSlotWidth / 4; ++k) cw[k] = 0;
+      for (int k = 0; k < kSlotWidth / 2; ++k) pw[k] = 0;
 #pragma unroll
-    for (int k = 0; k < kSlotWidth; ++k) {
-      const bool has = k < len;
-      const uint32_t p = has ? uint32_t(pos16[s + k]) : kSlotPad;
-      const uint32_t c = has ? uint32_t(val8[s + k]) : 0u;
-      pw[k / 2] |= p << (16 * (k % 2));
-      cw[k / 4] |= c << (8 * (k % 4));
+      for (int k = 0; k < kSlotWidth / 4; ++k) cw[k] = 0;
+#pragma unroll
+      for (int k = 0; k < kSlotWidth; ++k) {
+        const bool has = k < len;
+        const uint32_t p = has ? uint32_t(pos16[s + k]) : kSlotPad;
+        const uint32_t c = has ? uint32_t(val8[s + k]) : 0u;
+        pw[k / 2] |= p << (16 * (k % 2));
+        cw[k / 4] |= c << (8 * (k % 4));
+      }
+      uint4v* const pout = reinterpret_cast<uint4v*>(spos) + r;
+      uint2v* const cout = reinterpret_cast<uint2v*>(scode) + r;
+      *pout = uint4v{pw[0], pw[1], pw[2], pw[3]};
+      *cout = uint2v{cw[0], cw[1]};
     }
-    uint4v* const pout = reinterpret_cast<uint4v*>(spos) + r;
-    uint2v* const cout = reinterpret_cast<uint2v*>(scode) + r;
-    *pout = uint4v{pw[0], pw[1], pw[2], pw[3]};
-    *cout = uint2v{cw[0], cw[1]};
   }
 }
 
@@ -705,9 +792,10 @@ static bool row_slots_candidate(const nss_csr_s& A) {
          A.nnz <= int64_t(kSlotWidth) * A.m;
 }
 
-// the copy for the current launch plan; false (and no copy) when the matrix is not eligible.  Synchronises the stream.
-static bool build_row_slots(nss_csr_s& A, hipStream_t st) {
-  if (A.slot_pos && A.slot_gen == A.plan_gen) return A.row_slots();
+// the copy for the current launch plan, in the packed 20-byte layout or the 24-byte one; false (and no copy) when the
+// matrix is not eligible.  Synchronises the stream.
+static bool build_row_slots(nss_csr_s& A, bool packed, hipStream_t st) {
+  if (A.slot_pos && A.slot_gen == A.plan_gen && A.slot_packed == packed) return A.row_slots();
   NSS_HIP(hipDeviceSynchronize());                       // (a stale copy goes: no kernel may still read it)
   drop_row_slots(A);
   if (!row_slots_candidate(A)) return false;
@@ -716,11 +804,14 @@ static bool build_row_slots(nss_csr_s& A, hipStream_t st) {
   DeviceBuffer<int32_t> wide;
   int32_t h_wide = 1;
   spos.alloc(kSlotWidth * size_t(A.m));
-  scode.alloc(size_t(kSlotWidth) * size_t(A.m));
+  scode.alloc((packed ? sizeof(uint32_t) : size_t(kSlotWidth)) * size_t(A.m));
   wide.alloc(1);
   NSS_HIP(hipMemsetAsync(wide, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(slot_build_kernel, dim3(stream_grid(A.m, kBlock * 4)), dim3(kBlock), 0, st, A.m, A.rowptr, A.pos16,
-                     A.val8, spos, scode, wide);
+  const dim3 grid(stream_grid(A.m, kBlock * 4));
+  if (packed)
+    hipLaunchKernelGGL(slot_build_kernel<true>, grid, dim3(kBlock), 0, st, A.m, A.rowptr, A.pos16, A.val8, spos, scode, wide);
+  else
+    hipLaunchKernelGGL(slot_build_kernel<false>, grid, dim3(kBlock), 0, st, A.m, A.rowptr, A.pos16, A.val8, spos, scode, wide);
   NSS_CHECK_LAUNCH();
   NSS_HIP(hipMemcpyAsync(&h_wide, wide, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   NSS_HIP(hipStreamSynchronize(st));
@@ -728,6 +819,7 @@ static bool build_row_slots(nss_csr_s& A, hipStream_t st) {
   A.slot_pos = std::move(spos);
   A.slot_code = std::move(scode);
   A.slot_gen = A.plan_gen;
+  A.slot_packed = packed;
   return A.row_slots();
 }
 
@@ -739,6 +831,7 @@ static void drop_value_codes(nss_csr_s& A) {
   A.val8.reset();
   A.dict.reset();
   A.ell_code.reset();
+  drop_direct_col16(A);
   A.dict_count = 0;
 }
 
@@ -937,6 +1030,7 @@ static void drop_plan_forms(nss_csr_s& A) {
   A.ell_col.reset();
   A.ell_val.reset();
   A.ell_code.reset();
+  drop_direct_col16(A);                                  // (window bases per row block of the plan that goes)
   A.jb_first.reset();                                    // a plan around Jacobi blocks ends with the plan
   A.jb_order.reset();
   A.jb_serial = 0;
@@ -1025,18 +1119,18 @@ int nss_csr_plan_for_pairs(nss_csr_t a, int32_t* pair_staged) {
 int nss_csr_plan_row_slots(nss_csr_t a, int32_t mode, int32_t* valid) {
   return guarded([&] {
     NSS_REQUIRE(a != nullptr, "csr_plan_row_slots: NULL matrix");
-    NSS_REQUIRE(mode >= -1 && mode <= 2, "csr_plan_row_slots: -1 (by the size rule of the value codes), 0 (drop and refuse), 1 (build) or 2 (ask)");
+    NSS_REQUIRE(mode >= -1 && mode <= 3, "csr_plan_row_slots: -1 (by the size rule of the value codes), 0 (drop and refuse), 1 (build), 2 (ask) or 3 (build 24-byte rows)");
     if (mode == 0) {
       if (a->slot_pos) NSS_HIP(hipDeviceSynchronize());  // no kernel may still read the arrays that go away
       drop_row_slots(*a);
       a->slot_state = -1;
-    } else if (mode == 1) {
+    } else if (mode == 1 || mode == 3) {
       a->slot_state = 0;
-      build_row_slots(*a, nullptr);
+      build_row_slots(*a, mode == 1, nullptr);
     } else if (mode == -1 && a->slot_state >= 0 && !a->row_slots()) {
       // automatic: where the codes are there by their size rule, not forced by the override -- the regime the form was
       // measured in (bound by bytes, not by launches)
-      if (g_value_code_mode < 0 && a->m >= int64_t(NSS_VALUE_CODES_MIN_ROWS)) build_row_slots(*a, nullptr);
+      if (g_value_code_mode < 0 && a->m >= int64_t(NSS_VALUE_CODES_MIN_ROWS)) build_row_slots(*a, true, nullptr);
     }
     if (valid) *valid = a->row_slots() ? 1 : 0;
   });
@@ -1115,6 +1209,29 @@ int nss_csr_dispatch_info(nss_csr_t a, double* period, int32_t* planes) {
   });
 }
 
+int nss_csr_narrow_direct_columns(nss_csr_t a, int32_t mode, int32_t* narrow) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr, "csr_narrow_direct_columns: NULL matrix");
+    NSS_REQUIRE(mode >= 0 && mode <= 2, "csr_narrow_direct_columns: 0 (drop and refuse), 1 (build) or 2 (ask)");
+    if (mode == 0) {
+      if (a->ell_col16) NSS_HIP(hipDeviceSynchronize());   // no kernel may still read the arrays that go away
+      drop_direct_col16(*a);
+      a->ell16_state = -1;
+    } else if (mode == 1) {
+      a->ell16_state = 0;
+      if (!a->ell_col16) build_direct_col16(*a, nullptr);
+    }
+    if (narrow) *narrow = a->direct_col16() ? 1 : 0;
+  });
+}
+
+int nss_csr_row_slot_bytes(nss_csr_t a, int32_t* bytes) {
+  return guarded([&] {
+    NSS_REQUIRE(a != nullptr && bytes != nullptr, "csr_row_slot_bytes: NULL argument");
+    *bytes = !a->row_slots() ? 0 : (a->slot_packed ? kPackedRowBytes : 3 * kSlotWidth);
+  });
+}
+
 int nss_csr_pair_mode(int32_t mode) {
   return guarded([&] {
     NSS_REQUIRE(mode >= -1 && mode <= 1, "csr_pair_mode: -1 (automatic), 0 (never) or 1");
@@ -1136,7 +1253,7 @@ int nss_csr_spmv_f64(nss_csr_t a, double alpha, const double* x, double beta, do
     // (the one user of EpiAxpby with a coded form; its other users keep reading `val`)
     const EpiAxpby epi{alpha, beta, y};
     if (launch_csr_slots(*a, x, epi, as_stream(stream))) return;       // (a valid row-slot copy: same bits)
-    launch_csr<kF32 | kCodes>(*a, x, epi, as_stream(stream));
+    launch_csr<kF32 | kCodes | kCol16>(*a, x, epi, as_stream(stream));
   });
 }
 
@@ -1183,9 +1300,9 @@ int nss_csr_info(nss_csr_t a, int32_t* nrows, int32_t* ncols, int64_t* nnz, int3
     // pointers, x once and y once.  (The CSR fp64/int32 textbook figure is 12 nnz + ...; pricing a
     // launch that streams 10 bytes per entry at 12 would overstate its bandwidth.)
     // A coded matrix (nss_csr_code_values) streams 1 byte per entry and the 2-KiB dictionary once per row block.
-    // A row-slot copy (nss_csr_plan_row_slots) does not change the figure: its 24 bytes per row stand for the 3 bytes
-    // per entry and 4 per row of the CSR streams, and at seven entries per row the two agree within 0.5 % (the Stokes
-    // blocks of the 1e7-DoF case: 240.2 against 241.3 MB over A and B), so the launch stays priced as the CSR stream.
+    // A row-slot copy (nss_csr_plan_row_slots) does not change the figure: the launch stays priced as the CSR stream,
+    // 3 bytes per entry and 4 per row (the Stokes blocks of the 1e7-DoF case: 241.3 MB over A and B).  What the copy
+    // really streams per row is nss_csr_row_slot_bytes: 20 (200.2 MB there), or 24 in the unpacked layout (240.2 MB).
     const bool coded = a->coded() && !a->val32;
     if (algorithmic_bytes && a->ell_col && coded && a->ell_code)   // 8 bytes of columns + one 16-bit code word per row
       *algorithmic_bytes = int64_t(4 * nss::kDirectWidth + 2) * a->m + int64_t(sizeof(double)) * kDictSize * a->nblk +

@@ -223,7 +223,8 @@ int nss_step_project_f64(nss_csr_t c, const double* phi, const double* raw, doub
     NSS_REQUIRE(partials == nullptr || cap >= c->nblk, "step_project: partials hold fewer entries than C has row blocks");
     const EpiStepProject epi{done, raw, out, u, mass, tau, partials};
     hipLaunchKernelGGL((csr_direct_kernel<EpiStepProject>), dim3(nss_csr_s::grid(c->nblk)), dim3(kBlock), 0,
-                       as_stream(stream), c->view(0, c->nblk, 0), c->fw_col, c->fw_val, (const uint16_t*)nullptr, phi, epi);
+                       as_stream(stream), c->view(0, c->nblk, 0), c->fw_col, c->fw_val, (const uint16_t*)nullptr,
+                       (const int32_t*)nullptr, phi, epi);
     NSS_CHECK_LAUNCH();
   });
 }

@@ -39,7 +39,7 @@ class Bpcg2State(C.Structure):
                    ("ghost_p_mode", C.c_int32), ("ghost_p_n", C.c_int32), ("ghost_b", C.c_void_p),
                    ("ghost_t3", C.c_void_p), ("ghost_w1", C.c_void_p), ("ghost_minv", C.c_void_p),
                    ("local_sums", C.c_int32), ("pre_dist_amg", C.c_void_p), ("dist_compact", C.c_int32),
-                   ("pre_dist_aux", C.c_void_p), ("p2p", C.c_void_p)]
+                   ("minv_uniform", C.c_int32), ("pre_dist_aux", C.c_void_p), ("p2p", C.c_void_p)]
                 + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)]
                 + [("pre_fdm", C.c_void_p), ("sweep_A", C.c_void_p)])
 
@@ -489,6 +489,9 @@ class Bpcg2Loop(FusedLoop):
         st.k = float(k) * pa.scale
         self.minv = scaled_diag(pm)
         st.minv = self.minv.data_ptr()
+        # a lumped-mass diagonal that is one double throughout (uniform grids) goes to C4 as one value: looked for at every
+        # start(), where the codes are in force (the regime bound by bytes); tests and measurements flip the attribute
+        self.uniform_diagonal = self.value_coded and hasattr(self.lib, "nss_bpcg2_uniform_diagonal")
         for name in ("u0", "u1", "d0", "d1", "w0", "w1", "s0", "s1", "z0", "q", "t0", "t1", "t2", "t3", "t4"):
             setattr(st, name, vecs[name].buf.data_ptr())
         st.n_u, st.n_p = matA.height, (matB.height if n_p is None else int(n_p))
@@ -516,6 +519,13 @@ class Bpcg2Loop(FusedLoop):
         scal[S_WD], scal[S_ERR0], scal[S_TOL], scal[S_REL] = wdn, err0, tol, 1.0 if rel_err else 0.0
         eng.upload(scal, self.scal)
         self.ctrl.zero_()
+        st.minv_uniform = 0
+        if getattr(self, "uniform_diagonal", False):                     # one launch, one read: minv may have changed
+            eng._check(self.lib.nss_bpcg2_uniform_diagonal(C.byref(st), 1, eng.stream))
+
+    def diagonal_by_value(self):
+        """Whether C4 takes the diagonal preM as one value (found uniform at the last start()) instead of streaming it."""
+        return bool(self.state.minv_uniform)
 
     def enqueue(self, it_begin, it_end):
         """Enqueue iterations [it_begin, it_end) on the current stream; returns immediately."""

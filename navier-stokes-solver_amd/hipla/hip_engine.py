@@ -61,6 +61,8 @@ def _signatures():
         "nss_csr_pair_staged": (C.c_int, [vp, c_i32_p]),
         "nss_csr_plan_generation": (C.c_int, [vp, c_i64_p]),
         "nss_csr_plan_row_slots": (C.c_int, [vp, i32, c_i32_p]),
+        "nss_csr_row_slot_bytes": (C.c_int, [vp, c_i32_p]),
+        "nss_csr_narrow_direct_columns": (C.c_int, [vp, i32, c_i32_p]),
         "nss_csr_pair_mode": (C.c_int, [i32]),
         "nss_p2p_blob_bytes": (C.c_int, [i32, i32, c_i64_p]),
         "nss_p2p_create": (C.c_int, [i32, i32, i32, vp, vp, C.POINTER(vp), vp]),
@@ -179,6 +181,7 @@ def _signatures():
         "nss_bpcg2_phase": (C.c_int, [vp, i32, i32, vp]),
         "nss_bpcg2_phases": (C.c_int, [vp, i32, i32, i32, vp]),
         "nss_bpcg2_iterate": (C.c_int, [vp, i32, i32, vp]),
+        "nss_bpcg2_uniform_diagonal": (C.c_int, [vp, i32, vp]),
         "nss_bpcg2_iterate_classic": (C.c_int, [vp, i32, i32, vp]),
         "nss_bpcg2_cphases": (C.c_int, [vp, i32, i32, i32, vp]),
         "nss_bpcg2_folds_sums": (C.c_int, [vp, c_i32_p]),
@@ -346,12 +349,34 @@ class _CsrHandle:
         """The eight-slot copy of a coded, staged matrix with at most 8 entries per row for the row-per-lane kernel of
         the staged operand (nss_csr_plan_row_slots, set-up only).  mode 1: build wherever the matrix is eligible; -1:
         only where the value codes' size rule coded it, and leave a refused handle alone; 0: drop the copy and refuse
-        later -1 calls; None: only ask.  Returns whether a copy valid for the current launch plan exists."""
+        later -1 calls; None: only ask; 3: as 1 with 24-byte rows in place of the packed 20-byte ones (tests,
+        measurements).  Returns whether a copy valid for the current launch plan exists."""
         lib = self.engine.lib
         if not hasattr(lib, "nss_csr_plan_row_slots"):               # (absent in older A/B builds)
             return False
         out = C.c_int32()
         self.engine._check(lib.nss_csr_plan_row_slots(self.ptr, 2 if mode is None else int(mode), C.byref(out)))
+        return bool(out.value)
+
+    def row_slot_bytes(self):
+        """Bytes per row the row-slot kernels stream from the copy (nss_csr_row_slot_bytes): 20, 24 in the unpacked
+        layout, 0 without a copy they take now."""
+        lib = self.engine.lib
+        if not hasattr(lib, "nss_csr_row_slot_bytes"):               # (absent in older A/B builds)
+            return 24 if self.plan_row_slots(None) else 0
+        out = C.c_int32()
+        self.engine._check(lib.nss_csr_row_slot_bytes(self.ptr, C.byref(out)))
+        return out.value
+
+    def narrow_direct_columns(self, mode=1):
+        """16-bit columns of the coded fixed-width copy (nss_csr_narrow_direct_columns, set-up only).  mode 1: build
+        where every row block's columns fit a window of 65534; 0: drop them and refuse later builds; None: only ask.
+        Returns whether the row-per-lane kernel takes them now."""
+        lib = self.engine.lib
+        if not hasattr(lib, "nss_csr_narrow_direct_columns"):        # (absent in older A/B builds)
+            return False
+        out = C.c_int32()
+        self.engine._check(lib.nss_csr_narrow_direct_columns(self.ptr, 2 if mode is None else int(mode), C.byref(out)))
         return bool(out.value)
 
     def code_values(self):
@@ -391,7 +416,8 @@ class _CsrHandle:
                 "dispatch_period": period.value, "dispatch_planes": planes.value,
                 "rows": m.value, "cols": n.value, "nnz": nnz.value, "row_blocks": nb.value,
                 "lanes_per_row": rg.value, "algorithmic_bytes": nbytes.value, "index_bytes": width.value,
-                "index_group": group.value, "value_bytes": self.value_bytes(), "row_slots": self.plan_row_slots(None)}
+                "index_group": group.value, "value_bytes": self.value_bytes(), "row_slots": self.plan_row_slots(None),
+                "row_slot_bytes": self.row_slot_bytes(), "direct_columns_16": self.narrow_direct_columns(None)}
 
     def __del__(self):
         try:
