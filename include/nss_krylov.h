@@ -50,7 +50,7 @@ NSS_API int nss_stream_synchronize(nss_stream_t stream);
 NSS_API int nss_fill_f64(int64_t n, double value, double* x, nss_stream_t stream);
 NSS_API int nss_copy_f64(int64_t n, const double* x, double* y, nss_stream_t stream);
 NSS_API int nss_scal_f64(int64_t n, double a, double* x, nss_stream_t stream);
-/* y_i = 1 / x_i (inverse diagonals of the AMG levels; IEEE division) */
+/* y_i = 1 / x_i (inverse diagonals of the AMG levels; IEEE division); y may be x, no other overlap */
 NSS_API int nss_reciprocal_f64(int64_t n, const double* x, double* y, nss_stream_t stream);
 /* y = sum_{i<nterms} h_coeff[i] * x_i, 1 <= nterms <= 4, evaluated left to right;
  * y may alias any x_i (element-wise).  h_x is a HOST array of device pointers. */

@@ -2,9 +2,11 @@
 // lincomb (<= 4 terms) / deterministic dot / STREAM triad / diagonal scale.
 //
 // Every kernel is a grid-stride loop over 16-byte (double2) accesses, 256-thread
-// workgroups (one wave per SIMD), at most 2048 workgroups (8 per CU) -- the
-// element-wise recipe of cdna_hip_programming.md Appendix B.  Unaligned views fall
-// back to 8-byte accesses.
+// workgroups (one wave per SIMD), at most NSS_MAX_STREAM_BLOCKS = 65536 workgroups
+// (nss_common.h: high enough that every per-iteration launch is one-shot; the dot
+// takes at most half of that per pair).  Unaligned views fall back to 8-byte
+// accesses.  The triad and the flux are one-shot launches without a stride loop;
+// gather, reciprocal and flux use 8-byte accesses only.
 #include "nss_common.h"
 
 #include <atomic>
@@ -80,8 +82,8 @@ Scratch& scratch() {
 }
 
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void reciprocal_kernel(int64_t n, const double* __restrict__ x,
-                                                             double* __restrict__ y) {
+// y = 1 / x element-wise; y may be x (the in-place inverse of a diagonal): no __restrict__
+__global__ __launch_bounds__(kBlock) void reciprocal_kernel(int64_t n, const double* x, double* y) {
   const int64_t stride = int64_t(gridDim.x) * kBlock;
   for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) y[i] = 1.0 / x[i];
 }

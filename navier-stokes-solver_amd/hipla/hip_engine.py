@@ -589,6 +589,9 @@ class HipEngine:
         return self.dot_multi([(x, y)])
 
     def dot_multi(self, pairs):
+        for x, y in pairs:                   # the kernel takes each length from x alone
+            if x.shape[0] != y.shape[0]:
+                raise ValueError("dot size mismatch: %d vs %d" % (x.shape[0], y.shape[0]))
         total = 0.0
         for k in range(0, len(pairs), 4):
             chunk = pairs[k:k + 4]

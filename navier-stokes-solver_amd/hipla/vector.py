@@ -234,19 +234,26 @@ class Vector(BaseVector):
 
     # -- element / slice access ---------------------------------------------
     def __setitem__(self, key, value):
-        if isinstance(key, slice) and _is_scalar(value):
-            if key == slice(None, None, None):
-                self.engine.fill(self.buf, float(value))
-            else:
-                self.engine.fill(self.engine.view(self.buf, *key.indices(self.size)[:2]), float(value))
-            return
-        if isinstance(key, (int, np.integer)) and _is_scalar(value):
-            i = int(key) % self.size
-            self.engine.fill(self.engine.view(self.buf, i, i + 1), float(value))
-            return
+        """Same keys as __getitem__: a contiguous range or one index in range, IndexError otherwise."""
         if isinstance(key, slice):
+            a, b, st = key.indices(self.size)
+            if st != 1:
+                raise IndexError("only contiguous ranges are supported")
+            if _is_scalar(value):
+                if b > a:
+                    self.engine.fill(self.buf if (a, b) == (0, self.size) else self.engine.view(self.buf, a, b),
+                                     float(value))
+                return
             sub = self[key]
             sub.data = value
+            return
+        if isinstance(key, (int, np.integer)) and _is_scalar(value):
+            i = int(key)
+            if i < 0:
+                i += self.size
+            if not 0 <= i < self.size:
+                raise IndexError(key)
+            self.engine.fill(self.engine.view(self.buf, i, i + 1), float(value))
             return
         raise TypeError("unsupported vector assignment")
 
@@ -287,7 +294,10 @@ class Vector(BaseVector):
         return isinstance(other, Vector) and self.engine.same_buffer(self.buf, other.buf)
 
     def _prepare(self, expr):
-        """Resolve aliasing of matvec operands with the destination."""
+        """Resolve aliasing of the operands with the destination: a matvec operand that overlaps it in any way is
+        applied into a temporary, a plain operand that overlaps it without being the same storage is copied (the
+        element-wise kernels read and write in one launch: only element i of an operand may be element i of the
+        destination).  All of this happens before the destination is written."""
         terms = []
         for t in expr.terms:
             if t.mat is not None and self._overlaps(t.vec):
@@ -296,7 +306,23 @@ class Vector(BaseVector):
                 terms.append(Term(t.scale, None, tmp))
             else:
                 terms.append(t)
-        return terms
+        return self._detach_plain(terms)
+
+    def _detach_plain(self, terms):
+        """Plain operands that partly overlap the destination, replaced by copies (one per distinct operand)."""
+        copies, out = [], []
+        for t in terms:
+            if t.mat is None and isinstance(t.vec, Vector) and not self._same_storage(t.vec) \
+                    and self.engine.overlaps(self.buf, t.vec.buf):
+                for src, tmp in copies:
+                    if src._same_storage(t.vec):
+                        break
+                else:
+                    tmp = t.vec.Copy()
+                    copies.append((t.vec, tmp))
+                t = Term(t.scale, None, tmp)
+            out.append(t)
+        return out
 
     def _overlaps(self, vec):
         if isinstance(vec, Vector):
@@ -479,8 +505,8 @@ class BlockVector(BaseVector):
 
         def flush():
             if run:
-                for i, c in enumerate(self.components):
-                    c._add_terms([self._component_terms(t, i) for t in run])
+                for i, c in enumerate(self.components):           # (each component resolves its own aliasing)
+                    c._accumulate(Expr([self._component_terms(t, i) for t in run]))
                 del run[:]
 
         for t in terms:
@@ -511,6 +537,9 @@ def _local_inner(a, b):
     if isinstance(a, BlockVector) or isinstance(b, BlockVector):
         if not (isinstance(a, BlockVector) and isinstance(b, BlockVector)) or a.nblocks != b.nblocks:
             raise TypeError("InnerProduct of mismatching block layouts")
+        for i, (x, y) in enumerate(zip(a.components, b.components)):      # before any launch: the kernels trust n
+            if x.size != y.size:
+                raise ValueError("InnerProduct size mismatch in component %d: %d vs %d" % (i, x.size, y.size))
         eng = a.engine
         if hasattr(eng, "dot_multi"):
             return eng.dot_multi([(x.buf, y.buf) for x, y in zip(a.components, b.components)])
