@@ -773,7 +773,8 @@ NSS_API int nss_cg_shift_jacobi_f64(int64_t n, const double* mass, double m0, do
  *
  * nss_step_flux_f64: flux[i] = adv_i avg_i - |adv_i| diff_i / 2 with adv = I_adv u, avg = Avg u, diff = Diff u, one
  *   lane per flux point over the two-slot copies of the three matrices (built on the first call: set-up); fails when
- *   a row of one of them holds more than two entries.  `flux` is meant to be the tail of one buffer [u | F].
+ *   a row of one of them holds more than two entries, or when they have rows but no columns (an absent slot gathers
+ *   element 0 of u and drops it).  `flux` is meant to be the tail of one buffer [u | F].
  * nss_step_rhs_f64: temp = f - AD uf for one CSR matrix AD = [A | D] and the operand uf = [u | F]
  *   ( = conv(u) + f - A u with conv(u) = -D F ).
  * nss_step_project_f64: out = raw - C phi (C = M_u^-1 B^T: two entries per row; out may be raw);  with u != NULL
@@ -811,7 +812,8 @@ NSS_API int nss_step_record_f64(const double* partials_energy, int64_t n_energy,
  * nss_scalar_flux_f64: per face r (row of avg and diff, at most two entries each; their two-slot copies are built on
  *   the first call: set-up)  G[r] = u[r] (avg T)_r - |u[r]| (diff T)_r / 2, the donor-cell flux, and with w_b != NULL
  *   f_eff[r] = f[r] + w_b[r] ((avg T)_r - t_ref); w_b == NULL (the passive scalar) reads no f and writes no f_eff.
- *   Fails when a row holds more than two entries.  `G` is meant to be the tail of one buffer [T | G].
+ *   Fails when a row holds more than two entries, or when avg has rows but no columns (an absent slot gathers element
+ *   0 of T and drops it).  `G` is meant to be the tail of one buffer [T | G].
  * nss_scalar_update_f64: T += tau delta; with w != NULL also partials[workgroup] of <w, T> over the updated T (cap
  *   entries, at least what nss_scalar_workspace reports for n); w and partials are both NULL or both given.
  * nss_scalar_record_f64: record[slot] = c0 - sum(partials[0 .. n)), summed by the fixed tree of the Krylov loops. */

@@ -1,4 +1,5 @@
-// The second-order limited upwind face value of the convection terms (limited.hip), said once:
+// The second-order limited upwind face value of the convection terms and the load helpers of the flux kernels
+// (flux.hip).  The face value, said once:
 //
 //   a >= 0:  U = q_lo, D = q_hi, UU = q_ll        a < 0:  U = q_hi, D = q_lo, UU = q_hh
 //   s = phi(U - UU, D - U) if UU exists, else 0;   F = a * (U + s / 2)
@@ -35,10 +36,7 @@ __device__ __forceinline__ double limited_face(double a, const int4v& c, double 
   return a * (up + 0.5 * s);
 }
 
-// ---- what the limited launches and their extrapolating forms (limited.hip, ab2.hip) share ----
-// S1' runs grid-stride over at most this many workgroups, as S1 (scalar.hip): one pass covers 2^20 faces
-constexpr int kLimitedScalarBlocks = 4096;
-
+// ---- the loads of the four flux kernels (flux.hip) ----
 // A gather that no branch guards: an absent entry (-1) reads element 0, which exists, and its value is dropped in
 // registers.  Guarded by `c >= 0 ? q[c] : 0` every gather sits in a branch of its own, and the wait counts the compiler
 // can prove across those branches make the later gathers wait for the earlier ones.
@@ -52,9 +50,9 @@ __device__ __forceinline__ void loads_in_flight(double a, double b, double c, do
                                                 double g = 0.0) {
   asm volatile("" ::"v"(a), "v"(b), "v"(c), "v"(d), "v"(e), "v"(f), "v"(g));
 }
-// (the extrapolating forms add the history reads: up to nine values)
+// (the scalar forms add the force and the history reads of an extrapolating output: up to nine values)
 __device__ __forceinline__ void loads_in_flight(double a, double b, double c, double d, double e, double f, double g,
-                                                double h, double i) {
+                                                double h, double i = 0.0) {
   asm volatile("" ::"v"(a), "v"(b), "v"(c), "v"(d), "v"(e), "v"(f), "v"(g), "v"(h), "v"(i));
 }
 

@@ -3,7 +3,7 @@
 // equation as a Boussinesq force.  One step adds, around the velocity step of step.hip,
 //
 //   S1  faces           : G = u (avg T) - |u| (diff T) / 2 written behind T in ONE operand buffer [T | G];
-//                         f_eff = f + w_b (avg T - T_ref)                                  (scalar_flux_kernel)
+//                         f_eff = f + w_b (avg T - T_ref)                        (scalar_flux_kernel, flux.hip)
 //   S2  rows of [K | B] : temp_T = q - [K | B] [T | G]                                     (EpiStepRhs, step.hip)
 //   ..  delta = (M_p + tau K)^-1 temp_T                                                    (the fused CG loop, cg.hip)
 //   S3  cells           : T += tau delta;  partials of <w, T>                              (scalar_update_kernel)
@@ -14,41 +14,6 @@
 #include "loop_parts.h"
 
 namespace nss {
-
-// S1 runs grid-stride over at most this many workgroups (16 per CU): one pass covers 2^20 faces, a 3-D grid of n = 64
-// (774 144 faces) is one-shot
-constexpr int kScalarFluxBlocks = 4096;
-
-struct ScalarOps {
-  const int32_t *avg_col, *diff_col;
-  const double *avg_val, *diff_val;
-};
-
-// S1: one lane per face.  The four slots of the two rows are requested first, then the gathers of T together (on a grid
-// avg and diff share their columns: the second pair hits the lines of the first), then the arithmetic of
-// step_flux_kernel with the face's own velocity as the advecting one.
-template <bool BUOYANT>
-__global__ __launch_bounds__(kBlock) void scalar_flux_kernel(const int32_t* __restrict__ done, int32_t nface, ScalarOps m,
-                                                              const double* __restrict__ w_b,
-                                                              const double* __restrict__ u, const double* __restrict__ f,
-                                                              const double* __restrict__ T, double t_ref,
-                                                              double* __restrict__ G, double* __restrict__ f_eff) {
-  if (step_done(done)) return;
-  const int stride = gridDim.x * kBlock;
-  for (int r = blockIdx.x * kBlock + threadIdx.x; r < nface; r += stride) {
-    const int2v cm = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.avg_col) + r);
-    const int2v cj = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.diff_col) + r);
-    const dbl2v vm = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.avg_val) + r);
-    const dbl2v vj = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.diff_val) + r);
-    const double m0 = cm.x >= 0 ? T[cm.x] : 0.0, m1 = cm.y >= 0 ? T[cm.y] : 0.0;
-    const double j0 = cj.x >= 0 ? T[cj.x] : 0.0, j1 = cj.y >= 0 ? T[cj.y] : 0.0;
-    const double adv = u[r];
-    const double avg = two_slot_sum(cm, vm, m0, m1);
-    const double dif = two_slot_sum(cj, vj, j0, j1);
-    NSS_ST(G[r], fma(adv, avg, -0.5 * (fabs(adv) * dif)));
-    if constexpr (BUOYANT) NSS_ST(f_eff[r], fma(w_b[r], avg - t_ref, f[r]));
-  }
-}
 
 // S3: T += tau delta; with w: partials[workgroup] of sum_i w_i T_i over the updated T
 __global__ __launch_bounds__(kBlock) void scalar_update_kernel(const int32_t* __restrict__ done, int32_t n, double tau,
@@ -84,31 +49,6 @@ static int update_grid(int64_t n) { return stream_grid(n, kBlock); }
 using namespace nss;
 
 extern "C" {
-
-int nss_scalar_flux_f64(nss_csr_t avg, nss_csr_t diff, const double* w_b, const double* u, const double* f,
-                        const double* T, double t_ref, double* G, double* f_eff, const int32_t* done,
-                        nss_stream_t stream) {
-  return guarded([&] {
-    NSS_REQUIRE(avg && diff && u && T && G, "scalar_flux: NULL argument");
-    NSS_REQUIRE(avg->m == diff->m && avg->n == diff->n, "scalar_flux: avg and diff differ in shape");
-    NSS_REQUIRE(w_b == nullptr || (f && f_eff), "scalar_flux: w_b without f or f_eff");
-    NSS_REQUIRE(G != T && G != u && f_eff != u && f_eff != T, "scalar_flux: an output aliases an operand");
-    require_f64_values(avg, "scalar_flux");
-    require_f64_values(diff, "scalar_flux");
-    if (avg->m == 0) return;                               // (no faces: there is no two-slot copy to build)
-    NSS_REQUIRE(fixed_width_copy(*avg) && fixed_width_copy(*diff),
-                "scalar_flux: a row of avg or diff has more than two entries");
-    const ScalarOps m{avg->fw_col, diff->fw_col, avg->fw_val, diff->fw_val};
-    const dim3 grid(stream_grid(avg->m, kBlock) < kScalarFluxBlocks ? stream_grid(avg->m, kBlock) : kScalarFluxBlocks);
-    if (w_b != nullptr)
-      hipLaunchKernelGGL(scalar_flux_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), done, avg->m, m, w_b, u, f, T,
-                         t_ref, G, f_eff);
-    else
-      hipLaunchKernelGGL(scalar_flux_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), done, avg->m, m, w_b, u, f,
-                         T, t_ref, G, f_eff);
-    NSS_CHECK_LAUNCH();
-  });
-}
 
 int nss_scalar_workspace(int64_t n, int64_t* partials) {
   return guarded([&] {

@@ -2,7 +2,7 @@
 // templates/NavierStokesSIMPLE_iterative.py:424-443).  One step is
 //
 //   F1  flux points     : F = adv*avg - |adv| diff / 2 with adv = I_adv u, avg = Avg u, diff = Diff u, written behind u
-//                         in ONE operand buffer [u | F]                                     (step_flux_kernel)
+//                         in ONE operand buffer [u | F]                           (step_flux_kernel, flux.hip)
 //   F2  rows of [A | D] : temp = f - [A | D] [u | F]  ( = conv(u) + f - A u, conv = -D F )  (EpiStepRhs)
 //   ..  raw = mstar^-1 temp, phi = (B M^-1 B^T)^-1 B raw                                    (the fused CG loop, cg.hip)
 //   P1  rows of C       : out = raw - C phi;  u += tau out;  partials of <u, M u>           (EpiStepProject)
@@ -19,34 +19,6 @@
 #include "bpcg2.h"
 
 namespace nss {
-
-struct FluxOps {
-  const int32_t *adv_col, *avg_col, *diff_col;
-  const double *adv_val, *avg_val, *diff_val;
-};
-
-// F1: one lane per flux point.  The six slots of the three rows are requested first, then all six gathers of u, then the
-// arithmetic of upwind_flux_kernel (blas1.hip) on the three row sums.
-__global__ __launch_bounds__(kBlock) void step_flux_kernel(const int32_t* __restrict__ done, int32_t nflux, FluxOps m,
-                                                            const double* __restrict__ u, double* __restrict__ flux) {
-  if (step_done(done)) return;
-  const int stride = gridDim.x * kBlock;
-  for (int r = blockIdx.x * kBlock + threadIdx.x; r < nflux; r += stride) {
-    const int2v ca = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.adv_col) + r);
-    const int2v cm = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.avg_col) + r);
-    const int2v cj = __builtin_nontemporal_load(reinterpret_cast<const int2v*>(m.diff_col) + r);
-    const dbl2v va = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.adv_val) + r);
-    const dbl2v vm = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.avg_val) + r);
-    const dbl2v vj = __builtin_nontemporal_load(reinterpret_cast<const dbl2v*>(m.diff_val) + r);
-    const double a0 = ca.x >= 0 ? u[ca.x] : 0.0, a1 = ca.y >= 0 ? u[ca.y] : 0.0;
-    const double m0 = cm.x >= 0 ? u[cm.x] : 0.0, m1 = cm.y >= 0 ? u[cm.y] : 0.0;
-    const double j0 = cj.x >= 0 ? u[cj.x] : 0.0, j1 = cj.y >= 0 ? u[cj.y] : 0.0;
-    const double adv = two_slot_sum(ca, va, a0, a1);
-    const double avg = two_slot_sum(cm, vm, m0, m1);
-    const double dif = two_slot_sum(cj, vj, j0, j1);
-    NSS_ST(flux[r], fma(adv, avg, -0.5 * (fabs(adv) * dif)));
-  }
-}
 
 // F2: temp = f - (row of [A | D]) . [u | F]
 struct EpiStepRhs {
@@ -183,25 +155,6 @@ static int div_grid(const nss_csr_s& B) { return stream_grid(B.m, kBlock); }
 using namespace nss;
 
 extern "C" {
-
-int nss_step_flux_f64(nss_csr_t adv, nss_csr_t avg, nss_csr_t diff, const double* u, double* flux, const int32_t* done,
-                      nss_stream_t stream) {
-  return guarded([&] {
-    NSS_REQUIRE(adv && avg && diff && u && flux, "step_flux: NULL argument");
-    NSS_REQUIRE(adv->m == avg->m && adv->m == diff->m && adv->n == avg->n && adv->n == diff->n,
-                "step_flux: adv, avg and diff differ in shape");
-    require_f64_values(adv, "step_flux");
-    require_f64_values(avg, "step_flux");
-    require_f64_values(diff, "step_flux");
-    if (adv->m == 0) return;                               // (no flux points: there is no two-slot copy to build)
-    NSS_REQUIRE(fixed_width_copy(*adv) && fixed_width_copy(*avg) && fixed_width_copy(*diff),
-                "step_flux: a row of adv, avg or diff has more than two entries");
-    const FluxOps m{adv->fw_col, avg->fw_col, diff->fw_col, adv->fw_val, avg->fw_val, diff->fw_val};
-    hipLaunchKernelGGL(step_flux_kernel, dim3(stream_grid(adv->m, kBlock)), dim3(kBlock), 0, as_stream(stream), done,
-                       adv->m, m, u, flux);
-    NSS_CHECK_LAUNCH();
-  });
-}
 
 int nss_step_rhs_f64(nss_csr_t ad, const double* uf, const double* f, double* temp, const int32_t* done,
                      nss_stream_t stream) {

@@ -178,7 +178,7 @@ class ConvectiveFlux:
     two-slot copies of the operators, "minmod" / "vanleer" the limited kernel over the uploaded stencil (avg and diff are
     then not uploaded).  The device operands are looked up in, and left in, `shared` ("adv", "avg", "diff", "stencil"),
     so that the objects of one system keep them once; `launch` is the package's one caller of the two `KERNELS`,
-    `launch_ab2` of their extrapolating twins `KERNELS_AB2` (csrc/ab2.hip)."""
+    `launch_ab2` of `KERNELS_AB2`, the same kernels with the extrapolating output policy (all in csrc/flux.hip)."""
 
     avg = diff = stencil = None
 

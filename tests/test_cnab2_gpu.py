@@ -1,4 +1,4 @@
-"""The second-order IMEX step on the product engine: the four extrapolating flux kernels (csrc/ab2.hip) through the C ABI
+"""The second-order IMEX step on the product engine: the extrapolating flux kernels (csrc/flux.hip) through the C ABI
 on the random tables of tests/test_limited_convection_gpu.py, the right-hand side over [A | D | B^T], and
 `NavierStokes(time_scheme="cnab2").Advance` against tests/cnab2_reference.py (direct solves), against `DoTimeStep`, and
 against itself across calls.
@@ -249,6 +249,8 @@ def test_refusals_empty_input_and_done_flag(hip_engine):
                 rc = eng.lib.nss_step_flux_limited_ab2_f64(adv.handle.ptr, d_st.data_ptr(), nflux, lim, buf.data_ptr(), 1.5,
                                                            -0.5, prev.data_ptr(), tail, None, eng.stream)
                 refused(eng, rc, word)
+        bare = upload(sp.csr_matrix((3, 0)))                        # rows but no columns: u has no element 0
+        refused(eng, step(mat=bare, mats=(bare, bare), rows=3), "no columns")
         assert np.array_equal(eng.to_host(buf), host) and np.array_equal(eng.to_host(prev), phost)      # nothing ran
         assert step(mat=empty, mats=(empty, empty), rows=0) == 0, eng.lib.nss_last_error()
         assert step(done=stop) == 0
@@ -303,6 +305,8 @@ def test_refusals_empty_input_and_done_flag(hip_engine):
         refused(eng, scalar(out=tg), word)
         if form == "twin":
             refused(eng, scalar(mats=(savg, upload(sp.csr_matrix((nflux, n_p + 1))))), word)
+            bare = upload(sp.csr_matrix((3, 0)))                    # faces but no cells: T has no element 0
+            refused(eng, scalar(mats=(bare, bare), rows=3), "no columns")
         else:
             refused(eng, scalar(rows=-1), word)
             refused(eng, scalar(stencil=d_sst.view(-1)[1:]), word)

@@ -1,7 +1,7 @@
 """Second-order limited convection (minmod, van Leer) on the host: the four-point stencils of `StokesSystem` against
 the operators they stand beside, the vectorised `limited_flux` against direct loops over the grid, the order of accuracy
 and the bounds of the scheme, the statement path of `NavierStokes(convection=)` on the checker engine, and the C ABI of
-csrc/limited.hip (header, exports, argument errors).  No GPU."""
+the limited kernels of csrc/flux.hip (header, exports, argument errors).  No GPU."""
 
 import contextlib
 import io

@@ -1,4 +1,4 @@
-"""The second-order limited flux kernels (csrc/limited.hip) through the C ABI on operands a staggered grid never
+"""The second-order limited flux kernels (csrc/flux.hip) through the C ABI on operands a staggered grid never
 produces -- random stencil rows with every presence pattern, random two-slot adv rows, slopes forced onto every branch of
 the limiters -- and through `hipla.fused.TimeStepper` / `ScalarStepper` / `NavierStokes(convection=)` on grid operands:
 against the vectorised `staggered_grid.limited_flux`, the oracle's `do_time_step` with `limited_convection`,

@@ -1,4 +1,4 @@
-"""The kernels of the scalar transport (csrc/scalar.hip) one at a time, through the C ABI as `hipla.fused.ScalarStepper`
+"""The scalar-transport kernels (csrc/scalar.hip, flux.hip) one at a time, through the C ABI as `hipla.fused.ScalarStepper`
 calls it, on operands no grid produces: avg and diff with random, DIFFERENT two-slot rows of 0, 1 or 2 entries, u of
 mixed sign with exact zeros, sizes around a workgroup and above one grid-stride pass of the flux kernel (2^20 faces),
 the `done` flag, partial arrays on both sides of 4096 (where the summation tree changes its formulation).
@@ -121,6 +121,8 @@ def test_flux_refusals_and_no_faces(hip_engine):
     refused(eng, call(*good, out=None), "w_b without")
     refused(eng, call(*good, G=tg.data_ptr()), "aliases")
     refused(eng, lib.nss_scalar_flux_f64(None, None, None, None, None, None, 0.0, None, None, None, None), "scalar_flux")
+    bare = [upload(eng, sp.csr_matrix((3, 0))) for _ in range(2)]  # faces but no cells: T has no element 0
+    refused(eng, call(*bare), "no columns")
     empty = [upload(eng, sp.csr_matrix((0, n_p))) for _ in range(2)]
     assert call(*empty) == 0, lib.nss_last_error()
     eng.synchronize()

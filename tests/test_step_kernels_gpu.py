@@ -1,4 +1,4 @@
-"""The kernels of the device-resident time step (csrc/step.hip) and the device-started CG (`nss_cg_start`,
+"""The kernels of the device-resident time step (csrc/step.hip, csrc/flux.hip) and the device-started CG (`nss_cg_start`,
 `CgLoop.solve_resident`) one at a time, through the C ABI as `hipla.fused.TimeStepper` calls it, on operands a
 staggered grid never produces: random two-slot rows with 0, 1 or 2 entries (equal columns included), non-uniform
 masses, the `done` flag, partial arrays on both sides of every change of shape of the summation tree.
@@ -168,6 +168,9 @@ def test_flux_refusals_and_no_flux_points(hip_engine):
         mats[pos] = wide
         refused(eng, lib.nss_step_flux_f64(*(m.handle.ptr for m in mats), buf.data_ptr(), tail, None, eng.stream),
                 "step_flux")
+    bare = [upload(eng, sp.csr_matrix((3, 0))) for _ in range(3)]        # rows but no columns: u has no element 0
+    refused(eng, lib.nss_step_flux_f64(*(m.handle.ptr for m in bare), buf.data_ptr(), tail, None, eng.stream),
+            "no columns")
     empty = [upload(eng, sp.csr_matrix((0, n_u))) for _ in range(3)]
     assert lib.nss_step_flux_f64(*(m.handle.ptr for m in empty), buf.data_ptr(), tail, None, eng.stream) == 0, \
         lib.nss_last_error()

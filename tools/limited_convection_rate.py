@@ -5,9 +5,11 @@
 
 (a) The flux kernels alone on the operators of one 3-D grid (`--grid`, no NavierStokes object): F1-limited
     (nss_step_flux_limited_f64; donor, minmod, van Leer) and nss_step_flux_f64 of the same library, then S1-limited
-    (nss_scalar_flux_limited_f64, buoyant) and nss_scalar_flux_f64, alternated in `--rounds` rounds of `--reps` launches
-    between two events each: median and spread (max - min) of the rounds, against the algorithmic bytes (48 / 80 per
-    flux point plus u once; 56 / 88 per face plus T once).
+    (nss_scalar_flux_limited_f64, buoyant) and nss_scalar_flux_f64, each followed by its extrapolating export
+    (nss_*_ab2_f64: the same kernel with the extrapolating output policy) at the weights (1, 0), which does not read the
+    history, and (3/2, -1/2), alternated in `--rounds` rounds of `--reps` launches between two events each: median and
+    spread (max - min) of the rounds, against the algorithmic bytes (48 / 80 per flux point plus u once; 56 / 88 per
+    face plus T once; extrapolating + 8 per history written and + 8 per history read).
 (b) Per-step time of `Advance(inner_pre="jacobi")` for "upwind", "minmod", "vanleer" on twins of one 3-D system set up
     as in tools/scalar_step_rate.py: after `--warmup` steps each, `--rounds` interleaved windows of `--steps` steps,
     wall and device time, median and spread of the windows.
@@ -70,25 +72,48 @@ def kernels(args, eng, torch, lines):
     uf = eng.from_host(np.concatenate([np.random.default_rng(2).standard_normal(s.n_u), np.zeros(nflux)]))
     flux = eng.view(uf, s.n_u, s.n_u + nflux)
 
+    prev = eng.zeros(nflux)
+    weights = {"(1, 0)": (1.0, 0.0), "(3/2, -1/2)": (1.5, -0.5)}
+    limiters = ("donor", "minmod", "van Leer")
+
     def limited(code):
         return lambda: eng._check(lib.nss_step_flux_limited_f64(adv.handle.ptr, stencil.data_ptr(), nflux, code,
                                                                 uf.data_ptr(), flux.data_ptr(), None, eng.stream))
-    bodies = {"nss_step_flux_f64 (80 B / point)": lambda: eng._check(lib.nss_step_flux_f64(
-        adv.handle.ptr, avg.handle.ptr, dif.handle.ptr, uf.data_ptr(), flux.data_ptr(), None, eng.stream))}
-    for code, name in enumerate(("donor", "minmod", "van Leer")):
-        bodies["limited, %s (48 B / point)" % name] = limited(code)
+
+    def donor_ab2(w):
+        return lambda: eng._check(lib.nss_step_flux_ab2_f64(adv.handle.ptr, avg.handle.ptr, dif.handle.ptr, uf.data_ptr(),
+                                                            w[0], w[1], prev.data_ptr(), flux.data_ptr(), None, eng.stream))
+
+    def limited_ab2(code, w):
+        return lambda: eng._check(lib.nss_step_flux_limited_ab2_f64(adv.handle.ptr, stencil.data_ptr(), nflux, code,
+                                                                    uf.data_ptr(), w[0], w[1], prev.data_ptr(),
+                                                                    flux.data_ptr(), None, eng.stream))
+    bodies, per = {}, {}                           # name -> launch, name -> algorithmic bytes per point
+
+    def add(name, nbytes, body, unit="point"):
+        name = "%s (%d B / %s)" % (name, nbytes, unit)
+        bodies[name], per[name] = body, nbytes
+    add("nss_step_flux_f64", 80, lambda: eng._check(lib.nss_step_flux_f64(
+        adv.handle.ptr, avg.handle.ptr, dif.handle.ptr, uf.data_ptr(), flux.data_ptr(), None, eng.stream)))
+    for code, name in enumerate(limiters):
+        add("limited, %s" % name, 48, limited(code))
+    for label, w in weights.items():
+        extra = 8 + 8 * (w[1] != 0.0)              # prev written, and read unless w_old == 0
+        add("nss_step_flux_ab2_f64 %s" % label, 80 + extra, donor_ab2(w))
+        for code, name in enumerate(limiters):
+            add("limited ab2, %s %s" % (name, label), 48 + extra, limited_ab2(code, w))
     lines += ["## (a) The flux kernels alone, 3-D n = %d, %d launches per measurement, alternated, median of %d, %s" %
               (args.grid, args.reps, args.rounds, eng.device_info()["arch"]), "",
               "| kernel | points | algorithmic MB | us (spread) | GB/s | time / twin |", "|---|---|---|---|---|---|"]
 
-    def table(res, count, per, once):
+    def table(res, count, once):
         twin = next(iter(res.values()))[0]
         for name, (t, spread) in res.items():
             nbytes = per[name] * count + once
             lines.append("| %s | %d | %.1f | %.1f (%.1f) | %.0f | %.2f |" % (name, count, nbytes / 1e6, 1e3 * t,
                                                                              1e3 * spread, nbytes / t / 1e6, t / twin))
         lines.append("")
-    table(alternate(torch, bodies, args.reps, args.rounds), nflux, {k: 80 if "80" in k else 48 for k in bodies}, 8 * s.n_u)
+    table(alternate(torch, bodies, args.reps, args.rounds), nflux, 8 * s.n_u)
 
     sops = s.scalar_operators(0.01, WALLS)
     savg, sdif = (hipla.SparseMatrix.from_scipy(sops[k]) for k in ("avg", "diff"))
@@ -96,18 +121,32 @@ def kernels(args, eng, torch, lines):
     tg = eng.from_host(np.concatenate([np.random.default_rng(6).random(s.n_p), np.zeros(s.n_u)]))
     G = eng.view(tg, s.n_p, s.n_p + s.n_u)
     u, f, w_b = (eng.from_host(np.random.default_rng(k).standard_normal(s.n_u)) for k in (2, 8, 9))
-    f_eff = eng.zeros(s.n_u)
+    f_eff, G_prev, b_prev = eng.zeros(s.n_u), eng.zeros(s.n_u), eng.zeros(s.n_u)
+    operands = (w_b.data_ptr(), u.data_ptr(), f.data_ptr(), tg.data_ptr(), 0.5)
 
     def scalar(code):
-        return lambda: eng._check(lib.nss_scalar_flux_limited_f64(sst.data_ptr(), s.n_u, code, w_b.data_ptr(), u.data_ptr(),
-                                                                  f.data_ptr(), tg.data_ptr(), 0.5, G.data_ptr(),
+        return lambda: eng._check(lib.nss_scalar_flux_limited_f64(sst.data_ptr(), s.n_u, code, *operands, G.data_ptr(),
                                                                   f_eff.data_ptr(), None, eng.stream))
-    bodies = {"nss_scalar_flux_f64, buoyant (88 B / face)": lambda: eng._check(lib.nss_scalar_flux_f64(
-        savg.handle.ptr, sdif.handle.ptr, w_b.data_ptr(), u.data_ptr(), f.data_ptr(), tg.data_ptr(), 0.5, G.data_ptr(),
-        f_eff.data_ptr(), None, eng.stream))}
-    for code, name in enumerate(("donor", "minmod", "van Leer")):
-        bodies["limited, %s, buoyant (56 B / face)" % name] = scalar(code)
-    table(alternate(torch, bodies, args.reps, args.rounds), s.n_u, {k: 88 if "88" in k else 56 for k in bodies}, 8 * s.n_p)
+
+    def history(w):
+        return (w[0], w[1], G_prev.data_ptr(), G.data_ptr(), b_prev.data_ptr(), f_eff.data_ptr(), None, eng.stream)
+
+    def scalar_ab2(w):
+        return lambda: eng._check(lib.nss_scalar_flux_ab2_f64(savg.handle.ptr, sdif.handle.ptr, *operands, *history(w)))
+
+    def scalar_limited_ab2(code, w):
+        return lambda: eng._check(lib.nss_scalar_flux_limited_ab2_f64(sst.data_ptr(), s.n_u, code, *operands, *history(w)))
+    bodies, per = {}, {}
+    add("nss_scalar_flux_f64, buoyant", 88, lambda: eng._check(lib.nss_scalar_flux_f64(
+        savg.handle.ptr, sdif.handle.ptr, *operands, G.data_ptr(), f_eff.data_ptr(), None, eng.stream)), "face")
+    for code, name in enumerate(limiters):
+        add("limited, %s, buoyant" % name, 56, scalar(code), "face")
+    for label, w in weights.items():
+        both = 2 * (8 + 8 * (w[1] != 0.0))         # G_prev and b_prev
+        add("nss_scalar_flux_ab2_f64, buoyant %s" % label, 88 + both, scalar_ab2(w), "face")
+        for code, name in enumerate(limiters):
+            add("limited ab2, %s, buoyant %s" % (name, label), 56 + both, scalar_limited_ab2(code, w), "face")
+    table(alternate(torch, bodies, args.reps, args.rounds), s.n_u, 8 * s.n_p)
 
 
 def fresh(mesh, v0, scheme):
