@@ -987,6 +987,19 @@ NSS_API int nss_fdmi_contract_f64(int64_t n, int64_t nq, int32_t lines, int32_t 
                                   nss_stream_t stream);
 NSS_API int nss_fdmi_set_tile(nss_fdmi_t h, int32_t mode);
 
+/* ---- the factors of the fast-diagonalisation solvers, read off a resident matrix ------------------------------
+ * `hipla.fdm.gather_factors` (csrc/fdm_gather.hip).  The layout is the one nss_fdmc_create takes
+ * (ncomp, dim, n_total, h_base, pitch, h_extents: HOST, with the refusals of that entry point); `a` is n_total x n_total
+ * with fp64 values (a narrowed matrix, nss_csr_narrow_f32, is refused).
+ *
+ * nss_fdm_gather_factors: h_T_out[c * dim + k] (HOST, e x e row-major, e the k-th extent of component c) receives
+ *   T[x, y] = a[line[x], line[y]] on the grid line through the component's origin along axis k -- the rule of
+ *   `hipla.fdm.fdm_factors` -- and 0 where nothing, or a zero, is stored; duplicates are not summed.  One small launch
+ *   on `stream`, one synchronisation; nothing else of the matrix is downloaded. */
+NSS_API int nss_fdm_gather_factors(nss_csr_t a, int32_t ncomp, int32_t dim, int64_t n_total, const int64_t* h_base,
+                                   int64_t pitch, const int64_t* h_extents, double* const* h_T_out,
+                                   nss_stream_t stream);
+
 /* ---- device-resident heat exponential integrator -------------------------------------------------
  * The kernels of `heat.evolve` around its inner CG solves (the reference's heat.py:95-142 and orthonormalization.py:
  * 5-16).  The operand is a basis of d vectors (1 <= d <= 8) of length n in ONE device allocation, stored as planes:

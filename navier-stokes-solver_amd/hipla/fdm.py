@@ -18,7 +18,11 @@ The velocity operator and the scalar's diffusion operator have the same structur
 Without a mass the same factors give the inverse of the velocity operator itself: `inverse_factors` runs the checks of
 `component_factors` and asks that the operator be definite, and `FastDiagonalizationInverse` applies ``mat^-1`` as a
 preconditioner of the Stokes solvers -- ``nss_fdmi_apply_f64`` (csrc/fdm_inverse.hip), inside the
-fused loops on the HIP engine, or the numpy restatement."""
+fused loops on the HIP engine, or the numpy restatement.
+
+`gather_factors` reads the same 1-D factors off a matrix that is resident on the HIP engine (``nss_fdm_gather_factors``,
+csrc/fdm_gather.hip) without fetching it; the proof that the matrix is their Kronecker sum is the
+host's."""
 
 import ctypes as C
 import os
@@ -138,6 +142,48 @@ def fdm_factors(Lp, extents):
     if not (np.array_equal(L.indptr, K.indptr) and np.array_equal(L.indices, K.indices)):
         return None, "the pattern is not that of a Kronecker sum over these extents"
     return FdmFactors(extents, T, error), None
+
+
+def gather_available(eng):
+    """Whether `eng` is the HIP engine with the entry point that reads the factors off a resident matrix."""
+    return _hip(eng) and hasattr(getattr(eng, "lib", None), "nss_fdm_gather_factors")
+
+
+def gather_factors(mat, bases, pitch, shapes):
+    """The 1-D factors of the resident `mat` (a `SparseMatrix` of the HIP engine) on components laid out as
+    `component_factors` asks -- entry (k, j, i) of component c at ``bases[c] + k * pitch + j * e_2 + i``, `shapes` their
+    extents -- by the rule of `fdm_factors`, without fetching the matrix: T_a[x, y] = mat[line_a[x], line_a[y]] on the
+    grid line through the component's origin is gathered on the device (``nss_fdm_gather_factors``; DESIGN.md section
+    19), e x e doubles per axis are downloaded, and (d - 1) / d * mat[origin, origin] is taken off the diagonal here, the
+    same fp64 operation on the same operands as on the host: for a matrix without duplicates the arrays EQUAL the
+    ``FdmFactors.T`` of the host.  Per component the list of its d arrays.  Nothing is proved about the rest of the
+    matrix.  ``ValueError`` when the engine or the matrix cannot do it (not the HIP engine, not a `SparseMatrix`, fp32
+    storage, a layout the library refuses)."""
+    from .hip_engine import NssError
+    if not isinstance(mat, SparseMatrix):
+        raise ValueError("gather_factors: the matrix is a %s, not a SparseMatrix" % type(mat).__name__)
+    eng = mat.engine
+    if not gather_available(eng):
+        raise ValueError("gather_factors: the engine %r has no nss_fdm_gather_factors" % (getattr(eng, "name", eng),))
+    shapes = [tuple(int(e) for e in s) for s in shapes]
+    ncomp, d = len(shapes), len(shapes[0]) if shapes else 0
+    if not 1 <= ncomp <= 3 or d not in (2, 3) or any(len(s) != d or min(s) < 1 for s in shapes) or len(bases) != ncomp:
+        raise ValueError("gather_factors: one to three components over two, or over three, positive extents each, and "
+                         "a base for each")
+    base = (C.c_int64 * ncomp)(*[int(b) for b in bases])
+    ext = (C.c_int64 * (ncomp * d))(*[e for s in shapes for e in s])
+    T = [[np.zeros((e, e)) for e in s] for s in shapes]
+    out = (C.c_void_p * (ncomp * d))(*[t.ctypes.data for ts in T for t in ts])
+    try:
+        eng._check(eng.lib.nss_fdm_gather_factors(mat.handle.ptr, ncomp, d, mat.m, base, int(pitch), ext, out,
+                                                  eng.stream))
+    except NssError as err:
+        raise ValueError("gather_factors: %s" % err)
+    for ts in T:
+        corner = ts[0][0, 0]
+        for t in ts:
+            t[np.diag_indices(t.shape[0])] -= (d - 1) / d * corner
+    return T
 
 
 class _FdmHandle:

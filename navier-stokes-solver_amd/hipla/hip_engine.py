@@ -171,6 +171,7 @@ def _signatures():
         "nss_fdmi_apply_f64": (C.c_int, [vp, dbl, vp, vp, vp, vp]),
         "nss_fdmi_contract_f64": (C.c_int, [i64, i64, i32, i32, vp, i32, vp, vp, vp, vp]),
         "nss_fdmi_set_tile": (C.c_int, [vp, i32]),
+        "nss_fdm_gather_factors": (C.c_int, [vp, i32, i32, i64, c_i64_p, i64, c_i64_p, C.POINTER(vp), vp]),
         "nss_heat_workspace": (C.c_int, [i64, i32, c_i64_p]),
         "nss_mgs_f64": (C.c_int, [i64, i32, i64, vp, i32, vp, vp, i64, vp]),
         "nss_galerkin_f64": (C.c_int, [vp, i32, i64, vp, vp, vp, i64, vp]),
