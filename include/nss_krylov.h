@@ -766,6 +766,73 @@ NSS_API int nss_cg_start(const nss_cg_t* s, const double* b, double tol, nss_str
 NSS_API int nss_cg_shift_jacobi_f64(int64_t n, const double* mass, double m0, double sigma, const double* diag,
                                     double* dinv, nss_stream_t stream);
 
+/* ---- fused BiCGStab for nonsymmetric operators -------------------------------------------------
+ * The Krylov loop of the linearly implicit convection step (`NavierStokes.SetConvectionTreatment("implicit")`; not in
+ * the reference, whose convection is explicit: templates/NavierStokesSIMPLE_iterative.py:427-431) and of
+ * `hipla.BiCGStabSolver` (csrc/bicgstab.hip).  Right-preconditioned, from x = 0: rhat = r0 = b, p = r0, rho = <rhat, r0>,
+ * and per iteration
+ *   phat = P p;  v = Op phat;  alpha = rho / <rhat, v>;  s = r - alpha v
+ *   shat = P s;  t = Op shat;  omega = <t, s> / <t, t>      (<t, t> == 0: omega = 0)
+ *   x += alpha phat + omega shat;  r = s - omega t;  hist[it] = |r|_2;  stop when |r|_2 < tol |b|_2
+ *   rho' = <rhat, r>;  beta = (rho'/rho)(alpha/omega);  p = r + beta (p - omega v);  rho = rho'
+ * Launches per iteration: 8 -- rows (v, partials <rhat, v>), sum, element-wise (s, shat), rows (t, partials <t, s> and
+ * <t, t>), sum, element-wise (x, r, partials <rhat, r> and <r, r>), sum (books), element-wise (p, phat); P = identity
+ * or pre_diag rides in the element-wise launches.  Form (ii) adds the two flux launches (10); pre_fdm adds its 2 dim
+ * passes in front of each of the two applies.  The sums: per-workgroup partials finished by the fixed tree of minres,
+ * bpcg2, step and heat (fixed_sums_1024, two sums per launch); no atomics, the same bits every run.  The scalars stay
+ * on the device; every launch that writes loop state returns before its first load once ctrl[done] is set, the passes
+ * of pre_fdm included.
+ *
+ * Op, form (i) (avg == diff == NULL): the square matrix A.  Form (ii): y = m v + shift_sigma [L | Dv] [v | F(a; v)],
+ * F(a; v)_i = a_i (avg v)_i - |a_i| (diff v)_i / 2 -- A = [L | Dv] with n rows and n + nflux columns (the stepper's
+ * [A | D], or [K | B] for the scalar), avg and diff nflux x n with at most two entries per row, adv = a (nflux), m_r =
+ * shift_mass[r] or shift_m0 (shift_mass NULL).  sigma goes by value: one state serves every step size.
+ * Vector lengths: n for x, r, rhat, p, v, t; the columns of A for phat and shat (form (ii): the flux tail behind them).
+ * scal: double[16] = { rho, <rhat,v>, alpha, <t,s>, <t,t>, omega, rho', <r,r>, beta, |b|, tol, ... };
+ * ctrl: int32[4] = { done, it_final, last_it, code }; hist[it] = |r|_2 after iteration it.
+ * code: 0 converged (or a zero right-hand side); 1: <rhat, v> or rho' zero or not finite (or alpha, omega, <r, r> not
+ * finite) -- found before x is touched in the iteration where the scalar appears, x stays at its last iterate; 2:
+ * <t, t> == 0 without convergence.  it_final = the last iteration whose update of x was applied (-1: none).  The cap
+ * reached: done stays 0. */
+typedef struct nss_fdmc_s* nss_fdmc_t;
+typedef struct nss_bicgstab_s {
+  nss_csr_t A;
+  nss_csr_t avg, diff;        /* form (ii), else both NULL */
+  const double* adv;
+  const double* shift_mass;
+  double shift_m0, shift_sigma;
+  const double* pre_diag;     /* phat = dinv p               -- or NULL */
+  nss_fdmc_t pre_fdm;         /* form (ii): phat = (M + shift_sigma L)^-1 p, the direct viscous inverse -- or NULL;
+                                 neither: P = identity.  Its work buffers are shared: every solve with the handle is
+                                 ordered on the loop's stream */
+  double *x, *r, *rhat, *p, *v, *t, *phat, *shat;
+  double* scal;
+  int32_t* ctrl;
+  double* hist;
+  double *partials_a, *partials_b;  /* 2 x A's row-block count / 2 x the element-wise grid: nss_bicgstab_workspace() */
+  int32_t n, nflux;
+  /* the launch plan the partials were sized for, as in nss_cg_t: a stale plan_gen or a short cap_* is refused before
+   * any launch */
+  int64_t plan_gen;
+  int64_t cap_a, cap_b;
+} nss_bicgstab_t;
+NSS_API int nss_bicgstab_workspace(const nss_bicgstab_t* s, int64_t* partials_a, int64_t* partials_b);
+/* x = 0, r = rhat = p = b, phat = P b (identity / pre_diag), scal, ctrl = { 0, -1, -1, 0 }; a zero right-hand side sets
+ * done at once.  hist must hold as many entries as iterations will be enqueued.  No synchronisation, no allocation. */
+NSS_API int nss_bicgstab_start(const nss_bicgstab_t* s, const double* b, double tol, nss_stream_t stream);
+/* iterations [it_begin, it_end) back to back; the first call of a form-(ii) state builds the two-slot copies of avg and
+ * diff (set-up) */
+NSS_API int nss_bicgstab_iterate(const nss_bicgstab_t* s, int32_t it_begin, int32_t it_end, nss_stream_t stream);
+NSS_API int nss_bicgstab_poll(const nss_bicgstab_t* s, int32_t* done, int32_t* it_final, int32_t* last_it, int32_t* code,
+                              nss_stream_t stream);
+/* y = Op v as the loop applies it (inspection, tests, `hipla.stepping.LinearisedConvection`): `operand` holds v in its
+ * first n entries and has the columns of A; form (ii) writes F(a; v) behind v (two launches).  Reads A, avg, diff, adv,
+ * the shift, n, nflux and ctrl (nothing is written once ctrl[done] is set) of the state, none of its vectors. */
+NSS_API int nss_bicgstab_apply_f64(const nss_bicgstab_t* s, double* operand, double* y, nss_stream_t stream);
+/* dinv_i = 1 / (m_i + sigma (L_ii + sum_p Dv[i,p] (a_p avg[p,i] - |a_p| diff[p,i] / 2))): the point-Jacobi diagonal of
+ * form (ii) for the state's adv and shift_sigma, one launch per step, into the buffer pre_diag names (n doubles) */
+NSS_API int nss_bicgstab_jacobi_f64(const nss_bicgstab_t* s, double* dinv, nss_stream_t stream);
+
 /* ---- device-resident IMEX time step ------------------------------------------------------------
  * The kernels of `NavierStokes.Advance` around the two inner CG solves (DoTimeStep / Project of the reference,
  * templates/NavierStokesSIMPLE_iterative.py:424-443).  All fp64, deterministic (no atomics); `done` (device int32,
@@ -941,7 +1008,7 @@ NSS_API int nss_fdm_solve_f64(nss_fdm_t h, const double* rhs, double* phi, nss_s
  * nss_fdmc_pass_f64: one batched pass along `axis` (0 .. dim - 1) from src to dst (DEVICE, n_total, distinct), with Q_a
  *   (transpose = 0) or Q_a^T; `scaled`: the entries are multiplied by the factor above for `sigma`.  The entries
  *   outside the components are neither read nor written. */
-typedef struct nss_fdmc_s* nss_fdmc_t;
+/* (nss_fdmc_t: the typedef stands in front of nss_bicgstab_t, which names it) */
 NSS_API int nss_fdmc_create(int32_t ncomp, int32_t dim, int64_t n_total, const int64_t* h_base, int64_t pitch,
                             const int64_t* h_extents, const double* const* h_Q, const double* const* h_lambda,
                             const double* h_mass, nss_fdmc_t* out);

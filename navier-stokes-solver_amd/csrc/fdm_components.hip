@@ -50,6 +50,7 @@ struct FdmcPass {
   int32_t axis;                                            // internal: 0, 1 or 2
   int32_t transpose, scaled, dim;
   double sigma;
+  const int32_t* done;                                     // device int (or NULL): non-zero -> the pass returns at once
 };
 
 // the tiles of a component in a pass along `axis`: (tiles of q, tiles of i, workgroups along o)
@@ -67,6 +68,7 @@ __host__ __device__ inline FdmcTiles fdmc_tiles(const int32_t* ext, int axis) {
 template <bool LINES>                                      // LINES <=> axis == 2
 __global__ __launch_bounds__(kBlock) void fdmc_pass_kernel(FdmcPass p, const double* __restrict__ src,
                                                             double* __restrict__ dst) {
+  if (p.done != nullptr && *p.done != 0) return;           // (a frozen loop: nss::fdmc_solve)
   uint32_t blk = blockIdx.x;
   const bool past0 = blk >= p.end[0], past1 = blk >= p.end[1];
   const FdmcComp& d = past1 ? p.comp[2] : past0 ? p.comp[1] : p.comp[0];
@@ -131,8 +133,9 @@ static int fdmc_axis(int dim, int a) { return fdm_internal_axis(dim, a); }
 
 // one batched pass; the arguments have been checked
 static void fdmc_launch(const nss_fdmc_s& h, int axis, int transpose, int scaled, double sigma, const double* src,
-                        double* dst, hipStream_t st) {
+                        double* dst, hipStream_t st, const int32_t* done = nullptr) {
   FdmcPass p{};
+  p.done = done;
   p.axis = axis;
   p.transpose = transpose;
   p.scaled = scaled;
@@ -162,6 +165,25 @@ static void fdmc_launch(const nss_fdmc_s& h, int axis, int transpose, int scaled
     hipLaunchKernelGGL(fdmc_pass_kernel<false>, grid, block, 0, st, p, src, dst);
   NSS_CHECK_LAUNCH();
 }
+
+namespace nss {
+
+int64_t fdmc_rows(const nss_fdmc_s& h) { return h.n_total; }                 // (loop_parts.h: the BiCGStab loop asks)
+
+// forward: Q_a^T along every axis, the shifted scaling on the last of them; backward: Q_a along every axis.
+// rhs -> work0 -> work1 -> work0 -> ... -> out: pass k reads what pass k - 1 wrote.  `done`: see FdmcPass.
+void fdmc_solve(const nss_fdmc_s& h, double sigma, const double* rhs, double* out, const int32_t* done, hipStream_t st) {
+  NSS_REQUIRE(rhs && out && rhs != out, "fdmc_solve: NULL argument, or out aliases rhs");
+  NSS_REQUIRE(std::isfinite(sigma) && sigma >= 0.0, "fdmc_solve: sigma is negative or not finite");
+  const int d = h.dim, passes = 2 * d;
+  for (int k = 0; k < passes; ++k) {
+    const double* src = k == 0 ? rhs : h.work[(k - 1) % 2];
+    double* dst = k == passes - 1 ? out : h.work[k % 2];
+    fdmc_launch(h, fdmc_axis(d, k % d), /*transpose=*/k < d, /*scaled=*/k == d - 1, sigma, src, dst, st, done);
+  }
+}
+
+}  // namespace nss
 
 extern "C" {
 
@@ -224,16 +246,7 @@ int nss_fdmc_solve_f64(nss_fdmc_t h, double sigma, const double* rhs, double* ou
   return guarded([&] {
     NSS_REQUIRE(h && rhs && out, "fdmc_solve: NULL argument");
     NSS_REQUIRE(rhs != out, "fdmc_solve: out aliases rhs");
-    NSS_REQUIRE(std::isfinite(sigma) && sigma >= 0.0, "fdmc_solve: sigma is negative or not finite");
-    const int d = h->dim, passes = 2 * d;
-    // forward: Q_a^T along every axis, the shifted scaling on the last of them; backward: Q_a along every axis.
-    // rhs -> work0 -> work1 -> work0 -> ... -> out: pass k reads what pass k - 1 wrote.
-    for (int k = 0; k < passes; ++k) {
-      const double* src = k == 0 ? rhs : h->work[(k - 1) % 2];
-      double* dst = k == passes - 1 ? out : h->work[k % 2];
-      fdmc_launch(*h, fdmc_axis(d, k % d), /*transpose=*/k < d, /*scaled=*/k == d - 1, sigma, src, dst,
-                  as_stream(stream));
-    }
+    fdmc_solve(*h, sigma, rhs, out, nullptr, as_stream(stream));
   });
 }
 

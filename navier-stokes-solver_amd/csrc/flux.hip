@@ -306,6 +306,12 @@ static void launch_scalar_flux(const Who& who, nss_csr_s& avg, nss_csr_s& diff, 
   NSS_CHECK_LAUNCH();
 }
 
+// S1 as the flux of the linearised convection (loop_parts.h): the passive form on (a, v)
+void linear_donor_flux(nss_csr_s& avg, nss_csr_s& diff, const double* a, const double* v, double* F, const int32_t* done,
+                       hipStream_t st) {
+  launch_scalar_flux(Who{"linear_donor_flux"}, avg, diff, nullptr, a, nullptr, v, 0.0, done, st, StoreFlux{F, nullptr});
+}
+
 // the operands of S1' that do not depend on the output
 static void limited_scalar_rows(const Who& who, const int32_t* stencil, int64_t nface, int32_t limiter) {
   require_limiter(who, limiter);

@@ -1,9 +1,9 @@
-// The small parts the device-resident loops (cg, lanczos, minres, bpcg1, bpcg2, step, heat) are put together from, said
-// once: the dot-partial finish of a kernel, the sum of such partials by one 1024-thread workgroup, the guarded dot kernel,
-// the poll of a loop's control words and the setter of a plan override.
-// Three sum trees exist, each with its own bits: fixed_sums_1024 (nss_common.h: minres, bpcg2, step, heat, the folded
-// forms of bpcg1 and lanczos), sum_partials_1024 below (cg, the stand-alone sums of lanczos) and the one-accumulator,
-// two-input tree of bpcg1_scalar_kernel (bpcg1.hip).
+// The small parts the device-resident loops (cg, bicgstab, lanczos, minres, bpcg1, bpcg2, step, heat) are put together
+// from, said once: the dot-partial finish of a kernel, the sum of such partials by one 1024-thread workgroup, the guarded
+// dot kernel, the poll of a loop's control words and the setter of a plan override.
+// Three sum trees exist, each with its own bits: fixed_sums_1024 (nss_common.h: minres, bpcg2, bicgstab, step, heat, the
+// folded forms of bpcg1 and lanczos), sum_partials_1024 below (cg, the stand-alone sums of lanczos) and the
+// one-accumulator, two-input tree of bpcg1_scalar_kernel (bpcg1.hip).
 #pragma once
 
 #include "nss_common.h"
@@ -53,6 +53,16 @@ __device__ __forceinline__ double two_slot_sum(const int2v& c, const dbl2v& v, d
 __device__ __forceinline__ double donor_flux(double adv, double avg, double dif) {
   return fma(adv, avg, -0.5 * (fabs(adv) * dif));
 }
+
+// F[r] = donor_flux(a[r], (avg v)_r, (diff v)_r) over the two-slot copies of avg and diff (which the caller has built:
+// fixed_width_copy): the scalar flux launch S1 of flux.hip without a force, with the frozen advecting vector `a` in the
+// place of the face velocities and `v` in the place of T -- the flux of the linearised convection (bicgstab.hip)
+void linear_donor_flux(nss_csr_s& avg, nss_csr_s& diff, const double* a, const double* v, double* F, const int32_t* done,
+                       hipStream_t st);
+// the entries of the vector an nss_fdmc_t was made for, and nss_fdmc_solve_f64 with a `done` word (device int, may be
+// NULL): every pass returns at once when it is non-zero (fdm_components.hip)
+int64_t fdmc_rows(const nss_fdmc_s& h);
+void fdmc_solve(const nss_fdmc_s& h, double sigma, const double* rhs, double* out, const int32_t* done, hipStream_t st);
 
 // the stop test of a loop that freezes once one control word is set (cg, lanczos)
 struct StopWord {

@@ -939,6 +939,164 @@ class CgLoop(FusedLoop):
         return it_final + 1 if done else maxsteps
 
 
+class BicgstabState(C.Structure):
+    """ctypes mirror of ``nss_bicgstab_t`` (include/nss_krylov.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "avg", "diff", "adv", "shift_mass")]
+                + [("shift_m0", C.c_double), ("shift_sigma", C.c_double), ("pre_diag", C.c_void_p), ("pre_fdm", C.c_void_p)]
+                + [(n, C.c_void_p) for n in ("x", "r", "rhat", "p", "v", "t", "phat", "shat", "scal", "ctrl", "hist",
+                                             "partials_a", "partials_b")]
+                + [("n", C.c_int32), ("nflux", C.c_int32), ("plan_gen", C.c_int64), ("cap_a", C.c_int64),
+                   ("cap_b", C.c_int64)])
+
+
+class ConvectiveForm(NamedTuple):
+    """The device operands of form (ii) of the BiCGStab loop, ``y = m v + sigma [L | Dv] [v | F(a; v)]``: `rows` = the
+    `SparseMatrix` [L | Dv] (n rows, n + nflux columns), `avg` and `diff` (nflux x n, at most two entries per row), `adv`
+    = the device buffer of a (nflux entries; its owner rewrites it once per step) and `mass` = (device buffer or None,
+    m0): the mass vector, or its one value when it is uniform."""
+    rows: object
+    avg: object
+    diff: object
+    adv: object
+    mass: tuple
+
+    @staticmethod
+    def mass_operand(eng, mass):
+        mass = np.asarray(mass, dtype=np.float64)
+        uniform = bool(mass.size) and bool((mass == mass[0]).all())
+        return (None, float(mass[0])) if uniform else (eng.from_host(mass), 0.0)
+
+
+class BicgstabLoop(FusedLoop):
+    """Device-resident right-preconditioned BiCGStab (``nss_bicgstab_*``, csrc/bicgstab.hip) behind
+    `hipla.BiCGStabSolver` and the linearly implicit convection step of `hipla.stepping.TimeStepper`.  Form (i): a
+    square `SparseMatrix`; form (ii): a `ConvectiveForm`.  Preconditioners: none, an inverse diagonal (a device buffer),
+    or -- form (ii) -- the direct viscous inverse of a `ComponentFastDiagonalization`, applied with the loop's sigma."""
+
+    CODES = {1: "<rhat, v> or rho is zero or not finite", 2: "<t, t> is zero before convergence"}
+
+    @classmethod
+    def try_create(cls, mat, pre):
+        return cls._decided(cls._try_create(mat, pre))
+
+    @classmethod
+    def _try_create(cls, mat, pre):
+        from .fdm import ComponentFastDiagonalization            # (fdm.py imports this module)
+        from .stepping import LinearisedConvection
+        convective = isinstance(mat, LinearisedConvection)
+        if not convective and (not isinstance(mat, SparseMatrix) or mat.height != mat.width):
+            return "the matrix is neither a square SparseMatrix nor a LinearisedConvection"
+        eng = mat.engine
+        if (declined := cls._engine_declined(eng)) is not None:
+            return declined
+        if not hasattr(eng.lib, "nss_bicgstab_iterate"):
+            return "the library has no BiCGStab loop"
+        diag = fdm_pre = None
+        if isinstance(pre, ComponentFastDiagonalization):
+            if not convective or pre.handle is None or pre.n != mat.height:
+                return "the direct viscous inverse goes with a LinearisedConvection of its size on the HIP engine"
+            fdm_pre = pre
+        elif isinstance(pre, DiagonalMatrix):
+            if pre.n != mat.height:
+                return "the diagonal preconditioner has another size"
+            diag = pre.d
+        elif pre is not None:
+            return "the preconditioner is not native"
+        if convective:
+            form = mat.device_form()
+            if form is None:
+                return "the LinearisedConvection holds no device operands"
+            return cls(eng, form.rows, diag, form, fdm_pre, op=mat)
+        return cls(eng, mat, diag)
+
+    def __init__(self, eng, mat, diag=None, form=None, fdm_pre=None, op=None):
+        """`mat`: the square matrix, or [L | Dv] of `form`; `diag`: device buffer of the inverse diagonal or None;
+        `fdm_pre`: a `ComponentFastDiagonalization` or None; `op`: the `LinearisedConvection` whose sigma a solve reads
+        (None: `set_sigma`)."""
+        torch = eng.torch
+        n = mat.height
+        self.eng, self.lib, self.mat, self.form, self.op = eng, eng.lib, mat, form, op
+        self.keep = (diag, fdm_pre)
+        self.work = {name: eng.zeros(n) for name in ("r", "rhat", "p", "v", "t")}
+        self.work.update({name: eng.zeros(mat.width) for name in ("phat", "shat")})
+        st = BicgstabState()
+        st.A, st.n, st.nflux = mat.handle.ptr, n, mat.width - n
+        if form is not None:
+            st.avg, st.diff, st.adv = form.avg.handle.ptr, form.diff.handle.ptr, form.adv.data_ptr()
+            st.shift_mass = None if form.mass[0] is None else form.mass[0].data_ptr()
+            st.shift_m0 = form.mass[1]
+        st.pre_diag = None if diag is None else diag.data_ptr()
+        st.pre_fdm = None if fdm_pre is None else fdm_pre.handle.ptr
+        for name, buf in self.work.items():
+            setattr(st, name, buf.data_ptr())
+        self.partials = fit_partials(eng, st, self.lib.nss_bicgstab_workspace, ("A",))
+        self.scal = eng.zeros(16)
+        self.ctrl = torch.zeros(4, dtype=torch.int32, device=eng.device)
+        st.scal, st.ctrl = self.scal.data_ptr(), self.ctrl.data_ptr()
+        self.state = st
+        self.hist = None
+        self.code = 0
+        self.last_count = None        # iterations of the last solve: the size of the next solve's first chunk
+
+    def set_sigma(self, sigma):
+        """Form (ii): the operator becomes M + `sigma` (L + N(a)) -- by value, nothing is launched."""
+        sigma = float(sigma)
+        if self.form is None or not (sigma >= 0.0 and np.isfinite(sigma)):
+            raise ValueError("BicgstabLoop.set_sigma: a form-(ii) loop, and a sigma that is non-negative and finite")
+        self.state.shift_sigma = sigma
+
+    def write_jacobi(self, dinv):
+        """Form (ii): the point-Jacobi diagonal of the operator for the current a and sigma into the device buffer `dinv`
+        (one launch; once per step, after a was frozen)."""
+        self.eng._check(self.lib.nss_bicgstab_jacobi_f64(C.byref(self.state), dinv.data_ptr(), self.eng.stream))
+
+    def apply(self, operand, y):
+        """y = Op v for the v in the first n entries of the device buffer `operand` (the columns of `mat` long; form (ii)
+        writes the flux behind v)."""
+        self.eng._check(self.lib.nss_bicgstab_apply_f64(C.byref(self.state), operand.data_ptr(), y.data_ptr(),
+                                                        self.eng.stream))
+
+    def enqueue(self, it_begin, it_end):
+        self.eng._check(self.lib.nss_bicgstab_iterate(C.byref(self.state), it_begin, it_end, self.eng.stream))
+
+    def poll(self):
+        """Drain the stream; returns (done, it_final, code)."""
+        done, it_final, last, code = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self.eng._check(self.lib.nss_bicgstab_poll(C.byref(self.state), C.byref(done), C.byref(it_final), C.byref(last),
+                                                   C.byref(code), self.eng.stream))
+        return bool(done.value), it_final.value, code.value
+
+    def solve_resident(self, b, x, precision, maxsteps, poll_every=None):
+        """x = Op^-1 b from x = 0, started on the device (``nss_bicgstab_start``): no allocation after the first call, no
+        history download -- the only synchronisations are the polls.  Returns the iteration count (0 for a zero
+        right-hand side, `maxsteps` when the cap was reached); the breakdown code (0: none) is left in `self.code`."""
+        eng, st = self.eng, self.state
+        if self.op is not None:
+            self.set_sigma(self.op.sigma)
+        self.partials = fit_partials(eng, st, self.lib.nss_bicgstab_workspace, ("A",), self.partials)
+        if self.hist is None or self.hist.numel() < max(1, maxsteps):
+            self.hist = eng.zeros(max(1, maxsteps))
+        st.hist, st.x = self.hist.data_ptr(), x.data_ptr()
+        eng._check(self.lib.nss_bicgstab_start(C.byref(st), b.data_ptr(), float(precision), eng.stream))
+        # The first chunk is what the last solve needed, plus one: a solve of a time step repeats the count of the step
+        # before, and every iteration enqueued past the stop is 8 to 22 launches that return at once.  The chunking
+        # changes no bit: the loop freezes in the iteration where it stops.
+        every = poll_every or POLL_EVERY
+        first = every if self.last_count is None else max(1, min(every, self.last_count + 1))
+        out = run_chunked(self.enqueue, self.poll, 0, min(first, maxsteps), first)
+        if not out[0] and first < maxsteps:
+            out = run_chunked(self.enqueue, self.poll, first, maxsteps, every)
+        done, it_final, self.code = out
+        self.last_count = it_final + 1 if done else maxsteps
+        return self.last_count
+
+    def solve(self, b, x, precision, maxsteps, poll_every=None):
+        """As `solve_resident`, with the history read back.  Returns (iterations, errors, code), errors[0] = |b|."""
+        count = self.solve_resident(b, x, precision, maxsteps, poll_every)
+        err0 = float(self.eng.to_host(self.scal)[9])
+        return count, [err0] + [float(v) for v in self.eng.to_host(self.hist)[:count]], self.code
+
+
 # The integrators in time live in hipla/stepping.py; their public names stay importable from here.
 from .stepping import (CONVECTION_SCHEMES, HeatIntegrator, HeatRecord, ScalarStepper, StepRecord,  # noqa: E402,F401
                        TimeStepper, check_convection, constants_in_kernel, two_entry_rows, upload_stencil)

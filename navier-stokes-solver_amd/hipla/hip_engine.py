@@ -138,6 +138,12 @@ def _signatures():
         "nss_cg_poll": (C.c_int, [vp, c_i32_p, c_i32_p, c_i32_p, vp]),
         "nss_cg_start": (C.c_int, [vp, vp, dbl, vp]),
         "nss_cg_shift_jacobi_f64": (C.c_int, [i64, vp, dbl, dbl, vp, vp, vp]),
+        "nss_bicgstab_workspace": (C.c_int, [vp, c_i64_p, c_i64_p]),
+        "nss_bicgstab_start": (C.c_int, [vp, vp, dbl, vp]),
+        "nss_bicgstab_iterate": (C.c_int, [vp, i32, i32, vp]),
+        "nss_bicgstab_poll": (C.c_int, [vp, c_i32_p, c_i32_p, c_i32_p, c_i32_p, vp]),
+        "nss_bicgstab_apply_f64": (C.c_int, [vp, vp, vp, vp]),
+        "nss_bicgstab_jacobi_f64": (C.c_int, [vp, vp, vp]),
         "nss_step_flux_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "nss_step_rhs_f64": (C.c_int, [vp, vp, vp, vp, vp, vp]),
         "nss_step_project_f64": (C.c_int, [vp, vp, vp, vp, vp, dbl, vp, vp, i64, vp, vp]),

@@ -934,6 +934,104 @@ class CGSolver(BaseMatrix):
         return self
 
 
+class BiCGStabSolver(BaseMatrix):
+    """``BiCGStabSolver(mat, pre, precision, maxsteps, printrates)`` as an operator ``y = mat^-1 x`` for a nonsymmetric
+    `mat` (not in the reference, whose inner solves are all symmetric): right-preconditioned BiCGStab from y = 0, written
+    through the protocol, so it runs on any engine and with any `BaseMatrix`.  With rhat = r0 = x, p = r0,
+    rho = <rhat, r0>, per iteration
+
+        phat = pre p;  v = mat phat;  alpha = rho / <rhat, v>;  s = r - alpha v
+        shat = pre s;  t = mat shat;  omega = <t, s> / <t, t>      (<t, t> == 0: omega = 0)
+        y += alpha phat + omega shat;  r = s - omega t;  stop when |r|_2 < precision |x|_2
+        rho' = <rhat, r>;  beta = (rho'/rho)(alpha/omega);  p = r + beta (p - omega v);  rho = rho'
+
+    `errors` = [|x|_2, |r|_2 after every iteration], `iterations` their count.  A breakdown raises
+    ``FloatingPointError`` naming its code -- 1: <rhat, v> or rho' is zero or not finite, 2: <t, t> == 0 without
+    convergence -- and leaves y at its last iterate.  Native operands (a square `SparseMatrix` or a
+    `hipla.stepping.LinearisedConvection` on the HIP engine, `pre` None, a `DiagonalMatrix` or, for the latter, a
+    `ComponentFastDiagonalization`) run the device-resident loop ``nss_bicgstab_*`` (`hipla.fused.BicgstabLoop`)."""
+
+    def __init__(self, mat, pre=None, precision=1e-8, maxsteps=200, printrates=False):
+        super().__init__()
+        self.mat, self.pre = mat, pre
+        self.precision, self.maxsteps, self.printrates = float(precision), int(maxsteps), printrates
+        self.iterations = 0
+        self.errors = []
+        self._fused = False           # device-resident loop (nss_bicgstab_*), created on first use
+
+    def Height(self):
+        return self.mat.height
+
+    def Width(self):
+        return self.mat.width
+
+    @staticmethod
+    def _breakdown(code, it):
+        raise FloatingPointError("BiCGStabSolver: breakdown, code %d (%s) in iteration %d"
+                                 % (code, "<rhat, v> or rho is zero or not finite" if code == 1 else
+                                    "<t, t> is zero before convergence", it))
+
+    def Mult(self, x, y):
+        from math import isfinite, sqrt
+        from .vector import InnerProduct, Vector
+        if self._fused is False:
+            from .fused import BicgstabLoop
+            self._fused = BicgstabLoop.try_create(self.mat, self.pre)
+        if self._fused is not None and isinstance(x, Vector) and isinstance(y, Vector) and not self.printrates:
+            self.iterations, self.errors, code = self._fused.solve(x.buf, y.buf, self.precision, self.maxsteps)
+            if code:
+                self._breakdown(code, self.iterations)
+            return
+        dot, pre = InnerProduct, self.pre
+        r, rhat, p, v, t, phat, shat = (y.CreateVector() for _ in range(7))
+        y[:] = 0.0
+        r.data = x
+        rhat.data = x
+        p.data = x
+        rho = dot(rhat, r)
+        err0 = sqrt(abs(rho))
+        self.errors = [err0]
+        self.iterations = 0
+        if err0 == 0.0:
+            return
+        if not isfinite(rho):
+            self._breakdown(1, 0)
+        for it in range(self.maxsteps):
+            phat.data = pre * p if pre is not None else p
+            v.data = self.mat * phat
+            rv = dot(rhat, v)
+            if rv == 0.0 or not isfinite(rv) or not isfinite(rho / rv):
+                self._breakdown(1, it)
+            alpha = rho / rv
+            r.data -= alpha * v                              # s, in the place of r
+            shat.data = pre * r if pre is not None else r
+            t.data = self.mat * shat
+            ts, tt = dot(t, r), dot(t, t)
+            omega = 0.0 if tt == 0.0 else ts / tt
+            if not isfinite(omega):
+                self._breakdown(1, it)
+            y.data += alpha * phat + omega * shat
+            r.data -= omega * t
+            rho_new, rr = dot(rhat, r), dot(r, r)
+            err = sqrt(rr) if rr >= 0.0 else float("nan")
+            self.errors.append(err)
+            self.iterations = it + 1
+            if self.printrates:
+                print("it = ", it, " err = ", err)
+            if err < self.precision * err0:
+                break
+            if not isfinite(rr):
+                self._breakdown(1, it)
+            if omega == 0.0:
+                self._breakdown(2, it)
+            if rho_new == 0.0 or not isfinite(rho_new):
+                self._breakdown(1, it)
+            beta = (rho_new / rho) * (alpha / omega)
+            p.data -= omega * v
+            p.data = r + beta * p
+            rho = rho_new
+
+
 class Embedding(BaseMatrix):
     """``Embedding(height, range)``: places a vector of ``len(range)`` entries at rows
     ``range.start .. range.stop`` of a zero vector of ``height`` entries; ``.T`` restricts.  The reference

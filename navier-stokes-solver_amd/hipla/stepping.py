@@ -10,7 +10,7 @@ import numpy as np
 from . import fdm, fused
 from .amg import SmoothedAggregationAMG
 from .fused import NO_PRE, CgLoop, FusedLoop, _hip, pre_for
-from .matrix import JacobiPreconditioner, ScaledMatrix, SparseMatrix, SumMatrix
+from .matrix import BaseMatrix, DiagonalMatrix, JacobiPreconditioner, ScaledMatrix, SparseMatrix, SumMatrix
 from .vector import Vector
 
 
@@ -287,6 +287,145 @@ class ScalarFlux(ConvectiveFlux):
                                                                CONVECTION_SCHEMES[self.scheme], *tail))
 
 
+CONVECTION_TREATMENTS = ("explicit", "implicit")
+
+
+def check_convection_treatment(treatment, who):
+    if treatment not in CONVECTION_TREATMENTS:
+        raise ValueError("%s: the convection treatment is \"explicit\" or \"implicit\", not %r" % (who, treatment))
+    return treatment
+
+
+class LinearisedConvection(BaseMatrix):
+    """The operator of the linearly implicit (Picard-linearised) convection step as a protocol operator,
+
+        y = m v + sigma (L v + Dv F(a; v)),     F(a; v)_i = a_i (Avg v)_i - |a_i| (Diff v)_i / 2,
+
+    form (ii) of the BiCGStab loop (csrc/bicgstab.hip).  `system_ops`: dict of scipy matrices -- "avg", "diff" (flux
+    points x n), "div" = Dv (n x flux points) and, for the velocity, "adv" = I_adv (`StokesSystem.convection_operators()`
+    as it stands); without "adv" the advecting vector is the frozen operand itself (the scalar: the face velocities,
+    with avg, diff of `scalar_operators` and "div" = B).  `mass`: host array m; `lap`: scipy L (A, or K).
+    `freeze(u)` does a = I_adv u (one SpMV; a copy without "adv"); `sigma` is a property.  On the HIP engine with native
+    operands `Mult` is the loop's own apply (``nss_bicgstab_apply_f64``: the flux launch and the rows of [L | Dv]) and
+    `hipla.BiCGStabSolver` runs the device-resident loop on it; on any other engine the statements go through the
+    protocol.  `jacobi()`: the point-Jacobi preconditioner of the whole operator for the current a and sigma (a
+    `DiagonalMatrix`, the same object every time, rewritten in place)."""
+
+    def __init__(self, system_ops, mass, lap, sigma=0.0, engine=None):
+        import scipy.sparse as sp
+        super().__init__()
+        if engine is None:
+            from .engine import get_engine
+            engine = get_engine()
+        self.engine = engine
+        self.ops = {key: sp.csr_matrix(system_ops[key]) for key in ("adv", "avg", "diff", "div") if key in system_ops}
+        self.lap = sp.csr_matrix(lap)
+        self.mass_host = np.ascontiguousarray(mass, dtype=np.float64)
+        self.n, self.nflux = self.ops["avg"].shape[1], self.ops["avg"].shape[0]
+        if self.lap.shape != (self.n, self.n) or self.ops["div"].shape != (self.n, self.nflux) or \
+                self.ops["diff"].shape != (self.nflux, self.n) or self.mass_host.shape != (self.n,):
+            raise ValueError("LinearisedConvection: the shapes of avg, diff, div, lap and mass do not fit")
+        self.sigma = sigma
+        self.adv = SparseMatrix.from_scipy(self.ops["adv"], engine=engine) if "adv" in self.ops else None
+        self.a = Vector(self.nflux, engine=engine)
+        self._protocol = self._device = self._jacobi = None
+        self._frozen = False
+
+    @property
+    def sigma(self):
+        return self._sigma
+
+    @sigma.setter
+    def sigma(self, value):
+        value = float(value)
+        if not (value >= 0.0 and np.isfinite(value)):
+            raise ValueError("LinearisedConvection: sigma is non-negative and finite, not %r" % (value,))
+        self._sigma = value
+
+    def Height(self):
+        return self.n
+
+    def Width(self):
+        return self.n
+
+    def freeze(self, u):
+        """a = I_adv u (without "adv": a = u), held until the next call."""
+        if self.adv is not None:
+            self.a.data = self.adv * u
+        else:
+            self.a.data = u
+        self._frozen = True
+
+    def device_form(self):
+        """The `fused.ConvectiveForm` of the operator on the HIP engine (built on first use), or None: another engine,
+        ``fused.ENABLED`` off, a library without the loop, or a row of avg or diff with more than two entries."""
+        import scipy.sparse as sp
+        eng = self.engine
+        if not fused.ENABLED or not _hip(eng) or not hasattr(eng.lib, "nss_bicgstab_apply_f64") or \
+                ConvectiveFlux.declined(self.ops, ("avg", "diff")) is not None or not isinstance(self.a, Vector):
+            return None
+        if self._device is None:
+            rows = sp.hstack([self.lap, self.ops["div"]], format="csr")
+            rows.sort_indices()
+            form = fused.ConvectiveForm(SparseMatrix.from_scipy(rows, engine=eng),
+                                        SparseMatrix.from_scipy(self.ops["avg"], engine=eng),
+                                        SparseMatrix.from_scipy(self.ops["diff"], engine=eng), self.a.buf,
+                                        fused.ConvectiveForm.mass_operand(eng, self.mass_host))
+            self._device = (form, fused.BicgstabLoop(eng, form.rows, form=form, op=self), eng.zeros(self.n + self.nflux))
+        return self._device[0]
+
+    def _statements(self):
+        if self._protocol is None:
+            eng = self.engine
+            self._protocol = dict(avg=SparseMatrix.from_scipy(self.ops["avg"], engine=eng),
+                                  diff=SparseMatrix.from_scipy(self.ops["diff"], engine=eng),
+                                  div=SparseMatrix.from_scipy(self.ops["div"], engine=eng),
+                                  lap=SparseMatrix.from_scipy(self.lap, engine=eng),
+                                  mass=DiagonalMatrix(self.mass_host, engine=eng))
+            self._protocol.update(work=[self._protocol["avg"].CreateColVector() for _ in range(3)])
+        return self._protocol
+
+    def Mult(self, x, y):
+        if not self._frozen:
+            raise ValueError("LinearisedConvection: freeze(u) comes before the first product")
+        if isinstance(x, Vector) and isinstance(y, Vector) and self.device_form() is not None:
+            _, loop, operand = self._device
+            loop.set_sigma(self._sigma)
+            self.engine.copy(x.buf, self.engine.view(operand, 0, self.n))
+            loop.apply(operand, y.buf)
+            return
+        p = self._statements()
+        avg, dif, flux = p["work"]
+        avg.data = p["avg"] * x
+        dif.data = p["diff"] * x
+        flux.engine.upwind_flux(self.a.buf, avg.buf, dif.buf, flux.buf)
+        y.data = p["mass"] * x
+        y.data += self._sigma * (p["lap"] * x)
+        y.data += self._sigma * (p["div"] * flux)
+
+    def to_scipy(self, a=None):
+        """The operator assembled on the host for the frozen a (or the host array `a`): what tests hand to spsolve."""
+        import scipy.sparse as sp
+        a = self.a.numpy() if a is None else np.asarray(a, dtype=np.float64)
+        conv = self.ops["div"] @ (sp.diags(a) @ self.ops["avg"] - sp.diags(0.5 * np.abs(a)) @ self.ops["diff"])
+        return (sp.diags(self.mass_host) + self._sigma * (self.lap + conv)).tocsr()
+
+    def jacobi(self):
+        """The inverse diagonal of the operator for the current a and sigma: one launch on the device
+        (``nss_bicgstab_jacobi_f64``), the assembled diagonal on the host otherwise."""
+        if not self._frozen:
+            raise ValueError("LinearisedConvection: freeze(u) comes before jacobi()")
+        if self._jacobi is None:
+            self._jacobi = DiagonalMatrix(np.ones(self.n), engine=self.engine)
+        if self.device_form() is not None:
+            loop = self._device[1]
+            loop.set_sigma(self._sigma)
+            loop.write_jacobi(self._jacobi.d)
+        else:
+            self.engine.upload(1.0 / self.to_scipy().diagonal(), self._jacobi.d)
+        return self._jacobi
+
+
 class StepRecord:
     """What `NavierStokes.Advance` returns: one entry per step of `mstar_iterations`, `proj_iterations` (pseudo time
     stepping: the two projections of a step added), `div_norm` = |B u| and `kinetic_energy` = <u, M_u u> / 2 after the
@@ -299,13 +438,16 @@ class StepRecord:
     within the call, `cfl` = tau_n * rate(u^n), and with `cfl=` also `limited_by` = the codes of `choose_timestep`.
     `projection`: "cg", or "fdm" -- the direct solve of `NavierStokes.SetProjection("fdm")`, whose `proj_iterations` are
     all zero.  `implicit`: "cg", or "fdm" -- the direct velocity and scalar solves of `NavierStokes.SetImplicitSolve("fdm")`,
-    whose `mstar_iterations` and `scalar_iterations` are all zero."""
+    whose `mstar_iterations` and `scalar_iterations` are all zero.  `convection_treatment`: "explicit", or "implicit" --
+    the linearly implicit convection of `NavierStokes.SetConvectionTreatment("implicit")`, whose `mstar_iterations` and
+    `scalar_iterations` count BiCGStab iterations (with `implicit` = "fdm": preconditioned by the direct solve)."""
 
     def __init__(self, mstar_iterations, proj_iterations, div_norm, kinetic_energy, declined=None, flux_declined=None,
                  scalar_iterations=None, wall_flux=None, convection="upwind", time_scheme="euler", timestep=None,
-                 time=None, cfl=None, limited_by=None, projection="cg", implicit="cg"):
+                 time=None, cfl=None, limited_by=None, projection="cg", implicit="cg", convection_treatment="explicit"):
         self.timestep, self.time, self.cfl, self.limited_by = timestep, time, cfl, limited_by
         self.projection, self.implicit = projection, implicit
+        self.convection_treatment = convection_treatment
         self.mstar_iterations = np.asarray(mstar_iterations, dtype=np.int64)
         self.proj_iterations = np.asarray(proj_iterations, dtype=np.int64)
         self.div_norm, self.kinetic_energy = div_norm, kinetic_energy
@@ -374,7 +516,8 @@ class TimeStepper(FusedLoop):
 
     @classmethod
     def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
-                   convection="upwind", time_scheme="euler", variable=False, m_p=None, projection="cg", implicit="cg"):
+                   convection="upwind", time_scheme="euler", variable=False, m_p=None, projection="cg", implicit="cg",
+                   convection_treatment="explicit"):
         """`system`: the `StokesSystem` (its `convection_operators`); `A`, `B`: `SparseMatrix`; `f`: `Vector`;
         `m_u`: host array, the lumped velocity mass; `inner_pre`: "jacobi" | "amg", the preconditioner of both inner
         solves; `conv_operator`: callable giving the protocol `ConvectionOperator`, used when the flux kernel declines
@@ -394,9 +537,13 @@ class TimeStepper(FusedLoop):
         `system.component_ids`, kept under "fdm_u" in `shared` (built when missing; the stepper declines with the reason
         when A does not factor), with sigma = the step size ("euler") or half of it ("cnab2"): no mstar / mhalf, no `cg_m`,
         no `pre_m` and no hierarchy of the velocity operator are built, and a variable-step stepper takes any `inner_pre`,
-        which then concerns a "cg" projection alone.  Returns None, the reason in `last_declined`."""
+        which then concerns a "cg" projection alone.  `convection_treatment`: "explicit", or "implicit" -- the velocity
+        solve is then the BiCGStab loop (`fused.BicgstabLoop`) on M_u + sigma (A + N(a)) read from [A | D] itself, a =
+        I_adv u^n frozen once per step, preconditioned by the point-Jacobi diagonal of the whole operator (`implicit` =
+        "cg") or by the direct viscous inverse (`implicit` = "fdm"); "euler" and "upwind" only, any step size, no mstar.
+        Returns None, the reason in `last_declined`."""
         return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection,
-                                            time_scheme, variable, m_p, projection, implicit))
+                                            time_scheme, variable, m_p, projection, implicit, convection_treatment))
 
     @staticmethod
     def _projection_matrices(eng, B, m_u, shared):
@@ -411,7 +558,12 @@ class TimeStepper(FusedLoop):
 
     @classmethod
     def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme,
-                    variable=False, m_p=None, projection="cg", implicit="cg"):
+                    variable=False, m_p=None, projection="cg", implicit="cg", convection_treatment="explicit"):
+        check_convection_treatment(convection_treatment, "TimeStepper")
+        if convection_treatment == "implicit" and (time_scheme != "euler" or convection != "upwind" or
+                                                   (inner_pre != "jacobi" and implicit != "fdm")):
+            raise ValueError("implicit convection goes with time_scheme=\"euler\", convection=\"upwind\" and "
+                             "inner_pre=\"jacobi\"")
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
         if projection not in ("cg", "fdm"):
@@ -438,6 +590,13 @@ class TimeStepper(FusedLoop):
                 shared["flux_declined"] = MomentumFlux.declined(system.convection_operators())
             if shared["flux_declined"] is not None:
                 return "cnab2: the flux kernel declines the convection operators: " + shared["flux_declined"]
+        if convection_treatment == "implicit":
+            if not hasattr(A.engine.lib, "nss_bicgstab_iterate"):
+                return "the library has no BiCGStab loop"
+            if "flux_declined" not in shared:
+                shared["flux_declined"] = MomentumFlux.declined(system.convection_operators())
+            if shared["flux_declined"] is not None:
+                return "implicit convection: the flux kernel declines the convection operators: " + shared["flux_declined"]
         if variable and not hasattr(A.engine.lib, "nss_step_cfl_f64"):
             return "the library has no CFL rate kernel"
         if projection == "fdm" and shared.get("fdm") is None:
@@ -457,14 +616,17 @@ class TimeStepper(FusedLoop):
                 return "fdm: " + fdm.ComponentFastDiagonalization.last_declined
             shared["fdm_u"] = made
         return cls(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme, variable,
-                   m_p, projection, implicit)
+                   m_p, projection, implicit, convection_treatment)
 
     def __init__(self, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection="upwind",
-                 time_scheme="euler", variable=False, m_p=None, projection="cg", implicit="cg"):
+                 time_scheme="euler", variable=False, m_p=None, projection="cg", implicit="cg",
+                 convection_treatment="explicit"):
         import scipy.sparse as sp
         eng = self.eng = A.engine
         self.time_scheme, self.variable = time_scheme, bool(variable)
         self.projection, self.implicit = projection, implicit
+        self.convection_treatment = convection_treatment
+        implicit_conv = convection_treatment == "implicit"     # the velocity solve is the BiCGStab loop: no mstar, no cg_m
         self.fdm = shared["fdm"] if projection == "fdm" else None
         if self.fdm is not None and self.fdm.handle is None:
             raise ValueError("TimeStepper: the FastDiagonalization holds no device handle")
@@ -501,11 +663,12 @@ class TimeStepper(FusedLoop):
         self.rhs_p, self.phi = eng.zeros(self.n_p), eng.zeros(self.n_p)
         # ---- the inner solves ----
         direct_m = self.fdm_u is not None           # the velocity solve is the direct one: no mstar, no cg_m, no pre_m
-        if not variable and not direct_m and mstar_key not in shared:   # M_u + timestep A, or M_u + timestep/2 A
+        if not variable and not direct_m and not implicit_conv and mstar_key not in shared:   # M_u + timestep (/2) A
             theta = 0.5 * self.timestep if cnab2 else self.timestep
             shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(m_u) + theta * A.to_scipy()).tocsr(), engine=eng)
         self._projection_matrices(eng, B, m_u, shared)
-        self.mstar, self.Lp, self.C = None if variable or direct_m else shared[mstar_key], shared["Lp"], shared["C"]
+        self.mstar = None if variable or direct_m or implicit_conv else shared[mstar_key]
+        self.Lp, self.C = shared["Lp"], shared["C"]
         if "singular" not in shared:
             ok, why = two_entry_rows(self.C.to_scipy())
             if not ok:
@@ -513,7 +676,7 @@ class TimeStepper(FusedLoop):
             shared["singular"] = constants_in_kernel(self.Lp.to_scipy())
         self.singular = shared["singular"]
         direct = self.fdm is not None               # the projection is the direct solve: no cg_p, no pre_p
-        if direct_m:                                # (`inner_pre` concerns a "cg" projection alone)
+        if direct_m or implicit_conv:               # (`inner_pre` concerns a "cg" projection alone)
             self.pre_m = self.cg_m = None
             self.pre_p = None if direct else JacobiPreconditioner(self.Lp) if inner_pre != "amg" else \
                 SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
@@ -535,6 +698,13 @@ class TimeStepper(FusedLoop):
                 self.pre_p = None if direct else JacobiPreconditioner(self.Lp)
             self.cg_m = CgLoop(eng, self.mstar, pre_for("cg", self.pre_m))
         self.cg_p = None if direct else CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
+        self.bicg_m = None
+        if implicit_conv:                           # form (ii) over the stepper's own [A | D], a = I_adv u^n in `self.a`
+            self.a = eng.zeros(max(1, self.nflux))
+            form = fused.ConvectiveForm(self.AD, self.avg, self.diff, self.a, fused.ConvectiveForm.mass_operand(eng, m_u))
+            self.dinv_m = None if direct_m else eng.zeros(self.n_u)
+            self.bicg_m = fused.BicgstabLoop(eng, self.AD, self.dinv_m, form, self.fdm_u)
+            self.u_back, self.phi_back = eng.zeros(self.n_u), eng.zeros(self.n_p)
         # ---- the record ----
         uniform = bool(m_u.size) and bool((m_u == m_u[0]).all())
         self.mass = None if uniform else eng.from_host(m_u)
@@ -625,6 +795,8 @@ class TimeStepper(FusedLoop):
             raise ValueError("advance: variable steps want the clock and do no pseudo time stepping")
         if self.variable and scalar is not None and not scalar.variable:
             raise ValueError("advance: the scalar stepper is not a variable-step one")
+        if self.bicg_m is not None and (pseudo or (scalar is not None and scalar.bicg is None)):
+            raise ValueError("advance: implicit convection does no pseudo time stepping and takes an implicit scalar stepper")
         if timesteps is not None:
             timesteps = [check_step_size(t, "advance") for t in timesteps]
             if len(timesteps) != nsteps or controller is not None:
@@ -681,7 +853,22 @@ class TimeStepper(FusedLoop):
                 self.right_hand_side(force)
             else:
                 self.right_hand_side(None if scalar is None else scalar.flux(self.u))     # (S1,) F1, F2  :429-431
-            if self.fdm_u is not None:              # (the pseudo time stepping is an "euler" stepper's: sigma = timestep)
+            if self.bicg_m is not None:
+                if scalar is not None:              # (a breakdown of the scalar's solve puts this state back)
+                    eng.copy(self.u, self.u_back)
+                    eng.copy(self.phi, self.phi_back)
+                if self.nflux:
+                    eng.csr_spmv(self.adv.handle, 1.0, self.u, 0.0, self.a)       # a = I_adv u^n, frozen for the step
+                self.bicg_m.set_sigma(self.timestep if tau is None else tau)
+                if self.dinv_m is not None:
+                    self.bicg_m.write_jacobi(self.dinv_m)
+                count_m = self.bicg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0])
+                if self.bicg_m.code:                # (u is still u^n: the last finished step)
+                    failure = FloatingPointError("Advance: the velocity solve of step %d broke down, code %d (%s)"
+                                                 % (step, self.bicg_m.code, self.bicg_m.CODES[self.bicg_m.code]))
+                    break
+                its_m.append(count_m)
+            elif self.fdm_u is not None:            # (the pseudo time stepping is an "euler" stepper's: sigma = timestep)
                 size = self.timestep if tau is None else tau
                 its_m.append(self.fdm_u.solve_resident(self.temp, self.raw, 0.5 * size if cnab2 else size))
             else:
@@ -696,7 +883,15 @@ class TimeStepper(FusedLoop):
             if diagnostics:
                 self.write_record(record, step)
             if scalar is not None:
-                its_s.append(scalar.step(record_s, step, tau))                    # S2, the solve, S3, S4
+                try:
+                    its_s.append(scalar.step(record_s, step, tau))                # S2, the solve, S3, S4
+                except FloatingPointError as err:   # (implicit convection: T is still T^n; u and phi go back)
+                    failure = err
+                    eng.copy(self.u_back, self.u)
+                    eng.copy(self.phi_back, self.phi)
+                    its_m.pop()
+                    its_p.pop()
+                    break
             if not pseudo:
                 tau_prev = self.timestep if tau is None else tau
         nsteps = len(its_m)                                               # (a duration may end the call early)
@@ -729,7 +924,8 @@ class TimeStepper(FusedLoop):
                 extra = variable_record(taus, host[nrec:], codes)
         return StepRecord(its_m, its_p, div, energy, flux_declined=self.flux_declined, convection=self.convection,
                           scalar_iterations=its_s, wall_flux=wall, time_scheme=self.time_scheme,
-                          projection=self.projection, implicit=self.implicit, **extra)
+                          projection=self.projection, implicit=self.implicit,
+                          convection_treatment=self.convection_treatment, **extra)
 
 
 class ScalarStepper:
@@ -749,7 +945,7 @@ class ScalarStepper:
 
     def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
                  maxsteps=None, shared=None, convection="upwind", stencil=None, time_scheme="euler", variable=False,
-                 implicit="cg", extents=None):
+                 implicit="cg", extents=None, convection_treatment="explicit"):
         """`ops`: `StokesSystem.scalar_operators(...)`; `B`: the divergence (`SparseMatrix`); `f`: the force `Vector`
         the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
         (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
@@ -758,10 +954,19 @@ class ScalarStepper:
         when missing) with the sigma of each step, Jacobi only.  `implicit`: "cg", or "fdm" -- the solve launches
         ``nss_fdmc_solve_f64`` of the `hipla.fdm.ComponentFastDiagonalization` of K over the cells, kept under "fdm_T" in
         `shared` (built when missing, over the grid `extents`; ``ValueError`` with the reason when K does not factor),
-        with the sigma of each step: no mstar / mhalf, no `cg`, no `pre`, any `inner_pre`."""
+        with the sigma of each step: no mstar / mhalf, no `cg`, no `pre`, any `inner_pre`.  `convection_treatment`:
+        "explicit", or "implicit" -- the solve is the BiCGStab loop on M_p + sigma (K + B G(u^n; .)) read from [K | B]
+        itself, u^n copied by `flux`, preconditioned by the point-Jacobi diagonal of the whole operator or (`implicit` =
+        "fdm") by (M_p + sigma K)^-1; "euler" and "upwind" only.  A breakdown makes `step` raise ``FloatingPointError``
+        before T is touched."""
         import scipy.sparse as sp
         shared = {} if shared is None else shared
         self.variable = bool(variable)
+        implicit_conv = check_convection_treatment(convection_treatment, "ScalarStepper") == "implicit"
+        if implicit_conv and (time_scheme != "euler" or convection != "upwind" or
+                              (inner_pre != "jacobi" and implicit != "fdm")):
+            raise ValueError("ScalarStepper: implicit convection goes with time_scheme=\"euler\", convection=\"upwind\" "
+                             "and inner_pre=\"jacobi\"")
         if implicit not in ("cg", "fdm"):
             raise ValueError("ScalarStepper: implicit is \"cg\" or \"fdm\"")
         self.implicit = implicit
@@ -796,6 +1001,8 @@ class ScalarStepper:
                 shared["fdm_T"] = made
             if shared["fdm_T"].handle is None:
                 raise ValueError("ScalarStepper: the ComponentFastDiagonalization holds no device handle")
+        elif implicit_conv:
+            pass                                    # (the loop reads K from [K | B])
         elif variable:
             if "K" not in shared:
                 shared["K"] = SparseMatrix.from_scipy(sp.csr_matrix(ops["K"]), engine=eng)
@@ -806,7 +1013,7 @@ class ScalarStepper:
             shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + theta * ops["K"]).tocsr(), engine=eng)
         self.KB, self.q, self.w_b, self.w = (shared[key] for key in ("KB", "q", "w_b", "w"))
         self.fdm = shared["fdm_T"] if implicit == "fdm" else None
-        self.mstar = None if variable or self.fdm is not None else shared[mstar_key]
+        self.mstar = None if variable or implicit_conv or self.fdm is not None else shared[mstar_key]
         self.c0, self.records = (0.0 if flux is None else float(flux[0])), flux is not None
         self.tg = eng.zeros(self.n_p + self.n_u)             # the operand [T | G]
         self.T, self.G = eng.view(self.tg, 0, self.n_p), eng.view(self.tg, self.n_p, self.n_p + self.n_u)
@@ -815,7 +1022,15 @@ class ScalarStepper:
             self.G_prev = eng.zeros(self.n_u)
             self.b_prev = None if w_b is None else eng.zeros(self.n_u)
         self.temp, self.delta = eng.zeros(self.n_p), eng.zeros(self.n_p)
-        if self.fdm is not None:
+        self.bicg = None
+        if implicit_conv:                           # form (ii) over [K | B], the frozen u^n in `self.a`
+            self.pre = self.cg = None
+            self.a = eng.zeros(self.n_u)
+            form = fused.ConvectiveForm(self.KB, self.avg, self.diff, self.a,
+                                        fused.ConvectiveForm.mass_operand(eng, ops["mass"]))
+            self.dinv = None if self.fdm is not None else eng.zeros(self.n_p)
+            self.bicg = fused.BicgstabLoop(eng, self.KB, self.dinv, form, self.fdm)
+        elif self.fdm is not None:
             self.pre = self.cg = None
         elif variable:
             self.pre = None
@@ -831,6 +1046,8 @@ class ScalarStepper:
     def flux(self, u):
         """S1 on (u, T): G, and for a buoyant scalar f_eff.  Returns the force buffer of the velocity step (None: f)."""
         self.scalar_flux.launch(u, self.f.buf, self.T, self.t_ref, self.G, self.w_b, self.f_eff)
+        if self.bicg is not None:
+            self.eng.copy(u, self.a)                # u^n, frozen for the scalar's solve behind the velocity step
         return self.f_eff
 
     def flux_ab2(self, u, weights):
@@ -861,7 +1078,15 @@ class ScalarStepper:
             self.cg.set_shift(sigma)
         eng._check(lib.nss_step_rhs_f64(self.KB.handle.ptr, self.tg.data_ptr(), self.q.data_ptr(), self.temp.data_ptr(),
                                         None, eng.stream))
-        if self.fdm is not None:
+        if self.bicg is not None:
+            self.bicg.set_sigma(sigma)
+            if self.dinv is not None:
+                self.bicg.write_jacobi(self.dinv)
+            its = self.bicg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
+            if self.bicg.code:
+                raise FloatingPointError("Advance: the scalar's solve of step %d broke down, code %d (%s)"
+                                         % (slot, self.bicg.code, self.bicg.CODES[self.bicg.code]))
+        elif self.fdm is not None:
             its = self.fdm.solve_resident(self.temp, self.delta, sigma)
         else:
             its = self.cg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)

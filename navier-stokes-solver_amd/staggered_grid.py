@@ -359,6 +359,32 @@ class StokesSystem:
                 out[g[idx]] = -hface * total
         return out
 
+    # ---- linearly implicit (Picard-linearised) convection: the host restatements --------------------------------------
+    def linearised_convection(self, a, ops=None):
+        """N(a) as scipy CSR (n_u x n_u): N(a) v = D F(a; v) with the donor-cell flux F(a; v)_i = a_i (Avg v)_i -
+        |a_i| (Diff v)_i / 2, linear in v for the frozen advecting vector `a` (one entry per flux point; the step takes
+        a = I_adv u^n).  With a = I_adv u it reproduces the explicit term: N(I_adv u) u == -conv(u).  `ops`:
+        `convection_operators()`, when the caller holds them."""
+        ops = self.convection_operators() if ops is None else ops
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (ops["avg"].shape[0],):
+            raise ValueError("linearised_convection: a holds %s entries, the grid has %d flux points"
+                             % (a.shape, ops["avg"].shape[0]))
+        out = (ops["div"] @ (sp.diags(a) @ ops["avg"] - sp.diags(0.5 * np.abs(a)) @ ops["diff"])).tocsr()
+        out.sort_indices()
+        return out
+
+    def linearised_scalar_convection(self, u, ops):
+        """B G(u; .) as scipy CSR (n_p x n_p): G(u; T)_r = u_r (avg T)_r - |u_r| (diff T)_r / 2 with avg and diff of
+        `ops` = `scalar_operators(...)`, linear in T for the frozen face velocities `u`: the convective part of the
+        scalar's linearly implicit step, B G(u; T) == -scalar_convection_reference(u, T)."""
+        u = np.asarray(u, dtype=np.float64)
+        if u.shape != (self.n_u,):
+            raise ValueError("linearised_scalar_convection: u holds %s entries, the grid has %d faces" % (u.shape, self.n_u))
+        out = (self.B @ (sp.diags(u) @ ops["avg"] - sp.diags(0.5 * np.abs(u)) @ ops["diff"])).tocsr()
+        out.sort_indices()
+        return out
+
     # ---- second-order limited convection: the four-point stencils and their evaluations ------------------------------
     def convection_stencil(self):
         """int32 (nflux, 4): the dofs (ll, lo, hi, hh) of the transported component along the flux direction at

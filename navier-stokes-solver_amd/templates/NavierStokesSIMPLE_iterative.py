@@ -36,6 +36,9 @@ sizes than the constructor's, the last one chosen from that rate (DESIGN.md sect
 ``SetProjection("fdm")`` replaces the CG solve of the projection by the direct solve of the fast diagonalisation method
 (`hipla.FastDiagonalization`; not in the reference).  ``SetImplicitSolve("fdm")`` does the same for
 the velocity solve and the scalar's (`hipla.ComponentFastDiagonalization`; not in the reference).
+``SetConvectionTreatment("implicit")`` makes convection and the scalar's transport linearly implicit: the velocity solve
+becomes a BiCGStab solve with ``M_u + timestep (A + N(a))``, a = I_adv u^n (`hipla.BiCGStabSolver`,
+`hipla.stepping.LinearisedConvection`; not in the reference).
 
 Out of scope: the MCS/HDG assembly itself and the sparse direct branch
 ``iterative=False`` (raises ``NotImplementedError``)."""
@@ -44,9 +47,10 @@ import numpy as np
 import scipy.sparse as sp
 
 import hipla
-from hipla import BlockVector, CGSolver, ComponentFastDiagonalization, FastDiagonalization, fused
-from hipla.stepping import (CflRate, MomentumFlux, ScalarFlux, ScalarStepper, StepController, StepRecord, TimeHistory,
-                            TimeStepper, check_convection, check_step_size, check_time_scheme, pair, variable_record)
+from hipla import BiCGStabSolver, BlockVector, CGSolver, ComponentFastDiagonalization, FastDiagonalization, fused
+from hipla.stepping import (CflRate, LinearisedConvection, MomentumFlux, ScalarFlux, ScalarStepper, StepController,
+                            StepRecord, TimeHistory, TimeStepper, check_convection, check_convection_treatment,
+                            check_step_size, check_time_scheme, pair, variable_record)
 from discretizations import AssembledForm, CondensedForm, SyntheticMesh, assemble, bdm_hybrid
 from solvers.bramblepasciak_new import BramblePasciakCG
 
@@ -232,6 +236,7 @@ class ScalarField:
         self.steppers, self.shared = {}, {}
         self.by_step = {}                 # step size -> the CG inverse of M_p + theta K (`DoTimeStep(timestep=)`)
         self.last_solver = None
+        self.lin = self.lin_inv = None    # the linearly implicit transport (`implicit_solver`), built on first use
 
     @property
     def solver(self):
@@ -256,6 +261,32 @@ class ScalarField:
             self.by_step[tau] = CGSolver(mat, pre=hipla.JacobiPreconditioner(mat))
         inv = self.last_solver = self.by_step[tau]
         inv.precision, inv.maxsteps = self.solver.precision, self.solver.maxsteps
+        return inv
+
+    def linearised(self, b_scipy):
+        """The `LinearisedConvection` of the scalar over avg, diff and B = `b_scipy` (built on first use, with its
+        BiCGStab inverse `lin_inv`); the caller freezes u^n into it at the head of a step."""
+        if self.lin is None:
+            self.lin = LinearisedConvection(dict(avg=self.ops["avg"], diff=self.ops["diff"], div=b_scipy),
+                                            self.ops["mass"], self.ops["K"], self.timestep)
+            self.lin_inv = BiCGStabSolver(self.lin, None, precision=self.precision, maxsteps=self.maxsteps)
+        return self.lin
+
+    def implicit_solver(self, b_scipy, tau):
+        """The BiCGStab inverse of M_p + sigma (K + B G(u^n; .)) for a step of size `tau` (None: the object's own), u^n
+        frozen by the caller (``self.lin.freeze``): the `LinearisedConvection` over avg, diff and B, built on first use,
+        preconditioned by the point-Jacobi diagonal of the whole operator or, with `implicit` at "fdm", by
+        (M_p + sigma K)^-1."""
+        self.linearised(b_scipy)
+        inv = self.last_solver = self.lin_inv
+        self.lin.sigma = self.timestep if tau is None else tau
+        if self.implicit == "fdm":
+            pre = self.direct_solver()
+            pre.sigma = self.lin.sigma
+        else:
+            pre = self.lin.jacobi()
+        if inv.pre is not pre:
+            inv.pre, inv._fused = pre, False
         return inv
 
     def direct_solver(self):
@@ -317,6 +348,9 @@ class NavierStokes:
         self._fdm = None                  # the `FastDiagonalization` of Lp, built by the first SetProjection("fdm")
         self._implicit = "cg"             # how the velocity and the scalar solve (`SetImplicitSolve`)
         self._fdm_u = None                # the `ComponentFastDiagonalization` of A, built by the first SetImplicitSolve("fdm")
+        self._convection_treatment = "explicit"   # or "implicit" (`SetConvectionTreatment`)
+        self._lin_conv = None             # the `LinearisedConvection` of the velocity and its BiCGStab inverse
+        self._conv_replaced = False       # the user set `conv_operator`
 
     @property
     def projection(self):
@@ -388,6 +422,74 @@ class NavierStokes:
             self._scalar.implicit = kind
 
     @property
+    def convection_treatment(self):
+        """"explicit" or "implicit": see `SetConvectionTreatment`."""
+        return self._convection_treatment
+
+    def _refuse_implicit_convection(self, who):
+        """``ValueError`` with the reason when the object cannot step with linearly implicit convection."""
+        why = None
+        if self.time_scheme == "cnab2":
+            why = "time_scheme=\"cnab2\" extrapolates the convective flux; the implicit treatment is first order (\"euler\")"
+        elif self.convection != "upwind" or (self._scalar is not None and self._scalar.convection != "upwind"):
+            why = "the limited schemes are not linear in the transported quantity; convection=\"upwind\" only"
+        elif self.system.block_size > 1:
+            why = "block_size > 1: an inflated system is not supported"
+        elif self._conv_replaced:
+            why = "conv_operator was replaced by the user; the linearisation is that of the package's donor-cell operator"
+        if why is not None:
+            raise ValueError("%s: implicit convection: %s" % (who, why))
+
+    def SetConvectionTreatment(self, kind):
+        """How convection (and the transport of the scalar) enters a step, from now on and in `DoTimeStep`,
+        `DoTimeStep(timestep=)` and `Advance` in all its modes: "explicit" (the default: the reference's step) or
+        "implicit", the linearly implicit (Picard-linearised) step
+
+            (M_u + tau A + tau N(a)) raw = conv(u^n) + f - A u^n,    a = I_adv u^n frozen for the step,
+            N(a) v = D F(a; v),   F(a; v)_i = a_i (Avg v)_i - |a_i| (Diff v)_i / 2,
+
+        the reference's step in increment form with the donor-cell flux linearised around u^n -- the right-hand side is
+        unchanged, `Project` and u += tau (raw - C phi) follow as before.  With a scalar:
+        (M_p + tau K + tau B G(u^n; .)) delta = q - K T^n - B G(u^n; T^n); the buoyancy stays lagged.  The solves are
+        right-preconditioned BiCGStab (`hipla.BiCGStabSolver`; in `Advance` the device-resident loop) stopping at
+        |r|_2 < precision |b|_2, `precision` and `maxsteps` with the meaning and defaults they have (1e-4, 500);
+        `SetImplicitSolve` picks the preconditioner: "cg" -- point Jacobi of the whole operator, "fdm" -- the direct
+        viscous inverse (M_u + tau A)^-1, for the scalar (M_p + tau K)^-1.  For a discretely divergence-free a the
+        symmetric part of N(a) is positive semi-definite, so the step does not raise the kinetic energy for any tau: the
+        convective limit on the step size is gone (accuracy still wants a moderate CFL number).
+
+        ``ValueError`` with the reason for `time_scheme="cnab2"`, `convection != "upwind"` (the velocity's or the
+        scalar's), an inflated system and a user-replaced `conv_operator`; `Advance` refuses `pseudo=True` and
+        `inner_pre="amg"` with it.  A breakdown of a solve raises ``FloatingPointError`` and leaves the state of the last
+        finished step.  `SetConvectionTreatment("explicit")` puts the explicit step back: an object that never calls this
+        method, or is back at "explicit", keeps its bits in every entry point."""
+        check_convection_treatment(kind, "SetConvectionTreatment")
+        if kind == "implicit":
+            self._refuse_implicit_convection("SetConvectionTreatment")
+        self._convection_treatment = kind
+
+    def _implicit_momentum_solver(self, tau):
+        """The BiCGStab inverse of M_u + sigma (A + N(a)) for a step of size `tau` (None: the object's own) with
+        a = I_adv gfu frozen here; the operator and the solver are built on first use."""
+        if self._lin_conv is None:
+            s = self.system
+            m_u = np.full(s.n_u, s.h ** s.dim * self.V.dofs_per_site ** 0)
+            op = LinearisedConvection(s.convection_operators(), m_u, s.A, self.timestep)
+            self._lin_conv = dict(op=op, inv=BiCGStabSolver(op, None, precision=1e-4, maxsteps=500))
+        op, inv = self._lin_conv["op"], self._lin_conv["inv"]
+        op.freeze(self.gfu)
+        op.sigma = self.timestep if tau is None else tau
+        if self._implicit == "fdm":
+            pre = self._fdm_u
+            pre.sigma = op.sigma
+        else:
+            pre = op.jacobi()
+        if inv.pre is not pre:
+            inv.pre, inv._fused = pre, False
+        self._last_momentum_solver = inv
+        return inv
+
+    @property
     def conv_operator(self):
         if self._conv_operator is None:
             self._conv_operator = ConvectionOperator(self.system, self.convection)
@@ -396,6 +498,7 @@ class NavierStokes:
     @conv_operator.setter
     def conv_operator(self, op):
         self._conv_operator = op
+        self._conv_replaced = True
 
     def _time_stepping_operators(self):
         """mstar = M_u + timestep*A with its CG inverse (:85-96) and the projection operators
@@ -665,7 +768,10 @@ class NavierStokes:
         sc = self._scalar
         sc.temp.data = sc.q - sc.K * self.temperature
         sc.temp.data -= self.b.mat * sc.G
-        sc.delta.data = sc.solver_for(tau) * sc.temp
+        if self._convection_treatment == "implicit":
+            sc.delta.data = sc.implicit_solver(self.system.B, tau) * sc.temp
+        else:
+            sc.delta.data = sc.solver_for(tau) * sc.temp
         self.temperature.data += (self.timestep if tau is None else tau) * sc.delta
 
     def DoTimeStep(self, timestep=None):
@@ -687,12 +793,37 @@ class NavierStokes:
         temp.data = self.conv_operator * self.gfu        # :429
         temp.data += force
         temp.data += -self.a.mat * self.gfu
+        if self._convection_treatment == "implicit":
+            return self._finish_implicit_step(temp, temp2, tau)
         temp2.data = self._momentum_solver_for(tau) * temp
         self.Project(temp2)
         self.gfu.data += (self.timestep if tau is None else tau) * temp2
         if self._scalar is not None:
             self._scalar_step(tau)
         self._clock.tau_prev = self.timestep if tau is None else tau
+
+    def _finish_implicit_step(self, temp, temp2, tau):
+        """The statements of `DoTimeStep` behind the right-hand side `temp` with linearly implicit convection: the
+        BiCGStab solve with M_u + tau (A + N(I_adv u^n)), the projection, the update, and the scalar's step with u^n
+        frozen before the update.  A breakdown leaves `gfu`, `gfup` and the temperature as they were."""
+        self._refuse_implicit_convection("DoTimeStep")
+        size = self.timestep if tau is None else tau
+        if self._scalar is not None:
+            self._scalar.linearised(self.system.B).freeze(self.gfu)   # u^n, before the update
+        temp2.data = self._implicit_momentum_solver(tau) * temp       # (raises before anything is touched)
+        u_back, p_back = self.gfu.CreateVector(), self.gfup.CreateVector()
+        u_back.data = self.gfu
+        p_back.data = self.gfup
+        self.Project(temp2)
+        self.gfu.data += size * temp2
+        if self._scalar is not None:
+            try:
+                self._scalar_step(tau)
+            except FloatingPointError:
+                self.gfu.data = u_back
+                self.gfup.data = p_back
+                raise
+        self._clock.tau_prev = size
 
     def _extrapolate(self, now, prev, weights, out):
         """out = w_new now + w_old prev;  prev = now  (w_old == 0: `prev` is not read)."""
@@ -822,11 +953,27 @@ class NavierStokes:
         ``record.implicit == "fdm"``, `mstar_iterations` and `scalar_iterations` all zero, no mstar, CG loop,
         preconditioner or velocity hierarchy in the stepper, and variable steps with any `inner_pre`, which then concerns
         a "cg" projection alone.  With both switches at "fdm" a fixed-step call does not wait for the host between its
-        first launch and its read-back."""
+        first launch and its read-back.
+
+        After `SetConvectionTreatment("implicit")` the steppers (keyed by that switch too) solve the velocity, and the
+        scalar, with the device-resident BiCGStab loop on the linearised operator read from `[A | D]` (`[K | B]`), a =
+        I_adv u^n formed once per step; the polls of the loop are the only new host synchronisation.
+        ``record.convection_treatment == "implicit"``, `mstar_iterations` and `scalar_iterations` count BiCGStab
+        iterations, the velocity entries of `precision` and `maxsteps` are the loop's.  ``ValueError`` for `pseudo=True`
+        and `inner_pre="amg"`; a breakdown of a solve leaves the state of the last finished step and raises
+        ``FloatingPointError``."""
         if inner_pre not in ("jacobi", "amg"):
             raise ValueError("Advance: inner_pre is \"jacobi\" or \"amg\"")
         if pseudo and self._scalar is not None:
             raise ValueError("Advance: the pseudo time stepping carries no scalar")
+        treatment = self._convection_treatment
+        if treatment == "implicit":
+            self._refuse_implicit_convection("Advance")
+            if pseudo:
+                raise ValueError("Advance: implicit convection: the pseudo time stepping has no convection term")
+            if inner_pre == "amg":
+                raise ValueError("Advance: implicit convection: inner_pre=\"amg\" is a hierarchy of the symmetric "
+                                 "operator of one step size; the BiCGStab solves take point Jacobi or the direct inverse")
         nsteps = int(nsteps)
         variable = timesteps is not None or cfl is not None
         controller = None
@@ -850,6 +997,7 @@ class NavierStokes:
         key = ("variable", key) if variable else key
         key = (key, "fdm") if self._projection == "fdm" else key
         key = (key, "implicit fdm") if self._implicit == "fdm" else key
+        key = (key, "implicit convection") if treatment == "implicit" else key
         stepper = steppers.get(key) if fused.ENABLED else None
         if stepper is None:
             s = self.system
@@ -867,7 +1015,7 @@ class NavierStokes:
                                              conv_operator=lambda: self.conv_operator, shared=self._stepper_shared,
                                              convection=self.convection, time_scheme=scheme, variable=variable,
                                              m_p=self.system.mass, projection=self._projection,
-                                             implicit=self._implicit)
+                                             implicit=self._implicit, convection_treatment=treatment)
             if stepper is not None:
                 steppers[key] = stepper
         self.advance_declined = TimeStepper.last_declined if stepper is None else None
@@ -875,12 +1023,14 @@ class NavierStokes:
             sc = self._scalar
             skey = "variable" if variable else inner_pre
             skey = (skey, "implicit fdm") if self._implicit == "fdm" else skey
+            skey = (skey, "implicit convection") if treatment == "implicit" else skey
             if skey not in sc.steppers:
                 sc.steppers[skey] = ScalarStepper(self.gfu.engine, sc.ops, self.b.mat, self.f.vec, self.timestep,
                                                   inner_pre, sc.w_b, sc.t_ref, sc.flux, sc.precision, sc.maxsteps,
                                                   shared=sc.shared, convection=sc.convection, stencil=sc.stencil,
                                                   time_scheme=self.time_scheme, variable=variable,
-                                                  implicit=self._implicit, extents=sc.extents)
+                                                  implicit=self._implicit, extents=sc.extents,
+                                                  convection_treatment=treatment)
             return stepper.advance(self.gfu, self.gfup, nsteps, precision, maxsteps, diagnostics,
                                    scalar=sc.steppers[skey], temperature=self.temperature, history=self._history,
                                    timesteps=timesteps, controller=controller, clock=self._clock)
@@ -899,7 +1049,10 @@ class NavierStokes:
         import contextlib
         import io
         ops = self._time_stepping_operators()
-        if self._implicit == "fdm":       # (the direct solve takes precision and maxsteps, and ignores them)
+        if self._convection_treatment == "implicit":
+            self._implicit_momentum_solver(None)
+            solvers = (self._lin_conv["inv"], ops["invproj"])
+        elif self._implicit == "fdm":     # (the direct solve takes precision and maxsteps, and ignores them)
             solvers = (self._fdm_u, ops["invproj"])
         else:
             held, name = self._momentum_solver(pseudo)
@@ -954,5 +1107,6 @@ class NavierStokes:
                            np.array(energy) if diagnostics else None, declined=self.advance_declined,
                            scalar_iterations=its_s, convection=self.convection,
                            time_scheme="euler" if pseudo else self.time_scheme, projection=self._projection,
-                           implicit=self._implicit, **(variable_record(taus, rates, codes) if variable else {}),
+                           implicit=self._implicit, convection_treatment=self._convection_treatment,
+                           **(variable_record(taus, rates, codes) if variable else {}),
                            wall_flux=np.array(wall) if sc is not None and diagnostics and sc.flux is not None else None)
