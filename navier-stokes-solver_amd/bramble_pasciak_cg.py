@@ -132,6 +132,10 @@ def bramble_pasciak_cg(a_matrix, b_matrix, c_matrix, pre_a, pre_schur_complement
         fused_loop = Bpcg1DistLoop.try_create(a_matrix, b_matrix, c_matrix, pre_a, pre_schur_complement, k,
                                               dict(x=solution, r=r, d=d, a=ar, t1=t1, t2=t2))
     if fused_loop is not None:
+        if err0 == 0.0 and max_steps > 0:
+            # a zero right-hand side: the reference divides err / err0 at :118 (the device would record 0 / 0 = nan as
+            # hist[0], never stop, and return a solution of nans)
+            raise ZeroDivisionError("float division by zero")
         errors, converged = fused_loop.run(rho, err0, tolerance, max_steps)
         if print_rates:
             for i, e in enumerate(errors):

@@ -173,6 +173,10 @@ struct MK4Args {
   const int32_t* run;
   const double* packed;
   int32_t vec;                 // all vectors 16-byte aligned: two doubles per access
+  // where the partials of <z_new, v_new> go: the velocity workgroups' to slots [0, gu) when vel_partials, the pressure
+  // workgroups' from slot pfirst on.  With a stand-alone block Jacobi that M3 could have applied itself the apply
+  // writes the velocity slots -- the layout of the fused form, so that both forms sum the same array in the same order
+  int32_t pfirst, vel_partials;
 };
 
 constexpr int kMPerBlock = 2 * kBlock;     // one-shot element-wise launches: two elements per lane
@@ -281,7 +285,8 @@ __global__ __launch_bounds__(kBlock) void minres_m3_kernel(MK4Args a) {
       }
     }
   }
-  store_block_partial(acc, wg, a.partials, lds);
+  if (velocity && !a.vel_partials) return;     // (uniform over the workgroup)
+  store_block_partial(acc, velocity ? wg : a.pfirst + (wg - a.gu), a.partials, lds);
 }
 
 // the stop test of dot_partials_kernel: <z_new, v_new> of the velocity block after a preconditioner apply that is not fused
@@ -544,8 +549,16 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
              s.v[in][0], s.v[in][1], s.z[zn][0], s.z[zn][1], (s.pre_amg || s.pre_bjac) ? nullptr : s.pre_diag, s.minv,
              s.partials_c, m3_gu(s), m_gp(s), fold ? 1 : 0, s.A->nblk, s.B->nblk, s.partials_a, s.partials_b,
              fused ? s.pre_bjac->nblocks : 0, fused ? s.pre_bjac->run : nullptr, fused ? s.pre_bjac->inv_sym : nullptr,
-             vec ? 1 : 0};
-  const int g3 = a4.gu + a4.gp;
+             vec ? 1 : 0, 0, 1};
+  // a block Jacobi that M3 could apply itself, applied on its own: its partials of <z_new, v_new> (one per 256 blocks,
+  // the grouping and the in-lane order of the fused M3) go in front of the pressure partials, where the fused M3 puts
+  // them -- the two forms then sum the same array and agree bit for bit (up to kMaxStreamBlocks * 256 blocks, where
+  // the apply begins to stride)
+  const bool twin = !fused && m_fusable_bjac(s);
+  const int g3 = a4.gu + a4.gp;                  // workgroups of M3
+  a4.pfirst = twin ? bjac_dot_grid(*s.pre_bjac) : a4.gu;
+  a4.vel_partials = twin ? 0 : 1;
+  const int n3 = a4.pfirst + a4.gp;              // partials of M3's array
   int nb2 = 0;
   if (on(3)) {
   if (!fused) {
@@ -559,21 +572,22 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
     // block Jacobi: <z_new, v_new> out of the apply kernel
     const bool dot_in_apply = !s.pre_amg && !s.pre_fdm && !s.pre_bjac->gs_mat;
     if (!on(3)) {                   // phases 4 / 5 issued on their own: the partial count of phase 3
-      nb2 = dot_in_apply ? bjac_dot_grid(*s.pre_bjac) : m_dot_grid(s);
+      nb2 = twin ? 0 : dot_in_apply ? bjac_dot_grid(*s.pre_bjac) : m_dot_grid(s);
     } else
     // z_new[0] = preA v_new[0] outside the element-wise kernel; after the stop these launches only
     // touch ring slots nobody reads any more
     {
-    if (dot_in_apply) nb2 = bjac_apply_dot(*s.pre_bjac, 1.0, s.v[in][0], s.z[zn][0], s.partials_a, nullptr, st);
+    if (twin) bjac_apply_dot(*s.pre_bjac, 1.0, s.v[in][0], s.z[zn][0], s.partials_c, nullptr, st);
+    else if (dot_in_apply) nb2 = bjac_apply_dot(*s.pre_bjac, 1.0, s.v[in][0], s.z[zn][0], s.partials_a, nullptr, st);
     else pre_a_apply(pre_a_of(s), s.pre_fdm ? s.pre_fdm_scale : 1.0, s.v[in][0], s.z[zn][0], nullptr, nullptr, st);
-    if (nb2 == 0) {
+    if (nb2 == 0 && !twin) {
       nb2 = m_dot_grid(s);
       launch_dot_partials(MinresSkip{s.ctrl, k}, nb2, s.n_u, s.z[zn][0], s.v[in][0], s.partials_a, st);
     }
     }
   }
   if (on(4) && !fold) {
-    hipLaunchKernelGGL(minres_sum_kernel, dim3(1), dim3(kSumLanes), 0, st, s.ctrl, k, nb2, s.partials_a, g3,
+    hipLaunchKernelGGL(minres_sum_kernel, dim3(1), dim3(kSumLanes), 0, st, s.ctrl, k, nb2, s.partials_a, n3,
                        s.partials_c, set, int(s.local_sums ? M_G2_LOC : M_G2));
     NSS_CHECK_LAUNCH();
   }
@@ -582,7 +596,7 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
   // M4
   MK5Args a5{s.ctrl, s.scal, s.hist, s.n_u, s.n_p, k, s.z[zn][0], s.z[zn][1], s.v[in][0], s.v[in][1], s.w[in][0],
              s.w[in][1], s.u[0], s.u[1], s.z[zc][0], s.z[zc][1], s.w[io][0], s.w[io][1], s.w[ic][0], s.w[ic][1],
-             m_gu(s), fold ? 1 : 0, nb2, g3, s.partials_a, s.partials_c, vec ? 1 : 0};
+             m_gu(s), fold ? 1 : 0, nb2, n3, s.partials_a, s.partials_c, vec ? 1 : 0};
   if (stream_vector_loads(s.n_u)) hipLaunchKernelGGL(minres_m4_kernel<true>, dim3(m_gu(s) + m_gp(s)), dim3(kBlock), 0, st, a5);
   else hipLaunchKernelGGL(minres_m4_kernel<false>, dim3(m_gu(s) + m_gp(s)), dim3(kBlock), 0, st, a5);
   NSS_CHECK_LAUNCH();
