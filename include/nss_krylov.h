@@ -1155,8 +1155,8 @@ NSS_API int nss_lanczos_fold_mode(int32_t mode);
 NSS_API int nss_tridiag_extremes(const double* diag, const double* off, int32_t n, double* lo, double* hi);
 
 /* ---- fused preconditioned MINRES ----------------------------------------------------------
- * Replaces the loop body of minres.py:96-144 for K = [[A, B^T], [B, 0]], C = diag(preA, preS)
- * (the operands run.py:45-46 builds).  Vectors are given per block component ([0] velocity, n_u;
+ * Replaces the loop body of minres.py:96-144 for K = [[A, B^T], [B, 0]] -- or [[A, B^T], [B, C]], see the field C --
+ * and the preconditioner diag(preA, preS) (the operands run.py:45-46 builds).  Vectors are given per block component ([0] velocity, n_u;
  * [1] pressure, n_p).  The three-vector rotations of minres.py:131-133 are index arithmetic on
  * the rings: at iteration k (1-based)  v_old = v[(k-1)%3], v = v[k%3], v_new = v[(k+1)%3]
  * (same for w);  z = z[k%2], z_new = z[(k+1)%2].
@@ -1199,6 +1199,13 @@ typedef struct nss_minres_s {
    * reads any more. */
   nss_fdmi_t pre_fdm;
   double pre_fdm_scale;
+  /* the lower-right block of K = [[A, B^T], [B, C]] (n_p x n_p, stabilised systems) -- or NULL for the zero block.  It
+   * enters once per iteration (:97): kz1 = fl(B z0) + fl(C z1), each row sum in its kernel's own order, added once
+   * (Mult then MultAdd) before the store and the partial <kz1, z1>.  C_work: n_p doubles the loop owns (required with
+   * C).  One launch more per iteration; with C == NULL the launches and every bit are those of the state without these
+   * fields.  Nothing is sized from C's launch plan, which therefore is not part of plan_gen.  One GPU. */
+  nss_csr_t C;
+  double* C_work;
 } nss_minres_t;
 
 NSS_API int nss_minres_workspace(const nss_minres_t* s, int64_t* partials_a, int64_t* partials_b,
@@ -1232,7 +1239,7 @@ NSS_API int nss_minres_fuse_mode(int32_t mode);
 
 /* ---- fused Bramble-Pasciak CG, textbook form ------------------------------------------------
  * Replaces the loop body of bramble_pasciak_cg.py:110-143 (6 SpMV per iteration) for
- * C = None, pre_a Jacobi / block-Jacobi / AMG / AMG + Jacobi, pre_schur diagonal.  Block vectors per component
+ * C = None or a CSR matrix (the field C: one SpMV more), pre_a Jacobi / block-Jacobi / AMG / AMG + Jacobi, pre_schur diagonal.  Block vectors per component
  * ([0] velocity n_u, [1] pressure n_p): x = solution, r = residuum, d =
  * full_preconditioned_residuum, a = a_preconditioned_residuum, t1 / t2 = temp_1 / temp_2.
  * scal: double[16] = { rho, <d,t1>, rho_new, alpha, beta, err0, tolerance, -, local <d,t1>, local rho_new, .. };
@@ -1264,6 +1271,14 @@ typedef struct nss_bpcg1_s {
   /* the exact inverse of A by fast diagonalisation (nss_fdmi_create) as preA -- or NULL.  Exclusive with pre_diag,
    * pre_bjac and every term; one GPU (local_sums == 0). */
   nss_fdmi_t pre_fdm;
+  /* the lower-right block of a stabilised system [[A, B^T], [B, C]] (n_p x n_p; the method wants it symmetric negative
+   * semi-definite, which nobody checks) -- or NULL for the zero block.  It enters the loop once per iteration (:125):
+   * kp = fl(B du) + fl(C dp), each row sum in its kernel's own order, added once -- Mult then MultAdd.  C_work: n_p
+   * doubles the loop owns (C dp of the iteration; required with C).  One launch more per iteration; with C == NULL the
+   * launches and every bit are those of the state without these fields.  Nothing is sized from C's launch plan, which
+   * therefore is not part of plan_gen.  One GPU (local_sums == 0). */
+  nss_csr_t C;
+  double* C_work;
 } nss_bpcg1_t;
 
 NSS_API int nss_bpcg1_workspace(const nss_bpcg1_t* s, int64_t* partials_a, int64_t* partials_b,

@@ -2,13 +2,15 @@
 ``bramble_pasciak_cg.bramble_pasciak_cg`` (bramble_pasciak_cg.py:65-148) and its two
 operator wrappers ``ScaledPreconditioner`` (:9-36) and ``MatrixAB`` (:39-62).
 
-Solves ``[[A, B^T], [B, C]] [u; p] = [f; g]`` (C = None -> zero block) by CG on the
+Solves ``[[A, B^T], [B, C]] [u; p] = [f; g]`` (C = None -> zero block; else the method wants C
+symmetric negative semi-definite, which -- as in the reference -- nobody checks) by CG on the
 Bramble-Pasciak transformed, SPD-in-a-special-inner-product system with
 ``A~ = k * pre_a``, ``k = 1/lambda_min(pre_a A) + 1e-3`` (:70-71).
 
 Execution paths (both on the GPU): the fused device-resident loop behind the C ABI
-(``nss_bpcg1_*``) when every operand is native, otherwise the operator protocol below,
-statement for statement -- 6 SpMV, 1 pre_a, 1 pre_s, 2 inner products per iteration."""
+(``nss_bpcg1_*``) when every operand is native (C: None or an n_p x n_p ``SparseMatrix``),
+otherwise the operator protocol below, statement for statement -- 6 SpMV, 1 pre_a, 1 pre_s,
+2 inner products per iteration."""
 
 from math import sqrt
 

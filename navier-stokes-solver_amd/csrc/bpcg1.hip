@@ -7,6 +7,8 @@
 //   V1b  rows of B^T : ku = t1u + B^T dp;  t1u = -ku;  Jacobi: t2u = k dinv ku        (:125-126)
 //   [J]  block-Jacobi: t2u = -k J t1u                                                 (:126)
 //   V1c  rows of B   : kp = B du;  t1p = -kp;  t2p = kp                               (:125-126)
+//   [C]  rows of C   : cdp = C dp  (stabilised systems, nss_bpcg1_t.C: a launch of its own in front of V1c, whose
+//                      epilogue then forms kp = fl(B du) + fl(C dp) -- the protocol's Mult then MultAdd)   (:125)
 //   V3a  rows of A   : t1u += A t2u, partial <du, t1u>                                (:127,130)
 //   V3b  rows of B   : t1p += B t2u, partial <dp, t1p>                                (:127,130)
 //   R1   alpha = rho / sum                                                            (:129)
@@ -80,9 +82,11 @@ struct EpiV1c {
   const double* top_scal = nullptr;
   double* top_hist = nullptr;
   int it = 0;
+  const double* __restrict__ cdp = nullptr;   // C dp (nss_bpcg1_t.C_work) -- or nullptr: no C, and the sum keeps its sign of zero
   __device__ bool skip() const { return ctrl[PC_STOP] != 0; }
   __device__ bool prologue(double*) const { return top_ctrl ? v1_loop_top(top_ctrl, top_scal, top_hist, it) : true; }
   __device__ void row(int r, double kp) const {
+    if (cdp) kp += cdp[r];
     t1p[r] = -kp;
     t2p[r] = kp;
   }
@@ -343,6 +347,11 @@ static void bpcg1_check(const nss_bpcg1_t* s) {
               "bpcg1: NULL work buffer");
   for (int c = 0; c < 2; ++c)
     NSS_REQUIRE(s->x[c] && s->r[c] && s->d[c] && s->a[c] && s->t1[c] && s->t2[c], "bpcg1: NULL vector");
+  if (s->C) {             // (nothing is sized from C's launch plan: it stays out of the plan stamp)
+    NSS_REQUIRE(s->C->m == s->n_p && s->C->n == s->n_p, "bpcg1: C is not n_p x n_p");
+    NSS_REQUIRE(s->C_work != nullptr, "bpcg1: C without its work vector C_work (n_p)");
+    NSS_REQUIRE(!s->local_sums, "bpcg1: C (stabilised saddle point) runs on one GPU");
+  }
   const int64_t need[3] = {s->A->nblk, s->B->nblk, p_grid(*s)};     // = nss_bpcg1_workspace
   const int64_t cap[3] = {s->cap_a, s->cap_b, s->cap_c};
   check_plan("bpcg1", plan_stamp({s->A, s->B, s->BT}), s->plan_gen, need, cap, 3);
@@ -399,6 +408,9 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
       const nss_halo_t h0 = halo_of(dist->hu, s.d[0]), h1 = halo_of(dist->hp, s.d[1]);
       exchange(*dist->d, h0, st, &h1);
     }
+    // C dp for the epilogue of B's rows below; the launch writes only its work vector, so in the fast form it may sit in
+    // front of the launch that opens the iteration (after the stop of an earlier iteration it is skipped like the rest)
+    if (s.C) launch_csr(*s.C, s.d[1], EpiStore1{s.ctrl, s.C_work}, st);
     if (merge) {
       // rows of A (+ their row of B^T dp, V1b's combination) and rows of B in one launch, which (fast) opens the iteration
       int32_t* top = fast ? s.ctrl : nullptr;
@@ -410,7 +422,7 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
                          s.d[1], top, s.scal, s.hist, it, fused_j ? s.A->jb_first : nullptr,
                          fused_j ? s.A->jb_order : nullptr, fused_j ? J->run : nullptr, fused_j ? J->inv_sym : nullptr,
                          fused_j ? J->nblocks : 0, fused_j ? J->bs : 0};
-      const EpiV1c e1c{s.ctrl, s.t1[1], s.t2[1], top, s.scal, s.hist, it};
+      const EpiV1c e1c{s.ctrl, s.t1[1], s.t2[1], top, s.scal, s.hist, it, s.C ? s.C_work : nullptr};
       if (!launch_csr_dual(*s.A, s.d[0], e1, *s.B, s.d[0], e1c, st, lds)) {
         launch_csr(*s.A, s.d[0], e1, st, 0, -1, lds);    // (opens the iteration; the second launch repeats the
         launch_csr(*s.B, s.d[0], e1c, st);               //  test from the same scalars: same outcome)
@@ -418,7 +430,7 @@ static void bpcg1_iteration(const nss_bpcg1_t& s, int it, hipStream_t st, int fi
     } else {
     // V1a and V1c multiply the same operand (du) and do not depend on each other: one launch
     const EpiStore1 e1a{s.ctrl, s.t1[0]};
-    const EpiV1c e1c{s.ctrl, s.t1[1], s.t2[1]};
+    const EpiV1c e1c{s.ctrl, s.t1[1], s.t2[1], nullptr, nullptr, nullptr, 0, s.C ? s.C_work : nullptr};
     if (!launch_csr_dual(*s.A, s.d[0], e1a, *s.B, s.d[0], e1c, st)) {
       launch_csr(*s.A, s.d[0], e1a, st);
       launch_csr(*s.B, s.d[0], e1c, st);

@@ -4,6 +4,9 @@
 //
 //   M1  rows of B^T and rows of B in ONE launch (neither depends on the other):
 //         kz0 = B^T z1;   kz1 = B z0, partial <kz1, z1>                                 (:97-98)
+//       Stabilised systems (nss_minres_t.C, K = [[A, B^T], [B, C]]): one launch in front of M1 stores C z1 in the
+//       loop's work vector and the epilogue of B's rows forms kz1 = fl(B z0) + fl(C z1) before its store and its
+//       partial -- the protocol's Mult then MultAdd.
 //   M2  rows of A   : kz0 += A z0, partial <kz0, z0>                                    (:97-98)
 //       Launch-bound systems whose B^T has at most two entries per row (the staggered grids) run M1 + M2 as ONE
 //       launch: the rows of A add their row of B^T z1 from a fixed-width copy in the epilogue (same products, same
@@ -84,6 +87,7 @@ struct EpiMAccDot {  // y (+)= A (scale * x) ; partial <y, scale * z>
   const double* __restrict__ z;
   double* __restrict__ partials;
   const double* __restrict__ set;    // scalars of iteration k
+  const double* __restrict__ add = nullptr;   // rows of B: C z1 (nss_minres_t.C_work) -- or nullptr: nothing is added
   double acc = 0.0;
   double sz = 1.0;
   __device__ bool skip() const { return minres_skip(ctrl, k); }
@@ -96,6 +100,7 @@ struct EpiMAccDot {  // y (+)= A (scale * x) ; partial <y, scale * z>
   struct Pre { double y = 0.0, z = 0.0; };
   __device__ Pre fetch(int r) const { return Pre{accumulate ? y[r] : 0.0, z[r]}; }   // (before the prologue)
   __device__ void row(int r, double ax, const Pre& p) {
+    if (add) ax += add[r];
     const double t = accumulate ? p.y + ax : ax;
     y[r] = t;
     acc = fma(t, p.z * sz, acc);
@@ -480,6 +485,11 @@ static void minres_check(const nss_minres_t* s) {
     NSS_REQUIRE(s->u[c] && s->kz[c] && s->z[0][c] && s->z[1][c], "minres: NULL vector");
     for (int j = 0; j < 3; ++j) NSS_REQUIRE(s->v[j][c] && s->w[j][c], "minres: NULL ring vector");
   }
+  if (s->C) {             // (nothing is sized from C's launch plan: it stays out of the plan stamp)
+    NSS_REQUIRE(s->C->m == s->n_p && s->C->n == s->n_p, "minres: C is not n_p x n_p");
+    NSS_REQUIRE(s->C_work != nullptr, "minres: C without its work vector C_work (n_p)");
+    NSS_REQUIRE(!s->local_sums, "minres: C (stabilised saddle point) runs on one GPU");
+  }
   int64_t need[3];
   minres_need(*s, need);
   const int64_t cap[3] = {s->cap_a, s->cap_b, s->cap_c};
@@ -516,7 +526,9 @@ static void minres_iteration(const nss_minres_t& s, int k, hipStream_t st, int f
     exchange(*dist->d, h0, st, &h1);
   }
   // M1: kz0 = B^T z1 and kz1 = B z0 with <kz1, z1>;  M2: kz0 += A z0 with <kz0, z0>
-  EpiMAccDot e_b{s.ctrl, k, 0, s.kz[1], s.z[zc][1], s.partials_b, set};
+  // C z1 for the epilogue of B's rows (the launch writes only the work vector)
+  if (s.C) launch_csr(*s.C, s.z[zc][1], EpiMStore{s.ctrl, k, s.C_work, set}, st);
+  EpiMAccDot e_b{s.ctrl, k, 0, s.kz[1], s.z[zc][1], s.partials_b, set, s.C ? s.C_work : nullptr};
   if (m_merged_rows(s)) {                   // one launch: rows of A (+ their row of B^T z1) and rows of B
     EpiMRowsA e_a{s.ctrl, k, s.kz[0], s.z[zc][0], s.partials_a, set, s.BT->fw_col, s.BT->fw_val, s.z[zc][1]};
     if (!launch_csr_dual(*s.A, s.z[zc][0], e_a, *s.B, s.z[zc][0], e_b, st)) {

@@ -607,7 +607,8 @@ class MinresState(C.Structure):
                    ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("partials_c", C.c_void_p),
                    ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)]
                 + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)]
-                + [("pre_fdm", C.c_void_p), ("pre_fdm_scale", C.c_double)])
+                + [("pre_fdm", C.c_void_p), ("pre_fdm_scale", C.c_double)]
+                + [("C", C.c_void_p), ("C_work", C.c_void_p)])
 
 
 (M_DELTA, M_GAMMA, M_G2, M_ETA_OLD, M_C_OLD, M_C, M_S_OLD, M_S, M_RES_OLD, M_ERR0, M_TOL) = range(11)
@@ -617,9 +618,32 @@ def _block2(v, n_u, n_p):
     return (isinstance(v, BlockVector) and v.nblocks == 2 and _plain(v[0], n_u) and _plain(v[1], n_p))
 
 
+def native_c_block(c, a, b):
+    """Whether the fused MINRES and textbook BPCG loops take `c` as the lower-right block of [[a, b^T], [b, c]]: None
+    (the zero block), or a `SparseMatrix` of shape n_p x n_p on the engine of `a`.  Symmetry is not checked (the
+    reference does not check it either); the methods want `c` symmetric negative semi-definite."""
+    if c is None:
+        return True
+    n_p = getattr(b, "height", None)
+    return (isinstance(c, SparseMatrix) and (c.height, c.width) == (n_p, n_p)
+            and c.engine is getattr(a, "engine", None))
+
+
+def write_c_block(eng, st, c):
+    """Point the ``C`` / ``C_work`` fields of loop state `st` at `c` (`native_c_block`) and a work vector of its
+    height, which is returned for the loop to keep (None without `c`)."""
+    if c is None:
+        return None
+    work = eng.zeros(c.height)
+    st.C, st.C_work = c.handle.ptr, work.data_ptr()
+    return work
+
+
 class MinresLoop(FusedLoop):
-    """Device-resident iteration of minres.py:96-144 for K = [[A, B^T], [B, None]] and
-    C = [[preA, None], [None, preS]] (the operands run.py:45-46 builds)."""
+    """Device-resident iteration of minres.py:96-144 for K = [[A, B^T], [B, C]] and the preconditioner
+    [[preA, None], [None, preS]] (the operands run.py:45-46 builds, where K[1,1] is None).  K[1,1]: None, or the
+    lower-right block of a stabilised system as an n_p x n_p `SparseMatrix` (the method wants it symmetric negative
+    semi-definite; nobody checks): one launch more per iteration (csrc/minres.hip)."""
 
     @classmethod
     def try_create(cls, mat, pre, u, v_ring, w_ring, z_ring, kz):
@@ -632,7 +656,7 @@ class MinresLoop(FusedLoop):
         if (mat.nrows, mat.ncols) != (2, 2) or (pre.nrows, pre.ncols) != (2, 2):
             return "K or C is not 2 x 2"
         A, BT, B, C11 = mat[0, 0], mat[0, 1], mat[1, 0], mat[1, 1]
-        if C11 is not None or pre[0, 1] is not None or pre[1, 0] is not None:
+        if not native_c_block(C11, A, B) or pre[0, 1] is not None or pre[1, 0] is not None:
             return "K or C has another non-zero block"
         if not all(isinstance(m, SparseMatrix) for m in (A, BT, B)):
             return "A, B or B^T is not a SparseMatrix"
@@ -650,15 +674,17 @@ class MinresLoop(FusedLoop):
         vecs = [u, kz] + list(v_ring) + list(w_ring) + list(z_ring)
         if len(v_ring) != 3 or len(w_ring) != 3 or len(z_ring) != 2 or not all(_block2(x, n_u, n_p) for x in vecs):
             return "a work vector is not a plain BlockVector of its size"
-        return cls(eng, A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz)
+        return cls(eng, A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz, C11)
 
-    def __init__(self, eng, A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz):
-        """`pa`, `ps`: the `PreParts` of preA and preS (pre_for("minres"), native_diag)."""
+    def __init__(self, eng, A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz, c_block=None):
+        """`pa`, `ps`: the `PreParts` of preA and preS (pre_for("minres"), native_diag).  `c_block`: the lower-right
+        block of K (`native_c_block`) or None."""
         torch = eng.torch
         self.eng, self.lib = eng, eng.lib
-        self.keep = [A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz]
+        self.keep = [A, B, BT, pa, ps, u, v_ring, w_ring, z_ring, kz, c_block]
         st = MinresState()
         st.A, st.B, st.BT = A.handle.ptr, B.handle.ptr, BT.handle.ptr
+        self.c_work = write_c_block(eng, st, c_block)
         self.dinv = write_pre(st, pa, scale_diag=True)
         st.pre_fdm_scale = float(pa.scale)
         self.minv = scaled_diag(ps)
@@ -717,11 +743,14 @@ class Bpcg1State(C.Structure):
                    ("partials_a", C.c_void_p), ("partials_b", C.c_void_p), ("partials_c", C.c_void_p),
                    ("k", C.c_double), ("n_u", C.c_int32), ("n_p", C.c_int32), ("local_sums", C.c_int32)]
                 + [("plan_gen", C.c_int64), ("cap_a", C.c_int64), ("cap_b", C.c_int64), ("cap_c", C.c_int64)]
-                + [("pre_fdm", C.c_void_p)])
+                + [("pre_fdm", C.c_void_p)]
+                + [("C", C.c_void_p), ("C_work", C.c_void_p)])
 
 
 class Bpcg1Loop(FusedLoop):
-    """Device-resident iteration of bramble_pasciak_cg.py:110-143."""
+    """Device-resident iteration of bramble_pasciak_cg.py:110-143.  `c_matrix`: None, or the lower-right block of a
+    stabilised system as an n_p x n_p `SparseMatrix` (the method wants it symmetric negative semi-definite; as in the
+    reference, nobody checks): one launch more per iteration (csrc/bpcg1.hip)."""
 
     @classmethod
     def try_create(cls, a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs):
@@ -729,7 +758,7 @@ class Bpcg1Loop(FusedLoop):
 
     @classmethod
     def _try_create(cls, a_matrix, b_matrix, c_matrix, pre_a, pre_s, k, vecs):
-        if c_matrix is not None:
+        if not native_c_block(c_matrix, a_matrix, b_matrix):
             return "C is given"
         if not (isinstance(a_matrix, SparseMatrix) and isinstance(b_matrix, SparseMatrix)):
             return "A or B is not a SparseMatrix"
@@ -746,18 +775,20 @@ class Bpcg1Loop(FusedLoop):
             return "preA is not native"
         if any(not _block2(vecs.get(name), n_u, n_p) for name in ("x", "r", "d", "a", "t1", "t2")):
             return "a work vector is not a plain BlockVector of its size"
-        return cls(eng, a_matrix, b_matrix, pa, ps, k, vecs)
+        return cls(eng, a_matrix, b_matrix, pa, ps, k, vecs, None, c_matrix)
 
-    def __init__(self, eng, A, B, pa, ps, k, vecs, BT=None):
+    def __init__(self, eng, A, B, pa, ps, k, vecs, BT=None, c_block=None):
         """`pa`, `ps`: the `PreParts` of preA and preS (pre_for("bpcg1"), native_diag).  `BT`: the rows of B^T this
-        process owns, when they are not the transpose of its B (row-partitioned runs: distributed.Bpcg1DistLoop)."""
+        process owns, when they are not the transpose of its B (row-partitioned runs: distributed.Bpcg1DistLoop).
+        `c_block`: the lower-right block C (`native_c_block`) or None."""
         torch = eng.torch
         self.eng, self.lib = eng, eng.lib
         if BT is None:
             BT = B.CreateTranspose()
-        self.keep = [A, B, BT, pa, ps, vecs]
+        self.keep = [A, B, BT, pa, ps, vecs, c_block]
         st = Bpcg1State()
         st.A, st.B, st.BT = A.handle.ptr, B.handle.ptr, BT.handle.ptr
+        self.c_work = write_c_block(eng, st, c_block)
         write_pre(st, pa)
         # block Jacobi alone: A's row blocks are planned around its blocks (small systems) and the launch of A's rows
         # applies it in its epilogue (csrc/bpcg1.hip: EpiV1Rows)

@@ -4,8 +4,9 @@ reference's ``minres.MinRes`` (minres.py:12-149; same signature, same return val
 
 Two execution paths, both on the GPU:
 
-* fused -- when ``mat`` is ``BlockMatrix([[A, B.T], [B, None]])`` of native
-  ``SparseMatrix`` blocks and ``pre`` is ``BlockMatrix([[preA, None], [None, preS]])`` of
+* fused -- when ``mat`` is ``BlockMatrix([[A, B.T], [B, C]])`` of native
+  ``SparseMatrix`` blocks (``C`` is ``None``, or n_p x n_p for a stabilised system: the method
+  wants it symmetric negative semi-definite, which nobody checks) and ``pre`` is ``BlockMatrix([[preA, None], [None, preS]])`` of
   native Jacobi / block-Jacobi preconditioners (the operands ``run.py:45-46`` builds), the
   whole iteration runs behind the C ABI (``nss_minres_*``): 3 SpMVs with fused vector
   updates and dot partials, scalars kept on the device, no host sync per iteration.

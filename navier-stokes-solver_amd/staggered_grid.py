@@ -175,6 +175,18 @@ class StokesSystem:
     def saddle_matrix(self):
         return sp.bmat([[self.A, self.B.T], [self.B, None]], format="csr")
 
+    def pressure_stabilisation(self, eps):
+        """The lower-right block C of a stabilised system [[A, B^T], [B, C]]: ``-eps h^(2 - dim) B B^T`` as a sorted
+        CSR matrix, i.e. -eps h^2 times the cell-centred Laplacian (interior faces only) in the integrated scaling of
+        A and B.  Symmetric negative semi-definite, and it annihilates the constants as B^T does.  Plain systems
+        only."""
+        if self.block_size != 1:
+            raise ValueError("pressure_stabilisation: plain systems only (block_size == 1)")
+        C = (self.B @ self.B.T).tocsr() * (-float(eps) * self.h ** (2 - self.dim))
+        C.sum_duplicates()
+        C.sort_indices()
+        return C
+
     def facet_blocks(self):
         """One block per grid cell: its 'plus' faces (u_{i+1/2}, v_{j+1/2}[, w_{k+1/2}]) --
         the facet-like block-Jacobi variant (bs = dim) of SURVEY.md section 8a row A7.
