@@ -296,6 +296,99 @@ def check_convection_treatment(treatment, who):
     return treatment
 
 
+def check_implicit_solve(who, inner_pre, implicit, variable, time_scheme, convection, convection_treatment,
+                         projection="cg"):
+    """The rules for the arguments of a stepper's implicit solve (``ValueError``), in the order of their messages:
+    implicit convection goes with "euler", "upwind" and "jacobi" (any `inner_pre` once `implicit` is "fdm"); `implicit`
+    is "cg" or "fdm"; variable steps take "jacobi" unless the solve is direct.  `who`: "ScalarStepper", whose messages
+    carry its name, or "TimeStepper", which has the names of `inner_pre` and `projection` checked between the rules."""
+    scalar = who == "ScalarStepper"
+    prefix = "ScalarStepper: " if scalar else ""
+    if convection_treatment == "implicit" and (time_scheme != "euler" or convection != "upwind" or
+                                               (inner_pre != "jacobi" and implicit != "fdm")):
+        raise ValueError(prefix + "implicit convection goes with time_scheme=\"euler\", convection=\"upwind\" and "
+                         "inner_pre=\"jacobi\"")
+    if not scalar and inner_pre not in ("jacobi", "amg"):
+        raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
+    if projection not in ("cg", "fdm"):
+        raise ValueError("projection is \"cg\" or \"fdm\"")
+    if implicit not in ("cg", "fdm"):
+        raise ValueError(prefix + "implicit is \"cg\" or \"fdm\"")
+    if variable and inner_pre != "jacobi" and implicit != "fdm":
+        raise ValueError(prefix + "a variable-step stepper takes inner_pre=\"jacobi\""
+                         + ("" if scalar else ": a hierarchy belongs to one step size"))
+
+
+class ImplicitSolve:
+    """The implicit solve of one transported quantity, out = (M + sigma L)^-1 rhs with sigma = theta tau (theta = 1, or
+    1/2 for "cnab2"): the velocity's (M_u, A, rows [A | D]) or the scalar's (M_p, K, rows [K | B]), of one `kind`:
+
+      "cg"        `CgLoop` on the assembled M + theta timestep L (`assembled`) with `pre`, Jacobi or AMG (`inner_pre`)
+      "shifted"   `CgLoop` on L itself with the shift (M, diag L): the sigma of each step, Jacobi written by `set_shift`
+      "fdm"       the direct solve of the `ComponentFastDiagonalization` `fdm`: the sigma of each step, no iteration
+      "bicgstab"  `fused.BicgstabLoop` on M + sigma (L + N(a)) read from `rows`: the advecting field `a` is allocated
+                  here and written by the owner once per step; the preconditioner is the point-Jacobi diagonal `dinv`
+                  of the whole operator or, given `fdm`, the direct viscous inverse
+
+    Of `assembled`, `pre`, `cg`, `fdm`, `bicg`, `dinv`, `a`, those the kind does not use are not built and stay None.
+    `lap`: L, the `SparseMatrix` the caller holds (the shifted loop runs on that very object) or a scipy matrix, which
+    the shifted kind alone uploads (`keys["lap"]` of `shared`, beside `keys["assembled"]` and `keys["diag"]`, built when
+    missing); `mass`: host array; `label`: the owner's name for the solve in the message of a breakdown."""
+
+    assembled = pre = cg = fdm = bicg = dinv = a = None
+
+    @staticmethod
+    def kind_of(variable, implicit, convection_treatment):
+        """The kind for a stepper's three switches; with implicit convection `implicit` names the preconditioner."""
+        return "bicgstab" if convection_treatment == "implicit" else "fdm" if implicit == "fdm" else \
+            "shifted" if variable else "cg"
+
+    def __init__(self, eng, kind, label, inner_pre, timestep, theta, mass, lap, shared, keys, fdm=None, rows=None,
+                 avg=None, diff=None):
+        import scipy.sparse as sp
+        self.kind, self.label, self.theta, self.fdm = kind, label, float(theta), fdm
+        resident = isinstance(lap, SparseMatrix)
+        if kind == "cg":                            # M + timestep L, or the half-step operator M + timestep/2 L
+            if keys["assembled"] not in shared:
+                host = sp.diags(mass) + self.theta * float(timestep) * (lap.to_scipy() if resident else lap)
+                shared[keys["assembled"]] = SparseMatrix.from_scipy(host.tocsr(), engine=eng)
+            self.assembled = shared[keys["assembled"]]
+            self.pre = SmoothedAggregationAMG(self.assembled) if inner_pre == "amg" else JacobiPreconditioner(self.assembled)
+            self.cg = CgLoop(eng, self.assembled, pre_for("cg", self.pre))
+        elif kind == "shifted":
+            if keys["diag"] not in shared:
+                shared[keys["diag"]] = eng.from_host((lap.to_scipy() if resident else sp.csr_matrix(lap)).diagonal())
+            if not resident:
+                if keys["lap"] not in shared:
+                    shared[keys["lap"]] = SparseMatrix.from_scipy(sp.csr_matrix(lap), engine=eng)
+                lap = shared[keys["lap"]]
+            self.cg = CgLoop(eng, lap, NO_PRE, shift=(mass, shared[keys["diag"]]))
+        elif kind == "bicgstab":
+            self.a = eng.zeros(max(1, avg.height))
+            form = fused.ConvectiveForm(rows, avg, diff, self.a, fused.ConvectiveForm.mass_operand(eng, mass))
+            self.dinv = None if fdm is not None else eng.zeros(rows.height)
+            self.bicg = fused.BicgstabLoop(eng, rows, self.dinv, form, fdm)
+
+    def solve(self, rhs, out, tau, precision, maxsteps, step):
+        """out = (M + theta `tau` L)^-1 rhs from zero (device buffers; "bicgstab": with the N(a) of the current `a`).
+        Returns the iterations (0: the direct solve); a BiCGStab breakdown raises ``FloatingPointError`` naming `step`."""
+        sigma = self.theta * tau                    # ("bicgstab" is an "euler" stepper's: theta = 1, its sigma is tau)
+        if self.kind == "fdm":
+            return self.fdm.solve_resident(rhs, out, sigma)
+        if self.kind == "bicgstab":
+            self.bicg.set_sigma(sigma)
+            if self.dinv is not None:
+                self.bicg.write_jacobi(self.dinv)
+            its = self.bicg.solve_resident(rhs, out, precision, maxsteps)
+            if self.bicg.code:
+                raise FloatingPointError("Advance: %s of step %d broke down, code %d (%s)"
+                                         % (self.label, step, self.bicg.code, self.bicg.CODES[self.bicg.code]))
+            return its
+        if self.kind == "shifted":
+            self.cg.set_shift(sigma)
+        return self.cg.solve_resident(rhs, out, precision, maxsteps)
+
+
 class LinearisedConvection(BaseMatrix):
     """The operator of the linearly implicit (Picard-linearised) convection step as a protocol operator,
 
@@ -511,8 +604,10 @@ class TimeStepper(FusedLoop):
     no host poll between its first launch and its read-back."""
 
     PRECISION, MAXSTEPS = (1e-4, 1e-8), (500, 5000)        # those of the template's CGSolvers invmstar / invproj
-    momentum_flux = adv = avg = diff = stencil = None      # with `flux_declined`: no flux object, no flux operands
+    momentum_flux = AD = adv = avg = diff = stencil = None # with `flux_declined`: no flux object, no flux operands
     nflux = 0
+    cg_m, pre_m, mstar, fdm_u, bicg_m, dinv_m = (          # the parts of `solve_m`, where tests and tools read them
+        property(lambda self, p=p: getattr(self.solve_m, p)) for p in ("cg", "pre", "assembled", "fdm", "bicg", "dinv"))
 
     @classmethod
     def try_create(cls, system, A, B, f, timestep, m_u, inner_pre="jacobi", conv_operator=None, shared=None,
@@ -527,21 +622,16 @@ class TimeStepper(FusedLoop):
         under "mstar", "Lp", "C" -- keep them once.  `convection`: the scheme of F1 (`MomentumFlux`), "upwind" (donor
         cell, first order) or the second-order limited "minmod" / "vanleer".  `time_scheme`: "euler" or "cnab2"; a "cnab2"
         stepper keeps its matrices under keys of their own ("mhalf", "ADBt") and declines when the flux kernel declines the
-        convection operators.  `variable`: a variable-step stepper -- no mstar / mhalf: the velocity solve runs the shifted
-        `CgLoop` over `A` with sigma = tau_n ("euler") or tau_n / 2 ("cnab2"), Jacobi only; `m_p`: host array, the lumped
-        pressure mass of the rate kernel (None: ones).  `projection`: "cg", or "fdm" -- `project` then launches the direct
-        solve ``nss_fdm_solve_f64`` of a `hipla.fdm.FastDiagonalization` of Lp over the extents (system.n,) * system.dim,
-        kept under "fdm" in `shared` (built when missing; the stepper declines with the reason when Lp is no Kronecker
-        sum), and neither `cg_p` nor `pre_p` -- for "amg": the hierarchy of Lp -- is built.  `implicit`: "cg", or "fdm" -- the
-        velocity solve then launches ``nss_fdmc_solve_f64`` of a `hipla.fdm.ComponentFastDiagonalization` of A over
-        `system.component_ids`, kept under "fdm_u" in `shared` (built when missing; the stepper declines with the reason
-        when A does not factor), with sigma = the step size ("euler") or half of it ("cnab2"): no mstar / mhalf, no `cg_m`,
-        no `pre_m` and no hierarchy of the velocity operator are built, and a variable-step stepper takes any `inner_pre`,
-        which then concerns a "cg" projection alone.  `convection_treatment`: "explicit", or "implicit" -- the velocity
-        solve is then the BiCGStab loop (`fused.BicgstabLoop`) on M_u + sigma (A + N(a)) read from [A | D] itself, a =
-        I_adv u^n frozen once per step, preconditioned by the point-Jacobi diagonal of the whole operator (`implicit` =
-        "cg") or by the direct viscous inverse (`implicit` = "fdm"); "euler" and "upwind" only, any step size, no mstar.
-        Returns None, the reason in `last_declined`."""
+        convection operators.  `m_p`: host array, the lumped pressure mass of the rate kernel (None: ones).  `projection`:
+        "cg", or "fdm" -- `project` then launches the direct solve ``nss_fdm_solve_f64`` of a
+        `hipla.fdm.FastDiagonalization` of Lp over the extents (system.n,) * system.dim, kept under "fdm" in `shared` (built
+        when missing; the stepper declines with the reason when Lp is no Kronecker sum), and neither `cg_p` nor `pre_p`
+        -- for "amg": the hierarchy of Lp -- is built.  `variable`, `implicit` ("cg" | "fdm") and `convection_treatment`
+        ("explicit" | "implicit") choose the kind of the velocity solve `solve_m` (`ImplicitSolve`; the combinations:
+        `check_implicit_solve`), with theta = 1 ("euler") or 1/2 ("cnab2").  The direct solve is that of a
+        `hipla.fdm.ComponentFastDiagonalization` of A over `system.component_ids`, kept under "fdm_u" in `shared` (built
+        when missing; the stepper declines with the reason when A does not factor); `inner_pre` then concerns a "cg"
+        projection alone.  With implicit convection a = I_adv u^n is frozen once per step.  None: see `last_declined`."""
         return cls._decided(cls._try_create(system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection,
                                             time_scheme, variable, m_p, projection, implicit, convection_treatment))
 
@@ -560,18 +650,8 @@ class TimeStepper(FusedLoop):
     def _try_create(cls, system, A, B, f, timestep, m_u, inner_pre, conv_operator, shared, convection, time_scheme,
                     variable=False, m_p=None, projection="cg", implicit="cg", convection_treatment="explicit"):
         check_convection_treatment(convection_treatment, "TimeStepper")
-        if convection_treatment == "implicit" and (time_scheme != "euler" or convection != "upwind" or
-                                                   (inner_pre != "jacobi" and implicit != "fdm")):
-            raise ValueError("implicit convection goes with time_scheme=\"euler\", convection=\"upwind\" and "
-                             "inner_pre=\"jacobi\"")
-        if inner_pre not in ("jacobi", "amg"):
-            raise ValueError("inner_pre is \"jacobi\" or \"amg\"")
-        if projection not in ("cg", "fdm"):
-            raise ValueError("projection is \"cg\" or \"fdm\"")
-        if implicit not in ("cg", "fdm"):
-            raise ValueError("implicit is \"cg\" or \"fdm\"")
-        if variable and inner_pre != "jacobi" and implicit != "fdm":
-            raise ValueError("a variable-step stepper takes inner_pre=\"jacobi\": a hierarchy belongs to one step size")
+        check_implicit_solve("TimeStepper", inner_pre, implicit, variable, time_scheme, convection, convection_treatment,
+                             projection)
         check_convection(convection, "TimeStepper")
         check_time_scheme(time_scheme, "TimeStepper")
         if not fused.ENABLED:
@@ -626,12 +706,11 @@ class TimeStepper(FusedLoop):
         self.time_scheme, self.variable = time_scheme, bool(variable)
         self.projection, self.implicit = projection, implicit
         self.convection_treatment = convection_treatment
-        implicit_conv = convection_treatment == "implicit"     # the velocity solve is the BiCGStab loop: no mstar, no cg_m
         self.fdm = shared["fdm"] if projection == "fdm" else None
         if self.fdm is not None and self.fdm.handle is None:
             raise ValueError("TimeStepper: the FastDiagonalization holds no device handle")
-        self.fdm_u = shared["fdm_u"] if implicit == "fdm" else None
-        if self.fdm_u is not None and self.fdm_u.handle is None:
+        fdm_u = shared["fdm_u"] if implicit == "fdm" else None
+        if fdm_u is not None and fdm_u.handle is None:
             raise ValueError("TimeStepper: the ComponentFastDiagonalization holds no device handle")
         cnab2 = time_scheme == "cnab2"
         rows_key, mstar_key = ("ADBt", "mhalf") if cnab2 else ("AD", "mstar")
@@ -662,12 +741,12 @@ class TimeStepper(FusedLoop):
         self.temp, self.raw, self.temp2 = eng.zeros(self.n_u), eng.zeros(self.n_u), eng.zeros(self.n_u)
         self.rhs_p, self.phi = eng.zeros(self.n_p), eng.zeros(self.n_p)
         # ---- the inner solves ----
-        direct_m = self.fdm_u is not None           # the velocity solve is the direct one: no mstar, no cg_m, no pre_m
-        if not variable and not direct_m and not implicit_conv and mstar_key not in shared:   # M_u + timestep (/2) A
-            theta = 0.5 * self.timestep if cnab2 else self.timestep
-            shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(m_u) + theta * A.to_scipy()).tocsr(), engine=eng)
+        kind = ImplicitSolve.kind_of(variable, implicit, convection_treatment)
+        self.solve_m = ImplicitSolve(eng, kind, "the velocity solve", inner_pre, self.timestep, 0.5 if cnab2 else 1.0, m_u,
+                                     A, shared, dict(assembled=mstar_key, diag="diagA"), fdm_u, self.AD, self.avg, self.diff)
+        if kind == "bicgstab":                      # (a breakdown of a scalar's solve puts the step's u and phi back)
+            self.u_back, self.phi_back = eng.zeros(self.n_u), eng.zeros(self.n_p)
         self._projection_matrices(eng, B, m_u, shared)
-        self.mstar = None if variable or direct_m or implicit_conv else shared[mstar_key]
         self.Lp, self.C = shared["Lp"], shared["C"]
         if "singular" not in shared:
             ok, why = two_entry_rows(self.C.to_scipy())
@@ -675,36 +754,14 @@ class TimeStepper(FusedLoop):
                 raise ValueError("TimeStepper: M_u^-1 B^T: " + why)
             shared["singular"] = constants_in_kernel(self.Lp.to_scipy())
         self.singular = shared["singular"]
-        direct = self.fdm is not None               # the projection is the direct solve: no cg_p, no pre_p
-        if direct_m or implicit_conv:               # (`inner_pre` concerns a "cg" projection alone)
-            self.pre_m = self.cg_m = None
-            self.pre_p = None if direct else JacobiPreconditioner(self.Lp) if inner_pre != "amg" else \
+        # The projection: direct (no cg_p, no pre_p), else CG with Jacobi or the hierarchy of Lp (never beside "shifted").
+        self.pre_p = self.cg_p = None
+        if self.fdm is None:
+            self.pre_p = JacobiPreconditioner(self.Lp) if inner_pre != "amg" or kind == "shifted" else \
                 SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
-            if variable:
-                self.rate = CflRate(eng, B, m_p)
-        elif variable:                              # the shifted loop over A: M_u + sigma A for the sigma of each step
-            if "diagA" not in shared:
-                shared["diagA"] = eng.from_host(A.to_scipy().diagonal())
-            self.pre_m, self.pre_p = None, None if direct else JacobiPreconditioner(self.Lp)
-            self.cg_m = CgLoop(eng, A, NO_PRE, shift=(m_u, shared["diagA"]))
+            self.cg_p = CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
+        if variable:
             self.rate = CflRate(eng, B, m_p)
-        else:
-            if inner_pre == "amg":
-                self.pre_m = SmoothedAggregationAMG(self.mstar)
-                self.pre_p = None if direct else \
-                    SmoothedAggregationAMG(self.Lp, nullspace="constants" if self.singular else None)
-            else:
-                self.pre_m = JacobiPreconditioner(self.mstar)
-                self.pre_p = None if direct else JacobiPreconditioner(self.Lp)
-            self.cg_m = CgLoop(eng, self.mstar, pre_for("cg", self.pre_m))
-        self.cg_p = None if direct else CgLoop(eng, self.Lp, pre_for("cg", self.pre_p))
-        self.bicg_m = None
-        if implicit_conv:                           # form (ii) over the stepper's own [A | D], a = I_adv u^n in `self.a`
-            self.a = eng.zeros(max(1, self.nflux))
-            form = fused.ConvectiveForm(self.AD, self.avg, self.diff, self.a, fused.ConvectiveForm.mass_operand(eng, m_u))
-            self.dinv_m = None if direct_m else eng.zeros(self.n_u)
-            self.bicg_m = fused.BicgstabLoop(eng, self.AD, self.dinv_m, form, self.fdm_u)
-            self.u_back, self.phi_back = eng.zeros(self.n_u), eng.zeros(self.n_p)
         # ---- the record ----
         uniform = bool(m_u.size) and bool((m_u == m_u[0]).all())
         self.mass = None if uniform else eng.from_host(m_u)
@@ -795,7 +852,8 @@ class TimeStepper(FusedLoop):
             raise ValueError("advance: variable steps want the clock and do no pseudo time stepping")
         if self.variable and scalar is not None and not scalar.variable:
             raise ValueError("advance: the scalar stepper is not a variable-step one")
-        if self.bicg_m is not None and (pseudo or (scalar is not None and scalar.bicg is None)):
+        implicit_conv = self.solve_m.kind == "bicgstab"
+        if implicit_conv and (pseudo or (scalar is not None and scalar.solve_T.kind != "bicgstab")):
             raise ValueError("advance: implicit convection does no pseudo time stepping and takes an implicit scalar stepper")
         if timesteps is not None:
             timesteps = [check_step_size(t, "advance") for t in timesteps]
@@ -840,12 +898,10 @@ class TimeStepper(FusedLoop):
                     tau = chosen[0]
                     codes.append(chosen[1])
                 taus.append(tau)
-                if self.cg_m is not None:
-                    self.cg_m.set_shift(0.5 * tau if cnab2 else tau)
+            size = self.timestep if tau is None else tau
             if pseudo:
                 eng.csr_spmv(self.A.handle, -1.0, self.u, 0.0, self.temp)         # :411  temp = -A u
             elif cnab2:
-                size = self.timestep if tau is None else tau
                 self.weights = TimeHistory.ab2_weights(valid["momentum"], size, tau_prev)
                 force = None if scalar is None else \
                     scalar.flux_ab2(self.u, TimeHistory.ab2_weights(valid["scalar"], size, tau_prev))
@@ -853,26 +909,17 @@ class TimeStepper(FusedLoop):
                 self.right_hand_side(force)
             else:
                 self.right_hand_side(None if scalar is None else scalar.flux(self.u))     # (S1,) F1, F2  :429-431
-            if self.bicg_m is not None:
+            if implicit_conv:
                 if scalar is not None:              # (a breakdown of the scalar's solve puts this state back)
                     eng.copy(self.u, self.u_back)
                     eng.copy(self.phi, self.phi_back)
-                if self.nflux:
-                    eng.csr_spmv(self.adv.handle, 1.0, self.u, 0.0, self.a)       # a = I_adv u^n, frozen for the step
-                self.bicg_m.set_sigma(self.timestep if tau is None else tau)
-                if self.dinv_m is not None:
-                    self.bicg_m.write_jacobi(self.dinv_m)
-                count_m = self.bicg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0])
-                if self.bicg_m.code:                # (u is still u^n: the last finished step)
-                    failure = FloatingPointError("Advance: the velocity solve of step %d broke down, code %d (%s)"
-                                                 % (step, self.bicg_m.code, self.bicg_m.CODES[self.bicg_m.code]))
-                    break
-                its_m.append(count_m)
-            elif self.fdm_u is not None:            # (the pseudo time stepping is an "euler" stepper's: sigma = timestep)
-                size = self.timestep if tau is None else tau
-                its_m.append(self.fdm_u.solve_resident(self.temp, self.raw, 0.5 * size if cnab2 else size))
-            else:
-                its_m.append(self.cg_m.solve_resident(self.temp, self.raw, self.precision[0], self.maxsteps[0]))   # :433
+                if self.nflux:                      # a = I_adv u^n, frozen for the step
+                    eng.csr_spmv(self.adv.handle, 1.0, self.u, 0.0, self.solve_m.a)
+            try:                                    # :433  (the pseudo time stepping is an "euler" stepper's: theta = 1)
+                its_m.append(self.solve_m.solve(self.temp, self.raw, size, self.precision[0], self.maxsteps[0], step))
+            except FloatingPointError as err:       # (u is still u^n: the last finished step)
+                failure = err
+                break
             count = self.project(self.raw, out=self.temp2, update=self.u, energy=diagnostics and not pseudo,
                                  tau=tau)                                                                       # :434,438
             if pseudo:
@@ -893,7 +940,7 @@ class TimeStepper(FusedLoop):
                     its_p.pop()
                     break
             if not pseudo:
-                tau_prev = self.timestep if tau is None else tau
+                tau_prev = size
         nsteps = len(its_m)                                               # (a duration may end the call early)
         if clock is not None and nsteps:
             clock.tau_prev = tau_prev
@@ -942,6 +989,8 @@ class ScalarStepper:
     histories G_prev and b_prev), and the solve is with M_p + timestep/2 K (key "mhalf")."""
 
     PRECISION, MAXSTEPS = 1e-4, 500          # those of invmstar: the same kind of operator
+    cg, pre, mstar, fdm, bicg = (            # the parts of `solve_T`, where tests read them
+        property(lambda self, p=p: getattr(self.solve_T, p)) for p in ("cg", "pre", "assembled", "fdm", "bicg"))
 
     def __init__(self, eng, ops, B, f, timestep, inner_pre="jacobi", w_b=None, t_ref=0.0, flux=None, precision=None,
                  maxsteps=None, shared=None, convection="upwind", stencil=None, time_scheme="euler", variable=False,
@@ -950,28 +999,17 @@ class ScalarStepper:
         the flux launch reads every step; `w_b`: host array of buoyancy weights (None: passive scalar); `flux`:
         (c0, w) of `ops["wall_flux"](wall)` or None; `shared`: dict for the device matrices that do not depend on
         `inner_pre`.  `convection`, `stencil`: the scheme of S1 and, for a limited one, `scalar_stencil()` (`ScalarFlux`).
-        `variable`: a variable-step stepper -- no mstar / mhalf: the shifted `CgLoop` over K ("K" of `shared`, uploaded
-        when missing) with the sigma of each step, Jacobi only.  `implicit`: "cg", or "fdm" -- the solve launches
-        ``nss_fdmc_solve_f64`` of the `hipla.fdm.ComponentFastDiagonalization` of K over the cells, kept under "fdm_T" in
-        `shared` (built when missing, over the grid `extents`; ``ValueError`` with the reason when K does not factor),
-        with the sigma of each step: no mstar / mhalf, no `cg`, no `pre`, any `inner_pre`.  `convection_treatment`:
-        "explicit", or "implicit" -- the solve is the BiCGStab loop on M_p + sigma (K + B G(u^n; .)) read from [K | B]
-        itself, u^n copied by `flux`, preconditioned by the point-Jacobi diagonal of the whole operator or (`implicit` =
-        "fdm") by (M_p + sigma K)^-1; "euler" and "upwind" only.  A breakdown makes `step` raise ``FloatingPointError``
-        before T is touched."""
+        `variable`, `implicit` and `convection_treatment` choose the kind of the solve `solve_T` (`ImplicitSolve`) as for
+        the velocity.  The direct solve is that of the `hipla.fdm.ComponentFastDiagonalization` of K over the cells, kept
+        under "fdm_T" in `shared` (built when missing, over the grid `extents`; ``ValueError`` with the reason when K does
+        not factor); the BiCGStab loop is on M_p + sigma (K + B G(u^n; .)), u^n copied by `flux`, and a breakdown makes
+        `step` raise ``FloatingPointError`` before T is touched."""
         import scipy.sparse as sp
         shared = {} if shared is None else shared
         self.variable = bool(variable)
-        implicit_conv = check_convection_treatment(convection_treatment, "ScalarStepper") == "implicit"
-        if implicit_conv and (time_scheme != "euler" or convection != "upwind" or
-                              (inner_pre != "jacobi" and implicit != "fdm")):
-            raise ValueError("ScalarStepper: implicit convection goes with time_scheme=\"euler\", convection=\"upwind\" "
-                             "and inner_pre=\"jacobi\"")
-        if implicit not in ("cg", "fdm"):
-            raise ValueError("ScalarStepper: implicit is \"cg\" or \"fdm\"")
+        check_convection_treatment(convection_treatment, "ScalarStepper")
+        check_implicit_solve("ScalarStepper", inner_pre, implicit, variable, time_scheme, convection, convection_treatment)
         self.implicit = implicit
-        if variable and inner_pre != "jacobi" and implicit != "fdm":
-            raise ValueError("ScalarStepper: a variable-step stepper takes inner_pre=\"jacobi\"")
         self.time_scheme = check_time_scheme(time_scheme, "ScalarStepper")
         cnab2 = time_scheme == "cnab2"
         if cnab2 and not ScalarFlux.available_ab2(eng, convection):
@@ -989,7 +1027,6 @@ class ScalarStepper:
             shared["q"] = eng.from_host(np.asarray(ops["q"], dtype=np.float64))
             shared["w_b"] = None if w_b is None else eng.from_host(np.asarray(w_b, dtype=np.float64))
             shared["w"] = None if flux is None else eng.from_host(np.asarray(flux[1], dtype=np.float64))
-        mstar_key = "mhalf" if cnab2 else "mstar"
         if implicit == "fdm":
             if shared.get("fdm_T") is None:
                 if extents is None or int(np.prod(extents, dtype=np.int64)) != self.n_p:
@@ -1001,19 +1038,11 @@ class ScalarStepper:
                 shared["fdm_T"] = made
             if shared["fdm_T"].handle is None:
                 raise ValueError("ScalarStepper: the ComponentFastDiagonalization holds no device handle")
-        elif implicit_conv:
-            pass                                    # (the loop reads K from [K | B])
-        elif variable:
-            if "K" not in shared:
-                shared["K"] = SparseMatrix.from_scipy(sp.csr_matrix(ops["K"]), engine=eng)
-            if "diagK" not in shared:
-                shared["diagK"] = eng.from_host(sp.csr_matrix(ops["K"]).diagonal())
-        elif mstar_key not in shared:               # M_p + timestep K, or the half-step operator M_p + timestep/2 K
-            theta = 0.5 * self.timestep if cnab2 else self.timestep
-            shared[mstar_key] = SparseMatrix.from_scipy((sp.diags(ops["mass"]) + theta * ops["K"]).tocsr(), engine=eng)
         self.KB, self.q, self.w_b, self.w = (shared[key] for key in ("KB", "q", "w_b", "w"))
-        self.fdm = shared["fdm_T"] if implicit == "fdm" else None
-        self.mstar = None if variable or implicit_conv or self.fdm is not None else shared[mstar_key]
+        self.solve_T = ImplicitSolve(eng, ImplicitSolve.kind_of(variable, implicit, convection_treatment),
+                                     "the scalar's solve", inner_pre, self.timestep, 0.5 if cnab2 else 1.0, ops["mass"],
+                                     ops["K"], shared, dict(assembled="mhalf" if cnab2 else "mstar", lap="K", diag="diagK"),
+                                     shared["fdm_T"] if implicit == "fdm" else None, self.KB, self.avg, self.diff)
         self.c0, self.records = (0.0 if flux is None else float(flux[0])), flux is not None
         self.tg = eng.zeros(self.n_p + self.n_u)             # the operand [T | G]
         self.T, self.G = eng.view(self.tg, 0, self.n_p), eng.view(self.tg, self.n_p, self.n_p + self.n_u)
@@ -1022,22 +1051,6 @@ class ScalarStepper:
             self.G_prev = eng.zeros(self.n_u)
             self.b_prev = None if w_b is None else eng.zeros(self.n_u)
         self.temp, self.delta = eng.zeros(self.n_p), eng.zeros(self.n_p)
-        self.bicg = None
-        if implicit_conv:                           # form (ii) over [K | B], the frozen u^n in `self.a`
-            self.pre = self.cg = None
-            self.a = eng.zeros(self.n_u)
-            form = fused.ConvectiveForm(self.KB, self.avg, self.diff, self.a,
-                                        fused.ConvectiveForm.mass_operand(eng, ops["mass"]))
-            self.dinv = None if self.fdm is not None else eng.zeros(self.n_p)
-            self.bicg = fused.BicgstabLoop(eng, self.KB, self.dinv, form, self.fdm)
-        elif self.fdm is not None:
-            self.pre = self.cg = None
-        elif variable:
-            self.pre = None
-            self.cg = CgLoop(eng, shared["K"], NO_PRE, shift=(ops["mass"], shared["diagK"]))
-        else:
-            self.pre = SmoothedAggregationAMG(self.mstar) if inner_pre == "amg" else JacobiPreconditioner(self.mstar)
-            self.cg = CgLoop(eng, self.mstar, pre_for("cg", self.pre))
         count = C.c_int64()
         eng._check(self.lib.nss_scalar_workspace(self.n_p, C.byref(count)))
         self.n_partials = count.value
@@ -1046,8 +1059,8 @@ class ScalarStepper:
     def flux(self, u):
         """S1 on (u, T): G, and for a buoyant scalar f_eff.  Returns the force buffer of the velocity step (None: f)."""
         self.scalar_flux.launch(u, self.f.buf, self.T, self.t_ref, self.G, self.w_b, self.f_eff)
-        if self.bicg is not None:
-            self.eng.copy(u, self.a)                # u^n, frozen for the scalar's solve behind the velocity step
+        if self.solve_T.a is not None:
+            self.eng.copy(u, self.solve_T.a)        # u^n, frozen for the scalar's solve behind the velocity step
         return self.f_eff
 
     def flux_ab2(self, u, weights):
@@ -1073,25 +1086,11 @@ class ScalarStepper:
         Returns the CG iterations."""
         eng, lib = self.eng, self.lib
         size = self.timestep if tau is None else tau
-        sigma = 0.5 * size if self.time_scheme == "cnab2" else size
-        if self.variable and self.cg is not None:
-            self.cg.set_shift(sigma)
         eng._check(lib.nss_step_rhs_f64(self.KB.handle.ptr, self.tg.data_ptr(), self.q.data_ptr(), self.temp.data_ptr(),
                                         None, eng.stream))
-        if self.bicg is not None:
-            self.bicg.set_sigma(sigma)
-            if self.dinv is not None:
-                self.bicg.write_jacobi(self.dinv)
-            its = self.bicg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
-            if self.bicg.code:
-                raise FloatingPointError("Advance: the scalar's solve of step %d broke down, code %d (%s)"
-                                         % (slot, self.bicg.code, self.bicg.CODES[self.bicg.code]))
-        elif self.fdm is not None:
-            its = self.fdm.solve_resident(self.temp, self.delta, sigma)
-        else:
-            its = self.cg.solve_resident(self.temp, self.delta, self.precision, self.maxsteps)
+        its = self.solve_T.solve(self.temp, self.delta, size, self.precision, self.maxsteps, slot)
         write = record is not None
-        eng._check(lib.nss_scalar_update_f64(self.n_p, self.timestep if tau is None else tau, self.delta.data_ptr(), self.T.data_ptr(),
+        eng._check(lib.nss_scalar_update_f64(self.n_p, size, self.delta.data_ptr(), self.T.data_ptr(),
                                              _ptr(self.w if write else None), _ptr(self.partials if write else None),
                                              self.partials.numel() if write else 0, None, eng.stream))
         if write:

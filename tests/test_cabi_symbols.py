@@ -132,9 +132,10 @@ def test_host_routine_tridiagonal_extremes_against_lapack(lib):
 
 def _struct_mirrors():
     """C name -> ctypes mirror of every state struct the host fills in and passes by pointer."""
-    from hipla import eigen, fused
+    from hipla import eigen, fused, hip_engine
     return {"nss_bpcg2_t": fused.Bpcg2State, "nss_minres_t": fused.MinresState, "nss_bpcg1_t": fused.Bpcg1State,
-            "nss_cg_t": fused.CgState, "nss_lanczos_t": eigen._LanczosState.get(), "nss_halo_t": fused.HaloStruct}
+            "nss_cg_t": fused.CgState, "nss_lanczos_t": eigen._LanczosState.get(), "nss_halo_t": fused.HaloStruct,
+            "nss_bicgstab_t": fused.BicgstabState, "nss_amg_level_t": hip_engine.AmgLevelStruct}
 
 
 def test_ctypes_state_mirrors_match_the_header(tmp_path):
@@ -168,6 +169,6 @@ def test_ctypes_state_mirrors_match_the_header(tmp_path):
             assert got[(cname, fname)] == (desc.offset, desc.size), (cname, fname)
             assert desc.size == ctypes.sizeof(ftype), (cname, fname)
     # the state structs end with the plan generation and the capacities of the partials (plan-sharing guard)
-    for cname in ("nss_bpcg2_t", "nss_minres_t", "nss_bpcg1_t", "nss_cg_t", "nss_lanczos_t"):
+    for cname in ("nss_bpcg2_t", "nss_minres_t", "nss_bpcg1_t", "nss_cg_t", "nss_lanczos_t", "nss_bicgstab_t"):
         names = [f for f, _ in mirrors[cname]._fields_]
         assert "plan_gen" in names and "cap_a" in names and "cap_b" in names, cname
