@@ -1146,6 +1146,11 @@ NSS_API int nss_lanczos_poll(const nss_lanczos_t* s, int32_t* stop, int32_t* j_s
  * consecutive dofs and a sum has <= 1024 partials -- a step is launch-bound there.  Process-wide override for tests
  * and A/B runs: -1 by size (default), 0 never, 1 whenever the operands allow. */
 NSS_API int nss_lanczos_fold_mode(int32_t mode);
+/* The form a step of this state takes under the override in force, as launches per step (no device work): 2 = the
+ * two-launch step with the sum of A's partials folded into it, 3 = the same with that sum in a launch of its own (A has
+ * more than 1024 row blocks), 5 = the five launches.  (The last step of a batch of the first two adds the launch that
+ * keeps its books.) */
+NSS_API int nss_lanczos_form(const nss_lanczos_t* s, int32_t* launches_per_step);
 /* HOST function (no device work): smallest and largest eigenvalue of the symmetric tridiagonal matrix with diagonal
  * diag[0..n) and off-diagonal off[0..n-1) -- the convergence check of the Ritz values every `check_every` steps
  * (Laguerre's iteration from outside the spectrum, verified by Sturm counts, bisection as the fallback; absolute

@@ -544,6 +544,13 @@ int nss_lanczos_fold_mode(int32_t mode) {
   });
 }
 
+int nss_lanczos_form(const nss_lanczos_t* s, int32_t* launches_per_step) {
+  return guarded([&] {
+    NSS_REQUIRE(s && s->A && launches_per_step, "lanczos_form: NULL argument");
+    *launches_per_step = !lz_fused(*s) ? 5 : lz_fold_a(*s) ? 2 : 3;
+  });
+}
+
 int nss_lanczos_poll(const nss_lanczos_t* s, int32_t* stop, int32_t* j_stop, int32_t* last_j, nss_stream_t stream) {
   return guarded([&] {
     NSS_REQUIRE(s && s->ctrl, "lanczos_poll: NULL state");

@@ -8,6 +8,7 @@ All n-sized work (operator applies, dots, updates) runs through the protocol on
 the engine; only the j x j tridiagonal eigenproblem is solved on the host."""
 
 from math import sqrt
+from typing import NamedTuple
 
 import numpy as np
 
@@ -61,6 +62,46 @@ def _mark(label):
         TRACE.append((label, time.perf_counter()))
 
 
+class LanczosWork(NamedTuple):
+    """An ``nss_lanczos_t`` and the buffers it points at (whoever holds this keeps them alive)."""
+    state: object
+    vecs: list           # v[0], v[1], v[2], z[0], z[1], p
+    partials: list       # partials_a, partials_b
+    scal: object
+    ctrl: object
+    hist: object
+
+
+def lanczos_state(mat, pa, start, maxsteps, sweep_A=None, vecs=None):
+    """The state of the device-resident recurrence (csrc/lanczos.hip) for the native matrix `mat` and the `PreParts`
+    `pa`, with `start` copied into v[0] and room for `maxsteps` steps in the history; nothing is launched besides that
+    copy.  `sweep_A`: see `_native_lanczos`.  `vecs`: six buffers of ``mat.height`` doubles to use for v[0..2], z[0..1]
+    and p instead of fresh ones (the single-step tests hand in views with guard entries around them)."""
+    from . import fused
+    eng = mat.engine
+    n = mat.height
+    st = _LanczosState.get()()
+    st.A = mat.handle.ptr
+    fused.write_pre(st, pa)
+    st.pre_scale = float(pa.scale)
+    st.sweep_A = sweep_A.handle.ptr if sweep_A is not None else None
+    if pa.multiplicative and fused.own_residual_matrix(pa.bjac) is not None:
+        st.sweep_A = fused.own_residual_matrix(pa.bjac).handle.ptr        # fp32 storage: the handle's own copy
+    if vecs is None:
+        vecs = [eng.zeros(n) for _ in range(6)]
+    eng.copy(start.buf, vecs[0])
+    for i in range(3):
+        st.v[i] = vecs[i].data_ptr()
+    st.z[0], st.z[1], st.p = vecs[3].data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr()
+    st.n = n
+    partials = fused.fit_partials(eng, st, eng.lib.nss_lanczos_workspace, ("A",))
+    scal = eng.zeros(8)
+    ctrl = eng.torch.zeros(4, dtype=eng.torch.int32, device=eng.device)
+    hist = eng.zeros(2 * maxsteps)
+    st.scal, st.ctrl, st.hist = scal.data_ptr(), ctrl.data_ptr(), hist.data_ptr()
+    return LanczosWork(st, list(vecs), partials, scal, ctrl, hist)
+
+
 def _native_lanczos(mat, pre, start, tol, maxsteps, check_every, sweep_A=None):
     """The same recurrence resident on the device (csrc/lanczos.hip: nss_lanczos_*): per step an SpMV with the dot in
     its epilogue, one element-wise kernel, the preconditioner (+ dot) and two single-workgroup sums that also advance
@@ -85,24 +126,8 @@ def _native_lanczos(mat, pre, start, tol, maxsteps, check_every, sweep_A=None):
         return None
     n = mat.height
     _mark("enter")
-    st = _LanczosState.get()()
-    st.A = mat.handle.ptr
-    fused.write_pre(st, pa)
-    st.pre_scale = float(pa.scale)
-    st.sweep_A = sweep_A.handle.ptr if sweep_A is not None else None
-    if pa.multiplicative and fused.own_residual_matrix(pa.bjac) is not None:
-        st.sweep_A = fused.own_residual_matrix(pa.bjac).handle.ptr        # fp32 storage: the handle's own copy
-    vecs = [eng.zeros(n) for _ in range(6)]
-    eng.copy(start.buf, vecs[0])
-    for i in range(3):
-        st.v[i] = vecs[i].data_ptr()
-    st.z[0], st.z[1], st.p = vecs[3].data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr()
-    st.n = n
-    partials = fused.fit_partials(eng, st, eng.lib.nss_lanczos_workspace, ("A",))    # noqa: F841 (keeps them alive)
-    scal = eng.zeros(8)
-    ctrl = eng.torch.zeros(4, dtype=eng.torch.int32, device=eng.device)
-    hist = eng.zeros(2 * maxsteps)
-    st.scal, st.ctrl, st.hist = scal.data_ptr(), ctrl.data_ptr(), hist.data_ptr()
+    work = lanczos_state(mat, pa, start, maxsteps, sweep_A)
+    st, ctrl, hist = work.state, work.ctrl, work.hist
     _mark("workspace")
     eng._check(eng.lib.nss_lanczos_start(C.byref(st), eng.stream))
     torch = eng.torch

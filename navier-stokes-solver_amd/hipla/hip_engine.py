@@ -204,6 +204,7 @@ def _signatures():
         "nss_minres_iterate_dist": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),
         "nss_minres_fold_mode": (C.c_int, [i32]),
         "nss_lanczos_fold_mode": (C.c_int, [i32]),
+        "nss_lanczos_form": (C.c_int, [vp, c_i32_p]),
         "nss_bpcg1_fold_mode": (C.c_int, [i32]),
         "nss_amg_batch_components": (C.c_int, [i32]),
         "nss_bpcg2_fuse_block_jacobi": (C.c_int, [i32]),
@@ -561,6 +562,12 @@ class HipEngine:
     def lanczos_start_values(self, buf, offset):
         """buf[i] = hipla.eigen.lanczos_start_values(offset, len(buf))[i], formed on the device (the same bits)"""
         self._check(self.lib.nss_lanczos_start_values(int(offset), buf.numel(), buf.data_ptr(), self.stream))
+
+    def lanczos_form(self, state):
+        """Launches per step of the ``nss_lanczos_t`` `state` under the override in force (nss_lanczos_form): 2, 3 or 5"""
+        out = C.c_int32()
+        self._check(self.lib.nss_lanczos_form(C.byref(state), C.byref(out)))
+        return out.value
 
     def to_host(self, buf):
         return buf.detach().cpu().numpy()
